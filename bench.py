@@ -14,11 +14,16 @@ other rank derives the LayerNorm-folded tail itself).
 
 Timing: W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize on
 both sides -> `value` (max over ranks, wall clock). The same region is also bracketed by HIP events on the
-launch stream, and `--repeats` (default 5) further K-step runs are timed the same way: `timing` carries every
-run and their median.
+launch stream; with `--full`, `--repeats` (default 5) K-step runs are timed the same way in all: `timing` carries
+every run and their median.
 
-Rank 0 prints ONE JSON line (< 8 KB, strict JSON, parsed back before it is printed: result_line); besides the
-contract fields it carries
+A plain run (no `--full`) does only what the headline figure needs: set-up, warm-up, the K timed steps, the
+outputs of the last timed step when `--dump-outputs DIR` is given (DIR/latents.npy and DIR/noise_pred.npy, rank 0's
+batch, float32), and the result line. `--full` adds everything below (box probe, repeats, the once-per-request side
+note, roofline, secondary shapes, CPU baseline, `bench_detail.json`); the `--no-*` options trim a `--full` run.
+
+Rank 0 prints ONE JSON line (< 8 KB, strict JSON, parsed back before it is printed: result_line); with `--full`,
+besides the contract fields it carries
   "roofline":     the layer role with the largest share of step time, timed live with HIP events on the launch
                   stream (ia2p_profile_*): algorithmic FLOPs (2*M*N*K) per launch / average launch duration;
                   plus `whole_step` and `conv_blocks` (MFMA and HBM fractions of the conv-block region on the
@@ -275,6 +280,24 @@ def write_detail(detail, path=None):
         log(f"[bench] could not write {path}: {e}")
     log("[bench detail] " + json.dumps(_finite(detail)))
     return path
+
+
+DUMP_LIMIT = 60 << 20       # bytes of all --dump-outputs files together (headers aside): under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: each tensor as DIR/<name>.npy in float32. A tensor over its share of DUMP_LIMIT is written as a fixed, seeded sample of its
+    flattened elements (the same indices on every run of the same shape), so that two builds compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"[bench] outputs of the last timed step -> {out_dir}: {', '.join(arrays)}")
 
 
 def pin_rank(local_rank, local_world):
@@ -694,7 +717,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="K-step runs timed in all (the first one is `value`); their median goes to `timing`")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure (box probe, repeats, roofline, "
+                                                         "secondary shapes, CPU baseline, bench_detail.json); a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the outputs of the last timed step (rank 0's latents and noise prediction) "
+                                                                       "as float32 .npy files into DIR")
+    ap.add_argument("--repeats", type=int, default=None, help="with --full: K-step runs timed in all (default 5; the first one is `value`); their median goes to `timing`")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--latent", type=int, default=64, help="latent side (64 = 512x512 pixels)")
     ap.add_argument("--ctx", type=int, default=81, help="context tokens (77 text + 4 image tokens)")
@@ -711,6 +738,12 @@ def main():
     ap.add_argument("--save-plans", default=None, help="write the kernel plan table in use to this file")
     ap.add_argument("--kernel-table", default=None, help="write the per-kernel timing table (JSON) to this file")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    elif args.repeats > 1 and not args.full:
+        ap.error("--repeats > 1 is a --full measurement")
+    if args.kernel_table and not args.full:
+        ap.error("--kernel-table comes from the roofline profile: pass --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # no launcher around us: be the launcher (before anything touches a GPU)
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -765,7 +798,7 @@ def main():
         f"{world} rank(s){', backend ' + backend if backend else ''})")
 
     probe = None
-    if rank == 0 and not args.no_box_probe:
+    if rank == 0 and args.full and not args.no_box_probe:
         probe = box_probe(dev)
         log(f"[box probe] 4096^3 GEMM {probe['gemm_4096_tflops']:.0f} TFLOP/s, 1 GiB copy {probe['copy_1gib_gbs']:.0f} GB/s, launch floor {probe['launch_floor_us']:.2f} us, "
             f"K->0 intercept {probe['k0_intercept_us_2048x3840']:.2f} us")
@@ -818,6 +851,8 @@ def main():
     if spread_warn and rank == 0:
         log("[bench] WARNING: " + spread_warn)
     assert torch.isfinite(wl.x).all(), "non-finite latents after the timed run"
+    if rank == 0 and args.dump_outputs:      # what the last timed step handed its caller, before anything else runs on these buffers
+        dump_outputs(args.dump_outputs, {"latents": wl.x, "noise_pred": wl.eps})
     runs = [ev_ms / args.steps]
     for _ in range(max(0, args.repeats - 1)):
         D.barrier()
@@ -837,7 +872,7 @@ def main():
                    "global_batch": B * world, "parallelism": f"dp{world}", "kernel_plans": plans,
                    "context_kv": "projected in every step (reference schedule, as rounds 1-4)",
                    "ranks": world, "dist_backend": backend or "none (single process)", "per_rank_ms_per_step": per_rank_ms, "per_rank_spread": spread,
-                   "weight_broadcast_s": bcast_s if world > 1 else None, "weight_broadcast_route": bcast_route, "detail_file": "bench_detail.json"},
+                   "weight_broadcast_s": bcast_s if world > 1 else None, "weight_broadcast_route": bcast_route, "detail_file": "bench_detail.json" if args.full else None},
         "timing": {"runs_ms_per_step": runs, "median_ms_per_step": statistics.median(runs)},
     }
     # what the line does not carry goes to stderr and to bench_detail.json beside this script
@@ -849,13 +884,13 @@ def main():
     if probe:
         detail["box_probe"] = probe
         res["config"]["box_probe"] = {k: probe[k] for k in ("gemm_4096_tflops", "copy_1gib_gbs", "launch_floor_us")}      # tells a fast box from a slow one
-    if rank == 0:      # side note, not `value`: the loop the product's pipelines run -- one whole 50-step request per timed run, its context projected once, inside
+    if rank == 0 and args.full:      # side note, not `value`: the loop the product's pipelines run -- one whole 50-step request per timed run, its context projected once, inside
         wl.context_kv = "per_request"
         wl.run(1)
         _, ms = wl.timed(50)
         res["config"]["ms_per_step_context_kv_once_per_request"] = ms / 50
         wl.context_kv = "per_step"
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         nprof = 3
         table, regions, roles = wl.profile(nprof)
         rb = roofline_block(table, regions, roles, nprof, B, hw, use_ip, statistics.median(runs), probe)
@@ -867,7 +902,7 @@ def main():
             json.dump({"steps_profiled": nprof, "kernels": table, "regions": regions, "roles": roles}, open(args.kernel_table, "w"), indent=1)
 
     # ---- the other single-GPU BASELINE shapes, same process, non-headline ----------------------------------------------------
-    if rank == 0 and world == 1 and default_cfg and not args.no_secondary:
+    if rank == 0 and world == 1 and default_cfg and args.full and not args.no_secondary:
         sec = {}
         for name, (b2, hw2, L2, g2, cid) in {"configs[1]: 512x512, batch 1, 77-token text-only context": (1, 64, 77, 0.0, 2),
                                               "configs[4]: 768x768, 4 requests with classifier-free guidance 10 (B_eff 8), 81-token contexts": (8, 96, 81, 10.0, 5),
@@ -905,7 +940,7 @@ def main():
         with open(args.save_plans, "w") as f:
             f.write(export_plans() + "\n")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         inputs_cpu = [t.cpu() for t in (wl.lat, wl.ctx, wl.added["text_embeds"], wl.added["time_ids"])]
         t_step, cores, what = cpu_baseline(cfg, unet_specs, ip_specs, seed, dev, inputs_cpu, L, B)
         detail["cpu_baseline_sample"] = what
@@ -914,8 +949,9 @@ def main():
                                          if "EXTRAPOLATED" not in what else f"oracle (torch fp32, {cores} threads): steps of 1 and 2 requests, batch-{B} step EXTRAPOLATED ({t_step:.1f} s)"}
 
     if rank == 0:
-        detail["line"] = res
-        write_detail(detail, args.detail)
+        if args.full:
+            detail["line"] = res
+            write_detail(detail, args.detail)
         print(result_line(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

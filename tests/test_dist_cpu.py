@@ -110,6 +110,33 @@ def _bench_module():
     return b
 
 
+def test_bench_dump_outputs_float32_and_bounded(tmp_path):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float32; one over its share of the size limit becomes a fixed, seeded sample (the same indices
+    on every run), so the files of two runs compare element for element."""
+    import numpy as np
+    b = _bench_module()
+    small = torch.randn(2, 4, 8, 8).half()
+    big = torch.arange(b.DUMP_LIMIT // 4, dtype=torch.float32)            # twice its share of the limit
+    for d in (tmp_path / "a", tmp_path / "b"):
+        b.dump_outputs(str(d), {"latents": small, "noise_pred": big})
+    lat = np.load(tmp_path / "a" / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (2, 4, 8, 8) and np.array_equal(lat, small.float().numpy())
+    s1, s2 = np.load(tmp_path / "a" / "noise_pred.npy"), np.load(tmp_path / "b" / "noise_pred.npy")
+    assert s1.dtype == np.float32 and s1.size == b.DUMP_LIMIT // 8 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0)                                       # distinct elements, in order
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) < 64e6
+
+
+def test_bench_extras_need_full():
+    """A plain run times the K steps and nothing else: repeats and the per-kernel table are --full measurements and are refused without it."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for extra in (["--repeats", "3"], ["--kernel-table", "kt.json"]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", *extra], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-2000:]
+
+
 def test_result_line_is_bounded_strict_json():
     """bench.result_line: the ONE stdout line stays under 8 KB whatever a run produced (round 5's line was 31.5 KB and the driver's record could not parse it),
     carries `roofline` and `cpu_baseline`, holds no NaN / Infinity tokens, and optional blocks are shed in a fixed order before the contract fields would be."""

@@ -42,7 +42,7 @@ def test_bench_gpus2_real_step_two_ranks_on_one_gpu():
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", IA2P_DIST_BACKEND="gloo", IA2P_FORCE_DEVICE="0")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--repeats", "1", "--no-cpu-baseline",
                         "--no-secondary", "--no-roofline", "--no-box-probe"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -5,6 +5,6 @@
 #   then:  gpurun -- 'bash tools/ab_old.sh'
 cd $GRAFT_REPO_ROOT
 for i in 1 2 3; do
-(cd tools/old_tree && python3 bench.py --steps 30 --warmup 3 --repeats 3 --no-cpu-baseline --no-secondary --no-roofline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('OLD', d['timing']['runs_ms_per_step'])")
-python3 bench.py --steps 30 --warmup 3 --repeats 3 --no-cpu-baseline --no-secondary --no-roofline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('NEW', d['timing']['runs_ms_per_step'])"
+(cd tools/old_tree && python3 bench.py $(grep -qs -- '"--full"' bench.py && echo --full) --steps 30 --warmup 3 --repeats 3 --no-cpu-baseline --no-secondary --no-roofline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('OLD', d['timing']['runs_ms_per_step'])")
+python3 bench.py --full --steps 30 --warmup 3 --repeats 3 --no-cpu-baseline --no-secondary --no-roofline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('NEW', d['timing']['runs_ms_per_step'])"
 done

@@ -16,7 +16,7 @@ for sh in "${SH[@]}"; do
     for t in $TREES; do
       label=${t%%=*}; dir=${t#*=}; extra=""
       if [[ "$dir" == *:* ]]; then extra=${dir#*:}; dir=${dir%%:*}; fi      # "label=dir:--flag": a flag only this tree's bench.py knows (e.g. r06tune=.:--tune)
-      (cd $dir && python3 bench.py --steps 30 --warmup 3 --repeats 3 --no-cpu-baseline --no-secondary --no-roofline $flags $extra 2>/dev/null | python3 -c "
+      (cd $dir && python3 bench.py $(grep -qs -- '"--full"' bench.py && echo --full) --steps 30 --warmup 3 --repeats 3 --no-cpu-baseline --no-secondary --no-roofline $flags $extra 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); c = d['config']; runs = d['timing']['runs_ms_per_step']
 # which schedule the tree's headline loop runs, and where it reports the other one (rounds 1-4: every step + _hoisted; round 5: once per request + _every_step; round 6: every step + _once_per_request)
