@@ -302,6 +302,23 @@ size_t ia2p_vae_workspace_bytes(ia2p_vae* vae, int B, int h, int w, int decode);
 ia2p_status ia2p_vae_decode(ia2p_vae* vae, void* stream, const void* latents, void* image, int B, int h, int w, void* workspace, size_t workspace_bytes);
 ia2p_status ia2p_vae_encode(ia2p_vae* vae, void* stream, const void* image, void* moments, int B, int h, int w, void* workspace, size_t workspace_bytes);
 
+/* ---- image codec: 8-bit images <-> the VAE's fp16 tensors ---------------------------------------------------------------------------------
+ * The reference takes a base image FILE (pipeline.py:289-293 `loas_base_img`: open, `resize_and_crop`, resize to 1024^2; :328), runs it through
+ * `image_processor.preprocess` before the VAE encode (ddim/pnp_pipeline.py:190-204) and returns PIL images (pipeline.py:356-386, after
+ * `image_processor.postprocess` in ddim/sdxl_pipeline.py:859-880). Resizing stays on the host (PIL); these kernels do the per-pixel work, bit for
+ * bit with diffusers 0.26.3 VaeImageProcessor: src / dst are device pointers; u8 images are [B,H,W,C] (HWC, as PIL / numpy hold them); fp16
+ * tensors are NCHW; C is 1 or 3; B*H*W*C < 2^31. Arguments are checked before any HIP call (IA2P_ERR_INVALID / IA2P_ERR_SHAPE). */
+/* u8 -> fp16 [B,C,H,W]: normalize = 1: 2 (q / 255) - 1 (pil_to_numpy -> numpy_to_pt -> normalize -> .to(float16): fp32 math, one rounding to fp16);
+ * normalize = 0: q / 255 (masks) */
+ia2p_status ia2p_image_from_u8(void* stream, const void* src, void* dst, int B, int H, int W, int C, int normalize);
+/* fp16 [B,C,H,W] in [-1, 1] -> u8 [B,H,W,C]: rint_half_even(clamp(x / 2 + 0.5, 0, 1) * 255) in fp32 (postprocess + numpy_to_pil); NaN -> 0 */
+ia2p_status ia2p_image_to_u8(void* stream, const void* src, void* dst, int B, int H, int W, int C);
+/* fp16 [B,C,H,W] -> fp32 clamp(x / 2 + 0.5, 0, 1) (denormalize) as [B,H,W,C] (nhwc = 1: output_type "np") or [B,C,H,W] (nhwc = 0: "pt") */
+ia2p_status ia2p_image_to_f32(void* stream, const void* src, float* dst, int B, int H, int W, int C, int nhwc);
+/* fp16 [n] -> fp16 [n]: the 8-bit round trip of the refiner hand-over (pipeline.py:358-361: postprocess to PIL, then preprocess) in one launch,
+ * = ia2p_image_from_u8(ia2p_image_to_u8(x), normalize = 1) element-wise. dst may equal src. */
+ia2p_status ia2p_image_requantize(void* stream, const void* src, void* dst, int64_t n);
+
 /* ---- CLIP text encoders (conditioning side): the two encoders behind `encode_prompt` ------------------
  * (reference ddim/sdxl_pipeline.py:202-395: `text_encoder(ids, output_hidden_states=True)`, `.hidden_states[-2]` of both encoders
  * concatenated, pooled `[0]` of the second). transformers `CLIPTextModel` / `CLIPTextModelWithProjection` semantics: token + position

@@ -133,6 +133,10 @@ SIGNATURES = {
     "ia2p_vae_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
     "ia2p_vae_decode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _SZ]),
     "ia2p_vae_encode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _SZ]),
+    "ia2p_image_from_u8": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
+    "ia2p_image_to_u8": (_I, [_P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_image_to_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
+    "ia2p_image_requantize": (_I, [_P, _P, _P, _I64]),
     "ia2p_profile_enable": (_I, [_P, _I]),
     "ia2p_profile_classes": (_I, []),
     "ia2p_profile_read_region": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -20,6 +20,8 @@ import torch
 
 from .scheduler import DDIMScheduler, fused_update
 
+OUTPUT_TYPES = ("latent", "pt", "np", "pil")            # (image_processor.OUTPUT_TYPES; repeated so that importing this module loads no PIL)
+
 
 class StableDiffusionXLPipelineOutput(SimpleNamespace):
     """`.images` like diffusers' output class (reference pnp_pipeline.py:278)."""
@@ -40,14 +42,29 @@ def get_add_time_ids(unet, original_size, crops_coords_top_left, target_size, pr
 
 class _PipelineBase:
     vae_scale_factor = 8
+    vae = None
+    image_processor = None          # VaeImageProcessor when a VAE is attached (vae=): images in and out as in diffusers
+    mask_processor = None
 
     def __init__(self, unet, scheduler: Optional[DDIMScheduler] = None, encode_prompt: Optional[Callable] = None,
-                 vae_encode: Optional[Callable] = None, vae_decode: Optional[Callable] = None):
+                 vae_encode: Optional[Callable] = None, vae_decode: Optional[Callable] = None, vae=None):
         self.unet = unet
         self.scheduler = scheduler or DDIMScheduler()
         self._encode_prompt = encode_prompt
         self._vae_encode = vae_encode
         self._vae_decode = vae_decode
+        if vae is not None:
+            # a HipAutoencoderKL: its encode / decode become the hooks, and `image=` / `output_type` mean what they mean in diffusers
+            if vae_encode is not None or vae_decode is not None:
+                raise ValueError("pass either vae= or the vae_encode= / vae_decode= hooks, not both")
+            from .image_processor import VaeImageProcessor
+            self.vae = vae
+            self.vae_scale_factor = 2 ** (len(vae.config.block_out_channels) - 1)
+            self.image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor, device=vae.device)
+            self.mask_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor, do_normalize=False, do_binarize=True,
+                                                    do_convert_grayscale=True, device=vae.device)
+            self._vae_encode = vae.encode_to_latents
+            self._vae_decode = vae.decode_from_latents
 
     @property
     def device(self):
@@ -62,6 +79,29 @@ class _PipelineBase:
                                       "or construct the pipeline with encode_prompt=<callable>")
         return self._encode_prompt(prompt=prompt, num_images_per_prompt=num_images_per_prompt,
                                    do_classifier_free_guidance=do_classifier_free_guidance, negative_prompt=negative_prompt, **kw)
+
+    def _check_output_type(self, output_type):
+        if self.vae is not None and output_type not in OUTPUT_TYPES:
+            raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
+
+    def _image_latents(self, image, height=None, width=None):
+        """`image=` -> scaled latents: with a VAE attached, `image_processor.preprocess` (PIL, uint8 arrays, [0, 1] floats, [-1, 1] tensors;
+        4-channel tensors are latents already) then the posterior sample; with hooks only, the hook gets `image` as it is."""
+        if self._vae_encode is None:
+            raise NotImplementedError("VAE encode is not attached: pass latents=, or construct with vae= or vae_encode=<callable>")
+        if self.vae is None:
+            return self._vae_encode(image)
+        image = self.image_processor.preprocess(image, height=height, width=width)
+        return image if image.shape[1] == 4 else self._vae_encode(image)
+
+    def _output(self, latents, output_type):
+        """final latents -> what `output_type` asks for; with hooks only every type but "latent" returns the decode hook's raw tensor"""
+        if output_type == "latent":
+            return latents
+        if self._vae_decode is None:
+            raise NotImplementedError("VAE decode is not attached: use output_type='latent' or pass vae= or vae_decode=")
+        image = self._vae_decode(latents)
+        return image if self.vae is None else self.image_processor.postprocess(image, output_type=output_type)
 
     def _check_embeds(self, prompt, prompt_embeds, pooled):
         # same conditions as check_inputs (reference sdxl_pipeline.py:429-486) for the arguments that remain
@@ -89,16 +129,17 @@ class SDXLDDIMPipeline(_PipelineBase):
         if num_inference_steps is None or not isinstance(num_inference_steps, int) or num_inference_steps <= 0:
             raise ValueError(f"`num_inference_steps` has to be a positive integer but is {num_inference_steps}")
         self._check_embeds(prompt, prompt_embeds, pooled_prompt_embeds)
+        self._check_output_type(output_type)
         if prompt_embeds is None:
             prompt_embeds, _, pooled_prompt_embeds, _ = self.encode_prompt(
                 prompt=prompt, num_images_per_prompt=num_images_per_prompt, do_classifier_free_guidance=False, negative_prompt=negative_prompt)
         dev = self.device
         if latents is None:                                                                     # :190-204 (VAE: "next" row)
             if image is None:
-                raise ValueError("inverse() needs `image` (with a vae_encode callable) or `latents`")
+                raise ValueError("inverse() needs `image` (with vae= or a vae_encode callable) or `latents`")
             if self._vae_encode is None:
-                raise NotImplementedError("VAE encode is outside the denoise hot path: pass latents=, or construct with vae_encode=<callable>")
-            latents = self._vae_encode(image)
+                raise NotImplementedError("VAE encode is outside the denoise hot path: pass latents=, or construct with vae= or vae_encode=<callable>")
+            latents = self._image_latents(image)
         latents = latents.to(device=dev, dtype=torch.float16).contiguous().clone()    # the loop ping-pongs buffers: never the caller's tensor
         batch = latents.shape[0]
         self.scheduler.set_timesteps(num_inference_steps, device=dev)                           # :192
@@ -147,6 +188,7 @@ class StableDiffusionXLPipeline(_PipelineBase):
         if guidance_rescale != 0.0 or eta != 0.0:
             raise NotImplementedError("guidance_rescale / eta are inactive on the reference's path (sdxl_pipeline.py:846, eta=0)")
         self._check_embeds(prompt, prompt_embeds, pooled_prompt_embeds)
+        self._check_output_type(output_type)
         do_cfg = guidance_scale > 1.0                                                           # sdxl_pipeline.py:735
         if prompt_embeds is None:
             prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = self.encode_prompt(
@@ -207,10 +249,5 @@ class StableDiffusionXLPipeline(_PipelineBase):
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, model_in[:B])
         latents = model_in[:B]
-        if output_type == "latent":
-            image = latents
-        else:                                                                                   # :859-871 (VAE: "next" row)
-            if self._vae_decode is None:
-                raise NotImplementedError("VAE decode is outside the denoise hot path: use output_type='latent' or pass vae_decode=")
-            image = self._vae_decode(latents)
+        image = self._output(latents, output_type)                                              # :859-880
         return StableDiffusionXLPipelineOutput(images=image) if return_dict else (image,)

@@ -50,8 +50,8 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
     """The refiner pipeline object (`InstructAny2PixPipeline.piperf`)."""
 
     def __init__(self, unet, scheduler: Optional[EulerDiscreteScheduler] = None, encode_prompt=None, vae_encode=None, vae_decode=None,
-                 requires_aesthetics_score: bool = True):
-        super().__init__(unet, scheduler or EulerDiscreteScheduler(), encode_prompt, vae_encode, vae_decode)
+                 requires_aesthetics_score: bool = True, vae=None):
+        super().__init__(unet, scheduler or EulerDiscreteScheduler(), encode_prompt, vae_encode, vae_decode, vae=vae)
         self.config = type("Config", (), {"requires_aesthetics_score": requires_aesthetics_score})()
 
     def get_timesteps(self, num_inference_steps: int, strength: float):
@@ -74,6 +74,7 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
         if num_inference_steps is None or not isinstance(num_inference_steps, int) or num_inference_steps <= 0:
             raise ValueError(f"`num_inference_steps` has to be a positive integer but is {num_inference_steps} of type {type(num_inference_steps)}.")
         self._check_embeds(prompt, prompt_embeds, pooled_prompt_embeds)
+        self._check_output_type(output_type)
         do_cfg = guidance_scale > 1.0
         if prompt_embeds is None:
             prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = self.encode_prompt(
@@ -90,10 +91,8 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
         # prepare_latents: encode, scale, add noise at the first kept timestep
         if latents is None:
             if image is None:
-                raise ValueError("img2img needs `image` (with a vae_encode callable) or `latents`")
-            if self._vae_encode is None:
-                raise NotImplementedError("VAE encode is not attached: pass latents=, or construct with vae_encode=<callable>")
-            latents = self._vae_encode(image)
+                raise ValueError("img2img needs `image` (with vae= or a vae_encode callable) or `latents`")
+            latents = self._image_latents(image)
         latents = latents.to(device=dev, dtype=torch.float16).contiguous()
         batch = latents.shape[0]
         if noise is None:
@@ -145,10 +144,5 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
             x, nxt = nxt, x
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, x)
-        if output_type == "latent":
-            image_out = x
-        else:
-            if self._vae_decode is None:
-                raise NotImplementedError("VAE decode is not attached: use output_type='latent' or pass vae_decode=")
-            image_out = self._vae_decode(x)
+        image_out = self._output(x, output_type)
         return StableDiffusionXLPipelineOutput(images=image_out) if return_dict else (image_out,)

@@ -41,6 +41,12 @@ def prepare_mask(mask_image, h: int, w: int, device) -> torch.Tensor:
     return m.to(device=device, dtype=torch.float16).contiguous()
 
 
+def _is_pil(x) -> bool:
+    if isinstance(x, list):
+        return len(x) > 0 and all(_is_pil(i) for i in x)
+    return type(x).__module__.startswith("PIL.")
+
+
 class StableDiffusionXLInpaintPipeline(_PipelineBase):
     def get_timesteps(self, num_inference_steps: int, strength: float):
         init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
@@ -63,6 +69,7 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
         if mask_image is None:
             raise ValueError("`mask_image` input cannot be undefined.")
         self._check_embeds(prompt, prompt_embeds, pooled_prompt_embeds)
+        self._check_output_type(output_type)
         do_cfg = guidance_scale > 1.0
         if prompt_embeds is None:
             prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = self.encode_prompt(
@@ -77,12 +84,12 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
                              f"{n_steps} which is < 1 and not appropriate for this pipeline.")
         if latents is None:
             if image is None:
-                raise ValueError("inpainting needs `image` (with a vae_encode callable) or `latents`")
-            if self._vae_encode is None:
-                raise NotImplementedError("VAE encode is not attached: pass latents=, or construct with vae_encode=<callable>")
-            latents = self._vae_encode(image)
+                raise ValueError("inpainting needs `image` (with vae= or a vae_encode callable) or `latents`")
+            latents = self._image_latents(image, height, width)
         image_latents = latents.to(device=dev, dtype=torch.float16).contiguous()
         B, _, h, w = image_latents.shape
+        if self.vae is not None and _is_pil(mask_image):                   # PIL mask: mask_processor (resize, grayscale, binarise at 0.5)
+            mask_image = self.mask_processor.preprocess(mask_image, height=h * self.vae_scale_factor, width=w * self.vae_scale_factor)
         mask = prepare_mask(mask_image, h, w, dev)
         if mask.shape[0] != B:
             mask = mask.expand(B, -1, -1, -1).contiguous()
@@ -132,12 +139,7 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, model_in[:B])
         out = model_in[:B].clone()
-        if output_type == "latent":
-            image_out = out
-        else:
-            if self._vae_decode is None:
-                raise NotImplementedError("VAE decode is not attached: use output_type='latent' or pass vae_decode=")
-            image_out = self._vae_decode(out)
+        image_out = self._output(out, output_type)
         return StableDiffusionXLPipelineOutput(images=image_out) if return_dict else (image_out,)
 
 

@@ -21,12 +21,14 @@ from __future__ import annotations
 
 from typing import Any, Callable, Optional
 
+import PIL.Image
 import torch
 
 from .config import UNetConfig, sdxl_base
 from .ddim import SDXLDDIMPipeline, StableDiffusionXLPipeline
 from .img2img import StableDiffusionXLImg2ImgPipeline
 from .inpaint import StableDiffusionXLInpaintPipeline, subject_consistency
+from .image_processor import OUTPUT_TYPES, requantize
 from .ip_adapter import IPAdapterXL
 from .prior import MODALITY
 from .scheduler import DDIMScheduler
@@ -52,6 +54,34 @@ def to_8bit_image(image):
     return (q / 255.0 * 2.0 - 1.0).to(image.dtype)
 
 
+def resize_and_crop(img, size, crop_type="middle"):
+    """Scale a PIL image so that it covers `size` = (width, height) and cut the excess along the longer relative side (reference
+    pipeline.py:39-83). The scaled side is truncated to an int; crop_type "top" keeps the top / left part, "middle" the centre (the box is
+    in floats and may have .5 edges, which PIL's `crop` rounds), "bottom" the bottom / right part. Same PIL calls as the reference: `resize`
+    with its default resampling, `crop` with the float box. An unknown crop_type raises ValueError (the reference only notices it when
+    the aspect ratios differ)."""
+    if crop_type not in ("top", "middle", "bottom"):
+        raise ValueError(f"invalid crop_type {crop_type!r}: 'top', 'middle' or 'bottom'")
+    img_ratio = img.size[0] / float(img.size[1])
+    ratio = size[0] / float(size[1])
+    if ratio > img_ratio:                           # relatively taller than the target: fit the width, crop rows
+        img = img.resize((size[0], int(size[0] * img.size[1] / img.size[0])))
+        lo = {"top": 0, "middle": (img.size[1] - size[1]) / 2, "bottom": img.size[1] - size[1]}[crop_type]
+        return img.crop((0, lo, img.size[0], lo + size[1]))
+    if ratio < img_ratio:                           # relatively wider: fit the height, crop columns
+        img = img.resize((int(size[1] * img.size[0] / img.size[1]), size[1]))
+        lo = {"top": 0, "middle": (img.size[0] - size[0]) / 2, "bottom": img.size[0] - size[0]}[crop_type]
+        return img.crop((lo, 0, lo + size[0], img.size[1]))
+    return img.resize((int(size[0]), int(size[1])))
+
+
+def loas_base_img(base_img_path, size: int = 1024):
+    """reference pipeline.py:289-293 (name kept, typo included): open the file, `resize_and_crop` to size x size (middle), resize to size x size."""
+    img = PIL.Image.open(base_img_path)
+    img = resize_and_crop(img, (size, size), crop_type="middle")
+    return img.resize((size, size))
+
+
 def _need(c, keys, stage):
     missing = [k for k in keys if k not in c]
     if missing:
@@ -71,7 +101,8 @@ class InstructAny2PixPipeline:
                  conditioner: Optional[Callable] = None, text_encoder: Optional[Callable] = None,
                  vae_encode: Optional[Callable] = None, vae_decode: Optional[Callable] = None, clip_embeddings_dim: int = 1024,
                  refiner_unet: Optional[HipUNet2DConditionModel] = None, refiner_text_encoder: Optional[Callable] = None, prior=None,
-                 refiner_handoff: str = "image"):
+                 refiner_handoff: str = "image", vae=None):
+        # vae: a HipAutoencoderKL shared by every pipeline (in place of the vae_encode / vae_decode hooks): base images in, images out
         # how the base result reaches the refiner: "image" = the reference's route (decode, 8-bit image, VAE re-encode with a posterior
         # sample; needs vae_encode and vae_decode), "latent" = the sampled latents go in directly (no VAE round trip; the only route
         # when no VAE is attached)
@@ -89,14 +120,15 @@ class InstructAny2PixPipeline:
         self.unet = unet
         new_sch = DDIMScheduler()
         # one shared UNet object for sampling and inversion (reference :106-116)
-        self.pipe = StableDiffusionXLPipeline(unet, DDIMScheduler(), encode_prompt=text_encoder, vae_decode=vae_decode)
-        self.pipe_inversion = SDXLDDIMPipeline(unet, new_sch, encode_prompt=text_encoder, vae_encode=vae_encode)
+        self.vae = vae
+        self.pipe = StableDiffusionXLPipeline(unet, DDIMScheduler(), encode_prompt=text_encoder, vae_decode=vae_decode, vae=vae)
+        self.pipe_inversion = SDXLDDIMPipeline(unet, new_sch, encode_prompt=text_encoder, vae_encode=vae_encode, vae=vae)
         # the refiner pipeline object (:128-131): second UNet config of the same engine, Euler img2img loop (img2img.py)
         self.piperf = StableDiffusionXLImg2ImgPipeline(refiner_unet, encode_prompt=refiner_text_encoder, vae_encode=vae_encode,
-                                                       vae_decode=vae_decode) if refiner_unet is not None else None
+                                                       vae_decode=vae_decode, vae=vae) if refiner_unet is not None else None
         # inpainting pipeline assembled from the base pipeline's own modules: same UNet object, same scheduler object (:132-139)
         self.pipe_inpainting = StableDiffusionXLInpaintPipeline(unet, self.pipe.scheduler, encode_prompt=text_encoder, vae_encode=vae_encode,
-                                                                vae_decode=vae_decode)
+                                                                vae_decode=vae_decode, vae=vae)
         self.conditioner = conditioner           # stands in for forward_llm + prior (:309-317)
         self.cache = None
         self.mode = "ipa_v2"
@@ -136,9 +168,35 @@ class InstructAny2PixPipeline:
         self.pipe_inversion.unet = self.pipe.unet
         return denoise_batch(self, requests, group=group, shard=shard)
 
+    # ---- base image -> latents (reference :289-293, :328-330) -------------------------------------------------------------
+    base_image_size = 1024          # the square `loas_base_img` loads a base_img_path to
+
+    def loas_base_img(self, base_img_path):
+        return loas_base_img(base_img_path, self.base_image_size)
+
+    def _base_latents(self, c):
+        """the conditioner's `base_latents`, else its `base_image` (PIL) or `base_img_path` (loaded by `loas_base_img`) through the inversion
+        pipeline's image processor and the VAE (a posterior sample, as in the reference's `inverse(image=...)`)"""
+        if c.get("base_latents") is not None:
+            return c["base_latents"]
+        img = c.get("base_image")
+        if img is None and c.get("base_img_path") is not None:
+            img = self.loas_base_img(c["base_img_path"])
+        if img is None:
+            raise KeyError("the conditioner returned none of base_latents / base_image / base_img_path")
+        if self.vae is None:
+            raise ValueError("a base_image / base_img_path needs the pipeline built with vae=<HipAutoencoderKL>")
+        return self.pipe_inversion._image_latents(img)
+
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
-                 use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0) -> Any:
+                 use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent") -> Any:
+        """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
+        `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images)."""
+        if output_type not in OUTPUT_TYPES:
+            raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
+        if output_type != "latent" and self.vae is None:
+            raise ValueError(f"output_type={output_type!r} needs the pipeline built with vae=<HipAutoencoderKL>")
         if self.conditioner is None:
             raise NotImplementedError("the LLM / ImageBind / prior stages are outside the denoise hot path (SURVEY.md §8): construct with "
                                       "conditioner=<callable returning dict(image_embeds, base_embed, y, caption, base_latents, "
@@ -158,13 +216,14 @@ class InstructAny2PixPipeline:
                                               force_guidence_t0=True, do_classifier_free_guidance=True, score=6.5)
             y0 = y[0].to(device=c["base_embed"].device, dtype=c["base_embed"].dtype)
         latent_la = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], y0, h, norm)
-        images, latent_inv = self.denoise(c["base_latents"], latent_la.reshape(1, -1)[0], prompt_embeds=c["prompt_embeds"],
+        images, latent_inv = self.denoise(self._base_latents(c), latent_la.reshape(1, -1)[0], prompt_embeds=c["prompt_embeds"],
                                           pooled_prompt_embeds=c["pooled_prompt_embeds"], negative_prompt_embeds=c["negative_prompt_embeds"],
                                           negative_pooled_prompt_embeds=c["negative_pooled_prompt_embeds"],
                                           inv_prompt_embeds=c.get("inv_prompt_embeds"), inv_pooled_prompt_embeds=c.get("inv_pooled_prompt_embeds"),
                                           alpha=alpha, num_inference_steps=num_inference_steps, cfg=cfg, scale=scale)
         non_refined = images
         oo = images
+        decoded = None          # the decode of `images`, when the refiner hand-over made it
         if refinement > 0 and self.piperf is not None:                                         # :358-361
             _need(c, ("refiner_prompt_embeds", "refiner_pooled_prompt_embeds", "refiner_negative_prompt_embeds", "refiner_negative_pooled_prompt_embeds"),
                   "refiner pass")
@@ -183,7 +242,11 @@ class InstructAny2PixPipeline:
             if vae_route:
                 # the reference hands a decoded 8-bit image over and the refiner pipeline re-encodes it with the shared VAE
                 # (`retrieve_latents(vae.encode(image)) * scaling_factor`: a posterior SAMPLE, global RNG)
-                oo = self.piperf(image=to_8bit_image(self.pipe._vae_decode(images)), **kw).images
+                decoded = self.pipe._vae_decode(images)
+                if self.vae is not None:    # the same steps with the 8-bit round trip in one HIP launch (bit-identical to to_8bit_image)
+                    oo = self.piperf(latents=self.piperf._vae_encode(requantize(decoded)), **kw).images
+                else:
+                    oo = self.piperf(image=to_8bit_image(decoded), **kw).images
             else:
                 oo = self.piperf(latents=images, **kw).images
         subject_data = c.get("subject_data") or []
@@ -195,4 +258,9 @@ class InstructAny2PixPipeline:
                                      negative_prompt_embeds=c["subject_negative_prompt_embeds"],
                                      negative_pooled_prompt_embeds=c["subject_negative_pooled_prompt_embeds"], noise=c.get("subject_noise"))
         msg = "SUCCESS!" if not debug else dict(output_caption=c["caption"], latent_inv=latent_inv, latent_la=latent_la)
+        if output_type != "latent":
+            post = self.pipe.image_processor.postprocess
+            refined_is_base = oo is non_refined
+            non_refined = post(decoded if decoded is not None else self.pipe._vae_decode(non_refined), output_type=output_type)
+            oo = non_refined if refined_is_base else post(self.pipe._vae_decode(oo), output_type=output_type)
         return non_refined, oo, msg

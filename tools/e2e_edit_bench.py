@@ -1,12 +1,15 @@
 """End-to-end latency of ONE edit request at the reference's own defaults, every model at full size with seeded synthetic weights:
-1024x1024 image, num_inference_steps=25, cfg=10, refinement=0.5 (reference pipeline.py:303-386). Everything downstream of the LLM / ImageBind
-stage runs on the HIP path: VAE encode -> embedding prior (CLIP ViT-H text + GPT-2 medium) -> encode_prompt (CLIP-L + bigG) -> 25-step DDIM
-inversion (B=1) -> polar mixing -> 25-step IP-Adapter guided CFG sampling (B_eff=2) -> SDXL-refiner img2img (strength 0.5 of 50 steps, CFG)
--> VAE decode. The LLM / ImageBind outputs (1024-d embeddings, caption) are stand-ins: that stage is out of scope.
+1024x1024 image, num_inference_steps=25, cfg=10, refinement=0.5 (reference pipeline.py:303-386). A seeded synthetic PIL image goes in and PIL
+images come out (`output_type="pil"`); everything downstream of the LLM / ImageBind stage runs on the HIP path: image in (8-bit codec) -> VAE
+encode -> embedding prior (CLIP ViT-H text + GPT-2 medium) -> encode_prompt (CLIP-L + bigG) -> 25-step DDIM inversion (B=1) -> polar mixing
+-> 25-step IP-Adapter guided CFG sampling (B_eff=2) -> VAE decode + 8-bit hand-over -> SDXL-refiner img2img (strength 0.5 of 50 steps, CFG)
+-> VAE decode -> image out (8-bit codec, uint8 back to the host). The LLM / ImageBind outputs (1024-d embeddings, caption) are stand-ins: that stage is out of scope.
 Prints per-stage wall times (stream-synchronised) after one warm-up request."""
 import os
 import sys
 import time
+import numpy as np
+import PIL.Image
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -50,23 +53,22 @@ def timed(name, fn):
 
 
 g = torch.Generator().manual_seed(1)
-image = (torch.rand(1, 3, PX, PX, generator=g) * 2 - 1).half().to(DEV)
+image = PIL.Image.fromarray(np.random.default_rng(1).integers(0, 256, size=(PX, PX, 3), dtype=np.uint8))      # the base image (reference: loas_base_img)
 image_embeds, base_embed = torch.randn(1, 1024, generator=g), torch.randn(1, 1024, generator=g)      # stand-ins for the LLM / ImageBind stage
 caption = "a watercolor painting of a fox in the snow"
 
 
 def conditioner(inst, mm, use_cache=False):
-    lat = timed("vae_encode", lambda: vae.encode_to_latents(image, torch.Generator().manual_seed(2)))
     pe, ne, pp, npl = timed("encode_prompt(base)", lambda: enc.encode_prompt(prompt=caption, negative_prompt="", do_classifier_free_guidance=True))
     ipe, _, ipp, _ = timed("encode_prompt(inversion '')", lambda: enc.encode_prompt(prompt="", do_classifier_free_guidance=False))
     rpe, rne, rpp, rnp = timed("encode_prompt(refiner)", lambda: enc_ref.encode_prompt(prompt=caption + ",high quality,well-formed,award-winning", negative_prompt="", do_classifier_free_guidance=True))
-    return dict(image_embeds=image_embeds, base_embed=base_embed, caption=caption, base_latents=lat, prompt_embeds=pe, pooled_prompt_embeds=pp,
+    return dict(image_embeds=image_embeds, base_embed=base_embed, caption=caption, base_image=image, prompt_embeds=pe, pooled_prompt_embeds=pp,
                 negative_prompt_embeds=ne, negative_pooled_prompt_embeds=npl, inv_prompt_embeds=ipe, inv_pooled_prompt_embeds=ipp,
                 refiner_prompt_embeds=rpe, refiner_pooled_prompt_embeds=rpp, refiner_negative_prompt_embeds=rne, refiner_negative_pooled_prompt_embeds=rnp)
 
 
 pipe = InstructAny2PixPipeline(unet=base, ip_ckpt=ck, device=DEV, clip_embeddings_dim=1024, conditioner=conditioner, refiner_unet=ref, prior=prior,
-                               vae_encode=vae.encode_to_latents, vae_decode=vae.decode_from_latents)
+                               vae=vae)
 if os.environ.get("TUNE", "1") == "1":      # measure kernel plans for the three UNet shapes of a request (what bench.py does for its shape)
     t0 = time.perf_counter()
     h = PX // 8
@@ -84,19 +86,23 @@ def _wrap(obj, name, label):
 
 
 _wrap(pipe.pipe_inversion, "inverse", "inversion loop (25 x B=1)")
+_wrap(pipe.pipe_inversion.image_processor, "preprocess", "image_in")
+_wrap(pipe.pipe_inversion, "_vae_encode", "vae_encode")
+_wrap(pipe.pipe, "_vae_decode", "vae_decode (hand-over + 2 outputs)")
+_wrap(pipe.pipe.image_processor, "postprocess", "image_out")
 _wrap(pipe.ip_adapter_xl, "generate", "guided sampling loop (25 x B_eff=2, incl. image-token projection)")
 if getattr(pipe, "model", None) is not None:
     _wrap(pipe.model, "generate_diffusion", "embedding prior")
 _piperf_call = pipe.piperf.__call__
-pipe.piperf = type("TimedRefiner", (), {"__call__": lambda self, *a, **k: timed("refiner pass (incl. VAE hand-off encode)", lambda: _piperf_call(*a, **k)),
+pipe.piperf = type("TimedRefiner", (), {"__call__": lambda self, *a, **k: timed("refiner pass", lambda: _piperf_call(*a, **k)),
                                         "__getattr__": lambda self, n: getattr(_piperf_call.__self__, n)})()
+_wrap(pipe.piperf, "_vae_encode", "vae_encode (refiner hand-over)")
 for rnd in range(2):            # request 0 warms up (workspaces, kernel plans from the cost model), request 1 is reported
     stages.clear()
     torch.manual_seed(3)
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    non_refined, refined, msg = pipe("turn the fox blue", [], num_inference_steps=25, cfg=10, refinement=0.5)
-    out = timed("vae_decode", lambda: vae.decode_from_latents(refined))
+    non_refined, refined, msg = pipe("turn the fox blue", [], num_inference_steps=25, cfg=10, refinement=0.5, output_type="pil")
     torch.cuda.synchronize(); total = (time.perf_counter() - t0) * 1e3
-    assert msg == "SUCCESS!" and torch.isfinite(out.float()).all() and tuple(out.shape) == (1, 3, PX, PX)
+    assert msg == "SUCCESS!" and all(isinstance(o, list) and o[0].size == (PX, PX) and o[0].mode == "RGB" for o in (non_refined, refined))
     print(f"request {rnd}: {total:.0f} ms total; stages (ms): " + ", ".join(f"{k} {v:.1f}" for k, v in stages.items())
           + f", host glue / the rest {total - sum(stages.values()):.0f}", flush=True)
