@@ -361,6 +361,53 @@ ia2p_status ia2p_clip_encode_embeds(ia2p_clip* clip, void* stream, const void* i
 ia2p_status ia2p_prior_step(void* stream, const float* sample, const void* out_cond, const void* out_uncond, const float* noise, float g,
                             float sqrt_a, float sqrt_b, float k0, float k1, float sigma, float* out, int64_t n);
 
+/* ---- the instruction LLM: LLaMA decoder with a KV cache (reference pipeline.py:151-279 `forward_llm`; the model is a Vicuna-7B shaped
+ * `LlamaForCausalLM`, llm/model/language_model/any2pix_llama.py, driven by `any2pix_lm.generate(...)` at pipeline.py:201-211 with use_cache=False:
+ * one full forward per new token there, one cached row here). transformers `LlamaModel` + `lm_head` semantics: pre-RMSNorm blocks, rotary
+ * embeddings (rotate_half convention, rope_theta), multi-head attention at head dim 128 (num_kv_heads must equal num_heads), bias-free
+ * projections, SwiGLU MLP, final `model.norm`, untied `lm_head`. Batch 1 (the reference asserts it, llm/mm_utils.py:93). Parameter keys are
+ * the `LlamaForCausalLM` state-dict names ("model.layers.0.self_attn.q_proj.weight", ...), fp16. The reference loads the checkpoint as 4-bit NF4
+ * with fp32 compute (pipeline.py:28-31); this engine computes from the fp16 weights. */
+typedef struct ia2p_llm ia2p_llm;
+typedef struct {
+  int vocab_size, hidden_size, num_layers, num_heads, num_kv_heads, intermediate_size;
+  float rms_norm_eps;     /* <= 0: 1e-5 */
+  float rope_theta;       /* <= 0: 10000 */
+} ia2p_llm_config;
+ia2p_status ia2p_llm_create(const ia2p_llm_config* cfg, ia2p_llm** out);
+void ia2p_llm_destroy(ia2p_llm* llm);
+const char* ia2p_llm_last_error(ia2p_llm* llm);
+size_t ia2p_llm_arena_bytes(ia2p_llm* llm);
+ia2p_status ia2p_llm_bind_arena(ia2p_llm* llm, void* dev_arena, size_t bytes);
+ia2p_status ia2p_llm_load_tensor(ia2p_llm* llm, const char* key, const void* dev_src, const int64_t* shape, int ndim, void* stream);
+ia2p_status ia2p_llm_finalize_weights(ia2p_llm* llm);
+/* KV cache: fp16 [layer][k | v][max_positions][hidden], caller-owned device memory (16-byte aligned), max_positions <= 8192 (0 bytes otherwise).
+ * Binding a cache sets the position to 0. */
+size_t ia2p_llm_kv_bytes(ia2p_llm* llm, int max_positions);
+ia2p_status ia2p_llm_bind_kv(ia2p_llm* llm, void* dev_cache, size_t bytes, int max_positions);
+/* workspace that serves a prefill of up to max_T rows and any decode step */
+size_t ia2p_llm_workspace_bytes(ia2p_llm* llm, int max_T);
+/* a new request: position 0 (the cache's contents past the position are never read) */
+ia2p_status ia2p_llm_reset(ia2p_llm* llm);
+int ia2p_llm_position(ia2p_llm* llm);
+/* rows of `model.embed_tokens` for int32 device ids [T] -> fp16 [T, hidden] (`embed_tokens(input_ids)`, any2pix_llama.py:277; ids are clamped to the table) */
+ia2p_status ia2p_llm_embed(ia2p_llm* llm, void* stream, const int32_t* input_ids, int T, void* out);
+/* T rows of `inputs_embeds` (fp16 [T, hidden], device) at positions position .. position + T - 1: fills the cache and returns, for the LAST row,
+ * the final-normed hidden state (fp32 [hidden]: `hidden_states[-1][:, -1:]`, what pipeline.py:236,242,257 read) and the logits (fp32 [vocab_size]).
+ * IA2P_ERR_SHAPE when the rows do not fit the cache, IA2P_ERR_NOMEM when they do not fit the workspace. */
+ia2p_status ia2p_llm_prefill(ia2p_llm* llm, void* stream, const void* inputs_embeds, int T, float* hidden_out, float* logits_out, void* workspace,
+                             size_t workspace_bytes);
+/* one row at the current position: the table embedding of token_id (generated tokens are always embedded from the table, `<video>` included:
+ * any2pix_llama.py:286-287 touches the first n `<video>` positions only). Same outputs.
+ * IA2P_ERR_STATE before a prefill (position 0), IA2P_ERR_SHAPE when the position is past the cache or the token outside the vocabulary. */
+ia2p_status ia2p_llm_decode(ia2p_llm* llm, void* stream, int token_id, float* hidden_out, float* logits_out, void* workspace, size_t workspace_bytes);
+/* the weight-streaming GEMV of the decode path on its own (tools/llm_decode_bench.py measures it against ia2p_linear_small):
+ * out[N] fp32 = W[N, K] fp16 . x[K] fp32, K a multiple of 8 */
+ia2p_status ia2p_llm_gemv(void* stream, const void* W, const float* x, float* out, int N, int K);
+/* exact (erf) GELU in place on fp16 [n]: the activation of an `mlpNx_gelu` projector head between two ia2p_linear_small calls
+ * (llm/model/multimodal_projector/builder.py:33-74 `nn.GELU()`) */
+ia2p_status ia2p_gelu(void* stream, void* x, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,10 +3,10 @@
 Importing this package touches no GPU and no native code; the HIP library (libia2p_hip.so, built by
 `python -m instructany2pix_amd.build`) is loaded on first use and there is no non-HIP fallback.
 """
-from .config import UNetConfig, sdxl_base, sdxl_refiner, tiny
+from .config import LLMConfig, UNetConfig, sdxl_base, sdxl_refiner, tiny, tiny_llm, vicuna_7b
 
 __all__ = ["InstructAny2PixPrior", "prior_config", "MODALITY", "HipGPT2Model", "DDPMScheduler", "HipCLIPTextModel", "SDXLTextEncoders", "UNetConfig", "sdxl_base", "sdxl_refiner", "tiny", "StableDiffusionXLImg2ImgPipeline", "EulerDiscreteScheduler", "InstructAny2PixPipeline", "HipUNet2DConditionModel", "DDIMScheduler",
-           "SDXLDDIMPipeline", "StableDiffusionXLPipeline", "IPAdapterXL", "ImageProjModel", "HipAutoencoderKL", "EditRequest", "VaeImageProcessor"]
+           "SDXLDDIMPipeline", "StableDiffusionXLPipeline", "IPAdapterXL", "ImageProjModel", "HipAutoencoderKL", "EditRequest", "VaeImageProcessor", "HipInstructAny2PixLM", "KeywordsStoppingCriteria", "LLMConfig", "vicuna_7b", "tiny_llm"]
 
 
 def __getattr__(name):          # lazy: keep `import instructany2pix_amd` free of torch/ctypes work
@@ -31,6 +31,9 @@ def __getattr__(name):          # lazy: keep `import instructany2pix_amd` free o
     elif name in ("HipCLIPTextModel", "SDXLTextEncoders"):
         from . import clip
         v = getattr(clip, name)
+    elif name in ("HipInstructAny2PixLM", "KeywordsStoppingCriteria"):
+        from . import llm
+        v = getattr(llm, name)
     elif name == "EditRequest":
         from .batch import EditRequest as v
     elif name == "HipAutoencoderKL":

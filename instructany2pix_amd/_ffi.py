@@ -36,6 +36,11 @@ class CLIPConfigC(C.Structure):
                 ("max_positions", C.c_int), ("projection_dim", C.c_int), ("hidden_act", C.c_int), ("eos_token_id", C.c_int), ("layer_norm_eps", C.c_float)]
 
 
+class LLMConfigC(C.Structure):
+    _fields_ = [("vocab_size", C.c_int), ("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int), ("num_kv_heads", C.c_int),
+                ("intermediate_size", C.c_int), ("rms_norm_eps", C.c_float), ("rope_theta", C.c_float)]
+
+
 class VAEConfigC(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("latent_channels", C.c_int), ("n_blocks", C.c_int),
                 ("block_out_channels", C.c_int * MAX_BLOCKS), ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int),
@@ -123,6 +128,23 @@ SIGNATURES = {
     "ia2p_clip_encode": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _SZ]),
     "ia2p_clip_encode_embeds": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _SZ]),
     "ia2p_prior_step": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P, _I64]),
+    "ia2p_llm_create": (_I, [C.POINTER(LLMConfigC), C.POINTER(_P)]),
+    "ia2p_llm_destroy": (None, [_P]),
+    "ia2p_llm_last_error": (C.c_char_p, [_P]),
+    "ia2p_llm_arena_bytes": (_SZ, [_P]),
+    "ia2p_llm_bind_arena": (_I, [_P, _P, _SZ]),
+    "ia2p_llm_load_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I, _P]),
+    "ia2p_llm_finalize_weights": (_I, [_P]),
+    "ia2p_llm_kv_bytes": (_SZ, [_P, _I]),
+    "ia2p_llm_bind_kv": (_I, [_P, _P, _SZ, _I]),
+    "ia2p_llm_workspace_bytes": (_SZ, [_P, _I]),
+    "ia2p_llm_reset": (_I, [_P]),
+    "ia2p_llm_position": (_I, [_P]),
+    "ia2p_llm_embed": (_I, [_P, _P, _P, _I, _P]),
+    "ia2p_llm_prefill": (_I, [_P, _P, _P, _I, _P, _P, _P, _SZ]),
+    "ia2p_llm_decode": (_I, [_P, _P, _I, _P, _P, _P, _SZ]),
+    "ia2p_llm_gemv": (_I, [_P, _P, _P, _P, _I, _I]),
+    "ia2p_gelu": (_I, [_P, _P, _I64]),
     "ia2p_vae_create": (_I, [C.POINTER(VAEConfigC), C.POINTER(_P)]),
     "ia2p_vae_destroy": (None, [_P]),
     "ia2p_vae_last_error": (C.c_char_p, [_P]),
@@ -179,12 +201,13 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def check(status: int, ctx=None, vae=False, clip=False):
+def check(status: int, ctx=None, vae=False, clip=False, llm=False):
     """Map ia2p_status to the exception types the reference raises at the same conditions
     (ValueError from check_inputs/_get_add_time_ids, reference pnp_pipeline.py:49-66)."""
     if status == IA2P_OK:
         return
-    msg = lib().ia2p_clip_last_error(ctx) if clip else lib().ia2p_vae_last_error(ctx) if vae else lib().ia2p_last_error(ctx)
+    msg = (lib().ia2p_llm_last_error(ctx) if llm else lib().ia2p_clip_last_error(ctx) if clip else lib().ia2p_vae_last_error(ctx) if vae
+           else lib().ia2p_last_error(ctx))
     msg = msg.decode() if msg else ""
     text = f"ia2p {_STATUS_NAMES.get(status, status)}: {msg}"
     if status in (1, 2):
@@ -235,6 +258,14 @@ def make_clip_config(cfg) -> CLIPConfigC:
     c.intermediate_size, c.max_positions, c.projection_dim = cfg.intermediate_size, cfg.max_position_embeddings, cfg.projection_dim
     c.hidden_act = {"gelu": 1, "quick_gelu": 2, "gelu_new": 3}[cfg.hidden_act]
     c.eos_token_id, c.layer_norm_eps = cfg.eos_token_id, cfg.layer_norm_eps
+    return c
+
+
+def make_llm_config(cfg) -> LLMConfigC:
+    c = LLMConfigC()
+    c.vocab_size, c.hidden_size, c.num_layers, c.num_heads = cfg.vocab_size, cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads
+    c.num_kv_heads, c.intermediate_size = cfg.num_key_value_heads, cfg.intermediate_size
+    c.rms_norm_eps, c.rope_theta = cfg.rms_norm_eps, cfg.rope_theta
     return c
 
 

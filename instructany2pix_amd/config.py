@@ -205,3 +205,39 @@ def tiny_gpt2() -> GPT2Config:
 def tiny_clip(projection_dim: int = 0, hidden_act: str = "quick_gelu") -> CLIPTextConfig:
     return CLIPTextConfig(vocab_size=1000, hidden_size=128, num_hidden_layers=3, num_attention_heads=2, intermediate_size=256,
                           hidden_act=hidden_act, projection_dim=projection_dim).validate()
+
+
+@dataclass
+class LLMConfig:
+    """transformers `LlamaConfig` fields of the instruction LLM (`InstructAny2PixLMForCausalLM`, a Vicuna-7B shaped LLaMA; reference
+    instructany2pix/pipeline.py:22-37 `build_lm`) plus the two `InstructAny2PixLMMetaModel` fields its projector heads read
+    (`mm_projector_type`, llm/model/any2pix_arch.py:38-43). `vocab_size` counts the special tokens the checkpoint's tokenizer added."""
+    vocab_size: int = 32000
+    hidden_size: int = 4096
+    num_hidden_layers: int = 32
+    num_attention_heads: int = 32
+    num_key_value_heads: Optional[int] = None      # None = num_attention_heads (plain multi-head attention, the only form built)
+    intermediate_size: int = 11008
+    rms_norm_eps: float = 1e-5
+    rope_theta: float = 10000.0
+    embed_dim: int = 1024                          # width of the modality embeddings (ImageBind) the heads map from / to
+    mm_projector_type: str = "linear"              # "linear" or "mlpNx_gelu"
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+    def validate(self):
+        if self.num_key_value_heads is None:
+            self.num_key_value_heads = self.num_attention_heads
+        assert self.hidden_size == 128 * self.num_attention_heads, "head dim 128 only"
+        assert self.num_key_value_heads == self.num_attention_heads, "grouped-query attention is not built"
+        assert self.intermediate_size % 64 == 0 and self.embed_dim % 8 == 0
+        return self
+
+
+def vicuna_7b(vocab_size: int = 32000, **kw) -> LLMConfig:
+    return LLMConfig(vocab_size=vocab_size, **kw).validate()
+
+
+def tiny_llm(vocab_size: int = 512, **kw) -> LLMConfig:
+    return LLMConfig(vocab_size=vocab_size, hidden_size=512, num_hidden_layers=4, num_attention_heads=4, intermediate_size=1408, **kw).validate()

@@ -1,0 +1,522 @@
+// LLaMA decoder executor (the instruction LLM) and its C ABI (ia2p_llm_*): see include/ia2p.h and DESIGN.md §10. Runtime and operator wrappers: engine_rt.h / engine.hip.
+#include "engine_rt.h"
+
+// =====================================================================================================================
+// transformers LlamaModel + lm_head (reference instructany2pix/pipeline.py:201-211 `any2pix_lm.generate`, a Vicuna-7B shaped model):
+// pre-RMSNorm blocks, rotary embeddings in the rotate_half convention, multi-head attention at head dim 128, SwiGLU MLP, final norm, untied head.
+// Two paths over one fp16 KV cache [layer][k|v][max_positions][hidden]:
+//   prefill (T rows): op_gemm projections + row kernels (RMSNorm, RoPE + cache write, SiLU-multiply) + causal attention against the cache
+//   decode (one row): five weight-streaming launches per layer -- QKV GEMV (RMSNorm in, RoPE + cache write out), attention, o_proj GEMV (+ residual),
+//                     gate/up GEMV (RMSNorm in, silu(gate) * up out), down_proj GEMV (+ residual); the residual stream of the row stays fp32
+// =====================================================================================================================
+
+enum { EPI_PLAIN = 0, EPI_RESID = 1, EPI_QKV = 2, EPI_SWIGLU = 3 };
+struct LlmGemv {
+  const half_t* W;        // [N, K] row-major
+  const float* X;         // [K] fp32
+  const half_t* gamma;    // RMSNorm weight applied to X on the way in (with eps), or null
+  float eps;
+  int N, K;
+  float* out;             // EPI_PLAIN: out[n] = r;  EPI_RESID: out[n] += r;  EPI_SWIGLU: out[i] = silu(r[i]) * r[I + i] (N = 2 I)
+  float* hid;             // EPI_PLAIN with gamma: the normed input row (workgroup 0 writes it), or null
+  // EPI_QKV (N = 3 H): q row (fp32, rotated), k / v rows of the cache at `pos`
+  const float* inv_freq;  // [64]
+  int pos, H;
+  float* q;
+  half_t* kc;
+  half_t* vc;
+};
+
+// out = epilogue(W . f(x)): a workgroup of 4 waves owns R weight rows; its threads walk K in 16-byte pieces (thread t: pieces t, t + 256, ...), so each
+// step of the workgroup reads 4 KiB of every row, once, with non-temporal loads; fp32 accumulation; the 4 waves' partial sums meet in LDS in wave order
+// (a K split inside the workgroup: deterministic, no atomics). The RMSNorm in front is folded in: sum x^2 over the pieces the threads hold anyway,
+// out = rstd * sum (x gamma) w.
+template <int R, int EPI>
+__global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemv a) {
+  __shared__ float red[4][R + 1];
+  constexpr int HR = R / 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = a.K;
+  int rows[R];
+  if (EPI == EPI_QKV) {            // R / 2 rotary pairs (d, d + 64) of one head block
+#pragma unroll
+    for (int i = 0; i < HR; ++i) {
+      const int pidx = min((int)blockIdx.x * HR + i, a.N / 2 - 1);
+      rows[i] = (pidx >> 6) * 128 + (pidx & 63);
+      rows[i + HR] = rows[i] + 64;
+    }
+  } else if (EPI == EPI_SWIGLU) {  // R / 2 gate rows and their up rows
+#pragma unroll
+    for (int i = 0; i < HR; ++i) {
+      rows[i] = min((int)blockIdx.x * HR + i, a.N / 2 - 1);
+      rows[i + HR] = a.N / 2 + rows[i];
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < R; ++r) rows[r] = min((int)blockIdx.x * R + r, a.N - 1);
+  }
+  float acc[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = 0.f;
+  float ss = 0.f;
+  const int nvec = K >> 3;
+#pragma unroll 2
+  for (int v = tid; v < nvec; v += 256) {
+    h8 w[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) w[r] = __builtin_nontemporal_load((const h8*)(a.W + (size_t)rows[r] * K) + v);
+    const f4 x0 = ((const f4*)a.X)[2 * v], x1 = ((const f4*)a.X)[2 * v + 1];
+    float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+    if (a.gamma) {
+      const h8 g = ((const h8*)a.gamma)[v];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { ss = fmaf(x[e], x[e], ss); x[e] *= (float)g[e]; }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[r] = fmaf(x[e], (float)w[r][e], acc[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
+  ss = wave_sum(ss);
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) red[wave][r] = acc[r];
+    red[wave][R] = ss;
+  }
+  __syncthreads();
+  float rstd = 1.f;
+  if (a.gamma) rstd = 1.0f / sqrtf(((red[0][R] + red[1][R]) + (red[2][R] + red[3][R])) / (float)K + a.eps);
+  auto total = [&](int r) { return ((red[0][r] + red[1][r]) + (red[2][r] + red[3][r])) * rstd; };
+  if (EPI == EPI_PLAIN || EPI == EPI_RESID) {
+    const int n = (int)blockIdx.x * R + tid;
+    if (tid < R && n < a.N) {
+      const float r = total(tid);
+      a.out[n] = EPI == EPI_RESID ? a.out[n] + r : r;
+    }
+    if (EPI == EPI_PLAIN && a.hid && a.gamma && blockIdx.x == 0)
+      for (int i = tid; i < K; i += 256) a.hid[i] = a.X[i] * rstd * (float)a.gamma[i];
+  } else if (EPI == EPI_SWIGLU) {
+    const int i = (int)blockIdx.x * HR + tid;
+    if (tid < HR && i < a.N / 2) {
+      const float g = total(tid), u = total(tid + HR);
+      a.out[i] = g / (1.0f + expf(-g)) * u;
+    }
+  } else {
+    const int pidx = (int)blockIdx.x * HR + tid;
+    if (tid < HR && pidx < a.N / 2) {
+      const int lo = (pidx >> 6) * 128 + (pidx & 63), sec = lo / a.H, c = lo - sec * a.H;
+      float x1 = total(tid), x2 = total(tid + HR);
+      if (sec < 2) {               // q, k: x cos + rotate_half(x) sin
+        const float ang = (float)a.pos * a.inv_freq[pidx & 63];
+        const float cs = cosf(ang), sn = sinf(ang);
+        const float y1 = x1 * cs - x2 * sn, y2 = x2 * cs + x1 * sn;
+        x1 = y1; x2 = y2;
+      }
+      if (sec == 0) { a.q[c] = x1; a.q[c + 64] = x2; }
+      else {
+        half_t* dst = (sec == 1 ? a.kc : a.vc) + (size_t)a.pos * a.H + c;
+        dst[0] = (half_t)x1; dst[64] = (half_t)x2;
+      }
+    }
+  }
+}
+
+// One query row per workgroup (head = blockIdx.x, row t = blockIdx.y at position p0 + t) against the cached keys 0 .. p0 + t, head dim 128:
+// 16 lanes per key (16 bytes of it each), 16 keys per pass; scores in LDS, softmax in fp32, P.V summed per key group and combined in group order.
+template <typename OT>
+__global__ __launch_bounds__(256) void llm_attn_kernel(const float* q, const half_t* kc, const half_t* vc, OT* out, int H, int p0, float scale) {
+  extern __shared__ float llm_sm[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = tid >> 4, l = tid & 15;
+  const int head = blockIdx.x, t = blockIdx.y, nk = p0 + t + 1;
+  float* sc = llm_sm;                 // [nk]
+  float* part = llm_sm + ((nk + 3) & ~3);   // [16][128]
+  float* red = part + 16 * 128;       // [8]
+  float qv[8];
+  {
+    const float* qp = q + (size_t)t * H + head * 128 + l * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qv[e] = qp[e] * scale;
+  }
+  for (int j0 = 0; j0 < nk; j0 += 16) {      // (uniform trip count: the shuffles below need every lane)
+    const int j = j0 + g;
+    float s = 0.f;
+    if (j < nk) {
+      const h8 k = *(const h8*)(kc + (size_t)j * H + head * 128 + l * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s = fmaf(qv[e], (float)k[e], s);
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
+    if (l == 0 && j < nk) sc[j] = s;
+  }
+  __syncthreads();
+  float m = -INFINITY;
+  for (int j = tid; j < nk; j += 256) m = fmaxf(m, sc[j]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sum = 0.f;
+  for (int j = tid; j < nk; j += 256) { const float e = expf(sc[j] - m); sc[j] = e; sum += e; }
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = (red[4] + red[5]) + (red[6] + red[7]);
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = 0.f;
+  for (int j = g; j < nk; j += 16) {
+    const float p = sc[j];
+    const h8 v = *(const h8*)(vc + (size_t)j * H + head * 128 + l * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = fmaf(p, (float)v[e], o[e]);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) part[g * 128 + l * 8 + e] = o[e];
+  __syncthreads();
+  if (tid < 128) {
+    float r = 0.f;
+#pragma unroll
+    for (int gg = 0; gg < 16; ++gg) r += part[gg * 128 + tid];
+    out[(size_t)t * H + head * 128 + tid] = (OT)(r / sum);
+  }
+}
+
+// ---- row kernels of the prefill path -------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void llm_rmsnorm_rows_kernel(const half_t* x, half_t* y, const half_t* gamma, int H, float eps) {
+  __shared__ float red[4];
+  const half_t* xr = x + (size_t)blockIdx.x * H;
+  half_t* yr = y + (size_t)blockIdx.x * H;
+  float ss = 0.f;
+  for (int i = threadIdx.x; i < H; i += 256) { const float v = (float)xr[i]; ss = fmaf(v, v, ss); }
+  ss = wave_sum(ss);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+  __syncthreads();
+  const float rstd = 1.0f / sqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)H + eps);
+  for (int i = threadIdx.x; i < H; i += 256) yr[i] = (half_t)((float)xr[i] * rstd * (float)gamma[i]);
+}
+// qkv [T, 3 H] fp16 -> q [T, H] fp32 (rotated), cache rows p0 + t (k rotated, v as is)
+__global__ __launch_bounds__(256) void llm_rope_cache_rows_kernel(const half_t* qkv, float* q, half_t* kc, half_t* vc, const float* inv_freq, int H, int p0) {
+  const int t = blockIdx.x, pos = p0 + t;
+  const half_t* r = qkv + (size_t)t * 3 * H;
+  for (int i = threadIdx.x; i < H / 2; i += 256) {
+    const int c = (i >> 6) * 128 + (i & 63);
+    const float ang = (float)pos * inv_freq[i & 63];
+    const float cs = cosf(ang), sn = sinf(ang);
+    const float q1 = (float)r[c], q2 = (float)r[c + 64], k1 = (float)r[H + c], k2 = (float)r[H + c + 64];
+    q[(size_t)t * H + c] = q1 * cs - q2 * sn;
+    q[(size_t)t * H + c + 64] = q2 * cs + q1 * sn;
+    kc[(size_t)pos * H + c] = (half_t)(k1 * cs - k2 * sn);
+    kc[(size_t)pos * H + c + 64] = (half_t)(k2 * cs + k1 * sn);
+    vc[(size_t)pos * H + c] = r[2 * H + c];
+    vc[(size_t)pos * H + c + 64] = r[2 * H + c + 64];
+  }
+}
+__global__ __launch_bounds__(256) void llm_silu_mul_rows_kernel(const half_t* gu, half_t* act, int I) {
+  const half_t* r = gu + (size_t)blockIdx.x * 2 * I;
+  for (int i = threadIdx.x; i < I; i += 256) {
+    const float g = (float)r[i], u = (float)r[I + i];
+    act[(size_t)blockIdx.x * I + i] = (half_t)(g / (1.0f + expf(-g)) * u);
+  }
+}
+__global__ __launch_bounds__(256) void llm_row_f32_kernel(const half_t* src, float* dst, int H) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < H; i += gridDim.x * 256) dst[i] = (float)src[i];
+}
+__global__ __launch_bounds__(256) void llm_gather_rows_kernel(const int* ids, const half_t* tok, half_t* out, int H, int vocab) {
+  const int id = min(max(ids[blockIdx.x], 0), vocab - 1);
+  for (int i = threadIdx.x; i < H / 8; i += 256) ((h8*)(out + (size_t)blockIdx.x * H))[i] = ((const h8*)(tok + (size_t)id * H))[i];
+}
+// exact (erf) GELU in place: the activation between the two linears of an `mlpNx_gelu` projector head
+__global__ __launch_bounds__(256) void llm_gelu_kernel(half_t* x, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) { const float v = (float)x[i]; x[i] = (half_t)(0.5f * v * (1.0f + erff(v * 0.70710678118654752440f))); }
+}
+
+template <int R>
+static hipError_t gemv_launch_r(const LlmGemv& a, int epi, hipStream_t s) {
+  const int units = epi == EPI_QKV || epi == EPI_SWIGLU ? (a.N / 2 + R / 2 - 1) / (R / 2) : (a.N + R - 1) / R;
+  switch (epi) {
+    case EPI_PLAIN: hipLaunchKernelGGL((llm_gemv_kernel<R, EPI_PLAIN>), dim3(units), dim3(256), 0, s, a); break;
+    case EPI_RESID: hipLaunchKernelGGL((llm_gemv_kernel<R, EPI_RESID>), dim3(units), dim3(256), 0, s, a); break;
+    case EPI_QKV: hipLaunchKernelGGL((llm_gemv_kernel<R, EPI_QKV>), dim3(units), dim3(256), 0, s, a); break;
+    case EPI_SWIGLU: hipLaunchKernelGGL((llm_gemv_kernel<R, EPI_SWIGLU>), dim3(units), dim3(256), 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+// 8 rows per workgroup where that still leaves every CU several workgroups (N >= 8192: 1024+ of them), 4 below (N = 4096: 1024 workgroups)
+static hipError_t llm_launch_gemv(const LlmGemv& a, int epi, hipStream_t s) {
+  if (!a.W || !a.X || a.N < 1 || a.K < 8 || a.K % 8) return hipErrorInvalidValue;
+  if ((epi == EPI_QKV && (a.N != 3 * a.H || a.H % 128)) || (epi == EPI_SWIGLU && a.N % 2)) return hipErrorInvalidValue;
+  return a.N >= 8192 ? gemv_launch_r<8>(a, epi, s) : gemv_launch_r<4>(a, epi, s);
+}
+static size_t attn_lds(int nk) { return ((size_t)((nk + 3) & ~3) + 16 * 128 + 8) * sizeof(float); }
+constexpr int LLM_MAX_POSITIONS = 8192;       // scores of one query row live in LDS (32 KiB of the 64)
+
+struct LLayer { size_t ln1, ln2, wqkv, wo, wgu, wd; };
+struct ia2p_llm : RunCtx {
+  ia2p_llm_config cfg;
+  size_t tok, normf, head, invf;
+  std::vector<LLayer> layers;
+  half_t* kv = nullptr;
+  int max_pos = 0, pos = 0;
+};
+
+static ia2p_status llm_plan(ia2p_llm* c) {
+  const ia2p_llm_config& g = c->cfg;
+  const int H = g.hidden_size, I = g.intermediate_size;
+  if (g.num_layers < 1 || g.num_heads < 1 || g.vocab_size < 1 || H < 128 || I < 64)
+    return fail(c, IA2P_ERR_INVALID, "llm: layers %d, heads %d, vocabulary %d, hidden %d, intermediate %d", g.num_layers, g.num_heads, g.vocab_size, H, I);
+  if (H % 64 || g.num_heads * 128 != H) return fail(c, IA2P_ERR_SHAPE, "llm: hidden %d must be a multiple of 64 and heads (%d) * 128 (head dim 128 only)", H, g.num_heads);
+  if (g.num_kv_heads != g.num_heads) return fail(c, IA2P_ERR_SHAPE, "llm: %d key/value heads for %d heads (grouped-query attention is not built)", g.num_kv_heads, g.num_heads);
+  if (I % 64) return fail(c, IA2P_ERR_SHAPE, "llm: intermediate %d must be a multiple of 64", I);
+  size_t cur = 0;
+  auto take = [&](size_t e) { size_t o = cur; cur += (e + 127) & ~(size_t)127; return o; };
+  auto reg = [&](const std::string& k, size_t off, size_t n) { c->params[k] = Param{off, n, PK_COPY, 0, 0, false, false}; };
+  auto par = [&](const std::string& k, size_t n) { size_t o = take(n); reg(k, o, n); return o; };
+  c->tok = par("model.embed_tokens.weight", (size_t)g.vocab_size * H);
+  for (int i = 0; i < g.num_layers; ++i) {
+    const std::string p = "model.layers." + std::to_string(i) + ".";
+    LLayer l;
+    l.ln1 = par(p + "input_layernorm.weight", H);
+    l.wqkv = take((size_t)3 * H * H);                       // q | k | v rows stacked: one projection
+    const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
+    for (int j = 0; j < 3; ++j) reg(p + "self_attn." + nm[j] + ".weight", l.wqkv + (size_t)j * H * H, (size_t)H * H);
+    l.wo = par(p + "self_attn.o_proj.weight", (size_t)H * H);
+    l.ln2 = par(p + "post_attention_layernorm.weight", H);
+    l.wgu = take((size_t)2 * I * H);                        // gate | up rows stacked
+    reg(p + "mlp.gate_proj.weight", l.wgu, (size_t)I * H);
+    reg(p + "mlp.up_proj.weight", l.wgu + (size_t)I * H, (size_t)I * H);
+    l.wd = par(p + "mlp.down_proj.weight", (size_t)H * I);
+    c->layers.push_back(l);
+  }
+  c->normf = par("model.norm.weight", H);
+  c->head = par("lm_head.weight", (size_t)g.vocab_size * H);
+  c->invf = take(128);                                      // 64 fp32 rotary frequencies (derived at finalize)
+  c->arena_elems = cur;
+  return IA2P_OK;
+}
+
+static half_t* KC(ia2p_llm* c, int layer) { return c->kv + (size_t)layer * 2 * c->max_pos * c->cfg.hidden_size; }
+static half_t* VC(ia2p_llm* c, int layer) { return KC(c, layer) + (size_t)c->max_pos * c->cfg.hidden_size; }
+
+// final norm + lm_head of the fp32 row xf: hidden_out [H] fp32, logits_out [vocab] fp32
+static void llm_head(ia2p_llm* c, const float* xf, float* hidden_out, float* logits_out) {
+  LlmGemv a{};
+  a.W = W_(c, c->head); a.X = xf; a.gamma = W_(c, c->normf); a.eps = c->cfg.rms_norm_eps; a.N = c->cfg.vocab_size; a.K = c->cfg.hidden_size;
+  a.out = logits_out; a.hid = hidden_out;
+  CHECK_LAUNCH(c, llm_launch_gemv(a, EPI_PLAIN, c->stream), "llm lm_head");
+}
+
+static ia2p_status llm_run_decode(ia2p_llm* c, int token, float* hidden_out, float* logits_out) {
+  const ia2p_llm_config& g = c->cfg;
+  const int H = g.hidden_size, I = g.intermediate_size, pos = c->pos;
+  T2 xt = wsalloc(c, (size_t)2 * H), qt = wsalloc(c, (size_t)2 * H), at = wsalloc(c, (size_t)2 * H), ft = wsalloc(c, (size_t)2 * I);
+  float *xf = (float*)xt.p, *qf = (float*)qt.p, *af = (float*)at.p, *ff = (float*)ft.p;
+  if (!c->dry && !c->failed) {
+    const half_t* src = W_(c, c->tok) + (size_t)token * H;
+    hipLaunchKernelGGL(llm_row_f32_kernel, dim3((H + 255) / 256), dim3(256), 0, c->stream, src, xf, H);
+    CHECK_LAUNCH(c, hipGetLastError(), "llm embedding row");
+  }
+  for (int i = 0; i < g.num_layers; ++i) {
+    const LLayer& l = c->layers[i];
+    if (c->dry || c->failed) break;
+    LlmGemv a{};
+    a.W = W_(c, l.wqkv); a.X = xf; a.gamma = W_(c, l.ln1); a.eps = g.rms_norm_eps; a.N = 3 * H; a.K = H; a.H = H; a.pos = pos;
+    a.inv_freq = (const float*)W_(c, c->invf); a.q = qf; a.kc = KC(c, i); a.vc = VC(c, i);
+    CHECK_LAUNCH(c, llm_launch_gemv(a, EPI_QKV, c->stream), "llm qkv");
+    hipLaunchKernelGGL(llm_attn_kernel<float>, dim3(g.num_heads, 1), dim3(256), attn_lds(pos + 1), c->stream, (const float*)qf, (const half_t*)KC(c, i), (const half_t*)VC(c, i), af, H, pos,
+                       0.08838834764831845f);
+    CHECK_LAUNCH(c, hipGetLastError(), "llm attention");
+    LlmGemv o{};
+    o.W = W_(c, l.wo); o.X = af; o.N = H; o.K = H; o.out = xf;
+    CHECK_LAUNCH(c, llm_launch_gemv(o, EPI_RESID, c->stream), "llm o_proj");
+    LlmGemv u{};
+    u.W = W_(c, l.wgu); u.X = xf; u.gamma = W_(c, l.ln2); u.eps = g.rms_norm_eps; u.N = 2 * I; u.K = H; u.out = ff;
+    CHECK_LAUNCH(c, llm_launch_gemv(u, EPI_SWIGLU, c->stream), "llm gate/up");
+    LlmGemv d{};
+    d.W = W_(c, l.wd); d.X = ff; d.N = H; d.K = I; d.out = xf;
+    CHECK_LAUNCH(c, llm_launch_gemv(d, EPI_RESID, c->stream), "llm down_proj");
+  }
+  if (!c->dry) llm_head(c, xf, hidden_out, logits_out);
+  wsfree(c, ft); wsfree(c, at); wsfree(c, qt); wsfree(c, xt);
+  return c->failed ? IA2P_ERR_HIP : IA2P_OK;
+}
+
+static ia2p_status llm_run_prefill(ia2p_llm* c, const half_t* embeds, int T, float* hidden_out, float* logits_out) {
+  const ia2p_llm_config& g = c->cfg;
+  const int H = g.hidden_size, I = g.intermediate_size, p0 = c->pos;
+  T2 x = wsalloc(c, (size_t)T * H), xn = wsalloc(c, (size_t)T * H), qkv = wsalloc(c, (size_t)T * 3 * H), qt = wsalloc(c, (size_t)T * H * 2);
+  T2 att = wsalloc(c, (size_t)T * H), gu = wsalloc(c, (size_t)T * 2 * I), act = wsalloc(c, (size_t)T * I), xt = wsalloc(c, (size_t)2 * H);
+  float *qf = (float*)qt.p, *xf = (float*)xt.p;
+  if (!c->dry && !c->failed) {
+    hipError_t e = hipMemcpyAsync(x.p, embeds, (size_t)T * H * sizeof(half_t), hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) fail_hip(c, e, "llm prefill");
+  }
+  for (int i = 0; i < g.num_layers; ++i) {
+    const LLayer& l = c->layers[i];
+    if (!c->dry && !c->failed) {
+      hipLaunchKernelGGL(llm_rmsnorm_rows_kernel, dim3(T), dim3(256), 0, c->stream, (const half_t*)x.p, xn.p, W_(c, l.ln1), H, g.rms_norm_eps);
+      CHECK_LAUNCH(c, hipGetLastError(), "llm input_layernorm");
+    }
+    op_gemm(c, xn.p, H, W_(c, l.wqkv), nullptr, nullptr, 0, qkv.p, 3 * H, T, 3 * H, H);
+    if (!c->dry && !c->failed) {
+      hipLaunchKernelGGL(llm_rope_cache_rows_kernel, dim3(T), dim3(256), 0, c->stream, (const half_t*)qkv.p, qf, KC(c, i), VC(c, i), (const float*)W_(c, c->invf), H, p0);
+      CHECK_LAUNCH(c, hipGetLastError(), "llm rope");
+      hipLaunchKernelGGL(llm_attn_kernel<half_t>, dim3(g.num_heads, T), dim3(256), attn_lds(p0 + T), c->stream, (const float*)qf, (const half_t*)KC(c, i), (const half_t*)VC(c, i), att.p, H, p0,
+                         0.08838834764831845f);
+      CHECK_LAUNCH(c, hipGetLastError(), "llm attention");
+    }
+    op_gemm(c, att.p, H, W_(c, l.wo), nullptr, x.p, H, x.p, H, T, H, H);
+    if (!c->dry && !c->failed) {
+      hipLaunchKernelGGL(llm_rmsnorm_rows_kernel, dim3(T), dim3(256), 0, c->stream, (const half_t*)x.p, xn.p, W_(c, l.ln2), H, g.rms_norm_eps);
+      CHECK_LAUNCH(c, hipGetLastError(), "llm post_attention_layernorm");
+    }
+    op_gemm(c, xn.p, H, W_(c, l.wgu), nullptr, nullptr, 0, gu.p, 2 * I, T, 2 * I, H);
+    if (!c->dry && !c->failed) {
+      hipLaunchKernelGGL(llm_silu_mul_rows_kernel, dim3(T), dim3(256), 0, c->stream, (const half_t*)gu.p, act.p, I);
+      CHECK_LAUNCH(c, hipGetLastError(), "llm silu-multiply");
+    }
+    op_gemm(c, act.p, I, W_(c, l.wd), nullptr, x.p, H, x.p, H, T, H, I);
+  }
+  if (!c->dry && !c->failed) {          // only the last row goes through model.norm and lm_head
+    hipLaunchKernelGGL(llm_row_f32_kernel, dim3((H + 255) / 256), dim3(256), 0, c->stream, (const half_t*)(x.p + (size_t)(T - 1) * H), xf, H);
+    CHECK_LAUNCH(c, hipGetLastError(), "llm last row");
+    llm_head(c, xf, hidden_out, logits_out);
+  }
+  wsfree(c, xt); wsfree(c, act); wsfree(c, gu); wsfree(c, att); wsfree(c, qt); wsfree(c, qkv); wsfree(c, xn); wsfree(c, x);
+  return c->failed ? IA2P_ERR_HIP : IA2P_OK;
+}
+
+static size_t llm_dry(ia2p_llm* c, int T) {
+  c->dry = true; c->failed = false; c->record = false;
+  c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
+  if (T > 0) (void)llm_run_prefill(c, nullptr, T, nullptr, nullptr);
+  else (void)llm_run_decode(c, 0, nullptr, nullptr);
+  c->dry = false;
+  return c->failed ? 0 : c->ws.high + 256;
+}
+static ia2p_status llm_ready(ia2p_llm* c, const char* what) {
+  if (!c->finalized) return fail(c, IA2P_ERR_STATE, "%s before weights were finalized", what);
+  if (!c->kv) return fail(c, IA2P_ERR_STATE, "%s before ia2p_llm_bind_kv", what);
+  return IA2P_OK;
+}
+static ia2p_status llm_enter(ia2p_llm* c, void* stream, void* ws, size_t ws_bytes, size_t need) {
+  const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
+  const size_t lost = base - (uintptr_t)ws;
+  if (need == 0 || ws_bytes < lost || ws_bytes - lost + 256 < need) return fail(c, IA2P_ERR_NOMEM, "llm: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  c->wseq.clear(); c->widx = 0; c->dry = false; c->failed = false; c->stream = (hipStream_t)stream;
+  c->ws.reset(ws_bytes - lost); c->ws_base = (char*)base;
+  return IA2P_OK;
+}
+static ia2p_status llm_leave(ia2p_llm* c, ia2p_status st) {
+  if (c->failed && st == IA2P_OK) st = IA2P_ERR_HIP;
+  if (c->failed && c->err == "workspace too small") st = IA2P_ERR_NOMEM;
+  return st;
+}
+
+extern "C" {
+
+ia2p_status ia2p_llm_create(const ia2p_llm_config* cfg, ia2p_llm** out) {
+  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_llm_create: null argument");
+  ia2p_llm* c = new ia2p_llm();
+  c->cfg = *cfg;
+  if (c->cfg.rms_norm_eps <= 0.f) c->cfg.rms_norm_eps = 1e-5f;
+  if (c->cfg.rope_theta <= 0.f) c->cfg.rope_theta = 10000.f;
+  ia2p_status st = llm_plan(c);
+  if (st != IA2P_OK) { g_err = c->err; delete c; *out = nullptr; return st; }
+  c->failed = false;
+  *out = c;
+  return IA2P_OK;
+}
+void ia2p_llm_destroy(ia2p_llm* c) { delete c; }
+const char* ia2p_llm_last_error(ia2p_llm* c) { return c ? c->err.c_str() : g_err.c_str(); }
+size_t ia2p_llm_arena_bytes(ia2p_llm* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
+ia2p_status ia2p_llm_bind_arena(ia2p_llm* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
+ia2p_status ia2p_llm_load_tensor(ia2p_llm* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
+  return rc_load_tensor(c, key, src, shape, ndim, stream);
+}
+ia2p_status ia2p_llm_finalize_weights(ia2p_llm* c) {
+  const ia2p_status st = rc_finalize(c, "LLM");
+  if (st != IA2P_OK) return st;
+  float f[64];      // transformers LlamaRotaryEmbedding: inv_freq = 1 / theta^(2 i / 128), fp32
+  for (int i = 0; i < 64; ++i) f[i] = 1.0f / powf(c->cfg.rope_theta, (float)(2 * i) / 128.0f);
+  hipError_t e = hipMemcpy(c->arena + c->invf, f, sizeof f, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { c->finalized = false; return fail_hip(c, e, "llm rotary table"); }
+  return IA2P_OK;
+}
+size_t ia2p_llm_kv_bytes(ia2p_llm* c, int max_positions) {
+  if (!c || max_positions < 1 || max_positions > LLM_MAX_POSITIONS) return 0;
+  return (size_t)c->cfg.num_layers * 2 * (size_t)max_positions * c->cfg.hidden_size * sizeof(half_t);
+}
+ia2p_status ia2p_llm_bind_kv(ia2p_llm* c, void* dev, size_t bytes, int max_positions) {
+  if (!c || !dev) return fail(c, IA2P_ERR_INVALID, "llm_bind_kv: null argument");
+  if (max_positions < 1 || max_positions > LLM_MAX_POSITIONS) return fail(c, IA2P_ERR_SHAPE, "llm_bind_kv: %d positions (1..%d)", max_positions, LLM_MAX_POSITIONS);
+  if (((uintptr_t)dev) & 15) return fail(c, IA2P_ERR_INVALID, "llm_bind_kv: the cache must be 16-byte aligned");
+  if (bytes < ia2p_llm_kv_bytes(c, max_positions)) return fail(c, IA2P_ERR_NOMEM, "llm_bind_kv: %zu bytes, %zu needed", bytes, ia2p_llm_kv_bytes(c, max_positions));
+  c->kv = (half_t*)dev; c->max_pos = max_positions; c->pos = 0;
+  return IA2P_OK;
+}
+size_t ia2p_llm_workspace_bytes(ia2p_llm* c, int max_T) {
+  if (!c || max_T < 1) return 0;
+  const size_t a = llm_dry(c, max_T), b = llm_dry(c, 0);
+  return a && b ? std::max(a, b) : 0;
+}
+ia2p_status ia2p_llm_reset(ia2p_llm* c) {
+  if (!c) return fail(nullptr, IA2P_ERR_INVALID, "llm_reset: null argument");
+  c->pos = 0;
+  return IA2P_OK;
+}
+int ia2p_llm_position(ia2p_llm* c) { return c ? c->pos : -1; }
+ia2p_status ia2p_llm_embed(ia2p_llm* c, void* stream, const int32_t* ids, int T, void* out) {
+  if (!c || !ids || !out) return fail(c, IA2P_ERR_INVALID, "llm_embed: null argument");
+  if (T < 1) return fail(c, IA2P_ERR_SHAPE, "llm_embed: T=%d", T);
+  if (!c->finalized) return fail(c, IA2P_ERR_STATE, "llm_embed before weights were finalized");
+  hipLaunchKernelGGL(llm_gather_rows_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, (const int*)ids, W_(c, c->tok), (half_t*)out, c->cfg.hidden_size, c->cfg.vocab_size);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? IA2P_OK : fail_hip(c, e, "llm_embed");
+}
+ia2p_status ia2p_llm_prefill(ia2p_llm* c, void* stream, const void* inputs_embeds, int T, float* hidden_out, float* logits_out, void* ws, size_t ws_bytes) {
+  if (!c || !inputs_embeds || !hidden_out || !logits_out || !ws) return fail(c, IA2P_ERR_INVALID, "llm_prefill: null argument");
+  ia2p_status st = llm_ready(c, "llm_prefill");
+  if (st != IA2P_OK) return st;
+  if (T < 1 || c->pos + T > c->max_pos) return fail(c, IA2P_ERR_SHAPE, "llm_prefill: %d rows at position %d, the cache holds %d", T, c->pos, c->max_pos);
+  if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
+  st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, T));
+  if (st != IA2P_OK) return st;
+  st = llm_leave(c, llm_run_prefill(c, (const half_t*)inputs_embeds, T, hidden_out, logits_out));
+  if (st == IA2P_OK) c->pos += T;
+  return st;
+}
+ia2p_status ia2p_llm_decode(ia2p_llm* c, void* stream, int token_id, float* hidden_out, float* logits_out, void* ws, size_t ws_bytes) {
+  if (!c || !hidden_out || !logits_out || !ws) return fail(c, IA2P_ERR_INVALID, "llm_decode: null argument");
+  ia2p_status st = llm_ready(c, "llm_decode");
+  if (st != IA2P_OK) return st;
+  if (c->pos < 1) return fail(c, IA2P_ERR_STATE, "llm_decode before a prefill (position 0)");
+  if (c->pos >= c->max_pos) return fail(c, IA2P_ERR_SHAPE, "llm_decode: position %d is past the cache (%d positions)", c->pos, c->max_pos);
+  if (token_id < 0 || token_id >= c->cfg.vocab_size) return fail(c, IA2P_ERR_SHAPE, "llm_decode: token %d outside the vocabulary (%d)", token_id, c->cfg.vocab_size);
+  st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, 0));
+  if (st != IA2P_OK) return st;
+  st = llm_leave(c, llm_run_decode(c, token_id, hidden_out, logits_out));
+  if (st == IA2P_OK) c->pos += 1;
+  return st;
+}
+ia2p_status ia2p_llm_gemv(void* stream, const void* W, const float* x, float* out, int N, int K) {
+  if (!W || !x || !out) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv: null argument");
+  if (N < 1 || K < 8 || K % 8) return fail(nullptr, IA2P_ERR_SHAPE, "llm_gemv: N=%d K=%d (K a multiple of 8)", N, K);
+  LlmGemv a{};
+  a.W = (const half_t*)W; a.X = x; a.N = N; a.K = K; a.out = out;
+  hipError_t e = llm_launch_gemv(a, EPI_PLAIN, (hipStream_t)stream);
+  RET_HIP(e, "llm_gemv");
+}
+ia2p_status ia2p_gelu(void* stream, void* x, int64_t n) {
+  if (!x) return fail(nullptr, IA2P_ERR_INVALID, "gelu: null argument");
+  if (n < 1 || n > ((int64_t)1 << 31)) return fail(nullptr, IA2P_ERR_SHAPE, "gelu: n=%lld", (long long)n);
+  hipLaunchKernelGGL(llm_gelu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (half_t*)x, (long)n);
+  hipError_t e = hipGetLastError();
+  RET_HIP(e, "gelu");
+}
+
+}  // extern "C"

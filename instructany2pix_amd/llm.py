@@ -1,0 +1,382 @@
+"""The instruction LLM on the HIP kernels and the host plumbing of `forward_llm` (reference instructany2pix/pipeline.py:151-279).
+
+  HipInstructAny2PixLM(config)      <- `InstructAny2PixLMForCausalLM` at inference: a LLaMA decoder (transformers `LlamaForCausalLM`) plus the two
+                                       heads of `InstructAny2PixLMMetaModel` the live call uses (llm/model/any2pix_arch.py:38-43):
+                                       `vae_projector_image` (1024-d embedding -> hidden) and `vae_predictor_image` (hidden -> embedding)
+  .generate(input_ids, ...)         <- `any2pix_lm.generate(...)` as pipeline.py:201-211 calls it. The reference runs one full forward per new
+                                       token (`use_cache=False`); here the prompt is prefilled once and each token is one `ia2p_llm_decode`.
+  KeywordsStoppingCriteria          <- llm/mm_utils.py:77-107
+  vicuna_v1_prompt(inst)            <- `conv_templates['vicuna_v1']` with one user turn and an open assistant turn (llm/conversation.py:51-62,252-262)
+  parse_generation(...)             <- pipeline.py:213-279: what `forward_llm` reads out of the generated sequence and its hidden rows
+
+Everything between `inputs_embeds` and (final-normed hidden row, logits row) runs through `ia2p_llm_*`; sampling from the logits row, stopping and
+the text parsing are host code. The tokenizer is injected (its sentencepiece model is checkpoint data). The reference loads the checkpoint as
+4-bit NF4 with fp32 compute (pipeline.py:28-31); this engine computes from the fp16 weights."""
+from __future__ import annotations
+
+import ctypes as C
+import re
+from types import SimpleNamespace
+from typing import Optional
+
+import torch
+
+from . import _ffi
+from .config import LLMConfig
+from .weights import projector_depth
+
+try:                                  # the protocol `generate(stopping_criteria=[...])` expects; the class works without transformers too
+    from transformers import StoppingCriteria as _StoppingCriteria
+except Exception:                     # pragma: no cover
+    _StoppingCriteria = object
+
+
+class REPLACEMENT_TYPE:               # reference pipeline.py:89-92
+    INPUT = 0
+    BASE = 1
+    GEN = 2
+
+
+VICUNA_V1_SYSTEM = ("A chat between a curious user and an artificial intelligence assistant. "
+                    "The assistant gives helpful, detailed, and polite answers to the user's questions.")
+VICUNA_V1_ROLES = ("USER", "ASSISTANT")
+VICUNA_V1_SEP, VICUNA_V1_SEP2 = " ", "</s>"
+
+
+def vicuna_v1_prompt(inst) -> str:
+    """`conv.append_message(USER, inst); conv.append_message(ASSISTANT, None); conv.get_prompt()` under SeparatorStyle.TWO: an empty
+    message leaves `role:` without a separator."""
+    seps = [VICUNA_V1_SEP, VICUNA_V1_SEP2]
+    ret = VICUNA_V1_SYSTEM + seps[0]
+    for i, (role, message) in enumerate(((VICUNA_V1_ROLES[0], inst), (VICUNA_V1_ROLES[1], None))):
+        if message:
+            ret += role + ": " + message + seps[i % 2]
+        else:
+            ret += role + ":"
+    return ret
+
+
+class KeywordsStoppingCriteria(_StoppingCriteria):
+    """llm/mm_utils.py:77-107: stop when the sequence ends in a keyword's ids, or the text decoded from the newest tokens contains a keyword."""
+
+    def __init__(self, keywords, tokenizer, input_ids):
+        self.keywords = keywords
+        self.keyword_ids = []
+        self.max_keyword_len = 0
+        for keyword in keywords:
+            cur_keyword_ids = tokenizer(keyword).input_ids
+            if len(cur_keyword_ids) > 1 and cur_keyword_ids[0] == tokenizer.bos_token_id:
+                cur_keyword_ids = cur_keyword_ids[1:]
+            if len(cur_keyword_ids) > self.max_keyword_len:
+                self.max_keyword_len = len(cur_keyword_ids)
+            self.keyword_ids.append(torch.tensor(cur_keyword_ids))
+        self.tokenizer = tokenizer
+        self.start_len = input_ids.shape[1]
+
+    def call_bse(self, output_ids, scores, **kwargs) -> bool:
+        assert output_ids.shape[0] == 1, "Only support batch size 1 (yet)"
+        offset = min(output_ids.shape[1] - self.start_len, self.max_keyword_len)
+        self.keyword_ids = [keyword_id.to(output_ids.device) for keyword_id in self.keyword_ids]
+        for keyword_id in self.keyword_ids:
+            tail = output_ids[0, -keyword_id.shape[0]:]
+            if tail.shape[0] == keyword_id.shape[0] and (tail == keyword_id).all():
+                return True
+        outputs = self.tokenizer.batch_decode(output_ids[:, -offset:], skip_special_tokens=True)[0]
+        for keyword in self.keywords:
+            if keyword in outputs:
+                return True
+        return False
+
+    def __call__(self, output_ids, scores, **kwargs) -> bool:
+        return all(self.call_bse(output_ids[i:i + 1], scores=None, **kwargs) for i in range(output_ids.shape[0]))
+
+
+def sample_probs(logits: torch.Tensor, temperature: float = 0.3, top_k: Optional[int] = 50) -> torch.Tensor:
+    """The distribution transformers' sampling loop draws from: `TemperatureLogitsWarper` -> `TopKLogitsWarper` -> softmax, in that order.
+    (transformers 4.34.1, which the reference pins, carries `top_k=50` in its default generation config.) logits: [..., vocab] fp32."""
+    scores = logits.float() / temperature
+    if top_k is not None and top_k > 0:
+        k = min(int(top_k), scores.shape[-1])
+        scores = scores.masked_fill(scores < torch.topk(scores, k)[0][..., -1, None], -float("inf"))
+    return torch.nn.functional.softmax(scores, dim=-1)
+
+
+def sample_next(logits: torch.Tensor, do_sample: bool = True, temperature: float = 0.3, top_k: Optional[int] = 50) -> torch.Tensor:
+    """[1, vocab] logits -> [1] token ids; `torch.multinomial` on the global RNG of the logits' device, or argmax."""
+    if not do_sample:
+        return torch.argmax(logits, dim=-1)
+    return torch.multinomial(sample_probs(logits, temperature, top_k), num_samples=1).squeeze(1)
+
+
+class _LastOnly(tuple):
+    """`hidden_states[i]` of the output object: only [-1] is materialised, and of it only the last position (all the reference reads:
+    `output_ids.hidden_states[i][-1][:, -1:]`, pipeline.py:236,242,257)."""
+
+    def __new__(cls, h, n):
+        t = super().__new__(cls, (h,))
+        t._n = n
+        return t
+
+    def __getitem__(self, i):
+        if i in (-1, self._n - 1):
+            return tuple.__getitem__(self, 0)
+        raise IndexError("only hidden_states[i][-1] (its last position) is computed on the HIP path")
+
+    def __len__(self):
+        return self._n
+
+
+class _Head:
+    """`nn.Linear` or `mlpNx_gelu` Sequential of Linears (builder.py:33-74) on ia2p_linear_small (+ ia2p_gelu between the linears)."""
+
+    def __init__(self, name, depth):
+        self.name, self.depth = name, depth
+        self.w, self.b = [None] * depth, [None] * depth
+
+    def key_slot(self, key):
+        rest = key[len(self.name) + 1:]
+        if self.depth == 1 and rest in ("weight", "bias"):
+            return 0, rest
+        m = re.match(r"^(\d+)\.(weight|bias)$", rest)
+        if not m or int(m.group(1)) % 2 or int(m.group(1)) // 2 >= self.depth:
+            raise KeyError(f"unknown parameter key '{key}'")
+        return int(m.group(1)) // 2, m.group(2)
+
+    def load(self, key, t):
+        j, what = self.key_slot(key)
+        (self.w if what == "weight" else self.b)[j] = t
+
+    def missing(self):
+        return [f"{self.name}[{j}]" for j in range(self.depth) if self.w[j] is None or self.b[j] is None]
+
+    def __call__(self, lib, x):
+        lead = x.shape[:-1]
+        h = x.reshape(-1, x.shape[-1]).to(device=self.w[0].device, dtype=torch.float16).contiguous()
+        for j in range(self.depth):
+            N, K = self.w[j].shape
+            if h.shape[1] != K:
+                raise ValueError(f"{self.name}: input width {h.shape[1]}, expected {K}")
+            out = torch.empty(h.shape[0], N, dtype=torch.float16, device=h.device)
+            for r0 in range(0, h.shape[0], 16):
+                rows = min(16, h.shape[0] - r0)
+                _ffi.check(lib.ia2p_linear_small(_ffi.current_stream(), _ffi.ptr(h[r0:r0 + rows]), _ffi.ptr(self.w[j]), _ffi.ptr(self.b[j]),
+                                                 _ffi.ptr(out[r0:r0 + rows]), rows, N, K, 0, 0))
+            if j < self.depth - 1 and out.numel():
+                _ffi.check(lib.ia2p_gelu(_ffi.current_stream(), _ffi.ptr(out), out.numel()))
+            h = out
+        return h.float().reshape(*lead, h.shape[-1])
+
+
+class HipInstructAny2PixLM:
+    PROJECTOR, PREDICTOR = "model.vae_projector_image", "model.vae_predictor_image"
+
+    def __init__(self, config: LLMConfig, device="cuda:0", max_positions: int = 1024, video_token_id: Optional[int] = None):
+        self.config = config.validate()
+        self.device = torch.device(device)
+        self.max_positions = max_positions
+        self.DEFAULT_VIDEO_TOKEN_IDX = video_token_id        # id of `<video>` (set by the tokenizer side, any2pix_arch.py:285-288)
+        self._lib = _ffi.lib()
+        self._h = C.c_void_p()
+        self._cfg_c = _ffi.make_llm_config(config)
+        _ffi.check(self._lib.ia2p_llm_create(C.byref(self._cfg_c), C.byref(self._h)), None, llm=True)
+        with torch.cuda.device(self.device):
+            self.arena = torch.zeros(self._lib.ia2p_llm_arena_bytes(self._h), dtype=torch.uint8, device=self.device)
+            self.kv = torch.zeros(self._lib.ia2p_llm_kv_bytes(self._h, max_positions), dtype=torch.uint8, device=self.device)
+        _ffi.check(self._lib.ia2p_llm_bind_arena(self._h, _ffi.ptr(self.arena), self.arena.numel()), self._h, llm=True)
+        _ffi.check(self._lib.ia2p_llm_bind_kv(self._h, _ffi.ptr(self.kv), self.kv.numel(), max_positions), self._h, llm=True)
+        d = projector_depth(config.mm_projector_type)
+        self._projector, self._predictor = _Head(self.PROJECTOR, d), _Head(self.PREDICTOR, d)
+        self._ws, self._ws_T = None, 0
+        self.dtype = torch.float16
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.ia2p_llm_destroy(self._h)
+        except Exception:
+            pass
+
+    def to(self, *a, **kw):
+        return self
+
+    def eval(self):
+        return self
+
+    def get_model(self):               # `any2pix_lm.get_model().vae_predictor_image(...)` (pipeline.py:236)
+        return self
+
+    def _check(self, st):
+        _ffi.check(st, self._h, llm=True)
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        items = state_dict.items() if hasattr(state_dict, "items") else state_dict
+        for k, v in items:
+            if k.endswith("rotary_emb.inv_freq"):          # buffer in older transformers checkpoints
+                continue
+            t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
+            if k.startswith(self.PROJECTOR + "."):
+                self._projector.load(k, t)
+            elif k.startswith(self.PREDICTOR + "."):
+                self._predictor.load(k, t)
+            else:
+                shape = (C.c_int64 * t.ndim)(*t.shape)
+                self._check(self._lib.ia2p_llm_load_tensor(self._h, k.encode(), _ffi.ptr(t), shape, t.ndim, _ffi.current_stream()))
+                torch.cuda.current_stream().synchronize()
+        if strict:
+            missing = self._projector.missing() + self._predictor.missing()
+            if missing:
+                raise KeyError(f"projector head parameters not loaded: {missing}")
+            self._check(self._lib.ia2p_llm_finalize_weights(self._h))
+
+    # ---- the two heads -----------------------------------------------------------------------------------------------
+    def vae_projector_image(self, x):
+        return self._projector(self._lib, x)
+
+    def vae_predictor_image(self, x):
+        return self._predictor(self._lib, x)
+
+    # ---- engine calls ---------------------------------------------------------------------------------------------------
+    def _workspace(self, T):
+        if self._ws is None or T > self._ws_T:
+            n = self._lib.ia2p_llm_workspace_bytes(self._h, T)
+            if n == 0:
+                self._check(2)
+            self._ws, self._ws_T = torch.empty(n, dtype=torch.uint8, device=self.device), T
+        return self._ws
+
+    def reset(self):
+        self._check(self._lib.ia2p_llm_reset(self._h))
+
+    @property
+    def position(self) -> int:
+        return self._lib.ia2p_llm_position(self._h)
+
+    def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
+        ids = ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        out = torch.empty(ids.numel(), self.config.hidden_size, dtype=torch.float16, device=self.device)
+        self._check(self._lib.ia2p_llm_embed(self._h, _ffi.current_stream(), _ffi.ptr(ids), ids.numel(), _ffi.ptr(out)))
+        return out
+
+    def _outputs(self):
+        return (torch.empty(self.config.hidden_size, dtype=torch.float32, device=self.device),
+                torch.empty(self.config.vocab_size, dtype=torch.float32, device=self.device))
+
+    @torch.no_grad()
+    def prefill(self, inputs_embeds: torch.Tensor):
+        """[T, hidden] rows at the current position -> (final-normed hidden row [hidden], logits row [vocab]) of the last one, fp32"""
+        x = inputs_embeds.to(device=self.device, dtype=torch.float16).contiguous()
+        if x.ndim != 2 or x.shape[1] != self.config.hidden_size:
+            raise ValueError("inputs_embeds must be [T, hidden]")
+        ws = self._workspace(x.shape[0])
+        hid, logits = self._outputs()
+        self._check(self._lib.ia2p_llm_prefill(self._h, _ffi.current_stream(), _ffi.ptr(x), x.shape[0], _ffi.ptr(hid), _ffi.ptr(logits),
+                                               _ffi.ptr(ws), ws.numel()))
+        return hid, logits
+
+    @torch.no_grad()
+    def decode(self, token_id: int):
+        """one row (the table embedding of token_id) at the current position -> (hidden row, logits row), fp32"""
+        ws = self._workspace(max(self._ws_T, 1))
+        hid, logits = self._outputs()
+        self._check(self._lib.ia2p_llm_decode(self._h, _ffi.current_stream(), int(token_id), _ffi.ptr(hid), _ffi.ptr(logits), _ffi.ptr(ws), ws.numel()))
+        return hid, logits
+
+    def prepare_inputs_embeds(self, input_ids: torch.Tensor, extra_replacement=None) -> torch.Tensor:
+        """`embed_tokens(input_ids)` with the modality vectors at the `<video>` positions, as any2pix_llama.py:277-291 builds them at
+        inference: with n = len(mask), the first n `<video>` positions are candidates (`a[:n]`, `b[:n]`), those whose mask entry is INPUT
+        receive `vae_projector_image(data[mask == INPUT])` in order. The reference ADDS the projection to the table embedding of `<video>`:
+        its line 289 zeroes a temporary (chained advanced indexing returns a copy), so `z + inputs_embeds` keeps the table row. Later
+        `<video>` positions -- generated ones included -- keep their table embedding alone."""
+        ids = input_ids.reshape(-1)
+        emb = self.embed_tokens(ids)
+        if extra_replacement is None:
+            return emb
+        if self.DEFAULT_VIDEO_TOKEN_IDX is None:
+            raise ValueError("extra_replacement needs video_token_id (the id of `<video>`)")
+        mask = torch.as_tensor(extra_replacement["mask"]).reshape(-1).cpu()
+        n = mask.shape[0]
+        pos = torch.where(ids.cpu() == self.DEFAULT_VIDEO_TOKEN_IDX)[0][:n]
+        if pos.shape[0] != n:
+            raise ValueError(f"{n} replacement entries for {pos.shape[0]} `<video>` tokens in the prompt")
+        sel = mask == REPLACEMENT_TYPE.INPUT
+        if sel.any():
+            z2 = self.vae_projector_image(torch.as_tensor(extra_replacement["data"])[sel])
+            rows = pos[sel].to(self.device)
+            emb[rows] = (emb[rows].float() + z2).to(torch.float16)
+        return emb
+
+    @torch.no_grad()
+    def generate(self, input_ids, extra_replacement=None, do_sample: bool = True, temperature: float = 0.3, max_new_tokens: int = 100,
+                 stopping_criteria=None, top_k: Optional[int] = 50, **unused):
+        """-> object with `.sequences` ([1, prompt + new] on the host) and `.hidden_states` (one entry per new token;
+        `hidden_states[i][-1][:, -1:]` is step i's final-normed last-position row, [1, 1, hidden] fp32 on the device)."""
+        if input_ids.ndim != 2 or input_ids.shape[0] != 1:
+            raise ValueError("input_ids must be [1, tokens] (batch 1, as the reference asserts)")
+        seq = input_ids.detach().cpu().long()
+        T = seq.shape[1]
+        if T + max_new_tokens > self.max_positions:
+            raise ValueError(f"{T} prompt tokens + {max_new_tokens} new ones do not fit {self.max_positions} cached positions")
+        emb = self.prepare_inputs_embeds(seq, extra_replacement)
+        self.reset()
+        hid, logits = self.prefill(emb)
+        nl = self.config.num_hidden_layers + 1
+        hidden_states = []
+        for step in range(max_new_tokens):
+            hidden_states.append(_LastOnly(hid.reshape(1, 1, -1), nl))
+            nxt = sample_next(logits.reshape(1, -1).cpu(), do_sample, temperature, top_k)
+            seq = torch.cat([seq, nxt.reshape(1, 1).long()], dim=1)
+            if stopping_criteria is not None and any(bool(torch.as_tensor(c(seq, None)).all()) for c in stopping_criteria):
+                break
+            if step + 1 < max_new_tokens:
+                hid, logits = self.decode(int(nxt))
+        return SimpleNamespace(sequences=seq, hidden_states=tuple(hidden_states))
+
+
+def get_all_objs(s):
+    """reference pipeline.py:281-287"""
+    matched = re.compile(r'additions:(.*)\</s\>').findall(s)
+    if not matched:
+        return []
+    return re.compile('([^:]+):<video>').findall(matched[0])
+
+
+def parse_generation(sequences, prompt_len, hidden_states, text, aux_info, mm_data, predictor, video_id, base_id, im_gen_id):
+    """pipeline.py:213-279 behind the `generate` call: -> (image_embeds, base_embed, output_caption, base_img_path, extra_data), or
+    (None, None, <text after 'ASSISTANT:'>, None, None) when no `<im_gen>` was produced. `text` = `batch_decode(sequences)[0]`;
+    `predictor` = `vae_predictor_image`; `hidden_states[i][-1][:, -1:]` = final-normed last row of step i."""
+    out_seq = sequences[:, prompt_len:]
+    assert len(hidden_states) == out_seq.shape[1]
+    flat = out_seq.reshape(-1).cpu()
+    hits = torch.where(flat == im_gen_id)[0]
+    if hits.numel() == 0:
+        return None, None, text.split("ASSISTANT:")[-1], None, None
+    im_gem_idx = hits[-1].item()
+    all_gen_tokens = torch.where(flat == video_id)[0]
+    all_gen_tokens = all_gen_tokens[all_gen_tokens > im_gem_idx]
+    gen_idx = all_gen_tokens[0]
+    remaining_tokens = all_gen_tokens[1:]
+
+    def predict(i):
+        return predictor(hidden_states[int(i)][-1][:, -1:]).detach().float().cpu()
+
+    image_embeds = predict(gen_idx)
+    extra_embeds = [predict(idx)[0] for idx in remaining_tokens]
+    extra_embeds = torch.cat(extra_embeds) if extra_embeds else torch.zeros(0, image_embeds.shape[-1])
+    if len(mm_data) == 1:
+        base_idx = 0
+        base_embed = aux_info[0]
+    else:
+        gen_idx = flat.tolist().index(base_id) + 1
+        base_embed = predict(gen_idx)[0]
+        base_idx = torch.einsum('ac,bc->ab', base_embed.float() / base_embed.norm() * 20, aux_info.float())[0].argmax().item()
+    b = mm_data[base_idx]['fname']
+    all_objs = get_all_objs(text)
+    if len(all_objs) != len(extra_embeds):
+        all_objs = []
+    extra_idx = []
+    if all_objs:
+        extra_idx = torch.einsum('ac,bc->ab', extra_embeds.float() / extra_embeds.norm() * 20, aux_info.float()).argmax(1)
+        extra_embeds = aux_info[extra_idx]
+    output_caption = re.compile(r'\[([^\]]+)\]').findall(text)[0]
+    extra_data = dict(all_objs=all_objs, extra_embeds=extra_embeds, extra_idx=extra_idx)
+    return image_embeds, base_embed, output_caption, b, extra_data

@@ -101,7 +101,13 @@ class InstructAny2PixPipeline:
                  conditioner: Optional[Callable] = None, text_encoder: Optional[Callable] = None,
                  vae_encode: Optional[Callable] = None, vae_decode: Optional[Callable] = None, clip_embeddings_dim: int = 1024,
                  refiner_unet: Optional[HipUNet2DConditionModel] = None, refiner_text_encoder: Optional[Callable] = None, prior=None,
-                 refiner_handoff: str = "image", vae=None):
+                 refiner_handoff: str = "image", vae=None, llm=None, llm_tokenizer: Optional[Callable] = None,
+                 modality_encoder: Optional[Callable] = None):
+        # llm: a HipInstructAny2PixLM (reference :117 `self.any2pix_lm`) with its tokenizer (:126 `self.any2pix_tokenizer`, injected: the
+        # sentencepiece model is checkpoint data); modality_encoder(entry) -> [1024] embedding of an mm_data entry (reference :155-166:
+        # ImageBind, which stays outside; an entry may carry its vector directly as entry["embed"])
+        self.any2pix_lm, self.any2pix_tokenizer, self.modality_encoder = llm, llm_tokenizer, modality_encoder
+        self._text_encoder, self._refiner_text_encoder = text_encoder, refiner_text_encoder
         # vae: a HipAutoencoderKL shared by every pipeline (in place of the vae_encode / vae_decode hooks): base images in, images out
         # how the base result reaches the refiner: "image" = the reference's route (decode, 8-bit image, VAE re-encode with a posterior
         # sample; needs vae_encode and vae_decode), "latent" = the sampled latents go in directly (no VAE round trip; the only route
@@ -188,6 +194,82 @@ class InstructAny2PixPipeline:
             raise ValueError("a base_image / base_img_path needs the pipeline built with vae=<HipAutoencoderKL>")
         return self.pipe_inversion._image_latents(img)
 
+    # ---- the instruction LLM (reference :151-279) ---------------------------------------------------------------------------
+    def _modality_embeds(self, mm_data):
+        """:154-168: one 1024-d vector per mm_data entry, normalised to norm 20 (host fp32, as the reference's CPU ImageBind run leaves them)"""
+        all_tensors = []
+        for r in mm_data:
+            if r.get("embed") is not None:
+                res = torch.as_tensor(r["embed"])
+            elif self.modality_encoder is not None:
+                res = self.modality_encoder(r)
+            else:
+                raise ValueError("an mm_data entry needs entry['embed'] or the pipeline built with modality_encoder=")
+            all_tensors.append(res.detach().float().cpu().reshape(1, -1))
+        if not all_tensors:
+            raise ValueError("forward_llm needs at least one mm_data entry (the reference's torch.cat of none fails the same way)")
+        aux_info = torch.cat(all_tensors)
+        return aux_info / (aux_info.norm(dim=-1, keepdim=True) + 1e-9) * 20
+
+    def _llm_special_ids(self):
+        tok = self.any2pix_tokenizer
+        return {k: tok(k, add_special_tokens=False).input_ids[0] for k in ("<video>", "<base>", "<base_null>", "<im_gen>")}
+
+    def _llm_generate(self, inst, aux_info):
+        """:171-211: prompt, stopping criterion and the one `generate` call -> (input_ids, generate output)"""
+        from .llm import KeywordsStoppingCriteria, REPLACEMENT_TYPE, VICUNA_V1_SEP2, vicuna_v1_prompt
+        extra_replacement = {"data": aux_info, "mask": torch.tensor([REPLACEMENT_TYPE.INPUT] * aux_info.shape[0], dtype=torch.long)}
+        prompt = vicuna_v1_prompt(inst)
+        input_ids = self.any2pix_tokenizer(prompt, return_tensors="pt").input_ids
+        stopping_criteria = KeywordsStoppingCriteria([VICUNA_V1_SEP2], self.any2pix_tokenizer, input_ids)
+        lm = self.any2pix_lm
+        if lm.DEFAULT_VIDEO_TOKEN_IDX is None:
+            lm.DEFAULT_VIDEO_TOKEN_IDX = self._llm_special_ids()["<video>"]
+        lm.eval()
+        out = lm.generate(input_ids, images=None, do_sample=True, temperature=0.3, max_new_tokens=100, output_hidden_states=True, use_cache=False,
+                          return_dict_in_generate=True, extra_replacement=extra_replacement, stopping_criteria=[stopping_criteria])
+        return input_ids, out
+
+    def forward_llm(self, inst, mm_data=[], use_cache=False):
+        """-> (image_embeds, base_embed, output_caption, base_img_path, extra_data); (None, None, text, None, None) without an `<im_gen>`"""
+        if use_cache:
+            return self.cache
+        if self.any2pix_lm is None or self.any2pix_tokenizer is None:
+            raise NotImplementedError("forward_llm needs the pipeline built with llm=<HipInstructAny2PixLM> and llm_tokenizer=")
+        from .llm import parse_generation
+        aux_info = self._modality_embeds(mm_data)
+        input_ids, out = self._llm_generate(inst, aux_info)
+        ids = self._llm_special_ids()
+        tp = self.any2pix_tokenizer.batch_decode(out.sequences)
+        return parse_generation(out.sequences, input_ids.shape[1], out.hidden_states, tp[0], aux_info, mm_data,
+                                self.any2pix_lm.get_model().vae_predictor_image, ids["<video>"], ids["<base>"], ids["<im_gen>"])
+
+    def _condition_from_llm(self, inst, mm_data, use_cache, llm_only):
+        """the conditioning dict a `conditioner=` would return, from forward_llm + the attached text encoders (:309-310, :330, :342-345, :358-361)"""
+        image_embeds, base_embed, output_caption, base_img_path, extra_data = self.forward_llm(inst, mm_data, use_cache=use_cache)
+        self.cache = image_embeds, base_embed, output_caption, base_img_path, extra_data
+        c = dict(image_embeds=image_embeds, base_embed=base_embed, caption=output_caption, base_img_path=base_img_path, extra_data=extra_data)
+        if llm_only:
+            return c
+        if image_embeds is None:
+            raise RuntimeError(f"the LLM produced no <im_gen>: {output_caption!r}")
+        if self._text_encoder is None:
+            raise ValueError("a pipeline built with llm= needs text_encoder=<encode_prompt callable> for the denoise stages")
+        c["image_embeds"], c["base_embed"] = image_embeds.reshape(1, -1), base_embed.reshape(1, -1)      # host fp32, as the reference holds them (:236, :253)
+        for e in mm_data:
+            if e.get("fname") == base_img_path and e.get("image") is not None:
+                c["base_image"] = e["image"]
+        pe, ne, pp, npl = self._text_encoder(prompt="best quality, high quality" + output_caption, negative_prompt="", do_classifier_free_guidance=True)
+        ipe, _, ipp, _ = self._text_encoder(prompt="", do_classifier_free_guidance=False)
+        c.update(prompt_embeds=pe, pooled_prompt_embeds=pp, negative_prompt_embeds=ne, negative_pooled_prompt_embeds=npl,
+                 inv_prompt_embeds=ipe, inv_pooled_prompt_embeds=ipp)
+        if self._refiner_text_encoder is not None:
+            rpe, rne, rpp, rnp = self._refiner_text_encoder(prompt=output_caption + ",high quality,well-formed,award-winning", negative_prompt="",
+                                                            do_classifier_free_guidance=True)
+            c.update(refiner_prompt_embeds=rpe, refiner_pooled_prompt_embeds=rpp, refiner_negative_prompt_embeds=rne,
+                     refiner_negative_pooled_prompt_embeds=rnp)
+        return c
+
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
                  use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent") -> Any:
@@ -197,15 +279,20 @@ class InstructAny2PixPipeline:
             raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
         if output_type != "latent" and self.vae is None:
             raise ValueError(f"output_type={output_type!r} needs the pipeline built with vae=<HipAutoencoderKL>")
-        if self.conditioner is None:
+        if self.conditioner is None and self.any2pix_lm is not None:
+            c = self._condition_from_llm(inst, mm_data, use_cache, llm_only)
+            if llm_only:
+                return None, None, c["caption"]
+        elif self.conditioner is None:
             raise NotImplementedError("the LLM / ImageBind / prior stages are outside the denoise hot path (SURVEY.md §8): construct with "
                                       "conditioner=<callable returning dict(image_embeds, base_embed, y, caption, base_latents, "
                                       "prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds)> "
                                       "or call .denoise() with explicit conditioning")
-        c = self.conditioner(inst, mm_data, use_cache=use_cache)
-        self.cache = c
-        if llm_only:
-            return None, None, c["caption"]
+        else:
+            c = self.conditioner(inst, mm_data, use_cache=use_cache)
+            self.cache = c
+            if llm_only:
+                return None, None, c["caption"]
         y0 = c.get("y")
         if y0 is None:                                                                         # :313-317, the prior's one live call
             if self.model is None:

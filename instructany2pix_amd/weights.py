@@ -408,3 +408,49 @@ def prior_param_specs(gpt_cfg, clip_cfg, sequence_input_embed_dim=(0, 1024, 1024
     s += [("cond_stage_models.0.model." + k, shp, kind) for k, shp, kind in clip_param_specs(clip_cfg)]
     s += gpt2_param_specs(gpt_cfg, "model.")
     return s
+
+
+# ---- instruction LLM (transformers LlamaForCausalLM + the two projector heads of InstructAny2PixLMMetaModel) -----------------
+def projector_depth(projector_type: str) -> int:
+    """`linear` -> 1, `mlpNx_gelu` -> N (llm/model/multimodal_projector/builder.py:33-74)"""
+    import re
+    if projector_type == "linear":
+        return 1
+    m = re.match(r"^mlp(\d+)x_gelu$", projector_type)
+    if not m or int(m.group(1)) < 1:
+        raise ValueError(f"Unknown projector type: {projector_type}")
+    return int(m.group(1))
+
+
+def llm_head_specs(cfg, embed_dim: int = 1024, projector_type: str = "linear") -> List[Spec]:
+    """`model.vae_projector_image` (embedding -> hidden) and `model.vae_predictor_image` (hidden -> embedding): an `nn.Linear`, or an
+    `nn.Sequential` whose Linear modules sit at the even (projector) / even (predictor) indices with `nn.GELU()` between them."""
+    H, d = cfg.hidden_size, projector_depth(projector_type)
+    if d == 1:
+        return [("model.vae_projector_image.weight", (H, embed_dim), "w"), ("model.vae_projector_image.bias", (H,), "b"),
+                ("model.vae_predictor_image.weight", (embed_dim, H), "w"), ("model.vae_predictor_image.bias", (embed_dim,), "b")]
+    s: List[Spec] = []
+    for j in range(d):
+        s += [(f"model.vae_projector_image.{2 * j}.weight", (H, embed_dim if j == 0 else H), "w"), (f"model.vae_projector_image.{2 * j}.bias", (H,), "b")]
+    for j in range(d):
+        o = embed_dim if j == d - 1 else H
+        s += [(f"model.vae_predictor_image.{2 * j}.weight", (o, H), "w"), (f"model.vae_predictor_image.{2 * j}.bias", (o,), "b")]
+    return s
+
+
+def llama_param_specs(cfg) -> List[Spec]:
+    """transformers `LlamaForCausalLM.state_dict()` keys and shapes"""
+    H, I = cfg.hidden_size, cfg.intermediate_size
+    s: List[Spec] = [("model.embed_tokens.weight", (cfg.vocab_size, H), "emb")]
+    for i in range(cfg.num_hidden_layers):
+        p = f"model.layers.{i}."
+        s += [(p + "self_attn.q_proj.weight", (H, H), "w"), (p + "self_attn.k_proj.weight", (H, H), "w"), (p + "self_attn.v_proj.weight", (H, H), "w"),
+              (p + "self_attn.o_proj.weight", (H, H), "w_res"),
+              (p + "mlp.gate_proj.weight", (I, H), "w"), (p + "mlp.up_proj.weight", (I, H), "w"), (p + "mlp.down_proj.weight", (H, I), "w_res"),
+              (p + "input_layernorm.weight", (H,), "gamma"), (p + "post_attention_layernorm.weight", (H,), "gamma")]
+    s += [("model.norm.weight", (H,), "gamma"), ("lm_head.weight", (cfg.vocab_size, H), "w")]
+    return s
+
+
+def llm_param_specs(cfg, embed_dim: int = 1024, projector_type: str = "linear") -> List[Spec]:
+    return llama_param_specs(cfg) + llm_head_specs(cfg, embed_dim, projector_type)

@@ -1,0 +1,228 @@
+"""Host side of the LLM stage without a GPU: prompt, stopping criterion, sampling arithmetic, the parsing half of `forward_llm`, and the
+argument / state checks of the ia2p_llm_* ABI (none of which reaches a HIP call)."""
+import ctypes as C
+import json
+import os
+import sys
+
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return json.load(open(os.path.join(HERE, "golden", "llm_host.json")))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from instructany2pix_amd import build, _ffi
+    build.build(verbose=False)
+    return _ffi.lib()
+
+
+def test_prompt_matches_reference_conversation(gold):
+    from instructany2pix_amd.llm import VICUNA_V1_SEP2, vicuna_v1_prompt
+    assert len(gold["prompts"]) == 3
+    for rec in gold["prompts"]:
+        assert vicuna_v1_prompt(rec["inst"]) == rec["prompt"]
+    assert VICUNA_V1_SEP2 == gold["stop_str"]
+
+
+def test_get_all_objs_matches_reference(gold):
+    from instructany2pix_amd.llm import get_all_objs
+    assert len(gold["objs"]) == 4
+    for rec in gold["objs"]:
+        assert get_all_objs(rec["text"]) == rec["objs"]
+
+
+def test_sampling_step_is_transformers_warpers():
+    from transformers import TemperatureLogitsWarper, TopKLogitsWarper
+    from instructany2pix_amd.llm import sample_next, sample_probs
+    g = torch.Generator().manual_seed(5)
+    for vocab, scale in ((512, 3.0), (32003, 6.0), (40, 1.0)):      # (40 < top_k: the warper clamps k to the vocabulary)
+        logits = torch.randn(1, vocab, generator=g) * scale
+        ids = torch.zeros(1, 4, dtype=torch.long)
+        ref = TopKLogitsWarper(50)(ids, TemperatureLogitsWarper(0.3)(ids, logits.clone()))
+        ref = torch.nn.functional.softmax(ref, dim=-1)
+        got = sample_probs(logits, 0.3, 50)
+        assert torch.equal(got, ref)
+        assert int((got > 0).sum()) <= 50
+        torch.manual_seed(11)
+        want = torch.multinomial(ref, num_samples=1).squeeze(1)
+        torch.manual_seed(11)
+        assert torch.equal(sample_next(logits, True, 0.3, 50), want)
+        assert torch.equal(sample_next(logits, False), logits.argmax(-1))
+    # top_k=None: temperature only
+    assert torch.equal(sample_probs(logits, 0.3, None), torch.nn.functional.softmax(logits / 0.3, dim=-1))
+
+
+def test_keywords_stopping_criteria():
+    from transformers import StoppingCriteria, StoppingCriteriaList
+    from stub_llm_tokenizer import StubLlamaTokenizer
+    from instructany2pix_amd.llm import KeywordsStoppingCriteria
+    tok = StubLlamaTokenizer()
+    prompt = tok("USER: hello ASSISTANT:", return_tensors="pt").input_ids
+    crit = KeywordsStoppingCriteria(["</s>"], tok, prompt)
+    assert isinstance(crit, StoppingCriteria)
+    assert crit.start_len == prompt.shape[1] and crit.max_keyword_len == 1 and crit.keyword_ids[0].tolist() == [2]      # BOS stripped
+    words = tok("a blue fox", add_special_tokens=False).input_ids
+    seq = torch.cat([prompt, torch.tensor([words])], dim=1)
+    assert crit(seq, None) is False
+    assert not bool(torch.as_tensor(StoppingCriteriaList([crit])(seq, None)).all())
+    done = torch.cat([seq, torch.tensor([[2]])], dim=1)
+    assert crit(done, None) is True
+    assert bool(torch.as_tensor(StoppingCriteriaList([crit])(done, None)).all())
+    # a keyword that is ordinary text is found in the decoded tail
+    crit2 = KeywordsStoppingCriteria(["fox"], tok, prompt)
+    assert crit2(seq, None) is True and crit2(seq[:, :-1], None) is False
+    with pytest.raises(AssertionError):
+        crit.call_bse(torch.cat([seq, seq]), None)
+
+
+class _LinearPredictor:
+    def __init__(self, W):
+        self.W = W
+
+    def __call__(self, x):
+        return x.float() @ self.W.t()
+
+
+def _scripted(tokens, H=16, seed=0):
+    """sequences [1, 3 + n] and one hidden-state entry per generated token (entry i: a tuple whose [-1] is [1, 1, H])"""
+    g = torch.Generator().manual_seed(seed)
+    seq = torch.tensor([[1, 7, 8] + tokens])
+    hs = tuple((None, torch.randn(1, 1, H, generator=g)) for _ in tokens)
+    return seq, hs
+
+
+VIDEO, BASE, IM_GEN, EOS = 509, 510, 504, 2
+
+
+def test_parse_generation_single_entry():
+    from instructany2pix_amd.llm import parse_generation
+    g = torch.Generator().manual_seed(1)
+    W = torch.randn(8, 16, generator=g)
+    aux = torch.randn(1, 8, generator=g)
+    seq, hs = _scripted([20, 21, IM_GEN, VIDEO, EOS])
+    text = "<s> USER: x ASSISTANT: [a blue fox] <im_gen> <video></s>"
+    ie, be, cap, path, extra = parse_generation(seq, 3, hs, text, aux, [{"type": "image", "fname": "a.png"}], _LinearPredictor(W), VIDEO, BASE, IM_GEN)
+    assert cap == "a blue fox" and path == "a.png"
+    assert torch.equal(be, aux[0])                                   # one entry: base = entry 0
+    assert ie.shape == (1, 1, 8) and torch.allclose(ie, hs[3][-1] @ W.t())      # the row that PREDICTED the <video> after <im_gen>
+    assert extra["all_objs"] == [] and extra["extra_embeds"].shape == (0, 8) and extra["extra_idx"] == []
+
+
+def test_parse_generation_three_entries_base_rule_and_subjects():
+    from instructany2pix_amd.llm import parse_generation
+    g = torch.Generator().manual_seed(2)
+    W = torch.randn(8, 16, generator=g)
+    aux = torch.randn(3, 8, generator=g)
+    aux = aux / aux.norm(dim=-1, keepdim=True) * 20
+    #          0     1     2    3       4      5    6      7   8      9
+    tokens = [BASE, VIDEO, 30, IM_GEN, VIDEO, 31, VIDEO, 32, VIDEO, EOS]
+    seq, hs = _scripted(tokens)
+    mm = [{"type": "image", "fname": f"{i}.png"} for i in range(3)]
+    text = "<s> USER: x ASSISTANT: [a fox and a dog] <base><video> <im_gen><video> additions: fox:<video>, dog:<video></s>"
+    ie, be, cap, path, extra = parse_generation(seq, 3, hs, text, aux, mm, _LinearPredictor(W), VIDEO, BASE, IM_GEN)
+    assert cap == "a fox and a dog"
+    assert torch.allclose(ie, hs[4][-1] @ W.t())
+    want_base = (hs[1][-1] @ W.t())[0]                                # the step after <base>
+    assert torch.allclose(be, want_base)
+    idx = (want_base / want_base.norm() * 20 @ aux.t())[0].argmax().item()
+    assert path == f"{idx}.png"
+    assert extra["all_objs"] == [" fox", ", dog"]
+    ee = torch.cat([(hs[6][-1] @ W.t())[0], (hs[8][-1] @ W.t())[0]])
+    want_idx = (ee / ee.norm() * 20 @ aux.t()).argmax(1)
+    assert torch.equal(extra["extra_idx"], want_idx) and torch.equal(extra["extra_embeds"], aux[want_idx])
+    # subject count mismatch (one name, two <video> rows): all_objs emptied, the raw predicted rows are kept
+    text2 = "<s> USER: x ASSISTANT: [a fox and a dog] <base><video> <im_gen><video> additions: fox:<video></s>"
+    _, _, _, _, extra2 = parse_generation(seq, 3, hs, text2, aux, mm, _LinearPredictor(W), VIDEO, BASE, IM_GEN)
+    assert extra2["all_objs"] == [] and extra2["extra_idx"] == [] and torch.allclose(extra2["extra_embeds"], ee)
+
+
+def test_parse_generation_without_im_gen():
+    from instructany2pix_amd.llm import parse_generation
+    seq, hs = _scripted([20, 21, EOS])
+    out = parse_generation(seq, 3, hs, "<s> USER: x ASSISTANT: I cannot do that</s>", torch.zeros(1, 8), [{"fname": "a"}], None, VIDEO, BASE, IM_GEN)
+    assert out == (None, None, " I cannot do that</s>", None, None)
+
+
+def _cfg(**kw):
+    from instructany2pix_amd import _ffi
+    from instructany2pix_amd.config import LLMConfig
+    c = LLMConfig(vocab_size=64, hidden_size=256, num_hidden_layers=1, num_attention_heads=2, intermediate_size=128)
+    cc = _ffi.make_llm_config(c.validate())
+    for k, v in kw.items():
+        setattr(cc, k, v)
+    return cc
+
+
+def test_llm_abi_refuses_shapes(lib):
+    h = C.c_void_p()
+    for kw, word in ((dict(num_heads=4, num_kv_heads=4), b"head dim 128"), (dict(num_kv_heads=1), b"key/value heads"),
+                     (dict(hidden_size=288, num_heads=2), b"multiple of 64"), (dict(intermediate_size=100), b"intermediate")):
+        assert lib.ia2p_llm_create(C.byref(_cfg(**kw)), C.byref(h)) == 2, kw
+        assert not h.value and word in lib.ia2p_llm_last_error(None), lib.ia2p_llm_last_error(None)
+    assert lib.ia2p_llm_create(None, C.byref(h)) == 1
+    assert lib.ia2p_llm_create(C.byref(_cfg()), None) == 1
+
+
+def test_llm_abi_sizes_and_state(lib):
+    from instructany2pix_amd import _ffi
+    from instructany2pix_amd.config import tiny_llm, vicuna_7b
+    from instructany2pix_amd.weights import llama_param_specs, param_count
+    cfg = vicuna_7b(32000)
+    h = C.c_void_p()
+    _ffi.check(lib.ia2p_llm_create(C.byref(_ffi.make_llm_config(cfg)), C.byref(h)), None, llm=True)
+    n = param_count(llama_param_specs(cfg))
+    assert 6.7e9 < n < 6.8e9
+    assert 2 * n <= lib.ia2p_llm_arena_bytes(h) <= 2 * n * 1.01
+    assert lib.ia2p_llm_kv_bytes(h, 1024) == 2 * 32 * 1024 * 4096 * 2
+    assert lib.ia2p_llm_kv_bytes(h, 0) == 0 and lib.ia2p_llm_kv_bytes(h, 8193) == 0 and lib.ia2p_llm_kv_bytes(None, 16) == 0
+    lib.ia2p_llm_destroy(h)
+
+    h = C.c_void_p()
+    _ffi.check(lib.ia2p_llm_create(C.byref(_ffi.make_llm_config(tiny_llm())), C.byref(h)), None, llm=True)
+    assert lib.ia2p_llm_position(h) == 0 and lib.ia2p_llm_position(None) == -1
+    ws64, ws8 = lib.ia2p_llm_workspace_bytes(h, 64), lib.ia2p_llm_workspace_bytes(h, 8)      # a host dry run
+    assert ws64 > ws8 > 0 and lib.ia2p_llm_workspace_bytes(h, 0) == 0
+    one = C.c_void_p(256)           # never dereferenced: every call below is refused before any HIP call
+    # null arguments
+    assert lib.ia2p_llm_bind_arena(h, None, 1 << 20) == 1
+    assert lib.ia2p_llm_bind_kv(h, None, 1 << 20, 16) == 1
+    assert lib.ia2p_llm_prefill(h, None, None, 4, one, one, one, 1 << 20) == 1
+    assert lib.ia2p_llm_decode(h, None, 3, None, one, one, 1 << 20) == 1
+    assert lib.ia2p_llm_embed(h, None, None, 4, one) == 1
+    assert lib.ia2p_llm_reset(None) == 1
+    assert lib.ia2p_llm_gemv(None, None, one, one, 8, 8) == 1 and lib.ia2p_llm_gemv(None, one, one, one, 8, 12) == 2
+    assert lib.ia2p_gelu(None, None, 8) == 1 and lib.ia2p_gelu(None, one, 0) == 2
+    # wrong state: nothing bound, nothing loaded
+    assert lib.ia2p_llm_load_tensor(h, b"model.norm.weight", one, (C.c_int64 * 1)(512), 1, None) == 4
+    assert lib.ia2p_llm_finalize_weights(h) == 4
+    assert lib.ia2p_llm_prefill(h, None, one, 4, one, one, one, 1 << 20) == 4
+    assert lib.ia2p_llm_decode(h, None, 3, one, one, one, 1 << 20) == 4
+    assert b"finalized" in lib.ia2p_llm_last_error(h)
+    assert lib.ia2p_llm_embed(h, None, one, 4, one) == 4
+    # cache too small / too many positions
+    assert lib.ia2p_llm_bind_kv(h, one, 16, 16) == 5
+    assert lib.ia2p_llm_bind_kv(h, one, 1 << 40, 8193) == 2
+    with pytest.raises(_ffi.IA2PError):
+        _ffi.check(lib.ia2p_llm_finalize_weights(h), h, llm=True)
+    lib.ia2p_llm_destroy(h)
+
+
+def test_llm_param_specs_cover_the_checkpoint_keys():
+    from instructany2pix_amd.config import tiny_llm
+    from instructany2pix_amd.weights import llm_param_specs, synthetic_state_dict
+    cfg = tiny_llm()
+    sd = synthetic_state_dict(llm_param_specs(cfg, 1024, "linear"))
+    assert sd["model.vae_projector_image.weight"].shape == (512, 1024) and sd["model.vae_predictor_image.bias"].shape == (1024,)
+    assert sd["model.layers.3.mlp.down_proj.weight"].shape == (512, 1408) and sd["lm_head.weight"].shape == (512, 512)
+    keys = [k for k, _, _ in llm_param_specs(cfg, 1024, "mlp2x_gelu")]
+    assert "model.vae_projector_image.0.weight" in keys and "model.vae_projector_image.2.bias" in keys and "model.vae_predictor_image.2.weight" in keys
+    with pytest.raises(ValueError):
+        llm_param_specs(cfg, 1024, "identity")

@@ -1,9 +1,13 @@
 """End-to-end latency of ONE edit request at the reference's own defaults, every model at full size with seeded synthetic weights:
 1024x1024 image, num_inference_steps=25, cfg=10, refinement=0.5 (reference pipeline.py:303-386). A seeded synthetic PIL image goes in and PIL
-images come out (`output_type="pil"`); everything downstream of the LLM / ImageBind stage runs on the HIP path: image in (8-bit codec) -> VAE
+images come out (`output_type="pil"`); everything downstream of ImageBind runs on the HIP path: instruction LLM -> image in (8-bit codec) -> VAE
 encode -> embedding prior (CLIP ViT-H text + GPT-2 medium) -> encode_prompt (CLIP-L + bigG) -> 25-step DDIM inversion (B=1) -> polar mixing
 -> 25-step IP-Adapter guided CFG sampling (B_eff=2) -> VAE decode + 8-bit hand-over -> SDXL-refiner img2img (strength 0.5 of 50 steps, CFG)
--> VAE decode -> image out (8-bit codec, uint8 back to the host). The LLM / ImageBind outputs (1024-d embeddings, caption) are stand-ins: that stage is out of scope.
+-> VAE decode -> image out (8-bit codec, uint8 back to the host). The request's conditioning comes from `forward_llm`: the instruction LLM at full
+size (Vicuna-7B shape) prefills the prompt and generates 100 tokens on the HIP engine, `vae_predictor_image` reads the hidden rows. Two stand-ins
+remain: the ImageBind vectors of the mm_data entries are seeded 1024-d noise (ImageBind stays outside), and, because synthetic weights cannot
+speak, the TOKEN CHOSEN at each step follows a script ("[ caption ] <base> <video> <im_gen> <video> </s>", 100 tokens) instead of the sampled one; every step's
+engine work, its logits and its sampling arithmetic still run.
 Prints per-stage wall times (stream-synchronised) after one warm-up request."""
 import os
 import sys
@@ -22,7 +26,10 @@ from instructany2pix_amd.unet import HipUNet2DConditionModel
 from instructany2pix_amd.vae import HipAutoencoderKL
 from instructany2pix_amd.weights import (unet_param_specs, ip_adapter_specs, vae_param_specs, clip_param_specs, prior_param_specs,
                                          iter_synthetic, synthetic_state_dict)
-from instructany2pix_amd.config import gpt2_medium, laion_clip_h_text
+from instructany2pix_amd.config import gpt2_medium, laion_clip_h_text, vicuna_7b
+import instructany2pix_amd.llm as llm_mod
+from instructany2pix_amd.weights import llm_param_specs
+from stub_llm_tokenizer import ADDED_TOKENS, StubLlamaTokenizer
 
 DEV = "cuda:0"
 PX = int(os.environ.get("PX", 1024))
@@ -40,7 +47,11 @@ prior = InstructAny2PixPrior(**prior_config, device=DEV, tokenizer=StubTokenizer
 prior.load_state_dict(synthetic_state_dict(prior_param_specs(gpt2_medium(), laion_clip_h_text()), seed=47))
 specs = ip_adapter_specs(bcfg, 1024)
 ck = {"image_proj": synthetic_state_dict(specs["image_proj"], seed=7), "ip_adapter": synthetic_state_dict(specs["ip_adapter"], seed=7)}
-print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior)", flush=True)
+lcfg = vicuna_7b(32000 + len(ADDED_TOKENS))
+ltok = StubLlamaTokenizer(32000)
+lm = llm_mod.HipInstructAny2PixLM(lcfg, DEV, max_positions=512)
+lm.load_state_dict(iter_synthetic(llm_param_specs(lcfg), 9, DEV, torch.float16))
+print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior, LLM)", flush=True)
 
 stages = {}
 
@@ -54,21 +65,24 @@ def timed(name, fn):
 
 g = torch.Generator().manual_seed(1)
 image = PIL.Image.fromarray(np.random.default_rng(1).integers(0, 256, size=(PX, PX, 3), dtype=np.uint8))      # the base image (reference: loas_base_img)
-image_embeds, base_embed = torch.randn(1, 1024, generator=g), torch.randn(1, 1024, generator=g)      # stand-ins for the LLM / ImageBind stage
-caption = "a watercolor painting of a fox in the snow"
+# the scripted reply: 100 tokens, "[ <93 caption words> ] <base> <video> <im_gen> <video> </s>" (two mm_data entries: the base image is chosen by the `<base>` rule)
+SCRIPT = ltok("[ " + " ".join(f"word{i}" for i in range(93)) + " ] <base> <video> <im_gen> <video> </s>", add_special_tokens=False).input_ids
+assert len(SCRIPT) == 100
+_sample_next, _script = llm_mod.sample_next, iter(())
 
 
-def conditioner(inst, mm, use_cache=False):
-    pe, ne, pp, npl = timed("encode_prompt(base)", lambda: enc.encode_prompt(prompt=caption, negative_prompt="", do_classifier_free_guidance=True))
-    ipe, _, ipp, _ = timed("encode_prompt(inversion '')", lambda: enc.encode_prompt(prompt="", do_classifier_free_guidance=False))
-    rpe, rne, rpp, rnp = timed("encode_prompt(refiner)", lambda: enc_ref.encode_prompt(prompt=caption + ",high quality,well-formed,award-winning", negative_prompt="", do_classifier_free_guidance=True))
-    return dict(image_embeds=image_embeds, base_embed=base_embed, caption=caption, base_image=image, prompt_embeds=pe, pooled_prompt_embeds=pp,
-                negative_prompt_embeds=ne, negative_pooled_prompt_embeds=npl, inv_prompt_embeds=ipe, inv_pooled_prompt_embeds=ipp,
-                refiner_prompt_embeds=rpe, refiner_pooled_prompt_embeds=rpp, refiner_negative_prompt_embeds=rne, refiner_negative_pooled_prompt_embeds=rnp)
+def scripted_sample_next(logits, *a, **k):
+    _sample_next(logits, *a, **k)                       # the sampling arithmetic of the step still runs (and draws from the RNG)
+    return torch.tensor([next(_script)])
 
 
-pipe = InstructAny2PixPipeline(unet=base, ip_ckpt=ck, device=DEV, clip_embeddings_dim=1024, conditioner=conditioner, refiner_unet=ref, prior=prior,
-                               vae=vae)
+llm_mod.sample_next = scripted_sample_next
+mm_data = [{"type": "image", "fname": "base.png", "image": image, "embed": torch.randn(1024, generator=g)},
+           {"type": "image", "fname": "style.png", "image": image, "embed": torch.randn(1024, generator=g)}]      # (either may be chosen as the base)
+pipe = InstructAny2PixPipeline(unet=base, ip_ckpt=ck, device=DEV, clip_embeddings_dim=1024, refiner_unet=ref, prior=prior, vae=vae,
+                               llm=lm, llm_tokenizer=ltok,
+                               text_encoder=lambda **k: timed("encode_prompt(base, inversion '')", lambda: enc.encode_prompt(**k)),
+                               refiner_text_encoder=lambda **k: timed("encode_prompt(refiner)", lambda: enc_ref.encode_prompt(**k)))
 if os.environ.get("TUNE", "1") == "1":      # measure kernel plans for the three UNet shapes of a request (what bench.py does for its shape)
     t0 = time.perf_counter()
     h = PX // 8
@@ -91,6 +105,7 @@ _wrap(pipe.pipe_inversion, "_vae_encode", "vae_encode")
 _wrap(pipe.pipe, "_vae_decode", "vae_decode (hand-over + 2 outputs)")
 _wrap(pipe.pipe.image_processor, "postprocess", "image_out")
 _wrap(pipe.ip_adapter_xl, "generate", "guided sampling loop (25 x B_eff=2, incl. image-token projection)")
+_wrap(pipe, "forward_llm", "LLM (forward_llm: prefill + 100 tokens + predictor heads)")
 if getattr(pipe, "model", None) is not None:
     _wrap(pipe.model, "generate_diffusion", "embedding prior")
 _piperf_call = pipe.piperf.__call__
@@ -100,8 +115,9 @@ _wrap(pipe.piperf, "_vae_encode", "vae_encode (refiner hand-over)")
 for rnd in range(2):            # request 0 warms up (workspaces, kernel plans from the cost model), request 1 is reported
     stages.clear()
     torch.manual_seed(3)
+    _script = iter(SCRIPT)
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    non_refined, refined, msg = pipe("turn the fox blue", [], num_inference_steps=25, cfg=10, refinement=0.5, output_type="pil")
+    non_refined, refined, msg = pipe("add <video> to <video> and turn the fox blue", mm_data, num_inference_steps=25, cfg=10, refinement=0.5, output_type="pil")
     torch.cuda.synchronize(); total = (time.perf_counter() - t0) * 1e3
     assert msg == "SUCCESS!" and all(isinstance(o, list) and o[0].size == (PX, PX) and o[0].mode == "RGB" for o in (non_refined, refined))
     print(f"request {rnd}: {total:.0f} ms total; stages (ms): " + ", ".join(f"{k} {v:.1f}" for k, v in stages.items())

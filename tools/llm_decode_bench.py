@@ -1,0 +1,115 @@
+"""Decode speed of the instruction LLM at full size (Vicuna-7B shape, seeded synthetic weights), and the decode GEMV against the only kernel
+the library had for M = 1, `ia2p_linear_small`.
+
+  part 1  prompt of 64 rows, 100 decode tokens (teacher-forced ids: the time of a token does not depend on which one it is), after one
+          warm-up request; stream-synchronised wall time. Prints the prefill time, ms per token, weight bytes per token / that time in TB/s
+          and its fraction of the 6.29 TB/s copy rate (MI355X_MICROARCH.md). The weight bytes are what one token must read: the 32 layers'
+          projections and the lm_head, counted from the shapes (norm weights, the KV cache and the activations are left out).
+  part 2  the four layer shapes N x K = 12288 x 4096 (fused QKV), 4096 x 4096, 22016 x 4096 (fused gate/up), 4096 x 11008: `ia2p_llm_gemv`
+          and `ia2p_linear_small` (M = 1) in the same process, interleaved, each launch on another copy of the weights out of a pool larger
+          than the 256 MiB Infinity Cache so both read from HBM; device events around one pass over the pool; median of REPS repetitions.
+
+    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--skip-decode] [--skip-gemv]
+"""
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from instructany2pix_amd import _ffi
+from instructany2pix_amd.config import vicuna_7b
+from instructany2pix_amd.llm import HipInstructAny2PixLM
+from instructany2pix_amd.weights import iter_synthetic, llm_param_specs
+
+DEV = "cuda:0"
+COPY_RATE = 6.29e12
+
+
+def decode_part(layers, tokens):
+    cfg = vicuna_7b(32000)
+    cfg.num_hidden_layers = layers
+    t0 = time.perf_counter()
+    lm = HipInstructAny2PixLM(cfg, DEV, max_positions=256)
+    lm.load_state_dict(iter_synthetic(llm_param_specs(cfg), 7, DEV, torch.float16))
+    torch.cuda.synchronize()
+    print(f"model ready in {time.perf_counter() - t0:.1f} s ({layers} layers, arena {lm.arena.numel() / 1e9:.2f} GB)", flush=True)
+    H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
+    wbytes = 2 * (layers * (4 * H * H + 3 * H * I) + V * H)
+    g = torch.Generator().manual_seed(1)
+    prompt = torch.randint(3, V, (64,), generator=g)
+    nxt = torch.randint(3, V, (tokens,), generator=g).tolist()
+    for rnd in range(2):           # request 0 warms up
+        lm.reset()
+        emb = lm.embed_tokens(prompt)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        lm.prefill(emb)
+        torch.cuda.synchronize(); t1 = time.perf_counter()
+        for t in nxt:
+            lm.decode(t)
+        torch.cuda.synchronize(); t2 = time.perf_counter()
+        ms = (t2 - t1) * 1e3 / tokens
+        print(f"request {rnd}: prefill(64) {(t1 - t0) * 1e3:.2f} ms; decode {ms:.3f} ms per token over {tokens} tokens; "
+              f"{wbytes / 1e9:.2f} GB of weights per token -> {wbytes / (ms * 1e-3) / 1e12:.2f} TB/s = {wbytes / (ms * 1e-3) / COPY_RATE:.3f} of the copy rate",
+              flush=True)
+    del lm
+    torch.cuda.empty_cache()
+
+
+def gemv_part(reps):
+    lib = _ffi.lib()
+    g = torch.Generator(device=DEV).manual_seed(2)
+    print("GEMV vs linear_small, M = 1, weights cycled through a pool > 256 MiB, median us per launch:")
+    for N, K in ((12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008)):
+        nbytes = N * K * 2
+        copies = max(4, -(-(640 << 20) // nbytes))
+        pool = [(torch.randn(N, K, generator=g, device=DEV, dtype=torch.float32) * K ** -0.5).half() for _ in range(copies)]
+        x16 = torch.randn(1, K, generator=g, device=DEV).half()
+        x32 = x16.float().reshape(-1).contiguous()
+        o16 = torch.empty(1, N, dtype=torch.float16, device=DEV)
+        o32 = torch.empty(N, dtype=torch.float32, device=DEV)
+        s = _ffi.current_stream()
+
+        def run_gemv():
+            for w in pool:
+                _ffi.check(lib.ia2p_llm_gemv(s, _ffi.ptr(w), _ffi.ptr(x32), _ffi.ptr(o32), N, K))
+
+        def run_small():
+            for w in pool:
+                _ffi.check(lib.ia2p_linear_small(s, _ffi.ptr(x16), _ffi.ptr(w), None, _ffi.ptr(o16), 1, N, K, 0, 0))
+
+        run_gemv(); run_small()
+        torch.cuda.synchronize()
+        err = float((o32 - o16.float().reshape(-1)).abs().max())
+        times = {"gemv": [], "small": []}
+        for _ in range(reps):
+            for name, fn in (("gemv", run_gemv), ("small", run_small)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); fn(); e1.record()
+                e1.synchronize()
+                times[name].append(e0.elapsed_time(e1) * 1e3 / copies)
+        a, b = statistics.median(times["gemv"]), statistics.median(times["small"])
+        print(f"  {N:6d} x {K:5d} ({nbytes / 1e6:6.1f} MB, pool of {copies}): llm_gemv {a:7.2f} us ({nbytes / a / 1e6:.2f} TB/s), linear_small {b:7.2f} us "
+              f"({nbytes / b / 1e6:.2f} TB/s), ratio {b / a:.2f}x, min {min(times['gemv']):.2f} / {min(times['small']):.2f}, max |difference of the outputs| {err:.2e}", flush=True)
+        del pool
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--tokens", type=int, default=100)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--skip-decode", action="store_true")
+    ap.add_argument("--skip-gemv", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("llm_decode_bench needs the GPU: no timing is reported without one")
+    if not a.skip_gemv:
+        gemv_part(a.reps)
+    if not a.skip_decode:
+        decode_part(a.layers, a.tokens)
