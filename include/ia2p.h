@@ -366,8 +366,11 @@ ia2p_status ia2p_prior_step(void* stream, const float* sample, const void* out_c
  * one full forward per new token there, one cached row here). transformers `LlamaModel` + `lm_head` semantics: pre-RMSNorm blocks, rotary
  * embeddings (rotate_half convention, rope_theta), multi-head attention at head dim 128 (num_kv_heads must equal num_heads), bias-free
  * projections, SwiGLU MLP, final `model.norm`, untied `lm_head`. Batch 1 (the reference asserts it, llm/mm_utils.py:93). Parameter keys are
- * the `LlamaForCausalLM` state-dict names ("model.layers.0.self_attn.q_proj.weight", ...), fp16. The reference loads the checkpoint as 4-bit NF4
- * with fp32 compute (pipeline.py:28-31); this engine computes from the fp16 weights. */
+ * the `LlamaForCausalLM` state-dict names ("model.layers.0.self_attn.q_proj.weight", ...), fp16. The reference's live call loads the checkpoint with
+ * `load_in_4bit=True, bnb_4bit_compute_dtype=torch.float32` and names no quant type (pipeline.py:28-31); the default of the transformers version it pins
+ * is believed to be "fp4" without double quantisation, which could not be verified where this was written (neither that version nor bitsandbytes was at
+ * hand). Its unused llm/model/builder.py:31-37 asks for NF4 with double quantisation. This engine computes from the fp16 weights by default and from
+ * 4-bit codes of either codebook after ia2p_llm_set_weight_format. */
 typedef struct ia2p_llm ia2p_llm;
 typedef struct {
   int vocab_size, hidden_size, num_layers, num_heads, num_kv_heads, intermediate_size;
@@ -381,6 +384,15 @@ size_t ia2p_llm_arena_bytes(ia2p_llm* llm);
 ia2p_status ia2p_llm_bind_arena(ia2p_llm* llm, void* dev_arena, size_t bytes);
 ia2p_status ia2p_llm_load_tensor(ia2p_llm* llm, const char* key, const void* dev_src, const int64_t* shape, int ndim, void* stream);
 ia2p_status ia2p_llm_finalize_weights(ia2p_llm* llm);
+/* After ia2p_llm_create, before ia2p_llm_bind_arena: bits = 4 holds the seven projections of every decoder layer as 4-bit codes of `codebook` (16 values,
+ * index = code), quantised block-wise at load as bitsandbytes does: blocks of 64 along the flattened tensor, absmax = max |w| as fp32, code = the entry
+ * nearest to w / absmax (thresholds: the fp32 midpoints of the sorted codebook; a value on a threshold takes the lower entry; an all-zero block stores
+ * absmax 0). Embeddings, norms and lm_head stay fp16. ia2p_llm_load_tensor still takes the fp16 tensor of a projection and quantises it into the arena;
+ * ia2p_llm_arena_bytes and ia2p_llm_workspace_bytes (a prefill dequantises one projection at a time into the workspace) follow the format. Decode reads
+ * the codes directly; rows of up to 14336 weights. bits = 16 restores the default. IA2P_ERR_INVALID for other bit counts or a null codebook,
+ * IA2P_ERR_STATE once an arena is bound. */
+ia2p_status ia2p_llm_set_weight_format(ia2p_llm* llm, int bits, const float* codebook);
+int ia2p_llm_weight_bits(ia2p_llm* llm);
 /* KV cache: fp16 [layer][k | v][max_positions][hidden], caller-owned device memory (16-byte aligned), max_positions <= 8192 (0 bytes otherwise).
  * Binding a cache sets the position to 0. */
 size_t ia2p_llm_kv_bytes(ia2p_llm* llm, int max_positions);
@@ -404,6 +416,13 @@ ia2p_status ia2p_llm_decode(ia2p_llm* llm, void* stream, int token_id, float* hi
 /* the weight-streaming GEMV of the decode path on its own (tools/llm_decode_bench.py measures it against ia2p_linear_small):
  * out[N] fp32 = W[N, K] fp16 . x[K] fp32, K a multiple of 8 */
 ia2p_status ia2p_llm_gemv(void* stream, const void* W, const float* x, float* out, int N, int K);
+/* The 4-bit format per operation (unit tests, tools/llm_decode_bench.py). W: fp16 [N, K] on the device, K a multiple of 64; `packed`:
+ * ia2p_llm_q4_packed_bytes(N, K) bytes (0 for a K that cannot be packed; the layout inside is the engine's own); absmax: fp32 [N * K / 64]; codebook: 16
+ * host floats. Dequantising gives fp16(codebook[code] * absmax). The GEMV is the decode path's: out[N] fp32 = dequantised W . x[K] fp32, K <= 14336. */
+size_t ia2p_llm_q4_packed_bytes(int64_t N, int64_t K);
+ia2p_status ia2p_llm_quantize_q4(void* stream, const void* W, int64_t N, int64_t K, const float* codebook, void* packed, float* absmax);
+ia2p_status ia2p_llm_dequantize_q4(void* stream, const void* packed, const float* absmax, int64_t N, int64_t K, const float* codebook, void* W);
+ia2p_status ia2p_llm_gemv_q4(void* stream, const void* packed, const float* absmax, const float* codebook, const float* x, float* out, int N, int K);
 /* exact (erf) GELU in place on fp16 [n]: the activation of an `mlpNx_gelu` projector head between two ia2p_linear_small calls
  * (llm/model/multimodal_projector/builder.py:33-74 `nn.GELU()`) */
 ia2p_status ia2p_gelu(void* stream, void* x, int64_t n);

@@ -3,10 +3,10 @@
 Importing this package touches no GPU and no native code; the HIP library (libia2p_hip.so, built by
 `python -m instructany2pix_amd.build`) is loaded on first use and there is no non-HIP fallback.
 """
-from .config import LLMConfig, UNetConfig, sdxl_base, sdxl_refiner, tiny, tiny_llm, vicuna_7b
+from .config import BNB_4BIT_CODEBOOKS, LLMConfig, UNetConfig, sdxl_base, sdxl_refiner, tiny, tiny_llm, vicuna_7b
 
 __all__ = ["InstructAny2PixPrior", "prior_config", "MODALITY", "HipGPT2Model", "DDPMScheduler", "HipCLIPTextModel", "SDXLTextEncoders", "UNetConfig", "sdxl_base", "sdxl_refiner", "tiny", "StableDiffusionXLImg2ImgPipeline", "EulerDiscreteScheduler", "InstructAny2PixPipeline", "HipUNet2DConditionModel", "DDIMScheduler",
-           "SDXLDDIMPipeline", "StableDiffusionXLPipeline", "IPAdapterXL", "ImageProjModel", "HipAutoencoderKL", "EditRequest", "VaeImageProcessor", "HipInstructAny2PixLM", "KeywordsStoppingCriteria", "LLMConfig", "vicuna_7b", "tiny_llm"]
+           "SDXLDDIMPipeline", "StableDiffusionXLPipeline", "IPAdapterXL", "ImageProjModel", "HipAutoencoderKL", "EditRequest", "VaeImageProcessor", "HipInstructAny2PixLM", "KeywordsStoppingCriteria", "LLMConfig", "vicuna_7b", "tiny_llm", "BNB_4BIT_CODEBOOKS"]
 
 
 def __getattr__(name):          # lazy: keep `import instructany2pix_amd` free of torch/ctypes work

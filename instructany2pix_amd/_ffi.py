@@ -144,6 +144,12 @@ SIGNATURES = {
     "ia2p_llm_prefill": (_I, [_P, _P, _P, _I, _P, _P, _P, _SZ]),
     "ia2p_llm_decode": (_I, [_P, _P, _I, _P, _P, _P, _SZ]),
     "ia2p_llm_gemv": (_I, [_P, _P, _P, _P, _I, _I]),
+    "ia2p_llm_set_weight_format": (_I, [_P, _I, C.POINTER(_F)]),
+    "ia2p_llm_weight_bits": (_I, [_P]),
+    "ia2p_llm_q4_packed_bytes": (_SZ, [_I64, _I64]),
+    "ia2p_llm_quantize_q4": (_I, [_P, _P, _I64, _I64, C.POINTER(_F), _P, _P]),
+    "ia2p_llm_dequantize_q4": (_I, [_P, _P, _P, _I64, _I64, C.POINTER(_F), _P]),
+    "ia2p_llm_gemv_q4": (_I, [_P, _P, _P, C.POINTER(_F), _P, _P, _I, _I]),
     "ia2p_gelu": (_I, [_P, _P, _I64]),
     "ia2p_vae_create": (_I, [C.POINTER(VAEConfigC), C.POINTER(_P)]),
     "ia2p_vae_destroy": (None, [_P]),

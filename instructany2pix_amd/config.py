@@ -235,6 +235,17 @@ class LLMConfig:
         return self
 
 
+# The 16 values a 4-bit code stands for (index = code), scaled by the block's absmax: `bnb_4bit_quant_type` of the reference's `load_in_4bit` loading.
+# Both tables are written from memory of bitsandbytes 0.41.2 (`create_fp4_map` / the table of its kernels) and of the QLoRA paper (NF4); neither
+# package was at hand to check them against. The kernels take the table as data, so a wrong constant is corrected here.
+BNB_4BIT_CODEBOOKS = {
+    "fp4": tuple(v / 12.0 for v in (0.0, 0.0625, 8.0, 12.0, 4.0, 6.0, 2.0, 3.0, -0.0, -0.0625, -8.0, -12.0, -4.0, -6.0, -2.0, -3.0)),
+    "nf4": (-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453, -0.28444138169288635, -0.18477343022823334,
+            -0.09105003625154495, 0.0, 0.07958029955625534, 0.16093020141124725, 0.24611230194568634, 0.33791524171829224,
+            0.44070982933044434, 0.5626170039176941, 0.7229568362236023, 1.0),
+}
+
+
 def vicuna_7b(vocab_size: int = 32000, **kw) -> LLMConfig:
     return LLMConfig(vocab_size=vocab_size, **kw).validate()
 

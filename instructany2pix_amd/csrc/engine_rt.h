@@ -74,7 +74,7 @@ hipError_t ia2p_launch_conv1x1_nchw(const half_t* x, const half_t* w, const half
 extern thread_local std::string g_err;   // error of a failed ia2p_*_create / ctx-less entry point
 const half_t* zero_page();
 
-enum PKind { PK_COPY = 0, PK_CONV = 1, PK_GEGLU_W = 2, PK_GEGLU_B = 3, PK_PAD_CONV_IN = 4, PK_CONV_TAP = 5 };   // PK_CONV / PK_CONV_TAP: 3x3 weights [Co][tap][Ci] (one layout since round 4; two kinds kept for the callers that name their consumer: implicit GEMM / conv_out_kernel);   // PK_PAD_CONV_IN: d0 = Co, d1 = Cin*9; arena holds [Co][64]
+enum PKind { PK_COPY = 0, PK_CONV = 1, PK_GEGLU_W = 2, PK_GEGLU_B = 3, PK_PAD_CONV_IN = 4, PK_CONV_TAP = 5, PK_Q4 = 6 };   // PK_Q4: a 4-bit LLM projection (llm_engine.hip quantises it at load; d0 = rows, d1 = K; the arena holds elems / 4)   // PK_CONV / PK_CONV_TAP: 3x3 weights [Co][tap][Ci] (one layout since round 4; two kinds kept for the callers that name their consumer: implicit GEMM / conv_out_kernel);   // PK_PAD_CONV_IN: d0 = Co, d1 = Cin*9; arena holds [Co][64]
 
 struct Param {
   size_t off;       // element offset in the arena

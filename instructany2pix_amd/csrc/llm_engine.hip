@@ -8,6 +8,8 @@
 //   prefill (T rows): op_gemm projections + row kernels (RMSNorm, RoPE + cache write, SiLU-multiply) + causal attention against the cache
 //   decode (one row): five weight-streaming launches per layer -- QKV GEMV (RMSNorm in, RoPE + cache write out), attention, o_proj GEMV (+ residual),
 //                     gate/up GEMV (RMSNorm in, silu(gate) * up out), down_proj GEMV (+ residual); the residual stream of the row stays fp32
+// The projections of the layers are fp16, or 4-bit codes (ia2p_llm_set_weight_format): decode then runs the same five launches on llm_gemv_q4_kernel and
+// prefill dequantises one projection at a time in front of its op_gemm.
 // =====================================================================================================================
 
 enum { EPI_PLAIN = 0, EPI_RESID = 1, EPI_QKV = 2, EPI_SWIGLU = 3 };
@@ -26,6 +28,22 @@ struct LlmGemv {
   half_t* kc;
   half_t* vc;
 };
+
+// EPI_QKV: rows (d, d + 64) of rotary pair `pidx` -> q row (rotated), k row (rotated) or v row of the cache at `pos`
+__device__ __forceinline__ void llm_store_qkv_pair(const LlmGemv& a, int pidx, float x1, float x2) {
+  const int lo = (pidx >> 6) * 128 + (pidx & 63), sec = lo / a.H, c = lo - sec * a.H;
+  if (sec < 2) {               // q, k: x cos + rotate_half(x) sin
+    const float ang = (float)a.pos * a.inv_freq[pidx & 63];
+    const float cs = cosf(ang), sn = sinf(ang);
+    const float y1 = x1 * cs - x2 * sn, y2 = x2 * cs + x1 * sn;
+    x1 = y1; x2 = y2;
+  }
+  if (sec == 0) { a.q[c] = x1; a.q[c + 64] = x2; }
+  else {
+    half_t* dst = (sec == 1 ? a.kc : a.vc) + (size_t)a.pos * a.H + c;
+    dst[0] = (half_t)x1; dst[64] = (half_t)x2;
+  }
+}
 
 // out = epilogue(W . f(x)): a workgroup of 4 waves owns R weight rows; its threads walk K in 16-byte pieces (thread t: pieces t, t + 256, ...), so each
 // step of the workgroup reads 4 KiB of every row, once, with non-temporal loads; fp32 accumulation; the 4 waves' partial sums meet in LDS in wave order
@@ -105,21 +123,7 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemv a) {
     }
   } else {
     const int pidx = (int)blockIdx.x * HR + tid;
-    if (tid < HR && pidx < a.N / 2) {
-      const int lo = (pidx >> 6) * 128 + (pidx & 63), sec = lo / a.H, c = lo - sec * a.H;
-      float x1 = total(tid), x2 = total(tid + HR);
-      if (sec < 2) {               // q, k: x cos + rotate_half(x) sin
-        const float ang = (float)a.pos * a.inv_freq[pidx & 63];
-        const float cs = cosf(ang), sn = sinf(ang);
-        const float y1 = x1 * cs - x2 * sn, y2 = x2 * cs + x1 * sn;
-        x1 = y1; x2 = y2;
-      }
-      if (sec == 0) { a.q[c] = x1; a.q[c + 64] = x2; }
-      else {
-        half_t* dst = (sec == 1 ? a.kc : a.vc) + (size_t)a.pos * a.H + c;
-        dst[0] = (half_t)x1; dst[64] = (half_t)x2;
-      }
-    }
+    if (tid < HR && pidx < a.N / 2) llm_store_qkv_pair(a, pidx, total(tid), total(tid + HR));
   }
 }
 
@@ -252,17 +256,229 @@ static hipError_t llm_launch_gemv(const LlmGemv& a, int epi, hipStream_t s) {
   if ((epi == EPI_QKV && (a.N != 3 * a.H || a.H % 128)) || (epi == EPI_SWIGLU && a.N % 2)) return hipErrorInvalidValue;
   return a.N >= 8192 ? gemv_launch_r<8>(a, epi, s) : gemv_launch_r<4>(a, epi, s);
 }
+// =====================================================================================================================
+// 4-bit weights (bitsandbytes `load_in_4bit`: block-wise absmax quantisation at load, block 64, fp32 absmax, a 16-entry codebook passed in as data).
+// Arena layout of a quantised [N, K] matrix: codes in row-major weight order, two per byte (weight 2 b in the low nibble of byte b, 2 b + 1 in the high
+// one), so a row is K / 2 bytes and a 16-byte piece is half a block; one fp32 absmax per block in a second array, [N * K / 64] in the same order.
+// =====================================================================================================================
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+struct Q4Codebook { float v[16]; };                       // index = 4-bit code
+struct Q4Thresholds { float thr[15]; unsigned long long code_at; };   // fp32 midpoints of the sorted codebook; code_at: the code at sorted position i in bits 4 i .. 4 i + 3
+struct LlmQ4 { const u4v* Wq; const float* absmax; Q4Codebook cb; };
+constexpr int Q4_RW = 2, Q4_U = 2;                         // rows per unit of a wave, units per wave (llm_gemv_q4_kernel)
+constexpr int Q4_MAX_K = 14336;                           // the staged input row: 7 chunks of 2048 floats + the byte table fit the 64 KiB of LDS a launch gets
+
+// 8 weights per thread, 8 threads per block: absmax = max |w| (exact in fp32), x = w / absmax (correctly rounded), code = the sorted codebook's entry at
+// position #{thresholds strictly below x}; an all-zero block stores absmax 0 and the code of x = 0
+__global__ __launch_bounds__(256) void llm_quantize_q4_kernel(const half_t* W, long n8, Q4Thresholds t, unsigned* packed, float* absmax) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const h8 w = ((const h8*)W)[i < n8 ? i : n8 - 1];       // (n8 is a multiple of 8: the 8 lanes of a block are all inside or all outside)
+  float m = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf((float)w[e]));
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 8));
+  unsigned out = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float x = m > 0.f ? __fdiv_rn((float)w[e], m) : 0.f;
+    int pos = 0;
+#pragma unroll
+    for (int j = 0; j < 15; ++j) pos += t.thr[j] < x ? 1 : 0;
+    out |= (unsigned)((t.code_at >> (4 * pos)) & 15) << (4 * e);
+  }
+  if (i < n8) {
+    packed[i] = out;
+    if ((i & 7) == 0) absmax[i >> 3] = m;
+  }
+}
+// packed -> fp16 [N, K]: codebook[code] * absmax, the fp32 product rounded to fp16 (what bitsandbytes hands its matmul)
+// (the empty asm keeps the fp32 product a value of its own: selected together with the conversion into one v_fma_mix*_f16 it is rounded once, straight to
+//  fp16, and a -0 product comes out +0)
+__global__ __launch_bounds__(256) void llm_dequantize_q4_kernel(const unsigned* packed, const float* absmax, long n8, Q4Codebook cb, half_t* W) {
+  __shared__ float tab[16];
+  if (threadIdx.x < 16) tab[threadIdx.x] = cb.v[threadIdx.x];
+  __syncthreads();
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  const unsigned c = packed[i];
+  const float m = absmax[i >> 3];
+  h8 w;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float p = tab[(c >> (4 * e)) & 15] * m;
+    asm volatile("" : "+v"(p));
+    w[e] = (half_t)p;
+  }
+  ((h8*)W)[i] = w;
+}
+
+// The decode GEMV on 4-bit weights; contract of llm_gemv_kernel (fp32 input row, RMSNorm folded in, the four epilogues, fp32 accumulation, fixed summation order,
+// no atomics). A packed K = 4096 row is 128 pieces of 16 bytes, so a wave owns whole rows -- a unit of RW = 2 (EPI_QKV / EPI_SWIGLU: the two rows of one output) -- and
+// no sum crosses waves: lane l takes pieces l, l + 64, ... of each row (32 weights of one block: one absmax), sums their products unscaled and scales once.
+// A wave works through U such units one after the other, the next pieces loading under the current step's arithmetic, so the staging is paid once per
+// 4 U RW rows (RW = U = 2: the fastest of the mappings measured on the four Vicuna-7B shapes, docs/LOG.md §15.2).
+// The input row is staged once per workgroup in LDS, gamma applied, transposed so that the eight 16-byte reads of a lane's 32 inputs are contiguous across
+// the wave (chunk of 2048 floats: [8][64 lanes][4]). Codes are decoded two at a time through a 256-entry LDS table of float pairs indexed by the byte.
+template <int EPI>
+__global__ __launch_bounds__(256) void llm_gemv_q4_kernel(LlmGemv a, LlmQ4 q) {
+  constexpr int RW = Q4_RW, U = Q4_U;
+  extern __shared__ float q4_sm[];
+  f2* tab = (f2*)q4_sm;               // [256]
+  float* red = q4_sm + 512;           // [4]
+  float* xs = q4_sm + 512 + 4;        // [chunks][8][64][4]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = a.K, pieces = K >> 5, nit = (pieces + 63) >> 6;
+  const int unit0 = ((int)blockIdx.x * 4 + wave) * U;
+  auto row_of = [&](int unit, int r) {
+    if (EPI == EPI_QKV) { const int pidx = min(unit, a.N / 2 - 1); return (pidx >> 6) * 128 + (pidx & 63) + 64 * r; }
+    if (EPI == EPI_SWIGLU) return min(unit, a.N / 2 - 1) + r * (a.N / 2);
+    return min(unit * RW + r, a.N - 1);
+  };
+  auto fetch = [&](int unit, int it, u4v* w, float* am) {
+    const int p = min(it * 64 + lane, pieces - 1);
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+      const size_t row = (size_t)row_of(unit, r);
+      w[r] = __builtin_nontemporal_load(q.Wq + row * pieces + p);
+      am[r] = q.absmax[row * (K >> 6) + (p >> 1)];
+    }
+  };
+  // the first pieces are on their way while the input row is staged
+  u4v w[RW], wn[RW];
+  float am[RW], amn[RW];
+  fetch(unit0, 0, w, am);
+  tab[tid] = f2{q.cb.v[tid & 15], q.cb.v[tid >> 4]};
+  float ss = 0.f;
+  for (int i = tid; i < (K >> 2); i += 256) {
+    f4 x = ((const f4*)a.X)[i];
+    if (a.gamma) {
+      const h4 g = ((const h4*)a.gamma)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { ss = fmaf(x[e], x[e], ss); x[e] *= (float)g[e]; }
+    }
+    const int p = i >> 3, j = i & 7;
+    *(f4*)(xs + ((((p >> 6) << 3) + j) << 8) + ((p & 63) << 2)) = x;
+  }
+  ss = wave_sum(ss);
+  if (lane == 0) red[wave] = ss;
+  __syncthreads();
+  float rstd = 1.f;
+  if (a.gamma) rstd = 1.0f / sqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)K + a.eps);
+#pragma unroll 1
+  for (int u = 0; u < U; ++u) {
+    const int unit = unit0 + u;
+    float acc[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) acc[r] = 0.f;
+    for (int it = 0; it < nit; ++it) {
+      const bool more = it + 1 < nit || u + 1 < U;     // the next pieces (of this unit or the wave's next one) load under this step's arithmetic
+      if (more) fetch(it + 1 < nit ? unit : unit + 1, it + 1 < nit ? it + 1 : 0, wn, amn);
+      if (it * 64 + lane < pieces) {
+        f4 x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = *(const f4*)(xs + (((it << 3) + j) << 8) + (lane << 2));
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+          f2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {         // half a piece at a time: its 8 table reads are issued together, then consumed
+            f2 t[8];
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+              for (int b = 0; b < 4; ++b) t[4 * k + b] = tab[(w[r][2 * h + k] >> (8 * b)) & 255];
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+              for (int b = 0; b < 4; b += 2) {
+                const f4 xv = x[4 * h + 2 * k + (b >> 1)];
+                s0 = __builtin_elementwise_fma(t[4 * k + b], f2{xv[0], xv[1]}, s0);
+                s1 = __builtin_elementwise_fma(t[4 * k + b + 1], f2{xv[2], xv[3]}, s1);
+              }
+          }
+          const f2 s = s0 + s1;
+          acc[r] = fmaf(s[0] + s[1], am[r], acc[r]);
+        }
+      }
+      if (more) {
+#pragma unroll
+        for (int r = 0; r < RW; ++r) { w[r] = wn[r]; am[r] = amn[r]; }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RW; ++r) acc[r] = wave_sum(acc[r]) * rstd;
+    if (EPI == EPI_PLAIN || EPI == EPI_RESID) {
+#pragma unroll
+      for (int r = 0; r < RW; ++r) {
+        const int n = unit * RW + r;
+        if (lane == r && n < a.N) a.out[n] = EPI == EPI_RESID ? a.out[n] + acc[r] : acc[r];
+      }
+    } else if (lane == 0 && unit < a.N / 2) {
+      if (EPI == EPI_SWIGLU) a.out[unit] = acc[0] / (1.0f + expf(-acc[0])) * acc[RW - 1];
+      else llm_store_qkv_pair(a, unit, acc[0], acc[RW - 1]);
+    }
+  }
+  if (EPI == EPI_PLAIN && a.hid && a.gamma && blockIdx.x == 0)
+    for (int i = tid; i < K; i += 256) a.hid[i] = a.X[i] * rstd * (float)a.gamma[i];
+}
+
+static size_t q4_gemv_lds(int K) { return (size_t)(512 + 4 + (((K >> 5) + 63) >> 6) * 2048) * sizeof(float); }
+static hipError_t llm_launch_gemv_q4(const LlmGemv& a, const LlmQ4& q, int epi, hipStream_t s) {
+  if (!q.Wq || !q.absmax || !a.X || a.N < 1 || a.K < 64 || a.K % 64 || a.K > Q4_MAX_K) return hipErrorInvalidValue;
+  if ((epi == EPI_QKV && (a.N != 3 * a.H || a.H % 128)) || (epi == EPI_SWIGLU && a.N % 2)) return hipErrorInvalidValue;
+  const int units = epi == EPI_QKV || epi == EPI_SWIGLU ? a.N / 2 : (a.N + Q4_RW - 1) / Q4_RW;
+  const dim3 grid((units + 4 * Q4_U - 1) / (4 * Q4_U)), block(256);
+  const size_t lds = q4_gemv_lds(a.K);
+  switch (epi) {
+    case EPI_PLAIN: hipLaunchKernelGGL((llm_gemv_q4_kernel<EPI_PLAIN>), grid, block, lds, s, a, q); break;
+    case EPI_RESID: hipLaunchKernelGGL((llm_gemv_q4_kernel<EPI_RESID>), grid, block, lds, s, a, q); break;
+    case EPI_QKV: hipLaunchKernelGGL((llm_gemv_q4_kernel<EPI_QKV>), grid, block, lds, s, a, q); break;
+    case EPI_SWIGLU: hipLaunchKernelGGL((llm_gemv_q4_kernel<EPI_SWIGLU>), grid, block, lds, s, a, q); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+// sorted codebook -> thresholds and the code at each sorted position (equal values keep their code order)
+static Q4Thresholds q4_thresholds(const float* cb) {
+  int idx[16];
+  for (int i = 0; i < 16; ++i) idx[i] = i;
+  std::stable_sort(idx, idx + 16, [&](int x, int y) { return cb[x] < cb[y]; });
+  Q4Thresholds t{};
+  for (int i = 0; i < 15; ++i) t.thr[i] = (cb[idx[i]] + cb[idx[i + 1]]) / 2.0f;
+  for (int i = 0; i < 16; ++i) t.code_at |= (unsigned long long)idx[i] << (4 * i);
+  return t;
+}
+static hipError_t llm_launch_quantize_q4(const half_t* W, size_t elems, const float* cb, void* packed, float* absmax, hipStream_t s) {
+  const long n8 = (long)(elems / 8);
+  hipLaunchKernelGGL(llm_quantize_q4_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, W, n8, q4_thresholds(cb), (unsigned*)packed, absmax);
+  return hipGetLastError();
+}
+static hipError_t llm_launch_dequantize_q4(const void* packed, const float* absmax, size_t elems, const float* cb, half_t* W, hipStream_t s) {
+  const long n8 = (long)(elems / 8);
+  Q4Codebook c;
+  memcpy(c.v, cb, sizeof c.v);
+  hipLaunchKernelGGL(llm_dequantize_q4_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, (const unsigned*)packed, absmax, n8, c, W);
+  return hipGetLastError();
+}
 static size_t attn_lds(int nk) { return ((size_t)((nk + 3) & ~3) + 16 * 128 + 8) * sizeof(float); }
 constexpr int LLM_MAX_POSITIONS = 8192;       // scores of one query row live in LDS (32 KiB of the 64)
 
-struct LLayer { size_t ln1, ln2, wqkv, wo, wgu, wd; };
+struct LLayer { size_t ln1, ln2, wqkv, wo, wgu, wd; size_t aqkv, ao, agu, ad; };      // a*: the absmax arrays of the 4-bit format (w*: the packed codes then)
 struct ia2p_llm : RunCtx {
   ia2p_llm_config cfg;
   size_t tok, normf, head, invf;
   std::vector<LLayer> layers;
   half_t* kv = nullptr;
   int max_pos = 0, pos = 0;
+  int wbits = 16;                                      // 16: fp16 projections; 4: codes of `codebook`, block 64, fp32 absmax (ia2p_llm_set_weight_format)
+  float codebook[16] = {};
+  std::unordered_map<std::string, size_t> q4_absmax;   // projection key -> offset of its absmax rows (arena elements)
 };
+// arena elements (2 bytes each) of a quantised [N, K]: packed codes, absmax
+static size_t q4_code_elems(size_t nk) { return nk / 4; }
+static size_t q4_absmax_elems(size_t nk) { return nk / 64 * 2; }
 
 static ia2p_status llm_plan(ia2p_llm* c) {
   const ia2p_llm_config& g = c->cfg;
@@ -272,6 +488,9 @@ static ia2p_status llm_plan(ia2p_llm* c) {
   if (H % 64 || g.num_heads * 128 != H) return fail(c, IA2P_ERR_SHAPE, "llm: hidden %d must be a multiple of 64 and heads (%d) * 128 (head dim 128 only)", H, g.num_heads);
   if (g.num_kv_heads != g.num_heads) return fail(c, IA2P_ERR_SHAPE, "llm: %d key/value heads for %d heads (grouped-query attention is not built)", g.num_kv_heads, g.num_heads);
   if (I % 64) return fail(c, IA2P_ERR_SHAPE, "llm: intermediate %d must be a multiple of 64", I);
+  const bool q4 = c->wbits == 4;
+  if (q4 && (H > Q4_MAX_K || I > Q4_MAX_K)) return fail(c, IA2P_ERR_SHAPE, "llm: 4-bit weights serve rows of up to %d (hidden %d, intermediate %d)", Q4_MAX_K, H, I);
+  c->params.clear(); c->layers.clear(); c->q4_absmax.clear();
   size_t cur = 0;
   auto take = [&](size_t e) { size_t o = cur; cur += (e + 127) & ~(size_t)127; return o; };
   auto reg = [&](const std::string& k, size_t off, size_t n) { c->params[k] = Param{off, n, PK_COPY, 0, 0, false, false}; };
@@ -281,15 +500,22 @@ static ia2p_status llm_plan(ia2p_llm* c) {
     const std::string p = "model.layers." + std::to_string(i) + ".";
     LLayer l;
     l.ln1 = par(p + "input_layernorm.weight", H);
-    l.wqkv = take((size_t)3 * H * H);                       // q | k | v rows stacked: one projection
-    const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
-    for (int j = 0; j < 3; ++j) reg(p + "self_attn." + nm[j] + ".weight", l.wqkv + (size_t)j * H * H, (size_t)H * H);
-    l.wo = par(p + "self_attn.o_proj.weight", (size_t)H * H);
+    // a projection of `parts` equal [rows, K] tensors stacked as rows (blocks never cross a row, so in 4 bits the codes and the absmax rows stack the same way)
+    auto proj = [&](size_t* w, size_t* am, const std::vector<std::string>& keys, size_t rows, size_t K) {
+      const size_t nk = rows * K, parts = keys.size();
+      *w = take(q4 ? q4_code_elems(parts * nk) : parts * nk);
+      *am = q4 ? take(q4_absmax_elems(parts * nk)) : 0;
+      for (size_t j = 0; j < parts; ++j) {
+        if (!q4) { reg(p + keys[j], *w + j * nk, nk); continue; }
+        c->params[p + keys[j]] = Param{*w + j * q4_code_elems(nk), nk, PK_Q4, (int)rows, (int)K, false, false};
+        c->q4_absmax[p + keys[j]] = *am + j * q4_absmax_elems(nk);
+      }
+    };
+    proj(&l.wqkv, &l.aqkv, {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight"}, H, H);     // q | k | v rows stacked: one projection
+    proj(&l.wo, &l.ao, {"self_attn.o_proj.weight"}, H, H);
     l.ln2 = par(p + "post_attention_layernorm.weight", H);
-    l.wgu = take((size_t)2 * I * H);                        // gate | up rows stacked
-    reg(p + "mlp.gate_proj.weight", l.wgu, (size_t)I * H);
-    reg(p + "mlp.up_proj.weight", l.wgu + (size_t)I * H, (size_t)I * H);
-    l.wd = par(p + "mlp.down_proj.weight", (size_t)H * I);
+    proj(&l.wgu, &l.agu, {"mlp.gate_proj.weight", "mlp.up_proj.weight"}, I, H);                                              // gate | up rows stacked
+    proj(&l.wd, &l.ad, {"mlp.down_proj.weight"}, H, I);
     c->layers.push_back(l);
   }
   c->normf = par("model.norm.weight", H);
@@ -310,6 +536,21 @@ static void llm_head(ia2p_llm* c, const float* xf, float* hidden_out, float* log
   CHECK_LAUNCH(c, llm_launch_gemv(a, EPI_PLAIN, c->stream), "llm lm_head");
 }
 
+// one decode projection on the context's weight format
+static hipError_t llm_proj_gemv(ia2p_llm* c, LlmGemv& a, size_t w, size_t am, int epi) {
+  if (c->wbits != 4) { a.W = W_(c, w); return llm_launch_gemv(a, epi, c->stream); }
+  LlmQ4 q;
+  q.Wq = (const u4v*)W_(c, w); q.absmax = (const float*)W_(c, am);
+  memcpy(q.cb.v, c->codebook, sizeof q.cb.v);
+  return llm_launch_gemv_q4(a, q, epi, c->stream);
+}
+// a prefill projection's fp16 weights: the arena's, or (4 bits) dequantised into `scratch` in front of the GEMM that reads them
+static const half_t* llm_proj_f16(ia2p_llm* c, size_t w, size_t am, size_t elems, T2 scratch, const char* what) {
+  if (c->wbits != 4) return W_(c, w);
+  CHECK_LAUNCH(c, llm_launch_dequantize_q4(W_(c, w), (const float*)W_(c, am), elems, c->codebook, scratch.p, c->stream), what);
+  return scratch.p;
+}
+
 static ia2p_status llm_run_decode(ia2p_llm* c, int token, float* hidden_out, float* logits_out) {
   const ia2p_llm_config& g = c->cfg;
   const int H = g.hidden_size, I = g.intermediate_size, pos = c->pos;
@@ -324,21 +565,21 @@ static ia2p_status llm_run_decode(ia2p_llm* c, int token, float* hidden_out, flo
     const LLayer& l = c->layers[i];
     if (c->dry || c->failed) break;
     LlmGemv a{};
-    a.W = W_(c, l.wqkv); a.X = xf; a.gamma = W_(c, l.ln1); a.eps = g.rms_norm_eps; a.N = 3 * H; a.K = H; a.H = H; a.pos = pos;
+    a.X = xf; a.gamma = W_(c, l.ln1); a.eps = g.rms_norm_eps; a.N = 3 * H; a.K = H; a.H = H; a.pos = pos;
     a.inv_freq = (const float*)W_(c, c->invf); a.q = qf; a.kc = KC(c, i); a.vc = VC(c, i);
-    CHECK_LAUNCH(c, llm_launch_gemv(a, EPI_QKV, c->stream), "llm qkv");
+    CHECK_LAUNCH(c, llm_proj_gemv(c, a, l.wqkv, l.aqkv, EPI_QKV), "llm qkv");
     hipLaunchKernelGGL(llm_attn_kernel<float>, dim3(g.num_heads, 1), dim3(256), attn_lds(pos + 1), c->stream, (const float*)qf, (const half_t*)KC(c, i), (const half_t*)VC(c, i), af, H, pos,
                        0.08838834764831845f);
     CHECK_LAUNCH(c, hipGetLastError(), "llm attention");
     LlmGemv o{};
-    o.W = W_(c, l.wo); o.X = af; o.N = H; o.K = H; o.out = xf;
-    CHECK_LAUNCH(c, llm_launch_gemv(o, EPI_RESID, c->stream), "llm o_proj");
+    o.X = af; o.N = H; o.K = H; o.out = xf;
+    CHECK_LAUNCH(c, llm_proj_gemv(c, o, l.wo, l.ao, EPI_RESID), "llm o_proj");
     LlmGemv u{};
-    u.W = W_(c, l.wgu); u.X = xf; u.gamma = W_(c, l.ln2); u.eps = g.rms_norm_eps; u.N = 2 * I; u.K = H; u.out = ff;
-    CHECK_LAUNCH(c, llm_launch_gemv(u, EPI_SWIGLU, c->stream), "llm gate/up");
+    u.X = xf; u.gamma = W_(c, l.ln2); u.eps = g.rms_norm_eps; u.N = 2 * I; u.K = H; u.out = ff;
+    CHECK_LAUNCH(c, llm_proj_gemv(c, u, l.wgu, l.agu, EPI_SWIGLU), "llm gate/up");
     LlmGemv d{};
-    d.W = W_(c, l.wd); d.X = ff; d.N = H; d.K = I; d.out = xf;
-    CHECK_LAUNCH(c, llm_launch_gemv(d, EPI_RESID, c->stream), "llm down_proj");
+    d.X = ff; d.N = H; d.K = I; d.out = xf;
+    CHECK_LAUNCH(c, llm_proj_gemv(c, d, l.wd, l.ad, EPI_RESID), "llm down_proj");
   }
   if (!c->dry) llm_head(c, xf, hidden_out, logits_out);
   wsfree(c, ft); wsfree(c, at); wsfree(c, qt); wsfree(c, xt);
@@ -350,6 +591,8 @@ static ia2p_status llm_run_prefill(ia2p_llm* c, const half_t* embeds, int T, flo
   const int H = g.hidden_size, I = g.intermediate_size, p0 = c->pos;
   T2 x = wsalloc(c, (size_t)T * H), xn = wsalloc(c, (size_t)T * H), qkv = wsalloc(c, (size_t)T * 3 * H), qt = wsalloc(c, (size_t)T * H * 2);
   T2 att = wsalloc(c, (size_t)T * H), gu = wsalloc(c, (size_t)T * 2 * I), act = wsalloc(c, (size_t)T * I), xt = wsalloc(c, (size_t)2 * H);
+  T2 wq{(size_t)-1, nullptr};           // 4 bits: one projection at a time as fp16 (the largest: gate | up)
+  if (c->wbits == 4) wq = wsalloc(c, std::max((size_t)3 * H * H, (size_t)2 * I * H));
   float *qf = (float*)qt.p, *xf = (float*)xt.p;
   if (!c->dry && !c->failed) {
     hipError_t e = hipMemcpyAsync(x.p, embeds, (size_t)T * H * sizeof(half_t), hipMemcpyDeviceToDevice, c->stream);
@@ -361,7 +604,7 @@ static ia2p_status llm_run_prefill(ia2p_llm* c, const half_t* embeds, int T, flo
       hipLaunchKernelGGL(llm_rmsnorm_rows_kernel, dim3(T), dim3(256), 0, c->stream, (const half_t*)x.p, xn.p, W_(c, l.ln1), H, g.rms_norm_eps);
       CHECK_LAUNCH(c, hipGetLastError(), "llm input_layernorm");
     }
-    op_gemm(c, xn.p, H, W_(c, l.wqkv), nullptr, nullptr, 0, qkv.p, 3 * H, T, 3 * H, H);
+    op_gemm(c, xn.p, H, llm_proj_f16(c, l.wqkv, l.aqkv, (size_t)3 * H * H, wq, "llm dequantize qkv"), nullptr, nullptr, 0, qkv.p, 3 * H, T, 3 * H, H);
     if (!c->dry && !c->failed) {
       hipLaunchKernelGGL(llm_rope_cache_rows_kernel, dim3(T), dim3(256), 0, c->stream, (const half_t*)qkv.p, qf, KC(c, i), VC(c, i), (const float*)W_(c, c->invf), H, p0);
       CHECK_LAUNCH(c, hipGetLastError(), "llm rope");
@@ -369,23 +612,24 @@ static ia2p_status llm_run_prefill(ia2p_llm* c, const half_t* embeds, int T, flo
                          0.08838834764831845f);
       CHECK_LAUNCH(c, hipGetLastError(), "llm attention");
     }
-    op_gemm(c, att.p, H, W_(c, l.wo), nullptr, x.p, H, x.p, H, T, H, H);
+    op_gemm(c, att.p, H, llm_proj_f16(c, l.wo, l.ao, (size_t)H * H, wq, "llm dequantize o_proj"), nullptr, x.p, H, x.p, H, T, H, H);
     if (!c->dry && !c->failed) {
       hipLaunchKernelGGL(llm_rmsnorm_rows_kernel, dim3(T), dim3(256), 0, c->stream, (const half_t*)x.p, xn.p, W_(c, l.ln2), H, g.rms_norm_eps);
       CHECK_LAUNCH(c, hipGetLastError(), "llm post_attention_layernorm");
     }
-    op_gemm(c, xn.p, H, W_(c, l.wgu), nullptr, nullptr, 0, gu.p, 2 * I, T, 2 * I, H);
+    op_gemm(c, xn.p, H, llm_proj_f16(c, l.wgu, l.agu, (size_t)2 * I * H, wq, "llm dequantize gate/up"), nullptr, nullptr, 0, gu.p, 2 * I, T, 2 * I, H);
     if (!c->dry && !c->failed) {
       hipLaunchKernelGGL(llm_silu_mul_rows_kernel, dim3(T), dim3(256), 0, c->stream, (const half_t*)gu.p, act.p, I);
       CHECK_LAUNCH(c, hipGetLastError(), "llm silu-multiply");
     }
-    op_gemm(c, act.p, I, W_(c, l.wd), nullptr, x.p, H, x.p, H, T, H, I);
+    op_gemm(c, act.p, I, llm_proj_f16(c, l.wd, l.ad, (size_t)H * I, wq, "llm dequantize down_proj"), nullptr, x.p, H, x.p, H, T, H, I);
   }
   if (!c->dry && !c->failed) {          // only the last row goes through model.norm and lm_head
     hipLaunchKernelGGL(llm_row_f32_kernel, dim3((H + 255) / 256), dim3(256), 0, c->stream, (const half_t*)(x.p + (size_t)(T - 1) * H), xf, H);
     CHECK_LAUNCH(c, hipGetLastError(), "llm last row");
     llm_head(c, xf, hidden_out, logits_out);
   }
+  if (c->wbits == 4) wsfree(c, wq);
   wsfree(c, xt); wsfree(c, act); wsfree(c, gu); wsfree(c, att); wsfree(c, qt); wsfree(c, qkv); wsfree(c, xn); wsfree(c, x);
   return c->failed ? IA2P_ERR_HIP : IA2P_OK;
 }
@@ -436,7 +680,61 @@ const char* ia2p_llm_last_error(ia2p_llm* c) { return c ? c->err.c_str() : g_err
 size_t ia2p_llm_arena_bytes(ia2p_llm* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
 ia2p_status ia2p_llm_bind_arena(ia2p_llm* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
 ia2p_status ia2p_llm_load_tensor(ia2p_llm* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
-  return rc_load_tensor(c, key, src, shape, ndim, stream);
+  if (!c || !key || !src || !shape || !c->arena) return rc_load_tensor(c, key, src, shape, ndim, stream);      // (its refusals)
+  auto it = c->params.find(key);
+  if (it == c->params.end() || it->second.kind != PK_Q4) return rc_load_tensor(c, key, src, shape, ndim, stream);
+  Param& p = it->second;              // a 4-bit projection: quantised from the fp16 tensor into the arena
+  size_t n = 1;
+  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+  if (n != p.elems) return fail(c, IA2P_ERR_SHAPE, "parameter '%s': expected %zu elements, got %zu", key, p.elems, n);
+  hipError_t e = llm_launch_quantize_q4((const half_t*)src, n, c->codebook, c->arena + p.off, (float*)(c->arena + c->q4_absmax[key]), (hipStream_t)stream);
+  if (e != hipSuccess) return fail_hip(c, e, (std::string("quantize '") + key + "'").c_str());
+  p.loaded = true;
+  return IA2P_OK;
+}
+ia2p_status ia2p_llm_set_weight_format(ia2p_llm* c, int bits, const float* codebook) {
+  if (!c) return fail(nullptr, IA2P_ERR_INVALID, "llm_set_weight_format: null argument");
+  if (bits != 16 && bits != 4) return fail(c, IA2P_ERR_INVALID, "llm_set_weight_format: %d bits (16 or 4)", bits);
+  if (bits == 4 && !codebook) return fail(c, IA2P_ERR_INVALID, "llm_set_weight_format: 4 bits need a codebook of 16 values");
+  if (c->arena) return fail(c, IA2P_ERR_STATE, "llm_set_weight_format after ia2p_llm_bind_arena");
+  const int old = c->wbits;
+  c->wbits = bits;
+  if (bits == 4) memcpy(c->codebook, codebook, sizeof c->codebook);
+  const ia2p_status st = llm_plan(c);
+  if (st != IA2P_OK) { c->wbits = old; (void)llm_plan(c); c->failed = false; }
+  return st;
+}
+int ia2p_llm_weight_bits(ia2p_llm* c) { return c ? c->wbits : 0; }
+size_t ia2p_llm_q4_packed_bytes(int64_t N, int64_t K) { return N < 1 || K < 64 || K % 64 ? 0 : (size_t)N * (size_t)K / 2; }
+static ia2p_status q4_op_args(const char* what, const void* a, const void* b, const void* d, const void* cb, int64_t N, int64_t K) {
+  if (!a || !b || !d || !cb) return fail(nullptr, IA2P_ERR_INVALID, "%s: null argument", what);
+  if (N < 1 || K < 64 || K % 64 || N * K > ((int64_t)1 << 34)) return fail(nullptr, IA2P_ERR_SHAPE, "%s: N=%lld K=%lld (K a multiple of 64)", what, (long long)N, (long long)K);
+  return IA2P_OK;
+}
+ia2p_status ia2p_llm_quantize_q4(void* stream, const void* W, int64_t N, int64_t K, const float* codebook, void* packed, float* absmax) {
+  const ia2p_status st = q4_op_args("llm_quantize_q4", W, packed, absmax, codebook, N, K);
+  if (st != IA2P_OK) return st;
+  hipError_t e = llm_launch_quantize_q4((const half_t*)W, (size_t)(N * K), codebook, packed, absmax, (hipStream_t)stream);
+  RET_HIP(e, "llm_quantize_q4");
+}
+ia2p_status ia2p_llm_dequantize_q4(void* stream, const void* packed, const float* absmax, int64_t N, int64_t K, const float* codebook, void* W) {
+  const ia2p_status st = q4_op_args("llm_dequantize_q4", packed, absmax, W, codebook, N, K);
+  if (st != IA2P_OK) return st;
+  hipError_t e = llm_launch_dequantize_q4(packed, absmax, (size_t)(N * K), codebook, (half_t*)W, (hipStream_t)stream);
+  RET_HIP(e, "llm_dequantize_q4");
+}
+ia2p_status ia2p_llm_gemv_q4(void* stream, const void* packed, const float* absmax, const float* codebook, const float* x, float* out, int N, int K) {
+  if (!x || !out) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv_q4: null argument");
+  const ia2p_status st = q4_op_args("llm_gemv_q4", packed, absmax, out, codebook, N, K);
+  if (st != IA2P_OK) return st;
+  if (K > Q4_MAX_K) return fail(nullptr, IA2P_ERR_SHAPE, "llm_gemv_q4: K=%d (at most %d)", K, Q4_MAX_K);
+  LlmGemv a{};
+  a.X = x; a.N = N; a.K = K; a.out = out;
+  LlmQ4 q;
+  q.Wq = (const u4v*)packed; q.absmax = absmax;
+  memcpy(q.cb.v, codebook, sizeof q.cb.v);
+  hipError_t e = llm_launch_gemv_q4(a, q, EPI_PLAIN, (hipStream_t)stream);
+  RET_HIP(e, "llm_gemv_q4");
 }
 ia2p_status ia2p_llm_finalize_weights(ia2p_llm* c) {
   const ia2p_status st = rc_finalize(c, "LLM");

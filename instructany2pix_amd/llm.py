@@ -10,8 +10,14 @@
   parse_generation(...)             <- pipeline.py:213-279: what `forward_llm` reads out of the generated sequence and its hidden rows
 
 Everything between `inputs_embeds` and (final-normed hidden row, logits row) runs through `ia2p_llm_*`; sampling from the logits row, stopping and
-the text parsing are host code. The tokenizer is injected (its sentencepiece model is checkpoint data). The reference loads the checkpoint as
-4-bit NF4 with fp32 compute (pipeline.py:28-31); this engine computes from the fp16 weights."""
+the text parsing are host code. The tokenizer is injected (its sentencepiece model is checkpoint data).
+
+Weight format. The reference's live call loads the checkpoint with `load_in_4bit=True, bnb_4bit_compute_dtype=torch.float32` and names no
+`bnb_4bit_quant_type` (pipeline.py:28-31). The default of the transformers version it pins (4.34.1) is believed to be "fp4" without double
+quantisation; neither that version nor bitsandbytes was at hand to verify it. The unused llm/model/builder.py:31-37 asks for NF4 with double
+quantisation. By default this engine computes from the fp16 weights; `load_in_4bit=True` quantises the decoder projections and the two heads
+block-wise at load (block 64, fp32 absmax, no double quantisation) with the "fp4" or "nf4" codebook of config.BNB_4BIT_CODEBOOKS, as
+bitsandbytes does, and every projection then computes from the dequantised 4-bit weights."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,7 +28,7 @@ from typing import Optional
 import torch
 
 from . import _ffi
-from .config import LLMConfig
+from .config import BNB_4BIT_CODEBOOKS, LLMConfig
 from .weights import projector_depth
 
 try:                                  # the protocol `generate(stopping_criteria=[...])` expects; the class works without transformers too
@@ -170,7 +176,13 @@ class _Head:
 class HipInstructAny2PixLM:
     PROJECTOR, PREDICTOR = "model.vae_projector_image", "model.vae_predictor_image"
 
-    def __init__(self, config: LLMConfig, device="cuda:0", max_positions: int = 1024, video_token_id: Optional[int] = None):
+    def __init__(self, config: LLMConfig, device="cuda:0", max_positions: int = 1024, video_token_id: Optional[int] = None, *,
+                 load_in_4bit: bool = False, bnb_4bit_quant_type: str = "fp4", quantize_heads: bool = True):
+        """load_in_4bit / bnb_4bit_quant_type: the reference's `from_pretrained` keywords. quantize_heads: the two projector heads are
+        `nn.Linear`s inside the model, so the reference's loader quantises them with the decoder (it skips `lm_head` only); False keeps
+        their fp16 weights."""
+        if bnb_4bit_quant_type not in BNB_4BIT_CODEBOOKS:
+            raise ValueError(f"bnb_4bit_quant_type '{bnb_4bit_quant_type}': one of {sorted(BNB_4BIT_CODEBOOKS)}")
         self.config = config.validate()
         self.device = torch.device(device)
         self.max_positions = max_positions
@@ -179,6 +191,11 @@ class HipInstructAny2PixLM:
         self._h = C.c_void_p()
         self._cfg_c = _ffi.make_llm_config(config)
         _ffi.check(self._lib.ia2p_llm_create(C.byref(self._cfg_c), C.byref(self._h)), None, llm=True)
+        self.quant_type = bnb_4bit_quant_type if load_in_4bit else None
+        self._codebook = (C.c_float * 16)(*BNB_4BIT_CODEBOOKS[bnb_4bit_quant_type])
+        self._quantize_heads = bool(load_in_4bit and quantize_heads)
+        if load_in_4bit:
+            _ffi.check(self._lib.ia2p_llm_set_weight_format(self._h, 4, self._codebook), self._h, llm=True)
         with torch.cuda.device(self.device):
             self.arena = torch.zeros(self._lib.ia2p_llm_arena_bytes(self._h), dtype=torch.uint8, device=self.device)
             self.kv = torch.zeros(self._lib.ia2p_llm_kv_bytes(self._h, max_positions), dtype=torch.uint8, device=self.device)
@@ -208,16 +225,36 @@ class HipInstructAny2PixLM:
     def _check(self, st):
         _ffi.check(st, self._h, llm=True)
 
+    @property
+    def weight_bits(self) -> int:
+        """16, or 4 when the decoder projections are held as 4-bit codes"""
+        return self._lib.ia2p_llm_weight_bits(self._h)
+
+    def _quantize_round_trip(self, key, w):
+        """fp16 [N, K] -> the fp16 weights bitsandbytes' Linear4bit computes from: quantised block-wise and dequantised once"""
+        N, K = w.shape
+        if w.numel() % 64:
+            raise ValueError(f"'{key}': {w.numel()} weights do not divide into blocks of 64")
+        rows, cols = w.numel() // 64, 64          # blocks run along the flattened tensor
+        packed = torch.empty(self._lib.ia2p_llm_q4_packed_bytes(rows, cols), dtype=torch.uint8, device=w.device)
+        absmax = torch.empty(rows, dtype=torch.float32, device=w.device)
+        out = torch.empty_like(w)
+        s = _ffi.current_stream()
+        _ffi.check(self._lib.ia2p_llm_quantize_q4(s, _ffi.ptr(w), rows, cols, self._codebook, _ffi.ptr(packed), _ffi.ptr(absmax)), None, llm=True)
+        _ffi.check(self._lib.ia2p_llm_dequantize_q4(s, _ffi.ptr(packed), _ffi.ptr(absmax), rows, cols, self._codebook, _ffi.ptr(out)), None, llm=True)
+        torch.cuda.current_stream().synchronize()
+        return out
+
     def load_state_dict(self, state_dict, strict: bool = True):
         items = state_dict.items() if hasattr(state_dict, "items") else state_dict
         for k, v in items:
             if k.endswith("rotary_emb.inv_freq"):          # buffer in older transformers checkpoints
                 continue
             t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
-            if k.startswith(self.PROJECTOR + "."):
-                self._projector.load(k, t)
-            elif k.startswith(self.PREDICTOR + "."):
-                self._predictor.load(k, t)
+            if k.startswith((self.PROJECTOR + ".", self.PREDICTOR + ".")):
+                if self._quantize_heads and k.endswith(".weight"):
+                    t = self._quantize_round_trip(k, t)
+                (self._projector if k.startswith(self.PROJECTOR + ".") else self._predictor).load(k, t)
             else:
                 shape = (C.c_int64 * t.ndim)(*t.shape)
                 self._check(self._lib.ia2p_llm_load_tensor(self._h, k.encode(), _ffi.ptr(t), shape, t.ndim, _ffi.current_stream()))

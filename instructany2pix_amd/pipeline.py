@@ -103,7 +103,8 @@ class InstructAny2PixPipeline:
                  refiner_unet: Optional[HipUNet2DConditionModel] = None, refiner_text_encoder: Optional[Callable] = None, prior=None,
                  refiner_handoff: str = "image", vae=None, llm=None, llm_tokenizer: Optional[Callable] = None,
                  modality_encoder: Optional[Callable] = None):
-        # llm: a HipInstructAny2PixLM (reference :117 `self.any2pix_lm`) with its tokenizer (:126 `self.any2pix_tokenizer`, injected: the
+        # llm: a HipInstructAny2PixLM (reference :117 `self.any2pix_lm`; built with `load_in_4bit=True` it computes from 4-bit weights as the
+        # reference's `from_pretrained(..., load_in_4bit=True)` model does, nothing changes here) with its tokenizer (:126 `self.any2pix_tokenizer`, injected: the
         # sentencepiece model is checkpoint data); modality_encoder(entry) -> [1024] embedding of an mm_data entry (reference :155-166:
         # ImageBind, which stays outside; an entry may carry its vector directly as entry["embed"])
         self.any2pix_lm, self.any2pix_tokenizer, self.modality_encoder = llm, llm_tokenizer, modality_encoder

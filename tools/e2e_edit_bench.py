@@ -8,7 +8,10 @@ size (Vicuna-7B shape) prefills the prompt and generates 100 tokens on the HIP e
 remain: the ImageBind vectors of the mm_data entries are seeded 1024-d noise (ImageBind stays outside), and, because synthetic weights cannot
 speak, the TOKEN CHOSEN at each step follows a script ("[ caption ] <base> <video> <im_gen> <video> </s>", 100 tokens) instead of the sampled one; every step's
 engine work, its logits and its sampling arithmetic still run.
-Prints per-stage wall times (stream-synchronised) after one warm-up request."""
+Prints per-stage wall times (stream-synchronised) after one warm-up request.
+
+    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)"""
+import argparse
 import os
 import sys
 import time
@@ -31,6 +34,10 @@ import instructany2pix_amd.llm as llm_mod
 from instructany2pix_amd.weights import llm_param_specs
 from stub_llm_tokenizer import ADDED_TOKENS, StubLlamaTokenizer
 
+_ap = argparse.ArgumentParser()
+_ap.add_argument("--llm-bits", type=int, default=16, choices=(16, 4))
+_ap.add_argument("--llm-quant-type", default="fp4", choices=("fp4", "nf4"))
+ARGS = _ap.parse_args()
 DEV = "cuda:0"
 PX = int(os.environ.get("PX", 1024))
 t_all = time.perf_counter()
@@ -49,9 +56,10 @@ specs = ip_adapter_specs(bcfg, 1024)
 ck = {"image_proj": synthetic_state_dict(specs["image_proj"], seed=7), "ip_adapter": synthetic_state_dict(specs["ip_adapter"], seed=7)}
 lcfg = vicuna_7b(32000 + len(ADDED_TOKENS))
 ltok = StubLlamaTokenizer(32000)
-lm = llm_mod.HipInstructAny2PixLM(lcfg, DEV, max_positions=512)
+lm = llm_mod.HipInstructAny2PixLM(lcfg, DEV, max_positions=512, load_in_4bit=ARGS.llm_bits == 4, bnb_4bit_quant_type=ARGS.llm_quant_type)
 lm.load_state_dict(iter_synthetic(llm_param_specs(lcfg), 9, DEV, torch.float16))
-print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior, LLM)", flush=True)
+print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior, LLM with {lm.weight_bits}-bit "
+      f"projections: arena {lm.arena.numel() / 1e9:.2f} GB)", flush=True)
 
 stages = {}
 

@@ -9,7 +9,11 @@ the library had for M = 1, `ia2p_linear_small`.
           and `ia2p_linear_small` (M = 1) in the same process, interleaved, each launch on another copy of the weights out of a pool larger
           than the 256 MiB Infinity Cache so both read from HBM; device events around one pass over the pool; median of REPS repetitions.
 
-    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--skip-decode] [--skip-gemv]
+  --bits 4 [--quant-type fp4|nf4]: part 1 runs both weight formats one after the other in the one process (fp16, then 4-bit: codes + one
+          fp32 absmax per 64 weights, 0.5625 bytes per projection weight), and part 2 gets a third column for `ia2p_llm_gemv_q4` on the same
+          shapes, interleaved with the other two, its pool holding the quantised copies of the same matrices (a pool over 256 MiB as well).
+
+    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--bits 4] [--quant-type fp4] [--skip-decode] [--skip-gemv]
 """
 import argparse
 import ctypes as C
@@ -22,7 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from instructany2pix_amd import _ffi
-from instructany2pix_amd.config import vicuna_7b
+from instructany2pix_amd.config import BNB_4BIT_CODEBOOKS, vicuna_7b
 from instructany2pix_amd.llm import HipInstructAny2PixLM
 from instructany2pix_amd.weights import iter_synthetic, llm_param_specs
 
@@ -30,16 +34,17 @@ DEV = "cuda:0"
 COPY_RATE = 6.29e12
 
 
-def decode_part(layers, tokens):
+def decode_part(layers, tokens, bits=16, quant_type="fp4"):
     cfg = vicuna_7b(32000)
     cfg.num_hidden_layers = layers
     t0 = time.perf_counter()
-    lm = HipInstructAny2PixLM(cfg, DEV, max_positions=256)
+    lm = HipInstructAny2PixLM(cfg, DEV, max_positions=256, load_in_4bit=bits == 4, bnb_4bit_quant_type=quant_type)
     lm.load_state_dict(iter_synthetic(llm_param_specs(cfg), 7, DEV, torch.float16))
     torch.cuda.synchronize()
-    print(f"model ready in {time.perf_counter() - t0:.1f} s ({layers} layers, arena {lm.arena.numel() / 1e9:.2f} GB)", flush=True)
+    fmt = "fp16" if bits == 16 else f"4-bit {quant_type}"
+    print(f"[{fmt}] model ready in {time.perf_counter() - t0:.1f} s ({layers} layers, arena {lm.arena.numel() / 1e9:.3f} GB)", flush=True)
     H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
-    wbytes = 2 * (layers * (4 * H * H + 3 * H * I) + V * H)
+    wbytes = int((2 if bits == 16 else 0.5625) * layers * (4 * H * H + 3 * H * I)) + 2 * V * H
     g = torch.Generator().manual_seed(1)
     prompt = torch.randint(3, V, (64,), generator=g)
     nxt = torch.randint(3, V, (tokens,), generator=g).tolist()
@@ -53,15 +58,16 @@ def decode_part(layers, tokens):
             lm.decode(t)
         torch.cuda.synchronize(); t2 = time.perf_counter()
         ms = (t2 - t1) * 1e3 / tokens
-        print(f"request {rnd}: prefill(64) {(t1 - t0) * 1e3:.2f} ms; decode {ms:.3f} ms per token over {tokens} tokens; "
+        print(f"[{fmt}] request {rnd}: prefill(64) {(t1 - t0) * 1e3:.2f} ms; decode {ms:.3f} ms per token over {tokens} tokens; "
               f"{wbytes / 1e9:.2f} GB of weights per token -> {wbytes / (ms * 1e-3) / 1e12:.2f} TB/s = {wbytes / (ms * 1e-3) / COPY_RATE:.3f} of the copy rate",
               flush=True)
     del lm
     torch.cuda.empty_cache()
 
 
-def gemv_part(reps):
+def gemv_part(reps, bits=16, quant_type="fp4"):
     lib = _ffi.lib()
+    cb = (C.c_float * 16)(*BNB_4BIT_CODEBOOKS[quant_type])
     g = torch.Generator(device=DEV).manual_seed(2)
     print("GEMV vs linear_small, M = 1, weights cycled through a pool > 256 MiB, median us per launch:")
     for N, K in ((12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008)):
@@ -82,19 +88,45 @@ def gemv_part(reps):
             for w in pool:
                 _ffi.check(lib.ia2p_linear_small(s, _ffi.ptr(x16), _ffi.ptr(w), None, _ffi.ptr(o16), 1, N, K, 0, 0))
 
-        run_gemv(); run_small()
+        runs = [("gemv", run_gemv), ("small", run_small)]
+        if bits == 4:
+            qbytes = lib.ia2p_llm_q4_packed_bytes(N, K) + 4 * (N * K // 64)
+            qcopies = max(4, -(-(640 << 20) // qbytes))
+            qpool = []
+            for i in range(qcopies):
+                w = pool[i] if i < copies else (torch.randn(N, K, generator=g, device=DEV, dtype=torch.float32) * K ** -0.5).half()
+                packed = torch.empty(lib.ia2p_llm_q4_packed_bytes(N, K), dtype=torch.uint8, device=DEV)
+                absmax = torch.empty(N * K // 64, dtype=torch.float32, device=DEV)
+                _ffi.check(lib.ia2p_llm_quantize_q4(s, _ffi.ptr(w), N, K, cb, _ffi.ptr(packed), _ffi.ptr(absmax)), None, llm=True)
+                qpool.append((packed, absmax))
+            del w
+            o4 = torch.empty(N, dtype=torch.float32, device=DEV)
+
+            def run_q4():
+                for packed, absmax in qpool:
+                    _ffi.check(lib.ia2p_llm_gemv_q4(s, _ffi.ptr(packed), _ffi.ptr(absmax), cb, _ffi.ptr(x32), _ffi.ptr(o4), N, K), None, llm=True)
+
+            runs.append(("q4", run_q4))
+        for _, fn in runs:
+            fn()
         torch.cuda.synchronize()
         err = float((o32 - o16.float().reshape(-1)).abs().max())
-        times = {"gemv": [], "small": []}
+        times = {name: [] for name, _ in runs}
+        per = {"gemv": copies, "small": copies, "q4": qcopies if bits == 4 else 1}
         for _ in range(reps):
-            for name, fn in (("gemv", run_gemv), ("small", run_small)):
+            for name, fn in runs:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(); fn(); e1.record()
                 e1.synchronize()
-                times[name].append(e0.elapsed_time(e1) * 1e3 / copies)
+                times[name].append(e0.elapsed_time(e1) * 1e3 / per[name])
         a, b = statistics.median(times["gemv"]), statistics.median(times["small"])
         print(f"  {N:6d} x {K:5d} ({nbytes / 1e6:6.1f} MB, pool of {copies}): llm_gemv {a:7.2f} us ({nbytes / a / 1e6:.2f} TB/s), linear_small {b:7.2f} us "
               f"({nbytes / b / 1e6:.2f} TB/s), ratio {b / a:.2f}x, min {min(times['gemv']):.2f} / {min(times['small']):.2f}, max |difference of the outputs| {err:.2e}", flush=True)
+        if bits == 4:
+            q = statistics.median(times["q4"])
+            print(f"  {'':6s}   {'':5s}  4-bit {quant_type} ({qbytes / 1e6:6.1f} MB, pool of {qcopies}): llm_gemv_q4 {q:7.2f} us ({qbytes / q / 1e6:.2f} TB/s of the bytes it reads), "
+                  f"min {min(times['q4']):.2f}, fp16 / 4-bit time {a / q:.2f}x", flush=True)
+            del qpool
         del pool
         torch.cuda.empty_cache()
 
@@ -104,12 +136,16 @@ if __name__ == "__main__":
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--tokens", type=int, default=100)
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--bits", type=int, default=16, choices=(16, 4))
+    ap.add_argument("--quant-type", default="fp4", choices=sorted(BNB_4BIT_CODEBOOKS))
     ap.add_argument("--skip-decode", action="store_true")
     ap.add_argument("--skip-gemv", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("llm_decode_bench needs the GPU: no timing is reported without one")
     if not a.skip_gemv:
-        gemv_part(a.reps)
+        gemv_part(a.reps, a.bits, a.quant_type)
     if not a.skip_decode:
         decode_part(a.layers, a.tokens)
+        if a.bits == 4:
+            decode_part(a.layers, a.tokens, 4, a.quant_type)
