@@ -263,6 +263,15 @@ ia2p_status ia2p_qproj_attention(void* stream, const void* X, const void* Wq, co
  * weight (rows: all of to_q, then to_k, then to_v; gamma-folded when ln != NULL, as ia2p_gemm_ex); bias [3*heads*64] or NULL (ignored with ln). */
 ia2p_status ia2p_qkv_self_attention(void* stream, const void* X, const void* Wqkv, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo,
                                     int B, int heads, int K);
+/* The same launch carrying the layer's slice of the context K/V projection (reference attention_processor.py:358-359 `attn.to_k` / `attn.to_v` of the text rows,
+ * :379-380 `to_k_ip` / `to_v_ip` of the image-token rows of IPAttnProcessor2_0) on the compute units its (image, head) tiles leave empty -- what ia2p_unet_forward does
+ * in every step for each block that takes the fused launch. context [B, L, ctx_dim]: rows [0, L - Li) of every context are text, the last Li the image tokens (Li = 0:
+ * text only, Wkv_ip / kv_ip NULL). Wkv_text / Wkv_ip [N, ctx_dim] (K rows then V rows, N = 2 * heads * 64 in the UNet); kv_text [B * (L - Li), ldkv], kv_ip [B * Li, ldkv].
+ * O and the K/V written have the bits of ia2p_qkv_self_attention and of ia2p_project_context's columns of the layer. When B * heads tiles + the slice's 128 x 160 tiles
+ * exceed the device's compute units the projections run as launches of their own in front; *in_launch (optional) says which way it went. */
+ia2p_status ia2p_qkv_self_attention_ctx(void* stream, const void* X, const void* Wqkv, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo,
+                                        int B, int heads, int K, const void* context, int L, int Li, int ctx_dim, const void* Wkv_text, const void* Wkv_ip,
+                                        void* kv_text, void* kv_ip, int ldkv, int N, int* in_launch);
 /* The `attn_map` side effect of IPAttnProcessor2_0 (reference attention_processor.py:390-391; stored on the processor, read only by the
  * attention-map hooks of diffusion/ip_adapter/utils.py:15-20):  out[b,h,q,t] = sum_d Q[b,q,h*64+d] * softmax_t(Kip[b,t,h*64+d]) -- the
  * softmax binds to ip_key^T, i.e. runs over the TOKEN axis, unscaled, before the matmul. Q rows stride ldq, Kip [B*ntok, ldk], out fp16

@@ -76,7 +76,7 @@ __device__ __forceinline__ void store8_wt(__amdgpu_buffer_rsrc_t r, size_t byte_
 }
 // Experiment knobs (A/B runs of a structure or a heuristic constant) are read from the environment only in builds made with -DIA2P_EXPERIMENTS
 // (IA2P_EXTRA_FLAGS=-DIA2P_EXPERIMENTS python -m instructany2pix_amd.build --force); the product library answers with the built-in default.
-// The eight runtime switches the product does read are listed in DESIGN.md §4 (IA2P_LN_FOLD, IA2P_XATTN_FUSE, IA2P_PREFETCH, IA2P_WT, IA2P_TILE_GROUP,
+// The nine runtime switches the product does read are listed in DESIGN.md §4 (IA2P_LN_FOLD, IA2P_XATTN_FUSE, IA2P_CTX_KV_INLAUNCH, IA2P_PREFETCH, IA2P_WT, IA2P_TILE_GROUP,
 // IA2P_SPLITK_INKERNEL, IA2P_TUNE_LOG, IA2P_TUNE_EXCLUDE).
 static inline const char* ia2p_exp_env(const char* name) {
 #ifdef IA2P_EXPERIMENTS
@@ -213,6 +213,18 @@ static inline bool ia2p_conv_halo_ok(const GemmArgs& a) {
          c3 % 64 == 0 && a.Cin2 == c2 && (a.A3 == nullptr || a.A2 != nullptr) && a.K == 9 * a.Cin + c2 + c3 && a.M % (a.Ho * a.Wo) == 0 && !a.rpb && !a.geglu &&
          ia2p_fits_buffer(a.M, a.lda) && ia2p_fits_buffer(a.N, a.ldw) && (!a.A2 || ia2p_fits_buffer(a.M, a.lda2)) && (!a.A3 || ia2p_fits_buffer(a.M, a.lda3));
 }
+
+// Context K/V tiles riding in the fused QKV + self-attention launch (qxattn.hip, round 7): workgroups [tiles, tiles + nt[0] + nt[1]) of that launch are plain
+// 128 x 160 ping-pong GEMM tiles of the layer's slice of the context projection (reference attention_processor.py:358-359 to_k / to_v, :379-380 to_k_ip / to_v_ip) --
+// g[0]: text rows against the layer's rows of the stacked text weights, g[1]: image-token rows against the IP-Adapter pair. The work depends on nothing the step
+// computes and its first reader (the layer's cross-attention) follows the launch in stream order; it runs on the CUs the (image, head) tiles leave empty.
+struct CtxKvArgs {
+  GemmArgs g[2];
+  int nt[2];             // workgroups of g[0] / g[1] (0: none)
+};
+// host side of the same: a layer's slice of the context K/V projection as the executor hands it to ia2p_launch_qkv_sattn --
+// ctx [B, L, K] (row stride lda), text rows [0, Lt) of every context against Wt [N, K] -> Ct [B * Lt, ldc], image-token rows [Lt, L) against Wi -> Ci [B * Li, ldc]
+struct CtxKvSlice { const half_t* ctx; int lda, L, Lt, Li, B; const half_t* Wt; const half_t* Wi; half_t* Ct; half_t* Ci; int ldc, N, K; };
 
 struct GemmPlan { int variant; int splitk; int gn = 0; };      // gn = 1 (measured plans of 3x3 sites behind a GroupNorm only): the norm runs INSIDE the halo-staged convolution (conv_halo_kernel.h GN = 1)
 // tile variants of gemm_f16_kernel (id = index): {BM, BN, LDS ring stages}; 4 waves (2 x 2), BK = 64

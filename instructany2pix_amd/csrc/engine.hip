@@ -466,9 +466,11 @@ static int gn_epilogue_rows(const GemmArgs& a, bool conv, int variant, int split
 }
 // gw != nullptr: the launch also leaves the GroupNorm statistics of its output (gn_fold.h) -- from its own epilogue when the tile allows, else from a gn_colstats_kernel pass
 static void run_gemm(RunCtx* c, GemmArgs& a, bool conv, const char* what, double flops, double bytes, int* stat_slots = nullptr, GnWant* gw = nullptr) {
-  if (c->tuning && !c->dry && !c->failed) tune_site(c, a, conv);
+  const int plan_n = c->plan_n > 0 ? c->plan_n : a.N;      // (a column range of a stacked projection: the whole projection's plan -- project_context)
+  c->plan_n = 0;
+  if (c->tuning && !c->dry && !c->failed && plan_n == a.N) tune_site(c, a, conv);
   c->tune_fused = nullptr; c->tune_gn_ms = 0.0;
-  const GemmPlan pl = ia2p_gemm_plan(a.M, a.N, a.K, conv, a.geglu != 0);
+  const GemmPlan pl = ia2p_gemm_plan(a.M, plan_n, a.K, conv, a.geglu != 0);
   if (pl.variant < 0 || pl.variant >= IA2P_GEMM_NVARIANT) { fail(c, IA2P_ERR_INVALID, "%s: tile variant %d out of range", what, pl.variant); return; }
   if (c->tuning && !c->dry && pl.splitk > 1 && (size_t)pl.splitk * a.M * a.N * sizeof(float) > c->tune_slab_bytes) {
     fail(c, IA2P_ERR_NOMEM, "%s: plan (variant %d, K split %d) needs %zu bytes of slabs, the autotune scratch holds %zu", what, pl.variant, pl.splitk,
@@ -615,6 +617,7 @@ struct Fwd {
   // the tensor -- possibly much later (the skips of the down path) --, released with the tensor
   std::unordered_map<size_t, GnStats> gst;
   bool gn_on = false;
+  std::unordered_map<int, int> kv_inlaunch;      // context K/V column (TBlock::kv_col) -> 1: left for the block's fused QKV + self-attention launch to project (plan_context_kv); 2: done
   bool tune_like = false;      // the autotune pass (or the dry pass that sizes the workspace for it): GroupNorm launches, plus what tune_site needs to time the fused forms beside them
 };
 static void gst_put(Fwd& f, T2 t, const GnStats& s) { if (s.ok() && t.off != (size_t)-1) f.gst[t.off] = s; else if (s.buf.off != (size_t)-1) wsfree(f.c, s.buf); }
@@ -782,7 +785,8 @@ static T2 run_resnet(Fwd& f, const Resnet& r, T2 x, int H, int Wd, const T2* x2t
 }
 
 // QKV projection (LayerNorm folded) + the self-attention that consumes it in ONE launch (qxattn.hip): Q, K, V never leave the CU. x: O / ldo / B / heads / Nq = 256
-static void op_qkv_sattn(RunCtx* c, const half_t* A, int lda, const half_t* W, const LnIn* ln, int M, int C, const AttnArgs& x) {
+// ck != nullptr: the launch also projects the layer's context K / V on the CUs its (image, head) tiles leave empty (CtxKvSlice; the caller asked ia2p_qkv_sattn_ctx_ok)
+static void op_qkv_sattn(RunCtx* c, const half_t* A, int lda, const half_t* W, const LnIn* ln, int M, int C, const AttnArgs& x, const CtxKvSlice* ck = nullptr) {
   GemmArgs a;
   memset(&a, 0, sizeof a);
   a.pad = 1;
@@ -798,9 +802,11 @@ static void op_qkv_sattn(RunCtx* c, const half_t* A, int lda, const half_t* W, c
     ++c->stamp_n;
   }
 #endif
-  ProfScope ps(c, PK_QKVATTN, 2.0 * M * 3.0 * C * C + 4.0 * x.B * x.heads * (double)x.Nq * x.Nq * 64, 2.0 * ((double)M * C + 3.0 * C * C + (double)M * C));
+  const double ck_rows = ck ? (double)ck->B * ck->L : 0.0;      // (the slices' work is booked with the launch that carries it: the role's TFLOP/s stays what the launch did)
+  ProfScope ps(c, PK_QKVATTN, 2.0 * M * 3.0 * C * C + 4.0 * x.B * x.heads * (double)x.Nq * x.Nq * 64 + (ck ? 2.0 * ck_rows * ck->N * ck->K : 0.0),
+               2.0 * ((double)M * C + 3.0 * C * C + (double)M * C) + (ck ? 2.0 * (ck_rows * ck->K + (ck->Li > 0 ? 2.0 : 1.0) * ck->N * ck->K + ck_rows * ck->N) : 0.0));
   ps.pf = a.pf ? (double)a.pf_bytes : 0.0;
-  CHECK_LAUNCH(c, ia2p_launch_qkv_sattn(a, x, c->stream), "qkv projection + self-attention");
+  CHECK_LAUNCH(c, ia2p_launch_qkv_sattn(a, x, c->stream, ck), "qkv projection + self-attention");
 }
 
 static void op_attn(RunCtx* c, const AttnArgs& a) {
@@ -836,6 +842,95 @@ static void op_qxattn(RunCtx* c, const half_t* A, int lda, const half_t* W, cons
   CHECK_LAUNCH(c, ia2p_launch_qproj_xattn(a, x, c->stream), "to_q + cross-attention");
 }
 
+// context K/V of every cross-attention layer in one GEMM each (text rows / image-token rows of ctx); per layer: reference
+// attention_processor.py:358-359 (to_k/to_v) and :379-380 (to_k_ip/to_v_ip). kv_text: [B*Lt, kv_rows], kv_ip: [B*Li, kv_rows].
+// [col0, col0 + ncols): the layers whose columns are projected (ncols < 0: all). A column range runs on the plan of the whole projection -- same tile, same K split,
+// hence the same bits whichever way the columns are cut (and no plan-table entries of its own).
+static void project_context(ia2p_ctx* c, const half_t* context, int L, int B, half_t* kv_text, half_t* kv_ip, int col0 = 0, int ncols = -1) {
+  RegionScope rs(c, PR_TRANSFORMER);
+  RoleScope role(c, ROLE_CTX_KV);
+  const int ctxd = c->cfg.cross_attention_dim;
+  const int Lt = c->ip_enabled ? L - c->ip_tokens : L, Li = c->ip_enabled ? c->ip_tokens : 0;
+  if (ncols < 0) ncols = c->kv_rows - col0;
+  const bool part = ncols != c->kv_rows;
+  if (part) c->plan_n = c->kv_rows;
+  op_gemm(c, context, ctxd, W_(c, c->kv_text_base + (size_t)col0 * ctxd), nullptr, nullptr, 0, kv_text ? kv_text + col0 : nullptr, c->kv_rows, B * Lt, ncols, ctxd, 0, Lt, L, 0);
+  if (part && Li) c->plan_n = c->kv_rows;
+  if (Li) op_gemm(c, context, ctxd, W_(c, c->kv_ip_base + (size_t)col0 * ctxd), nullptr, nullptr, 0, kv_ip ? kv_ip + col0 : nullptr, c->kv_rows, B * Li, ncols, ctxd, 0, Li, L, Lt);
+}
+
+// does transformer block b of t, at HW tokens per image, take the fused QKV + self-attention launch? (workspace and arena offsets are 256-byte aligned: the dry pass, with
+// null pointers, decides the same way)
+static bool sattn_fusable(Fwd& f, const Transformer& t, const TBlock& b, int HW, const half_t* tk, const float* st, int slots, half_t* O) {
+#ifdef IA2P_NO_SATTN_FUSE      // A/B builds: projection and self-attention as two launches everywhere
+  return false;
+#else
+  ia2p_ctx* c = f.c;
+  const int C = t.c, M = f.B * HW;
+  if (!(c->ln_fold && c->sattn_fuse && HW == 256 && C == t.heads * 64 && (long)f.B * t.heads >= c->xattn_min_tiles)) return false;
+  AttnArgs sa;
+  memset(&sa, 0, sizeof sa);
+  sa.O = O; sa.ldo = C; sa.B = f.B; sa.heads = t.heads; sa.Nq = HW; sa.nseg = 1;
+  GemmArgs g;
+  memset(&g, 0, sizeof g);
+  g.A = tk; g.W = W_(c, b.fqkv); g.M = M; g.N = 3 * C; g.K = C; g.lda = C; g.ldw = C; g.ldc = 3 * C;
+  g.ln_stats = st; g.ln_slots = slots; g.ln_cs = (const float*)(c->arena + b.cs1); g.ln_bias = (const float*)(c->arena + b.lb1);
+  return ia2p_qkv_sattn_ok(g, sa);
+#endif
+}
+// the slice of the context projection that belongs to block b (columns [kv_col, kv_col + 2C) of kv_text / kv_ip)
+static CtxKvSlice ctx_kv_slice(Fwd& f, const Transformer& t, const TBlock& b) {
+  ia2p_ctx* c = f.c;
+  const int ctxd = c->cfg.cross_attention_dim;
+  const int Li = c->ip_enabled ? c->ip_tokens : 0, Lt = f.L - Li;
+  CtxKvSlice k;
+  memset(&k, 0, sizeof k);
+  k.ctx = f.ctxp; k.lda = ctxd; k.L = f.L; k.Lt = Lt; k.Li = Li; k.B = f.B;
+  k.Wt = W_(c, b.wkv2); k.Wi = Li ? W_(c, b.wkvip) : nullptr;
+  k.Ct = f.kv_text.p ? f.kv_text.p + b.kv_col : nullptr; k.Ci = (Li && f.kv_ip.p) ? f.kv_ip.p + b.kv_col : nullptr;
+  k.ldc = c->kv_rows; k.N = 2 * t.c; k.K = ctxd;
+  return k;
+}
+// Which blocks' context K/V does their own fused QKV + self-attention launch project? Those that take the fused launch (sattn_fusable) with room for the slice's tiles
+// beside the (image, head) tiles (ia2p_qkv_sattn_ctx_ok) -- and only while the whole projection's plans run without a K split: the in-launch tiles do not split, and a
+// split changes the order of the sums. Fills f.kv_inlaunch and returns the column ranges [first, second) left for the head of the step, merged where adjacent.
+static std::vector<std::pair<int, int>> plan_context_kv(Fwd& f, int h, int w) {
+  ia2p_ctx* c = f.c;
+  std::vector<std::pair<int, int>> up_front;
+  f.kv_inlaunch.clear();
+  const int ctxd = c->cfg.cross_attention_dim;
+  const int Li = c->ip_enabled ? c->ip_tokens : 0, Lt = f.L - Li;
+  bool on = c->ctx_kv_inlaunch && ia2p_gemm_plan(f.B * Lt, c->kv_rows, ctxd, false, false).splitk <= 1 && (!Li || ia2p_gemm_plan(f.B * Li, c->kv_rows, ctxd, false, false).splitk <= 1);
+  std::vector<std::pair<int, int>> cols;      // every block's {column, width}
+  auto visit = [&](const Transformer& t, int HW) {
+    for (const TBlock& b : t.blocks) {
+      cols.push_back({b.kv_col, 2 * t.c});
+      if (!on || !sattn_fusable(f, t, b, HW, nullptr, c->dry ? nullptr : (const float*)16, 1, nullptr)) continue;
+      AttnArgs sa;
+      memset(&sa, 0, sizeof sa);
+      sa.B = f.B; sa.heads = t.heads;
+      if (ia2p_qkv_sattn_ctx_ok(sa, ctx_kv_slice(f, t, b))) f.kv_inlaunch[b.kv_col] = 1;
+    }
+  };
+  int H = h, Wd = w;
+  for (const Stage& st : c->down) {
+    for (const Transformer& t : st.att) visit(t, H * Wd);
+    if (st.resample) { H = (H - 1) / 2 + 1; Wd = (Wd - 1) / 2 + 1; }
+  }
+  visit(c->mid_t, H * Wd);
+  for (const Stage& st : c->up) {
+    for (const Transformer& t : st.att) visit(t, H * Wd);
+    if (st.resample) { H *= 2; Wd *= 2; }
+  }
+  std::sort(cols.begin(), cols.end());
+  for (const auto& cw : cols) {
+    if (f.kv_inlaunch.count(cw.first)) continue;
+    if (!up_front.empty() && up_front.back().second == cw.first) up_front.back().second = cw.first + cw.second;
+    else up_front.push_back({cw.first, cw.first + cw.second});
+  }
+  return up_front;
+}
+
 static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, bool out_stats = false) {
   ia2p_ctx* c = f.c;
   RegionScope rs(c, PR_TRANSFORMER);
@@ -869,25 +964,22 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
     // as ONE launch when there are enough (image, head) pairs to fill the chip (same threshold and switch as the fused cross-attention)
     {
     RoleScope role_sa(c, ROLE_QKV_SATTN);
-#ifdef IA2P_NO_SATTN_FUSE      // A/B builds: projection and self-attention as two launches everywhere
-    bool fuse_sa = false;
-#else
-    bool fuse_sa = fold && c->sattn_fuse && HW == 256 && C == t.heads * 64 && (long)f.B * t.heads >= c->xattn_min_tiles;
-#endif
+    // (a site the fused tile does not take -- alignment of O / the folded constants, the 31-bit operand limit -- runs projection + attention as two launches)
+    const bool fuse_sa = sattn_fusable(f, t, b, HW, tk.p, st, slots, att.p);
     AttnArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.O = att.p; sa.ldo = C; sa.B = f.B; sa.heads = t.heads; sa.Nq = HW; sa.nseg = 1; sa.scale_log2e = sl2e;
     sa.seg[0].nkeys = HW; sa.seg[0].weight = 1.f;
-    if (fuse_sa) {      // a site the fused tile does not take (alignment of O / the folded constants, the 31-bit operand limit) runs projection + attention as two launches
-      GemmArgs g;       // (workspace and arena offsets are 256-byte aligned: the dry pass, with null pointers, decides the same way)
-      memset(&g, 0, sizeof g);
-      g.A = tk.p; g.W = W_(c, b.fqkv); g.M = M; g.N = 3 * C; g.K = C; g.lda = C; g.ldw = C; g.ldc = 3 * C;
-      g.ln_stats = st; g.ln_slots = slots; g.ln_cs = F_(b.cs1); g.ln_bias = F_(b.lb1);
-      fuse_sa = ia2p_qkv_sattn_ok(g, sa);
-    }
+    // this block's context K / V: left to this launch by plan_context_kv, on the CUs the (image, head) tiles leave empty
+    auto kvi = f.kv_inlaunch.find(b.kv_col);
+    const bool kv_mine = kvi != f.kv_inlaunch.end() && kvi->second == 1;
+    const CtxKvSlice ck = ctx_kv_slice(f, t, b);
+    const bool kv_here = kv_mine && fuse_sa && ia2p_qkv_sattn_ctx_ok(sa, ck);
+    if (kv_mine && !kv_here) project_context(c, f.ctxp, f.L, f.B, f.kv_text.p, f.kv_ip.p, b.kv_col, 2 * C);      // (the site refused after all: today's route, for this block's columns)
+    if (kv_mine) kvi->second = 2;
     if (fuse_sa) {
       const LnIn ln{st, slots, F_(b.cs1), F_(b.lb1), eps};
-      op_qkv_sattn(c, tk.p, C, W_(c, b.fqkv), &ln, M, C, sa);
+      op_qkv_sattn(c, tk.p, C, W_(c, b.fqkv), &ln, M, C, sa, kv_here ? &ck : nullptr);
     } else if (fold) {
       const LnIn ln{st, slots, F_(b.cs1), F_(b.lb1), eps};
       op_gemm(c, tk.p, C, W_(c, b.fqkv), nullptr, nullptr, 0, qkv.p, 3 * C, M, 3 * C, C, 0, 0, 0, 0, 0, &ln);
@@ -952,17 +1044,6 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
   return out;
 }
 
-// context K/V of every cross-attention layer in one GEMM each (text rows / image-token rows of ctx); per layer: reference
-// attention_processor.py:358-359 (to_k/to_v) and :379-380 (to_k_ip/to_v_ip). kv_text: [B*Lt, kv_rows], kv_ip: [B*Li, kv_rows].
-static void project_context(ia2p_ctx* c, const half_t* context, int L, int B, half_t* kv_text, half_t* kv_ip) {
-  RegionScope rs(c, PR_TRANSFORMER);
-  RoleScope role(c, ROLE_CTX_KV);
-  const int ctxd = c->cfg.cross_attention_dim;
-  const int Lt = c->ip_enabled ? L - c->ip_tokens : L, Li = c->ip_enabled ? c->ip_tokens : 0;
-  op_gemm(c, context, ctxd, W_(c, c->kv_text_base), nullptr, nullptr, 0, kv_text, c->kv_rows, B * Lt, c->kv_rows, ctxd, 0, Lt, L, 0);
-  if (Li) op_gemm(c, context, ctxd, W_(c, c->kv_ip_base), nullptr, nullptr, 0, kv_ip, c->kv_rows, B * Li, c->kv_rows, ctxd, 0, Li, L, Lt);
-}
-
 // kv_cached != nullptr: the context projections were computed before (ia2p_project_context) and are read from there
 static ia2p_status run_forward(ia2p_ctx* c, const half_t* sample, float timestep, const half_t* context, int L,
                                const half_t* text_embeds, const half_t* time_ids, half_t* out, int B, int h, int w,
@@ -1019,7 +1100,12 @@ static ia2p_status run_forward(ia2p_ctx* c, const half_t* sample, float timestep
       if (Li) f.kv_ip = wsalloc(c, (size_t)B * Li * c->kv_rows);
       // (On a low-priority side stream beside the start of the step -- round 3, docs/LOG.md -- the projection cost +0.7 ms per step: the work is conserved, the
       //  interleaving costs. The step belongs on ONE queue; the pipelines hoist the projection out of the loop anyway.)
-      project_context(c, context, L, B, f.kv_text.p, f.kv_ip.p);
+      // Round 7: a block that takes the fused QKV + self-attention launch has its columns projected by extra workgroups of that launch (plan_context_kv); the head of the
+      // step keeps the other blocks' column ranges. The autotune pass projects everything here as well -- the whole projection's plan is what every range runs on, and
+      // it is measured on the whole projection -- and lets the fused launches rewrite their columns with the same bits.
+      const std::vector<std::pair<int, int>> up_front = plan_context_kv(f, h, w);
+      if (c->tuning || f.tune_like) project_context(c, context, L, B, f.kv_text.p, f.kv_ip.p);
+      else for (const auto& r : up_front) project_context(c, context, L, B, f.kv_text.p, f.kv_ip.p, r.first, r.second - r.first);
     }
   }
 
@@ -1819,6 +1905,52 @@ ia2p_status ia2p_qkv_self_attention(void* stream, const void* X, const void* Wqk
   if (!ia2p_qkv_sattn_ok(a, x)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention: shape / alignment not supported by the fused tile");
   hipError_t e = ia2p_launch_qkv_sattn(a, x, (hipStream_t)stream);
   RET_HIP(e, "qkv_self_attention");
+}
+// The same launch with the layer's slice of the context K/V projection riding on the CUs the (image, head) tiles leave empty (what the executor does per step for every
+// block that takes the fused launch; reference attention_processor.py:358-359 to_k / to_v on the text rows, :379-380 to_k_ip / to_v_ip on the image-token rows).
+// *in_launch (optional) = 1 when the slice ran inside the launch, 0 when fused tiles + context tiles exceed the device's compute units and the two projections ran as
+// launches of their own in front of it (the executor's route for such a block). Same bits either way.
+ia2p_status ia2p_qkv_self_attention_ctx(void* stream, const void* X, const void* Wqkv, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo, int B, int heads, int K,
+                                        const void* context, int L, int Li, int ctx_dim, const void* Wkv_text, const void* Wkv_ip, void* kv_text, void* kv_ip, int ldkv, int N,
+                                        int* in_launch) {
+  if (!X || !Wqkv || !O || !context || !Wkv_text || !kv_text || (Li > 0 && (!Wkv_ip || !kv_ip))) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention_ctx: null argument");
+  if (ln && (!ln->stats || !ln->colsum || !ln->fbias || ln->slots < 1)) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention_ctx: incomplete ia2p_ln_fold");
+  if (B < 1 || heads < 1 || K < 64 || K % 64 || ldo % 8 || (((uintptr_t)O) & 15)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: K=%d (multiple of 64), ldo=%d (multiple of 8), O 16-byte aligned", K, ldo);
+  if (Li < 0 || L <= Li || L > 0xffff || ctx_dim < 64 || ctx_dim % 64 || N < 8 || N % 8 || ldkv < N || ldkv % 8 || (((uintptr_t)kv_text) & 15) || (Li > 0 && (((uintptr_t)kv_ip) & 15)))
+    return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: L=%d > Li=%d >= 0, ctx_dim=%d (multiple of 64), N=%d and ldkv=%d (multiples of 8, ldkv >= N), outputs 16-byte aligned", L, Li, ctx_dim, N, ldkv);
+  if (!zero_page()) return fail(nullptr, IA2P_ERR_HIP, "cannot allocate zero page");
+  GemmArgs a;
+  memset(&a, 0, sizeof a);
+  a.pad = 1;
+  a.A = (const half_t*)X; a.W = (const half_t*)Wqkv; a.zero = zero_page(); a.M = B * 256; a.N = 3 * heads * 64; a.K = K; a.ldw = K; a.lda = K; a.ldc = a.N;
+  a.bias = (const half_t*)bias; a.rows_per_batch = 1;
+  if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->colsum; a.ln_bias = ln->fbias; a.ln_eps = ln->eps; }
+  AttnArgs x;
+  memset(&x, 0, sizeof x);
+  x.O = (half_t*)O; x.ldo = ldo; x.B = B; x.heads = heads; x.Nq = 256; x.nseg = 1;
+  x.scale_log2e = 0.125f * 1.4426950408889634f;
+  x.seg[0].nkeys = 256; x.seg[0].weight = 1.f;
+  if (!ia2p_qkv_sattn_ok(a, x)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: shape / alignment not supported by the fused tile");
+  const int Lt = L - Li;
+  CtxKvSlice k;
+  memset(&k, 0, sizeof k);
+  k.ctx = (const half_t*)context; k.lda = ctx_dim; k.L = L; k.Lt = Lt; k.Li = Li; k.B = B; k.Wt = (const half_t*)Wkv_text; k.Wi = (const half_t*)Wkv_ip;
+  k.Ct = (half_t*)kv_text; k.Ci = (half_t*)kv_ip; k.ldc = ldkv; k.N = N; k.K = ctx_dim;
+  const bool inl = ia2p_qkv_sattn_ctx_ok(x, k);
+  if (in_launch) *in_launch = inl ? 1 : 0;
+  hipError_t e = hipSuccess;
+  if (!inl) {      // the two projections as launches of their own (project_context's, for this slice)
+    for (int seg = 0; seg < (Li > 0 ? 2 : 1) && e == hipSuccess; ++seg) {
+      GemmArgs g;
+      memset(&g, 0, sizeof g);
+      g.pad = 1;
+      g.A = k.ctx; g.W = seg ? k.Wi : k.Wt; g.C = seg ? k.Ci : k.Ct; g.zero = zero_page(); g.M = B * (seg ? Li : Lt); g.N = N; g.K = ctx_dim; g.ldw = ctx_dim; g.lda = ctx_dim; g.ldc = ldkv;
+      g.rpb = seg ? Li : Lt; g.bstride = L; g.roff = seg ? Lt : 0; g.rows_per_batch = 1; g.m_fastest = g.M <= g.N ? 1 : 0; g.acc_scale = g.bias_scale = 1.f;
+      e = ia2p_launch_gemm_variant(g, false, ia2p_gemm_plan(g.M, g.N, g.K, false, false).variant, (hipStream_t)stream);
+    }
+  }
+  if (e == hipSuccess) e = ia2p_launch_qkv_sattn(a, x, (hipStream_t)stream, inl ? &k : nullptr);
+  RET_HIP(e, "qkv_self_attention_ctx");
 }
 ia2p_status ia2p_ip_attn_map(void* stream, const void* Q, int ldq, const void* Kip, int ldk, void* out, int B, int heads, int Nq, int ntok) {
   if (!Q || !Kip || !out || B < 1 || heads < 1 || Nq < 1) return fail(nullptr, IA2P_ERR_INVALID, "ip_attn_map: bad argument");

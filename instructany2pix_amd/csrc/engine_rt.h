@@ -36,7 +36,10 @@ hipError_t ia2p_launch_attention(const AttnArgs& a, hipStream_t s);
 bool ia2p_qproj_xattn_ok(const GemmArgs& a, const AttnArgs& x);
 hipError_t ia2p_launch_qproj_xattn(const GemmArgs& a, const AttnArgs& x, hipStream_t s);   // qxattn.hip: to_q tile -> attention core, one launch
 bool ia2p_qkv_sattn_ok(const GemmArgs& a, const AttnArgs& x);
-hipError_t ia2p_launch_qkv_sattn(const GemmArgs& a, const AttnArgs& x, hipStream_t s);      // qxattn.hip: QKV tile of one image x one head -> self-attention, one launch
+int ia2p_cu_count();                                                          // compute units of the current device (0: no device)
+int ia2p_qkv_sattn_ctx_tiles(const CtxKvSlice& k);
+bool ia2p_qkv_sattn_ctx_ok(const AttnArgs& x, const CtxKvSlice& k);         // fused tiles + context tiles fit the chip in one round (and the slice's shape is one the tile takes)
+hipError_t ia2p_launch_qkv_sattn(const GemmArgs& a, const AttnArgs& x, hipStream_t s, const CtxKvSlice* ctx = nullptr);      // qxattn.hip: QKV tile of one image x one head -> self-attention, one launch
 int ia2p_gn_chunks(int B, int HW);
 hipError_t ia2p_launch_groupnorm(const half_t* x, int ldx, half_t* y, int ldy, const half_t* gamma, const half_t* beta,
                                  float* partial, int B, int HW, int C, int G, float eps, int silu, hipStream_t s, const half_t* x2 = nullptr, int ldx2 = 0, int Ca = 0);
@@ -162,6 +165,8 @@ struct RunCtx {
   int gn_fuse = 1;           // 1: GroupNorm + SiLU of a ResnetBlock2D applied inside the halo-staged convolution that consumes it, statistics from the producers' epilogues;
                              // 0 (IA2P_GN_FUSE=0): GroupNorm launches; 2: the fused path's UNFUSED TWIN -- the same statistics, gn_apply_stats_kernel + the plain convolution (tests: same bits as 1)
   bool sattn_fuse = true;    // QKV projection + self-attention as one launch at 256 tokens per image (follows IA2P_XATTN_FUSE=0; IA2P_SATTN_FUSE in experiment builds)
+  bool ctx_kv_inlaunch = true;      // context K/V of a layer projected by extra workgroups of that layer's fused QKV + self-attention launch (IA2P_CTX_KV_INLAUNCH=0: all of it up front, for A/B runs)
+  int plan_n = 0;            // > 0: the NEXT run_gemm call takes the plan of the same problem with this many columns (a column range of a stacked projection runs on the whole projection's plan: same K split, same bits); reset by it
   bool ln_fold = true;       // LayerNorms folded into their consumer GEMMs (IA2P_LN_FOLD=0: separate layernorm_kernel launches, for A/B runs)
   bool prof = false;
 #ifdef IA2P_CLOCK_STAMP
@@ -198,6 +203,7 @@ struct RunCtx {
     if (const char* e = getenv("IA2P_PREFETCH")) prefetch = atoi(e) != 0;
     if (const char* e = getenv("IA2P_LN_FOLD")) ln_fold = atoi(e) != 0;
     if (const char* e = getenv("IA2P_XATTN_FUSE")) xattn_fuse = sattn_fuse = atoi(e) != 0;
+    if (const char* e = getenv("IA2P_CTX_KV_INLAUNCH")) ctx_kv_inlaunch = atoi(e) != 0;
     if (const char* e = getenv("IA2P_GN_FUSE")) gn_fuse = atoi(e);
     if (const char* e = ia2p_exp_env("IA2P_SATTN_FUSE")) sattn_fuse = atoi(e) != 0;
     if (const char* e = ia2p_exp_env("IA2P_SC_FUSE")) sc_fuse = atoi(e) != 0;

@@ -13,9 +13,10 @@
 // (profiles/r01g_gemm_loop_ablation.txt: the fill is the largest term of the 128x128 kernel).
 // XA != 0 (qxattn.hip; 128 x 64 tiles only): the tile is the to_q projection of 128 queries x ONE head and never leaves the CU -- the epilogue turns it
 // into the Q fragments of the attention core (attention_core.h, MODE = XA - 1) and writes the cross-attention output instead.
-template <int BM, int BN, int NSTAGE, bool CONV, int WGM = 2, int BK = 64, int PP = 0, int WGN = 2, int XA = 0>
+template <int BM, int BN, int NSTAGE, bool CONV, int WGM = 2, int BK = 64, int PP = 0, int WGN = 2, int XA = 0, bool SUB = false>
 __device__ __forceinline__ void gemm_tile_body(const half_t* hA, const half_t* hW, const half_t* hzero, int hM, int hN, int hK, int hlda, int hldw, int hrpb, int hbstride,
-                                               int hroff, int hsplitk, int hgroup_w, int hflags, const GemmArgs& p, const AttnArgs* xa, const float* pre_ln_stats = nullptr, int pre_ln_slots = 0) {
+                                               int hroff, int hsplitk, int hgroup_w, int hflags, const GemmArgs& p, const AttnArgs* xa, const float* pre_ln_stats = nullptr, int pre_ln_slots = 0, int bid0 = 0) {
+  // bid0: first block of this problem inside the launch (the context K/V tiles of the fused QKV + self-attention launch, below; 0 everywhere else)
   // hflags (preloaded with the other leading arguments): bit 0 = p.m_fastest, bit 1 = p.ln_stats != nullptr. Read from `p` they are scalar loads from the cold argument block
   // whose results stand between the workgroup's entry and its first DMA piece: the tile decode does not even use m_fastest under a grouped order, but the load was in flight
   // into registers the decode reuses (a wait for it, in every launch), and every launch asked p.ln_stats whether it had statistics to fetch ahead of its DMA.
@@ -38,7 +39,11 @@ __device__ __forceinline__ void gemm_tile_body(const half_t* hA, const half_t* h
   constexpr int KSUB = BK / 32;                                       // 32-deep MFMA sub-steps per k-tile
   extern __shared__ __attribute__((aligned(1024))) char smem[];
 
-  const int tid = threadIdx.x;
+  int tid_ = threadIdx.x;
+  // SUB: this body runs as a sub-problem behind the unlikely branch of another tile's kernel (the context K/V tiles, below). Its thread index is a value of its own: shared
+  // with the host tile's, `lane` has a user on both sides of that branch and stays in front of it, and the host tile's entry path grows by an instruction
+  if constexpr (SUB) asm volatile("" : "+v"(tid_));
+  const int tid = tid_;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // linear layers: both operands through buffer loads -- a piece is (descriptor, this lane's byte offset of its row and chunk at k = 0, scalar byte offset of the
@@ -51,13 +56,31 @@ __device__ __forceinline__ void gemm_tile_body(const half_t* hA, const half_t* h
 
   // ---- tile of this workgroup; blocks b, b+8, ... share an XCD (its L2): give each XCD a contiguous tile range
   const int tiles_m = (hM + BM - 1) / BM, tiles_n = (hN + BN - 1) / BN;
-  int bid = blockIdx.x;
+  int bid = blockIdx.x - bid0;
   const int nsplit = hsplitk > 1 ? hsplitk : 1;
   const int split = bid < tiles_m * tiles_n ? 0 : udiv_small(bid, tiles_m * tiles_n);          // >= nsplit: prefetch workgroup (the common case, a tile of an unsplit launch: one comparison)
   if (split < nsplit) bid -= split * tiles_m * tiles_n;
   if (__builtin_expect(split >= nsplit, 0)) {   // prefetch workgroup: touch its slice of the next kernel's weights and leave (out of line: a tile workgroup's start should FALL THROUGH -- every
                                                 // taken branch over a cold block is an instruction fetch the sequential prefetcher has not made, a few hundred ns at a launch's start)
     bid -= nsplit * tiles_m * tiles_n;
+    if constexpr (XA == 4) {
+      // fused QKV + self-attention launch: the blocks behind the (image, head) tiles are first the layer's context K/V tiles (CtxKvArgs, common.h), then the prefetch
+      // workgroups. Everything here is behind the unlikely branch: the fused tile's path to its first DMA piece is what it was. The descriptor sits behind `p` and the
+      // attention arguments in the argument block and is read cold (offset opaque to the optimizer, as p_opaque below: nothing of it is loaded ahead of the branch).
+      int off = 56 + (int)sizeof(GemmArgs) + (int)sizeof(AttnArgs);
+      asm volatile("" : "+s"(off));
+      const CtxKvArgs* ck = (const CtxKvArgs*)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+      const int nt0 = ck->nt[0], nct = nt0 + ck->nt[1];
+      if (bid < nct) {
+        const int which = bid >= nt0 ? 1 : 0;
+        const GemmArgs* g = ck->g + which;      // (a pointer into the argument block: a copy of the selected struct would live in scratch)
+        // the 128 x 160 ping-pong tile of the GEMM family (variant 19) as it is: same k-loop, same epilogue, same bits as the stand-alone projection
+        gemm_tile_body<128, 160, 3, false, 4, 64, 1, 2, 0, true>(g->A, g->W, g->zero, g->M, g->N, g->K, g->lda, g->ldw, g->rpb, g->bstride, g->roff, 0, g->group_w, g->m_fastest ? 1 : 0, *g, nullptr,
+                                                            nullptr, 0, (int)blockIdx.x - (which ? bid - nt0 : bid));
+        return;
+      }
+      bid -= nct;
+    }
     const long per = ((p.pf_bytes + p.pf_blocks - 1) / p.pf_blocks + 4095) & ~4095L;
     const long lo = (long)bid * per, hi = min(lo + per, p.pf_bytes & ~15L);
     const char* src = (const char*)p.pf;

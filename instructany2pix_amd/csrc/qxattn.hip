@@ -11,6 +11,8 @@
 // to running `gemm_f16_kernel<128, 64, ...>` + `attention_f16_kernel` (tests/test_ops_gpu.py).
 #include "gemm_kernel.h"
 
+#include <cstring>
+
 #ifndef IA2P_QX_STAGES
 #define IA2P_QX_STAGES 2      // LDS ring depth of the projection loop (build-time knob for A/B builds)
 #endif
@@ -79,7 +81,8 @@ hipError_t ia2p_launch_qproj_xattn(const GemmArgs& a, const AttnArgs& x, hipStre
 // attention core and writes only O: no QKV tensor (15.7 MB per layer at batch 8), no second launch. Same arithmetic in the same order as the stand-alone
 // pair: bit-identical to `ia2p_gemm_ex` + `ia2p_attention` (tests/test_ops_gpu.py).
 __global__ __launch_bounds__(512, 2) void qkv_sattn_kernel(const half_t* hA, const half_t* hW, const half_t* hzero, const float* h_ln_stats, int hM, int hN, int hK, int hlda, int hldw,
-                                                           int h_slots_gw, const GemmArgs p, const AttnArgs xa) {
+                                                           int h_slots_gw, const GemmArgs p, const AttnArgs xa, const CtxKvArgs ck) {
+  // (`ck`: the layer's context K/V tiles, blocks [tiles, tiles + ck.nt[0] + ck.nt[1]) -- read from the argument block by those workgroups only, gemm_kernel.h)
 #ifndef IA2P_SATTN_PP
 #define IA2P_SATTN_PP 3      // k-loop schedule of the fused QKV + self-attention tile: 3 = two-slot ping-pong, 0 = plain loop (one barrier per k-step); A/B builds
 #endif
@@ -93,10 +96,62 @@ bool ia2p_qkv_sattn_ok(const GemmArgs& a, const AttnArgs& x) {
          (!a.ln_stats || (((((uintptr_t)a.ln_cs) | ((uintptr_t)a.ln_bias)) & 15) == 0)) && ia2p_fits_buffer(a.M, a.lda) && ia2p_fits_buffer(a.N, a.ldw);
 }
 
-hipError_t ia2p_launch_qkv_sattn(const GemmArgs& a, const AttnArgs& x, hipStream_t s) {
+// ---- context K/V tiles of the launch (round 7). The (image, head) tiles number B * heads -- 160 on 256 CUs at batch 8 -- and hold a CU each (> 96 KiB of LDS): the
+//      other CUs stand idle for the whole launch. The layer's slice of the context projection (text rows x [2C, ctx] + image-token rows x [2C, ctx]; reference
+//      attention_processor.py:358-359, :379-380) depends on nothing the step computes and is first read by the layer's cross-attention, which follows this launch in
+//      stream order: it rides along as 128 x 160 ping-pong tiles, one per idle CU. Every workgroup of the launch asks for the fused tile's LDS, so a context tile never
+//      shares a CU with a fused tile. Taken only when fused tiles + context tiles fit the chip's CUs in ONE round: a context tile that had to queue up behind a
+//      fused tile would lengthen the launch instead of filling its holes.
+constexpr int CK_BM = 128, CK_BN = 160;
+int ia2p_cu_count() {
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 0; }
+  if (!cus[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); n = 0; }
+    cus[dev] = n > 0 ? n : -1;
+  }
+  return cus[dev] > 0 ? cus[dev] : 0;
+}
+int ia2p_qkv_sattn_ctx_tiles(const CtxKvSlice& k) {
+  const int tn = (k.N + CK_BN - 1) / CK_BN;
+  return ((k.B * k.Lt + CK_BM - 1) / CK_BM) * tn + (k.Li > 0 ? ((k.B * k.Li + CK_BM - 1) / CK_BM) * tn : 0);
+}
+// shapes only (the dry pass, with null pointers, decides as the live pass does)
+bool ia2p_qkv_sattn_ctx_ok(const AttnArgs& x, const CtxKvSlice& k) {
+  if (k.B < 1 || k.B != x.B || k.Lt < 1 || k.Li < 0 || k.L != k.Lt + k.Li || k.N < 8 || k.N % 8 || k.K < 64 || k.K % 64 || k.lda < k.K || k.ldc < k.N) return false;
+  if (k.Lt > 0xffff || k.Li > 0xffff || (long)k.B * k.L >= (1L << 21)) return false;
+  if (!ia2p_fits_buffer((size_t)k.B * k.L + k.L, k.lda) || !ia2p_fits_buffer(k.N, k.K)) return false;
+  return (long)x.B * x.heads + ia2p_qkv_sattn_ctx_tiles(k) <= ia2p_cu_count();
+}
+
+hipError_t ia2p_launch_qkv_sattn(const GemmArgs& a, const AttnArgs& x, hipStream_t s, const CtxKvSlice* ctx) {
   if (!ia2p_qkv_sattn_ok(a, x)) return hipErrorInvalidValue;
   constexpr int SMEM = EpiCfg<256, 192, 2, 4, 64, 2, 0>::SMEM;      // (the epilogue configuration does not depend on the k-loop schedule)
   static_assert(SMEM >= 96 * 1024 + (2 * 256 + 2 * 192) * 4, "K / V / Q images + row and column constants");
+  constexpr int CK_SMEM = EpiCfg<CK_BM, CK_BN, 3, 4, 64, 2, 1>::SMEM;
+  static_assert(CK_SMEM <= SMEM, "a context K/V tile runs in the fused tile's LDS request");
+  CtxKvArgs ck;
+  memset(&ck, 0, sizeof ck);
+  if (ctx) {
+    if (!ia2p_qkv_sattn_ctx_ok(x, *ctx) || !ctx->ctx || !ctx->Wt || !ctx->Ct || (ctx->Li > 0 && (!ctx->Wi || !ctx->Ci))) return hipErrorInvalidValue;
+    const int tn = (ctx->N + CK_BN - 1) / CK_BN;
+    auto fill = [&](GemmArgs& g, const half_t* W, half_t* C, int rows, int roff) {      // what op_gemm + launch_cfg make of the stand-alone projection
+      g.pad = 1;
+      g.A = ctx->ctx; g.W = W; g.C = C; g.zero = a.zero; g.M = ctx->B * rows; g.N = ctx->N; g.K = ctx->K; g.ldw = ctx->K; g.lda = ctx->lda; g.ldc = ctx->ldc;
+      g.rpb = rows; g.bstride = ctx->L; g.roff = roff; g.rows_per_batch = 1;
+      g.m_fastest = g.M <= g.N ? 1 : 0;
+      g.acc_scale = g.bias_scale = 1.f;
+      ia2p_gemm_prepare(g, CK_SMEM, CK_BM, CK_BN);
+    };
+    fill(ck.g[0], ctx->Wt, ctx->Ct, ctx->Lt, 0);
+    ck.nt[0] = ((ck.g[0].M + CK_BM - 1) / CK_BM) * tn;
+    if (ctx->Li > 0) {
+      fill(ck.g[1], ctx->Wi, ctx->Ci, ctx->Li, ctx->Lt);
+      ck.nt[1] = ((ck.g[1].M + CK_BM - 1) / CK_BM) * tn;
+    }
+  }
   static bool attr_set[64] = {false};
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -117,8 +172,9 @@ hipError_t ia2p_launch_qkv_sattn(const GemmArgs& a, const AttnArgs& x, hipStream
   y.seg[0].nkeys = 256; y.seg[0].weight = 1.f; y.nseg = 1;
   y.xcd_map = ((ia2p_wt_mask() & 8) && (size_t)x.B * x.Nq * x.ldo * 2 < (size_t)0x7ffffff0) ? 2 : 0;      // bit 1: write-through O
   const int extra = (a.pf && a.pf_bytes >= 4096) ? a.pf_blocks : 0;
+  const int nct = ck.nt[0] + ck.nt[1];
   int slots_gw;
-  if (tiles + extra >= (1 << 21) || !ia2p_pack_skgw(b.ln_stats ? b.ln_slots : 0, b.group_w, b.m_fastest, b.ln_stats != nullptr, &slots_gw)) return hipErrorInvalidValue;      // (udiv_small in the tile decode: counts below 2^21)
-  hipLaunchKernelGGL(qkv_sattn_kernel, dim3(tiles + extra), dim3(512), SMEM, s, b.A, b.W, b.zero, b.ln_stats, b.M, b.N, b.K, b.lda, b.ldw, slots_gw, b, y);
+  if (tiles + nct + extra >= (1 << 21) || !ia2p_pack_skgw(b.ln_stats ? b.ln_slots : 0, b.group_w, b.m_fastest, b.ln_stats != nullptr, &slots_gw)) return hipErrorInvalidValue;      // (udiv_small in the tile decode: counts below 2^21)
+  hipLaunchKernelGGL(qkv_sattn_kernel, dim3(tiles + nct + extra), dim3(512), SMEM, s, b.A, b.W, b.zero, b.ln_stats, b.M, b.N, b.K, b.lda, b.ldw, slots_gw, b, y, ck);
   return hipGetLastError();
 }
