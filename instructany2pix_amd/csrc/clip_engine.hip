@@ -1,4 +1,4 @@
-// CLIP text-encoder executor and its C ABI (ia2p_clip_*): see include/ia2p.h and DESIGN.md §8. Runtime and operator wrappers: engine_rt.h / engine.hip.
+// CLIP text-encoder executor and its C ABI (ia2p_clip_*): see include/ia2p.h and DESIGN.md §8. Runtime and operator wrappers: engine_rt.h / engine_rt.hip.
 #include "engine_rt.h"
 
 // =====================================================================================================================

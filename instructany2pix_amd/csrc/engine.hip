@@ -1,4 +1,5 @@
-// Host-side executor of one conditional-UNet evaluation + the C ABI (include/ia2p.h).
+// Host-side executor of one conditional-UNet evaluation + the ia2p_ctx C ABI (include/ia2p.h). The runtime it runs on is engine_rt.hip (shared with the other
+// executors), the context-less per-operator entry points are ops_abi.hip: nothing outside this file needs anything defined in it.
 //
 // The module wiring follows diffusers' UNet2DConditionModel with the SDXL-base config, i.e. the object the
 // reference calls at instructany2pix/ddim/pnp_pipeline.py:253-260 and ddim/sdxl_pipeline.py:832-839
@@ -12,19 +13,6 @@
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>      // types and prototypes only: the symbols are bound at run time (ia2p_bcast_arena), the library is not linked
-
-thread_local std::string g_err;
-
-const half_t* zero_page() {
-  static thread_local void* z[16] = {nullptr};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!z[dev]) {
-    if (hipMalloc(&z[dev], 256) != hipSuccess) return nullptr;
-    (void)hipMemset(z[dev], 0, 256);
-  }
-  return (const half_t*)z[dev];
-}
 
 struct Resnet {
   int cin, cout, temb_off;
@@ -52,33 +40,6 @@ struct Stage {            // one down/up block
   int rc;
 };
 
-static int g_xattn_min_tiles = -1;      // test hook: fusion threshold of contexts created from now on (< 0: the built-in 128)
-int ia2p_default_xattn_min_tiles() { return g_xattn_min_tiles; }
-extern "C" void ia2p_debug_set_xattn_min_tiles(int tiles) { g_xattn_min_tiles = tiles; }
-
-const char* prof_name(int k) {
-  static char buf[PK_NCLASS][64];
-  static const char* const other[] = {"attention_f16_kernel", "gn_stats_kernel+gn_apply_kernel", "layernorm_kernel",
-                                      "embed_kernel+linear_small_kernel", "conv_in_kernel", "conv_out_kernel", "concat_kernel", "splitk_reduce_kernel", "qproj_xattn_kernel", "qkv_sattn_kernel"};
-  if (k >= PK_HALO_GN0) { snprintf(buf[k], sizeof buf[k], "conv_halo_f16_kernel<%d, 1>", IA2P_GEMM_TILES[24 + k - PK_HALO_GN0].bn); return buf[k]; }
-  if (k >= PK_ATTN) return other[k - PK_ATTN];
-  const GemmTile t = IA2P_GEMM_TILES[(k % PK_CONV0) % IA2P_GEMM_NVARIANT];
-  if (t.halo) snprintf(buf[k], sizeof buf[k], "conv_halo_f16_kernel<%d, 0>", t.bn);
-  else if (t.pp == 4) snprintf(buf[k], sizeof buf[k], "gemm_geglu_f16_kernel");
-  else if (t.pp == 2) snprintf(buf[k], sizeof buf[k], "gemm_f16_kernel<%d, %d, %d, %s, 2, 64, 2, 4>", t.bm, t.bn, t.stages, k >= PK_CONV0 ? "true" : "false");
-  else if (t.pp) snprintf(buf[k], sizeof buf[k], "gemm_f16_kernel<%d, %d, %d, %s, 4, 64, 1, 2>", t.bm, t.bn, t.stages, k >= PK_CONV0 ? "true" : "false");
-  else if (t.bn == 80) snprintf(buf[k], sizeof buf[k], "gemm_f16_kernel<%d, %d, %d, %s, 4, 64, 0, 1>", t.bm, t.bn, t.stages, k >= PK_CONV0 ? "true" : "false");
-  else snprintf(buf[k], sizeof buf[k], "gemm_f16_kernel<%d, %d, %d, %s, 2, 64, 0, 2>", t.bm, t.bn, t.stages, k >= PK_CONV0 ? "true" : "false");
-  return buf[k];
-}
-
-const char* role_name(int r) {
-  static const char* const names[ROLE_NROLE] = {"other", "ff_in (GEGLU projection, norm3 folded)", "ff_out", "qkv + self-attention (norm1 folded)", "attention out-projections (attn1 / attn2 to_out)",
-                                                "to_q + cross-attention (norm2 folded)", "conv3x3 (ResnetBlock2D convs incl. fused shortcut, resample convs)", "groupnorm (+SiLU)",
-                                                "proj_in / proj_out", "context K/V projection", "time / add embeddings", "conv_in / conv_out"};
-  return r >= 0 && r < ROLE_NROLE ? names[r] : "?";
-}
-
 struct ia2p_ctx : RunCtx {
   ia2p_unet_config cfg;
   int ip_enabled = 0, ip_tokens = 4;
@@ -97,21 +58,6 @@ struct ia2p_ctx : RunCtx {
   int n_attn2 = 0;
   size_t arena_raw_elems = 0;   // head of the arena: everything a checkpoint provides; [arena_raw_elems, arena_elems) is derived at finalize
 };
-
-ia2p_status fail(RunCtx* c, ia2p_status st, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (c) { c->err = buf; c->failed = true; }
-  g_err = buf;
-  return st;      // (K-split tickets: invalidated where a launch / sync error is seen -- CHECK_LAUNCH, RET_HIP, fail_hip -- not for argument refusals)
-}
-ia2p_status fail_hip(RunCtx* c, hipError_t e, const char* what) {
-  if (e != hipErrorInvalidValue) ia2p_sk_counters_invalidate();
-  return fail(c, IA2P_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // plan: enumerate parameters in the diffusers key layout (same walk as instructany2pix_amd/weights.py)
@@ -323,233 +269,6 @@ static ia2p_status build_plan(ia2p_ctx* c) {
   return IA2P_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// run helpers
-// ---------------------------------------------------------------------------------------------------------------------
-T2 wsalloc(RunCtx* c, size_t elems) {
-  const size_t off = c->ws.alloc(elems * sizeof(half_t));
-  if (off == (size_t)-1) { if (!c->failed) fail(c, IA2P_ERR_NOMEM, "workspace too small"); return T2{off, nullptr}; }
-  return T2{off, c->dry ? nullptr : (half_t*)(c->ws_base + off)};
-}
-void wsfree(RunCtx* c, T2 t) {
-  if (t.off == (size_t)-1) return;
-  c->ws.release(t.off);
-}
-
-hipEvent_t get_event(RunCtx* c) {
-  if (!c->evpool.empty()) { hipEvent_t e = c->evpool.back(); c->evpool.pop_back(); return e; }
-  hipEvent_t e; (void)hipEventCreate(&e); return e;
-}
-static void set_prefetch(RunCtx* c, GemmArgs& a, const half_t* W, size_t bytes) {
-  if (c->dry) { if (c->record) c->wseq.push_back({W, bytes}); return; }
-  if (!c->prefetch || c->widx + 1 > c->wseq.size()) { ++c->widx; return; }
-  const bool last = c->widx + 1 == c->wseq.size();
-  if (last && !c->tail_pf) { ++c->widx; return; }
-  const std::pair<const half_t*, size_t> nx = last ? std::make_pair(c->tail_pf, c->tail_pf_bytes) : c->wseq[c->widx + 1];
-  ++c->widx;
-  if (nx.second > ((size_t)96 << 20)) return;           // larger than the Infinity Cache can usefully hold
-  a.pf = nx.first; a.pf_bytes = (long)nx.second;
-  static const size_t pf_cap = ia2p_exp_env("IA2P_PF_BLOCKS") ? (size_t)atoi(ia2p_exp_env("IA2P_PF_BLOCKS")) : 128;            // tuning hooks: most prefetch workgroups per launch,
-  static const size_t pf_per = ia2p_exp_env("IA2P_PF_BLOCK_BYTES") ? (size_t)atol(ia2p_exp_env("IA2P_PF_BLOCK_BYTES")) : 131072;   // bytes per workgroup below that
-  a.pf_blocks = (int)std::max<size_t>(1, std::min<size_t>(pf_cap, (nx.second + pf_per - 1) / pf_per));
-}
-
-// In-place measurement of the candidate plans of one GEMM / conv site (autotune pass). Every candidate runs once untimed and
-// tune_reps times bracketed by events (round-robin over the candidates), with the L2s flushed (a memset over the flush region)
-// before every launch and the site's activations read back in: in the real sequence the activations were just written and the weights sit in the Infinity Cache (prefetched by
-// the previous launch), not in L2. The prefetch workgroups of the site are part of every candidate launch. The fastest
-// goes into the plan table. Re-running a site is harmless: outputs are rewritten (in-place residuals only drift).
-static void tune_site(RunCtx* c, const GemmArgs& a, bool conv) {
-  // (what the caller left for THIS site -- taken and cleared before anything else: the pointer refers to the caller's frame)
-  const GemmArgs* fa = c->tune_fused;
-  const float gn_ms = (float)c->tune_gn_ms;
-  c->tune_fused = nullptr; c->tune_gn_ms = 0.0;
-  if (ia2p_plan_lookup(a.M, a.N, a.K, conv, a.geglu != 0, nullptr)) return;
-  std::vector<GemmPlan> cands;
-  ia2p_gemm_candidates(a.M, a.N, a.K, conv, a.geglu != 0, c->tune_slab_bytes, ia2p_exp_env("IA2P_TUNE_SLACK") ? atof(ia2p_exp_env("IA2P_TUNE_SLACK")) : 2.5, &cands);      // (2.5 x the modelled best: -0.04 ms per step against 1.7 on the same box, profiles/r05t_slack_ab.txt; 4.0 measures 4 x the candidates for the same picks)
-  static const bool tune_log = getenv("IA2P_TUNE_LOG") != nullptr;      // every candidate's time, for calibrating the cost model
-  hipEvent_t e0 = get_event(c), e1 = get_event(c);
-  // Rounds over all candidates (round -1 untimed), so that clock / cache drift during the measurement hits every candidate alike;
-  // a candidate's score is its FASTEST round (launch-time noise only ever adds).
-  std::vector<float> best_ms(cands.size(), 1e30f);
-  std::vector<char> ok(cands.size(), 1);
-  for (size_t i = 0; i < cands.size(); ++i)
-    if (IA2P_GEMM_TILES[cands[i].variant].halo && !(conv && ia2p_conv_halo_ok(a) && cands[i].splitk <= a.Cin / 64)) ok[i] = 0;      // (this site is not one for the halo-staged kernel: its twin tile is in the list anyway)
-  for (int r = -1; r < c->tune_reps; ++r)
-    for (size_t i = 0; i < cands.size(); ++i) {
-      if (!ok[i]) continue;
-      GemmArgs b = a;
-      b.splitk = cands[i].splitk > 1 ? cands[i].splitk : 0;
-      b.partial = cands[i].splitk > 1 ? (float*)c->tune_scratch : nullptr;
-      bool good = hipMemsetAsync(c->tune_scratch + c->tune_slab_bytes, r & 1, c->tune_flush_bytes, c->stream) == hipSuccess;
-      // ... but the site's activations (and residual) were written by the launch just before it in the real sequence: warm them again
-      const size_t a_bytes = conv ? (size_t)(a.M / std::max(1, a.Ho * a.Wo)) * a.Hs * a.Ws * a.Cin * sizeof(half_t)
-                                  : (a.rpb ? 0 : (size_t)a.M * a.lda * sizeof(half_t));
-      good = good && ia2p_launch_touch(a.A, std::min<size_t>(a_bytes, (size_t)64 << 20), (unsigned*)c->tune_scratch, c->stream) == hipSuccess;
-      if (a.residual) good = good && ia2p_launch_touch(a.residual, std::min<size_t>((size_t)a.M * a.ldr * sizeof(half_t), (size_t)64 << 20), (unsigned*)c->tune_scratch, c->stream) == hipSuccess;
-      good = good && hipEventRecord(e0, c->stream) == hipSuccess;
-      good = good && ia2p_launch_gemm_variant(b, conv, cands[i].variant, c->stream) == hipSuccess;
-      good = good && hipEventRecord(e1, c->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
-      float ms = 0.f;
-      good = good && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-      if (!good) { (void)hipGetLastError(); ok[i] = 0; continue; }
-      if (r >= 0 && ms < best_ms[i]) best_ms[i] = ms;
-    }
-  c->evpool.push_back(e0); c->evpool.push_back(e1);
-  float fastest = 1e30f;
-  for (size_t i = 0; i < cands.size(); ++i) {
-    if (!ok[i]) continue;
-    if (tune_log) fprintf(stderr, "[ia2p tune] %d %d %d conv=%d geglu=%d variant=%d splitk=%d us=%.2f\n", a.M, a.N, a.K, (int)conv, a.geglu, cands[i].variant, cands[i].splitk, 1e3 * best_ms[i]);
-    fastest = std::min(fastest, best_ms[i]);
-  }
-  // candidates come best-modelled first: among those within 2 % of the fastest measurement the model's favourite wins (stable picks)
-  GemmPlan best{-1, 1};
-  for (size_t i = 0; i < cands.size() && best.variant < 0; ++i)
-    if (ok[i] && best_ms[i] <= 1.02f * fastest) best = cands[i];
-  // A site behind a GroupNorm (the caller left c->tune_fused: the site's GroupNorm-FUSED form -- raw operand, producer statistics -- and c->tune_gn_ms: what the
-  // GroupNorm launch in front of it just took): the fused launch on every halo-staged tile / K split it may run on is timed the same way, and taken when it beats
-  // GroupNorm launch + best plain plan. The fused kernel normalises every halo image in LDS beside its MFMAs (+15 ... 25 % per launch): it pays where the norm's
-  // launch is expensive against the convolution (few input channels on the large maps), not everywhere.
-  if (fa && conv && best.variant >= 0 && gn_ms > 0.f) {
-    std::vector<GemmPlan> fc;
-    ia2p_conv_gn_candidates(*fa, c->tune_slab_bytes, &fc);
-    std::vector<float> fms(fc.size(), 1e30f);
-    hipEvent_t f0 = get_event(c), f1 = get_event(c);
-    for (int r = -1; r < c->tune_reps; ++r)
-      for (size_t i = 0; i < fc.size(); ++i) {
-        GemmArgs b = *fa;
-        b.splitk = fc[i].splitk > 1 ? fc[i].splitk : 0;
-        b.partial = fc[i].splitk > 1 ? (float*)c->tune_scratch : nullptr;
-        bool good = hipMemsetAsync(c->tune_scratch + c->tune_slab_bytes, r & 1, c->tune_flush_bytes, c->stream) == hipSuccess;
-        const size_t a_bytes = (size_t)(fa->M / std::max(1, fa->Ho * fa->Wo)) * fa->Hs * fa->Ws * fa->gn.C0 * sizeof(half_t);
-        good = good && ia2p_launch_touch(fa->A, std::min<size_t>(a_bytes, (size_t)64 << 20), (unsigned*)c->tune_scratch, c->stream) == hipSuccess;
-        if (fa->A1b) good = good && ia2p_launch_touch(fa->A1b, std::min<size_t>((size_t)fa->M * fa->lda1b * sizeof(half_t), (size_t)64 << 20), (unsigned*)c->tune_scratch, c->stream) == hipSuccess;
-        if (fa->residual) good = good && ia2p_launch_touch(fa->residual, std::min<size_t>((size_t)fa->M * fa->ldr * sizeof(half_t), (size_t)64 << 20), (unsigned*)c->tune_scratch, c->stream) == hipSuccess;
-        good = good && hipEventRecord(f0, c->stream) == hipSuccess;
-        good = good && ia2p_launch_gemm_variant(b, true, fc[i].variant, c->stream) == hipSuccess;
-        good = good && hipEventRecord(f1, c->stream) == hipSuccess && hipEventSynchronize(f1) == hipSuccess;
-        float ms = 0.f;
-        good = good && hipEventElapsedTime(&ms, f0, f1) == hipSuccess;
-        if (!good) { (void)hipGetLastError(); fms[i] = -1.f; continue; }
-        if (r >= 0 && fms[i] >= 0.f && ms < fms[i]) fms[i] = ms;
-      }
-    c->evpool.push_back(f0); c->evpool.push_back(f1);
-    float unfused = 1e30f;
-    for (size_t i = 0; i < cands.size(); ++i)
-      if (ok[i]) unfused = std::min(unfused, best_ms[i]);
-    unfused += gn_ms;
-    int bi = -1;
-    for (size_t i = 0; i < fc.size(); ++i) {
-      if (tune_log && fms[i] >= 0.f) fprintf(stderr, "[ia2p tune] %d %d %d conv=1 FUSED groupnorm variant=%d splitk=%d us=%.2f (groupnorm launch %.2f us + best plain plan = %.2f us)\n", fa->M, fa->N, fa->K, fc[i].variant, fc[i].splitk,
-                                             1e3 * fms[i], 1e3 * gn_ms, 1e3 * unfused);
-      if (fms[i] >= 0.f && fms[i] < 1e29f && (bi < 0 || fms[i] < fms[bi])) bi = (int)i;
-    }
-    if (bi >= 0 && fms[bi] < 0.97f * unfused) best = fc[bi];      // (3 % margin: the fused form also pays for the statistics in its producers' epilogues)
-  }
-  if (best.variant < 0) { fail(c, IA2P_ERR_HIP, "autotune: no candidate plan ran for %d x %d x %d", a.M, a.N, a.K); return; }
-  ia2p_plan_set(a.M, a.N, a.K, conv, a.geglu != 0, best);
-  ++c->tune_sites;
-}
-
-// plan, K-split slabs, profiling class and launch of one GEMM / implicit-GEMM conv
-// rows per slot of the stand-alone statistics pass over an image of HW rows: the largest multiple of 16 that divides HW and is <= 1024 (0: none)
-static int gn_fallback_rows(int HW) {
-  for (int k = 1; k <= HW / 16; ++k)
-    if (HW % k == 0 && (HW / k) % 16 == 0 && HW / k <= 1024) return HW / k;
-  return 0;
-}
-// rows per slot of the column sums a launch's own epilogue leaves (0: it cannot): whole 16-row runs, whole tiles per image, 16-byte epilogue routes, at most
-// IA2P_GN_MAX_SLOTS slots per image; a K split only when it combines inside the launch
-static int gn_epilogue_rows(const GemmArgs& a, bool conv, int variant, int splitk, bool combined, int HW) {
-  const int bm = IA2P_GEMM_TILES[ia2p_gemm_variant_ran(a, conv, variant)].bm;
-  return (!a.geglu && !a.act && a.ldc % 8 == 0 && a.N % 8 == 0 && bm % 16 == 0 && HW % bm == 0 && a.M % HW == 0 && HW / bm <= IA2P_GN_MAX_SLOTS && (splitk <= 1 || combined)) ? bm : 0;
-}
-// gw != nullptr: the launch also leaves the GroupNorm statistics of its output (gn_fold.h) -- from its own epilogue when the tile allows, else from a gn_colstats_kernel pass
-static void run_gemm(RunCtx* c, GemmArgs& a, bool conv, const char* what, double flops, double bytes, int* stat_slots = nullptr, GnWant* gw = nullptr) {
-  const int plan_n = c->plan_n > 0 ? c->plan_n : a.N;      // (a column range of a stacked projection: the whole projection's plan -- project_context)
-  c->plan_n = 0;
-  if (c->tuning && !c->dry && !c->failed && plan_n == a.N) tune_site(c, a, conv);
-  c->tune_fused = nullptr; c->tune_gn_ms = 0.0;
-  const GemmPlan pl = ia2p_gemm_plan(a.M, plan_n, a.K, conv, a.geglu != 0);
-  if (pl.variant < 0 || pl.variant >= IA2P_GEMM_NVARIANT) { fail(c, IA2P_ERR_INVALID, "%s: tile variant %d out of range", what, pl.variant); return; }
-  if (c->tuning && !c->dry && pl.splitk > 1 && (size_t)pl.splitk * a.M * a.N * sizeof(float) > c->tune_slab_bytes) {
-    fail(c, IA2P_ERR_NOMEM, "%s: plan (variant %d, K split %d) needs %zu bytes of slabs, the autotune scratch holds %zu", what, pl.variant, pl.splitk,
-         (size_t)pl.splitk * a.M * a.N * sizeof(float), c->tune_slab_bytes);
-    return;
-  }
-  T2 slab{(size_t)-1, nullptr};
-  if (pl.splitk > 1) {
-    a.splitk = pl.splitk;
-    if (c->tuning && !c->dry) a.partial = (float*)c->tune_scratch;      // plans change during the pass: slabs live outside the workspace
-    else { slab = wsalloc(c, (size_t)pl.splitk * a.M * a.N * 2); a.partial = (float*)slab.p; }
-  }
-  struct Rel { RunCtx* c; T2 t; ~Rel() { wsfree(c, t); } } rel{c, slab};
-  int combined = pl.splitk > 1 && ia2p_splitk_inkernel(a.M, a.N, pl.splitk);     // (dry pass: the policy's answer; the launcher reports what it really did)
-  int gn_rows_epi = 0;
-  if (gw) {      // (a launch whose tile cannot take the sums leaves none: the consumer that wants them runs the canonical pass itself, gn_ensure_stats)
-    gw->out = GnStats{};
-    gn_rows_epi = gn_epilogue_rows(a, conv, pl.variant, pl.splitk, combined != 0, gw->HW);
-    if (gn_rows_epi) {
-      gw->out.buf = wsalloc(c, (size_t)(a.M / gn_rows_epi) * a.N * 8);      // double2 per slot and column
-      a.gn_out = (double*)gw->out.buf.p;
-    }
-  }
-#ifdef IA2P_CLOCK_STAMP
-  if (c->stamp_buf && c->role == c->stamp_role && (pl.splitk <= 1 || combined) && !c->dry && !c->tuning && c->stamp_n < c->stamp_cap) {
-    const GemmTile& t = IA2P_GEMM_TILES[pl.variant];
-    const int tiles = ((a.M + t.bm - 1) / t.bm) * ((a.N + t.bn - 1) / t.bn) * (pl.splitk > 1 ? pl.splitk : 1);      // (workgroups: a K split launches one per tile and slice)
-    if (tiles <= RunCtx::STAMP_WG && !t.halo) {
-      unsigned long long* rec = c->stamp_buf + (size_t)c->stamp_n * RunCtx::STAMP_WG * 8;
-      if (pl.splitk > 1) a.stamp = rec;
-      else a.partial = (float*)rec;
-      c->stamp_meta.push_back({a.M, a.N, a.K, pl.splitk > 1 ? -100 * pl.splitk - pl.variant : pl.variant, tiles});
-      ++c->stamp_n;
-    }
-  }
-#endif
-  {
-    ProfScope ps(c, (conv ? PK_CONV0 : PK_GEMM0) + pl.variant, flops, bytes);
-    ps.pf = a.pf ? (double)a.pf_bytes : 0.0;
-    int ran = pl.variant;
-    CHECK_LAUNCH(c, ia2p_launch_gemm_variant(a, conv, pl.variant, c->stream, false, &combined, &ran), what);
-    ps.set_class(conv && a.gn.st0 && ran >= 24 && ran <= 26 ? PK_HALO_GN0 + ran - 24 : (conv ? PK_CONV0 : PK_GEMM0) + ran);      // (a halo-staged plan runs its gathered twin at a site it does not take: booked under the kernel that ran)
-  }
-  if (pl.splitk > 1 && !combined) {
-    ProfScope ps(c, PK_REDUCE, 0, (double)pl.splitk * a.M * a.N * 4 + 2.0 * a.M * a.N);
-    CHECK_LAUNCH(c, ia2p_launch_splitk_reduce(a, c->stream), what);
-  }
-  if (gw && gw->out.buf.off != (size_t)-1) {
-    if (gn_rows_epi && (pl.splitk <= 1 || combined)) gw->out.rows = gn_rows_epi;
-    else { wsfree(c, gw->out.buf); gw->out = GnStats{}; }      // (the launcher finished the K split with a reduce launch after all)
-  }
-  // row-statistics slots of this launch's output: one per tile column, or ONE when a reduce launch wrote it
-  if (stat_slots) *stat_slots = (pl.splitk > 1 && !combined) ? 1 : (a.N + IA2P_GEMM_TILES[pl.variant].bn - 1) / IA2P_GEMM_TILES[pl.variant].bn;
-}
-
-static GemmArgs gemm_args(RunCtx* c, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
-                          half_t* C, int ldc, int M, int N, int K, int geglu, int rpb, int bstride, int roff, int ldw,
-                          const LnIn* ln, float* stats_out, int act) {
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->cs; a.ln_bias = ln->lb; a.ln_eps = ln->eps; }
-  a.stats_out = stats_out;
-  a.act = act;
-  a.A = A; a.W = W; a.C = C; a.zero = zero_page(); a.M = M; a.N = N; a.K = K; a.ldw = ldw ? ldw : K; a.lda = lda; a.ldc = ldc;
-  a.rpb = rpb; a.bstride = bstride; a.roff = roff; a.bias = bias; a.residual = residual; a.ldr = ldr; a.geglu = geglu;
-  a.rows_per_batch = 1;
-  a.m_fastest = (long)M * K <= (long)N * K ? 1 : 0;
-  a.acc_scale = c->ep_acc_scale; a.bias_scale = c->ep_bias_scale; c->ep_acc_scale = c->ep_bias_scale = 1.f;
-  return a;
-}
-static double gemm_bytes(int M, int N, int K, int geglu, bool residual) { return 2.0 * ((double)M * K + (double)N * K + (double)M * (geglu ? N / 2 : N) + (residual ? (double)M * N : 0)); }
-void op_gemm(RunCtx* c, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
-             half_t* C, int ldc, int M, int N, int K, int geglu, int rpb, int bstride, int roff, int ldw,
-             const LnIn* ln, float* stats_out, int* stat_slots, int act, GnWant* gw) {
-  GemmArgs a = gemm_args(c, A, lda, W, bias, residual, ldr, C, ldc, M, N, K, geglu, rpb, bstride, roff, ldw, ln, stats_out, act);
-  set_prefetch(c, a, W, (size_t)N * K * sizeof(half_t));
-  run_gemm(c, a, false, "gemm", 2.0 * M * N * K, gemm_bytes(M, N, K, geglu, residual != nullptr), stat_slots, gw);
-}
 // GEGLU feed-forward: ff.net.0 (a: K = C, N = 8 C packed, GEGLU epilogue -> H [M, 4 C]) then ff.net.2 (b: reads H, + bias + residual): two launches.
 // (One launch with a per-row-panel hand-off between the two was built and measured in round 3: +0.45 ... +0.8 ms per step, docs/LOG.md; removed in round 4.)
 static void run_ffn(RunCtx* c, GemmArgs& a, GemmArgs& b, int* stat_slots_b) {
@@ -558,51 +277,6 @@ static void run_ffn(RunCtx* c, GemmArgs& a, GemmArgs& b, int* stat_slots_b) {
   { RoleScope role(c, ROLE_FF_IN); run_gemm(c, a, false, "ff.net.0", 2.0 * a.M * (double)a.N * a.K, gemm_bytes(a.M, a.N, a.K, 1, false)); }
   RoleScope role(c, ROLE_FF_OUT);
   run_gemm(c, b, false, "ff.net.2", 2.0 * b.M * (double)b.N * b.K, gemm_bytes(b.M, b.N, b.K, 0, true), stat_slots_b);
-}
-void op_conv3(RunCtx* c, const half_t* X, int B, int Hs, int Ws, int Cin, const half_t* W, const half_t* bias, int Co,
-              int stride, int up, const half_t* rowvec, int rowvec_ld, const half_t* residual, half_t* Y, int pad_lo, const half_t* X2, int Cin2,
-              const half_t* X3, int Cin3, const ConvGn* gn, GnWant* gw) {
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  // (appended blocks are described by their channel counts: in a dry pass the pointers are null, the shapes -- hence plans and slabs -- must not change)
-  if ((Cin2 > 0 && (stride != 1 || up || pad_lo != 1 || Cin2 % 64)) || (Cin3 > 0 && (Cin2 <= 0 || Cin3 % 64)) || Cin2 < 0 || Cin3 < 0 ||
-      (!c->dry && ((Cin2 > 0) != (X2 != nullptr) || (Cin3 > 0) != (X3 != nullptr)))) { fail(c, IA2P_ERR_SHAPE, "conv3x3 with appended 1x1 blocks: stride 1, no upsampling, Cin2 / Cin3 %% 64 == 0 (stride %d up %d pad %d Cin %d Cin2 %d Cin3 %d, X2 %s, X3 %s)", stride, up, pad_lo, Cin, Cin2, Cin3, X2 ? "set" : "null", X3 ? "set" : "null"); return; }
-  a.pad = pad_lo;           // zero rows/cols before the image; one row/col of zeros after it in every mode
-  const int Hv = Hs << up, Wv = Ws << up;
-  a.Ho = (Hv + pad_lo + 1 - 3) / stride + 1; a.Wo = (Wv + pad_lo + 1 - 3) / stride + 1;
-  a.A = X; a.W = W; a.C = Y; a.zero = zero_page(); a.M = B * a.Ho * a.Wo; a.N = Co; a.K = 9 * Cin + Cin2 + Cin3; a.ldw = a.K; a.lda = Cin; a.ldc = Co;
-  if (gn && gn->fused) {      // GroupNorm + SiLU applied inside the convolution: X [| X1b] is the RAW input of the norm (the caller asked ia2p_conv_gn_fusable)
-    a.lda = gn->C0; a.A1b = gn->X1b; a.lda1b = Cin - gn->C0;
-    a.gn.st0 = (const double*)gn->s0.buf.p; a.gn.rows0 = gn->s0.rows; a.gn.st1 = (const double*)gn->s1.buf.p; a.gn.rows1 = gn->s1.rows; a.gn.C0 = gn->C0;
-    a.gn.gamma = gn->gamma; a.gn.beta = gn->beta; a.gn.groups = gn->groups; a.gn.gs = Cin / gn->groups; a.gn.eps = gn->eps; a.gn.silu = 1;
-  }
-  a.A2 = X2; a.lda2 = Cin2; a.Cin2 = Cin2;
-  a.A3 = X3; a.lda3 = Cin3; a.Cin3 = Cin3;
-  a.Hs = Hs; a.Ws = Ws; a.stride = stride; a.up = up; a.Cin = Cin;
-  a.bias = bias; a.rowvec = rowvec; a.rowvec_ld = rowvec_ld; a.rows_per_batch = a.Ho * a.Wo; a.residual = residual; a.ldr = Co;
-  a.m_fastest = 0;
-  a.acc_scale = c->ep_acc_scale; a.bias_scale = c->ep_bias_scale; c->ep_acc_scale = c->ep_bias_scale = 1.f;
-  set_prefetch(c, a, W, (size_t)Co * a.K * sizeof(half_t));
-  GemmArgs fa;      // autotune pass: the site's GroupNorm-fused form, for tune_site to time against GroupNorm launch + plain plan
-  if (gn && gn->tune && !gn->fused && c->tuning && !c->dry && gn->s0.ok() && gn->Xraw) {
-    fa = a;
-    fa.A = gn->Xraw; fa.lda = gn->C0; fa.A1b = gn->X1b; fa.lda1b = Cin - gn->C0;
-    fa.gn.st0 = (const double*)gn->s0.buf.p; fa.gn.rows0 = gn->s0.rows; fa.gn.st1 = gn->X1b ? (const double*)gn->s1.buf.p : nullptr; fa.gn.rows1 = gn->s1.rows; fa.gn.C0 = gn->C0;
-    fa.gn.gamma = gn->gamma; fa.gn.beta = gn->beta; fa.gn.groups = gn->groups; fa.gn.gs = Cin / gn->groups; fa.gn.eps = gn->eps; fa.gn.silu = 1;
-    if (ia2p_conv_gn_ok(fa)) c->tune_fused = &fa;
-  }
-  RoleScope role(c, ROLE_CONV3X3);
-  run_gemm(c, a, true, "conv3x3", 2.0 * a.M * (double)Co * a.K, 2.0 * ((double)B * Hs * Ws * Cin + (double)Co * a.K + (double)a.M * Co + (residual ? (double)a.M * Co : 0) + (double)a.M * (Cin2 + Cin3)), nullptr, gw);
-}
-void op_gn(RunCtx* c, const half_t* x, half_t* y, size_t g, size_t b, int B, int HW, int C, float eps, int silu, float* partial, const half_t* x2, int Ca) {
-  RoleScope role(c, ROLE_GROUPNORM);
-  ProfScope ps(c, PK_GN, 8.0 * B * HW * C, 4.0 * B * HW * C);
-  if (x2) CHECK_LAUNCH(c, ia2p_launch_groupnorm(x, Ca, y, C, W_(c, g), W_(c, b), partial, B, HW, C, c->groups, eps, silu, c->stream, x2, C - Ca, Ca), "groupnorm");
-  else CHECK_LAUNCH(c, ia2p_launch_groupnorm(x, C, y, C, W_(c, g), W_(c, b), partial, B, HW, C, c->groups, eps, silu, c->stream), "groupnorm");
-}
-void op_ln(RunCtx* c, const half_t* x, half_t* y, size_t g, size_t b, int M, int C) {
-  ProfScope ps(c, PK_LN, 8.0 * M * C, 4.0 * M * C);
-  CHECK_LAUNCH(c, ia2p_launch_layernorm(x, C, y, C, W_(c, g), W_(c, b), M, C, 1e-5f, c->stream), "layernorm");
 }
 
 struct Fwd {
@@ -650,12 +324,9 @@ struct RegionScope { RunCtx* c; int prev; RegionScope(RunCtx* c_, int r) : c(c_)
 // the plan table gives the site a halo-staged tile; the statistics part: every source has its producer's column sums, at most IA2P_GN_MAX_SLOTS slots per image
 static bool gn_conv_fusable(Fwd& f, int H, int Wd, int cin, int cout, int cin2, int cin3, const GnStats& s0, const GnStats* s1, int c0) {
   if (!f.gn_on || !s0.ok() || (s1 && !s1->ok())) return false;
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1; a.Hs = a.Ho = H; a.Ws = a.Wo = Wd; a.stride = 1; a.Cin = cin; a.M = f.B * H * Wd; a.N = cout; a.K = 9 * cin + cin2 + cin3; a.lda = c0; a.ldw = a.K; a.ldc = cout;
-  a.Cin2 = cin2; a.Cin3 = cin3; a.lda2 = cin2; a.lda3 = cin3;
-  if (cin2) a.A2 = (const half_t*)16;      // (shape query: any non-null pointer)
-  if (cin3) a.A3 = (const half_t*)16;
+  const half_t* const any = (const half_t*)16;      // (shape query: any non-null pointer for the appended blocks)
+  GemmArgs a = conv3_desc(nullptr, nullptr, f.B, H, Wd, cin, nullptr, nullptr, cout, 1, 0, 1, nullptr, 0, nullptr, nullptr, cin2 ? any : nullptr, cin2, cin3 ? any : nullptr, cin3);
+  a.lda = c0;
   const GemmPlan pl = ia2p_gemm_plan(a.M, a.N, a.K, true, false);
   if (!pl.gn || !ia2p_conv_gn_fusable(a, pl.variant, pl.splitk)) return false;      // (the measured plan of the site says whether fusing pays there: tune_site)
   const int HW = H * Wd, groups = f.c->groups;
@@ -709,10 +380,7 @@ static T2 run_resnet(Fwd& f, const Resnet& r, T2 x, int H, int Wd, const T2* x2t
   T2 hh = wsalloc(c, (size_t)M * r.cout);
   const bool twin = (c->gn_dry_mode >= 0 ? c->gn_dry_mode : c->gn_fuse) == 2;      // the fused path's unfused twin: the SAME statistics, normalised by a pass of its own, then the plain convolution
   auto apply_stats = [&](const half_t* a0, int c0, const half_t* a1, const GnStats& s0, const GnStats& s1, size_t gam, size_t bet, int C, half_t* y) {
-    GemmArgs::GnIn g;
-    memset(&g, 0, sizeof g);
-    g.st0 = (const double*)s0.buf.p; g.rows0 = s0.rows; g.st1 = a1 ? (const double*)s1.buf.p : nullptr; g.rows1 = s1.rows; g.C0 = c0; g.gamma = W_(c, gam); g.beta = W_(c, bet);
-    g.groups = c->groups; g.gs = C / c->groups; g.eps = c->cfg.norm_eps; g.silu = 1;
+    const GemmArgs::GnIn g = gn_in_desc((const double*)s0.buf.p, s0.rows, a1 ? (const double*)s1.buf.p : nullptr, s1.rows, c0, C, W_(c, gam), W_(c, bet), c->groups, c->cfg.norm_eps, 1);
     RoleScope role(c, ROLE_GROUPNORM);
     ProfScope ps(c, PK_GN, 8.0 * M * C, 4.0 * M * C);
     CHECK_LAUNCH(c, ia2p_launch_gn_apply_stats(a0, c0, a1, C - c0, y, C, f.B, HW, C, g, c->stream), "groupnorm (apply from producer statistics)");
@@ -787,12 +455,8 @@ static T2 run_resnet(Fwd& f, const Resnet& r, T2 x, int H, int Wd, const T2* x2t
 // QKV projection (LayerNorm folded) + the self-attention that consumes it in ONE launch (qxattn.hip): Q, K, V never leave the CU. x: O / ldo / B / heads / Nq = 256
 // ck != nullptr: the launch also projects the layer's context K / V on the CUs its (image, head) tiles leave empty (CtxKvSlice; the caller asked ia2p_qkv_sattn_ctx_ok)
 static void op_qkv_sattn(RunCtx* c, const half_t* A, int lda, const half_t* W, const LnIn* ln, int M, int C, const AttnArgs& x, const CtxKvSlice* ck = nullptr) {
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->cs; a.ln_bias = ln->lb; a.ln_eps = ln->eps; }
-  a.A = A; a.W = W; a.zero = zero_page(); a.M = M; a.N = 3 * C; a.K = C; a.ldw = C; a.lda = lda; a.ldc = 3 * C;
-  a.rows_per_batch = 1;
+  GemmArgs a = qkv_desc(zero_page(), A, lda, W, nullptr, M, 3 * C, C);
+  ln_attach(a, ln);
   set_prefetch(c, a, W, (size_t)3 * C * C * sizeof(half_t));
   RoleScope role(c, ROLE_QKV_SATTN);
 #ifdef IA2P_CLOCK_STAMP
@@ -818,14 +482,8 @@ static void op_attn(RunCtx* c, const AttnArgs& a) {
 
 // to_q projection + the cross-attention that consumes it in ONE launch (qxattn.hip); Q never leaves the CU
 static void op_qxattn(RunCtx* c, const half_t* A, int lda, const half_t* W, const LnIn* ln, int M, int N, int K, const AttnArgs& x) {
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->cs; a.ln_bias = ln->lb; a.ln_eps = ln->eps; }
-  a.A = A; a.W = W; a.zero = zero_page(); a.M = M; a.N = N; a.K = K; a.ldw = K; a.lda = lda; a.ldc = N;
-  a.rows_per_batch = 1;
-  a.m_fastest = M <= N ? 1 : 0;
-  a.acc_scale = a.bias_scale = 1.f;
+  GemmArgs a = gemm_desc(zero_page(), A, lda, W, K, nullptr, nullptr, 0, nullptr, N, M, N, K);
+  ln_attach(a, ln);
   set_prefetch(c, a, W, (size_t)N * K * sizeof(half_t));
   double keys = 0;
   for (int s = 0; s < x.nseg; ++s) keys += x.seg[s].nkeys;
@@ -868,14 +526,10 @@ static bool sattn_fusable(Fwd& f, const Transformer& t, const TBlock& b, int HW,
   ia2p_ctx* c = f.c;
   const int C = t.c, M = f.B * HW;
   if (!(c->ln_fold && c->sattn_fuse && HW == 256 && C == t.heads * 64 && (long)f.B * t.heads >= c->xattn_min_tiles)) return false;
-  AttnArgs sa;
-  memset(&sa, 0, sizeof sa);
-  sa.O = O; sa.ldo = C; sa.B = f.B; sa.heads = t.heads; sa.Nq = HW; sa.nseg = 1;
-  GemmArgs g;
-  memset(&g, 0, sizeof g);
-  g.A = tk; g.W = W_(c, b.fqkv); g.M = M; g.N = 3 * C; g.K = C; g.lda = C; g.ldw = C; g.ldc = 3 * C;
-  g.ln_stats = st; g.ln_slots = slots; g.ln_cs = (const float*)(c->arena + b.cs1); g.ln_bias = (const float*)(c->arena + b.lb1);
-  return ia2p_qkv_sattn_ok(g, sa);
+  GemmArgs g = qkv_desc(nullptr, tk, C, W_(c, b.fqkv), nullptr, M, 3 * C, C);
+  const LnIn ln{st, slots, (const float*)(c->arena + b.cs1), (const float*)(c->arena + b.lb1), 0.f};
+  ln_attach(g, &ln);
+  return ia2p_qkv_sattn_ok(g, sattn_desc(O, C, f.B, t.heads, HW));
 #endif
 }
 // the slice of the context projection that belongs to block b (columns [kv_col, kv_col + 2C) of kv_text / kv_ip)
@@ -906,10 +560,7 @@ static std::vector<std::pair<int, int>> plan_context_kv(Fwd& f, int h, int w) {
     for (const TBlock& b : t.blocks) {
       cols.push_back({b.kv_col, 2 * t.c});
       if (!on || !sattn_fusable(f, t, b, HW, nullptr, c->dry ? nullptr : (const float*)16, 1, nullptr)) continue;
-      AttnArgs sa;
-      memset(&sa, 0, sizeof sa);
-      sa.B = f.B; sa.heads = t.heads;
-      if (ia2p_qkv_sattn_ctx_ok(sa, ctx_kv_slice(f, t, b))) f.kv_inlaunch[b.kv_col] = 1;
+      if (ia2p_qkv_sattn_ctx_ok(sattn_desc(nullptr, t.c, f.B, t.heads, HW), ctx_kv_slice(f, t, b))) f.kv_inlaunch[b.kv_col] = 1;
     }
   };
   int H = h, Wd = w;
@@ -938,7 +589,6 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
   const int ctxd = c->cfg.cross_attention_dim;
   const int Lt = c->ip_enabled ? f.L - c->ip_tokens : f.L;
   const int Li = c->ip_enabled ? c->ip_tokens : 0;
-  const float sl2e = 0.125f * 1.4426950408889634f;
   T2 n = wsalloc(c, (size_t)M * C);
   op_gn(c, x.p, n.p, t.ng, t.nb, f.B, HW, C, 1e-6f, 0, f.gn_partial);
   // The three LayerNorms of a block never run as kernels: every GEMM that writes the token stream `tk` also emits per-row
@@ -966,10 +616,7 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
     RoleScope role_sa(c, ROLE_QKV_SATTN);
     // (a site the fused tile does not take -- alignment of O / the folded constants, the 31-bit operand limit -- runs projection + attention as two launches)
     const bool fuse_sa = sattn_fusable(f, t, b, HW, tk.p, st, slots, att.p);
-    AttnArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.O = att.p; sa.ldo = C; sa.B = f.B; sa.heads = t.heads; sa.Nq = HW; sa.nseg = 1; sa.scale_log2e = sl2e;
-    sa.seg[0].nkeys = HW; sa.seg[0].weight = 1.f;
+    const AttnArgs sa = sattn_desc(att.p, C, f.B, t.heads, HW);
     // this block's context K / V: left to this launch by plan_context_kv, on the CUs the (image, head) tiles leave empty
     auto kvi = f.kv_inlaunch.find(b.kv_col);
     const bool kv_mine = kvi != f.kv_inlaunch.end() && kvi->second == 1;
@@ -988,25 +635,16 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
       op_gemm(c, lnb.p, C, W_(c, b.wqkv), nullptr, nullptr, 0, qkv.p, 3 * C, M, 3 * C, C);
     }
     if (!fuse_sa) {
-      AttnArgs a;
-      memset(&a, 0, sizeof a);
-      a.Q = qkv.p; a.ldq = 3 * C; a.O = att.p; a.ldo = C; a.B = f.B; a.heads = t.heads; a.Nq = HW; a.nseg = 1; a.scale_log2e = sl2e;
-      a.seg[0].K = c->dry ? nullptr : qkv.p + C; a.seg[0].V = c->dry ? nullptr : qkv.p + 2 * C;
-      a.seg[0].nkeys = HW; a.seg[0].ld = 3 * C; a.seg[0].rows_per_batch = HW; a.seg[0].weight = 1.f;
-      op_attn(c, a);
+      op_attn(c, attn_desc(qkv.p, 3 * C, att.p, C, f.B, t.heads, HW, 1, AttnSeg{c->dry ? nullptr : qkv.p + C, c->dry ? nullptr : qkv.p + 2 * C, HW, 3 * C, HW, 1.f}));
     }
     }
     { RoleScope role(c, ROLE_ATTN_OUT); op_gemm(c, att.p, C, W_(c, b.wo1), W_(c, b.bo1), tk.p, C, tk.p, C, M, C, C, 0, 0, 0, 0, 0, nullptr, st, &slots); }
     // cross-attention (IPAttnProcessor2_0 :310-412 when the adapter is installed, else AttnProcessor2_0)
     {
       RoleScope role(c, ROLE_Q_XATTN);
-      AttnArgs a;
-      memset(&a, 0, sizeof a);
-      a.Q = qkv.p; a.ldq = C; a.O = att.p; a.ldo = C; a.B = f.B; a.heads = t.heads; a.Nq = HW; a.nseg = Li ? 2 : 1; a.scale_log2e = sl2e;
       const half_t* kt = c->dry ? nullptr : f.kv_text.p + b.kv_col;
       const half_t* ki = (c->dry || !Li) ? nullptr : f.kv_ip.p + b.kv_col;
-      a.seg[0].K = kt; a.seg[0].V = c->dry ? nullptr : kt + C; a.seg[0].nkeys = Lt; a.seg[0].ld = ldkv; a.seg[0].rows_per_batch = Lt; a.seg[0].weight = 1.f;
-      a.seg[1].K = ki; a.seg[1].V = ki ? ki + C : nullptr; a.seg[1].nkeys = Li; a.seg[1].ld = ldkv; a.seg[1].rows_per_batch = Li; a.seg[1].weight = c->ip_scale;
+      AttnArgs a = attn_desc(qkv.p, C, att.p, C, f.B, t.heads, HW, Li ? 2 : 1, AttnSeg{kt, c->dry ? nullptr : kt + C, Lt, ldkv, Lt, 1.f}, AttnSeg{ki, ki ? ki + C : nullptr, Li, ldkv, Li, c->ip_scale});
       a.w1_b = Li ? f.ip_scales : nullptr;
       // a 128 x 64 tile of to_q is 128 queries x one head: projection and attention run as one launch when tiles do not straddle batch elements
       // (and the context fits 3 key tiles: its K / V ride in registers through the projection loop); small problems keep the finer 64 x 64 split
@@ -1209,67 +847,7 @@ static ia2p_status run_forward(ia2p_ctx* c, const half_t* sample, float timestep
 // ---------------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------------
-// ---- weight arena plumbing shared by the UNet, VAE and CLIP contexts
-ia2p_status rc_bind_arena(RunCtx* c, void* dev, size_t bytes) {
-  if (!c || !dev) return fail(c, IA2P_ERR_INVALID, "bind_arena: null argument");
-  if (bytes < c->arena_elems * sizeof(half_t)) return fail(c, IA2P_ERR_NOMEM, "arena needs %zu bytes, got %zu", c->arena_elems * sizeof(half_t), bytes);
-  if (((uintptr_t)dev) & 255) return fail(c, IA2P_ERR_INVALID, "arena must be 256-byte aligned");
-  c->arena = (half_t*)dev;
-  c->finalized = false;
-  c->wseq_key = -1;
-  return IA2P_OK;
-}
-ia2p_status rc_load_tensor(RunCtx* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
-  if (!c || !key || !src || !shape) return fail(c, IA2P_ERR_INVALID, "load_tensor: null argument");
-  if (!c->arena) return fail(c, IA2P_ERR_STATE, "load_tensor before bind_arena");
-  auto it = c->params.find(key);
-  if (it == c->params.end()) return fail(c, IA2P_ERR_KEY, "unknown parameter key '%s'", key);
-  Param& p = it->second;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  if (n != p.elems) return fail(c, IA2P_ERR_SHAPE, "parameter '%s': expected %zu elements, got %zu", key, p.elems, n);
-  hipStream_t s = (hipStream_t)stream;
-  half_t* dst = c->arena + p.off;
-  hipError_t e = hipSuccess;
-  switch (p.kind) {
-    case PK_COPY: e = hipMemcpyAsync(dst, src, n * sizeof(half_t), hipMemcpyDeviceToDevice, s); break;
-    case PK_CONV: e = ia2p_launch_pack_conv((const half_t*)src, dst, p.d0, p.d1, s); break;
-    case PK_CONV_TAP: e = ia2p_launch_pack_conv((const half_t*)src, dst, p.d0, p.d1, s); break;
-    case PK_GEGLU_W: case PK_GEGLU_B: e = ia2p_launch_pack_geglu((const half_t*)src, dst, p.d0, p.d1, s); break;
-    case PK_PAD_CONV_IN: e = ia2p_launch_pack_conv_in((const half_t*)src, dst, p.d0, p.d1, s); break;
-  }
-  if (e != hipSuccess) return fail_hip(c, e, (std::string("load '") + key + "'").c_str());
-  p.loaded = true;
-  c->fold_dirty = true;     // data derived from the parameters at finalize (LayerNorm folds) is stale until the owner re-derives it
-  return IA2P_OK;
-}
-ia2p_status rc_finalize(RunCtx* c, const char* what) {
-  if (!c) return IA2P_ERR_INVALID;
-  if (!c->arena) return fail(c, IA2P_ERR_STATE, "finalize before bind_arena");
-  int missing = 0;
-  std::string first;
-  for (auto& kv : c->params)
-    if (!kv.second.loaded && !kv.second.optional) { if (!missing) first = kv.first; ++missing; }
-  if (missing) return fail(c, IA2P_ERR_KEY, "%d %s parameters not loaded (e.g. '%s')", missing, what, first.c_str());
-  c->finalized = true;
-  return IA2P_OK;
-}
-ia2p_status rc_adopt(RunCtx* c, bool with_optional) {
-  if (!c || !c->arena) return fail(c, IA2P_ERR_STATE, "adopt_arena before bind_arena");
-  for (auto& kv : c->params)
-    if (with_optional || !kv.second.optional) kv.second.loaded = true;
-  c->finalized = true;
-  return IA2P_OK;
-}
-
 extern "C" {
-
-int ia2p_device_is_gfx950(void) {
-  int dev = 0;
-  hipDeviceProp_t p;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-  return strncmp(p.gcnArchName, "gfx950", 6) == 0;
-}
 
 ia2p_status ia2p_create(const ia2p_unet_config* cfg, ia2p_ctx** out) {
   if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_create: null argument");
@@ -1528,22 +1106,6 @@ ia2p_status ia2p_unet_forward_kv(ia2p_ctx* c, void* stream, const void* sample, 
 // Measure-and-pick pass: one forward in which every GEMM / conv site whose shape has no measured plan yet times its
 // candidate tile / K-split plans in place (tune_site) and records the fastest in the process-wide plan table.
 // Re-query ia2p_workspace_bytes afterwards: K-split choices change the slab sizes.
-static ia2p_status tune_begin(RunCtx* c, int reps) {
-  c->tune_slab_bytes = (size_t)256 << 20; c->tune_flush_bytes = (size_t)48 << 20;
-  if (hipMalloc((void**)&c->tune_scratch, c->tune_slab_bytes + c->tune_flush_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    c->tune_scratch = nullptr;
-    return fail(c, IA2P_ERR_NOMEM, "autotune: cannot allocate %zu MiB of scratch", (c->tune_slab_bytes + c->tune_flush_bytes) >> 20);
-  }
-  c->tuning = true; c->tune_reps = reps < 1 ? 5 : reps; c->tune_sites = 0;
-  return IA2P_OK;
-}
-static void tune_end(RunCtx* c, hipStream_t s) {
-  c->tuning = false;
-  (void)hipStreamSynchronize(s);
-  (void)hipFree(c->tune_scratch);
-  c->tune_scratch = nullptr;
-}
 ia2p_status ia2p_autotune(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, int L, const void* text_embeds,
                           const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes, int reps, int* sites) {
   if (!c) return fail(c, IA2P_ERR_INVALID, "autotune: null context");
@@ -1558,49 +1120,6 @@ ia2p_status ia2p_autotune(ia2p_ctx* c, void* stream, const void* sample, float t
   return st;
 }
 
-ia2p_status ia2p_ddim_step(void* stream, const void* x, const void* eu, const void* ec, float g, float c_x, float c_e, void* out, void* out2, int64_t n) {
-  if (!x || !eu || !out || n < 0) return fail(nullptr, IA2P_ERR_INVALID, "ddim_step: null argument");
-  hipError_t e = ia2p_launch_ddim_step((const half_t*)x, (const half_t*)eu, (const half_t*)ec, g, c_x, c_e, (half_t*)out, (half_t*)out2, (long)n, (hipStream_t)stream);
-  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "ddim_step");
-}
-
-// The same update with per-request coefficients: coef (device, float [B][3]) = {guidance g, c_x, c_e} of batch element b, `per` elements each --
-// requests with their own guidance scale (reference pipeline.py:303 `cfg`) at their own step of their own schedule share one launch.
-ia2p_status ia2p_ddim_step_v(void* stream, const void* x, const void* eu, const void* ec, const float* coef, void* out, void* out2, int B, int64_t per) {
-  if (!x || !eu || !out || !coef || B < 0 || per < 1) return fail(nullptr, IA2P_ERR_INVALID, "ddim_step_v: bad argument");
-  hipError_t e = ia2p_launch_ddim_step((const half_t*)x, (const half_t*)eu, (const half_t*)ec, 0.f, 0.f, 0.f, (half_t*)out, (half_t*)out2, (long)B * per, (hipStream_t)stream, coef, (long)per);
-  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "ddim_step_v");
-}
-
-ia2p_status ia2p_mask_blend(void* stream, const void* x, const void* init, const void* noise, const void* mask, float c0, float c1,
-                            void* out, void* out2, int B, int C, int64_t HW) {
-  if (!x || !init || !noise || !mask || !out || B < 0 || C < 1 || HW < 1) return fail(nullptr, IA2P_ERR_INVALID, "mask_blend: bad argument");
-  hipError_t e = ia2p_launch_mask_blend((const half_t*)x, (const half_t*)init, (const half_t*)noise, (const half_t*)mask, c0, c1, (half_t*)out, (half_t*)out2,
-                                        B, C, (long)HW, (hipStream_t)stream);
-  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "mask_blend");
-}
-
-ia2p_status ia2p_prior_step(void* stream, const float* sample, const void* out_cond, const void* out_uncond, const float* noise, float g, float sqrt_a,
-                            float sqrt_b, float k0, float k1, float sigma, float* out, int64_t n) {
-  if (!sample || !out_uncond || !out || n < 0 || !(sqrt_a > 0.f) || !(sqrt_b > 0.f)) return fail(nullptr, IA2P_ERR_INVALID, "prior_step: bad argument");
-  hipError_t e = ia2p_launch_prior_step(sample, (const half_t*)out_cond, (const half_t*)out_uncond, noise, g, sqrt_a, sqrt_b, k0, k1, sigma, out, (long)n, (hipStream_t)stream);
-  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "prior_step");
-}
-
-// ---- per-operator entry points ---------------------------------------------------------------------------------------
-
-ia2p_status ia2p_groupnorm_silu(void* stream, const void* x, void* y, const void* gamma, const void* beta, int B, int HW, int C, int groups, float eps, int silu, float* partial) {
-  if (!x || !y || !gamma || !beta || !partial) return fail(nullptr, IA2P_ERR_INVALID, "groupnorm: null argument");
-  if (C % 8 || C % groups || groups > 256) return fail(nullptr, IA2P_ERR_SHAPE, "groupnorm: C=%d groups=%d", C, groups);
-  hipError_t e = ia2p_launch_groupnorm((const half_t*)x, C, (half_t*)y, C, (const half_t*)gamma, (const half_t*)beta, partial, B, HW, C, groups, eps, silu, (hipStream_t)stream);
-  RET_HIP(e, "groupnorm");
-}
-ia2p_status ia2p_layernorm(void* stream, const void* x, void* y, const void* gamma, const void* beta, int M, int C, float eps) {
-  if (!x || !y || !gamma || !beta) return fail(nullptr, IA2P_ERR_INVALID, "layernorm: null argument");
-  if (C % 8 || C > 2048) return fail(nullptr, IA2P_ERR_SHAPE, "layernorm: C=%d must be a multiple of 8 and <= 2048", C);
-  hipError_t e = ia2p_launch_layernorm((const half_t*)x, C, (half_t*)y, C, (const half_t*)gamma, (const half_t*)beta, M, C, eps, (hipStream_t)stream);
-  RET_HIP(e, "layernorm");
-}
 #ifdef IA2P_CLOCK_STAMP
 // Diagnostic builds only (IA2P_EXTRA_FLAGS=-DIA2P_CLOCK_STAMP; not declared in the headers, not part of the product library): in-kernel s_memrealtime stamps of the
 // launches of one layer role INSIDE a step. buf: device memory, `launch_slots` x STAMP_WG x 8 u64, zeroed by the caller; role: ROLE_* index (ia2p_profile_read_role).
@@ -1619,352 +1138,6 @@ int ia2p_debug_stamp_read(ia2p_ctx* c, int* meta, int max_launches) {
   return (int)c->stamp_meta.size();
 }
 #endif
-ia2p_status ia2p_gemm(void* stream, const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K, int geglu) {
-  if (!A || !W || !C) return fail(nullptr, IA2P_ERR_INVALID, "gemm: null argument");
-  if (K % 64 || N % 4 || (geglu && (N % 32 || !bias))) return fail(nullptr, IA2P_ERR_SHAPE, "gemm: K=%d must be a multiple of 64, N=%d of 4 (GEGLU: 32, with bias)", K, N);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  const int No = geglu ? N / 2 : N;
-  a.A = (const half_t*)A; a.W = (const half_t*)W; a.C = (half_t*)C; a.zero = zero_page(); a.M = M; a.N = N; a.K = K; a.ldw = a.K; a.lda = K; a.ldc = No;
-  a.bias = (const half_t*)bias; a.residual = (const half_t*)residual; a.ldr = No; a.geglu = geglu; a.rows_per_batch = 1;
-  a.m_fastest = M <= N;
-  hipError_t e = ia2p_launch_gemm(a, false, (hipStream_t)stream, nullptr);
-  RET_HIP(e, "gemm");
-}
-// GEGLU feed-forward of a BasicTransformerBlock as an operator: H = geglu(X . W1p^T + b1p) [M, 4 C] (packed weights: ia2p_pack_geglu), out = H . W2^T + b2 + R,
-// as the executor runs it (two launches, the library's plans). splitk / partial: K split of the second GEMM (partial: splitk * M * C floats) or 0.
-ia2p_status ia2p_ffn(void* stream, const void* X, const void* W1p, const void* b1p, const void* W2, const void* b2, const void* R, void* H, void* out,
-                     int M, int C, int splitk, float* partial) {
-  if (!X || !W1p || !b1p || !W2 || !H || !out) return fail(nullptr, IA2P_ERR_INVALID, "ffn: null argument");
-  if (C % 64 || (splitk > 1 && (!partial || splitk > 4 * C / 64 || splitk > 255))) return fail(nullptr, IA2P_ERR_SHAPE, "ffn: C=%d must be a multiple of 64, splitk=%d needs slabs", C, splitk);
-  RunCtx rc;
-  GemmArgs a = gemm_args(&rc, (const half_t*)X, C, (const half_t*)W1p, (const half_t*)b1p, nullptr, 0, (half_t*)H, 4 * C, M, 8 * C, C, 1, 0, 0, 0, 0, nullptr, nullptr, 0);
-  GemmArgs b = gemm_args(&rc, (const half_t*)H, 4 * C, (const half_t*)W2, (const half_t*)b2, (const half_t*)R, C, (half_t*)out, C, M, C, 4 * C, 0, 0, 0, 0, 0, nullptr, nullptr, 0);
-  a.m_fastest = a.M <= a.N; b.m_fastest = b.M <= b.N;
-  if (splitk > 1) { b.splitk = splitk; b.partial = partial; }
-  const GemmPlan pa = ia2p_gemm_plan(a.M, a.N, a.K, false, true), pb = ia2p_gemm_plan(b.M, b.N, b.K, false, false);
-  hipError_t e = ia2p_launch_gemm_variant(a, false, pa.variant, (hipStream_t)stream);
-  if (e == hipSuccess) e = ia2p_launch_gemm_variant(b, false, pb.variant, (hipStream_t)stream);
-  RET_HIP(e, "ffn");
-}
-ia2p_status ia2p_fold_layernorm(void* stream, const void* W, const void* gamma, const void* beta, const void* bias, void* Wf, float* colsum,
-                                float* fbias, int N, int K) {
-  if (!W || !gamma || !beta || !Wf || !colsum || !fbias || N < 1 || K < 1) return fail(nullptr, IA2P_ERR_INVALID, "fold_layernorm: bad argument");
-  hipError_t e = ia2p_launch_fold_ln((const half_t*)W, (const half_t*)gamma, (const half_t*)beta, (const half_t*)bias, (half_t*)Wf, colsum, fbias, N, K, (hipStream_t)stream);
-  RET_HIP(e, "fold_layernorm");
-}
-ia2p_status ia2p_gemm_ex(void* stream, const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K, int geglu,
-                         const ia2p_ln_fold* ln, float* stats_out, int* stats_slots, int splitk, float* partial) {
-  if (!A || !W || !C) return fail(nullptr, IA2P_ERR_INVALID, "gemm_ex: null argument");
-  if (K % 64 || N % 4 || (geglu && (N % 32 || (!bias && !ln)))) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_ex: K=%d must be a multiple of 64, N=%d of 4 (GEGLU: 32, with bias)", K, N);
-  if (splitk > 1 && (!partial || geglu || splitk > K / 64 || splitk > 255)) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_ex: splitk=%d needs a slab, no GEGLU, and <= min(K/64, 255)", splitk);
-  if (ln && (!ln->stats || !ln->colsum || !ln->fbias || ln->slots < 1)) return fail(nullptr, IA2P_ERR_INVALID, "gemm_ex: incomplete ia2p_ln_fold");
-  if (stats_out && geglu) return fail(nullptr, IA2P_ERR_INVALID, "gemm_ex: row statistics of a GEGLU output are not provided");
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  const int No = geglu ? N / 2 : N;
-  a.A = (const half_t*)A; a.W = (const half_t*)W; a.C = (half_t*)C; a.zero = zero_page(); a.M = M; a.N = N; a.K = K; a.ldw = a.K; a.lda = K; a.ldc = No;
-  a.bias = (const half_t*)bias; a.residual = (const half_t*)residual; a.ldr = No; a.geglu = geglu; a.rows_per_batch = 1;
-  a.m_fastest = M <= N;
-  if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->colsum; a.ln_bias = ln->fbias; a.ln_eps = ln->eps; }
-  a.stats_out = stats_out;
-  if (splitk > 1) { a.splitk = splitk; a.partial = partial; }
-#ifdef IA2P_CLOCK_STAMP
-  else if (partial) a.partial = partial;      // (diagnostic builds: the in-kernel stamps of an unsplit launch go to the caller's buffer, tools/insitu_stamps.py)
-#endif
-  int pick = 0, combined = 0;
-  hipError_t e = ia2p_launch_gemm(a, false, (hipStream_t)stream, &pick, &combined);
-  if (stats_slots && pick >= 0 && pick < IA2P_GEMM_NVARIANT) *stats_slots = (splitk > 1 && !combined) ? 1 : (N + IA2P_GEMM_TILES[pick].bn - 1) / IA2P_GEMM_TILES[pick].bn;
-  RET_HIP(e, "gemm_ex");
-}
-ia2p_status ia2p_gemm_splitk(void* stream, const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K,
-                             int splitk, float* partial) {
-  if (!A || !W || !C || !partial) return fail(nullptr, IA2P_ERR_INVALID, "gemm_splitk: null argument");
-  if (K % 64 || N % 4 || splitk < 1 || splitk > K / 64 || splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_splitk: K=%d N=%d splitk=%d (1 .. min(K / 64, 255))", K, N, splitk);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  a.A = (const half_t*)A; a.W = (const half_t*)W; a.C = (half_t*)C; a.zero = zero_page(); a.M = M; a.N = N; a.K = K; a.ldw = a.K; a.lda = K; a.ldc = N;
-  a.bias = (const half_t*)bias; a.residual = (const half_t*)residual; a.ldr = N; a.rows_per_batch = 1; a.m_fastest = M <= N;
-  a.splitk = splitk; a.partial = partial;
-  hipError_t e = ia2p_launch_gemm(a, false, (hipStream_t)stream, nullptr);
-  RET_HIP(e, "gemm_splitk");
-}
-ia2p_status ia2p_conv3x3(void* stream, const void* x, const void* Wp, const void* bias, const void* rowvec, const void* residual, void* y,
-                         int B, int Hs, int Ws, int Cin, int Co, int stride, int up) {
-  if (!x || !Wp || !y) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3: null argument");
-  if (Cin % 64 || Co % 4 || (stride != 1 && stride != 2) || (up != 0 && up != 1)) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3: Cin=%d (mult of 64) Co=%d (mult of 4) stride=%d up=%d", Cin, Co, stride, up);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  const int Hv = Hs << up, Wv = Ws << up;
-  a.Ho = (Hv - 1) / stride + 1; a.Wo = (Wv - 1) / stride + 1;
-  a.A = (const half_t*)x; a.W = (const half_t*)Wp; a.C = (half_t*)y; a.zero = zero_page(); a.M = B * a.Ho * a.Wo; a.N = Co; a.K = 9 * Cin; a.ldw = a.K; a.lda = Cin; a.ldc = Co;
-  a.Hs = Hs; a.Ws = Ws; a.stride = stride; a.up = up; a.Cin = Cin; a.bias = (const half_t*)bias;
-  a.rowvec = (const half_t*)rowvec; a.rowvec_ld = Co; a.rows_per_batch = a.Ho * a.Wo; a.residual = (const half_t*)residual; a.ldr = Co;
-  hipError_t e = ia2p_launch_gemm(a, true, (hipStream_t)stream, nullptr);
-  RET_HIP(e, "conv3x3");
-}
-// the stride-1 form with K split over `splitk` workgroups per tile (what the executor launches for the 16 x 16 feature maps); partial: splitk * B*Hs*Ws * Co floats
-ia2p_status ia2p_conv3x3_splitk(void* stream, const void* x, const void* Wp, const void* bias, const void* rowvec, const void* residual, void* y,
-                                int B, int Hs, int Ws, int Cin, int Co, int splitk, float* partial) {
-  if (!x || !Wp || !y || (splitk > 1 && !partial)) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_splitk: null argument (partial is needed for splitk > 1 only)");
-  if (Cin % 64 || Co % 4 || splitk < 1 || splitk > 9 * Cin / 64 || splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_splitk: Cin=%d (mult of 64) Co=%d (mult of 4) splitk=%d (1 .. 9 Cin / 64)", Cin, Co, splitk);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  a.Ho = Hs; a.Wo = Ws;
-  a.A = (const half_t*)x; a.W = (const half_t*)Wp; a.C = (half_t*)y; a.zero = zero_page(); a.M = B * Hs * Ws; a.N = Co; a.K = 9 * Cin; a.ldw = a.K; a.lda = Cin; a.ldc = Co;
-  a.Hs = Hs; a.Ws = Ws; a.stride = 1; a.up = 0; a.Cin = Cin; a.bias = (const half_t*)bias;
-  a.rowvec = (const half_t*)rowvec; a.rowvec_ld = Co; a.rows_per_batch = Hs * Ws; a.residual = (const half_t*)residual; a.ldr = Co;
-  if (splitk > 1) { a.splitk = splitk; a.partial = partial; }
-  hipError_t e = ia2p_launch_gemm(a, true, (hipStream_t)stream, nullptr);
-  RET_HIP(e, "conv3x3_splitk");
-}
-// ---- GroupNorm from producer-side column sums (round 5; csrc/gn_fold.h): the operators of the fused path, one by one -----------------------------------------------
-// canonical statistics of a tensor x [M, C]: out[(slot * C + c) * 2 + {0, 1}] = {sum, sum of squares} (fp64) over the `rows` rows of slot `slot` (what a GEMM / conv epilogue
-// leaves for its own output when asked: ia2p_gemm_gnstats, ia2p_conv3x3_gn)
-ia2p_status ia2p_gn_colstats(void* stream, const void* x, int M, int C, int rows, double* out) {
-  if (!x || !out) return fail(nullptr, IA2P_ERR_INVALID, "gn_colstats: null argument");
-  if (C < 8 || C % 8 || rows < 16 || rows % 16 || M < 1 || M % rows) return fail(nullptr, IA2P_ERR_SHAPE, "gn_colstats: C=%d (multiple of 8), rows=%d (multiple of 16 dividing M=%d)", C, rows, M);
-  hipError_t e = ia2p_launch_gn_colstats((const half_t*)x, C, M, C, rows, out, (hipStream_t)stream);
-  RET_HIP(e, "gn_colstats");
-}
-static ia2p_status gn_in_from_abi(const char* what, GemmArgs::GnIn* g, int C0, const double* st0, int rows0, int C1, const double* st1, int rows1, const void* gamma, const void* beta, int groups, float eps, int silu, int HW) {
-  const int C = C0 + C1;
-  if (!st0 || !gamma || !beta || (C1 > 0 && !st1)) return fail(nullptr, IA2P_ERR_INVALID, "%s: null argument", what);
-  if (groups < 1 || groups > 64 || C % groups || C0 < 8 || C0 % 8 || C1 < 0 || C1 % 8 || rows0 < 1 || HW % rows0 || (C1 > 0 && (rows1 < 1 || HW % rows1)))
-    return fail(nullptr, IA2P_ERR_SHAPE, "%s: C0=%d C1=%d groups=%d rows0=%d rows1=%d HW=%d", what, C0, C1, groups, rows0, rows1, HW);
-  memset(g, 0, sizeof *g);
-  g->st0 = st0; g->rows0 = rows0; g->st1 = C1 > 0 ? st1 : nullptr; g->rows1 = rows1; g->C0 = C0; g->gamma = (const half_t*)gamma; g->beta = (const half_t*)beta;
-  g->groups = groups; g->gs = C / groups; g->eps = eps; g->silu = silu;
-  return IA2P_OK;
-}
-// y = [silu](GroupNorm(groups)([x0 | x1])) with the statistics folded from the column sums of the sources' producers: the stand-alone twin of what ia2p_conv3x3_gn
-// does to its operand inside the convolution (same fold, same scale / shift, same element formula: the two agree to the bit)
-ia2p_status ia2p_gn_apply_stats(void* stream, const void* x0, int C0, const double* st0, int rows0, const void* x1, int C1, const double* st1, int rows1,
-                                const void* gamma, const void* beta, void* y, int B, int HW, int groups, float eps, int silu) {
-  if (!x0 || !y || (C1 > 0 && !x1)) return fail(nullptr, IA2P_ERR_INVALID, "gn_apply_stats: null argument");
-  GemmArgs::GnIn g;
-  const ia2p_status st = gn_in_from_abi("gn_apply_stats", &g, C0, st0, rows0, C1, st1, rows1, gamma, beta, groups, eps, silu, HW);
-  if (st != IA2P_OK) return st;
-  hipError_t e = ia2p_launch_gn_apply_stats((const half_t*)x0, C0, C1 > 0 ? (const half_t*)x1 : nullptr, C1, (half_t*)y, C0 + C1, B, HW, C0 + C1, g, (hipStream_t)stream);
-  RET_HIP(e, "gn_apply_stats");
-}
-// 3x3 convolution (stride 1) of silu(GroupNorm([x0 | x1])) with the norm applied INSIDE the convolution (d->st0 != NULL; conv_halo_kernel.h GN = 1), or of x0 itself
-// (d->st0 == NULL), + optional appended 1x1 block, time-embedding row, residual, K split; d->gn_out != NULL: also the column sums of y (*gn_out_rows: rows per slot,
-// 0 when this launch could not take them). Fused form: the site must have a halo-staged plan (IA2P_ERR_SHAPE otherwise; tests force one with ia2p_debug_set_gemm_tile).
-ia2p_status ia2p_conv3x3_gn(void* stream, const ia2p_conv_gn* d, int* gn_out_rows) {
-  if (gn_out_rows) *gn_out_rows = 0;
-  if (!d || !d->x0 || !d->Wp || !d->y || (d->splitk > 1 && !d->partial) || (d->Ca > 0 && !d->xa)) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_gn: null argument");
-  const int Cin = d->C0 + (d->st0 ? d->C1 : 0), HW = d->H * d->W;
-  if (Cin % 64 || d->C0 % 64 || d->Co % 8 || d->Ca % 64 || d->B < 1 || HW < 1 || d->splitk < 0 || d->splitk > (9 * Cin + d->Ca) / 64 || d->splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_gn: C0=%d C1=%d Co=%d Ca=%d splitk=%d", d->C0, d->C1, d->Co, d->Ca, d->splitk);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1; a.Ho = a.Hs = d->H; a.Wo = a.Ws = d->W; a.stride = 1;
-  a.A = (const half_t*)d->x0; a.W = (const half_t*)d->Wp; a.C = (half_t*)d->y; a.zero = zero_page(); a.M = d->B * HW; a.N = d->Co; a.K = 9 * Cin + d->Ca; a.ldw = a.K; a.lda = d->C0; a.ldc = d->Co;
-  a.Cin = Cin; a.bias = (const half_t*)d->bias; a.rowvec = (const half_t*)d->rowvec; a.rowvec_ld = d->Co; a.rows_per_batch = HW; a.residual = (const half_t*)d->residual; a.ldr = d->Co;
-  if (d->Ca > 0) { a.A2 = (const half_t*)d->xa; a.lda2 = d->Ca; a.Cin2 = d->Ca; }
-  if (d->splitk > 1) { a.splitk = d->splitk; a.partial = d->partial; }
-  const GemmPlan pl = ia2p_gemm_plan(a.M, a.N, a.K, true, false);
-  if (d->st0) {
-    const ia2p_status st = gn_in_from_abi("conv3x3_gn", &a.gn, d->C0, d->st0, d->rows0, d->C1, d->st1, d->rows1, d->gamma, d->beta, d->groups, d->eps, 1, HW);
-    if (st != IA2P_OK) return st;
-    a.A1b = d->C1 > 0 ? (const half_t*)d->x1 : nullptr; a.lda1b = d->C1;
-    if (d->C1 > 0 && !d->x1) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_gn: null second source");
-    if (!ia2p_conv_gn_fusable(a, pl.variant, a.splitk) || !ia2p_conv_gn_ok(a)) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_gn: this site has no halo-staged plan (variant %d) or its statistics do not fit the fused kernel", pl.variant);
-  }
-  const bool combined = a.splitk > 1 && ia2p_splitk_inkernel(a.M, a.N, a.splitk);
-  int rows = 0;
-  if (d->gn_out) { rows = gn_epilogue_rows(a, true, pl.variant, a.splitk, combined, HW); if (rows) a.gn_out = d->gn_out; }
-  int comb = 0;
-  hipError_t e = ia2p_launch_gemm_variant(a, true, pl.variant, (hipStream_t)stream, true, &comb);
-  if (e == hipSuccess && gn_out_rows) *gn_out_rows = (rows && (a.splitk <= 1 || comb)) ? rows : 0;
-  RET_HIP(e, "conv3x3_gn");
-}
-// C = A . W^T + bias + residual as ia2p_gemm_splitk (splitk <= 1: no split), also leaving the GroupNorm column sums of C for images of HW rows (a Transformer2DModel's
-// proj_out in front of the next ResnetBlock2D); *rows: rows per slot, 0 when the tile the plan picked cannot take them (the caller runs ia2p_gn_colstats)
-ia2p_status ia2p_gemm_gnstats(void* stream, const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K, int splitk, float* partial,
-                              int HW, double* gn_out, int* rows) {
-  if (rows) *rows = 0;
-  if (!A || !W || !C || !gn_out || !rows || (splitk > 1 && !partial)) return fail(nullptr, IA2P_ERR_INVALID, "gemm_gnstats: null argument");
-  if (K % 64 || N % 8 || HW < 16 || M % HW || splitk < 0 || splitk > K / 64 || splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_gnstats: K=%d N=%d HW=%d splitk=%d", K, N, HW, splitk);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  a.A = (const half_t*)A; a.W = (const half_t*)W; a.C = (half_t*)C; a.zero = zero_page(); a.M = M; a.N = N; a.K = K; a.ldw = a.K; a.lda = K; a.ldc = N;
-  a.bias = (const half_t*)bias; a.residual = (const half_t*)residual; a.ldr = N; a.rows_per_batch = 1; a.m_fastest = M <= N;
-  if (splitk > 1) { a.splitk = splitk; a.partial = partial; }
-  const GemmPlan pl = ia2p_gemm_plan(M, N, K, false, false);
-  const bool combined = splitk > 1 && ia2p_splitk_inkernel(M, N, splitk);
-  const int r = gn_epilogue_rows(a, false, pl.variant, a.splitk, combined, HW);
-  if (r) a.gn_out = gn_out;
-  int comb = 0;
-  hipError_t e = ia2p_launch_gemm_variant(a, false, pl.variant, (hipStream_t)stream, true, &comb);
-  if (e == hipSuccess) *rows = (r && (a.splitk <= 1 || comb)) ? r : 0;
-  RET_HIP(e, "gemm_gnstats");
-}
-// ResnetBlock2D tail as one implicit GEMM: y = conv3x3(x, W2) + conv1x1(x2, Wsc) + bias (+ rowvec), K = 9 Cin + Cin2; Wcat rows = [packed W2 row | Wsc row]
-ia2p_status ia2p_conv3x3_cat(void* stream, const void* x, const void* x2, const void* Wcat, const void* bias, void* y, int B, int Hs, int Ws, int Cin, int Cin2, int Co) {
-  if (!x || !x2 || !Wcat || !y) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_cat: null argument");
-  if (Cin % 64 || Cin2 % 64 || Cin2 < 64 || Co % 4) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_cat: Cin=%d, Cin2=%d (multiples of 64) Co=%d (mult of 4)", Cin, Cin2, Co);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  a.Ho = Hs; a.Wo = Ws;
-  a.A = (const half_t*)x; a.W = (const half_t*)Wcat; a.C = (half_t*)y; a.zero = zero_page(); a.M = B * Hs * Ws; a.N = Co; a.K = 9 * Cin + Cin2; a.ldw = a.K; a.lda = Cin; a.ldc = Co;
-  a.Hs = Hs; a.Ws = Ws; a.stride = 1; a.up = 0; a.Cin = Cin; a.bias = (const half_t*)bias; a.rows_per_batch = Hs * Ws;
-  a.A2 = (const half_t*)x2; a.lda2 = Cin2; a.Cin2 = Cin2;
-  hipError_t e = ia2p_launch_gemm(a, true, (hipStream_t)stream, nullptr);
-  RET_HIP(e, "conv3x3_cat");
-}
-ia2p_status ia2p_pack_conv3x3(void* stream, const void* src, void* dst, int Co, int Cin) {
-  if (!src || !dst) return fail(nullptr, IA2P_ERR_INVALID, "pack_conv3x3: null argument");
-  if (Cin % 64) return fail(nullptr, IA2P_ERR_SHAPE, "pack_conv3x3: Cin=%d must be a multiple of 64 (the layout of ia2p_conv3x3; ia2p_pack_conv_out packs for ia2p_conv_out)", Cin);
-  hipError_t e = ia2p_launch_pack_conv((const half_t*)src, (half_t*)dst, Co, Cin, (hipStream_t)stream);
-  RET_HIP(e, "pack_conv3x3");
-}
-ia2p_status ia2p_pack_conv_out(void* stream, const void* src, void* dst, int Co, int C) {
-  if (!src || !dst) return fail(nullptr, IA2P_ERR_INVALID, "pack_conv_out: null argument");
-  hipError_t e = ia2p_launch_pack_conv((const half_t*)src, (half_t*)dst, Co, C, (hipStream_t)stream);
-  RET_HIP(e, "pack_conv_out");
-}
-// latent-boundary convolutions as operators (the executors call the launchers directly): conv_in reads NCHW and writes channels-last,
-// conv_out reads channels-last and writes NCHW; reference call sites: the diffusers UNet's conv_in / conv_out behind pnp_pipeline.py:253-260
-ia2p_status ia2p_conv_in(void* stream, const void* x_nchw, const void* w_oihw, const void* bias, void* y_nhwc, void* w_scratch, int B, int Cin, int H, int W, int Co) {
-  if (!x_nchw || !w_oihw || !bias || !y_nhwc || !w_scratch) return fail(nullptr, IA2P_ERR_INVALID, "conv_in: null argument");
-  if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cin * 9 > 64 || Co < 8 || Co % 8) return fail(nullptr, IA2P_ERR_SHAPE, "conv_in: Cin*9=%d must be <= 64, Co=%d a multiple of 8", Cin * 9, Co);
-  hipError_t e = ia2p_launch_pack_conv_in((const half_t*)w_oihw, (half_t*)w_scratch, Co, Cin * 9, (hipStream_t)stream);
-  if (e == hipSuccess) e = ia2p_launch_conv_in((const half_t*)x_nchw, (const half_t*)w_scratch, (const half_t*)bias, (half_t*)y_nhwc, B, Cin, H, W, Co, (hipStream_t)stream);
-  RET_HIP(e, "conv_in");
-}
-ia2p_status ia2p_conv_out(void* stream, const void* x_nhwc, const void* w_packed, const void* bias, void* y_nchw, int B, int C, int H, int W, int Co) {
-  if (!x_nhwc || !w_packed || !bias || !y_nchw) return fail(nullptr, IA2P_ERR_INVALID, "conv_out: null argument");
-  if (B < 1 || H < 1 || W < 1 || C < 32 || C % 32 || Co < 1 || Co > 8) return fail(nullptr, IA2P_ERR_SHAPE, "conv_out: C=%d must be a multiple of 32, Co=%d <= 8", C, Co);
-  hipError_t e = ia2p_launch_conv_out((const half_t*)x_nhwc, C, (const half_t*)w_packed, (const half_t*)bias, (half_t*)y_nchw, B, C, H, W, Co, (hipStream_t)stream);
-  RET_HIP(e, "conv_out");
-}
-ia2p_status ia2p_pack_geglu(void* stream, const void* src, void* dst, int rows, int rowlen) {
-  if (!src || !dst || rows % 32) return fail(nullptr, IA2P_ERR_SHAPE, "pack_geglu: rows must be a multiple of 32");
-  hipError_t e = ia2p_launch_pack_geglu((const half_t*)src, (half_t*)dst, rows, rowlen, (hipStream_t)stream);
-  RET_HIP(e, "pack_geglu");
-}
-ia2p_status ia2p_attention(void* stream, const void* Q, int ldq, void* O, int ldo, int B, int heads, int Nq, int nseg,
-                           const void* K0, const void* V0, int ld0, int nkeys0, float w0, const void* K1, const void* V1, int ld1, int nkeys1, float w1) {
-  if (!Q || !O || !K0 || !V0 || nseg < 1 || nseg > 2 || (nseg == 2 && (!K1 || !V1))) return fail(nullptr, IA2P_ERR_INVALID, "attention: bad argument");
-  if (nkeys0 < 1 || (nseg == 2 && nkeys1 < 1) || ldq % 8 || ldo % 8 || (((uintptr_t)O) & 15) || ld0 % 8 || (nseg == 2 && ld1 % 8)) return fail(nullptr, IA2P_ERR_SHAPE, "attention: key counts must be >= 1, strides multiples of 8, O 16-byte aligned");
-  AttnArgs a;
-  memset(&a, 0, sizeof a);
-  a.Q = (const half_t*)Q; a.ldq = ldq; a.O = (half_t*)O; a.ldo = ldo; a.B = B; a.heads = heads; a.Nq = Nq; a.nseg = nseg;
-  a.scale_log2e = 0.125f * 1.4426950408889634f;
-  a.seg[0] = AttnSeg{(const half_t*)K0, (const half_t*)V0, nkeys0, ld0, nkeys0, w0};
-  a.seg[1] = AttnSeg{(const half_t*)K1, (const half_t*)V1, nkeys1, ld1, nkeys1, w1};
-  hipError_t e = ia2p_launch_attention(a, (hipStream_t)stream);
-  RET_HIP(e, "attention");
-}
-ia2p_status ia2p_qproj_attention(void* stream, const void* X, const void* Wq, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo, int B, int heads,
-                                 int Nq, int K, int nseg, const void* K0, const void* V0, int ld0, int nkeys0, float w0,
-                                 const void* K1, const void* V1, int ld1, int nkeys1, float w1) {
-  if (!X || !Wq || !O || !K0 || !V0 || nseg < 1 || nseg > 2 || (nseg == 2 && (!K1 || !V1))) return fail(nullptr, IA2P_ERR_INVALID, "qproj_attention: bad argument");
-  if (ln && (!ln->stats || !ln->colsum || !ln->fbias || ln->slots < 1)) return fail(nullptr, IA2P_ERR_INVALID, "qproj_attention: incomplete ia2p_ln_fold");
-  if (B < 1 || heads < 1 || Nq < 128 || Nq % 128 || K < 64 || K % 64 || nkeys0 < 1 || (nseg == 2 && nkeys1 < 1) || ldo % 8 || (((uintptr_t)O) & 15) || ld0 % 8 || (nseg == 2 && ld1 % 8))
-    return fail(nullptr, IA2P_ERR_SHAPE, "qproj_attention: Nq=%d must be a multiple of 128, K=%d of 64, key counts >= 1, strides multiples of 8, O 16-byte aligned", Nq, K);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  a.A = (const half_t*)X; a.W = (const half_t*)Wq; a.zero = zero_page(); a.M = B * Nq; a.N = heads * 64; a.K = K; a.ldw = K; a.lda = K; a.ldc = a.N;
-  a.bias = (const half_t*)bias; a.rows_per_batch = 1; a.m_fastest = a.M <= a.N;
-  if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->colsum; a.ln_bias = ln->fbias; a.ln_eps = ln->eps; }
-  AttnArgs x;
-  memset(&x, 0, sizeof x);
-  x.O = (half_t*)O; x.ldo = ldo; x.B = B; x.heads = heads; x.Nq = Nq; x.nseg = nseg;
-  x.scale_log2e = 0.125f * 1.4426950408889634f;
-  x.seg[0] = AttnSeg{(const half_t*)K0, (const half_t*)V0, nkeys0, ld0, nkeys0, w0};
-  x.seg[1] = AttnSeg{(const half_t*)K1, (const half_t*)V1, nkeys1, ld1, nkeys1, w1};
-  if (!ia2p_qproj_xattn_ok(a, x)) return fail(nullptr, IA2P_ERR_SHAPE, "qproj_attention: shape not supported by the fused tile (bias must be 16-byte aligned)");
-  hipError_t e = ia2p_launch_qproj_xattn(a, x, (hipStream_t)stream);
-  RET_HIP(e, "qproj_attention");
-}
-ia2p_status ia2p_qkv_self_attention(void* stream, const void* X, const void* Wqkv, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo, int B, int heads, int K) {
-  if (!X || !Wqkv || !O) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention: null argument");
-  if (ln && (!ln->stats || !ln->colsum || !ln->fbias || ln->slots < 1)) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention: incomplete ia2p_ln_fold");
-  if (B < 1 || heads < 1 || K < 64 || K % 64 || ldo % 8 || (((uintptr_t)O) & 15)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention: K=%d (multiple of 64), ldo=%d (multiple of 8), O 16-byte aligned", K, ldo);
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  a.A = (const half_t*)X; a.W = (const half_t*)Wqkv; a.zero = zero_page(); a.M = B * 256; a.N = 3 * heads * 64; a.K = K; a.ldw = K; a.lda = K; a.ldc = a.N;
-  a.bias = (const half_t*)bias; a.rows_per_batch = 1;
-  if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->colsum; a.ln_bias = ln->fbias; a.ln_eps = ln->eps; }
-  AttnArgs x;
-  memset(&x, 0, sizeof x);
-  x.O = (half_t*)O; x.ldo = ldo; x.B = B; x.heads = heads; x.Nq = 256; x.nseg = 1;
-  x.scale_log2e = 0.125f * 1.4426950408889634f;
-  x.seg[0].nkeys = 256; x.seg[0].weight = 1.f;
-  if (!ia2p_qkv_sattn_ok(a, x)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention: shape / alignment not supported by the fused tile");
-  hipError_t e = ia2p_launch_qkv_sattn(a, x, (hipStream_t)stream);
-  RET_HIP(e, "qkv_self_attention");
-}
-// The same launch with the layer's slice of the context K/V projection riding on the CUs the (image, head) tiles leave empty (what the executor does per step for every
-// block that takes the fused launch; reference attention_processor.py:358-359 to_k / to_v on the text rows, :379-380 to_k_ip / to_v_ip on the image-token rows).
-// *in_launch (optional) = 1 when the slice ran inside the launch, 0 when fused tiles + context tiles exceed the device's compute units and the two projections ran as
-// launches of their own in front of it (the executor's route for such a block). Same bits either way.
-ia2p_status ia2p_qkv_self_attention_ctx(void* stream, const void* X, const void* Wqkv, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo, int B, int heads, int K,
-                                        const void* context, int L, int Li, int ctx_dim, const void* Wkv_text, const void* Wkv_ip, void* kv_text, void* kv_ip, int ldkv, int N,
-                                        int* in_launch) {
-  if (!X || !Wqkv || !O || !context || !Wkv_text || !kv_text || (Li > 0 && (!Wkv_ip || !kv_ip))) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention_ctx: null argument");
-  if (ln && (!ln->stats || !ln->colsum || !ln->fbias || ln->slots < 1)) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention_ctx: incomplete ia2p_ln_fold");
-  if (B < 1 || heads < 1 || K < 64 || K % 64 || ldo % 8 || (((uintptr_t)O) & 15)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: K=%d (multiple of 64), ldo=%d (multiple of 8), O 16-byte aligned", K, ldo);
-  if (Li < 0 || L <= Li || L > 0xffff || ctx_dim < 64 || ctx_dim % 64 || N < 8 || N % 8 || ldkv < N || ldkv % 8 || (((uintptr_t)kv_text) & 15) || (Li > 0 && (((uintptr_t)kv_ip) & 15)))
-    return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: L=%d > Li=%d >= 0, ctx_dim=%d (multiple of 64), N=%d and ldkv=%d (multiples of 8, ldkv >= N), outputs 16-byte aligned", L, Li, ctx_dim, N, ldkv);
-  if (!zero_page()) return fail(nullptr, IA2P_ERR_HIP, "cannot allocate zero page");
-  GemmArgs a;
-  memset(&a, 0, sizeof a);
-  a.pad = 1;
-  a.A = (const half_t*)X; a.W = (const half_t*)Wqkv; a.zero = zero_page(); a.M = B * 256; a.N = 3 * heads * 64; a.K = K; a.ldw = K; a.lda = K; a.ldc = a.N;
-  a.bias = (const half_t*)bias; a.rows_per_batch = 1;
-  if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->colsum; a.ln_bias = ln->fbias; a.ln_eps = ln->eps; }
-  AttnArgs x;
-  memset(&x, 0, sizeof x);
-  x.O = (half_t*)O; x.ldo = ldo; x.B = B; x.heads = heads; x.Nq = 256; x.nseg = 1;
-  x.scale_log2e = 0.125f * 1.4426950408889634f;
-  x.seg[0].nkeys = 256; x.seg[0].weight = 1.f;
-  if (!ia2p_qkv_sattn_ok(a, x)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: shape / alignment not supported by the fused tile");
-  const int Lt = L - Li;
-  CtxKvSlice k;
-  memset(&k, 0, sizeof k);
-  k.ctx = (const half_t*)context; k.lda = ctx_dim; k.L = L; k.Lt = Lt; k.Li = Li; k.B = B; k.Wt = (const half_t*)Wkv_text; k.Wi = (const half_t*)Wkv_ip;
-  k.Ct = (half_t*)kv_text; k.Ci = (half_t*)kv_ip; k.ldc = ldkv; k.N = N; k.K = ctx_dim;
-  const bool inl = ia2p_qkv_sattn_ctx_ok(x, k);
-  if (in_launch) *in_launch = inl ? 1 : 0;
-  hipError_t e = hipSuccess;
-  if (!inl) {      // the two projections as launches of their own (project_context's, for this slice)
-    for (int seg = 0; seg < (Li > 0 ? 2 : 1) && e == hipSuccess; ++seg) {
-      GemmArgs g;
-      memset(&g, 0, sizeof g);
-      g.pad = 1;
-      g.A = k.ctx; g.W = seg ? k.Wi : k.Wt; g.C = seg ? k.Ci : k.Ct; g.zero = zero_page(); g.M = B * (seg ? Li : Lt); g.N = N; g.K = ctx_dim; g.ldw = ctx_dim; g.lda = ctx_dim; g.ldc = ldkv;
-      g.rpb = seg ? Li : Lt; g.bstride = L; g.roff = seg ? Lt : 0; g.rows_per_batch = 1; g.m_fastest = g.M <= g.N ? 1 : 0; g.acc_scale = g.bias_scale = 1.f;
-      e = ia2p_launch_gemm_variant(g, false, ia2p_gemm_plan(g.M, g.N, g.K, false, false).variant, (hipStream_t)stream);
-    }
-  }
-  if (e == hipSuccess) e = ia2p_launch_qkv_sattn(a, x, (hipStream_t)stream, inl ? &k : nullptr);
-  RET_HIP(e, "qkv_self_attention_ctx");
-}
-ia2p_status ia2p_ip_attn_map(void* stream, const void* Q, int ldq, const void* Kip, int ldk, void* out, int B, int heads, int Nq, int ntok) {
-  if (!Q || !Kip || !out || B < 1 || heads < 1 || Nq < 1) return fail(nullptr, IA2P_ERR_INVALID, "ip_attn_map: bad argument");
-  if (ntok < 1 || ntok > 16 || ldq % 8 || ldq < heads * 64 || ldk < heads * 64) return fail(nullptr, IA2P_ERR_SHAPE, "ip_attn_map: ntok=%d (1..16), ldq=%d (mult of 8), ldk=%d", ntok, ldq, ldk);
-  hipError_t e = ia2p_launch_ip_attn_map((const half_t*)Q, ldq, (const half_t*)Kip, ldk, (half_t*)out, B, heads, Nq, ntok, (hipStream_t)stream);
-  RET_HIP(e, "ip_attn_map");
-}
-ia2p_status ia2p_linear_small(void* stream, const void* X, const void* W, const void* bias, void* out, int M, int N, int K, int silu_in, int silu_out) {
-  if (!X || !W || !out) return fail(nullptr, IA2P_ERR_INVALID, "linear_small: null argument");
-  if (M > 16 || K % 8) return fail(nullptr, IA2P_ERR_SHAPE, "linear_small: M=%d (<=16) K=%d (mult of 8)", M, K);
-  hipError_t e = ia2p_launch_linear_small((const half_t*)X, K, (const half_t*)W, (const half_t*)bias, nullptr, 0, (half_t*)out, N, M, N, K, silu_in, silu_out, (hipStream_t)stream);
-  RET_HIP(e, "linear_small");
-}
-
 ia2p_status ia2p_profile_enable(ia2p_ctx* c, int on) {
   if (!c) return IA2P_ERR_INVALID;
   for (auto& r : c->recs) { c->evpool.push_back(r.e0); c->evpool.push_back(r.e1); }

@@ -1,6 +1,6 @@
-// Runtime shared by the three executors (conditional UNet: engine.hip, VAE: vae_engine.hip, CLIP text towers: clip_engine.hip):
-// weight arena + parameter table, workspace allocator, weight-prefetch plan, per-kernel event timing, and the operator wrappers that
-// plan and launch the HIP kernels. Definitions live in engine.hip.
+// Runtime shared by the executors (conditional UNet: engine.hip, VAE: vae_engine.hip, CLIP text towers: clip_engine.hip, instruction LLM: llm_engine.hip) and the
+// per-operator C ABI (ops_abi.hip): weight arena + parameter table, workspace allocator, weight-prefetch plan, per-kernel event timing, and the operator wrappers that
+// plan and launch the HIP kernels. Definitions live in engine_rt.hip; the launch descriptors are built in launch_args.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "../../include/ia2p_debug.h"      // (the product ABI, ia2p.h, + the test hooks / profile interface this library also exports)
-#include "common.h"
+#include "launch_args.h"
 
 // ---- kernel launchers (gemm.hip, attention.hip, norm.hip, misc.hip) ------------------------------------------
 hipError_t ia2p_launch_gemm(const GemmArgs& a, bool conv, hipStream_t s, int* picked, int* combined = nullptr);
@@ -135,7 +135,7 @@ const char* prof_name(int k);
 
 // state shared by the executors (conditional UNet, VAE): weights, workspace, prefetch plan, per-kernel timing
 void ia2p_sk_counters_invalidate();      // gemm.hip: new epoch of the K-split ticket buffers
-int ia2p_default_xattn_min_tiles();      // < 0: the built-in threshold (engine.hip; test hook ia2p_debug_set_xattn_min_tiles)
+int ia2p_default_xattn_min_tiles();      // < 0: the built-in threshold (engine_rt.hip; test hook ia2p_debug_set_xattn_min_tiles)
 struct RunCtx {
   std::string err;
   std::unordered_map<std::string, Param> params;
@@ -257,8 +257,23 @@ struct ConvGn { bool fused = false; const half_t* X1b = nullptr; int C0 = 0; GnS
                 bool tune = false; const half_t* Xraw = nullptr; };
 // LayerNorm folded into a GEMM: where the consumer finds the row statistics and the folded constants
 struct LnIn { const float* stats; int slots; const float* cs; const float* lb; float eps; };
+// ... attached to the consumer's descriptor: from the executor's LnIn, or from the C ABI's ia2p_ln_fold (complete or refused: ln_fold_ok)
+inline void ln_attach(GemmArgs& a, const LnIn* ln) { if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->cs; a.ln_bias = ln->lb; a.ln_eps = ln->eps; } }
+inline void ln_attach(GemmArgs& a, const ia2p_ln_fold* ln) { if (ln) { a.ln_stats = ln->stats; a.ln_slots = ln->slots; a.ln_cs = ln->colsum; a.ln_bias = ln->fbias; a.ln_eps = ln->eps; } }
+inline bool ln_fold_ok(const ia2p_ln_fold* ln) { return !ln || (ln->stats && ln->colsum && ln->fbias && ln->slots >= 1); }
 
 // ---- operator wrappers: plan (tile / K-split / autotune), slabs, weight prefetch, profiling class, launch
+// the pieces op_gemm / op_conv3 are made of, for the executors' fused launches and the operator ABI: next launch's weight prefetch; the executor's linear-layer descriptor;
+// plan + slabs + launch of a finished descriptor; HBM bytes of a linear layer; rows per slot of GroupNorm column sums (stand-alone pass / a launch's own epilogue)
+void set_prefetch(RunCtx* c, GemmArgs& a, const half_t* W, size_t bytes);
+GemmArgs gemm_args(RunCtx* c, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
+                   half_t* C, int ldc, int M, int N, int K, int geglu, int rpb, int bstride, int roff, int ldw, const LnIn* ln, float* stats_out, int act);
+void run_gemm(RunCtx* c, GemmArgs& a, bool conv, const char* what, double flops, double bytes, int* stat_slots = nullptr, GnWant* gw = nullptr);
+double gemm_bytes(int M, int N, int K, int geglu, bool residual);
+int gn_fallback_rows(int HW);
+int gn_epilogue_rows(const GemmArgs& a, bool conv, int variant, int splitk, bool combined, int HW);
+ia2p_status tune_begin(RunCtx* c, int reps);      // autotune pass: scratch + RunCtx::tuning on / off (every run_gemm site of an unmeasured shape then times its candidates in place)
+void tune_end(RunCtx* c, hipStream_t s);
 void op_gemm(RunCtx* c, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
              half_t* C, int ldc, int M, int N, int K, int geglu = 0, int rpb = 0, int bstride = 0, int roff = 0, int ldw = 0,
              const LnIn* ln = nullptr, float* stats_out = nullptr, int* stat_slots = nullptr, int act = 0, GnWant* gw = nullptr);

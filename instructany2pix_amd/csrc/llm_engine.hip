@@ -1,4 +1,4 @@
-// LLaMA decoder executor (the instruction LLM) and its C ABI (ia2p_llm_*): see include/ia2p.h and DESIGN.md §10. Runtime and operator wrappers: engine_rt.h / engine.hip.
+// LLaMA decoder executor (the instruction LLM) and its C ABI (ia2p_llm_*): see include/ia2p.h and DESIGN.md §10. Runtime and operator wrappers: engine_rt.h / engine_rt.hip.
 #include "engine_rt.h"
 
 // =====================================================================================================================

@@ -1,0 +1,327 @@
+// The context-less C ABI (include/ia2p.h, ia2p_debug.h): the sampler updates and one entry point per operator -- argument checks, a launch descriptor from launch_args.h,
+// the launcher. The surface the per-operator GPU tests go through; needs engine_rt.hip (error state, zero page, plan helpers), nothing of any executor.
+#include "engine_rt.h"
+
+extern "C" {
+
+int ia2p_device_is_gfx950(void) {
+  int dev = 0;
+  hipDeviceProp_t p;
+  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
+  return strncmp(p.gcnArchName, "gfx950", 6) == 0;
+}
+
+ia2p_status ia2p_ddim_step(void* stream, const void* x, const void* eu, const void* ec, float g, float c_x, float c_e, void* out, void* out2, int64_t n) {
+  if (!x || !eu || !out || n < 0) return fail(nullptr, IA2P_ERR_INVALID, "ddim_step: null argument");
+  hipError_t e = ia2p_launch_ddim_step((const half_t*)x, (const half_t*)eu, (const half_t*)ec, g, c_x, c_e, (half_t*)out, (half_t*)out2, (long)n, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "ddim_step");
+}
+
+// The same update with per-request coefficients: coef (device, float [B][3]) = {guidance g, c_x, c_e} of batch element b, `per` elements each --
+// requests with their own guidance scale (reference pipeline.py:303 `cfg`) at their own step of their own schedule share one launch.
+ia2p_status ia2p_ddim_step_v(void* stream, const void* x, const void* eu, const void* ec, const float* coef, void* out, void* out2, int B, int64_t per) {
+  if (!x || !eu || !out || !coef || B < 0 || per < 1) return fail(nullptr, IA2P_ERR_INVALID, "ddim_step_v: bad argument");
+  hipError_t e = ia2p_launch_ddim_step((const half_t*)x, (const half_t*)eu, (const half_t*)ec, 0.f, 0.f, 0.f, (half_t*)out, (half_t*)out2, (long)B * per, (hipStream_t)stream, coef, (long)per);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "ddim_step_v");
+}
+
+ia2p_status ia2p_mask_blend(void* stream, const void* x, const void* init, const void* noise, const void* mask, float c0, float c1,
+                            void* out, void* out2, int B, int C, int64_t HW) {
+  if (!x || !init || !noise || !mask || !out || B < 0 || C < 1 || HW < 1) return fail(nullptr, IA2P_ERR_INVALID, "mask_blend: bad argument");
+  hipError_t e = ia2p_launch_mask_blend((const half_t*)x, (const half_t*)init, (const half_t*)noise, (const half_t*)mask, c0, c1, (half_t*)out, (half_t*)out2,
+                                        B, C, (long)HW, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "mask_blend");
+}
+
+ia2p_status ia2p_prior_step(void* stream, const float* sample, const void* out_cond, const void* out_uncond, const float* noise, float g, float sqrt_a,
+                            float sqrt_b, float k0, float k1, float sigma, float* out, int64_t n) {
+  if (!sample || !out_uncond || !out || n < 0 || !(sqrt_a > 0.f) || !(sqrt_b > 0.f)) return fail(nullptr, IA2P_ERR_INVALID, "prior_step: bad argument");
+  hipError_t e = ia2p_launch_prior_step(sample, (const half_t*)out_cond, (const half_t*)out_uncond, noise, g, sqrt_a, sqrt_b, k0, k1, sigma, out, (long)n, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "prior_step");
+}
+
+// ---- per-operator entry points ---------------------------------------------------------------------------------------
+
+ia2p_status ia2p_groupnorm_silu(void* stream, const void* x, void* y, const void* gamma, const void* beta, int B, int HW, int C, int groups, float eps, int silu, float* partial) {
+  if (!x || !y || !gamma || !beta || !partial) return fail(nullptr, IA2P_ERR_INVALID, "groupnorm: null argument");
+  if (C % 8 || C % groups || groups > 256) return fail(nullptr, IA2P_ERR_SHAPE, "groupnorm: C=%d groups=%d", C, groups);
+  hipError_t e = ia2p_launch_groupnorm((const half_t*)x, C, (half_t*)y, C, (const half_t*)gamma, (const half_t*)beta, partial, B, HW, C, groups, eps, silu, (hipStream_t)stream);
+  RET_HIP(e, "groupnorm");
+}
+ia2p_status ia2p_layernorm(void* stream, const void* x, void* y, const void* gamma, const void* beta, int M, int C, float eps) {
+  if (!x || !y || !gamma || !beta) return fail(nullptr, IA2P_ERR_INVALID, "layernorm: null argument");
+  if (C % 8 || C > 2048) return fail(nullptr, IA2P_ERR_SHAPE, "layernorm: C=%d must be a multiple of 8 and <= 2048", C);
+  hipError_t e = ia2p_launch_layernorm((const half_t*)x, C, (half_t*)y, C, (const half_t*)gamma, (const half_t*)beta, M, C, eps, (hipStream_t)stream);
+  RET_HIP(e, "layernorm");
+}
+ia2p_status ia2p_gemm(void* stream, const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K, int geglu) {
+  if (!A || !W || !C) return fail(nullptr, IA2P_ERR_INVALID, "gemm: null argument");
+  if (K % 64 || N % 4 || (geglu && (N % 32 || !bias))) return fail(nullptr, IA2P_ERR_SHAPE, "gemm: K=%d must be a multiple of 64, N=%d of 4 (GEGLU: 32, with bias)", K, N);
+  const int No = geglu ? N / 2 : N;
+  const GemmArgs a = gemm_desc(zero_page(), (const half_t*)A, K, (const half_t*)W, K, (const half_t*)bias, (const half_t*)residual, No, (half_t*)C, No, M, N, K, geglu);
+  hipError_t e = ia2p_launch_gemm(a, false, (hipStream_t)stream, nullptr);
+  RET_HIP(e, "gemm");
+}
+// GEGLU feed-forward of a BasicTransformerBlock as an operator: H = geglu(X . W1p^T + b1p) [M, 4 C] (packed weights: ia2p_pack_geglu), out = H . W2^T + b2 + R,
+// as the executor runs it (two launches, the library's plans). splitk / partial: K split of the second GEMM (partial: splitk * M * C floats) or 0.
+ia2p_status ia2p_ffn(void* stream, const void* X, const void* W1p, const void* b1p, const void* W2, const void* b2, const void* R, void* H, void* out,
+                     int M, int C, int splitk, float* partial) {
+  if (!X || !W1p || !b1p || !W2 || !H || !out) return fail(nullptr, IA2P_ERR_INVALID, "ffn: null argument");
+  if (C % 64 || (splitk > 1 && (!partial || splitk > 4 * C / 64 || splitk > 255))) return fail(nullptr, IA2P_ERR_SHAPE, "ffn: C=%d must be a multiple of 64, splitk=%d needs slabs", C, splitk);
+  const GemmArgs a = gemm_desc(zero_page(), (const half_t*)X, C, (const half_t*)W1p, C, (const half_t*)b1p, nullptr, 0, (half_t*)H, 4 * C, M, 8 * C, C, 1);
+  GemmArgs b = gemm_desc(zero_page(), (const half_t*)H, 4 * C, (const half_t*)W2, 4 * C, (const half_t*)b2, (const half_t*)R, C, (half_t*)out, C, M, C, 4 * C);
+  if (splitk > 1) { b.splitk = splitk; b.partial = partial; }
+  const GemmPlan pa = ia2p_gemm_plan(a.M, a.N, a.K, false, true), pb = ia2p_gemm_plan(b.M, b.N, b.K, false, false);
+  hipError_t e = ia2p_launch_gemm_variant(a, false, pa.variant, (hipStream_t)stream);
+  if (e == hipSuccess) e = ia2p_launch_gemm_variant(b, false, pb.variant, (hipStream_t)stream);
+  RET_HIP(e, "ffn");
+}
+ia2p_status ia2p_fold_layernorm(void* stream, const void* W, const void* gamma, const void* beta, const void* bias, void* Wf, float* colsum,
+                                float* fbias, int N, int K) {
+  if (!W || !gamma || !beta || !Wf || !colsum || !fbias || N < 1 || K < 1) return fail(nullptr, IA2P_ERR_INVALID, "fold_layernorm: bad argument");
+  hipError_t e = ia2p_launch_fold_ln((const half_t*)W, (const half_t*)gamma, (const half_t*)beta, (const half_t*)bias, (half_t*)Wf, colsum, fbias, N, K, (hipStream_t)stream);
+  RET_HIP(e, "fold_layernorm");
+}
+ia2p_status ia2p_gemm_ex(void* stream, const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K, int geglu,
+                         const ia2p_ln_fold* ln, float* stats_out, int* stats_slots, int splitk, float* partial) {
+  if (!A || !W || !C) return fail(nullptr, IA2P_ERR_INVALID, "gemm_ex: null argument");
+  if (K % 64 || N % 4 || (geglu && (N % 32 || (!bias && !ln)))) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_ex: K=%d must be a multiple of 64, N=%d of 4 (GEGLU: 32, with bias)", K, N);
+  if (splitk > 1 && (!partial || geglu || splitk > K / 64 || splitk > 255)) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_ex: splitk=%d needs a slab, no GEGLU, and <= min(K/64, 255)", splitk);
+  if (!ln_fold_ok(ln)) return fail(nullptr, IA2P_ERR_INVALID, "gemm_ex: incomplete ia2p_ln_fold");
+  if (stats_out && geglu) return fail(nullptr, IA2P_ERR_INVALID, "gemm_ex: row statistics of a GEGLU output are not provided");
+  const int No = geglu ? N / 2 : N;
+  GemmArgs a = gemm_desc(zero_page(), (const half_t*)A, K, (const half_t*)W, K, (const half_t*)bias, (const half_t*)residual, No, (half_t*)C, No, M, N, K, geglu);
+  ln_attach(a, ln);
+  a.stats_out = stats_out;
+  if (splitk > 1) { a.splitk = splitk; a.partial = partial; }
+#ifdef IA2P_CLOCK_STAMP
+  else if (partial) a.partial = partial;      // (diagnostic builds: the in-kernel stamps of an unsplit launch go to the caller's buffer, tools/insitu_stamps.py)
+#endif
+  int pick = 0, combined = 0;
+  hipError_t e = ia2p_launch_gemm(a, false, (hipStream_t)stream, &pick, &combined);
+  if (stats_slots && pick >= 0 && pick < IA2P_GEMM_NVARIANT) *stats_slots = (splitk > 1 && !combined) ? 1 : (N + IA2P_GEMM_TILES[pick].bn - 1) / IA2P_GEMM_TILES[pick].bn;
+  RET_HIP(e, "gemm_ex");
+}
+ia2p_status ia2p_gemm_splitk(void* stream, const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K,
+                             int splitk, float* partial) {
+  if (!A || !W || !C || !partial) return fail(nullptr, IA2P_ERR_INVALID, "gemm_splitk: null argument");
+  if (K % 64 || N % 4 || splitk < 1 || splitk > K / 64 || splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_splitk: K=%d N=%d splitk=%d (1 .. min(K / 64, 255))", K, N, splitk);
+  GemmArgs a = gemm_desc(zero_page(), (const half_t*)A, K, (const half_t*)W, K, (const half_t*)bias, (const half_t*)residual, N, (half_t*)C, N, M, N, K);
+  a.splitk = splitk; a.partial = partial;
+  hipError_t e = ia2p_launch_gemm(a, false, (hipStream_t)stream, nullptr);
+  RET_HIP(e, "gemm_splitk");
+}
+ia2p_status ia2p_conv3x3(void* stream, const void* x, const void* Wp, const void* bias, const void* rowvec, const void* residual, void* y,
+                         int B, int Hs, int Ws, int Cin, int Co, int stride, int up) {
+  if (!x || !Wp || !y) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3: null argument");
+  if (Cin % 64 || Co % 4 || (stride != 1 && stride != 2) || (up != 0 && up != 1)) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3: Cin=%d (mult of 64) Co=%d (mult of 4) stride=%d up=%d", Cin, Co, stride, up);
+  const GemmArgs a = conv3_desc(zero_page(), (const half_t*)x, B, Hs, Ws, Cin, (const half_t*)Wp, (const half_t*)bias, Co, stride, up, 1, (const half_t*)rowvec, Co, (const half_t*)residual, (half_t*)y);
+  hipError_t e = ia2p_launch_gemm(a, true, (hipStream_t)stream, nullptr);
+  RET_HIP(e, "conv3x3");
+}
+// the stride-1 form with K split over `splitk` workgroups per tile (what the executor launches for the 16 x 16 feature maps); partial: splitk * B*Hs*Ws * Co floats
+ia2p_status ia2p_conv3x3_splitk(void* stream, const void* x, const void* Wp, const void* bias, const void* rowvec, const void* residual, void* y,
+                                int B, int Hs, int Ws, int Cin, int Co, int splitk, float* partial) {
+  if (!x || !Wp || !y || (splitk > 1 && !partial)) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_splitk: null argument (partial is needed for splitk > 1 only)");
+  if (Cin % 64 || Co % 4 || splitk < 1 || splitk > 9 * Cin / 64 || splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_splitk: Cin=%d (mult of 64) Co=%d (mult of 4) splitk=%d (1 .. 9 Cin / 64)", Cin, Co, splitk);
+  GemmArgs a = conv3_desc(zero_page(), (const half_t*)x, B, Hs, Ws, Cin, (const half_t*)Wp, (const half_t*)bias, Co, 1, 0, 1, (const half_t*)rowvec, Co, (const half_t*)residual, (half_t*)y);
+  if (splitk > 1) { a.splitk = splitk; a.partial = partial; }
+  hipError_t e = ia2p_launch_gemm(a, true, (hipStream_t)stream, nullptr);
+  RET_HIP(e, "conv3x3_splitk");
+}
+// ---- GroupNorm from producer-side column sums (round 5; csrc/gn_fold.h): the operators of the fused path, one by one -----------------------------------------------
+// canonical statistics of a tensor x [M, C]: out[(slot * C + c) * 2 + {0, 1}] = {sum, sum of squares} (fp64) over the `rows` rows of slot `slot` (what a GEMM / conv epilogue
+// leaves for its own output when asked: ia2p_gemm_gnstats, ia2p_conv3x3_gn)
+ia2p_status ia2p_gn_colstats(void* stream, const void* x, int M, int C, int rows, double* out) {
+  if (!x || !out) return fail(nullptr, IA2P_ERR_INVALID, "gn_colstats: null argument");
+  if (C < 8 || C % 8 || rows < 16 || rows % 16 || M < 1 || M % rows) return fail(nullptr, IA2P_ERR_SHAPE, "gn_colstats: C=%d (multiple of 8), rows=%d (multiple of 16 dividing M=%d)", C, rows, M);
+  hipError_t e = ia2p_launch_gn_colstats((const half_t*)x, C, M, C, rows, out, (hipStream_t)stream);
+  RET_HIP(e, "gn_colstats");
+}
+static ia2p_status gn_in_from_abi(const char* what, GemmArgs::GnIn* g, int C0, const double* st0, int rows0, int C1, const double* st1, int rows1, const void* gamma, const void* beta, int groups, float eps, int silu, int HW) {
+  const int C = C0 + C1;
+  if (!st0 || !gamma || !beta || (C1 > 0 && !st1)) return fail(nullptr, IA2P_ERR_INVALID, "%s: null argument", what);
+  if (groups < 1 || groups > 64 || C % groups || C0 < 8 || C0 % 8 || C1 < 0 || C1 % 8 || rows0 < 1 || HW % rows0 || (C1 > 0 && (rows1 < 1 || HW % rows1)))
+    return fail(nullptr, IA2P_ERR_SHAPE, "%s: C0=%d C1=%d groups=%d rows0=%d rows1=%d HW=%d", what, C0, C1, groups, rows0, rows1, HW);
+  *g = gn_in_desc(st0, rows0, C1 > 0 ? st1 : nullptr, rows1, C0, C, (const half_t*)gamma, (const half_t*)beta, groups, eps, silu);
+  return IA2P_OK;
+}
+// y = [silu](GroupNorm(groups)([x0 | x1])) with the statistics folded from the column sums of the sources' producers: the stand-alone twin of what ia2p_conv3x3_gn
+// does to its operand inside the convolution (same fold, same scale / shift, same element formula: the two agree to the bit)
+ia2p_status ia2p_gn_apply_stats(void* stream, const void* x0, int C0, const double* st0, int rows0, const void* x1, int C1, const double* st1, int rows1,
+                                const void* gamma, const void* beta, void* y, int B, int HW, int groups, float eps, int silu) {
+  if (!x0 || !y || (C1 > 0 && !x1)) return fail(nullptr, IA2P_ERR_INVALID, "gn_apply_stats: null argument");
+  GemmArgs::GnIn g;
+  const ia2p_status st = gn_in_from_abi("gn_apply_stats", &g, C0, st0, rows0, C1, st1, rows1, gamma, beta, groups, eps, silu, HW);
+  if (st != IA2P_OK) return st;
+  hipError_t e = ia2p_launch_gn_apply_stats((const half_t*)x0, C0, C1 > 0 ? (const half_t*)x1 : nullptr, C1, (half_t*)y, C0 + C1, B, HW, C0 + C1, g, (hipStream_t)stream);
+  RET_HIP(e, "gn_apply_stats");
+}
+// 3x3 convolution (stride 1) of silu(GroupNorm([x0 | x1])) with the norm applied INSIDE the convolution (d->st0 != NULL; conv_halo_kernel.h GN = 1), or of x0 itself
+// (d->st0 == NULL), + optional appended 1x1 block, time-embedding row, residual, K split; d->gn_out != NULL: also the column sums of y (*gn_out_rows: rows per slot,
+// 0 when this launch could not take them). Fused form: the site must have a halo-staged plan (IA2P_ERR_SHAPE otherwise; tests force one with ia2p_debug_set_gemm_tile).
+ia2p_status ia2p_conv3x3_gn(void* stream, const ia2p_conv_gn* d, int* gn_out_rows) {
+  if (gn_out_rows) *gn_out_rows = 0;
+  if (!d || !d->x0 || !d->Wp || !d->y || (d->splitk > 1 && !d->partial) || (d->Ca > 0 && !d->xa)) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_gn: null argument");
+  const int Cin = d->C0 + (d->st0 ? d->C1 : 0), HW = d->H * d->W;
+  if (Cin % 64 || d->C0 % 64 || d->Co % 8 || d->Ca % 64 || d->B < 1 || HW < 1 || d->splitk < 0 || d->splitk > (9 * Cin + d->Ca) / 64 || d->splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_gn: C0=%d C1=%d Co=%d Ca=%d splitk=%d", d->C0, d->C1, d->Co, d->Ca, d->splitk);
+  GemmArgs a = conv3_desc(zero_page(), (const half_t*)d->x0, d->B, d->H, d->W, Cin, (const half_t*)d->Wp, (const half_t*)d->bias, d->Co, 1, 0, 1, (const half_t*)d->rowvec, d->Co, (const half_t*)d->residual, (half_t*)d->y,
+                          d->Ca > 0 ? (const half_t*)d->xa : nullptr, d->Ca > 0 ? d->Ca : 0);
+  a.lda = d->C0;
+  if (d->splitk > 1) { a.splitk = d->splitk; a.partial = d->partial; }
+  const GemmPlan pl = ia2p_gemm_plan(a.M, a.N, a.K, true, false);
+  if (d->st0) {
+    const ia2p_status st = gn_in_from_abi("conv3x3_gn", &a.gn, d->C0, d->st0, d->rows0, d->C1, d->st1, d->rows1, d->gamma, d->beta, d->groups, d->eps, 1, HW);
+    if (st != IA2P_OK) return st;
+    a.A1b = d->C1 > 0 ? (const half_t*)d->x1 : nullptr; a.lda1b = d->C1;
+    if (d->C1 > 0 && !d->x1) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_gn: null second source");
+    if (!ia2p_conv_gn_fusable(a, pl.variant, a.splitk) || !ia2p_conv_gn_ok(a)) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_gn: this site has no halo-staged plan (variant %d) or its statistics do not fit the fused kernel", pl.variant);
+  }
+  const bool combined = a.splitk > 1 && ia2p_splitk_inkernel(a.M, a.N, a.splitk);
+  int rows = 0;
+  if (d->gn_out) { rows = gn_epilogue_rows(a, true, pl.variant, a.splitk, combined, HW); if (rows) a.gn_out = d->gn_out; }
+  int comb = 0;
+  hipError_t e = ia2p_launch_gemm_variant(a, true, pl.variant, (hipStream_t)stream, true, &comb);
+  if (e == hipSuccess && gn_out_rows) *gn_out_rows = (rows && (a.splitk <= 1 || comb)) ? rows : 0;
+  RET_HIP(e, "conv3x3_gn");
+}
+// C = A . W^T + bias + residual as ia2p_gemm_splitk (splitk <= 1: no split), also leaving the GroupNorm column sums of C for images of HW rows (a Transformer2DModel's
+// proj_out in front of the next ResnetBlock2D); *rows: rows per slot, 0 when the tile the plan picked cannot take them (the caller runs ia2p_gn_colstats)
+ia2p_status ia2p_gemm_gnstats(void* stream, const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K, int splitk, float* partial,
+                              int HW, double* gn_out, int* rows) {
+  if (rows) *rows = 0;
+  if (!A || !W || !C || !gn_out || !rows || (splitk > 1 && !partial)) return fail(nullptr, IA2P_ERR_INVALID, "gemm_gnstats: null argument");
+  if (K % 64 || N % 8 || HW < 16 || M % HW || splitk < 0 || splitk > K / 64 || splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_gnstats: K=%d N=%d HW=%d splitk=%d", K, N, HW, splitk);
+  GemmArgs a = gemm_desc(zero_page(), (const half_t*)A, K, (const half_t*)W, K, (const half_t*)bias, (const half_t*)residual, N, (half_t*)C, N, M, N, K);
+  if (splitk > 1) { a.splitk = splitk; a.partial = partial; }
+  const GemmPlan pl = ia2p_gemm_plan(M, N, K, false, false);
+  const bool combined = splitk > 1 && ia2p_splitk_inkernel(M, N, splitk);
+  const int r = gn_epilogue_rows(a, false, pl.variant, a.splitk, combined, HW);
+  if (r) a.gn_out = gn_out;
+  int comb = 0;
+  hipError_t e = ia2p_launch_gemm_variant(a, false, pl.variant, (hipStream_t)stream, true, &comb);
+  if (e == hipSuccess) *rows = (r && (a.splitk <= 1 || comb)) ? r : 0;
+  RET_HIP(e, "gemm_gnstats");
+}
+// ResnetBlock2D tail as one implicit GEMM: y = conv3x3(x, W2) + conv1x1(x2, Wsc) + bias (+ rowvec), K = 9 Cin + Cin2; Wcat rows = [packed W2 row | Wsc row]
+ia2p_status ia2p_conv3x3_cat(void* stream, const void* x, const void* x2, const void* Wcat, const void* bias, void* y, int B, int Hs, int Ws, int Cin, int Cin2, int Co) {
+  if (!x || !x2 || !Wcat || !y) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_cat: null argument");
+  if (Cin % 64 || Cin2 % 64 || Cin2 < 64 || Co % 4) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_cat: Cin=%d, Cin2=%d (multiples of 64) Co=%d (mult of 4)", Cin, Cin2, Co);
+  const GemmArgs a = conv3_desc(zero_page(), (const half_t*)x, B, Hs, Ws, Cin, (const half_t*)Wcat, (const half_t*)bias, Co, 1, 0, 1, nullptr, 0, nullptr, (half_t*)y, (const half_t*)x2, Cin2);
+  hipError_t e = ia2p_launch_gemm(a, true, (hipStream_t)stream, nullptr);
+  RET_HIP(e, "conv3x3_cat");
+}
+ia2p_status ia2p_pack_conv3x3(void* stream, const void* src, void* dst, int Co, int Cin) {
+  if (!src || !dst) return fail(nullptr, IA2P_ERR_INVALID, "pack_conv3x3: null argument");
+  if (Cin % 64) return fail(nullptr, IA2P_ERR_SHAPE, "pack_conv3x3: Cin=%d must be a multiple of 64 (the layout of ia2p_conv3x3; ia2p_pack_conv_out packs for ia2p_conv_out)", Cin);
+  hipError_t e = ia2p_launch_pack_conv((const half_t*)src, (half_t*)dst, Co, Cin, (hipStream_t)stream);
+  RET_HIP(e, "pack_conv3x3");
+}
+ia2p_status ia2p_pack_conv_out(void* stream, const void* src, void* dst, int Co, int C) {
+  if (!src || !dst) return fail(nullptr, IA2P_ERR_INVALID, "pack_conv_out: null argument");
+  hipError_t e = ia2p_launch_pack_conv((const half_t*)src, (half_t*)dst, Co, C, (hipStream_t)stream);
+  RET_HIP(e, "pack_conv_out");
+}
+// latent-boundary convolutions as operators (the executors call the launchers directly): conv_in reads NCHW and writes channels-last,
+// conv_out reads channels-last and writes NCHW; reference call sites: the diffusers UNet's conv_in / conv_out behind pnp_pipeline.py:253-260
+ia2p_status ia2p_conv_in(void* stream, const void* x_nchw, const void* w_oihw, const void* bias, void* y_nhwc, void* w_scratch, int B, int Cin, int H, int W, int Co) {
+  if (!x_nchw || !w_oihw || !bias || !y_nhwc || !w_scratch) return fail(nullptr, IA2P_ERR_INVALID, "conv_in: null argument");
+  if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cin * 9 > 64 || Co < 8 || Co % 8) return fail(nullptr, IA2P_ERR_SHAPE, "conv_in: Cin*9=%d must be <= 64, Co=%d a multiple of 8", Cin * 9, Co);
+  hipError_t e = ia2p_launch_pack_conv_in((const half_t*)w_oihw, (half_t*)w_scratch, Co, Cin * 9, (hipStream_t)stream);
+  if (e == hipSuccess) e = ia2p_launch_conv_in((const half_t*)x_nchw, (const half_t*)w_scratch, (const half_t*)bias, (half_t*)y_nhwc, B, Cin, H, W, Co, (hipStream_t)stream);
+  RET_HIP(e, "conv_in");
+}
+ia2p_status ia2p_conv_out(void* stream, const void* x_nhwc, const void* w_packed, const void* bias, void* y_nchw, int B, int C, int H, int W, int Co) {
+  if (!x_nhwc || !w_packed || !bias || !y_nchw) return fail(nullptr, IA2P_ERR_INVALID, "conv_out: null argument");
+  if (B < 1 || H < 1 || W < 1 || C < 32 || C % 32 || Co < 1 || Co > 8) return fail(nullptr, IA2P_ERR_SHAPE, "conv_out: C=%d must be a multiple of 32, Co=%d <= 8", C, Co);
+  hipError_t e = ia2p_launch_conv_out((const half_t*)x_nhwc, C, (const half_t*)w_packed, (const half_t*)bias, (half_t*)y_nchw, B, C, H, W, Co, (hipStream_t)stream);
+  RET_HIP(e, "conv_out");
+}
+ia2p_status ia2p_pack_geglu(void* stream, const void* src, void* dst, int rows, int rowlen) {
+  if (!src || !dst || rows % 32) return fail(nullptr, IA2P_ERR_SHAPE, "pack_geglu: rows must be a multiple of 32");
+  hipError_t e = ia2p_launch_pack_geglu((const half_t*)src, (half_t*)dst, rows, rowlen, (hipStream_t)stream);
+  RET_HIP(e, "pack_geglu");
+}
+ia2p_status ia2p_attention(void* stream, const void* Q, int ldq, void* O, int ldo, int B, int heads, int Nq, int nseg,
+                           const void* K0, const void* V0, int ld0, int nkeys0, float w0, const void* K1, const void* V1, int ld1, int nkeys1, float w1) {
+  if (!Q || !O || !K0 || !V0 || nseg < 1 || nseg > 2 || (nseg == 2 && (!K1 || !V1))) return fail(nullptr, IA2P_ERR_INVALID, "attention: bad argument");
+  if (nkeys0 < 1 || (nseg == 2 && nkeys1 < 1) || ldq % 8 || ldo % 8 || (((uintptr_t)O) & 15) || ld0 % 8 || (nseg == 2 && ld1 % 8)) return fail(nullptr, IA2P_ERR_SHAPE, "attention: key counts must be >= 1, strides multiples of 8, O 16-byte aligned");
+  const AttnArgs a = attn_desc((const half_t*)Q, ldq, (half_t*)O, ldo, B, heads, Nq, nseg, AttnSeg{(const half_t*)K0, (const half_t*)V0, nkeys0, ld0, nkeys0, w0},
+                               AttnSeg{(const half_t*)K1, (const half_t*)V1, nkeys1, ld1, nkeys1, w1});
+  hipError_t e = ia2p_launch_attention(a, (hipStream_t)stream);
+  RET_HIP(e, "attention");
+}
+ia2p_status ia2p_qproj_attention(void* stream, const void* X, const void* Wq, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo, int B, int heads,
+                                 int Nq, int K, int nseg, const void* K0, const void* V0, int ld0, int nkeys0, float w0,
+                                 const void* K1, const void* V1, int ld1, int nkeys1, float w1) {
+  if (!X || !Wq || !O || !K0 || !V0 || nseg < 1 || nseg > 2 || (nseg == 2 && (!K1 || !V1))) return fail(nullptr, IA2P_ERR_INVALID, "qproj_attention: bad argument");
+  if (!ln_fold_ok(ln)) return fail(nullptr, IA2P_ERR_INVALID, "qproj_attention: incomplete ia2p_ln_fold");
+  if (B < 1 || heads < 1 || Nq < 128 || Nq % 128 || K < 64 || K % 64 || nkeys0 < 1 || (nseg == 2 && nkeys1 < 1) || ldo % 8 || (((uintptr_t)O) & 15) || ld0 % 8 || (nseg == 2 && ld1 % 8))
+    return fail(nullptr, IA2P_ERR_SHAPE, "qproj_attention: Nq=%d must be a multiple of 128, K=%d of 64, key counts >= 1, strides multiples of 8, O 16-byte aligned", Nq, K);
+  GemmArgs a = gemm_desc(zero_page(), (const half_t*)X, K, (const half_t*)Wq, K, (const half_t*)bias, nullptr, 0, nullptr, heads * 64, B * Nq, heads * 64, K);
+  ln_attach(a, ln);
+  const AttnArgs x = attn_desc(nullptr, 0, (half_t*)O, ldo, B, heads, Nq, nseg, AttnSeg{(const half_t*)K0, (const half_t*)V0, nkeys0, ld0, nkeys0, w0},
+                               AttnSeg{(const half_t*)K1, (const half_t*)V1, nkeys1, ld1, nkeys1, w1});
+  if (!ia2p_qproj_xattn_ok(a, x)) return fail(nullptr, IA2P_ERR_SHAPE, "qproj_attention: shape not supported by the fused tile (bias must be 16-byte aligned)");
+  hipError_t e = ia2p_launch_qproj_xattn(a, x, (hipStream_t)stream);
+  RET_HIP(e, "qproj_attention");
+}
+ia2p_status ia2p_qkv_self_attention(void* stream, const void* X, const void* Wqkv, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo, int B, int heads, int K) {
+  if (!X || !Wqkv || !O) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention: null argument");
+  if (!ln_fold_ok(ln)) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention: incomplete ia2p_ln_fold");
+  if (B < 1 || heads < 1 || K < 64 || K % 64 || ldo % 8 || (((uintptr_t)O) & 15)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention: K=%d (multiple of 64), ldo=%d (multiple of 8), O 16-byte aligned", K, ldo);
+  GemmArgs a = qkv_desc(zero_page(), (const half_t*)X, K, (const half_t*)Wqkv, (const half_t*)bias, B * 256, 3 * heads * 64, K);
+  ln_attach(a, ln);
+  const AttnArgs x = sattn_desc((half_t*)O, ldo, B, heads, 256);
+  if (!ia2p_qkv_sattn_ok(a, x)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention: shape / alignment not supported by the fused tile");
+  hipError_t e = ia2p_launch_qkv_sattn(a, x, (hipStream_t)stream);
+  RET_HIP(e, "qkv_self_attention");
+}
+// The same launch with the layer's slice of the context K/V projection riding on the CUs the (image, head) tiles leave empty (what the executor does per step for every
+// block that takes the fused launch; reference attention_processor.py:358-359 to_k / to_v on the text rows, :379-380 to_k_ip / to_v_ip on the image-token rows).
+// *in_launch (optional) = 1 when the slice ran inside the launch, 0 when fused tiles + context tiles exceed the device's compute units and the two projections ran as
+// launches of their own in front of it (the executor's route for such a block). Same bits either way.
+ia2p_status ia2p_qkv_self_attention_ctx(void* stream, const void* X, const void* Wqkv, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo, int B, int heads, int K,
+                                        const void* context, int L, int Li, int ctx_dim, const void* Wkv_text, const void* Wkv_ip, void* kv_text, void* kv_ip, int ldkv, int N,
+                                        int* in_launch) {
+  if (!X || !Wqkv || !O || !context || !Wkv_text || !kv_text || (Li > 0 && (!Wkv_ip || !kv_ip))) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention_ctx: null argument");
+  if (!ln_fold_ok(ln)) return fail(nullptr, IA2P_ERR_INVALID, "qkv_self_attention_ctx: incomplete ia2p_ln_fold");
+  if (B < 1 || heads < 1 || K < 64 || K % 64 || ldo % 8 || (((uintptr_t)O) & 15)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: K=%d (multiple of 64), ldo=%d (multiple of 8), O 16-byte aligned", K, ldo);
+  if (Li < 0 || L <= Li || L > 0xffff || ctx_dim < 64 || ctx_dim % 64 || N < 8 || N % 8 || ldkv < N || ldkv % 8 || (((uintptr_t)kv_text) & 15) || (Li > 0 && (((uintptr_t)kv_ip) & 15)))
+    return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: L=%d > Li=%d >= 0, ctx_dim=%d (multiple of 64), N=%d and ldkv=%d (multiples of 8, ldkv >= N), outputs 16-byte aligned", L, Li, ctx_dim, N, ldkv);
+  if (!zero_page()) return fail(nullptr, IA2P_ERR_HIP, "cannot allocate zero page");
+  GemmArgs a = qkv_desc(zero_page(), (const half_t*)X, K, (const half_t*)Wqkv, (const half_t*)bias, B * 256, 3 * heads * 64, K);
+  ln_attach(a, ln);
+  const AttnArgs x = sattn_desc((half_t*)O, ldo, B, heads, 256);
+  if (!ia2p_qkv_sattn_ok(a, x)) return fail(nullptr, IA2P_ERR_SHAPE, "qkv_self_attention_ctx: shape / alignment not supported by the fused tile");
+  const int Lt = L - Li;
+  CtxKvSlice k;
+  memset(&k, 0, sizeof k);
+  k.ctx = (const half_t*)context; k.lda = ctx_dim; k.L = L; k.Lt = Lt; k.Li = Li; k.B = B; k.Wt = (const half_t*)Wkv_text; k.Wi = (const half_t*)Wkv_ip;
+  k.Ct = (half_t*)kv_text; k.Ci = (half_t*)kv_ip; k.ldc = ldkv; k.N = N; k.K = ctx_dim;
+  const bool inl = ia2p_qkv_sattn_ctx_ok(x, k);
+  if (in_launch) *in_launch = inl ? 1 : 0;
+  hipError_t e = hipSuccess;
+  if (!inl) {      // the two projections as launches of their own (project_context's, for this slice)
+    for (int seg = 0; seg < (Li > 0 ? 2 : 1) && e == hipSuccess; ++seg) {
+      const GemmArgs g = gemm_desc(zero_page(), k.ctx, ctx_dim, seg ? k.Wi : k.Wt, ctx_dim, nullptr, nullptr, 0, seg ? k.Ci : k.Ct, ldkv, B * (seg ? Li : Lt), N, ctx_dim, 0, seg ? Li : Lt, L, seg ? Lt : 0);
+      e = ia2p_launch_gemm_variant(g, false, ia2p_gemm_plan(g.M, g.N, g.K, false, false).variant, (hipStream_t)stream);
+    }
+  }
+  if (e == hipSuccess) e = ia2p_launch_qkv_sattn(a, x, (hipStream_t)stream, inl ? &k : nullptr);
+  RET_HIP(e, "qkv_self_attention_ctx");
+}
+ia2p_status ia2p_ip_attn_map(void* stream, const void* Q, int ldq, const void* Kip, int ldk, void* out, int B, int heads, int Nq, int ntok) {
+  if (!Q || !Kip || !out || B < 1 || heads < 1 || Nq < 1) return fail(nullptr, IA2P_ERR_INVALID, "ip_attn_map: bad argument");
+  if (ntok < 1 || ntok > 16 || ldq % 8 || ldq < heads * 64 || ldk < heads * 64) return fail(nullptr, IA2P_ERR_SHAPE, "ip_attn_map: ntok=%d (1..16), ldq=%d (mult of 8), ldk=%d", ntok, ldq, ldk);
+  hipError_t e = ia2p_launch_ip_attn_map((const half_t*)Q, ldq, (const half_t*)Kip, ldk, (half_t*)out, B, heads, Nq, ntok, (hipStream_t)stream);
+  RET_HIP(e, "ip_attn_map");
+}
+ia2p_status ia2p_linear_small(void* stream, const void* X, const void* W, const void* bias, void* out, int M, int N, int K, int silu_in, int silu_out) {
+  if (!X || !W || !out) return fail(nullptr, IA2P_ERR_INVALID, "linear_small: null argument");
+  if (M > 16 || K % 8) return fail(nullptr, IA2P_ERR_SHAPE, "linear_small: M=%d (<=16) K=%d (mult of 8)", M, K);
+  hipError_t e = ia2p_launch_linear_small((const half_t*)X, K, (const half_t*)W, (const half_t*)bias, nullptr, 0, (half_t*)out, N, M, N, K, silu_in, silu_out, (hipStream_t)stream);
+  RET_HIP(e, "linear_small");
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 // same order as the two stand-alone kernels (projection epilogue in fp32, ONE rounding to fp16, the attention core unchanged): bit-identical
 // to running `gemm_f16_kernel<128, 64, ...>` + `attention_f16_kernel` (tests/test_ops_gpu.py).
 #include "gemm_kernel.h"
+#include "launch_args.h"
 
 #include <cstring>
 
@@ -137,12 +138,8 @@ hipError_t ia2p_launch_qkv_sattn(const GemmArgs& a, const AttnArgs& x, hipStream
   if (ctx) {
     if (!ia2p_qkv_sattn_ctx_ok(x, *ctx) || !ctx->ctx || !ctx->Wt || !ctx->Ct || (ctx->Li > 0 && (!ctx->Wi || !ctx->Ci))) return hipErrorInvalidValue;
     const int tn = (ctx->N + CK_BN - 1) / CK_BN;
-    auto fill = [&](GemmArgs& g, const half_t* W, half_t* C, int rows, int roff) {      // what op_gemm + launch_cfg make of the stand-alone projection
-      g.pad = 1;
-      g.A = ctx->ctx; g.W = W; g.C = C; g.zero = a.zero; g.M = ctx->B * rows; g.N = ctx->N; g.K = ctx->K; g.ldw = ctx->K; g.lda = ctx->lda; g.ldc = ctx->ldc;
-      g.rpb = rows; g.bstride = ctx->L; g.roff = roff; g.rows_per_batch = 1;
-      g.m_fastest = g.M <= g.N ? 1 : 0;
-      g.acc_scale = g.bias_scale = 1.f;
+    auto fill = [&](GemmArgs& g, const half_t* W, half_t* C, int rows, int roff) {      // the stand-alone projection's descriptor (op_gemm's), prepared for this tile as launch_cfg would
+      g = gemm_desc(a.zero, ctx->ctx, ctx->lda, W, ctx->K, nullptr, nullptr, 0, C, ctx->ldc, ctx->B * rows, ctx->N, ctx->K, 0, rows, ctx->L, roff);
       ia2p_gemm_prepare(g, CK_SMEM, CK_BM, CK_BN);
     };
     fill(ck.g[0], ctx->Wt, ctx->Ct, ctx->Lt, 0);

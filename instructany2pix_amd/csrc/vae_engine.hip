@@ -1,4 +1,4 @@
-// VAE executor and its C ABI (ia2p_vae_*): see include/ia2p.h and DESIGN.md §8. Runtime and operator wrappers: engine_rt.h / engine.hip.
+// VAE executor and its C ABI (ia2p_vae_*): see include/ia2p.h and DESIGN.md §8. Runtime and operator wrappers: engine_rt.h / engine_rt.hip.
 #include "engine_rt.h"
 
 // =====================================================================================================================

@@ -1,7 +1,7 @@
 """Yardstick (NOT used by the product): ia2p_gemm against the vendor GEMM library (torch.nn.functional.linear -> hipBLASLt / rocBLAS) on the
 contraction shapes of the denoise step and on 4096^3, BOTH columns under ONE protocol, on the same random fp16 data:
 
-  cold : the autotuner's protocol (csrc/engine.hip::tune_site) -- before every timed launch the L2s are flushed (memset of a 48 MiB region) and the
+  cold : the autotuner's protocol (csrc/engine_rt.hip::tune_site / time_candidates) -- before every timed launch the L2s are flushed (memset of a 48 MiB region) and the
          activations are read back in (in the real step they were written by the launch just before); ONE launch between two events; fastest of
          REPS rounds, candidates interleaved round-robin (cdna guide §5.4 rule 24). Epilogue-free call (no bias, no residual).
   warm : 20 back-to-back launches between two events (what round 1's yardstick file did for the vendor column only).
