@@ -432,6 +432,37 @@ size_t ia2p_llm_q4_packed_bytes(int64_t N, int64_t K);
 ia2p_status ia2p_llm_quantize_q4(void* stream, const void* W, int64_t N, int64_t K, const float* codebook, void* packed, float* absmax);
 ia2p_status ia2p_llm_dequantize_q4(void* stream, const void* packed, const float* absmax, int64_t N, int64_t K, const float* codebook, void* W);
 ia2p_status ia2p_llm_gemv_q4(void* stream, const void* packed, const float* absmax, const float* codebook, const float* x, float* out, int N, int K);
+/* ---- Several sequences per weight pass ----------------------------------------------------------------------------------------------------------
+ * The cache as n_slots independent sequences, fp16 [slot][layer][k | v][max_positions][hidden] (one slot: the layout above), each slot with its own
+ * position. ia2p_llm_bind_kv is the one-slot form; ia2p_llm_prefill / _decode / _reset / _position act on slot 0 and run the single-sequence kernels.
+ * ia2p_llm_kv_slots_bytes: 0 for n_slots < 1 or max_positions outside 1..8192. Binding sets every position to 0. */
+#define IA2P_LLM_MAX_ROWS 8
+size_t ia2p_llm_kv_slots_bytes(ia2p_llm* llm, int max_positions, int n_slots);
+ia2p_status ia2p_llm_bind_kv_slots(ia2p_llm* llm, void* dev_cache, size_t bytes, int max_positions, int n_slots);
+int ia2p_llm_slots(ia2p_llm* llm);
+ia2p_status ia2p_llm_reset_slot(ia2p_llm* llm, int slot);            /* IA2P_ERR_INVALID for a slot outside the cache */
+int ia2p_llm_slot_position(ia2p_llm* llm, int slot);                 /* -1 for a slot outside the cache */
+/* ia2p_llm_prefill on the cache and position of `slot` (prompts differ in length: they are prefilled one at a time); other slots are not touched.
+ * IA2P_ERR_INVALID for a slot outside the cache. */
+ia2p_status ia2p_llm_prefill_slot(ia2p_llm* llm, void* stream, int slot, const void* inputs_embeds, int T, float* hidden_out, float* logits_out,
+                                  void* workspace, size_t workspace_bytes);
+/* One decode step for n = 1..IA2P_LLM_MAX_ROWS sequences. `slots` and `token_ids` are HOST arrays [n]: row r embeds token_ids[r] from the table and runs at
+ * the position of slot slots[r], which then advances by one. Per layer five weight launches and one attention launch serve all rows, then one launch for
+ * the final norm and lm_head: every weight is read (4 bits: decoded) once per step. hidden_out: fp32 [n, hidden], logits_out: fp32 [n, vocab_size]
+ * (device). Row r equals, bit for bit, what ia2p_llm_decode returns for that sequence alone.
+ * IA2P_ERR_INVALID: n outside 1..8, a slot outside the cache, a slot named twice. IA2P_ERR_STATE: a slot at position 0, weights or cache not bound.
+ * IA2P_ERR_SHAPE: a slot whose position is past the cache, a token outside the vocabulary. IA2P_ERR_NOMEM: the (256-byte aligned) workspace is smaller
+ * than ia2p_llm_batch_workspace_bytes(llm, 0, n). A refused call changes no position. */
+ia2p_status ia2p_llm_decode_batch(ia2p_llm* llm, void* stream, const int32_t* slots, const int32_t* token_ids, int n, float* hidden_out, float* logits_out,
+                                  void* workspace, size_t workspace_bytes);
+/* workspace that serves a prefill of any row count up to max_T (0: none; the largest need over 1..max_T, which is not monotone in T) and decode steps of up to
+ * max_rows rows; 0 for max_T < 0 or max_rows outside 1..8 */
+size_t ia2p_llm_batch_workspace_bytes(ia2p_llm* llm, int max_T, int max_rows);
+/* the multi-row GEMVs of ia2p_llm_decode_batch on their own: x fp32 [M, K], out fp32 [M, N], M = 1..8 (IA2P_ERR_SHAPE otherwise); K as for the
+ * single-row calls. out[m] equals the single-row call on x[m] bit for bit. */
+ia2p_status ia2p_llm_gemv_rows(void* stream, const void* W, const float* x, float* out, int N, int K, int M);
+ia2p_status ia2p_llm_gemv_q4_rows(void* stream, const void* packed, const float* absmax, const float* codebook, const float* x, float* out, int N, int K,
+                                  int M);
 /* exact (erf) GELU in place on fp16 [n]: the activation of an `mlpNx_gelu` projector head between two ia2p_linear_small calls
  * (llm/model/multimodal_projector/builder.py:33-74 `nn.GELU()`) */
 ia2p_status ia2p_gelu(void* stream, void* x, int64_t n);

@@ -151,6 +151,16 @@ SIGNATURES = {
     "ia2p_llm_quantize_q4": (_I, [_P, _P, _I64, _I64, C.POINTER(_F), _P, _P]),
     "ia2p_llm_dequantize_q4": (_I, [_P, _P, _P, _I64, _I64, C.POINTER(_F), _P]),
     "ia2p_llm_gemv_q4": (_I, [_P, _P, _P, C.POINTER(_F), _P, _P, _I, _I]),
+    "ia2p_llm_kv_slots_bytes": (_SZ, [_P, _I, _I]),
+    "ia2p_llm_bind_kv_slots": (_I, [_P, _P, _SZ, _I, _I]),
+    "ia2p_llm_slots": (_I, [_P]),
+    "ia2p_llm_reset_slot": (_I, [_P, _I]),
+    "ia2p_llm_slot_position": (_I, [_P, _I]),
+    "ia2p_llm_prefill_slot": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _SZ]),
+    "ia2p_llm_decode_batch": (_I, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _P, _P, _SZ]),
+    "ia2p_llm_batch_workspace_bytes": (_SZ, [_P, _I, _I]),
+    "ia2p_llm_gemv_rows": (_I, [_P, _P, _P, _P, _I, _I, _I]),
+    "ia2p_llm_gemv_q4_rows": (_I, [_P, _P, _P, C.POINTER(_F), _P, _P, _I, _I, _I]),
     "ia2p_gelu": (_I, [_P, _P, _I64]),
     "ia2p_vae_create": (_I, [C.POINTER(VAEConfigC), C.POINTER(_P)]),
     "ia2p_vae_destroy": (None, [_P]),

@@ -465,13 +465,434 @@ static hipError_t llm_launch_dequantize_q4(const void* packed, const float* absm
 static size_t attn_lds(int nk) { return ((size_t)((nk + 3) & ~3) + 16 * 128 + 8) * sizeof(float); }
 constexpr int LLM_MAX_POSITIONS = 8192;       // scores of one query row live in LDS (32 KiB of the 64)
 
+// =====================================================================================================================
+// Up to IA2P_LLM_MAX_ROWS sequences per weight pass (ia2p_llm_decode_batch). The kernels above serve one input row; the three below read (in 4 bits:
+// decode) every weight once and apply it to M input rows, each row at its own position and in its own cache slot. A row's arithmetic never involves
+// another row and keeps the single-row kernel's order of operations, so row m of a launch equals the single-row launch on that row bit for bit:
+//   llm_gemv_rows_kernel     thread t walks pieces t, t + 256, ... of K; per piece the same fmaf chain; the four waves' partials meet in LDS in wave order
+//   llm_gemv_q4_rows_kernel  lane l takes pieces l, l + 64, ... (32 weights, one absmax); the same s0 / s1 packed-FMA order, fmaf(sum, absmax, acc) per
+//                            block, wave_sum, rstd afterwards
+//   llm_attn_rows_kernel     llm_attn_kernel's algorithm on grid (heads, rows); row r reads the cache of its slot up to its own position
+// The tails the compiler contracts in the single-row kernels (out[n] + sum * rstd -> one fma) are written as fmaf here, so they do not depend on what
+// the compiler decides per kernel. Everything stays on VALU in fp32 (the residual stream of a decoded row is fp32).
+// The per-row pointers and positions travel by value in the kernel arguments: a decode step copies nothing to the device.
+// MT = rows a launch computes (1, 2, 4 or 8: M rounded up; the host repeats row M - 1 in the unused entries and the kernel stores rows m < M only).
+// =====================================================================================================================
+constexpr int LLM_MAX_ROWS = IA2P_LLM_MAX_ROWS;
+struct LlmRows {
+  const float* X[LLM_MAX_ROWS];   // input rows [K] fp32
+  float* out[LLM_MAX_ROWS];       // as LlmGemv::out, per row
+  float* hid[LLM_MAX_ROWS];       // as LlmGemv::hid
+  float* q[LLM_MAX_ROWS];         // EPI_QKV: q row, cache rows of the row's slot (this layer), position
+  half_t* kc[LLM_MAX_ROWS];
+  half_t* vc[LLM_MAX_ROWS];
+  int pos[LLM_MAX_ROWS];
+  int M;
+};
+__device__ __forceinline__ LlmGemv llm_row_view(const LlmGemv& a, const LlmRows& b, int m) {
+  LlmGemv v = a;
+  v.pos = b.pos[m]; v.q = b.q[m]; v.kc = b.kc[m]; v.vc = b.vc[m];
+  return v;
+}
+
+// `a` carries what the rows share (W, gamma, eps, N, K, inv_freq, H); R weight rows per workgroup as in llm_gemv_kernel (R does not enter a row's arithmetic)
+template <int R, int EPI, int MT>
+__global__ __launch_bounds__(256) void llm_gemv_rows_kernel(LlmGemv a, LlmRows b) {
+  __shared__ float red[4][MT][R + 1];
+  constexpr int HR = R / 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = a.K;
+  int rows[R];
+  if (EPI == EPI_QKV) {
+#pragma unroll
+    for (int i = 0; i < HR; ++i) {
+      const int pidx = min((int)blockIdx.x * HR + i, a.N / 2 - 1);
+      rows[i] = (pidx >> 6) * 128 + (pidx & 63);
+      rows[i + HR] = rows[i] + 64;
+    }
+  } else if (EPI == EPI_SWIGLU) {
+#pragma unroll
+    for (int i = 0; i < HR; ++i) {
+      rows[i] = min((int)blockIdx.x * HR + i, a.N / 2 - 1);
+      rows[i + HR] = a.N / 2 + rows[i];
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < R; ++r) rows[r] = min((int)blockIdx.x * R + r, a.N - 1);
+  }
+  float acc[MT][R], ss[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    ss[m] = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[m][r] = 0.f;
+  }
+  const int nvec = K >> 3;
+  constexpr int UNROLL = MT <= 2 ? 2 : 1;
+#pragma unroll UNROLL
+  for (int v = tid; v < nvec; v += 256) {
+    h8 w[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) w[r] = __builtin_nontemporal_load((const h8*)(a.W + (size_t)rows[r] * K) + v);
+    h8 g;
+    if (a.gamma) g = ((const h8*)a.gamma)[v];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {      // the piece is in registers: every input row uses it before the next one is loaded
+      const f4 x0 = ((const f4*)b.X[m])[2 * v], x1 = ((const f4*)b.X[m])[2 * v + 1];
+      float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+      if (a.gamma) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { ss[m] = fmaf(x[e], x[e], ss[m]); x[e] *= (float)g[e]; }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[m][r] = fmaf(x[e], (float)w[r][e], acc[m][r]);
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[m][r] = wave_sum(acc[m][r]);
+    ss[m] = wave_sum(ss[m]);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) red[wave][m][r] = acc[m][r];
+      red[wave][m][R] = ss[m];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    if (m >= b.M) break;
+    float rstd = 1.f;
+    if (a.gamma) rstd = 1.0f / sqrtf(((red[0][m][R] + red[1][m][R]) + (red[2][m][R] + red[3][m][R])) / (float)K + a.eps);
+    auto sum4 = [&](int r) { return (red[0][m][r] + red[1][m][r]) + (red[2][m][r] + red[3][m][r]); };
+    if (EPI == EPI_PLAIN || EPI == EPI_RESID) {
+      const int n = (int)blockIdx.x * R + tid;
+      if (tid < R && n < a.N) b.out[m][n] = EPI == EPI_RESID ? fmaf(rstd, sum4(tid), b.out[m][n]) : sum4(tid) * rstd;
+      if (EPI == EPI_PLAIN && b.hid[m] && a.gamma && blockIdx.x == 0)
+        for (int i = tid; i < K; i += 256) b.hid[m][i] = b.X[m][i] * rstd * (float)a.gamma[i];
+    } else if (EPI == EPI_SWIGLU) {
+      const int i = (int)blockIdx.x * HR + tid;
+      if (tid < HR && i < a.N / 2) {
+        const float g = sum4(tid) * rstd, u = sum4(tid + HR) * rstd;
+        b.out[m][i] = g / (1.0f + expf(-g)) * u;
+      }
+    } else {
+      const int pidx = (int)blockIdx.x * HR + tid;
+      if (tid < HR && pidx < a.N / 2) llm_store_qkv_pair(llm_row_view(a, b, m), pidx, sum4(tid) * rstd, sum4(tid + HR) * rstd);
+    }
+  }
+}
+
+// The 4-bit GEMV for M rows. Units, pieces and the per-piece arithmetic are llm_gemv_q4_kernel's: a wave owns U units of RW = 2 weight rows, lane l takes
+// pieces l, l + 64, ... of each. M input rows do not fit LDS whole (a row is 16 KiB at K = 4096, 43 KiB at K = 11008), so K is staged a chunk at a time: chunk
+// `it` = the 2048 inputs of every row that step `it` of the lanes consumes ([MT][8][64 lanes][4] floats, gamma applied), 64 KiB at MT = 8. Per chunk a wave
+// decodes the two pieces of a unit once into registers (the same byte table) and applies them to each of the MT rows in turn, so the table reads, the
+// shifts and the absmax fetch are paid once per code instead of once per code and row; the U RW MT sums stay in registers across the chunks, each
+// receiving its fmaf(sum, absmax, acc) in step order as in the single-row kernel. The next chunk's pieces load under the current chunk's arithmetic.
+// sum x^2 of a row: thread t adds float4s t, t + 256, ... of the row in that order, across the chunks -- the single-row kernel's order.
+constexpr int Q4R_U = 2;
+template <int EPI, int MT>
+__global__ __launch_bounds__(256, 2) void llm_gemv_q4_rows_kernel(LlmGemv a, LlmQ4 q, LlmRows b) {
+  constexpr int RW = Q4_RW, U = Q4R_U;
+  extern __shared__ float q4r_sm[];
+  f2* tab = (f2*)q4r_sm;                 // [256]
+  float* red = q4r_sm + 512;             // [4][MT]
+  float* xs = q4r_sm + 512 + 4 * MT;     // [MT][8][64][4]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = a.K, pieces = K >> 5, nit = (pieces + 63) >> 6;
+  const int unit0 = ((int)blockIdx.x * 4 + wave) * U;
+  auto row_of = [&](int unit, int r) {
+    if (EPI == EPI_QKV) { const int pidx = min(unit, a.N / 2 - 1); return (pidx >> 6) * 128 + (pidx & 63) + 64 * r; }
+    if (EPI == EPI_SWIGLU) return min(unit, a.N / 2 - 1) + r * (a.N / 2);
+    return min(unit * RW + r, a.N - 1);
+  };
+  auto fetch = [&](int it, u4v (*w)[RW], float (*am)[RW]) {
+    const int p = min(it * 64 + lane, pieces - 1);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int r = 0; r < RW; ++r) {
+        const size_t row = (size_t)row_of(unit0 + u, r);
+        w[u][r] = __builtin_nontemporal_load(q.Wq + row * pieces + p);
+        am[u][r] = q.absmax[row * (K >> 6) + (p >> 1)];
+      }
+  };
+  u4v w[U][RW], wn[U][RW];
+  float am[U][RW], amn[U][RW];
+  fetch(0, w, am);
+  tab[tid] = f2{q.cb.v[tid & 15], q.cb.v[tid >> 4]};
+  float ss[MT], acc[U][RW][MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    ss[m] = 0.f;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int r = 0; r < RW; ++r) acc[u][r][m] = 0.f;
+  }
+#pragma unroll 1
+  for (int it = 0; it < nit; ++it) {
+    if (it) __syncthreads();              // every wave is done with the previous chunk
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii) {
+      const int i = it * 512 + ii * 256 + tid;      // float4 index in the row
+      if (i < (K >> 2)) {
+        h4 g;
+        if (a.gamma) g = ((const h4*)a.gamma)[i];
+        const int p = i >> 3, j = i & 7;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+          f4 x = ((const f4*)b.X[m])[i];
+          if (a.gamma) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { ss[m] = fmaf(x[e], x[e], ss[m]); x[e] *= (float)g[e]; }
+          }
+          *(f4*)(xs + (m << 11) + (j << 8) + ((p & 63) << 2)) = x;
+        }
+      }
+    }
+    __syncthreads();
+    const bool more = it + 1 < nit;
+    if (more) fetch(it + 1, wn, amn);
+    if (it * 64 + lane < pieces) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        f2 t[RW][16];                     // the unit's two pieces, decoded once
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t[r][4 * k + c] = tab[(w[u][r][k] >> (8 * c)) & 255];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+          f4 x[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) x[j] = *(const f4*)(xs + (m << 11) + (j << 8) + (lane << 2));
+#pragma unroll
+          for (int r = 0; r < RW; ++r) {
+            f2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)         // word k of the piece: bytes 0..3 against inputs 8 k .. 8 k + 7 (the single-row kernel's order)
+#pragma unroll
+              for (int c = 0; c < 4; c += 2) {
+                const f4 xv = x[2 * k + (c >> 1)];
+                s0 = __builtin_elementwise_fma(t[r][4 * k + c], f2{xv[0], xv[1]}, s0);
+                s1 = __builtin_elementwise_fma(t[r][4 * k + c + 1], f2{xv[2], xv[3]}, s1);
+              }
+            const f2 s = s0 + s1;
+            acc[u][r][m] = fmaf(s[0] + s[1], am[u][r], acc[u][r][m]);
+          }
+          __builtin_amdgcn_sched_barrier(0);      // one row's 32 inputs live at a time: hoisting the next rows' LDS reads costs more registers than two workgroups per CU leave
+        }
+      }
+    }
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int r = 0; r < RW; ++r) { w[u][r] = wn[u][r]; am[u][r] = amn[u][r]; }
+    }
+  }
+  float rstd[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    ss[m] = wave_sum(ss[m]);
+    if (lane == 0) red[wave * MT + m] = ss[m];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    rstd[m] = 1.f;
+    if (a.gamma) rstd[m] = 1.0f / sqrtf(((red[m] + red[MT + m]) + (red[2 * MT + m] + red[3 * MT + m])) / (float)K + a.eps);
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int unit = unit0 + u;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      float v[RW];
+#pragma unroll
+      for (int r = 0; r < RW; ++r) v[r] = wave_sum(acc[u][r][m]);
+      if (m >= b.M) continue;
+      if (EPI == EPI_PLAIN || EPI == EPI_RESID) {
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+          const int n = unit * RW + r;
+          if (lane == r && n < a.N) b.out[m][n] = EPI == EPI_RESID ? fmaf(v[r], rstd[m], b.out[m][n]) : v[r] * rstd[m];
+        }
+      } else if (lane == 0 && unit < a.N / 2) {
+        const float y0 = v[0] * rstd[m], y1 = v[RW - 1] * rstd[m];
+        if (EPI == EPI_SWIGLU) b.out[m][unit] = y0 / (1.0f + expf(-y0)) * y1;
+        else llm_store_qkv_pair(llm_row_view(a, b, m), unit, y0, y1);
+      }
+    }
+  }
+  if (EPI == EPI_PLAIN && a.gamma && blockIdx.x == 0) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+      if (m < b.M && b.hid[m])
+        for (int i = tid; i < K; i += 256) b.hid[m][i] = b.X[m][i] * rstd[m] * (float)a.gamma[i];
+  }
+}
+
+// llm_attn_kernel for one decoded row per sequence: row r = blockIdx.y against the keys 0 .. pos[r] of its own cache slot
+struct LlmAttnRows {
+  const half_t* kc[LLM_MAX_ROWS];
+  const half_t* vc[LLM_MAX_ROWS];
+  int pos[LLM_MAX_ROWS];
+};
+__global__ __launch_bounds__(256) void llm_attn_rows_kernel(const float* q, LlmAttnRows rows, float* out, int H, float scale) {
+  extern __shared__ float llm_sm[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = tid >> 4, l = tid & 15;
+  const int head = blockIdx.x, t = blockIdx.y, nk = rows.pos[t] + 1;
+  const half_t* kc = rows.kc[t];
+  const half_t* vc = rows.vc[t];
+  float* sc = llm_sm;                 // [nk]
+  float* part = llm_sm + ((nk + 3) & ~3);   // [16][128]
+  float* red = part + 16 * 128;       // [8]
+  float qv[8];
+  {
+    const float* qp = q + (size_t)t * H + head * 128 + l * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qv[e] = qp[e] * scale;
+  }
+  for (int j0 = 0; j0 < nk; j0 += 16) {
+    const int j = j0 + g;
+    float s = 0.f;
+    if (j < nk) {
+      const h8 k = *(const h8*)(kc + (size_t)j * H + head * 128 + l * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s = fmaf(qv[e], (float)k[e], s);
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
+    if (l == 0 && j < nk) sc[j] = s;
+  }
+  __syncthreads();
+  float m = -INFINITY;
+  for (int j = tid; j < nk; j += 256) m = fmaxf(m, sc[j]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sum = 0.f;
+  for (int j = tid; j < nk; j += 256) { const float e = expf(sc[j] - m); sc[j] = e; sum += e; }
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = (red[4] + red[5]) + (red[6] + red[7]);
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = 0.f;
+  for (int j = g; j < nk; j += 16) {
+    const float p = sc[j];
+    const h8 v = *(const h8*)(vc + (size_t)j * H + head * 128 + l * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = fmaf(p, (float)v[e], o[e]);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) part[g * 128 + l * 8 + e] = o[e];
+  __syncthreads();
+  if (tid < 128) {
+    float r = 0.f;
+#pragma unroll
+    for (int gg = 0; gg < 16; ++gg) r += part[gg * 128 + tid];
+    out[(size_t)t * H + head * 128 + tid] = r / sum;
+  }
+}
+// token rows of the embedding table as fp32: row r = blockIdx.y, the ids by value
+struct LlmTokRows { int id[LLM_MAX_ROWS]; };
+__global__ __launch_bounds__(256) void llm_rows_f32_kernel(const half_t* tok, LlmTokRows ids, float* dst, int H) {
+  const half_t* src = tok + (size_t)ids.id[blockIdx.y] * H;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < H; i += gridDim.x * 256) dst[(size_t)blockIdx.y * H + i] = (float)src[i];
+}
+
+static int rows_mt(int M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8; }
+static void rows_pad(LlmRows& b) {      // entries M .. 7 repeat row M - 1: loaded and computed where MT > M, never stored
+  for (int m = b.M; m < LLM_MAX_ROWS; ++m) {
+    b.X[m] = b.X[b.M - 1]; b.out[m] = b.out[b.M - 1]; b.hid[m] = b.hid[b.M - 1]; b.q[m] = b.q[b.M - 1];
+    b.kc[m] = b.kc[b.M - 1]; b.vc[m] = b.vc[b.M - 1]; b.pos[m] = b.pos[b.M - 1];
+  }
+}
+template <int R, int MT>
+static hipError_t gemv_rows_launch_r(const LlmGemv& a, const LlmRows& b, int epi, hipStream_t s) {
+  const int units = epi == EPI_QKV || epi == EPI_SWIGLU ? (a.N / 2 + R / 2 - 1) / (R / 2) : (a.N + R - 1) / R;
+  switch (epi) {
+    case EPI_PLAIN: hipLaunchKernelGGL((llm_gemv_rows_kernel<R, EPI_PLAIN, MT>), dim3(units), dim3(256), 0, s, a, b); break;
+    case EPI_RESID: hipLaunchKernelGGL((llm_gemv_rows_kernel<R, EPI_RESID, MT>), dim3(units), dim3(256), 0, s, a, b); break;
+    case EPI_QKV: hipLaunchKernelGGL((llm_gemv_rows_kernel<R, EPI_QKV, MT>), dim3(units), dim3(256), 0, s, a, b); break;
+    case EPI_SWIGLU: hipLaunchKernelGGL((llm_gemv_rows_kernel<R, EPI_SWIGLU, MT>), dim3(units), dim3(256), 0, s, a, b); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+// weight rows per workgroup: llm_launch_gemv's rule for one or two input rows; from four input rows on always 8, because every workgroup reads all the
+// input rows (4 M K bytes from L2 against 2 R K bytes of weights) and more weight rows per workgroup halve that share
+static hipError_t llm_launch_gemv_rows(const LlmGemv& a, LlmRows b, int epi, hipStream_t s) {
+  if (!a.W || b.M < 1 || b.M > LLM_MAX_ROWS || a.N < 1 || a.K < 8 || a.K % 8) return hipErrorInvalidValue;
+  if ((epi == EPI_QKV && (a.N != 3 * a.H || a.H % 128)) || (epi == EPI_SWIGLU && a.N % 2)) return hipErrorInvalidValue;
+  rows_pad(b);
+  const bool r8 = a.N >= 8192;
+  switch (rows_mt(b.M)) {
+    case 1: return r8 ? gemv_rows_launch_r<8, 1>(a, b, epi, s) : gemv_rows_launch_r<4, 1>(a, b, epi, s);
+    case 2: return r8 ? gemv_rows_launch_r<8, 2>(a, b, epi, s) : gemv_rows_launch_r<4, 2>(a, b, epi, s);
+    case 4: return gemv_rows_launch_r<8, 4>(a, b, epi, s);
+    default: return gemv_rows_launch_r<8, 8>(a, b, epi, s);
+  }
+}
+static size_t q4_rows_lds(int mt) { return (size_t)(512 + 4 * mt + mt * 2048) * sizeof(float); }
+template <int MT>
+static hipError_t gemv_q4_rows_launch(const LlmGemv& a, const LlmQ4& q, const LlmRows& b, int epi, hipStream_t s) {
+  const int units = epi == EPI_QKV || epi == EPI_SWIGLU ? a.N / 2 : (a.N + Q4_RW - 1) / Q4_RW;
+  const dim3 grid((units + 4 * Q4R_U - 1) / (4 * Q4R_U)), block(256);
+  const size_t lds = q4_rows_lds(MT);
+  if (lds > 64 * 1024) {          // MT = 8: 66 KiB of the CU's 160
+    static bool done = false;
+    if (!done) {
+      hipError_t e = hipFuncSetAttribute((const void*)llm_gemv_q4_rows_kernel<EPI_PLAIN, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)llm_gemv_q4_rows_kernel<EPI_RESID, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)llm_gemv_q4_rows_kernel<EPI_QKV, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)llm_gemv_q4_rows_kernel<EPI_SWIGLU, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      done = true;
+    }
+  }
+  switch (epi) {
+    case EPI_PLAIN: hipLaunchKernelGGL((llm_gemv_q4_rows_kernel<EPI_PLAIN, MT>), grid, block, lds, s, a, q, b); break;
+    case EPI_RESID: hipLaunchKernelGGL((llm_gemv_q4_rows_kernel<EPI_RESID, MT>), grid, block, lds, s, a, q, b); break;
+    case EPI_QKV: hipLaunchKernelGGL((llm_gemv_q4_rows_kernel<EPI_QKV, MT>), grid, block, lds, s, a, q, b); break;
+    case EPI_SWIGLU: hipLaunchKernelGGL((llm_gemv_q4_rows_kernel<EPI_SWIGLU, MT>), grid, block, lds, s, a, q, b); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+static hipError_t llm_launch_gemv_q4_rows(const LlmGemv& a, const LlmQ4& q, LlmRows b, int epi, hipStream_t s) {
+  if (!q.Wq || !q.absmax || b.M < 1 || b.M > LLM_MAX_ROWS || a.N < 1 || a.K < 64 || a.K % 64 || a.K > Q4_MAX_K) return hipErrorInvalidValue;
+  if ((epi == EPI_QKV && (a.N != 3 * a.H || a.H % 128)) || (epi == EPI_SWIGLU && a.N % 2)) return hipErrorInvalidValue;
+  rows_pad(b);
+  switch (rows_mt(b.M)) {
+    case 1: return gemv_q4_rows_launch<1>(a, q, b, epi, s);
+    case 2: return gemv_q4_rows_launch<2>(a, q, b, epi, s);
+    case 4: return gemv_q4_rows_launch<4>(a, q, b, epi, s);
+    default: return gemv_q4_rows_launch<8>(a, q, b, epi, s);
+  }
+}
+
 struct LLayer { size_t ln1, ln2, wqkv, wo, wgu, wd; size_t aqkv, ao, agu, ad; };      // a*: the absmax arrays of the 4-bit format (w*: the packed codes then)
 struct ia2p_llm : RunCtx {
   ia2p_llm_config cfg;
   size_t tok, normf, head, invf;
   std::vector<LLayer> layers;
-  half_t* kv = nullptr;
-  int max_pos = 0, pos = 0;
+  half_t* kv = nullptr;                                // [slot][layer][k|v][max_pos][hidden]
+  int max_pos = 0, n_slots = 0, cur = 0;               // cur: the slot the single-sequence paths (prefill, decode) act on
+  std::vector<int> spos{0};                            // position of every slot
   int wbits = 16;                                      // 16: fp16 projections; 4: codes of `codebook`, block 64, fp32 absmax (ia2p_llm_set_weight_format)
   float codebook[16] = {};
   std::unordered_map<std::string, size_t> q4_absmax;   // projection key -> offset of its absmax rows (arena elements)
@@ -525,8 +946,11 @@ static ia2p_status llm_plan(ia2p_llm* c) {
   return IA2P_OK;
 }
 
-static half_t* KC(ia2p_llm* c, int layer) { return c->kv + (size_t)layer * 2 * c->max_pos * c->cfg.hidden_size; }
-static half_t* VC(ia2p_llm* c, int layer) { return KC(c, layer) + (size_t)c->max_pos * c->cfg.hidden_size; }
+static half_t* KCS(ia2p_llm* c, int slot, int layer) { return c->kv + ((size_t)slot * c->cfg.num_layers + layer) * 2 * c->max_pos * c->cfg.hidden_size; }
+static half_t* VCS(ia2p_llm* c, int slot, int layer) { return KCS(c, slot, layer) + (size_t)c->max_pos * c->cfg.hidden_size; }
+static half_t* KC(ia2p_llm* c, int layer) { return KCS(c, c->cur, layer); }
+static half_t* VC(ia2p_llm* c, int layer) { return VCS(c, c->cur, layer); }
+static int& POS(ia2p_llm* c) { return c->spos[c->cur]; }
 
 // final norm + lm_head of the fp32 row xf: hidden_out [H] fp32, logits_out [vocab] fp32
 static void llm_head(ia2p_llm* c, const float* xf, float* hidden_out, float* logits_out) {
@@ -553,7 +977,7 @@ static const half_t* llm_proj_f16(ia2p_llm* c, size_t w, size_t am, size_t elems
 
 static ia2p_status llm_run_decode(ia2p_llm* c, int token, float* hidden_out, float* logits_out) {
   const ia2p_llm_config& g = c->cfg;
-  const int H = g.hidden_size, I = g.intermediate_size, pos = c->pos;
+  const int H = g.hidden_size, I = g.intermediate_size, pos = POS(c);
   T2 xt = wsalloc(c, (size_t)2 * H), qt = wsalloc(c, (size_t)2 * H), at = wsalloc(c, (size_t)2 * H), ft = wsalloc(c, (size_t)2 * I);
   float *xf = (float*)xt.p, *qf = (float*)qt.p, *af = (float*)at.p, *ff = (float*)ft.p;
   if (!c->dry && !c->failed) {
@@ -586,9 +1010,69 @@ static ia2p_status llm_run_decode(ia2p_llm* c, int token, float* hidden_out, flo
   return c->failed ? IA2P_ERR_HIP : IA2P_OK;
 }
 
+// one decode projection for the rows of `b`
+static hipError_t llm_proj_gemv_rows(ia2p_llm* c, LlmGemv& a, const LlmRows& b, size_t w, size_t am, int epi) {
+  if (c->wbits != 4) { a.W = W_(c, w); return llm_launch_gemv_rows(a, b, epi, c->stream); }
+  LlmQ4 q;
+  q.Wq = (const u4v*)W_(c, w); q.absmax = (const float*)W_(c, am);
+  memcpy(q.cb.v, c->codebook, sizeof q.cb.v);
+  return llm_launch_gemv_q4_rows(a, q, b, epi, c->stream);
+}
+
+// n rows, row r = token tokens[r] at the position of slot slots[r]: the launches of llm_run_decode, each once for all rows
+static ia2p_status llm_run_decode_rows(ia2p_llm* c, const int32_t* slots, const int32_t* tokens, int n, float* hidden_out, float* logits_out) {
+  const ia2p_llm_config& g = c->cfg;
+  const int H = g.hidden_size, I = g.intermediate_size;
+  T2 xt = wsalloc(c, (size_t)2 * n * H), qt = wsalloc(c, (size_t)2 * n * H), at = wsalloc(c, (size_t)2 * n * H), ft = wsalloc(c, (size_t)2 * n * I);
+  float *xf = (float*)xt.p, *qf = (float*)qt.p, *af = (float*)at.p, *ff = (float*)ft.p;
+  if (!c->dry && !c->failed) {
+    LlmTokRows ids{};
+    int longest = 0;
+    for (int r = 0; r < n; ++r) { ids.id[r] = tokens[r]; longest = std::max(longest, c->spos[slots[r]] + 1); }
+    hipLaunchKernelGGL(llm_rows_f32_kernel, dim3((H + 255) / 256, n), dim3(256), 0, c->stream, W_(c, c->tok), ids, xf, H);
+    CHECK_LAUNCH(c, hipGetLastError(), "llm embedding rows");
+    auto rows = [&](const float* x, size_t xs, float* out, size_t os) {
+      LlmRows b{};
+      b.M = n;
+      for (int r = 0; r < n; ++r) { b.X[r] = x + r * xs; b.out[r] = out ? out + r * os : nullptr; }
+      return b;
+    };
+    for (int i = 0; i < g.num_layers && !c->failed; ++i) {
+      const LLayer& l = c->layers[i];
+      LlmGemv a{};
+      a.gamma = W_(c, l.ln1); a.eps = g.rms_norm_eps; a.N = 3 * H; a.K = H; a.H = H; a.inv_freq = (const float*)W_(c, c->invf);
+      LlmRows b = rows(xf, H, nullptr, 0);
+      LlmAttnRows ar{};
+      for (int r = 0; r < n; ++r) {
+        b.q[r] = qf + (size_t)r * H; b.kc[r] = KCS(c, slots[r], i); b.vc[r] = VCS(c, slots[r], i); b.pos[r] = c->spos[slots[r]];
+        ar.kc[r] = b.kc[r]; ar.vc[r] = b.vc[r]; ar.pos[r] = b.pos[r];
+      }
+      CHECK_LAUNCH(c, llm_proj_gemv_rows(c, a, b, l.wqkv, l.aqkv, EPI_QKV), "llm qkv rows");
+      hipLaunchKernelGGL(llm_attn_rows_kernel, dim3(g.num_heads, n), dim3(256), attn_lds(longest), c->stream, (const float*)qf, ar, af, H, 0.08838834764831845f);
+      CHECK_LAUNCH(c, hipGetLastError(), "llm attention rows");
+      LlmGemv o{};
+      o.N = H; o.K = H;
+      CHECK_LAUNCH(c, llm_proj_gemv_rows(c, o, rows(af, H, xf, H), l.wo, l.ao, EPI_RESID), "llm o_proj rows");
+      LlmGemv u{};
+      u.gamma = W_(c, l.ln2); u.eps = g.rms_norm_eps; u.N = 2 * I; u.K = H;
+      CHECK_LAUNCH(c, llm_proj_gemv_rows(c, u, rows(xf, H, ff, I), l.wgu, l.agu, EPI_SWIGLU), "llm gate/up rows");
+      LlmGemv d{};
+      d.N = H; d.K = I;
+      CHECK_LAUNCH(c, llm_proj_gemv_rows(c, d, rows(ff, I, xf, H), l.wd, l.ad, EPI_RESID), "llm down_proj rows");
+    }
+    LlmGemv h{};          // final norm + lm_head of every row
+    h.W = W_(c, c->head); h.gamma = W_(c, c->normf); h.eps = g.rms_norm_eps; h.N = g.vocab_size; h.K = H;
+    LlmRows hb = rows(xf, H, logits_out, g.vocab_size);
+    for (int r = 0; r < n; ++r) hb.hid[r] = hidden_out + (size_t)r * H;
+    CHECK_LAUNCH(c, llm_launch_gemv_rows(h, hb, EPI_PLAIN, c->stream), "llm lm_head rows");
+  }
+  wsfree(c, ft); wsfree(c, at); wsfree(c, qt); wsfree(c, xt);
+  return c->failed ? IA2P_ERR_HIP : IA2P_OK;
+}
+
 static ia2p_status llm_run_prefill(ia2p_llm* c, const half_t* embeds, int T, float* hidden_out, float* logits_out) {
   const ia2p_llm_config& g = c->cfg;
-  const int H = g.hidden_size, I = g.intermediate_size, p0 = c->pos;
+  const int H = g.hidden_size, I = g.intermediate_size, p0 = POS(c);
   T2 x = wsalloc(c, (size_t)T * H), xn = wsalloc(c, (size_t)T * H), qkv = wsalloc(c, (size_t)T * 3 * H), qt = wsalloc(c, (size_t)T * H * 2);
   T2 att = wsalloc(c, (size_t)T * H), gu = wsalloc(c, (size_t)T * 2 * I), act = wsalloc(c, (size_t)T * I), xt = wsalloc(c, (size_t)2 * H);
   T2 wq{(size_t)-1, nullptr};           // 4 bits: one projection at a time as fp16 (the largest: gate | up)
@@ -642,15 +1126,23 @@ static size_t llm_dry(ia2p_llm* c, int T) {
   c->dry = false;
   return c->failed ? 0 : c->ws.high + 256;
 }
+static size_t llm_dry_rows(ia2p_llm* c, int n) {
+  c->dry = true; c->failed = false; c->record = false;
+  c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
+  (void)llm_run_decode_rows(c, nullptr, nullptr, n, nullptr, nullptr);
+  c->dry = false;
+  return c->failed ? 0 : c->ws.high + 256;
+}
 static ia2p_status llm_ready(ia2p_llm* c, const char* what) {
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "%s before weights were finalized", what);
   if (!c->kv) return fail(c, IA2P_ERR_STATE, "%s before ia2p_llm_bind_kv", what);
   return IA2P_OK;
 }
-static ia2p_status llm_enter(ia2p_llm* c, void* stream, void* ws, size_t ws_bytes, size_t need) {
+// exact: the batched decode takes `need` as the least size of an aligned workspace (the earlier entry points allow the alignment slack to be missing)
+static ia2p_status llm_enter(ia2p_llm* c, void* stream, void* ws, size_t ws_bytes, size_t need, bool exact = false) {
   const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
   const size_t lost = base - (uintptr_t)ws;
-  if (need == 0 || ws_bytes < lost || ws_bytes - lost + 256 < need) return fail(c, IA2P_ERR_NOMEM, "llm: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  if (need == 0 || ws_bytes < lost || ws_bytes - lost + (exact ? 0 : 256) < need) return fail(c, IA2P_ERR_NOMEM, "llm: workspace of %zu bytes, %zu needed", ws_bytes, need);
   c->wseq.clear(); c->widx = 0; c->dry = false; c->failed = false; c->stream = (hipStream_t)stream;
   c->ws.reset(ws_bytes - lost); c->ws_base = (char*)base;
   return IA2P_OK;
@@ -745,29 +1237,52 @@ ia2p_status ia2p_llm_finalize_weights(ia2p_llm* c) {
   if (e != hipSuccess) { c->finalized = false; return fail_hip(c, e, "llm rotary table"); }
   return IA2P_OK;
 }
-size_t ia2p_llm_kv_bytes(ia2p_llm* c, int max_positions) {
-  if (!c || max_positions < 1 || max_positions > LLM_MAX_POSITIONS) return 0;
-  return (size_t)c->cfg.num_layers * 2 * (size_t)max_positions * c->cfg.hidden_size * sizeof(half_t);
+size_t ia2p_llm_kv_slots_bytes(ia2p_llm* c, int max_positions, int n_slots) {
+  if (!c || n_slots < 1 || max_positions < 1 || max_positions > LLM_MAX_POSITIONS) return 0;
+  return (size_t)n_slots * c->cfg.num_layers * 2 * (size_t)max_positions * c->cfg.hidden_size * sizeof(half_t);
 }
-ia2p_status ia2p_llm_bind_kv(ia2p_llm* c, void* dev, size_t bytes, int max_positions) {
-  if (!c || !dev) return fail(c, IA2P_ERR_INVALID, "llm_bind_kv: null argument");
-  if (max_positions < 1 || max_positions > LLM_MAX_POSITIONS) return fail(c, IA2P_ERR_SHAPE, "llm_bind_kv: %d positions (1..%d)", max_positions, LLM_MAX_POSITIONS);
-  if (((uintptr_t)dev) & 15) return fail(c, IA2P_ERR_INVALID, "llm_bind_kv: the cache must be 16-byte aligned");
-  if (bytes < ia2p_llm_kv_bytes(c, max_positions)) return fail(c, IA2P_ERR_NOMEM, "llm_bind_kv: %zu bytes, %zu needed", bytes, ia2p_llm_kv_bytes(c, max_positions));
-  c->kv = (half_t*)dev; c->max_pos = max_positions; c->pos = 0;
+size_t ia2p_llm_kv_bytes(ia2p_llm* c, int max_positions) { return ia2p_llm_kv_slots_bytes(c, max_positions, 1); }
+static ia2p_status llm_bind_slots(ia2p_llm* c, const char* what, void* dev, size_t bytes, int max_positions, int n_slots) {
+  if (!c || !dev) return fail(c, IA2P_ERR_INVALID, "%s: null argument", what);
+  if (n_slots < 1) return fail(c, IA2P_ERR_INVALID, "%s: %d slots", what, n_slots);
+  if (max_positions < 1 || max_positions > LLM_MAX_POSITIONS) return fail(c, IA2P_ERR_SHAPE, "%s: %d positions (1..%d)", what, max_positions, LLM_MAX_POSITIONS);
+  if (((uintptr_t)dev) & 15) return fail(c, IA2P_ERR_INVALID, "%s: the cache must be 16-byte aligned", what);
+  const size_t need = ia2p_llm_kv_slots_bytes(c, max_positions, n_slots);
+  if (bytes < need) return fail(c, IA2P_ERR_NOMEM, "%s: %zu bytes, %zu needed", what, bytes, need);
+  c->kv = (half_t*)dev; c->max_pos = max_positions; c->n_slots = n_slots; c->cur = 0;
+  c->spos.assign((size_t)n_slots, 0);
   return IA2P_OK;
 }
+ia2p_status ia2p_llm_bind_kv(ia2p_llm* c, void* dev, size_t bytes, int max_positions) { return llm_bind_slots(c, "llm_bind_kv", dev, bytes, max_positions, 1); }
+ia2p_status ia2p_llm_bind_kv_slots(ia2p_llm* c, void* dev, size_t bytes, int max_positions, int n_slots) {
+  return llm_bind_slots(c, "llm_bind_kv_slots", dev, bytes, max_positions, n_slots);
+}
+int ia2p_llm_slots(ia2p_llm* c) { return c ? c->n_slots : 0; }
 size_t ia2p_llm_workspace_bytes(ia2p_llm* c, int max_T) {
   if (!c || max_T < 1) return 0;
   const size_t a = llm_dry(c, max_T), b = llm_dry(c, 0);
   return a && b ? std::max(a, b) : 0;
 }
+size_t ia2p_llm_batch_workspace_bytes(ia2p_llm* c, int max_T, int max_rows) {
+  if (!c || max_T < 0 || max_rows < 1 || max_rows > LLM_MAX_ROWS) return 0;
+  size_t a = 1;       // every T up to max_T: a prefill's need is not monotone in T (the K-split of its GEMMs changes with the row count)
+  for (int T = 1; T <= max_T && a; ++T) { const size_t t = llm_dry(c, T); a = t ? std::max(a, t) : 0; }
+  const size_t b = llm_dry_rows(c, max_rows);
+  return a && b ? std::max(a, b) : 0;
+}
 ia2p_status ia2p_llm_reset(ia2p_llm* c) {
   if (!c) return fail(nullptr, IA2P_ERR_INVALID, "llm_reset: null argument");
-  c->pos = 0;
+  c->spos[0] = 0;
   return IA2P_OK;
 }
-int ia2p_llm_position(ia2p_llm* c) { return c ? c->pos : -1; }
+int ia2p_llm_position(ia2p_llm* c) { return c ? c->spos[0] : -1; }
+ia2p_status ia2p_llm_reset_slot(ia2p_llm* c, int slot) {
+  if (!c) return fail(nullptr, IA2P_ERR_INVALID, "llm_reset_slot: null argument");
+  if (slot < 0 || slot >= c->n_slots) return fail(c, IA2P_ERR_INVALID, "llm_reset_slot: slot %d of %d", slot, c->n_slots);
+  c->spos[slot] = 0;
+  return IA2P_OK;
+}
+int ia2p_llm_slot_position(ia2p_llm* c, int slot) { return c && slot >= 0 && slot < c->n_slots ? c->spos[slot] : -1; }
 ia2p_status ia2p_llm_embed(ia2p_llm* c, void* stream, const int32_t* ids, int T, void* out) {
   if (!c || !ids || !out) return fail(c, IA2P_ERR_INVALID, "llm_embed: null argument");
   if (T < 1) return fail(c, IA2P_ERR_SHAPE, "llm_embed: T=%d", T);
@@ -776,30 +1291,96 @@ ia2p_status ia2p_llm_embed(ia2p_llm* c, void* stream, const int32_t* ids, int T,
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? IA2P_OK : fail_hip(c, e, "llm_embed");
 }
-ia2p_status ia2p_llm_prefill(ia2p_llm* c, void* stream, const void* inputs_embeds, int T, float* hidden_out, float* logits_out, void* ws, size_t ws_bytes) {
-  if (!c || !inputs_embeds || !hidden_out || !logits_out || !ws) return fail(c, IA2P_ERR_INVALID, "llm_prefill: null argument");
-  ia2p_status st = llm_ready(c, "llm_prefill");
+static ia2p_status llm_prefill_at(ia2p_llm* c, const char* what, int slot, void* stream, const void* inputs_embeds, int T, float* hidden_out, float* logits_out, void* ws,
+                                  size_t ws_bytes) {
+  if (!c || !inputs_embeds || !hidden_out || !logits_out || !ws) return fail(c, IA2P_ERR_INVALID, "%s: null argument", what);
+  ia2p_status st = llm_ready(c, what);
   if (st != IA2P_OK) return st;
-  if (T < 1 || c->pos + T > c->max_pos) return fail(c, IA2P_ERR_SHAPE, "llm_prefill: %d rows at position %d, the cache holds %d", T, c->pos, c->max_pos);
+  if (slot < 0 || slot >= c->n_slots) return fail(c, IA2P_ERR_INVALID, "%s: slot %d of %d", what, slot, c->n_slots);
+  const int pos = c->spos[slot];
+  if (T < 1 || pos + T > c->max_pos) return fail(c, IA2P_ERR_SHAPE, "%s: %d rows at position %d, the cache holds %d", what, T, pos, c->max_pos);
   if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
+  c->cur = slot;
   st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, T));
-  if (st != IA2P_OK) return st;
-  st = llm_leave(c, llm_run_prefill(c, (const half_t*)inputs_embeds, T, hidden_out, logits_out));
-  if (st == IA2P_OK) c->pos += T;
+  if (st == IA2P_OK) st = llm_leave(c, llm_run_prefill(c, (const half_t*)inputs_embeds, T, hidden_out, logits_out));
+  c->cur = 0;
+  if (st == IA2P_OK) c->spos[slot] += T;
   return st;
+}
+ia2p_status ia2p_llm_prefill(ia2p_llm* c, void* stream, const void* inputs_embeds, int T, float* hidden_out, float* logits_out, void* ws, size_t ws_bytes) {
+  return llm_prefill_at(c, "llm_prefill", 0, stream, inputs_embeds, T, hidden_out, logits_out, ws, ws_bytes);
+}
+ia2p_status ia2p_llm_prefill_slot(ia2p_llm* c, void* stream, int slot, const void* inputs_embeds, int T, float* hidden_out, float* logits_out, void* ws, size_t ws_bytes) {
+  return llm_prefill_at(c, "llm_prefill_slot", slot, stream, inputs_embeds, T, hidden_out, logits_out, ws, ws_bytes);
 }
 ia2p_status ia2p_llm_decode(ia2p_llm* c, void* stream, int token_id, float* hidden_out, float* logits_out, void* ws, size_t ws_bytes) {
   if (!c || !hidden_out || !logits_out || !ws) return fail(c, IA2P_ERR_INVALID, "llm_decode: null argument");
   ia2p_status st = llm_ready(c, "llm_decode");
   if (st != IA2P_OK) return st;
-  if (c->pos < 1) return fail(c, IA2P_ERR_STATE, "llm_decode before a prefill (position 0)");
-  if (c->pos >= c->max_pos) return fail(c, IA2P_ERR_SHAPE, "llm_decode: position %d is past the cache (%d positions)", c->pos, c->max_pos);
+  const int pos = c->spos[0];
+  if (pos < 1) return fail(c, IA2P_ERR_STATE, "llm_decode before a prefill (position 0)");
+  if (pos >= c->max_pos) return fail(c, IA2P_ERR_SHAPE, "llm_decode: position %d is past the cache (%d positions)", pos, c->max_pos);
   if (token_id < 0 || token_id >= c->cfg.vocab_size) return fail(c, IA2P_ERR_SHAPE, "llm_decode: token %d outside the vocabulary (%d)", token_id, c->cfg.vocab_size);
+  c->cur = 0;
   st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, 0));
   if (st != IA2P_OK) return st;
   st = llm_leave(c, llm_run_decode(c, token_id, hidden_out, logits_out));
-  if (st == IA2P_OK) c->pos += 1;
+  if (st == IA2P_OK) c->spos[0] += 1;
   return st;
+}
+ia2p_status ia2p_llm_decode_batch(ia2p_llm* c, void* stream, const int32_t* slots, const int32_t* token_ids, int n, float* hidden_out, float* logits_out, void* ws,
+                                  size_t ws_bytes) {
+  if (!c || !slots || !token_ids || !hidden_out || !logits_out || !ws) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch: null argument");
+  ia2p_status st = llm_ready(c, "llm_decode_batch");
+  if (st != IA2P_OK) return st;
+  if (n < 1 || n > LLM_MAX_ROWS) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch: %d rows (1..%d)", n, LLM_MAX_ROWS);
+  for (int r = 0; r < n; ++r) {
+    if (slots[r] < 0 || slots[r] >= c->n_slots) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch: row %d names slot %d, the cache has %d", r, slots[r], c->n_slots);
+    for (int p = 0; p < r; ++p)
+      if (slots[p] == slots[r]) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch: slot %d is named twice (rows %d and %d)", slots[r], p, r);
+  }
+  for (int r = 0; r < n; ++r) {
+    const int pos = c->spos[slots[r]];
+    if (pos < 1) return fail(c, IA2P_ERR_STATE, "llm_decode_batch: slot %d before a prefill (position 0)", slots[r]);
+    if (pos >= c->max_pos) return fail(c, IA2P_ERR_SHAPE, "llm_decode_batch: slot %d at position %d is past the cache (%d positions)", slots[r], pos, c->max_pos);
+    if (token_ids[r] < 0 || token_ids[r] >= c->cfg.vocab_size)
+      return fail(c, IA2P_ERR_SHAPE, "llm_decode_batch: token %d of row %d outside the vocabulary (%d)", token_ids[r], r, c->cfg.vocab_size);
+  }
+  st = llm_enter(c, stream, ws, ws_bytes, llm_dry_rows(c, n), true);
+  if (st != IA2P_OK) return st;
+  st = llm_leave(c, llm_run_decode_rows(c, slots, token_ids, n, hidden_out, logits_out));
+  if (st == IA2P_OK)
+    for (int r = 0; r < n; ++r) c->spos[slots[r]] += 1;
+  return st;
+}
+static LlmRows gemv_rows_args(const float* x, float* out, int N, int K, int M) {
+  LlmRows b{};
+  b.M = M;
+  for (int m = 0; m < M; ++m) { b.X[m] = x + (size_t)m * K; b.out[m] = out + (size_t)m * N; }
+  return b;
+}
+ia2p_status ia2p_llm_gemv_rows(void* stream, const void* W, const float* x, float* out, int N, int K, int M) {
+  if (!W || !x || !out) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv_rows: null argument");
+  if (N < 1 || K < 8 || K % 8) return fail(nullptr, IA2P_ERR_SHAPE, "llm_gemv_rows: N=%d K=%d (K a multiple of 8)", N, K);
+  if (M < 1 || M > LLM_MAX_ROWS) return fail(nullptr, IA2P_ERR_SHAPE, "llm_gemv_rows: M=%d (1..%d)", M, LLM_MAX_ROWS);
+  LlmGemv a{};
+  a.W = (const half_t*)W; a.N = N; a.K = K;
+  hipError_t e = llm_launch_gemv_rows(a, gemv_rows_args(x, out, N, K, M), EPI_PLAIN, (hipStream_t)stream);
+  RET_HIP(e, "llm_gemv_rows");
+}
+ia2p_status ia2p_llm_gemv_q4_rows(void* stream, const void* packed, const float* absmax, const float* codebook, const float* x, float* out, int N, int K, int M) {
+  if (!x || !out) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv_q4_rows: null argument");
+  const ia2p_status st = q4_op_args("llm_gemv_q4_rows", packed, absmax, out, codebook, N, K);
+  if (st != IA2P_OK) return st;
+  if (K > Q4_MAX_K) return fail(nullptr, IA2P_ERR_SHAPE, "llm_gemv_q4_rows: K=%d (at most %d)", K, Q4_MAX_K);
+  if (M < 1 || M > LLM_MAX_ROWS) return fail(nullptr, IA2P_ERR_SHAPE, "llm_gemv_q4_rows: M=%d (1..%d)", M, LLM_MAX_ROWS);
+  LlmGemv a{};
+  a.N = N; a.K = K;
+  LlmQ4 q;
+  q.Wq = (const u4v*)packed; q.absmax = absmax;
+  memcpy(q.cb.v, codebook, sizeof q.cb.v);
+  hipError_t e = llm_launch_gemv_q4_rows(a, q, gemv_rows_args(x, out, N, K, M), EPI_PLAIN, (hipStream_t)stream);
+  RET_HIP(e, "llm_gemv_q4_rows");
 }
 ia2p_status ia2p_llm_gemv(void* stream, const void* W, const float* x, float* out, int N, int K) {
   if (!W || !x || !out) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv: null argument");

@@ -5,6 +5,8 @@
                                        `vae_projector_image` (1024-d embedding -> hidden) and `vae_predictor_image` (hidden -> embedding)
   .generate(input_ids, ...)         <- `any2pix_lm.generate(...)` as pipeline.py:201-211 calls it. The reference runs one full forward per new
                                        token (`use_cache=False`); here the prompt is prefilled once and each token is one `ia2p_llm_decode`.
+  .generate_batch(input_ids_list)   <- several requests at once (no counterpart in the reference): `max_batch` cache slots, each request prefilled
+                                       into its own, then one `ia2p_llm_decode_batch` per step reads every weight once for all active requests
   KeywordsStoppingCriteria          <- llm/mm_utils.py:77-107
   vicuna_v1_prompt(inst)            <- `conv_templates['vicuna_v1']` with one user turn and an open assistant turn (llm/conversation.py:51-62,252-262)
   parse_generation(...)             <- pipeline.py:213-279: what `forward_llm` reads out of the generated sequence and its hidden rows
@@ -176,16 +178,22 @@ class _Head:
 class HipInstructAny2PixLM:
     PROJECTOR, PREDICTOR = "model.vae_projector_image", "model.vae_predictor_image"
 
+    MAX_ROWS = 8                       # IA2P_LLM_MAX_ROWS: sequences per decode_batch call
+
     def __init__(self, config: LLMConfig, device="cuda:0", max_positions: int = 1024, video_token_id: Optional[int] = None, *,
-                 load_in_4bit: bool = False, bnb_4bit_quant_type: str = "fp4", quantize_heads: bool = True):
-        """load_in_4bit / bnb_4bit_quant_type: the reference's `from_pretrained` keywords. quantize_heads: the two projector heads are
+                 load_in_4bit: bool = False, bnb_4bit_quant_type: str = "fp4", quantize_heads: bool = True, max_batch: int = 1):
+        """max_batch: cache slots, i.e. requests `generate_batch` decodes together (a slot holds `max_positions` rows of every layer: 512 MiB
+        at Vicuna-7B size and 1024 positions; the default keeps the single-sequence memory). load_in_4bit / bnb_4bit_quant_type: the reference's `from_pretrained` keywords. quantize_heads: the two projector heads are
         `nn.Linear`s inside the model, so the reference's loader quantises them with the decoder (it skips `lm_head` only); False keeps
         their fp16 weights."""
         if bnb_4bit_quant_type not in BNB_4BIT_CODEBOOKS:
             raise ValueError(f"bnb_4bit_quant_type '{bnb_4bit_quant_type}': one of {sorted(BNB_4BIT_CODEBOOKS)}")
+        if max_batch < 1:
+            raise ValueError(f"max_batch {max_batch}: at least one slot")
         self.config = config.validate()
         self.device = torch.device(device)
         self.max_positions = max_positions
+        self.max_batch = int(max_batch)
         self.DEFAULT_VIDEO_TOKEN_IDX = video_token_id        # id of `<video>` (set by the tokenizer side, any2pix_arch.py:285-288)
         self._lib = _ffi.lib()
         self._h = C.c_void_p()
@@ -198,9 +206,9 @@ class HipInstructAny2PixLM:
             _ffi.check(self._lib.ia2p_llm_set_weight_format(self._h, 4, self._codebook), self._h, llm=True)
         with torch.cuda.device(self.device):
             self.arena = torch.zeros(self._lib.ia2p_llm_arena_bytes(self._h), dtype=torch.uint8, device=self.device)
-            self.kv = torch.zeros(self._lib.ia2p_llm_kv_bytes(self._h, max_positions), dtype=torch.uint8, device=self.device)
+            self.kv = torch.zeros(self._lib.ia2p_llm_kv_slots_bytes(self._h, max_positions, self.max_batch), dtype=torch.uint8, device=self.device)
         _ffi.check(self._lib.ia2p_llm_bind_arena(self._h, _ffi.ptr(self.arena), self.arena.numel()), self._h, llm=True)
-        _ffi.check(self._lib.ia2p_llm_bind_kv(self._h, _ffi.ptr(self.kv), self.kv.numel(), max_positions), self._h, llm=True)
+        _ffi.check(self._lib.ia2p_llm_bind_kv_slots(self._h, _ffi.ptr(self.kv), self.kv.numel(), max_positions, self.max_batch), self._h, llm=True)
         d = projector_depth(config.mm_projector_type)
         self._projector, self._predictor = _Head(self.PROJECTOR, d), _Head(self.PREDICTOR, d)
         self._ws, self._ws_T = None, 0
@@ -275,7 +283,7 @@ class HipInstructAny2PixLM:
     # ---- engine calls ---------------------------------------------------------------------------------------------------
     def _workspace(self, T):
         if self._ws is None or T > self._ws_T:
-            n = self._lib.ia2p_llm_workspace_bytes(self._h, T)
+            n = self._lib.ia2p_llm_batch_workspace_bytes(self._h, T, min(self.max_batch, self.MAX_ROWS))
             if n == 0:
                 self._check(2)
             self._ws, self._ws_T = torch.empty(n, dtype=torch.uint8, device=self.device), T
@@ -316,6 +324,41 @@ class HipInstructAny2PixLM:
         ws = self._workspace(max(self._ws_T, 1))
         hid, logits = self._outputs()
         self._check(self._lib.ia2p_llm_decode(self._h, _ffi.current_stream(), int(token_id), _ffi.ptr(hid), _ffi.ptr(logits), _ffi.ptr(ws), ws.numel()))
+        return hid, logits
+
+    # ---- slots: several sequences in one cache ------------------------------------------------------------------------------
+    def reset_slot(self, slot: int):
+        self._check(self._lib.ia2p_llm_reset_slot(self._h, int(slot)))
+
+    def slot_position(self, slot: int) -> int:
+        return self._lib.ia2p_llm_slot_position(self._h, int(slot))
+
+    @torch.no_grad()
+    def prefill_slot(self, slot: int, inputs_embeds: torch.Tensor):
+        """`prefill` on the cache and position of `slot`; the other slots are not touched"""
+        x = inputs_embeds.to(device=self.device, dtype=torch.float16).contiguous()
+        if x.ndim != 2 or x.shape[1] != self.config.hidden_size:
+            raise ValueError("inputs_embeds must be [T, hidden]")
+        ws = self._workspace(x.shape[0])
+        hid, logits = self._outputs()
+        self._check(self._lib.ia2p_llm_prefill_slot(self._h, _ffi.current_stream(), int(slot), _ffi.ptr(x), x.shape[0], _ffi.ptr(hid), _ffi.ptr(logits),
+                                                    _ffi.ptr(ws), ws.numel()))
+        return hid, logits
+
+    @torch.no_grad()
+    def decode_batch(self, slots, token_ids):
+        """one decode step of the sequences in `slots` (distinct, at most 8): row r is the table embedding of token_ids[r] at the position of
+        slots[r] -> (hidden rows [n, hidden], logits rows [n, vocab]), fp32; every weight is read once for all rows"""
+        slots, token_ids = [int(s) for s in slots], [int(t) for t in token_ids]
+        if len(slots) != len(token_ids):
+            raise ValueError(f"{len(slots)} slots for {len(token_ids)} token ids")
+        n = len(slots)
+        ws = self._workspace(max(self._ws_T, 1))
+        hid = torch.empty(max(n, 1), self.config.hidden_size, dtype=torch.float32, device=self.device)
+        logits = torch.empty(max(n, 1), self.config.vocab_size, dtype=torch.float32, device=self.device)
+        ids = C.c_int32 * max(n, 1)
+        self._check(self._lib.ia2p_llm_decode_batch(self._h, _ffi.current_stream(), ids(*slots), ids(*token_ids), n, _ffi.ptr(hid), _ffi.ptr(logits),
+                                                    _ffi.ptr(ws), ws.numel()))
         return hid, logits
 
     def prepare_inputs_embeds(self, input_ids: torch.Tensor, extra_replacement=None) -> torch.Tensor:
@@ -367,6 +410,67 @@ class HipInstructAny2PixLM:
             if step + 1 < max_new_tokens:
                 hid, logits = self.decode(int(nxt))
         return SimpleNamespace(sequences=seq, hidden_states=tuple(hidden_states))
+
+
+    @torch.no_grad()
+    def generate_batch(self, input_ids_list, extra_replacements=None, do_sample: bool = True, temperature: float = 0.3, max_new_tokens: int = 100,
+                       stopping_criteria=None, top_k: Optional[int] = 50, **unused):
+        """`generate` for several requests. input_ids_list: [1, T_i] prompts; extra_replacements / stopping_criteria: one entry per request (an
+        `extra_replacement` dict / a list of criteria, or None), or None. -> a list with one `generate`-shaped object per request
+        (`.sequences` [1, T_i + new_i], `.hidden_states` with one entry per new token).
+
+        Requests run in consecutive groups of `max_batch`, at most 8 to a group. Each request of a group is prefilled into its own slot, then every
+        step brings the active rows' logits to the host in one copy, draws one token per row and decodes the rows that go on in one
+        `decode_batch` call; a request that stops, or has `max_new_tokens`, leaves the active set and the later calls carry fewer rows.
+        Each request's stopping criteria see that request's sequence only.
+
+        do_sample=False gives exactly the sequences and hidden rows of serial `generate(do_sample=False)` calls (a row of `decode_batch` equals
+        the single-sequence step bit for bit). do_sample=True draws all active rows of a step with ONE `torch.multinomial` call over the
+        [n_active, vocab] block, in request order: the draws of the requests interleave in the global RNG stream, so a batch is reproducible
+        for a seed but is not the stream serial `generate` calls would consume."""
+        prompts = list(input_ids_list)
+        n_req = len(prompts)
+        reps = list(extra_replacements) if extra_replacements is not None else [None] * n_req
+        crits = list(stopping_criteria) if stopping_criteria is not None else [None] * n_req
+        if len(reps) != n_req or len(crits) != n_req:
+            raise ValueError(f"{n_req} prompts, {len(reps)} extra_replacements, {len(crits)} stopping_criteria: one entry per request")
+        seqs = []
+        for p in prompts:
+            if p.ndim != 2 or p.shape[0] != 1:
+                raise ValueError("every prompt must be [1, tokens]")
+            if p.shape[1] + max_new_tokens > self.max_positions:
+                raise ValueError(f"{p.shape[1]} prompt tokens + {max_new_tokens} new ones do not fit {self.max_positions} cached positions")
+            seqs.append(p.detach().cpu().long())
+        nl = self.config.num_hidden_layers + 1
+        hidden = [[] for _ in range(n_req)]
+        group = min(self.max_batch, self.MAX_ROWS)
+        for g0 in range(0, n_req, group):
+            active = list(range(g0, min(g0 + group, n_req)))             # request i of the group lives in slot i - g0
+            rows = []
+            for i in active:
+                self.reset_slot(i - g0)
+                rows.append(self.prefill_slot(i - g0, self.prepare_inputs_embeds(seqs[i], reps[i])))
+            hid, logits = torch.stack([r[0] for r in rows]), torch.stack([r[1] for r in rows])
+            for step in range(max_new_tokens):
+                for r, i in enumerate(active):
+                    hidden[i].append(_LastOnly(hid[r].reshape(1, 1, -1), nl))
+                block = logits.cpu()                                     # [n_active, vocab]: one copy per step
+                if do_sample:
+                    nxt = torch.multinomial(sample_probs(block, temperature, top_k), num_samples=1).squeeze(1)
+                else:
+                    nxt = torch.argmax(block, dim=-1)
+                go_on, tokens = [], []
+                for r, i in enumerate(active):
+                    seqs[i] = torch.cat([seqs[i], nxt[r].reshape(1, 1).long()], dim=1)
+                    if crits[i] is not None and any(bool(torch.as_tensor(c(seqs[i], None)).all()) for c in crits[i]):
+                        continue
+                    go_on.append(i)
+                    tokens.append(int(nxt[r]))
+                active = go_on
+                if not active or step + 1 == max_new_tokens:
+                    break
+                hid, logits = self.decode_batch([i - g0 for i in active], tokens)
+        return [SimpleNamespace(sequences=seqs[i], hidden_states=tuple(hidden[i])) for i in range(n_req)]
 
 
 def get_all_objs(s):

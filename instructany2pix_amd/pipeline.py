@@ -216,8 +216,8 @@ class InstructAny2PixPipeline:
         tok = self.any2pix_tokenizer
         return {k: tok(k, add_special_tokens=False).input_ids[0] for k in ("<video>", "<base>", "<base_null>", "<im_gen>")}
 
-    def _llm_generate(self, inst, aux_info):
-        """:171-211: prompt, stopping criterion and the one `generate` call -> (input_ids, generate output)"""
+    def _llm_request(self, inst, aux_info):
+        """:171-200: -> (input_ids, extra_replacement, stopping criterion) of one request"""
         from .llm import KeywordsStoppingCriteria, REPLACEMENT_TYPE, VICUNA_V1_SEP2, vicuna_v1_prompt
         extra_replacement = {"data": aux_info, "mask": torch.tensor([REPLACEMENT_TYPE.INPUT] * aux_info.shape[0], dtype=torch.long)}
         prompt = vicuna_v1_prompt(inst)
@@ -227,6 +227,12 @@ class InstructAny2PixPipeline:
         if lm.DEFAULT_VIDEO_TOKEN_IDX is None:
             lm.DEFAULT_VIDEO_TOKEN_IDX = self._llm_special_ids()["<video>"]
         lm.eval()
+        return input_ids, extra_replacement, stopping_criteria
+
+    def _llm_generate(self, inst, aux_info):
+        """:171-211: prompt, stopping criterion and the one `generate` call -> (input_ids, generate output)"""
+        input_ids, extra_replacement, stopping_criteria = self._llm_request(inst, aux_info)
+        lm = self.any2pix_lm
         out = lm.generate(input_ids, images=None, do_sample=True, temperature=0.3, max_new_tokens=100, output_hidden_states=True, use_cache=False,
                           return_dict_in_generate=True, extra_replacement=extra_replacement, stopping_criteria=[stopping_criteria])
         return input_ids, out
@@ -244,6 +250,37 @@ class InstructAny2PixPipeline:
         tp = self.any2pix_tokenizer.batch_decode(out.sequences)
         return parse_generation(out.sequences, input_ids.shape[1], out.hidden_states, tp[0], aux_info, mm_data,
                                 self.any2pix_lm.get_model().vae_predictor_image, ids["<video>"], ids["<base>"], ids["<im_gen>"])
+
+    def _llm_generate_batch(self, requests):
+        """the one `generate_batch` call for [(input_ids, extra_replacement, stopping criterion), ...] -> list of generate outputs"""
+        return self.any2pix_lm.generate_batch([r[0] for r in requests], extra_replacements=[r[1] for r in requests], do_sample=True, temperature=0.3,
+                                              max_new_tokens=100, stopping_criteria=[[r[2]] for r in requests])
+
+    def forward_llm_batch(self, insts, mm_datas):
+        """`forward_llm` for several requests, their decode steps sharing every read of the LLM's weights (`HipInstructAny2PixLM.generate_batch`):
+        -> a list of the five-tuples `forward_llm` returns, in request order. More requests than the LLM's `max_batch` run in consecutive groups.
+        The sampled tokens are reproducible for a seed but are not those of serial `forward_llm` calls (the draws of a step interleave across the
+        requests). `self.cache` is not touched."""
+        insts, mm_datas = list(insts), list(mm_datas)
+        if len(insts) != len(mm_datas):
+            raise ValueError(f"{len(insts)} instructions for {len(mm_datas)} mm_data lists")
+        if self.any2pix_lm is None or self.any2pix_tokenizer is None:
+            raise NotImplementedError("forward_llm_batch needs the pipeline built with llm=<HipInstructAny2PixLM> and llm_tokenizer=")
+        if len(insts) > 1 and getattr(self.any2pix_lm, "max_batch", 1) == 1:
+            raise ValueError(f"{len(insts)} requests for an LLM built with max_batch=1: build it with max_batch > 1, or call forward_llm per request")
+        if not insts:
+            return []
+        from .llm import parse_generation
+        aux = [self._modality_embeds(mm) for mm in mm_datas]
+        requests = [self._llm_request(inst, a) for inst, a in zip(insts, aux)]
+        outs = self._llm_generate_batch(requests)
+        ids = self._llm_special_ids()
+        results = []
+        for (input_ids, _, _), out, a, mm in zip(requests, outs, aux, mm_datas):
+            tp = self.any2pix_tokenizer.batch_decode(out.sequences)
+            results.append(parse_generation(out.sequences, input_ids.shape[1], out.hidden_states, tp[0], a, mm,
+                                            self.any2pix_lm.get_model().vae_predictor_image, ids["<video>"], ids["<base>"], ids["<im_gen>"]))
+        return results
 
     def _condition_from_llm(self, inst, mm_data, use_cache, llm_only):
         """the conditioning dict a `conditioner=` would return, from forward_llm + the attached text encoders (:309-310, :330, :342-345, :358-361)"""

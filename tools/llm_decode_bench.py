@@ -13,7 +13,13 @@ the library had for M = 1, `ia2p_linear_small`.
           fp32 absmax per 64 weights, 0.5625 bytes per projection weight), and part 2 gets a third column for `ia2p_llm_gemv_q4` on the same
           shapes, interleaved with the other two, its pool holding the quantised copies of the same matrices (a pool over 256 MiB as well).
 
-    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--bits 4] [--quant-type fp4] [--skip-decode] [--skip-gemv]
+  --batch 1,2,4,8: part 1 is followed, per format, by the batched decode (`ia2p_llm_decode_batch`, n sequences per weight pass): for every n the ms per
+          decode step at n rows beside n serial `ia2p_llm_decode` steps, measured in the same process one after the other (second request, 64-row
+          prompts, the same tokens, stream-synchronised wall time; the serial figure is n x the ms of one serial step over the same number of steps).
+          Part 2 gets one more line per shape and M: `ia2p_llm_gemv_rows` (and `ia2p_llm_gemv_q4_rows` with --bits 4) on the same pools, interleaved
+          with the single-row launches, us per launch and per row.
+
+    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--bits 4] [--quant-type fp4] [--batch 1,2,4,8] [--skip-decode] [--skip-gemv]
 """
 import argparse
 import ctypes as C
@@ -65,7 +71,42 @@ def decode_part(layers, tokens, bits=16, quant_type="fp4"):
     torch.cuda.empty_cache()
 
 
-def gemv_part(reps, bits=16, quant_type="fp4"):
+def batch_part(layers, tokens, rows, bits=16, quant_type="fp4"):
+    cfg = vicuna_7b(32000)
+    cfg.num_hidden_layers = layers
+    lm = HipInstructAny2PixLM(cfg, DEV, max_positions=64 + tokens + 8, load_in_4bit=bits == 4, bnb_4bit_quant_type=quant_type, max_batch=max(rows))
+    lm.load_state_dict(iter_synthetic(llm_param_specs(cfg), 7, DEV, torch.float16))
+    torch.cuda.synchronize()
+    fmt = "fp16" if bits == 16 else f"4-bit {quant_type}"
+    g = torch.Generator().manual_seed(1)
+    prompt = torch.randint(3, cfg.vocab_size, (64,), generator=g)
+    nxt = torch.randint(3, cfg.vocab_size, (tokens,), generator=g).tolist()
+    emb = lm.embed_tokens(prompt)
+    print(f"[{fmt}] batched decode, {layers} layers, {max(rows)} slots of {lm.max_positions} positions ({lm.kv.numel() / 2 ** 20:.0f} MiB of cache); ms per step over {tokens} steps")
+    for rnd in range(2):           # request 0 warms up
+        for n in rows:
+            slots = list(range(n))
+            for s in slots:
+                lm.reset_slot(s)
+                lm.prefill_slot(s, emb)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for t in nxt:
+                lm.decode_batch(slots, [t] * n)
+            torch.cuda.synchronize(); t1 = time.perf_counter()
+            lm.reset()
+            lm.prefill(emb)
+            torch.cuda.synchronize(); t2 = time.perf_counter()
+            for t in nxt:
+                lm.decode(t)
+            torch.cuda.synchronize(); t3 = time.perf_counter()
+            b, s1 = (t1 - t0) * 1e3 / tokens, (t3 - t2) * 1e3 / tokens
+            print(f"[{fmt}] request {rnd}: n = {n}: decode_batch {b:.3f} ms per step, {n} serial decode steps {n * s1:.3f} ms ({s1:.3f} each), "
+                  f"serial / batched {n * s1 / b:.2f}x, {n / (b * 1e-3):.0f} tokens per second over the {n} requests", flush=True)
+    del lm
+    torch.cuda.empty_cache()
+
+
+def gemv_part(reps, bits=16, quant_type="fp4", rows=()):
     lib = _ffi.lib()
     cb = (C.c_float * 16)(*BNB_4BIT_CODEBOOKS[quant_type])
     g = torch.Generator(device=DEV).manual_seed(2)
@@ -76,6 +117,8 @@ def gemv_part(reps, bits=16, quant_type="fp4"):
         pool = [(torch.randn(N, K, generator=g, device=DEV, dtype=torch.float32) * K ** -0.5).half() for _ in range(copies)]
         x16 = torch.randn(1, K, generator=g, device=DEV).half()
         x32 = x16.float().reshape(-1).contiguous()
+        xm = torch.cat([x32[None], torch.randn(7, K, generator=g, device=DEV)]).contiguous()      # [8, K]: row 0 is the single-row input
+        om = torch.empty(8, N, dtype=torch.float32, device=DEV)
         o16 = torch.empty(1, N, dtype=torch.float16, device=DEV)
         o32 = torch.empty(N, dtype=torch.float32, device=DEV)
         s = _ffi.current_stream()
@@ -88,7 +131,13 @@ def gemv_part(reps, bits=16, quant_type="fp4"):
             for w in pool:
                 _ffi.check(lib.ia2p_linear_small(s, _ffi.ptr(x16), _ffi.ptr(w), None, _ffi.ptr(o16), 1, N, K, 0, 0))
 
-        runs = [("gemv", run_gemv), ("small", run_small)]
+        def run_rows(M):
+            def fn():
+                for w in pool:
+                    _ffi.check(lib.ia2p_llm_gemv_rows(s, _ffi.ptr(w), _ffi.ptr(xm), _ffi.ptr(om), N, K, M), None, llm=True)
+            return fn
+
+        runs = [("gemv", run_gemv), ("small", run_small)] + [(f"rows{M}", run_rows(M)) for M in rows]
         if bits == 4:
             qbytes = lib.ia2p_llm_q4_packed_bytes(N, K) + 4 * (N * K // 64)
             qcopies = max(4, -(-(640 << 20) // qbytes))
@@ -106,13 +155,20 @@ def gemv_part(reps, bits=16, quant_type="fp4"):
                 for packed, absmax in qpool:
                     _ffi.check(lib.ia2p_llm_gemv_q4(s, _ffi.ptr(packed), _ffi.ptr(absmax), cb, _ffi.ptr(x32), _ffi.ptr(o4), N, K), None, llm=True)
 
+            def run_q4_rows(M):
+                def fn():
+                    for packed, absmax in qpool:
+                        _ffi.check(lib.ia2p_llm_gemv_q4_rows(s, _ffi.ptr(packed), _ffi.ptr(absmax), cb, _ffi.ptr(xm), _ffi.ptr(om), N, K, M), None, llm=True)
+                return fn
+
             runs.append(("q4", run_q4))
+            runs += [(f"q4rows{M}", run_q4_rows(M)) for M in rows]
         for _, fn in runs:
             fn()
         torch.cuda.synchronize()
         err = float((o32 - o16.float().reshape(-1)).abs().max())
         times = {name: [] for name, _ in runs}
-        per = {"gemv": copies, "small": copies, "q4": qcopies if bits == 4 else 1}
+        per = {name: (qcopies if name.startswith("q4") else copies) for name, _ in runs}
         for _ in range(reps):
             for name, fn in runs:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -126,6 +182,14 @@ def gemv_part(reps, bits=16, quant_type="fp4"):
             q = statistics.median(times["q4"])
             print(f"  {'':6s}   {'':5s}  4-bit {quant_type} ({qbytes / 1e6:6.1f} MB, pool of {qcopies}): llm_gemv_q4 {q:7.2f} us ({qbytes / q / 1e6:.2f} TB/s of the bytes it reads), "
                   f"min {min(times['q4']):.2f}, fp16 / 4-bit time {a / q:.2f}x", flush=True)
+        for M in rows:
+            r = statistics.median(times[f"rows{M}"])
+            line = f"  {'':6s}   {'':5s}  M = {M}: llm_gemv_rows {r:7.2f} us ({r / M:6.2f} per row, {M * a / r:.2f}x of {M} single-row launches)"
+            if bits == 4:
+                rq = statistics.median(times[f"q4rows{M}"])
+                line += f"; llm_gemv_q4_rows {rq:7.2f} us ({rq / M:6.2f} per row, {M * q / rq:.2f}x of {M} single-row launches)"
+            print(line, flush=True)
+        if bits == 4:
             del qpool
         del pool
         torch.cuda.empty_cache()
@@ -138,14 +202,22 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--bits", type=int, default=16, choices=(16, 4))
     ap.add_argument("--quant-type", default="fp4", choices=sorted(BNB_4BIT_CODEBOOKS))
+    ap.add_argument("--batch", default="", help="comma-separated row counts (1..8) for the batched decode and the multi-row GEMVs, e.g. 1,2,4,8")
     ap.add_argument("--skip-decode", action="store_true")
     ap.add_argument("--skip-gemv", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("llm_decode_bench needs the GPU: no timing is reported without one")
+    rows = tuple(int(x) for x in a.batch.split(",") if x)
+    if any(n < 1 or n > 8 for n in rows):
+        sys.exit("--batch: row counts of 1..8")
     if not a.skip_gemv:
-        gemv_part(a.reps, a.bits, a.quant_type)
+        gemv_part(a.reps, a.bits, a.quant_type, rows)
     if not a.skip_decode:
         decode_part(a.layers, a.tokens)
+        if rows:
+            batch_part(a.layers, a.tokens, rows)
         if a.bits == 4:
             decode_part(a.layers, a.tokens, 4, a.quant_type)
+            if rows:
+                batch_part(a.layers, a.tokens, rows, 4, a.quant_type)
