@@ -180,6 +180,26 @@ def test_prefill_slot_does_not_disturb_its_neighbours(tiny):
     assert lm.slot_position(0) == 9 and lm.slot_position(1) == 33
 
 
+def test_one_row_batches_and_single_decodes_continue_a_batched_stream(tiny):
+    """one decode driver serves `decode` and `decode_batch`: a batch of one row on a slot other than 0 is the serial stream, and after a step
+    at n = 3 `decode` (slot 0) continues its stream where the batch left it, and the other way round"""
+    lm = tiny.lm
+    tiny.prefill_all()                       # streams 0, 1, 2 live in slots 5, 0, 2
+
+    def alone(step):
+        tiny.step([0], step)                 # n = 1, slot 5
+        hid, logits = lm.decode(int(tiny.ids[1][PROMPTS[1] + step]))          # the single-sequence entry point: slot 0
+        assert torch.equal(hid, tiny.ref[1][0][1 + step]) and torch.equal(logits, tiny.ref[1][1][1 + step]), f"step {step}: decode after a batch differs"
+        tiny.step([2], step)                 # n = 1, slot 2
+
+    alone(0)
+    tiny.step([0, 1, 2], 1)
+    alone(2)
+    tiny.step([0, 1, 2], 3)
+    alone(4)
+    assert [lm.slot_position(s) for s in (5, 0, 2)] == [5 + 5, 12 + 5, 33 + 5] and lm.position == 12 + 5
+
+
 # ---- full width -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("fmt", ["fp16", "fp4"])
 def test_full_width_eight_rows(fmt):

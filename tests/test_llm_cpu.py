@@ -215,6 +215,27 @@ def test_llm_abi_sizes_and_state(lib):
     lib.ia2p_llm_destroy(h)
 
 
+@pytest.mark.parametrize("bits", [16, 4])
+def test_llm_workspace_bytes_are_the_recorded_ones(lib, bits):
+    """`tiny_llm()`: the bytes `ia2p_llm_workspace_bytes(c, T)` and `ia2p_llm_batch_workspace_bytes(c, T, n)` returned before the single-row and the
+    batched decode driver became one (host dry runs; a decode step of one row allocates the four buffers it always did)"""
+    from instructany2pix_amd import _ffi
+    from instructany2pix_amd.config import BNB_4BIT_CODEBOOKS, tiny_llm
+    prefill = {16: {1: 18944, 9: 152064, 33: 551424}, 4: {1: 2902528, 9: 3035648, 33: 3435008}}[bits]
+    decode = {1: 12032, 2: 23808, 8: 94464}          # n rows, either format (T = 0: no prefill)
+    h = C.c_void_p()
+    _ffi.check(lib.ia2p_llm_create(C.byref(_ffi.make_llm_config(tiny_llm())), C.byref(h)), None, llm=True)
+    if bits == 4:
+        _ffi.check(lib.ia2p_llm_set_weight_format(h, 4, (C.c_float * 16)(*BNB_4BIT_CODEBOOKS["fp4"])), h, llm=True)
+    for T, want in prefill.items():
+        assert lib.ia2p_llm_workspace_bytes(h, T) == want, (bits, T)
+        for n in (1, 8):
+            assert lib.ia2p_llm_batch_workspace_bytes(h, T, n) == max(want, decode[n]), (bits, T, n)
+    for n, want in decode.items():
+        assert lib.ia2p_llm_batch_workspace_bytes(h, 0, n) == want, (bits, n)
+    lib.ia2p_llm_destroy(h)
+
+
 def test_llm_param_specs_cover_the_checkpoint_keys():
     from instructany2pix_amd.config import tiny_llm
     from instructany2pix_amd.weights import llm_param_specs, synthetic_state_dict
