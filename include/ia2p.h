@@ -370,6 +370,42 @@ ia2p_status ia2p_clip_encode_embeds(ia2p_clip* clip, void* stream, const void* i
 ia2p_status ia2p_prior_step(void* stream, const float* sample, const void* out_cond, const void* out_uncond, const float* noise, float g,
                             float sqrt_a, float sqrt_b, float k0, float k1, float sigma, float* out, int64_t n);
 
+/* ---- ViT towers: ImageBind's vision and audio encoders (reference pipeline.py:118-121 `imagebind_huge`, :155-168: every mm_data entry becomes a
+ * 1024-d vector) ------------------------------------------------------------------------------------------------------------------------
+ * One tower: a bias-free patch convolution (patch x patch, stride patch_stride; the grid is floor((size - patch) / stride) + 1 per axis), optional
+ * LayerNorm of the patch rows (stem_ln), class token in front, learned position embeddings, optional pre-transformer LayerNorm (pre_ln), pre-LayerNorm
+ * blocks with non-causal self-attention at head dim 64 or 80 and an exact-GELU MLP, LayerNorm of the class row, bias-free projection to out_dim.
+ * bias_kv: every attention sees one more key / value row, `attn.bias_k` / `attn.bias_v` (torch nn.MultiheadAttention(add_bias_kv=True)).
+ * Parameter keys: "stem.weight" [hidden, C, patch, patch], "stem.norm.{weight,bias}", "cls_token", "pos_embed" [tokens, hidden],
+ * "pre_ln.{weight,bias}", "blocks.<i>.norm_1|norm_2.{weight,bias}", "blocks.<i>.attn.in_proj_weight|in_proj_bias|out_proj.weight|out_proj.bias|bias_k|bias_v",
+ * "blocks.<i>.mlp.fc1|fc2.{weight,bias}", "head.norm.{weight,bias}", "head.proj.weight" [out_dim, hidden]; all fp16.
+ * IA2P_ERR_SHAPE at create: hidden not a multiple of 64, a head dim other than 64 / 80, a patch larger than the input, more than 272 keys per image. */
+typedef struct ia2p_vit ia2p_vit;
+typedef struct {
+  int hidden_size, num_layers, num_heads, intermediate_size;
+  int in_channels, image_h, image_w;
+  int patch_size, patch_stride;
+  int pre_ln, stem_ln, bias_kv;     /* 0 / 1 each */
+  int out_dim;
+  float layer_norm_eps;             /* <= 0: 1e-6 */
+} ia2p_vit_config;
+ia2p_status ia2p_vit_create(const ia2p_vit_config* cfg, ia2p_vit** out);
+void ia2p_vit_destroy(ia2p_vit* vit);
+const char* ia2p_vit_last_error(ia2p_vit* vit);
+size_t ia2p_vit_arena_bytes(ia2p_vit* vit);
+int ia2p_vit_tokens(ia2p_vit* vit);                /* class token + patches */
+ia2p_status ia2p_vit_bind_arena(ia2p_vit* vit, void* dev_arena, size_t bytes);
+ia2p_status ia2p_vit_load_tensor(ia2p_vit* vit, const char* key, const void* dev_src, const int64_t* shape, int ndim, void* stream);
+ia2p_status ia2p_vit_finalize_weights(ia2p_vit* vit);
+size_t ia2p_vit_workspace_bytes(ia2p_vit* vit, int B);
+/* pixels: fp16 [B, C, H, W] on the device. out: fp32 [B, out_dim], the head's output (no normalisation). last_hidden (optional): fp16 [B, tokens, hidden],
+ * the last block's output before the head's LayerNorm. */
+ia2p_status ia2p_vit_encode(ia2p_vit* vit, void* stream, const void* pixels, int B, float* out, void* last_hidden, void* workspace, size_t workspace_bytes);
+/* The towers' attention launch alone: O = softmax(Q K^T / sqrt(D)) V over all T keys of an image, no mask. qkv: fp16 [B*T, 3*heads*D] rows = [q | k | v];
+ * out: fp16 [B*T, heads*D]; D = 64 or 80. bias_k / bias_v (both or neither): fp16 [heads*D], one more key / value row after the T token rows.
+ * At most 272 keys (IA2P_ERR_SHAPE). Scores and softmax in fp32, fixed reduction order. */
+ia2p_status ia2p_attention_full(void* stream, const void* qkv, void* out, const void* bias_k, const void* bias_v, int B, int T, int heads, int D);
+
 /* ---- the instruction LLM: LLaMA decoder with a KV cache (reference pipeline.py:151-279 `forward_llm`; the model is a Vicuna-7B shaped
  * `LlamaForCausalLM`, llm/model/language_model/any2pix_llama.py, driven by `any2pix_lm.generate(...)` at pipeline.py:201-211 with use_cache=False:
  * one full forward per new token there, one cached row here). transformers `LlamaModel` + `lm_head` semantics: pre-RMSNorm blocks, rotary

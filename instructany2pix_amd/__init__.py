@@ -6,7 +6,8 @@ Importing this package touches no GPU and no native code; the HIP library (libia
 from .config import BNB_4BIT_CODEBOOKS, LLMConfig, UNetConfig, sdxl_base, sdxl_refiner, tiny, tiny_llm, vicuna_7b
 
 __all__ = ["InstructAny2PixPrior", "prior_config", "MODALITY", "HipGPT2Model", "DDPMScheduler", "HipCLIPTextModel", "SDXLTextEncoders", "UNetConfig", "sdxl_base", "sdxl_refiner", "tiny", "StableDiffusionXLImg2ImgPipeline", "EulerDiscreteScheduler", "InstructAny2PixPipeline", "HipUNet2DConditionModel", "DDIMScheduler",
-           "SDXLDDIMPipeline", "StableDiffusionXLPipeline", "IPAdapterXL", "ImageProjModel", "HipAutoencoderKL", "EditRequest", "VaeImageProcessor", "HipInstructAny2PixLM", "KeywordsStoppingCriteria", "LLMConfig", "vicuna_7b", "tiny_llm", "BNB_4BIT_CODEBOOKS"]
+           "SDXLDDIMPipeline", "StableDiffusionXLPipeline", "IPAdapterXL", "ImageProjModel", "HipAutoencoderKL", "EditRequest", "VaeImageProcessor", "HipInstructAny2PixLM", "KeywordsStoppingCriteria", "LLMConfig", "vicuna_7b", "tiny_llm", "BNB_4BIT_CODEBOOKS",
+           "HipImageBindModel", "ModalityType", "imagebind_huge_config"]
 
 
 def __getattr__(name):          # lazy: keep `import instructany2pix_amd` free of torch/ctypes work
@@ -34,6 +35,9 @@ def __getattr__(name):          # lazy: keep `import instructany2pix_amd` free o
     elif name in ("HipInstructAny2PixLM", "KeywordsStoppingCriteria"):
         from . import llm
         v = getattr(llm, name)
+    elif name in ("HipImageBindModel", "ModalityType", "imagebind_huge_config"):
+        from . import imagebind
+        v = getattr(imagebind, name)
     elif name == "EditRequest":
         from .batch import EditRequest as v
     elif name == "HipAutoencoderKL":

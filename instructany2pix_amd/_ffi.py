@@ -36,6 +36,12 @@ class CLIPConfigC(C.Structure):
                 ("max_positions", C.c_int), ("projection_dim", C.c_int), ("hidden_act", C.c_int), ("eos_token_id", C.c_int), ("layer_norm_eps", C.c_float)]
 
 
+class ViTConfigC(C.Structure):
+    _fields_ = [("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int), ("intermediate_size", C.c_int), ("in_channels", C.c_int),
+                ("image_h", C.c_int), ("image_w", C.c_int), ("patch_size", C.c_int), ("patch_stride", C.c_int), ("pre_ln", C.c_int), ("stem_ln", C.c_int),
+                ("bias_kv", C.c_int), ("out_dim", C.c_int), ("layer_norm_eps", C.c_float)]
+
+
 class LLMConfigC(C.Structure):
     _fields_ = [("vocab_size", C.c_int), ("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int), ("num_kv_heads", C.c_int),
                 ("intermediate_size", C.c_int), ("rms_norm_eps", C.c_float), ("rope_theta", C.c_float)]
@@ -128,6 +134,17 @@ SIGNATURES = {
     "ia2p_clip_workspace_bytes": (_SZ, [_P, _I, _I]),
     "ia2p_clip_encode": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _SZ]),
     "ia2p_clip_encode_embeds": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _SZ]),
+    "ia2p_vit_create": (_I, [C.POINTER(ViTConfigC), C.POINTER(_P)]),
+    "ia2p_vit_destroy": (None, [_P]),
+    "ia2p_vit_last_error": (C.c_char_p, [_P]),
+    "ia2p_vit_arena_bytes": (_SZ, [_P]),
+    "ia2p_vit_tokens": (_I, [_P]),
+    "ia2p_vit_bind_arena": (_I, [_P, _P, _SZ]),
+    "ia2p_vit_load_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I, _P]),
+    "ia2p_vit_finalize_weights": (_I, [_P]),
+    "ia2p_vit_workspace_bytes": (_SZ, [_P, _I]),
+    "ia2p_vit_encode": (_I, [_P, _P, _P, _I, _P, _P, _P, _SZ]),
+    "ia2p_attention_full": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "ia2p_prior_step": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P, _I64]),
     "ia2p_llm_create": (_I, [C.POINTER(LLMConfigC), C.POINTER(_P)]),
     "ia2p_llm_destroy": (None, [_P]),
@@ -218,12 +235,12 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def check(status: int, ctx=None, vae=False, clip=False, llm=False):
+def check(status: int, ctx=None, vae=False, clip=False, llm=False, vit=False):
     """Map ia2p_status to the exception types the reference raises at the same conditions
     (ValueError from check_inputs/_get_add_time_ids, reference pnp_pipeline.py:49-66)."""
     if status == IA2P_OK:
         return
-    msg = (lib().ia2p_llm_last_error(ctx) if llm else lib().ia2p_clip_last_error(ctx) if clip else lib().ia2p_vae_last_error(ctx) if vae
+    msg = (lib().ia2p_vit_last_error(ctx) if vit else lib().ia2p_llm_last_error(ctx) if llm else lib().ia2p_clip_last_error(ctx) if clip else lib().ia2p_vae_last_error(ctx) if vae
            else lib().ia2p_last_error(ctx))
     msg = msg.decode() if msg else ""
     text = f"ia2p {_STATUS_NAMES.get(status, status)}: {msg}"
@@ -275,6 +292,13 @@ def make_clip_config(cfg) -> CLIPConfigC:
     c.intermediate_size, c.max_positions, c.projection_dim = cfg.intermediate_size, cfg.max_position_embeddings, cfg.projection_dim
     c.hidden_act = {"gelu": 1, "quick_gelu": 2, "gelu_new": 3}[cfg.hidden_act]
     c.eos_token_id, c.layer_norm_eps = cfg.eos_token_id, cfg.layer_norm_eps
+    return c
+
+
+def make_vit_config(cfg) -> ViTConfigC:
+    c = ViTConfigC()
+    for name, _ in ViTConfigC._fields_:
+        setattr(c, name, getattr(cfg, name))
     return c
 
 

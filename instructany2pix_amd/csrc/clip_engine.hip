@@ -1,13 +1,12 @@
 // CLIP text-encoder executor and its C ABI (ia2p_clip_*): see include/ia2p.h and DESIGN.md §8. Runtime and operator wrappers: engine_rt.h / engine_rt.hip.
-#include "engine_rt.h"
+#include "xf_layer.h"
 
 // =====================================================================================================================
 // CLIP text encoders: the conditioning side of the path, on the same GEMM kernel.
 // transformers CLIPTextModel / CLIPTextModelWithProjection (reference encode_prompt, ddim/sdxl_pipeline.py:202-395).
-// Per layer: 4 GEMMs (QKV with layer_norm1 folded, out-proj + residual, fc1 with layer_norm2 folded + activation,
+// Per layer (xf_layer.h): 4 GEMMs (QKV with layer_norm1 folded, out-proj + residual, fc1 with layer_norm2 folded + activation,
 // fc2 + residual) and one causal attention launch; no LayerNorm launches (row statistics travel as in the UNet).
 // =====================================================================================================================
-struct CLayer { size_t ln1g, ln1b, wqkv, bqkv, wo, bo, ln2g, ln2b, w1, b1, w2, b2, fqkv, cs1, lb1, f1, cs2, lb2; };
 struct ia2p_clip : RunCtx {
   ia2p_clip_config cfg;
   size_t tok, pos, lnfg, lnfb, wproj;
@@ -53,14 +52,7 @@ static ia2p_status clip_plan(ia2p_clip* c) {
 }
 
 static ia2p_status clip_fold(ia2p_clip* c, hipStream_t stream = nullptr, bool sync = true) {
-  const int H = c->cfg.hidden_size, I = c->cfg.intermediate_size;
-  hipError_t e = hipSuccess;
-  auto Hp = [&](size_t off) { return c->arena + off; };
-  auto Fp = [&](size_t off) { return (float*)(c->arena + off); };
-  for (const CLayer& l : c->layers) {
-    if (e == hipSuccess) e = ia2p_launch_fold_ln(Hp(l.wqkv), Hp(l.ln1g), Hp(l.ln1b), Hp(l.bqkv), Hp(l.fqkv), Fp(l.cs1), Fp(l.lb1), 3 * H, H, stream);
-    if (e == hipSuccess) e = ia2p_launch_fold_ln(Hp(l.w1), Hp(l.ln2g), Hp(l.ln2b), Hp(l.b1), Hp(l.f1), Fp(l.cs2), Fp(l.lb2), I, H, stream);
-  }
+  hipError_t e = xf_fold(c, c->layers, c->cfg.hidden_size, c->cfg.intermediate_size, stream);
   if (e == hipSuccess && sync) e = hipStreamSynchronize(stream);
   if (e != hipSuccess) return fail_hip(c, e, "clip LayerNorm folding");
   c->fold_dirty = false;
@@ -70,7 +62,6 @@ static ia2p_status clip_fold(ia2p_clip* c, hipStream_t stream = nullptr, bool sy
 static ia2p_status clip_run(ia2p_clip* c, const int* ids, const half_t* embeds, int B, int T, half_t* hid2, half_t* last, half_t* pooled) {
   const ia2p_clip_config& g = c->cfg;
   const int H = g.hidden_size, I = g.intermediate_size, M = B * T, L = g.num_layers;
-  auto Fp = [&](size_t off) { return (const float*)(c->arena + off); };
   T2 x = wsalloc(c, (size_t)M * H), qkv = wsalloc(c, (size_t)M * 3 * H), att = wsalloc(c, (size_t)M * H), ff = wsalloc(c, (size_t)M * I);
   T2 stt = wsalloc(c, (size_t)M * ((H + 63) / 64) * 2 * 2);
   float* st = (float*)stt.p;
@@ -84,17 +75,8 @@ static ia2p_status clip_run(ia2p_clip* c, const int* ids, const half_t* embeds, 
       hipError_t e = hipMemcpyAsync(hid2, x.p, (size_t)M * H * sizeof(half_t), hipMemcpyDeviceToDevice, c->stream);
       if (e != hipSuccess) fail_hip(c, e, "clip");
     }
-    {
-      const LnIn ln{st, slots, Fp(l.cs1), Fp(l.lb1), g.layer_norm_eps};
-      op_gemm(c, x.p, H, W_(c, l.fqkv), nullptr, nullptr, 0, qkv.p, 3 * H, M, 3 * H, H, 0, 0, 0, 0, 0, &ln);
-    }
-    CHECK_LAUNCH(c, ia2p_launch_causal_attention_small(qkv.p, att.p, B, T, g.num_heads, c->stream), "clip attention");
-    op_gemm(c, att.p, H, W_(c, l.wo), W_(c, l.bo), x.p, H, x.p, H, M, H, H, 0, 0, 0, 0, 0, nullptr, st, &slots);
-    {
-      const LnIn ln{st, slots, Fp(l.cs2), Fp(l.lb2), g.layer_norm_eps};
-      op_gemm(c, x.p, H, W_(c, l.f1), nullptr, nullptr, 0, ff.p, I, M, I, H, 0, 0, 0, 0, 0, &ln, nullptr, nullptr, g.hidden_act);
-    }
-    op_gemm(c, ff.p, I, W_(c, l.w2), W_(c, l.b2), x.p, H, x.p, H, M, H, I, 0, 0, 0, 0, 0, nullptr, st, &slots);
+    xf_layer(c, l, x.p, qkv.p, att.p, ff.p, st, slots, M, H, I, g.layer_norm_eps, g.hidden_act,
+             [&] { CHECK_LAUNCH(c, ia2p_launch_causal_attention_small(qkv.p, att.p, B, T, g.num_heads, c->stream), "clip attention"); });
   }
   if (!need_last && hid2 && !c->dry && !c->failed) {
     hipError_t e = hipMemcpyAsync(hid2, x.p, (size_t)M * H * sizeof(half_t), hipMemcpyDeviceToDevice, c->stream);

@@ -1,4 +1,4 @@
-// Runtime shared by the executors (conditional UNet: engine.hip, VAE: vae_engine.hip, CLIP text towers: clip_engine.hip, instruction LLM: llm_engine.hip) and the
+// Runtime shared by the executors (conditional UNet: engine.hip, VAE: vae_engine.hip, CLIP text towers: clip_engine.hip, ViT towers: vit_engine.hip, instruction LLM: llm_engine.hip) and the
 // per-operator C ABI (ops_abi.hip): weight arena + parameter table, workspace allocator, weight-prefetch plan, per-kernel event timing, and the operator wrappers that
 // plan and launch the HIP kernels. Definitions live in engine_rt.hip; the launch descriptors are built in launch_args.h.
 #pragma once
@@ -66,6 +66,13 @@ hipError_t ia2p_launch_prior_step(const float* smp, const half_t* o_c, const hal
 hipError_t ia2p_launch_causal_attention_small(const half_t* qkv, half_t* out, int B, int T, int heads, hipStream_t s);
 hipError_t ia2p_launch_clip_pool(const int* ids, const half_t* x, const half_t* gamma, const half_t* beta, half_t* out, int B, int T, int H, int eos_id,
                                  float eps, hipStream_t s);
+// vit.hip: the ViT executor's kernels (non-causal attention over <= ia2p_full_attention_max_keys() keys at head dim 64 / 80, patch im2col, embedding row pass, fp32 class-row projection)
+int ia2p_full_attention_max_keys();
+hipError_t ia2p_launch_full_attention(const half_t* qkv, half_t* out, const half_t* bias_k, const half_t* bias_v, int B, int T, int heads, int D, hipStream_t s);
+hipError_t ia2p_launch_patch_gather(const half_t* px, half_t* cols, int B, int C, int Hi, int Wi, int ps, int stride, int gh, int gw, int Kpad, hipStream_t s);
+hipError_t ia2p_launch_vit_embed(const half_t* patches, const half_t* cls, const half_t* pos, const half_t* stem_g, const half_t* stem_b, const half_t* pre_g, const half_t* pre_b,
+                                 half_t* x, float* stats, int B, int T, int H, float eps, hipStream_t s);
+hipError_t ia2p_launch_vit_project(const half_t* X, const half_t* W, float* out, int B, int N, int K, hipStream_t s);
 hipError_t ia2p_launch_ip_attn_map(const half_t* Q, int ldq, const half_t* Kip, int ldk, half_t* out, int B, int heads, int Nq, int ntok, hipStream_t s);
 hipError_t ia2p_launch_touch(const void* p, size_t bytes, unsigned* sink, hipStream_t s);
 hipError_t ia2p_launch_pack_conv(const half_t* src, half_t* dst, int Co, int Ci, hipStream_t s);      // [Co][Ci][3][3] -> [Co][tap][Ci]

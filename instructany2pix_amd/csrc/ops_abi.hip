@@ -323,5 +323,12 @@ ia2p_status ia2p_linear_small(void* stream, const void* X, const void* W, const 
   hipError_t e = ia2p_launch_linear_small((const half_t*)X, K, (const half_t*)W, (const half_t*)bias, nullptr, 0, (half_t*)out, N, M, N, K, silu_in, silu_out, (hipStream_t)stream);
   RET_HIP(e, "linear_small");
 }
+ia2p_status ia2p_attention_full(void* stream, const void* qkv, void* out, const void* bias_k, const void* bias_v, int B, int T, int heads, int D) {
+  if (!qkv || !out || B < 1 || T < 1 || heads < 1 || (!bias_k) != (!bias_v)) return fail(nullptr, IA2P_ERR_INVALID, "attention_full: bad argument");
+  if ((D != 64 && D != 80) || T + (bias_k ? 1 : 0) > ia2p_full_attention_max_keys() || (size_t)B * heads > 65535)
+    return fail(nullptr, IA2P_ERR_SHAPE, "attention_full: D=%d (64 or 80), %d keys (<= %d)", D, T + (bias_k ? 1 : 0), ia2p_full_attention_max_keys());
+  hipError_t e = ia2p_launch_full_attention((const half_t*)qkv, (half_t*)out, (const half_t*)bias_k, (const half_t*)bias_v, B, T, heads, D, (hipStream_t)stream);
+  RET_HIP(e, "attention_full");
+}
 
 }  // extern "C"

@@ -1,0 +1,37 @@
+// One pre-LayerNorm transformer block on op_gemm, shared by the CLIP text executor (clip_engine.hip) and the ViT executor (vit_engine.hip):
+// QKV GEMM with the first LayerNorm folded, the caller's attention launch, out-proj + residual, fc1 with the second LayerNorm folded + activation,
+// fc2 + residual. No LayerNorm launches: row statistics travel from each residual GEMM's epilogue to the next folded GEMM (as in the UNet).
+#pragma once
+#include "engine_rt.h"
+
+// arena offsets of a block: parameters as loaded (wqkv / bqkv: q, k, v rows stacked) and what xf_fold derives from them
+struct CLayer { size_t ln1g, ln1b, wqkv, bqkv, wo, bo, ln2g, ln2b, w1, b1, w2, b2, fqkv, cs1, lb1, f1, cs2, lb2; };
+
+// gamma-folded copies of the two LayerNorm-consuming weights of every block (+ column sums and folded biases)
+inline hipError_t xf_fold(RunCtx* c, const std::vector<CLayer>& layers, int H, int I, hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  auto Hp = [&](size_t off) { return c->arena + off; };
+  auto Fp = [&](size_t off) { return (float*)(c->arena + off); };
+  for (const CLayer& l : layers) {
+    if (e == hipSuccess) e = ia2p_launch_fold_ln(Hp(l.wqkv), Hp(l.ln1g), Hp(l.ln1b), Hp(l.bqkv), Hp(l.fqkv), Fp(l.cs1), Fp(l.lb1), 3 * H, H, stream);
+    if (e == hipSuccess) e = ia2p_launch_fold_ln(Hp(l.w1), Hp(l.ln2g), Hp(l.ln2b), Hp(l.b1), Hp(l.f1), Fp(l.cs2), Fp(l.lb2), I, H, stream);
+  }
+  return e;
+}
+
+// x [M, H] is updated in place; st holds its row statistics in `slots` slots on entry and on exit. attn(): qkv [M, 3H] -> att [M, H].
+template <class Attn>
+inline void xf_layer(RunCtx* c, const CLayer& l, half_t* x, half_t* qkv, half_t* att, half_t* ff, float* st, int& slots, int M, int H, int I, float eps, int act, Attn&& attn) {
+  auto Fp = [&](size_t off) { return (const float*)(c->arena + off); };
+  {
+    const LnIn ln{st, slots, Fp(l.cs1), Fp(l.lb1), eps};
+    op_gemm(c, x, H, W_(c, l.fqkv), nullptr, nullptr, 0, qkv, 3 * H, M, 3 * H, H, 0, 0, 0, 0, 0, &ln);
+  }
+  attn();
+  op_gemm(c, att, H, W_(c, l.wo), W_(c, l.bo), x, H, x, H, M, H, H, 0, 0, 0, 0, 0, nullptr, st, &slots);
+  {
+    const LnIn ln{st, slots, Fp(l.cs2), Fp(l.lb2), eps};
+    op_gemm(c, x, H, W_(c, l.f1), nullptr, nullptr, 0, ff, I, M, I, H, 0, 0, 0, 0, 0, &ln, nullptr, nullptr, act);
+  }
+  op_gemm(c, ff, I, W_(c, l.w2), W_(c, l.b2), x, H, x, H, M, H, I, 0, 0, 0, 0, 0, nullptr, st, &slots);
+}

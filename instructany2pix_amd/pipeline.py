@@ -102,12 +102,14 @@ class InstructAny2PixPipeline:
                  vae_encode: Optional[Callable] = None, vae_decode: Optional[Callable] = None, clip_embeddings_dim: int = 1024,
                  refiner_unet: Optional[HipUNet2DConditionModel] = None, refiner_text_encoder: Optional[Callable] = None, prior=None,
                  refiner_handoff: str = "image", vae=None, llm=None, llm_tokenizer: Optional[Callable] = None,
-                 modality_encoder: Optional[Callable] = None):
+                 modality_encoder: Optional[Callable] = None, imagebind=None):
         # llm: a HipInstructAny2PixLM (reference :117 `self.any2pix_lm`; built with `load_in_4bit=True` it computes from 4-bit weights as the
         # reference's `from_pretrained(..., load_in_4bit=True)` model does, nothing changes here) with its tokenizer (:126 `self.any2pix_tokenizer`, injected: the
         # sentencepiece model is checkpoint data); modality_encoder(entry) -> [1024] embedding of an mm_data entry (reference :155-166:
-        # ImageBind, which stays outside; an entry may carry its vector directly as entry["embed"])
+        # ImageBind; an entry may carry its vector directly as entry["embed"]); imagebind: a HipImageBindModel (reference :118-121 `self.model_imb`) that
+        # encodes the entries' files itself when neither of the two is given
         self.any2pix_lm, self.any2pix_tokenizer, self.modality_encoder = llm, llm_tokenizer, modality_encoder
+        self.model_imb = imagebind
         self._text_encoder, self._refiner_text_encoder = text_encoder, refiner_text_encoder
         # vae: a HipAutoencoderKL shared by every pipeline (in place of the vae_encode / vae_decode hooks): base images in, images out
         # how the base result reaches the refiner: "image" = the reference's route (decode, 8-bit image, VAE re-encode with a posterior
@@ -198,15 +200,21 @@ class InstructAny2PixPipeline:
     # ---- the instruction LLM (reference :151-279) ---------------------------------------------------------------------------
     def _modality_embeds(self, mm_data):
         """:154-168: one 1024-d vector per mm_data entry, normalised to norm 20 (host fp32, as the reference's CPU ImageBind run leaves them)"""
-        all_tensors = []
-        for r in mm_data:
+        all_tensors, files = [None] * len(mm_data), {}
+        for i, r in enumerate(mm_data):
             if r.get("embed") is not None:
-                res = torch.as_tensor(r["embed"])
+                all_tensors[i] = torch.as_tensor(r["embed"])
             elif self.modality_encoder is not None:
-                res = self.modality_encoder(r)
+                all_tensors[i] = self.modality_encoder(r)
+            elif self.model_imb is not None:
+                files.setdefault(r["type"], []).append(i)      # the entries of one type go through their tower as one batch
             else:
                 raise ValueError("an mm_data entry needs entry['embed'] or the pipeline built with modality_encoder=")
-            all_tensors.append(res.detach().float().cpu().reshape(1, -1))
+        for kind, idx in files.items():
+            from .imagebind import encode_mm_entries
+            for i, row in zip(idx, encode_mm_entries(self.model_imb, kind, [mm_data[i]["fname"] for i in idx])):
+                all_tensors[i] = row
+        all_tensors = [t.detach().float().cpu().reshape(1, -1) for t in all_tensors]
         if not all_tensors:
             raise ValueError("forward_llm needs at least one mm_data entry (the reference's torch.cat of none fails the same way)")
         aux_info = torch.cat(all_tensors)

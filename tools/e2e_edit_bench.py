@@ -5,12 +5,13 @@ encode -> embedding prior (CLIP ViT-H text + GPT-2 medium) -> encode_prompt (CLI
 -> 25-step IP-Adapter guided CFG sampling (B_eff=2) -> VAE decode + 8-bit hand-over -> SDXL-refiner img2img (strength 0.5 of 50 steps, CFG)
 -> VAE decode -> image out (8-bit codec, uint8 back to the host). The request's conditioning comes from `forward_llm`: the instruction LLM at full
 size (Vicuna-7B shape) prefills the prompt and generates 100 tokens on the HIP engine, `vae_predictor_image` reads the hidden rows. Two stand-ins
-remain: the ImageBind vectors of the mm_data entries are seeded 1024-d noise (ImageBind stays outside), and, because synthetic weights cannot
+remain: the ImageBind vectors of the mm_data entries are seeded 1024-d noise unless --imagebind is given (then the entries name PNG files that
+`imagebind_huge`-sized towers with seeded weights encode on the HIP path, timed as their own stage), and, because synthetic weights cannot
 speak, the TOKEN CHOSEN at each step follows a script ("[ caption ] <base> <video> <im_gen> <video> </s>", 100 tokens) instead of the sampled one; every step's
 engine work, its logits and its sampling arithmetic still run.
 Prints per-stage wall times (stream-synchronised) after one warm-up request.
 
-    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)"""
+    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4] [--imagebind]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)"""
 import argparse
 import os
 import sys
@@ -37,6 +38,7 @@ from stub_llm_tokenizer import ADDED_TOKENS, StubLlamaTokenizer
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--llm-bits", type=int, default=16, choices=(16, 4))
 _ap.add_argument("--llm-quant-type", default="fp4", choices=("fp4", "nf4"))
+_ap.add_argument("--imagebind", action="store_true", help="encode the mm_data entries' files with the HIP ImageBind towers instead of seeded vectors")
 ARGS = _ap.parse_args()
 DEV = "cuda:0"
 PX = int(os.environ.get("PX", 1024))
@@ -87,8 +89,19 @@ def scripted_sample_next(logits, *a, **k):
 llm_mod.sample_next = scripted_sample_next
 mm_data = [{"type": "image", "fname": "base.png", "image": image, "embed": torch.randn(1024, generator=g)},
            {"type": "image", "fname": "style.png", "image": image, "embed": torch.randn(1024, generator=g)}]      # (either may be chosen as the base)
+imb = None
+if ARGS.imagebind:              # the entries carry files instead of vectors: `_modality_embeds` runs them through the vision tower as one batch
+    import tempfile
+    from instructany2pix_amd.imagebind import HipImageBindModel, imagebind_huge_config, imagebind_param_specs
+    imb = HipImageBindModel(imagebind_huge_config(), DEV, modalities=("vision",))
+    imb.load_state_dict(iter_synthetic(imagebind_param_specs(imb.config, ("vision",)), 13, DEV, torch.float16))
+    _dir = tempfile.mkdtemp(prefix="ia2p_e2e_")
+    for r in mm_data:
+        r["fname"] = os.path.join(_dir, r["fname"])
+        image.save(r["fname"])
+        del r["embed"]
 pipe = InstructAny2PixPipeline(unet=base, ip_ckpt=ck, device=DEV, clip_embeddings_dim=1024, refiner_unet=ref, prior=prior, vae=vae,
-                               llm=lm, llm_tokenizer=ltok,
+                               llm=lm, llm_tokenizer=ltok, imagebind=imb,
                                text_encoder=lambda **k: timed("encode_prompt(base, inversion '')", lambda: enc.encode_prompt(**k)),
                                refiner_text_encoder=lambda **k: timed("encode_prompt(refiner)", lambda: enc_ref.encode_prompt(**k)))
 if os.environ.get("TUNE", "1") == "1":      # measure kernel plans for the three UNet shapes of a request (what bench.py does for its shape)
@@ -113,6 +126,8 @@ _wrap(pipe.pipe_inversion, "_vae_encode", "vae_encode")
 _wrap(pipe.pipe, "_vae_decode", "vae_decode (hand-over + 2 outputs)")
 _wrap(pipe.pipe.image_processor, "postprocess", "image_out")
 _wrap(pipe.ip_adapter_xl, "generate", "guided sampling loop (25 x B_eff=2, incl. image-token projection)")
+if imb is not None:
+    _wrap(pipe, "_modality_embeds", "ImageBind (2 PNG files: load, transform, vision tower; inside forward_llm)")
 _wrap(pipe, "forward_llm", "LLM (forward_llm: prefill + 100 tokens + predictor heads)")
 if getattr(pipe, "model", None) is not None:
     _wrap(pipe.model, "generate_diffusion", "embedding prior")
@@ -128,5 +143,6 @@ for rnd in range(2):            # request 0 warms up (workspaces, kernel plans f
     non_refined, refined, msg = pipe("add <video> to <video> and turn the fox blue", mm_data, num_inference_steps=25, cfg=10, refinement=0.5, output_type="pil")
     torch.cuda.synchronize(); total = (time.perf_counter() - t0) * 1e3
     assert msg == "SUCCESS!" and all(isinstance(o, list) and o[0].size == (PX, PX) and o[0].mode == "RGB" for o in (non_refined, refined))
+    outer = sum(v for k, v in stages.items() if not k.startswith("ImageBind"))      # (the ImageBind stage is part of forward_llm's)
     print(f"request {rnd}: {total:.0f} ms total; stages (ms): " + ", ".join(f"{k} {v:.1f}" for k, v in stages.items())
-          + f", host glue / the rest {total - sum(stages.values()):.0f}", flush=True)
+          + f", host glue / the rest {total - outer:.0f}", flush=True)
