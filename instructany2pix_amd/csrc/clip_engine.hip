@@ -128,11 +128,7 @@ static ia2p_status clip_check(ia2p_clip* c, int B, int T) {
 }
 size_t ia2p_clip_workspace_bytes(ia2p_clip* c, int B, int T) {
   if (!c || clip_check(c, B, T) != IA2P_OK) return 0;
-  c->dry = true; c->failed = false; c->record = false;
-  c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
-  (void)clip_run(c, nullptr, nullptr, B, T, nullptr, (half_t*)1, c->cfg.vocab_size ? (half_t*)1 : nullptr);
-  c->dry = false;
-  return c->failed ? 0 : c->ws.high + 256;
+  return pass_dry(c, [&] { return clip_run(c, nullptr, nullptr, B, T, nullptr, (half_t*)1, c->cfg.vocab_size ? (half_t*)1 : nullptr); });
 }
 static ia2p_status clip_encode_impl(ia2p_clip* c, void* stream, const int32_t* ids, const half_t* embeds, int B, int T, void* hid2, void* last, void* pooled,
                                     void* ws, size_t ws_bytes) {
@@ -144,22 +140,11 @@ static ia2p_status clip_encode_impl(ia2p_clip* c, void* stream, const int32_t* i
     st = clip_fold(c, (hipStream_t)stream, false);
     if (st != IA2P_OK) return st;
   }
-  const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
-  const size_t usable = ws_bytes - (base - (uintptr_t)ws);
+  st = pass_enter(c, stream, ws, ws_bytes);
+  if (st != IA2P_OK) return st;
   const int key = (last || pooled) ? 1 : 2;
-  if (c->wseq_key != key) {
-    c->wseq.clear();
-    c->dry = true; c->record = true; c->failed = false;
-    c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
-    (void)clip_run(c, nullptr, nullptr, B, T, nullptr, key == 1 ? (half_t*)1 : nullptr, nullptr);
-    c->dry = false; c->record = false; c->wseq_key = key;
-  }
-  c->widx = 0; c->dry = false; c->failed = false; c->stream = (hipStream_t)stream;
-  c->ws.reset(usable); c->ws_base = (char*)base;
-  st = clip_run(c, ids, embeds, B, T, (half_t*)hid2, (half_t*)last, (half_t*)pooled);
-  if (c->failed && st == IA2P_OK) st = IA2P_ERR_HIP;
-  if (c->failed && c->err == "workspace too small") st = IA2P_ERR_NOMEM;
-  return st;
+  pass_record(c, key, [&] { return clip_run(c, nullptr, nullptr, B, T, nullptr, key == 1 ? (half_t*)1 : nullptr, nullptr); });
+  return pass_leave(c, clip_run(c, ids, embeds, B, T, (half_t*)hid2, (half_t*)last, (half_t*)pooled));
 }
 ia2p_status ia2p_clip_encode(ia2p_clip* c, void* stream, const int32_t* ids, int B, int T, void* hid2, void* last, void* pooled, void* ws, size_t ws_bytes) {
   if (!c || !ids || !ws || (!hid2 && !last && !pooled)) return fail(c, IA2P_ERR_INVALID, "clip_encode: null argument");

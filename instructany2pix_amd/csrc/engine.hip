@@ -169,14 +169,8 @@ static ia2p_status plan_pass(ia2p_ctx* c, size_t fold_base, size_t* raw_elems, s
   c->ae1w = P.mat("add_embedding.linear_1.weight", T, g.projection_class_embeddings_input_dim); c->ae1b = P.vec("add_embedding.linear_1.bias", T);
   c->ae2w = P.mat("add_embedding.linear_2.weight", T, T); c->ae2b = P.vec("add_embedding.linear_2.bias", T);
   // all time_emb_proj matrices stacked into one [sum Cout, T] projection
-  int nres = 0, tot = 0;
-  {
-    int skipn = 0;
-    for (int i = 0; i < n; ++i) { nres += g.layers_per_block; tot += g.layers_per_block * ch[i]; }
-    tot += 2 * ch[n - 1];
-    for (int i = 0; i < n; ++i) tot += (g.layers_per_block + 1) * ch[n - 1 - i];
-    (void)skipn; (void)nres;
-  }
+  int tot = 2 * ch[n - 1];
+  for (int i = 0; i < n; ++i) tot += g.layers_per_block * ch[i] + (g.layers_per_block + 1) * ch[n - 1 - i];
   c->tw_all = P.take((size_t)tot * T);
   c->tb_all = P.take(tot);
   c->embed_lo = c->te1w; c->embed_hi = P.cur;      // [time/add embedding MLPs | stacked time_emb_proj]: the first weights a pass reads
@@ -276,7 +270,8 @@ static void run_ffn(RunCtx* c, GemmArgs& a, GemmArgs& b, int* stat_slots_b) {
   set_prefetch(c, b, b.W, (size_t)b.N * b.K * sizeof(half_t));
   { RoleScope role(c, ROLE_FF_IN); run_gemm(c, a, false, "ff.net.0", 2.0 * a.M * (double)a.N * a.K, gemm_bytes(a.M, a.N, a.K, 1, false)); }
   RoleScope role(c, ROLE_FF_OUT);
-  run_gemm(c, b, false, "ff.net.2", 2.0 * b.M * (double)b.N * b.K, gemm_bytes(b.M, b.N, b.K, 0, true), stat_slots_b);
+  RunOpt r; r.stat_slots = stat_slots_b;
+  run_gemm(c, b, false, "ff.net.2", 2.0 * b.M * (double)b.N * b.K, gemm_bytes(b.M, b.N, b.K, 0, true), r);
 }
 
 struct Fwd {
@@ -290,6 +285,7 @@ struct Fwd {
   // GroupNorm statistics of live activation tensors (keyed by workspace offset): left by the producer's epilogue, read by the GroupNorm-fused convolution that consumes
   // the tensor -- possibly much later (the skips of the down path) --, released with the tensor
   std::unordered_map<size_t, GnStats> gst;
+  int gn_mode = 0;             // GroupNorm mode of this pass (run_forward): 0 launches, 1 fused into the convolutions, 2 the fused path's unfused twin, 3 the autotune pass's sizing
   bool gn_on = false;
   std::unordered_map<int, int> kv_inlaunch;      // context K/V column (TBlock::kv_col) -> 1: left for the block's fused QKV + self-attention launch to project (plan_context_kv); 2: done
   bool tune_like = false;      // the autotune pass (or the dry pass that sizes the workspace for it): GroupNorm launches, plus what tune_site needs to time the fused forms beside them
@@ -302,18 +298,19 @@ static void act_free(Fwd& f, T2 t) {      // release an activation tensor and it
   wsfree(f.c, t);
 }
 
-// autotune pass: times a GroupNorm launch in place and leaves the figure for the tune_site call of the convolution behind it
+// autotune pass: times a GroupNorm launch in place, for the tune_site call of the convolution behind it (ConvGn::gn_ms)
 struct TuneGnTimer {
   RunCtx* c; hipEvent_t e0{}, e1{}; bool on;
   explicit TuneGnTimer(RunCtx* c_) : c(c_), on(c_->tuning && !c_->dry && !c_->failed && c_->gn_fuse != 0) {
     if (on) { e0 = get_event(c); e1 = get_event(c); (void)hipEventRecord(e0, c->stream); }
   }
-  void stop() {
-    if (!on) return;
+  float stop() {      // ms; 0: not timed
+    if (!on) return 0.f;
     float ms = 0.f;
-    if (hipEventRecord(e1, c->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->tune_gn_ms = ms;
+    if (!(hipEventRecord(e1, c->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)) ms = 0.f;
     c->evpool.push_back(e0); c->evpool.push_back(e1);
     on = false;
+    return ms;
   }
 };
 struct RegionScope { RunCtx* c; int prev; RegionScope(RunCtx* c_, int r) : c(c_), prev(c_->region) { c->region = r; } ~RegionScope() { c->region = prev; } };
@@ -356,84 +353,77 @@ static GnStats gn_ensure_stats(Fwd& f, T2 t, int C, int HW) {
   return s;
 }
 
+// GroupNorm + SiLU over [x (c0 channels) | x2 (C - c0)] in front of a 3x3 convolution of a ResnetBlock2D, one of three ways: inside the convolution (`fusable`: the site is a
+// halo-staged one and g.s0 / g.s1 hold the producers' statistics); as the fused path's unfused twin (gn_mode 2: the SAME statistics, normalised by a pass of its own, then the
+// plain convolution); or as a GroupNorm launch. The autotune pass (`tune`; tune_like implies !gn_on, so only ever beside a GroupNorm launch) measures the site both ways: the
+// launch is timed, and g describes the fused form -- raw tensor(s) with their statistics -- for tune_site. Fills g for op_conv3 and returns the normalised tensor the
+// convolution reads (none when fused: it reads x). stats_first: whether the autotune pass's statistics are allocated before the normalised tensor or behind it -- the
+// workspace is first-fit, the order of allocations decides ia2p_workspace_bytes, and the two convolutions of a block have always differed in it.
+static T2 gn_before_conv(Fwd& f, T2 x, const T2* x2t, int c0, int C, size_t gam, size_t bet, int HW, bool fusable, bool tune, bool stats_first, ConvGn& g) {
+  ia2p_ctx* c = f.c;
+  const int M = f.B * HW;
+  const half_t* x2 = x2t ? x2t->p : nullptr;
+  g.X1b = x2; g.C0 = c0; g.gamma = W_(c, gam); g.beta = W_(c, bet); g.eps = c->cfg.norm_eps; g.groups = c->groups;
+  g.fused = fusable && f.gn_mode != 2;
+  if (g.fused) return T2{(size_t)-1, nullptr};
+  tune = tune && !fusable;
+  auto tune_stats = [&] { g.tune = true; g.Xraw = x.p; g.s0 = gn_ensure_stats(f, x, c0, HW); if (x2t) g.s1 = gn_ensure_stats(f, *x2t, C - c0, HW); };
+  if (tune && stats_first) tune_stats();
+  T2 n = wsalloc(c, (size_t)M * C);
+  if (tune && !stats_first) tune_stats();
+  if (fusable) {
+    const GemmArgs::GnIn gi = gn_in_desc((const double*)g.s0.buf.p, g.s0.rows, x2 ? (const double*)g.s1.buf.p : nullptr, g.s1.rows, c0, C, g.gamma, g.beta, g.groups, g.eps, 1);
+    RoleScope role(c, ROLE_GROUPNORM);
+    ProfScope ps(c, PK_GN, 8.0 * M * C, 4.0 * M * C);
+    CHECK_LAUNCH(c, ia2p_launch_gn_apply_stats(x.p, c0, x2, C - c0, n.p, C, f.B, HW, C, gi, c->stream), "groupnorm (apply from producer statistics)");
+  } else {
+    TuneGnTimer tg(c);
+    op_gn(c, x.p, n.p, gam, bet, f.B, HW, C, g.eps, 1, f.gn_partial, x2, c0);
+    g.gn_ms = tg.stop();
+  }
+  return n;
+}
+
 // out_stats: the block's output feeds another GroupNorm-fusable convolution (the next ResnetBlock2D, or -- as a skip -- one of the up path): its statistics are taken
 static T2 run_resnet(Fwd& f, const Resnet& r, T2 x, int H, int Wd, const T2* x2t = nullptr, int cx = 0, bool out_stats = false) {
   const half_t* x2 = x2t ? x2t->p : nullptr;
   const bool two = x2t != nullptr;
   ia2p_ctx* c = f.c;
   RegionScope rs(c, PR_CONV_BLOCK);
-  const int HW = H * Wd, M = f.B * HW;
+  const int HW = H * Wd, M = f.B * HW, c0 = two ? cx : r.cin;
   // norm1 + SiLU + conv1: inside the convolution when the site is a halo-staged one and the producers left their statistics (conv_halo_kernel.h, GN = 1)
   // (first by shape alone -- does the plan give conv1 a halo-staged tile? -- then with the statistics, fetched or computed only when the site can use them)
   GnStats probe; probe.rows = gn_fallback_rows(HW);
-  GnStats sx, sx2;
-  bool fuse1 = probe.ok() && gn_conv_fusable(f, H, Wd, r.cin, r.cout, 0, 0, probe, two ? &probe : nullptr, two ? cx : r.cin);
+  ConvGn g1, g2;
+  bool fuse1 = probe.ok() && gn_conv_fusable(f, H, Wd, r.cin, r.cout, 0, 0, probe, two ? &probe : nullptr, c0);
   if (fuse1) {
-    sx = gn_ensure_stats(f, x, two ? cx : r.cin, HW);
-    if (two) sx2 = gn_ensure_stats(f, *x2t, r.cin - cx, HW);
-    fuse1 = gn_conv_fusable(f, H, Wd, r.cin, r.cout, 0, 0, sx, two ? &sx2 : nullptr, two ? cx : r.cin);
+    g1.s0 = gn_ensure_stats(f, x, c0, HW);
+    if (two) g1.s1 = gn_ensure_stats(f, *x2t, r.cin - cx, HW);
+    fuse1 = gn_conv_fusable(f, H, Wd, r.cin, r.cout, 0, 0, g1.s0, two ? &g1.s1 : nullptr, c0);
   }
   GnWant w1{HW};
   const bool cat = r.shortcut && c->sc_fuse;      // conv2(h) + conv_shortcut(x) as ONE implicit GEMM (K = 9 cout + cin): no shortcut launch, no xs round trip
+  const int cat2 = cat ? c0 : 0, cat3 = cat && two ? r.cin - cx : 0;      // ... its appended 1x1 blocks: x [| x2]
   // (conv1's statistics are wanted when conv2 can take them: its plan is a halo-staged one)
-  const bool want1 = f.gn_on && probe.ok() && gn_conv_fusable(f, H, Wd, r.cout, r.cout, cat ? (two ? cx : r.cin) : 0, cat && two ? r.cin - cx : 0, probe, nullptr, r.cout);
+  const bool want1 = f.gn_on && probe.ok() && gn_conv_fusable(f, H, Wd, r.cout, r.cout, cat2, cat3, probe, nullptr, r.cout);
+  // autotune pass: both convolutions are measured both ways -- GroupNorm launch + the best plain plan against the fused launch on the raw tensor(s) with their statistics
+  const bool tune = f.tune_like && probe.ok() && H % 16 == 0 && Wd % 16 == 0;
   T2 hh = wsalloc(c, (size_t)M * r.cout);
-  const bool twin = (c->gn_dry_mode >= 0 ? c->gn_dry_mode : c->gn_fuse) == 2;      // the fused path's unfused twin: the SAME statistics, normalised by a pass of its own, then the plain convolution
-  auto apply_stats = [&](const half_t* a0, int c0, const half_t* a1, const GnStats& s0, const GnStats& s1, size_t gam, size_t bet, int C, half_t* y) {
-    const GemmArgs::GnIn g = gn_in_desc((const double*)s0.buf.p, s0.rows, a1 ? (const double*)s1.buf.p : nullptr, s1.rows, c0, C, W_(c, gam), W_(c, bet), c->groups, c->cfg.norm_eps, 1);
-    RoleScope role(c, ROLE_GROUPNORM);
-    ProfScope ps(c, PK_GN, 8.0 * M * C, 4.0 * M * C);
-    CHECK_LAUNCH(c, ia2p_launch_gn_apply_stats(a0, c0, a1, C - c0, y, C, f.B, HW, C, g, c->stream), "groupnorm (apply from producer statistics)");
-  };
-  if (fuse1 && twin) {
-    T2 n1 = wsalloc(c, (size_t)M * r.cin);
-    apply_stats(x.p, two ? cx : r.cin, x2, sx, sx2, r.n1g, r.n1b, r.cin, n1.p);
-    op_conv3(c, n1.p, f.B, H, Wd, r.cin, W_(c, r.w1), W_(c, r.b1), r.cout, 1, 0, c->dry ? nullptr : f.temb_all.p + r.temb_off, c->temb_total, nullptr, hh.p, 1, nullptr, 0, nullptr, 0, nullptr, want1 ? &w1 : nullptr);
-    wsfree(c, n1);
-  } else if (fuse1) {
-    ConvGn g;
-    g.fused = true; g.X1b = x2; g.C0 = two ? cx : r.cin; g.s0 = sx; g.s1 = sx2; g.gamma = W_(c, r.n1g); g.beta = W_(c, r.n1b); g.eps = c->cfg.norm_eps; g.groups = c->groups;
-    op_conv3(c, x.p, f.B, H, Wd, r.cin, W_(c, r.w1), W_(c, r.b1), r.cout, 1, 0, c->dry ? nullptr : f.temb_all.p + r.temb_off, c->temb_total, nullptr, hh.p, 1, nullptr, 0, nullptr, 0, &g, want1 ? &w1 : nullptr);
-  } else {
-    T2 n1 = wsalloc(c, (size_t)M * r.cin);
-    // autotune pass: the site is measured both ways -- this GroupNorm launch + the best plain plan against the fused launch on the raw tensor(s) with their statistics
-    const bool tune = f.tune_like && probe.ok() && H % 16 == 0 && Wd % 16 == 0;
-    ConvGn tg1;
-    if (tune) {
-      tg1.tune = true; tg1.Xraw = x.p; tg1.X1b = x2; tg1.C0 = two ? cx : r.cin; tg1.gamma = W_(c, r.n1g); tg1.beta = W_(c, r.n1b); tg1.eps = c->cfg.norm_eps; tg1.groups = c->groups;
-      tg1.s0 = gn_ensure_stats(f, x, tg1.C0, HW);
-      if (two) tg1.s1 = gn_ensure_stats(f, *x2t, r.cin - cx, HW);
-    }
-    TuneGnTimer tg(c);
-    op_gn(c, x.p, n1.p, r.n1g, r.n1b, f.B, HW, r.cin, c->cfg.norm_eps, 1, f.gn_partial, x2, cx);
-    tg.stop();
-    op_conv3(c, n1.p, f.B, H, Wd, r.cin, W_(c, r.w1), W_(c, r.b1), r.cout, 1, 0, c->dry ? nullptr : f.temb_all.p + r.temb_off, c->temb_total, nullptr, hh.p, 1, nullptr, 0, nullptr, 0, tune ? &tg1 : nullptr,
-             want1 ? &w1 : nullptr);
-    wsfree(c, n1);
-  }
-  const GnStats sh = w1.out;
-  const bool fuse2 = want1 && gn_conv_fusable(f, H, Wd, r.cout, r.cout, cat ? (two ? cx : r.cin) : 0, cat && two ? r.cin - cx : 0, sh, nullptr, r.cout);
-  ConvGn g2;
-  g2.fused = fuse2 && !twin; g2.C0 = r.cout; g2.s0 = sh; g2.gamma = W_(c, r.n2g); g2.beta = W_(c, r.n2b); g2.eps = c->cfg.norm_eps; g2.groups = c->groups;
-  T2 n2{(size_t)-1, nullptr};
-  const bool tune2 = f.tune_like && probe.ok() && H % 16 == 0 && Wd % 16 == 0;      // (autotune pass: conv2 measured both ways, as conv1 above; hh stays alive for it)
-  if (tune2) {
-    g2.tune = true; g2.Xraw = hh.p;
-    g2.s0 = gn_ensure_stats(f, hh, r.cout, HW);
-  }
-  if (!fuse2 || twin) {
-    n2 = wsalloc(c, (size_t)M * r.cout);
-    if (fuse2) apply_stats(hh.p, r.cout, nullptr, sh, GnStats{}, r.n2g, r.n2b, r.cout, n2.p);
-    else {
-      TuneGnTimer tg(c);
-      op_gn(c, hh.p, n2.p, r.n2g, r.n2b, f.B, HW, r.cout, c->cfg.norm_eps, 1, f.gn_partial);
-      tg.stop();
-    }
-    if (!tune2) wsfree(c, hh);
-  }
-  const half_t* in2 = g2.fused ? hh.p : n2.p;
+  T2 n1 = gn_before_conv(f, x, x2t, c0, r.cin, r.n1g, r.n1b, HW, fuse1, tune, false, g1);
+  ConvOpt o1;
+  o1.rowvec = c->dry ? nullptr : f.temb_all.p + r.temb_off; o1.rowvec_ld = c->temb_total;
+  o1.gn = &g1; o1.gw = want1 ? &w1 : nullptr;
+  op_conv3(c, g1.fused ? x.p : n1.p, f.B, H, Wd, r.cin, W_(c, r.w1), W_(c, r.b1), r.cout, hh.p, o1);
+  wsfree(c, n1);
+  // norm2 + SiLU + conv2, the same three ways, on the statistics conv1's epilogue left
+  g2.s0 = w1.out;
+  const bool fuse2 = want1 && gn_conv_fusable(f, H, Wd, r.cout, r.cout, cat2, cat3, g2.s0, nullptr, r.cout);
+  T2 n2 = gn_before_conv(f, hh, nullptr, r.cout, r.cout, r.n2g, r.n2b, HW, fuse2, tune, true, g2);
+  if (!g2.fused && !tune) wsfree(c, hh);      // (autotune pass: hh stays alive, the fused candidates read it)
   GnWant w2{HW};
-  GnWant* gw2 = f.gn_on && out_stats && ia2p_plan_any_gn(M) ? &w2 : nullptr;      // (only when some 3x3 site of this resolution level fuses its GroupNorm under the measured plans)
+  ConvOpt o2;
+  o2.gn = &g2;
+  o2.gw = f.gn_on && out_stats && ia2p_plan_any_gn(M) ? &w2 : nullptr;      // (only when some 3x3 site of this resolution level fuses its GroupNorm under the measured plans)
   T2 xs{(size_t)-1, nullptr};
   const half_t* resid = x.p;
   if (r.shortcut && !cat) {
@@ -442,13 +432,13 @@ static T2 run_resnet(Fwd& f, const Resnet& r, T2 x, int H, int Wd, const T2* x2t
     resid = xs.p;
   }
   T2 out = wsalloc(c, (size_t)M * r.cout);
-  if (cat && two) op_conv3(c, in2, f.B, H, Wd, r.cout, W_(c, r.wcat), W_(c, r.bcat), r.cout, 1, 0, nullptr, 0, nullptr, out.p, 1, x.p, cx, x2, r.cin - cx, &g2, gw2);
-  else if (cat) op_conv3(c, in2, f.B, H, Wd, r.cout, W_(c, r.wcat), W_(c, r.bcat), r.cout, 1, 0, nullptr, 0, nullptr, out.p, 1, x.p, r.cin, nullptr, 0, &g2, gw2);
-  else op_conv3(c, in2, f.B, H, Wd, r.cout, W_(c, r.w2), W_(c, r.b2), r.cout, 1, 0, nullptr, 0, c->dry ? nullptr : resid, out.p, 1, nullptr, 0, nullptr, 0, &g2, gw2);
-  if (g2.fused) wsfree(c, hh); else { wsfree(c, n2); if (tune2) act_free(f, hh); }
-  if (sh.buf.off != (size_t)-1) wsfree(c, sh.buf);
+  if (cat) { o2.X2 = x.p; o2.Cin2 = cat2; o2.X3 = x2; o2.Cin3 = cat3; }
+  else o2.residual = c->dry ? nullptr : resid;
+  op_conv3(c, g2.fused ? hh.p : n2.p, f.B, H, Wd, r.cout, W_(c, cat ? r.wcat : r.w2), W_(c, cat ? r.bcat : r.b2), r.cout, out.p, o2);
+  if (g2.fused) wsfree(c, hh); else { wsfree(c, n2); if (tune) act_free(f, hh); }
+  if (w1.out.buf.off != (size_t)-1) wsfree(c, w1.out.buf);
   if (r.shortcut && !cat) wsfree(c, xs);
-  if (gw2) gst_put(f, out, w2.out);
+  if (o2.gw) gst_put(f, out, w2.out);
   return out;
 }
 
@@ -510,11 +500,11 @@ static void project_context(ia2p_ctx* c, const half_t* context, int L, int B, ha
   const int ctxd = c->cfg.cross_attention_dim;
   const int Lt = c->ip_enabled ? L - c->ip_tokens : L, Li = c->ip_enabled ? c->ip_tokens : 0;
   if (ncols < 0) ncols = c->kv_rows - col0;
-  const bool part = ncols != c->kv_rows;
-  if (part) c->plan_n = c->kv_rows;
-  op_gemm(c, context, ctxd, W_(c, c->kv_text_base + (size_t)col0 * ctxd), nullptr, nullptr, 0, kv_text ? kv_text + col0 : nullptr, c->kv_rows, B * Lt, ncols, ctxd, 0, Lt, L, 0);
-  if (part && Li) c->plan_n = c->kv_rows;
-  if (Li) op_gemm(c, context, ctxd, W_(c, c->kv_ip_base + (size_t)col0 * ctxd), nullptr, nullptr, 0, kv_ip ? kv_ip + col0 : nullptr, c->kv_rows, B * Li, ncols, ctxd, 0, Li, L, Lt);
+  GemmOpt o;      // rows of the text / image tokens of every batch element; a column range on the whole projection's plan
+  o.rpb = Lt; o.bstride = L; o.roff = 0; o.plan_n = ncols != c->kv_rows ? c->kv_rows : 0;
+  op_gemm(c, context, ctxd, W_(c, c->kv_text_base + (size_t)col0 * ctxd), nullptr, nullptr, 0, kv_text ? kv_text + col0 : nullptr, c->kv_rows, B * Lt, ncols, ctxd, o);
+  o.rpb = Li; o.roff = Lt;
+  if (Li) op_gemm(c, context, ctxd, W_(c, c->kv_ip_base + (size_t)col0 * ctxd), nullptr, nullptr, 0, kv_ip ? kv_ip + col0 : nullptr, c->kv_rows, B * Li, ncols, ctxd, o);
 }
 
 // does transformer block b of t, at HW tokens per image, take the fused QKV + self-attention launch? (workspace and arena offsets are 256-byte aligned: the dry pass, with
@@ -586,7 +576,6 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
   ia2p_ctx* c = f.c;
   RegionScope rs(c, PR_TRANSFORMER);
   const int HW = H * Wd, M = f.B * HW, C = t.c;
-  const int ctxd = c->cfg.cross_attention_dim;
   const int Lt = c->ip_enabled ? f.L - c->ip_tokens : f.L;
   const int Li = c->ip_enabled ? c->ip_tokens : 0;
   T2 n = wsalloc(c, (size_t)M * C);
@@ -602,7 +591,10 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
   auto F_ = [&](size_t off) { return (const float*)(c->arena + off); };
   const bool fold = c->ln_fold;
   if (!fold) st = nullptr;
-  { RoleScope role(c, ROLE_PROJ_IO); op_gemm(c, n.p, C, W_(c, t.win), W_(c, t.bin), nullptr, 0, tk.p, C, M, C, C, 0, 0, 0, 0, 0, nullptr, st, &slots); }
+  GemmOpt to_tk;      // a GEMM that writes the token stream leaves the row statistics of its output
+  to_tk.stats = st; to_tk.stat_slots = &slots;
+  auto folded = [](const LnIn& ln) { GemmOpt o; o.ln = &ln; return o; };      // a GEMM that reads LN(tk) as raw tk against the folded weights
+  { RoleScope role(c, ROLE_PROJ_IO); op_gemm(c, n.p, C, W_(c, t.win), W_(c, t.bin), nullptr, 0, tk.p, C, M, C, C, to_tk); }
   wsfree(c, n);
   T2 lnb = fold ? T2{(size_t)-1, nullptr} : wsalloc(c, (size_t)M * C);
   T2 qkv = wsalloc(c, (size_t)M * 3 * C), att = wsalloc(c, (size_t)M * C);
@@ -629,7 +621,7 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
       op_qkv_sattn(c, tk.p, C, W_(c, b.fqkv), &ln, M, C, sa, kv_here ? &ck : nullptr);
     } else if (fold) {
       const LnIn ln{st, slots, F_(b.cs1), F_(b.lb1), eps};
-      op_gemm(c, tk.p, C, W_(c, b.fqkv), nullptr, nullptr, 0, qkv.p, 3 * C, M, 3 * C, C, 0, 0, 0, 0, 0, &ln);
+      op_gemm(c, tk.p, C, W_(c, b.fqkv), nullptr, nullptr, 0, qkv.p, 3 * C, M, 3 * C, C, folded(ln));
     } else {
       op_ln(c, tk.p, lnb.p, b.ln1g, b.ln1b, M, C);
       op_gemm(c, lnb.p, C, W_(c, b.wqkv), nullptr, nullptr, 0, qkv.p, 3 * C, M, 3 * C, C);
@@ -638,7 +630,7 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
       op_attn(c, attn_desc(qkv.p, 3 * C, att.p, C, f.B, t.heads, HW, 1, AttnSeg{c->dry ? nullptr : qkv.p + C, c->dry ? nullptr : qkv.p + 2 * C, HW, 3 * C, HW, 1.f}));
     }
     }
-    { RoleScope role(c, ROLE_ATTN_OUT); op_gemm(c, att.p, C, W_(c, b.wo1), W_(c, b.bo1), tk.p, C, tk.p, C, M, C, C, 0, 0, 0, 0, 0, nullptr, st, &slots); }
+    { RoleScope role(c, ROLE_ATTN_OUT); op_gemm(c, att.p, C, W_(c, b.wo1), W_(c, b.bo1), tk.p, C, tk.p, C, M, C, C, to_tk); }
     // cross-attention (IPAttnProcessor2_0 :310-412 when the adapter is installed, else AttnProcessor2_0)
     {
       RoleScope role(c, ROLE_Q_XATTN);
@@ -652,7 +644,7 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
       if (fold) {
         const LnIn ln{st, slots, F_(b.cs2), F_(b.lb2), eps};
         if (fuse) op_qxattn(c, tk.p, C, W_(c, b.fq2), &ln, M, C, C, a);
-        else op_gemm(c, tk.p, C, W_(c, b.fq2), nullptr, nullptr, 0, qkv.p, C, M, C, C, 0, 0, 0, 0, 0, &ln);
+        else op_gemm(c, tk.p, C, W_(c, b.fq2), nullptr, nullptr, 0, qkv.p, C, M, C, C, folded(ln));
       } else {
         op_ln(c, tk.p, lnb.p, b.ln2g, b.ln2b, M, C);
         if (fuse) op_qxattn(c, lnb.p, C, W_(c, b.wq2), nullptr, M, C, C, a);
@@ -660,30 +652,35 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
       }
       if (!fuse) op_attn(c, a);
     }
-    { RoleScope role(c, ROLE_ATTN_OUT); op_gemm(c, att.p, C, W_(c, b.wo2), W_(c, b.bo2), tk.p, C, tk.p, C, M, C, C, 0, 0, 0, 0, 0, nullptr, st, &slots); }
+    { RoleScope role(c, ROLE_ATTN_OUT); op_gemm(c, att.p, C, W_(c, b.wo2), W_(c, b.bo2), tk.p, C, tk.p, C, M, C, C, to_tk); }
     // GEGLU feed-forward
     if (!fold) op_ln(c, tk.p, lnb.p, b.ln3g, b.ln3b, M, C);
     {
       const LnIn ln{st, slots, F_(b.cs3), F_(b.lb3), eps};
-      GemmArgs g1 = fold ? gemm_args(c, tk.p, C, W_(c, b.fff1), W_(c, b.bff1), nullptr, 0, ff.p, 4 * C, M, 8 * C, C, 1, 0, 0, 0, 0, &ln, nullptr, 0)
-                         : gemm_args(c, lnb.p, C, W_(c, b.wff1), W_(c, b.bff1), nullptr, 0, ff.p, 4 * C, M, 8 * C, C, 1, 0, 0, 0, 0, nullptr, nullptr, 0);
-      GemmArgs g2 = gemm_args(c, ff.p, 4 * C, W_(c, b.wff2), W_(c, b.bff2), tk.p, C, tk.p, C, M, C, 4 * C, 0, 0, 0, 0, 0, nullptr, st, 0);
+      GemmOpt o1, o2;
+      o1.geglu = 1; o1.ln = fold ? &ln : nullptr;
+      o2.stats = st;
+      GemmArgs g1 = gemm_args(c, fold ? tk.p : lnb.p, C, W_(c, fold ? b.fff1 : b.wff1), W_(c, b.bff1), nullptr, 0, ff.p, 4 * C, M, 8 * C, C, o1);
+      GemmArgs g2 = gemm_args(c, ff.p, 4 * C, W_(c, b.wff2), W_(c, b.bff2), tk.p, C, tk.p, C, M, C, 4 * C, o2);
       run_ffn(c, g1, g2, &slots);
     }
   }
   wsfree(c, stt); wsfree(c, lnb); wsfree(c, qkv); wsfree(c, att); wsfree(c, ff);
-  (void)ctxd;
   T2 out = wsalloc(c, (size_t)M * C);
   GnWant gw{HW};
   const bool want = f.gn_on && out_stats && ia2p_plan_any_gn(M);
-  { RoleScope role(c, ROLE_PROJ_IO); op_gemm(c, tk.p, C, W_(c, t.wout), W_(c, t.bout), x.p, C, out.p, C, M, C, C, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, 0, want ? &gw : nullptr); }
+  GemmOpt po;
+  po.gw = want ? &gw : nullptr;
+  { RoleScope role(c, ROLE_PROJ_IO); op_gemm(c, tk.p, C, W_(c, t.wout), W_(c, t.bout), x.p, C, out.p, C, M, C, C, po); }
   wsfree(c, tk);
   if (want) gst_put(f, out, gw.out);
   return out;
 }
 
 // kv_cached != nullptr: the context projections were computed before (ia2p_project_context) and are read from there
-static ia2p_status run_forward(ia2p_ctx* c, const half_t* sample, float timestep, const half_t* context, int L,
+// gn_mode: the GroupNorm mode of the pass -- the context's gn_fuse (0 launches, 1 fused, 2 the unfused twin), or, from ia2p_workspace_bytes, every one of them and
+// 3: the sizing pass of ia2p_autotune
+static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, float timestep, const half_t* context, int L,
                                const half_t* text_embeds, const half_t* time_ids, half_t* out, int B, int h, int w,
                                const half_t* kv_cached = nullptr, const float* timesteps = nullptr, const float* ip_scales = nullptr) {
   const ia2p_unet_config& g = c->cfg;
@@ -692,8 +689,8 @@ static ia2p_status run_forward(ia2p_ctx* c, const half_t* sample, float timestep
   const int pooled = Ain - g.num_time_ids * Ad;
   Fwd f{c, B, h, w, L, context, T2{(size_t)-1, nullptr}, nullptr, T2{(size_t)-1, nullptr}, T2{(size_t)-1, nullptr}};
   f.ip_scales = ip_scales;
-  const int gn_mode = c->gn_dry_mode >= 0 ? c->gn_dry_mode : c->gn_fuse;
-  f.tune_like = c->gn_fuse != 0 && (c->dry ? c->gn_dry_mode == 3 || (c->gn_dry_mode < 0 && c->tuning) : c->tuning);
+  f.gn_mode = gn_mode;
+  f.tune_like = c->gn_fuse != 0 && (c->dry && !c->record ? gn_mode == 3 : c->tuning);      // (a sizing pass takes its mode's word; a recording or real pass is what the context is doing)
   f.gn_on = gn_mode != 0 && gn_mode != 3 && !c->tuning;      // (the autotune pass measures the plain kernels: GroupNorm launches there)
 
   // GroupNorm partial sums (fp32) live at the front of the workspace
@@ -776,7 +773,9 @@ static ia2p_status run_forward(ia2p_ctx* c, const half_t* sample, float timestep
       T2 d = wsalloc(c, (size_t)B * Ho * Wo * st.rc);
       GnWant gw{Ho * Wo};
       const bool want = f.gn_on && ia2p_plan_any_gn(B * Ho * Wo);
-      op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, 2, 0, nullptr, 0, nullptr, d.p, 1, nullptr, 0, nullptr, 0, nullptr, want ? &gw : nullptr);
+      ConvOpt o;
+      o.stride = 2; o.gw = want ? &gw : nullptr;
+      op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, d.p, o);
       if (want) gst_put(f, d, gw.out);
       H = Ho; Wd = Wo; x = d;
       skips.push_back(x); skip_c.push_back(st.rc);
@@ -821,7 +820,9 @@ static ia2p_status run_forward(ia2p_ctx* c, const half_t* sample, float timestep
       T2 u = wsalloc(c, (size_t)B * (2 * H) * (2 * Wd) * st.rc);
       GnWant gw{4 * H * Wd};
       const bool want = f.gn_on && ia2p_plan_any_gn(4 * B * H * Wd);
-      op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, 1, 1, nullptr, 0, nullptr, u.p, 1, nullptr, 0, nullptr, 0, nullptr, want ? &gw : nullptr);
+      ConvOpt o;
+      o.up = 1; o.gw = want ? &gw : nullptr;
+      op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, u.p, o);
       if (want) gst_put(f, u, gw.out);
       act_free(f, x);
       H *= 2; Wd *= 2; x = u;
@@ -1002,18 +1003,13 @@ size_t ia2p_workspace_bytes(ia2p_ctx* c, int B, int h, int w, int L) {
   if (!c || check_fwd_shape(c, B, h, w, L) != IA2P_OK) return 0;
   // four dry passes: the GroupNorms as launches of their own, inside their convolutions (the product path), the fused path's unfused twin, and the autotune pass
   // (GroupNorm launches + the statistics and live tensors its fused candidates need) -- a workspace sized here serves every ia2p_set_gn_fuse mode and ia2p_autotune
-  size_t high = 0;
-  for (int pass = 0; pass < 4; ++pass) {
-    c->dry = true; c->failed = false;
-    c->gn_dry_mode = pass;
-    c->ws.reset((size_t)1 << 46);
-    c->ws_base = nullptr;
-    (void)run_forward(c, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w);
-    c->dry = false; c->gn_dry_mode = -1;
-    if (c->failed) return 0;
-    high = std::max(high, c->ws.high);
+  size_t need = 0;
+  for (int mode = 0; mode < 4; ++mode) {
+    const size_t n = pass_dry(c, [&] { return run_forward(c, mode, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w); });
+    if (!n) return 0;
+    need = std::max(need, n);
   }
-  return high + 256;
+  return need;
 }
 
 static ia2p_status unet_forward_impl(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, const void* kv, int L,
@@ -1028,27 +1024,14 @@ static ia2p_status unet_forward_impl(ia2p_ctx* c, void* stream, const void* samp
     st = fold_all(c, (hipStream_t)stream, true);       // (rare; the wait keeps a following forward on ANOTHER stream from reading half-written folds)
     if (st != IA2P_OK) return st;
   }
-  const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
-  const size_t usable = ws_bytes - (base - (uintptr_t)ws);
-  const int key = (c->ip_enabled ? 1 + c->ip_tokens : 0) + (kv ? 1000 : 0);
-  if (c->wseq_key != key) {          // (re)build the weight launch sequence with a dry pass of the same code path
-    c->wseq.clear();
-    c->dry = true; c->record = true; c->failed = false;
-    c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
-    (void)run_forward(c, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, kv ? (const half_t*)1 : nullptr);
-    c->dry = false; c->record = false;
-    c->wseq_key = key;
-  }
-  c->widx = 0;
-  c->dry = false; c->failed = false; c->stream = (hipStream_t)stream;
-  c->ws.reset(usable);
-  c->ws_base = (char*)base;
+  st = pass_enter(c, stream, ws, ws_bytes);
+  if (st != IA2P_OK) return st;
+  // the weight launch sequence: a dry pass of the same code path
+  pass_record(c, (c->ip_enabled ? 1 + c->ip_tokens : 0) + (kv ? 1000 : 0),
+              [&] { return run_forward(c, c->gn_fuse, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, kv ? (const half_t*)1 : nullptr); });
   c->tail_pf = c->arena + c->embed_lo; c->tail_pf_bytes = (c->embed_hi - c->embed_lo) * sizeof(half_t);   // the next step starts with these
-  st = run_forward(c, (const half_t*)sample, timestep, (const half_t*)context, L, (const half_t*)text_embeds, (const half_t*)time_ids, (half_t*)out, B, h, w,
-                   (const half_t*)kv, timesteps, ip_scales);
-  if (c->failed && st == IA2P_OK) st = IA2P_ERR_HIP;
-  if (c->failed && c->err == "workspace too small") st = IA2P_ERR_NOMEM;
-  return st;
+  return pass_leave(c, run_forward(c, c->gn_fuse, (const half_t*)sample, timestep, (const half_t*)context, L, (const half_t*)text_embeds, (const half_t*)time_ids, (half_t*)out,
+                                   B, h, w, (const half_t*)kv, timesteps, ip_scales));
 }
 ia2p_status ia2p_unet_forward(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, int L,
                               const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes) {
@@ -1084,18 +1067,15 @@ ia2p_status ia2p_project_context(ia2p_ctx* c, void* stream, const void* context,
     const ia2p_status fs = fold_all(c, (hipStream_t)stream, true);
     if (fs != IA2P_OK) return fs;
   }
-  const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
+  const ia2p_status st = pass_enter(c, stream, ws, ws_bytes);
+  if (st != IA2P_OK) return st;
   const bool pf = c->prefetch;
   c->prefetch = false;               // a stand-alone call: no "next launch" to stream weights for
-  c->widx = 0; c->dry = false; c->failed = false; c->stream = (hipStream_t)stream;
-  c->ws.reset(ws_bytes - (base - (uintptr_t)ws));
-  c->ws_base = (char*)base;
   const int Lt = c->ip_enabled ? L - c->ip_tokens : L;
   project_context(c, (const half_t*)context, L, B, (half_t*)kv, (half_t*)kv + (size_t)B * Lt * c->kv_rows);
   c->prefetch = pf;
   c->wseq_key = -1;                  // the launch sequence of the next forward is rebuilt
-  if (c->failed) return c->err == "workspace too small" ? IA2P_ERR_NOMEM : IA2P_ERR_HIP;
-  return IA2P_OK;
+  return pass_leave(c, IA2P_OK);
 }
 ia2p_status ia2p_unet_forward_kv(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* kv, int L, const void* text_embeds,
                                  const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes) {
@@ -1142,9 +1122,7 @@ ia2p_status ia2p_profile_enable(ia2p_ctx* c, int on) {
   if (!c) return IA2P_ERR_INVALID;
   for (auto& r : c->recs) { c->evpool.push_back(r.e0); c->evpool.push_back(r.e1); }
   c->recs.clear();
-  for (int k = 0; k < PK_NCLASS; ++k) { c->p_ms[k] = c->p_fl[k] = c->p_by[k] = c->p_pf[k] = 0; c->p_n[k] = 0; }
-  for (int k = 0; k < PR_NREGION; ++k) { c->r_ms[k] = c->r_fl[k] = c->r_by[k] = 0; c->r_n[k] = 0; }
-  for (int k = 0; k < ROLE_NROLE; ++k) { c->o_ms[k] = c->o_fl[k] = c->o_by[k] = 0; c->o_n[k] = 0; for (int q = 0; q < PK_NCLASS; ++q) { c->oc_ms[k][q] = 0; c->oc_n[k][q] = 0; } }
+  c->prof_zero();
   c->prof = on != 0;
   return IA2P_OK;
 }

@@ -1,6 +1,8 @@
 // Runtime shared by the executors (conditional UNet: engine.hip, VAE: vae_engine.hip, CLIP text towers: clip_engine.hip, ViT towers: vit_engine.hip, instruction LLM: llm_engine.hip) and the
-// per-operator C ABI (ops_abi.hip): weight arena + parameter table, workspace allocator, weight-prefetch plan, per-kernel event timing, and the operator wrappers that
-// plan and launch the HIP kernels. Definitions live in engine_rt.hip; the launch descriptors are built in launch_args.h.
+// per-operator C ABI (ops_abi.hip): weight arena + parameter table, workspace allocator, weight-prefetch plan, the pass protocol every entry point follows (pass_dry /
+// pass_enter / pass_record / pass_leave), per-kernel event timing, and the operator wrappers that plan and launch the HIP kernels. What a wrapper call needs beyond
+// its operands travels WITH the call (GemmOpt / ConvOpt / RunOpt): RunCtx holds the state of a pass, nothing addressed to "the next call".
+// Definitions live in engine_rt.hip; the launch descriptors are built in launch_args.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -156,6 +158,7 @@ struct RunCtx {
   bool dry = false;
   hipStream_t stream = nullptr;
   bool failed = false;
+  bool ws_full = false;      // the workspace ran out during this pass (wsalloc): pass_leave answers IA2P_ERR_NOMEM
   // weight prefetch plan: weights of every GEMM/conv launch of a pass, in launch order
   std::vector<std::pair<const half_t*, size_t>> wseq;
   size_t widx = 0;
@@ -168,12 +171,10 @@ struct RunCtx {
   bool cat_free = true;      // up path: torch.cat([hidden, skip]) never materialised (needs sc_fuse; IA2P_CAT_FREE=0: concat_kernel, for A/B runs)
   bool sc_fuse = true;       // ResnetBlock2D: conv2 + conv_shortcut as one implicit GEMM (IA2P_SC_FUSE=0: separate 1x1 launch + residual, for A/B runs)
   bool xattn_fuse = true;    // to_q + cross-attention as one launch where the shape allows (IA2P_XATTN_FUSE=0: two launches, for A/B runs)
-  int gn_dry_mode = -1;      // (ia2p_workspace_bytes: the dry passes walk every gn_fuse mode; -1: the context's own)
   int gn_fuse = 1;           // 1: GroupNorm + SiLU of a ResnetBlock2D applied inside the halo-staged convolution that consumes it, statistics from the producers' epilogues;
                              // 0 (IA2P_GN_FUSE=0): GroupNorm launches; 2: the fused path's UNFUSED TWIN -- the same statistics, gn_apply_stats_kernel + the plain convolution (tests: same bits as 1)
   bool sattn_fuse = true;    // QKV projection + self-attention as one launch at 256 tokens per image (follows IA2P_XATTN_FUSE=0; IA2P_SATTN_FUSE in experiment builds)
   bool ctx_kv_inlaunch = true;      // context K/V of a layer projected by extra workgroups of that layer's fused QKV + self-attention launch (IA2P_CTX_KV_INLAUNCH=0: all of it up front, for A/B runs)
-  int plan_n = 0;            // > 0: the NEXT run_gemm call takes the plan of the same problem with this many columns (a column range of a stacked projection runs on the whole projection's plan: same K split, same bits); reset by it
   bool ln_fold = true;       // LayerNorms folded into their consumer GEMMs (IA2P_LN_FOLD=0: separate layernorm_kernel launches, for A/B runs)
   bool prof = false;
 #ifdef IA2P_CLOCK_STAMP
@@ -188,8 +189,6 @@ struct RunCtx {
   // autotune pass (ia2p_autotune): every GEMM / conv site of an unmeasured shape times its candidate plans in place
   bool tuning = false;
   int tune_reps = 5, tune_sites = 0;
-  double tune_gn_ms = 0.0;                       // autotune: time of the GroupNorm launch in front of the convolution being tuned next ...
-  const GemmArgs* tune_fused = nullptr;          // ... and that convolution's GroupNorm-FUSED form (raw operand + producer statistics): its candidates are timed against GroupNorm launch + plain plan
   char* tune_scratch = nullptr;                 // [slab region | flush region]
   size_t tune_slab_bytes = 0, tune_flush_bytes = 0;
   std::vector<ProfRec> recs;
@@ -204,7 +203,6 @@ struct RunCtx {
   int64_t oc_n[ROLE_NROLE][PK_NCLASS];
   double r_ms[PR_NREGION], r_fl[PR_NREGION], r_by[PR_NREGION];
   int64_t r_n[PR_NREGION];
-  float ep_acc_scale = 1.f, ep_bias_scale = 1.f;   // epilogue scales of the NEXT op_gemm / op_conv3 call (reset by it): range extension, vae_engine.hip
   bool fold_dirty = false;   // a LayerNorm-fold source tensor was (re)loaded after the last fold: re-fold before the next forward
   RunCtx() {
     if (const char* e = getenv("IA2P_PREFETCH")) prefetch = atoi(e) != 0;
@@ -216,6 +214,9 @@ struct RunCtx {
     if (const char* e = ia2p_exp_env("IA2P_SC_FUSE")) sc_fuse = atoi(e) != 0;
     if (const char* e = ia2p_exp_env("IA2P_CAT_FREE")) cat_free = atoi(e) != 0;
     if (ia2p_default_xattn_min_tiles() >= 0) xattn_min_tiles = ia2p_default_xattn_min_tiles();      // (test hook: ia2p_debug_set_xattn_min_tiles)
+    prof_zero();
+  }
+  void prof_zero() {      // the profile sums (constructor, ia2p_profile_enable)
     for (int k = 0; k < PK_NCLASS; ++k) { p_ms[k] = p_fl[k] = p_by[k] = p_pf[k] = 0; p_n[k] = 0; }
     for (int k = 0; k < PR_NREGION; ++k) { r_ms[k] = r_fl[k] = r_by[k] = 0; r_n[k] = 0; }
     for (int k = 0; k < ROLE_NROLE; ++k) { o_ms[k] = o_fl[k] = o_by[k] = 0; o_n[k] = 0; for (int q = 0; q < PK_NCLASS; ++q) { oc_ms[k][q] = 0; oc_n[k][q] = 0; } }
@@ -235,6 +236,30 @@ struct T2 { size_t off; half_t* p; };   // workspace tensor
 T2 wsalloc(RunCtx* c, size_t elems);
 void wsfree(RunCtx* c, T2 t);
 hipEvent_t get_event(RunCtx* c);
+
+// ---- the pass protocol of every executor entry point: [pass_dry: what a pass needs] ... preconditions, pass_enter, pass_record, the pass itself, pass_leave
+// a pass over `run` that launches nothing and allocates from an unbounded workspace; returns the bytes a real pass needs (high-water mark + alignment slack), 0 on failure
+template <class Run> size_t pass_dry(RunCtx* c, Run&& run) {
+  c->dry = true; c->failed = c->ws_full = false;
+  c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
+  (void)run();
+  c->dry = false;
+  return c->failed ? 0 : c->ws.high + 256;
+}
+// the caller's workspace, aligned to 256 bytes, becomes the pass's; IA2P_ERR_NOMEM when it does not even cover the alignment loss. Then: stream, first launch, not dry, not failed
+ia2p_status pass_enter(RunCtx* c, void* stream, void* ws, size_t ws_bytes);
+// (after pass_enter) the weight-prefetch sequence of the pass `key` names, when it is not the recorded one: a dry pass over `run` that notes every contraction's weights
+template <class Run> void pass_record(RunCtx* c, int key, Run&& run) {
+  if (c->wseq_key == key) return;
+  const size_t cap = c->ws.cap; char* const base = c->ws_base;      // (what pass_enter set up)
+  c->wseq.clear(); c->record = true;
+  (void)pass_dry(c, run);
+  c->record = false; c->wseq_key = key;
+  c->failed = c->ws_full = false;
+  c->ws.reset(cap); c->ws_base = base;
+}
+// status of the pass that returned st: the workspace ran out -> IA2P_ERR_NOMEM; any other failure -> st, IA2P_ERR_HIP when the pass itself reported none
+ia2p_status pass_leave(RunCtx* c, ia2p_status st);
 
 struct ProfScope {
   RunCtx* c; int k; double fl, by; hipEvent_t e0, e1; bool on; double pf = 0;
@@ -259,9 +284,10 @@ struct GnStats { T2 buf{(size_t)-1, nullptr}; int rows = 0; bool ok() const { re
 // what a producer launch is asked for: statistics of its output, an image being HW rows; filled in by run_gemm / op_gemm / op_conv3
 struct GnWant { int HW; GnStats out; };
 // GroupNorm fused into a 3x3 convolution (op_conv3): the operand is the raw tensor X (C0 channels) [| X1b (Cin - C0)] with the statistics of its producer(s)
-// (tune: autotune pass -- the launch itself is the plain one, on the normalised tensor; Xraw [| X1b] + statistics describe the site's FUSED form for tune_site to time beside it)
+// (tune: autotune pass -- the launch itself is the plain one, on the normalised tensor; Xraw [| X1b] + statistics describe the site's FUSED form for tune_site to time beside it,
+//  gn_ms: what the GroupNorm launch in front of it just took)
 struct ConvGn { bool fused = false; const half_t* X1b = nullptr; int C0 = 0; GnStats s0, s1; const half_t* gamma = nullptr; const half_t* beta = nullptr; float eps = 1e-5f; int groups = 32;
-                bool tune = false; const half_t* Xraw = nullptr; };
+                bool tune = false; const half_t* Xraw = nullptr; float gn_ms = 0.f; };
 // LayerNorm folded into a GEMM: where the consumer finds the row statistics and the folded constants
 struct LnIn { const float* stats; int slots; const float* cs; const float* lb; float eps; };
 // ... attached to the consumer's descriptor: from the executor's LnIn, or from the C ABI's ia2p_ln_fold (complete or refused: ln_fold_ok)
@@ -272,21 +298,38 @@ inline bool ln_fold_ok(const ia2p_ln_fold* ln) { return !ln || (ln->stats && ln-
 // ---- operator wrappers: plan (tile / K-split / autotune), slabs, weight prefetch, profiling class, launch
 // the pieces op_gemm / op_conv3 are made of, for the executors' fused launches and the operator ABI: next launch's weight prefetch; the executor's linear-layer descriptor;
 // plan + slabs + launch of a finished descriptor; HBM bytes of a linear layer; rows per slot of GroupNorm column sums (stand-alone pass / a launch's own epilogue)
+// Options of a wrapper call: a site names the ones it uses (`GemmOpt o; o.ln = &ln; o.stats = st; ...`), the rest keep these defaults.
+// run_gemm's: where to report the row-statistics slots of the output; GroupNorm statistics wanted of it; plan_n > 0: the launch takes the plan of the same problem with that
+// many columns (a column range of a stacked projection runs on the whole projection's plan: same K split, same bits); autotune pass, a convolution behind a GroupNorm:
+// the site's GroupNorm-FUSED form and the time of the GroupNorm launch, its candidates are timed against that launch + the best plain plan
+struct RunOpt { int* stat_slots = nullptr; GnWant* gw = nullptr; int plan_n = 0; const GemmArgs* tune_fused = nullptr; float tune_gn_ms = 0.f; };
+// op_gemm's / gemm_args': GEGLU epilogue; the linear row map (rpb == 0: identity); ldw (0: K); activation; LayerNorm folded in front; row statistics behind (stats) and their
+// slot count (stat_slots); GroupNorm statistics wanted (gw); epilogue scales (range extension, vae_engine.hip); plan_n as in RunOpt
+struct GemmOpt {
+  int geglu = 0, rpb = 0, bstride = 0, roff = 0, ldw = 0, act = 0;
+  const LnIn* ln = nullptr; float* stats = nullptr; int* stat_slots = nullptr; GnWant* gw = nullptr;
+  float acc_scale = 1.f, bias_scale = 1.f; int plan_n = 0;
+};
+// op_conv3's: stride, nearest-x2 upsampled input, zero rows / columns before the image; a per-image row vector; residual [M, Co]; appended 1x1 blocks X2 / X3 of
+// Cin2 / Cin3 channels; the GroupNorm in front (fused, or the autotune pass's description of the fused form); GroupNorm statistics wanted; epilogue scales
+struct ConvOpt {
+  int stride = 1, up = 0, pad_lo = 1;
+  const half_t* rowvec = nullptr; int rowvec_ld = 0; const half_t* residual = nullptr;
+  const half_t* X2 = nullptr; int Cin2 = 0; const half_t* X3 = nullptr; int Cin3 = 0;
+  const ConvGn* gn = nullptr; GnWant* gw = nullptr; float acc_scale = 1.f, bias_scale = 1.f;
+};
 void set_prefetch(RunCtx* c, GemmArgs& a, const half_t* W, size_t bytes);
 GemmArgs gemm_args(RunCtx* c, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
-                   half_t* C, int ldc, int M, int N, int K, int geglu, int rpb, int bstride, int roff, int ldw, const LnIn* ln, float* stats_out, int act);
-void run_gemm(RunCtx* c, GemmArgs& a, bool conv, const char* what, double flops, double bytes, int* stat_slots = nullptr, GnWant* gw = nullptr);
+                   half_t* C, int ldc, int M, int N, int K, const GemmOpt& o = GemmOpt{});
+void run_gemm(RunCtx* c, GemmArgs& a, bool conv, const char* what, double flops, double bytes, const RunOpt& r = RunOpt{});
 double gemm_bytes(int M, int N, int K, int geglu, bool residual);
 int gn_fallback_rows(int HW);
 int gn_epilogue_rows(const GemmArgs& a, bool conv, int variant, int splitk, bool combined, int HW);
 ia2p_status tune_begin(RunCtx* c, int reps);      // autotune pass: scratch + RunCtx::tuning on / off (every run_gemm site of an unmeasured shape then times its candidates in place)
 void tune_end(RunCtx* c, hipStream_t s);
 void op_gemm(RunCtx* c, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
-             half_t* C, int ldc, int M, int N, int K, int geglu = 0, int rpb = 0, int bstride = 0, int roff = 0, int ldw = 0,
-             const LnIn* ln = nullptr, float* stats_out = nullptr, int* stat_slots = nullptr, int act = 0, GnWant* gw = nullptr);
-void op_conv3(RunCtx* c, const half_t* X, int B, int Hs, int Ws, int Cin, const half_t* W, const half_t* bias, int Co,
-              int stride, int up, const half_t* rowvec, int rowvec_ld, const half_t* residual, half_t* Y, int pad_lo = 1, const half_t* X2 = nullptr, int Cin2 = 0, const half_t* X3 = nullptr, int Cin3 = 0,
-              const ConvGn* gn = nullptr, GnWant* gw = nullptr);
+             half_t* C, int ldc, int M, int N, int K, const GemmOpt& o = GemmOpt{});
+void op_conv3(RunCtx* c, const half_t* X, int B, int Hs, int Ws, int Cin, const half_t* W, const half_t* bias, int Co, half_t* Y, const ConvOpt& o = ConvOpt{});
 void op_gn(RunCtx* c, const half_t* x, half_t* y, size_t g, size_t b, int B, int HW, int C, float eps, int silu, float* partial, const half_t* x2 = nullptr, int Ca = 0);
 void op_ln(RunCtx* c, const half_t* x, half_t* y, size_t g, size_t b, int M, int C);
 

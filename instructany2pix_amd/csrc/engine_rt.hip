@@ -1,6 +1,6 @@
-// Definitions of the runtime engine_rt.h declares: error state, workspace and event pool, weight prefetch, the in-place autotuner, the operator wrappers (plan, K-split
-// slabs, profiling class, launch) and the weight-arena plumbing. Host code only; every executor (engine.hip, vae_engine.hip, clip_engine.hip, llm_engine.hip) and the
-// per-operator C ABI (ops_abi.hip) link against this file and need nothing from each other.
+// Definitions of the runtime engine_rt.h declares: error state, workspace and event pool, the pass protocol's enter / leave, weight prefetch, the in-place autotuner, the
+// operator wrappers (plan, K-split slabs, profiling class, launch) and the weight-arena plumbing. Host code only; every executor (engine.hip, vae_engine.hip,
+// clip_engine.hip, vit_engine.hip, llm_engine.hip) and the per-operator C ABI (ops_abi.hip) link against this file and need nothing from each other.
 #include "engine_rt.h"
 
 thread_local std::string g_err;
@@ -60,12 +60,25 @@ ia2p_status fail_hip(RunCtx* c, hipError_t e, const char* what) {
 
 T2 wsalloc(RunCtx* c, size_t elems) {
   const size_t off = c->ws.alloc(elems * sizeof(half_t));
-  if (off == (size_t)-1) { if (!c->failed) fail(c, IA2P_ERR_NOMEM, "workspace too small"); return T2{off, nullptr}; }
+  if (off == (size_t)-1) { if (!c->failed) { fail(c, IA2P_ERR_NOMEM, "workspace too small"); c->ws_full = true; } return T2{off, nullptr}; }
   return T2{off, c->dry ? nullptr : (half_t*)(c->ws_base + off)};
 }
 void wsfree(RunCtx* c, T2 t) {
   if (t.off == (size_t)-1) return;
   c->ws.release(t.off);
+}
+
+ia2p_status pass_enter(RunCtx* c, void* stream, void* ws, size_t ws_bytes) {
+  const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
+  const size_t lost = base - (uintptr_t)ws;
+  if (ws_bytes < lost) return fail(c, IA2P_ERR_NOMEM, "workspace too small");      // (caller-supplied values: the difference below must not wrap)
+  c->widx = 0; c->dry = false; c->failed = c->ws_full = false; c->stream = (hipStream_t)stream;
+  c->ws.reset(ws_bytes - lost); c->ws_base = (char*)base;
+  return IA2P_OK;
+}
+ia2p_status pass_leave(RunCtx* c, ia2p_status st) {
+  if (!c->failed) return st;
+  return c->ws_full ? IA2P_ERR_NOMEM : st == IA2P_OK ? IA2P_ERR_HIP : st;
 }
 
 hipEvent_t get_event(RunCtx* c) {
@@ -116,11 +129,7 @@ static std::vector<float> time_candidates(RunCtx* c, const GemmArgs& a, bool con
 // In-place measurement of the candidate plans of one GEMM / conv site (autotune pass): time_candidates over the plain candidates -- the prefetch workgroups of the site
 // are part of every candidate launch -- and, behind a GroupNorm, over the fused ones. The fastest goes into the plan table. Re-running a site is harmless: outputs are
 // rewritten (in-place residuals only drift).
-static void tune_site(RunCtx* c, const GemmArgs& a, bool conv) {
-  // (what the caller left for THIS site -- taken and cleared before anything else: the pointer refers to the caller's frame)
-  const GemmArgs* fa = c->tune_fused;
-  const float gn_ms = (float)c->tune_gn_ms;
-  c->tune_fused = nullptr; c->tune_gn_ms = 0.0;
+static void tune_site(RunCtx* c, const GemmArgs& a, bool conv, const GemmArgs* fa, float gn_ms) {
   if (ia2p_plan_lookup(a.M, a.N, a.K, conv, a.geglu != 0, nullptr)) return;
   std::vector<GemmPlan> cands;
   ia2p_gemm_candidates(a.M, a.N, a.K, conv, a.geglu != 0, c->tune_slab_bytes, ia2p_exp_env("IA2P_TUNE_SLACK") ? atof(ia2p_exp_env("IA2P_TUNE_SLACK")) : 2.5, &cands);      // (2.5 x the modelled best: -0.04 ms per step against 1.7 on the same box, profiles/r05t_slack_ab.txt; 4.0 measures 4 x the candidates for the same picks)
@@ -142,8 +151,8 @@ static void tune_site(RunCtx* c, const GemmArgs& a, bool conv) {
   GemmPlan best{-1, 1};
   for (size_t i = 0; i < cands.size() && best.variant < 0; ++i)
     if (ok[i] && best_ms[i] <= 1.02f * fastest) best = cands[i];
-  // A site behind a GroupNorm (the caller left c->tune_fused: the site's GroupNorm-FUSED form -- raw operand, producer statistics -- and c->tune_gn_ms: what the
-  // GroupNorm launch in front of it just took): the fused launch on every halo-staged tile / K split it may run on is timed the same way, and taken when it beats
+  // A site behind a GroupNorm (fa: the site's GroupNorm-FUSED form -- raw operand, producer statistics --, gn_ms: what the GroupNorm launch in front of it just
+  // took; RunOpt): the fused launch on every halo-staged tile / K split it may run on is timed the same way, and taken when it beats
   // GroupNorm launch + best plain plan. The fused kernel normalises every halo image in LDS beside its MFMAs (+15 ... 25 % per launch): it pays where the norm's
   // launch is expensive against the convolution (few input channels on the large maps), not everywhere.
   if (fa && conv && best.variant >= 0 && gn_ms > 0.f) {
@@ -183,11 +192,10 @@ int gn_epilogue_rows(const GemmArgs& a, bool conv, int variant, int splitk, bool
 }
 // plan, K-split slabs, profiling class and launch of one GEMM / implicit-GEMM conv
 // gw != nullptr: the launch also leaves the GroupNorm statistics of its output (gn_fold.h) -- from its own epilogue when the tile allows, else from a gn_colstats_kernel pass
-void run_gemm(RunCtx* c, GemmArgs& a, bool conv, const char* what, double flops, double bytes, int* stat_slots, GnWant* gw) {
-  const int plan_n = c->plan_n > 0 ? c->plan_n : a.N;      // (a column range of a stacked projection: the whole projection's plan -- project_context)
-  c->plan_n = 0;
-  if (c->tuning && !c->dry && !c->failed && plan_n == a.N) tune_site(c, a, conv);
-  c->tune_fused = nullptr; c->tune_gn_ms = 0.0;
+void run_gemm(RunCtx* c, GemmArgs& a, bool conv, const char* what, double flops, double bytes, const RunOpt& r) {
+  int* const stat_slots = r.stat_slots; GnWant* const gw = r.gw;
+  const int plan_n = r.plan_n > 0 ? r.plan_n : a.N;      // (a column range of a stacked projection: the whole projection's plan -- project_context)
+  if (c->tuning && !c->dry && !c->failed && plan_n == a.N) tune_site(c, a, conv, r.tune_fused, r.tune_gn_ms);
   const GemmPlan pl = ia2p_gemm_plan(a.M, plan_n, a.K, conv, a.geglu != 0);
   if (pl.variant < 0 || pl.variant >= IA2P_GEMM_NVARIANT) { fail(c, IA2P_ERR_INVALID, "%s: tile variant %d out of range", what, pl.variant); return; }
   if (c->tuning && !c->dry && pl.splitk > 1 && (size_t)pl.splitk * a.M * a.N * sizeof(float) > c->tune_slab_bytes) {
@@ -244,47 +252,46 @@ void run_gemm(RunCtx* c, GemmArgs& a, bool conv, const char* what, double flops,
   if (stat_slots) *stat_slots = (pl.splitk > 1 && !combined) ? 1 : (a.N + IA2P_GEMM_TILES[pl.variant].bn - 1) / IA2P_GEMM_TILES[pl.variant].bn;
 }
 
-// the descriptor of an executor's linear layer: gemm_desc + the folded LayerNorm in front, the row statistics behind, and the epilogue scales left for this call
-GemmArgs gemm_args(RunCtx* c, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
-                   half_t* C, int ldc, int M, int N, int K, int geglu, int rpb, int bstride, int roff, int ldw,
-                   const LnIn* ln, float* stats_out, int act) {
-  GemmArgs a = gemm_desc(zero_page(), A, lda, W, ldw ? ldw : K, bias, residual, ldr, C, ldc, M, N, K, geglu, rpb, bstride, roff, act);
-  ln_attach(a, ln);
-  a.stats_out = stats_out;
-  a.acc_scale = c->ep_acc_scale; a.bias_scale = c->ep_bias_scale; c->ep_acc_scale = c->ep_bias_scale = 1.f;
+// the descriptor of an executor's linear layer: gemm_desc + the folded LayerNorm in front, the row statistics behind, and the epilogue scales
+GemmArgs gemm_args(RunCtx*, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
+                   half_t* C, int ldc, int M, int N, int K, const GemmOpt& o) {
+  GemmArgs a = gemm_desc(zero_page(), A, lda, W, o.ldw ? o.ldw : K, bias, residual, ldr, C, ldc, M, N, K, o.geglu, o.rpb, o.bstride, o.roff, o.act);
+  ln_attach(a, o.ln);
+  a.stats_out = o.stats;
+  a.acc_scale = o.acc_scale; a.bias_scale = o.bias_scale;
   return a;
 }
 double gemm_bytes(int M, int N, int K, int geglu, bool residual) { return 2.0 * ((double)M * K + (double)N * K + (double)M * (geglu ? N / 2 : N) + (residual ? (double)M * N : 0)); }
 void op_gemm(RunCtx* c, const half_t* A, int lda, const half_t* W, const half_t* bias, const half_t* residual, int ldr,
-             half_t* C, int ldc, int M, int N, int K, int geglu, int rpb, int bstride, int roff, int ldw,
-             const LnIn* ln, float* stats_out, int* stat_slots, int act, GnWant* gw) {
-  GemmArgs a = gemm_args(c, A, lda, W, bias, residual, ldr, C, ldc, M, N, K, geglu, rpb, bstride, roff, ldw, ln, stats_out, act);
+             half_t* C, int ldc, int M, int N, int K, const GemmOpt& o) {
+  GemmArgs a = gemm_args(c, A, lda, W, bias, residual, ldr, C, ldc, M, N, K, o);
   set_prefetch(c, a, W, (size_t)N * K * sizeof(half_t));
-  run_gemm(c, a, false, "gemm", 2.0 * M * N * K, gemm_bytes(M, N, K, geglu, residual != nullptr), stat_slots, gw);
+  RunOpt r; r.stat_slots = o.stat_slots; r.gw = o.gw; r.plan_n = o.plan_n;
+  run_gemm(c, a, false, "gemm", 2.0 * M * N * K, gemm_bytes(M, N, K, o.geglu, residual != nullptr), r);
 }
 // the GroupNorm-fused form of a convolution descriptor: the operand is the norm's RAW input X [| gn.X1b], with its producers' statistics
 static void conv_gn_attach(GemmArgs& a, const ConvGn& gn, const half_t* X) {
   a.A = X; a.lda = gn.C0; a.A1b = gn.X1b; a.lda1b = a.Cin - gn.C0;
   a.gn = gn_in_desc((const double*)gn.s0.buf.p, gn.s0.rows, gn.X1b ? (const double*)gn.s1.buf.p : nullptr, gn.s1.rows, gn.C0, a.Cin, gn.gamma, gn.beta, gn.groups, gn.eps, 1);
 }
-void op_conv3(RunCtx* c, const half_t* X, int B, int Hs, int Ws, int Cin, const half_t* W, const half_t* bias, int Co,
-              int stride, int up, const half_t* rowvec, int rowvec_ld, const half_t* residual, half_t* Y, int pad_lo, const half_t* X2, int Cin2,
-              const half_t* X3, int Cin3, const ConvGn* gn, GnWant* gw) {
+void op_conv3(RunCtx* c, const half_t* X, int B, int Hs, int Ws, int Cin, const half_t* W, const half_t* bias, int Co, half_t* Y, const ConvOpt& o) {
+  const int Cin2 = o.Cin2, Cin3 = o.Cin3; const half_t *X2 = o.X2, *X3 = o.X3; const ConvGn* gn = o.gn;
   // (appended blocks are described by their channel counts: in a dry pass the pointers are null, the shapes -- hence plans and slabs -- must not change)
-  if ((Cin2 > 0 && (stride != 1 || up || pad_lo != 1 || Cin2 % 64)) || (Cin3 > 0 && (Cin2 <= 0 || Cin3 % 64)) || Cin2 < 0 || Cin3 < 0 ||
-      (!c->dry && ((Cin2 > 0) != (X2 != nullptr) || (Cin3 > 0) != (X3 != nullptr)))) { fail(c, IA2P_ERR_SHAPE, "conv3x3 with appended 1x1 blocks: stride 1, no upsampling, Cin2 / Cin3 %% 64 == 0 (stride %d up %d pad %d Cin %d Cin2 %d Cin3 %d, X2 %s, X3 %s)", stride, up, pad_lo, Cin, Cin2, Cin3, X2 ? "set" : "null", X3 ? "set" : "null"); return; }
-  GemmArgs a = conv3_desc(zero_page(), X, B, Hs, Ws, Cin, W, bias, Co, stride, up, pad_lo, rowvec, rowvec_ld, residual, Y, X2, Cin2, X3, Cin3);
+  if ((Cin2 > 0 && (o.stride != 1 || o.up || o.pad_lo != 1 || Cin2 % 64)) || (Cin3 > 0 && (Cin2 <= 0 || Cin3 % 64)) || Cin2 < 0 || Cin3 < 0 ||
+      (!c->dry && ((Cin2 > 0) != (X2 != nullptr) || (Cin3 > 0) != (X3 != nullptr)))) { fail(c, IA2P_ERR_SHAPE, "conv3x3 with appended 1x1 blocks: stride 1, no upsampling, Cin2 / Cin3 %% 64 == 0 (stride %d up %d pad %d Cin %d Cin2 %d Cin3 %d, X2 %s, X3 %s)", o.stride, o.up, o.pad_lo, Cin, Cin2, Cin3, X2 ? "set" : "null", X3 ? "set" : "null"); return; }
+  GemmArgs a = conv3_desc(zero_page(), X, B, Hs, Ws, Cin, W, bias, Co, o.stride, o.up, o.pad_lo, o.rowvec, o.rowvec_ld, o.residual, Y, X2, Cin2, X3, Cin3);
   if (gn && gn->fused) conv_gn_attach(a, *gn, X);      // GroupNorm + SiLU applied inside the convolution (the caller asked ia2p_conv_gn_fusable)
-  a.acc_scale = c->ep_acc_scale; a.bias_scale = c->ep_bias_scale; c->ep_acc_scale = c->ep_bias_scale = 1.f;
+  a.acc_scale = o.acc_scale; a.bias_scale = o.bias_scale;
   set_prefetch(c, a, W, (size_t)Co * a.K * sizeof(half_t));
+  RunOpt r; r.gw = o.gw;
   GemmArgs fa;      // autotune pass: the site's GroupNorm-fused form, for tune_site to time against GroupNorm launch + plain plan
   if (gn && gn->tune && !gn->fused && c->tuning && !c->dry && gn->s0.ok() && gn->Xraw) {
     fa = a;
     conv_gn_attach(fa, *gn, gn->Xraw);
-    if (ia2p_conv_gn_ok(fa)) c->tune_fused = &fa;
+    if (ia2p_conv_gn_ok(fa)) { r.tune_fused = &fa; r.tune_gn_ms = gn->gn_ms; }
   }
   RoleScope role(c, ROLE_CONV3X3);
-  run_gemm(c, a, true, "conv3x3", 2.0 * a.M * (double)Co * a.K, 2.0 * ((double)B * Hs * Ws * Cin + (double)Co * a.K + (double)a.M * Co + (residual ? (double)a.M * Co : 0) + (double)a.M * (Cin2 + Cin3)), nullptr, gw);
+  run_gemm(c, a, true, "conv3x3", 2.0 * a.M * (double)Co * a.K, 2.0 * ((double)B * Hs * Ws * Cin + (double)Co * a.K + (double)a.M * Co + (o.residual ? (double)a.M * Co : 0) + (double)a.M * (Cin2 + Cin3)), r);
 }
 void op_gn(RunCtx* c, const half_t* x, half_t* y, size_t g, size_t b, int B, int HW, int C, float eps, int silu, float* partial, const half_t* x2, int Ca) {
   RoleScope role(c, ROLE_GROUPNORM);

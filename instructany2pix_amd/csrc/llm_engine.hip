@@ -206,12 +206,7 @@ static ia2p_status llm_run_prefill(ia2p_llm* c, const half_t* embeds, int T, flo
 
 // workspace need of a prefill of T rows (T > 0) or of a decode step of n rows: a host dry run
 static size_t llm_dry(ia2p_llm* c, int T, int n = 1) {
-  c->dry = true; c->failed = false; c->record = false;
-  c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
-  if (T > 0) (void)llm_run_prefill(c, nullptr, T, nullptr, nullptr);
-  else (void)llm_run_decode_rows(c, nullptr, nullptr, n, nullptr, nullptr);
-  c->dry = false;
-  return c->failed ? 0 : c->ws.high + 256;
+  return pass_dry(c, [&] { return T > 0 ? llm_run_prefill(c, nullptr, T, nullptr, nullptr) : llm_run_decode_rows(c, nullptr, nullptr, n, nullptr, nullptr); });
 }
 static ia2p_status llm_ready(ia2p_llm* c, const char* what) {
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "%s before weights were finalized", what);
@@ -220,17 +215,10 @@ static ia2p_status llm_ready(ia2p_llm* c, const char* what) {
 }
 // exact: the batched decode takes `need` as the least size of an aligned workspace (the earlier entry points allow the alignment slack to be missing)
 static ia2p_status llm_enter(ia2p_llm* c, void* stream, void* ws, size_t ws_bytes, size_t need, bool exact = false) {
-  const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
-  const size_t lost = base - (uintptr_t)ws;
+  const size_t lost = (size_t)(-(uintptr_t)ws & 255);      // what aligning ws to 256 bytes costs
   if (need == 0 || ws_bytes < lost || ws_bytes - lost + (exact ? 0 : 256) < need) return fail(c, IA2P_ERR_NOMEM, "llm: workspace of %zu bytes, %zu needed", ws_bytes, need);
-  c->wseq.clear(); c->widx = 0; c->dry = false; c->failed = false; c->stream = (hipStream_t)stream;
-  c->ws.reset(ws_bytes - lost); c->ws_base = (char*)base;
-  return IA2P_OK;
-}
-static ia2p_status llm_leave(ia2p_llm* c, ia2p_status st) {
-  if (c->failed && st == IA2P_OK) st = IA2P_ERR_HIP;
-  if (c->failed && c->err == "workspace too small") st = IA2P_ERR_NOMEM;
-  return st;
+  c->wseq.clear();      // (no prefetch plan: the decode launches stream their own weights)
+  return pass_enter(c, stream, ws, ws_bytes);
 }
 
 extern "C" {
@@ -373,7 +361,7 @@ static ia2p_status llm_prefill_at(ia2p_llm* c, const char* what, int slot, void*
   if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
   c->cur = slot;
   st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, T));
-  if (st == IA2P_OK) st = llm_leave(c, llm_run_prefill(c, (const half_t*)inputs_embeds, T, hidden_out, logits_out));
+  if (st == IA2P_OK) st = pass_leave(c, llm_run_prefill(c, (const half_t*)inputs_embeds, T, hidden_out, logits_out));
   c->cur = 0;
   if (st == IA2P_OK) c->spos[slot] += T;
   return st;
@@ -395,7 +383,7 @@ ia2p_status ia2p_llm_decode(ia2p_llm* c, void* stream, int token_id, float* hidd
   st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, 0));
   if (st != IA2P_OK) return st;
   const int32_t slot = 0, token = token_id;
-  st = llm_leave(c, llm_run_decode_rows(c, &slot, &token, 1, hidden_out, logits_out));
+  st = pass_leave(c, llm_run_decode_rows(c, &slot, &token, 1, hidden_out, logits_out));
   if (st == IA2P_OK) c->spos[0] += 1;
   return st;
 }
@@ -419,7 +407,7 @@ ia2p_status ia2p_llm_decode_batch(ia2p_llm* c, void* stream, const int32_t* slot
   }
   st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, 0, n), true);
   if (st != IA2P_OK) return st;
-  st = llm_leave(c, llm_run_decode_rows(c, slots, token_ids, n, hidden_out, logits_out));
+  st = pass_leave(c, llm_run_decode_rows(c, slots, token_ids, n, hidden_out, logits_out));
   if (st == IA2P_OK)
     for (int r = 0; r < n; ++r) c->spos[slots[r]] += 1;
   return st;

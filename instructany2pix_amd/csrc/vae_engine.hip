@@ -124,8 +124,9 @@ static T2 vae_resnet(ia2p_vae* c, const VRes& r, T2 x, int B, int H, int Wd, flo
   T2 n1 = wsalloc(c, (size_t)M * r.cin);
   op_gn(c, x.p, n1.p, r.n1g, r.n1b, B, HW, r.cin, eps, 1, gnp);
   T2 hh = wsalloc(c, (size_t)M * r.cout);
-  c->ep_acc_scale = ss; c->ep_bias_scale = ss;                 // hh = ss * conv1(...)
-  op_conv3(c, n1.p, B, H, Wd, r.cin, W_(c, r.w1), W_(c, r.b1), r.cout, 1, 0, nullptr, 0, nullptr, hh.p);
+  ConvOpt o1;
+  o1.acc_scale = ss; o1.bias_scale = ss;                       // hh = ss * conv1(...)
+  op_conv3(c, n1.p, B, H, Wd, r.cin, W_(c, r.w1), W_(c, r.b1), r.cout, hh.p, o1);
   wsfree(c, n1);
   T2 n2 = wsalloc(c, (size_t)M * r.cout);
   op_gn(c, hh.p, n2.p, r.n2g, r.n2b, B, HW, r.cout, eps, 1, gnp);
@@ -134,13 +135,16 @@ static T2 vae_resnet(ia2p_vae* c, const VRes& r, T2 x, int B, int H, int Wd, flo
   const half_t* resid = x.p;
   if (r.shortcut) {
     xs = wsalloc(c, (size_t)M * r.cout);
-    c->ep_acc_scale = 1.f; c->ep_bias_scale = ss;               // linear in the (scaled) stream: only the bias is scaled
-    op_gemm(c, x.p, r.cin, W_(c, r.wsc), W_(c, r.bsc), nullptr, 0, xs.p, r.cout, (int)M, r.cout, r.cin);
+    GemmOpt o;
+    o.bias_scale = ss;                                          // linear in the (scaled) stream: only the bias is scaled
+    op_gemm(c, x.p, r.cin, W_(c, r.wsc), W_(c, r.bsc), nullptr, 0, xs.p, r.cout, (int)M, r.cout, r.cin, o);
     resid = xs.p;
   }
   T2 out = wsalloc(c, (size_t)M * r.cout);
-  c->ep_acc_scale = ss; c->ep_bias_scale = ss;                 // ss * (conv2 + b) + (scaled) residual
-  op_conv3(c, n2.p, B, H, Wd, r.cout, W_(c, r.w2), W_(c, r.b2), r.cout, 1, 0, nullptr, 0, c->dry ? nullptr : resid, out.p);
+  ConvOpt o2;
+  o2.acc_scale = ss; o2.bias_scale = ss;                       // ss * (conv2 + b) + (scaled) residual
+  o2.residual = c->dry ? nullptr : resid;
+  op_conv3(c, n2.p, B, H, Wd, r.cout, W_(c, r.w2), W_(c, r.b2), r.cout, out.p, o2);
   wsfree(c, n2);
   if (r.shortcut) wsfree(c, xs);
   return out;
@@ -160,16 +164,18 @@ static T2 vae_mid(ia2p_vae* c, const VMid& m, T2 x, int B, int H, int Wd, float*
     const half_t* nb = c->dry ? nullptr : n.p + (size_t)b * HW * C;
     op_gemm(c, nb, C, W_(c, m.wqk), W_(c, m.bqk), nullptr, 0, qk.p, 2 * C, HW, 2 * C, C);                  // [q | k]
     op_gemm(c, W_(c, m.wv), C, nb, nullptr, nullptr, 0, vt.p, HW, C, HW, C);                              // V^T = W_v . X^T (bias added after P.V: rows of P sum to 1)
-    c->ep_acc_scale = 1.0f / sqrtf((float)C);                                                              // scores leave the accumulator already scaled: |q.k| can pass the fp16 maximum
-    op_gemm(c, qk.p, 2 * C, c->dry ? nullptr : qk.p + C, nullptr, nullptr, 0, sc.p, HW, HW, HW, C, 0, 0, 0, 0, 2 * C);   // S = Q . K^T / sqrt(C)
+    GemmOpt os;
+    os.ldw = 2 * C; os.acc_scale = 1.0f / sqrtf((float)C);                                                 // scores leave the accumulator already scaled: |q.k| can pass the fp16 maximum
+    op_gemm(c, qk.p, 2 * C, c->dry ? nullptr : qk.p + C, nullptr, nullptr, 0, sc.p, HW, HW, HW, C, os);   // S = Q . K^T / sqrt(C)
     {
       ProfScope ps(c, PK_ATTN, 0, 4.0 * HW * HW);
       CHECK_LAUNCH(c, ia2p_launch_softmax_rows(sc.p, HW, HW, HW, 1.0f, c->stream), "vae softmax");
     }
     op_gemm(c, sc.p, HW, vt.p, W_(c, m.bv), nullptr, 0, o.p, C, HW, C, HW);                                // O = P . V + b_v
-    c->ep_acc_scale = ss; c->ep_bias_scale = ss;
+    GemmOpt oo;
+    oo.acc_scale = ss; oo.bias_scale = ss;
     op_gemm(c, o.p, C, W_(c, m.wo), W_(c, m.bo), c->dry ? nullptr : a.p + (size_t)b * HW * C, C,
-            c->dry ? nullptr : out.p + (size_t)b * HW * C, C, HW, C, C);                                  // + residual
+            c->dry ? nullptr : out.p + (size_t)b * HW * C, C, HW, C, C, oo);                              // + residual
   }
   wsfree(c, n); wsfree(c, qk); wsfree(c, vt); wsfree(c, sc); wsfree(c, o); wsfree(c, a);
   T2 r = vae_resnet(c, m.r1, out, B, H, Wd, gnp);
@@ -205,8 +211,9 @@ static ia2p_status vae_run_decode(ia2p_vae* c, const half_t* zin, half_t* img, i
     for (const VRes& r : st.res) { T2 y = vae_resnet(c, r, x, B, H, Wd, gp); wsfree(c, x); x = y; }
     if (st.resample) {
       T2 u = wsalloc(c, (size_t)B * (2 * H) * (2 * Wd) * st.rc);
-      c->ep_acc_scale = 1.f; c->ep_bias_scale = c->ss;
-      op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, 1, 1, nullptr, 0, nullptr, u.p);
+      ConvOpt o;
+      o.up = 1; o.bias_scale = c->ss;
+      op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, u.p, o);
       wsfree(c, x); x = u; H *= 2; Wd *= 2;
     }
   }
@@ -237,8 +244,9 @@ static ia2p_status vae_run_encode(ia2p_vae* c, const half_t* img, half_t* moment
     for (const VRes& r : st.res) { T2 y = vae_resnet(c, r, x, B, H, Wd, gp); wsfree(c, x); x = y; }
     if (st.resample) {       // F.pad(x, (0,1,0,1)) + conv stride 2 padding 0 (ldm Downsample, blocks.py:73-77)
       T2 d = wsalloc(c, (size_t)B * (H / 2) * (Wd / 2) * st.rc);
-      c->ep_acc_scale = 1.f; c->ep_bias_scale = c->ss;
-      op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, 2, 0, nullptr, 0, nullptr, d.p, 0);
+      ConvOpt o;
+      o.stride = 2; o.pad_lo = 0; o.bias_scale = c->ss;
+      op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, d.p, o);
       wsfree(c, x); x = d; H /= 2; Wd /= 2;
     }
   }
@@ -287,11 +295,7 @@ ia2p_status ia2p_vae_finalize_weights(ia2p_vae* c) { return rc_finalize(c, "VAE"
 size_t ia2p_vae_workspace_bytes(ia2p_vae* c, int B, int h, int w, int decode) {
   if (!c || vae_check(c, B, h, w) != IA2P_OK) return 0;
   const int f = 1 << (c->cfg.n_blocks - 1);
-  c->dry = true; c->failed = false; c->record = false;
-  c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
-  if (decode) (void)vae_run_decode(c, nullptr, nullptr, B, h, w); else (void)vae_run_encode(c, nullptr, nullptr, B, h * f, w * f);
-  c->dry = false;
-  return c->failed ? 0 : c->ws.high + 256;
+  return pass_dry(c, [&] { return decode ? vae_run_decode(c, nullptr, nullptr, B, h, w) : vae_run_encode(c, nullptr, nullptr, B, h * f, w * f); });
 }
 
 static ia2p_status vae_run(ia2p_vae* c, void* stream, const void* in, void* out, int B, int h, int w, void* ws, size_t ws_bytes, bool decode) {
@@ -301,22 +305,10 @@ static ia2p_status vae_run(ia2p_vae* c, void* stream, const void* in, void* out,
   if (st != IA2P_OK) return st;
   if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
   const int f = 1 << (c->cfg.n_blocks - 1);
-  const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
-  const size_t usable = ws_bytes - (base - (uintptr_t)ws);
-  const int key = decode ? 1 : 2;
-  if (c->wseq_key != key) {
-    c->wseq.clear();
-    c->dry = true; c->record = true; c->failed = false;
-    c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
-    if (decode) (void)vae_run_decode(c, nullptr, nullptr, B, h, w); else (void)vae_run_encode(c, nullptr, nullptr, B, h * f, w * f);
-    c->dry = false; c->record = false; c->wseq_key = key;
-  }
-  c->widx = 0; c->dry = false; c->failed = false; c->stream = (hipStream_t)stream;
-  c->ws.reset(usable); c->ws_base = (char*)base;
-  st = decode ? vae_run_decode(c, (const half_t*)in, (half_t*)out, B, h, w) : vae_run_encode(c, (const half_t*)in, (half_t*)out, B, h * f, w * f);
-  if (c->failed && st == IA2P_OK) st = IA2P_ERR_HIP;
-  if (c->failed && c->err == "workspace too small") st = IA2P_ERR_NOMEM;
-  return st;
+  st = pass_enter(c, stream, ws, ws_bytes);
+  if (st != IA2P_OK) return st;
+  pass_record(c, decode ? 1 : 2, [&] { return decode ? vae_run_decode(c, nullptr, nullptr, B, h, w) : vae_run_encode(c, nullptr, nullptr, B, h * f, w * f); });
+  return pass_leave(c, decode ? vae_run_decode(c, (const half_t*)in, (half_t*)out, B, h, w) : vae_run_encode(c, (const half_t*)in, (half_t*)out, B, h * f, w * f));
 }
 ia2p_status ia2p_vae_decode(ia2p_vae* c, void* stream, const void* latents, void* image, int B, int h, int w, void* ws, size_t ws_bytes) {
   return vae_run(c, stream, latents, image, B, h, w, ws, ws_bytes, true);

@@ -140,11 +140,7 @@ static ia2p_status vit_check(ia2p_vit* c, int B) {
 }
 size_t ia2p_vit_workspace_bytes(ia2p_vit* c, int B) {
   if (!c || vit_check(c, B) != IA2P_OK) return 0;
-  c->dry = true; c->failed = false; c->record = false;
-  c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
-  (void)vit_run(c, nullptr, B, nullptr, (half_t*)1);
-  c->dry = false;
-  return c->failed ? 0 : c->ws.high + 256;
+  return pass_dry(c, [&] { return vit_run(c, nullptr, B, nullptr, (half_t*)1); });
 }
 ia2p_status ia2p_vit_encode(ia2p_vit* c, void* stream, const void* pixels, int B, float* out, void* last_hidden, void* ws, size_t ws_bytes) {
   if (!c || !pixels || !out || !ws) return fail(c, IA2P_ERR_INVALID, "vit_encode: null argument");
@@ -156,20 +152,8 @@ ia2p_status ia2p_vit_encode(ia2p_vit* c, void* stream, const void* pixels, int B
     st = vit_fold(c, (hipStream_t)stream, false);
     if (st != IA2P_OK) return st;
   }
-  const uintptr_t base = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
-  if (ws_bytes < base - (uintptr_t)ws) return fail(c, IA2P_ERR_NOMEM, "workspace too small");
-  const size_t usable = ws_bytes - (base - (uintptr_t)ws);
-  if (c->wseq_key != 1) {         // weight-prefetch plan: the contractions of a pass in launch order (the same for every B)
-    c->wseq.clear();
-    c->dry = true; c->record = true; c->failed = false;
-    c->ws.reset((size_t)1 << 46); c->ws_base = nullptr;
-    (void)vit_run(c, nullptr, B, nullptr, nullptr);
-    c->dry = false; c->record = false; c->wseq_key = 1;
-  }
-  c->widx = 0; c->dry = false; c->failed = false; c->stream = (hipStream_t)stream;
-  c->ws.reset(usable); c->ws_base = (char*)base;
-  st = vit_run(c, (const half_t*)pixels, B, out, (half_t*)last_hidden);
-  if (c->failed && st == IA2P_OK) st = IA2P_ERR_HIP;
-  if (c->failed && c->err == "workspace too small") st = IA2P_ERR_NOMEM;
-  return st;
+  st = pass_enter(c, stream, ws, ws_bytes);
+  if (st != IA2P_OK) return st;
+  pass_record(c, 1, [&] { return vit_run(c, nullptr, B, nullptr, nullptr); });      // weight-prefetch plan: the contractions of a pass in launch order (the same for every B)
+  return pass_leave(c, vit_run(c, (const half_t*)pixels, B, out, (half_t*)last_hidden));
 }

@@ -23,15 +23,21 @@ inline hipError_t xf_fold(RunCtx* c, const std::vector<CLayer>& layers, int H, i
 template <class Attn>
 inline void xf_layer(RunCtx* c, const CLayer& l, half_t* x, half_t* qkv, half_t* att, half_t* ff, float* st, int& slots, int M, int H, int I, float eps, int act, Attn&& attn) {
   auto Fp = [&](size_t off) { return (const float*)(c->arena + off); };
+  GemmOpt to_x;      // a GEMM that writes x leaves the row statistics of its output
+  to_x.stats = st; to_x.stat_slots = &slots;
   {
     const LnIn ln{st, slots, Fp(l.cs1), Fp(l.lb1), eps};
-    op_gemm(c, x, H, W_(c, l.fqkv), nullptr, nullptr, 0, qkv, 3 * H, M, 3 * H, H, 0, 0, 0, 0, 0, &ln);
+    GemmOpt o;
+    o.ln = &ln;
+    op_gemm(c, x, H, W_(c, l.fqkv), nullptr, nullptr, 0, qkv, 3 * H, M, 3 * H, H, o);
   }
   attn();
-  op_gemm(c, att, H, W_(c, l.wo), W_(c, l.bo), x, H, x, H, M, H, H, 0, 0, 0, 0, 0, nullptr, st, &slots);
+  op_gemm(c, att, H, W_(c, l.wo), W_(c, l.bo), x, H, x, H, M, H, H, to_x);
   {
     const LnIn ln{st, slots, Fp(l.cs2), Fp(l.lb2), eps};
-    op_gemm(c, x, H, W_(c, l.f1), nullptr, nullptr, 0, ff, I, M, I, H, 0, 0, 0, 0, 0, &ln, nullptr, nullptr, act);
+    GemmOpt o;
+    o.ln = &ln; o.act = act;
+    op_gemm(c, x, H, W_(c, l.f1), nullptr, nullptr, 0, ff, I, M, I, H, o);
   }
-  op_gemm(c, ff, I, W_(c, l.w2), W_(c, l.b2), x, H, x, H, M, H, I, 0, 0, 0, 0, 0, nullptr, st, &slots);
+  op_gemm(c, ff, I, W_(c, l.w2), W_(c, l.b2), x, H, x, H, M, H, I, to_x);
 }

@@ -74,6 +74,43 @@ def test_workspace_scales_with_batch(lib):
     lib.ia2p_destroy(ctx)
 
 
+def test_workspace_bytes_are_the_recorded_ones(lib):
+    """every executor's workspace query (host dry runs over a first-fit allocator: the ORDER of allocations decides the answer) returns the bytes it returned before the
+    pass protocol moved into engine_rt (pass_dry) and run_resnet's two GroupNorm-before-convolution branches became one helper. UNet: the maximum over the four GroupNorm
+    modes, on the cost-model plans and with every eligible 3x3 site on its GroupNorm-fused plan."""
+    from instructany2pix_amd import _ffi
+    from instructany2pix_amd import imagebind as ib
+    from instructany2pix_amd.config import sdxl_base, tiny, tiny_clip, tiny_vae
+    lib.ia2p_plan_clear()
+    unet = {"tiny": (tiny(), {(-1, 1, 16, 16, 77): 1889280, (-1, 2, 16, 24, 77): 4474112, (1, 1, 16, 16, 77): 1897472, (1, 2, 16, 24, 77): 4523264}),
+            "sdxl": (sdxl_base(), {(-1, 1, 64, 64, 77): 78135808, (-1, 8, 64, 64, 77): 457310464, (1, 1, 64, 64, 77): 78135808, (1, 8, 64, 64, 77): 457310464})}
+    try:
+        for name, (cfg, want) in unet.items():
+            ctx = C.c_void_p()
+            _ffi.check(lib.ia2p_create(C.byref(_ffi.make_config(cfg)), C.byref(ctx)))
+            for (plan, *shape), n in want.items():
+                lib.ia2p_debug_set_gn_plan(plan)
+                assert lib.ia2p_workspace_bytes(ctx, *shape) == n, (name, plan, shape)
+            lib.ia2p_destroy(ctx)
+    finally:
+        lib.ia2p_debug_set_gn_plan(-1)
+    h = C.c_void_p()
+    _ffi.check(lib.ia2p_vae_create(C.byref(_ffi.make_vae_config(tiny_vae())), C.byref(h)), None, vae=True)
+    for (B, hh, ww, decode), n in {(2, 8, 8, 1): 1343744, (2, 8, 8, 0): 819456, (3, 16, 16, 1): 7913728, (3, 16, 16, 0): 4768000}.items():
+        assert lib.ia2p_vae_workspace_bytes(h, B, hh, ww, decode) == n, (B, hh, ww, decode)
+    lib.ia2p_vae_destroy(h)
+    towers = ib.imagebind_huge_config()
+    for (m, B), n in {("vision", 1): 11226112, ("vision", 3): 33677568, ("audio", 1): 6001920, ("audio", 3): 10964224}.items():
+        h = C.c_void_p()
+        _ffi.check(lib.ia2p_vit_create(C.byref(_ffi.make_vit_config(getattr(towers, m))), C.byref(h)), None, vit=True)
+        assert lib.ia2p_vit_workspace_bytes(h, B) == n, (m, B)
+        lib.ia2p_vit_destroy(h)
+    h = C.c_void_p()
+    _ffi.check(lib.ia2p_clip_create(C.byref(_ffi.make_clip_config(tiny_clip(64, "gelu"))), C.byref(h)), None, clip=True)
+    assert lib.ia2p_clip_workspace_bytes(h, 3, 77) == 418816
+    lib.ia2p_clip_destroy(h)
+
+
 def test_gemm_plan_is_a_pure_host_function_and_the_plan_table_round_trips(lib):
     """tile / K-split choice needs no GPU: cost model by default, measured-plan table (ia2p_autotune) when present"""
     def plan(M, N, K, conv=0, geglu=0):

@@ -4,7 +4,6 @@ tests/imagebind_ref.py, fp32 on the CPU with the same fp16-rounded weights and i
 Tolerances: the attention launch alone rel-L2 < 2e-3 (what test_ops_gpu.py::test_self_attention holds `ia2p_attention` to), a dominant late key max abs < 6e-3
 (test_self_attention_online_softmax_rescale); tower outputs rel-L2 <= 5e-3 (tests/test_clip_gpu.py: the same GEMMs, fp16 activations vs an fp32 oracle);
 end to end after L2 normalisation <= 1e-2 (normalising a vector at most doubles a relative error of 5e-3)."""
-import hashlib
 import os
 from dataclasses import replace
 
@@ -224,26 +223,3 @@ def test_pipeline_modality_embeds(tiny_model, files):
     own = torch.cat([model({"vision": ib.load_and_transform_vision_data([a], DEV)})["vision"], model({"audio": ib.load_and_transform_audio_data([c], DEV)})["audio"]]).cpu()
     own = own / own.norm(dim=-1, keepdim=True) * 20
     assert torch.allclose(out, own, atol=1e-5)
-
-
-# ---- the text towers share the block with the ViT executor now: same bits as before -----------------------------------------------------------------------------
-CLIP_SHA256_PARENT = "03f2a83fb3b60b0a0fc165e30c4546de8708939a0225ccbdd205ecd7ef4d472f"      # recorded from a run of the parent commit on an MI355X
-
-
-def test_clip_outputs_bit_identical_to_the_parent():
-    from instructany2pix_amd.clip import HipCLIPTextModel
-    from instructany2pix_amd.config import tiny_clip
-    from instructany2pix_amd.weights import clip_param_specs, synthetic_state_dict
-    cfg = tiny_clip(64, "gelu")
-    hip = HipCLIPTextModel(cfg, DEV)
-    hip.load_state_dict(synthetic_state_dict(clip_param_specs(cfg), seed=21))
-    g = torch.Generator().manual_seed(5)
-    ids = torch.randint(3, cfg.vocab_size - 1, (3, 77), generator=g)
-    ids[:, 0] = 0
-    ids[:, 40:] = cfg.vocab_size - 1
-    out = hip(ids, output_hidden_states=True, want_last_hidden=True)
-    torch.cuda.synchronize()
-    h = hashlib.sha256()
-    for t in (out.hidden_states[-2], out.last_hidden_state, out.text_embeds):
-        h.update(t.cpu().contiguous().numpy().tobytes())
-    assert h.hexdigest() == CLIP_SHA256_PARENT
