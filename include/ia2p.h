@@ -491,6 +491,32 @@ ia2p_status ia2p_llm_prefill_slot(ia2p_llm* llm, void* stream, int slot, const v
  * than ia2p_llm_batch_workspace_bytes(llm, 0, n). A refused call changes no position. */
 ia2p_status ia2p_llm_decode_batch(ia2p_llm* llm, void* stream, const int32_t* slots, const int32_t* token_ids, int n, float* hidden_out, float* logits_out,
                                   void* workspace, size_t workspace_bytes);
+/* ia2p_llm_decode_batch with the ids in DEVICE memory: row r embeds dev_tokens[token_index[r]] (dev_tokens: int32, device, e.g. what ia2p_sample_tokens wrote on
+ * the same stream; token_index: HOST array [n] of non-negative indices into it, or NULL for 0..n-1 -- the caller answers for the buffer holding them). The host
+ * never reads the ids: the embedding kernel does, and clamps an id outside [0, vocab_size) into the table (a sampler's -1 embeds row 0; the caller finds the -1
+ * when it reads the token and discards the step). Everything else -- checks, statuses, launches, bits of a row given its id -- is ia2p_llm_decode_batch's; the
+ * vocabulary check of the ids is the one check that cannot be made on the host. */
+ia2p_status ia2p_llm_decode_batch_dev(ia2p_llm* llm, void* stream, const int32_t* slots, const int32_t* dev_tokens, const int32_t* token_index, int n,
+                                      float* hidden_out, float* logits_out, void* workspace, size_t workspace_bytes);
+/* ---- Sampling on the device -------------------------------------------------------------------------------------------------------------------------
+ * One token per logits row, by the step transformers' sampling loop applies (TemperatureLogitsWarper -> TopKLogitsWarper -> softmax -> one draw):
+ * logits fp32, row r at logits + r * ld (device; ld = 0 draws M times from one row, otherwise ld >= V), M = 1..4096 rows, V = 1..2^20, any alignment of a row.
+ *   do_sample = 0   tokens_out[r] = the lowest index among the row's maxima; nothing else is written, seeds / steps may be NULL
+ *   do_sample = 1   score = logit / temperature (fp32, temperature > 0). 0 < top_k < V keeps every index whose score is >= the k-th largest score of the row
+ *                   (ties at that value are all kept, as `scores < kth` removes nothing equal); any other top_k keeps everything. p = exp(score - max) / sum over
+ *                   the kept set, fp32. tokens_out[r] = the first kept index, in ascending order, whose inclusive cumulative sum exceeds u * sum; if rounding
+ *                   leaves none, the last index with a positive term. An index whose term is 0 (a -inf entry, an underflow) is never drawn.
+ *   u               = (word 0 of Philox4x32-10 at counter (steps[r], 0, 0, 0) under key (low, high half of seeds[r])) >> 8, times 2^-24: in [0, 1). The draw of
+ *                   a row depends on its logits, its seed and its step only -- not on M, the row's place or alignment, or the other rows.
+ * A row holding NaN or +inf (also: a score that overflows), or whose maximum is -inf, gets token -1 and no probs_out row.
+ * seeds, steps: HOST arrays [M]. For M <= 8 they travel by value in the kernel arguments and nothing is copied to the device. For M > 8 the call allocates a
+ * device staging block, copies both arrays into it on `stream`, and waits for the stream before it frees the block and returns (a path for tests and tools;
+ * a decode step never has more than IA2P_LLM_MAX_ROWS rows).
+ * tokens_out: int32 [M], device. probs_out: fp32 [M, V] dense, device, or NULL: the whole row, exactly 0.0f outside the kept set. u_out: fp32 [M], device,
+ * or NULL. Every sum has one fixed association: two launches give the same tokens and the same probs_out bits.
+ * IA2P_ERR_INVALID: a null or misaligned pointer, do_sample outside {0, 1}, a temperature that is not positive and finite. IA2P_ERR_SHAPE: M, V or ld. */
+ia2p_status ia2p_sample_tokens(void* stream, const float* logits, int64_t ld, int M, int V, float temperature, int top_k, int do_sample, const uint64_t* seeds,
+                               const uint32_t* steps, int32_t* tokens_out, float* probs_out, float* u_out);
 /* workspace that serves a prefill of any row count up to max_T (0: none; the largest need over 1..max_T, which is not monotone in T) and decode steps of up to
  * max_rows rows; 0 for max_T < 0 or max_rows outside 1..8 */
 size_t ia2p_llm_batch_workspace_bytes(ia2p_llm* llm, int max_T, int max_rows);

@@ -175,6 +175,8 @@ SIGNATURES = {
     "ia2p_llm_slot_position": (_I, [_P, _I]),
     "ia2p_llm_prefill_slot": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _SZ]),
     "ia2p_llm_decode_batch": (_I, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _P, _P, _SZ]),
+    "ia2p_llm_decode_batch_dev": (_I, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), _I, _P, _P, _P, _SZ]),
+    "ia2p_sample_tokens": (_I, [_P, _P, _I64, _I, _I, _F, _I, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _P, _P, _P]),
     "ia2p_llm_batch_workspace_bytes": (_SZ, [_P, _I, _I]),
     "ia2p_llm_gemv_rows": (_I, [_P, _P, _P, _P, _I, _I, _I]),
     "ia2p_llm_gemv_q4_rows": (_I, [_P, _P, _P, C.POINTER(_F), _P, _P, _I, _I, _I]),

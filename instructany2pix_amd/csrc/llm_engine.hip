@@ -105,8 +105,10 @@ static hipError_t llm_proj_gemv_rows(ia2p_llm* c, LlmGemv& a, const LlmRows& b, 
   return llm_launch_gemv_q4_rows(a, llm_q4(W_(c, w), W_(c, am), c->codebook), b, epi, c->stream);
 }
 
-// n rows, row r = token tokens[r] at the position of slot slots[r]: per layer five GEMV launches and one attention launch, each once for all rows
-static ia2p_status llm_run_decode_rows(ia2p_llm* c, const int32_t* slots, const int32_t* tokens, int n, float* hidden_out, float* logits_out) {
+// n rows, row r = token tokens[r] (dev_tokens == nullptr: host ids) or dev_tokens[tokens[r]] (ids in device memory, `tokens` the host indices into them) at
+// the position of slot slots[r]: per layer five GEMV launches and one attention launch, each once for all rows
+static ia2p_status llm_run_decode_rows(ia2p_llm* c, const int32_t* slots, const int32_t* tokens, const int32_t* dev_tokens, int n, float* hidden_out,
+                                       float* logits_out) {
   const ia2p_llm_config& g = c->cfg;
   const int H = g.hidden_size, I = g.intermediate_size;
   T2 xt = wsalloc(c, (size_t)2 * n * H), qt = wsalloc(c, (size_t)2 * n * H), at = wsalloc(c, (size_t)2 * n * H), ft = wsalloc(c, (size_t)2 * n * I);
@@ -115,7 +117,8 @@ static ia2p_status llm_run_decode_rows(ia2p_llm* c, const int32_t* slots, const 
     LlmTokRows ids{};
     int longest = 0;
     for (int r = 0; r < n; ++r) { ids.id[r] = tokens[r]; longest = std::max(longest, c->spos[slots[r]] + 1); }
-    hipLaunchKernelGGL(llm_rows_f32_kernel, dim3((H + 255) / 256, n), dim3(256), 0, c->stream, W_(c, c->tok), ids, xf, H);
+    if (dev_tokens) hipLaunchKernelGGL(llm_rows_dev_f32_kernel, dim3((H + 255) / 256, n), dim3(256), 0, c->stream, W_(c, c->tok), (const int*)dev_tokens, ids, xf, H, g.vocab_size);
+    else hipLaunchKernelGGL(llm_rows_f32_kernel, dim3((H + 255) / 256, n), dim3(256), 0, c->stream, W_(c, c->tok), ids, xf, H);
     CHECK_LAUNCH(c, hipGetLastError(), "llm embedding rows");
     auto rows = [&](const float* x, size_t xs, float* out, size_t os) {
       LlmRows b{};
@@ -206,7 +209,7 @@ static ia2p_status llm_run_prefill(ia2p_llm* c, const half_t* embeds, int T, flo
 
 // workspace need of a prefill of T rows (T > 0) or of a decode step of n rows: a host dry run
 static size_t llm_dry(ia2p_llm* c, int T, int n = 1) {
-  return pass_dry(c, [&] { return T > 0 ? llm_run_prefill(c, nullptr, T, nullptr, nullptr) : llm_run_decode_rows(c, nullptr, nullptr, n, nullptr, nullptr); });
+  return pass_dry(c, [&] { return T > 0 ? llm_run_prefill(c, nullptr, T, nullptr, nullptr) : llm_run_decode_rows(c, nullptr, nullptr, nullptr, n, nullptr, nullptr); });
 }
 static ia2p_status llm_ready(ia2p_llm* c, const char* what) {
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "%s before weights were finalized", what);
@@ -383,34 +386,49 @@ ia2p_status ia2p_llm_decode(ia2p_llm* c, void* stream, int token_id, float* hidd
   st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, 0));
   if (st != IA2P_OK) return st;
   const int32_t slot = 0, token = token_id;
-  st = pass_leave(c, llm_run_decode_rows(c, &slot, &token, 1, hidden_out, logits_out));
+  st = pass_leave(c, llm_run_decode_rows(c, &slot, &token, nullptr, 1, hidden_out, logits_out));
   if (st == IA2P_OK) c->spos[0] += 1;
+  return st;
+}
+// the batched decode step behind both entry points: `tokens` are host ids (dev_tokens == nullptr; checked against the vocabulary) or host indices into dev_tokens
+static ia2p_status llm_decode_rows_at(ia2p_llm* c, const char* what, void* stream, const int32_t* slots, const int32_t* tokens, const int32_t* dev_tokens, int n,
+                                      float* hidden_out, float* logits_out, void* ws, size_t ws_bytes) {
+  if (!c || !slots || !tokens || !hidden_out || !logits_out || !ws) return fail(c, IA2P_ERR_INVALID, "%s: null argument", what);
+  ia2p_status st = llm_ready(c, what);
+  if (st != IA2P_OK) return st;
+  if (n < 1 || n > LLM_MAX_ROWS) return fail(c, IA2P_ERR_INVALID, "%s: %d rows (1..%d)", what, n, LLM_MAX_ROWS);
+  for (int r = 0; r < n; ++r) {
+    if (slots[r] < 0 || slots[r] >= c->n_slots) return fail(c, IA2P_ERR_INVALID, "%s: row %d names slot %d, the cache has %d", what, r, slots[r], c->n_slots);
+    for (int p = 0; p < r; ++p)
+      if (slots[p] == slots[r]) return fail(c, IA2P_ERR_INVALID, "%s: slot %d is named twice (rows %d and %d)", what, slots[r], p, r);
+  }
+  for (int r = 0; r < n; ++r) {
+    const int pos = c->spos[slots[r]];
+    if (pos < 1) return fail(c, IA2P_ERR_STATE, "%s: slot %d before a prefill (position 0)", what, slots[r]);
+    if (pos >= c->max_pos) return fail(c, IA2P_ERR_SHAPE, "%s: slot %d at position %d is past the cache (%d positions)", what, slots[r], pos, c->max_pos);
+    if (dev_tokens) {
+      if (tokens[r] < 0) return fail(c, IA2P_ERR_INVALID, "%s: token index %d of row %d", what, tokens[r], r);
+    } else if (tokens[r] < 0 || tokens[r] >= c->cfg.vocab_size) {
+      return fail(c, IA2P_ERR_SHAPE, "%s: token %d of row %d outside the vocabulary (%d)", what, tokens[r], r, c->cfg.vocab_size);
+    }
+  }
+  st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, 0, n), true);
+  if (st != IA2P_OK) return st;
+  st = pass_leave(c, llm_run_decode_rows(c, slots, tokens, dev_tokens, n, hidden_out, logits_out));
+  if (st == IA2P_OK)
+    for (int r = 0; r < n; ++r) c->spos[slots[r]] += 1;
   return st;
 }
 ia2p_status ia2p_llm_decode_batch(ia2p_llm* c, void* stream, const int32_t* slots, const int32_t* token_ids, int n, float* hidden_out, float* logits_out, void* ws,
                                   size_t ws_bytes) {
-  if (!c || !slots || !token_ids || !hidden_out || !logits_out || !ws) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch: null argument");
-  ia2p_status st = llm_ready(c, "llm_decode_batch");
-  if (st != IA2P_OK) return st;
-  if (n < 1 || n > LLM_MAX_ROWS) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch: %d rows (1..%d)", n, LLM_MAX_ROWS);
-  for (int r = 0; r < n; ++r) {
-    if (slots[r] < 0 || slots[r] >= c->n_slots) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch: row %d names slot %d, the cache has %d", r, slots[r], c->n_slots);
-    for (int p = 0; p < r; ++p)
-      if (slots[p] == slots[r]) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch: slot %d is named twice (rows %d and %d)", slots[r], p, r);
-  }
-  for (int r = 0; r < n; ++r) {
-    const int pos = c->spos[slots[r]];
-    if (pos < 1) return fail(c, IA2P_ERR_STATE, "llm_decode_batch: slot %d before a prefill (position 0)", slots[r]);
-    if (pos >= c->max_pos) return fail(c, IA2P_ERR_SHAPE, "llm_decode_batch: slot %d at position %d is past the cache (%d positions)", slots[r], pos, c->max_pos);
-    if (token_ids[r] < 0 || token_ids[r] >= c->cfg.vocab_size)
-      return fail(c, IA2P_ERR_SHAPE, "llm_decode_batch: token %d of row %d outside the vocabulary (%d)", token_ids[r], r, c->cfg.vocab_size);
-  }
-  st = llm_enter(c, stream, ws, ws_bytes, llm_dry(c, 0, n), true);
-  if (st != IA2P_OK) return st;
-  st = pass_leave(c, llm_run_decode_rows(c, slots, token_ids, n, hidden_out, logits_out));
-  if (st == IA2P_OK)
-    for (int r = 0; r < n; ++r) c->spos[slots[r]] += 1;
-  return st;
+  return llm_decode_rows_at(c, "llm_decode_batch", stream, slots, token_ids, nullptr, n, hidden_out, logits_out, ws, ws_bytes);
+}
+ia2p_status ia2p_llm_decode_batch_dev(ia2p_llm* c, void* stream, const int32_t* slots, const int32_t* dev_tokens, const int32_t* token_index, int n, float* hidden_out,
+                                      float* logits_out, void* ws, size_t ws_bytes) {
+  if (!dev_tokens) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch_dev: null argument");
+  if (((uintptr_t)dev_tokens) & 3) return fail(c, IA2P_ERR_INVALID, "llm_decode_batch_dev: the token buffer must be 4-byte aligned");
+  static const int32_t in_order[LLM_MAX_ROWS] = {0, 1, 2, 3, 4, 5, 6, 7};
+  return llm_decode_rows_at(c, "llm_decode_batch_dev", stream, slots, token_index ? token_index : in_order, dev_tokens, n, hidden_out, logits_out, ws, ws_bytes);
 }
 static LlmRows gemv_rows_args(const float* x, float* out, int N, int K, int M) {
   LlmRows b{};

@@ -357,6 +357,13 @@ __global__ __launch_bounds__(256) void llm_rows_f32_kernel(const half_t* tok, Ll
   const half_t* src = tok + (size_t)ids.id[blockIdx.y] * H;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < H; i += gridDim.x * 256) dst[(size_t)blockIdx.y * H + i] = (float)src[i];
 }
+// the same with the ids in device memory (ia2p_llm_decode_batch_dev: the sampler's output is never read by the host in between): row r takes
+// dev_ids[idx.id[r]], the indices by value. The id is data another kernel wrote, so it is clamped into the table here and never indexes it unchecked.
+__global__ __launch_bounds__(256) void llm_rows_dev_f32_kernel(const half_t* tok, const int* dev_ids, LlmTokRows idx, float* dst, int H, int vocab) {
+  const int id = min(max(dev_ids[idx.id[blockIdx.y]], 0), vocab - 1);
+  const half_t* src = tok + (size_t)id * H;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < H; i += gridDim.x * 256) dst[(size_t)blockIdx.y * H + i] = (float)src[i];
+}
 
 // ---- launchers ------------------------------------------------------------------------------------------------------
 // the run-time epilogue as a compile-time constant: f(std::integral_constant<int, EPI>) picks the kernel instantiation (the one switch over the four)

@@ -11,8 +11,10 @@
   vicuna_v1_prompt(inst)            <- `conv_templates['vicuna_v1']` with one user turn and an open assistant turn (llm/conversation.py:51-62,252-262)
   parse_generation(...)             <- pipeline.py:213-279: what `forward_llm` reads out of the generated sequence and its hidden rows
 
-Everything between `inputs_embeds` and (final-normed hidden row, logits row) runs through `ia2p_llm_*`; sampling from the logits row, stopping and
-the text parsing are host code. The tokenizer is injected (its sentencepiece model is checkpoint data).
+Everything between `inputs_embeds` and (final-normed hidden row, logits row) runs through `ia2p_llm_*`; stopping and the text parsing are host code. The
+token is drawn from the logits row on the host (`sampler="host"`, the default: `sample_next` on torch's global RNG) or on the device (`sampler="device"`:
+`ia2p_sample_tokens`, one Philox stream per request, the next decode step reading the id from device memory while the host still checks the stopping
+criteria). The tokenizer is injected (its sentencepiece model is checkpoint data).
 
 Weight format. The reference's live call loads the checkpoint with `load_in_4bit=True, bnb_4bit_compute_dtype=torch.float32` and names no
 `bnb_4bit_quant_type` (pipeline.py:28-31). The default of the transformers version it pins (4.34.1) is believed to be "fp4" without double
@@ -116,6 +118,30 @@ def sample_next(logits: torch.Tensor, do_sample: bool = True, temperature: float
     return torch.multinomial(sample_probs(logits, temperature, top_k), num_samples=1).squeeze(1)
 
 
+SAMPLERS = ("host", "device")
+
+
+def _resolve_sampler(sampler, default=None):
+    """the `sampler` argument of the constructor and of `generate` / `generate_batch` (None there: the constructor's choice)"""
+    if sampler is None and default is not None:
+        return default
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler {sampler!r}: one of {SAMPLERS}")
+    return sampler
+
+
+def _resolve_seeds(seeds, n_req):
+    """one Philox key per request: the given ones, or 63-bit draws from torch's global CPU generator in request order (`torch.manual_seed` fixes a run)"""
+    if seeds is None:
+        return [int(torch.randint(0, 2 ** 63 - 1, (1,)).item()) for _ in range(n_req)]
+    seeds = [int(s) for s in seeds]
+    if len(seeds) != n_req:
+        raise ValueError(f"{len(seeds)} seeds for {n_req} requests: one per request")
+    if any(s < 0 or s >= 2 ** 64 for s in seeds):
+        raise ValueError("a seed is a 64-bit unsigned integer")
+    return seeds
+
+
 class _LastOnly(tuple):
     """`hidden_states[i]` of the output object: only [-1] is materialised, and of it only the last position (all the reference reads:
     `output_ids.hidden_states[i][-1][:, -1:]`, pipeline.py:236,242,257)."""
@@ -179,10 +205,13 @@ class HipInstructAny2PixLM:
     PROJECTOR, PREDICTOR = "model.vae_projector_image", "model.vae_predictor_image"
 
     MAX_ROWS = 8                       # IA2P_LLM_MAX_ROWS: sequences per decode_batch call
+    sampler = "host"                   # the constructor sets it per instance; the class default serves subclasses that stand in for the engine without
+                                       # running the constructor (tests/test_llm_batch_cpu.py drives `generate_batch` through one)
 
     def __init__(self, config: LLMConfig, device="cuda:0", max_positions: int = 1024, video_token_id: Optional[int] = None, *,
-                 load_in_4bit: bool = False, bnb_4bit_quant_type: str = "fp4", quantize_heads: bool = True, max_batch: int = 1):
-        """max_batch: cache slots, i.e. requests `generate_batch` decodes together (a slot holds `max_positions` rows of every layer: 512 MiB
+                 load_in_4bit: bool = False, bnb_4bit_quant_type: str = "fp4", quantize_heads: bool = True, max_batch: int = 1, sampler: str = "host"):
+        """sampler: where `generate` / `generate_batch` draw the next token, "host" (torch on the CPU, from a copy of the logits row) or "device"
+        (`ia2p_sample_tokens` on the row where it lies); either call takes `sampler=` to override it. max_batch: cache slots, i.e. requests `generate_batch` decodes together (a slot holds `max_positions` rows of every layer: 512 MiB
         at Vicuna-7B size and 1024 positions; the default keeps the single-sequence memory). load_in_4bit / bnb_4bit_quant_type: the reference's `from_pretrained` keywords. quantize_heads: the two projector heads are
         `nn.Linear`s inside the model, so the reference's loader quantises them with the decoder (it skips `lm_head` only); False keeps
         their fp16 weights."""
@@ -190,6 +219,7 @@ class HipInstructAny2PixLM:
             raise ValueError(f"bnb_4bit_quant_type '{bnb_4bit_quant_type}': one of {sorted(BNB_4BIT_CODEBOOKS)}")
         if max_batch < 1:
             raise ValueError(f"max_batch {max_batch}: at least one slot")
+        self.sampler = _resolve_sampler(sampler)
         self.config = config.validate()
         self.device = torch.device(device)
         self.max_positions = max_positions
@@ -212,6 +242,7 @@ class HipInstructAny2PixLM:
         d = projector_depth(config.mm_projector_type)
         self._projector, self._predictor = _Head(self.PROJECTOR, d), _Head(self.PREDICTOR, d)
         self._ws, self._ws_T = None, 0
+        self._tok_dev = self._tok_host = None              # device sampler: the drawn ids on the device and their pinned host copy
         self.dtype = torch.float16
 
     def __del__(self):
@@ -361,6 +392,40 @@ class HipInstructAny2PixLM:
                                                     _ffi.ptr(ws), ws.numel()))
         return hid, logits
 
+    @torch.no_grad()
+    def decode_batch_dev(self, slots, dev_tokens: torch.Tensor, token_index=None):
+        """`decode_batch` with the ids in device memory: row r embeds dev_tokens[token_index[r]] (dev_tokens: int32 on the device, token_index: host
+        indices into it, None = 0..n-1). The host never reads the ids; an id outside the vocabulary is clamped into the table by the kernel."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        index = list(range(n)) if token_index is None else [int(t) for t in token_index]
+        if len(index) != n:
+            raise ValueError(f"{n} slots for {len(index)} token indices")
+        if dev_tokens.dtype != torch.int32 or dev_tokens.device != self.device or (index and max(index) >= dev_tokens.numel()):
+            raise ValueError(f"dev_tokens must be int32 on {self.device} and hold every index of token_index")
+        ws = self._workspace(max(self._ws_T, 1))
+        hid = torch.empty(max(n, 1), self.config.hidden_size, dtype=torch.float32, device=self.device)
+        logits = torch.empty(max(n, 1), self.config.vocab_size, dtype=torch.float32, device=self.device)
+        ids = C.c_int32 * max(n, 1)
+        self._check(self._lib.ia2p_llm_decode_batch_dev(self._h, _ffi.current_stream(), ids(*slots), _ffi.ptr(dev_tokens), ids(*index), n, _ffi.ptr(hid),
+                                                        _ffi.ptr(logits), _ffi.ptr(ws), ws.numel()))
+        return hid, logits
+
+    def sample_tokens(self, logits: torch.Tensor, seeds, steps, do_sample: bool = True, temperature: float = 0.3, top_k: Optional[int] = 50, out=None):
+        """`ia2p_sample_tokens` on the fp32 rows [n, vocab] of `logits` (device): row r drawn with key seeds[r] at counter steps[r] -> int32 [n] on the
+        device (`out`, or a new tensor). Nothing is synchronised."""
+        block = logits.reshape(-1, logits.shape[-1])
+        if block.dtype != torch.float32 or block.stride(1) != 1:
+            raise ValueError("logits must be fp32 rows")
+        n, V = block.shape
+        if len(seeds) != n or len(steps) != n:
+            raise ValueError(f"{n} rows, {len(seeds)} seeds, {len(steps)} steps")
+        out = torch.empty(n, dtype=torch.int32, device=block.device) if out is None else out[:n]
+        _ffi.check(self._lib.ia2p_sample_tokens(_ffi.current_stream(), C.c_void_p(block.data_ptr()), block.stride(0) if n > 1 else V, n, V, float(temperature),
+                                                int(top_k or 0), int(bool(do_sample)), (C.c_uint64 * n)(*seeds), (C.c_uint32 * n)(*steps), _ffi.ptr(out), None, None),
+                   None, llm=True)
+        return out
+
     def prepare_inputs_embeds(self, input_ids: torch.Tensor, extra_replacement=None) -> torch.Tensor:
         """`embed_tokens(input_ids)` with the modality vectors at the `<video>` positions, as any2pix_llama.py:277-291 builds them at
         inference: with n = len(mask), the first n `<video>` positions are candidates (`a[:n]`, `b[:n]`), those whose mask entry is INPUT
@@ -387,11 +452,18 @@ class HipInstructAny2PixLM:
 
     @torch.no_grad()
     def generate(self, input_ids, extra_replacement=None, do_sample: bool = True, temperature: float = 0.3, max_new_tokens: int = 100,
-                 stopping_criteria=None, top_k: Optional[int] = 50, **unused):
+                 stopping_criteria=None, top_k: Optional[int] = 50, sampler: Optional[str] = None, seed: Optional[int] = None, **unused):
         """-> object with `.sequences` ([1, prompt + new] on the host) and `.hidden_states` (one entry per new token;
-        `hidden_states[i][-1][:, -1:]` is step i's final-normed last-position row, [1, 1, hidden] fp32 on the device)."""
+        `hidden_states[i][-1][:, -1:]` is step i's final-normed last-position row, [1, 1, hidden] fp32 on the device).
+        sampler: "host" or "device" (None: the constructor's). seed ("device" only): the request's Philox key; None draws one from torch's global CPU
+        generator. The tokens of a seed are those the request gets inside any `generate_batch(sampler="device")` call under the same seed. Under "host"
+        `seed` is not used: that path draws from torch's global RNG, as it always has."""
+        sampler = _resolve_sampler(sampler, self.sampler)
         if input_ids.ndim != 2 or input_ids.shape[0] != 1:
             raise ValueError("input_ids must be [1, tokens] (batch 1, as the reference asserts)")
+        if sampler == "device":
+            return self._generate_device([input_ids], [extra_replacement], do_sample, temperature, max_new_tokens, [stopping_criteria], top_k,
+                                         None if seed is None else [seed])[0]
         seq = input_ids.detach().cpu().long()
         T = seq.shape[1]
         if T + max_new_tokens > self.max_positions:
@@ -414,7 +486,7 @@ class HipInstructAny2PixLM:
 
     @torch.no_grad()
     def generate_batch(self, input_ids_list, extra_replacements=None, do_sample: bool = True, temperature: float = 0.3, max_new_tokens: int = 100,
-                       stopping_criteria=None, top_k: Optional[int] = 50, **unused):
+                       stopping_criteria=None, top_k: Optional[int] = 50, sampler: Optional[str] = None, seeds=None, **unused):
         """`generate` for several requests. input_ids_list: [1, T_i] prompts; extra_replacements / stopping_criteria: one entry per request (an
         `extra_replacement` dict / a list of criteria, or None), or None. -> a list with one `generate`-shaped object per request
         (`.sequences` [1, T_i + new_i], `.hidden_states` with one entry per new token).
@@ -427,9 +499,20 @@ class HipInstructAny2PixLM:
         do_sample=False gives exactly the sequences and hidden rows of serial `generate(do_sample=False)` calls (a row of `decode_batch` equals
         the single-sequence step bit for bit). do_sample=True draws all active rows of a step with ONE `torch.multinomial` call over the
         [n_active, vocab] block, in request order: the draws of the requests interleave in the global RNG stream, so a batch is reproducible
-        for a seed but is not the stream serial `generate` calls would consume."""
+        for a seed but is not the stream serial `generate` calls would consume.
+
+        sampler="device" (None: the constructor's choice) draws on the device instead, request i from its own Philox stream keyed by seeds[i] (None: one
+        63-bit seed per request from torch's global CPU generator): each request then gets exactly the tokens and hidden rows of
+        `generate(sampler="device", seed=seeds[i])`, whatever shares its batch. See `_generate_device`. Under "host" `seeds` is checked for its length
+        and otherwise not used: that path draws from torch's global RNG, as it always has."""
+        sampler = _resolve_sampler(sampler, self.sampler)
         prompts = list(input_ids_list)
         n_req = len(prompts)
+        seeds = None if seeds is None else list(seeds)
+        if seeds is not None and len(seeds) != n_req:
+            raise ValueError(f"{len(seeds)} seeds for {n_req} requests: one per request")
+        if sampler == "device":
+            return self._generate_device(prompts, extra_replacements, do_sample, temperature, max_new_tokens, stopping_criteria, top_k, seeds)
         reps = list(extra_replacements) if extra_replacements is not None else [None] * n_req
         crits = list(stopping_criteria) if stopping_criteria is not None else [None] * n_req
         if len(reps) != n_req or len(crits) != n_req:
@@ -470,6 +553,69 @@ class HipInstructAny2PixLM:
                 if not active or step + 1 == max_new_tokens:
                     break
                 hid, logits = self.decode_batch([i - g0 for i in active], tokens)
+        return [SimpleNamespace(sequences=seqs[i], hidden_states=tuple(hidden[i])) for i in range(n_req)]
+
+
+    @torch.no_grad()
+    def _generate_device(self, prompts, extra_replacements, do_sample, temperature, max_new_tokens, stopping_criteria, top_k, seeds):
+        """`generate_batch` with the token drawn on the device. Per step of a group: `ia2p_sample_tokens` on the step's logits block, the ids copied
+        asynchronously into pinned host memory, an event behind the copy, and -- before the host waits for that event -- the next `decode_batch_dev`
+        for every row still active, reading its id from device memory. Only then are the ids read, appended and shown to the stopping criteria. A
+        request that turns out to have stopped has had one decode row too many computed: that row is dropped (it is never appended to
+        `hidden_states`, and the slot is reset at its next use), and from the next step on `token_index` names the live rows of the id buffer.
+        Row r of a step is drawn under (seed of its request, number of tokens the request has): nothing depends on the other rows."""
+        n_req = len(prompts)
+        reps = list(extra_replacements) if extra_replacements is not None else [None] * n_req
+        crits = list(stopping_criteria) if stopping_criteria is not None else [None] * n_req
+        if len(reps) != n_req or len(crits) != n_req:
+            raise ValueError(f"{n_req} prompts, {len(reps)} extra_replacements, {len(crits)} stopping_criteria: one entry per request")
+        seeds = _resolve_seeds(seeds, n_req) if do_sample or seeds is not None else [0] * n_req      # (argmax consumes no random numbers)
+        seqs = []
+        for p in prompts:
+            if p.ndim != 2 or p.shape[0] != 1:
+                raise ValueError("every prompt must be [1, tokens]")
+            if p.shape[1] + max_new_tokens > self.max_positions:
+                raise ValueError(f"{p.shape[1]} prompt tokens + {max_new_tokens} new ones do not fit {self.max_positions} cached positions")
+            seqs.append(p.detach().cpu().long())
+        if self._tok_dev is None:
+            self._tok_dev = torch.zeros(self.MAX_ROWS, dtype=torch.int32, device=self.device)
+            self._tok_host = torch.zeros(self.MAX_ROWS, dtype=torch.int32).pin_memory()
+        nl = self.config.num_hidden_layers + 1
+        hidden = [[] for _ in range(n_req)]
+        group = min(self.max_batch, self.MAX_ROWS)
+        for g0 in range(0, n_req, group):
+            block = list(range(g0, min(g0 + group, n_req)))              # the requests behind the rows of `logits`; request i lives in slot i - g0
+            rows = []
+            for i in block:
+                self.reset_slot(i - g0)
+                rows.append(self.prefill_slot(i - g0, self.prepare_inputs_embeds(seqs[i], reps[i])))
+            hid, logits = torch.stack([r[0] for r in rows]), torch.stack([r[1] for r in rows])
+            active = list(block)                                         # the requests that have not stopped: a subset of `block`, in its order
+            for step in range(max_new_tokens):
+                for i in active:
+                    hidden[i].append(_LastOnly(hid[block.index(i)].reshape(1, 1, -1), nl))
+                self.sample_tokens(logits, [seeds[i] for i in block], [step] * len(block), do_sample, temperature, top_k, out=self._tok_dev)
+                self._tok_host[:len(block)].copy_(self._tok_dev[:len(block)], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record()
+                drawn_for = block
+                if step + 1 < max_new_tokens:                            # one step ahead: every active row, before the host knows which of them stop
+                    hid, logits = self.decode_batch_dev([i - g0 for i in active], self._tok_dev, [block.index(i) for i in active])
+                    block = active
+                done.synchronize()
+                tokens = self._tok_host[:len(drawn_for)].tolist()
+                go_on = []
+                for i in active:
+                    t = tokens[drawn_for.index(i)]
+                    if t < 0:
+                        raise RuntimeError(f"request {i}: the logits of step {step} hold NaN or +inf, or nothing finite (no token can be drawn)")
+                    seqs[i] = torch.cat([seqs[i], torch.tensor([[t]], dtype=torch.long)], dim=1)
+                    if crits[i] is not None and any(bool(torch.as_tensor(c(seqs[i], None)).all()) for c in crits[i]):
+                        continue
+                    go_on.append(i)
+                active = go_on
+                if not active:
+                    break
         return [SimpleNamespace(sequences=seqs[i], hidden_states=tuple(hidden[i])) for i in range(n_req)]
 
 

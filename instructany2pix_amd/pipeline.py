@@ -238,7 +238,8 @@ class InstructAny2PixPipeline:
         return input_ids, extra_replacement, stopping_criteria
 
     def _llm_generate(self, inst, aux_info):
-        """:171-211: prompt, stopping criterion and the one `generate` call -> (input_ids, generate output)"""
+        """:171-211: prompt, stopping criterion and the one `generate` call -> (input_ids, generate output). Where the token is drawn (host or
+        device) is the LLM's own setting, `HipInstructAny2PixLM(sampler=...)`; `_llm_generate_batch` likewise."""
         input_ids, extra_replacement, stopping_criteria = self._llm_request(inst, aux_info)
         lm = self.any2pix_lm
         out = lm.generate(input_ids, images=None, do_sample=True, temperature=0.3, max_new_tokens=100, output_hidden_states=True, use_cache=False,

@@ -11,7 +11,10 @@ speak, the TOKEN CHOSEN at each step follows a script ("[ caption ] <base> <vide
 engine work, its logits and its sampling arithmetic still run.
 Prints per-stage wall times (stream-synchronised) after one warm-up request.
 
-    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4] [--imagebind]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)"""
+--sampler device (the switch of tools/llm_decode_bench.py; also spelled --llm-sampler) draws the token on the device (`HipInstructAny2PixLM(sampler="device")`): the sampler kernel runs on every step's logits row and the
+script then overwrites the id in device memory (one fill launch per step, which the product does not have), so the next decode step still reads it there.
+
+    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4] [--sampler host|device] [--imagebind]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)"""
 import argparse
 import os
 import sys
@@ -38,6 +41,7 @@ from stub_llm_tokenizer import ADDED_TOKENS, StubLlamaTokenizer
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--llm-bits", type=int, default=16, choices=(16, 4))
 _ap.add_argument("--llm-quant-type", default="fp4", choices=("fp4", "nf4"))
+_ap.add_argument("--sampler", "--llm-sampler", dest="llm_sampler", default="host", choices=("host", "device"))
 _ap.add_argument("--imagebind", action="store_true", help="encode the mm_data entries' files with the HIP ImageBind towers instead of seeded vectors")
 ARGS = _ap.parse_args()
 DEV = "cuda:0"
@@ -58,7 +62,8 @@ specs = ip_adapter_specs(bcfg, 1024)
 ck = {"image_proj": synthetic_state_dict(specs["image_proj"], seed=7), "ip_adapter": synthetic_state_dict(specs["ip_adapter"], seed=7)}
 lcfg = vicuna_7b(32000 + len(ADDED_TOKENS))
 ltok = StubLlamaTokenizer(32000)
-lm = llm_mod.HipInstructAny2PixLM(lcfg, DEV, max_positions=512, load_in_4bit=ARGS.llm_bits == 4, bnb_4bit_quant_type=ARGS.llm_quant_type)
+lm = llm_mod.HipInstructAny2PixLM(lcfg, DEV, max_positions=512, load_in_4bit=ARGS.llm_bits == 4, bnb_4bit_quant_type=ARGS.llm_quant_type,
+                                  sampler=ARGS.llm_sampler)
 lm.load_state_dict(iter_synthetic(llm_param_specs(lcfg), 9, DEV, torch.float16))
 print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior, LLM with {lm.weight_bits}-bit "
       f"projections: arena {lm.arena.numel() / 1e9:.2f} GB)", flush=True)
@@ -87,6 +92,15 @@ def scripted_sample_next(logits, *a, **k):
 
 
 llm_mod.sample_next = scripted_sample_next
+_sample_tokens = lm.sample_tokens
+
+
+def scripted_sample_tokens(logits, *a, **k):
+    out = _sample_tokens(logits, *a, **k)               # the sampler kernel of the step still runs
+    return out.fill_(next(_script))                     # (stream-ordered behind it: the look-ahead decode reads the scripted id)
+
+
+lm.sample_tokens = scripted_sample_tokens
 mm_data = [{"type": "image", "fname": "base.png", "image": image, "embed": torch.randn(1024, generator=g)},
            {"type": "image", "fname": "style.png", "image": image, "embed": torch.randn(1024, generator=g)}]      # (either may be chosen as the base)
 imb = None
@@ -128,7 +142,7 @@ _wrap(pipe.pipe.image_processor, "postprocess", "image_out")
 _wrap(pipe.ip_adapter_xl, "generate", "guided sampling loop (25 x B_eff=2, incl. image-token projection)")
 if imb is not None:
     _wrap(pipe, "_modality_embeds", "ImageBind (2 PNG files: load, transform, vision tower; inside forward_llm)")
-_wrap(pipe, "forward_llm", "LLM (forward_llm: prefill + 100 tokens + predictor heads)")
+_wrap(pipe, "forward_llm", f"LLM (forward_llm: prefill + 100 tokens + predictor heads, {ARGS.llm_sampler} sampler)")
 if getattr(pipe, "model", None) is not None:
     _wrap(pipe.model, "generate_diffusion", "embedding prior")
 _piperf_call = pipe.piperf.__call__

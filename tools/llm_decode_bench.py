@@ -19,7 +19,14 @@ the library had for M = 1, `ia2p_linear_small`.
           Part 2 gets one more line per shape and M: `ia2p_llm_gemv_rows` (and `ia2p_llm_gemv_q4_rows` with --bits 4) on the same pools, interleaved
           with the single-row launches, us per launch and per row.
 
-    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--bits 4] [--quant-type fp4] [--batch 1,2,4,8] [--skip-decode] [--skip-gemv]
+  --sampler host,device: whole `generate` (n = 1) and `generate_batch` (n = 8) calls, sampling on (temperature 0.3, top-k 50), 64-row prompts, no stopping
+          criterion, per format. The samplers named alternate in the one process (round 0 warms up); a call is timed stream-synchronised, once for --tokens new
+          tokens and once for one, and the figure is the difference per further token: ms per generated token with the prefills taken out. Under "host" the
+          tool passes no `sampler` keyword when the tree's `generate` has none, so the same command times a tree from before the keyword. Then the sampler
+          launch alone (`ia2p_sample_tokens` on 1 and 8 logits rows of the vocabulary, device events around 200 launches, us per launch).
+
+    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--bits 4] [--quant-type fp4] [--batch 1,2,4,8] [--sampler host,device] [--rounds 3]
+                                     [--skip-decode] [--skip-gemv]
 """
 import argparse
 import ctypes as C
@@ -102,6 +109,60 @@ def batch_part(layers, tokens, rows, bits=16, quant_type="fp4"):
             b, s1 = (t1 - t0) * 1e3 / tokens, (t3 - t2) * 1e3 / tokens
             print(f"[{fmt}] request {rnd}: n = {n}: decode_batch {b:.3f} ms per step, {n} serial decode steps {n * s1:.3f} ms ({s1:.3f} each), "
                   f"serial / batched {n * s1 / b:.2f}x, {n / (b * 1e-3):.0f} tokens per second over the {n} requests", flush=True)
+    del lm
+    torch.cuda.empty_cache()
+
+
+def sampler_part(layers, tokens, samplers, rounds, bits=16, quant_type="fp4"):
+    import inspect
+    cfg = vicuna_7b(32000)
+    cfg.num_hidden_layers = layers
+    lm = HipInstructAny2PixLM(cfg, DEV, max_positions=64 + tokens + 8, load_in_4bit=bits == 4, bnb_4bit_quant_type=quant_type, max_batch=8)
+    lm.load_state_dict(iter_synthetic(llm_param_specs(cfg), 7, DEV, torch.float16))
+    torch.cuda.synchronize()
+    fmt = "fp16" if bits == 16 else f"4-bit {quant_type}"
+    has_kw = "sampler" in inspect.signature(lm.generate).parameters
+    if not has_kw and samplers != ["host"]:
+        sys.exit("--sampler: this tree's generate() has the host sampler only")
+    g = torch.Generator().manual_seed(1)
+    prompts = [torch.randint(3, cfg.vocab_size, (1, 64), generator=g) for _ in range(8)]
+    print(f"[{fmt}] whole generate / generate_batch calls, {layers} layers, sampling at temperature 0.3, top-k 50; ms per generated token = "
+          f"(call with {tokens} new tokens - call with 1) / {tokens - 1}", flush=True)
+
+    def call(n, sampler, new):
+        kw = dict(do_sample=True, temperature=0.3, max_new_tokens=new, **({"sampler": sampler} if has_kw else {}))
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        if n == 1:
+            lm.generate(prompts[0], **kw)
+        else:
+            lm.generate_batch(prompts[:n], **kw)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for rnd in range(rounds + 1):          # round 0 warms up
+        for n in (1, 8):
+            for sampler in samplers:
+                torch.manual_seed(rnd)
+                one, full = call(n, sampler, 1), call(n, sampler, tokens)
+                print(f"[{fmt}] round {rnd}{' (warm-up)' if rnd == 0 else ''}: n = {n}, sampler {sampler}: {(full - one) / (tokens - 1):.3f} ms per generated token "
+                      f"(call of {tokens} tokens {full:.1f} ms, of one token {one:.1f} ms)", flush=True)
+    if "device" in samplers:
+        lib, s = _ffi.lib(), _ffi.current_stream()
+        V = cfg.vocab_size
+        logits = torch.randn(8, V, generator=torch.Generator().manual_seed(2)).to(DEV) * 4
+        out = torch.empty(8, dtype=torch.int32, device=DEV)
+        for n in (1, 8):
+            seeds, steps = (C.c_uint64 * n)(*range(1, n + 1)), (C.c_uint32 * n)(*range(n))
+            for do_sample, what in ((1, "temperature 0.3, top-k 50"), (0, "argmax")):
+                med = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(200):
+                        _ffi.check(lib.ia2p_sample_tokens(s, _ffi.ptr(logits), V, n, V, 0.3, 50, do_sample, seeds, steps, _ffi.ptr(out), None, None), None, llm=True)
+                    e1.record(); e1.synchronize()
+                    med.append(e0.elapsed_time(e1) * 1e3 / 200)
+                print(f"  ia2p_sample_tokens, {n} row{'s' if n > 1 else ''} of {V}, {what}: {statistics.median(med):.2f} us per launch (back to back, median of 5 x 200; min {min(med):.2f})", flush=True)
     del lm
     torch.cuda.empty_cache()
 
@@ -203,6 +264,8 @@ if __name__ == "__main__":
     ap.add_argument("--bits", type=int, default=16, choices=(16, 4))
     ap.add_argument("--quant-type", default="fp4", choices=sorted(BNB_4BIT_CODEBOOKS))
     ap.add_argument("--batch", default="", help="comma-separated row counts (1..8) for the batched decode and the multi-row GEMVs, e.g. 1,2,4,8")
+    ap.add_argument("--sampler", default="", help="comma-separated samplers (host, device) for the whole-call timing of generate / generate_batch")
+    ap.add_argument("--rounds", type=int, default=3, help="timed rounds of the --sampler part (after one warm-up round)")
     ap.add_argument("--skip-decode", action="store_true")
     ap.add_argument("--skip-gemv", action="store_true")
     a = ap.parse_args()
@@ -211,6 +274,9 @@ if __name__ == "__main__":
     rows = tuple(int(x) for x in a.batch.split(",") if x)
     if any(n < 1 or n > 8 for n in rows):
         sys.exit("--batch: row counts of 1..8")
+    samplers = [x for x in a.sampler.split(",") if x]
+    if any(x not in ("host", "device") for x in samplers):
+        sys.exit("--sampler: host, device or both")
     if not a.skip_gemv:
         gemv_part(a.reps, a.bits, a.quant_type, rows)
     if not a.skip_decode:
@@ -221,3 +287,7 @@ if __name__ == "__main__":
             decode_part(a.layers, a.tokens, 4, a.quant_type)
             if rows:
                 batch_part(a.layers, a.tokens, rows, 4, a.quant_type)
+    if samplers:
+        sampler_part(a.layers, a.tokens, samplers, a.rounds)
+        if a.bits == 4:
+            sampler_part(a.layers, a.tokens, samplers, a.rounds, 4, a.quant_type)
