@@ -525,6 +525,42 @@ size_t ia2p_llm_batch_workspace_bytes(ia2p_llm* llm, int max_T, int max_rows);
 ia2p_status ia2p_llm_gemv_rows(void* stream, const void* W, const float* x, float* out, int N, int K, int M);
 ia2p_status ia2p_llm_gemv_q4_rows(void* stream, const void* packed, const float* absmax, const float* codebook, const float* x, float* out, int N, int K,
                                   int M);
+/* ---- The other launches of the decode and prefill paths on their own (unit tests, tools) ---------------------------------------------------------------
+ * Each runs the launcher or kernel the drivers run, with the arithmetic and the fixed summation order it has inside a model; tests/llm_ops_ref.py holds an fp64
+ * reference and an error bound per operation. Every refusal is decided on the host before any launch, and a refused call writes nothing.
+ * Weights: W is fp16 [N, K] (absmax and codebook NULL, K a multiple of 8) or the packed codes of ia2p_llm_quantize_q4 with their absmax and codebook (K a multiple
+ * of 64, at most 14336). x: fp32 [M, K], M = 1..8 rows; one row runs the single-row kernels, and row m of a launch equals the single-row launch on that row bit
+ * for bit. gamma (optional, fp16 [K]) with eps folds RMSNorm(x) * gamma into the product: out = rstd * (W . (x gamma)), rstd = 1 / sqrt(mean(x^2) + eps).
+ * IA2P_ERR_INVALID: a null pointer, absmax without codebook or the reverse, an epilogue outside 0..2, hid without the plain epilogue and a gamma, a negative eps,
+ * a cache that is not 16-byte aligned (attention). IA2P_ERR_SHAPE: N, K, M as for ia2p_llm_gemv_rows / ia2p_llm_gemv_q4_rows, an odd N with SwiGLU, H not
+ * heads * 128, a position outside 0..8191 or rows that run past it. */
+#define IA2P_LLM_EPI_PLAIN 0  /* out[m][n] = r[n]: fp32 [M, N] */
+#define IA2P_LLM_EPI_RESID 1  /* out[m][n] += r[n]: fp32 [M, N], read and written */
+#define IA2P_LLM_EPI_SWIGLU 2 /* out[m][i] = silu(r[i]) * r[N / 2 + i]: fp32 [M, N / 2]; rows 0 .. N / 2 - 1 of W are the gate, the rest the up projection */
+/* the GEMV with an epilogue (o_proj, gate / up, down_proj, lm_head). hid (optional; plain epilogue with gamma): fp32 [M, K], the normed input rows x rstd gamma */
+ia2p_status ia2p_llm_gemv_epi(void* stream, const void* W, const float* absmax, const float* codebook, const float* x, const void* gamma, float eps, int epi,
+                              float* out, float* hid, int N, int K, int M);
+/* the QKV GEMV, W [3 H, K] = q | k | v rows: rotary embedding of q and k at the row's position (angle = fp32 product of the position and inv_freq[i], i the
+ * index of the pair (c, c + 64) inside its head; rotate_half convention) and the cache write. pos, k_cache, v_cache: HOST arrays [M] -- row m writes row pos[m]
+ * of its own caches (device, fp16 [positions, H]; k rotated, v as computed) and nothing else of them. q: fp32 [M, H], rotated. inv_freq: fp32 [64], device. */
+ia2p_status ia2p_llm_gemv_qkv(void* stream, const void* W, const float* absmax, const float* codebook, const float* x, const void* gamma, float eps,
+                              const float* inv_freq, const int32_t* pos, float* q, void* const* k_cache, void* const* v_cache, int H, int K, int M);
+/* attention of decoded rows: row m = softmax(q[m] . K^T / sqrt(128)) V per head over rows 0 .. pos[m] of its own caches; rows past pos[m] are never read.
+ * q, out: fp32 [M, H]; pos, k_cache, v_cache: HOST arrays [M]. */
+ia2p_status ia2p_llm_attention_rows(void* stream, const float* q, const void* const* k_cache, const void* const* v_cache, const int32_t* pos, float* out, int heads,
+                                    int H, int M);
+/* causal attention of prefill rows: row t of q (fp32 [T, H]) is at position p0 + t of one cache and sees its rows 0 .. p0 + t. out: fp16 [T, H]. */
+ia2p_status ia2p_llm_attention_prefill(void* stream, const float* q, const void* k_cache, const void* v_cache, void* out, int heads, int H, int p0, int T);
+/* the row kernels of the prefill path, fp16 in and out:
+ *   rmsnorm_rows     y [T, H] = x rstd gamma, the product rounded once
+ *   rope_cache_rows  qkv [T, 3 H] (q | k | v) -> q fp32 [T, H] rotated, rows p0 .. p0 + T - 1 of k_cache (rotated) and v_cache (copied)
+ *   silu_mul_rows    gate_up [T, 2 I] (gate | up) -> act [T, I] = silu(gate) * up */
+ia2p_status ia2p_llm_rmsnorm_rows(void* stream, const void* x, const void* gamma, float eps, void* y, int T, int H);
+ia2p_status ia2p_llm_rope_cache_rows(void* stream, const void* qkv, const float* inv_freq, float* q, void* k_cache, void* v_cache, int H, int p0, int T);
+ia2p_status ia2p_llm_silu_mul_rows(void* stream, const void* gate_up, void* act, int T, int I);
+/* the 64 rotary frequencies ia2p_llm_finalize_weights derives for a rope_theta (a host function; inv_freq: HOST fp32 [64]): 1 / theta^(2 i / 128).
+ * IA2P_ERR_INVALID for a theta that is not positive and finite. */
+ia2p_status ia2p_llm_rope_inv_freq(float rope_theta, float* inv_freq);
 /* exact (erf) GELU in place on fp16 [n]: the activation of an `mlpNx_gelu` projector head between two ia2p_linear_small calls
  * (llm/model/multimodal_projector/builder.py:33-74 `nn.GELU()`) */
 ia2p_status ia2p_gelu(void* stream, void* x, int64_t n);

@@ -180,6 +180,14 @@ SIGNATURES = {
     "ia2p_llm_batch_workspace_bytes": (_SZ, [_P, _I, _I]),
     "ia2p_llm_gemv_rows": (_I, [_P, _P, _P, _P, _I, _I, _I]),
     "ia2p_llm_gemv_q4_rows": (_I, [_P, _P, _P, C.POINTER(_F), _P, _P, _I, _I, _I]),
+    "ia2p_llm_gemv_epi": (_I, [_P, _P, _P, C.POINTER(_F), _P, _P, _F, _I, _P, _P, _I, _I, _I]),
+    "ia2p_llm_gemv_qkv": (_I, [_P, _P, _P, C.POINTER(_F), _P, _P, _F, _P, C.POINTER(C.c_int32), _P, C.POINTER(_P), C.POINTER(_P), _I, _I, _I]),
+    "ia2p_llm_attention_rows": (_I, [_P, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32), _P, _I, _I, _I]),
+    "ia2p_llm_attention_prefill": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_llm_rmsnorm_rows": (_I, [_P, _P, _P, _F, _P, _I, _I]),
+    "ia2p_llm_rope_cache_rows": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I]),
+    "ia2p_llm_silu_mul_rows": (_I, [_P, _P, _P, _I, _I]),
+    "ia2p_llm_rope_inv_freq": (_I, [_F, C.POINTER(_F)]),
     "ia2p_gelu": (_I, [_P, _P, _I64]),
     "ia2p_vae_create": (_I, [C.POINTER(VAEConfigC), C.POINTER(_P)]),
     "ia2p_vae_destroy": (None, [_P]),

@@ -224,6 +224,11 @@ static ia2p_status llm_enter(ia2p_llm* c, void* stream, void* ws, size_t ws_byte
   return pass_enter(c, stream, ws, ws_bytes);
 }
 
+// transformers LlamaRotaryEmbedding: inv_freq[i] = 1 / theta^(2 i / 128), fp32 (the table ia2p_llm_finalize_weights uploads and ia2p_llm_rope_inv_freq returns)
+static void llm_rope_inv_freq(float theta, float* f) {
+  for (int i = 0; i < 64; ++i) f[i] = 1.0f / powf(theta, (float)(2 * i) / 128.0f);
+}
+
 extern "C" {
 
 ia2p_status ia2p_llm_create(const ia2p_llm_config* cfg, ia2p_llm** out) {
@@ -293,8 +298,8 @@ ia2p_status ia2p_llm_gemv_q4(void* stream, const void* packed, const float* absm
 ia2p_status ia2p_llm_finalize_weights(ia2p_llm* c) {
   const ia2p_status st = rc_finalize(c, "LLM");
   if (st != IA2P_OK) return st;
-  float f[64];      // transformers LlamaRotaryEmbedding: inv_freq = 1 / theta^(2 i / 128), fp32
-  for (int i = 0; i < 64; ++i) f[i] = 1.0f / powf(c->cfg.rope_theta, (float)(2 * i) / 128.0f);
+  float f[64];
+  llm_rope_inv_freq(c->cfg.rope_theta, f);
   hipError_t e = hipMemcpy(c->arena + c->invf, f, sizeof f, hipMemcpyHostToDevice);
   if (e != hipSuccess) { c->finalized = false; return fail_hip(c, e, "llm rotary table"); }
   return IA2P_OK;
@@ -462,6 +467,125 @@ ia2p_status ia2p_llm_gemv(void* stream, const void* W, const float* x, float* ou
   a.W = (const half_t*)W; a.X = x; a.N = N; a.K = K; a.out = out;
   hipError_t e = llm_launch_gemv(a, EPI_PLAIN, (hipStream_t)stream);
   RET_HIP(e, "llm_gemv");
+}
+// ---- the remaining launches of the decode and prefill paths on their own: the launchers and kernels the drivers run, every refusal made here on the host ----
+// fp16 weights (absmax and codebook both null) or 4-bit codes (both given); the shared refusals of the two GEMV entry points below
+static ia2p_status llm_gemv_op_check(const char* what, const void* W, const float* absmax, const float* codebook, const float* x, const void* gamma, float eps, int N, int K,
+                                     int H, int M, int epi) {
+  if ((absmax == nullptr) != (codebook == nullptr)) return fail(nullptr, IA2P_ERR_INVALID, "%s: absmax and codebook go together (both: 4-bit codes, neither: fp16 weights)", what);
+  if (gamma && !(eps >= 0.f && eps < INFINITY)) return fail(nullptr, IA2P_ERR_INVALID, "%s: eps=%g", what, (double)eps);
+  const bool q4 = absmax != nullptr;
+  const ia2p_status st = q4 ? llm_gemv_q4_check(W, absmax, codebook, x, N, K, H, M, epi) : llm_gemv_check(W, x, N, K, H, M, epi);
+  if (st == IA2P_ERR_SHAPE && N >= 1 && !llm_epi_shape_ok(epi, N, H)) return fail(nullptr, st, "%s: N=%d H=%d (SwiGLU: N even; QKV: N = 3 H, H = heads * 128)", what, N, H);
+  return st == IA2P_OK ? st : q4 ? llm_refuse(what, st, N, K, 64, Q4_MAX_K, M) : llm_refuse(what, st, N, K, 8, 0, M);
+}
+static bool llm_positions_ok(const int32_t* pos, int M) {
+  for (int m = 0; m < M; ++m)
+    if (pos[m] < 0 || pos[m] >= LLM_MAX_POSITIONS) return false;
+  return true;
+}
+ia2p_status ia2p_llm_gemv_epi(void* stream, const void* W, const float* absmax, const float* codebook, const float* x, const void* gamma, float eps, int epi, float* out,
+                              float* hid, int N, int K, int M) {
+  static const int epis[3] = {EPI_PLAIN, EPI_RESID, EPI_SWIGLU};
+  if (!out) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv_epi: null argument");
+  if (epi < 0 || epi > 2) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv_epi: epilogue %d (0 plain, 1 residual, 2 SwiGLU)", epi);
+  if (hid && (epi != IA2P_LLM_EPI_PLAIN || !gamma)) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv_epi: hid goes with the plain epilogue and a gamma");
+  const ia2p_status st = llm_gemv_op_check("llm_gemv_epi", W, absmax, codebook, x, gamma, eps, N, K, 0, M, epis[epi]);
+  if (st != IA2P_OK) return st;
+  LlmGemv a{};
+  a.W = absmax ? nullptr : (const half_t*)W; a.gamma = (const half_t*)gamma; a.eps = eps; a.N = N; a.K = K;
+  LlmRows b = gemv_rows_args(x, out, epi == IA2P_LLM_EPI_SWIGLU ? N / 2 : N, K, M);
+  for (int m = 0; m < M; ++m) b.hid[m] = hid ? hid + (size_t)m * K : nullptr;
+  hipError_t e = absmax ? llm_launch_gemv_q4_rows(a, llm_q4(W, absmax, codebook), b, epis[epi], (hipStream_t)stream) : llm_launch_gemv_rows(a, b, epis[epi], (hipStream_t)stream);
+  RET_HIP(e, "llm_gemv_epi");
+}
+ia2p_status ia2p_llm_gemv_qkv(void* stream, const void* W, const float* absmax, const float* codebook, const float* x, const void* gamma, float eps, const float* inv_freq,
+                              const int32_t* pos, float* q, void* const* k_cache, void* const* v_cache, int H, int K, int M) {
+  if (!inv_freq || !pos || !q || !k_cache || !v_cache) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv_qkv: null argument");
+  if (H < 128 || H > (1 << 20)) return fail(nullptr, IA2P_ERR_SHAPE, "llm_gemv_qkv: H=%d (heads * 128)", H);
+  const ia2p_status st = llm_gemv_op_check("llm_gemv_qkv", W, absmax, codebook, x, gamma, eps, 3 * H, K, H, M, EPI_QKV);
+  if (st != IA2P_OK) return st;
+  for (int m = 0; m < M; ++m)
+    if (!k_cache[m] || !v_cache[m]) return fail(nullptr, IA2P_ERR_INVALID, "llm_gemv_qkv: null cache of row %d", m);
+  if (!llm_positions_ok(pos, M)) return fail(nullptr, IA2P_ERR_SHAPE, "llm_gemv_qkv: a position outside 0..%d", LLM_MAX_POSITIONS - 1);
+  LlmGemv a{};
+  a.W = absmax ? nullptr : (const half_t*)W; a.gamma = (const half_t*)gamma; a.eps = eps; a.N = 3 * H; a.K = K; a.H = H; a.inv_freq = inv_freq;
+  LlmRows b{};
+  b.M = M;
+  for (int m = 0; m < M; ++m) { b.X[m] = x + (size_t)m * K; b.q[m] = q + (size_t)m * H; b.kc[m] = (half_t*)k_cache[m]; b.vc[m] = (half_t*)v_cache[m]; b.pos[m] = pos[m]; }
+  hipError_t e = absmax ? llm_launch_gemv_q4_rows(a, llm_q4(W, absmax, codebook), b, EPI_QKV, (hipStream_t)stream) : llm_launch_gemv_rows(a, b, EPI_QKV, (hipStream_t)stream);
+  RET_HIP(e, "llm_gemv_qkv");
+}
+// heads and H of an attention entry point
+static ia2p_status llm_attn_shape(const char* what, int heads, int H) {
+  if (heads < 1 || heads > 65535 || H != heads * 128) return fail(nullptr, IA2P_ERR_SHAPE, "%s: H=%d for %d heads (head dim 128 only)", what, H, heads);
+  return IA2P_OK;
+}
+ia2p_status ia2p_llm_attention_rows(void* stream, const float* q, const void* const* k_cache, const void* const* v_cache, const int32_t* pos, float* out, int heads, int H,
+                                    int M) {
+  if (!q || !k_cache || !v_cache || !pos || !out) return fail(nullptr, IA2P_ERR_INVALID, "llm_attention_rows: null argument");
+  const ia2p_status st = llm_attn_shape("llm_attention_rows", heads, H);
+  if (st != IA2P_OK) return st;
+  if (M < 1 || M > LLM_MAX_ROWS) return fail(nullptr, IA2P_ERR_SHAPE, "llm_attention_rows: M=%d (1..%d)", M, LLM_MAX_ROWS);
+  LlmAttnRows ar{};
+  int longest = 0;
+  for (int m = 0; m < M; ++m) {
+    if (!k_cache[m] || !v_cache[m]) return fail(nullptr, IA2P_ERR_INVALID, "llm_attention_rows: null cache of row %d", m);
+    if ((((uintptr_t)k_cache[m]) | ((uintptr_t)v_cache[m])) & 15) return fail(nullptr, IA2P_ERR_INVALID, "llm_attention_rows: the caches must be 16-byte aligned");
+    ar.kc[m] = (const half_t*)k_cache[m]; ar.vc[m] = (const half_t*)v_cache[m]; ar.pos[m] = pos[m];
+  }
+  if (!llm_positions_ok(pos, M)) return fail(nullptr, IA2P_ERR_SHAPE, "llm_attention_rows: a position outside 0..%d", LLM_MAX_POSITIONS - 1);
+  for (int m = 0; m < M; ++m) longest = std::max(longest, pos[m] + 1);
+  hipLaunchKernelGGL(llm_attn_rows_kernel, dim3(heads, M), dim3(256), attn_lds(longest), (hipStream_t)stream, q, ar, out, H, 0.08838834764831845f);
+  hipError_t e = hipGetLastError();
+  RET_HIP(e, "llm_attention_rows");
+}
+// T rows at positions p0 .. p0 + T - 1 of one cache
+static ia2p_status llm_rows_span(const char* what, int p0, int T) {
+  if (T < 1 || p0 < 0 || p0 >= LLM_MAX_POSITIONS || T > LLM_MAX_POSITIONS - p0)
+    return fail(nullptr, IA2P_ERR_SHAPE, "%s: %d rows at position %d (positions 0..%d)", what, T, p0, LLM_MAX_POSITIONS - 1);
+  return IA2P_OK;
+}
+ia2p_status ia2p_llm_attention_prefill(void* stream, const float* q, const void* k_cache, const void* v_cache, void* out, int heads, int H, int p0, int T) {
+  if (!q || !k_cache || !v_cache || !out) return fail(nullptr, IA2P_ERR_INVALID, "llm_attention_prefill: null argument");
+  if ((((uintptr_t)k_cache) | ((uintptr_t)v_cache)) & 15) return fail(nullptr, IA2P_ERR_INVALID, "llm_attention_prefill: the caches must be 16-byte aligned");
+  ia2p_status st = llm_attn_shape("llm_attention_prefill", heads, H);
+  if (st == IA2P_OK) st = llm_rows_span("llm_attention_prefill", p0, T);
+  if (st != IA2P_OK) return st;
+  hipLaunchKernelGGL(llm_attn_kernel<half_t>, dim3(heads, T), dim3(256), attn_lds(p0 + T), (hipStream_t)stream, q, (const half_t*)k_cache, (const half_t*)v_cache, (half_t*)out, H,
+                     p0, 0.08838834764831845f);
+  hipError_t e = hipGetLastError();
+  RET_HIP(e, "llm_attention_prefill");
+}
+ia2p_status ia2p_llm_rmsnorm_rows(void* stream, const void* x, const void* gamma, float eps, void* y, int T, int H) {
+  if (!x || !gamma || !y) return fail(nullptr, IA2P_ERR_INVALID, "llm_rmsnorm_rows: null argument");
+  if (!(eps >= 0.f && eps < INFINITY)) return fail(nullptr, IA2P_ERR_INVALID, "llm_rmsnorm_rows: eps=%g", (double)eps);
+  if (T < 1 || H < 1) return fail(nullptr, IA2P_ERR_SHAPE, "llm_rmsnorm_rows: T=%d H=%d", T, H);
+  hipLaunchKernelGGL(llm_rmsnorm_rows_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, (const half_t*)x, (half_t*)y, (const half_t*)gamma, H, eps);
+  hipError_t e = hipGetLastError();
+  RET_HIP(e, "llm_rmsnorm_rows");
+}
+ia2p_status ia2p_llm_rope_cache_rows(void* stream, const void* qkv, const float* inv_freq, float* q, void* k_cache, void* v_cache, int H, int p0, int T) {
+  if (!qkv || !inv_freq || !q || !k_cache || !v_cache) return fail(nullptr, IA2P_ERR_INVALID, "llm_rope_cache_rows: null argument");
+  if (H < 128 || H % 128) return fail(nullptr, IA2P_ERR_SHAPE, "llm_rope_cache_rows: H=%d (heads * 128)", H);
+  const ia2p_status st = llm_rows_span("llm_rope_cache_rows", p0, T);
+  if (st != IA2P_OK) return st;
+  hipLaunchKernelGGL(llm_rope_cache_rows_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, (const half_t*)qkv, q, (half_t*)k_cache, (half_t*)v_cache, inv_freq, H, p0);
+  hipError_t e = hipGetLastError();
+  RET_HIP(e, "llm_rope_cache_rows");
+}
+ia2p_status ia2p_llm_silu_mul_rows(void* stream, const void* gate_up, void* act, int T, int I) {
+  if (!gate_up || !act) return fail(nullptr, IA2P_ERR_INVALID, "llm_silu_mul_rows: null argument");
+  if (T < 1 || I < 1 || I > (1 << 30)) return fail(nullptr, IA2P_ERR_SHAPE, "llm_silu_mul_rows: T=%d I=%d", T, I);
+  hipLaunchKernelGGL(llm_silu_mul_rows_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, (const half_t*)gate_up, (half_t*)act, I);
+  hipError_t e = hipGetLastError();
+  RET_HIP(e, "llm_silu_mul_rows");
+}
+ia2p_status ia2p_llm_rope_inv_freq(float rope_theta, float* inv_freq) {
+  if (!inv_freq) return fail(nullptr, IA2P_ERR_INVALID, "llm_rope_inv_freq: null argument");
+  if (!(rope_theta > 0.f && rope_theta < INFINITY)) return fail(nullptr, IA2P_ERR_INVALID, "llm_rope_inv_freq: rope_theta=%g", (double)rope_theta);
+  llm_rope_inv_freq(rope_theta, inv_freq);
+  return IA2P_OK;
 }
 ia2p_status ia2p_gelu(void* stream, void* x, int64_t n) {
   if (!x) return fail(nullptr, IA2P_ERR_INVALID, "gelu: null argument");

@@ -200,6 +200,30 @@ def test_one_row_batches_and_single_decodes_continue_a_batched_stream(tiny):
     assert [lm.slot_position(s) for s in (5, 0, 2)] == [5 + 5, 12 + 5, 33 + 5] and lm.position == 12 + 5
 
 
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_one_batched_step_past_256_positions(fmt):
+    """two layers, 2048 cached positions, four slots whose streams stand at positions 255, 256, 257 and 1024: one step at n = 4 against each stream alone
+    (slot 0 of the same model on the single-sequence path)"""
+    from instructany2pix_amd.config import tiny_llm
+    from instructany2pix_amd.weights import llm_param_specs, synthetic_state_dict
+    cfg = tiny_llm()
+    cfg.num_hidden_layers = 2
+    lm = _make(cfg, synthetic_state_dict(llm_param_specs(cfg, cfg.embed_dim, "linear"), seed=22), fmt, 2048, 4)
+    at = (255, 256, 257, 1024)
+    ids = [_ids(T + 1, 512, 70 + T) for T in at]
+    ref = [_serial(lm, ids[j], T) for j, T in enumerate(at)]
+    for j, T in enumerate(at):
+        lm.reset_slot(j)
+        hid, logits = lm.prefill_slot(j, lm.embed_tokens(ids[j][:T]))
+        assert torch.equal(hid, ref[j][0][0]) and torch.equal(logits, ref[j][1][0])
+    assert [lm.slot_position(j) for j in range(4)] == list(at)
+    hid, logits = lm.decode_batch([0, 1, 2, 3], [int(ids[j][T]) for j, T in enumerate(at)])
+    for j, T in enumerate(at):
+        assert torch.equal(hid[j], ref[j][0][1]), f"{fmt} position {T}: hidden row differs"
+        assert torch.equal(logits[j], ref[j][1][1]), f"{fmt} position {T}: logits row differ"
+    assert [lm.slot_position(j) for j in range(4)] == [T + 1 for T in at]
+
+
 # ---- full width -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("fmt", ["fp16", "fp4"])
 def test_full_width_eight_rows(fmt):

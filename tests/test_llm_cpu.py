@@ -215,6 +215,109 @@ def test_llm_abi_sizes_and_state(lib):
     lib.ia2p_llm_destroy(h)
 
 
+def test_llm_operation_entry_points_refuse_before_any_launch(lib):
+    """every call below is refused on the host (the pointers are never dereferenced and no GPU is needed); a refused call leaves its outputs untouched (the
+    host output here; tests/test_llm_ops_gpu.py::test_refused_calls_write_nothing looks at the device outputs)"""
+    INVALID, SHAPE = 1, 2
+    one, odd = C.c_void_p(256), C.c_void_p(264)          # 16-byte aligned / not
+    cb = (C.c_float * 16)(*range(16))
+    ptrs, nulls = (C.c_void_p * 8)(*[256] * 8), (C.c_void_p * 8)(256, None)
+    pos = lambda *p: (C.c_int32 * 8)(*(list(p) + [0] * (8 - len(p))))      # noqa: E731
+    epi, qkv, att, pre = lib.ia2p_llm_gemv_epi, lib.ia2p_llm_gemv_qkv, lib.ia2p_llm_attention_rows, lib.ia2p_llm_attention_prefill
+    cases = [
+        # the GEMV with an epilogue: W, absmax, codebook, x, gamma, eps, epi, out, hid, N, K, M
+        (epi(None, None, None, None, one, None, 0.0, 0, one, None, 64, 64, 1), INVALID),          # W
+        (epi(None, one, None, None, None, None, 0.0, 0, one, None, 64, 64, 1), INVALID),          # x
+        (epi(None, one, None, None, one, None, 0.0, 0, None, None, 64, 64, 1), INVALID),          # out
+        (epi(None, one, one, None, one, None, 0.0, 0, one, None, 64, 64, 1), INVALID),            # absmax without a codebook
+        (epi(None, one, None, cb, one, None, 0.0, 0, one, None, 64, 64, 1), INVALID),             # a codebook without absmax
+        (epi(None, one, None, None, one, None, 0.0, 3, one, None, 64, 64, 1), INVALID),           # epilogue
+        (epi(None, one, None, None, one, None, 0.0, -1, one, None, 64, 64, 1), INVALID),
+        (epi(None, one, None, None, one, None, 0.0, 0, one, one, 64, 64, 1), INVALID),            # hid without gamma
+        (epi(None, one, None, None, one, one, 1e-5, 1, one, one, 64, 64, 1), INVALID),            # hid with the residual epilogue
+        (epi(None, one, None, None, one, one, -1.0, 0, one, None, 64, 64, 1), INVALID),           # eps
+        (epi(None, one, None, None, one, None, 0.0, 0, one, None, 64, 64, 0), SHAPE),             # M
+        (epi(None, one, None, None, one, None, 0.0, 0, one, None, 64, 64, 9), SHAPE),
+        (epi(None, one, None, None, one, None, 0.0, 0, one, None, 64, 12, 1), SHAPE),             # K (fp16: a multiple of 8)
+        (epi(None, one, None, None, one, None, 0.0, 0, one, None, 0, 64, 1), SHAPE),              # N
+        (epi(None, one, None, None, one, None, 0.0, 2, one, None, 65, 64, 1), SHAPE),             # SwiGLU: an odd N
+        (epi(None, one, one, cb, one, None, 0.0, 0, one, None, 64, 96, 2), SHAPE),                # K (4 bits: a multiple of 64, at most 14336)
+        (epi(None, one, one, cb, one, None, 0.0, 0, one, None, 64, 14400, 2), SHAPE),
+        # QKV: W, absmax, codebook, x, gamma, eps, inv_freq, pos, q, k_cache, v_cache, H, K, M
+        (qkv(None, one, None, None, one, None, 0.0, None, pos(1), one, ptrs, ptrs, 128, 64, 1), INVALID),
+        (qkv(None, one, None, None, one, None, 0.0, one, None, one, ptrs, ptrs, 128, 64, 1), INVALID),
+        (qkv(None, one, None, None, one, None, 0.0, one, pos(1), None, ptrs, ptrs, 128, 64, 1), INVALID),
+        (qkv(None, one, None, None, one, None, 0.0, one, pos(1), one, None, ptrs, 128, 64, 1), INVALID),
+        (qkv(None, None, None, None, one, None, 0.0, one, pos(1), one, ptrs, ptrs, 128, 64, 1), INVALID),
+        (qkv(None, one, None, None, one, None, 0.0, one, pos(1, 1), one, ptrs, nulls, 128, 64, 2), INVALID),      # the cache of row 1
+        (qkv(None, one, None, None, one, None, 0.0, one, pos(1), one, ptrs, ptrs, 192, 64, 1), SHAPE),            # H
+        (qkv(None, one, None, None, one, None, 0.0, one, pos(1), one, ptrs, ptrs, 0, 64, 1), SHAPE),
+        (qkv(None, one, None, None, one, None, 0.0, one, pos(1), one, ptrs, ptrs, 128, 64, 9), SHAPE),            # M
+        (qkv(None, one, None, None, one, None, 0.0, one, pos(1, 8192), one, ptrs, ptrs, 128, 64, 2), SHAPE),      # positions
+        (qkv(None, one, None, None, one, None, 0.0, one, pos(-1), one, ptrs, ptrs, 128, 64, 1), SHAPE),
+        (qkv(None, one, one, cb, one, None, 0.0, one, pos(1), one, ptrs, ptrs, 128, 32, 1), SHAPE),               # K, 4 bits
+        # decode attention: q, k_cache, v_cache, pos, out, heads, H, M
+        (att(None, None, ptrs, ptrs, pos(1), one, 1, 128, 1), INVALID),
+        (att(None, one, ptrs, ptrs, pos(1), None, 1, 128, 1), INVALID),
+        (att(None, one, ptrs, None, pos(1), one, 1, 128, 1), INVALID),
+        (att(None, one, nulls, ptrs, pos(1, 1), one, 1, 128, 2), INVALID),
+        (att(None, one, (C.c_void_p * 8)(264), ptrs, pos(1), one, 1, 128, 1), INVALID),          # alignment
+        (att(None, one, ptrs, ptrs, pos(1), one, 2, 128, 1), SHAPE),                               # H is not heads * 128
+        (att(None, one, ptrs, ptrs, pos(1), one, 0, 0, 1), SHAPE),
+        (att(None, one, ptrs, ptrs, pos(1), one, 1, 128, 0), SHAPE),
+        (att(None, one, ptrs, ptrs, pos(1), one, 1, 128, 9), SHAPE),
+        (att(None, one, ptrs, ptrs, pos(1, 8192), one, 1, 128, 2), SHAPE),
+        (att(None, one, ptrs, ptrs, pos(-1), one, 1, 128, 1), SHAPE),
+        # prefill attention: q, k_cache, v_cache, out, heads, H, p0, T
+        (pre(None, None, one, one, one, 1, 128, 0, 1), INVALID),
+        (pre(None, one, one, one, None, 1, 128, 0, 1), INVALID),
+        (pre(None, one, odd, one, one, 1, 128, 0, 1), INVALID),
+        (pre(None, one, one, one, one, 3, 256, 0, 1), SHAPE),
+        (pre(None, one, one, one, one, 1, 128, 0, 0), SHAPE),
+        (pre(None, one, one, one, one, 1, 128, -1, 1), SHAPE),
+        (pre(None, one, one, one, one, 1, 128, 8192, 1), SHAPE),
+        (pre(None, one, one, one, one, 1, 128, 8000, 193), SHAPE),
+        # the prefill row kernels
+        (lib.ia2p_llm_rmsnorm_rows(None, None, one, 1e-5, one, 1, 128), INVALID),
+        (lib.ia2p_llm_rmsnorm_rows(None, one, one, 1e-5, None, 1, 128), INVALID),
+        (lib.ia2p_llm_rmsnorm_rows(None, one, one, -1.0, one, 1, 128), INVALID),
+        (lib.ia2p_llm_rmsnorm_rows(None, one, one, 1e-5, one, 0, 128), SHAPE),
+        (lib.ia2p_llm_rmsnorm_rows(None, one, one, 1e-5, one, 1, 0), SHAPE),
+        (lib.ia2p_llm_rope_cache_rows(None, one, None, one, one, one, 128, 0, 1), INVALID),
+        (lib.ia2p_llm_rope_cache_rows(None, one, one, one, one, None, 128, 0, 1), INVALID),
+        (lib.ia2p_llm_rope_cache_rows(None, one, one, one, one, one, 192, 0, 1), SHAPE),
+        (lib.ia2p_llm_rope_cache_rows(None, one, one, one, one, one, 128, 8191, 2), SHAPE),
+        (lib.ia2p_llm_rope_cache_rows(None, one, one, one, one, one, 128, -1, 1), SHAPE),
+        (lib.ia2p_llm_silu_mul_rows(None, None, one, 1, 64), INVALID),
+        (lib.ia2p_llm_silu_mul_rows(None, one, one, 0, 64), SHAPE),
+        (lib.ia2p_llm_silu_mul_rows(None, one, one, 1, 0), SHAPE),
+    ]
+    wrong = [(i, got, want) for i, (got, want) in enumerate(cases) if got != want]
+    assert not wrong, wrong
+    assert b"llm_silu_mul_rows" in lib.ia2p_llm_last_error(None)
+    f = (C.c_float * 64)(*[7.0] * 64)
+    for theta in (0.0, -1.0, float("inf"), float("nan")):
+        assert lib.ia2p_llm_rope_inv_freq(theta, f) == INVALID and list(f) == [7.0] * 64, theta
+    assert lib.ia2p_llm_rope_inv_freq(10000.0, None) == INVALID
+
+
+@pytest.mark.parametrize("theta", [10000.0, 500000.0, 1e6])
+def test_rotary_table_against_torch(lib, theta):
+    """the table ia2p_llm_finalize_weights uploads (the same host function) against transformers' torch expression: every entry within one fp32 ulp.
+    Entries that differ and the largest angle difference they make at position 8191 are printed; docs/LOG.md records them."""
+    import numpy as np
+    from llm_ops_ref import inv_freq_torch
+    f = (C.c_float * 64)()
+    assert lib.ia2p_llm_rope_inv_freq(theta, f) == 0
+    got, want = np.array(list(f), dtype=np.float32), inv_freq_torch(theta).numpy()
+    assert want.dtype == np.float32 and want.shape == (64,) and got[0] == 1.0
+    ulps = np.abs(got.view(np.int32).astype(np.int64) - want.view(np.int32).astype(np.int64))
+    angle = np.abs(np.float32(8191) * got - np.float32(8191) * want).astype(np.float64)
+    print(f"[llm] rotary table theta={theta:g}: {int((ulps != 0).sum())} of 64 entries differ from torch's, largest difference {int(ulps.max())} ulp, "
+          f"largest angle difference at position 8191 {float(angle.max()):.3e} rad")
+    assert int(ulps.max()) <= 1
+
+
 @pytest.mark.parametrize("bits", [16, 4])
 def test_llm_workspace_bytes_are_the_recorded_ones(lib, bits):
     """`tiny_llm()`: the bytes `ia2p_llm_workspace_bytes(c, T)` and `ia2p_llm_batch_workspace_bytes(c, T, n)` returned before the single-row and the

@@ -44,13 +44,13 @@ def oracle_rows(model, ids=None, embeds=None):
 
 
 class Bundle:
-    def __init__(self, cfg, seed, projector_type="linear"):
+    def __init__(self, cfg, seed, projector_type="linear", max_positions=256):
         from instructany2pix_amd.llm import HipInstructAny2PixLM
         from instructany2pix_amd.weights import llm_param_specs, synthetic_state_dict
         self.cfg = cfg
         self.sd = synthetic_state_dict(llm_param_specs(cfg, cfg.embed_dim, projector_type), seed=seed)
         self.o32, self.o16 = make_oracle(cfg, self.sd)
-        self.lm = HipInstructAny2PixLM(cfg, DEV, max_positions=256, video_token_id=cfg.vocab_size - 3)
+        self.lm = HipInstructAny2PixLM(cfg, DEV, max_positions=max_positions, video_token_id=cfg.vocab_size - 3)
         self.lm.load_state_dict(self.sd)
 
     def refs(self, ids=None, embeds=None):
@@ -123,6 +123,39 @@ def test_one_prefill_equals_prefill_plus_decodes_within_tolerance_and_decode_is_
     ok2 = _check("prefill(17) + 24 decodes", a_h[-1], a_l[-1], h32[-1], l32[-1], eh, el)
     assert ok1 and ok2
     assert torch.equal(a_h, b_h) and torch.equal(a_l, b_l)          # run-to-run identical bits
+
+
+@pytest.fixture(scope="module")
+def long2():
+    """two layers and 2048 cached positions: rows past position 255, where the attention's loops over the keys take a second trip and more"""
+    from instructany2pix_amd.config import tiny_llm
+    cfg = tiny_llm()
+    cfg.num_hidden_layers = 2
+    return Bundle(cfg, seed=22, max_positions=2048)
+
+
+@pytest.mark.parametrize("T", [257, 1025])
+def test_prefill_past_256_positions_against_oracle(long2, T):
+    ids = _ids(T, 512, 200 + T)
+    h32, l32, h16, l16 = long2.refs(ids)
+    long2.lm.reset()
+    hid, logits = long2.lm.prefill(long2.lm.embed_tokens(ids))
+    assert long2.lm.position == T
+    assert _check(f"2 layers, prefill T={T}", hid, logits, h32[-1], l32[-1], rel_l2(h16[-1], h32[-1]), rel_l2(l16[-1], l32[-1]))
+
+
+@pytest.mark.parametrize("n_prefill,steps", [(250, 10), (1020, 8)])
+def test_decode_steps_across_a_256_position_boundary(long2, n_prefill, steps):
+    """teacher-forced decode steps whose positions cross 256 (250 .. 259) and 1024 (1020 .. 1027); row i of the run against row n_prefill - 1 + i of the
+    oracle's forward of all the ids"""
+    ids = _ids(n_prefill + steps, 512, 300 + n_prefill)
+    h32, l32, h16, l16 = long2.refs(ids)
+    hid, logits = _prefill_then_decode(long2.lm, ids, n_prefill)
+    lo = n_prefill - 1
+    assert hid.shape[0] == steps + 1 and long2.lm.position == n_prefill + steps
+    eh, el = rel_l2(h16[lo:], h32[lo:]), rel_l2(l16[lo:], l32[lo:])
+    oks = [_check(f"2 layers, position {lo + i}", hid[i], logits[i], h32[lo + i], l32[lo + i], eh, el) for i in range(steps + 1)]
+    assert all(oks)
 
 
 def test_reset_leaves_no_state(tiny):

@@ -193,6 +193,38 @@ def test_one_prefill_equals_prefill_plus_decodes_and_runs_are_bit_identical(tiny
     assert torch.equal(a_h, b_h) and torch.equal(a_l, b_l)
 
 
+@pytest.fixture(scope="module", params=KINDS)
+def long4(request):
+    """two layers and 2048 cached positions: rows past position 255, where the attention's loops over the keys take a second trip and more"""
+    from instructany2pix_amd.config import tiny_llm
+    cfg = tiny_llm()
+    cfg.num_hidden_layers = 2
+    return Bundle4(cfg, seed=22, kind=request.param, max_positions=2048)
+
+
+@pytest.mark.parametrize("T", [257, 1025])
+def test_prefill_past_256_positions_against_quantised_oracle(long4, T):
+    ids = _ids(T, 512, 200 + T)
+    h32, l32, h16, l16 = long4.refs(ids)
+    long4.lm.reset()
+    hid, logits = long4.lm.prefill(long4.lm.embed_tokens(ids))
+    assert long4.lm.position == T
+    assert _check(f"{long4.kind} 2 layers, prefill T={T}", hid, logits, h32[-1], l32[-1], rel_l2(h16[-1], h32[-1]), rel_l2(l16[-1], l32[-1]))
+
+
+@pytest.mark.parametrize("n_prefill,steps", [(250, 10), (1020, 8)])
+def test_decode_steps_across_a_256_position_boundary(long4, n_prefill, steps):
+    """teacher-forced decode steps whose positions cross 256 (250 .. 259) and 1024 (1020 .. 1027)"""
+    ids = _ids(n_prefill + steps, 512, 300 + n_prefill)
+    h32, l32, h16, l16 = long4.refs(ids)
+    hid, logits = _prefill_then_decode(long4.lm, ids, n_prefill)
+    lo = n_prefill - 1
+    assert hid.shape[0] == steps + 1 and long4.lm.position == n_prefill + steps
+    eh, el = rel_l2(h16[lo:], h32[lo:]), rel_l2(l16[lo:], l32[lo:])
+    oks = [_check(f"{long4.kind} 2 layers, position {lo + i}", hid[i], logits[i], h32[lo + i], l32[lo + i], eh, el) for i in range(steps + 1)]
+    assert all(oks)
+
+
 def test_loading_twice_gives_the_same_arena(tiny4):
     from instructany2pix_amd.llm import HipInstructAny2PixLM
     other = HipInstructAny2PixLM(tiny4.cfg, DEV, max_positions=8, load_in_4bit=True, bnb_4bit_quant_type=tiny4.kind)
