@@ -406,6 +406,59 @@ ia2p_status ia2p_vit_encode(ia2p_vit* vit, void* stream, const void* pixels, int
  * At most 272 keys (IA2P_ERR_SHAPE). Scores and softmax in fp32, fixed reduction order. */
 ia2p_status ia2p_attention_full(void* stream, const void* qkv, void* out, const void* bias_k, const void* bias_v, int B, int T, int heads, int D);
 
+/* ---- Segment Anything: the subject segmenter of the subject-consistency pass (reference gdino/lib.py:21-51 `get_mask`: `SamPredictor.set_image`, then
+ * `predict(box=...)` per subject; pipeline.py:363-368). transformers `SamModel` semantics: a ViT image encoder whose blocks attend inside
+ * window x window tiles of the token grid or, at global_attn_indexes, over the whole grid, both with the decomposed relative-position bias; a neck to
+ * output_channels; a prompt encoder for ONE box per mask (evaluated on the host in fp32); the two-way mask decoder (dec_layers blocks, dec_heads heads,
+ * attention inner width dec_hidden / dec_downsample_rate) with the single-mask output (mask token 0, `multimask_output=False`). Head dim 64 or 80 in the
+ * encoder, 16 or 32 in the decoder; window <= 16; image_size a multiple of patch_size; dec_hidden == output_channels (IA2P_ERR_SHAPE otherwise, also for a
+ * grid whose bias rows do not fit the attention launch's LDS). Parameter keys: see instructany2pix_amd/sam.py (`internal_state_dict`), fp16. */
+#define IA2P_SAM_MAX_GLOBAL 8
+typedef struct ia2p_sam ia2p_sam;
+typedef struct {
+  int hidden_size, num_layers, num_heads, mlp_dim, image_size, patch_size, window_size;
+  int num_global, global_attn_indexes[IA2P_SAM_MAX_GLOBAL];
+  int output_channels;
+  int dec_hidden, dec_layers, dec_heads, dec_mlp_dim, dec_downsample_rate;
+  float layer_norm_eps;   /* <= 0: 1e-6 */
+} ia2p_sam_config;
+ia2p_status ia2p_sam_create(const ia2p_sam_config* cfg, ia2p_sam** out);
+void ia2p_sam_destroy(ia2p_sam* sam);
+const char* ia2p_sam_last_error(ia2p_sam* sam);
+size_t ia2p_sam_arena_bytes(ia2p_sam* sam);
+ia2p_status ia2p_sam_bind_arena(ia2p_sam* sam, void* dev_arena, size_t bytes);
+ia2p_status ia2p_sam_load_tensor(ia2p_sam* sam, const char* key, const void* dev_src, const int64_t* shape, int ndim, void* stream);
+/* also reads the small prompt tensors back to the host and uploads the dense positional encoding of the token grid (synchronises the device) */
+ia2p_status ia2p_sam_finalize_weights(ia2p_sam* sam);
+/* workspace that serves ia2p_sam_encode_image of B images and ia2p_sam_predict_boxes of up to n_boxes boxes (1..64 each; 0 otherwise) */
+size_t ia2p_sam_workspace_bytes(ia2p_sam* sam, int B, int n_boxes);
+/* pixels: fp16 [B, 3, S, S] on the device (normalised, zero-padded to the square). embeddings: fp16 [B, gh * gw, output_channels], channels-last rows. */
+ia2p_status ia2p_sam_encode_image(ia2p_sam* sam, void* stream, const void* pixels, int B, void* embeddings, void* workspace, size_t workspace_bytes);
+/* embeddings: ONE image's rows. boxes: HOST fp32 [n, 4], x0 y0 x1 y1 in pixels of the S x S input; a box that is not inside the input is IA2P_ERR_SHAPE.
+ * low_res_logits: fp32 [n, 4 gh, 4 gw], iou: fp32 [n], both on the device. Waits for the stream's earlier work before it reuses its host staging buffer. */
+ia2p_status ia2p_sam_predict_boxes(ia2p_sam* sam, void* stream, const void* embeddings, const float* boxes, int n, float* low_res_logits, float* iou,
+                                   void* workspace, size_t workspace_bytes);
+/* The executor's own launches one by one (unit tests, tools/sam_bench.py). Scores and softmax in fp32, fixed reduction order, no atomics.
+ * Attention with SAM's decomposed relative-position bias over the [gh, gw] token grid of each image, from the fused QKV buffer: qkv fp16 [B * gh * gw, 3 heads D]
+ * rows = [q | k | v] in grid order, out fp16 [B * gh * gw, heads D], D = 64 or 80;
+ *   score[q][k] = (q . k) / sqrt(D) + q . rel_h[qh - kh + S - 1] + q . rel_w[qw - kw + S - 1]        (the bias terms on the unscaled q)
+ * window: S = window <= 16, rel_h / rel_w fp16 [2 S - 1, D]; the grid is cut into S x S tiles from the top-left corner, a tile's positions past the grid's edge
+ * are keys whose k / v are rows [H, 2H) / [2H, 3H) of qkv_bias (fp16 [3 heads D]: SAM pads after norm1) and are no queries.
+ * global: one tile, the whole grid; rel_h fp16 [2 gh - 1, D], rel_w fp16 [2 gw - 1, D]; IA2P_ERR_SHAPE when gh + gw bias rows of 64 queries do not fit in LDS. */
+ia2p_status ia2p_attention_window_relpos(void* stream, const void* qkv, void* out, const void* qkv_bias, const void* rel_h, const void* rel_w, int B, int gh, int gw,
+                                         int heads, int D, int window);
+ia2p_status ia2p_attention_global_relpos(void* stream, const void* qkv, void* out, const void* rel_h, const void* rel_w, int B, int gh, int gw, int heads, int D);
+/* the mask decoder's attention: q fp16 [B, Tq, heads D], k / v fp16 [B, Tk, heads D], out as q; D = 16 or 32, any Tq / Tk; scale 1 / sqrt(D) */
+ia2p_status ia2p_attention_small_head(void* stream, const void* q, const void* k, const void* v, void* out, int B, int Tq, int Tk, int heads, int D);
+/* bilinear resize (torch `F.interpolate(mode="bilinear", align_corners=False)`) of n fp32 images, src_h x src_w pixels at row stride src_ld and image stride
+ * src_image_stride (a crop is a smaller src_h / src_w over the same strides), to H x W: out_logits fp32 [n, H, W] and / or out_mask uint8 [n, H, W] =
+ * (value > threshold ? 255 : 0); either may be NULL. */
+ia2p_status ia2p_mask_upsample_threshold(void* stream, const float* logits, int n, int src_h, int src_w, int src_ld, int64_t src_image_stride, int H, int W,
+                                         float threshold, float* out_logits, void* out_mask);
+/* erode (is_dilate = 0: minimum) or dilate (maximum) a uint8 [H, W] image with a k x k window of offsets -(k / 2) .. k - k / 2 - 1 on both axes; pixels outside
+ * the image are ignored. tmp: uint8 [H, W] scratch (the row pass); dst may be src. */
+ia2p_status ia2p_mask_morph(void* stream, const void* src, void* dst, void* tmp, int H, int W, int k, int is_dilate);
+
 /* ---- the instruction LLM: LLaMA decoder with a KV cache (reference pipeline.py:151-279 `forward_llm`; the model is a Vicuna-7B shaped
  * `LlamaForCausalLM`, llm/model/language_model/any2pix_llama.py, driven by `any2pix_lm.generate(...)` at pipeline.py:201-211 with use_cache=False:
  * one full forward per new token there, one cached row here). transformers `LlamaModel` + `lm_head` semantics: pre-RMSNorm blocks, rotary

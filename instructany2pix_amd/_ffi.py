@@ -42,6 +42,12 @@ class ViTConfigC(C.Structure):
                 ("bias_kv", C.c_int), ("out_dim", C.c_int), ("layer_norm_eps", C.c_float)]
 
 
+class SAMConfigC(C.Structure):
+    _fields_ = [("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int), ("mlp_dim", C.c_int), ("image_size", C.c_int), ("patch_size", C.c_int),
+                ("window_size", C.c_int), ("num_global", C.c_int), ("global_attn_indexes", C.c_int * 8), ("output_channels", C.c_int), ("dec_hidden", C.c_int),
+                ("dec_layers", C.c_int), ("dec_heads", C.c_int), ("dec_mlp_dim", C.c_int), ("dec_downsample_rate", C.c_int), ("layer_norm_eps", C.c_float)]
+
+
 class LLMConfigC(C.Structure):
     _fields_ = [("vocab_size", C.c_int), ("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int), ("num_kv_heads", C.c_int),
                 ("intermediate_size", C.c_int), ("rms_norm_eps", C.c_float), ("rope_theta", C.c_float)]
@@ -145,6 +151,21 @@ SIGNATURES = {
     "ia2p_vit_workspace_bytes": (_SZ, [_P, _I]),
     "ia2p_vit_encode": (_I, [_P, _P, _P, _I, _P, _P, _P, _SZ]),
     "ia2p_attention_full": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_sam_create": (_I, [C.POINTER(SAMConfigC), C.POINTER(_P)]),
+    "ia2p_sam_destroy": (None, [_P]),
+    "ia2p_sam_last_error": (C.c_char_p, [_P]),
+    "ia2p_sam_arena_bytes": (_SZ, [_P]),
+    "ia2p_sam_bind_arena": (_I, [_P, _P, _SZ]),
+    "ia2p_sam_load_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I, _P]),
+    "ia2p_sam_finalize_weights": (_I, [_P]),
+    "ia2p_sam_workspace_bytes": (_SZ, [_P, _I, _I]),
+    "ia2p_sam_encode_image": (_I, [_P, _P, _P, _I, _P, _P, _SZ]),
+    "ia2p_sam_predict_boxes": (_I, [_P, _P, _P, C.POINTER(_F), _I, _P, _P, _P, _SZ]),
+    "ia2p_attention_window_relpos": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
+    "ia2p_attention_global_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
+    "ia2p_attention_small_head": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
+    "ia2p_mask_upsample_threshold": (_I, [_P, _P, _I, _I, _I, _I, _I64, _I, _I, _F, _P, _P]),
+    "ia2p_mask_morph": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
     "ia2p_prior_step": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P, _I64]),
     "ia2p_llm_create": (_I, [C.POINTER(LLMConfigC), C.POINTER(_P)]),
     "ia2p_llm_destroy": (None, [_P]),
@@ -245,12 +266,12 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def check(status: int, ctx=None, vae=False, clip=False, llm=False, vit=False):
+def check(status: int, ctx=None, vae=False, clip=False, llm=False, vit=False, sam=False):
     """Map ia2p_status to the exception types the reference raises at the same conditions
     (ValueError from check_inputs/_get_add_time_ids, reference pnp_pipeline.py:49-66)."""
     if status == IA2P_OK:
         return
-    msg = (lib().ia2p_vit_last_error(ctx) if vit else lib().ia2p_llm_last_error(ctx) if llm else lib().ia2p_clip_last_error(ctx) if clip else lib().ia2p_vae_last_error(ctx) if vae
+    msg = (lib().ia2p_sam_last_error(ctx) if sam else lib().ia2p_vit_last_error(ctx) if vit else lib().ia2p_llm_last_error(ctx) if llm else lib().ia2p_clip_last_error(ctx) if clip else lib().ia2p_vae_last_error(ctx) if vae
            else lib().ia2p_last_error(ctx))
     msg = msg.decode() if msg else ""
     text = f"ia2p {_STATUS_NAMES.get(status, status)}: {msg}"
@@ -309,6 +330,21 @@ def make_vit_config(cfg) -> ViTConfigC:
     c = ViTConfigC()
     for name, _ in ViTConfigC._fields_:
         setattr(c, name, getattr(cfg, name))
+    return c
+
+
+def make_sam_config(cfg) -> SAMConfigC:
+    c = SAMConfigC()
+    if len(cfg.global_attn_indexes) > 8:
+        raise ValueError("at most 8 global-attention blocks are supported")
+    for name, _ in SAMConfigC._fields_:
+        if name == "num_global":
+            c.num_global = len(cfg.global_attn_indexes)
+        elif name == "global_attn_indexes":
+            for i, v in enumerate(cfg.global_attn_indexes):
+                c.global_attn_indexes[i] = int(v)
+        else:
+            setattr(c, name, getattr(cfg, name))
     return c
 
 

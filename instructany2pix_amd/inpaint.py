@@ -6,8 +6,9 @@ per-step latent blend under a mask.
          (instructany2pix/pipeline.py:132-139) and drives through `IPAdapterXL(pipe_inpainting).generate(image=, mask_image=,
          strength=subject_strength, clip_image_embeds_local=emb[None], mode='local', num_inference_steps=50, scale=0.8)`
          (instructany2pix/gdino/lib.py:89-102, called from pipeline.py:363-368)
-  subject_consistency(...)   <- the loop over detected subjects of gdino/lib.py:69-104, on given masks (SAM / GroundingDINO
-                                produce them in the reference; they are outside this path)
+  subject_consistency(...)   <- the loop over detected subjects of gdino/lib.py:69-104, on given masks
+  subject_consistency_from_boxes(...)   <- the same loop from detector boxes: the masks come from SAM on HIP (sam.py `get_mask`); the boxes from the
+                                caller or an injected detector (GroundingDINO is not built here)
 
 The denoising loop follows diffusers 0.26.3 `StableDiffusionXLInpaintPipeline.__call__` for a 4-channel UNet: `get_timesteps`
 (strength -> tail of the schedule), start latents = noise (strength 1) or `add_noise(image_latents, noise, t_0)`, the mask resized to
@@ -152,3 +153,24 @@ def subject_consistency(subject_data, latents, ip_adapter_xl_inpaint, subject_st
                                                  clip_image_embeds_local=emb[None] if emb.ndim == 1 else emb, mode="local",
                                                  num_inference_steps=50, scale=0.8, **generate_kwargs)
     return subject
+
+
+def subject_consistency_from_boxes(subject_data, latents, ip_adapter_xl_inpaint, segmenter, boxes, phrases, vae, subject_strength: float = 0.7, **generate_kwargs):
+    """Reference gdino/lib.py:69-103 on given detector output: `subject_data` = [(phrase, subject embedding)], `boxes` cxcywh in [0, 1] [n, 4] with their
+    `phrases`. The current result is decoded through `vae` once and set as the segmenter's image (:73); per subject the phrase loses '.' and "'s" (:86), its
+    mask is `get_mask(..., d=40, b=20)` (:87) and the inpaint pass of `subject_consistency` follows. Boxes are scaled by the decoded image's longer side
+    (the reference's literal 1024 is the side of the images it generates). -> (latents, masks as PIL images)"""
+    import numpy as np
+    from .sam import get_mask
+    if segmenter is None:
+        raise ValueError("subjects given as (phrase, embedding) need the pipeline built with segmenter=<HipSamPredictor>")
+    if vae is None:
+        raise ValueError("subjects given as (phrase, embedding) need the pipeline built with vae=<HipAutoencoderKL> (the segmenter sees the decoded image)")
+    if boxes is None or phrases is None:
+        raise KeyError("subjects given as (phrase, embedding) need boxes and phrases: build the pipeline with detector= or return c['subject_boxes'] = (boxes, phrases)")
+    x = vae.decode_from_latents(latents)[:1]                                  # [-1, 1]; the 8-bit image of `postprocess(output_type="pil")`
+    a = ((x.float() / 2 + 0.5).clamp(0, 1) * 255.0).round().to(torch.uint8)[0].permute(1, 2, 0).cpu().numpy()
+    segmenter.set_image(np.ascontiguousarray(a))
+    masks = [get_mask(ph.replace(".", "").replace("'s", ""), boxes, phrases, segmenter, i=0, d=40, b=20, size=max(a.shape[0], a.shape[1])) for ph, _ in subject_data]
+    pairs = [(torch.from_numpy(np.array(m)), emb) for m, (_, emb) in zip(masks, subject_data)]
+    return subject_consistency(pairs, latents, ip_adapter_xl_inpaint, subject_strength, **generate_kwargs), masks

@@ -27,7 +27,7 @@ import torch
 from .config import UNetConfig, sdxl_base
 from .ddim import SDXLDDIMPipeline, StableDiffusionXLPipeline
 from .img2img import StableDiffusionXLImg2ImgPipeline
-from .inpaint import StableDiffusionXLInpaintPipeline, subject_consistency
+from .inpaint import StableDiffusionXLInpaintPipeline, subject_consistency, subject_consistency_from_boxes
 from .image_processor import OUTPUT_TYPES, requantize
 from .ip_adapter import IPAdapterXL
 from .prior import MODALITY
@@ -102,7 +102,7 @@ class InstructAny2PixPipeline:
                  vae_encode: Optional[Callable] = None, vae_decode: Optional[Callable] = None, clip_embeddings_dim: int = 1024,
                  refiner_unet: Optional[HipUNet2DConditionModel] = None, refiner_text_encoder: Optional[Callable] = None, prior=None,
                  refiner_handoff: str = "image", vae=None, llm=None, llm_tokenizer: Optional[Callable] = None,
-                 modality_encoder: Optional[Callable] = None, imagebind=None):
+                 modality_encoder: Optional[Callable] = None, imagebind=None, segmenter=None, detector: Optional[Callable] = None):
         # llm: a HipInstructAny2PixLM (reference :117 `self.any2pix_lm`; built with `load_in_4bit=True` it computes from 4-bit weights as the
         # reference's `from_pretrained(..., load_in_4bit=True)` model does, nothing changes here) with its tokenizer (:126 `self.any2pix_tokenizer`, injected: the
         # sentencepiece model is checkpoint data); modality_encoder(entry) -> [1024] embedding of an mm_data entry (reference :155-166:
@@ -110,6 +110,9 @@ class InstructAny2PixPipeline:
         # encodes the entries' files itself when neither of the two is given
         self.any2pix_lm, self.any2pix_tokenizer, self.modality_encoder = llm, llm_tokenizer, modality_encoder
         self.model_imb = imagebind
+        # segmenter: a sam.HipSamPredictor (reference :147 `self.sam`); detector(image uint8 [H, W, 3], text_prompt) -> (boxes cxcywh in [0, 1] [n, 4], phrases): stands in
+        # for GroundingDINO (:148 `self.gdino`, not built here). Both serve subjects the conditioner names by phrase: subject_data = [(phrase, embedding)]
+        self.sam, self.gdino = segmenter, detector
         self._text_encoder, self._refiner_text_encoder = text_encoder, refiner_text_encoder
         # vae: a HipAutoencoderKL shared by every pipeline (in place of the vae_encode / vae_decode hooks): base images in, images out
         # how the base result reaches the refiner: "image" = the reference's route (decode, 8-bit image, VAE re-encode with a posterior
@@ -310,12 +313,39 @@ class InstructAny2PixPipeline:
         ipe, _, ipp, _ = self._text_encoder(prompt="", do_classifier_free_guidance=False)
         c.update(prompt_embeds=pe, pooled_prompt_embeds=pp, negative_prompt_embeds=ne, negative_pooled_prompt_embeds=npl,
                  inv_prompt_embeds=ipe, inv_pooled_prompt_embeds=ipp)
+        if extra_data is not None and len(extra_data.get("extra_idx", [])) > 0:                # :363-366: the subjects that are image entries
+            c["subject_data"] = [(k, v) for (k, v, i) in zip(extra_data["all_objs"], extra_data["extra_embeds"], extra_data["extra_idx"])
+                                 if mm_data[int(i)]["type"] == "image"]
+            # the inpaint pass runs IPAdapterXL.generate without a prompt: its defaults (ip_adapter.py `generate`)
+            spe, sne, spp, snp = self._text_encoder(prompt="best quality, high quality", negative_prompt="monochrome, lowres, bad anatomy, worst quality, low quality",
+                                                    do_classifier_free_guidance=True)
+            c.update(subject_prompt_embeds=spe, subject_pooled_prompt_embeds=spp, subject_negative_prompt_embeds=sne, subject_negative_pooled_prompt_embeds=snp)
         if self._refiner_text_encoder is not None:
             rpe, rne, rpp, rnp = self._refiner_text_encoder(prompt=output_caption + ",high quality,well-formed,award-winning", negative_prompt="",
                                                             do_classifier_free_guidance=True)
             c.update(refiner_prompt_embeds=rpe, refiner_pooled_prompt_embeds=rpp, refiner_negative_prompt_embeds=rne,
                      refiner_negative_pooled_prompt_embeds=rnp)
         return c
+
+    def _subjects_from_phrases(self, c, subject_data, latents, subject_strength, kw):
+        """the subject-consistency pass for subjects named by phrase: boxes from c["subject_boxes"] = (boxes, phrases) or from the detector on the decoded
+        result (prompt: the phrases joined by '. ', gdino/lib.py:70), masks from the segmenter"""
+        if self.sam is None:
+            raise ValueError("subject_data names subjects by phrase: build the pipeline with segmenter=<HipSamPredictor> (or pass subject_strength=0)")
+        if self.vae is None:
+            raise ValueError("subject_data names subjects by phrase: build the pipeline with vae=<HipAutoencoderKL> (the segmenter sees the decoded image)")
+        if c.get("subject_boxes") is not None:
+            boxes, phrases = c["subject_boxes"]
+        elif self.gdino is not None:
+            x = self.vae.decode_from_latents(latents)[:1]
+            img = ((x.float() / 2 + 0.5).clamp(0, 1) * 255.0).round().to(torch.uint8)[0].permute(1, 2, 0).cpu().numpy()
+            boxes, phrases = self.gdino(img, ". ".join(k for k, _ in subject_data))
+        else:
+            raise KeyError("subject_data names subjects by phrase: the conditioner returned no 'subject_boxes' and the pipeline has no detector= "
+                           "(pass subject_strength=0 to skip the subject-consistency pass)")
+        out, self.subject_masks = subject_consistency_from_boxes(subject_data, latents, self.ip_adapter_xl_inpaint, self.sam, boxes, phrases, self.vae,
+                                                                 subject_strength, **kw)
+        return out
 
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
@@ -384,13 +414,19 @@ class InstructAny2PixPipeline:
             else:
                 oo = self.piperf(latents=images, **kw).images
         subject_data = c.get("subject_data") or []
-        if subject_strength > 0 and len(subject_data) > 0:                                     # :363-368 (masks: SAM / GroundingDINO, off-path)
+        if subject_strength > 0 and len(subject_data) > 0:                                     # :363-368
             _need(c, ("subject_prompt_embeds", "subject_pooled_prompt_embeds", "subject_negative_prompt_embeds", "subject_negative_pooled_prompt_embeds"),
                   "subject-consistency pass")
-            oo = subject_consistency(subject_data, oo, self.ip_adapter_xl_inpaint, subject_strength, output_type="latent",
-                                     prompt_embeds=c["subject_prompt_embeds"], pooled_prompt_embeds=c["subject_pooled_prompt_embeds"],
-                                     negative_prompt_embeds=c["subject_negative_prompt_embeds"],
-                                     negative_pooled_prompt_embeds=c["subject_negative_pooled_prompt_embeds"], noise=c.get("subject_noise"))
+            kw = dict(output_type="latent", prompt_embeds=c["subject_prompt_embeds"], pooled_prompt_embeds=c["subject_pooled_prompt_embeds"],
+                      negative_prompt_embeds=c["subject_negative_prompt_embeds"],
+                      negative_pooled_prompt_embeds=c["subject_negative_pooled_prompt_embeds"], noise=c.get("subject_noise"))
+            by_phrase = [isinstance(k, str) for k, _ in subject_data]
+            if any(by_phrase) and not all(by_phrase):
+                raise ValueError("subject_data mixes (mask, embedding) and (phrase, embedding) entries: give one kind")
+            if all(by_phrase):                                                                 # gdino/lib.py:69-103: masks from SAM on the detector's boxes
+                oo = self._subjects_from_phrases(c, subject_data, oo, subject_strength, kw)
+            else:                                                                              # masks given by the conditioner
+                oo = subject_consistency(subject_data, oo, self.ip_adapter_xl_inpaint, subject_strength, **kw)
         msg = "SUCCESS!" if not debug else dict(output_caption=c["caption"], latent_inv=latent_inv, latent_la=latent_la)
         if output_type != "latent":
             post = self.pipe.image_processor.postprocess
