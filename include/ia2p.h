@@ -618,6 +618,46 @@ ia2p_status ia2p_llm_rope_inv_freq(float rope_theta, float* inv_freq);
  * (llm/model/multimodal_projector/builder.py:33-74 `nn.GELU()`) */
 ia2p_status ia2p_gelu(void* stream, void* x, int64_t n);
 
+/* ---- the small launches around the UNet, one by one (every refusal is decided on the host, before a launch; device pointers, fp16 unless said otherwise) ----
+ * clip_embed             x [rows, H] = tok[clamp(ids[row], 0, vocab - 1)] + pos[row % T] (embeds != NULL: embeds[row] instead of the table row; ids and tok may be
+ *                        NULL then); stats: fp32 [rows, 2] = {sum, sum of squares} of the fp16 row of x. H % 8 == 0.
+ * causal_attention_small qkv [B T, 3 heads D] = q | k | v -> out [B T, heads D], softmax(q . k / 8) over keys 0 .. q. D == 64, T <= 128.
+ * clip_pool              out [B, H] = LayerNorm(x[b, p_b]), p_b the first position of the largest id (eos_id == 2), else the first position of eos_id (0 when absent).
+ *                        ids: int32 [B, T], not negative.
+ * softmax_rows           in place, x[r, :n] = softmax(scale x[r, :n]) for rows of stride ld >= n; n % 8 == 0, n <= 16384, ld % 8 == 0.
+ * conv1x1_nchw           y [B, Co, HW] = w [Co, Ci] x [B, Ci, HW] + bias, Ci and Co <= 8.
+ * patch_gather           px [B, C, Hi, Wi] -> cols [B gh gw, Kpad]: column (c, ky, kx) of the patch at (py stride, px stride), zero for columns >= C ps ps.
+ * vit_embed              x [B, T, H]: row 0 = cls + pos[0], row 1 + p = LN_stem?(patches[b, p]) + pos[1 + p], then LN_pre?; stats as clip_embed. A gamma and its
+ *                        beta are both given or both NULL. H % 64 == 0, H <= 2048, T >= 2.
+ * vit_project            out fp32 [B, N] = X [B, K] . W [N, K]^T, K % 8 == 0.
+ * embed                  tsin [B, Tp] = [cos(t f_i) | sin(t f_i)], f_i = exp(-ln(10000) i / (Tp / 2)); addin [B, P + nids Ad] = [text_embeds[b] | the same sinusoid
+ *                        of width Ad of each of time_ids [B, nids]]. ts (optional, device fp32 [B]): one t per batch element. Tp and Ad even.
+ * concat                 y [M, Ca + Cb] = [a[m, :Ca] | b[m, :Cb]], rows of stride lda / ldb; multiples of 8.
+ * cat_rows               dst [rows, Ka + Kb] = [a[r] | b[r]], bias_dst = bias_a + bias_b (one rounding); multiples of 8. */
+ia2p_status ia2p_clip_embed(void* stream, const int32_t* ids, const void* tok, const void* embeds, const void* pos, void* x, float* stats, int rows, int T, int H, int vocab);
+ia2p_status ia2p_causal_attention_small(void* stream, const void* qkv, void* out, int B, int T, int heads, int D);
+ia2p_status ia2p_clip_pool(void* stream, const int32_t* ids, const void* x, const void* gamma, const void* beta, void* out, int B, int T, int H, int eos_id, float eps);
+ia2p_status ia2p_softmax_rows(void* stream, void* x, int64_t ld, int rows, int n, float scale);
+ia2p_status ia2p_conv1x1_nchw(void* stream, const void* x, const void* w, const void* bias, void* y, int B, int Ci, int Co, int64_t HW);
+ia2p_status ia2p_patch_gather(void* stream, const void* px, void* cols, int B, int C, int Hi, int Wi, int ps, int stride, int gh, int gw, int Kpad);
+ia2p_status ia2p_vit_embed(void* stream, const void* patches, const void* cls, const void* pos, const void* stem_g, const void* stem_b, const void* pre_g, const void* pre_b,
+                           void* x, float* stats, int B, int T, int H, float eps);
+ia2p_status ia2p_vit_project(void* stream, const void* X, const void* W, float* out, int B, int N, int K);
+ia2p_status ia2p_embed(void* stream, float t, const float* ts, const void* text_embeds, const void* time_ids, void* tsin, void* addin, int B, int Tp, int P, int Ad, int nids);
+ia2p_status ia2p_concat(void* stream, const void* a, int lda, int Ca, const void* b, int ldb, int Cb, void* y, int64_t M);
+ia2p_status ia2p_cat_rows(void* stream, const void* a, int Ka, const void* b, int Kb, const void* bias_a, const void* bias_b, void* dst, void* bias_dst, int rows);
+/* the small launches of the SAM mask decoder:
+ *   pixel_shuffle2  g [B, Hs, Ws, (ky, kx, co)] -> y [B, 2 Hs, 2 Ws, Co] (the GEMM form of a ConvTranspose2d(k = 2, s = 2)); Co % 8 == 0
+ *   hyper_dot       mask fp32 [n, P] = sum_c hyper[n, c] up[n, p, c], rows of hyper at stride hyper_stride >= C; C % 8 == 0, no upper limit on C
+ *   sam_act         in place on fp16 [n]: kind 0 ReLU, 1 exact (erf) GELU
+ *   sam_add_rows    out[i] = a[i] + b[i % period] (out may alias a); n, period multiples of 8, period dividing n
+ *   sam_take_col    dst fp32 [n] = src[i ld] */
+ia2p_status ia2p_pixel_shuffle2(void* stream, const void* g, void* y, int B, int Hs, int Ws, int Co);
+ia2p_status ia2p_hyper_dot(void* stream, const void* hyper, int64_t hyper_stride, const void* up, float* mask, int n, int P, int C);
+ia2p_status ia2p_sam_act(void* stream, void* x, int64_t n, int kind);
+ia2p_status ia2p_sam_add_rows(void* stream, const void* a, const void* b, void* out, int64_t n, int64_t period);
+ia2p_status ia2p_sam_take_col(void* stream, const void* src, int64_t ld, float* dst, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,22 @@ SIGNATURES = {
     "ia2p_llm_silu_mul_rows": (_I, [_P, _P, _P, _I, _I]),
     "ia2p_llm_rope_inv_freq": (_I, [_F, C.POINTER(_F)]),
     "ia2p_gelu": (_I, [_P, _P, _I64]),
+    "ia2p_clip_embed": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_causal_attention_small": (_I, [_P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_clip_pool": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F]),
+    "ia2p_softmax_rows": (_I, [_P, _P, _I64, _I, _I, _F]),
+    "ia2p_conv1x1_nchw": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I64]),
+    "ia2p_patch_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "ia2p_vit_embed": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F]),
+    "ia2p_vit_project": (_I, [_P, _P, _P, _P, _I, _I, _I]),
+    "ia2p_embed": (_I, [_P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
+    "ia2p_concat": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _I64]),
+    "ia2p_cat_rows": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _I]),
+    "ia2p_pixel_shuffle2": (_I, [_P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_hyper_dot": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I]),
+    "ia2p_sam_act": (_I, [_P, _P, _I64, _I]),
+    "ia2p_sam_add_rows": (_I, [_P, _P, _P, _P, _I64, _I64]),
+    "ia2p_sam_take_col": (_I, [_P, _P, _I64, _P, _I]),
     "ia2p_vae_create": (_I, [C.POINTER(VAEConfigC), C.POINTER(_P)]),
     "ia2p_vae_destroy": (None, [_P]),
     "ia2p_vae_last_error": (C.c_char_p, [_P]),

@@ -331,4 +331,79 @@ ia2p_status ia2p_attention_full(void* stream, const void* qkv, void* out, const 
   RET_HIP(e, "attention_full");
 }
 
+// ---- the small launches around the UNet, one by one (tests/test_encoder_ops_gpu.py): CLIP text / prior stem and pooling, VAE softmax and 1x1 convolution, ViT stem and
+//      head projection, the UNet's embeddings, channel concat and weight-row concat. Every refusal is decided here, before a launch: what the kernels assume
+//      (head dim 64, even sinusoid widths, 16-byte rows, a gamma with its beta) the launchers do not all check.
+ia2p_status ia2p_clip_embed(void* stream, const int32_t* ids, const void* tok, const void* embeds, const void* pos, void* x, float* stats, int rows, int T, int H, int vocab) {
+  if (!pos || !x || !stats || (!embeds && (!ids || !tok))) return fail(nullptr, IA2P_ERR_INVALID, "clip_embed: null argument (embeds, or ids with the token table)");
+  if (rows < 1 || T < 1 || H < 8 || H % 8 || (!embeds && vocab < 1)) return fail(nullptr, IA2P_ERR_SHAPE, "clip_embed: rows=%d T=%d H=%d (multiple of 8) vocab=%d", rows, T, H, vocab);
+  hipError_t e = ia2p_launch_clip_embed((const int*)ids, (const half_t*)tok, (const half_t*)embeds, (const half_t*)pos, (half_t*)x, stats, rows, T, H, vocab, (hipStream_t)stream);
+  RET_HIP(e, "clip_embed");
+}
+ia2p_status ia2p_causal_attention_small(void* stream, const void* qkv, void* out, int B, int T, int heads, int D) {
+  if (!qkv || !out) return fail(nullptr, IA2P_ERR_INVALID, "causal_attention_small: null argument");
+  if (B < 1 || heads < 1 || T < 1 || T > 128 || D != 64 || (size_t)B * heads > 0x7fffffff) return fail(nullptr, IA2P_ERR_SHAPE, "causal_attention_small: B=%d heads=%d T=%d (1..128) D=%d (64)", B, heads, T, D);
+  hipError_t e = ia2p_launch_causal_attention_small((const half_t*)qkv, (half_t*)out, B, T, heads, (hipStream_t)stream);
+  RET_HIP(e, "causal_attention_small");
+}
+ia2p_status ia2p_clip_pool(void* stream, const int32_t* ids, const void* x, const void* gamma, const void* beta, void* out, int B, int T, int H, int eos_id, float eps) {
+  if (!ids || !x || !gamma || !beta || !out || !(eps >= 0.f)) return fail(nullptr, IA2P_ERR_INVALID, "clip_pool: null argument or negative eps");
+  if (B < 1 || T < 1 || H < 1) return fail(nullptr, IA2P_ERR_SHAPE, "clip_pool: B=%d T=%d H=%d", B, T, H);
+  hipError_t e = ia2p_launch_clip_pool((const int*)ids, (const half_t*)x, (const half_t*)gamma, (const half_t*)beta, (half_t*)out, B, T, H, eos_id, eps, (hipStream_t)stream);
+  RET_HIP(e, "clip_pool");
+}
+ia2p_status ia2p_softmax_rows(void* stream, void* x, int64_t ld, int rows, int n, float scale) {
+  if (!x) return fail(nullptr, IA2P_ERR_INVALID, "softmax_rows: null argument");
+  if (rows < 1 || n < 8 || n % 8 || n > 8 * 256 * 8 || ld < n || ld % 8) return fail(nullptr, IA2P_ERR_SHAPE, "softmax_rows: rows=%d n=%d (multiple of 8, <= 16384) ld=%lld (multiple of 8, >= n)", rows, n, (long long)ld);
+  hipError_t e = ia2p_launch_softmax_rows((half_t*)x, (long)ld, rows, n, scale, (hipStream_t)stream);
+  RET_HIP(e, "softmax_rows");
+}
+ia2p_status ia2p_conv1x1_nchw(void* stream, const void* x, const void* w, const void* bias, void* y, int B, int Ci, int Co, int64_t HW) {
+  if (!x || !w || !bias || !y) return fail(nullptr, IA2P_ERR_INVALID, "conv1x1_nchw: null argument");
+  if (B < 1 || Ci < 1 || Ci > 8 || Co < 1 || Co > 8 || HW < 1) return fail(nullptr, IA2P_ERR_SHAPE, "conv1x1_nchw: B=%d Ci=%d Co=%d (1..8) HW=%lld", B, Ci, Co, (long long)HW);
+  hipError_t e = ia2p_launch_conv1x1_nchw((const half_t*)x, (const half_t*)w, (const half_t*)bias, (half_t*)y, B, Ci, Co, (long)HW, (hipStream_t)stream);
+  RET_HIP(e, "conv1x1_nchw");
+}
+ia2p_status ia2p_patch_gather(void* stream, const void* px, void* cols, int B, int C, int Hi, int Wi, int ps, int stride, int gh, int gw, int Kpad) {
+  if (!px || !cols) return fail(nullptr, IA2P_ERR_INVALID, "patch_gather: null argument");
+  if (B < 1 || C < 1 || ps < 1 || stride < 1 || gh < 1 || gw < 1 || (long)(gh - 1) * stride + ps > Hi || (long)(gw - 1) * stride + ps > Wi || (long)Kpad < (long)C * ps * ps || (long)B * gh * gw > 0x7fffffffL)
+    return fail(nullptr, IA2P_ERR_SHAPE, "patch_gather: a %d x %d grid of %d-pixel patches at stride %d does not fit %d x %d, or Kpad=%d < C ps ps", gh, gw, ps, stride, Hi, Wi, Kpad);
+  hipError_t e = ia2p_launch_patch_gather((const half_t*)px, (half_t*)cols, B, C, Hi, Wi, ps, stride, gh, gw, Kpad, (hipStream_t)stream);
+  RET_HIP(e, "patch_gather");
+}
+ia2p_status ia2p_vit_embed(void* stream, const void* patches, const void* cls, const void* pos, const void* stem_g, const void* stem_b, const void* pre_g, const void* pre_b,
+                           void* x, float* stats, int B, int T, int H, float eps) {
+  if (!patches || !cls || !pos || !x || !stats || (!stem_g) != (!stem_b) || (!pre_g) != (!pre_b) || !(eps >= 0.f)) return fail(nullptr, IA2P_ERR_INVALID, "vit_embed: null argument, a gamma without its beta, or negative eps");
+  if (B < 1 || T < 2 || H < 64 || H % 64 || H > 2048 || (long)B * T > 0x7fffffffL) return fail(nullptr, IA2P_ERR_SHAPE, "vit_embed: B=%d T=%d (>= 2) H=%d (multiple of 64, <= 2048)", B, T, H);
+  hipError_t e = ia2p_launch_vit_embed((const half_t*)patches, (const half_t*)cls, (const half_t*)pos, (const half_t*)stem_g, (const half_t*)stem_b, (const half_t*)pre_g, (const half_t*)pre_b,
+                                       (half_t*)x, stats, B, T, H, eps, (hipStream_t)stream);
+  RET_HIP(e, "vit_embed");
+}
+ia2p_status ia2p_vit_project(void* stream, const void* X, const void* W, float* out, int B, int N, int K) {
+  if (!X || !W || !out) return fail(nullptr, IA2P_ERR_INVALID, "vit_project: null argument");
+  if (B < 1 || B > 65535 || N < 1 || K < 8 || K % 8) return fail(nullptr, IA2P_ERR_SHAPE, "vit_project: B=%d (1..65535) N=%d K=%d (multiple of 8)", B, N, K);
+  hipError_t e = ia2p_launch_vit_project((const half_t*)X, (const half_t*)W, out, B, N, K, (hipStream_t)stream);
+  RET_HIP(e, "vit_project");
+}
+// ts != NULL: one timestep per batch element (device, fp32 [B]) instead of the scalar t
+ia2p_status ia2p_embed(void* stream, float t, const float* ts, const void* text_embeds, const void* time_ids, void* tsin, void* addin, int B, int Tp, int P, int Ad, int nids) {
+  if (!tsin || !addin || (P > 0 && !text_embeds) || (nids > 0 && !time_ids)) return fail(nullptr, IA2P_ERR_INVALID, "embed: null argument");
+  if (B < 1 || Tp < 2 || Tp % 2 || P < 0 || nids < 0 || (nids > 0 && (Ad < 2 || Ad % 2)) || (long)P + (long)nids * Ad > 0x7fffffffL)
+    return fail(nullptr, IA2P_ERR_SHAPE, "embed: B=%d Tp=%d Ad=%d (even, >= 2) P=%d nids=%d", B, Tp, Ad, P, nids);
+  hipError_t e = ia2p_launch_embed(t, ts, (const half_t*)text_embeds, (const half_t*)time_ids, (half_t*)tsin, (half_t*)addin, B, Tp, P, nids > 0 ? Ad : 0, nids, (hipStream_t)stream);
+  RET_HIP(e, "embed");
+}
+ia2p_status ia2p_concat(void* stream, const void* a, int lda, int Ca, const void* b, int ldb, int Cb, void* y, int64_t M) {
+  if (!a || !b || !y) return fail(nullptr, IA2P_ERR_INVALID, "concat: null argument");
+  if (M < 1 || Ca < 8 || Ca % 8 || Cb < 8 || Cb % 8 || lda < Ca || lda % 8 || ldb < Cb || ldb % 8) return fail(nullptr, IA2P_ERR_SHAPE, "concat: Ca=%d Cb=%d lda=%d ldb=%d (multiples of 8, ld >= C) M=%lld", Ca, Cb, lda, ldb, (long long)M);
+  hipError_t e = ia2p_launch_concat((const half_t*)a, lda, Ca, (const half_t*)b, ldb, Cb, (half_t*)y, (long)M, (hipStream_t)stream);
+  RET_HIP(e, "concat");
+}
+ia2p_status ia2p_cat_rows(void* stream, const void* a, int Ka, const void* b, int Kb, const void* bias_a, const void* bias_b, void* dst, void* bias_dst, int rows) {
+  if (!a || !b || !bias_a || !bias_b || !dst || !bias_dst) return fail(nullptr, IA2P_ERR_INVALID, "cat_rows: null argument");
+  if (rows < 1 || Ka < 8 || Ka % 8 || Kb < 8 || Kb % 8) return fail(nullptr, IA2P_ERR_SHAPE, "cat_rows: Ka=%d Kb=%d (multiples of 8) rows=%d", Ka, Kb, rows);
+  hipError_t e = ia2p_launch_cat_rows((const half_t*)a, Ka, (const half_t*)b, Kb, (const half_t*)bias_a, (const half_t*)bias_b, (half_t*)dst, (half_t*)bias_dst, rows, (hipStream_t)stream);
+  RET_HIP(e, "cat_rows");
+}
+
 }  // extern "C"

@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void pixel_shuffle2_kernel(const half_t* g, ha
   const h8 v = *(const h8*)(g + i * 8);
   *(h8*)(y + (((b * 2 * Hs + 2 * h + ky) * (long)(2 * Ws)) + 2 * w + kx) * Co + c) = v;
 }
-// mask[n, p] = sum_c hyper[n, c] up[n, p, c] (fp32 out; C % 8 == 0, C <= 512): one thread per pixel
+// mask[n, p] = sum_c hyper[n, c] up[n, p, c] (fp32 out; C % 8 == 0, any C: a serial chain per pixel): one thread per pixel
 __global__ __launch_bounds__(256) void hyper_dot_kernel(const half_t* hyper, long hyper_stride, const half_t* up, float* mask, int P, int C) {
   const int p = blockIdx.x * 256 + threadIdx.x, n = blockIdx.y;
   if (p >= P) return;

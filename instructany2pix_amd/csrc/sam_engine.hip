@@ -427,5 +427,36 @@ ia2p_status ia2p_mask_morph(void* stream, const void* src, void* dst, void* tmp,
   hipError_t e = ia2p_launch_mask_morph((const unsigned char*)src, (unsigned char*)dst, (unsigned char*)tmp, H, W, k, is_dilate != 0, (hipStream_t)stream);
   RET_HIP(e, "mask_morph");
 }
+// the small launches of the mask decoder, one by one (tests/test_encoder_ops_gpu.py)
+ia2p_status ia2p_pixel_shuffle2(void* stream, const void* g, void* y, int B, int Hs, int Ws, int Co) {
+  if (!g || !y) return fail(nullptr, IA2P_ERR_INVALID, "pixel_shuffle2: null argument");
+  if (B < 1 || Hs < 1 || Ws < 1 || Co < 8 || Co % 8 || ((long)B * Hs * Ws * 4 * (Co / 8) + 255) / 256 > 0x7fffffffL) return fail(nullptr, IA2P_ERR_SHAPE, "pixel_shuffle2: B=%d %d x %d Co=%d (multiple of 8)", B, Hs, Ws, Co);
+  hipError_t e = ia2p_launch_pixel_shuffle2((const half_t*)g, (half_t*)y, B, Hs, Ws, Co, (hipStream_t)stream);
+  RET_HIP(e, "pixel_shuffle2");
+}
+ia2p_status ia2p_hyper_dot(void* stream, const void* hyper, int64_t hyper_stride, const void* up, float* mask, int n, int P, int C) {
+  if (!hyper || !up || !mask) return fail(nullptr, IA2P_ERR_INVALID, "hyper_dot: null argument");
+  if (n < 1 || n > 65535 || P < 1 || C < 8 || C % 8 || hyper_stride < C || hyper_stride % 8) return fail(nullptr, IA2P_ERR_SHAPE, "hyper_dot: n=%d (1..65535) P=%d C=%d stride=%lld (multiples of 8, stride >= C)", n, P, C, (long long)hyper_stride);
+  hipError_t e = ia2p_launch_hyper_dot((const half_t*)hyper, (long)hyper_stride, (const half_t*)up, mask, n, P, C, (hipStream_t)stream);
+  RET_HIP(e, "hyper_dot");
+}
+ia2p_status ia2p_sam_act(void* stream, void* x, int64_t n, int kind) {
+  if (!x) return fail(nullptr, IA2P_ERR_INVALID, "sam_act: null argument");
+  if (n < 1 || (n + 255) / 256 > 0x7fffffffL || (kind != 0 && kind != 1)) return fail(nullptr, IA2P_ERR_SHAPE, "sam_act: n=%lld kind=%d (0 ReLU, 1 GELU)", (long long)n, kind);
+  hipError_t e = ia2p_launch_sam_act((half_t*)x, (long)n, kind, (hipStream_t)stream);
+  RET_HIP(e, "sam_act");
+}
+ia2p_status ia2p_sam_add_rows(void* stream, const void* a, const void* b, void* out, int64_t n, int64_t period) {
+  if (!a || !b || !out) return fail(nullptr, IA2P_ERR_INVALID, "sam_add_rows: null argument");
+  if (n < 8 || n % 8 || period < 8 || period % 8 || n % period || (n / 8 + 255) / 256 > 0x7fffffffL) return fail(nullptr, IA2P_ERR_SHAPE, "sam_add_rows: n=%lld period=%lld (multiples of 8, period dividing n)", (long long)n, (long long)period);
+  hipError_t e = ia2p_launch_sam_add_rows((const half_t*)a, (const half_t*)b, (half_t*)out, (long)n, (long)period, (hipStream_t)stream);
+  RET_HIP(e, "sam_add_rows");
+}
+ia2p_status ia2p_sam_take_col(void* stream, const void* src, int64_t ld, float* dst, int n) {
+  if (!src || !dst) return fail(nullptr, IA2P_ERR_INVALID, "sam_take_col: null argument");
+  if (n < 1 || ld < 1) return fail(nullptr, IA2P_ERR_SHAPE, "sam_take_col: n=%d ld=%lld", n, (long long)ld);
+  hipError_t e = ia2p_launch_sam_take_col((const half_t*)src, (long)ld, dst, n, (hipStream_t)stream);
+  RET_HIP(e, "sam_take_col");
+}
 
 }  // extern "C"
