@@ -3,7 +3,8 @@ tests/imagebind_ref.py, fp32 on the CPU with the same fp16-rounded weights and i
 
 Tolerances: the attention launch alone rel-L2 < 2e-3 (what test_ops_gpu.py::test_self_attention holds `ia2p_attention` to), a dominant late key max abs < 6e-3
 (test_self_attention_online_softmax_rescale); tower outputs rel-L2 <= 5e-3 (tests/test_clip_gpu.py: the same GEMMs, fp16 activations vs an fp32 oracle);
-end to end after L2 normalisation <= 1e-2 (normalising a vector at most doubles a relative error of 5e-3)."""
+end to end after L2 normalisation <= 1e-2 (normalising a vector at most doubles a relative error of 5e-3).
+The per-launch fp64 bound of `ia2p_attention_full`, at every sub-tile edge up to its 272 keys, lives in tests/attn_ops_ref.py / tests/test_attn_ops_gpu.py."""
 import os
 from dataclasses import replace
 

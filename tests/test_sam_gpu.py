@@ -3,6 +3,7 @@ of the attention launches.
 
 Tolerances.
   Attention launches alone: rel-L2 < 2e-3 against the fp64 arithmetic on the same fp16 inputs (the bound `ia2p_attention_full` is held to, test_imagebind_gpu.py).
+  The per-launch fp64 bounds of the three attention launches, the resize and the morphology live in tests/attn_ops_ref.py / tests/test_attn_ops_gpu.py.
   Encoder and box-to-mask: 3 x the error of the ORACLE ITSELF run in fp16 (`model.half()` on the CPU, same fp16-rounded weights) against fp64, measured on the
   CPU at exactly these shapes and seeds (tiny config, head dim 80, image 320, seed 0, the two boxes of sam_ref.BOXES); the margin is for reduction order and for
   the fp16 probability / activation stores the HIP path has and torch's CPU fp16 has not. Measured -> bound:
