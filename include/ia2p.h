@@ -570,6 +570,21 @@ ia2p_status ia2p_llm_decode_batch_dev(ia2p_llm* llm, void* stream, const int32_t
  * IA2P_ERR_INVALID: a null or misaligned pointer, do_sample outside {0, 1}, a temperature that is not positive and finite. IA2P_ERR_SHAPE: M, V or ld. */
 ia2p_status ia2p_sample_tokens(void* stream, const float* logits, int64_t ld, int M, int V, float temperature, int top_k, int do_sample, const uint64_t* seeds,
                                const uint32_t* steps, int32_t* tokens_out, float* probs_out, float* u_out);
+/* ia2p_sample_tokens with a nucleus (TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> softmax -> one draw). Limits on M, V, ld and alignment,
+ * do_sample = 0 (which ignores top_p), u, the -1 of a row that cannot be sampled, the by-value path for M <= 8 and the statuses are ia2p_sample_tokens's;
+ * top_p = 1 IS ia2p_sample_tokens, bit for bit (that call forwards here). A top_p that is NaN, <= 0 or > 1 is refused with IA2P_ERR_INVALID before any HIP call,
+ * whatever do_sample says.
+ * The rule for top_p < 1. Let K be the set top-k keeps (ties included, as above), e_i = exp(score_i - max) for i in K and Z their sum; for a score value v let
+ * T(v) be the sum of e_i over the i in K with score_i <= v. Index i is in the nucleus iff e_i > 0 and T(score_i) > (1 - top_p) * Z. For distinct scores this is
+ * transformers' rule (sort ascending, remove while the cumulative probability is <= 1 - top_p, always keep the last). Equal scores are kept or dropped
+ * TOGETHER: transformers splits a tied group by its position in the sort, which is unspecified; here a group that reaches into the nucleus is kept whole, as the
+ * top-k step keeps the ties at the k-th value. The maximum (with its ties) is always in the nucleus.
+ * Then p = e / Z' over the nucleus (Z' its fp32 sum), the cumulative sum in index order against u * Z', and probs_out exactly 0 outside the nucleus, all as above.
+ * T and Z are integer sums of trunc(e_i * 2^43) (1 - top_p taken in double from the fp32 top_p; the comparison is made on integers, with the threshold capped at
+ * Z - 1), so they have no summation order: the nucleus of a row does not depend on the launch, M, the row's place or its alignment. A term below 2^-43 of the
+ * largest counts as 0 there. */
+ia2p_status ia2p_sample_tokens_p(void* stream, const float* logits, int64_t ld, int M, int V, float temperature, int top_k, float top_p, int do_sample,
+                                 const uint64_t* seeds, const uint32_t* steps, int32_t* tokens_out, float* probs_out, float* u_out);
 /* workspace that serves a prefill of any row count up to max_T (0: none; the largest need over 1..max_T, which is not monotone in T) and decode steps of up to
  * max_rows rows; 0 for max_T < 0 or max_rows outside 1..8 */
 size_t ia2p_llm_batch_workspace_bytes(ia2p_llm* llm, int max_T, int max_rows);

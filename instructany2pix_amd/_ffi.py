@@ -198,6 +198,7 @@ SIGNATURES = {
     "ia2p_llm_decode_batch": (_I, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _P, _P, _SZ]),
     "ia2p_llm_decode_batch_dev": (_I, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), _I, _P, _P, _P, _SZ]),
     "ia2p_sample_tokens": (_I, [_P, _P, _I64, _I, _I, _F, _I, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _P, _P, _P]),
+    "ia2p_sample_tokens_p": (_I, [_P, _P, _I64, _I, _I, _F, _I, _F, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _P, _P, _P]),
     "ia2p_llm_batch_workspace_bytes": (_SZ, [_P, _I, _I]),
     "ia2p_llm_gemv_rows": (_I, [_P, _P, _P, _P, _I, _I, _I]),
     "ia2p_llm_gemv_q4_rows": (_I, [_P, _P, _P, C.POINTER(_F), _P, _P, _I, _I, _I]),

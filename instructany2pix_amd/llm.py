@@ -14,7 +14,8 @@
 Everything between `inputs_embeds` and (final-normed hidden row, logits row) runs through `ia2p_llm_*`; stopping and the text parsing are host code. The
 token is drawn from the logits row on the host (`sampler="host"`, the default: `sample_next` on torch's global RNG) or on the device (`sampler="device"`:
 `ia2p_sample_tokens`, one Philox stream per request, the next decode step reading the id from device memory while the host still checks the stopping
-criteria). The tokenizer is injected (its sentencepiece model is checkpoint data).
+criteria). Either sampler takes a nucleus (`top_p=`; `ia2p_sample_tokens_p` on the device), by default the one the checkpoint's generation_config.json names
+(`load_generation_config`), else none. The tokenizer is injected (its sentencepiece model is checkpoint data).
 
 Weight format. The reference's live call loads the checkpoint with `load_in_4bit=True, bnb_4bit_compute_dtype=torch.float32` and names no
 `bnb_4bit_quant_type` (pipeline.py:28-31). The default of the transformers version it pins (4.34.1) is believed to be "fp4" without double
@@ -101,21 +102,81 @@ class KeywordsStoppingCriteria(_StoppingCriteria):
         return all(self.call_bse(output_ids[i:i + 1], scores=None, **kwargs) for i in range(output_ids.shape[0]))
 
 
-def sample_probs(logits: torch.Tensor, temperature: float = 0.3, top_k: Optional[int] = 50) -> torch.Tensor:
-    """The distribution transformers' sampling loop draws from: `TemperatureLogitsWarper` -> `TopKLogitsWarper` -> softmax, in that order.
-    (transformers 4.34.1, which the reference pins, carries `top_k=50` in its default generation config.) logits: [..., vocab] fp32."""
+def _check_top_p(top_p) -> float:
+    """`TopPLogitsWarper.__init__`'s check and wording; NaN and 0 are refused too (the device sampler refuses them, and a nucleus of mass 0 names no token)"""
+    try:
+        p = float(top_p)
+    except (TypeError, ValueError):
+        p = float("nan")
+    if not (0.0 < p <= 1.0):
+        raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+    return p
+
+
+def _check_top_k(top_k):
+    """None and 0 switch top-k off (as `generate` reads them); anything else is `TopKLogitsWarper.__init__`'s check and wording"""
+    if top_k is None or (isinstance(top_k, int) and not isinstance(top_k, bool) and top_k == 0):
+        return None
+    if not isinstance(top_k, int) or isinstance(top_k, bool) or top_k <= 0:
+        raise ValueError(f"`top_k` has to be a strictly positive integer, but is {top_k}")
+    return top_k
+
+
+def sample_probs(logits: torch.Tensor, temperature: float = 0.3, top_k: Optional[int] = 50, top_p: float = 1.0) -> torch.Tensor:
+    """The distribution transformers' sampling loop draws from: `TemperatureLogitsWarper` -> `TopKLogitsWarper` -> `TopPLogitsWarper` -> softmax, in that
+    order. (transformers 4.34.1, which the reference pins, carries `top_k=50, top_p=1.0` in its default generation config; `generate` starts from the
+    checkpoint's own generation_config.json, and adds the top-p warper only when that holds `top_p < 1`: at `top_p >= 1` nothing is sorted here either.)
+    The top-p step is `TopPLogitsWarper.__call__` restated: sort ascending, remove while the cumulative probability is <= 1 - top_p, never the last.
+    logits: [..., vocab] fp32."""
+    top_p = _check_top_p(top_p)
     scores = logits.float() / temperature
     if top_k is not None and top_k > 0:
         k = min(int(top_k), scores.shape[-1])
         scores = scores.masked_fill(scores < torch.topk(scores, k)[0][..., -1, None], -float("inf"))
+    if top_p < 1.0:
+        sorted_scores, sorted_indices = torch.sort(scores, descending=False)
+        remove = sorted_scores.softmax(dim=-1).cumsum(dim=-1) <= (1 - top_p)
+        remove[..., -1:] = False                          # min_tokens_to_keep = 1
+        scores = scores.masked_fill(remove.scatter(-1, sorted_indices, remove), -float("inf"))
     return torch.nn.functional.softmax(scores, dim=-1)
 
 
-def sample_next(logits: torch.Tensor, do_sample: bool = True, temperature: float = 0.3, top_k: Optional[int] = 50) -> torch.Tensor:
+def sample_next(logits: torch.Tensor, do_sample: bool = True, temperature: float = 0.3, top_k: Optional[int] = 50, top_p: float = 1.0) -> torch.Tensor:
     """[1, vocab] logits -> [1] token ids; `torch.multinomial` on the global RNG of the logits' device, or argmax."""
     if not do_sample:
         return torch.argmax(logits, dim=-1)
-    return torch.multinomial(sample_probs(logits, temperature, top_k), num_samples=1).squeeze(1)
+    return torch.multinomial(sample_probs(logits, temperature, top_k, top_p), num_samples=1).squeeze(1)
+
+
+GENERATION_CONFIG_NAME = "generation_config.json"
+GENERATION_DEFAULTS = {"top_k": 50, "top_p": 1.0}          # transformers' default generation config, as far as this sampler reads it
+
+
+def read_generation_config(path_or_dict) -> dict:
+    """A generation_config.json (a dict with its content, the file, or a checkpoint folder that holds one) -> the keys this sampler reads, `top_k`,
+    `top_p` and `temperature`, checked; every other key is ignored, a key the file does not carry is not in the result."""
+    import json
+    import os
+    cfg = path_or_dict
+    if not isinstance(cfg, dict):
+        path = os.fspath(cfg)
+        if os.path.isdir(path):
+            path = os.path.join(path, GENERATION_CONFIG_NAME)
+        with open(path) as f:
+            cfg = json.load(f)
+        if not isinstance(cfg, dict):
+            raise ValueError(f"{path}: a generation config is a JSON object")
+    out = {}
+    if cfg.get("top_p") is not None:
+        out["top_p"] = _check_top_p(cfg["top_p"])
+    if "top_k" in cfg:
+        out["top_k"] = _check_top_k(cfg["top_k"])
+    if cfg.get("temperature") is not None:
+        t = cfg["temperature"]
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not (t > 0 and t < float("inf")):
+            raise ValueError(f"`temperature` has to be a strictly positive float, but is {t}")
+        out["temperature"] = float(t)
+    return out
 
 
 SAMPLERS = ("host", "device")
@@ -207,6 +268,7 @@ class HipInstructAny2PixLM:
     MAX_ROWS = 8                       # IA2P_LLM_MAX_ROWS: sequences per decode_batch call
     sampler = "host"                   # the constructor sets it per instance; the class default serves subclasses that stand in for the engine without
                                        # running the constructor (tests/test_llm_batch_cpu.py drives `generate_batch` through one)
+    generation_defaults = dict(GENERATION_DEFAULTS)      # likewise: the constructor gives the instance its own copy, `load_generation_config` a new one
 
     def __init__(self, config: LLMConfig, device="cuda:0", max_positions: int = 1024, video_token_id: Optional[int] = None, *,
                  load_in_4bit: bool = False, bnb_4bit_quant_type: str = "fp4", quantize_heads: bool = True, max_batch: int = 1, sampler: str = "host"):
@@ -220,6 +282,7 @@ class HipInstructAny2PixLM:
         if max_batch < 1:
             raise ValueError(f"max_batch {max_batch}: at least one slot")
         self.sampler = _resolve_sampler(sampler)
+        self.generation_defaults = dict(GENERATION_DEFAULTS)
         self.config = config.validate()
         self.device = torch.device(device)
         self.max_positions = max_positions
@@ -411,9 +474,25 @@ class HipInstructAny2PixLM:
                                                         _ffi.ptr(logits), _ffi.ptr(ws), ws.numel()))
         return hid, logits
 
-    def sample_tokens(self, logits: torch.Tensor, seeds, steps, do_sample: bool = True, temperature: float = 0.3, top_k: Optional[int] = 50, out=None):
-        """`ia2p_sample_tokens` on the fp32 rows [n, vocab] of `logits` (device): row r drawn with key seeds[r] at counter steps[r] -> int32 [n] on the
-        device (`out`, or a new tensor). Nothing is synchronised."""
+    def load_generation_config(self, path_or_dict) -> dict:
+        """What `from_pretrained` does with the checkpoint's generation_config.json: its `top_k`, `top_p` and `temperature` (a dict, the file, or the
+        checkpoint folder; other keys are ignored, an invalid value raises ValueError and changes nothing) replace the entries of
+        `generation_defaults`. `generate` / `generate_batch` read `top_p` from there when the call passes none. Their `top_k` and `temperature` keywords carry
+        defaults of their own (50, 0.3: the reference passes the temperature explicitly), which a call that names neither still gets; the loaded
+        values stand in `generation_defaults` for a caller to pass on. -> the new `generation_defaults`."""
+        self.generation_defaults = {**self.generation_defaults, **read_generation_config(path_or_dict)}
+        return self.generation_defaults
+
+    def _resolve_top_p(self, top_p) -> float:
+        """the `top_p` keyword: the call's own value, else the loaded generation config's, else 1.0; checked before any device work"""
+        return _check_top_p(self.generation_defaults.get("top_p", 1.0) if top_p is None else top_p)
+
+    def sample_tokens(self, logits: torch.Tensor, seeds, steps, do_sample: bool = True, temperature: float = 0.3, top_k: Optional[int] = 50, out=None,
+                      top_p: Optional[float] = None):
+        """`ia2p_sample_tokens_p` on the fp32 rows [n, vocab] of `logits` (device): row r drawn with key seeds[r] at counter steps[r] -> int32 [n] on the
+        device (`out`, or a new tensor). top_p None: `generation_defaults`' (1.0 unless a generation config was loaded; at 1.0 the launch is
+        `ia2p_sample_tokens`'s). Nothing is synchronised."""
+        top_p = self._resolve_top_p(top_p)
         block = logits.reshape(-1, logits.shape[-1])
         if block.dtype != torch.float32 or block.stride(1) != 1:
             raise ValueError("logits must be fp32 rows")
@@ -421,9 +500,9 @@ class HipInstructAny2PixLM:
         if len(seeds) != n or len(steps) != n:
             raise ValueError(f"{n} rows, {len(seeds)} seeds, {len(steps)} steps")
         out = torch.empty(n, dtype=torch.int32, device=block.device) if out is None else out[:n]
-        _ffi.check(self._lib.ia2p_sample_tokens(_ffi.current_stream(), C.c_void_p(block.data_ptr()), block.stride(0) if n > 1 else V, n, V, float(temperature),
-                                                int(top_k or 0), int(bool(do_sample)), (C.c_uint64 * n)(*seeds), (C.c_uint32 * n)(*steps), _ffi.ptr(out), None, None),
-                   None, llm=True)
+        _ffi.check(self._lib.ia2p_sample_tokens_p(_ffi.current_stream(), C.c_void_p(block.data_ptr()), block.stride(0) if n > 1 else V, n, V, float(temperature),
+                                                  int(top_k or 0), top_p, int(bool(do_sample)), (C.c_uint64 * n)(*seeds), (C.c_uint32 * n)(*steps), _ffi.ptr(out),
+                                                  None, None), None, llm=True)
         return out
 
     def prepare_inputs_embeds(self, input_ids: torch.Tensor, extra_replacement=None) -> torch.Tensor:
@@ -452,18 +531,21 @@ class HipInstructAny2PixLM:
 
     @torch.no_grad()
     def generate(self, input_ids, extra_replacement=None, do_sample: bool = True, temperature: float = 0.3, max_new_tokens: int = 100,
-                 stopping_criteria=None, top_k: Optional[int] = 50, sampler: Optional[str] = None, seed: Optional[int] = None, **unused):
+                 stopping_criteria=None, top_k: Optional[int] = 50, sampler: Optional[str] = None, seed: Optional[int] = None, top_p: Optional[float] = None,
+                 **unused):
         """-> object with `.sequences` ([1, prompt + new] on the host) and `.hidden_states` (one entry per new token;
         `hidden_states[i][-1][:, -1:]` is step i's final-normed last-position row, [1, 1, hidden] fp32 on the device).
         sampler: "host" or "device" (None: the constructor's). seed ("device" only): the request's Philox key; None draws one from torch's global CPU
         generator. The tokens of a seed are those the request gets inside any `generate_batch(sampler="device")` call under the same seed. Under "host"
-        `seed` is not used: that path draws from torch's global RNG, as it always has."""
+        `seed` is not used: that path draws from torch's global RNG, as it always has. top_p: the nucleus of either sampler; None takes
+        `generation_defaults["top_p"]` (what `load_generation_config` read, else 1.0: no nucleus, the path this call has always taken)."""
         sampler = _resolve_sampler(sampler, self.sampler)
+        top_p = self._resolve_top_p(top_p)
         if input_ids.ndim != 2 or input_ids.shape[0] != 1:
             raise ValueError("input_ids must be [1, tokens] (batch 1, as the reference asserts)")
         if sampler == "device":
             return self._generate_device([input_ids], [extra_replacement], do_sample, temperature, max_new_tokens, [stopping_criteria], top_k,
-                                         None if seed is None else [seed])[0]
+                                         None if seed is None else [seed], top_p)[0]
         seq = input_ids.detach().cpu().long()
         T = seq.shape[1]
         if T + max_new_tokens > self.max_positions:
@@ -475,7 +557,7 @@ class HipInstructAny2PixLM:
         hidden_states = []
         for step in range(max_new_tokens):
             hidden_states.append(_LastOnly(hid.reshape(1, 1, -1), nl))
-            nxt = sample_next(logits.reshape(1, -1).cpu(), do_sample, temperature, top_k)
+            nxt = sample_next(logits.reshape(1, -1).cpu(), do_sample, temperature, top_k, top_p)
             seq = torch.cat([seq, nxt.reshape(1, 1).long()], dim=1)
             if stopping_criteria is not None and any(bool(torch.as_tensor(c(seq, None)).all()) for c in stopping_criteria):
                 break
@@ -486,7 +568,7 @@ class HipInstructAny2PixLM:
 
     @torch.no_grad()
     def generate_batch(self, input_ids_list, extra_replacements=None, do_sample: bool = True, temperature: float = 0.3, max_new_tokens: int = 100,
-                       stopping_criteria=None, top_k: Optional[int] = 50, sampler: Optional[str] = None, seeds=None, **unused):
+                       stopping_criteria=None, top_k: Optional[int] = 50, sampler: Optional[str] = None, seeds=None, top_p: Optional[float] = None, **unused):
         """`generate` for several requests. input_ids_list: [1, T_i] prompts; extra_replacements / stopping_criteria: one entry per request (an
         `extra_replacement` dict / a list of criteria, or None), or None. -> a list with one `generate`-shaped object per request
         (`.sequences` [1, T_i + new_i], `.hidden_states` with one entry per new token).
@@ -504,15 +586,16 @@ class HipInstructAny2PixLM:
         sampler="device" (None: the constructor's choice) draws on the device instead, request i from its own Philox stream keyed by seeds[i] (None: one
         63-bit seed per request from torch's global CPU generator): each request then gets exactly the tokens and hidden rows of
         `generate(sampler="device", seed=seeds[i])`, whatever shares its batch. See `_generate_device`. Under "host" `seeds` is checked for its length
-        and otherwise not used: that path draws from torch's global RNG, as it always has."""
+        and otherwise not used: that path draws from torch's global RNG, as it always has. top_p: as in `generate`."""
         sampler = _resolve_sampler(sampler, self.sampler)
+        top_p = self._resolve_top_p(top_p)
         prompts = list(input_ids_list)
         n_req = len(prompts)
         seeds = None if seeds is None else list(seeds)
         if seeds is not None and len(seeds) != n_req:
             raise ValueError(f"{len(seeds)} seeds for {n_req} requests: one per request")
         if sampler == "device":
-            return self._generate_device(prompts, extra_replacements, do_sample, temperature, max_new_tokens, stopping_criteria, top_k, seeds)
+            return self._generate_device(prompts, extra_replacements, do_sample, temperature, max_new_tokens, stopping_criteria, top_k, seeds, top_p)
         reps = list(extra_replacements) if extra_replacements is not None else [None] * n_req
         crits = list(stopping_criteria) if stopping_criteria is not None else [None] * n_req
         if len(reps) != n_req or len(crits) != n_req:
@@ -539,7 +622,7 @@ class HipInstructAny2PixLM:
                     hidden[i].append(_LastOnly(hid[r].reshape(1, 1, -1), nl))
                 block = logits.cpu()                                     # [n_active, vocab]: one copy per step
                 if do_sample:
-                    nxt = torch.multinomial(sample_probs(block, temperature, top_k), num_samples=1).squeeze(1)
+                    nxt = torch.multinomial(sample_probs(block, temperature, top_k, top_p), num_samples=1).squeeze(1)
                 else:
                     nxt = torch.argmax(block, dim=-1)
                 go_on, tokens = [], []
@@ -557,14 +640,15 @@ class HipInstructAny2PixLM:
 
 
     @torch.no_grad()
-    def _generate_device(self, prompts, extra_replacements, do_sample, temperature, max_new_tokens, stopping_criteria, top_k, seeds):
-        """`generate_batch` with the token drawn on the device. Per step of a group: `ia2p_sample_tokens` on the step's logits block, the ids copied
+    def _generate_device(self, prompts, extra_replacements, do_sample, temperature, max_new_tokens, stopping_criteria, top_k, seeds, top_p: Optional[float] = None):
+        """`generate_batch` with the token drawn on the device. Per step of a group: `ia2p_sample_tokens_p` on the step's logits block, the ids copied
         asynchronously into pinned host memory, an event behind the copy, and -- before the host waits for that event -- the next `decode_batch_dev`
         for every row still active, reading its id from device memory. Only then are the ids read, appended and shown to the stopping criteria. A
         request that turns out to have stopped has had one decode row too many computed: that row is dropped (it is never appended to
         `hidden_states`, and the slot is reset at its next use), and from the next step on `token_index` names the live rows of the id buffer.
         Row r of a step is drawn under (seed of its request, number of tokens the request has): nothing depends on the other rows."""
         n_req = len(prompts)
+        top_p = self._resolve_top_p(top_p)
         reps = list(extra_replacements) if extra_replacements is not None else [None] * n_req
         crits = list(stopping_criteria) if stopping_criteria is not None else [None] * n_req
         if len(reps) != n_req or len(crits) != n_req:
@@ -594,7 +678,7 @@ class HipInstructAny2PixLM:
             for step in range(max_new_tokens):
                 for i in active:
                     hidden[i].append(_LastOnly(hid[block.index(i)].reshape(1, 1, -1), nl))
-                self.sample_tokens(logits, [seeds[i] for i in block], [step] * len(block), do_sample, temperature, top_k, out=self._tok_dev)
+                self.sample_tokens(logits, [seeds[i] for i in block], [step] * len(block), do_sample, temperature, top_k, out=self._tok_dev, top_p=top_p)
                 self._tok_host[:len(block)].copy_(self._tok_dev[:len(block)], non_blocking=True)
                 done = torch.cuda.Event()
                 done.record()

@@ -19,6 +19,7 @@ already-computed conditioning and is what bench.py and the parity tests drive.
 """
 from __future__ import annotations
 
+import os
 from typing import Any, Callable, Optional
 
 import PIL.Image
@@ -109,6 +110,11 @@ class InstructAny2PixPipeline:
         # ImageBind; an entry may carry its vector directly as entry["embed"]); imagebind: a HipImageBindModel (reference :118-121 `self.model_imb`) that
         # encodes the entries' files itself when neither of the two is given
         self.any2pix_lm, self.any2pix_tokenizer, self.modality_encoder = llm, llm_tokenizer, modality_encoder
+        # the checkpoint's own generation_config.json (reference :28 `from_pretrained(f"{ckpt}/{llm_folder}")` reads it; `generate` then starts from its top_k /
+        # top_p): loaded into the LLM's `generation_defaults` when the folder holds one. forward_llm passes neither keyword, so they come from there.
+        gen_cfg = os.path.join(str(ckpt), str(llm_folder), "generation_config.json")
+        if llm is not None and hasattr(llm, "load_generation_config") and os.path.isfile(gen_cfg):
+            llm.load_generation_config(gen_cfg)
         self.model_imb = imagebind
         # segmenter: a sam.HipSamPredictor (reference :147 `self.sam`); detector(image uint8 [H, W, 3], text_prompt) -> (boxes cxcywh in [0, 1] [n, 4], phrases): stands in
         # for GroundingDINO (:148 `self.gdino`, not built here). Both serve subjects the conditioner names by phrase: subject_data = [(phrase, embedding)]

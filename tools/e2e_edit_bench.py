@@ -14,7 +14,7 @@ Prints per-stage wall times (stream-synchronised) after one warm-up request.
 --sampler device (the switch of tools/llm_decode_bench.py; also spelled --llm-sampler) draws the token on the device (`HipInstructAny2PixLM(sampler="device")`): the sampler kernel runs on every step's logits row and the
 script then overwrites the id in device memory (one fill launch per step, which the product does not have), so the next decode step still reads it there.
 
-    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4] [--sampler host|device] [--imagebind]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)"""
+    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4] [--sampler host|device] [--top-p P] [--imagebind]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)"""
 import argparse
 import os
 import sys
@@ -42,6 +42,7 @@ _ap = argparse.ArgumentParser()
 _ap.add_argument("--llm-bits", type=int, default=16, choices=(16, 4))
 _ap.add_argument("--llm-quant-type", default="fp4", choices=("fp4", "nf4"))
 _ap.add_argument("--sampler", "--llm-sampler", dest="llm_sampler", default="host", choices=("host", "device"))
+_ap.add_argument("--top-p", type=float, default=None, help="nucleus of the LLM's sampler, as a checkpoint's generation_config.json would set it (default: none, top_p = 1)")
 _ap.add_argument("--imagebind", action="store_true", help="encode the mm_data entries' files with the HIP ImageBind towers instead of seeded vectors")
 ARGS = _ap.parse_args()
 DEV = "cuda:0"
@@ -65,6 +66,8 @@ ltok = StubLlamaTokenizer(32000)
 lm = llm_mod.HipInstructAny2PixLM(lcfg, DEV, max_positions=512, load_in_4bit=ARGS.llm_bits == 4, bnb_4bit_quant_type=ARGS.llm_quant_type,
                                   sampler=ARGS.llm_sampler)
 lm.load_state_dict(iter_synthetic(llm_param_specs(lcfg), 9, DEV, torch.float16))
+if ARGS.top_p is not None:      # forward_llm passes no top_p: it reaches `generate` the way a loaded generation config does
+    lm.load_generation_config({"top_p": ARGS.top_p})
 print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior, LLM with {lm.weight_bits}-bit "
       f"projections: arena {lm.arena.numel() / 1e9:.2f} GB)", flush=True)
 

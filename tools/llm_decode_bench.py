@@ -24,8 +24,10 @@ the library had for M = 1, `ia2p_linear_small`.
           tokens and once for one, and the figure is the difference per further token: ms per generated token with the prefills taken out. Under "host" the
           tool passes no `sampler` keyword when the tree's `generate` has none, so the same command times a tree from before the keyword. Then the sampler
           launch alone (`ia2p_sample_tokens` on 1 and 8 logits rows of the vocabulary, device events around 200 launches, us per launch).
+  --top-p P (with --sampler): the calls above pass `top_p=P`, and the `ia2p_sample_tokens_p` launch at that top-p is timed next to the `ia2p_sample_tokens`
+          launch, the two alternating in the one process: 1 and 8 rows of 32000, top-k 50 and 0.
 
-    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--bits 4] [--quant-type fp4] [--batch 1,2,4,8] [--sampler host,device] [--rounds 3]
+    python tools/llm_decode_bench.py [--layers 32] [--tokens 100] [--reps 30] [--bits 4] [--quant-type fp4] [--batch 1,2,4,8] [--sampler host,device] [--top-p P] [--rounds 3]
                                      [--skip-decode] [--skip-gemv]
 """
 import argparse
@@ -113,7 +115,7 @@ def batch_part(layers, tokens, rows, bits=16, quant_type="fp4"):
     torch.cuda.empty_cache()
 
 
-def sampler_part(layers, tokens, samplers, rounds, bits=16, quant_type="fp4"):
+def sampler_part(layers, tokens, samplers, rounds, bits=16, quant_type="fp4", top_p=None):
     import inspect
     cfg = vicuna_7b(32000)
     cfg.num_hidden_layers = layers
@@ -126,11 +128,11 @@ def sampler_part(layers, tokens, samplers, rounds, bits=16, quant_type="fp4"):
         sys.exit("--sampler: this tree's generate() has the host sampler only")
     g = torch.Generator().manual_seed(1)
     prompts = [torch.randint(3, cfg.vocab_size, (1, 64), generator=g) for _ in range(8)]
-    print(f"[{fmt}] whole generate / generate_batch calls, {layers} layers, sampling at temperature 0.3, top-k 50; ms per generated token = "
+    print(f"[{fmt}] whole generate / generate_batch calls, {layers} layers, sampling at temperature 0.3, top-k 50{'' if top_p is None else f', top-p {top_p}'}; ms per generated token = "
           f"(call with {tokens} new tokens - call with 1) / {tokens - 1}", flush=True)
 
     def call(n, sampler, new):
-        kw = dict(do_sample=True, temperature=0.3, max_new_tokens=new, **({"sampler": sampler} if has_kw else {}))
+        kw = dict(do_sample=True, temperature=0.3, max_new_tokens=new, **({"sampler": sampler} if has_kw else {}), **({} if top_p is None else {"top_p": top_p}))
         torch.cuda.synchronize(); t0 = time.perf_counter()
         if n == 1:
             lm.generate(prompts[0], **kw)
@@ -163,8 +165,40 @@ def sampler_part(layers, tokens, samplers, rounds, bits=16, quant_type="fp4"):
                     e1.record(); e1.synchronize()
                     med.append(e0.elapsed_time(e1) * 1e3 / 200)
                 print(f"  ia2p_sample_tokens, {n} row{'s' if n > 1 else ''} of {V}, {what}: {statistics.median(med):.2f} us per launch (back to back, median of 5 x 200; min {min(med):.2f})", flush=True)
+        if top_p is not None:
+            nucleus_launch_part(lib, s, logits, out, top_p)
     del lm
     torch.cuda.empty_cache()
+
+
+def nucleus_launch_part(lib, s, logits, out, top_p):
+    """the `ia2p_sample_tokens_p` launch next to the `ia2p_sample_tokens` launch, interleaved in the one process: V = 32000, 1 and 8 rows, top-k 50 and 0"""
+    V = logits.shape[1]
+
+    def launches(n, top_k, p, seeds, steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(200):
+            if p is None:
+                st = lib.ia2p_sample_tokens(s, _ffi.ptr(logits), V, n, V, 0.3, top_k, 1, seeds, steps, _ffi.ptr(out), None, None)
+            else:
+                st = lib.ia2p_sample_tokens_p(s, _ffi.ptr(logits), V, n, V, 0.3, top_k, p, 1, seeds, steps, _ffi.ptr(out), None, None)
+            _ffi.check(st, None, llm=True)
+        e1.record(); e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / 200
+
+    for n in (1, 8):
+        seeds, steps = (C.c_uint64 * n)(*range(1, n + 1)), (C.c_uint32 * n)(*range(n))
+        for top_k in (50, 0):
+            med = {None: [], top_p: []}
+            for rnd in range(6):               # round 0 warms up; the two launches alternate
+                for p in (None, top_p):
+                    t = launches(n, top_k, p, seeds, steps)
+                    if rnd:
+                        med[p].append(t)
+            a, b = statistics.median(med[None]), statistics.median(med[top_p])
+            print(f"  {n} row{'s' if n > 1 else ''} of {V}, temperature 0.3, top-k {top_k}: ia2p_sample_tokens {a:.2f} us per launch (min {min(med[None]):.2f}), "
+                  f"ia2p_sample_tokens_p at top-p {top_p} {b:.2f} us (min {min(med[top_p]):.2f}): + {b - a:.2f} us (back to back, median of 5 x 200, interleaved)", flush=True)
 
 
 def gemv_part(reps, bits=16, quant_type="fp4", rows=()):
@@ -265,6 +299,7 @@ if __name__ == "__main__":
     ap.add_argument("--quant-type", default="fp4", choices=sorted(BNB_4BIT_CODEBOOKS))
     ap.add_argument("--batch", default="", help="comma-separated row counts (1..8) for the batched decode and the multi-row GEMVs, e.g. 1,2,4,8")
     ap.add_argument("--sampler", default="", help="comma-separated samplers (host, device) for the whole-call timing of generate / generate_batch")
+    ap.add_argument("--top-p", type=float, default=None, help="with --sampler: pass top_p to generate / generate_batch, and time the ia2p_sample_tokens_p launch next to ia2p_sample_tokens")
     ap.add_argument("--rounds", type=int, default=3, help="timed rounds of the --sampler part (after one warm-up round)")
     ap.add_argument("--skip-decode", action="store_true")
     ap.add_argument("--skip-gemv", action="store_true")
@@ -288,6 +323,6 @@ if __name__ == "__main__":
             if rows:
                 batch_part(a.layers, a.tokens, rows, 4, a.quant_type)
     if samplers:
-        sampler_part(a.layers, a.tokens, samplers, a.rounds)
+        sampler_part(a.layers, a.tokens, samplers, a.rounds, top_p=a.top_p)
         if a.bits == 4:
-            sampler_part(a.layers, a.tokens, samplers, a.rounds, 4, a.quant_type)
+            sampler_part(a.layers, a.tokens, samplers, a.rounds, 4, a.quant_type, top_p=a.top_p)
