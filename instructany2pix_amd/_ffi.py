@@ -5,7 +5,9 @@ symbols, and every compute entry point needs device pointers on an MI355X.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -283,13 +285,23 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def check(status: int, ctx=None, vae=False, clip=False, llm=False, vit=False, sam=False):
+FAMILIES = ("", "vae", "clip", "vit", "sam", "llm")      # the executors behind `ia2p_<family>_*`; "" is the UNet's unprefixed `ia2p_*`
+
+
+def _family_fn(l, family: str, name: str):
+    return getattr(l, f"ia2p_{family}_{name}" if family else f"ia2p_{name}")
+
+
+def check(status: int, ctx=None, family: str = "", **spelled):
     """Map ia2p_status to the exception types the reference raises at the same conditions
-    (ValueError from check_inputs/_get_add_time_ids, reference pnp_pipeline.py:49-66)."""
+    (ValueError from check_inputs/_get_add_time_ids, reference pnp_pipeline.py:49-66). The text is `ia2p_<family>_last_error(ctx)`;
+    `vae=True` and the other family names as keywords are spellings of `family="vae"`."""
     if status == IA2P_OK:
         return
-    msg = (lib().ia2p_sam_last_error(ctx) if sam else lib().ia2p_vit_last_error(ctx) if vit else lib().ia2p_llm_last_error(ctx) if llm else lib().ia2p_clip_last_error(ctx) if clip else lib().ia2p_vae_last_error(ctx) if vae
-           else lib().ia2p_last_error(ctx))
+    family = next((f for f, on in spelled.items() if on), family)
+    if family not in FAMILIES:
+        raise TypeError(f"check: no executor family '{family}'")
+    msg = _family_fn(lib(), family, "last_error")(ctx)
     msg = msg.decode() if msg else ""
     text = f"ia2p {_STATUS_NAMES.get(status, status)}: {msg}"
     if status in (1, 2):
@@ -312,6 +324,100 @@ def ptr(t):
 def current_stream():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def on_device(method):
+    """A method of an `Executor` that hands the library a stream: runs with the executor's device current (see `Executor`)."""
+    @functools.wraps(method)
+    def run(self, *a, **kw):
+        with self._on_device():
+            return method(self, *a, **kw)
+    return run
+
+
+class Executor:
+    """One handle behind `ia2p_<family>_*` and the device memory it runs in; the six model classes derive from it. The lifecycle they share
+    (DESIGN.md §13): create -> arena_bytes -> allocate and bind the arena -> load_tensor per parameter -> finalize -> workspace -> the
+    model's own pass entry points -> destroy. The arena (`arena`) and the workspace (`_ws`) are torch tensors this object owns; the
+    library borrows them and allocates nothing itself.
+
+    Device rule: whatever hands the library a stream runs with `self.device` current. `current_stream()` is the CURRENT device's stream,
+    and the pointers next to it live on `self.device`: without the guard a process whose current device is another GPU would pair a
+    stream of one GPU with memory of another. The guard is scoped (`torch.cuda.device`); it leaves the process's current device alone."""
+
+    _h = None            # class-level defaults: an object whose constructor raised (or never ran: a test stand-in) still destroys cleanly
+    _ws = None
+
+    def __init__(self, family: str, config_c, device, prepare=None):
+        """`config_c`: the family's config struct; `prepare()`: what must happen between create and the sizing of the arena."""
+        import torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise IA2PError(f"{type(self).__name__} runs only on an MI355X device (no CPU path exists)")
+        self._family, self._lib = family, lib()
+        with self._on_device():
+            if not self._lib.ia2p_device_is_gfx950():
+                raise IA2PError("libia2p_hip.so is compiled for gfx950 only")
+            h = C.c_void_p()
+            check(self._fn("create")(C.byref(config_c), C.byref(h)), None, family)
+            self._h = h
+            if prepare is not None:
+                prepare()
+            n = self._fn("arena_bytes")(h)
+            self.arena = torch.zeros(n, dtype=torch.uint8, device=self.device)     # the ONE flat weight buffer
+            self.check(self._fn("bind_arena")(h, ptr(self.arena), n))
+
+    def _fn(self, name: str):
+        return _family_fn(self._lib, self._family, name)
+
+    def _on_device(self):
+        import torch
+        if self.device.type != "cuda":     # only a stand-in that skipped the constructor (the tests drive the LLM's host bookkeeping through one on the CPU)
+            return contextlib.nullcontext()
+        return torch.cuda.device(self.device)
+
+    def check(self, status: int):
+        check(status, self._h, self._family)
+
+    def __del__(self):
+        try:
+            h, self._h = self._h, None
+            if h:
+                self._fn("destroy")(h)
+        except Exception:
+            pass
+
+    # torch.nn.Module look-alikes the pipelines call
+    def to(self, *a, **kw):
+        return self
+
+    def eval(self):
+        return self
+
+    @on_device
+    def load_tensor(self, key: str, tensor):
+        import torch
+        t = tensor.detach().to(device=self.device, dtype=torch.float16).contiguous()
+        shape = (C.c_int64 * t.ndim)(*t.shape)
+        self.check(self._fn("load_tensor")(self._h, key.encode(), ptr(t), shape, t.ndim, current_stream()))
+        # the copy into the arena is only enqueued, and `t` is a temporary whenever the caller's tensor was not fp16, contiguous and on
+        # this device already: wait for the copy before the temporary can die
+        torch.cuda.current_stream().synchronize()
+
+    @on_device
+    def finalize(self):
+        self.check(self._fn("finalize_weights")(self._h))
+
+    @on_device
+    def workspace(self, nbytes: int):
+        """The workspace tensor for a pass that needs `nbytes` (the answer of a `*_workspace_bytes` query; 0 is that query's refusal, raised
+        with the handle's message). One buffer, which grows only when it is too small."""
+        import torch
+        if nbytes == 0:
+            self.check(2)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
 
 
 def make_config(cfg) -> UNetConfigC:

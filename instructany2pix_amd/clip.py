@@ -11,7 +11,6 @@ checkpoint data): `tokenizer(prompts, padding="max_length", max_length=77, trunc
 """
 from __future__ import annotations
 
-import ctypes as C
 from types import SimpleNamespace
 from typing import Callable, List, Optional
 
@@ -43,42 +42,24 @@ class CLIPTextOutput(SimpleNamespace):
         return [getattr(self, k) for k in self._order][i]
 
 
-class HipCLIPTextModel:
+class HipCLIPTextModel(_ffi.Executor):
+    dtype = torch.float16
+
     def __init__(self, config: CLIPTextConfig, device="cuda:0"):
         self.config = config.validate()
-        self.device = torch.device(device)
-        self._lib = _ffi.lib()
-        self._h = C.c_void_p()
-        _ffi.check(self._lib.ia2p_clip_create(C.byref(_ffi.make_clip_config(config)), C.byref(self._h)), None, clip=True)
-        with torch.cuda.device(self.device):
-            self.arena = torch.zeros(self._lib.ia2p_clip_arena_bytes(self._h), dtype=torch.uint8, device=self.device)
-        _ffi.check(self._lib.ia2p_clip_bind_arena(self._h, _ffi.ptr(self.arena), self.arena.numel()), self._h, clip=True)
-        self._ws = None
-        self.dtype = torch.float16
-
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.ia2p_clip_destroy(self._h)
-        except Exception:
-            pass
-
-    def to(self, *a, **kw):
-        return self
+        super().__init__("clip", _ffi.make_clip_config(config), device)
 
     def load_state_dict(self, state_dict, strict: bool = True):
         items = state_dict.items() if hasattr(state_dict, "items") else state_dict
         for k, v in items:
             if k.endswith("position_ids"):          # buffer in older transformers checkpoints
                 continue
-            t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
-            shape = (C.c_int64 * t.ndim)(*t.shape)
-            _ffi.check(self._lib.ia2p_clip_load_tensor(self._h, k.encode(), _ffi.ptr(t), shape, t.ndim, _ffi.current_stream()), self._h, clip=True)
-            torch.cuda.current_stream().synchronize()
+            self.load_tensor(k, v)
         if strict:
-            _ffi.check(self._lib.ia2p_clip_finalize_weights(self._h), self._h, clip=True)
+            self.finalize()
 
     @torch.no_grad()
+    @_ffi.on_device
     def __call__(self, input_ids: torch.Tensor, output_hidden_states: bool = False, want_last_hidden: Optional[bool] = None,
                  want_pooled: bool = True, **unused):
         """want_last_hidden / want_pooled = False skip work the caller does not read (the last layer, when only hidden_states[-2]
@@ -87,11 +68,7 @@ class HipCLIPTextModel:
             raise ValueError("input_ids must be [batch, tokens]")
         B, T = input_ids.shape
         ids = input_ids.to(device=self.device, dtype=torch.int32).contiguous()
-        n = self._lib.ia2p_clip_workspace_bytes(self._h, B, T)
-        if n == 0:
-            _ffi.check(2, self._h, clip=True)
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        ws = self.workspace(self._lib.ia2p_clip_workspace_bytes(self._h, B, T))
         cfg = self.config
         hid2 = torch.empty(B, T, cfg.hidden_size, dtype=torch.float16, device=self.device) if output_hidden_states else None
         if want_last_hidden is None:
@@ -100,8 +77,8 @@ class HipCLIPTextModel:
         pooled = torch.empty(B, cfg.projection_dim or cfg.hidden_size, dtype=torch.float16, device=self.device) if want_pooled else None
         if hid2 is None and last is None and pooled is None:
             raise ValueError("nothing requested")
-        _ffi.check(self._lib.ia2p_clip_encode(self._h, _ffi.current_stream(), _ffi.ptr(ids), B, T, _ffi.ptr(hid2), _ffi.ptr(last), _ffi.ptr(pooled),
-                                              _ffi.ptr(self._ws), self._ws.numel()), self._h, clip=True)
+        self.check(self._lib.ia2p_clip_encode(self._h, _ffi.current_stream(), _ffi.ptr(ids), B, T, _ffi.ptr(hid2), _ffi.ptr(last), _ffi.ptr(pooled),
+                                              _ffi.ptr(ws), ws.numel()))
         hs = _PenultimateOnly(hid2, cfg.num_hidden_layers + 1) if hid2 is not None else None
         if cfg.projection_dim:            # CLIPTextModelWithProjection: (text_embeds, last_hidden_state, hidden_states)
             out = CLIPTextOutput(text_embeds=pooled, last_hidden_state=last, hidden_states=hs)

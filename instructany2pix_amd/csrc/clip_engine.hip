@@ -20,43 +20,35 @@ static ia2p_status clip_plan(ia2p_clip* c) {
     return fail(c, IA2P_ERR_SHAPE, "clip: hidden %d must be heads*64, intermediate %d a multiple of 64, 1..128 positions", H, I);
   if (g.hidden_act < 1 || g.hidden_act > 3) return fail(c, IA2P_ERR_INVALID, "clip: hidden_act must be 1 (gelu), 2 (quick_gelu) or 3 (gelu_new)");
   if (g.projection_dim < 0 || g.projection_dim % 8) return fail(c, IA2P_ERR_SHAPE, "clip: projection_dim %d", g.projection_dim);
-  size_t cur = 0;
-  auto take = [&](size_t e) { size_t o = cur; cur += (e + 127) & ~(size_t)127; return o; };
-  auto reg = [&](const std::string& k, size_t off, size_t n) { c->params[k] = Param{off, n, PK_COPY, 0, 0, false, false}; };
-  auto par = [&](const std::string& k, size_t n) { size_t o = take(n); reg(k, o, n); return o; };
+  ArenaPlan A{c};
   const std::string tm = "text_model.";
-  c->tok = g.vocab_size ? par(tm + "embeddings.token_embedding.weight", (size_t)g.vocab_size * H) : 0;   // 0: inputs_embeds only (the GPT-2 prior)
-  c->pos = par(tm + "embeddings.position_embedding.weight", (size_t)g.max_positions * H);
+  c->tok = g.vocab_size ? A.par(tm + "embeddings.token_embedding.weight", (size_t)g.vocab_size * H) : 0;   // 0: inputs_embeds only (the GPT-2 prior)
+  c->pos = A.par(tm + "embeddings.position_embedding.weight", (size_t)g.max_positions * H);
   for (int i = 0; i < g.num_layers; ++i) {
     const std::string p = tm + "encoder.layers." + std::to_string(i) + ".";
     CLayer l;
-    l.ln1g = par(p + "layer_norm1.weight", H); l.ln1b = par(p + "layer_norm1.bias", H);
-    l.wqkv = take((size_t)3 * H * H); l.bqkv = take((size_t)3 * H);
+    l.ln1g = A.par(p + "layer_norm1.weight", H); l.ln1b = A.par(p + "layer_norm1.bias", H);
+    l.wqkv = A.take((size_t)3 * H * H); l.bqkv = A.take((size_t)3 * H);
     const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
     for (int j = 0; j < 3; ++j) {
-      reg(p + "self_attn." + nm[j] + ".weight", l.wqkv + (size_t)j * H * H, (size_t)H * H);
-      reg(p + "self_attn." + nm[j] + ".bias", l.bqkv + (size_t)j * H, H);
+      A.reg(p + "self_attn." + nm[j] + ".weight", l.wqkv + (size_t)j * H * H, (size_t)H * H);
+      A.reg(p + "self_attn." + nm[j] + ".bias", l.bqkv + (size_t)j * H, H);
     }
-    l.wo = par(p + "self_attn.out_proj.weight", (size_t)H * H); l.bo = par(p + "self_attn.out_proj.bias", H);
-    l.ln2g = par(p + "layer_norm2.weight", H); l.ln2b = par(p + "layer_norm2.bias", H);
-    l.w1 = par(p + "mlp.fc1.weight", (size_t)I * H); l.b1 = par(p + "mlp.fc1.bias", I);
-    l.w2 = par(p + "mlp.fc2.weight", (size_t)H * I); l.b2 = par(p + "mlp.fc2.bias", H);
-    l.fqkv = take((size_t)3 * H * H); l.cs1 = take((size_t)2 * 3 * H); l.lb1 = take((size_t)2 * 3 * H);
-    l.f1 = take((size_t)I * H); l.cs2 = take((size_t)2 * I); l.lb2 = take((size_t)2 * I);
+    l.wo = A.par(p + "self_attn.out_proj.weight", (size_t)H * H); l.bo = A.par(p + "self_attn.out_proj.bias", H);
+    l.ln2g = A.par(p + "layer_norm2.weight", H); l.ln2b = A.par(p + "layer_norm2.bias", H);
+    l.w1 = A.par(p + "mlp.fc1.weight", (size_t)I * H); l.b1 = A.par(p + "mlp.fc1.bias", I);
+    l.w2 = A.par(p + "mlp.fc2.weight", (size_t)H * I); l.b2 = A.par(p + "mlp.fc2.bias", H);
+    xf_take_folds(A, l, H, I);
     c->layers.push_back(l);
   }
-  c->lnfg = par(tm + "final_layer_norm.weight", H); c->lnfb = par(tm + "final_layer_norm.bias", H);
-  c->wproj = g.projection_dim ? par("text_projection.weight", (size_t)g.projection_dim * H) : 0;
-  c->arena_elems = cur;
+  c->lnfg = A.par(tm + "final_layer_norm.weight", H); c->lnfb = A.par(tm + "final_layer_norm.bias", H);
+  c->wproj = g.projection_dim ? A.par("text_projection.weight", (size_t)g.projection_dim * H) : 0;
+  c->arena_elems = A.cur;
   return IA2P_OK;
 }
 
 static ia2p_status clip_fold(ia2p_clip* c, hipStream_t stream = nullptr, bool sync = true) {
-  hipError_t e = xf_fold(c, c->layers, c->cfg.hidden_size, c->cfg.intermediate_size, stream);
-  if (e == hipSuccess && sync) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) return fail_hip(c, e, "clip LayerNorm folding");
-  c->fold_dirty = false;
-  return IA2P_OK;
+  return xf_refold(c, c->layers, c->cfg.hidden_size, c->cfg.intermediate_size, stream, sync, "clip");
 }
 
 static ia2p_status clip_run(ia2p_clip* c, const int* ids, const half_t* embeds, int B, int T, half_t* hid2, half_t* last, half_t* pooled) {
@@ -101,19 +93,14 @@ static ia2p_status clip_run(ia2p_clip* c, const int* ids, const half_t* embeds, 
 }
 
 ia2p_status ia2p_clip_create(const ia2p_clip_config* cfg, ia2p_clip** out) {
-  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_clip_create: null argument");
-  ia2p_clip* c = new ia2p_clip();
-  c->cfg = *cfg;
-  if (c->cfg.layer_norm_eps <= 0.f) c->cfg.layer_norm_eps = 1e-5f;
-  ia2p_status st = clip_plan(c);
-  if (st != IA2P_OK) { g_err = c->err; delete c; *out = nullptr; return st; }
-  c->failed = false;
-  *out = c;
-  return IA2P_OK;
+  return rc_create(cfg, out, "ia2p_clip_create", [](ia2p_clip* c) {
+    if (c->cfg.layer_norm_eps <= 0.f) c->cfg.layer_norm_eps = 1e-5f;
+    return clip_plan(c);
+  });
 }
 void ia2p_clip_destroy(ia2p_clip* c) { delete c; }
-const char* ia2p_clip_last_error(ia2p_clip* c) { return c ? c->err.c_str() : g_err.c_str(); }
-size_t ia2p_clip_arena_bytes(ia2p_clip* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
+const char* ia2p_clip_last_error(ia2p_clip* c) { return rc_last_error(c); }
+size_t ia2p_clip_arena_bytes(ia2p_clip* c) { return rc_arena_bytes(c); }
 ia2p_status ia2p_clip_bind_arena(ia2p_clip* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
 ia2p_status ia2p_clip_load_tensor(ia2p_clip* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
   return rc_load_tensor(c, key, src, shape, ndim, stream);
@@ -135,12 +122,8 @@ static ia2p_status clip_encode_impl(ia2p_clip* c, void* stream, const int32_t* i
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "clip_encode before weights were finalized");
   ia2p_status st = clip_check(c, B, T);
   if (st != IA2P_OK) return st;
-  if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
-  if (c->fold_dirty) {            // a tensor was reloaded after finalize: re-derive the folded LayerNorm copies, stream-ordered
-    st = clip_fold(c, (hipStream_t)stream, false);
-    if (st != IA2P_OK) return st;
-  }
-  st = pass_enter(c, stream, ws, ws_bytes);
+  st = pass_ready(c, [&] { return clip_fold(c, (hipStream_t)stream, false); });
+  if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
   if (st != IA2P_OK) return st;
   const int key = (last || pooled) ? 1 : 2;
   pass_record(c, key, [&] { return clip_run(c, nullptr, nullptr, B, T, nullptr, key == 1 ? (half_t*)1 : nullptr, nullptr); });

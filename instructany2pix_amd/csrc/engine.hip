@@ -851,23 +851,17 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
 extern "C" {
 
 ia2p_status ia2p_create(const ia2p_unet_config* cfg, ia2p_ctx** out) {
-  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_create: null argument");
-  ia2p_ctx* c = new ia2p_ctx();
-  c->cfg = *cfg;
-  ia2p_status st = build_plan(c);
-  if (st != IA2P_OK) { g_err = c->err; delete c; *out = nullptr; return st; }
-  c->failed = false;
-  c->groups = cfg->norm_num_groups;
-  ia2p_sk_counters_invalidate();      // a fresh context never trusts tickets an earlier (possibly failed) one left behind
-  *out = c;
-  return IA2P_OK;
+  return rc_create(cfg, out, "ia2p_create", [](ia2p_ctx* c) {
+    const ia2p_status st = build_plan(c);
+    if (st != IA2P_OK) return st;
+    c->groups = c->cfg.norm_num_groups;
+    ia2p_sk_counters_invalidate();      // a fresh context never trusts tickets an earlier (possibly failed) one left behind
+    return IA2P_OK;
+  });
 }
-
 void ia2p_destroy(ia2p_ctx* c) { delete c; }
-
-const char* ia2p_last_error(ia2p_ctx* c) { return c ? c->err.c_str() : g_err.c_str(); }
-
-size_t ia2p_arena_bytes(ia2p_ctx* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
+const char* ia2p_last_error(ia2p_ctx* c) { return rc_last_error(c); }
+size_t ia2p_arena_bytes(ia2p_ctx* c) { return rc_arena_bytes(c); }
 
 ia2p_status ia2p_bind_arena(ia2p_ctx* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
 ia2p_status ia2p_load_tensor(ia2p_ctx* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
@@ -1019,12 +1013,10 @@ static ia2p_status unet_forward_impl(ia2p_ctx* c, void* stream, const void* samp
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "unet_forward before weights were finalized");
   ia2p_status st = check_fwd_shape(c, B, h, w, L);
   if (st != IA2P_OK) return st;
-  if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
-  if (c->fold_dirty) {            // a tensor was reloaded after finalize (hot swap, strict=False load): re-derive the folds on this stream and wait
-    st = fold_all(c, (hipStream_t)stream, true);       // (rare; the wait keeps a following forward on ANOTHER stream from reading half-written folds)
-    if (st != IA2P_OK) return st;
-  }
-  st = pass_enter(c, stream, ws, ws_bytes);
+  // a tensor was reloaded after finalize (hot swap, strict=False load): re-derive the folds on this stream and wait (rare; the wait keeps a following forward on
+  // ANOTHER stream from reading half-written folds)
+  st = pass_ready(c, [&] { return fold_all(c, (hipStream_t)stream, true); });
+  if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
   if (st != IA2P_OK) return st;
   // the weight launch sequence: a dry pass of the same code path
   pass_record(c, (c->ip_enabled ? 1 + c->ip_tokens : 0) + (kv ? 1000 : 0),
@@ -1062,12 +1054,8 @@ ia2p_status ia2p_project_context(ia2p_ctx* c, void* stream, const void* context,
   const size_t need = ia2p_context_kv_bytes(c, B, L);
   if (!need) return fail(c, IA2P_ERR_SHAPE, "project_context: B=%d L=%d", B, L);
   if (kv_bytes < need) return fail(c, IA2P_ERR_NOMEM, "project_context: kv buffer holds %zu bytes, needs %zu", kv_bytes, need);
-  if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
-  if (c->fold_dirty) {
-    const ia2p_status fs = fold_all(c, (hipStream_t)stream, true);
-    if (fs != IA2P_OK) return fs;
-  }
-  const ia2p_status st = pass_enter(c, stream, ws, ws_bytes);
+  ia2p_status st = pass_ready(c, [&] { return fold_all(c, (hipStream_t)stream, true); });
+  if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
   if (st != IA2P_OK) return st;
   const bool pf = c->prefetch;
   c->prefetch = false;               // a stand-alone call: no "next launch" to stream weights for

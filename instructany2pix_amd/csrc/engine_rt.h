@@ -333,8 +333,39 @@ void op_conv3(RunCtx* c, const half_t* X, int B, int Hs, int Ws, int Cin, const 
 void op_gn(RunCtx* c, const half_t* x, half_t* y, size_t g, size_t b, int B, int HW, int C, float eps, int silu, float* partial, const half_t* x2 = nullptr, int Ca = 0);
 void op_ln(RunCtx* c, const half_t* x, half_t* y, size_t g, size_t b, int M, int C);
 
-// ---- weight arena plumbing shared by the three contexts
+// ---- handle lifecycle and weight arena plumbing shared by the six contexts
+// ia2p_*_create: null check, a new context holding a copy of cfg, init(c) (defaults the config leaves open, then the plan); a refusal's message moves to the thread's
+// error string (the context is gone) and *out is null
+template <class Ctx, class Cfg, class Init> ia2p_status rc_create(const Cfg* cfg, Ctx** out, const char* name, Init&& init) {
+  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "%s: null argument", name);
+  Ctx* c = new Ctx();
+  c->cfg = *cfg;
+  const ia2p_status st = init(c);
+  if (st != IA2P_OK) { g_err = c->err; delete c; *out = nullptr; return st; }
+  c->failed = false;
+  *out = c;
+  return IA2P_OK;
+}
+inline const char* rc_last_error(const RunCtx* c) { return c ? c->err.c_str() : g_err.c_str(); }
+inline size_t rc_arena_bytes(const RunCtx* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
+// arena layout of a plan: element offsets, every tensor on a multiple of 128 elements. take: room the executor derives at load or finalize; par: a parameter loaded as
+// it is; reg: a parameter inside room taken before (the q / k / v rows of a stacked projection)
+struct ArenaPlan {
+  RunCtx* c;
+  size_t cur = 0;
+  size_t take(size_t elems) { const size_t o = cur; cur += (elems + 127) & ~(size_t)127; return o; }
+  void reg(const std::string& key, size_t off, size_t elems) { c->params[key] = Param{off, elems, PK_COPY, 0, 0, false, false}; }
+  size_t par(const std::string& key, size_t elems) { const size_t o = take(elems); reg(key, o, elems); return o; }
+};
 ia2p_status rc_bind_arena(RunCtx* c, void* dev, size_t bytes);
 ia2p_status rc_load_tensor(RunCtx* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream);
+// a [rows, Kraw] tensor into arena rows of Kpad elements at `off`, the padding zero (a patch stem: its GEMM takes K in multiples of 64)
+ia2p_status rc_load_padded_rows(RunCtx* c, const char* key, size_t off, int rows, int Kraw, int Kpad, const void* src, const int64_t* shape, int ndim, void* stream);
 ia2p_status rc_finalize(RunCtx* c, const char* what);
 ia2p_status rc_adopt(RunCtx* c, bool with_optional = true);
+// what an entry point still needs once its own arguments passed, before pass_enter: the device's zero page, and -- when a tensor was reloaded after finalize
+// (fold_dirty) -- the executor's derived data again: refold() re-derives it on the pass's stream
+template <class Refold> ia2p_status pass_ready(RunCtx* c, Refold&& refold) {
+  if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
+  return c->fold_dirty ? refold() : IA2P_OK;
+}

@@ -304,7 +304,7 @@ void op_ln(RunCtx* c, const half_t* x, half_t* y, size_t g, size_t b, int M, int
   CHECK_LAUNCH(c, ia2p_launch_layernorm(x, C, y, C, W_(c, g), W_(c, b), M, C, 1e-5f, c->stream), "layernorm");
 }
 
-// ---- weight arena plumbing shared by the UNet, VAE and CLIP contexts
+// ---- weight arena plumbing shared by the six contexts
 ia2p_status rc_bind_arena(RunCtx* c, void* dev, size_t bytes) {
   if (!c || !dev) return fail(c, IA2P_ERR_INVALID, "bind_arena: null argument");
   if (bytes < c->arena_elems * sizeof(half_t)) return fail(c, IA2P_ERR_NOMEM, "arena needs %zu bytes, got %zu", c->arena_elems * sizeof(half_t), bytes);
@@ -336,6 +336,17 @@ ia2p_status rc_load_tensor(RunCtx* c, const char* key, const void* src, const in
   if (e != hipSuccess) return fail_hip(c, e, (std::string("load '") + key + "'").c_str());
   p.loaded = true;
   c->fold_dirty = true;     // data derived from the parameters at finalize (LayerNorm folds) is stale until the owner re-derives it
+  return IA2P_OK;
+}
+ia2p_status rc_load_padded_rows(RunCtx* c, const char* key, size_t off, int rows, int Kraw, int Kpad, const void* src, const int64_t* shape, int ndim, void* stream) {
+  size_t n = 1;
+  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+  if (n != (size_t)rows * Kraw) return fail(c, IA2P_ERR_SHAPE, "parameter '%s': expected %zu elements, got %zu", key, (size_t)rows * Kraw, n);
+  half_t* dst = c->arena + off;
+  hipError_t e = hipMemsetAsync(dst, 0, (size_t)rows * Kpad * sizeof(half_t), (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(dst, Kpad * sizeof(half_t), src, Kraw * sizeof(half_t), Kraw * sizeof(half_t), rows, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (e != hipSuccess) return fail_hip(c, e, (std::string("load '") + key + "'").c_str());
+  c->params[key].loaded = true;
   return IA2P_OK;
 }
 ia2p_status rc_finalize(RunCtx* c, const char* what) {

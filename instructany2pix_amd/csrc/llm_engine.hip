@@ -44,37 +44,34 @@ static ia2p_status llm_plan(ia2p_llm* c) {
   const bool q4 = c->wbits == 4;
   if (q4 && (H > Q4_MAX_K || I > Q4_MAX_K)) return fail(c, IA2P_ERR_SHAPE, "llm: 4-bit weights serve rows of up to %d (hidden %d, intermediate %d)", Q4_MAX_K, H, I);
   c->params.clear(); c->layers.clear(); c->q4_absmax.clear();
-  size_t cur = 0;
-  auto take = [&](size_t e) { size_t o = cur; cur += (e + 127) & ~(size_t)127; return o; };
-  auto reg = [&](const std::string& k, size_t off, size_t n) { c->params[k] = Param{off, n, PK_COPY, 0, 0, false, false}; };
-  auto par = [&](const std::string& k, size_t n) { size_t o = take(n); reg(k, o, n); return o; };
-  c->tok = par("model.embed_tokens.weight", (size_t)g.vocab_size * H);
+  ArenaPlan A{c};
+  c->tok = A.par("model.embed_tokens.weight", (size_t)g.vocab_size * H);
   for (int i = 0; i < g.num_layers; ++i) {
     const std::string p = "model.layers." + std::to_string(i) + ".";
     LLayer l;
-    l.ln1 = par(p + "input_layernorm.weight", H);
+    l.ln1 = A.par(p + "input_layernorm.weight", H);
     // a projection of `parts` equal [rows, K] tensors stacked as rows (blocks never cross a row, so in 4 bits the codes and the absmax rows stack the same way)
     auto proj = [&](size_t* w, size_t* am, const std::vector<std::string>& keys, size_t rows, size_t K) {
       const size_t nk = rows * K, parts = keys.size();
-      *w = take(q4 ? q4_code_elems(parts * nk) : parts * nk);
-      *am = q4 ? take(q4_absmax_elems(parts * nk)) : 0;
+      *w = A.take(q4 ? q4_code_elems(parts * nk) : parts * nk);
+      *am = q4 ? A.take(q4_absmax_elems(parts * nk)) : 0;
       for (size_t j = 0; j < parts; ++j) {
-        if (!q4) { reg(p + keys[j], *w + j * nk, nk); continue; }
+        if (!q4) { A.reg(p + keys[j], *w + j * nk, nk); continue; }
         c->params[p + keys[j]] = Param{*w + j * q4_code_elems(nk), nk, PK_Q4, (int)rows, (int)K, false, false};
         c->q4_absmax[p + keys[j]] = *am + j * q4_absmax_elems(nk);
       }
     };
     proj(&l.wqkv, &l.aqkv, {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight"}, H, H);     // q | k | v rows stacked: one projection
     proj(&l.wo, &l.ao, {"self_attn.o_proj.weight"}, H, H);
-    l.ln2 = par(p + "post_attention_layernorm.weight", H);
+    l.ln2 = A.par(p + "post_attention_layernorm.weight", H);
     proj(&l.wgu, &l.agu, {"mlp.gate_proj.weight", "mlp.up_proj.weight"}, I, H);                                              // gate | up rows stacked
     proj(&l.wd, &l.ad, {"mlp.down_proj.weight"}, H, I);
     c->layers.push_back(l);
   }
-  c->normf = par("model.norm.weight", H);
-  c->head = par("lm_head.weight", (size_t)g.vocab_size * H);
-  c->invf = take(128);                                      // 64 fp32 rotary frequencies (derived at finalize)
-  c->arena_elems = cur;
+  c->normf = A.par("model.norm.weight", H);
+  c->head = A.par("lm_head.weight", (size_t)g.vocab_size * H);
+  c->invf = A.take(128);                                      // 64 fp32 rotary frequencies (derived at finalize)
+  c->arena_elems = A.cur;
   return IA2P_OK;
 }
 
@@ -232,20 +229,15 @@ static void llm_rope_inv_freq(float theta, float* f) {
 extern "C" {
 
 ia2p_status ia2p_llm_create(const ia2p_llm_config* cfg, ia2p_llm** out) {
-  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_llm_create: null argument");
-  ia2p_llm* c = new ia2p_llm();
-  c->cfg = *cfg;
-  if (c->cfg.rms_norm_eps <= 0.f) c->cfg.rms_norm_eps = 1e-5f;
-  if (c->cfg.rope_theta <= 0.f) c->cfg.rope_theta = 10000.f;
-  ia2p_status st = llm_plan(c);
-  if (st != IA2P_OK) { g_err = c->err; delete c; *out = nullptr; return st; }
-  c->failed = false;
-  *out = c;
-  return IA2P_OK;
+  return rc_create(cfg, out, "ia2p_llm_create", [](ia2p_llm* c) {
+    if (c->cfg.rms_norm_eps <= 0.f) c->cfg.rms_norm_eps = 1e-5f;
+    if (c->cfg.rope_theta <= 0.f) c->cfg.rope_theta = 10000.f;
+    return llm_plan(c);
+  });
 }
 void ia2p_llm_destroy(ia2p_llm* c) { delete c; }
-const char* ia2p_llm_last_error(ia2p_llm* c) { return c ? c->err.c_str() : g_err.c_str(); }
-size_t ia2p_llm_arena_bytes(ia2p_llm* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
+const char* ia2p_llm_last_error(ia2p_llm* c) { return rc_last_error(c); }
+size_t ia2p_llm_arena_bytes(ia2p_llm* c) { return rc_arena_bytes(c); }
 ia2p_status ia2p_llm_bind_arena(ia2p_llm* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
 ia2p_status ia2p_llm_load_tensor(ia2p_llm* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
   if (!c || !key || !src || !shape || !c->arena) return rc_load_tensor(c, key, src, shape, ndim, stream);      // (its refusals)

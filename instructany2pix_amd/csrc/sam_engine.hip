@@ -58,13 +58,10 @@ static ia2p_status sam_plan(ia2p_sam* c) {
       return fail(c, IA2P_ERR_SHAPE, "sam: the decoder's attention needs head dim 16 or 32 (hidden %d / %d over %d heads)", C, ds, g.dec_heads);
   }
   c->Kraw = 3 * g.patch_size * g.patch_size; c->Kpad = (c->Kraw + 63) & ~63;
-  size_t cur = 0;
-  auto take = [&](size_t e) { size_t o = cur; cur += (e + 127) & ~(size_t)127; return o; };
-  auto reg = [&](const std::string& k, size_t off, size_t n) { c->params[k] = Param{off, n, PK_COPY, 0, 0, false, false}; };
-  auto par = [&](const std::string& k, size_t n) { size_t o = take(n); reg(k, o, n); return o; };
-  c->stem = take((size_t)H * c->Kpad); reg("patch_embed.weight", c->stem, (size_t)H * c->Kraw);
-  c->stemb = par("patch_embed.bias", H);
-  c->pos = par("pos_embed", (size_t)c->P * H);
+  ArenaPlan A{c};
+  c->stem = A.take((size_t)H * c->Kpad); A.reg("patch_embed.weight", c->stem, (size_t)H * c->Kraw);
+  c->stemb = A.par("patch_embed.bias", H);
+  c->pos = A.par("pos_embed", (size_t)c->P * H);
   c->is_global.assign(g.num_layers, 0);
   for (int i = 0; i < g.num_global; ++i) {
     if (g.global_attn_indexes[i] < 0 || g.global_attn_indexes[i] >= g.num_layers) return fail(c, IA2P_ERR_SHAPE, "sam: global-attention block index %d outside 0..%d", g.global_attn_indexes[i], g.num_layers - 1);
@@ -74,68 +71,63 @@ static ia2p_status sam_plan(ia2p_sam* c) {
     const std::string p = "blocks." + std::to_string(i) + ".";
     const int S = c->is_global[i] ? c->g : g.window_size;
     CLayer l;
-    l.ln1g = par(p + "norm1.weight", H); l.ln1b = par(p + "norm1.bias", H);
-    l.wqkv = par(p + "attn.qkv.weight", (size_t)3 * H * H); l.bqkv = par(p + "attn.qkv.bias", (size_t)3 * H);
-    l.wo = par(p + "attn.proj.weight", (size_t)H * H); l.bo = par(p + "attn.proj.bias", H);
-    c->rph.push_back(par(p + "attn.rel_pos_h", (size_t)(2 * S - 1) * c->D)); c->rpw.push_back(par(p + "attn.rel_pos_w", (size_t)(2 * S - 1) * c->D));
-    l.ln2g = par(p + "norm2.weight", H); l.ln2b = par(p + "norm2.bias", H);
-    l.w1 = par(p + "mlp.lin1.weight", (size_t)I * H); l.b1 = par(p + "mlp.lin1.bias", I);
-    l.w2 = par(p + "mlp.lin2.weight", (size_t)H * I); l.b2 = par(p + "mlp.lin2.bias", H);
-    l.fqkv = take((size_t)3 * H * H); l.cs1 = take((size_t)2 * 3 * H); l.lb1 = take((size_t)2 * 3 * H);
-    l.f1 = take((size_t)I * H); l.cs2 = take((size_t)2 * I); l.lb2 = take((size_t)2 * I);
+    l.ln1g = A.par(p + "norm1.weight", H); l.ln1b = A.par(p + "norm1.bias", H);
+    l.wqkv = A.par(p + "attn.qkv.weight", (size_t)3 * H * H); l.bqkv = A.par(p + "attn.qkv.bias", (size_t)3 * H);
+    l.wo = A.par(p + "attn.proj.weight", (size_t)H * H); l.bo = A.par(p + "attn.proj.bias", H);
+    c->rph.push_back(A.par(p + "attn.rel_pos_h", (size_t)(2 * S - 1) * c->D)); c->rpw.push_back(A.par(p + "attn.rel_pos_w", (size_t)(2 * S - 1) * c->D));
+    l.ln2g = A.par(p + "norm2.weight", H); l.ln2b = A.par(p + "norm2.bias", H);
+    l.w1 = A.par(p + "mlp.lin1.weight", (size_t)I * H); l.b1 = A.par(p + "mlp.lin1.bias", I);
+    l.w2 = A.par(p + "mlp.lin2.weight", (size_t)H * I); l.b2 = A.par(p + "mlp.lin2.bias", H);
+    xf_take_folds(A, l, H, I);
     c->layers.push_back(l);
   }
-  c->nc1 = par("neck.conv1.weight", (size_t)C * H);
-  c->n1g = par("neck.norm1.weight", C); c->n1b = par("neck.norm1.bias", C);
-  c->nc2 = take((size_t)C * 9 * C); c->params["neck.conv2.weight"] = Param{c->nc2, (size_t)C * 9 * C, PK_CONV, C, C, false, false};
-  c->n2g = par("neck.norm2.weight", C); c->n2b = par("neck.norm2.bias", C);
+  c->nc1 = A.par("neck.conv1.weight", (size_t)C * H);
+  c->n1g = A.par("neck.norm1.weight", C); c->n1b = A.par("neck.norm1.bias", C);
+  c->nc2 = A.take((size_t)C * 9 * C); c->params["neck.conv2.weight"] = Param{c->nc2, (size_t)C * 9 * C, PK_CONV, C, C, false, false};
+  c->n2g = A.par("neck.norm2.weight", C); c->n2b = A.par("neck.norm2.bias", C);
   // prompt encoder
-  c->gauss = par("prompt.pe_gaussian", (size_t)2 * (C / 2));
-  c->pe2 = par("prompt.point_embed.2", C); c->pe3 = par("prompt.point_embed.3", C);
-  c->nomask = par("prompt.no_mask_embed", C);
-  c->densepe = take((size_t)c->P * C);
+  c->gauss = A.par("prompt.pe_gaussian", (size_t)2 * (C / 2));
+  c->pe2 = A.par("prompt.point_embed.2", C); c->pe3 = A.par("prompt.point_embed.3", C);
+  c->nomask = A.par("prompt.no_mask_embed", C);
+  c->densepe = A.take((size_t)c->P * C);
   // mask decoder
-  c->ioutok = par("decoder.iou_token", C); c->masktok = par("decoder.mask_tokens", (size_t)SAM_MASK_TOKENS * C);
+  c->ioutok = A.par("decoder.iou_token", C); c->masktok = A.par("decoder.mask_tokens", (size_t)SAM_MASK_TOKENS * C);
   auto attn = [&](const std::string& p, int ds) {
     SamAttn a; a.Ci = C / ds;
-    a.wq = par(p + "q.weight", (size_t)a.Ci * C); a.bq = par(p + "q.bias", a.Ci);
-    a.wk = par(p + "k.weight", (size_t)a.Ci * C); a.bk = par(p + "k.bias", a.Ci);
-    a.wv = par(p + "v.weight", (size_t)a.Ci * C); a.bv = par(p + "v.bias", a.Ci);
-    a.wo = par(p + "out.weight", (size_t)C * a.Ci); a.bo = par(p + "out.bias", C);
+    a.wq = A.par(p + "q.weight", (size_t)a.Ci * C); a.bq = A.par(p + "q.bias", a.Ci);
+    a.wk = A.par(p + "k.weight", (size_t)a.Ci * C); a.bk = A.par(p + "k.bias", a.Ci);
+    a.wv = A.par(p + "v.weight", (size_t)a.Ci * C); a.bv = A.par(p + "v.bias", a.Ci);
+    a.wo = A.par(p + "out.weight", (size_t)C * a.Ci); a.bo = A.par(p + "out.bias", C);
     return a;
   };
   for (int i = 0; i < g.dec_layers; ++i) {
     const std::string p = "decoder.layers." + std::to_string(i) + ".";
     SamDecLayer l;
     l.self = attn(p + "self_attn.", 1); l.t2i = attn(p + "t2i.", g.dec_downsample_rate); l.i2t = attn(p + "i2t.", g.dec_downsample_rate);
-    l.n1g = par(p + "norm1.weight", C); l.n1b = par(p + "norm1.bias", C); l.n2g = par(p + "norm2.weight", C); l.n2b = par(p + "norm2.bias", C);
-    l.n3g = par(p + "norm3.weight", C); l.n3b = par(p + "norm3.bias", C); l.n4g = par(p + "norm4.weight", C); l.n4b = par(p + "norm4.bias", C);
-    l.w1 = par(p + "mlp.lin1.weight", (size_t)g.dec_mlp_dim * C); l.b1 = par(p + "mlp.lin1.bias", g.dec_mlp_dim);
-    l.w2 = par(p + "mlp.lin2.weight", (size_t)C * g.dec_mlp_dim); l.b2 = par(p + "mlp.lin2.bias", C);
+    l.n1g = A.par(p + "norm1.weight", C); l.n1b = A.par(p + "norm1.bias", C); l.n2g = A.par(p + "norm2.weight", C); l.n2b = A.par(p + "norm2.bias", C);
+    l.n3g = A.par(p + "norm3.weight", C); l.n3b = A.par(p + "norm3.bias", C); l.n4g = A.par(p + "norm4.weight", C); l.n4b = A.par(p + "norm4.bias", C);
+    l.w1 = A.par(p + "mlp.lin1.weight", (size_t)g.dec_mlp_dim * C); l.b1 = A.par(p + "mlp.lin1.bias", g.dec_mlp_dim);
+    l.w2 = A.par(p + "mlp.lin2.weight", (size_t)C * g.dec_mlp_dim); l.b2 = A.par(p + "mlp.lin2.bias", C);
     c->dec.push_back(l);
   }
   c->fin = attn("decoder.final_attn.", g.dec_downsample_rate);
-  c->nfg = par("decoder.norm_final.weight", C); c->nfb = par("decoder.norm_final.bias", C);
+  c->nfg = A.par("decoder.norm_final.weight", C); c->nfb = A.par("decoder.norm_final.bias", C);
   // the two ConvTranspose2d(k = 2, s = 2) as GEMMs: rows (ky, kx, co) of [4 Co, Ci], the bias four times (the Python loader permutes the checkpoint's [Ci, Co, 2, 2])
-  c->up1w = par("decoder.upscale1.weight", (size_t)C * C); c->up1b = par("decoder.upscale1.bias", C);
-  c->upng = par("decoder.upscale_norm.weight", C / 4); c->upnb = par("decoder.upscale_norm.bias", C / 4);
-  c->up2w = par("decoder.upscale2.weight", (size_t)(C / 2) * (C / 4)); c->up2b = par("decoder.upscale2.bias", C / 2);
+  c->up1w = A.par("decoder.upscale1.weight", (size_t)C * C); c->up1b = A.par("decoder.upscale1.bias", C);
+  c->upng = A.par("decoder.upscale_norm.weight", C / 4); c->upnb = A.par("decoder.upscale_norm.bias", C / 4);
+  c->up2w = A.par("decoder.upscale2.weight", (size_t)(C / 2) * (C / 4)); c->up2b = A.par("decoder.upscale2.bias", C / 2);
   for (int k = 0; k < 3; ++k) {
     const int no = k == 2 ? C / 8 : C;
-    c->hy[k][0] = par("decoder.hyper0." + std::to_string(k) + ".weight", (size_t)no * C); c->hy[k][1] = par("decoder.hyper0." + std::to_string(k) + ".bias", no);
+    c->hy[k][0] = A.par("decoder.hyper0." + std::to_string(k) + ".weight", (size_t)no * C); c->hy[k][1] = A.par("decoder.hyper0." + std::to_string(k) + ".bias", no);
     const int ni = k == 2 ? SAM_MASK_TOKENS : C;
-    c->io[k][0] = par("decoder.iou_head." + std::to_string(k) + ".weight", (size_t)ni * C); c->io[k][1] = par("decoder.iou_head." + std::to_string(k) + ".bias", ni);
+    c->io[k][0] = A.par("decoder.iou_head." + std::to_string(k) + ".weight", (size_t)ni * C); c->io[k][1] = A.par("decoder.iou_head." + std::to_string(k) + ".bias", ni);
   }
-  c->arena_elems = cur;
+  c->arena_elems = A.cur;
   return IA2P_OK;
 }
 
 static ia2p_status sam_fold(ia2p_sam* c, hipStream_t stream = nullptr, bool sync = true) {
-  hipError_t e = xf_fold(c, c->layers, c->cfg.hidden_size, c->cfg.mlp_dim, stream);
-  if (e == hipSuccess && sync) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) return fail_hip(c, e, "sam LayerNorm folding");
-  c->fold_dirty = false;
-  return IA2P_OK;
+  return xf_refold(c, c->layers, c->cfg.hidden_size, c->cfg.mlp_dim, stream, sync, "sam");
 }
 
 // sin / cos random-Fourier features of a point in [0, 1]^2 (SamPositionalEmbedding): [sin(2 pi (2 p - 1) G) | cos(...)], fp32
@@ -283,33 +275,18 @@ static ia2p_status sam_decode_run(ia2p_sam* c, const half_t* emb, const half_t* 
 extern "C" {
 
 ia2p_status ia2p_sam_create(const ia2p_sam_config* cfg, ia2p_sam** out) {
-  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_sam_create: null argument");
-  ia2p_sam* c = new ia2p_sam();
-  c->cfg = *cfg;
-  if (c->cfg.layer_norm_eps <= 0.f) c->cfg.layer_norm_eps = 1e-6f;
-  ia2p_status st = sam_plan(c);
-  if (st != IA2P_OK) { g_err = c->err; delete c; *out = nullptr; return st; }
-  c->failed = false;
-  *out = c;
-  return IA2P_OK;
+  return rc_create(cfg, out, "ia2p_sam_create", [](ia2p_sam* c) {
+    if (c->cfg.layer_norm_eps <= 0.f) c->cfg.layer_norm_eps = 1e-6f;
+    return sam_plan(c);
+  });
 }
 void ia2p_sam_destroy(ia2p_sam* c) { delete c; }
-const char* ia2p_sam_last_error(ia2p_sam* c) { return c ? c->err.c_str() : g_err.c_str(); }
-size_t ia2p_sam_arena_bytes(ia2p_sam* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
+const char* ia2p_sam_last_error(ia2p_sam* c) { return rc_last_error(c); }
+size_t ia2p_sam_arena_bytes(ia2p_sam* c) { return rc_arena_bytes(c); }
 ia2p_status ia2p_sam_bind_arena(ia2p_sam* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
 ia2p_status ia2p_sam_load_tensor(ia2p_sam* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
-  if (c && key && src && shape && c->arena && c->Kpad != c->Kraw && !strcmp(key, "patch_embed.weight")) {      // [hidden, 3 * p * p] rows into rows of Kpad, the rest zero
-    const int H = c->cfg.hidden_size;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-    if (n != (size_t)H * c->Kraw) return fail(c, IA2P_ERR_SHAPE, "parameter '%s': expected %zu elements, got %zu", key, (size_t)H * c->Kraw, n);
-    half_t* dst = c->arena + c->stem;
-    hipError_t e = hipMemsetAsync(dst, 0, (size_t)H * c->Kpad * sizeof(half_t), (hipStream_t)stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(dst, c->Kpad * sizeof(half_t), src, c->Kraw * sizeof(half_t), c->Kraw * sizeof(half_t), H, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(c, e, "load 'patch_embed.weight'");
-    c->params[key].loaded = true;
-    return IA2P_OK;
-  }
+  if (c && key && src && shape && c->arena && c->Kpad != c->Kraw && !strcmp(key, "patch_embed.weight"))      // [hidden, 3 * p * p] rows into rows of Kpad, the rest zero
+    return rc_load_padded_rows(c, key, c->stem, c->cfg.hidden_size, c->Kraw, c->Kpad, src, shape, ndim, stream);
   return rc_load_tensor(c, key, src, shape, ndim, stream);
 }
 ia2p_status ia2p_sam_finalize_weights(ia2p_sam* c) {
@@ -332,14 +309,11 @@ size_t ia2p_sam_workspace_bytes(ia2p_sam* c, int B, int n_boxes) {
 }
 static ia2p_status sam_ready(ia2p_sam* c, void* stream, const char* what) {
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "%s before weights were finalized", what);
-  if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
-  if (c->fold_dirty) {            // a tensor was reloaded after finalize: re-derive the folded LayerNorm copies and the host tables
+  return pass_ready(c, [&] {      // a tensor was reloaded after finalize: the host tables again too (they read the arena: the reload's copies must have landed)
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail(c, IA2P_ERR_HIP, "%s: stream", what);
-    ia2p_status st = sam_host_tables(c);
-    if (st == IA2P_OK) st = sam_fold(c, (hipStream_t)stream, false);
-    if (st != IA2P_OK) return st;
-  }
-  return IA2P_OK;
+    const ia2p_status st = sam_host_tables(c);
+    return st == IA2P_OK ? sam_fold(c, (hipStream_t)stream, false) : st;
+  });
 }
 ia2p_status ia2p_sam_encode_image(ia2p_sam* c, void* stream, const void* pixels, int B, void* embeddings, void* ws, size_t ws_bytes) {
   if (!c || !pixels || !embeddings || !ws) return fail(c, IA2P_ERR_INVALID, "sam_encode_image: null argument");

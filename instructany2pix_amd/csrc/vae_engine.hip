@@ -267,24 +267,17 @@ static ia2p_status vae_run_encode(ia2p_vae* c, const half_t* img, half_t* moment
 extern "C" {
 
 ia2p_status ia2p_vae_create(const ia2p_vae_config* cfg, ia2p_vae** out) {
-  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_vae_create: null argument");
-  ia2p_vae* c = new ia2p_vae();
-  c->cfg = *cfg;
-  c->groups = cfg->norm_num_groups;
-  c->ss = cfg->stream_scale > 0.f ? cfg->stream_scale : 1.f;
-  {
+  return rc_create(cfg, out, "ia2p_vae_create", [](ia2p_vae* c) {
+    c->groups = c->cfg.norm_num_groups;
+    c->ss = c->cfg.stream_scale > 0.f ? c->cfg.stream_scale : 1.f;
     int ex = 0;
-    if (std::frexp(c->ss, &ex) != 0.5f || c->ss > 1.f || c->ss < 1.0f / 65536.f) { delete c; *out = nullptr; return fail(nullptr, IA2P_ERR_INVALID, "stream_scale must be a power of two in [2^-16, 1]"); }
-  }
-  ia2p_status st = vae_plan(c);
-  if (st != IA2P_OK) { g_err = c->err; delete c; *out = nullptr; return st; }
-  c->failed = false;
-  *out = c;
-  return IA2P_OK;
+    if (std::frexp(c->ss, &ex) != 0.5f || c->ss > 1.f || c->ss < 1.0f / 65536.f) return fail(c, IA2P_ERR_INVALID, "stream_scale must be a power of two in [2^-16, 1]");
+    return vae_plan(c);
+  });
 }
 void ia2p_vae_destroy(ia2p_vae* c) { delete c; }
-const char* ia2p_vae_last_error(ia2p_vae* c) { return c ? c->err.c_str() : g_err.c_str(); }
-size_t ia2p_vae_arena_bytes(ia2p_vae* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
+const char* ia2p_vae_last_error(ia2p_vae* c) { return rc_last_error(c); }
+size_t ia2p_vae_arena_bytes(ia2p_vae* c) { return rc_arena_bytes(c); }
 ia2p_status ia2p_vae_bind_arena(ia2p_vae* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
 ia2p_status ia2p_vae_load_tensor(ia2p_vae* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
   return rc_load_tensor(c, key, src, shape, ndim, stream);

@@ -28,42 +28,34 @@ static ia2p_status vit_plan(ia2p_vit* c) {
   if (c->T + (g.bias_kv ? 1 : 0) > ia2p_full_attention_max_keys())
     return fail(c, IA2P_ERR_SHAPE, "vit: %d x %d patches + class token%s exceed the %d keys the attention launch holds", c->gh, c->gw, g.bias_kv ? " + bias row" : "", ia2p_full_attention_max_keys());
   c->Kraw = g.in_channels * g.patch_size * g.patch_size; c->Kpad = (c->Kraw + 63) & ~63;
-  size_t cur = 0;
-  auto take = [&](size_t e) { size_t o = cur; cur += (e + 127) & ~(size_t)127; return o; };
-  auto reg = [&](const std::string& k, size_t off, size_t n) { c->params[k] = Param{off, n, PK_COPY, 0, 0, false, false}; };
-  auto par = [&](const std::string& k, size_t n) { size_t o = take(n); reg(k, o, n); return o; };
-  c->stem = take((size_t)H * c->Kpad); reg("stem.weight", c->stem, (size_t)H * c->Kraw);      // arena rows padded to Kpad with zeros (ia2p_vit_load_tensor)
+  ArenaPlan A{c};
+  c->stem = A.take((size_t)H * c->Kpad); A.reg("stem.weight", c->stem, (size_t)H * c->Kraw);      // arena rows padded to Kpad with zeros (ia2p_vit_load_tensor)
   c->sng = c->snb = c->plg = c->plb = 0;
-  if (g.stem_ln) { c->sng = par("stem.norm.weight", H); c->snb = par("stem.norm.bias", H); }
-  c->cls = par("cls_token", H);
-  c->pos = par("pos_embed", (size_t)c->T * H);
-  if (g.pre_ln) { c->plg = par("pre_ln.weight", H); c->plb = par("pre_ln.bias", H); }
+  if (g.stem_ln) { c->sng = A.par("stem.norm.weight", H); c->snb = A.par("stem.norm.bias", H); }
+  c->cls = A.par("cls_token", H);
+  c->pos = A.par("pos_embed", (size_t)c->T * H);
+  if (g.pre_ln) { c->plg = A.par("pre_ln.weight", H); c->plb = A.par("pre_ln.bias", H); }
   for (int i = 0; i < g.num_layers; ++i) {
     const std::string p = "blocks." + std::to_string(i) + ".";
     CLayer l;
-    l.ln1g = par(p + "norm_1.weight", H); l.ln1b = par(p + "norm_1.bias", H);
-    l.wqkv = par(p + "attn.in_proj_weight", (size_t)3 * H * H); l.bqkv = par(p + "attn.in_proj_bias", (size_t)3 * H);
-    l.wo = par(p + "attn.out_proj.weight", (size_t)H * H); l.bo = par(p + "attn.out_proj.bias", H);
-    if (g.bias_kv) { c->bk.push_back(par(p + "attn.bias_k", H)); c->bv.push_back(par(p + "attn.bias_v", H)); }
-    l.ln2g = par(p + "norm_2.weight", H); l.ln2b = par(p + "norm_2.bias", H);
-    l.w1 = par(p + "mlp.fc1.weight", (size_t)I * H); l.b1 = par(p + "mlp.fc1.bias", I);
-    l.w2 = par(p + "mlp.fc2.weight", (size_t)H * I); l.b2 = par(p + "mlp.fc2.bias", H);
-    l.fqkv = take((size_t)3 * H * H); l.cs1 = take((size_t)2 * 3 * H); l.lb1 = take((size_t)2 * 3 * H);
-    l.f1 = take((size_t)I * H); l.cs2 = take((size_t)2 * I); l.lb2 = take((size_t)2 * I);
+    l.ln1g = A.par(p + "norm_1.weight", H); l.ln1b = A.par(p + "norm_1.bias", H);
+    l.wqkv = A.par(p + "attn.in_proj_weight", (size_t)3 * H * H); l.bqkv = A.par(p + "attn.in_proj_bias", (size_t)3 * H);
+    l.wo = A.par(p + "attn.out_proj.weight", (size_t)H * H); l.bo = A.par(p + "attn.out_proj.bias", H);
+    if (g.bias_kv) { c->bk.push_back(A.par(p + "attn.bias_k", H)); c->bv.push_back(A.par(p + "attn.bias_v", H)); }
+    l.ln2g = A.par(p + "norm_2.weight", H); l.ln2b = A.par(p + "norm_2.bias", H);
+    l.w1 = A.par(p + "mlp.fc1.weight", (size_t)I * H); l.b1 = A.par(p + "mlp.fc1.bias", I);
+    l.w2 = A.par(p + "mlp.fc2.weight", (size_t)H * I); l.b2 = A.par(p + "mlp.fc2.bias", H);
+    xf_take_folds(A, l, H, I);
     c->layers.push_back(l);
   }
-  c->hng = par("head.norm.weight", H); c->hnb = par("head.norm.bias", H);
-  c->wproj = par("head.proj.weight", (size_t)g.out_dim * H);
-  c->arena_elems = cur;
+  c->hng = A.par("head.norm.weight", H); c->hnb = A.par("head.norm.bias", H);
+  c->wproj = A.par("head.proj.weight", (size_t)g.out_dim * H);
+  c->arena_elems = A.cur;
   return IA2P_OK;
 }
 
 static ia2p_status vit_fold(ia2p_vit* c, hipStream_t stream = nullptr, bool sync = true) {
-  hipError_t e = xf_fold(c, c->layers, c->cfg.hidden_size, c->cfg.intermediate_size, stream);
-  if (e == hipSuccess && sync) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) return fail_hip(c, e, "vit LayerNorm folding");
-  c->fold_dirty = false;
-  return IA2P_OK;
+  return xf_refold(c, c->layers, c->cfg.hidden_size, c->cfg.intermediate_size, stream, sync, "vit");
 }
 
 static ia2p_status vit_run(ia2p_vit* c, const half_t* pixels, int B, float* out, half_t* last) {
@@ -100,34 +92,19 @@ static ia2p_status vit_run(ia2p_vit* c, const half_t* pixels, int B, float* out,
 }
 
 ia2p_status ia2p_vit_create(const ia2p_vit_config* cfg, ia2p_vit** out) {
-  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_vit_create: null argument");
-  ia2p_vit* c = new ia2p_vit();
-  c->cfg = *cfg;
-  if (c->cfg.layer_norm_eps <= 0.f) c->cfg.layer_norm_eps = 1e-6f;
-  ia2p_status st = vit_plan(c);
-  if (st != IA2P_OK) { g_err = c->err; delete c; *out = nullptr; return st; }
-  c->failed = false;
-  *out = c;
-  return IA2P_OK;
+  return rc_create(cfg, out, "ia2p_vit_create", [](ia2p_vit* c) {
+    if (c->cfg.layer_norm_eps <= 0.f) c->cfg.layer_norm_eps = 1e-6f;
+    return vit_plan(c);
+  });
 }
 void ia2p_vit_destroy(ia2p_vit* c) { delete c; }
-const char* ia2p_vit_last_error(ia2p_vit* c) { return c ? c->err.c_str() : g_err.c_str(); }
-size_t ia2p_vit_arena_bytes(ia2p_vit* c) { return c ? c->arena_elems * sizeof(half_t) : 0; }
+const char* ia2p_vit_last_error(ia2p_vit* c) { return rc_last_error(c); }
+size_t ia2p_vit_arena_bytes(ia2p_vit* c) { return rc_arena_bytes(c); }
 int ia2p_vit_tokens(ia2p_vit* c) { return c ? c->T : 0; }
 ia2p_status ia2p_vit_bind_arena(ia2p_vit* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
 ia2p_status ia2p_vit_load_tensor(ia2p_vit* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
-  if (c && key && src && shape && c->arena && c->Kpad != c->Kraw && !strcmp(key, "stem.weight")) {      // [hidden, C * p * p] rows into rows of Kpad, the rest zero
-    const int H = c->cfg.hidden_size;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-    if (n != (size_t)H * c->Kraw) return fail(c, IA2P_ERR_SHAPE, "parameter '%s': expected %zu elements, got %zu", key, (size_t)H * c->Kraw, n);
-    half_t* dst = c->arena + c->stem;
-    hipError_t e = hipMemsetAsync(dst, 0, (size_t)H * c->Kpad * sizeof(half_t), (hipStream_t)stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(dst, c->Kpad * sizeof(half_t), src, c->Kraw * sizeof(half_t), c->Kraw * sizeof(half_t), H, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(c, e, "load 'stem.weight'");
-    c->params[key].loaded = true;
-    return IA2P_OK;
-  }
+  if (c && key && src && shape && c->arena && c->Kpad != c->Kraw && !strcmp(key, "stem.weight"))      // [hidden, C * p * p] rows into rows of Kpad, the rest zero
+    return rc_load_padded_rows(c, key, c->stem, c->cfg.hidden_size, c->Kraw, c->Kpad, src, shape, ndim, stream);
   return rc_load_tensor(c, key, src, shape, ndim, stream);
 }
 ia2p_status ia2p_vit_finalize_weights(ia2p_vit* c) {
@@ -147,12 +124,8 @@ ia2p_status ia2p_vit_encode(ia2p_vit* c, void* stream, const void* pixels, int B
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "vit_encode before weights were finalized");
   ia2p_status st = vit_check(c, B);
   if (st != IA2P_OK) return st;
-  if (!zero_page()) return fail(c, IA2P_ERR_HIP, "cannot allocate zero page");
-  if (c->fold_dirty) {            // a tensor was reloaded after finalize: re-derive the folded LayerNorm copies, stream-ordered
-    st = vit_fold(c, (hipStream_t)stream, false);
-    if (st != IA2P_OK) return st;
-  }
-  st = pass_enter(c, stream, ws, ws_bytes);
+  st = pass_ready(c, [&] { return vit_fold(c, (hipStream_t)stream, false); });
+  if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
   if (st != IA2P_OK) return st;
   pass_record(c, 1, [&] { return vit_run(c, nullptr, B, nullptr, nullptr); });      // weight-prefetch plan: the contractions of a pass in launch order (the same for every B)
   return pass_leave(c, vit_run(c, (const half_t*)pixels, B, out, (half_t*)last_hidden));

@@ -4,11 +4,18 @@
 #pragma once
 #include "engine_rt.h"
 
-// arena offsets of a block: parameters as loaded (wqkv / bqkv: q, k, v rows stacked) and what xf_fold derives from them
+// arena offsets of a block: parameters as loaded (wqkv / bqkv: q, k, v rows stacked) and what xf_refold derives from them
 struct CLayer { size_t ln1g, ln1b, wqkv, bqkv, wo, bo, ln2g, ln2b, w1, b1, w2, b2, fqkv, cs1, lb1, f1, cs2, lb2; };
 
-// gamma-folded copies of the two LayerNorm-consuming weights of every block (+ column sums and folded biases)
-inline hipError_t xf_fold(RunCtx* c, const std::vector<CLayer>& layers, int H, int I, hipStream_t stream) {
+// room for what xf_refold derives, behind the block's parameters
+inline void xf_take_folds(ArenaPlan& a, CLayer& l, int H, int I) {
+  l.fqkv = a.take((size_t)3 * H * H); l.cs1 = a.take((size_t)2 * 3 * H); l.lb1 = a.take((size_t)2 * 3 * H);
+  l.f1 = a.take((size_t)I * H); l.cs2 = a.take((size_t)2 * I); l.lb2 = a.take((size_t)2 * I);
+}
+
+// gamma-folded copies of the two LayerNorm-consuming weights of every block (+ column sums and folded biases). At finalize: null stream, sync. Before a pass that
+// finds fold_dirty set (a tensor was reloaded after finalize): on the pass's stream without a wait, so the pass's launches are ordered behind the new folds.
+inline ia2p_status xf_refold(RunCtx* c, const std::vector<CLayer>& layers, int H, int I, hipStream_t stream, bool sync, const char* what) {
   hipError_t e = hipSuccess;
   auto Hp = [&](size_t off) { return c->arena + off; };
   auto Fp = [&](size_t off) { return (float*)(c->arena + off); };
@@ -16,7 +23,10 @@ inline hipError_t xf_fold(RunCtx* c, const std::vector<CLayer>& layers, int H, i
     if (e == hipSuccess) e = ia2p_launch_fold_ln(Hp(l.wqkv), Hp(l.ln1g), Hp(l.ln1b), Hp(l.bqkv), Hp(l.fqkv), Fp(l.cs1), Fp(l.lb1), 3 * H, H, stream);
     if (e == hipSuccess) e = ia2p_launch_fold_ln(Hp(l.w1), Hp(l.ln2g), Hp(l.ln2b), Hp(l.b1), Hp(l.f1), Fp(l.cs2), Fp(l.lb2), I, H, stream);
   }
-  return e;
+  if (e == hipSuccess && sync) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return fail_hip(c, e, (std::string(what) + " LayerNorm folding").c_str());
+  c->fold_dirty = false;
+  return IA2P_OK;
 }
 
 // x [M, H] is updated in place; st holds its row statistics in `slots` slots on entry and on exit. attn(): qkv [M, 3H] -> att [M, H].

@@ -12,7 +12,6 @@ unpinned. WAV files only (scipy.io.wavfile); other sample rates
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import re
 from dataclasses import dataclass, field
@@ -130,57 +129,31 @@ def tower_key(key: str, cfg: ImageBindConfig):
     raise KeyError(f"unknown parameter key '{key}'")
 
 
-class HipViT:
+class HipViT(_ffi.Executor):
     """one tower behind the C ABI (`ia2p_vit_*`)"""
 
     def __init__(self, config: ViTTowerConfig, device="cuda:0"):
-        self.config, self.device = config, torch.device(device)
-        self._lib = _ffi.lib()
-        self._h = C.c_void_p()
-        _ffi.check(self._lib.ia2p_vit_create(C.byref(_ffi.make_vit_config(config)), C.byref(self._h)), None, vit=True)
-        with torch.cuda.device(self.device):
-            self.arena = torch.zeros(self._lib.ia2p_vit_arena_bytes(self._h), dtype=torch.uint8, device=self.device)
-        _ffi.check(self._lib.ia2p_vit_bind_arena(self._h, _ffi.ptr(self.arena), self.arena.numel()), self._h, vit=True)
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.ia2p_vit_destroy(self._h)
-        except Exception:
-            pass
+        self.config = config
+        super().__init__("vit", _ffi.make_vit_config(config), device)
 
     def load_tensor(self, key: str, v: torch.Tensor):
         if key == "stem.weight" and v.ndim == 5:          # Conv3d on a frame repeated along time == Conv2d with the kernel summed over time (fp32 sum, one rounding)
             v = v.detach().float().sum(dim=2)
-        with torch.cuda.device(self.device):
-            t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
-            shape = (C.c_int64 * t.ndim)(*t.shape)
-            _ffi.check(self._lib.ia2p_vit_load_tensor(self._h, key.encode(), _ffi.ptr(t), shape, t.ndim, _ffi.current_stream()), self._h, vit=True)
-            torch.cuda.current_stream().synchronize()
-
-    def finalize(self):
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ia2p_vit_finalize_weights(self._h), self._h, vit=True)
+        super().load_tensor(key, v)
 
     @torch.no_grad()
+    @_ffi.on_device
     def __call__(self, pixels: torch.Tensor, return_hidden: bool = False):
         """pixels [B, C, H, W] -> fp32 [B, out_dim] (head output, not normalised) [, fp16 [B, tokens, hidden]: the last block's output]"""
         cfg = self.config
         if pixels.ndim != 4 or tuple(pixels.shape[1:]) != (cfg.in_channels, cfg.image_h, cfg.image_w):
             raise ValueError(f"expected [B, {cfg.in_channels}, {cfg.image_h}, {cfg.image_w}], got {tuple(pixels.shape)}")
         B = pixels.shape[0]
-        with torch.cuda.device(self.device):
-            x = pixels.to(device=self.device, dtype=torch.float16).contiguous()
-            n = self._lib.ia2p_vit_workspace_bytes(self._h, B)
-            if n == 0:
-                _ffi.check(2, self._h, vit=True)
-            if self._ws is None or self._ws.numel() < n:
-                self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-            out = torch.empty(B, cfg.out_dim, dtype=torch.float32, device=self.device)
-            last = torch.empty(B, cfg.tokens, cfg.hidden_size, dtype=torch.float16, device=self.device) if return_hidden else None
-            _ffi.check(self._lib.ia2p_vit_encode(self._h, _ffi.current_stream(), _ffi.ptr(x), B, _ffi.ptr(out), _ffi.ptr(last), _ffi.ptr(self._ws), self._ws.numel()),
-                       self._h, vit=True)
+        x = pixels.to(device=self.device, dtype=torch.float16).contiguous()
+        ws = self.workspace(self._lib.ia2p_vit_workspace_bytes(self._h, B))
+        out = torch.empty(B, cfg.out_dim, dtype=torch.float32, device=self.device)
+        last = torch.empty(B, cfg.tokens, cfg.hidden_size, dtype=torch.float16, device=self.device) if return_hidden else None
+        self.check(self._lib.ia2p_vit_encode(self._h, _ffi.current_stream(), _ffi.ptr(x), B, _ffi.ptr(out), _ffi.ptr(last), _ffi.ptr(ws), ws.numel()))
         return (out, last) if return_hidden else out
 
 

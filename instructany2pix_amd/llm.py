@@ -262,7 +262,7 @@ class _Head:
         return h.float().reshape(*lead, h.shape[-1])
 
 
-class HipInstructAny2PixLM:
+class HipInstructAny2PixLM(_ffi.Executor):
     PROJECTOR, PREDICTOR = "model.vae_projector_image", "model.vae_predictor_image"
 
     MAX_ROWS = 8                       # IA2P_LLM_MAX_ROWS: sequences per decode_batch call
@@ -284,54 +284,36 @@ class HipInstructAny2PixLM:
         self.sampler = _resolve_sampler(sampler)
         self.generation_defaults = dict(GENERATION_DEFAULTS)
         self.config = config.validate()
-        self.device = torch.device(device)
         self.max_positions = max_positions
         self.max_batch = int(max_batch)
         self.DEFAULT_VIDEO_TOKEN_IDX = video_token_id        # id of `<video>` (set by the tokenizer side, any2pix_arch.py:285-288)
-        self._lib = _ffi.lib()
-        self._h = C.c_void_p()
-        self._cfg_c = _ffi.make_llm_config(config)
-        _ffi.check(self._lib.ia2p_llm_create(C.byref(self._cfg_c), C.byref(self._h)), None, llm=True)
         self.quant_type = bnb_4bit_quant_type if load_in_4bit else None
         self._codebook = (C.c_float * 16)(*BNB_4BIT_CODEBOOKS[bnb_4bit_quant_type])
         self._quantize_heads = bool(load_in_4bit and quantize_heads)
-        if load_in_4bit:
-            _ffi.check(self._lib.ia2p_llm_set_weight_format(self._h, 4, self._codebook), self._h, llm=True)
-        with torch.cuda.device(self.device):
-            self.arena = torch.zeros(self._lib.ia2p_llm_arena_bytes(self._h), dtype=torch.uint8, device=self.device)
+
+        def weight_format():               # decides the arena's layout: before the arena is sized
+            if load_in_4bit:
+                self.check(self._lib.ia2p_llm_set_weight_format(self._h, 4, self._codebook))
+
+        super().__init__("llm", _ffi.make_llm_config(config), device, prepare=weight_format)
+        with self._on_device():
             self.kv = torch.zeros(self._lib.ia2p_llm_kv_slots_bytes(self._h, max_positions, self.max_batch), dtype=torch.uint8, device=self.device)
-        _ffi.check(self._lib.ia2p_llm_bind_arena(self._h, _ffi.ptr(self.arena), self.arena.numel()), self._h, llm=True)
-        _ffi.check(self._lib.ia2p_llm_bind_kv_slots(self._h, _ffi.ptr(self.kv), self.kv.numel(), max_positions, self.max_batch), self._h, llm=True)
+        self.check(self._lib.ia2p_llm_bind_kv_slots(self._h, _ffi.ptr(self.kv), self.kv.numel(), max_positions, self.max_batch))
         d = projector_depth(config.mm_projector_type)
         self._projector, self._predictor = _Head(self.PROJECTOR, d), _Head(self.PREDICTOR, d)
-        self._ws, self._ws_T = None, 0
+        self._ws_T = 0
         self._tok_dev = self._tok_host = None              # device sampler: the drawn ids on the device and their pinned host copy
         self.dtype = torch.float16
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.ia2p_llm_destroy(self._h)
-        except Exception:
-            pass
-
-    def to(self, *a, **kw):
-        return self
-
-    def eval(self):
-        return self
-
     def get_model(self):               # `any2pix_lm.get_model().vae_predictor_image(...)` (pipeline.py:236)
         return self
-
-    def _check(self, st):
-        _ffi.check(st, self._h, llm=True)
 
     @property
     def weight_bits(self) -> int:
         """16, or 4 when the decoder projections are held as 4-bit codes"""
         return self._lib.ia2p_llm_weight_bits(self._h)
 
+    @_ffi.on_device
     def _quantize_round_trip(self, key, w):
         """fp16 [N, K] -> the fp16 weights bitsandbytes' Linear4bit computes from: quantised block-wise and dequantised once"""
         N, K = w.shape
@@ -342,8 +324,8 @@ class HipInstructAny2PixLM:
         absmax = torch.empty(rows, dtype=torch.float32, device=w.device)
         out = torch.empty_like(w)
         s = _ffi.current_stream()
-        _ffi.check(self._lib.ia2p_llm_quantize_q4(s, _ffi.ptr(w), rows, cols, self._codebook, _ffi.ptr(packed), _ffi.ptr(absmax)), None, llm=True)
-        _ffi.check(self._lib.ia2p_llm_dequantize_q4(s, _ffi.ptr(packed), _ffi.ptr(absmax), rows, cols, self._codebook, _ffi.ptr(out)), None, llm=True)
+        _ffi.check(self._lib.ia2p_llm_quantize_q4(s, _ffi.ptr(w), rows, cols, self._codebook, _ffi.ptr(packed), _ffi.ptr(absmax)), None, "llm")
+        _ffi.check(self._lib.ia2p_llm_dequantize_q4(s, _ffi.ptr(packed), _ffi.ptr(absmax), rows, cols, self._codebook, _ffi.ptr(out)), None, "llm")
         torch.cuda.current_stream().synchronize()
         return out
 
@@ -352,48 +334,47 @@ class HipInstructAny2PixLM:
         for k, v in items:
             if k.endswith("rotary_emb.inv_freq"):          # buffer in older transformers checkpoints
                 continue
-            t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
-            if k.startswith((self.PROJECTOR + ".", self.PREDICTOR + ".")):
+            if k.startswith((self.PROJECTOR + ".", self.PREDICTOR + ".")):      # the heads live in torch tensors of their own, not in the arena
+                t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
                 if self._quantize_heads and k.endswith(".weight"):
                     t = self._quantize_round_trip(k, t)
                 (self._projector if k.startswith(self.PROJECTOR + ".") else self._predictor).load(k, t)
             else:
-                shape = (C.c_int64 * t.ndim)(*t.shape)
-                self._check(self._lib.ia2p_llm_load_tensor(self._h, k.encode(), _ffi.ptr(t), shape, t.ndim, _ffi.current_stream()))
-                torch.cuda.current_stream().synchronize()
+                self.load_tensor(k, v)
         if strict:
             missing = self._projector.missing() + self._predictor.missing()
             if missing:
                 raise KeyError(f"projector head parameters not loaded: {missing}")
-            self._check(self._lib.ia2p_llm_finalize_weights(self._h))
+            self.finalize()
 
     # ---- the two heads -----------------------------------------------------------------------------------------------
+    @_ffi.on_device
     def vae_projector_image(self, x):
         return self._projector(self._lib, x)
 
+    @_ffi.on_device
     def vae_predictor_image(self, x):
         return self._predictor(self._lib, x)
 
     # ---- engine calls ---------------------------------------------------------------------------------------------------
     def _workspace(self, T):
         if self._ws is None or T > self._ws_T:
-            n = self._lib.ia2p_llm_batch_workspace_bytes(self._h, T, min(self.max_batch, self.MAX_ROWS))
-            if n == 0:
-                self._check(2)
-            self._ws, self._ws_T = torch.empty(n, dtype=torch.uint8, device=self.device), T
+            self.workspace(self._lib.ia2p_llm_batch_workspace_bytes(self._h, T, min(self.max_batch, self.MAX_ROWS)))
+            self._ws_T = T
         return self._ws
 
     def reset(self):
-        self._check(self._lib.ia2p_llm_reset(self._h))
+        self.check(self._lib.ia2p_llm_reset(self._h))
 
     @property
     def position(self) -> int:
         return self._lib.ia2p_llm_position(self._h)
 
+    @_ffi.on_device
     def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
         ids = ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
         out = torch.empty(ids.numel(), self.config.hidden_size, dtype=torch.float16, device=self.device)
-        self._check(self._lib.ia2p_llm_embed(self._h, _ffi.current_stream(), _ffi.ptr(ids), ids.numel(), _ffi.ptr(out)))
+        self.check(self._lib.ia2p_llm_embed(self._h, _ffi.current_stream(), _ffi.ptr(ids), ids.numel(), _ffi.ptr(out)))
         return out
 
     def _outputs(self):
@@ -401,6 +382,7 @@ class HipInstructAny2PixLM:
                 torch.empty(self.config.vocab_size, dtype=torch.float32, device=self.device))
 
     @torch.no_grad()
+    @_ffi.on_device
     def prefill(self, inputs_embeds: torch.Tensor):
         """[T, hidden] rows at the current position -> (final-normed hidden row [hidden], logits row [vocab]) of the last one, fp32"""
         x = inputs_embeds.to(device=self.device, dtype=torch.float16).contiguous()
@@ -408,26 +390,28 @@ class HipInstructAny2PixLM:
             raise ValueError("inputs_embeds must be [T, hidden]")
         ws = self._workspace(x.shape[0])
         hid, logits = self._outputs()
-        self._check(self._lib.ia2p_llm_prefill(self._h, _ffi.current_stream(), _ffi.ptr(x), x.shape[0], _ffi.ptr(hid), _ffi.ptr(logits),
+        self.check(self._lib.ia2p_llm_prefill(self._h, _ffi.current_stream(), _ffi.ptr(x), x.shape[0], _ffi.ptr(hid), _ffi.ptr(logits),
                                                _ffi.ptr(ws), ws.numel()))
         return hid, logits
 
     @torch.no_grad()
+    @_ffi.on_device
     def decode(self, token_id: int):
         """one row (the table embedding of token_id) at the current position -> (hidden row, logits row), fp32"""
         ws = self._workspace(max(self._ws_T, 1))
         hid, logits = self._outputs()
-        self._check(self._lib.ia2p_llm_decode(self._h, _ffi.current_stream(), int(token_id), _ffi.ptr(hid), _ffi.ptr(logits), _ffi.ptr(ws), ws.numel()))
+        self.check(self._lib.ia2p_llm_decode(self._h, _ffi.current_stream(), int(token_id), _ffi.ptr(hid), _ffi.ptr(logits), _ffi.ptr(ws), ws.numel()))
         return hid, logits
 
     # ---- slots: several sequences in one cache ------------------------------------------------------------------------------
     def reset_slot(self, slot: int):
-        self._check(self._lib.ia2p_llm_reset_slot(self._h, int(slot)))
+        self.check(self._lib.ia2p_llm_reset_slot(self._h, int(slot)))
 
     def slot_position(self, slot: int) -> int:
         return self._lib.ia2p_llm_slot_position(self._h, int(slot))
 
     @torch.no_grad()
+    @_ffi.on_device
     def prefill_slot(self, slot: int, inputs_embeds: torch.Tensor):
         """`prefill` on the cache and position of `slot`; the other slots are not touched"""
         x = inputs_embeds.to(device=self.device, dtype=torch.float16).contiguous()
@@ -435,11 +419,12 @@ class HipInstructAny2PixLM:
             raise ValueError("inputs_embeds must be [T, hidden]")
         ws = self._workspace(x.shape[0])
         hid, logits = self._outputs()
-        self._check(self._lib.ia2p_llm_prefill_slot(self._h, _ffi.current_stream(), int(slot), _ffi.ptr(x), x.shape[0], _ffi.ptr(hid), _ffi.ptr(logits),
+        self.check(self._lib.ia2p_llm_prefill_slot(self._h, _ffi.current_stream(), int(slot), _ffi.ptr(x), x.shape[0], _ffi.ptr(hid), _ffi.ptr(logits),
                                                     _ffi.ptr(ws), ws.numel()))
         return hid, logits
 
     @torch.no_grad()
+    @_ffi.on_device
     def decode_batch(self, slots, token_ids):
         """one decode step of the sequences in `slots` (distinct, at most 8): row r is the table embedding of token_ids[r] at the position of
         slots[r] -> (hidden rows [n, hidden], logits rows [n, vocab]), fp32; every weight is read once for all rows"""
@@ -451,11 +436,12 @@ class HipInstructAny2PixLM:
         hid = torch.empty(max(n, 1), self.config.hidden_size, dtype=torch.float32, device=self.device)
         logits = torch.empty(max(n, 1), self.config.vocab_size, dtype=torch.float32, device=self.device)
         ids = C.c_int32 * max(n, 1)
-        self._check(self._lib.ia2p_llm_decode_batch(self._h, _ffi.current_stream(), ids(*slots), ids(*token_ids), n, _ffi.ptr(hid), _ffi.ptr(logits),
+        self.check(self._lib.ia2p_llm_decode_batch(self._h, _ffi.current_stream(), ids(*slots), ids(*token_ids), n, _ffi.ptr(hid), _ffi.ptr(logits),
                                                     _ffi.ptr(ws), ws.numel()))
         return hid, logits
 
     @torch.no_grad()
+    @_ffi.on_device
     def decode_batch_dev(self, slots, dev_tokens: torch.Tensor, token_index=None):
         """`decode_batch` with the ids in device memory: row r embeds dev_tokens[token_index[r]] (dev_tokens: int32 on the device, token_index: host
         indices into it, None = 0..n-1). The host never reads the ids; an id outside the vocabulary is clamped into the table by the kernel."""
@@ -470,7 +456,7 @@ class HipInstructAny2PixLM:
         hid = torch.empty(max(n, 1), self.config.hidden_size, dtype=torch.float32, device=self.device)
         logits = torch.empty(max(n, 1), self.config.vocab_size, dtype=torch.float32, device=self.device)
         ids = C.c_int32 * max(n, 1)
-        self._check(self._lib.ia2p_llm_decode_batch_dev(self._h, _ffi.current_stream(), ids(*slots), _ffi.ptr(dev_tokens), ids(*index), n, _ffi.ptr(hid),
+        self.check(self._lib.ia2p_llm_decode_batch_dev(self._h, _ffi.current_stream(), ids(*slots), _ffi.ptr(dev_tokens), ids(*index), n, _ffi.ptr(hid),
                                                         _ffi.ptr(logits), _ffi.ptr(ws), ws.numel()))
         return hid, logits
 
@@ -500,9 +486,10 @@ class HipInstructAny2PixLM:
         if len(seeds) != n or len(steps) != n:
             raise ValueError(f"{n} rows, {len(seeds)} seeds, {len(steps)} steps")
         out = torch.empty(n, dtype=torch.int32, device=block.device) if out is None else out[:n]
-        _ffi.check(self._lib.ia2p_sample_tokens_p(_ffi.current_stream(), C.c_void_p(block.data_ptr()), block.stride(0) if n > 1 else V, n, V, float(temperature),
-                                                  int(top_k or 0), top_p, int(bool(do_sample)), (C.c_uint64 * n)(*seeds), (C.c_uint32 * n)(*steps), _ffi.ptr(out),
-                                                  None, None), None, llm=True)
+        with self._on_device():            # (behind the argument checks: they need no engine)
+            _ffi.check(self._lib.ia2p_sample_tokens_p(_ffi.current_stream(), C.c_void_p(block.data_ptr()), block.stride(0) if n > 1 else V, n, V, float(temperature),
+                                                      int(top_k or 0), top_p, int(bool(do_sample)), (C.c_uint64 * n)(*seeds), (C.c_uint32 * n)(*steps), _ffi.ptr(out),
+                                                      None, None), None, "llm")
         return out
 
     def prepare_inputs_embeds(self, input_ids: torch.Tensor, extra_replacement=None) -> torch.Tensor:
@@ -640,6 +627,7 @@ class HipInstructAny2PixLM:
 
 
     @torch.no_grad()
+    @_ffi.on_device
     def _generate_device(self, prompts, extra_replacements, do_sample, temperature, max_new_tokens, stopping_criteria, top_k, seeds, top_p: Optional[float] = None):
         """`generate_batch` with the token drawn on the device. Per step of a group: `ia2p_sample_tokens_p` on the step's logits block, the ids copied
         asynchronously into pinned host memory, an event behind the copy, and -- before the host waits for that event -- the next `decode_batch_dev`

@@ -18,7 +18,6 @@ transformer stacks compute in fp16 with fp32 accumulation (tolerances in tests/t
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Callable, Dict, List, Optional
 
@@ -125,15 +124,11 @@ class HipGPT2Model:
         if E != self.config.n_embd or T > self.max_positions:
             raise ValueError(f"inputs_embeds {tuple(inputs_embeds.shape)}: width must be {self.config.n_embd}, at most {self.max_positions} tokens")
         core = self._core
-        x = inputs_embeds.to(device=self.device, dtype=torch.float16).contiguous()
-        n = core._lib.ia2p_clip_workspace_bytes(core._h, B, T)
-        if n == 0:
-            _ffi.check(2, core._h, clip=True)
-        if core._ws is None or core._ws.numel() < n:
-            core._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        last = torch.empty(B, T, E, dtype=torch.float16, device=self.device)
-        _ffi.check(core._lib.ia2p_clip_encode_embeds(core._h, _ffi.current_stream(), _ffi.ptr(x), B, T, None, _ffi.ptr(last), _ffi.ptr(core._ws),
-                                                     core._ws.numel()), core._h, clip=True)
+        with torch.cuda.device(self.device):
+            x = inputs_embeds.to(device=self.device, dtype=torch.float16).contiguous()
+            ws = core.workspace(core._lib.ia2p_clip_workspace_bytes(core._h, B, T))
+            last = torch.empty(B, T, E, dtype=torch.float16, device=self.device)
+            core.check(core._lib.ia2p_clip_encode_embeds(core._h, _ffi.current_stream(), _ffi.ptr(x), B, T, None, _ffi.ptr(last), _ffi.ptr(ws), ws.numel()))
         return {"last_hidden_state": last}
 
 

@@ -196,80 +196,48 @@ def internal_state_dict(state_dict, original_names: Optional[bool] = None) -> di
 
 
 # ---- the model ---------------------------------------------------------------------------------------------------------------------------------
-class HipSamModel:
+class HipSamModel(_ffi.Executor):
     """SAM behind the C ABI (`ia2p_sam_*`): `encode_image(pixels)` and `predict_boxes(embeddings, boxes)`"""
 
     def __init__(self, config: SamConfig = None, device="cuda:0"):
-        self.config, self.device = config or sam_vit_h_config(), torch.device(device)
-        self._lib = _ffi.lib()
-        self._h = C.c_void_p()
-        _ffi.check(self._lib.ia2p_sam_create(C.byref(_ffi.make_sam_config(self.config)), C.byref(self._h)), None, sam=True)
-        with torch.cuda.device(self.device):
-            self.arena = torch.zeros(self._lib.ia2p_sam_arena_bytes(self._h), dtype=torch.uint8, device=self.device)
-        _ffi.check(self._lib.ia2p_sam_bind_arena(self._h, _ffi.ptr(self.arena), self.arena.numel()), self._h, sam=True)
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.ia2p_sam_destroy(self._h)
-        except Exception:
-            pass
-
-    def eval(self):
-        return self
-
-    def to(self, *a, **kw):
-        return self
-
-    def load_tensor(self, name: str, v: torch.Tensor):
-        with torch.cuda.device(self.device):
-            t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
-            shape = (C.c_int64 * t.ndim)(*t.shape)
-            _ffi.check(self._lib.ia2p_sam_load_tensor(self._h, name.encode(), _ffi.ptr(t), shape, t.ndim, _ffi.current_stream()), self._h, sam=True)
-            torch.cuda.current_stream().synchronize()
+        self.config = config or sam_vit_h_config()
+        super().__init__("sam", _ffi.make_sam_config(self.config), device)
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """transformers' `SamModel` names or the original checkpoint's; an unknown key is a KeyError, and so is a tensor the executor misses"""
         for name, v in internal_state_dict(state_dict).items():
             self.load_tensor(name, v)
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ia2p_sam_finalize_weights(self._h), self._h, sam=True)
+        self.finalize()
         return self
 
     def _workspace(self, n_boxes: int):
-        n = self._lib.ia2p_sam_workspace_bytes(self._h, 1, n_boxes)
-        if n == 0:
-            _ffi.check(2, self._h, sam=True)
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self.workspace(self._lib.ia2p_sam_workspace_bytes(self._h, 1, n_boxes))
 
     @torch.no_grad()
+    @_ffi.on_device
     def encode_image(self, pixels: torch.Tensor) -> torch.Tensor:
         """pixels [1, 3, S, S] (normalised, zero-padded) -> fp16 [1, gh * gw, 256] image embeddings, channels-last rows"""
         cfg = self.config
         if pixels.ndim != 4 or tuple(pixels.shape) != (1, 3, cfg.image_size, cfg.image_size):
             raise ValueError(f"expected [1, 3, {cfg.image_size}, {cfg.image_size}], got {tuple(pixels.shape)}")
-        with torch.cuda.device(self.device):
-            x = pixels.to(device=self.device, dtype=torch.float16).contiguous()
-            ws = self._workspace(1)
-            emb = torch.empty(1, cfg.grid * cfg.grid, cfg.output_channels, dtype=torch.float16, device=self.device)
-            _ffi.check(self._lib.ia2p_sam_encode_image(self._h, _ffi.current_stream(), _ffi.ptr(x), 1, _ffi.ptr(emb), _ffi.ptr(ws), ws.numel()), self._h, sam=True)
+        x = pixels.to(device=self.device, dtype=torch.float16).contiguous()
+        ws = self._workspace(1)
+        emb = torch.empty(1, cfg.grid * cfg.grid, cfg.output_channels, dtype=torch.float16, device=self.device)
+        self.check(self._lib.ia2p_sam_encode_image(self._h, _ffi.current_stream(), _ffi.ptr(x), 1, _ffi.ptr(emb), _ffi.ptr(ws), ws.numel()))
         return emb
 
     @torch.no_grad()
+    @_ffi.on_device
     def predict_boxes(self, embeddings: torch.Tensor, boxes) -> Tuple[torch.Tensor, torch.Tensor]:
         """boxes [n, 4] x0 y0 x1 y1 in pixels of the S x S input -> (low-res mask logits fp32 [n, 4 gh, 4 gw], predicted IoU fp32 [n]), on the device"""
         cfg = self.config
         b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
         n = b.shape[0]
-        with torch.cuda.device(self.device):
-            ws = self._workspace(n)
-            low = torch.empty(n, 4 * cfg.grid, 4 * cfg.grid, dtype=torch.float32, device=self.device)
-            iou = torch.empty(n, dtype=torch.float32, device=self.device)
-            _ffi.check(self._lib.ia2p_sam_predict_boxes(self._h, _ffi.current_stream(), _ffi.ptr(embeddings), b.ctypes.data_as(C.POINTER(C.c_float)), n,
-                                                        _ffi.ptr(low), _ffi.ptr(iou), _ffi.ptr(ws), ws.numel()), self._h, sam=True)
+        ws = self._workspace(n)
+        low = torch.empty(n, 4 * cfg.grid, 4 * cfg.grid, dtype=torch.float32, device=self.device)
+        iou = torch.empty(n, dtype=torch.float32, device=self.device)
+        self.check(self._lib.ia2p_sam_predict_boxes(self._h, _ffi.current_stream(), _ffi.ptr(embeddings), b.ctypes.data_as(C.POINTER(C.c_float)), n,
+                                                    _ffi.ptr(low), _ffi.ptr(iou), _ffi.ptr(ws), ws.numel()))
         return low, iou
 
 

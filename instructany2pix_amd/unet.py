@@ -25,25 +25,15 @@ from .config import UNetConfig
 from .weights import attn_processor_names
 
 
-class HipUNet2DConditionModel:
+class HipUNet2DConditionModel(_ffi.Executor):
     dtype = torch.float16
 
     def __init__(self, config: UNetConfig, device: Union[str, torch.device] = "cuda:0"):
         config.validate()
         self.config = config
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _ffi.IA2PError("HipUNet2DConditionModel runs only on an MI355X device (no CPU path exists)")
-        self._lib = _ffi.lib()
-        torch.cuda.set_device(self.device)
-        if not self._lib.ia2p_device_is_gfx950():
-            raise _ffi.IA2PError("libia2p_hip.so is compiled for gfx950 only")
-        self._ctx = C.c_void_p()
-        _ffi.check(self._lib.ia2p_create(C.byref(_ffi.make_config(config)), C.byref(self._ctx)))
-        nbytes = self._lib.ia2p_arena_bytes(self._ctx)
-        self.arena = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)     # the ONE flat weight buffer
-        _ffi.check(self._lib.ia2p_bind_arena(self._ctx, _ffi.ptr(self.arena), nbytes), self._ctx)
-        self._workspace: Optional[torch.Tensor] = None
+        super().__init__("", _ffi.make_config(config), device)
+        torch.cuda.set_device(self.device)       # process-wide and left set: callers rely on it (the forward takes no device guard of its own)
+        self._ctx = self._h                      # (the name the forward, bench.py and the tools use for the handle)
         self._ws_key = None
         # context K/V hoisting: the cross-attention K/V projections of a context are computed once and reused while the SAME context
         # tensor object (unmodified: torch's version counter) keeps arriving, i.e. over the denoise steps of a request
@@ -55,21 +45,6 @@ class HipUNet2DConditionModel:
         self._ip_sig = None
         self.add_embedding = SimpleNamespace(linear_1=SimpleNamespace(in_features=config.projection_class_embeddings_input_dim))
 
-    def __del__(self):
-        try:
-            if getattr(self, "_ctx", None):
-                self._lib.ia2p_destroy(self._ctx)
-                self._ctx = None
-        except Exception:
-            pass
-
-    # ---- torch.nn.Module look-alikes the pipelines call --------------------------------------------------------
-    def to(self, *a, **kw):
-        return self
-
-    def eval(self):
-        return self
-
     # ---- weights --------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Union[Dict[str, torch.Tensor], Iterable[Tuple[str, torch.Tensor]]], strict: bool = True):
         """Load parameters by diffusers key. Accepts a dict or an iterator of (key, tensor) so 5 GB of weights
@@ -80,14 +55,11 @@ class HipUNet2DConditionModel:
             self._load(k, v)
         torch.cuda.synchronize(self.device)
         if strict:
-            _ffi.check(self._lib.ia2p_finalize_weights(self._ctx), self._ctx)
+            self.finalize()
 
     def _load(self, key: str, v: torch.Tensor):
         self._weights_gen += 1
-        t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
-        shape = (C.c_int64 * t.ndim)(*t.shape)
-        _ffi.check(self._lib.ia2p_load_tensor(self._ctx, key.encode(), _ffi.ptr(t), shape, t.ndim, _ffi.current_stream()), self._ctx)
-        torch.cuda.current_stream().synchronize()      # `t` may be a temporary
+        self.load_tensor(key, v)
 
     @property
     def arena_raw(self) -> torch.Tensor:
@@ -169,13 +141,9 @@ class HipUNet2DConditionModel:
         # (ip on/off, scale, tokens); the kernel plan table decides the K-split slabs, so its generation is part of the key
         key = (B, h, w, L, self._ip_sig[:3] if self._ip_sig else None, self._lib.ia2p_plan_generation())
         if self._ws_key != key:
-            n = self._lib.ia2p_workspace_bytes(self._ctx, B, h, w, L)
-            if n == 0:
-                _ffi.check(2, self._ctx)
-            if self._workspace is None or self._workspace.numel() < n:
-                self._workspace = torch.empty(n, dtype=torch.uint8, device=self.device)
+            self.workspace(self._lib.ia2p_workspace_bytes(self._ctx, B, h, w, L))
             self._ws_key = key
-        return self._workspace
+        return self._ws
 
     def __call__(self, sample, timestep, encoder_hidden_states=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                  return_dict: bool = False, out: Optional[torch.Tensor] = None, _tune_reps: Optional[int] = None,

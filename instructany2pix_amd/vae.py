@@ -14,7 +14,6 @@ for non-finite values: an overflow raises instead of producing black images (tes
 """
 from __future__ import annotations
 
-import ctypes as C
 from types import SimpleNamespace
 from typing import Optional
 
@@ -42,57 +41,27 @@ class DiagonalGaussianDistribution:
         return self.mean.to(self.parameters.dtype)
 
 
-class HipAutoencoderKL:
+class HipAutoencoderKL(_ffi.Executor):
     dtype = torch.float16
 
     def __init__(self, config: VAEConfig, device="cuda:0"):
         config.validate()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _ffi.IA2PError("HipAutoencoderKL runs only on an MI355X device (no CPU path exists)")
         self._cfg = config
         self.config = SimpleNamespace(**{**config.__dict__, "force_upcast": False})
-        self._lib = _ffi.lib()
-        torch.cuda.set_device(self.device)
-        if not self._lib.ia2p_device_is_gfx950():
-            raise _ffi.IA2PError("libia2p_hip.so is compiled for gfx950 only")
-        self._h = C.c_void_p()
-        _ffi.check(self._lib.ia2p_vae_create(C.byref(_ffi.make_vae_config(config)), C.byref(self._h)), None, vae=True)
-        n = self._lib.ia2p_vae_arena_bytes(self._h)
-        self.arena = torch.zeros(n, dtype=torch.uint8, device=self.device)
-        _ffi.check(self._lib.ia2p_vae_bind_arena(self._h, _ffi.ptr(self.arena), n), self._h, vae=True)
-        self._ws: Optional[torch.Tensor] = None
+        super().__init__("vae", _ffi.make_vae_config(config), device)
+        torch.cuda.set_device(self.device)       # process-wide and left set: callers rely on it
         self._factor = 2 ** (len(config.block_out_channels) - 1)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ia2p_vae_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def to(self, *a, **kw):
-        return self
 
     def load_state_dict(self, state_dict, strict: bool = True):
         items = state_dict.items() if hasattr(state_dict, "items") else state_dict
         torch.cuda.set_device(self.device)
         for k, v in items:
-            t = v.detach().to(device=self.device, dtype=torch.float16).contiguous()
-            shape = (C.c_int64 * t.ndim)(*t.shape)
-            _ffi.check(self._lib.ia2p_vae_load_tensor(self._h, k.encode(), _ffi.ptr(t), shape, t.ndim, _ffi.current_stream()), self._h, vae=True)
-            torch.cuda.current_stream().synchronize()
+            self.load_tensor(k, v)
         if strict:
-            _ffi.check(self._lib.ia2p_vae_finalize_weights(self._h), self._h, vae=True)
+            self.finalize()
 
     def _workspace(self, B, h, w, decode):
-        n = self._lib.ia2p_vae_workspace_bytes(self._h, B, h, w, int(decode))
-        if n == 0:
-            _ffi.check(2, self._h, vae=True)
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self.workspace(self._lib.ia2p_vae_workspace_bytes(self._h, B, h, w, int(decode)))
 
     @torch.no_grad()
     def encode(self, image: torch.Tensor, return_dict: bool = True):
@@ -104,7 +73,7 @@ class HipAutoencoderKL:
         h, w = H // f, W // f
         ws = self._workspace(B, h, w, False)
         mom = torch.empty(B, 2 * self._cfg.latent_channels, h, w, dtype=torch.float16, device=self.device)
-        _ffi.check(self._lib.ia2p_vae_encode(self._h, _ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(mom), B, h, w, _ffi.ptr(ws), ws.numel()), self._h, vae=True)
+        self.check(self._lib.ia2p_vae_encode(self._h, _ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(mom), B, h, w, _ffi.ptr(ws), ws.numel()))
         self._check_finite(mom, "encode")
         dist = DiagonalGaussianDistribution(mom)
         return SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
@@ -118,7 +87,7 @@ class HipAutoencoderKL:
         f = self._factor
         ws = self._workspace(B, h, w, True)
         img = torch.empty(B, self._cfg.out_channels, h * f, w * f, dtype=torch.float16, device=self.device)
-        _ffi.check(self._lib.ia2p_vae_decode(self._h, _ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(img), B, h, w, _ffi.ptr(ws), ws.numel()), self._h, vae=True)
+        self.check(self._lib.ia2p_vae_decode(self._h, _ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(img), B, h, w, _ffi.ptr(ws), ws.numel()))
         self._check_finite(img, "decode")
         return SimpleNamespace(sample=img) if return_dict else (img,)
 

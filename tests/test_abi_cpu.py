@@ -111,6 +111,63 @@ def test_workspace_bytes_are_the_recorded_ones(lib):
     lib.ia2p_clip_destroy(h)
 
 
+def _families():
+    """family -> (good config struct, a field that makes create refuse, words of that refusal, a workspace query that refuses, words of its message).
+    The LLM's workspace queries answer 0 without a message of their own: `llm_reset_slot` leaves the handle's message there."""
+    from instructany2pix_amd import _ffi
+    from instructany2pix_amd import imagebind as ib
+    from instructany2pix_amd.config import tiny, tiny_clip, tiny_llm, tiny_vae
+    from instructany2pix_amd.sam import sam_tiny_config
+    return {
+        "": (_ffi.make_config(tiny()), ("cross_attention_dim", 100), "divisibility", lambda l, h: l.ia2p_workspace_bytes(h, 1, 15, 16, 77), "latent 15x16"),
+        "vae": (_ffi.make_vae_config(tiny_vae()), ("stream_scale", 0.3), "stream_scale must be a power of two", lambda l, h: l.ia2p_vae_workspace_bytes(h, 2, 3, 3, 1), "latent 3x3"),
+        "clip": (_ffi.make_clip_config(tiny_clip(64, "gelu")), ("hidden_act", 7), "hidden_act must be", lambda l, h: l.ia2p_clip_workspace_bytes(h, 3, 200), "T=200"),
+        "vit": (_ffi.make_vit_config(ib.imagebind_tiny_config().vision), ("patch_size", 500), "does not fit", lambda l, h: l.ia2p_vit_workspace_bytes(h, 0), "vit: B=0"),
+        "sam": (_ffi.make_sam_config(sam_tiny_config()), ("window_size", 0), "window size 0", lambda l, h: l.ia2p_sam_workspace_bytes(h, 1, 65), "65 boxes"),
+        "llm": (_ffi.make_llm_config(tiny_llm()), ("num_kv_heads", 1), "grouped-query", lambda l, h: l.ia2p_llm_reset_slot(h, 5) * 0 + l.ia2p_llm_workspace_bytes(h, 0), "slot 5 of 0"),
+    }
+
+
+@pytest.mark.parametrize("family", ["", "vae", "clip", "vit", "sam", "llm"])
+def test_check_reads_the_message_of_the_family_and_handle_it_is_given(lib, family):
+    """`_ffi.check` finds `ia2p_<family>_last_error` by name. A refused create raises the mapped type with the family's message (no handle: the thread's); a
+    refused workspace query raises with the message of the handle asked about, not that of a live handle of another family that refused something since."""
+    from instructany2pix_amd import _ffi
+    fams = _families()
+    fn = lambda fam, name: getattr(lib, f"ia2p_{fam}_{name}" if fam else f"ia2p_{name}")
+    cfg, (field, bad), words, refuse, refused_words = fams[family]
+    assert family in _ffi.FAMILIES
+    good = getattr(cfg, field)
+    setattr(cfg, field, bad)
+    h = C.c_void_p()
+    st = fn(family, "create")(C.byref(cfg), C.byref(h))
+    assert st in (1, 2) and not h.value
+    with pytest.raises(ValueError) as e:
+        _ffi.check(st, None, family)
+    assert words in str(e.value) and str(e.value) == f"ia2p {'INVALID' if st == 1 else 'SHAPE'}: {fn(family, 'last_error')(None).decode()}"
+    setattr(cfg, field, good)
+    other = _ffi.FAMILIES[(_ffi.FAMILIES.index(family) + 1) % len(_ffi.FAMILIES)]
+    ocfg, _, _, orefuse, owords = fams[other]
+    oh = C.c_void_p()
+    _ffi.check(fn(family, "create")(C.byref(cfg), C.byref(h)), None, family)
+    _ffi.check(fn(other, "create")(C.byref(ocfg), C.byref(oh)), None, other)
+    try:
+        assert refuse(lib, h) == 0
+        assert orefuse(lib, oh) == 0            # the other family's handle refuses AFTER this one: the thread's last message is its
+        mine = fn(family, "last_error")(h).decode()
+        assert refused_words in mine and owords in fn(other, "last_error")(oh).decode() and owords not in mine
+        spellings = [dict(family=family)] + ([{family: True}] if family else [{}])      # (`vae=True`, ...: the keywords the other tests use)
+        for kw in spellings:
+            with pytest.raises(ValueError) as e:
+                _ffi.check(2, h, **kw)
+            assert str(e.value) == f"ia2p SHAPE: {mine}"
+    finally:
+        fn(family, "destroy")(h)
+        fn(other, "destroy")(oh)
+    with pytest.raises(TypeError):
+        _ffi.check(2, None, "unet")
+
+
 def test_gemm_plan_is_a_pure_host_function_and_the_plan_table_round_trips(lib):
     """tile / K-split choice needs no GPU: cost model by default, measured-plan table (ia2p_autotune) when present"""
     def plan(M, N, K, conv=0, geglu=0):
