@@ -163,6 +163,12 @@ ia2p_status ia2p_ddim_step_v(void* stream, const void* x, const void* eps_u, con
  * region to the next timestep (DDIM add_noise); c0 = 1, c1 = 0 after the last step. out2 may be NULL. HW = h * w. */
 ia2p_status ia2p_mask_blend(void* stream, const void* x, const void* init, const void* noise, const void* mask, float c0, float c1,
                             void* out, void* out2, int B, int C, int64_t HW);
+/* the same blend with per-request coefficients: coef = device float [B][2] = {c0, c1} of batch element b, so that the inpaint passes of several requests
+ * (reference gdino/lib.py:85-103, one pass per subject, called from pipeline.py:363-368 one request at a time), each at its own step of its own
+ * strength-shortened schedule, share one launch. A request that is through carries {1, 0}: over a {0, 1} mask it gets x back where m = 1 and init where
+ * m = 0, bit for bit. Null pointers (out2 excepted): IA2P_ERR_INVALID; B, C or HW < 1: IA2P_ERR_SHAPE; both before any launch. */
+ia2p_status ia2p_mask_blend_v(void* stream, const void* x, const void* init, const void* noise, const void* mask, const float* coef,
+                              void* out, void* out2, int B, int C, int64_t HW);
 
 /* ---- per-operator entry points (unit tests, and hosts that keep their own module tree) ----------------------------- */
 /* Operand size: the linear-layer tiles (buffer-load staging), the halo-staged 3x3 convolution and the fused attention tiles address an operand (activations,

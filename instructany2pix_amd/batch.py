@@ -50,6 +50,38 @@ def _coef_table(rows: Sequence[Sequence[tuple]], device) -> torch.Tensor:
     return torch.tensor(rows, dtype=torch.float32).to(device).contiguous()
 
 
+def _shard(N: int, shard: bool):
+    """(world, lo, hi): the contiguous shard [lo, hi) of N requests this rank runs (`dist.shard_range`); everything when `shard` is off or no process group is up"""
+    world = torch.distributed.get_world_size() if (shard and torch.distributed.is_available() and torch.distributed.is_initialized()) else 1
+    rank = torch.distributed.get_rank() if world > 1 else 0
+    return (world,) + D.shard_range(N, world, rank)
+
+
+def _gather_shards(t: torch.Tensor, N: int, world: int) -> torch.Tensor:
+    """every rank's shard rows [n_r, ...] -> all N rows in request order on every rank (equal-sized shards for the all-gather: pad, gather, cut)"""
+    if world == 1:
+        return t
+    per = (N + world - 1) // world
+    pad = torch.zeros((per,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    pad[: t.shape[0]] = t
+    allr = D.gather_batches(pad).reshape(world, per, *t.shape[1:])
+    return torch.cat([allr[r][: D.shard_range(N, world, r)[1] - D.shard_range(N, world, r)[0]] for r in range(world)], dim=0)
+
+
+def _check_group(group, what: str):
+    if not 1 <= int(group) <= 8:
+        raise ValueError(f"group={group}: a group is one launch sequence of 1..8 requests (B_eff = 2 * group <= 16 rows, the limit of the image-projection and "
+                         f"embedding kernels) -- {what}")
+
+
+def _check_latents(latents: Sequence[torch.Tensor], what: str):
+    if len(latents) == 0:
+        raise ValueError(f"{what} needs at least one request")
+    shapes = {tuple(x.shape[-2:]) for x in latents}
+    if len(shapes) != 1:
+        raise ValueError(f"requests of one call must share the latent size, got {sorted(shapes)}")
+
+
 @torch.no_grad()
 def invert_batch(unet, scheduler_config, latents, prompt_embeds, pooled, steps: Sequence[int], ip_scales=None):
     """DDIM inversion x0 -> xT of B requests at once (reference loop pnp_pipeline.py:251-275 per request), each over its own `steps[b]`-step
@@ -154,9 +186,7 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
                          f"embedding kernels)")
     # polar-mixing noise comes from the global CPU RNG in REQUEST order (what N sequential reference calls would draw), on every rank alike
     noises = [r.noise if r.noise is not None else torch.randn(r.base_latents.shape, dtype=torch.float16) for r in requests]
-    world = torch.distributed.get_world_size() if (shard and torch.distributed.is_available() and torch.distributed.is_initialized()) else 1
-    rank = torch.distributed.get_rank() if world > 1 else 0
-    lo, hi = D.shard_range(N, world, rank)
+    world, lo, hi = _shard(N, shard)
     unet, cfgs = pipeline.pipe.unet, pipeline.pipe.scheduler.config
     ipa = pipeline.ip_adapter_xl
     dev = unet.device
@@ -181,12 +211,410 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
     like = requests[0].base_latents
     empty = torch.empty((0,) + tuple(like.shape[1:]), dtype=torch.float16, device=dev)
     out, inv = (torch.cat(outs) if outs else empty), (torch.cat(invs) if invs else empty)
-    if world > 1:                    # equal-sized shards for the all-gather: pad, gather, cut
-        per = (N + world - 1) // world
-        def gathered(t):
-            pad = torch.zeros((per,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-            pad[: t.shape[0]] = t
-            allr = D.gather_batches(pad).reshape(world, per, *t.shape[1:])
-            return torch.cat([allr[r][: D.shard_range(N, world, r)[1] - D.shard_range(N, world, r)[0]] for r in range(world)], dim=0)
-        out, inv = gathered(out), gathered(inv)
-    return out, inv
+    return _gather_shards(out, N, world), _gather_shards(inv, N, world)
+
+
+# ---- the stages after the hot segment, batched the same way: refiner pass and subject-consistency inpainting ---------------------------------------------
+# Row layout of every guided evaluation: [uncond x n | cond x n] (the reference's cat([latents] * 2) per request). All requests of a group start at
+# iteration 0 at their own first kept timestep; a request with fewer steps is through early and is HELD: evaluated at its last timestep, moved with
+# (g, 1, 0) (and, in the inpaint loop, blended with (1, 0)), which returns its latents bit for bit while the others finish.
+
+def _kept_steps(num_inference_steps: int, strength: float, request: int):
+    """`get_timesteps` of the img2img / inpaint pipelines: (t_start, number of steps kept); the serial pipelines' errors, naming the request"""
+    if strength < 0 or strength > 1:
+        raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength} (request {request})")
+    init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+    t_start = max(num_inference_steps - init_timestep, 0)
+    n_steps = num_inference_steps - t_start
+    if n_steps < 1:
+        raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
+                         f"{n_steps} which is < 1 and not appropriate for this pipeline. (request {request})")
+    return t_start, n_steps
+
+
+def _check_loop_args(num_inference_steps, guidance_scale, what: str):
+    if num_inference_steps is None or not isinstance(num_inference_steps, int) or num_inference_steps <= 0:
+        raise ValueError(f"`num_inference_steps` has to be a positive integer but is {num_inference_steps} of type {type(num_inference_steps)}.")
+    if float(guidance_scale) <= 1.0:
+        raise ValueError(f"{what} blends eps_u + g (eps_c - eps_u) for every request; guidance_scale={guidance_scale} <= 1 means NO guidance in the serial "
+                         f"pipeline: run such a request through it instead")
+
+
+@dataclass
+class RefineRequest:
+    """One refiner pass on explicit conditioning (what `StableDiffusionXLImg2ImgPipeline.__call__(latents=...)` takes), with its own strength."""
+    latents: torch.Tensor                      # [1, 4, h, w] clean latents, scaled
+    prompt_embeds: torch.Tensor                # the four refiner embeddings (text encoder 2)
+    pooled_prompt_embeds: torch.Tensor
+    negative_prompt_embeds: torch.Tensor
+    negative_pooled_prompt_embeds: torch.Tensor
+    strength: float = 0.3
+    noise: Optional[torch.Tensor] = None       # start noise; None: drawn from the global CPU RNG in request order
+
+
+@dataclass
+class RefineTables:
+    """Host tables of one group's joint Euler loop: `[iterations][requests]`, every coefficient triple in the (g, c_x, c_e) form of `ia2p_ddim_step_v`."""
+    steps: List[int]                 # steps each request takes
+    start_sigma: List[float]         # add_noise: x = latents + sigma * noise
+    timesteps: List[List[float]]
+    input_scale: List[List[float]]   # scale_model_input: 1 / sqrt(sigma^2 + 1)
+    coef: List[List[tuple]]          # (g, 1, sigma_next - sigma); (g, 1, 0) once a request is through
+
+
+def refine_tables(scheduler_config, strengths: Sequence[float], num_inference_steps: int = 50, guidance_scale: float = 5.0) -> RefineTables:
+    """What `EulerDiscreteScheduler` gives every request alone (img2img.py: `get_timesteps` tail, `add_noise` sigma, `input_scale` / `step_coeffs` at index
+    t_start + k), laid out for the joint loop. Pure host arithmetic: needs no GPU."""
+    from .scheduler import EulerDiscreteScheduler
+    sch = EulerDiscreteScheduler.from_config(scheduler_config)
+    sch.set_timesteps(num_inference_steps)
+    kept = [_kept_steps(num_inference_steps, float(s), i) for i, s in enumerate(strengths)]
+    nmax, g = max(n for _, n in kept), float(guidance_scale)
+    tb = RefineTables([n for _, n in kept], [], [[0.0] * len(kept) for _ in range(nmax)], [[1.0] * len(kept) for _ in range(nmax)],
+                      [[(g, 1.0, 0.0)] * len(kept) for _ in range(nmax)])
+    for r, (t_start, n) in enumerate(kept):
+        tb.start_sigma.append(float(sch.sigmas[sch.index_for_timestep(sch.timesteps[t_start])]))
+        for k in range(nmax):
+            idx = t_start + min(k, n - 1)
+            tb.timesteps[k][r], tb.input_scale[k][r] = float(sch.timesteps[idx]), sch.input_scale(idx)
+            if k < n:
+                tb.coef[k][r] = (g,) + tuple(sch.step_coeffs(idx))
+    return tb
+
+
+def _draw_noises(given: Sequence[Optional[torch.Tensor]], latents: Sequence[torch.Tensor]):
+    """missing noises from the global CPU RNG in REQUEST order (what the serial pipelines draw, one call after the other), on every rank alike"""
+    return [n if n is not None else torch.randn(x.shape, dtype=torch.float16) for n, x in zip(given, latents)]
+
+
+@torch.no_grad()
+def _refine_group(piperf, reqs: List[RefineRequest], noises, tb: RefineTables, aesthetic_score, negative_aesthetic_score):
+    from .img2img import get_add_time_ids_aesthetic
+    unet = piperf.unet
+    dev, n = unet.device, len(reqs)
+    f16 = lambda t: t.to(device=dev, dtype=torch.float16)
+    cat = lambda xs: torch.cat([f16(x) for x in xs], dim=0).contiguous()
+    lat, noise = cat([r.latents for r in reqs]), cat(noises)
+    size = (lat.shape[-2] * piperf.vae_scale_factor, lat.shape[-1] * piperf.vae_scale_factor)
+    ids, neg_ids = get_add_time_ids_aesthetic(unet, size, (0, 0), size, aesthetic_score, negative_aesthetic_score, size, (0, 0), size,
+                                              int(reqs[0].pooled_prompt_embeds.shape[-1]), piperf.config.requires_aesthetics_score)
+    ctx = torch.cat([cat([r.negative_prompt_embeds for r in reqs]), cat([r.prompt_embeds for r in reqs])], dim=0).contiguous()
+    pooled = torch.cat([cat([r.negative_pooled_prompt_embeds for r in reqs]), cat([r.pooled_prompt_embeds for r in reqs])], dim=0).contiguous()
+    added = {"text_embeds": pooled, "time_ids": torch.cat([neg_ids.repeat(n, 1), ids.repeat(n, 1)], dim=0).to(dev)}
+    ts_all = torch.tensor([row + row for row in tb.timesteps], dtype=torch.float32).to(dev).contiguous()
+    scale_all = _coef_table([[(1.0, s, 0.0) for s in row] for row in tb.input_scale], dev)
+    coef_all = _coef_table(tb.coef, dev)
+    x, nxt = torch.empty_like(lat), torch.empty_like(lat)
+    fused_update_v(lat, noise, None, _coef_table([(1.0, 1.0, s) for s in tb.start_sigma], dev), x)              # add_noise at every request's first kept timestep
+    model_in = torch.empty((2 * n,) + tuple(x.shape[1:]), dtype=torch.float16, device=dev)
+    eps = torch.empty_like(model_in)
+    for k in range(len(tb.timesteps)):
+        fused_update_v(x, x, None, scale_all[k], model_in[:n], model_in[n:])                                    # scale_model_input on cat([x] * 2)
+        unet(model_in, ts_all[k], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps)
+        fused_update_v(x, eps[:n], eps[n:], coef_all[k], nxt)                                                   # CFG + Euler step
+        x, nxt = nxt, x
+    return x
+
+
+@torch.no_grad()
+def refine_batch(piperf, requests: List[RefineRequest], group: int = 4, shard: bool = True, num_inference_steps: int = 50, guidance_scale: float = 5.0,
+                 aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5):
+    """The refiner's Euler img2img loop (`StableDiffusionXLImg2ImgPipeline.__call__`, reference pipeline.py:358-361) for N requests: one UNet evaluation at
+    B_eff = 2 n per iteration of a group, request r on its own `strength`-shortened tail of the shared 50-step schedule. The per-call values are the class
+    defaults the reference runs with. -> refined latents [N, 4, h, w] in request order on every rank."""
+    _check_latents([r.latents for r in requests], "refine_batch")
+    _check_group(group, "refine_batch")
+    _check_loop_args(num_inference_steps, guidance_scale, "refine_batch")
+    N = len(requests)
+    refine_tables(piperf.scheduler.config, [r.strength for r in requests], num_inference_steps, guidance_scale)      # every request's refusal before any launch
+    noises = _draw_noises([r.noise for r in requests], [r.latents for r in requests])
+    world, lo, hi = _shard(N, shard)
+    outs = []
+    for g0 in range(lo, hi, group):
+        reqs = requests[g0:min(g0 + group, hi)]
+        tb = refine_tables(piperf.scheduler.config, [r.strength for r in reqs], num_inference_steps, guidance_scale)
+        outs.append(_refine_group(piperf, reqs, noises[g0:g0 + len(reqs)], tb, aesthetic_score, negative_aesthetic_score))
+    dev = piperf.unet.device
+    out = torch.cat(outs) if outs else torch.empty((0,) + tuple(requests[0].latents.shape[1:]), dtype=torch.float16, device=dev)
+    return _gather_shards(out, N, world)
+
+
+@dataclass
+class InpaintRequest:
+    """One subject-consistency pass (what `IPAdapterXL(pipe_inpainting).generate(latents=, mask_image=, clip_image_embeds_local=, mode='local')` takes)."""
+    latents: torch.Tensor                      # [1, 4, h, w] clean latents, scaled
+    mask: torch.Tensor                         # anything `inpaint.prepare_mask` takes: 1 = repaint
+    subject_embed: torch.Tensor                # [D] the subject's embedding ('local' crop of the image-projection model)
+    prompt_embeds: torch.Tensor                # the four text embeddings of the pass (without image tokens)
+    pooled_prompt_embeds: torch.Tensor
+    negative_prompt_embeds: torch.Tensor
+    negative_pooled_prompt_embeds: torch.Tensor
+    strength: float = 0.7
+    noise: Optional[torch.Tensor] = None       # start and re-noising noise; None: drawn from the global CPU RNG in request order
+
+
+@dataclass
+class InpaintTables:
+    """Host tables of one group's joint inpaint loop: `[iterations][requests]`."""
+    steps: List[int]
+    start: List[tuple]               # (1, c_x, c_e): x = c_x latents + c_e noise -- add_noise at the first kept timestep; (1, 0, init_noise_sigma) at strength 1.0
+    timesteps: List[List[float]]
+    coef: List[List[tuple]]          # (g, c_x, c_e) of DDIMScheduler.step; (g, 1, 0) once a request is through
+    blend: List[List[tuple]]         # (c0, c1): add_noise to the NEXT timestep; (1, 0) after a request's last step and while it is held
+
+
+def inpaint_tables(scheduler_config, strengths: Sequence[float], num_inference_steps: int = 50, guidance_scale: float = 7.5) -> InpaintTables:
+    """What `DDIMScheduler` gives every request alone in inpaint.py's loop, laid out for the joint loop. Pure host arithmetic: needs no GPU."""
+    sch = DDIMScheduler.from_config(scheduler_config)
+    sch.set_timesteps(num_inference_steps)
+    kept = [_kept_steps(num_inference_steps, float(s), i) for i, s in enumerate(strengths)]
+    nmax, g = max(n for _, n in kept), float(guidance_scale)
+    tb = InpaintTables([n for _, n in kept], [], [[0.0] * len(kept) for _ in range(nmax)], [[(g, 1.0, 0.0)] * len(kept) for _ in range(nmax)],
+                       [[(1.0, 0.0)] * len(kept) for _ in range(nmax)])
+    for r, ((t_start, n), s) in enumerate(zip(kept, strengths)):
+        tail = [int(t) for t in sch.timesteps[t_start:]]
+        tb.start.append((1.0, 0.0, float(sch.init_noise_sigma)) if float(s) == 1.0 else (1.0,) + tuple(sch.add_noise_coeffs(tail[0])))
+        for k in range(nmax):
+            tb.timesteps[k][r] = float(tail[min(k, n - 1)])
+            if k < n:
+                tb.coef[k][r] = (g,) + tuple(sch.step_coeffs(tail[k]))
+                if k < n - 1:
+                    tb.blend[k][r] = tuple(sch.add_noise_coeffs(tail[k + 1]))
+    return tb
+
+
+@torch.no_grad()
+def _inpaint_group(ipa, reqs: List[InpaintRequest], noises, tb: InpaintTables, scale: float):
+    from .inpaint import prepare_mask
+    from .scheduler import mask_blend_v
+    unet = ipa.pipe.unet
+    dev, n = unet.device, len(reqs)
+    f16 = lambda t: t.to(device=dev, dtype=torch.float16)
+    cat = lambda xs: torch.cat([f16(x) for x in xs], dim=0).contiguous()
+    lat, noise = cat([r.latents for r in reqs]), cat(noises)
+    h, w = lat.shape[-2:]
+    mask = torch.cat([prepare_mask(r.mask, h, w, dev) for r in reqs], dim=0).contiguous()
+    if tuple(mask.shape) != (n, 1, h, w):
+        raise ValueError(f"every request carries ONE mask, got {tuple(mask.shape)} for {n} requests")
+    # the subjects' 'local' image tokens, one call per group, with the crop weights IPAdapterXL.generate passes (scale_g = 1.0, scale_l = 0.5)
+    ip, ip_un = ipa.get_image_embeds(clip_image_embeds_local=torch.stack([r.subject_embed.reshape(-1) for r in reqs]), mode="local", scale_g=1.0, scale_l=0.5)
+    ctx = torch.cat([torch.cat([cat([r.negative_prompt_embeds for r in reqs]), ip_un], dim=1),
+                     torch.cat([cat([r.prompt_embeds for r in reqs]), ip], dim=1)], dim=0).contiguous()             # ip_adapter.py:341-342
+    pooled = torch.cat([cat([r.negative_pooled_prompt_embeds for r in reqs]), cat([r.pooled_prompt_embeds for r in reqs])], dim=0).contiguous()
+    size = (h * ipa.pipe.vae_scale_factor, w * ipa.pipe.vae_scale_factor)
+    tid = get_add_time_ids(unet, size, (0, 0), size, int(reqs[0].pooled_prompt_embeds.shape[-1])).repeat(2 * n, 1).to(dev)
+    added = {"text_embeds": pooled, "time_ids": tid}
+    sc = torch.full((2 * n,), float(scale), dtype=torch.float32).to(dev)
+    ts_all = torch.tensor([row + row for row in tb.timesteps], dtype=torch.float32).to(dev).contiguous()
+    coef_all, blend_all = _coef_table(tb.coef, dev), _coef_table(tb.blend, dev)
+    x = torch.empty_like(lat)
+    fused_update_v(lat, noise, None, _coef_table(tb.start, dev), x)
+    model_in = torch.cat([x, x], dim=0).contiguous()
+    eps, stepped = torch.empty_like(model_in), torch.empty_like(x)
+    for k in range(len(tb.timesteps)):
+        unet(model_in, ts_all[k], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps, ip_scales=sc)
+        fused_update_v(model_in[:n], eps[:n], eps[n:], coef_all[k], stepped)
+        mask_blend_v(stepped, lat, noise, mask, blend_all[k], model_in[:n], model_in[n:])
+    return model_in[:n].clone()
+
+
+@torch.no_grad()
+def inpaint_batch(ipa, requests: List[InpaintRequest], group: int = 4, shard: bool = True, num_inference_steps: int = 50, guidance_scale: float = 7.5,
+                  scale: float = 0.8):
+    """The inpaint DDIM loop (`StableDiffusionXLInpaintPipeline.__call__` behind `IPAdapterXL.generate(mode='local')`, reference gdino/lib.py:89-102) for N
+    requests, one subject each: one UNet evaluation at B_eff = 2 n per iteration of a group, request r on its own `strength`-shortened tail of the shared
+    schedule with its own mask and subject tokens. `ipa` is the adapter over the inpainting pipeline (`InstructAny2PixPipeline.ip_adapter_xl_inpaint`); steps,
+    guidance and IP scale are what `subject_consistency` passes. The processors' own scale is left alone: the IP scale goes in per row.
+    -> latents [N, 4, h, w] in request order on every rank."""
+    _check_latents([r.latents for r in requests], "inpaint_batch")
+    _check_group(group, "inpaint_batch")
+    _check_loop_args(num_inference_steps, guidance_scale, "inpaint_batch")
+    N = len(requests)
+    cfgs = ipa.pipe.scheduler.config
+    inpaint_tables(cfgs, [r.strength for r in requests], num_inference_steps, guidance_scale)                  # every request's refusal before any launch
+    noises = _draw_noises([r.noise for r in requests], [r.latents for r in requests])
+    world, lo, hi = _shard(N, shard)
+    outs = []
+    for g0 in range(lo, hi, group):
+        reqs = requests[g0:min(g0 + group, hi)]
+        tb = inpaint_tables(cfgs, [r.strength for r in reqs], num_inference_steps, guidance_scale)
+        outs.append(_inpaint_group(ipa, reqs, noises[g0:g0 + len(reqs)], tb, scale))
+    dev = ipa.pipe.unet.device
+    out = torch.cat(outs) if outs else torch.empty((0,) + tuple(requests[0].latents.shape[1:]), dtype=torch.float16, device=dev)
+    return _gather_shards(out, N, world)
+
+
+# ---- whole edit requests ---------------------------------------------------------------------------------------------------------------------------------
+
+def per_request(value, N: int, name: str, is_one=None) -> list:
+    """a knob of `__call__` as a scalar (for all requests) or a list of N"""
+    one = is_one(value) if is_one is not None else not isinstance(value, (list, tuple))
+    if one:
+        return [value] * N
+    if len(value) != N:
+        raise ValueError(f"`{name}` has {len(value)} entries for {N} requests")
+    return list(value)
+
+
+def _is_one_h(v) -> bool:
+    return len(v) == 3 and not any(isinstance(x, (list, tuple)) or (torch.is_tensor(x) and x.ndim > 0) for x in v)
+
+
+def _vae_in_batches(pipeline, fn, t: torch.Tensor, group: int, decode: bool) -> torch.Tensor:
+    """a VAE hook over [n, ...] in equal batches of at most `group` rows, and of no more than the attached VAE takes in one launch sequence at this size
+    (`HipAutoencoderKL.max_batch`: at 1024 x 1024 a decode takes 3 images, an encode 7)"""
+    n, rows = t.shape[0], int(group)
+    if pipeline.vae is not None:
+        f = 1 if decode else pipeline.pipe.vae_scale_factor             # decode: latents in; encode: pixels in
+        rows = min(rows, pipeline.vae.max_batch(t.shape[-2] // f, t.shape[-1] // f, decode))
+    k = -(-n // rows)
+    per = -(-n // k)
+    return torch.cat([fn(t[i:i + per]) for i in range(0, n, per)], dim=0)
+
+
+@torch.no_grad()
+def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
+               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True):
+    """`InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
+    See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding)."""
+    from .image_processor import OUTPUT_TYPES, requantize
+    from .pipeline import _need, fuse_instruction_embedding, to_8bit_image
+    from .prior import MODALITY
+    insts, mm_datas = list(insts), list(mm_datas)
+    N = len(insts)
+    if N == 0:
+        raise ValueError("edit_batch needs at least one request")
+    if len(mm_datas) != N:
+        raise ValueError(f"{N} instructions for {len(mm_datas)} mm_data lists")
+    if output_type not in OUTPUT_TYPES:
+        raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
+    if output_type != "latent" and pipeline.vae is None:
+        raise ValueError(f"output_type={output_type!r} needs the pipeline built with vae=<HipAutoencoderKL>")
+    _check_group(group, "edit_batch")
+    alpha, norm, refinement = per_request(alpha, N, "alpha"), per_request(norm, N, "norm"), per_request(refinement, N, "refinement")
+    steps, subject_strength = per_request(num_inference_steps, N, "num_inference_steps"), per_request(subject_strength, N, "subject_strength")
+    cfg, scale, h = per_request(cfg, N, "cfg"), per_request(scale, N, "scale"), per_request(h, N, "h", _is_one_h)
+    for i in range(N):
+        if steps[i] is None or int(steps[i]) <= 0:
+            raise ValueError(f"`num_inference_steps` has to be a positive integer but is {steps[i]} (request {i})")
+        if float(cfg[i]) <= 1.0:
+            raise ValueError(f"edit_batch blends eps_u + g (eps_c - eps_u) for every request; cfg={cfg[i]} <= 1 (request {i}) means NO guidance in the "
+                             f"reference: run that request through __call__ instead")
+        if float(refinement[i]) > 0:
+            _kept_steps(50, float(refinement[i]), i)
+        if float(subject_strength[i]) > 0:
+            _kept_steps(50, float(subject_strength[i]), i)
+    if pipeline.ip_adapter_xl is None:
+        raise NotImplementedError("edit_batch drives the IP-Adapter path (construct the pipeline with ip_ckpt=)")
+    if pipeline.piperf is None and any(float(r) > 0 for r in refinement):
+        raise ValueError("refinement > 0 needs the pipeline built with refiner_unet= (pass refinement=0 to serve these requests without the refiner pass)")
+
+    # ---- conditioning: one LLM pass for all requests, or the conditioner per request; a request without <im_gen> is answered here -------------------------
+    results: list = [None] * N
+    cs = pipeline._conditions_for_batch(insts, mm_datas)
+    for i, c in enumerate(cs):
+        if c.get("image_embeds") is None:
+            results[i] = (None, None, f"FAILED: the LLM produced no <im_gen>: {c.get('caption')!r}")
+    live = [i for i in range(N) if results[i] is None]
+    if not live:
+        return results
+    latent_la = {}
+    for i in live:                                                                             # the prior runs per request (reference :313-317)
+        c, y0 = cs[i], cs[i].get("y")
+        if y0 is None:
+            if pipeline.model is None:
+                raise NotImplementedError("the conditioner returned no `y` and no prior= was attached")
+            ie = c["image_embeds"]
+            y = pipeline.model.generate_diffusion(MODALITY.VIDEO, MODALITY.IMAGE, ie / ie.norm() * 100, device="cpu", no_diffusion=True,
+                                                  num_inference_steps=25, image_bind_overwrite=None, dtype=torch.float32, guidance_scale=10,
+                                                  force_guidence_t0=True, do_classifier_free_guidance=True, score=6.5)
+            y0 = y[0].to(device=c["base_embed"].device, dtype=c["base_embed"].dtype)
+        latent_la[i] = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], y0, h[i], norm[i])
+
+    # ---- base images -> latents, the images among them encoded in batches (posterior samples: global RNG, request order) -----------------------------------
+    base = {i: cs[i]["base_latents"] for i in live if cs[i].get("base_latents") is not None}
+    todo = [i for i in live if i not in base]
+    if todo:
+        imgs = []
+        for i in todo:
+            img = cs[i].get("base_image")
+            if img is None and cs[i].get("base_img_path") is not None:
+                img = pipeline.loas_base_img(cs[i]["base_img_path"])
+            if img is None:
+                raise KeyError(f"the conditioner returned none of base_latents / base_image / base_img_path (request {i})")
+            if pipeline.vae is None:
+                raise ValueError("a base_image / base_img_path needs the pipeline built with vae=<HipAutoencoderKL>")
+            imgs.append(pipeline.pipe_inversion.image_processor.preprocess(img))
+        enc = _vae_in_batches(pipeline, pipeline.pipe_inversion._vae_encode, torch.cat(imgs, dim=0), group, False)
+        base.update({i: enc[j:j + 1] for j, i in enumerate(todo)})
+    _check_latents([base[i] for i in live], "edit_batch")
+
+    # ---- the hot segment ---------------------------------------------------------------------------------------------------------------------------------
+    reqs = [EditRequest(base_latents=base[i], latent_la=latent_la[i].reshape(1, -1)[0], prompt_embeds=cs[i]["prompt_embeds"],
+                        pooled_prompt_embeds=cs[i]["pooled_prompt_embeds"], negative_prompt_embeds=cs[i]["negative_prompt_embeds"],
+                        negative_pooled_prompt_embeds=cs[i]["negative_pooled_prompt_embeds"], inv_prompt_embeds=cs[i].get("inv_prompt_embeds"),
+                        inv_pooled_prompt_embeds=cs[i].get("inv_pooled_prompt_embeds"), alpha=alpha[i], num_inference_steps=int(steps[i]), cfg=float(cfg[i]),
+                        scale=float(scale[i]), noise=cs[i].get("polar_noise")) for i in live]
+    pipeline.pipe_inversion.unet = pipeline.pipe.unet
+    images, latent_inv = denoise_batch(pipeline, reqs, group=group, shard=shard)
+    row = {i: j for j, i in enumerate(live)}
+    non_refined = {i: images[row[i]:row[i] + 1] for i in live}
+    oo = dict(non_refined)
+    decoded = {}                     # request -> the decode of its `non_refined`, when the refiner hand-over made it
+
+    # ---- refiner pass for the requests that ask for it -----------------------------------------------------------------------------------------------------
+    ref = [i for i in live if float(refinement[i]) > 0]
+    if ref:
+        keys = ("refiner_prompt_embeds", "refiner_pooled_prompt_embeds", "refiner_negative_prompt_embeds", "refiner_negative_pooled_prompt_embeds")
+        for i in ref:
+            _need(cs[i], keys, "refiner pass")
+        piperf = pipeline.piperf
+        start = torch.cat([non_refined[i] for i in ref], dim=0)
+        vae_route = pipeline.refiner_handoff == "image" and pipeline.pipe._vae_decode is not None and piperf._vae_encode is not None
+        if pipeline.refiner_handoff == "image" and not vae_route and not pipeline._warned_handoff:
+            import warnings
+            warnings.warn("refiner_handoff='image' needs vae_decode= on the base pipeline and vae_encode= on the refiner pipeline; handing the "
+                          "latents over directly instead (pass refiner_handoff='latent' to choose this route explicitly)", RuntimeWarning, stacklevel=2)
+            pipeline._warned_handoff = True
+        if vae_route:                # the reference's hand-over: decode, 8-bit image, re-encode (a posterior SAMPLE: global RNG, request order)
+            dec = _vae_in_batches(pipeline, pipeline.pipe._vae_decode, start, group, True)
+            decoded.update({i: dec[j:j + 1] for j, i in enumerate(ref)})
+            img8 = requantize(dec) if pipeline.vae is not None else to_8bit_image(dec)
+            start = _vae_in_batches(pipeline, piperf._vae_encode, img8, group, False)
+        rr = [RefineRequest(latents=start[j:j + 1], prompt_embeds=cs[i][keys[0]], pooled_prompt_embeds=cs[i][keys[1]], negative_prompt_embeds=cs[i][keys[2]],
+                            negative_pooled_prompt_embeds=cs[i][keys[3]], strength=float(refinement[i]), noise=cs[i].get("refiner_noise"))
+              for j, i in enumerate(ref)]
+        refined = refine_batch(piperf, rr, group=group, shard=shard)
+        oo.update({i: refined[j:j + 1] for j, i in enumerate(ref)})
+
+    # ---- subject consistency: every request's masks first, then pass k over the requests with more than k subjects ---------------------------------------
+    sub = [i for i in live if float(subject_strength[i]) > 0 and len(cs[i].get("subject_data") or []) > 0]
+    if sub:
+        keys = ("subject_prompt_embeds", "subject_pooled_prompt_embeds", "subject_negative_prompt_embeds", "subject_negative_pooled_prompt_embeds")
+        pairs = {}
+        for i in sub:
+            _need(cs[i], keys, "subject-consistency pass")
+            pairs[i] = pipeline._subject_mask_pairs(cs[i], cs[i]["subject_data"], oo[i])
+        for k in range(max(len(p) for p in pairs.values())):
+            now = [i for i in sub if len(pairs[i]) > k]
+            ir = [InpaintRequest(latents=oo[i], mask=pairs[i][k][0], subject_embed=pairs[i][k][1], prompt_embeds=cs[i][keys[0]], pooled_prompt_embeds=cs[i][keys[1]],
+                                 negative_prompt_embeds=cs[i][keys[2]], negative_pooled_prompt_embeds=cs[i][keys[3]], strength=float(subject_strength[i]),
+                                 noise=cs[i].get("subject_noise")) for i in now]
+            painted = inpaint_batch(pipeline.ip_adapter_xl_inpaint, ir, group=group, shard=shard)
+            oo.update({i: painted[j:j + 1] for j, i in enumerate(now)})
+
+    # ---- results; every latent is decoded once ----------------------------------------------------------------------------------------------------------
+    shown_nr, shown_oo = dict(non_refined), dict(oo)
+    if output_type != "latent":
+        post = pipeline.pipe.image_processor.postprocess
+        want = [(i, False) for i in live if i not in decoded] + [(i, True) for i in live if oo[i] is not non_refined[i]]
+        if want:
+            dec = _vae_in_batches(pipeline, pipeline.pipe._vae_decode, torch.cat([(oo if final else non_refined)[i] for i, final in want], dim=0), group, True)
+        imgs = {key: dec[j:j + 1] for j, key in enumerate(want)}
+        for i in live:
+            shown_nr[i] = post(decoded[i] if i in decoded else imgs[(i, False)], output_type=output_type)
+            shown_oo[i] = shown_nr[i] if oo[i] is non_refined[i] else post(imgs[(i, True)], output_type=output_type)
+    for i in live:
+        msg = "SUCCESS!" if not debug else dict(output_caption=cs[i]["caption"], latent_inv=latent_inv[row[i]:row[i] + 1], latent_la=latent_la[i])
+        results[i] = (shown_nr[i], shown_oo[i], msg)
+    return results

@@ -57,7 +57,7 @@ hipError_t ia2p_launch_concat(const half_t* a, int lda, int Ca, const half_t* b,
 hipError_t ia2p_launch_ddim_step(const half_t* x, const half_t* eps_u, const half_t* eps_c, float g, float c_x, float c_e,
                                  half_t* out, half_t* out2, long n, hipStream_t s, const float* coef = nullptr, long per = 1);
 hipError_t ia2p_launch_mask_blend(const half_t* x, const half_t* init, const half_t* noise, const half_t* mask, float c0, float c1,
-                                  half_t* out, half_t* out2, int B, int C, long HW, hipStream_t s);
+                                  half_t* out, half_t* out2, int B, int C, long HW, hipStream_t s, const float* coef = nullptr);
 hipError_t ia2p_launch_cat_rows(const half_t* a, int Ka, const half_t* b, int Kb, const half_t* bias_a, const half_t* bias_b, half_t* dst, half_t* bias_dst, int rows, hipStream_t s);
 hipError_t ia2p_launch_fold_ln(const half_t* W, const half_t* gamma, const half_t* beta, const half_t* bias, half_t* Wf, float* cs, float* lb,
                                int N, int K, hipStream_t s);

@@ -323,10 +323,13 @@ __global__ void prior_step_kernel(const float* s, const half_t* o_c, const half_
 // out = (1 - m) * (c0 * init + c1 * noise) + m * x, m = mask[b, 0, y, x] shared by the C channels: the per-step latent blend of
 // the inpainting loop (diffusers StableDiffusionXLInpaintPipeline, 4-channel UNet branch: known region re-noised to the next
 // timestep with DDIM add_noise, c0 = sqrt(abar), c1 = sqrt(1 - abar); c0 = 1, c1 = 0 after the last step). out2 optional.
+// coef (optional, device [B][2] = {c0, c1} per batch element): requests at their own step of their own schedule share one launch (a finished one carries
+// {1, 0}: with a {0, 1} mask it gets its x / init back bit for bit); null: the scalars for all. Same arithmetic either way.
 __global__ void mask_blend_kernel(const half_t* x, const half_t* init, const half_t* noise, const half_t* mask, float c0, float c1,
-                                  half_t* out, half_t* out2, int C, long HW, long n) {
+                                  half_t* out, half_t* out2, int C, long HW, long n, const float* coef) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const long b = i / (C * HW), p = i % HW;
+    if (coef) { c0 = coef[2 * b]; c1 = coef[2 * b + 1]; }
     const float m = (float)mask[b * HW + p];
     const float keep = c0 * (float)init[i] + c1 * (float)noise[i];
     const half_t o = (half_t)((1.f - m) * keep + m * (float)x[i]);
@@ -670,9 +673,9 @@ hipError_t ia2p_launch_ddim_step(const half_t* x, const half_t* eps_u, const hal
   return hipGetLastError();
 }
 hipError_t ia2p_launch_mask_blend(const half_t* x, const half_t* init, const half_t* noise, const half_t* mask, float c0, float c1,
-                                  half_t* out, half_t* out2, int B, int C, long HW, hipStream_t s) {
+                                  half_t* out, half_t* out2, int B, int C, long HW, hipStream_t s, const float* coef) {
   const long n = (long)B * C * HW;
-  hipLaunchKernelGGL(mask_blend_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, x, init, noise, mask, c0, c1, out, out2, C, HW, n);
+  hipLaunchKernelGGL(mask_blend_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, x, init, noise, mask, c0, c1, out, out2, C, HW, n, coef);
   return hipGetLastError();
 }
 hipError_t ia2p_launch_prior_step(const float* smp, const half_t* o_c, const half_t* o_u, const float* noise, float g, float sqrt_a, float sqrt_b, float k0, float k1,

@@ -33,6 +33,17 @@ ia2p_status ia2p_mask_blend(void* stream, const void* x, const void* init, const
   return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "mask_blend");
 }
 
+// The same blend with per-request coefficients: coef (device, float [B][2]) = {c0, c1} of batch element b -- requests at their own step of their own
+// inpainting schedule share one launch; a request that is through carries {1, 0}.
+ia2p_status ia2p_mask_blend_v(void* stream, const void* x, const void* init, const void* noise, const void* mask, const float* coef,
+                              void* out, void* out2, int B, int C, int64_t HW) {
+  if (!x || !init || !noise || !mask || !coef || !out) return fail(nullptr, IA2P_ERR_INVALID, "mask_blend_v: null argument");
+  if (B < 1 || C < 1 || HW < 1) return fail(nullptr, IA2P_ERR_SHAPE, "mask_blend_v: B=%d C=%d HW=%lld must all be >= 1", B, C, (long long)HW);
+  hipError_t e = ia2p_launch_mask_blend((const half_t*)x, (const half_t*)init, (const half_t*)noise, (const half_t*)mask, 0.f, 0.f, (half_t*)out, (half_t*)out2,
+                                        B, C, (long)HW, (hipStream_t)stream, coef);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "mask_blend_v");
+}
+
 ia2p_status ia2p_prior_step(void* stream, const float* sample, const void* out_cond, const void* out_uncond, const float* noise, float g, float sqrt_a,
                             float sqrt_b, float k0, float k1, float sigma, float* out, int64_t n) {
   if (!sample || !out_uncond || !out || n < 0 || !(sqrt_a > 0.f) || !(sqrt_b > 0.f)) return fail(nullptr, IA2P_ERR_INVALID, "prior_step: bad argument");

@@ -160,6 +160,13 @@ def subject_consistency_from_boxes(subject_data, latents, ip_adapter_xl_inpaint,
     `phrases`. The current result is decoded through `vae` once and set as the segmenter's image (:73); per subject the phrase loses '.' and "'s" (:86), its
     mask is `get_mask(..., d=40, b=20)` (:87) and the inpaint pass of `subject_consistency` follows. Boxes are scaled by the decoded image's longer side
     (the reference's literal 1024 is the side of the images it generates). -> (latents, masks as PIL images)"""
+    pairs, masks = subject_masks_from_boxes(subject_data, latents, segmenter, boxes, phrases, vae)
+    return subject_consistency(pairs, latents, ip_adapter_xl_inpaint, subject_strength, **generate_kwargs), masks
+
+
+def subject_masks_from_boxes(subject_data, latents, segmenter, boxes, phrases, vae):
+    """The mask half of `subject_consistency_from_boxes` (gdino/lib.py:69-87): every subject's mask from the ONE decode of `latents`, before any pass
+    repaints it. -> ([(mask tensor, subject embedding)] for `subject_consistency`, masks as PIL images)"""
     import numpy as np
     from .sam import get_mask
     if segmenter is None:
@@ -172,5 +179,4 @@ def subject_consistency_from_boxes(subject_data, latents, ip_adapter_xl_inpaint,
     a = ((x.float() / 2 + 0.5).clamp(0, 1) * 255.0).round().to(torch.uint8)[0].permute(1, 2, 0).cpu().numpy()
     segmenter.set_image(np.ascontiguousarray(a))
     masks = [get_mask(ph.replace(".", "").replace("'s", ""), boxes, phrases, segmenter, i=0, d=40, b=20, size=max(a.shape[0], a.shape[1])) for ph, _ in subject_data]
-    pairs = [(torch.from_numpy(np.array(m)), emb) for m, (_, emb) in zip(masks, subject_data)]
-    return subject_consistency(pairs, latents, ip_adapter_xl_inpaint, subject_strength, **generate_kwargs), masks
+    return [(torch.from_numpy(np.array(m)), emb) for m, (_, emb) in zip(masks, subject_data)], masks

@@ -336,22 +336,110 @@ class InstructAny2PixPipeline:
     def _subjects_from_phrases(self, c, subject_data, latents, subject_strength, kw):
         """the subject-consistency pass for subjects named by phrase: boxes from c["subject_boxes"] = (boxes, phrases) or from the detector on the decoded
         result (prompt: the phrases joined by '. ', gdino/lib.py:70), masks from the segmenter"""
+        boxes, phrases = self._subject_boxes(c, subject_data, latents)
+        out, self.subject_masks = subject_consistency_from_boxes(subject_data, latents, self.ip_adapter_xl_inpaint, self.sam, boxes, phrases, self.vae,
+                                                                 subject_strength, **kw)
+        return out
+
+    def _subject_boxes(self, c, subject_data, latents):
+        """(boxes, phrases) for subjects named by phrase: the conditioner's, else the detector's on the decoded `latents`"""
         if self.sam is None:
             raise ValueError("subject_data names subjects by phrase: build the pipeline with segmenter=<HipSamPredictor> (or pass subject_strength=0)")
         if self.vae is None:
             raise ValueError("subject_data names subjects by phrase: build the pipeline with vae=<HipAutoencoderKL> (the segmenter sees the decoded image)")
         if c.get("subject_boxes") is not None:
-            boxes, phrases = c["subject_boxes"]
-        elif self.gdino is not None:
+            return c["subject_boxes"]
+        if self.gdino is not None:
             x = self.vae.decode_from_latents(latents)[:1]
             img = ((x.float() / 2 + 0.5).clamp(0, 1) * 255.0).round().to(torch.uint8)[0].permute(1, 2, 0).cpu().numpy()
-            boxes, phrases = self.gdino(img, ". ".join(k for k, _ in subject_data))
-        else:
-            raise KeyError("subject_data names subjects by phrase: the conditioner returned no 'subject_boxes' and the pipeline has no detector= "
-                           "(pass subject_strength=0 to skip the subject-consistency pass)")
-        out, self.subject_masks = subject_consistency_from_boxes(subject_data, latents, self.ip_adapter_xl_inpaint, self.sam, boxes, phrases, self.vae,
-                                                                 subject_strength, **kw)
-        return out
+            return self.gdino(img, ". ".join(k for k, _ in subject_data))
+        raise KeyError("subject_data names subjects by phrase: the conditioner returned no 'subject_boxes' and the pipeline has no detector= "
+                       "(pass subject_strength=0 to skip the subject-consistency pass)")
+
+    def _subject_mask_pairs(self, c, subject_data, latents):
+        """[(mask, subject embedding)] of one request, all masks taken before any pass repaints `latents`: the conditioner's own masks, or the
+        phrase -> box -> SAM path of `_subjects_from_phrases` (the PIL masks are kept in `self.subject_masks`, as there)"""
+        from .inpaint import subject_masks_from_boxes
+        by_phrase = [isinstance(k, str) for k, _ in subject_data]
+        if any(by_phrase) and not all(by_phrase):
+            raise ValueError("subject_data mixes (mask, embedding) and (phrase, embedding) entries: give one kind")
+        if not all(by_phrase):
+            return list(subject_data)
+        boxes, phrases = self._subject_boxes(c, subject_data, latents)
+        pairs, self.subject_masks = subject_masks_from_boxes(subject_data, latents, self.sam, boxes, phrases, self.vae)
+        return pairs
+
+    # ---- N whole requests: conditioning for all, then every stage batched (batch.py) -------------------------------------------------------------
+    def _conditions_for_batch(self, insts, mm_datas):
+        """one conditioning dict per request, as `__call__` gets it from the conditioner or from `_condition_from_llm`. With an LLM: ONE
+        `forward_llm_batch` call, the inversion prompt '' encoded once, the other prompts in one `encode_prompt` call per text-encoder role. A request
+        whose LLM output has no `<im_gen>` comes back as dict(image_embeds=None, caption=...)."""
+        if self.conditioner is not None:
+            cs = [self.conditioner(inst, mm, use_cache=False) for inst, mm in zip(insts, mm_datas)]
+            self.cache = cs[-1]
+            return cs
+        if self.any2pix_lm is None:
+            raise NotImplementedError("edit_batch needs the pipeline built with conditioner=<callable> or with llm= / llm_tokenizer= / text_encoder=")
+        if self._text_encoder is None:
+            raise ValueError("a pipeline built with llm= needs text_encoder=<encode_prompt callable> for the denoise stages")
+        cs = []
+        for mm, (image_embeds, base_embed, caption, base_img_path, extra_data) in zip(mm_datas, self.forward_llm_batch(insts, mm_datas)):
+            c = dict(image_embeds=image_embeds, base_embed=base_embed, caption=caption, base_img_path=base_img_path, extra_data=extra_data)
+            if image_embeds is not None:
+                c["image_embeds"], c["base_embed"] = image_embeds.reshape(1, -1), base_embed.reshape(1, -1)
+                for e in mm:
+                    if e.get("fname") == base_img_path and e.get("image") is not None:
+                        c["base_image"] = e["image"]
+                if extra_data is not None and len(extra_data.get("extra_idx", [])) > 0:
+                    c["subject_data"] = [(k, v) for (k, v, i) in zip(extra_data["all_objs"], extra_data["extra_embeds"], extra_data["extra_idx"])
+                                         if mm[int(i)]["type"] == "image"]
+            cs.append(c)
+        live = [c for c in cs if c["image_embeds"] is not None]
+        if not live:
+            return cs
+        te, row = self._text_encoder, lambda t, j: t[j:j + 1]
+        ipe, _, ipp, _ = te(prompt="", do_classifier_free_guidance=False)
+        pe, ne, pp, npl = te(prompt=["best quality, high quality" + c["caption"] for c in live], negative_prompt=[""] * len(live), do_classifier_free_guidance=True)
+        for j, c in enumerate(live):
+            c.update(prompt_embeds=row(pe, j), pooled_prompt_embeds=row(pp, j), negative_prompt_embeds=row(ne, j), negative_pooled_prompt_embeds=row(npl, j),
+                     inv_prompt_embeds=ipe, inv_pooled_prompt_embeds=ipp)
+        if any("subject_data" in c for c in live):          # the inpaint pass runs IPAdapterXL.generate without a prompt: its defaults, the same for every request
+            spe, sne, spp, snp = te(prompt="best quality, high quality", negative_prompt="monochrome, lowres, bad anatomy, worst quality, low quality",
+                                    do_classifier_free_guidance=True)
+            for c in live:
+                if "subject_data" in c:
+                    c.update(subject_prompt_embeds=spe, subject_pooled_prompt_embeds=spp, subject_negative_prompt_embeds=sne, subject_negative_pooled_prompt_embeds=snp)
+        if self._refiner_text_encoder is not None:
+            rpe, rne, rpp, rnp = self._refiner_text_encoder(prompt=[c["caption"] + ",high quality,well-formed,award-winning" for c in live],
+                                                            negative_prompt=[""] * len(live), do_classifier_free_guidance=True)
+            for j, c in enumerate(live):
+                c.update(refiner_prompt_embeds=row(rpe, j), refiner_pooled_prompt_embeds=row(rpp, j), refiner_negative_prompt_embeds=row(rne, j),
+                         refiner_negative_pooled_prompt_embeds=row(rnp, j))
+        return cs
+
+    def edit_batch(self, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
+                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True):
+        """`__call__` for N instructions on N images -> the list of its `(non_refined, oo, msg)` tuples, in request order. Every knob of `__call__` is a
+        scalar (for all requests) or a list of N (`h`: one triple or N triples). `group` requests share one launch sequence in every loop.
+
+        Conditioning: the `conditioner` per request, or ONE `forward_llm_batch` call and the text encoders over the list of prompts; a request whose
+        LLM output has no `<im_gen>` gets `(None, None, "FAILED: ...")` and the others go on. The prior runs per request. A conditioner may add
+        `polar_noise` (the mixing noise of `denoise`) next to `refiner_noise` / `subject_noise`.
+        Stages: base images encoded in batches -> `denoise_batch` -> for the requests with `refinement > 0` the refiner hand-off as configured
+        (`refiner_handoff="image"`: batched decode, `requantize`, batched encode) and `batch.refine_batch` -> for `subject_strength > 0` every request's
+        masks first (its own masks, or phrase -> box -> SAM), then inpaint pass k batches the requests with more than k subjects (`batch.inpaint_batch`;
+        the subjects of one request stay sequential, as in the reference) -> one decode per latent for `output_type != "latent"`.
+        Refused: `cfg <= 1` (no guidance in the reference: use `__call__`), mixed latent sizes, `group` outside 1..8, a strength that leaves no step,
+        `refinement > 0` on a pipeline without a refiner (where `__call__` skips the pass silently).
+
+        RNG rule: every stage draws from the global CPU generator in REQUEST order -- the VAE posterior samples of the base images, the polar-mixing
+        noise, the posterior samples of the refiner hand-off, the refiner noise, the inpaint noise of every pass -- where N serial calls interleave the
+        stages per request. A seeded `edit_batch` is therefore reproducible, and equals N serial calls only when the noises are supplied.
+        Sharding: as `denoise_batch` -- with a process group up (and `shard`), each of the three loops runs a contiguous shard of its requests per rank
+        and all-gathers the result in request order; the stages around them (conditioning, VAE, masks) run on every rank, which must be seeded alike."""
+        from .batch import edit_batch
+        return edit_batch(self, insts, mm_datas, alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
+                          subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard)
 
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,

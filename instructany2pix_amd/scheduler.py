@@ -105,6 +105,21 @@ def mask_blend(x, init, noise, mask, c0, c1, out, out2=None):
     return out
 
 
+def mask_blend_v(x, init, noise, mask, coef, out, out2=None):
+    """The same blend with per-request coefficients (ia2p_mask_blend_v): coef = float32 device tensor [B, 2] = (c0, c1) of every batch element of
+    x [B, C, h, w]; requests at their own step of their own inpainting schedule share one launch. A request that is through carries (1, 0): over a
+    {0, 1} mask (`inpaint.prepare_mask`) it keeps x where the mask is 1 and gets init where it is 0, bit for bit."""
+    B, Cc, h, w = x.shape
+    for t in (x, init, noise, mask, out):
+        assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous(), "latents and mask must be contiguous fp16 device tensors"
+    assert out2 is None or (out2.dtype == torch.float16 and out2.is_cuda and out2.is_contiguous() and out2.shape == x.shape)
+    assert coef.dtype == torch.float32 and coef.is_cuda and coef.is_contiguous() and tuple(coef.shape) == (B, 2)
+    assert init.shape == x.shape and noise.shape == x.shape and out.shape == x.shape and tuple(mask.shape) == (B, 1, h, w)
+    _ffi.check(_ffi.lib().ia2p_mask_blend_v(_ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(init), _ffi.ptr(noise), _ffi.ptr(mask), _ffi.ptr(coef),
+                                            _ffi.ptr(out), _ffi.ptr(out2), B, Cc, h * w))
+    return out
+
+
 def fused_update(x, eps_u, eps_c, guidance, c_x, c_e, out, out2=None):
     """out = c_x*x + c_e*(eps_u + g*(eps_c - eps_u)) on the current stream (ia2p_ddim_step)."""
     for t in (x, eps_u, out):

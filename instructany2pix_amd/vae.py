@@ -63,6 +63,14 @@ class HipAutoencoderKL(_ffi.Executor):
     def _workspace(self, B, h, w, decode):
         return self.workspace(self._lib.ia2p_vae_workspace_bytes(self._h, B, h, w, int(decode)))
 
+    def max_batch(self, h: int, w: int, decode: bool) -> int:
+        """The largest B one encode / decode of h x w latents takes. The executor's kernels address an operand with a 31-bit byte offset and refuse a
+        larger one (include/ia2p.h, "Operand size"); the largest operand is the widest full-resolution activation, [B H W, C] fp16: block_out_channels[0]
+        channels behind the encoder's conv_in, block_out_channels[1] entering the decoder's last block (SDXL VAE at 1024 x 1024: 7 and 3)."""
+        boc = self._cfg.block_out_channels
+        ch = boc[min(1, len(boc) - 1)] if decode else boc[0]
+        return max(1, (0x7ffffe00 - 1) // (h * self._factor * w * self._factor * ch * 2))
+
     @torch.no_grad()
     def encode(self, image: torch.Tensor, return_dict: bool = True):
         B, c, H, W = image.shape

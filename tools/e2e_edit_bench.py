@@ -14,7 +14,17 @@ Prints per-stage wall times (stream-synchronised) after one warm-up request.
 --sampler device (the switch of tools/llm_decode_bench.py; also spelled --llm-sampler) draws the token on the device (`HipInstructAny2PixLM(sampler="device")`): the sampler kernel runs on every step's logits row and the
 script then overwrites the id in device memory (one fill launch per step, which the product does not have), so the next decode step still reads it there.
 
-    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4] [--sampler host|device] [--top-p P] [--imagebind]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)"""
+    python tools/e2e_edit_bench.py [--llm-bits 4] [--llm-quant-type fp4|nf4] [--sampler host|device] [--top-p P] [--imagebind]      (4: the LLM loaded as the reference loads it, `load_in_4bit`)
+
+--batch 1,4,8 measures `InstructAny2PixPipeline.edit_batch` against the serial loop instead: for each N, in this one process, N serial `__call__`s and one
+`edit_batch` of the same N requests (groups of min(N, 8)) alternate --reps times after both have run once untimed (every shape warm); times are a host clock
+around a device synchronise. Printed per N: per-stage ms of both (median over the repeats), total ms per image with its min..max over the repeats, images/s.
+What a request carries into the timed region is what the LLM and the text encoders leave behind (`forward_llm_batch` and `encode_prompt` are measured by
+tools/llm_decode_bench.py and the single-request mode): a conditioner hands every request its seeded embeddings, its prompt embeddings (encoded once, before
+the clock, by the full-size text encoders) and its own 1024 x 1024 PIL image; the LLM is not built. Timed: image in, VAE encode, embedding prior, inversion,
+polar mixing, guided sampling, the refiner hand-over (decode, 8-bit, encode), the refiner pass, VAE decode, image out.
+
+    python tools/e2e_edit_bench.py --batch 1,4,8 [--reps 3] [--steps 25] [--refinement 0.5]"""
 import argparse
 import os
 import sys
@@ -44,7 +54,12 @@ _ap.add_argument("--llm-quant-type", default="fp4", choices=("fp4", "nf4"))
 _ap.add_argument("--sampler", "--llm-sampler", dest="llm_sampler", default="host", choices=("host", "device"))
 _ap.add_argument("--top-p", type=float, default=None, help="nucleus of the LLM's sampler, as a checkpoint's generation_config.json would set it (default: none, top_p = 1)")
 _ap.add_argument("--imagebind", action="store_true", help="encode the mm_data entries' files with the HIP ImageBind towers instead of seeded vectors")
+_ap.add_argument("--batch", default=None, help="comma-separated request counts: compare edit_batch with the serial loop (see the module docstring)")
+_ap.add_argument("--reps", type=int, default=3)
+_ap.add_argument("--steps", type=int, default=25)
+_ap.add_argument("--refinement", type=float, default=0.5)
 ARGS = _ap.parse_args()
+BATCHES = [int(n) for n in ARGS.batch.split(",")] if ARGS.batch else []
 DEV = "cuda:0"
 PX = int(os.environ.get("PX", 1024))
 t_all = time.perf_counter()
@@ -63,13 +78,17 @@ specs = ip_adapter_specs(bcfg, 1024)
 ck = {"image_proj": synthetic_state_dict(specs["image_proj"], seed=7), "ip_adapter": synthetic_state_dict(specs["ip_adapter"], seed=7)}
 lcfg = vicuna_7b(32000 + len(ADDED_TOKENS))
 ltok = StubLlamaTokenizer(32000)
-lm = llm_mod.HipInstructAny2PixLM(lcfg, DEV, max_positions=512, load_in_4bit=ARGS.llm_bits == 4, bnb_4bit_quant_type=ARGS.llm_quant_type,
-                                  sampler=ARGS.llm_sampler)
-lm.load_state_dict(iter_synthetic(llm_param_specs(lcfg), 9, DEV, torch.float16))
-if ARGS.top_p is not None:      # forward_llm passes no top_p: it reaches `generate` the way a loaded generation config does
-    lm.load_generation_config({"top_p": ARGS.top_p})
-print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior, LLM with {lm.weight_bits}-bit "
-      f"projections: arena {lm.arena.numel() / 1e9:.2f} GB)", flush=True)
+lm = None
+if not BATCHES:
+    lm = llm_mod.HipInstructAny2PixLM(lcfg, DEV, max_positions=512, load_in_4bit=ARGS.llm_bits == 4, bnb_4bit_quant_type=ARGS.llm_quant_type,
+                                      sampler=ARGS.llm_sampler)
+    lm.load_state_dict(iter_synthetic(llm_param_specs(lcfg), 9, DEV, torch.float16))
+    if ARGS.top_p is not None:      # forward_llm passes no top_p: it reaches `generate` the way a loaded generation config does
+        lm.load_generation_config({"top_p": ARGS.top_p})
+    print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior, LLM with {lm.weight_bits}-bit "
+          f"projections: arena {lm.arena.numel() / 1e9:.2f} GB)", flush=True)
+else:
+    print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, refiner UNet, VAE, CLIP-L, bigG, prior; no LLM in --batch mode)", flush=True)
 
 stages = {}
 
@@ -95,7 +114,7 @@ def scripted_sample_next(logits, *a, **k):
 
 
 llm_mod.sample_next = scripted_sample_next
-_sample_tokens = lm.sample_tokens
+_sample_tokens = lm.sample_tokens if lm is not None else None
 
 
 def scripted_sample_tokens(logits, *a, **k):
@@ -103,7 +122,8 @@ def scripted_sample_tokens(logits, *a, **k):
     return out.fill_(next(_script))                     # (stream-ordered behind it: the look-ahead decode reads the scripted id)
 
 
-lm.sample_tokens = scripted_sample_tokens
+if lm is not None:
+    lm.sample_tokens = scripted_sample_tokens
 mm_data = [{"type": "image", "fname": "base.png", "image": image, "embed": torch.randn(1024, generator=g)},
            {"type": "image", "fname": "style.png", "image": image, "embed": torch.randn(1024, generator=g)}]      # (either may be chosen as the base)
 imb = None
@@ -121,7 +141,7 @@ pipe = InstructAny2PixPipeline(unet=base, ip_ckpt=ck, device=DEV, clip_embedding
                                llm=lm, llm_tokenizer=ltok, imagebind=imb,
                                text_encoder=lambda **k: timed("encode_prompt(base, inversion '')", lambda: enc.encode_prompt(**k)),
                                refiner_text_encoder=lambda **k: timed("encode_prompt(refiner)", lambda: enc_ref.encode_prompt(**k)))
-if os.environ.get("TUNE", "1") == "1":      # measure kernel plans for the three UNet shapes of a request (what bench.py does for its shape)
+if os.environ.get("TUNE", "0" if BATCHES else "1") == "1":      # measure kernel plans for the three UNet shapes of a request (what bench.py does for its shape)
     t0 = time.perf_counter()
     h = PX // 8
     for net, B, L, cd, pd, nid in ((base, 1, 77, bcfg.cross_attention_dim, bcfg.pooled_dim, 6), (base, 2, 81, bcfg.cross_attention_dim, bcfg.pooled_dim, 6),
@@ -137,22 +157,24 @@ def _wrap(obj, name, label):
     setattr(obj, name, lambda *a, **k: timed(label, lambda: fn(*a, **k)))
 
 
-_wrap(pipe.pipe_inversion, "inverse", "inversion loop (25 x B=1)")
+LABEL = (lambda long, short: short) if BATCHES else (lambda long, short: long)      # --batch: one label per stage for the serial and the batched side
+_wrap(pipe.pipe_inversion, "inverse", LABEL("inversion loop (25 x B=1)", "inversion loop"))
 _wrap(pipe.pipe_inversion.image_processor, "preprocess", "image_in")
 _wrap(pipe.pipe_inversion, "_vae_encode", "vae_encode")
-_wrap(pipe.pipe, "_vae_decode", "vae_decode (hand-over + 2 outputs)")
+_wrap(pipe.pipe, "_vae_decode", LABEL("vae_decode (hand-over + 2 outputs)", "vae_decode"))
 _wrap(pipe.pipe.image_processor, "postprocess", "image_out")
-_wrap(pipe.ip_adapter_xl, "generate", "guided sampling loop (25 x B_eff=2, incl. image-token projection)")
+_wrap(pipe.ip_adapter_xl, "generate", LABEL("guided sampling loop (25 x B_eff=2, incl. image-token projection)", "guided sampling loop"))
 if imb is not None:
     _wrap(pipe, "_modality_embeds", "ImageBind (2 PNG files: load, transform, vision tower; inside forward_llm)")
-_wrap(pipe, "forward_llm", f"LLM (forward_llm: prefill + 100 tokens + predictor heads, {ARGS.llm_sampler} sampler)")
+if lm is not None:
+    _wrap(pipe, "forward_llm", f"LLM (forward_llm: prefill + 100 tokens + predictor heads, {ARGS.llm_sampler} sampler)")
 if getattr(pipe, "model", None) is not None:
     _wrap(pipe.model, "generate_diffusion", "embedding prior")
 _piperf_call = pipe.piperf.__call__
 pipe.piperf = type("TimedRefiner", (), {"__call__": lambda self, *a, **k: timed("refiner pass", lambda: _piperf_call(*a, **k)),
                                         "__getattr__": lambda self, n: getattr(_piperf_call.__self__, n)})()
 _wrap(pipe.piperf, "_vae_encode", "vae_encode (refiner hand-over)")
-for rnd in range(2):            # request 0 warms up (workspaces, kernel plans from the cost model), request 1 is reported
+for rnd in range(0 if BATCHES else 2):            # request 0 warms up (workspaces, kernel plans from the cost model), request 1 is reported
     stages.clear()
     torch.manual_seed(3)
     _script = iter(SCRIPT)
@@ -163,3 +185,62 @@ for rnd in range(2):            # request 0 warms up (workspaces, kernel plans f
     outer = sum(v for k, v in stages.items() if not k.startswith("ImageBind"))      # (the ImageBind stage is part of forward_llm's)
     print(f"request {rnd}: {total:.0f} ms total; stages (ms): " + ", ".join(f"{k} {v:.1f}" for k, v in stages.items())
           + f", host glue / the rest {total - outer:.0f}", flush=True)
+
+
+# ---- --batch: N serial calls against one edit_batch of the same requests ---------------------------------------------------------------------------------
+if BATCHES:
+    import statistics
+    import instructany2pix_amd.batch as batch_mod
+    for _name, _label in (("invert_batch", "inversion loop"), ("sample_batch", "guided sampling loop"), ("refine_batch", "refiner pass")):
+        _wrap(batch_mod, _name, _label)
+    NMAX = max(BATCHES)
+    rng = np.random.default_rng(2)
+    images = [PIL.Image.fromarray(rng.integers(0, 256, size=(PX, PX, 3), dtype=np.uint8)) for _ in range(NMAX)]
+    insts = [f"request {i}: turn the fox blue" for i in range(NMAX)]
+    conds = {}
+    ipe, _, ipp, _ = enc.encode_prompt(prompt="", do_classifier_free_guidance=False)
+    for i, inst in enumerate(insts):            # what forward_llm + encode_prompt leave behind, made once, before the clock
+        cap = f" a blue fox, variation {i}"
+        pe, ne, pp, npl = enc.encode_prompt(prompt="best quality, high quality" + cap, negative_prompt="", do_classifier_free_guidance=True)
+        rpe, rne, rpp, rnp = enc_ref.encode_prompt(prompt=cap + ",high quality,well-formed,award-winning", negative_prompt="", do_classifier_free_guidance=True)
+        conds[inst] = dict(image_embeds=torch.randn(1, 1024, generator=g), base_embed=torch.randn(1, 1024, generator=g), caption=cap, base_image=images[i],
+                           prompt_embeds=pe, pooled_prompt_embeds=pp, negative_prompt_embeds=ne, negative_pooled_prompt_embeds=npl, inv_prompt_embeds=ipe,
+                           inv_pooled_prompt_embeds=ipp, refiner_prompt_embeds=rpe, refiner_pooled_prompt_embeds=rpp, refiner_negative_prompt_embeds=rne,
+                           refiner_negative_pooled_prompt_embeds=rnp)
+    pipe.conditioner = lambda inst, mm, use_cache=False: conds[inst]
+    knobs = dict(num_inference_steps=ARGS.steps, cfg=10, refinement=ARGS.refinement, output_type="pil")
+
+    def serial(n):
+        return [pipe(inst, [], **knobs) for inst in insts[:n]]
+
+    def batched(n):
+        return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), **knobs)
+
+    def run(fn, n):
+        stages.clear()
+        torch.manual_seed(3)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = fn(n)
+        torch.cuda.synchronize(); total = (time.perf_counter() - t0) * 1e3
+        assert len(out) == n and all(msg == "SUCCESS!" and oo[0].size == (PX, PX) for _, oo, msg in out)
+        return total, dict(stages)
+
+    print(f"# {PX} x {PX}, {ARGS.steps} steps, cfg 10, refinement {ARGS.refinement}, output_type pil; {ARGS.reps} alternating repeats after one untimed run of each; "
+          f"kernel plans: {'measured for the single-request shapes' if os.environ.get('TUNE', '0') == '1' else 'cost model'}", flush=True)
+    for n in BATCHES:
+        run(serial, n), run(batched, n)             # every shape warm: workspaces, plans
+        runs = {"serial": [], "edit_batch": []}
+        for _ in range(ARGS.reps):
+            runs["serial"].append(run(serial, n))
+            runs["edit_batch"].append(run(batched, n))
+        print(f"N = {n} (group {min(n, 8)}, B_eff = {2 * min(n, 8)} in the guided loops)", flush=True)
+        per_image = {}
+        for side, rr in runs.items():
+            tot = [t / n for t, _ in rr]
+            per_image[side] = statistics.median(tot)
+            names = list(rr[0][1])
+            st = {k: statistics.median(s_.get(k, 0.0) for _, s_ in rr) for k in names}
+            glue = per_image[side] * n - sum(st.values())
+            print(f"  {side:10s}: {per_image[side]:8.1f} ms / image (min {min(tot):.1f}, max {max(tot):.1f} over {ARGS.reps}), {1e3 / per_image[side]:.3f} images/s; "
+                  f"stages, ms per call of {n}: " + ", ".join(f"{k} {v:.1f}" for k, v in st.items()) + f", host glue / the rest {glue:.0f}", flush=True)
+        print(f"  per image, edit_batch / serial: {per_image['edit_batch'] / per_image['serial']:.3f}", flush=True)
