@@ -170,6 +170,38 @@ ia2p_status ia2p_mask_blend(void* stream, const void* x, const void* init, const
 ia2p_status ia2p_mask_blend_v(void* stream, const void* x, const void* init, const void* noise, const void* mask, const float* coef,
                               void* out, void* out2, int B, int C, int64_t HW);
 
+/* ---- Seeded noise: every normal draw of an edit request from the request's own stream ------------------------------------------------------------------
+ * THE NOISE RULE. A request has a 64-bit `seed`; each of its normal draws has a 32-bit `draw` id (table below). Element e of a draw is the FLAT index inside
+ * the request's own tensor (the batch is not counted), e < 2^34. Its value comes from block j = e >> 2:
+ *   (w0, w1, w2, w3) = Philox4x32-10 at counter (j, draw, 0, 1) under key (low half of seed, high half of seed).
+ *   The last counter word is a domain tag: the token sampler draws at counter (step, 0, 0, 0), so one seed serves both without ever sharing a block.
+ *   For pair p = (e & 3) >> 1:   u1 = ((w[2p] >> 8) + 1) * 2^-24   in (0, 1], exact in fp32
+ *                                u2 = (w[2p + 1] >> 8) * 2^-24     in [0, 1)
+ *                                r  = sqrt(-2 ln u1)
+ *                                z  = r * cospi(2 u2) for even e,  r * sinpi(2 u2) for odd e
+ *   The argument 2 u2 is exact, and |z| <= sqrt(48 ln 2) < 5.77. logf, sqrtf and sincospif at full accuracy (no native approximation), one fp32 product.
+ *   The value is fp32; an fp16 output is its round-to-nearest-even.
+ * A value depends on (seed, draw, e) ONLY: not on the batch, the row's place in a launch, the output pointer's alignment, the grid or the sub-range asked for.
+ * Draw ids of an edit request (instructany2pix_amd/noise.py): 0 base-image VAE posterior, 1 polar-mixing noise, 2 posterior of the refiner hand-off
+ * re-encode, 3 refiner start noise, 4 + k inpaint noise of subject pass k.
+ * seeds, draws (and alphas below): HOST arrays [B]. They travel by value in the kernel arguments, 8 rows per launch; a larger B goes in chunks of 8 rows, one launch
+ * each. No call copies anything to the device, allocates or waits. Every refusal is decided on the host before any launch: a null (or misaligned) pointer is
+ * IA2P_ERR_INVALID; B < 1, per < 1, a `first` that is negative or no multiple of 4, first + per > 2^34 are IA2P_ERR_SHAPE.
+ *
+ * randn_seeded: row b of out ([B, per] dense, fp32, or fp16 with out_is_f16 = 1; element-size alignment is enough) receives elements first .. first + per - 1
+ *   of stream (seeds[b], draws[b]). Ownership is by element index; 16-byte stores where a row starts on a 16-byte boundary, scalar stores elsewhere. */
+ia2p_status ia2p_randn_seeded(void* stream, void* out, int out_is_f16, int B, int64_t per, int64_t first, const uint64_t* seeds, const uint32_t* draws);
+/* the VAE posterior sample from a seeded draw (diffusers DiagonalGaussianDistribution.sample, then the scaling): moments fp16 [B, 2 C, HW] = means | log-variances
+ * as the encoder leaves them, out fp16 [B, C, HW]. With z the fp32 normal of element e = c HW + p:
+ *   x = fp16(fmaf(exp(0.5 * clamp(logvar, -30, 20)), z, mean));   out = fp16(x * scaling_factor)        (fp32 arithmetic, full-accuracy expf) */
+ia2p_status ia2p_posterior_sample_seeded(void* stream, const void* moments, void* out, int B, int C, int64_t HW, float scaling_factor, const uint64_t* seeds,
+                                         const uint32_t* draws);
+/* the reference's `polar_intrtpolate` (pipeline.py:295-300) per request on the device: x, y, out fp16 [B, per]; per request, with a = alphas[b] and b1 = 1 - a,
+ *   n0 = |x|, n1 = |y|, ll = a x + b1 y (kept in fp32), nl = |ll|, out = fp16(ll * ((a n0 + b1 n1) / nl)).
+ * The three sums of squares have ONE fixed association that depends on `per` alone, so a row's bits do not depend on B or on its place in the batch.
+ * nl = 0 gives the reference's non-finite result; it is not an error. The arithmetic is fp32: it is NOT the bit pattern of the reference's CPU fp16 tensor ops. */
+ia2p_status ia2p_polar_mix_v(void* stream, const void* x, const void* y, const float* alphas, void* out, int B, int64_t per);
+
 /* ---- per-operator entry points (unit tests, and hosts that keep their own module tree) ----------------------------- */
 /* Operand size: the linear-layer tiles (buffer-load staging), the halo-staged 3x3 convolution and the fused attention tiles address an operand (activations,
  * weights) with a 31-bit byte offset and REFUSE a matrix of 2 GiB or more with IA2P_ERR_HIP / invalid value; the gathered 3x3 convolution kernels use 64-bit

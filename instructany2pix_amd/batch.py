@@ -23,6 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import dist as D
+from . import noise as _noise
 from .ddim import get_add_time_ids
 from .scheduler import DDIMScheduler, fused_update_v
 
@@ -43,6 +44,7 @@ class EditRequest:
     cfg: float = 10.0
     scale: float = 1.0
     noise: Optional[torch.Tensor] = None       # polar-mixing noise (CPU fp16); None: drawn from the global RNG in request order
+    seed: Optional[int] = None                 # the request's own Philox stream (noise.py): without `noise`, draw DRAW_POLAR of it, made and mixed on the device
 
 
 def _coef_table(rows: Sequence[Sequence[tuple]], device) -> torch.Tensor:
@@ -163,7 +165,10 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
     """N independent edit requests through the hot segment, batched and (with an initialised process group) sharded over the ranks.
     Returns (sampled latents [N,4,h,w], inverted latents [N,4,h,w]) in request order on every rank.
     `group` requests share one launch sequence (B_eff = 2 * group under guidance): 4 is the headline shape; with a queue of requests 8 is 16 %
-    cheaper per image (2.05 vs 2.44 ms per image-step, profiles/r03j_two_stream_probe.txt) at twice the latency of a group."""
+    cheaper per image (2.05 vs 2.44 ms per image-step, profiles/r03j_two_stream_probe.txt) at twice the latency of a group.
+    A request with a `seed` (and no `noise`) takes its mixing noise from its own Philox stream (noise.py, draw DRAW_POLAR) and is mixed on the device
+    (`ia2p_polar_mix_v`: fp32, not the bits of the CPU fp16 mix): its inverted latents never leave the device, its result does not depend on the requests around
+    it, and no rank needs to be seeded alike for it. Requests without a seed draw and mix as ever, also next to seeded ones in one group."""
     from .pipeline import polar_intrtpolate
     N = len(requests)
     if N == 0:
@@ -185,7 +190,8 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
         raise ValueError(f"group={group}: a group is one launch sequence of 1..8 requests (B_eff = 2 * group <= 16 rows, the limit of the image-projection and "
                          f"embedding kernels)")
     # polar-mixing noise comes from the global CPU RNG in REQUEST order (what N sequential reference calls would draw), on every rank alike
-    noises = [r.noise if r.noise is not None else torch.randn(r.base_latents.shape, dtype=torch.float16) for r in requests]
+    # (a request with a seed and no noise draws nothing here: its noise is made on the device below, from its own stream)
+    noises = [r.noise if r.noise is not None else None if r.seed is not None else torch.randn(r.base_latents.shape, dtype=torch.float16) for r in requests]
     world, lo, hi = _shard(N, shard)
     unet, cfgs = pipeline.pipe.unet, pipeline.pipe.scheduler.config
     ipa = pipeline.ip_adapter_xl
@@ -199,8 +205,18 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
         inv_pool = cat([(r.inv_pooled_prompt_embeds if r.inv_pooled_prompt_embeds is not None else r.negative_pooled_prompt_embeds) for r in reqs])
         x0 = cat([r.base_latents for r in reqs])
         x_inv = invert_batch(unet, cfgs, x0, inv_ctx, inv_pool, steps)
-        x_inv_cpu = x_inv.cpu()                                                                 # pipeline.py:331
-        mixed = torch.cat([polar_intrtpolate(x_inv_cpu[i:i + 1], noises[g0 + i].to(x_inv_cpu.dtype), r.alpha) for i, r in enumerate(reqs)], dim=0)
+        own = [i for i in range(len(reqs)) if noises[g0 + i] is None]
+        if len(own) < len(reqs):
+            x_inv_cpu = x_inv.cpu()                                                             # pipeline.py:331
+        if not own:
+            mixed = torch.cat([polar_intrtpolate(x_inv_cpu[i:i + 1], noises[g0 + i].to(x_inv_cpu.dtype), r.alpha) for i, r in enumerate(reqs)], dim=0)
+        else:                            # seeded rows: noise and mix on the device, one launch each over those rows; the latents never leave it
+            z = _noise.randn_seeded([reqs[i].seed for i in own], _noise.DRAW_POLAR, x_inv.shape[1:], torch.float16, dev)
+            mixed = torch.empty_like(x_inv)
+            mixed[own] = _noise.polar_mix(x_inv[own] if len(own) < len(reqs) else x_inv, z, [float(reqs[i].alpha) for i in own])
+            for i, r in enumerate(reqs):
+                if noises[g0 + i] is not None:
+                    mixed[i:i + 1] = polar_intrtpolate(x_inv_cpu[i:i + 1], noises[g0 + i].to(x_inv_cpu.dtype), r.alpha).to(dev)
         ip, ip_un = ipa.get_image_embeds(clip_image_embeds=torch.stack([r.latent_la.reshape(-1) for r in reqs]), mode="global")
         cond_ctx = torch.cat([cat([r.prompt_embeds for r in reqs]).to(torch.float16), ip], dim=1)              # ip_adapter.py:341-342
         uncond_ctx = torch.cat([cat([r.negative_prompt_embeds for r in reqs]).to(torch.float16), ip_un], dim=1)
@@ -250,6 +266,7 @@ class RefineRequest:
     negative_pooled_prompt_embeds: torch.Tensor
     strength: float = 0.3
     noise: Optional[torch.Tensor] = None       # start noise; None: drawn from the global CPU RNG in request order
+    seed: Optional[int] = None                 # without `noise`: draw DRAW_REFINER of the request's own stream, on the device
 
 
 @dataclass
@@ -282,9 +299,18 @@ def refine_tables(scheduler_config, strengths: Sequence[float], num_inference_st
     return tb
 
 
-def _draw_noises(given: Sequence[Optional[torch.Tensor]], latents: Sequence[torch.Tensor]):
-    """missing noises from the global CPU RNG in REQUEST order (what the serial pipelines draw, one call after the other), on every rank alike"""
-    return [n if n is not None else torch.randn(x.shape, dtype=torch.float16) for n, x in zip(given, latents)]
+def _draw_noises(given: Sequence[Optional[torch.Tensor]], latents: Sequence[torch.Tensor], seeds: Optional[Sequence[Optional[int]]] = None, draws=None, device=None):
+    """missing noises from the global CPU RNG in REQUEST order (what the serial pipelines draw, one call after the other), on every rank alike.
+    A request with a seed (and no noise given) draws nothing from it: its noise is draw `draws[i]` of its own stream, made on `device` in one launch
+    for all such requests."""
+    seeds = [None] * len(given) if seeds is None else list(seeds)
+    out = [n if n is not None else None if s is not None else torch.randn(x.shape, dtype=torch.float16) for n, x, s in zip(given, latents, seeds)]
+    own = [i for i, n in enumerate(out) if n is None]
+    if own:
+        z = _noise.randn_seeded([seeds[i] for i in own], [draws[i] for i in own], latents[own[0]].shape[1:], torch.float16, device)
+        for j, i in enumerate(own):
+            out[i] = z[j:j + 1]
+    return out
 
 
 @torch.no_grad()
@@ -327,7 +353,7 @@ def refine_batch(piperf, requests: List[RefineRequest], group: int = 4, shard: b
     _check_loop_args(num_inference_steps, guidance_scale, "refine_batch")
     N = len(requests)
     refine_tables(piperf.scheduler.config, [r.strength for r in requests], num_inference_steps, guidance_scale)      # every request's refusal before any launch
-    noises = _draw_noises([r.noise for r in requests], [r.latents for r in requests])
+    noises = _draw_noises([r.noise for r in requests], [r.latents for r in requests], [r.seed for r in requests], [_noise.DRAW_REFINER] * N, piperf.unet.device)
     world, lo, hi = _shard(N, shard)
     outs = []
     for g0 in range(lo, hi, group):
@@ -351,6 +377,8 @@ class InpaintRequest:
     negative_pooled_prompt_embeds: torch.Tensor
     strength: float = 0.7
     noise: Optional[torch.Tensor] = None       # start and re-noising noise; None: drawn from the global CPU RNG in request order
+    seed: Optional[int] = None                 # without `noise`: draw `draw` of the request's own stream, on the device
+    draw: int = _noise.DRAW_INPAINT            # DRAW_INPAINT + k for subject pass k
 
 
 @dataclass
@@ -432,7 +460,7 @@ def inpaint_batch(ipa, requests: List[InpaintRequest], group: int = 4, shard: bo
     N = len(requests)
     cfgs = ipa.pipe.scheduler.config
     inpaint_tables(cfgs, [r.strength for r in requests], num_inference_steps, guidance_scale)                  # every request's refusal before any launch
-    noises = _draw_noises([r.noise for r in requests], [r.latents for r in requests])
+    noises = _draw_noises([r.noise for r in requests], [r.latents for r in requests], [r.seed for r in requests], [r.draw for r in requests], ipa.pipe.unet.device)
     world, lo, hi = _shard(N, shard)
     outs = []
     for g0 in range(lo, hi, group):
@@ -460,21 +488,24 @@ def _is_one_h(v) -> bool:
     return len(v) == 3 and not any(isinstance(x, (list, tuple)) or (torch.is_tensor(x) and x.ndim > 0) for x in v)
 
 
-def _vae_in_batches(pipeline, fn, t: torch.Tensor, group: int, decode: bool) -> torch.Tensor:
+def _vae_in_batches(pipeline, fn, t: torch.Tensor, group: int, decode: bool, seeds=None, draw: int = 0) -> torch.Tensor:
     """a VAE hook over [n, ...] in equal batches of at most `group` rows, and of no more than the attached VAE takes in one launch sequence at this size
-    (`HipAutoencoderKL.max_batch`: at 1024 x 1024 a decode takes 3 images, an encode 7)"""
+    (`HipAutoencoderKL.max_batch`: at 1024 x 1024 a decode takes 3 images, an encode 7). `seeds` (encode with an attached VAE; entries None allowed): row i's
+    posterior sample comes from draw `draw` of its own stream; a `vae_encode=` hook draws its own sample and sees no seed."""
     n, rows = t.shape[0], int(group)
     if pipeline.vae is not None:
         f = 1 if decode else pipeline.pipe.vae_scale_factor             # decode: latents in; encode: pixels in
         rows = min(rows, pipeline.vae.max_batch(t.shape[-2] // f, t.shape[-1] // f, decode))
     k = -(-n // rows)
     per = -(-n // k)
-    return torch.cat([fn(t[i:i + per]) for i in range(0, n, per)], dim=0)
+    if seeds is None or pipeline.vae is None or all(s is None for s in seeds):
+        return torch.cat([fn(t[i:i + per]) for i in range(0, n, per)], dim=0)
+    return torch.cat([fn(t[i:i + per], seeds=seeds[i:i + per], draw=draw) for i in range(0, n, per)], dim=0)
 
 
 @torch.no_grad()
 def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
-               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True):
+               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None):
     """`InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
     See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding)."""
     from .image_processor import OUTPUT_TYPES, requantize
@@ -491,6 +522,8 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     if output_type != "latent" and pipeline.vae is None:
         raise ValueError(f"output_type={output_type!r} needs the pipeline built with vae=<HipAutoencoderKL>")
     _check_group(group, "edit_batch")
+    seeds = _noise.resolve_seeds(seeds, N)
+    seeded = any(s is not None for s in seeds)
     alpha, norm, refinement = per_request(alpha, N, "alpha"), per_request(norm, N, "norm"), per_request(refinement, N, "refinement")
     steps, subject_strength = per_request(num_inference_steps, N, "num_inference_steps"), per_request(subject_strength, N, "subject_strength")
     cfg, scale, h = per_request(cfg, N, "cfg"), per_request(scale, N, "scale"), per_request(h, N, "h", _is_one_h)
@@ -511,7 +544,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
 
     # ---- conditioning: one LLM pass for all requests, or the conditioner per request; a request without <im_gen> is answered here -------------------------
     results: list = [None] * N
-    cs = pipeline._conditions_for_batch(insts, mm_datas)
+    cs = pipeline._conditions_for_batch(insts, mm_datas, seeds=seeds) if seeded else pipeline._conditions_for_batch(insts, mm_datas)
     for i, c in enumerate(cs):
         if c.get("image_embeds") is None:
             results[i] = (None, None, f"FAILED: the LLM produced no <im_gen>: {c.get('caption')!r}")
@@ -545,7 +578,8 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             if pipeline.vae is None:
                 raise ValueError("a base_image / base_img_path needs the pipeline built with vae=<HipAutoencoderKL>")
             imgs.append(pipeline.pipe_inversion.image_processor.preprocess(img))
-        enc = _vae_in_batches(pipeline, pipeline.pipe_inversion._vae_encode, torch.cat(imgs, dim=0), group, False)
+        enc = _vae_in_batches(pipeline, pipeline.pipe_inversion._vae_encode, torch.cat(imgs, dim=0), group, False,
+                              seeds=[seeds[i] for i in todo], draw=_noise.DRAW_BASE_POSTERIOR)
         base.update({i: enc[j:j + 1] for j, i in enumerate(todo)})
     _check_latents([base[i] for i in live], "edit_batch")
 
@@ -554,7 +588,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
                         pooled_prompt_embeds=cs[i]["pooled_prompt_embeds"], negative_prompt_embeds=cs[i]["negative_prompt_embeds"],
                         negative_pooled_prompt_embeds=cs[i]["negative_pooled_prompt_embeds"], inv_prompt_embeds=cs[i].get("inv_prompt_embeds"),
                         inv_pooled_prompt_embeds=cs[i].get("inv_pooled_prompt_embeds"), alpha=alpha[i], num_inference_steps=int(steps[i]), cfg=float(cfg[i]),
-                        scale=float(scale[i]), noise=cs[i].get("polar_noise")) for i in live]
+                        scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i]) for i in live]
     pipeline.pipe_inversion.unet = pipeline.pipe.unet
     images, latent_inv = denoise_batch(pipeline, reqs, group=group, shard=shard)
     row = {i: j for j, i in enumerate(live)}
@@ -580,9 +614,9 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             dec = _vae_in_batches(pipeline, pipeline.pipe._vae_decode, start, group, True)
             decoded.update({i: dec[j:j + 1] for j, i in enumerate(ref)})
             img8 = requantize(dec) if pipeline.vae is not None else to_8bit_image(dec)
-            start = _vae_in_batches(pipeline, piperf._vae_encode, img8, group, False)
+            start = _vae_in_batches(pipeline, piperf._vae_encode, img8, group, False, seeds=[seeds[i] for i in ref], draw=_noise.DRAW_HANDOFF_POSTERIOR)
         rr = [RefineRequest(latents=start[j:j + 1], prompt_embeds=cs[i][keys[0]], pooled_prompt_embeds=cs[i][keys[1]], negative_prompt_embeds=cs[i][keys[2]],
-                            negative_pooled_prompt_embeds=cs[i][keys[3]], strength=float(refinement[i]), noise=cs[i].get("refiner_noise"))
+                            negative_pooled_prompt_embeds=cs[i][keys[3]], strength=float(refinement[i]), noise=cs[i].get("refiner_noise"), seed=seeds[i])
               for j, i in enumerate(ref)]
         refined = refine_batch(piperf, rr, group=group, shard=shard)
         oo.update({i: refined[j:j + 1] for j, i in enumerate(ref)})
@@ -599,7 +633,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             now = [i for i in sub if len(pairs[i]) > k]
             ir = [InpaintRequest(latents=oo[i], mask=pairs[i][k][0], subject_embed=pairs[i][k][1], prompt_embeds=cs[i][keys[0]], pooled_prompt_embeds=cs[i][keys[1]],
                                  negative_prompt_embeds=cs[i][keys[2]], negative_pooled_prompt_embeds=cs[i][keys[3]], strength=float(subject_strength[i]),
-                                 noise=cs[i].get("subject_noise")) for i in now]
+                                 noise=cs[i].get("subject_noise"), seed=seeds[i], draw=_noise.inpaint_draw(k)) for i in now]
             painted = inpaint_batch(pipeline.ip_adapter_xl_inpaint, ir, group=group, shard=shard)
             oo.update({i: painted[j:j + 1] for j, i in enumerate(now)})
 
@@ -615,6 +649,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             shown_nr[i] = post(decoded[i] if i in decoded else imgs[(i, False)], output_type=output_type)
             shown_oo[i] = shown_nr[i] if oo[i] is non_refined[i] else post(imgs[(i, True)], output_type=output_type)
     for i in live:
-        msg = "SUCCESS!" if not debug else dict(output_caption=cs[i]["caption"], latent_inv=latent_inv[row[i]:row[i] + 1], latent_la=latent_la[i])
+        msg = "SUCCESS!" if not debug else dict(output_caption=cs[i]["caption"], latent_inv=latent_inv[row[i]:row[i] + 1], latent_la=latent_la[i],
+                                                **({} if seeds[i] is None else {"seed": seeds[i]}))
         results[i] = (shown_nr[i], shown_oo[i], msg)
     return results

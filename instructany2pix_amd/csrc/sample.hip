@@ -31,6 +31,7 @@
 // terms themselves (one subtraction, one expf), which the "+ 2" of the tests' band 2 * (d + 2) * 2^-24 stands for. An entry whose q is 0 (a term below
 // 2^-43 of the largest) counts as weightless in the selection and is never in a nucleus. Passes 5 and 6 then run as they do without top-p, on the raised key.
 #include "engine_rt.h"
+#include "philox.h"
 
 #include <climits>
 #include <cmath>
@@ -54,15 +55,9 @@ struct SampleArgs {
 
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"): word 0 of the block at counter (step, 0, 0, 0) under key (seed low, seed high)
 __device__ __forceinline__ uint32_t philox_word0(uint64_t seed, uint32_t step) {
-  uint32_t c0 = step, c1 = 0, c2 = 0, c3 = 0, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0, hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c0;
+  uint32_t w[4];
+  philox4x32_10(step, 0, 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+  return w[0];
 }
 
 // four values at indices i .. i + 3 of the row (i a multiple of 4); entries at or past V read as 0 and are skipped by index

@@ -84,15 +84,19 @@ class _PipelineBase:
         if self.vae is not None and output_type not in OUTPUT_TYPES:
             raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
 
-    def _image_latents(self, image, height=None, width=None):
+    def _image_latents(self, image, height=None, width=None, seeds=None, draw=0):
         """`image=` -> scaled latents: with a VAE attached, `image_processor.preprocess` (PIL, uint8 arrays, [0, 1] floats, [-1, 1] tensors;
-        4-channel tensors are latents already) then the posterior sample; with hooks only, the hook gets `image` as it is."""
+        4-channel tensors are latents already) then the posterior sample; with hooks only, the hook gets `image` as it is.
+        `seeds` (one per image) / `draw`: the posterior sample from the images' own streams (`HipAutoencoderKL.encode_to_latents`); an attached VAE only --
+        a `vae_encode=` hook draws its own sample and never sees a seed."""
         if self._vae_encode is None:
             raise NotImplementedError("VAE encode is not attached: pass latents=, or construct with vae= or vae_encode=<callable>")
         if self.vae is None:
             return self._vae_encode(image)
         image = self.image_processor.preprocess(image, height=height, width=width)
-        return image if image.shape[1] == 4 else self._vae_encode(image)
+        if image.shape[1] == 4:
+            return image
+        return self._vae_encode(image) if seeds is None else self._vae_encode(image, seeds=seeds, draw=draw)
 
     def _output(self, latents, output_type):
         """final latents -> what `output_type` asks for; with hooks only every type but "latent" returns the decode hook's raw tensor"""

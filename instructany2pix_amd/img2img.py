@@ -18,6 +18,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import noise as _noise
 from .ddim import StableDiffusionXLPipelineOutput, _PipelineBase
 from .scheduler import EulerDiscreteScheduler, fused_update
 
@@ -66,9 +67,12 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
                  negative_pooled_prompt_embeds=None, output_type="pil", return_dict=True, callback=None, callback_steps=1,
                  cross_attention_kwargs=None, original_size: Tuple[int, int] = None, crops_coords_top_left=(0, 0),
                  target_size: Tuple[int, int] = None, negative_original_size=None, negative_crops_coords_top_left=(0, 0),
-                 negative_target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, **unused):
+                 negative_target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, noise_seed=None, noise_draw=None, **unused):
         """`latents` = clean image latents (already scaled by the VAE scaling factor) instead of `image`; `noise` = the
-        start noise instead of drawing it from `generator` (both are conveniences for tests and latent-space callers)."""
+        start noise instead of drawing it from `generator` (both are conveniences for tests and latent-space callers).
+        `noise_seed` (an int, or one per batch element; None: `generator` as ever): the start noise is drawn on the device from the request's own stream
+        (noise.py: draw id `noise_draw`, default DRAW_REFINER), and the posterior sample of an `image=` from draw DRAW_HANDOFF_POSTERIOR of the same seed.
+        A supplied `noise` wins over the seed, the seed over `generator`."""
         if strength < 0 or strength > 1:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if num_inference_steps is None or not isinstance(num_inference_steps, int) or num_inference_steps <= 0:
@@ -92,9 +96,13 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
         if latents is None:
             if image is None:
                 raise ValueError("img2img needs `image` (with vae= or a vae_encode callable) or `latents`")
-            latents = self._image_latents(image)
+            latents = self._image_latents(image) if noise_seed is None else self._image_latents(
+                image, seeds=_noise.batch_seeds(noise_seed, None), draw=_noise.DRAW_HANDOFF_POSTERIOR)
         latents = latents.to(device=dev, dtype=torch.float16).contiguous()
         batch = latents.shape[0]
+        if noise is None and noise_seed is not None:
+            noise = _noise.randn_seeded(_noise.batch_seeds(noise_seed, batch), _noise.DRAW_REFINER if noise_draw is None else noise_draw, latents.shape[1:],
+                                        torch.float16, dev)
         if noise is None:
             g = generator if not isinstance(generator, list) else generator[0]
             gen_dev = g.device if g is not None else torch.device("cpu")

@@ -22,6 +22,7 @@ from typing import Optional
 
 import torch
 
+from . import noise as _noise
 from .ddim import StableDiffusionXLPipelineOutput, _PipelineBase, get_add_time_ids
 from .scheduler import DDIMScheduler, fused_update, mask_blend
 
@@ -60,9 +61,11 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                  output_type="pil", return_dict=True, callback=None, callback_steps=1, cross_attention_kwargs=None,
-                 guidance_rescale: float = 0.0, original_size=None, crops_coords_top_left=(0, 0), target_size=None, **unused):
+                 guidance_rescale: float = 0.0, original_size=None, crops_coords_top_left=(0, 0), target_size=None, noise_seed=None, noise_draw=None, **unused):
         """`latents` = clean image latents (scaled) instead of `image`; `noise` = the start / re-noising noise instead of drawing it
-        from `generator` (conveniences for tests and latent-space callers, as in img2img.py)."""
+        from `generator` (conveniences for tests and latent-space callers, as in img2img.py).
+        `noise_seed` (an int, or one per batch element; None: `generator` as ever): the noise is drawn on the device from the request's own stream (noise.py:
+        draw id `noise_draw`, default DRAW_INPAINT, the first subject pass). A supplied `noise` wins over the seed, the seed over `generator`."""
         if strength < 0 or strength > 1:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if guidance_rescale != 0.0 or eta != 0.0:
@@ -94,6 +97,9 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
         mask = prepare_mask(mask_image, h, w, dev)
         if mask.shape[0] != B:
             mask = mask.expand(B, -1, -1, -1).contiguous()
+        if noise is None and noise_seed is not None:
+            noise = _noise.randn_seeded(_noise.batch_seeds(noise_seed, B), _noise.DRAW_INPAINT if noise_draw is None else noise_draw, image_latents.shape[1:],
+                                        torch.float16, dev)
         if noise is None:
             g = generator if not isinstance(generator, list) else generator[0]
             gen_dev = g.device if g is not None else torch.device("cpu")
@@ -146,9 +152,12 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
 
 def subject_consistency(subject_data, latents, ip_adapter_xl_inpaint, subject_strength: float = 0.7, **generate_kwargs):
     """The per-subject loop of reference gdino/lib.py:85-103 on given masks: `subject_data` = [(mask, subject embedding)], each pass
-    re-paints the masked region guided by the subject's 'local' image tokens (50 steps, IP scale 0.8)."""
+    re-paints the masked region guided by the subject's 'local' image tokens (50 steps, IP scale 0.8). With `noise_seed=` among the keywords, pass k
+    draws its noise from draw id DRAW_INPAINT + k of that seed (unless `noise=` is supplied, which wins)."""
     subject = latents
-    for msk, emb in subject_data:
+    for k, (msk, emb) in enumerate(subject_data):
+        if generate_kwargs.get("noise_seed") is not None:
+            generate_kwargs["noise_draw"] = _noise.inpaint_draw(k)
         subject = ip_adapter_xl_inpaint.generate(latents=subject, mask_image=msk, pil_image=None, strength=subject_strength,
                                                  clip_image_embeds_local=emb[None] if emb.ndim == 1 else emb, mode="local",
                                                  num_inference_steps=50, scale=0.8, **generate_kwargs)

@@ -172,7 +172,11 @@ class IPAdapterXL(IPAdapter):
     def generate(self, pil_image=None, prompt=None, negative_prompt=None, scale=1.0, scale_g=1.0, scale_l=0.5, num_samples=1,
                  seed=None, num_inference_steps=30, pil_image_local=None, clip_image_embeds_local=None, clip_image_embeds=None,
                  mode="global", prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
-                 negative_pooled_prompt_embeds=None, **kwargs):
+                 negative_pooled_prompt_embeds=None, noise_seed=None, noise_draw=None, **kwargs):
+        """`seed` builds the torch generator the pipeline draws from, as in the reference. `noise_seed` / `noise_draw` go through to a pipeline that draws noise
+        of its own (the inpainting pipeline): the request's Philox stream and the draw id in it (noise.py); they win over the generator."""
+        if noise_seed is not None:
+            kwargs.update(noise_seed=noise_seed, noise_draw=noise_draw)
         self.set_scale(scale)
         image_prompt_embeds, uncond_image_prompt_embeds = self.get_image_embeds(
             pil_image, clip_image_embeds, pil_image_local, clip_image_embeds_local, mode=mode, scale_g=scale_g, scale_l=scale_l)

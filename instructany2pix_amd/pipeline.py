@@ -25,6 +25,7 @@ from typing import Any, Callable, Optional
 import PIL.Image
 import torch
 
+from . import noise as _noise
 from .config import UNetConfig, sdxl_base
 from .ddim import SDXLDDIMPipeline, StableDiffusionXLPipeline
 from .img2img import StableDiffusionXLImg2ImgPipeline
@@ -158,18 +159,26 @@ class InstructAny2PixPipeline:
     # ---- the hot segment on explicit conditioning ------------------------------------------------------------------
     @torch.no_grad()
     def denoise(self, base_latents, latent_la, *, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds,
-                inv_prompt_embeds=None, inv_pooled_prompt_embeds=None, alpha=0.7, num_inference_steps=25, cfg=10, scale=1.0, noise=None):
-        """inversion -> polar mixing -> IP-Adapter guided sampling; returns (sampled latents, inverted latents)."""
+                inv_prompt_embeds=None, inv_pooled_prompt_embeds=None, alpha=0.7, num_inference_steps=25, cfg=10, scale=1.0, noise=None, seed=None):
+        """inversion -> polar mixing -> IP-Adapter guided sampling; returns (sampled latents, inverted latents).
+        `seed` (None: the draw below, as ever): the mixing noise is draw DRAW_POLAR of the request's own Philox stream (noise.py), made and mixed on the device
+        (`noise.randn_seeded`, `noise.polar_mix`): the inverted latents never leave it -- no `.cpu()`, no host `randn`, no CPU mix, no upload. Row b of a
+        batch of base latents draws from seed + b. A supplied `noise` wins over the seed. The device mix is fp32 arithmetic rounded once; it is not bit-equal
+        to the CPU fp16 mix of the unseeded path."""
         self.pipe_inversion.unet = self.pipe.unet                                              # :306
         self.pipe_inversion.scheduler = DDIMScheduler.from_config(self.pipe.scheduler.config)  # :307
         if inv_prompt_embeds is None:        # reference inverts with prompt='' (:330); callers pass its embedding
             inv_prompt_embeds, inv_pooled_prompt_embeds = negative_prompt_embeds, negative_pooled_prompt_embeds
         latent_inv = self.pipe_inversion.inverse(num_inference_steps=num_inference_steps, latents=base_latents,
                                                  prompt_embeds=inv_prompt_embeds, pooled_prompt_embeds=inv_pooled_prompt_embeds).images
-        latent_inv_cpu = latent_inv.cpu()                                                      # :331
-        if noise is None:
-            noise = torch.randn_like(latent_inv_cpu)                                           # :335 global RNG, CPU, fp16
-        mixed = polar_intrtpolate(latent_inv_cpu, noise, alpha)                                # :333-337
+        if noise is None and seed is not None:
+            z = _noise.randn_seeded(_noise.batch_seeds(seed, latent_inv.shape[0]), _noise.DRAW_POLAR, latent_inv.shape[1:], torch.float16, latent_inv.device)
+            mixed = _noise.polar_mix(latent_inv, z, float(alpha))
+        else:
+            latent_inv_cpu = latent_inv.cpu()                                                  # :331
+            if noise is None:
+                noise = torch.randn_like(latent_inv_cpu)                                       # :335 global RNG, CPU, fp16
+            mixed = polar_intrtpolate(latent_inv_cpu, noise, alpha)                            # :333-337
         images = self.ip_adapter_xl.generate(pil_image=None, num_samples=1, clip_image_embeds=latent_la, num_inference_steps=num_inference_steps,
                                              scale=scale, mode="global", guidance_scale=cfg, latents=mixed,
                                              prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
@@ -192,9 +201,9 @@ class InstructAny2PixPipeline:
     def loas_base_img(self, base_img_path):
         return loas_base_img(base_img_path, self.base_image_size)
 
-    def _base_latents(self, c):
+    def _base_latents(self, c, seed=None):
         """the conditioner's `base_latents`, else its `base_image` (PIL) or `base_img_path` (loaded by `loas_base_img`) through the inversion
-        pipeline's image processor and the VAE (a posterior sample, as in the reference's `inverse(image=...)`)"""
+        pipeline's image processor and the VAE (a posterior sample, as in the reference's `inverse(image=...)`; with `seed`, draw DRAW_BASE_POSTERIOR of it)"""
         if c.get("base_latents") is not None:
             return c["base_latents"]
         img = c.get("base_image")
@@ -204,7 +213,8 @@ class InstructAny2PixPipeline:
             raise KeyError("the conditioner returned none of base_latents / base_image / base_img_path")
         if self.vae is None:
             raise ValueError("a base_image / base_img_path needs the pipeline built with vae=<HipAutoencoderKL>")
-        return self.pipe_inversion._image_latents(img)
+        return self.pipe_inversion._image_latents(img) if seed is None else self.pipe_inversion._image_latents(
+            img, seeds=[_noise.check_seed(seed)], draw=_noise.DRAW_BASE_POSTERIOR)
 
     # ---- the instruction LLM (reference :151-279) ---------------------------------------------------------------------------
     def _modality_embeds(self, mm_data):
@@ -246,16 +256,23 @@ class InstructAny2PixPipeline:
         lm.eval()
         return input_ids, extra_replacement, stopping_criteria
 
-    def _llm_generate(self, inst, aux_info):
+    def _llm_seed_kw(self, key, value):
+        """{key: value} where the LLM draws its tokens on the device (its Philox stream is keyed by the request's seed); {} under the host sampler, which
+        keeps torch's global generator whatever the request's seed"""
+        return {key: value} if value is not None and getattr(self.any2pix_lm, "sampler", "host") == "device" else {}
+
+    def _llm_generate(self, inst, aux_info, seed=None):
         """:171-211: prompt, stopping criterion and the one `generate` call -> (input_ids, generate output). Where the token is drawn (host or
-        device) is the LLM's own setting, `HipInstructAny2PixLM(sampler=...)`; `_llm_generate_batch` likewise."""
+        device) is the LLM's own setting, `HipInstructAny2PixLM(sampler=...)`; `_llm_generate_batch` likewise. `seed`: the request's seed, which keys
+        the token stream under the device sampler (and is ignored under the host sampler)."""
         input_ids, extra_replacement, stopping_criteria = self._llm_request(inst, aux_info)
         lm = self.any2pix_lm
         out = lm.generate(input_ids, images=None, do_sample=True, temperature=0.3, max_new_tokens=100, output_hidden_states=True, use_cache=False,
-                          return_dict_in_generate=True, extra_replacement=extra_replacement, stopping_criteria=[stopping_criteria])
+                          return_dict_in_generate=True, extra_replacement=extra_replacement, stopping_criteria=[stopping_criteria],
+                          **self._llm_seed_kw("seed", seed))
         return input_ids, out
 
-    def forward_llm(self, inst, mm_data=[], use_cache=False):
+    def forward_llm(self, inst, mm_data=[], use_cache=False, seed=None):
         """-> (image_embeds, base_embed, output_caption, base_img_path, extra_data); (None, None, text, None, None) without an `<im_gen>`"""
         if use_cache:
             return self.cache
@@ -263,22 +280,24 @@ class InstructAny2PixPipeline:
             raise NotImplementedError("forward_llm needs the pipeline built with llm=<HipInstructAny2PixLM> and llm_tokenizer=")
         from .llm import parse_generation
         aux_info = self._modality_embeds(mm_data)
-        input_ids, out = self._llm_generate(inst, aux_info)
+        input_ids, out = self._llm_generate(inst, aux_info) if seed is None else self._llm_generate(inst, aux_info, seed=seed)
         ids = self._llm_special_ids()
         tp = self.any2pix_tokenizer.batch_decode(out.sequences)
         return parse_generation(out.sequences, input_ids.shape[1], out.hidden_states, tp[0], aux_info, mm_data,
                                 self.any2pix_lm.get_model().vae_predictor_image, ids["<video>"], ids["<base>"], ids["<im_gen>"])
 
-    def _llm_generate_batch(self, requests):
-        """the one `generate_batch` call for [(input_ids, extra_replacement, stopping criterion), ...] -> list of generate outputs"""
+    def _llm_generate_batch(self, requests, seeds=None):
+        """the one `generate_batch` call for [(input_ids, extra_replacement, stopping criterion), ...] -> list of generate outputs. `seeds` (one per request,
+        all given): the requests' token streams under the device sampler."""
         return self.any2pix_lm.generate_batch([r[0] for r in requests], extra_replacements=[r[1] for r in requests], do_sample=True, temperature=0.3,
-                                              max_new_tokens=100, stopping_criteria=[[r[2]] for r in requests])
+                                              max_new_tokens=100, stopping_criteria=[[r[2]] for r in requests], **self._llm_seed_kw("seeds", seeds))
 
-    def forward_llm_batch(self, insts, mm_datas):
+    def forward_llm_batch(self, insts, mm_datas, seeds=None):
         """`forward_llm` for several requests, their decode steps sharing every read of the LLM's weights (`HipInstructAny2PixLM.generate_batch`):
         -> a list of the five-tuples `forward_llm` returns, in request order. More requests than the LLM's `max_batch` run in consecutive groups.
         The sampled tokens are reproducible for a seed but are not those of serial `forward_llm` calls (the draws of a step interleave across the
-        requests). `self.cache` is not touched."""
+        requests). `self.cache` is not touched. `seeds` (one per request; an entry None gets a fresh one from the global generator): under the LLM's device sampler
+        request i draws its tokens from its own stream, the same alone and in any batch; the host sampler ignores them."""
         insts, mm_datas = list(insts), list(mm_datas)
         if len(insts) != len(mm_datas):
             raise ValueError(f"{len(insts)} instructions for {len(mm_datas)} mm_data lists")
@@ -291,7 +310,11 @@ class InstructAny2PixPipeline:
         from .llm import parse_generation
         aux = [self._modality_embeds(mm) for mm in mm_datas]
         requests = [self._llm_request(inst, a) for inst, a in zip(insts, aux)]
-        outs = self._llm_generate_batch(requests)
+        if seeds is not None and any(s is not None for s in seeds):
+            fresh = iter(_noise.seeds_from_global(sum(s is None for s in seeds)))
+            outs = self._llm_generate_batch(requests, seeds=[next(fresh) if s is None else s for s in seeds])
+        else:
+            outs = self._llm_generate_batch(requests)
         ids = self._llm_special_ids()
         results = []
         for (input_ids, _, _), out, a, mm in zip(requests, outs, aux, mm_datas):
@@ -300,9 +323,9 @@ class InstructAny2PixPipeline:
                                             self.any2pix_lm.get_model().vae_predictor_image, ids["<video>"], ids["<base>"], ids["<im_gen>"]))
         return results
 
-    def _condition_from_llm(self, inst, mm_data, use_cache, llm_only):
+    def _condition_from_llm(self, inst, mm_data, use_cache, llm_only, seed=None):
         """the conditioning dict a `conditioner=` would return, from forward_llm + the attached text encoders (:309-310, :330, :342-345, :358-361)"""
-        image_embeds, base_embed, output_caption, base_img_path, extra_data = self.forward_llm(inst, mm_data, use_cache=use_cache)
+        image_embeds, base_embed, output_caption, base_img_path, extra_data = self.forward_llm(inst, mm_data, use_cache=use_cache, **({} if seed is None else {"seed": seed}))
         self.cache = image_embeds, base_embed, output_caption, base_img_path, extra_data
         c = dict(image_embeds=image_embeds, base_embed=base_embed, caption=output_caption, base_img_path=base_img_path, extra_data=extra_data)
         if llm_only:
@@ -370,7 +393,7 @@ class InstructAny2PixPipeline:
         return pairs
 
     # ---- N whole requests: conditioning for all, then every stage batched (batch.py) -------------------------------------------------------------
-    def _conditions_for_batch(self, insts, mm_datas):
+    def _conditions_for_batch(self, insts, mm_datas, seeds=None):
         """one conditioning dict per request, as `__call__` gets it from the conditioner or from `_condition_from_llm`. With an LLM: ONE
         `forward_llm_batch` call, the inversion prompt '' encoded once, the other prompts in one `encode_prompt` call per text-encoder role. A request
         whose LLM output has no `<im_gen>` comes back as dict(image_embeds=None, caption=...)."""
@@ -383,7 +406,7 @@ class InstructAny2PixPipeline:
         if self._text_encoder is None:
             raise ValueError("a pipeline built with llm= needs text_encoder=<encode_prompt callable> for the denoise stages")
         cs = []
-        for mm, (image_embeds, base_embed, caption, base_img_path, extra_data) in zip(mm_datas, self.forward_llm_batch(insts, mm_datas)):
+        for mm, (image_embeds, base_embed, caption, base_img_path, extra_data) in zip(mm_datas, self.forward_llm_batch(insts, mm_datas, **({} if seeds is None else {"seeds": seeds}))):
             c = dict(image_embeds=image_embeds, base_embed=base_embed, caption=caption, base_img_path=base_img_path, extra_data=extra_data)
             if image_embeds is not None:
                 c["image_embeds"], c["base_embed"] = image_embeds.reshape(1, -1), base_embed.reshape(1, -1)
@@ -418,7 +441,7 @@ class InstructAny2PixPipeline:
         return cs
 
     def edit_batch(self, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
-                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True):
+                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None):
         """`__call__` for N instructions on N images -> the list of its `(non_refined, oo, msg)` tuples, in request order. Every knob of `__call__` is a
         scalar (for all requests) or a list of N (`h`: one triple or N triples). `group` requests share one launch sequence in every loop.
 
@@ -436,22 +459,44 @@ class InstructAny2PixPipeline:
         noise, the posterior samples of the refiner hand-off, the refiner noise, the inpaint noise of every pass -- where N serial calls interleave the
         stages per request. A seeded `edit_batch` is therefore reproducible, and equals N serial calls only when the noises are supplied.
         Sharding: as `denoise_batch` -- with a process group up (and `shard`), each of the three loops runs a contiguous shard of its requests per rank
-        and all-gathers the result in request order; the stages around them (conditioning, VAE, masks) run on every rank, which must be seeded alike."""
+        and all-gathers the result in request order; the stages around them (conditioning, VAE, masks) run on every rank, which must be seeded alike
+        for the draws that come from the global generator.
+
+        Seeded RNG rule (`seeds`: a list of N 64-bit seeds, entries None allowed, or ONE int s meaning s + i for request i; None: the rule above, bit for bit
+        as ever). Every normal draw of a seeded request comes from the request's own Philox stream on the device (include/ia2p.h, "Seeded noise"), draw ids of
+        noise.py: 0 the base image's posterior sample, 1 the polar-mixing noise, 2 the posterior sample of the refiner hand-off, 3 the refiner noise, 4 + k the
+        inpaint noise of subject pass k. A value depends on (seed, draw id, element) only, so request i with seed s gets the same noise -- and, rows of a group
+        being independent, the same bits in a group of the same size -- whatever shares the call, in whatever order; `__call__(seed=s)` serves it from the
+        same noise alone (equal within the batch-against-serial tolerance: bit identity across GROUP SIZES is not promised). The inverted latents stay on the
+        device: noise, mix (`ia2p_polar_mix_v`: fp32, not the bits of the unseeded path's CPU fp16 mix), posterior samples and `add_noise` inputs are all made
+        there. Where the LLM samples on the device the request's seed is also its entry of `generate_batch(seeds=)`; under the host sampler the LLM keeps the
+        global generator. Precedence: a noise tensor the conditioner supplies (`polar_noise`, `refiner_noise`, `subject_noise`) wins over the seed, the seed
+        over the global generator. Seeded and unseeded requests may share a call and a group; the unseeded ones draw from the global generator in request
+        order among themselves. Seeded draws need no rank to be seeded alike. With `debug=True` a seeded request's message also carries `seed`."""
         from .batch import edit_batch
         return edit_batch(self, insts, mm_datas, alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
-                          subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard)
+                          subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds)
 
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
-                 use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent") -> Any:
+                 use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None) -> Any:
         """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
-        `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images)."""
+        `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images).
+        `seed` (a 64-bit unsigned integer; None: every draw from the global CPU generator, as ever): every normal draw of the request comes from its own
+        Philox stream on the device, by the draw ids of noise.py -- the base image's posterior sample, the polar-mixing noise, the posterior sample of the
+        refiner hand-off, the refiner noise, the inpaint noise of subject pass k -- and, where the LLM samples on the device, so do its tokens (under the
+        host sampler the LLM keeps the global generator). The image then depends on the request and its seed alone: `edit_batch(seeds=[seed])` serves the
+        same request from the same noise (equal within the batch-against-serial tolerance; bit identity across group sizes is not promised, as the UNet's
+        batch-dependent plans sum in other orders). A noise the conditioner supplies (`polar_noise`, `refiner_noise`, `subject_noise`) wins over the seed.
+        With `debug=True` the message also carries `seed`."""
+        if seed is not None:
+            seed = _noise.check_seed(seed)
         if output_type not in OUTPUT_TYPES:
             raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
         if output_type != "latent" and self.vae is None:
             raise ValueError(f"output_type={output_type!r} needs the pipeline built with vae=<HipAutoencoderKL>")
         if self.conditioner is None and self.any2pix_lm is not None:
-            c = self._condition_from_llm(inst, mm_data, use_cache, llm_only)
+            c = self._condition_from_llm(inst, mm_data, use_cache, llm_only, **({} if seed is None else {"seed": seed}))
             if llm_only:
                 return None, None, c["caption"]
         elif self.conditioner is None:
@@ -474,11 +519,12 @@ class InstructAny2PixPipeline:
                                               force_guidence_t0=True, do_classifier_free_guidance=True, score=6.5)
             y0 = y[0].to(device=c["base_embed"].device, dtype=c["base_embed"].dtype)
         latent_la = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], y0, h, norm)
-        images, latent_inv = self.denoise(self._base_latents(c), latent_la.reshape(1, -1)[0], prompt_embeds=c["prompt_embeds"],
+        images, latent_inv = self.denoise(self._base_latents(c, seed), latent_la.reshape(1, -1)[0], prompt_embeds=c["prompt_embeds"],
                                           pooled_prompt_embeds=c["pooled_prompt_embeds"], negative_prompt_embeds=c["negative_prompt_embeds"],
                                           negative_pooled_prompt_embeds=c["negative_pooled_prompt_embeds"],
                                           inv_prompt_embeds=c.get("inv_prompt_embeds"), inv_pooled_prompt_embeds=c.get("inv_pooled_prompt_embeds"),
-                                          alpha=alpha, num_inference_steps=num_inference_steps, cfg=cfg, scale=scale)
+                                          alpha=alpha, num_inference_steps=num_inference_steps, cfg=cfg, scale=scale, seed=seed,
+                                          noise=c.get("polar_noise") if seed is not None else None)      # (unseeded: this call has always drawn its own)
         non_refined = images
         oo = images
         decoded = None          # the decode of `images`, when the refiner hand-over made it
@@ -488,7 +534,7 @@ class InstructAny2PixPipeline:
             # Conditioning = text encoder 2 on caption + ',high quality,well-formed,award-winning' (the conditioner supplies its embeddings).
             kw = dict(strength=refinement, prompt_embeds=c["refiner_prompt_embeds"], pooled_prompt_embeds=c["refiner_pooled_prompt_embeds"],
                       negative_prompt_embeds=c["refiner_negative_prompt_embeds"], negative_pooled_prompt_embeds=c["refiner_negative_pooled_prompt_embeds"],
-                      noise=c.get("refiner_noise"), output_type="latent")
+                      noise=c.get("refiner_noise"), output_type="latent", **({} if seed is None else {"noise_seed": seed}))
             vae_route = self.refiner_handoff == "image" and self.pipe._vae_decode is not None and self.piperf._vae_encode is not None
             if self.refiner_handoff == "image" and not vae_route and not self._warned_handoff:
                 # the reference's route was asked for (decode, 8-bit image, posterior SAMPLE from the global RNG) but cannot be taken: say so once --
@@ -502,7 +548,8 @@ class InstructAny2PixPipeline:
                 # (`retrieve_latents(vae.encode(image)) * scaling_factor`: a posterior SAMPLE, global RNG)
                 decoded = self.pipe._vae_decode(images)
                 if self.vae is not None:    # the same steps with the 8-bit round trip in one HIP launch (bit-identical to to_8bit_image)
-                    oo = self.piperf(latents=self.piperf._vae_encode(requantize(decoded)), **kw).images
+                    enc = {} if seed is None else dict(seeds=[seed], draw=_noise.DRAW_HANDOFF_POSTERIOR)
+                    oo = self.piperf(latents=self.piperf._vae_encode(requantize(decoded), **enc), **kw).images
                 else:
                     oo = self.piperf(image=to_8bit_image(decoded), **kw).images
             else:
@@ -514,6 +561,8 @@ class InstructAny2PixPipeline:
             kw = dict(output_type="latent", prompt_embeds=c["subject_prompt_embeds"], pooled_prompt_embeds=c["subject_pooled_prompt_embeds"],
                       negative_prompt_embeds=c["subject_negative_prompt_embeds"],
                       negative_pooled_prompt_embeds=c["subject_negative_pooled_prompt_embeds"], noise=c.get("subject_noise"))
+            if seed is not None:
+                kw["noise_seed"] = seed                                                        # pass k draws from DRAW_INPAINT + k (inpaint.subject_consistency)
             by_phrase = [isinstance(k, str) for k, _ in subject_data]
             if any(by_phrase) and not all(by_phrase):
                 raise ValueError("subject_data mixes (mask, embedding) and (phrase, embedding) entries: give one kind")
@@ -521,7 +570,7 @@ class InstructAny2PixPipeline:
                 oo = self._subjects_from_phrases(c, subject_data, oo, subject_strength, kw)
             else:                                                                              # masks given by the conditioner
                 oo = subject_consistency(subject_data, oo, self.ip_adapter_xl_inpaint, subject_strength, **kw)
-        msg = "SUCCESS!" if not debug else dict(output_caption=c["caption"], latent_inv=latent_inv, latent_la=latent_la)
+        msg = "SUCCESS!" if not debug else dict(output_caption=c["caption"], latent_inv=latent_inv, latent_la=latent_la, **({} if seed is None else {"seed": seed}))
         if output_type != "latent":
             post = self.pipe.image_processor.postprocess
             refined_is_base = oo is non_refined

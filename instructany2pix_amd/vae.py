@@ -108,8 +108,26 @@ class HipAutoencoderKL(_ffi.Executor):
                                  f"{self._cfg.stream_scale:g} (the reference runs this model in fp32); lower VAEConfig.stream_scale (a power of two)")
 
     # hooks with the signatures the loops in ddim.py accept (vae_encode= / vae_decode=)
-    def encode_to_latents(self, image, generator=None):
-        return self.encode(image).latent_dist.sample(generator) * self._cfg.scaling_factor
+    def encode_to_latents(self, image, generator=None, seeds=None, draw=0):
+        """the scaled posterior sample. `seeds` (one per image; None, or every entry None: the draw of `generator` / the global RNG, as ever): image b is sampled
+        on the device from its own stream (seeds[b], draw) (noise.py; `ia2p_posterior_sample_seeded`) and wins over `generator`. An image whose entry is None in
+        a list that names seeds for others is sampled from `generator` / the global RNG next to them."""
+        dist = self.encode(image).latent_dist
+        if seeds is None or all(s is None for s in seeds):
+            return dist.sample(generator) * self._cfg.scaling_factor
+        from . import noise as _noise
+        seeds, mom = list(seeds), dist.parameters
+        if len(seeds) != mom.shape[0]:
+            raise ValueError(f"{len(seeds)} seeds for {mom.shape[0]} images: one per image")
+        sf = self._cfg.scaling_factor
+        own = [b for b, s in enumerate(seeds) if s is not None]
+        if len(own) == len(seeds):
+            return _noise.posterior_sample(mom, seeds, draw, sf)
+        rest = [b for b, s in enumerate(seeds) if s is None]
+        out = torch.empty_like(dist.mean, dtype=mom.dtype)
+        out[rest] = DiagonalGaussianDistribution(mom[rest]).sample(generator) * sf
+        out[own] = _noise.posterior_sample(mom[own], [seeds[b] for b in own], draw, sf)
+        return out
 
     def decode_from_latents(self, latents):
         return self.decode(latents / self._cfg.scaling_factor, return_dict=False)[0]

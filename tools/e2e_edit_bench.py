@@ -24,7 +24,14 @@ tools/llm_decode_bench.py and the single-request mode): a conditioner hands ever
 the clock, by the full-size text encoders) and its own 1024 x 1024 PIL image; the LLM is not built. Timed: image in, VAE encode, embedding prior, inversion,
 polar mixing, guided sampling, the refiner hand-over (decode, 8-bit, encode), the refiner pass, VAE decode, image out.
 
-    python tools/e2e_edit_bench.py --batch 1,4,8 [--reps 3] [--steps 25] [--refinement 0.5]"""
+    python tools/e2e_edit_bench.py --batch 1,4,8 [--reps 3] [--steps 25] [--refinement 0.5]
+
+--seeded (with --batch) runs the same requests WITH per-request seeds (`__call__(seed=)`, `edit_batch(seeds=)`: every normal draw on the device from the request's
+own Philox stream, the inverted latents never leave it) next to the unseeded run, interleaved repeat by repeat in the one process: serial, serial seeded,
+edit_batch, edit_batch seeded. Its stage table gains the three seeded-noise launches ALONE (`ia2p_randn_seeded`, `ia2p_posterior_sample_seeded`, `ia2p_polar_mix_v`
+at B = 1 and B = 8 on 4 x PX/8 x PX/8 latents): microseconds per launch between two device events around 200 back-to-back launches, median of 5 such trains.
+
+    python tools/e2e_edit_bench.py --seeded --batch 1,8"""
 import argparse
 import os
 import sys
@@ -56,9 +63,12 @@ _ap.add_argument("--top-p", type=float, default=None, help="nucleus of the LLM's
 _ap.add_argument("--imagebind", action="store_true", help="encode the mm_data entries' files with the HIP ImageBind towers instead of seeded vectors")
 _ap.add_argument("--batch", default=None, help="comma-separated request counts: compare edit_batch with the serial loop (see the module docstring)")
 _ap.add_argument("--reps", type=int, default=3)
+_ap.add_argument("--seeded", action="store_true", help="with --batch: the same requests with per-request seeds next to the unseeded run, and the three noise launches alone")
 _ap.add_argument("--steps", type=int, default=25)
 _ap.add_argument("--refinement", type=float, default=0.5)
 ARGS = _ap.parse_args()
+if ARGS.seeded and not ARGS.batch:
+    _ap.error("--seeded compares against the unseeded run of --batch: give --batch too")
 BATCHES = [int(n) for n in ARGS.batch.split(",")] if ARGS.batch else []
 DEV = "cuda:0"
 PX = int(os.environ.get("PX", 1024))
@@ -216,6 +226,45 @@ if BATCHES:
     def batched(n):
         return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), **knobs)
 
+    SEEDS = [0x5EED0000 + 977 * i for i in range(NMAX)]
+
+    def serial_seeded(n):
+        return [pipe(inst, [], seed=SEEDS[i], **knobs) for i, inst in enumerate(insts[:n])]
+
+    def batched_seeded(n):
+        return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), seeds=SEEDS[:n], **knobs)
+
+    def launches_alone():
+        """the three seeded-noise launches on their own: us per launch, median of 5 trains of 200 launches between two device events"""
+        import statistics as st_
+        from instructany2pix_amd import noise
+        h = PX // 8
+        rows = []
+        for B in (1, 8):
+            seeds = SEEDS[:1] * B if NMAX < B else SEEDS[:B]
+            z = torch.empty(B, 4, h, h, dtype=torch.float16, device=DEV)
+            x = noise.randn_seeded(seeds, 9, (4, h, h), torch.float16, DEV)
+            mom = noise.randn_seeded(seeds, 8, (8, h, h), torch.float16, DEV)
+            work = {"ia2p_randn_seeded": lambda: noise.randn_seeded(seeds, noise.DRAW_POLAR, (4, h, h), torch.float16, DEV, out=z),
+                    "ia2p_posterior_sample_seeded": lambda: noise.posterior_sample(mom, seeds, noise.DRAW_BASE_POSTERIOR, 0.13025),
+                    "ia2p_polar_mix_v": lambda: noise.polar_mix(x, z, 0.7)}
+            for name, fn in work.items():
+                for _ in range(20):
+                    fn()
+                us = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    for _ in range(200):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us.append(e0.elapsed_time(e1) * 1e3 / 200)
+                rows.append(f"{name} B={B} {st_.median(us):.1f} (min {min(us):.1f}, max {max(us):.1f})")
+        print(f"# seeded-noise launches alone, 4 x {h} x {h} latents, us per launch incl. the Python call (posterior_sample and polar_mix allocate their output): "
+              + "; ".join(rows), flush=True)
+
     def run(fn, n):
         stages.clear()
         torch.manual_seed(3)
@@ -230,9 +279,14 @@ if BATCHES:
     for n in BATCHES:
         run(serial, n), run(batched, n)             # every shape warm: workspaces, plans
         runs = {"serial": [], "edit_batch": []}
+        sides = [("serial", serial), ("edit_batch", batched)]
+        if ARGS.seeded:
+            run(serial_seeded, n), run(batched_seeded, n)
+            runs = {"serial": [], "serial seeded": [], "edit_batch": [], "edit_batch seeded": []}
+            sides = [("serial", serial), ("serial seeded", serial_seeded), ("edit_batch", batched), ("edit_batch seeded", batched_seeded)]
         for _ in range(ARGS.reps):
-            runs["serial"].append(run(serial, n))
-            runs["edit_batch"].append(run(batched, n))
+            for side, fn in sides:
+                runs[side].append(run(fn, n))
         print(f"N = {n} (group {min(n, 8)}, B_eff = {2 * min(n, 8)} in the guided loops)", flush=True)
         per_image = {}
         for side, rr in runs.items():
@@ -241,6 +295,11 @@ if BATCHES:
             names = list(rr[0][1])
             st = {k: statistics.median(s_.get(k, 0.0) for _, s_ in rr) for k in names}
             glue = per_image[side] * n - sum(st.values())
-            print(f"  {side:10s}: {per_image[side]:8.1f} ms / image (min {min(tot):.1f}, max {max(tot):.1f} over {ARGS.reps}), {1e3 / per_image[side]:.3f} images/s; "
+            print(f"  {side:17s}: {per_image[side]:8.1f} ms / image (min {min(tot):.1f}, max {max(tot):.1f} over {ARGS.reps}), {1e3 / per_image[side]:.3f} images/s; "
                   f"stages, ms per call of {n}: " + ", ".join(f"{k} {v:.1f}" for k, v in st.items()) + f", host glue / the rest {glue:.0f}", flush=True)
         print(f"  per image, edit_batch / serial: {per_image['edit_batch'] / per_image['serial']:.3f}", flush=True)
+        if ARGS.seeded:
+            print(f"  per image, seeded / unseeded: serial {per_image['serial seeded'] / per_image['serial']:.4f}, "
+                  f"edit_batch {per_image['edit_batch seeded'] / per_image['edit_batch']:.4f}", flush=True)
+    if ARGS.seeded:
+        launches_alone()
