@@ -14,6 +14,17 @@ Per request the hot segment is the reference's: DDIM inversion of the base laten
 noise on the CPU in fp16 (pipeline.py:331-337), IP-Adapter guided sampling (ip_adapter.py:289-356 -> sdxl_pipeline.py:764-857).
 Batch element b of a heterogeneous batch gets the bits it gets in a uniform batch of the same size (tests/test_batch_gpu.py); against a
 batch-1 run only the summation order of batch-dependent kernel plans differs (fp16 tolerance).
+
+Layout of the module. The host code the serial pipelines also need lives with them and is called from here: `scheduler.kept_steps` (strength -> kept
+tail), `ddim.conditioning` ([uncond | cond] context, pooled embeddings, time ids), `noise.host_noises` / `noise.resolve_noises` (supplied noise, then
+seed, then generator), the request-level helpers of `pipeline.py`. Here:
+  * tables: `invert_tables`, `sample_tables`, `refine_tables`, `inpaint_tables` give every request what its scheduler gives it alone, and `_joint_tables`
+    lays them out `[iterations][requests]`, a request that is through HELD on its hold record;
+  * one driver, `_run_groups` (shard, groups, concatenate, empty shard, all-gather), under `denoise_batch`, `refine_batch` and `inpaint_batch`, which
+    validate and resolve the noises first;
+  * three group bodies with their own launch loops, `_denoise_group` (`invert_batch`, mix, `sample_batch`), `_refine_group`, `_inpaint_group`: their
+    buffer hand-offs differ (ping-pong through out2; x apart from the scaled input; `stepped` blended into both halves), so they are not one loop;
+  * `edit_batch`: whole requests through all of it.
 """
 from __future__ import annotations
 
@@ -24,8 +35,8 @@ import torch
 
 from . import dist as D
 from . import noise as _noise
-from .ddim import get_add_time_ids
-from .scheduler import DDIMScheduler, fused_update_v
+from .ddim import conditioning, get_add_time_ids
+from .scheduler import DDIMScheduler, check_kept_steps, fused_update_v, kept_steps, mask_blend_v
 
 
 @dataclass
@@ -48,8 +59,47 @@ class EditRequest:
 
 
 def _coef_table(rows: Sequence[Sequence[tuple]], device) -> torch.Tensor:
-    """[steps][B][3] float32 on the device: (g, c_x, c_e) of every request at every iteration of the joint loop"""
+    """a host table of the joint loop, float32 on the device: [steps][B] timesteps, [steps][B][3] (g, c_x, c_e) or [steps][B][2] (c0, c1) of every request"""
     return torch.tensor(rows, dtype=torch.float32).to(device).contiguous()
+
+
+def _joint_tables(records: Sequence[Sequence[tuple]], hold: Sequence[tuple]) -> tuple:
+    """The one layout of all four joint loops. `records[r]`: one tuple of fields per step of request r alone (its timestep, its coefficients, ...);
+    `hold[r]`: the tuple it carries once it is through -- its last timestep and coefficients that keep its latents bit for bit. -> per field one
+    `[iterations][requests]` table: every request starts at iteration 0, the shorter ones are padded with their hold record."""
+    nmax = max(len(rec) for rec in records)
+    rows = [[rec[k] if k < len(rec) else hold[r] for r, rec in enumerate(records)] for k in range(nmax)]
+    return tuple([[cell[f] for cell in row] for row in rows] for f in range(len(hold[0])))
+
+
+def invert_tables(scheduler_config, steps: Sequence[int]):
+    """What `SDXLDDIMPipeline.inverse` gives every request alone over its own `steps[r]`-step schedule, walked in ascending t, laid out for the joint loop:
+    -> (timesteps, coef). A live row is (0, *inversion_coeffs(abar_t, abar_prev)), the first step against `final_alpha_cumprod` (pnp_pipeline.py:262-267);
+    a held row is (0, 1, 0) at the request's last timestep. Pure host arithmetic: needs no GPU."""
+    records, hold = [], []
+    for n in steps:
+        sch = DDIMScheduler.from_config(scheduler_config)
+        sch.set_timesteps(n)
+        acp, asc = sch.alphas_cumprod, [int(t) for t in reversed(sch.timesteps)]
+        prev = [float(sch.final_alpha_cumprod)] + [float(acp[t]) for t in asc[:-1]]
+        records.append([(float(t), (0.0,) + DDIMScheduler.inversion_coeffs(float(acp[t]), a_prev)) for t, a_prev in zip(asc, prev)])
+        hold.append((float(asc[-1]), (0.0, 1.0, 0.0)))
+    return _joint_tables(records, hold)
+
+
+def sample_tables(scheduler_config, steps: Sequence[int], cfg: Sequence[float]):
+    """What `StableDiffusionXLPipeline.__call__` gives every request alone over its own schedule, laid out for the joint loop: -> (timesteps, coef), the
+    timesteps duplicated over both halves of [uncond x n | cond x n]. A live row is (cfg[r], *step_coeffs(t)); a held row is (0, 1, 0) at the request's last
+    timestep (g = 0 here, where the refiner and inpaint loops hold with their g: with c_e = 0 the guidance never enters). Pure host arithmetic."""
+    records, hold = [], []
+    for n, g in zip(steps, cfg):
+        sch = DDIMScheduler.from_config(scheduler_config)
+        sch.set_timesteps(n)
+        desc = [int(t) for t in sch.timesteps]
+        records.append([(float(t), (float(g),) + sch.step_coeffs(t)) for t in desc])
+        hold.append((float(desc[-1]), (0.0, 1.0, 0.0)))
+    ts, coef = _joint_tables(records, hold)
+    return [row + row for row in ts], coef
 
 
 def _shard(N: int, shard: bool):
@@ -70,6 +120,22 @@ def _gather_shards(t: torch.Tensor, N: int, world: int) -> torch.Tensor:
     return torch.cat([allr[r][: D.shard_range(N, world, r)[1] - D.shard_range(N, world, r)[0]] for r in range(world)], dim=0)
 
 
+def _run_groups(requests: list, like: torch.Tensor, unet, group: int, shard: bool, run_group, n_out: int = 1):
+    """The driver of the three batch functions: this rank's contiguous shard of the (validated) requests in groups of `group`, `run_group(g0, reqs)` -> a
+    tuple of `n_out` tensors [len(reqs), ...] for the group that starts at request g0; per output, the groups' rows concatenated (an empty shard gives
+    [0, ...] of `like`'s shape) and all-gathered -> a tuple of `n_out` tensors [N, ...] in request order on every rank."""
+    N = len(requests)
+    world, lo, hi = _shard(N, shard)
+    outs = [run_group(g0, requests[g0:min(g0 + group, hi)]) for g0 in range(lo, hi, group)]
+    empty = torch.empty((0,) + tuple(like.shape[1:]), dtype=torch.float16, device=unet.device)
+    return tuple(_gather_shards(torch.cat([o[j] for o in outs]) if outs else empty, N, world) for j in range(n_out))
+
+
+def _rows(xs: Sequence[torch.Tensor], device) -> torch.Tensor:
+    """the requests' [1, ...] tensors as the [n, ...] rows of their group, fp16 on the device"""
+    return torch.cat([x.to(device=device, dtype=torch.float16) for x in xs], dim=0).contiguous()
+
+
 def _check_group(group, what: str):
     if not 1 <= int(group) <= 8:
         raise ValueError(f"group={group}: a group is one launch sequence of 1..8 requests (B_eff = 2 * group <= 16 rows, the limit of the image-projection and "
@@ -87,33 +153,15 @@ def _check_latents(latents: Sequence[torch.Tensor], what: str):
 @torch.no_grad()
 def invert_batch(unet, scheduler_config, latents, prompt_embeds, pooled, steps: Sequence[int], ip_scales=None):
     """DDIM inversion x0 -> xT of B requests at once (reference loop pnp_pipeline.py:251-275 per request), each over its own `steps[b]`-step
-    schedule walked in ascending t. latents [B,4,h,w]; prompt_embeds [B,L,ctx]; pooled [B,P]."""
+    schedule walked in ascending t (`invert_tables`). latents [B,4,h,w]; prompt_embeds [B,L,ctx]; pooled [B,P]."""
     dev = unet.device
-    B = latents.shape[0]
     x = latents.to(device=dev, dtype=torch.float16).contiguous().clone()
     h, w = x.shape[-2] * 8, x.shape[-1] * 8
-    tid = get_add_time_ids(unet, (h, w), (0, 0), (h, w), int(pooled.shape[-1])).repeat(B, 1).to(dev)
-    ctx = prompt_embeds.to(device=dev, dtype=torch.float16).contiguous()
-    added = {"text_embeds": pooled.to(device=dev, dtype=torch.float16).contiguous(), "time_ids": tid}
-    nmax = max(steps)
-    ts_rows, coef_rows = [[0.0] * B for _ in range(nmax)], [[(0.0, 1.0, 0.0)] * B for _ in range(nmax)]
-    for b, n in enumerate(steps):
-        sch = DDIMScheduler.from_config(scheduler_config)
-        sch.set_timesteps(n)
-        acp, prev = sch.alphas_cumprod, None
-        asc = [int(t) for t in reversed(sch.timesteps)]
-        for i in range(nmax):
-            if i < n:
-                t = asc[i]
-                a_prev = float(acp[prev]) if prev is not None else float(sch.final_alpha_cumprod)      # :262-267
-                c_x, c_e = DDIMScheduler.inversion_coeffs(float(acp[t]), a_prev)
-                ts_rows[i][b], coef_rows[i][b], prev = float(t), (0.0, c_x, c_e), t
-            else:                        # this request is through: evaluated at its last timestep, latents kept as they are
-                ts_rows[i][b] = float(asc[-1])
-    ts_all = torch.tensor(ts_rows, dtype=torch.float32).to(dev).contiguous()
-    coef_all = _coef_table(coef_rows, dev)
+    ctx, added = conditioning(dev, prompt_embeds, pooled, get_add_time_ids(unet, (h, w), (0, 0), (h, w), int(pooled.shape[-1])))      # unguided
+    ts, coef = invert_tables(scheduler_config, steps)
+    ts_all, coef_all = _coef_table(ts, dev), _coef_table(coef, dev)
     eps, nxt = torch.empty_like(x), torch.empty_like(x)
-    for i in range(nmax):
+    for i in range(len(ts)):
         unet(x, ts_all[i], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps, ip_scales=ip_scales)
         fused_update_v(x, eps, None, coef_all[i], nxt)
         x, nxt = nxt, x
@@ -124,40 +172,57 @@ def invert_batch(unet, scheduler_config, latents, prompt_embeds, pooled, steps: 
 def sample_batch(unet, scheduler_config, latents, cond_ctx, uncond_ctx, cond_pooled, uncond_pooled, steps: Sequence[int], cfg: Sequence[float],
                  scales: Optional[Sequence[float]] = None):
     """Guided DDIM sampling xT -> x0 of n requests at once: one UNet evaluation at B_eff = 2 n per iteration, rows [uncond x n | cond x n]
-    (the reference's cat([latents] * 2), sdxl_pipeline.py:826, per request), request r with its own schedule length, guidance and IP scale."""
+    (the reference's cat([latents] * 2), sdxl_pipeline.py:826, per request), request r with its own schedule length, guidance and IP scale
+    (`sample_tables`)."""
     dev = unet.device
     n = latents.shape[0]
     x = latents.to(device=dev, dtype=torch.float16).contiguous()
     h, w = x.shape[-2] * 8, x.shape[-1] * 8
-    f16 = lambda t: t.to(device=dev, dtype=torch.float16)
-    ctx = torch.cat([f16(uncond_ctx), f16(cond_ctx)], dim=0).contiguous()
-    pooled = torch.cat([f16(uncond_pooled), f16(cond_pooled)], dim=0).contiguous()
-    tid = get_add_time_ids(unet, (h, w), (0, 0), (h, w), int(cond_pooled.shape[-1])).repeat(2 * n, 1).to(dev)
-    added = {"text_embeds": pooled, "time_ids": tid}
-    nmax = max(steps)
-    ts_rows, coef_rows = [[0.0] * (2 * n) for _ in range(nmax)], [[(0.0, 1.0, 0.0)] * n for _ in range(nmax)]
-    for r, ns in enumerate(steps):
-        sch = DDIMScheduler.from_config(scheduler_config)
-        sch.set_timesteps(ns)
-        desc = [int(t) for t in sch.timesteps]
-        for i in range(nmax):
-            t = desc[min(i, ns - 1)]
-            ts_rows[i][r] = ts_rows[i][n + r] = float(t)
-            if i < ns:
-                c_x, c_e = sch.step_coeffs(t)
-                coef_rows[i][r] = (float(cfg[r]), c_x, c_e)
-    ts_all = torch.tensor(ts_rows, dtype=torch.float32).to(dev).contiguous()
-    coef_all = _coef_table(coef_rows, dev)
+    ctx, added = conditioning(dev, cond_ctx, cond_pooled, get_add_time_ids(unet, (h, w), (0, 0), (h, w), int(cond_pooled.shape[-1])), uncond_ctx, uncond_pooled)
+    ts, coef = sample_tables(scheduler_config, steps, cfg)
+    ts_all, coef_all = _coef_table(ts, dev), _coef_table(coef, dev)
     sc = None
     if scales is not None:
         sc = torch.tensor(list(scales) * 2, dtype=torch.float32).to(dev)
     model_in = torch.cat([x, x], dim=0).contiguous()
     eps, nxt = torch.empty_like(model_in), torch.empty_like(model_in)
-    for i in range(nmax):
+    for i in range(len(ts)):
         unet(model_in, ts_all[i], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps, ip_scales=sc)
         fused_update_v(model_in[:n], eps[:n], eps[n:], coef_all[i], nxt[:n], nxt[n:])        # eps_u + g (eps_c - eps_u), x_{t-1} to both halves
         model_in, nxt = nxt, model_in
     return model_in[:n].clone()
+
+
+@torch.no_grad()
+def _denoise_group(pipeline, reqs: List[EditRequest], noises):
+    """one group through inversion, polar mixing and guided sampling -> (sampled latents, inverted latents). `noises[i]` None: request i mixes on the device
+    with draw DRAW_POLAR of its own stream."""
+    from . import pipeline as P                  # (`polar_intrtpolate` looked up at call time)
+    unet, cfgs, ipa = pipeline.pipe.unet, pipeline.pipe.scheduler.config, pipeline.ip_adapter_xl
+    dev = unet.device
+    steps = [int(r.num_inference_steps) for r in reqs]
+    cat = lambda xs: torch.cat([x.to(dev) for x in xs], dim=0)
+    inv_ctx = cat([(r.inv_prompt_embeds if r.inv_prompt_embeds is not None else r.negative_prompt_embeds) for r in reqs])
+    inv_pool = cat([(r.inv_pooled_prompt_embeds if r.inv_pooled_prompt_embeds is not None else r.negative_pooled_prompt_embeds) for r in reqs])
+    x_inv = invert_batch(unet, cfgs, cat([r.base_latents for r in reqs]), inv_ctx, inv_pool, steps)
+    own = [i for i in range(len(reqs)) if noises[i] is None]
+    if len(own) < len(reqs):
+        x_inv_cpu = x_inv.cpu()                                                             # pipeline.py:331
+    if not own:
+        mixed = torch.cat([P.polar_intrtpolate(x_inv_cpu[i:i + 1], noises[i].to(x_inv_cpu.dtype), r.alpha) for i, r in enumerate(reqs)], dim=0)
+    else:                            # seeded rows: noise and mix on the device, one launch each over those rows; the latents never leave it
+        z = _noise.randn_seeded([reqs[i].seed for i in own], _noise.DRAW_POLAR, x_inv.shape[1:], torch.float16, dev)
+        mixed = torch.empty_like(x_inv)
+        mixed[own] = _noise.polar_mix(x_inv[own] if len(own) < len(reqs) else x_inv, z, [float(reqs[i].alpha) for i in own])
+        for i, r in enumerate(reqs):
+            if noises[i] is not None:
+                mixed[i:i + 1] = P.polar_intrtpolate(x_inv_cpu[i:i + 1], noises[i].to(x_inv_cpu.dtype), r.alpha).to(dev)
+    ip, ip_un = ipa.get_image_embeds(clip_image_embeds=torch.stack([r.latent_la.reshape(-1) for r in reqs]), mode="global")
+    cond_ctx = torch.cat([cat([r.prompt_embeds for r in reqs]).to(torch.float16), ip], dim=1)              # ip_adapter.py:341-342
+    uncond_ctx = torch.cat([cat([r.negative_prompt_embeds for r in reqs]).to(torch.float16), ip_un], dim=1)
+    x = sample_batch(unet, cfgs, mixed, cond_ctx, uncond_ctx, cat([r.pooled_prompt_embeds for r in reqs]), cat([r.negative_pooled_prompt_embeds for r in reqs]),
+                     steps, [float(r.cfg) for r in reqs], [float(r.scale) for r in reqs])
+    return x, x_inv
 
 
 @torch.no_grad()
@@ -169,15 +234,10 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
     A request with a `seed` (and no `noise`) takes its mixing noise from its own Philox stream (noise.py, draw DRAW_POLAR) and is mixed on the device
     (`ia2p_polar_mix_v`: fp32, not the bits of the CPU fp16 mix): its inverted latents never leave the device, its result does not depend on the requests around
     it, and no rank needs to be seeded alike for it. Requests without a seed draw and mix as ever, also next to seeded ones in one group."""
-    from .pipeline import polar_intrtpolate
-    N = len(requests)
-    if N == 0:
-        raise ValueError("denoise_batch needs at least one request")
+    latents = [r.base_latents for r in requests]
+    _check_latents(latents, "denoise_batch")
     if pipeline.ip_adapter_xl is None:
         raise NotImplementedError("denoise_batch drives the IP-Adapter path (construct the pipeline with ip_ckpt=)")
-    shapes = {tuple(r.base_latents.shape[-2:]) for r in requests}
-    if len(shapes) != 1:
-        raise ValueError(f"requests of one call must share the latent size, got {sorted(shapes)}")
     for r in requests:
         if r.num_inference_steps is None or int(r.num_inference_steps) <= 0:
             raise ValueError(f"`num_inference_steps` has to be a positive integer but is {r.num_inference_steps}")
@@ -186,48 +246,11 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
             # behind do_classifier_free_guidance) -- while a batched group always evaluates [uncond | cond] and blends: not the same numbers. Say so instead.
             raise ValueError(f"denoise_batch blends eps_u + g (eps_c - eps_u) for every request; cfg={r.cfg} <= 1 means NO guidance in the reference: run that request "
                              f"through pipeline.denoise / __call__ instead")
-    if not 1 <= int(group) <= 8:
-        raise ValueError(f"group={group}: a group is one launch sequence of 1..8 requests (B_eff = 2 * group <= 16 rows, the limit of the image-projection and "
-                         f"embedding kernels)")
-    # polar-mixing noise comes from the global CPU RNG in REQUEST order (what N sequential reference calls would draw), on every rank alike
-    # (a request with a seed and no noise draws nothing here: its noise is made on the device below, from its own stream)
-    noises = [r.noise if r.noise is not None else None if r.seed is not None else torch.randn(r.base_latents.shape, dtype=torch.float16) for r in requests]
-    world, lo, hi = _shard(N, shard)
-    unet, cfgs = pipeline.pipe.unet, pipeline.pipe.scheduler.config
-    ipa = pipeline.ip_adapter_xl
-    dev = unet.device
-    outs, invs = [], []
-    for g0 in range(lo, hi, group):
-        reqs = requests[g0:min(g0 + group, hi)]
-        steps = [int(r.num_inference_steps) for r in reqs]
-        cat = lambda xs: torch.cat([x.to(dev) for x in xs], dim=0)
-        inv_ctx = cat([(r.inv_prompt_embeds if r.inv_prompt_embeds is not None else r.negative_prompt_embeds) for r in reqs])
-        inv_pool = cat([(r.inv_pooled_prompt_embeds if r.inv_pooled_prompt_embeds is not None else r.negative_pooled_prompt_embeds) for r in reqs])
-        x0 = cat([r.base_latents for r in reqs])
-        x_inv = invert_batch(unet, cfgs, x0, inv_ctx, inv_pool, steps)
-        own = [i for i in range(len(reqs)) if noises[g0 + i] is None]
-        if len(own) < len(reqs):
-            x_inv_cpu = x_inv.cpu()                                                             # pipeline.py:331
-        if not own:
-            mixed = torch.cat([polar_intrtpolate(x_inv_cpu[i:i + 1], noises[g0 + i].to(x_inv_cpu.dtype), r.alpha) for i, r in enumerate(reqs)], dim=0)
-        else:                            # seeded rows: noise and mix on the device, one launch each over those rows; the latents never leave it
-            z = _noise.randn_seeded([reqs[i].seed for i in own], _noise.DRAW_POLAR, x_inv.shape[1:], torch.float16, dev)
-            mixed = torch.empty_like(x_inv)
-            mixed[own] = _noise.polar_mix(x_inv[own] if len(own) < len(reqs) else x_inv, z, [float(reqs[i].alpha) for i in own])
-            for i, r in enumerate(reqs):
-                if noises[g0 + i] is not None:
-                    mixed[i:i + 1] = polar_intrtpolate(x_inv_cpu[i:i + 1], noises[g0 + i].to(x_inv_cpu.dtype), r.alpha).to(dev)
-        ip, ip_un = ipa.get_image_embeds(clip_image_embeds=torch.stack([r.latent_la.reshape(-1) for r in reqs]), mode="global")
-        cond_ctx = torch.cat([cat([r.prompt_embeds for r in reqs]).to(torch.float16), ip], dim=1)              # ip_adapter.py:341-342
-        uncond_ctx = torch.cat([cat([r.negative_prompt_embeds for r in reqs]).to(torch.float16), ip_un], dim=1)
-        x = sample_batch(unet, cfgs, mixed, cond_ctx, uncond_ctx, cat([r.pooled_prompt_embeds for r in reqs]), cat([r.negative_pooled_prompt_embeds for r in reqs]),
-                         steps, [float(r.cfg) for r in reqs], [float(r.scale) for r in reqs])
-        outs.append(x)
-        invs.append(x_inv)
-    like = requests[0].base_latents
-    empty = torch.empty((0,) + tuple(like.shape[1:]), dtype=torch.float16, device=dev)
-    out, inv = (torch.cat(outs) if outs else empty), (torch.cat(invs) if invs else empty)
-    return _gather_shards(out, N, world), _gather_shards(inv, N, world)
+    _check_group(group, "denoise_batch")
+    # polar-mixing noise comes from the global CPU RNG in REQUEST order (what N sequential reference calls would draw), on every rank alike; a request with a
+    # seed and no noise draws nothing here: its noise is made on the device in its group, from its own stream
+    noises = _noise.host_noises([r.noise for r in requests], [x.shape for x in latents], [r.seed for r in requests])
+    return _run_groups(requests, latents[0], pipeline.pipe.unet, group, shard, lambda g0, reqs: _denoise_group(pipeline, reqs, noises[g0:g0 + len(reqs)]), n_out=2)
 
 
 # ---- the stages after the hot segment, batched the same way: refiner pass and subject-consistency inpainting ---------------------------------------------
@@ -236,15 +259,11 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
 # (g, 1, 0) (and, in the inpaint loop, blended with (1, 0)), which returns its latents bit for bit while the others finish.
 
 def _kept_steps(num_inference_steps: int, strength: float, request: int):
-    """`get_timesteps` of the img2img / inpaint pipelines: (t_start, number of steps kept); the serial pipelines' errors, naming the request"""
+    """`scheduler.kept_steps` with the serial pipelines' two refusals, naming the request"""
     if strength < 0 or strength > 1:
         raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength} (request {request})")
-    init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
-    t_start = max(num_inference_steps - init_timestep, 0)
-    n_steps = num_inference_steps - t_start
-    if n_steps < 1:
-        raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
-                         f"{n_steps} which is < 1 and not appropriate for this pipeline. (request {request})")
+    t_start, n_steps = kept_steps(num_inference_steps, strength)
+    check_kept_steps(n_steps, strength, f" (request {request})")
     return t_start, n_steps
 
 
@@ -286,31 +305,11 @@ def refine_tables(scheduler_config, strengths: Sequence[float], num_inference_st
     sch = EulerDiscreteScheduler.from_config(scheduler_config)
     sch.set_timesteps(num_inference_steps)
     kept = [_kept_steps(num_inference_steps, float(s), i) for i, s in enumerate(strengths)]
-    nmax, g = max(n for _, n in kept), float(guidance_scale)
-    tb = RefineTables([n for _, n in kept], [], [[0.0] * len(kept) for _ in range(nmax)], [[1.0] * len(kept) for _ in range(nmax)],
-                      [[(g, 1.0, 0.0)] * len(kept) for _ in range(nmax)])
-    for r, (t_start, n) in enumerate(kept):
-        tb.start_sigma.append(float(sch.sigmas[sch.index_for_timestep(sch.timesteps[t_start])]))
-        for k in range(nmax):
-            idx = t_start + min(k, n - 1)
-            tb.timesteps[k][r], tb.input_scale[k][r] = float(sch.timesteps[idx]), sch.input_scale(idx)
-            if k < n:
-                tb.coef[k][r] = (g,) + tuple(sch.step_coeffs(idx))
-    return tb
-
-
-def _draw_noises(given: Sequence[Optional[torch.Tensor]], latents: Sequence[torch.Tensor], seeds: Optional[Sequence[Optional[int]]] = None, draws=None, device=None):
-    """missing noises from the global CPU RNG in REQUEST order (what the serial pipelines draw, one call after the other), on every rank alike.
-    A request with a seed (and no noise given) draws nothing from it: its noise is draw `draws[i]` of its own stream, made on `device` in one launch
-    for all such requests."""
-    seeds = [None] * len(given) if seeds is None else list(seeds)
-    out = [n if n is not None else None if s is not None else torch.randn(x.shape, dtype=torch.float16) for n, x, s in zip(given, latents, seeds)]
-    own = [i for i, n in enumerate(out) if n is None]
-    if own:
-        z = _noise.randn_seeded([seeds[i] for i in own], [draws[i] for i in own], latents[own[0]].shape[1:], torch.float16, device)
-        for j, i in enumerate(own):
-            out[i] = z[j:j + 1]
-    return out
+    g = float(guidance_scale)
+    records = [[(float(sch.timesteps[i]), sch.input_scale(i), (g,) + tuple(sch.step_coeffs(i))) for i in range(t_start, t_start + n)] for t_start, n in kept]
+    hold = [rec[-1][:2] + ((g, 1.0, 0.0),) for rec in records]
+    return RefineTables([n for _, n in kept], [float(sch.sigmas[sch.index_for_timestep(sch.timesteps[t_start])]) for t_start, _ in kept],
+                        *_joint_tables(records, hold))
 
 
 @torch.no_grad()
@@ -318,16 +317,13 @@ def _refine_group(piperf, reqs: List[RefineRequest], noises, tb: RefineTables, a
     from .img2img import get_add_time_ids_aesthetic
     unet = piperf.unet
     dev, n = unet.device, len(reqs)
-    f16 = lambda t: t.to(device=dev, dtype=torch.float16)
-    cat = lambda xs: torch.cat([f16(x) for x in xs], dim=0).contiguous()
-    lat, noise = cat([r.latents for r in reqs]), cat(noises)
+    lat, noise = _rows([r.latents for r in reqs], dev), _rows(noises, dev)
     size = (lat.shape[-2] * piperf.vae_scale_factor, lat.shape[-1] * piperf.vae_scale_factor)
     ids, neg_ids = get_add_time_ids_aesthetic(unet, size, (0, 0), size, aesthetic_score, negative_aesthetic_score, size, (0, 0), size,
                                               int(reqs[0].pooled_prompt_embeds.shape[-1]), piperf.config.requires_aesthetics_score)
-    ctx = torch.cat([cat([r.negative_prompt_embeds for r in reqs]), cat([r.prompt_embeds for r in reqs])], dim=0).contiguous()
-    pooled = torch.cat([cat([r.negative_pooled_prompt_embeds for r in reqs]), cat([r.pooled_prompt_embeds for r in reqs])], dim=0).contiguous()
-    added = {"text_embeds": pooled, "time_ids": torch.cat([neg_ids.repeat(n, 1), ids.repeat(n, 1)], dim=0).to(dev)}
-    ts_all = torch.tensor([row + row for row in tb.timesteps], dtype=torch.float32).to(dev).contiguous()
+    ctx, added = conditioning(dev, _rows([r.prompt_embeds for r in reqs], dev), _rows([r.pooled_prompt_embeds for r in reqs], dev), ids,
+                              _rows([r.negative_prompt_embeds for r in reqs], dev), _rows([r.negative_pooled_prompt_embeds for r in reqs], dev), neg_ids)
+    ts_all = _coef_table([row + row for row in tb.timesteps], dev)
     scale_all = _coef_table([[(1.0, s, 0.0) for s in row] for row in tb.input_scale], dev)
     coef_all = _coef_table(tb.coef, dev)
     x, nxt = torch.empty_like(lat), torch.empty_like(lat)
@@ -348,21 +344,16 @@ def refine_batch(piperf, requests: List[RefineRequest], group: int = 4, shard: b
     """The refiner's Euler img2img loop (`StableDiffusionXLImg2ImgPipeline.__call__`, reference pipeline.py:358-361) for N requests: one UNet evaluation at
     B_eff = 2 n per iteration of a group, request r on its own `strength`-shortened tail of the shared 50-step schedule. The per-call values are the class
     defaults the reference runs with. -> refined latents [N, 4, h, w] in request order on every rank."""
-    _check_latents([r.latents for r in requests], "refine_batch")
+    latents = [r.latents for r in requests]
+    _check_latents(latents, "refine_batch")
     _check_group(group, "refine_batch")
     _check_loop_args(num_inference_steps, guidance_scale, "refine_batch")
-    N = len(requests)
-    refine_tables(piperf.scheduler.config, [r.strength for r in requests], num_inference_steps, guidance_scale)      # every request's refusal before any launch
-    noises = _draw_noises([r.noise for r in requests], [r.latents for r in requests], [r.seed for r in requests], [_noise.DRAW_REFINER] * N, piperf.unet.device)
-    world, lo, hi = _shard(N, shard)
-    outs = []
-    for g0 in range(lo, hi, group):
-        reqs = requests[g0:min(g0 + group, hi)]
-        tb = refine_tables(piperf.scheduler.config, [r.strength for r in reqs], num_inference_steps, guidance_scale)
-        outs.append(_refine_group(piperf, reqs, noises[g0:g0 + len(reqs)], tb, aesthetic_score, negative_aesthetic_score))
-    dev = piperf.unet.device
-    out = torch.cat(outs) if outs else torch.empty((0,) + tuple(requests[0].latents.shape[1:]), dtype=torch.float16, device=dev)
-    return _gather_shards(out, N, world)
+    tables = lambda reqs: refine_tables(piperf.scheduler.config, [r.strength for r in reqs], num_inference_steps, guidance_scale)
+    tables(requests)                                                                                           # every request's refusal before any launch
+    noises = _noise.resolve_noises([r.noise for r in requests], [x.shape for x in latents], [r.seed for r in requests], [_noise.DRAW_REFINER] * len(requests),
+                                   piperf.unet.device)
+    return _run_groups(requests, latents[0], piperf.unet, group, shard, lambda g0, reqs: (_refine_group(
+        piperf, reqs, noises[g0:g0 + len(reqs)], tables(reqs), aesthetic_score, negative_aesthetic_score),))[0]
 
 
 @dataclass
@@ -396,44 +387,35 @@ def inpaint_tables(scheduler_config, strengths: Sequence[float], num_inference_s
     sch = DDIMScheduler.from_config(scheduler_config)
     sch.set_timesteps(num_inference_steps)
     kept = [_kept_steps(num_inference_steps, float(s), i) for i, s in enumerate(strengths)]
-    nmax, g = max(n for _, n in kept), float(guidance_scale)
-    tb = InpaintTables([n for _, n in kept], [], [[0.0] * len(kept) for _ in range(nmax)], [[(g, 1.0, 0.0)] * len(kept) for _ in range(nmax)],
-                       [[(1.0, 0.0)] * len(kept) for _ in range(nmax)])
-    for r, ((t_start, n), s) in enumerate(zip(kept, strengths)):
+    g, start, records = float(guidance_scale), [], []
+    for (t_start, n), s in zip(kept, strengths):
         tail = [int(t) for t in sch.timesteps[t_start:]]
-        tb.start.append((1.0, 0.0, float(sch.init_noise_sigma)) if float(s) == 1.0 else (1.0,) + tuple(sch.add_noise_coeffs(tail[0])))
-        for k in range(nmax):
-            tb.timesteps[k][r] = float(tail[min(k, n - 1)])
-            if k < n:
-                tb.coef[k][r] = (g,) + tuple(sch.step_coeffs(tail[k]))
-                if k < n - 1:
-                    tb.blend[k][r] = tuple(sch.add_noise_coeffs(tail[k + 1]))
-    return tb
+        start.append((1.0, 0.0, float(sch.init_noise_sigma)) if float(s) == 1.0 else (1.0,) + tuple(sch.add_noise_coeffs(tail[0])))
+        blend = [tuple(sch.add_noise_coeffs(t)) for t in tail[1:]] + [(1.0, 0.0)]                    # no re-noising after the last step
+        records.append([(float(t), (g,) + tuple(sch.step_coeffs(t)), b) for t, b in zip(tail, blend)])
+    hold = [(rec[-1][0], (g, 1.0, 0.0), (1.0, 0.0)) for rec in records]
+    return InpaintTables([n for _, n in kept], start, *_joint_tables(records, hold))
 
 
 @torch.no_grad()
 def _inpaint_group(ipa, reqs: List[InpaintRequest], noises, tb: InpaintTables, scale: float):
     from .inpaint import prepare_mask
-    from .scheduler import mask_blend_v
     unet = ipa.pipe.unet
     dev, n = unet.device, len(reqs)
-    f16 = lambda t: t.to(device=dev, dtype=torch.float16)
-    cat = lambda xs: torch.cat([f16(x) for x in xs], dim=0).contiguous()
-    lat, noise = cat([r.latents for r in reqs]), cat(noises)
+    lat, noise = _rows([r.latents for r in reqs], dev), _rows(noises, dev)
     h, w = lat.shape[-2:]
     mask = torch.cat([prepare_mask(r.mask, h, w, dev) for r in reqs], dim=0).contiguous()
     if tuple(mask.shape) != (n, 1, h, w):
         raise ValueError(f"every request carries ONE mask, got {tuple(mask.shape)} for {n} requests")
     # the subjects' 'local' image tokens, one call per group, with the crop weights IPAdapterXL.generate passes (scale_g = 1.0, scale_l = 0.5)
     ip, ip_un = ipa.get_image_embeds(clip_image_embeds_local=torch.stack([r.subject_embed.reshape(-1) for r in reqs]), mode="local", scale_g=1.0, scale_l=0.5)
-    ctx = torch.cat([torch.cat([cat([r.negative_prompt_embeds for r in reqs]), ip_un], dim=1),
-                     torch.cat([cat([r.prompt_embeds for r in reqs]), ip], dim=1)], dim=0).contiguous()             # ip_adapter.py:341-342
-    pooled = torch.cat([cat([r.negative_pooled_prompt_embeds for r in reqs]), cat([r.pooled_prompt_embeds for r in reqs])], dim=0).contiguous()
     size = (h * ipa.pipe.vae_scale_factor, w * ipa.pipe.vae_scale_factor)
-    tid = get_add_time_ids(unet, size, (0, 0), size, int(reqs[0].pooled_prompt_embeds.shape[-1])).repeat(2 * n, 1).to(dev)
-    added = {"text_embeds": pooled, "time_ids": tid}
+    ctx, added = conditioning(dev, torch.cat([_rows([r.prompt_embeds for r in reqs], dev), ip], dim=1), _rows([r.pooled_prompt_embeds for r in reqs], dev),
+                              get_add_time_ids(unet, size, (0, 0), size, int(reqs[0].pooled_prompt_embeds.shape[-1])),
+                              torch.cat([_rows([r.negative_prompt_embeds for r in reqs], dev), ip_un], dim=1),                 # ip_adapter.py:341-342
+                              _rows([r.negative_pooled_prompt_embeds for r in reqs], dev))
     sc = torch.full((2 * n,), float(scale), dtype=torch.float32).to(dev)
-    ts_all = torch.tensor([row + row for row in tb.timesteps], dtype=torch.float32).to(dev).contiguous()
+    ts_all = _coef_table([row + row for row in tb.timesteps], dev)
     coef_all, blend_all = _coef_table(tb.coef, dev), _coef_table(tb.blend, dev)
     x = torch.empty_like(lat)
     fused_update_v(lat, noise, None, _coef_table(tb.start, dev), x)
@@ -454,22 +436,14 @@ def inpaint_batch(ipa, requests: List[InpaintRequest], group: int = 4, shard: bo
     schedule with its own mask and subject tokens. `ipa` is the adapter over the inpainting pipeline (`InstructAny2PixPipeline.ip_adapter_xl_inpaint`); steps,
     guidance and IP scale are what `subject_consistency` passes. The processors' own scale is left alone: the IP scale goes in per row.
     -> latents [N, 4, h, w] in request order on every rank."""
-    _check_latents([r.latents for r in requests], "inpaint_batch")
+    latents, unet = [r.latents for r in requests], ipa.pipe.unet
+    _check_latents(latents, "inpaint_batch")
     _check_group(group, "inpaint_batch")
     _check_loop_args(num_inference_steps, guidance_scale, "inpaint_batch")
-    N = len(requests)
-    cfgs = ipa.pipe.scheduler.config
-    inpaint_tables(cfgs, [r.strength for r in requests], num_inference_steps, guidance_scale)                  # every request's refusal before any launch
-    noises = _draw_noises([r.noise for r in requests], [r.latents for r in requests], [r.seed for r in requests], [r.draw for r in requests], ipa.pipe.unet.device)
-    world, lo, hi = _shard(N, shard)
-    outs = []
-    for g0 in range(lo, hi, group):
-        reqs = requests[g0:min(g0 + group, hi)]
-        tb = inpaint_tables(cfgs, [r.strength for r in reqs], num_inference_steps, guidance_scale)
-        outs.append(_inpaint_group(ipa, reqs, noises[g0:g0 + len(reqs)], tb, scale))
-    dev = ipa.pipe.unet.device
-    out = torch.cat(outs) if outs else torch.empty((0,) + tuple(requests[0].latents.shape[1:]), dtype=torch.float16, device=dev)
-    return _gather_shards(out, N, world)
+    tables = lambda reqs: inpaint_tables(ipa.pipe.scheduler.config, [r.strength for r in reqs], num_inference_steps, guidance_scale)
+    tables(requests)                                                                                           # every request's refusal before any launch
+    noises = _noise.resolve_noises([r.noise for r in requests], [x.shape for x in latents], [r.seed for r in requests], [r.draw for r in requests], unet.device)
+    return _run_groups(requests, latents[0], unet, group, shard, lambda g0, reqs: (_inpaint_group(ipa, reqs, noises[g0:g0 + len(reqs)], tables(reqs), scale),))[0]
 
 
 # ---- whole edit requests ---------------------------------------------------------------------------------------------------------------------------------
@@ -508,19 +482,15 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
                scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None):
     """`InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
     See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding)."""
-    from .image_processor import OUTPUT_TYPES, requantize
-    from .pipeline import _need, fuse_instruction_embedding, to_8bit_image
-    from .prior import MODALITY
+    from . import pipeline as P
+    from .image_processor import requantize
     insts, mm_datas = list(insts), list(mm_datas)
     N = len(insts)
     if N == 0:
         raise ValueError("edit_batch needs at least one request")
     if len(mm_datas) != N:
         raise ValueError(f"{N} instructions for {len(mm_datas)} mm_data lists")
-    if output_type not in OUTPUT_TYPES:
-        raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
-    if output_type != "latent" and pipeline.vae is None:
-        raise ValueError(f"output_type={output_type!r} needs the pipeline built with vae=<HipAutoencoderKL>")
+    P.check_output_type(pipeline, output_type)
     _check_group(group, "edit_batch")
     seeds = _noise.resolve_seeds(seeds, N)
     seeded = any(s is not None for s in seeds)
@@ -551,42 +521,22 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     live = [i for i in range(N) if results[i] is None]
     if not live:
         return results
-    latent_la = {}
-    for i in live:                                                                             # the prior runs per request (reference :313-317)
-        c, y0 = cs[i], cs[i].get("y")
-        if y0 is None:
-            if pipeline.model is None:
-                raise NotImplementedError("the conditioner returned no `y` and no prior= was attached")
-            ie = c["image_embeds"]
-            y = pipeline.model.generate_diffusion(MODALITY.VIDEO, MODALITY.IMAGE, ie / ie.norm() * 100, device="cpu", no_diffusion=True,
-                                                  num_inference_steps=25, image_bind_overwrite=None, dtype=torch.float32, guidance_scale=10,
-                                                  force_guidence_t0=True, do_classifier_free_guidance=True, score=6.5)
-            y0 = y[0].to(device=c["base_embed"].device, dtype=c["base_embed"].dtype)
-        latent_la[i] = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], y0, h[i], norm[i])
+    # the prior runs per request (reference :313-317)
+    latent_la = {i: P.fuse_instruction_embedding(cs[i]["base_embed"], cs[i]["image_embeds"], P.prior_y0(pipeline, cs[i]), h[i], norm[i]) for i in live}
 
     # ---- base images -> latents, the images among them encoded in batches (posterior samples: global RNG, request order) -----------------------------------
     base = {i: cs[i]["base_latents"] for i in live if cs[i].get("base_latents") is not None}
     todo = [i for i in live if i not in base]
     if todo:
-        imgs = []
-        for i in todo:
-            img = cs[i].get("base_image")
-            if img is None and cs[i].get("base_img_path") is not None:
-                img = pipeline.loas_base_img(cs[i]["base_img_path"])
-            if img is None:
-                raise KeyError(f"the conditioner returned none of base_latents / base_image / base_img_path (request {i})")
-            if pipeline.vae is None:
-                raise ValueError("a base_image / base_img_path needs the pipeline built with vae=<HipAutoencoderKL>")
-            imgs.append(pipeline.pipe_inversion.image_processor.preprocess(img))
+        imgs = [P.base_image(pipeline, cs[i], f" (request {i})") for i in todo]                   # (every refusal before the image processor is touched)
+        imgs = [pipeline.pipe_inversion.image_processor.preprocess(img) for img in imgs]
         enc = _vae_in_batches(pipeline, pipeline.pipe_inversion._vae_encode, torch.cat(imgs, dim=0), group, False,
                               seeds=[seeds[i] for i in todo], draw=_noise.DRAW_BASE_POSTERIOR)
         base.update({i: enc[j:j + 1] for j, i in enumerate(todo)})
     _check_latents([base[i] for i in live], "edit_batch")
 
     # ---- the hot segment ---------------------------------------------------------------------------------------------------------------------------------
-    reqs = [EditRequest(base_latents=base[i], latent_la=latent_la[i].reshape(1, -1)[0], prompt_embeds=cs[i]["prompt_embeds"],
-                        pooled_prompt_embeds=cs[i]["pooled_prompt_embeds"], negative_prompt_embeds=cs[i]["negative_prompt_embeds"],
-                        negative_pooled_prompt_embeds=cs[i]["negative_pooled_prompt_embeds"], inv_prompt_embeds=cs[i].get("inv_prompt_embeds"),
+    reqs = [EditRequest(base_latents=base[i], latent_la=latent_la[i].reshape(1, -1)[0], **P.embeds(cs[i]), inv_prompt_embeds=cs[i].get("inv_prompt_embeds"),
                         inv_pooled_prompt_embeds=cs[i].get("inv_pooled_prompt_embeds"), alpha=alpha[i], num_inference_steps=int(steps[i]), cfg=float(cfg[i]),
                         scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i]) for i in live]
     pipeline.pipe_inversion.unet = pipeline.pipe.unet
@@ -599,24 +549,16 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     # ---- refiner pass for the requests that ask for it -----------------------------------------------------------------------------------------------------
     ref = [i for i in live if float(refinement[i]) > 0]
     if ref:
-        keys = ("refiner_prompt_embeds", "refiner_pooled_prompt_embeds", "refiner_negative_prompt_embeds", "refiner_negative_pooled_prompt_embeds")
         for i in ref:
-            _need(cs[i], keys, "refiner pass")
+            P._need(cs[i], P.REFINER_KEYS, "refiner pass")
         piperf = pipeline.piperf
         start = torch.cat([non_refined[i] for i in ref], dim=0)
-        vae_route = pipeline.refiner_handoff == "image" and pipeline.pipe._vae_decode is not None and piperf._vae_encode is not None
-        if pipeline.refiner_handoff == "image" and not vae_route and not pipeline._warned_handoff:
-            import warnings
-            warnings.warn("refiner_handoff='image' needs vae_decode= on the base pipeline and vae_encode= on the refiner pipeline; handing the "
-                          "latents over directly instead (pass refiner_handoff='latent' to choose this route explicitly)", RuntimeWarning, stacklevel=2)
-            pipeline._warned_handoff = True
-        if vae_route:                # the reference's hand-over: decode, 8-bit image, re-encode (a posterior SAMPLE: global RNG, request order)
+        if P.refiner_handoff_by_image(pipeline):     # the reference's hand-over: decode, 8-bit image, re-encode (a posterior SAMPLE: global RNG, request order)
             dec = _vae_in_batches(pipeline, pipeline.pipe._vae_decode, start, group, True)
             decoded.update({i: dec[j:j + 1] for j, i in enumerate(ref)})
-            img8 = requantize(dec) if pipeline.vae is not None else to_8bit_image(dec)
+            img8 = requantize(dec) if pipeline.vae is not None else P.to_8bit_image(dec)
             start = _vae_in_batches(pipeline, piperf._vae_encode, img8, group, False, seeds=[seeds[i] for i in ref], draw=_noise.DRAW_HANDOFF_POSTERIOR)
-        rr = [RefineRequest(latents=start[j:j + 1], prompt_embeds=cs[i][keys[0]], pooled_prompt_embeds=cs[i][keys[1]], negative_prompt_embeds=cs[i][keys[2]],
-                            negative_pooled_prompt_embeds=cs[i][keys[3]], strength=float(refinement[i]), noise=cs[i].get("refiner_noise"), seed=seeds[i])
+        rr = [RefineRequest(latents=start[j:j + 1], **P.embeds(cs[i], "refiner_"), strength=float(refinement[i]), noise=cs[i].get("refiner_noise"), seed=seeds[i])
               for j, i in enumerate(ref)]
         refined = refine_batch(piperf, rr, group=group, shard=shard)
         oo.update({i: refined[j:j + 1] for j, i in enumerate(ref)})
@@ -624,15 +566,13 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     # ---- subject consistency: every request's masks first, then pass k over the requests with more than k subjects ---------------------------------------
     sub = [i for i in live if float(subject_strength[i]) > 0 and len(cs[i].get("subject_data") or []) > 0]
     if sub:
-        keys = ("subject_prompt_embeds", "subject_pooled_prompt_embeds", "subject_negative_prompt_embeds", "subject_negative_pooled_prompt_embeds")
         pairs = {}
         for i in sub:
-            _need(cs[i], keys, "subject-consistency pass")
+            P._need(cs[i], P.SUBJECT_KEYS, "subject-consistency pass")
             pairs[i] = pipeline._subject_mask_pairs(cs[i], cs[i]["subject_data"], oo[i])
         for k in range(max(len(p) for p in pairs.values())):
             now = [i for i in sub if len(pairs[i]) > k]
-            ir = [InpaintRequest(latents=oo[i], mask=pairs[i][k][0], subject_embed=pairs[i][k][1], prompt_embeds=cs[i][keys[0]], pooled_prompt_embeds=cs[i][keys[1]],
-                                 negative_prompt_embeds=cs[i][keys[2]], negative_pooled_prompt_embeds=cs[i][keys[3]], strength=float(subject_strength[i]),
+            ir = [InpaintRequest(latents=oo[i], mask=pairs[i][k][0], subject_embed=pairs[i][k][1], **P.embeds(cs[i], "subject_"), strength=float(subject_strength[i]),
                                  noise=cs[i].get("subject_noise"), seed=seeds[i], draw=_noise.inpaint_draw(k)) for i in now]
             painted = inpaint_batch(pipeline.ip_adapter_xl_inpaint, ir, group=group, shard=shard)
             oo.update({i: painted[j:j + 1] for j, i in enumerate(now)})

@@ -40,6 +40,26 @@ def get_add_time_ids(unet, original_size, crops_coords_top_left, target_size, pr
     return torch.tensor([add_time_ids], dtype=dtype)
 
 
+def expand_rows(t, batch: int):
+    """the embeddings of one prompt for every row of a serial call's batch"""
+    return t if t.shape[0] == batch else t.expand(batch, *([-1] * (t.ndim - 1)))
+
+
+def conditioning(device, prompt_embeds, pooled_prompt_embeds, time_ids, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None, negative_time_ids=None):
+    """What every loop, serial or batched, hands the UNet next to the latents: -> (context, added_cond_kwargs), contiguous fp16 on `device`.
+    The embeddings come batched, [B, ...] (a serial pipeline's expanded to its batch, a group's concatenated over its requests); `time_ids` is ONE row.
+    With the negative embeddings the rows are [uncond x B | cond x B] (the reference's cat([negative, positive]), sdxl_pipeline.py:800-803) and the
+    uncond half carries `negative_time_ids` where the refiner gives some; without them the evaluation is unguided: the B cond rows alone."""
+    f16 = lambda t: t.to(device=device, dtype=torch.float16)
+    B = prompt_embeds.shape[0]
+    ctx, pooled, tid = f16(prompt_embeds), f16(pooled_prompt_embeds), time_ids.repeat(B, 1)
+    if negative_prompt_embeds is not None:
+        ctx = torch.cat([f16(negative_prompt_embeds), ctx], dim=0)
+        pooled = torch.cat([f16(negative_pooled_prompt_embeds), pooled], dim=0)
+        tid = torch.cat([(time_ids if negative_time_ids is None else negative_time_ids).repeat(B, 1), tid], dim=0)
+    return ctx.contiguous(), {"text_embeds": pooled.contiguous(), "time_ids": tid.to(device)}
+
+
 class _PipelineBase:
     vae_scale_factor = 8
     vae = None
@@ -150,16 +170,9 @@ class SDXLDDIMPipeline(_PipelineBase):
         height, width = latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor
         original_size = original_size or (height, width)
         target_size = target_size or (height, width)
-        add_time_ids = get_add_time_ids(self.unet, original_size, crops_coords_top_left, target_size,
-                                        int(pooled_prompt_embeds.shape[-1])).repeat(batch, 1).to(dev)   # :228-240
-        prompt_embeds = prompt_embeds.to(device=dev, dtype=torch.float16)
-        if prompt_embeds.shape[0] != batch:
-            prompt_embeds = prompt_embeds.expand(batch, -1, -1)
-        add_text_embeds = pooled_prompt_embeds.to(device=dev, dtype=torch.float16)
-        if add_text_embeds.shape[0] != batch:
-            add_text_embeds = add_text_embeds.expand(batch, -1)
-        prompt_embeds, add_text_embeds = prompt_embeds.contiguous(), add_text_embeds.contiguous()
-        added = {"text_embeds": add_text_embeds, "time_ids": add_time_ids}       # `image_embeds` zeros (:246-248) are ignored by a text_time UNet
+        add_time_ids = get_add_time_ids(self.unet, original_size, crops_coords_top_left, target_size, int(pooled_prompt_embeds.shape[-1]))      # :228-240
+        # unguided; `image_embeds` zeros (:246-248) are ignored by a text_time UNet
+        prompt_embeds, added = conditioning(dev, expand_rows(prompt_embeds, batch), expand_rows(pooled_prompt_embeds, batch), add_time_ids)
 
         eps = torch.empty_like(latents)
         nxt = torch.empty_like(latents)
@@ -222,16 +235,8 @@ class StableDiffusionXLPipeline(_PipelineBase):
         target_size = target_size or (height, width)
         add_time_ids = get_add_time_ids(self.unet, original_size, crops_coords_top_left, target_size,
                                         int(pooled_prompt_embeds.shape[-1]))
-        f16 = lambda t: t.to(device=dev, dtype=torch.float16)
-        add_text_embeds = f16(pooled_prompt_embeds)
-        prompt_embeds = f16(prompt_embeds)
-        if do_cfg:                                                                              # :800-803
-            prompt_embeds = torch.cat([f16(negative_prompt_embeds), prompt_embeds], dim=0)
-            add_text_embeds = torch.cat([f16(negative_pooled_prompt_embeds), add_text_embeds], dim=0)
-            add_time_ids = torch.cat([add_time_ids, add_time_ids], dim=0)
-        add_time_ids = add_time_ids.to(dev).repeat(batch, 1)                                    # :807
-        prompt_embeds, add_text_embeds = prompt_embeds.contiguous(), add_text_embeds.contiguous()
-        added = {"text_embeds": add_text_embeds, "time_ids": add_time_ids}
+        neg = (negative_prompt_embeds, negative_pooled_prompt_embeds) if do_cfg else ()          # :800-807
+        prompt_embeds, added = conditioning(dev, prompt_embeds, pooled_prompt_embeds, add_time_ids, *neg)
 
         B = latents.shape[0]
         if do_cfg:

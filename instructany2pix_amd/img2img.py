@@ -19,8 +19,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import noise as _noise
-from .ddim import StableDiffusionXLPipelineOutput, _PipelineBase
-from .scheduler import EulerDiscreteScheduler, fused_update
+from .ddim import StableDiffusionXLPipelineOutput, _PipelineBase, conditioning, expand_rows
+from .scheduler import EulerDiscreteScheduler, check_kept_steps, fused_update, kept_steps
 
 
 def get_add_time_ids_aesthetic(unet, original_size, crops_coords_top_left, target_size, aesthetic_score, negative_aesthetic_score,
@@ -56,9 +56,8 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
         self.config = type("Config", (), {"requires_aesthetics_score": requires_aesthetics_score})()
 
     def get_timesteps(self, num_inference_steps: int, strength: float):
-        init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
-        t_start = max(num_inference_steps - init_timestep, 0)
-        return self.scheduler.timesteps[t_start * self.scheduler.order:], num_inference_steps - t_start, t_start
+        t_start, n_steps = kept_steps(num_inference_steps, strength)
+        return self.scheduler.timesteps[t_start * self.scheduler.order:], n_steps, t_start
 
     @torch.no_grad()
     def __call__(self, prompt=None, image=None, strength: float = 0.3, num_inference_steps: int = 50, guidance_scale: float = 5.0,
@@ -88,9 +87,7 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
         dev = self.device
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         timesteps, n_steps, t_start = self.get_timesteps(num_inference_steps, strength)
-        if n_steps < 1:
-            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
-                             f"{n_steps} which is < 1 and not appropriate for this pipeline.")
+        check_kept_steps(n_steps, strength)
 
         # prepare_latents: encode, scale, add noise at the first kept timestep
         if latents is None:
@@ -100,13 +97,7 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
                 image, seeds=_noise.batch_seeds(noise_seed, None), draw=_noise.DRAW_HANDOFF_POSTERIOR)
         latents = latents.to(device=dev, dtype=torch.float16).contiguous()
         batch = latents.shape[0]
-        if noise is None and noise_seed is not None:
-            noise = _noise.randn_seeded(_noise.batch_seeds(noise_seed, batch), _noise.DRAW_REFINER if noise_draw is None else noise_draw, latents.shape[1:],
-                                        torch.float16, dev)
-        if noise is None:
-            g = generator if not isinstance(generator, list) else generator[0]
-            gen_dev = g.device if g is not None else torch.device("cpu")
-            noise = torch.randn(latents.shape, generator=g, device=gen_dev, dtype=torch.float16)
+        noise, = _noise.resolve_noises([noise], [latents.shape], [noise_seed], [_noise.DRAW_REFINER if noise_draw is None else noise_draw], dev, generator)
         noise = noise.to(device=dev, dtype=torch.float16).contiguous()
         x = self.scheduler.add_noise(latents, noise, timesteps[:1])
 
@@ -119,20 +110,8 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
                                                   negative_aesthetic_score, negative_original_size, negative_crops_coords_top_left,
                                                   negative_target_size, int(pooled_prompt_embeds.shape[-1]),
                                                   self.config.requires_aesthetics_score)
-        f16 = lambda t: t.to(device=dev, dtype=torch.float16)
-        prompt_embeds, add_text_embeds = f16(prompt_embeds), f16(pooled_prompt_embeds)
-        if prompt_embeds.shape[0] != batch:
-            prompt_embeds, add_text_embeds = prompt_embeds.expand(batch, -1, -1), add_text_embeds.expand(batch, -1)
-        add_time_ids = ids.repeat(batch, 1)
-        if do_cfg:
-            neg_e, neg_p = f16(negative_prompt_embeds), f16(negative_pooled_prompt_embeds)
-            if neg_e.shape[0] != batch:
-                neg_e, neg_p = neg_e.expand(batch, -1, -1), neg_p.expand(batch, -1)
-            prompt_embeds = torch.cat([neg_e, prompt_embeds], dim=0)
-            add_text_embeds = torch.cat([neg_p, add_text_embeds], dim=0)
-            add_time_ids = torch.cat([neg_ids.repeat(batch, 1), add_time_ids], dim=0)
-        added = {"text_embeds": add_text_embeds.contiguous(), "time_ids": add_time_ids.to(dev)}
-        prompt_embeds = prompt_embeds.contiguous()
+        neg = (expand_rows(negative_prompt_embeds, batch), expand_rows(negative_pooled_prompt_embeds, batch), neg_ids) if do_cfg else ()
+        prompt_embeds, added = conditioning(dev, expand_rows(prompt_embeds, batch), expand_rows(pooled_prompt_embeds, batch), ids, *neg)
 
         B = batch
         model_in = torch.empty((2 * B if do_cfg else B,) + tuple(x.shape[1:]), dtype=torch.float16, device=dev)

@@ -23,8 +23,8 @@ from typing import Optional
 import torch
 
 from . import noise as _noise
-from .ddim import StableDiffusionXLPipelineOutput, _PipelineBase, get_add_time_ids
-from .scheduler import DDIMScheduler, fused_update, mask_blend
+from .ddim import StableDiffusionXLPipelineOutput, _PipelineBase, conditioning, expand_rows, get_add_time_ids
+from .scheduler import DDIMScheduler, check_kept_steps, fused_update, kept_steps, mask_blend
 
 
 def prepare_mask(mask_image, h: int, w: int, device) -> torch.Tensor:
@@ -51,9 +51,8 @@ def _is_pil(x) -> bool:
 
 class StableDiffusionXLInpaintPipeline(_PipelineBase):
     def get_timesteps(self, num_inference_steps: int, strength: float):
-        init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
-        t_start = max(num_inference_steps - init_timestep, 0)
-        return self.scheduler.timesteps[t_start * self.scheduler.order:], num_inference_steps - t_start
+        t_start, n_steps = kept_steps(num_inference_steps, strength)
+        return self.scheduler.timesteps[t_start * self.scheduler.order:], n_steps
 
     @torch.no_grad()
     def __call__(self, prompt=None, image=None, mask_image=None, height=None, width=None, strength: float = 0.9999,
@@ -83,9 +82,7 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
         dev = self.device
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         timesteps, n_steps = self.get_timesteps(num_inference_steps, strength)
-        if n_steps < 1:
-            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
-                             f"{n_steps} which is < 1 and not appropriate for this pipeline.")
+        check_kept_steps(n_steps, strength)
         if latents is None:
             if image is None:
                 raise ValueError("inpainting needs `image` (with vae= or a vae_encode callable) or `latents`")
@@ -97,13 +94,7 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
         mask = prepare_mask(mask_image, h, w, dev)
         if mask.shape[0] != B:
             mask = mask.expand(B, -1, -1, -1).contiguous()
-        if noise is None and noise_seed is not None:
-            noise = _noise.randn_seeded(_noise.batch_seeds(noise_seed, B), _noise.DRAW_INPAINT if noise_draw is None else noise_draw, image_latents.shape[1:],
-                                        torch.float16, dev)
-        if noise is None:
-            g = generator if not isinstance(generator, list) else generator[0]
-            gen_dev = g.device if g is not None else torch.device("cpu")
-            noise = torch.randn(image_latents.shape, generator=g, device=gen_dev, dtype=torch.float16)
+        noise, = _noise.resolve_noises([noise], [image_latents.shape], [noise_seed], [_noise.DRAW_INPAINT if noise_draw is None else noise_draw], dev, generator)
         noise = noise.to(device=dev, dtype=torch.float16).contiguous()
         if strength == 1.0:
             x = (noise * self.scheduler.init_noise_sigma).contiguous()
@@ -114,20 +105,8 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
         original_size = original_size or (height, width)
         target_size = target_size or (height, width)
         add_time_ids = get_add_time_ids(self.unet, original_size, crops_coords_top_left, target_size, int(pooled_prompt_embeds.shape[-1]))
-        f16 = lambda t: t.to(device=dev, dtype=torch.float16)
-        prompt_embeds, add_text_embeds = f16(prompt_embeds), f16(pooled_prompt_embeds)
-        if prompt_embeds.shape[0] != B:
-            prompt_embeds, add_text_embeds = prompt_embeds.expand(B, -1, -1), add_text_embeds.expand(B, -1)
-        add_time_ids = add_time_ids.repeat(B, 1)
-        if do_cfg:
-            neg_e, neg_p = f16(negative_prompt_embeds), f16(negative_pooled_prompt_embeds)
-            if neg_e.shape[0] != B:
-                neg_e, neg_p = neg_e.expand(B, -1, -1), neg_p.expand(B, -1)
-            prompt_embeds = torch.cat([neg_e, prompt_embeds], dim=0)
-            add_text_embeds = torch.cat([neg_p, add_text_embeds], dim=0)
-            add_time_ids = torch.cat([add_time_ids, add_time_ids], dim=0)
-        added = {"text_embeds": add_text_embeds.contiguous(), "time_ids": add_time_ids.to(dev)}
-        prompt_embeds = prompt_embeds.contiguous()
+        neg = (expand_rows(negative_prompt_embeds, B), expand_rows(negative_pooled_prompt_embeds, B)) if do_cfg else ()
+        prompt_embeds, added = conditioning(dev, expand_rows(prompt_embeds, B), expand_rows(pooled_prompt_embeds, B), add_time_ids, *neg)
 
         model_in = torch.cat([x, x], dim=0) if do_cfg else x.clone()
         eps = torch.empty_like(model_in)

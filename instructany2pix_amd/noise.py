@@ -111,6 +111,32 @@ def randn_seeded(seeds: Sequence[int], draws, shape, dtype=torch.float16, device
     return out
 
 
+def host_noises(given, shapes, seeds, generator=None) -> list:
+    """The first two steps of the start-noise rule, per item (a request of a batch, or the whole batch of a serial call): a supplied tensor wins; an item
+    with a seed is left None (its noise is made on the device, `resolve_noises` or the caller's own launch) and draws NOTHING here; every other item draws
+    fp16 normals of its `shapes[i]` from `generator` (one, or a list whose first counts), else from torch's global CPU generator -- in item order, which
+    is what serial calls one after the other draw, on every rank alike."""
+    g = generator[0] if isinstance(generator, list) else generator
+    gen_dev = g.device if g is not None else torch.device("cpu")
+    return [n if n is not None or s is not None else torch.randn(tuple(shape), generator=g, device=gen_dev, dtype=torch.float16)
+            for n, shape, s in zip(given, shapes, seeds)]
+
+
+def resolve_noises(given, shapes, seeds, draws, device, generator=None) -> list:
+    """The start-noise rule of the serial pipelines and the batched loops: supplied `noise`, then the seed, then `generator` or the global RNG.
+    `seeds[i]`: None, an int (row b of the item draws from seed + b) or one seed per row (`batch_seeds`); `draws[i]`: the item's draw id. All host draws
+    come first (`host_noises`); the seeded items then share ONE `randn_seeded` launch on `device`."""
+    out = host_noises(given, shapes, seeds, generator)
+    own = [i for i, n in enumerate(out) if n is None]
+    if own:
+        rows = [batch_seeds(seeds[i], shapes[i][0]) for i in own]
+        ids = draws[own[0]] if len(own) == 1 else [draws[i] for i, r in zip(own, rows) for _ in r]      # (one item: one id for all its rows)
+        z = randn_seeded([s for r in rows for s in r], ids, tuple(shapes[own[0]][1:]), torch.float16, device)
+        for i, zi in zip(own, z.split([len(r) for r in rows])):
+            out[i] = zi
+    return out
+
+
 @torch.no_grad()
 def posterior_sample(moments: torch.Tensor, seeds: Sequence[int], draw, scaling_factor: float) -> torch.Tensor:
     """`DiagonalGaussianDistribution(moments).sample() * scaling_factor` with the normals of stream (seeds[b], draw) (`ia2p_posterior_sample_seeded`):

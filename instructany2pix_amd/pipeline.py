@@ -90,6 +90,83 @@ def _need(c, keys, stage):
         raise KeyError(f"the conditioner returned no {missing} (needed by the {stage}; pass refinement=0 / subject_strength=0 to skip that stage)")
 
 
+# ---- what `__call__` and `batch.edit_batch` share, request by request (functions of the pipeline object) -----------------------------------------------
+EMBED_KEYS = ("prompt_embeds", "pooled_prompt_embeds", "negative_prompt_embeds", "negative_pooled_prompt_embeds")
+REFINER_KEYS, SUBJECT_KEYS = tuple("refiner_" + k for k in EMBED_KEYS), tuple("subject_" + k for k in EMBED_KEYS)      # what `_need` asks of a conditioner per stage
+# the prompts around the LLM's caption (reference :342-345, :358-361); the inpaint pass runs IPAdapterXL.generate without a prompt: its defaults (ip_adapter.py)
+INVERSION_PROMPT, NEGATIVE_PROMPT = "", ""
+CAPTION_PREFIX = SUBJECT_PROMPT = "best quality, high quality"
+SUBJECT_NEGATIVE_PROMPT = "monochrome, lowres, bad anatomy, worst quality, low quality"
+REFINER_CAPTION_SUFFIX = ",high quality,well-formed,award-winning"
+
+
+def embeds(c, stage: str = "") -> dict:
+    """the four text embeddings of a stage ("", "refiner_", "subject_") of a conditioning dict, under the keyword names every loop takes them by"""
+    return {k: c[stage + k] for k in EMBED_KEYS}
+
+
+def check_output_type(pipeline, output_type):
+    if output_type not in OUTPUT_TYPES:
+        raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
+    if output_type != "latent" and pipeline.vae is None:
+        raise ValueError(f"output_type={output_type!r} needs the pipeline built with vae=<HipAutoencoderKL>")
+
+
+def prior_y0(pipeline, c):
+    """the conditioner's `y`, else the prior's one live call on the instruction embedding (reference :313-317)"""
+    if c.get("y") is not None:
+        return c["y"]
+    if pipeline.model is None:
+        raise NotImplementedError("the conditioner returned no `y` and no prior= was attached")
+    ie = c["image_embeds"]
+    y = pipeline.model.generate_diffusion(MODALITY.VIDEO, MODALITY.IMAGE, ie / ie.norm() * 100, device="cpu", no_diffusion=True,
+                                          num_inference_steps=25, image_bind_overwrite=None, dtype=torch.float32, guidance_scale=10,
+                                          force_guidence_t0=True, do_classifier_free_guidance=True, score=6.5)
+    return y[0].to(device=c["base_embed"].device, dtype=c["base_embed"].dtype)
+
+
+def base_image(pipeline, c, who: str = ""):
+    """the base image of a conditioning dict that carries no `base_latents`, not yet encoded: its `base_image` (PIL), else its `base_img_path` loaded by
+    `loas_base_img`; `who` names the request where several share a call"""
+    img = c.get("base_image")
+    if img is None and c.get("base_img_path") is not None:
+        img = pipeline.loas_base_img(c["base_img_path"])
+    if img is None:
+        raise KeyError(f"the conditioner returned none of base_latents / base_image / base_img_path{who}")
+    if pipeline.vae is None:
+        raise ValueError("a base_image / base_img_path needs the pipeline built with vae=<HipAutoencoderKL>")
+    return img
+
+
+def refiner_handoff_by_image(pipeline) -> bool:
+    """whether the base result reaches the refiner the reference's way (decode, 8-bit image, VAE re-encode with a posterior SAMPLE). Where that route was
+    asked for but cannot be taken, say so once: the latent route has different numerics and draws nothing from the RNG"""
+    vae_route = pipeline.refiner_handoff == "image" and pipeline.pipe._vae_decode is not None and pipeline.piperf._vae_encode is not None
+    if pipeline.refiner_handoff == "image" and not vae_route and not pipeline._warned_handoff:
+        import warnings
+        warnings.warn("refiner_handoff='image' needs vae_decode= on the base pipeline and vae_encode= on the refiner pipeline; handing the "
+                      "latents over directly instead (pass refiner_handoff='latent' to choose this route explicitly)", RuntimeWarning, stacklevel=3)
+        pipeline._warned_handoff = True
+    return vae_route
+
+
+def condition_from_llm_output(out, mm_data) -> dict:
+    """`forward_llm`'s five-tuple -> the LLM's part of the conditioning dict a `conditioner=` would return; without an `<im_gen>` only the caption counts.
+    `base_image`: the PIL image an mm_data entry carries for the base image's file; `subject_data`: the subjects that are image entries (:363-366)"""
+    image_embeds, base_embed, caption, base_img_path, extra_data = out
+    c = dict(image_embeds=image_embeds, base_embed=base_embed, caption=caption, base_img_path=base_img_path, extra_data=extra_data)
+    if image_embeds is None:
+        return c
+    c["image_embeds"], c["base_embed"] = image_embeds.reshape(1, -1), base_embed.reshape(1, -1)      # host fp32, as the reference holds them (:236, :253)
+    for e in mm_data:
+        if e.get("fname") == base_img_path and e.get("image") is not None:
+            c["base_image"] = e["image"]
+    if extra_data is not None and len(extra_data.get("extra_idx", [])) > 0:
+        c["subject_data"] = [(k, v) for (k, v, i) in zip(extra_data["all_objs"], extra_data["extra_embeds"], extra_data["extra_idx"])
+                             if mm_data[int(i)]["type"] == "image"]
+    return c
+
+
 def fuse_instruction_embedding(base_embed, image_embeds, y0, h, norm):
     """reference pipeline.py:322-324"""
     latent_la = base_embed * h[0] + image_embeds * h[1] + y0 / y0.norm() * 20.0 * h[2]
@@ -206,13 +283,7 @@ class InstructAny2PixPipeline:
         pipeline's image processor and the VAE (a posterior sample, as in the reference's `inverse(image=...)`; with `seed`, draw DRAW_BASE_POSTERIOR of it)"""
         if c.get("base_latents") is not None:
             return c["base_latents"]
-        img = c.get("base_image")
-        if img is None and c.get("base_img_path") is not None:
-            img = self.loas_base_img(c["base_img_path"])
-        if img is None:
-            raise KeyError("the conditioner returned none of base_latents / base_image / base_img_path")
-        if self.vae is None:
-            raise ValueError("a base_image / base_img_path needs the pipeline built with vae=<HipAutoencoderKL>")
+        img = base_image(self, c)
         return self.pipe_inversion._image_latents(img) if seed is None else self.pipe_inversion._image_latents(
             img, seeds=[_noise.check_seed(seed)], draw=_noise.DRAW_BASE_POSTERIOR)
 
@@ -325,32 +396,23 @@ class InstructAny2PixPipeline:
 
     def _condition_from_llm(self, inst, mm_data, use_cache, llm_only, seed=None):
         """the conditioning dict a `conditioner=` would return, from forward_llm + the attached text encoders (:309-310, :330, :342-345, :358-361)"""
-        image_embeds, base_embed, output_caption, base_img_path, extra_data = self.forward_llm(inst, mm_data, use_cache=use_cache, **({} if seed is None else {"seed": seed}))
-        self.cache = image_embeds, base_embed, output_caption, base_img_path, extra_data
-        c = dict(image_embeds=image_embeds, base_embed=base_embed, caption=output_caption, base_img_path=base_img_path, extra_data=extra_data)
+        self.cache = self.forward_llm(inst, mm_data, use_cache=use_cache, **({} if seed is None else {"seed": seed}))
+        c = condition_from_llm_output(self.cache, mm_data)
         if llm_only:
             return c
-        if image_embeds is None:
-            raise RuntimeError(f"the LLM produced no <im_gen>: {output_caption!r}")
+        if c["image_embeds"] is None:
+            raise RuntimeError(f"the LLM produced no <im_gen>: {c['caption']!r}")
         if self._text_encoder is None:
             raise ValueError("a pipeline built with llm= needs text_encoder=<encode_prompt callable> for the denoise stages")
-        c["image_embeds"], c["base_embed"] = image_embeds.reshape(1, -1), base_embed.reshape(1, -1)      # host fp32, as the reference holds them (:236, :253)
-        for e in mm_data:
-            if e.get("fname") == base_img_path and e.get("image") is not None:
-                c["base_image"] = e["image"]
-        pe, ne, pp, npl = self._text_encoder(prompt="best quality, high quality" + output_caption, negative_prompt="", do_classifier_free_guidance=True)
-        ipe, _, ipp, _ = self._text_encoder(prompt="", do_classifier_free_guidance=False)
+        pe, ne, pp, npl = self._text_encoder(prompt=CAPTION_PREFIX + c["caption"], negative_prompt=NEGATIVE_PROMPT, do_classifier_free_guidance=True)
+        ipe, _, ipp, _ = self._text_encoder(prompt=INVERSION_PROMPT, do_classifier_free_guidance=False)
         c.update(prompt_embeds=pe, pooled_prompt_embeds=pp, negative_prompt_embeds=ne, negative_pooled_prompt_embeds=npl,
                  inv_prompt_embeds=ipe, inv_pooled_prompt_embeds=ipp)
-        if extra_data is not None and len(extra_data.get("extra_idx", [])) > 0:                # :363-366: the subjects that are image entries
-            c["subject_data"] = [(k, v) for (k, v, i) in zip(extra_data["all_objs"], extra_data["extra_embeds"], extra_data["extra_idx"])
-                                 if mm_data[int(i)]["type"] == "image"]
-            # the inpaint pass runs IPAdapterXL.generate without a prompt: its defaults (ip_adapter.py `generate`)
-            spe, sne, spp, snp = self._text_encoder(prompt="best quality, high quality", negative_prompt="monochrome, lowres, bad anatomy, worst quality, low quality",
-                                                    do_classifier_free_guidance=True)
+        if "subject_data" in c:
+            spe, sne, spp, snp = self._text_encoder(prompt=SUBJECT_PROMPT, negative_prompt=SUBJECT_NEGATIVE_PROMPT, do_classifier_free_guidance=True)
             c.update(subject_prompt_embeds=spe, subject_pooled_prompt_embeds=spp, subject_negative_prompt_embeds=sne, subject_negative_pooled_prompt_embeds=snp)
         if self._refiner_text_encoder is not None:
-            rpe, rne, rpp, rnp = self._refiner_text_encoder(prompt=output_caption + ",high quality,well-formed,award-winning", negative_prompt="",
+            rpe, rne, rpp, rnp = self._refiner_text_encoder(prompt=c["caption"] + REFINER_CAPTION_SUFFIX, negative_prompt=NEGATIVE_PROMPT,
                                                             do_classifier_free_guidance=True)
             c.update(refiner_prompt_embeds=rpe, refiner_pooled_prompt_embeds=rpp, refiner_negative_prompt_embeds=rne,
                      refiner_negative_pooled_prompt_embeds=rnp)
@@ -405,36 +467,25 @@ class InstructAny2PixPipeline:
             raise NotImplementedError("edit_batch needs the pipeline built with conditioner=<callable> or with llm= / llm_tokenizer= / text_encoder=")
         if self._text_encoder is None:
             raise ValueError("a pipeline built with llm= needs text_encoder=<encode_prompt callable> for the denoise stages")
-        cs = []
-        for mm, (image_embeds, base_embed, caption, base_img_path, extra_data) in zip(mm_datas, self.forward_llm_batch(insts, mm_datas, **({} if seeds is None else {"seeds": seeds}))):
-            c = dict(image_embeds=image_embeds, base_embed=base_embed, caption=caption, base_img_path=base_img_path, extra_data=extra_data)
-            if image_embeds is not None:
-                c["image_embeds"], c["base_embed"] = image_embeds.reshape(1, -1), base_embed.reshape(1, -1)
-                for e in mm:
-                    if e.get("fname") == base_img_path and e.get("image") is not None:
-                        c["base_image"] = e["image"]
-                if extra_data is not None and len(extra_data.get("extra_idx", [])) > 0:
-                    c["subject_data"] = [(k, v) for (k, v, i) in zip(extra_data["all_objs"], extra_data["extra_embeds"], extra_data["extra_idx"])
-                                         if mm[int(i)]["type"] == "image"]
-            cs.append(c)
+        outs = self.forward_llm_batch(insts, mm_datas, **({} if seeds is None else {"seeds": seeds}))
+        cs = [condition_from_llm_output(out, mm) for out, mm in zip(outs, mm_datas)]
         live = [c for c in cs if c["image_embeds"] is not None]
         if not live:
             return cs
         te, row = self._text_encoder, lambda t, j: t[j:j + 1]
-        ipe, _, ipp, _ = te(prompt="", do_classifier_free_guidance=False)
-        pe, ne, pp, npl = te(prompt=["best quality, high quality" + c["caption"] for c in live], negative_prompt=[""] * len(live), do_classifier_free_guidance=True)
+        ipe, _, ipp, _ = te(prompt=INVERSION_PROMPT, do_classifier_free_guidance=False)
+        pe, ne, pp, npl = te(prompt=[CAPTION_PREFIX + c["caption"] for c in live], negative_prompt=[NEGATIVE_PROMPT] * len(live), do_classifier_free_guidance=True)
         for j, c in enumerate(live):
             c.update(prompt_embeds=row(pe, j), pooled_prompt_embeds=row(pp, j), negative_prompt_embeds=row(ne, j), negative_pooled_prompt_embeds=row(npl, j),
                      inv_prompt_embeds=ipe, inv_pooled_prompt_embeds=ipp)
-        if any("subject_data" in c for c in live):          # the inpaint pass runs IPAdapterXL.generate without a prompt: its defaults, the same for every request
-            spe, sne, spp, snp = te(prompt="best quality, high quality", negative_prompt="monochrome, lowres, bad anatomy, worst quality, low quality",
-                                    do_classifier_free_guidance=True)
+        if any("subject_data" in c for c in live):          # the same for every request
+            spe, sne, spp, snp = te(prompt=SUBJECT_PROMPT, negative_prompt=SUBJECT_NEGATIVE_PROMPT, do_classifier_free_guidance=True)
             for c in live:
                 if "subject_data" in c:
                     c.update(subject_prompt_embeds=spe, subject_pooled_prompt_embeds=spp, subject_negative_prompt_embeds=sne, subject_negative_pooled_prompt_embeds=snp)
         if self._refiner_text_encoder is not None:
-            rpe, rne, rpp, rnp = self._refiner_text_encoder(prompt=[c["caption"] + ",high quality,well-formed,award-winning" for c in live],
-                                                            negative_prompt=[""] * len(live), do_classifier_free_guidance=True)
+            rpe, rne, rpp, rnp = self._refiner_text_encoder(prompt=[c["caption"] + REFINER_CAPTION_SUFFIX for c in live],
+                                                            negative_prompt=[NEGATIVE_PROMPT] * len(live), do_classifier_free_guidance=True)
             for j, c in enumerate(live):
                 c.update(refiner_prompt_embeds=row(rpe, j), refiner_pooled_prompt_embeds=row(rpp, j), refiner_negative_prompt_embeds=row(rne, j),
                          refiner_negative_pooled_prompt_embeds=row(rnp, j))
@@ -491,10 +542,7 @@ class InstructAny2PixPipeline:
         With `debug=True` the message also carries `seed`."""
         if seed is not None:
             seed = _noise.check_seed(seed)
-        if output_type not in OUTPUT_TYPES:
-            raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
-        if output_type != "latent" and self.vae is None:
-            raise ValueError(f"output_type={output_type!r} needs the pipeline built with vae=<HipAutoencoderKL>")
+        check_output_type(self, output_type)
         if self.conditioner is None and self.any2pix_lm is not None:
             c = self._condition_from_llm(inst, mm_data, use_cache, llm_only, **({} if seed is None else {"seed": seed}))
             if llm_only:
@@ -509,19 +557,8 @@ class InstructAny2PixPipeline:
             self.cache = c
             if llm_only:
                 return None, None, c["caption"]
-        y0 = c.get("y")
-        if y0 is None:                                                                         # :313-317, the prior's one live call
-            if self.model is None:
-                raise NotImplementedError("the conditioner returned no `y` and no prior= was attached")
-            ie = c["image_embeds"]
-            y = self.model.generate_diffusion(MODALITY.VIDEO, MODALITY.IMAGE, ie / ie.norm() * 100, device="cpu", no_diffusion=True,
-                                              num_inference_steps=25, image_bind_overwrite=None, dtype=torch.float32, guidance_scale=10,
-                                              force_guidence_t0=True, do_classifier_free_guidance=True, score=6.5)
-            y0 = y[0].to(device=c["base_embed"].device, dtype=c["base_embed"].dtype)
-        latent_la = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], y0, h, norm)
-        images, latent_inv = self.denoise(self._base_latents(c, seed), latent_la.reshape(1, -1)[0], prompt_embeds=c["prompt_embeds"],
-                                          pooled_prompt_embeds=c["pooled_prompt_embeds"], negative_prompt_embeds=c["negative_prompt_embeds"],
-                                          negative_pooled_prompt_embeds=c["negative_pooled_prompt_embeds"],
+        latent_la = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], prior_y0(self, c), h, norm)
+        images, latent_inv = self.denoise(self._base_latents(c, seed), latent_la.reshape(1, -1)[0], **embeds(c),
                                           inv_prompt_embeds=c.get("inv_prompt_embeds"), inv_pooled_prompt_embeds=c.get("inv_pooled_prompt_embeds"),
                                           alpha=alpha, num_inference_steps=num_inference_steps, cfg=cfg, scale=scale, seed=seed,
                                           noise=c.get("polar_noise") if seed is not None else None)      # (unseeded: this call has always drawn its own)
@@ -529,21 +566,10 @@ class InstructAny2PixPipeline:
         oo = images
         decoded = None          # the decode of `images`, when the refiner hand-over made it
         if refinement > 0 and self.piperf is not None:                                         # :358-361
-            _need(c, ("refiner_prompt_embeds", "refiner_pooled_prompt_embeds", "refiner_negative_prompt_embeds", "refiner_negative_pooled_prompt_embeds"),
-                  "refiner pass")
+            _need(c, REFINER_KEYS, "refiner pass")
             # Conditioning = text encoder 2 on caption + ',high quality,well-formed,award-winning' (the conditioner supplies its embeddings).
-            kw = dict(strength=refinement, prompt_embeds=c["refiner_prompt_embeds"], pooled_prompt_embeds=c["refiner_pooled_prompt_embeds"],
-                      negative_prompt_embeds=c["refiner_negative_prompt_embeds"], negative_pooled_prompt_embeds=c["refiner_negative_pooled_prompt_embeds"],
-                      noise=c.get("refiner_noise"), output_type="latent", **({} if seed is None else {"noise_seed": seed}))
-            vae_route = self.refiner_handoff == "image" and self.pipe._vae_decode is not None and self.piperf._vae_encode is not None
-            if self.refiner_handoff == "image" and not vae_route and not self._warned_handoff:
-                # the reference's route was asked for (decode, 8-bit image, posterior SAMPLE from the global RNG) but cannot be taken: say so once --
-                # the latent route has different numerics and draws nothing from the RNG
-                import warnings
-                warnings.warn("refiner_handoff='image' needs vae_decode= on the base pipeline and vae_encode= on the refiner pipeline; handing the "
-                              "latents over directly instead (pass refiner_handoff='latent' to choose this route explicitly)", RuntimeWarning, stacklevel=2)
-                self._warned_handoff = True
-            if vae_route:
+            kw = dict(strength=refinement, **embeds(c, "refiner_"), noise=c.get("refiner_noise"), output_type="latent", **({} if seed is None else {"noise_seed": seed}))
+            if refiner_handoff_by_image(self):
                 # the reference hands a decoded 8-bit image over and the refiner pipeline re-encodes it with the shared VAE
                 # (`retrieve_latents(vae.encode(image)) * scaling_factor`: a posterior SAMPLE, global RNG)
                 decoded = self.pipe._vae_decode(images)
@@ -556,11 +582,8 @@ class InstructAny2PixPipeline:
                 oo = self.piperf(latents=images, **kw).images
         subject_data = c.get("subject_data") or []
         if subject_strength > 0 and len(subject_data) > 0:                                     # :363-368
-            _need(c, ("subject_prompt_embeds", "subject_pooled_prompt_embeds", "subject_negative_prompt_embeds", "subject_negative_pooled_prompt_embeds"),
-                  "subject-consistency pass")
-            kw = dict(output_type="latent", prompt_embeds=c["subject_prompt_embeds"], pooled_prompt_embeds=c["subject_pooled_prompt_embeds"],
-                      negative_prompt_embeds=c["subject_negative_prompt_embeds"],
-                      negative_pooled_prompt_embeds=c["subject_negative_pooled_prompt_embeds"], noise=c.get("subject_noise"))
+            _need(c, SUBJECT_KEYS, "subject-consistency pass")
+            kw = dict(output_type="latent", **embeds(c, "subject_"), noise=c.get("subject_noise"))
             if seed is not None:
                 kw["noise_seed"] = seed                                                        # pass k draws from DRAW_INPAINT + k (inpaint.subject_consistency)
             by_phrase = [isinstance(k, str) for k, _ in subject_data]

@@ -94,6 +94,20 @@ class DDIMScheduler:
         return (out,) if not return_dict else SimpleNamespace(prev_sample=out)
 
 
+def kept_steps(num_inference_steps: int, strength: float):
+    """`get_timesteps` of the img2img / inpaint pipelines (serial and batched): `strength` keeps the tail of the schedule -> (t_start, number of steps kept)"""
+    init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+    t_start = max(num_inference_steps - init_timestep, 0)
+    return t_start, num_inference_steps - t_start
+
+
+def check_kept_steps(n_steps: int, strength: float, who: str = ""):
+    """a strength that keeps no step is refused; `who` names the request where several share a call"""
+    if n_steps < 1:
+        raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
+                         f"{n_steps} which is < 1 and not appropriate for this pipeline.{who}")
+
+
 def mask_blend(x, init, noise, mask, c0, c1, out, out2=None):
     """out = (1 - mask) * (c0*init + c1*noise) + mask * x on the current stream (ia2p_mask_blend); mask is [B,1,h,w]."""
     B, Cc, h, w = x.shape
