@@ -170,6 +170,29 @@ ia2p_status ia2p_mask_blend(void* stream, const void* x, const void* init, const
 ia2p_status ia2p_mask_blend_v(void* stream, const void* x, const void* init, const void* noise, const void* mask, const float* coef,
                               void* out, void* out2, int B, int C, int64_t HW);
 
+/* ---- edit mask: an edit that leaves the rest of the base image alone (mask-guided decoding, DiffEdit: Couairon et al. 2022) -------------------------------
+ * New: the reference repaints the whole image (pipeline.py:303-386 has no mask). Outside the mask every sampling step is replaced by the DDIM-inverted latents
+ * of the same noise level, so the last step lands on the base latents themselves; the decoded image is composited with the base image in 8 bits.
+ *
+ * known_blend_v: x, out, out2 fp16 [B, C, HW]; known fp16 [levels, B, C, HW] (the inversion trajectory, level 0 = the base latents); level device int32 [B];
+ *   mask fp16 [B, 1, HW].   out[b, c, p] = mask[b, p] != 0 ? x[b, c, p] : known[level[b]][b, c, p]   (+0 and -0 are both "0")
+ *   A selection, not arithmetic: the 16-bit patterns are copied. out2 may be NULL; out may alias x. A level outside [0, levels) is clamped into it on the
+ *   device (the host checks its table before the upload). Null pointers (out2 excepted): IA2P_ERR_INVALID; B, C, HW or levels < 1: IA2P_ERR_SHAPE.
+ * mask_to_latent: mask u8 [B, H, W] -> out fp16 [B, 1, H / f, W / f]: 1.0 where any pixel of the cell's f x f block is >= 128, else 0.0.
+ *   f outside 1 .. 64: IA2P_ERR_INVALID; H % f or W % f non-zero: IA2P_ERR_SHAPE.
+ * mask_feather_u8: mask, out u8 [B, H, W] (out may not alias mask); workspace: B * H * W 16-bit sums (2-byte aligned; 16-byte aligned for the vector path).
+ *   bin = 255 where q >= 128 else 0;  S = sum of bin over the (2 r + 1)^2 window, coordinates clamped to the image (edge replicate), exact;
+ *   a = (S + A / 2) / A in integers, A = (2 r + 1)^2;  out = min(bin, a).   The ramp falls inside the mask only: out = 0 wherever the mask is 0, an all-ones
+ *   mask gives 255 everywhere, r = 0 gives bin. Two launches (rows, columns). r outside 0 .. 64: IA2P_ERR_INVALID.
+ * image_composite_u8: edited, base, out u8 [B, H, W, C] (C = 1 or 3, else IA2P_ERR_SHAPE), alpha u8 [B, H, W].
+ *   out = (a * e + (255 - a) * b + 127) / 255 in integers: a = 255 gives e and a = 0 gives b, exactly. out may alias edited.
+ * All four: more than 2^31 - 1 elements in one image tensor is IA2P_ERR_SHAPE (known_blend_v counts in 64 bits); every refusal comes before any launch. */
+ia2p_status ia2p_known_blend_v(void* stream, const void* x, const void* known, const int32_t* level, const void* mask, void* out, void* out2, int B, int C,
+                               int64_t HW, int levels);
+ia2p_status ia2p_mask_to_latent(void* stream, const void* mask_u8, void* out, int B, int H, int W, int f);
+ia2p_status ia2p_mask_feather_u8(void* stream, const void* mask_u8, void* out, void* workspace, int B, int H, int W, int r);
+ia2p_status ia2p_image_composite_u8(void* stream, const void* edited, const void* base, const void* alpha, void* out, int B, int H, int W, int C);
+
 /* ---- Seeded noise: every normal draw of an edit request from the request's own stream ------------------------------------------------------------------
  * THE NOISE RULE. A request has a 64-bit `seed`; each of its normal draws has a 32-bit `draw` id (table below). Element e of a draw is the FLAT index inside
  * the request's own tensor (the batch is not counted), e < 2^34. Its value comes from block j = e >> 2:

@@ -103,6 +103,10 @@ SIGNATURES = {
     "ia2p_ddim_step_v": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64]),
     "ia2p_mask_blend": (_I, [_P, _P, _P, _P, _P, _F, _F, _P, _P, _I, _I, _I64]),
     "ia2p_mask_blend_v": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I64]),
+    "ia2p_known_blend_v": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I64, _I]),
+    "ia2p_mask_to_latent": (_I, [_P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_mask_feather_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_image_composite_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "ia2p_randn_seeded": (_I, [_P, _P, _I, _I, _I64, _I64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ia2p_posterior_sample_seeded": (_I, [_P, _P, _P, _I, _I, _I64, _F, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ia2p_polar_mix_v": (_I, [_P, _P, _P, C.POINTER(_F), _P, _I, _I64]),

@@ -25,6 +25,10 @@ seed, then generator), the request-level helpers of `pipeline.py`. Here:
   * three group bodies with their own launch loops, `_denoise_group` (`invert_batch`, mix, `sample_batch`), `_refine_group`, `_inpaint_group`: their
     buffer hand-offs differ (ping-pong through out2; x apart from the scaled input; `stepped` blended into both halves), so they are not one loop;
   * `edit_batch`: whole requests through all of it.
+An edit inside a mask (`EditRequest.edit_mask`, `RefineRequest.known_latents` / `.edit_mask`, `edit_batch(edit_masks=)`): in a group where a request
+has a mask, `invert_batch` records its trajectory through `out2` of its update launch, `sample_batch` follows the start and every iteration with one selection
+launch at each request's own level (`scheduler.known_levels`, a table like the coefficient tables) and `_refine_group` blends the base latents in at the loop's
+noise level; a group without masks runs the launch sequence it always ran.
 """
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ import torch
 from . import dist as D
 from . import noise as _noise
 from .ddim import conditioning, get_add_time_ids
-from .scheduler import DDIMScheduler, check_kept_steps, fused_update_v, kept_steps, mask_blend_v
+from .scheduler import DDIMScheduler, check_kept_steps, fused_update_v, kept_steps, known_blend_v, known_levels, level_table, mask_blend_v
 
 
 @dataclass
@@ -56,6 +60,7 @@ class EditRequest:
     scale: float = 1.0
     noise: Optional[torch.Tensor] = None       # polar-mixing noise (CPU fp16); None: drawn from the global RNG in request order
     seed: Optional[int] = None                 # the request's own Philox stream (noise.py): without `noise`, draw DRAW_POLAR of it, made and mixed on the device
+    edit_mask: Optional[object] = None         # edit inside this mask only (what `pipeline.resolve_edit_mask` takes: a pixel mask, or a latent mask [1, 1, h, w])
 
 
 def _coef_table(rows: Sequence[Sequence[tuple]], device) -> torch.Tensor:
@@ -151,9 +156,12 @@ def _check_latents(latents: Sequence[torch.Tensor], what: str):
 
 
 @torch.no_grad()
-def invert_batch(unet, scheduler_config, latents, prompt_embeds, pooled, steps: Sequence[int], ip_scales=None):
+def invert_batch(unet, scheduler_config, latents, prompt_embeds, pooled, steps: Sequence[int], ip_scales=None, return_trajectory: bool = False):
     """DDIM inversion x0 -> xT of B requests at once (reference loop pnp_pipeline.py:251-275 per request), each over its own `steps[b]`-step
-    schedule walked in ascending t (`invert_tables`). latents [B,4,h,w]; prompt_embeds [B,L,ctx]; pooled [B,P]."""
+    schedule walked in ascending t (`invert_tables`). latents [B,4,h,w]; prompt_embeds [B,L,ctx]; pooled [B,P].
+    `return_trajectory` (False: nothing changes): -> (xT, trajectory fp16 [max(steps) + 1, B, 4, h, w]), level 0 the latents the loop starts from, level
+    j + 1 the result of iteration j, written through `out2` of the update launch (no extra launch). A request that is through is held: its levels above
+    its own N repeat its xT and are never read (`scheduler.known_levels`)."""
     dev = unet.device
     x = latents.to(device=dev, dtype=torch.float16).contiguous().clone()
     h, w = x.shape[-2] * 8, x.shape[-1] * 8
@@ -161,19 +169,30 @@ def invert_batch(unet, scheduler_config, latents, prompt_embeds, pooled, steps: 
     ts, coef = invert_tables(scheduler_config, steps)
     ts_all, coef_all = _coef_table(ts, dev), _coef_table(coef, dev)
     eps, nxt = torch.empty_like(x), torch.empty_like(x)
+    traj = None
+    if return_trajectory:
+        traj = torch.empty((len(ts) + 1,) + tuple(x.shape), dtype=torch.float16, device=dev)
+        traj[0].copy_(x)
     for i in range(len(ts)):
         unet(x, ts_all[i], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps, ip_scales=ip_scales)
-        fused_update_v(x, eps, None, coef_all[i], nxt)
+        if traj is None:
+            fused_update_v(x, eps, None, coef_all[i], nxt)
+        else:
+            fused_update_v(x, eps, None, coef_all[i], nxt, traj[i + 1])
         x, nxt = nxt, x
-    return x
+    return x if traj is None else (x, traj)
 
 
 @torch.no_grad()
 def sample_batch(unet, scheduler_config, latents, cond_ctx, uncond_ctx, cond_pooled, uncond_pooled, steps: Sequence[int], cfg: Sequence[float],
-                 scales: Optional[Sequence[float]] = None):
+                 scales: Optional[Sequence[float]] = None, known: Optional[torch.Tensor] = None, edit_mask: Optional[torch.Tensor] = None):
     """Guided DDIM sampling xT -> x0 of n requests at once: one UNet evaluation at B_eff = 2 n per iteration, rows [uncond x n | cond x n]
     (the reference's cat([latents] * 2), sdxl_pipeline.py:826, per request), request r with its own schedule length, guidance and IP scale
-    (`sample_tables`)."""
+    (`sample_tables`).
+    `known` + `edit_mask` (both None: nothing changes): mask-guided decoding. `known` is `invert_batch(return_trajectory=True)`'s store over the same
+    `steps`, `edit_mask` the {0, 1} latent masks [n, 1, h, w] (all ones for a request without a mask: the selection returns its bits). Where a mask is 0 the
+    start is the request's level N_r and the result of iteration i its level max(N_r - 1 - i, 0) (`scheduler.known_levels`, uploaded once next to the
+    coefficient tables): one `ia2p_known_blend_v` launch per iteration, written to both halves of the model input."""
     dev = unet.device
     n = latents.shape[0]
     x = latents.to(device=dev, dtype=torch.float16).contiguous()
@@ -184,19 +203,33 @@ def sample_batch(unet, scheduler_config, latents, cond_ctx, uncond_ctx, cond_poo
     sc = None
     if scales is not None:
         sc = torch.tensor(list(scales) * 2, dtype=torch.float32).to(dev)
+    lv = None
+    if (known is None) != (edit_mask is None):
+        raise ValueError("`known` and `edit_mask` go together: pass both or neither")
+    if known is not None:
+        if tuple(known.shape) != (len(ts) + 1,) + tuple(x.shape) or tuple(edit_mask.shape) != (n, 1) + tuple(x.shape[-2:]):
+            raise ValueError(f"`known` must be [max(steps) + 1 = {len(ts) + 1}, {', '.join(map(str, x.shape))}] and `edit_mask` [{n}, 1, {x.shape[-2]}, {x.shape[-1]}], "
+                             f"got {tuple(known.shape)} and {tuple(edit_mask.shape)}")
+        lv = level_table(known_levels(steps), known.shape[0], dev)
+        x = known_blend_v(x, known, lv[0], edit_mask, torch.empty_like(x))
     model_in = torch.cat([x, x], dim=0).contiguous()
     eps, nxt = torch.empty_like(model_in), torch.empty_like(model_in)
     for i in range(len(ts)):
         unet(model_in, ts_all[i], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps, ip_scales=sc)
-        fused_update_v(model_in[:n], eps[:n], eps[n:], coef_all[i], nxt[:n], nxt[n:])        # eps_u + g (eps_c - eps_u), x_{t-1} to both halves
+        if lv is None:
+            fused_update_v(model_in[:n], eps[:n], eps[n:], coef_all[i], nxt[:n], nxt[n:])    # eps_u + g (eps_c - eps_u), x_{t-1} to both halves
+        else:                                                                                # outside the masks: the inverted latents of each request's level
+            fused_update_v(model_in[:n], eps[:n], eps[n:], coef_all[i], nxt[:n])
+            known_blend_v(nxt[:n], known, lv[i + 1], edit_mask, nxt[:n], nxt[n:])
         model_in, nxt = nxt, model_in
     return model_in[:n].clone()
 
 
 @torch.no_grad()
-def _denoise_group(pipeline, reqs: List[EditRequest], noises):
+def _denoise_group(pipeline, reqs: List[EditRequest], noises, masks=None):
     """one group through inversion, polar mixing and guided sampling -> (sampled latents, inverted latents). `noises[i]` None: request i mixes on the device
-    with draw DRAW_POLAR of its own stream."""
+    with draw DRAW_POLAR of its own stream. `masks[i]`: request i's latent edit mask [1, 1, h, w] or None; with at least one mask in the group the inversion
+    records its trajectory and the sampling is mask-guided, the requests without one carrying all ones. Without any, the launch sequence is the unmasked one."""
     from . import pipeline as P                  # (`polar_intrtpolate` looked up at call time)
     unet, cfgs, ipa = pipeline.pipe.unet, pipeline.pipe.scheduler.config, pipeline.ip_adapter_xl
     dev = unet.device
@@ -204,7 +237,14 @@ def _denoise_group(pipeline, reqs: List[EditRequest], noises):
     cat = lambda xs: torch.cat([x.to(dev) for x in xs], dim=0)
     inv_ctx = cat([(r.inv_prompt_embeds if r.inv_prompt_embeds is not None else r.negative_prompt_embeds) for r in reqs])
     inv_pool = cat([(r.inv_pooled_prompt_embeds if r.inv_pooled_prompt_embeds is not None else r.negative_pooled_prompt_embeds) for r in reqs])
-    x_inv = invert_batch(unet, cfgs, cat([r.base_latents for r in reqs]), inv_ctx, inv_pool, steps)
+    guided = {}
+    if masks is not None and any(m is not None for m in masks):
+        hw = tuple(reqs[0].base_latents.shape[-2:])
+        guided["edit_mask"] = torch.cat([torch.ones((1, 1) + hw, dtype=torch.float16, device=dev) if m is None else m.to(device=dev, dtype=torch.float16)
+                                         for m in masks], dim=0).contiguous()
+        x_inv, guided["known"] = invert_batch(unet, cfgs, cat([r.base_latents for r in reqs]), inv_ctx, inv_pool, steps, return_trajectory=True)
+    else:
+        x_inv = invert_batch(unet, cfgs, cat([r.base_latents for r in reqs]), inv_ctx, inv_pool, steps)
     own = [i for i in range(len(reqs)) if noises[i] is None]
     if len(own) < len(reqs):
         x_inv_cpu = x_inv.cpu()                                                             # pipeline.py:331
@@ -221,7 +261,7 @@ def _denoise_group(pipeline, reqs: List[EditRequest], noises):
     cond_ctx = torch.cat([cat([r.prompt_embeds for r in reqs]).to(torch.float16), ip], dim=1)              # ip_adapter.py:341-342
     uncond_ctx = torch.cat([cat([r.negative_prompt_embeds for r in reqs]).to(torch.float16), ip_un], dim=1)
     x = sample_batch(unet, cfgs, mixed, cond_ctx, uncond_ctx, cat([r.pooled_prompt_embeds for r in reqs]), cat([r.negative_pooled_prompt_embeds for r in reqs]),
-                     steps, [float(r.cfg) for r in reqs], [float(r.scale) for r in reqs])
+                     steps, [float(r.cfg) for r in reqs], [float(r.scale) for r in reqs], **guided)
     return x, x_inv
 
 
@@ -250,7 +290,12 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
     # polar-mixing noise comes from the global CPU RNG in REQUEST order (what N sequential reference calls would draw), on every rank alike; a request with a
     # seed and no noise draws nothing here: its noise is made on the device in its group, from its own stream
     noises = _noise.host_noises([r.noise for r in requests], [x.shape for x in latents], [r.seed for r in requests])
-    return _run_groups(requests, latents[0], pipeline.pipe.unet, group, shard, lambda g0, reqs: _denoise_group(pipeline, reqs, noises[g0:g0 + len(reqs)]), n_out=2)
+    if all(r.edit_mask is None for r in requests):
+        return _run_groups(requests, latents[0], pipeline.pipe.unet, group, shard, lambda g0, reqs: _denoise_group(pipeline, reqs, noises[g0:g0 + len(reqs)]), n_out=2)
+    from .pipeline import resolve_edit_mask
+    masks = [None if r.edit_mask is None else resolve_edit_mask(pipeline, r.edit_mask, r.base_latents, pixels=False)[1] for r in requests]      # every refusal before any launch
+    return _run_groups(requests, latents[0], pipeline.pipe.unet, group, shard,
+                       lambda g0, reqs: _denoise_group(pipeline, reqs, noises[g0:g0 + len(reqs)], masks[g0:g0 + len(reqs)]), n_out=2)
 
 
 # ---- the stages after the hot segment, batched the same way: refiner pass and subject-consistency inpainting ---------------------------------------------
@@ -286,6 +331,8 @@ class RefineRequest:
     strength: float = 0.3
     noise: Optional[torch.Tensor] = None       # start noise; None: drawn from the global CPU RNG in request order
     seed: Optional[int] = None                 # without `noise`: draw DRAW_REFINER of the request's own stream, on the device
+    known_latents: Optional[torch.Tensor] = None   # with `edit_mask`: [1, 4, h, w] kept (re-noised with the loop's own noise) where the mask is 0
+    edit_mask: Optional[torch.Tensor] = None       # {0, 1} latent mask [1, 1, h, w]
 
 
 @dataclass
@@ -296,6 +343,7 @@ class RefineTables:
     timesteps: List[List[float]]
     input_scale: List[List[float]]   # scale_model_input: 1 / sqrt(sigma^2 + 1)
     coef: List[List[tuple]]          # (g, 1, sigma_next - sigma); (g, 1, 0) once a request is through
+    blend: List[List[tuple]]         # an edit inside a mask: (1, sigma_next), the known region at the noise level the step arrives at; (1, 0) after the last step and while held
 
 
 def refine_tables(scheduler_config, strengths: Sequence[float], num_inference_steps: int = 50, guidance_scale: float = 5.0) -> RefineTables:
@@ -306,8 +354,9 @@ def refine_tables(scheduler_config, strengths: Sequence[float], num_inference_st
     sch.set_timesteps(num_inference_steps)
     kept = [_kept_steps(num_inference_steps, float(s), i) for i, s in enumerate(strengths)]
     g = float(guidance_scale)
-    records = [[(float(sch.timesteps[i]), sch.input_scale(i), (g,) + tuple(sch.step_coeffs(i))) for i in range(t_start, t_start + n)] for t_start, n in kept]
-    hold = [rec[-1][:2] + ((g, 1.0, 0.0),) for rec in records]
+    records = [[(float(sch.timesteps[i]), sch.input_scale(i), (g,) + tuple(sch.step_coeffs(i)), (1.0, float(sch.sigmas[i + 1]))) for i in range(t_start, t_start + n)]
+               for t_start, n in kept]
+    hold = [rec[-1][:2] + ((g, 1.0, 0.0), (1.0, 0.0)) for rec in records]
     return RefineTables([n for _, n in kept], [float(sch.sigmas[sch.index_for_timestep(sch.timesteps[t_start])]) for t_start, _ in kept],
                         *_joint_tables(records, hold))
 
@@ -328,12 +377,25 @@ def _refine_group(piperf, reqs: List[RefineRequest], noises, tb: RefineTables, a
     coef_all = _coef_table(tb.coef, dev)
     x, nxt = torch.empty_like(lat), torch.empty_like(lat)
     fused_update_v(lat, noise, None, _coef_table([(1.0, 1.0, s) for s in tb.start_sigma], dev), x)              # add_noise at every request's first kept timestep
+    mask = None
+    if any(r.edit_mask is not None for r in reqs):       # an edit inside a mask: outside it the known latents at the loop's noise level, with the loop's own noise
+        if any((r.edit_mask is None) != (r.known_latents is None) for r in reqs):
+            raise ValueError("`known_latents` and `edit_mask` of a RefineRequest go together: give both or neither")
+        ones = torch.ones((1, 1) + tuple(lat.shape[-2:]), dtype=torch.float16, device=dev)
+        mask = torch.cat([ones if r.edit_mask is None else r.edit_mask.to(device=dev, dtype=torch.float16) for r in reqs], dim=0).contiguous()
+        known = _rows([r.latents if r.known_latents is None else r.known_latents for r in reqs], dev)          # (a row of ones keeps its x: the value is not used)
+        if mask.shape != (n, 1) + tuple(lat.shape[-2:]) or known.shape != lat.shape:
+            raise ValueError(f"every request carries ONE latent mask [1, 1, h, w] and known latents of its latents' shape, got {tuple(mask.shape)} and {tuple(known.shape)}")
+        blend_all = _coef_table(tb.blend, dev)
+        mask_blend_v(x, known, noise, mask, _coef_table([(1.0, s) for s in tb.start_sigma], dev), x)
     model_in = torch.empty((2 * n,) + tuple(x.shape[1:]), dtype=torch.float16, device=dev)
     eps = torch.empty_like(model_in)
     for k in range(len(tb.timesteps)):
         fused_update_v(x, x, None, scale_all[k], model_in[:n], model_in[n:])                                    # scale_model_input on cat([x] * 2)
         unet(model_in, ts_all[k], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps)
         fused_update_v(x, eps[:n], eps[n:], coef_all[k], nxt)                                                   # CFG + Euler step
+        if mask is not None:
+            mask_blend_v(nxt, known, noise, mask, blend_all[k], nxt)
         x, nxt = nxt, x
     return x
 
@@ -479,7 +541,7 @@ def _vae_in_batches(pipeline, fn, t: torch.Tensor, group: int, decode: bool, see
 
 @torch.no_grad()
 def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
-               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None):
+               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8):
     """`InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
     See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding)."""
     from . import pipeline as P
@@ -494,6 +556,11 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     _check_group(group, "edit_batch")
     seeds = _noise.resolve_seeds(seeds, N)
     seeded = any(s is not None for s in seeds)
+    edit_masks = per_request(edit_masks, N, "edit_masks")                 # one mask for all requests, or a list of N with None entries
+    if any(m is not None for m in edit_masks):
+        from .image_processor import check_edit_feather
+        P.check_edit_output_type(output_type)
+        edit_feather = check_edit_feather(edit_feather)
     alpha, norm, refinement = per_request(alpha, N, "alpha"), per_request(norm, N, "norm"), per_request(refinement, N, "refinement")
     steps, subject_strength = per_request(num_inference_steps, N, "num_inference_steps"), per_request(subject_strength, N, "subject_strength")
     cfg, scale, h = per_request(cfg, N, "cfg"), per_request(scale, N, "scale"), per_request(h, N, "h", _is_one_h)
@@ -527,18 +594,23 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     # ---- base images -> latents, the images among them encoded in batches (posterior samples: global RNG, request order) -----------------------------------
     base = {i: cs[i]["base_latents"] for i in live if cs[i].get("base_latents") is not None}
     todo = [i for i in live if i not in base]
+    base_px = {}                     # masked request -> its preprocessed base image, for the composite
     if todo:
         imgs = [P.base_image(pipeline, cs[i], f" (request {i})") for i in todo]                   # (every refusal before the image processor is touched)
         imgs = [pipeline.pipe_inversion.image_processor.preprocess(img) for img in imgs]
+        base_px.update({i: t for i, t in zip(todo, imgs) if edit_masks[i] is not None and t.shape[1] != 4})
         enc = _vae_in_batches(pipeline, pipeline.pipe_inversion._vae_encode, torch.cat(imgs, dim=0), group, False,
                               seeds=[seeds[i] for i in todo], draw=_noise.DRAW_BASE_POSTERIOR)
         base.update({i: enc[j:j + 1] for j, i in enumerate(todo)})
     _check_latents([base[i] for i in live], "edit_batch")
+    # edit masks: (pixel mask, latent mask) per masked request, every refusal before the hot segment
+    edit = {i: P.resolve_edit_mask(pipeline, edit_masks[i], base[i], P.edit_mask_file_size(cs[i])) for i in live if edit_masks[i] is not None}
+    edit_m = {i: (edit[i][1] if i in edit else None) for i in live}
 
     # ---- the hot segment ---------------------------------------------------------------------------------------------------------------------------------
     reqs = [EditRequest(base_latents=base[i], latent_la=latent_la[i].reshape(1, -1)[0], **P.embeds(cs[i]), inv_prompt_embeds=cs[i].get("inv_prompt_embeds"),
                         inv_pooled_prompt_embeds=cs[i].get("inv_pooled_prompt_embeds"), alpha=alpha[i], num_inference_steps=int(steps[i]), cfg=float(cfg[i]),
-                        scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i]) for i in live]
+                        scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i], edit_mask=edit_m[i]) for i in live]
     pipeline.pipe_inversion.unet = pipeline.pipe.unet
     images, latent_inv = denoise_batch(pipeline, reqs, group=group, shard=shard)
     row = {i: j for j, i in enumerate(live)}
@@ -558,8 +630,8 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             decoded.update({i: dec[j:j + 1] for j, i in enumerate(ref)})
             img8 = requantize(dec) if pipeline.vae is not None else P.to_8bit_image(dec)
             start = _vae_in_batches(pipeline, piperf._vae_encode, img8, group, False, seeds=[seeds[i] for i in ref], draw=_noise.DRAW_HANDOFF_POSTERIOR)
-        rr = [RefineRequest(latents=start[j:j + 1], **P.embeds(cs[i], "refiner_"), strength=float(refinement[i]), noise=cs[i].get("refiner_noise"), seed=seeds[i])
-              for j, i in enumerate(ref)]
+        rr = [RefineRequest(latents=start[j:j + 1], **P.embeds(cs[i], "refiner_"), strength=float(refinement[i]), noise=cs[i].get("refiner_noise"), seed=seeds[i],
+                            known_latents=base[i] if i in edit else None, edit_mask=edit_m[i]) for j, i in enumerate(ref)]
         refined = refine_batch(piperf, rr, group=group, shard=shard)
         oo.update({i: refined[j:j + 1] for j, i in enumerate(ref)})
 
@@ -570,6 +642,8 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
         for i in sub:
             P._need(cs[i], P.SUBJECT_KEYS, "subject-consistency pass")
             pairs[i] = pipeline._subject_mask_pairs(cs[i], cs[i]["subject_data"], oo[i])
+            if i in edit:                                                                          # a subject pass under an edit mask repaints inside both
+                pairs[i] = [(P.intersect_subject_mask(mk, edit[i][0]), emb) for mk, emb in pairs[i]]
         for k in range(max(len(p) for p in pairs.values())):
             now = [i for i in sub if len(pairs[i]) > k]
             ir = [InpaintRequest(latents=oo[i], mask=pairs[i][k][0], subject_embed=pairs[i][k][1], **P.embeds(cs[i], "subject_"), strength=float(subject_strength[i]),
@@ -585,11 +659,20 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
         if want:
             dec = _vae_in_batches(pipeline, pipeline.pipe._vae_decode, torch.cat([(oo if final else non_refined)[i] for i, final in want], dim=0), group, True)
         imgs = {key: dec[j:j + 1] for j, key in enumerate(want)}
+        if edit:                     # the masked requests' base images in 8 bits (the loaded image, or the decode of the base latents) and feathered masks
+            from .image_processor import image_to_u8, mask_feather
+            need = [i for i in edit if i not in base_px]
+            if need:
+                dec_base = _vae_in_batches(pipeline, pipeline.pipe._vae_decode, _rows([base[i] for i in need], pipeline.pipe.unet.device), group, True)
+                base_px.update({i: dec_base[j:j + 1] for j, i in enumerate(need)})
+            base_u8 = {i: image_to_u8(base_px[i].to(torch.float16).contiguous()) for i in edit}
+            alpha_u8 = {i: mask_feather(edit[i][0], edit_feather) for i in edit}
         for i in live:
-            shown_nr[i] = post(decoded[i] if i in decoded else imgs[(i, False)], output_type=output_type)
-            shown_oo[i] = shown_nr[i] if oo[i] is non_refined[i] else post(imgs[(i, True)], output_type=output_type)
+            show = (lambda x, i=i: P.composite_edit(pipeline, x, base_u8[i], alpha_u8[i])) if i in edit else (lambda x: post(x, output_type=output_type))
+            shown_nr[i] = show(decoded[i] if i in decoded else imgs[(i, False)])
+            shown_oo[i] = shown_nr[i] if oo[i] is non_refined[i] else show(imgs[(i, True)])
     for i in live:
         msg = "SUCCESS!" if not debug else dict(output_caption=cs[i]["caption"], latent_inv=latent_inv[row[i]:row[i] + 1], latent_la=latent_la[i],
-                                                **({} if seeds[i] is None else {"seed": seeds[i]}))
+                                                **({} if seeds[i] is None else {"seed": seeds[i]}), **({} if i not in edit else {"edit_mask_latent": edit_m[i]}))
         results[i] = (shown_nr[i], shown_oo[i], msg)
     return results

@@ -58,6 +58,12 @@ hipError_t ia2p_launch_ddim_step(const half_t* x, const half_t* eps_u, const hal
                                  half_t* out, half_t* out2, long n, hipStream_t s, const float* coef = nullptr, long per = 1);
 hipError_t ia2p_launch_mask_blend(const half_t* x, const half_t* init, const half_t* noise, const half_t* mask, float c0, float c1,
                                   half_t* out, half_t* out2, int B, int C, long HW, hipStream_t s, const float* coef = nullptr);
+hipError_t ia2p_launch_known_blend(const half_t* x, const half_t* known, const int* level, const half_t* mask, half_t* out, half_t* out2, int B, int C, long HW,
+                                   int levels, hipStream_t s);
+// image.hip: the edit-mask kernels behind ia2p_mask_to_latent / ia2p_mask_feather_u8 / ia2p_image_composite_u8 (arguments checked in ops_abi.hip)
+hipError_t ia2p_launch_mask_to_latent(const uint8_t* mask, half_t* out, int B, int H, int W, int f, hipStream_t s);
+hipError_t ia2p_launch_mask_feather_u8(const uint8_t* mask, uint8_t* out, uint16_t* ws, int B, int H, int W, int r, hipStream_t s);
+hipError_t ia2p_launch_image_composite_u8(const uint8_t* edited, const uint8_t* base, const uint8_t* alpha, uint8_t* out, int B, int H, int W, int C, hipStream_t s);
 hipError_t ia2p_launch_cat_rows(const half_t* a, int Ka, const half_t* b, int Kb, const half_t* bias_a, const half_t* bias_b, half_t* dst, half_t* bias_dst, int rows, hipStream_t s);
 hipError_t ia2p_launch_fold_ln(const half_t* W, const half_t* gamma, const half_t* beta, const half_t* bias, half_t* Wf, float* cs, float* lb,
                                int N, int K, hipStream_t s);

@@ -150,6 +150,159 @@ __global__ __launch_bounds__(BLOCK) void image_map_kernel(const half_t* src, OUT
   for (int e = 0; e < m; ++e) dst[i0 + e] = f(src[i0 + e]);
 }
 
+// ---- editing inside a mask (include/ia2p.h, "edit mask"): pixel mask -> latent mask, seam feather, 8-bit composite. Integer arithmetic only. ----------------
+// One thread owns PX = 16 consecutive pixels of one image row (the last chunk of a row may be shorter). `vec`: W % PX == 0 and 16-byte aligned pointers, so
+// that every chunk is whole and starts on a 16-byte boundary in the u8 planes (and on a 32-byte one in the u16 workspace); other shapes run the same
+// arithmetic through scalar accesses.
+__device__ __forceinline__ uint32_t bin255(uint32_t q) { return q >= 128u ? 255u : 0u; }
+
+// mask u8 [B, H, W] -> out fp16 [B, 1, H / f, W / f]: 1.0 where any pixel of the f x f block is >= 128. One thread per output cell; `pair` (f == 8, an even
+// number of cells per row, 16-byte aligned mask): one thread owns two neighbouring cells, reads their 8 rows as 16-byte pieces and stores both halfs as one word.
+__global__ __launch_bounds__(BLOCK) void mask_to_latent_kernel(const uint8_t* __restrict__ mask, half_t* __restrict__ out, int H, int W, int f, int total, int pair) {
+  const int t = blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= total) return;
+  const int h = H / f, w = W / f;
+  if (pair) {
+    const int wp = w >> 1, b = t / (h * wp), r = t - b * h * wp, cy = r / wp, cx = (r - cy * wp) * 2;
+    const uint8_t* s = mask + ((size_t)b * H + (size_t)cy * 8) * W + cx * 8;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {
+      const uint4 v = *(const uint4*)(s + (size_t)y * W);
+      lo |= (v.x | v.y) & 0x80808080u;        // q >= 128 is bit 7
+      hi |= (v.z | v.w) & 0x80808080u;
+    }
+    const half_t one = (half_t)1.0f, zero = (half_t)0.0f;
+    const uint32_t word = (uint32_t)__builtin_bit_cast(uint16_t, lo ? one : zero) | ((uint32_t)__builtin_bit_cast(uint16_t, hi ? one : zero) << 16);
+    *(uint32_t*)(out + ((size_t)b * h + cy) * w + cx) = word;
+    return;
+  }
+  const int b = t / (h * w), r = t - b * h * w, cy = r / w, cx = r - cy * w;
+  const uint8_t* s = mask + ((size_t)b * H + (size_t)cy * f) * W + (size_t)cx * f;
+  uint32_t any = 0;
+  for (int y = 0; y < f; ++y)
+    for (int x = 0; x < f; ++x) any |= s[(size_t)y * W + x] & 0x80u;
+  out[t] = any ? (half_t)1.0f : (half_t)0.0f;
+}
+
+// row pass of the box filter: ws[b, y, x] = sum over dx in [-r, r] of bin(mask[b, y, clamp(x + dx)]) (at most 129 * 255: fits 16 bits). A sliding window over
+// the thread's chunk: one clamped window sum, then one byte in and one byte out per pixel.
+__global__ __launch_bounds__(BLOCK) void mask_feather_rows_kernel(const uint8_t* __restrict__ mask, uint16_t* __restrict__ ws, int W, int chunks, int total, int r, int vec) {
+  const int t = blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= total) return;
+  const int row = t / chunks, x0 = (t - row * chunks) * PX, n = min(PX, W - x0);
+  const uint8_t* s = mask + (size_t)row * W;
+  auto at = [&](int x) { return bin255(s[min(max(x, 0), W - 1)]); };
+  uint32_t sum = 0;
+  for (int dx = -r; dx <= r; ++dx) sum += at(x0 + dx);
+  uint16_t* d = ws + (size_t)row * W + x0;
+  if (vec) {
+    uint32_t w[PX / 2];
+#pragma unroll
+    for (int j = 0; j < PX; ++j) {
+      w[j >> 1] = (j & 1) ? (w[j >> 1] | (sum << 16)) : sum;
+      sum += at(x0 + j + 1 + r) - at(x0 + j - r);
+    }
+    ((uint4*)d)[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    ((uint4*)d)[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    return;
+  }
+  for (int j = 0; j < n; ++j) {
+    d[j] = (uint16_t)sum;
+    sum += at(x0 + j + 1 + r) - at(x0 + j - r);
+  }
+}
+
+// column pass and the feather itself: S = sum over dy in [-r, r] of ws[b, clamp(y + dy), x] (exact, at most 129 * 129 * 255), a = (S + A / 2) / A with
+// A = (2 r + 1)^2, out = min(bin, a): the ramp falls INSIDE the mask only, so out = 0 wherever the mask is 0.
+__global__ __launch_bounds__(BLOCK) void mask_feather_cols_kernel(const uint8_t* __restrict__ mask, const uint16_t* __restrict__ ws, uint8_t* __restrict__ out, int H, int W,
+                                                                  int chunks, int total, int r, int vec) {
+  const int t = blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= total) return;
+  const int row = t / chunks, x0 = (t - row * chunks) * PX, n = min(PX, W - x0);
+  const int b = row / H, y = row - b * H;
+  const uint32_t A = (uint32_t)(2 * r + 1) * (uint32_t)(2 * r + 1);
+  uint32_t S[PX];
+#pragma unroll
+  for (int j = 0; j < PX; ++j) S[j] = 0;
+  for (int dy = -r; dy <= r; ++dy) {
+    const uint16_t* w = ws + ((size_t)b * H + min(max(y + dy, 0), H - 1)) * W + x0;
+    if (vec) {
+      const uint4 lo = ((const uint4*)w)[0], hi = ((const uint4*)w)[1];
+      const uint32_t v[PX / 2] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+      for (int j = 0; j < PX; ++j) S[j] += (v[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+    } else {
+      for (int j = 0; j < n; ++j) S[j] += w[j];
+    }
+  }
+  const uint8_t* m = mask + (size_t)row * W + x0;
+  uint8_t* d = out + (size_t)row * W + x0;
+  if (vec) {
+    const uint4 mv = *(const uint4*)m;
+    const uint32_t ms[4] = {mv.x, mv.y, mv.z, mv.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) word |= min(bin255((ms[q] >> (8 * k)) & 0xffu), (S[4 * q + k] + A / 2) / A) << (8 * k);
+      o[q] = word;
+    }
+    *(uint4*)d = make_uint4(o[0], o[1], o[2], o[3]);
+    return;
+  }
+  for (int j = 0; j < n; ++j) d[j] = (uint8_t)min(bin255(m[j]), (S[j] + A / 2) / A);
+}
+
+// out = (a * e + (255 - a) * b + 127) / 255 per byte, a = alpha[b, y, x] shared by the C channels of the pixel: a = 255 gives e, a = 0 gives b, exactly.
+// One thread owns PX pixels = PX * C bytes of edited / base / out (C 16-byte pieces each) and PX bytes of alpha. out may alias edited.
+template <int C>
+__global__ __launch_bounds__(BLOCK) void image_composite_kernel(const uint8_t* edited, const uint8_t* __restrict__ base, const uint8_t* __restrict__ alpha, uint8_t* out,
+                                                               int npix, int total, int vec) {
+  const int t = blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= total) return;
+  const int p0 = t * PX;
+  auto mix = [](uint32_t a, uint32_t e, uint32_t b) { return (a * e + (255u - a) * b + 127u) / 255u; };
+  if (vec) {                                  // (npix % PX == 0: every chunk is whole)
+    const uint4 av = *(const uint4*)(alpha + p0);
+    const uint32_t as[4] = {av.x, av.y, av.z, av.w};
+    uint32_t ew[4 * C], bw[4 * C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+      const uint4 ev = ((const uint4*)(edited + (size_t)p0 * C))[i], bv = ((const uint4*)(base + (size_t)p0 * C))[i];
+      ew[4 * i] = ev.x; ew[4 * i + 1] = ev.y; ew[4 * i + 2] = ev.z; ew[4 * i + 3] = ev.w;
+      bw[4 * i] = bv.x; bw[4 * i + 1] = bv.y; bw[4 * i + 2] = bv.z; bw[4 * i + 3] = bv.w;
+    }
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+      uint32_t o[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const int k = 16 * i + 4 * q + m, px = k / C;      // byte k of the run = pixel k / C
+          const uint32_t a = (as[px >> 2] >> (8 * (px & 3))) & 0xffu;
+          word |= mix(a, (ew[k >> 2] >> (8 * (k & 3))) & 0xffu, (bw[k >> 2] >> (8 * (k & 3))) & 0xffu) << (8 * m);
+        }
+        o[q] = word;
+      }
+      ((uint4*)(out + (size_t)p0 * C))[i] = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+    return;
+  }
+  const int n = min(PX, npix - p0);
+  for (int j = 0; j < n; ++j) {
+    const uint32_t a = alpha[p0 + j];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const size_t k = (size_t)(p0 + j) * C + c;
+      out[k] = (uint8_t)mix(a, edited[k], base[k]);
+    }
+  }
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline int blocks_for(long threads) { return (int)((threads + BLOCK - 1) / BLOCK); }
 
@@ -218,4 +371,31 @@ ia2p_status ia2p_image_requantize(void* stream, const void* src, void* dst, int6
                      (int)n, (int)(aligned16(src) && aligned16(dst)));
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "image_requantize");
+}
+
+// ---- edit-mask launchers (arguments checked in ops_abi.hip) ------------------------------------------------------------------------------------------------
+hipError_t ia2p_launch_mask_to_latent(const uint8_t* mask, half_t* out, int B, int H, int W, int f, hipStream_t s) {
+  const int h = H / f, w = W / f;
+  const int pair = f == 8 && w % 2 == 0 && aligned16(mask) && aligned16(out);
+  const int total = B * h * (pair ? w / 2 : w);
+  hipLaunchKernelGGL(mask_to_latent_kernel, dim3(blocks_for(total)), dim3(BLOCK), 0, s, mask, out, H, W, f, total, pair);
+  return hipGetLastError();
+}
+
+hipError_t ia2p_launch_mask_feather_u8(const uint8_t* mask, uint8_t* out, uint16_t* ws, int B, int H, int W, int r, hipStream_t s) {
+  const int chunks = (W + PX - 1) / PX, total = B * H * chunks;
+  const int vec = W % PX == 0 && aligned16(mask) && aligned16(out) && aligned16(ws);
+  hipLaunchKernelGGL(mask_feather_rows_kernel, dim3(blocks_for(total)), dim3(BLOCK), 0, s, mask, ws, W, chunks, total, r, vec);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mask_feather_cols_kernel, dim3(blocks_for(total)), dim3(BLOCK), 0, s, mask, (const uint16_t*)ws, out, H, W, chunks, total, r, vec);
+  return hipGetLastError();
+}
+
+hipError_t ia2p_launch_image_composite_u8(const uint8_t* edited, const uint8_t* base, const uint8_t* alpha, uint8_t* out, int B, int H, int W, int C, hipStream_t s) {
+  const int npix = B * H * W, total = (npix + PX - 1) / PX;
+  const int vec = npix % PX == 0 && aligned16(edited) && aligned16(base) && aligned16(alpha) && aligned16(out);
+  if (C == 3) hipLaunchKernelGGL(image_composite_kernel<3>, dim3(blocks_for(total)), dim3(BLOCK), 0, s, edited, base, alpha, out, npix, total, vec);
+  else hipLaunchKernelGGL(image_composite_kernel<1>, dim3(blocks_for(total)), dim3(BLOCK), 0, s, edited, base, alpha, out, npix, total, vec);
+  return hipGetLastError();
 }

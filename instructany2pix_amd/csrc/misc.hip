@@ -338,6 +338,42 @@ __global__ void mask_blend_kernel(const half_t* x, const half_t* init, const hal
   }
 }
 
+// out[b, c, p] = mask[b, p] != 0 ? x[b, c, p] : known[level[b]][b, c, p]: the mask-guided decoding of an edit inside a mask (DiffEdit). Outside the mask
+// the sampled latents are REPLACED by the stored latents of the request's own noise level (`known` = [levels][B][C][HW], the inversion trajectory); inside
+// they are kept. A selection, not arithmetic: the 16-bit patterns are copied, so m = 1 everywhere returns x's bits and m = 0 everywhere the stored level's.
+// level: device int32 [B] (clamped to [0, levels) here: a bad table can not read outside `known`). out may alias x (each thread reads what it writes first);
+// out2 optional. vec: HW % 8 == 0 and every pointer 16-byte aligned, so that one thread owns 8 halfs of one (b, c) row with one 16-byte access per operand;
+// other shapes take the scalar loop of the same kernel.
+__global__ __launch_bounds__(256) void known_blend_kernel(const uint16_t* x, const uint16_t* known, const int* level, const uint16_t* mask, uint16_t* out,
+                                                          uint16_t* out2, int C, long HW, long n, int levels, int vec) {
+  const long stride = (long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (vec) {
+    for (long i = t0 * 8; i < n; i += stride * 8) {
+      const long b = i / (C * HW), p = i % HW;
+      const int lv = min(max(level[b], 0), levels - 1);
+      const uint4 xv = *(const uint4*)(x + i), kv = *(const uint4*)(known + (long)lv * n + i), mv = *(const uint4*)(mask + b * HW + p);
+      const uint32_t xs[4] = {xv.x, xv.y, xv.z, xv.w}, ks[4] = {kv.x, kv.y, kv.z, kv.w}, ms[4] = {mv.x, mv.y, mv.z, mv.w};
+      uint32_t o[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {             // two halfs per word; +0 and -0 both count as "outside"
+        const uint32_t sel = ((ms[q] & 0x7fffu) ? 0xffffu : 0u) | ((ms[q] & 0x7fff0000u) ? 0xffff0000u : 0u);
+        o[q] = (xs[q] & sel) | (ks[q] & ~sel);
+      }
+      const uint4 ov = make_uint4(o[0], o[1], o[2], o[3]);
+      *(uint4*)(out + i) = ov;
+      if (out2) *(uint4*)(out2 + i) = ov;
+    }
+    return;
+  }
+  for (long i = t0; i < n; i += stride) {
+    const long b = i / (C * HW), p = i % HW;
+    const int lv = min(max(level[b], 0), levels - 1);
+    const uint16_t o = (mask[b * HW + p] & 0x7fffu) ? x[i] : known[(long)lv * n + i];
+    out[i] = o;
+    if (out2) out2[i] = o;
+  }
+}
+
 // Fold a LayerNorm (gamma, beta over K features) into the linear layer that consumes it (weights finalize, once):
 //   Wf[n][k] = fp16(W[n][k] * gamma[k]);  cs[n] = sum_k Wf[n][k] (of the ROUNDED values the MFMA will see);  lb[n] = bias[n] + sum_k W[n][k] * beta[k]
 // so that  LN(x) . W^T + bias = rstd * (x . Wf^T - mean * cs) + lb  (gemm_f16_kernel epilogue). One workgroup per output row.
@@ -676,6 +712,15 @@ hipError_t ia2p_launch_mask_blend(const half_t* x, const half_t* init, const hal
                                   half_t* out, half_t* out2, int B, int C, long HW, hipStream_t s, const float* coef) {
   const long n = (long)B * C * HW;
   hipLaunchKernelGGL(mask_blend_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, x, init, noise, mask, c0, c1, out, out2, C, HW, n, coef);
+  return hipGetLastError();
+}
+hipError_t ia2p_launch_known_blend(const half_t* x, const half_t* known, const int* level, const half_t* mask, half_t* out, half_t* out2, int B, int C, long HW,
+                                   int levels, hipStream_t s) {
+  const long n = (long)B * C * HW;
+  auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  const int vec = HW % 8 == 0 && a16(x) && a16(known) && a16(mask) && a16(out) && a16(out2);
+  hipLaunchKernelGGL(known_blend_kernel, dim3(grid_for(vec ? n / 8 : n, 256)), dim3(256), 0, s, (const uint16_t*)x, (const uint16_t*)known, level,
+                     (const uint16_t*)mask, (uint16_t*)out, (uint16_t*)out2, C, HW, n, levels, vec);
   return hipGetLastError();
 }
 hipError_t ia2p_launch_prior_step(const float* smp, const half_t* o_c, const half_t* o_u, const float* noise, float g, float sqrt_a, float sqrt_b, float k0, float k1,

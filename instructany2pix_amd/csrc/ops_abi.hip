@@ -44,6 +44,54 @@ ia2p_status ia2p_mask_blend_v(void* stream, const void* x, const void* init, con
   return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "mask_blend_v");
 }
 
+// ---- editing inside a mask: the selection of the sampling loops and the three image kernels. Every refusal comes before any HIP call. ----------------------
+ia2p_status ia2p_known_blend_v(void* stream, const void* x, const void* known, const int32_t* level, const void* mask, void* out, void* out2, int B, int C,
+                               int64_t HW, int levels) {
+  if (!x || !known || !level || !mask || !out) return fail(nullptr, IA2P_ERR_INVALID, "known_blend_v: null argument");
+  if (B < 1 || C < 1 || HW < 1 || levels < 1) return fail(nullptr, IA2P_ERR_SHAPE, "known_blend_v: B=%d C=%d HW=%lld levels=%d must all be >= 1", B, C, (long long)HW, levels);
+  if ((double)B * C * (double)HW * levels > 4.0e18) return fail(nullptr, IA2P_ERR_SHAPE, "known_blend_v: the trajectory store exceeds a 64-bit element count");
+  hipError_t e = ia2p_launch_known_blend((const half_t*)x, (const half_t*)known, (const int*)level, (const half_t*)mask, (half_t*)out, (half_t*)out2, B, C, (long)HW,
+                                         levels, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "known_blend_v");
+}
+
+static ia2p_status check_mask_image(const char* what, int B, int H, int W, int C) {
+  if (B < 0 || H < 0 || W < 0) return fail(nullptr, IA2P_ERR_INVALID, "%s: negative size B=%d H=%d W=%d", what, B, H, W);
+  if (B < 1 || H < 1 || W < 1) return fail(nullptr, IA2P_ERR_SHAPE, "%s: empty image B=%d H=%d W=%d", what, B, H, W);
+  if ((int64_t)B * H * W * C > INT32_MAX) return fail(nullptr, IA2P_ERR_SHAPE, "%s: %lld elements exceed the 32-bit count of one launch", what, (long long)B * H * W * C);
+  return IA2P_OK;
+}
+
+ia2p_status ia2p_mask_to_latent(void* stream, const void* mask_u8, void* out, int B, int H, int W, int f) {
+  if (!mask_u8 || !out) return fail(nullptr, IA2P_ERR_INVALID, "mask_to_latent: null pointer");
+  ia2p_status st = check_mask_image("mask_to_latent", B, H, W, 1);
+  if (st != IA2P_OK) return st;
+  if (f < 1 || f > 64) return fail(nullptr, IA2P_ERR_INVALID, "mask_to_latent: f=%d (1 .. 64)", f);
+  if (H % f || W % f) return fail(nullptr, IA2P_ERR_SHAPE, "mask_to_latent: H=%d W=%d are not multiples of f=%d", H, W, f);
+  hipError_t e = ia2p_launch_mask_to_latent((const uint8_t*)mask_u8, (half_t*)out, B, H, W, f, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "mask_to_latent");
+}
+
+ia2p_status ia2p_mask_feather_u8(void* stream, const void* mask_u8, void* out, void* workspace, int B, int H, int W, int r) {
+  if (!mask_u8 || !out || !workspace) return fail(nullptr, IA2P_ERR_INVALID, "mask_feather_u8: null pointer");
+  if (((uintptr_t)workspace & 1) != 0) return fail(nullptr, IA2P_ERR_INVALID, "mask_feather_u8: the workspace holds 16-bit sums and must be 2-byte aligned");
+  if (out == mask_u8) return fail(nullptr, IA2P_ERR_INVALID, "mask_feather_u8: out may not alias the mask (the column pass reads it)");
+  ia2p_status st = check_mask_image("mask_feather_u8", B, H, W, 2);
+  if (st != IA2P_OK) return st;
+  if (r < 0 || r > 64) return fail(nullptr, IA2P_ERR_INVALID, "mask_feather_u8: r=%d (0 .. 64)", r);
+  hipError_t e = ia2p_launch_mask_feather_u8((const uint8_t*)mask_u8, (uint8_t*)out, (uint16_t*)workspace, B, H, W, r, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "mask_feather_u8");
+}
+
+ia2p_status ia2p_image_composite_u8(void* stream, const void* edited, const void* base, const void* alpha, void* out, int B, int H, int W, int C) {
+  if (!edited || !base || !alpha || !out) return fail(nullptr, IA2P_ERR_INVALID, "image_composite_u8: null pointer");
+  if (C != 1 && C != 3) return fail(nullptr, IA2P_ERR_SHAPE, "image_composite_u8: C=%d (1 or 3 channels)", C);
+  ia2p_status st = check_mask_image("image_composite_u8", B, H, W, C);
+  if (st != IA2P_OK) return st;
+  hipError_t e = ia2p_launch_image_composite_u8((const uint8_t*)edited, (const uint8_t*)base, (const uint8_t*)alpha, (uint8_t*)out, B, H, W, C, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "image_composite_u8");
+}
+
 ia2p_status ia2p_prior_step(void* stream, const float* sample, const void* out_cond, const void* out_uncond, const float* noise, float g, float sqrt_a,
                             float sqrt_b, float k0, float k1, float sigma, float* out, int64_t n) {
   if (!sample || !out_uncond || !out || n < 0 || !(sqrt_a > 0.f) || !(sqrt_b > 0.f)) return fail(nullptr, IA2P_ERR_INVALID, "prior_step: bad argument");

@@ -18,7 +18,7 @@ from typing import Callable, Optional, Tuple
 
 import torch
 
-from .scheduler import DDIMScheduler, fused_update
+from .scheduler import DDIMScheduler, fused_update, known_blend_v, level_table
 
 OUTPUT_TYPES = ("latent", "pt", "np", "pil")            # (image_processor.OUTPUT_TYPES; repeated so that importing this module loads no PIL)
 
@@ -104,11 +104,12 @@ class _PipelineBase:
         if self.vae is not None and output_type not in OUTPUT_TYPES:
             raise ValueError(f"output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
 
-    def _image_latents(self, image, height=None, width=None, seeds=None, draw=0):
+    def _image_latents(self, image, height=None, width=None, seeds=None, draw=0, keep=None):
         """`image=` -> scaled latents: with a VAE attached, `image_processor.preprocess` (PIL, uint8 arrays, [0, 1] floats, [-1, 1] tensors;
         4-channel tensors are latents already) then the posterior sample; with hooks only, the hook gets `image` as it is.
         `seeds` (one per image) / `draw`: the posterior sample from the images' own streams (`HipAutoencoderKL.encode_to_latents`); an attached VAE only --
-        a `vae_encode=` hook draws its own sample and never sees a seed."""
+        a `vae_encode=` hook draws its own sample and never sees a seed. `keep` (a dict, an attached VAE only): receives the preprocessed image the
+        encoder sees as keep["image"] (an edit inside a mask composites its result with it)."""
         if self._vae_encode is None:
             raise NotImplementedError("VAE encode is not attached: pass latents=, or construct with vae= or vae_encode=<callable>")
         if self.vae is None:
@@ -116,6 +117,8 @@ class _PipelineBase:
         image = self.image_processor.preprocess(image, height=height, width=width)
         if image.shape[1] == 4:
             return image
+        if keep is not None:
+            keep["image"] = image
         return self._vae_encode(image) if seeds is None else self._vae_encode(image, seeds=seeds, draw=draw)
 
     def _output(self, latents, output_type):
@@ -146,7 +149,10 @@ class SDXLDDIMPipeline(_PipelineBase):
                 generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None, negative_prompt_embeds=None,
                 pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, output_type="pil", return_dict=True,
                 cross_attention_kwargs=None, original_size: Tuple[int, int] = None, crops_coords_top_left=(0, 0),
-                target_size: Tuple[int, int] = None, image_embeds=None, callback=None, **unused):
+                target_size: Tuple[int, int] = None, image_embeds=None, callback=None, return_trajectory: bool = False, **unused):
+        """`return_trajectory` (new; False: nothing changes): the output also carries `.trajectory`, fp16 [N + 1, B, 4, h, w]: level 0 the latents the loop
+        starts from, level j + 1 the result of iteration j (what `callback` sees there), written through `out2` of the update launch the loop makes anyway.
+        An edit inside a mask replaces the outside of every sampling step with the level of the same noise (`StableDiffusionXLPipeline(known_trajectory=)`)."""
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)                       # :133
         if strength < 0 or strength > 1:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
@@ -176,6 +182,10 @@ class SDXLDDIMPipeline(_PipelineBase):
 
         eps = torch.empty_like(latents)
         nxt = torch.empty_like(latents)
+        traj = None
+        if return_trajectory:
+            traj = torch.empty((num_inference_steps + 1,) + tuple(latents.shape), dtype=torch.float16, device=dev)
+            traj[0].copy_(latents)
         prev_t = None
         acp = self.scheduler.alphas_cumprod
         for i, t in enumerate(reversed(self.scheduler.timesteps)):                              # :251 ascending t
@@ -186,10 +196,12 @@ class SDXLDDIMPipeline(_PipelineBase):
             a_prev = acp[prev_t] if prev_t is not None else self.scheduler.final_alpha_cumprod  # :262-267
             prev_t = t
             c_x, c_e = DDIMScheduler.inversion_coeffs(float(a_t), float(a_prev))
-            fused_update(latents, eps, None, 1.0, c_x, c_e, nxt)                                # :270-275 _backward_ddim
+            fused_update(latents, eps, None, 1.0, c_x, c_e, nxt, None if traj is None else traj[i + 1])      # :270-275 _backward_ddim
             latents, nxt = nxt, latents
             if callback is not None:
                 callback(i, t, latents)
+        if traj is not None:
+            return StableDiffusionXLPipelineOutput(images=latents, trajectory=traj)
         return StableDiffusionXLPipelineOutput(images=latents)                                  # :278 raw latents
 
 
@@ -201,9 +213,16 @@ class StableDiffusionXLPipeline(_PipelineBase):
                  negative_prompt=None, num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                  output_type="latent", return_dict=True, callback=None, callback_steps=1, cross_attention_kwargs=None,
-                 guidance_rescale: float = 0.0, original_size=None, crops_coords_top_left=(0, 0), target_size=None, **unused):
+                 guidance_rescale: float = 0.0, original_size=None, crops_coords_top_left=(0, 0), target_size=None, known_trajectory=None, edit_mask=None,
+                 **unused):
+        """`known_trajectory` + `edit_mask` (new; both None: nothing changes): mask-guided decoding. `known_trajectory` is `inverse(return_trajectory=True)`'s
+        store over the SAME `num_inference_steps`, fp16 [N + 1, B, 4, h, w]; `edit_mask` a {0, 1} latent mask [B or 1, 1, h, w]. Where the mask is 0 the start
+        is level N and the result of sampling step i is replaced by level N - 1 - i (`ia2p_known_blend_v`: a selection, one launch per step), so the last
+        step leaves level 0 there, bit for bit."""
         if guidance_rescale != 0.0 or eta != 0.0:
             raise NotImplementedError("guidance_rescale / eta are inactive on the reference's path (sdxl_pipeline.py:846, eta=0)")
+        if (known_trajectory is None) != (edit_mask is None):
+            raise ValueError("`known_trajectory` and `edit_mask` go together: pass both or neither")
         self._check_embeds(prompt, prompt_embeds, pooled_prompt_embeds)
         self._check_output_type(output_type)
         do_cfg = guidance_scale > 1.0                                                           # sdxl_pipeline.py:735
@@ -239,6 +258,18 @@ class StableDiffusionXLPipeline(_PipelineBase):
         prompt_embeds, added = conditioning(dev, prompt_embeds, pooled_prompt_embeds, add_time_ids, *neg)
 
         B = latents.shape[0]
+        lv = None
+        if known_trajectory is not None:
+            known = known_trajectory.to(device=dev, dtype=torch.float16).contiguous()
+            if tuple(known.shape) != (num_inference_steps + 1,) + tuple(latents.shape):
+                raise ValueError(f"`known_trajectory` must be [num_inference_steps + 1 = {num_inference_steps + 1}, {', '.join(map(str, latents.shape))}], "
+                                 f"got {tuple(known.shape)}")
+            edit_mask = edit_mask.to(device=dev, dtype=torch.float16)
+            if tuple(edit_mask.shape) not in ((1, 1) + tuple(latents.shape[-2:]), (B, 1) + tuple(latents.shape[-2:])):
+                raise ValueError(f"`edit_mask` must be a latent mask [{B} or 1, 1, {latents.shape[-2]}, {latents.shape[-1]}], got {tuple(edit_mask.shape)}")
+            edit_mask = edit_mask.expand(B, -1, -1, -1).contiguous()
+            lv = level_table([[n] * B for n in range(num_inference_steps, -1, -1)], known.shape[0], dev)     # row 0: the start; row i + 1: after step i
+            latents = known_blend_v(latents, known, lv[0], edit_mask, torch.empty_like(latents))
         if do_cfg:
             model_in = torch.cat([latents, latents], dim=0)                                     # :826 cat([latents]*2)
             eps = torch.empty_like(model_in)
@@ -254,6 +285,8 @@ class StableDiffusionXLPipeline(_PipelineBase):
                 fused_update(model_in[:B], eps[:B], eps[B:], guidance_scale, c_x, c_e, nxt_in[:B], nxt_in[B:])
             else:
                 fused_update(model_in, eps, None, 1.0, c_x, c_e, nxt_in)
+            if lv is not None:                                                                  # outside the mask: the inverted latents of this noise level
+                known_blend_v(nxt_in[:B], known, lv[i + 1], edit_mask, nxt_in[:B], nxt_in[B:] if do_cfg else None)
             model_in, nxt_in = nxt_in, model_in
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, model_in[:B])

@@ -10,6 +10,9 @@ and returns what `image_processor.postprocess(image, output_type="pil")` makes o
                "latent": unchanged.
 
 Both directions equal diffusers' numpy / torch arithmetic bit for bit (tests/test_image_io_gpu.py checks every 8-bit code and every fp16 pattern).
+
+Editing inside a mask adds the mask's side: `load_edit_mask` (forms and sizes of a user's mask, on the host), `mask_to_latent`, `mask_feather`
+and `image_composite` (integer HIP kernels of csrc/image.hip: the latent mask, the inward seam feather, the 8-bit composite with the base image).
 """
 from __future__ import annotations
 
@@ -80,6 +83,105 @@ def requantize(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     with torch.cuda.device(x.device):
         _ffi.check(_ffi.lib().ia2p_image_requantize(_stream(x.device), _ffi.ptr(x), _ffi.ptr(out), x.numel()))
     return out
+
+
+# ---- editing inside a mask (include/ia2p.h, "edit mask") -------------------------------------------------------------------------------------------------
+EDIT_FEATHER_MAX = 64
+
+
+def check_edit_feather(r) -> int:
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) <= EDIT_FEATHER_MAX:
+        raise ValueError(f"edit_feather must be an integer radius of 0 .. {EDIT_FEATHER_MAX} pixels, got {r!r}")
+    return int(r)
+
+
+def mask_to_latent(mask_u8: torch.Tensor, f: int) -> torch.Tensor:
+    """uint8 [B, H, W] on the device -> fp16 [B, 1, H / f, W / f]: 1.0 where any pixel of the cell's f x f block is >= 128."""
+    _device_tensor(mask_u8, torch.uint8, "mask_to_latent")
+    if mask_u8.ndim != 3:
+        raise ValueError(f"mask_to_latent expects [B,H,W], got {tuple(mask_u8.shape)}")
+    B, H, W = mask_u8.shape
+    f = int(f)
+    out = torch.empty(B, 1, H // max(f, 1), W // max(f, 1), dtype=torch.float16, device=mask_u8.device)
+    with torch.cuda.device(mask_u8.device):
+        _ffi.check(_ffi.lib().ia2p_mask_to_latent(_stream(mask_u8.device), _ffi.ptr(mask_u8), _ffi.ptr(out), B, H, W, f))
+    return out
+
+
+def mask_feather(mask_u8: torch.Tensor, r: int) -> torch.Tensor:
+    """uint8 [B, H, W] on the device -> the compositing alpha, uint8 [B, H, W]: min(bin, box mean of bin over (2 r + 1)^2, edge replicate, rounded) with
+    bin = 255 where the mask is >= 128. The ramp lies inside the mask: alpha is 0 wherever the mask is 0."""
+    _device_tensor(mask_u8, torch.uint8, "mask_feather")
+    if mask_u8.ndim != 3:
+        raise ValueError(f"mask_feather expects [B,H,W], got {tuple(mask_u8.shape)}")
+    B, H, W = mask_u8.shape
+    out, ws = torch.empty_like(mask_u8), torch.empty(B, H, W, dtype=torch.int16, device=mask_u8.device)
+    with torch.cuda.device(mask_u8.device):
+        _ffi.check(_ffi.lib().ia2p_mask_feather_u8(_stream(mask_u8.device), _ffi.ptr(mask_u8), _ffi.ptr(out), _ffi.ptr(ws), B, H, W, int(r)))
+    return out
+
+
+def image_composite(edited: torch.Tensor, base: torch.Tensor, alpha: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """uint8 [B, H, W, C] images and uint8 [B, H, W] alpha on the device -> (a e + (255 - a) b + 127) / 255 per byte. `out` may be `edited`."""
+    for t in (edited, base, alpha):
+        _device_tensor(t, torch.uint8, "image_composite")
+    out = torch.empty_like(edited) if out is None else _device_tensor(out, torch.uint8, "image_composite")
+    if edited.ndim != 4 or base.shape != edited.shape or out.shape != edited.shape or tuple(alpha.shape) != tuple(edited.shape[:3]):
+        raise ValueError(f"image_composite expects [B,H,W,C] images of one shape and a [B,H,W] alpha, got {tuple(edited.shape)}, {tuple(base.shape)}, {tuple(alpha.shape)}")
+    B, H, W, Ch = edited.shape
+    with torch.cuda.device(edited.device):
+        _ffi.check(_ffi.lib().ia2p_image_composite_u8(_stream(edited.device), _ffi.ptr(edited), _ffi.ptr(base), _ffi.ptr(alpha), _ffi.ptr(out), B, H, W, Ch))
+    return out
+
+
+def fit_edit_mask(mask: PIL.Image.Image, size: int) -> PIL.Image.Image:
+    """a mask of the base image FILE's size through what `loas_base_img` does to the image: the geometry of `resize_and_crop(..., 'middle')` (scaled side
+    truncated to an int, float crop box) and the final resize, every resampling NEAREST, so that it stays registered with the image and stays binary"""
+    near = PIL.Image.Resampling.NEAREST
+    w, h = mask.size
+    if w > h:                                       # relatively wider than the square: fit the height, crop columns
+        mask = mask.resize((int(size * w / h), size), near)
+        lo = (mask.size[0] - size) / 2
+        mask = mask.crop((lo, 0, lo + size, mask.size[1]))
+    elif w < h:                                     # relatively taller: fit the width, crop rows
+        mask = mask.resize((size, int(size * h / w)), near)
+        lo = (mask.size[1] - size) / 2
+        mask = mask.crop((0, lo, mask.size[0], lo + size))
+    return mask.resize((size, size), near)
+
+
+def load_edit_mask(mask, height: int, width: int, file_size=None) -> np.ndarray:
+    """The mask-loading rule of an edit inside a mask -> uint8 [height, width] in {0, 255}, 255 = "may change".
+    Forms: a PIL image of any mode (converted to "L"), a file path, a numpy uint8 / bool / float [H, W] array; binarised at 128 (floats at 0.5).
+    Sizes: height x width (the pixels the base latents stand for: `base_image_size` squared for a loaded base image file, vae_scale_factor x the latent
+    grid for latent-only callers) is used as is; `file_size` = (width, height) of the base image FILE goes through `fit_edit_mask`. Any other size raises."""
+    if isinstance(mask, (str, bytes)) or hasattr(mask, "__fspath__"):
+        mask = PIL.Image.open(mask)
+    if isinstance(mask, PIL.Image.Image):
+        a = np.asarray(mask.convert("L"))
+    elif isinstance(mask, np.ndarray):
+        a = mask
+    else:
+        raise TypeError(f"edit_mask must be a PIL image, a numpy [H, W] array or a file path, got {type(mask)}")
+    if a.ndim != 2:
+        raise ValueError(f"edit_mask must be one [H, W] plane, got shape {tuple(a.shape)}")
+    if a.dtype == np.bool_:
+        on = a
+    elif a.dtype == np.uint8:
+        on = a >= 128
+    elif np.issubdtype(a.dtype, np.floating):
+        on = a >= 0.5
+    else:
+        raise TypeError(f"edit_mask arrays must be uint8, bool or float, got {a.dtype}")
+    u8 = np.where(on, 255, 0).astype(np.uint8)
+    if u8.shape == (height, width):
+        return np.ascontiguousarray(u8)
+    if file_size is not None and (u8.shape[1], u8.shape[0]) == tuple(file_size) and height == width:
+        return np.ascontiguousarray(np.asarray(fit_edit_mask(PIL.Image.fromarray(u8), height)))
+    sizes = f"{height} x {width} (height x width of the base image as the pipeline holds it)"
+    if file_size is not None:
+        sizes += f" or {file_size[1]} x {file_size[0]} (the base image file)"
+    raise ValueError(f"edit_mask is {u8.shape[0]} x {u8.shape[1]}: expected {sizes}")
 
 
 def _binarize_lut(normalize: bool) -> np.ndarray:

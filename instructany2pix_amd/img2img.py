@@ -20,7 +20,7 @@ import torch
 
 from . import noise as _noise
 from .ddim import StableDiffusionXLPipelineOutput, _PipelineBase, conditioning, expand_rows
-from .scheduler import EulerDiscreteScheduler, check_kept_steps, fused_update, kept_steps
+from .scheduler import EulerDiscreteScheduler, check_kept_steps, fused_update, kept_steps, mask_blend
 
 
 def get_add_time_ids_aesthetic(unet, original_size, crops_coords_top_left, target_size, aesthetic_score, negative_aesthetic_score,
@@ -66,12 +66,18 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
                  negative_pooled_prompt_embeds=None, output_type="pil", return_dict=True, callback=None, callback_steps=1,
                  cross_attention_kwargs=None, original_size: Tuple[int, int] = None, crops_coords_top_left=(0, 0),
                  target_size: Tuple[int, int] = None, negative_original_size=None, negative_crops_coords_top_left=(0, 0),
-                 negative_target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, noise_seed=None, noise_draw=None, **unused):
+                 negative_target_size=None, aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, noise_seed=None, noise_draw=None,
+                 known_latents=None, edit_mask=None, **unused):
         """`latents` = clean image latents (already scaled by the VAE scaling factor) instead of `image`; `noise` = the
         start noise instead of drawing it from `generator` (both are conveniences for tests and latent-space callers).
         `noise_seed` (an int, or one per batch element; None: `generator` as ever): the start noise is drawn on the device from the request's own stream
         (noise.py: draw id `noise_draw`, default DRAW_REFINER), and the posterior sample of an `image=` from draw DRAW_HANDOFF_POSTERIOR of the same seed.
-        A supplied `noise` wins over the seed, the seed over `generator`."""
+        A supplied `noise` wins over the seed, the seed over `generator`.
+        `known_latents` + `edit_mask` (both None: nothing changes): an edit inside a mask. Where the {0, 1} latent mask [B or 1, 1, h, w] is 0 the latents are
+        `known_latents` at the loop's noise level, known + sigma * noise with the loop's OWN noise (no new draw): `ia2p_mask_blend` with (1, sigma) at the
+        start, (1, sigma_next) after each Euler step, (1, 0) after the last, which leaves `known_latents` there bit for bit."""
+        if (known_latents is None) != (edit_mask is None):
+            raise ValueError("`known_latents` and `edit_mask` go together: pass both or neither")
         if strength < 0 or strength > 1:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if num_inference_steps is None or not isinstance(num_inference_steps, int) or num_inference_steps <= 0:
@@ -100,6 +106,14 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
         noise, = _noise.resolve_noises([noise], [latents.shape], [noise_seed], [_noise.DRAW_REFINER if noise_draw is None else noise_draw], dev, generator)
         noise = noise.to(device=dev, dtype=torch.float16).contiguous()
         x = self.scheduler.add_noise(latents, noise, timesteps[:1])
+        if edit_mask is not None:
+            known_latents = known_latents.to(device=dev, dtype=torch.float16).contiguous()
+            edit_mask = edit_mask.to(device=dev, dtype=torch.float16)
+            if known_latents.shape != latents.shape or tuple(edit_mask.shape) not in ((1, 1) + tuple(latents.shape[-2:]), (batch, 1) + tuple(latents.shape[-2:])):
+                raise ValueError(f"`known_latents` must have the latents' shape {tuple(latents.shape)} and `edit_mask` be [{batch} or 1, 1, {latents.shape[-2]}, "
+                                 f"{latents.shape[-1]}], got {tuple(known_latents.shape)} and {tuple(edit_mask.shape)}")
+            edit_mask = edit_mask.expand(batch, -1, -1, -1).contiguous()
+            mask_blend(x, known_latents, noise, edit_mask, 1.0, float(self.scheduler.sigmas[self.scheduler.index_for_timestep(timesteps[0])]), x)
 
         height, width = latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor
         original_size = original_size or (height, width)
@@ -128,6 +142,8 @@ class StableDiffusionXLImg2ImgPipeline(_PipelineBase):
                 fused_update(x, eps[:B], eps[B:], guidance_scale, c_x, c_e, nxt)
             else:
                 fused_update(x, eps, None, 1.0, c_x, c_e, nxt)
+            if edit_mask is not None:                                    # the known region at the noise level the step arrived at (sigma 0 after the last)
+                mask_blend(nxt, known_latents, noise, edit_mask, 1.0, float(self.scheduler.sigmas[idx + 1]), nxt)
             x, nxt = nxt, x
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, x)

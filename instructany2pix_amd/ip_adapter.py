@@ -174,7 +174,8 @@ class IPAdapterXL(IPAdapter):
                  mode="global", prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
                  negative_pooled_prompt_embeds=None, noise_seed=None, noise_draw=None, **kwargs):
         """`seed` builds the torch generator the pipeline draws from, as in the reference. `noise_seed` / `noise_draw` go through to a pipeline that draws noise
-        of its own (the inpainting pipeline): the request's Philox stream and the draw id in it (noise.py); they win over the generator."""
+        of its own (the inpainting pipeline): the request's Philox stream and the draw id in it (noise.py); they win over the generator.
+        `known_trajectory=` / `edit_mask=` (an edit inside a mask, ddim.py) reach the pipeline with the other keywords."""
         if noise_seed is not None:
             kwargs.update(noise_seed=noise_seed, noise_draw=noise_draw)
         self.set_scale(scale)

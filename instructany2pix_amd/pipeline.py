@@ -150,6 +150,63 @@ def refiner_handoff_by_image(pipeline) -> bool:
     return vae_route
 
 
+# ---- editing inside a mask: what `__call__` and `batch.edit_batch` share --------------------------------------------------------------
+def check_edit_output_type(output_type):
+    if output_type not in ("pil", "latent"):
+        raise ValueError(f"an edit_mask composites in 8 bits: output_type must be \"pil\" or \"latent\", got {output_type!r} (a float composite is not built)")
+
+
+def edit_mask_file_size(c):
+    """(width, height) of the base image FILE where the request's base image is loaded from it (a mask of that size is then accepted too), else None"""
+    if c.get("base_latents") is None and c.get("base_image") is None and c.get("base_img_path") is not None:
+        with PIL.Image.open(c["base_img_path"]) as im:
+            return im.size
+    return None
+
+
+def resolve_edit_mask(pipeline, mask, base_latents, file_size=None, pixels: bool = True):
+    """-> (pixel mask uint8 [1, H, W] in {0, 255}, latent mask fp16 [1, 1, h, w] in {0, 1}), both on the UNet's device. `mask`: anything
+    `image_processor.load_edit_mask` takes, at H x W = vae_scale_factor x the latent grid (or `file_size`); a latent cell is 1 if any of its pixels is in
+    the mask (`ia2p_mask_to_latent`). A torch tensor [1, 1, h, w] is a latent mask already; its pixel mask is each cell repeated, and is only built when
+    `pixels` asks for it (the loops need the latent mask alone: `denoise` and `denoise_batch` pass False, so a mask their caller resolved costs nothing more)."""
+    from .image_processor import load_edit_mask, mask_to_latent
+    dev, f = pipeline.pipe.unet.device, int(pipeline.pipe.vae_scale_factor)
+    h, w = int(base_latents.shape[-2]), int(base_latents.shape[-1])
+    if torch.is_tensor(mask):
+        if tuple(mask.shape) != (1, 1, h, w):
+            raise ValueError(f"a tensor edit_mask is a latent mask [1, 1, {h}, {w}], got {tuple(mask.shape)} (pixel masks: PIL, numpy or a file path, {f * h} x {f * w})")
+        m = (mask.to(dev) != 0).to(torch.float16).contiguous()
+        if not pixels:
+            return None, m
+        px = (m[0] * 255).to(torch.uint8).repeat_interleave(f, dim=-2).repeat_interleave(f, dim=-1).contiguous()
+        return px, m
+    px = torch.from_numpy(load_edit_mask(mask, f * h, f * w, file_size))[None].to(dev).contiguous()
+    return px, mask_to_latent(px, f)
+
+
+def intersect_subject_mask(mask, edit_px):
+    """a subject mask ([H, W] / [1, H, W] / [B, 1, H, W] in [0, 1], uint8 0..255 or PIL) times the edit mask (uint8 [1, H', W'] in {0, 255}; resized NEAREST
+    where the sizes differ), before `inpaint.prepare_mask`: a subject pass under an edit mask repaints inside both"""
+    if isinstance(mask, PIL.Image.Image):
+        import numpy as np
+        mask = torch.from_numpy(np.asarray(mask.convert("L")).copy())
+    m = torch.as_tensor(mask)
+    m = m.float() / 255.0 if m.dtype == torch.uint8 else m.float()
+    e = (edit_px.to(m.device).float() / 255.0)[None]
+    if tuple(e.shape[-2:]) != tuple(m.shape[-2:]):
+        e = torch.nn.functional.interpolate(e, size=tuple(m.shape[-2:]))
+    return m * e.reshape((1,) * (m.ndim - 2) + tuple(e.shape[-2:]))
+
+
+def composite_edit(pipeline, decoded, base_u8, alpha):
+    """decoded image fp16 [1, 3, H, W] in [-1, 1] -> the list of PIL images `postprocess(output_type="pil")` gives, composited in 8 bits with the base image
+    through the feathered mask: every pixel outside the user's mask carries the base image's byte"""
+    from .image_processor import image_composite, image_to_u8
+    u8 = image_to_u8(decoded.to(device=base_u8.device, dtype=torch.float16).contiguous())
+    u8 = image_composite(u8, base_u8, alpha, out=u8).cpu().numpy()
+    return [PIL.Image.fromarray(a[..., 0] if a.shape[-1] == 1 else a) for a in u8]
+
+
 def condition_from_llm_output(out, mm_data) -> dict:
     """`forward_llm`'s five-tuple -> the LLM's part of the conditioning dict a `conditioner=` would return; without an `<im_gen>` only the caption counts.
     `base_image`: the PIL image an mm_data entry carries for the base image's file; `subject_data`: the subjects that are image entries (:363-366)"""
@@ -236,8 +293,12 @@ class InstructAny2PixPipeline:
     # ---- the hot segment on explicit conditioning ------------------------------------------------------------------
     @torch.no_grad()
     def denoise(self, base_latents, latent_la, *, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds,
-                inv_prompt_embeds=None, inv_pooled_prompt_embeds=None, alpha=0.7, num_inference_steps=25, cfg=10, scale=1.0, noise=None, seed=None):
+                inv_prompt_embeds=None, inv_pooled_prompt_embeds=None, alpha=0.7, num_inference_steps=25, cfg=10, scale=1.0, noise=None, seed=None,
+                edit_mask=None):
         """inversion -> polar mixing -> IP-Adapter guided sampling; returns (sampled latents, inverted latents).
+        `edit_mask` (None: nothing changes): edit inside the mask only (`resolve_edit_mask`: a pixel mask at vae_scale_factor x the latent grid, or a latent
+        mask tensor [1, 1, h, w]). The inversion records its trajectory, the sampling start and every sampling step are replaced outside the mask by the
+        inverted latents of the same noise level, and the sampled latents equal `base_latents` (as the loop holds them in fp16) wherever the latent mask is 0.
         `seed` (None: the draw below, as ever): the mixing noise is draw DRAW_POLAR of the request's own Philox stream (noise.py), made and mixed on the device
         (`noise.randn_seeded`, `noise.polar_mix`): the inverted latents never leave it -- no `.cpu()`, no host `randn`, no CPU mix, no upload. Row b of a
         batch of base latents draws from seed + b. A supplied `noise` wins over the seed. The device mix is fp32 arithmetic rounded once; it is not bit-equal
@@ -246,8 +307,14 @@ class InstructAny2PixPipeline:
         self.pipe_inversion.scheduler = DDIMScheduler.from_config(self.pipe.scheduler.config)  # :307
         if inv_prompt_embeds is None:        # reference inverts with prompt='' (:330); callers pass its embedding
             inv_prompt_embeds, inv_pooled_prompt_embeds = negative_prompt_embeds, negative_pooled_prompt_embeds
-        latent_inv = self.pipe_inversion.inverse(num_inference_steps=num_inference_steps, latents=base_latents,
-                                                 prompt_embeds=inv_prompt_embeds, pooled_prompt_embeds=inv_pooled_prompt_embeds).images
+        masked = {}
+        if edit_mask is not None:
+            masked["edit_mask"] = resolve_edit_mask(self, edit_mask, base_latents, pixels=False)[1]
+        inverted = self.pipe_inversion.inverse(num_inference_steps=num_inference_steps, latents=base_latents, prompt_embeds=inv_prompt_embeds,
+                                               pooled_prompt_embeds=inv_pooled_prompt_embeds, **({"return_trajectory": True} if masked else {}))
+        latent_inv = inverted.images
+        if masked:
+            masked["known_trajectory"] = inverted.trajectory
         if noise is None and seed is not None:
             z = _noise.randn_seeded(_noise.batch_seeds(seed, latent_inv.shape[0]), _noise.DRAW_POLAR, latent_inv.shape[1:], torch.float16, latent_inv.device)
             mixed = _noise.polar_mix(latent_inv, z, float(alpha))
@@ -260,7 +327,7 @@ class InstructAny2PixPipeline:
                                              scale=scale, mode="global", guidance_scale=cfg, latents=mixed,
                                              prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                                              pooled_prompt_embeds=pooled_prompt_embeds, negative_pooled_prompt_embeds=negative_pooled_prompt_embeds,
-                                             output_type="latent")
+                                             output_type="latent", **masked)
         return images, latent_inv
 
     # ---- N independent requests as one batch per evaluation, sharded over the ranks (batch.py) ---------------------------------------------------
@@ -278,14 +345,17 @@ class InstructAny2PixPipeline:
     def loas_base_img(self, base_img_path):
         return loas_base_img(base_img_path, self.base_image_size)
 
-    def _base_latents(self, c, seed=None):
+    def _base_latents(self, c, seed=None, keep=None):
         """the conditioner's `base_latents`, else its `base_image` (PIL) or `base_img_path` (loaded by `loas_base_img`) through the inversion
-        pipeline's image processor and the VAE (a posterior sample, as in the reference's `inverse(image=...)`; with `seed`, draw DRAW_BASE_POSTERIOR of it)"""
+        pipeline's image processor and the VAE (a posterior sample, as in the reference's `inverse(image=...)`; with `seed`, draw DRAW_BASE_POSTERIOR of it).
+        `keep` (a dict; an edit inside a mask composites with the base image): receives the preprocessed image as keep["image"] (`_image_latents(keep=)`)."""
         if c.get("base_latents") is not None:
             return c["base_latents"]
         img = base_image(self, c)
-        return self.pipe_inversion._image_latents(img) if seed is None else self.pipe_inversion._image_latents(
-            img, seeds=[_noise.check_seed(seed)], draw=_noise.DRAW_BASE_POSTERIOR)
+        kw = {} if keep is None else {"keep": keep}
+        if seed is not None:
+            kw.update(seeds=[_noise.check_seed(seed)], draw=_noise.DRAW_BASE_POSTERIOR)
+        return self.pipe_inversion._image_latents(img, **kw)
 
     # ---- the instruction LLM (reference :151-279) ---------------------------------------------------------------------------
     def _modality_embeds(self, mm_data):
@@ -492,7 +562,7 @@ class InstructAny2PixPipeline:
         return cs
 
     def edit_batch(self, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
-                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None):
+                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8):
         """`__call__` for N instructions on N images -> the list of its `(non_refined, oo, msg)` tuples, in request order. Every knob of `__call__` is a
         scalar (for all requests) or a list of N (`h`: one triple or N triples). `group` requests share one launch sequence in every loop.
 
@@ -523,14 +593,23 @@ class InstructAny2PixPipeline:
         there. Where the LLM samples on the device the request's seed is also its entry of `generate_batch(seeds=)`; under the host sampler the LLM keeps the
         global generator. Precedence: a noise tensor the conditioner supplies (`polar_noise`, `refiner_noise`, `subject_noise`) wins over the seed, the seed
         over the global generator. Seeded and unseeded requests may share a call and a group; the unseeded ones draw from the global generator in request
-        order among themselves. Seeded draws need no rank to be seeded alike. With `debug=True` a seeded request's message also carries `seed`."""
+        order among themselves. Seeded draws need no rank to be seeded alike. With `debug=True` a seeded request's message also carries `seed`.
+
+        Edit masks (`edit_masks`: ONE mask for all requests, or a list of N with None entries; None: today's launches, bit for bit; `edit_feather` as in
+        `__call__`). Request i may change inside its mask only, as `__call__(edit_mask=)` serves it: in a group where at least one request has a mask the
+        inversion records its trajectory and every sampling step is followed by one selection launch (`ia2p_known_blend_v`), request r at its own level
+        max(N_r - 1 - i, 0); the requests without a mask carry all ones there, which returns their bits. The refiner loop blends the base latents at its own
+        noise level with its own noise (no new draw), the subject masks are multiplied by the edit mask, and "pil" results are composited with the base
+        image in 8 bits; "np" / "pt" are refused. A group where nobody has a mask runs exactly the unmasked launch sequence."""
         from .batch import edit_batch
         return edit_batch(self, insts, mm_datas, alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
-                          subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds)
+                          subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds,
+                          **({} if edit_masks is None else dict(edit_masks=edit_masks, edit_feather=edit_feather)))
 
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
-                 use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None) -> Any:
+                 use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None,
+                 edit_mask=None, edit_feather=8) -> Any:
         """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
         `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images).
         `seed` (a 64-bit unsigned integer; None: every draw from the global CPU generator, as ever): every normal draw of the request comes from its own
@@ -539,10 +618,21 @@ class InstructAny2PixPipeline:
         host sampler the LLM keeps the global generator). The image then depends on the request and its seed alone: `edit_batch(seeds=[seed])` serves the
         same request from the same noise (equal within the batch-against-serial tolerance; bit identity across group sizes is not promised, as the UNet's
         batch-dependent plans sum in other orders). A noise the conditioner supplies (`polar_noise`, `refiner_noise`, `subject_noise`) wins over the seed.
-        With `debug=True` the message also carries `seed`."""
+        With `debug=True` the message also carries `seed`.
+        `edit_mask` (None: nothing changes, no launch and no bit): the edit may change the image inside the mask only (forms and sizes:
+        `image_processor.load_edit_mask`). Inversion records its trajectory; outside the mask every sampling step is replaced by the inverted latents of the
+        same noise level (the last step lands on the base latents), the refiner pass keeps `base_latents` re-noised with its own noise there, and every
+        subject mask is multiplied by the edit mask. "latent": both results equal `base_latents` wherever the latent mask (a cell is 1 if any of its
+        pixels is in the mask) is 0. "pil": both images are composited in 8 bits with the base image (the loaded one, or the 8-bit decode of `base_latents`)
+        through the mask feathered inwards over `edit_feather` pixels (0 .. 64; 8 is a design choice): every pixel outside the mask carries the base image's
+        byte. "np" / "pt" are refused with a mask. With `debug=True` the message also carries `edit_mask_latent`."""
         if seed is not None:
             seed = _noise.check_seed(seed)
         check_output_type(self, output_type)
+        if edit_mask is not None:
+            from .image_processor import check_edit_feather
+            check_edit_output_type(output_type)
+            edit_feather = check_edit_feather(edit_feather)
         if self.conditioner is None and self.any2pix_lm is not None:
             c = self._condition_from_llm(inst, mm_data, use_cache, llm_only, **({} if seed is None else {"seed": seed}))
             if llm_only:
@@ -558,10 +648,15 @@ class InstructAny2PixPipeline:
             if llm_only:
                 return None, None, c["caption"]
         latent_la = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], prior_y0(self, c), h, norm)
-        images, latent_inv = self.denoise(self._base_latents(c, seed), latent_la.reshape(1, -1)[0], **embeds(c),
+        masked, kept, edit_px, edit_m = {}, {}, None, None
+        base_latents = self._base_latents(c, seed) if edit_mask is None else self._base_latents(c, seed, kept)
+        if edit_mask is not None:
+            edit_px, edit_m = resolve_edit_mask(self, edit_mask, base_latents, edit_mask_file_size(c))
+            masked = dict(edit_mask=edit_m)
+        images, latent_inv = self.denoise(base_latents, latent_la.reshape(1, -1)[0], **embeds(c),
                                           inv_prompt_embeds=c.get("inv_prompt_embeds"), inv_pooled_prompt_embeds=c.get("inv_pooled_prompt_embeds"),
                                           alpha=alpha, num_inference_steps=num_inference_steps, cfg=cfg, scale=scale, seed=seed,
-                                          noise=c.get("polar_noise") if seed is not None else None)      # (unseeded: this call has always drawn its own)
+                                          noise=c.get("polar_noise") if seed is not None else None, **masked)      # (unseeded: this call has always drawn its own)
         non_refined = images
         oo = images
         decoded = None          # the decode of `images`, when the refiner hand-over made it
@@ -569,6 +664,8 @@ class InstructAny2PixPipeline:
             _need(c, REFINER_KEYS, "refiner pass")
             # Conditioning = text encoder 2 on caption + ',high quality,well-formed,award-winning' (the conditioner supplies its embeddings).
             kw = dict(strength=refinement, **embeds(c, "refiner_"), noise=c.get("refiner_noise"), output_type="latent", **({} if seed is None else {"noise_seed": seed}))
+            if edit_m is not None:                                                             # outside the mask: the base latents at the loop's noise level
+                kw.update(known_latents=base_latents, edit_mask=edit_m)
             if refiner_handoff_by_image(self):
                 # the reference hands a decoded 8-bit image over and the refiner pipeline re-encodes it with the shared VAE
                 # (`retrieve_latents(vae.encode(image)) * scaling_factor`: a posterior SAMPLE, global RNG)
@@ -589,12 +686,23 @@ class InstructAny2PixPipeline:
             by_phrase = [isinstance(k, str) for k, _ in subject_data]
             if any(by_phrase) and not all(by_phrase):
                 raise ValueError("subject_data mixes (mask, embedding) and (phrase, embedding) entries: give one kind")
-            if all(by_phrase):                                                                 # gdino/lib.py:69-103: masks from SAM on the detector's boxes
+            if edit_px is not None:                                                            # every subject mask times the edit mask, then the same passes
+                pairs = [(intersect_subject_mask(mk, edit_px), emb) for mk, emb in self._subject_mask_pairs(c, subject_data, oo)]
+                oo = subject_consistency(pairs, oo, self.ip_adapter_xl_inpaint, subject_strength, **kw)
+            elif all(by_phrase):                                                               # gdino/lib.py:69-103: masks from SAM on the detector's boxes
                 oo = self._subjects_from_phrases(c, subject_data, oo, subject_strength, kw)
             else:                                                                              # masks given by the conditioner
                 oo = subject_consistency(subject_data, oo, self.ip_adapter_xl_inpaint, subject_strength, **kw)
-        msg = "SUCCESS!" if not debug else dict(output_caption=c["caption"], latent_inv=latent_inv, latent_la=latent_la, **({} if seed is None else {"seed": seed}))
-        if output_type != "latent":
+        msg = "SUCCESS!" if not debug else dict(output_caption=c["caption"], latent_inv=latent_inv, latent_la=latent_la, **({} if seed is None else {"seed": seed}),
+                                                **({} if edit_m is None else {"edit_mask_latent": edit_m}))
+        if output_type != "latent" and edit_px is not None:                                    # "pil": composited with the base image in 8 bits
+            from .image_processor import image_to_u8, mask_feather
+            base_u8 = image_to_u8(kept["image"] if "image" in kept else self.pipe._vae_decode(base_latents.to(self.pipe.unet.device, torch.float16)))
+            alpha_u8 = mask_feather(edit_px, edit_feather)
+            refined_is_base = oo is non_refined
+            non_refined = composite_edit(self, decoded if decoded is not None else self.pipe._vae_decode(non_refined), base_u8, alpha_u8)
+            oo = non_refined if refined_is_base else composite_edit(self, self.pipe._vae_decode(oo), base_u8, alpha_u8)
+        elif output_type != "latent":
             post = self.pipe.image_processor.postprocess
             refined_is_base = oo is non_refined
             non_refined = post(decoded if decoded is not None else self.pipe._vae_decode(non_refined), output_type=output_type)

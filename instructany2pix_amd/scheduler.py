@@ -134,6 +134,38 @@ def mask_blend_v(x, init, noise, mask, coef, out, out2=None):
     return out
 
 
+def known_levels(steps):
+    """The level table of an edit inside a mask, `[iterations + 1][requests]`, iterations = max(steps): which level of the inversion trajectory (0 = the base
+    latents, N = the fully inverted ones) replaces request r's latents outside its mask. Row 0 is the sampling start, level N_r; row i + 1 follows sampling
+    step i, level max(N_r - 1 - i, 0): a request that is through is held at level 0. Pure host arithmetic."""
+    steps = [int(n) for n in steps]
+    if not steps or min(steps) < 1:
+        raise ValueError(f"known_levels: every request takes at least one step, got {steps}")
+    return [list(steps)] + [[max(n - 1 - i, 0) for n in steps] for i in range(max(steps))]
+
+
+def level_table(rows, levels: int, device) -> torch.Tensor:
+    """a host level table, checked against the `levels` of the trajectory store it indexes, as int32 on the device"""
+    flat = [int(v) for row in rows for v in row]
+    if any(v < 0 or v >= levels for v in flat):
+        raise ValueError(f"level table entries must lie in [0, {levels}), got {sorted(set(flat))}")
+    return torch.tensor(rows, dtype=torch.int32).to(device).contiguous()
+
+
+def known_blend_v(x, known, level, mask, out, out2=None):
+    """out = x where mask != 0, known[level[b]] elsewhere (ia2p_known_blend_v): a selection, the bits are copied. x, out [B, C, h, w] fp16; known
+    [levels, B, C, h, w]; level int32 device [B]; mask [B, 1, h, w] fp16. `out` may be `x`."""
+    B, Cc, h, w = x.shape
+    for t in (x, known, mask, out):
+        assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous(), "latents, trajectory and mask must be contiguous fp16 device tensors"
+    assert out2 is None or (out2.dtype == torch.float16 and out2.is_cuda and out2.is_contiguous() and out2.shape == x.shape)
+    assert known.ndim == 5 and tuple(known.shape[1:]) == (B, Cc, h, w) and out.shape == x.shape and tuple(mask.shape) == (B, 1, h, w)
+    assert level.dtype == torch.int32 and level.is_cuda and level.is_contiguous() and tuple(level.shape) == (B,)
+    _ffi.check(_ffi.lib().ia2p_known_blend_v(_ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(known), _ffi.ptr(level), _ffi.ptr(mask), _ffi.ptr(out), _ffi.ptr(out2),
+                                             B, Cc, h * w, known.shape[0]))
+    return out
+
+
 def fused_update(x, eps_u, eps_c, guidance, c_x, c_e, out, out2=None):
     """out = c_x*x + c_e*(eps_u + g*(eps_c - eps_u)) on the current stream (ia2p_ddim_step)."""
     for t in (x, eps_u, out):

@@ -31,7 +31,14 @@ own Philox stream, the inverted latents never leave it) next to the unseeded run
 edit_batch, edit_batch seeded. Its stage table gains the three seeded-noise launches ALONE (`ia2p_randn_seeded`, `ia2p_posterior_sample_seeded`, `ia2p_polar_mix_v`
 at B = 1 and B = 8 on 4 x PX/8 x PX/8 latents): microseconds per launch between two device events around 200 back-to-back launches, median of 5 such trains.
 
-    python tools/e2e_edit_bench.py --seeded --batch 1,8"""
+    python tools/e2e_edit_bench.py --seeded --batch 1,8
+
+--edit-mask (with --batch) runs the same requests WITH a centred square mask of half the image's area (`__call__(edit_mask=)`, `edit_batch(edit_masks=)`, the
+default feather) next to the unmasked run, interleaved repeat by repeat in the one process: serial, serial masked, edit_batch, edit_batch masked. The masked path
+adds one selection launch per sampling step, one blend launch per refiner step and the image launches per request; its stage table gains `edit mask` (load, upload,
+`ia2p_mask_to_latent`) and `mask feather`, and its `image_out` is the 8-bit composite.
+
+    python tools/e2e_edit_bench.py --edit-mask --batch 1,8"""
 import argparse
 import os
 import sys
@@ -64,11 +71,14 @@ _ap.add_argument("--imagebind", action="store_true", help="encode the mm_data en
 _ap.add_argument("--batch", default=None, help="comma-separated request counts: compare edit_batch with the serial loop (see the module docstring)")
 _ap.add_argument("--reps", type=int, default=3)
 _ap.add_argument("--seeded", action="store_true", help="with --batch: the same requests with per-request seeds next to the unseeded run, and the three noise launches alone")
+_ap.add_argument("--edit-mask", action="store_true", help="with --batch: the same requests with a centred half-area edit mask next to the unmasked run")
 _ap.add_argument("--steps", type=int, default=25)
 _ap.add_argument("--refinement", type=float, default=0.5)
 ARGS = _ap.parse_args()
 if ARGS.seeded and not ARGS.batch:
     _ap.error("--seeded compares against the unseeded run of --batch: give --batch too")
+if ARGS.edit_mask and not ARGS.batch:
+    _ap.error("--edit-mask compares against the unmasked run of --batch: give --batch too")
 BATCHES = [int(n) for n in ARGS.batch.split(",")] if ARGS.batch else []
 DEV = "cuda:0"
 PX = int(os.environ.get("PX", 1024))
@@ -201,6 +211,11 @@ for rnd in range(0 if BATCHES else 2):            # request 0 warms up (workspac
 if BATCHES:
     import statistics
     import instructany2pix_amd.batch as batch_mod
+    import instructany2pix_amd.image_processor as ip_mod
+    import instructany2pix_amd.pipeline as pipeline_mod
+    _wrap(pipeline_mod, "composite_edit", "image_out")              # the masked path's image out: 8-bit codec + composite
+    _wrap(pipeline_mod, "resolve_edit_mask", "edit mask")
+    _wrap(ip_mod, "mask_feather", "mask feather")
     for _name, _label in (("invert_batch", "inversion loop"), ("sample_batch", "guided sampling loop"), ("refine_batch", "refiner pass")):
         _wrap(batch_mod, _name, _label)
     NMAX = max(BATCHES)
@@ -233,6 +248,16 @@ if BATCHES:
 
     def batched_seeded(n):
         return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), seeds=SEEDS[:n], **knobs)
+
+    side_px = int(round(PX / 2 ** 0.5))            # a centred square of half the area
+    MASK = np.zeros((PX, PX), np.uint8)
+    MASK[(PX - side_px) // 2:(PX + side_px) // 2, (PX - side_px) // 2:(PX + side_px) // 2] = 255
+
+    def serial_masked(n):
+        return [pipe(inst, [], edit_mask=MASK, **knobs) for inst in insts[:n]]
+
+    def batched_masked(n):
+        return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), edit_masks=MASK, **knobs)
 
     def launches_alone():
         """the three seeded-noise launches on their own: us per launch, median of 5 trains of 200 launches between two device events"""
@@ -284,6 +309,10 @@ if BATCHES:
             run(serial_seeded, n), run(batched_seeded, n)
             runs = {"serial": [], "serial seeded": [], "edit_batch": [], "edit_batch seeded": []}
             sides = [("serial", serial), ("serial seeded", serial_seeded), ("edit_batch", batched), ("edit_batch seeded", batched_seeded)]
+        if ARGS.edit_mask:
+            run(serial_masked, n), run(batched_masked, n)
+            runs.update({"serial masked": [], "edit_batch masked": []})
+            sides += [("serial masked", serial_masked), ("edit_batch masked", batched_masked)]
         for _ in range(ARGS.reps):
             for side, fn in sides:
                 runs[side].append(run(fn, n))
@@ -301,5 +330,8 @@ if BATCHES:
         if ARGS.seeded:
             print(f"  per image, seeded / unseeded: serial {per_image['serial seeded'] / per_image['serial']:.4f}, "
                   f"edit_batch {per_image['edit_batch seeded'] / per_image['edit_batch']:.4f}", flush=True)
+        if ARGS.edit_mask:
+            print(f"  per image, masked / unmasked: serial {per_image['serial masked'] / per_image['serial']:.4f}, "
+                  f"edit_batch {per_image['edit_batch masked'] / per_image['edit_batch']:.4f}", flush=True)
     if ARGS.seeded:
         launches_alone()
