@@ -206,7 +206,8 @@ ia2p_status ia2p_image_composite_u8(void* stream, const void* edited, const void
  *   The value is fp32; an fp16 output is its round-to-nearest-even.
  * A value depends on (seed, draw, e) ONLY: not on the batch, the row's place in a launch, the output pointer's alignment, the grid or the sub-range asked for.
  * Draw ids of an edit request (instructany2pix_amd/noise.py): 0 base-image VAE posterior, 1 polar-mixing noise, 2 posterior of the refiner hand-off
- * re-encode, 3 refiner start noise, 4 + k inpaint noise of subject pass k.
+ * re-encode, 3 refiner start noise, 4 + k inpaint noise of subject pass k (k < 65532: the ids stay below the next one), 65536 = 1 << 16 the n noises of an
+ * automatic edit mask (below; element k * per + e is element e of noise k).
  * seeds, draws (and alphas below): HOST arrays [B]. They travel by value in the kernel arguments, 8 rows per launch; a larger B goes in chunks of 8 rows, one launch
  * each. No call copies anything to the device, allocates or waits. Every refusal is decided on the host before any launch: a null (or misaligned) pointer is
  * IA2P_ERR_INVALID; B < 1, per < 1, a `first` that is negative or no multiple of 4, first + per > 2^34 are IA2P_ERR_SHAPE.
@@ -224,6 +225,32 @@ ia2p_status ia2p_posterior_sample_seeded(void* stream, const void* moments, void
  * The three sums of squares have ONE fixed association that depends on `per` alone, so a row's bits do not depend on B or on its place in the batch.
  * nl = 0 gives the reference's non-finite result; it is not an error. The arithmetic is fp32: it is NOT the bit pattern of the reference's CPU fp16 tensor ops. */
 ia2p_status ia2p_polar_mix_v(void* stream, const void* x, const void* y, const float* alphas, void* out, int B, int64_t per);
+
+/* ---- Automatic edit mask: where two noise predictions differ, the instruction wants a change (the DiffEdit construction, Couairon et al. 2022) ---------------
+ * New: the reference has no mask at all. The result is a latent mask that goes into the edit-mask path above unchanged.
+ * THE RULE, for one request with base latents x0 [1, C, h, w] (per = C h w, HW = h w), its own N-step DDIM schedule and the knobs (n, s, rho, d):
+ *   1. t = timesteps[t_start], where strength s keeps the tail of the schedule that starts at index t_start = max(N - min(int(N s), N), 0); a strength that
+ *      keeps no step is refused.
+ *   2. n noises z_k [C, h, w]: supplied, else element k per + e of draw 65536 of the request's stream (Seeded noise), else n fp16 host normals.
+ *   3. x_k = fp16(sqrt(abar_t) x0 + sqrt(1 - abar_t) z_k)                               (the sampler update launch)
+ *   4. eps_src[k] = UNet of x_k at t as an inversion evaluation of the request runs it; eps_tgt[k] = UNet of x_k at t as the conditional half of one of its
+ *      sampling evaluations runs it. No guidance combination.
+ *   5. map[p] = (1 / (n C)) * sum_k sum_c |fp32(eps_tgt[k, c, p]) - fp32(eps_src[k, c, p])|    fp32; ONE order: k outer, c inner, sequential; then one product
+ *      by fp32(1 / (n C)).
+ *   6. mean = (sum_p map[p]) / fp32(HW), the sum in ONE association that depends on HW alone (the convention of polar_mix_v): with 1024 threads, thread t adds
+ *      the groups of 4 at (j 1024 + t) 4, j = 0, 1, ..., in index order, 64 lanes fold by xor-butterfly, 16 wave totals are added in wave order.
+ *      tau = fp32(0.5 rho) * mean, one fp32 product;   m[p] = map[p] > tau ? 1 : 0, strictly. Equal predictions give mean = 0 and an empty mask; nothing is
+ *      non-finite unless an input is (a NaN map value compares false: 0).
+ *   7. mask[y, x] = max of m over |dy|, |dx| <= d inside the grid (outside counts 0, no wrap at a row end); d = 0 is the identity.
+ * eps_contrast_map: eps_tgt, eps_src fp16 [B, n, C, HW] -> map_out fp32 [B, HW]. 16-byte loads where HW % 8 == 0 and both bases are 16-byte aligned, scalar loads
+ *   elsewhere; the same values either way. B <= 65535, n C <= 2^20, HW < 2^31.
+ * contrast_mask: map fp32 [B, HW = h w]; ratio (rho) HOST float [B] and dilate (d) HOST int [B] travel by value, 8 requests per launch, one workgroup per request;
+ *   mask_out fp16 [B, 1, h, w] in {0, 1}; stats_out fp32 [B, 2] = (mean, tau). No atomics, no workspace: the window reads the map. A request's mean, tau and
+ *   mask depend on its own map, ratio and dilate only: not on B, its place in the call or any pointer's alignment.
+ * Refusals, all on the host before any launch: a null or misaligned pointer (2 bytes for fp16, 4 for fp32) is IA2P_ERR_INVALID; B, n, C, HW, h or w < 1, a ratio
+ *   that is not finite and positive, a dilate outside 0 .. 16 are IA2P_ERR_SHAPE. */
+ia2p_status ia2p_eps_contrast_map(void* stream, const void* eps_tgt, const void* eps_src, float* map_out, int B, int n, int C, int64_t HW);
+ia2p_status ia2p_contrast_mask(void* stream, const float* map, const float* ratio, const int* dilate, void* mask_out, float* stats_out, int B, int h, int w);
 
 /* ---- per-operator entry points (unit tests, and hosts that keep their own module tree) ----------------------------- */
 /* Operand size: the linear-layer tiles (buffer-load staging), the halo-staged 3x3 convolution and the fused attention tiles address an operand (activations,

@@ -110,6 +110,8 @@ SIGNATURES = {
     "ia2p_randn_seeded": (_I, [_P, _P, _I, _I, _I64, _I64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ia2p_posterior_sample_seeded": (_I, [_P, _P, _P, _I, _I, _I64, _F, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ia2p_polar_mix_v": (_I, [_P, _P, _P, C.POINTER(_F), _P, _I, _I64]),
+    "ia2p_eps_contrast_map": (_I, [_P, _P, _P, _P, _I, _I, _I, _I64]),
+    "ia2p_contrast_mask": (_I, [_P, _P, C.POINTER(_F), C.POINTER(C.c_int), _P, _P, _I, _I, _I]),
     "ia2p_groupnorm_silu": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     "ia2p_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _I, _F]),
     "ia2p_gemm": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),

@@ -61,6 +61,7 @@ class EditRequest:
     noise: Optional[torch.Tensor] = None       # polar-mixing noise (CPU fp16); None: drawn from the global RNG in request order
     seed: Optional[int] = None                 # the request's own Philox stream (noise.py): without `noise`, draw DRAW_POLAR of it, made and mixed on the device
     edit_mask: Optional[object] = None         # edit inside this mask only (what `pipeline.resolve_edit_mask` takes: a pixel mask, or a latent mask [1, 1, h, w])
+    auto_mask: Optional[object] = None         # estimate the mask from the request itself (auto_mask.py: True, a dict or an AutoMask); times `edit_mask` where both are given
 
 
 def _coef_table(rows: Sequence[Sequence[tuple]], device) -> torch.Tensor:
@@ -287,6 +288,9 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
             raise ValueError(f"denoise_batch blends eps_u + g (eps_c - eps_u) for every request; cfg={r.cfg} <= 1 means NO guidance in the reference: run that request "
                              f"through pipeline.denoise / __call__ instead")
     _check_group(group, "denoise_batch")
+    if any(r.auto_mask is not None for r in requests):      # the mask estimates come first: their host draws precede every polar-mixing draw
+        from .auto_mask import apply_auto_masks
+        requests = apply_auto_masks(pipeline, requests, group)
     # polar-mixing noise comes from the global CPU RNG in REQUEST order (what N sequential reference calls would draw), on every rank alike; a request with a
     # seed and no noise draws nothing here: its noise is made on the device in its group, from its own stream
     noises = _noise.host_noises([r.noise for r in requests], [x.shape for x in latents], [r.seed for r in requests])
@@ -541,10 +545,11 @@ def _vae_in_batches(pipeline, fn, t: torch.Tensor, group: int, decode: bool, see
 
 @torch.no_grad()
 def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
-               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8):
+               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None):
     """`InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
     See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding)."""
     from . import pipeline as P
+    from .auto_mask import auto_mask_t_start, estimate_requests, intersect, resolve_auto_mask
     from .image_processor import requantize
     insts, mm_datas = list(insts), list(mm_datas)
     N = len(insts)
@@ -557,7 +562,8 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     seeds = _noise.resolve_seeds(seeds, N)
     seeded = any(s is not None for s in seeds)
     edit_masks = per_request(edit_masks, N, "edit_masks")                 # one mask for all requests, or a list of N with None entries
-    if any(m is not None for m in edit_masks):
+    auto_masks = [resolve_auto_mask(a, f" (request {i})") for i, a in enumerate(per_request(auto_masks, N, "auto_masks"))]      # one value for all, or a list of N with None entries
+    if any(m is not None for m in edit_masks) or any(a is not None for a in auto_masks):
         from .image_processor import check_edit_feather
         P.check_edit_output_type(output_type)
         edit_feather = check_edit_feather(edit_feather)
@@ -574,6 +580,8 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             _kept_steps(50, float(refinement[i]), i)
         if float(subject_strength[i]) > 0:
             _kept_steps(50, float(subject_strength[i]), i)
+        if auto_masks[i] is not None:
+            auto_mask_t_start(int(steps[i]), auto_masks[i].strength, f" (request {i})")
     if pipeline.ip_adapter_xl is None:
         raise NotImplementedError("edit_batch drives the IP-Adapter path (construct the pipeline with ip_ckpt=)")
     if pipeline.piperf is None and any(float(r) > 0 for r in refinement):
@@ -598,7 +606,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     if todo:
         imgs = [P.base_image(pipeline, cs[i], f" (request {i})") for i in todo]                   # (every refusal before the image processor is touched)
         imgs = [pipeline.pipe_inversion.image_processor.preprocess(img) for img in imgs]
-        base_px.update({i: t for i, t in zip(todo, imgs) if edit_masks[i] is not None and t.shape[1] != 4})
+        base_px.update({i: t for i, t in zip(todo, imgs) if (edit_masks[i] is not None or auto_masks[i] is not None) and t.shape[1] != 4})
         enc = _vae_in_batches(pipeline, pipeline.pipe_inversion._vae_encode, torch.cat(imgs, dim=0), group, False,
                               seeds=[seeds[i] for i in todo], draw=_noise.DRAW_BASE_POSTERIOR)
         base.update({i: enc[j:j + 1] for j, i in enumerate(todo)})
@@ -610,8 +618,20 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     # ---- the hot segment ---------------------------------------------------------------------------------------------------------------------------------
     reqs = [EditRequest(base_latents=base[i], latent_la=latent_la[i].reshape(1, -1)[0], **P.embeds(cs[i]), inv_prompt_embeds=cs[i].get("inv_prompt_embeds"),
                         inv_pooled_prompt_embeds=cs[i].get("inv_pooled_prompt_embeds"), alpha=alpha[i], num_inference_steps=int(steps[i]), cfg=float(cfg[i]),
-                        scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i], edit_mask=edit_m[i]) for i in live]
+                        scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i], edit_mask=edit_m[i], auto_mask=auto_masks[i]) for i in live]
     pipeline.pipe_inversion.unet = pipeline.pipe.unet
+    # automatic masks, before the inversion: the estimate times the user's latent mask is the request's edit mask from here on; its pixel mask is
+    # the latent mask's cells, inside the user's pixel mask where there is one
+    auto = {}
+    if any(r.auto_mask is not None for r in reqs):
+        for j, (i, e) in enumerate(zip(live, estimate_requests(pipeline, reqs, group=group))):
+            if e is None:
+                continue
+            auto[i] = e
+            px, m = P.resolve_edit_mask(pipeline, intersect(e.mask, edit_m[i]), base[i])
+            edit[i] = (torch.minimum(px, edit[i][0]) if i in edit else px, m)
+            edit_m[i] = m
+            reqs[j].edit_mask, reqs[j].auto_mask = m, None
     images, latent_inv = denoise_batch(pipeline, reqs, group=group, shard=shard)
     row = {i: j for j, i in enumerate(live)}
     non_refined = {i: images[row[i]:row[i] + 1] for i in live}
@@ -673,6 +693,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             shown_oo[i] = shown_nr[i] if oo[i] is non_refined[i] else show(imgs[(i, True)])
     for i in live:
         msg = "SUCCESS!" if not debug else dict(output_caption=cs[i]["caption"], latent_inv=latent_inv[row[i]:row[i] + 1], latent_la=latent_la[i],
-                                                **({} if seeds[i] is None else {"seed": seeds[i]}), **({} if i not in edit else {"edit_mask_latent": edit_m[i]}))
+                                                **({} if seeds[i] is None else {"seed": seeds[i]}), **({} if i not in edit else {"edit_mask_latent": edit_m[i]}),
+                                                **({} if i not in auto else {"edit_mask": edit_m[i], "auto_mask_map": auto[i].map, "auto_mask_stats": auto[i].stats}))
         results[i] = (shown_nr[i], shown_oo[i], msg)
     return results

@@ -26,7 +26,8 @@ DRAW_BASE_POSTERIOR = 0        # VAE posterior sample of the base image
 DRAW_POLAR = 1                 # polar-mixing noise (reference pipeline.py:335)
 DRAW_HANDOFF_POSTERIOR = 2     # posterior sample of the refiner hand-off's re-encode
 DRAW_REFINER = 3               # refiner start noise
-DRAW_INPAINT = 4               # + k: inpaint noise of subject pass k
+DRAW_INPAINT = 4               # + k: inpaint noise of subject pass k (k < 65 532: below the next id)
+DRAW_AUTO_MASK = 1 << 16       # the n noises of an automatic edit mask (auto_mask.py): element k * per + e is element e of noise k
 
 
 def inpaint_draw(k: int) -> int:

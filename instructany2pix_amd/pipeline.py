@@ -294,8 +294,10 @@ class InstructAny2PixPipeline:
     @torch.no_grad()
     def denoise(self, base_latents, latent_la, *, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds,
                 inv_prompt_embeds=None, inv_pooled_prompt_embeds=None, alpha=0.7, num_inference_steps=25, cfg=10, scale=1.0, noise=None, seed=None,
-                edit_mask=None):
+                edit_mask=None, auto_mask=None):
         """inversion -> polar mixing -> IP-Adapter guided sampling; returns (sampled latents, inverted latents).
+        `auto_mask` (None: nothing changes, no launch and no draw): True, a dict or an `auto_mask.AutoMask` -- the edit mask is estimated from the request itself
+        before the inversion (`estimate_edit_mask`) and, where `edit_mask` is given too, multiplied by its latent mask; the rest is the `edit_mask` path.
         `edit_mask` (None: nothing changes): edit inside the mask only (`resolve_edit_mask`: a pixel mask at vae_scale_factor x the latent grid, or a latent
         mask tensor [1, 1, h, w]). The inversion records its trajectory, the sampling start and every sampling step are replaced outside the mask by the
         inverted latents of the same noise level, and the sampled latents equal `base_latents` (as the loop holds them in fp16) wherever the latent mask is 0.
@@ -310,7 +312,13 @@ class InstructAny2PixPipeline:
         masked = {}
         if edit_mask is not None:
             masked["edit_mask"] = resolve_edit_mask(self, edit_mask, base_latents, pixels=False)[1]
-        inverted = self.pipe_inversion.inverse(num_inference_steps=num_inference_steps, latents=base_latents, prompt_embeds=inv_prompt_embeds,
+        if auto_mask is not None:
+            from .auto_mask import intersect
+            est = self.estimate_edit_mask(base_latents, latent_la, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
+                                          inv_prompt_embeds=inv_prompt_embeds, inv_pooled_prompt_embeds=inv_pooled_prompt_embeds,
+                                          num_inference_steps=num_inference_steps, scale=scale, seed=seed, auto_mask=auto_mask)[0]
+            masked["edit_mask"] = intersect(est, masked.get("edit_mask"))
+        inverted =self.pipe_inversion.inverse(num_inference_steps=num_inference_steps, latents=base_latents, prompt_embeds=inv_prompt_embeds,
                                                pooled_prompt_embeds=inv_pooled_prompt_embeds, **({"return_trajectory": True} if masked else {}))
         latent_inv = inverted.images
         if masked:
@@ -329,6 +337,14 @@ class InstructAny2PixPipeline:
                                              pooled_prompt_embeds=pooled_prompt_embeds, negative_pooled_prompt_embeds=negative_pooled_prompt_embeds,
                                              output_type="latent", **masked)
         return images, latent_inv
+
+    def estimate_edit_mask(self, base_latents, latent_la, **kw):
+        """The automatic edit mask of one request on explicit conditioning, for a caller who wants to look at it (or change it) before `denoise(edit_mask=)`:
+        -> (latent mask fp16 [1, 1, h, w] in {0, 1}, contrast map fp32 [1, h, w], stats fp32 [2] = (mean, tau)), on the device. Keywords: the embeddings `denoise`
+        takes, `num_inference_steps`, `scale`, `seed`, `auto_mask` (`auto_mask.estimate_edit_mask`)."""
+        from .auto_mask import estimate_edit_mask
+        self.pipe_inversion.unet = self.pipe.unet
+        return estimate_edit_mask(self, base_latents, latent_la, **kw)
 
     # ---- N independent requests as one batch per evaluation, sharded over the ranks (batch.py) ---------------------------------------------------
     def denoise_batch(self, requests, group: int = 4, shard: bool = True):
@@ -562,7 +578,7 @@ class InstructAny2PixPipeline:
         return cs
 
     def edit_batch(self, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
-                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8):
+                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None):
         """`__call__` for N instructions on N images -> the list of its `(non_refined, oo, msg)` tuples, in request order. Every knob of `__call__` is a
         scalar (for all requests) or a list of N (`h`: one triple or N triples). `group` requests share one launch sequence in every loop.
 
@@ -600,16 +616,24 @@ class InstructAny2PixPipeline:
         inversion records its trajectory and every sampling step is followed by one selection launch (`ia2p_known_blend_v`), request r at its own level
         max(N_r - 1 - i, 0); the requests without a mask carry all ones there, which returns their bits. The refiner loop blends the base latents at its own
         noise level with its own noise (no new draw), the subject masks are multiplied by the edit mask, and "pil" results are composited with the base
-        image in 8 bits; "np" / "pt" are refused. A group where nobody has a mask runs exactly the unmasked launch sequence."""
+        image in 8 bits; "np" / "pt" are refused. A group where nobody has a mask runs exactly the unmasked launch sequence.
+
+        Automatic masks (`auto_masks`: ONE value for all requests -- True, a dict or an `auto_mask.AutoMask` -- or a list of N with None entries; None: nothing
+        changes, no launch and no draw). Request i's edit mask is estimated from the request itself before the inversion, the requests that ask
+        for one `group` at a time, 2 x group rows per UNet evaluation, on every rank; where `edit_masks[i]` is given too the two latent masks are multiplied. From
+        there on the request is served as under `edit_masks`. An unseeded request's n estimate noises come from the global generator in request order, after the
+        posterior samples of the base images and before the polar-mixing noise; a seeded one's are draw 65536 of its own stream. With `debug=True` the message
+        also carries `edit_mask`, `auto_mask_map` and `auto_mask_stats`."""
         from .batch import edit_batch
         return edit_batch(self, insts, mm_datas, alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
                           subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds,
-                          **({} if edit_masks is None else dict(edit_masks=edit_masks, edit_feather=edit_feather)))
+                          **({} if edit_masks is None else dict(edit_masks=edit_masks)), **({} if auto_masks is None else dict(auto_masks=auto_masks)),
+                          **({} if edit_masks is None and auto_masks is None else dict(edit_feather=edit_feather)))
 
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
                  use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None,
-                 edit_mask=None, edit_feather=8) -> Any:
+                 edit_mask=None, edit_feather=8, *, auto_mask=None) -> Any:
         """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
         `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images).
         `seed` (a 64-bit unsigned integer; None: every draw from the global CPU generator, as ever): every normal draw of the request comes from its own
@@ -625,11 +649,25 @@ class InstructAny2PixPipeline:
         subject mask is multiplied by the edit mask. "latent": both results equal `base_latents` wherever the latent mask (a cell is 1 if any of its
         pixels is in the mask) is 0. "pil": both images are composited in 8 bits with the base image (the loaded one, or the 8-bit decode of `base_latents`)
         through the mask feathered inwards over `edit_feather` pixels (0 .. 64; 8 is a design choice): every pixel outside the mask carries the base image's
-        byte. "np" / "pt" are refused with a mask. With `debug=True` the message also carries `edit_mask_latent`."""
+        byte. "np" / "pt" are refused with a mask. With `debug=True` the message also carries `edit_mask_latent`.
+        `auto_mask` (keyword only; None: nothing changes, no launch, no draw, no bit): True (the defaults), a dict or an `auto_mask.AutoMask(num_maps=8,
+        strength=0.5, ratio=3.0, dilate=1, noise=None, max_rows=None)`. The edit mask is estimated from the request itself, before the inversion:
+        the base latents noised `num_maps` times at the schedule's `strength` level, the UNet's noise prediction under the inversion's condition and under the
+        edit's (prompt embeddings + IP tokens, this call's `scale`), a cell on where their mean absolute difference exceeds `ratio / 2` times its mean over the
+        grid, grown by `dilate` cells. With `edit_mask` too the two latent masks are multiplied. From there on everything is the `edit_mask` path, its output
+        types and `edit_feather` included; the pixel mask of the composite is the latent mask's cells (inside the user's pixel mask where there is one). The
+        noises: the knob's `noise`, else draw 65536 of the request's `seed`, else ONE `torch.randn(n, C, h, w)` from the global CPU generator, drawn before the
+        polar-mixing noise. An empty mask returns the base image, a full one the unmasked edit. With `debug=True` the message also carries `edit_mask` (the
+        latent mask used), `auto_mask_map` (fp32 [1, h, w]) and `auto_mask_stats` (fp32 [2]: mean, threshold)."""
         if seed is not None:
             seed = _noise.check_seed(seed)
         check_output_type(self, output_type)
-        if edit_mask is not None:
+        if auto_mask is not None:
+            from .auto_mask import auto_mask_t_start, intersect, resolve_auto_mask
+            auto_mask = resolve_auto_mask(auto_mask)
+        if auto_mask is not None:                                                              # (False resolves to None: off)
+            auto_mask_t_start(num_inference_steps, auto_mask.strength)
+        if edit_mask is not None or auto_mask is not None:
             from .image_processor import check_edit_feather
             check_edit_output_type(output_type)
             edit_feather = check_edit_feather(edit_feather)
@@ -649,9 +687,17 @@ class InstructAny2PixPipeline:
                 return None, None, c["caption"]
         latent_la = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], prior_y0(self, c), h, norm)
         masked, kept, edit_px, edit_m = {}, {}, None, None
-        base_latents = self._base_latents(c, seed) if edit_mask is None else self._base_latents(c, seed, kept)
+        base_latents = self._base_latents(c, seed) if edit_mask is None and auto_mask is None else self._base_latents(c, seed, kept)
         if edit_mask is not None:
             edit_px, edit_m = resolve_edit_mask(self, edit_mask, base_latents, edit_mask_file_size(c))
+            masked = dict(edit_mask=edit_m)
+        auto = None
+        if auto_mask is not None:                                                              # the estimate, before the inversion; times the user's latent mask
+            auto = self.estimate_edit_mask(base_latents, latent_la.reshape(1, -1)[0], **embeds(c), inv_prompt_embeds=c.get("inv_prompt_embeds"),
+                                           inv_pooled_prompt_embeds=c.get("inv_pooled_prompt_embeds"), num_inference_steps=num_inference_steps, scale=scale,
+                                           seed=seed, auto_mask=auto_mask)
+            px, edit_m = resolve_edit_mask(self, intersect(auto[0], edit_m), base_latents)
+            edit_px = px if edit_px is None else torch.minimum(px, edit_px)
             masked = dict(edit_mask=edit_m)
         images, latent_inv = self.denoise(base_latents, latent_la.reshape(1, -1)[0], **embeds(c),
                                           inv_prompt_embeds=c.get("inv_prompt_embeds"), inv_pooled_prompt_embeds=c.get("inv_pooled_prompt_embeds"),
@@ -694,7 +740,8 @@ class InstructAny2PixPipeline:
             else:                                                                              # masks given by the conditioner
                 oo = subject_consistency(subject_data, oo, self.ip_adapter_xl_inpaint, subject_strength, **kw)
         msg = "SUCCESS!" if not debug else dict(output_caption=c["caption"], latent_inv=latent_inv, latent_la=latent_la, **({} if seed is None else {"seed": seed}),
-                                                **({} if edit_m is None else {"edit_mask_latent": edit_m}))
+                                                **({} if edit_m is None else {"edit_mask_latent": edit_m}),
+                                                **({} if auto is None else {"edit_mask": edit_m, "auto_mask_map": auto[1], "auto_mask_stats": auto[2]}))
         if output_type != "latent" and edit_px is not None:                                    # "pil": composited with the base image in 8 bits
             from .image_processor import image_to_u8, mask_feather
             base_u8 = image_to_u8(kept["image"] if "image" in kept else self.pipe._vae_decode(base_latents.to(self.pipe.unet.device, torch.float16)))

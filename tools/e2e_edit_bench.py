@@ -38,7 +38,13 @@ default feather) next to the unmasked run, interleaved repeat by repeat in the o
 adds one selection launch per sampling step, one blend launch per refiner step and the image launches per request; its stage table gains `edit mask` (load, upload,
 `ia2p_mask_to_latent`) and `mask feather`, and its `image_out` is the 8-bit composite.
 
-    python tools/e2e_edit_bench.py --edit-mask --batch 1,8"""
+    python tools/e2e_edit_bench.py --edit-mask --batch 1,8
+
+--auto-mask [N_MAPS] (with --batch; default 8 maps) runs the same requests WITH an automatic edit mask (`__call__(auto_mask=)`, `edit_batch(auto_masks=)`: the other knobs at
+their defaults) next to the run without one, interleaved repeat by repeat in the one process: serial, serial auto-masked, edit_batch, edit_batch auto-masked. The estimate --
+add_noise, two UNet evaluations of N_MAPS rows per request, the two mask launches -- is timed as a stage of its own, `mask estimate`.
+
+    python tools/e2e_edit_bench.py --auto-mask 8 --batch 1,8"""
 import argparse
 import os
 import sys
@@ -72,6 +78,7 @@ _ap.add_argument("--batch", default=None, help="comma-separated request counts: 
 _ap.add_argument("--reps", type=int, default=3)
 _ap.add_argument("--seeded", action="store_true", help="with --batch: the same requests with per-request seeds next to the unseeded run, and the three noise launches alone")
 _ap.add_argument("--edit-mask", action="store_true", help="with --batch: the same requests with a centred half-area edit mask next to the unmasked run")
+_ap.add_argument("--auto-mask", type=int, nargs="?", const=8, default=None, metavar="N_MAPS", help="with --batch: the same requests with an automatic edit mask of N_MAPS maps next to the run without")
 _ap.add_argument("--steps", type=int, default=25)
 _ap.add_argument("--refinement", type=float, default=0.5)
 ARGS = _ap.parse_args()
@@ -79,6 +86,8 @@ if ARGS.seeded and not ARGS.batch:
     _ap.error("--seeded compares against the unseeded run of --batch: give --batch too")
 if ARGS.edit_mask and not ARGS.batch:
     _ap.error("--edit-mask compares against the unmasked run of --batch: give --batch too")
+if ARGS.auto_mask is not None and not ARGS.batch:
+    _ap.error("--auto-mask compares against the run without a mask of --batch: give --batch too")
 BATCHES = [int(n) for n in ARGS.batch.split(",")] if ARGS.batch else []
 DEV = "cuda:0"
 PX = int(os.environ.get("PX", 1024))
@@ -210,12 +219,14 @@ for rnd in range(0 if BATCHES else 2):            # request 0 warms up (workspac
 # ---- --batch: N serial calls against one edit_batch of the same requests ---------------------------------------------------------------------------------
 if BATCHES:
     import statistics
+    import instructany2pix_amd.auto_mask as auto_mod
     import instructany2pix_amd.batch as batch_mod
     import instructany2pix_amd.image_processor as ip_mod
     import instructany2pix_amd.pipeline as pipeline_mod
     _wrap(pipeline_mod, "composite_edit", "image_out")              # the masked path's image out: 8-bit codec + composite
     _wrap(pipeline_mod, "resolve_edit_mask", "edit mask")
     _wrap(ip_mod, "mask_feather", "mask feather")
+    _wrap(auto_mod, "estimate_group", "mask estimate")
     for _name, _label in (("invert_batch", "inversion loop"), ("sample_batch", "guided sampling loop"), ("refine_batch", "refiner pass")):
         _wrap(batch_mod, _name, _label)
     NMAX = max(BATCHES)
@@ -258,6 +269,14 @@ if BATCHES:
 
     def batched_masked(n):
         return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), edit_masks=MASK, **knobs)
+
+    AUTO = None if ARGS.auto_mask is None else dict(num_maps=ARGS.auto_mask)
+
+    def serial_auto(n):
+        return [pipe(inst, [], auto_mask=AUTO, **knobs) for inst in insts[:n]]
+
+    def batched_auto(n):
+        return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), auto_masks=AUTO, **knobs)
 
     def launches_alone():
         """the three seeded-noise launches on their own: us per launch, median of 5 trains of 200 launches between two device events"""
@@ -313,6 +332,10 @@ if BATCHES:
             run(serial_masked, n), run(batched_masked, n)
             runs.update({"serial masked": [], "edit_batch masked": []})
             sides += [("serial masked", serial_masked), ("edit_batch masked", batched_masked)]
+        if AUTO is not None:
+            run(serial_auto, n), run(batched_auto, n)
+            runs.update({"serial auto-masked": [], "edit_batch auto-masked": []})
+            sides += [("serial auto-masked", serial_auto), ("edit_batch auto-masked", batched_auto)]
         for _ in range(ARGS.reps):
             for side, fn in sides:
                 runs[side].append(run(fn, n))
@@ -333,5 +356,8 @@ if BATCHES:
         if ARGS.edit_mask:
             print(f"  per image, masked / unmasked: serial {per_image['serial masked'] / per_image['serial']:.4f}, "
                   f"edit_batch {per_image['edit_batch masked'] / per_image['edit_batch']:.4f}", flush=True)
+        if AUTO is not None:
+            print(f"  per image, auto-masked / without: serial {per_image['serial auto-masked'] / per_image['serial']:.4f}, "
+                  f"edit_batch {per_image['edit_batch auto-masked'] / per_image['edit_batch']:.4f}", flush=True)
     if ARGS.seeded:
         launches_alone()
