@@ -79,6 +79,10 @@ ia2p_status ia2p_bind_arena(ia2p_ctx* ctx, void* dev_arena, size_t bytes);   /* 
  * or IP-Adapter key ("ip_adapter.<idx>.to_k_ip.weight", idx = position in unet.attn_processors; ip_adapter.py:168-169).
  * `dev_src` is fp16 in the checkpoint's own layout; it is re-laid-out into the arena on `stream`. */
 ia2p_status ia2p_load_tensor(ia2p_ctx* ctx, const char* key, const void* dev_src, const int64_t* shape, int ndim, void* stream);
+/* The inverse of ia2p_load_tensor: the parameter `key` back in the checkpoint's own layout, fp16, into `dev_dst` on `stream` (the 3x3 convolutions from [Co][tap][Ci]
+ * to [Co][Ci][3][3], the GEGLU pairing undone, conv_in without its padding: the re-layouts are permutations, so load then read returns the loaded bits). Same key,
+ * shape and state checks as ia2p_load_tensor; a key that was never loaded (an IP-Adapter tensor of a UNet without one) is refused with IA2P_ERR_STATE. */
+ia2p_status ia2p_read_tensor(ia2p_ctx* ctx, const char* key, void* dev_dst, const int64_t* shape, int ndim, void* stream);
 ia2p_status ia2p_finalize_weights(ia2p_ctx* ctx);      /* verifies every UNet parameter was loaded; derives the LayerNorm-folded copies */
 /* A tensor (re)loaded after finalize marks the derived data stale; the next forward re-derives it on its stream before running.
  * The arena is [head | tail]: head = the parameters as loaded (ia2p_arena_raw_bytes; what a data-parallel rank must RECEIVE), tail = data
@@ -760,6 +764,22 @@ ia2p_status ia2p_hyper_dot(void* stream, const void* hyper, int64_t hyper_stride
 ia2p_status ia2p_sam_act(void* stream, void* x, int64_t n, int kind);
 ia2p_status ia2p_sam_add_rows(void* stream, const void* a, const void* b, void* out, int64_t n, int64_t period);
 ia2p_status ia2p_sam_take_col(void* stream, const void* src, int64_t ld, float* dst, int n);
+
+/* ---- LoRA adapters: a weight with its low-rank updates merged in, one launch per weight ------------------------------------------------------------------------
+ * base, out: fp16 [N][K] row-major in the checkpoint's layout (a [Co][Ci][kh][kw] convolution weight is K = Ci kh kw); out == base (in place) is allowed, any other
+ * overlap of out with base, up or down is refused. up[a]: fp16 [N][rank[a]], down[a]: fp16 [rank[a]][K], device memory; up, down, rank and coef are HOST arrays of
+ * n entries, 1 <= n <= IA2P_LORA_MAX_ADAPTERS, 1 <= rank[a] <= IA2P_LORA_MAX_RANK. No divisibility rule on N, K or the ranks (guarded edges); rows move in 16-byte
+ * accesses where K % 8 == 0 (rank[a] % 8 == 0 for up) and the pointer is 16-byte aligned.
+ *   out[i][k] = fp16_rn( s_n ),  s_0 = float(base[i][k]),  s_{a+1} = fma(coef[a], acc_a[i][k], s_a)   (fp32, adapters in list order, one rounding each)
+ *   acc_a[i][k] = the fp32 accumulation of the products up_a[i][j] down_a[j][k] (each exact in fp32) on v_mfma_f32_16x16x32_f16, the rank zero-padded to a multiple of
+ *   32, 32-rank steps in ascending order into one accumulator; the order inside a step is the instruction's.
+ * ONE rounding to fp16, at the store. coef[a] = weight_a alpha_a / rank_a is the caller's, computed in fp32. An element's bits depend on its row of up, its column
+ * of down, its base value and coef alone -- not on N, K, the tile it falls in or the launch; no atomics. Refusals (null pointer, n or a rank out of range, a
+ * non-finite coefficient, N or K not positive, an overlap) are made on the host before anything is launched: IA2P_ERR_INVALID / IA2P_ERR_SHAPE, text through
+ * ia2p_last_error(NULL). */
+#define IA2P_LORA_MAX_ADAPTERS 8
+#define IA2P_LORA_MAX_RANK 256
+ia2p_status ia2p_lora_merge(void* stream, const void* base, void* out, int N, int64_t K, int n, const void* const* up, const void* const* down, const int* rank, const float* coef);
 
 #ifdef __cplusplus
 }

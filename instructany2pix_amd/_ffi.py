@@ -81,6 +81,7 @@ SIGNATURES = {
     "ia2p_arena_bytes": (_SZ, [_P]),
     "ia2p_bind_arena": (_I, [_P, _P, _SZ]),
     "ia2p_load_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(_I64), _I, _P]),
+    "ia2p_read_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(_I64), _I, _P]),
     "ia2p_finalize_weights": (_I, [_P]),
     "ia2p_adopt_arena": (_I, [_P, _I]),
     "ia2p_adopt_arena_on": (_I, [_P, _I, _P]),
@@ -239,6 +240,7 @@ SIGNATURES = {
     "ia2p_sam_act": (_I, [_P, _P, _I64, _I]),
     "ia2p_sam_add_rows": (_I, [_P, _P, _P, _P, _I64, _I64]),
     "ia2p_sam_take_col": (_I, [_P, _P, _I64, _P, _I]),
+    "ia2p_lora_merge": (_I, [_P, _P, _P, _I, _I64, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I), C.POINTER(_F)]),
     "ia2p_vae_create": (_I, [C.POINTER(VAEConfigC), C.POINTER(_P)]),
     "ia2p_vae_destroy": (None, [_P]),
     "ia2p_vae_last_error": (C.c_char_p, [_P]),

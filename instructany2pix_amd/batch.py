@@ -545,9 +545,16 @@ def _vae_in_batches(pipeline, fn, t: torch.Tensor, group: int, decode: bool, see
 
 @torch.no_grad()
 def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
-               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None):
+               scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None,
+               lora_scale=None):
     """`InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
-    See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding)."""
+    See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding). `lora_scale`: one number for the whole call (a batch
+    shares its weights: no per-request adapters); None launches nothing."""
+    if lora_scale is not None:
+        with pipeline.lora_scaled(lora_scale):
+            return edit_batch(pipeline, insts, mm_datas, alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
+                              subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds,
+                              edit_masks=edit_masks, edit_feather=edit_feather, auto_masks=auto_masks)
     from . import pipeline as P
     from .auto_mask import auto_mask_t_start, estimate_requests, intersect, resolve_auto_mask
     from .image_processor import requantize

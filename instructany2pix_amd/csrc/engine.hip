@@ -867,6 +867,9 @@ ia2p_status ia2p_bind_arena(ia2p_ctx* c, void* dev, size_t bytes) { return rc_bi
 ia2p_status ia2p_load_tensor(ia2p_ctx* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) {
   return rc_load_tensor(c, key, src, shape, ndim, stream);
 }
+ia2p_status ia2p_read_tensor(ia2p_ctx* c, const char* key, void* dst, const int64_t* shape, int ndim, void* stream) {
+  return rc_read_tensor(c, key, dst, shape, ndim, stream);
+}
 // LayerNorm folding pass over every transformer block (idempotent: reads the raw tensors, writes the folded copies)
 static ia2p_status fold_all(ia2p_ctx* c, hipStream_t stream, bool sync) {
   std::vector<const Transformer*> ts;

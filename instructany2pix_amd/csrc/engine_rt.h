@@ -86,6 +86,10 @@ hipError_t ia2p_launch_touch(const void* p, size_t bytes, unsigned* sink, hipStr
 hipError_t ia2p_launch_pack_conv(const half_t* src, half_t* dst, int Co, int Ci, hipStream_t s);      // [Co][Ci][3][3] -> [Co][tap][Ci]
 hipError_t ia2p_launch_pack_conv_in(const half_t* src, half_t* dst, int Co, int KT, hipStream_t s);
 hipError_t ia2p_launch_pack_geglu(const half_t* src, half_t* dst, int rows, int rowlen, hipStream_t s);
+// lora.hip: the inverses of the three re-layouts above (rc_read_tensor)
+hipError_t ia2p_launch_unpack_conv(const half_t* src, half_t* dst, int Co, int Ci, hipStream_t s);         // [Co][tap][Ci] -> [Co][Ci][3][3]
+hipError_t ia2p_launch_unpack_conv_in(const half_t* src, half_t* dst, int Co, int KT, hipStream_t s);
+hipError_t ia2p_launch_unpack_geglu(const half_t* src, half_t* dst, int rows, int rowlen, hipStream_t s);
 hipError_t ia2p_launch_softmax_rows(half_t* x, long ld, int rows, int n, float scale, hipStream_t s);
 hipError_t ia2p_launch_conv1x1_nchw(const half_t* x, const half_t* w, const half_t* bias, half_t* y, int B, int Ci, int Co, long HW, hipStream_t s);
 
@@ -365,6 +369,7 @@ struct ArenaPlan {
 };
 ia2p_status rc_bind_arena(RunCtx* c, void* dev, size_t bytes);
 ia2p_status rc_load_tensor(RunCtx* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream);
+ia2p_status rc_read_tensor(RunCtx* c, const char* key, void* dst, const int64_t* shape, int ndim, void* stream);      // (PK_COPY, the conv / GEGLU / conv_in re-layouts undone)
 // a [rows, Kraw] tensor into arena rows of Kpad elements at `off`, the padding zero (a patch stem: its GEMM takes K in multiples of 64)
 ia2p_status rc_load_padded_rows(RunCtx* c, const char* key, size_t off, int rows, int Kraw, int Kpad, const void* src, const int64_t* shape, int ndim, void* stream);
 ia2p_status rc_finalize(RunCtx* c, const char* what);

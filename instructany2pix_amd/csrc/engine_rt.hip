@@ -338,6 +338,30 @@ ia2p_status rc_load_tensor(RunCtx* c, const char* key, const void* src, const in
   c->fold_dirty = true;     // data derived from the parameters at finalize (LayerNorm folds) is stale until the owner re-derives it
   return IA2P_OK;
 }
+// the inverse of rc_load_tensor for the kinds the UNet family registers: the parameter back in the checkpoint's layout (the re-layouts are permutations: the loaded bits)
+ia2p_status rc_read_tensor(RunCtx* c, const char* key, void* dst, const int64_t* shape, int ndim, void* stream) {
+  if (!c || !key || !dst || !shape) return fail(c, IA2P_ERR_INVALID, "read_tensor: null argument");
+  if (!c->arena) return fail(c, IA2P_ERR_STATE, "read_tensor before bind_arena");
+  auto it = c->params.find(key);
+  if (it == c->params.end()) return fail(c, IA2P_ERR_KEY, "unknown parameter key '%s'", key);
+  const Param& p = it->second;
+  size_t n = 1;
+  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+  if (n != p.elems) return fail(c, IA2P_ERR_SHAPE, "parameter '%s': expected %zu elements, got %zu", key, p.elems, n);
+  if (!p.loaded) return fail(c, IA2P_ERR_STATE, "parameter '%s' was never loaded", key);
+  hipStream_t s = (hipStream_t)stream;
+  const half_t* src = c->arena + p.off;
+  hipError_t e = hipSuccess;
+  switch (p.kind) {
+    case PK_COPY: e = hipMemcpyAsync(dst, src, n * sizeof(half_t), hipMemcpyDeviceToDevice, s); break;
+    case PK_CONV: case PK_CONV_TAP: e = ia2p_launch_unpack_conv(src, (half_t*)dst, p.d0, p.d1, s); break;
+    case PK_GEGLU_W: case PK_GEGLU_B: e = ia2p_launch_unpack_geglu(src, (half_t*)dst, p.d0, p.d1, s); break;
+    case PK_PAD_CONV_IN: e = ia2p_launch_unpack_conv_in(src, (half_t*)dst, p.d0, p.d1, s); break;
+    default: return fail(c, IA2P_ERR_INVALID, "parameter '%s': kind %d cannot be read back", key, p.kind);
+  }
+  if (e != hipSuccess) return fail_hip(c, e, (std::string("read '") + key + "'").c_str());
+  return IA2P_OK;
+}
 ia2p_status rc_load_padded_rows(RunCtx* c, const char* key, size_t off, int rows, int Kraw, int Kpad, const void* src, const int64_t* shape, int ndim, void* stream) {
   size_t n = 1;
   for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];

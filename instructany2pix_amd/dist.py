@@ -7,6 +7,7 @@ conditioning (GroupNorm / LayerNorm / attention are per-sample, CFG pairs stay o
 is the one-time broadcast of the head of the flat weight arena (UNet + IP-Adapter parameters as loaded, ~5.8 GB fp16; the LayerNorm-folded
 copies behind it are re-derived on every rank) from rank 0 over xGMI,
 plus an optional all-gather of the final latents (64 KB per rank at cfg 4).
+LoRA adapters (lora.py) are applied by every rank itself: the merge kernel is deterministic, so the replicas stay bit-identical without a broadcast.
 """
 from __future__ import annotations
 

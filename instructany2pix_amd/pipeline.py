@@ -19,6 +19,7 @@ already-computed conditioning and is what bench.py and the parity tests drive.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Any, Callable, Optional
 
@@ -289,6 +290,60 @@ class InstructAny2PixPipeline:
         # second adapter object over the same UNet (:143-146): it re-installs the same processors and weights
         self.ip_adapter_xl_inpaint = IPAdapterXL(self.pipe_inpainting, "", ip_ckpt=ip_ckpt, device=device,
                                                  clip_embeddings_dim=clip_embeddings_dim) if ip_ckpt is not None else None
+
+    # ---- LoRA adapters on the UNets (lora.py) ----------------------------------------------------------
+    def _lora_unets(self, target=None):
+        both = {"unet": self.unet, "refiner": self.piperf.unet if self.piperf is not None else None}
+        if target is None:
+            return [u for u in both.values() if u is not None]
+        if target not in both:
+            raise ValueError("target must be 'unet' or 'refiner'")
+        if both[target] is None:
+            raise ValueError("this pipeline has no refiner UNet")
+        return [both[target]]
+
+    def load_lora_weights(self, path_or_dict, adapter_name: str = "default", target: str = "unet", text_encoder_keys: str = "error"):
+        """Load a LoRA adapter (`.safetensors` path or state dict; spellings: `lora.parse_lora_state_dict`) into the base UNet (`target="unet"`) or the
+        refiner's and activate it at weight 1 beside the adapters already active there, as diffusers' `load_lora_weights` does. Text-encoder keys are
+        refused (`"error"`) or dropped (`"skip"`): adapters are applied to the UNets only. In a multi-rank run every rank loads the adapter itself."""
+        (u,) = self._lora_unets(target)
+        u.load_lora_adapter(path_or_dict, adapter_name, text_encoder_keys=text_encoder_keys)
+        act = u.lora.active
+        u.set_adapters(list(act) + [adapter_name], list(act.values()) + [1.0])
+
+    def set_adapters(self, names, weights=1.0, target: str = "unet"):
+        self._lora_unets(target)[0].set_adapters(names, weights)
+
+    def disable_lora(self):
+        for u in self._lora_unets():
+            u.disable_lora()
+
+    def enable_lora(self):
+        for u in self._lora_unets():
+            u.enable_lora()
+
+    def delete_adapters(self, names, target: str = "unet"):
+        self._lora_unets(target)[0].delete_adapters(names)
+
+    def unload_lora_weights(self):
+        for u in self._lora_unets():
+            u.unload_lora()
+
+    def get_active_adapters(self, target: str = "unet"):
+        return [n for n, _ in self._lora_unets(target)[0].active_adapters()]
+
+    @contextlib.contextmanager
+    def lora_scaled(self, lora_scale):
+        """Inside the block the active adapter weights of both UNets are multiplied by `lora_scale`; the state before comes back afterwards, also when the
+        block raises. None: no launch, no bit."""
+        if lora_scale is None:
+            yield
+            return
+        with contextlib.ExitStack() as st:
+            for u in self._lora_unets():
+                if u._lora is not None:
+                    st.enter_context(u._lora.scaled(lora_scale))
+            yield
 
     # ---- the hot segment on explicit conditioning ------------------------------------------------------------------
     @torch.no_grad()
@@ -578,7 +633,8 @@ class InstructAny2PixPipeline:
         return cs
 
     def edit_batch(self, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
-                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None):
+                   scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None,
+                   lora_scale=None):
         """`__call__` for N instructions on N images -> the list of its `(non_refined, oo, msg)` tuples, in request order. Every knob of `__call__` is a
         scalar (for all requests) or a list of N (`h`: one triple or N triples). `group` requests share one launch sequence in every loop.
 
@@ -623,9 +679,13 @@ class InstructAny2PixPipeline:
         for one `group` at a time, 2 x group rows per UNet evaluation, on every rank; where `edit_masks[i]` is given too the two latent masks are multiplied. From
         there on the request is served as under `edit_masks`. An unseeded request's n estimate noises come from the global generator in request order, after the
         posterior samples of the base images and before the polar-mixing noise; a seeded one's are draw 65536 of its own stream. With `debug=True` the message
-        also carries `edit_mask`, `auto_mask_map` and `auto_mask_stats`."""
+        also carries `edit_mask`, `auto_mask_map` and `auto_mask_stats`.
+
+        LoRA (`lora_scale`: ONE number for the call; None: no launch, no bit): the active adapter weights of both UNets are multiplied by it for this call and
+        the state before is put back afterwards, also when the call raises. A batch shares its weights: per-request adapters inside one `edit_batch` are not
+        offered (requests that want different adapters go into different calls)."""
         from .batch import edit_batch
-        return edit_batch(self, insts, mm_datas, alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
+        return edit_batch(self, insts, mm_datas, **({} if lora_scale is None else dict(lora_scale=lora_scale)), alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
                           subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds,
                           **({} if edit_masks is None else dict(edit_masks=edit_masks)), **({} if auto_masks is None else dict(auto_masks=auto_masks)),
                           **({} if edit_masks is None and auto_masks is None else dict(edit_feather=edit_feather)))
@@ -633,7 +693,7 @@ class InstructAny2PixPipeline:
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
                  use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None,
-                 edit_mask=None, edit_feather=8, *, auto_mask=None) -> Any:
+                 edit_mask=None, edit_feather=8, *, auto_mask=None, lora_scale=None) -> Any:
         """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
         `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images).
         `seed` (a 64-bit unsigned integer; None: every draw from the global CPU generator, as ever): every normal draw of the request comes from its own
@@ -658,7 +718,14 @@ class InstructAny2PixPipeline:
         types and `edit_feather` included; the pixel mask of the composite is the latent mask's cells (inside the user's pixel mask where there is one). The
         noises: the knob's `noise`, else draw 65536 of the request's `seed`, else ONE `torch.randn(n, C, h, w)` from the global CPU generator, drawn before the
         polar-mixing noise. An empty mask returns the base image, a full one the unmasked edit. With `debug=True` the message also carries `edit_mask` (the
-        latent mask used), `auto_mask_map` (fp32 [1, h, w]) and `auto_mask_stats` (fp32 [2]: mean, threshold)."""
+        latent mask used), `auto_mask_map` (fp32 [1, h, w]) and `auto_mask_stats` (fp32 [2]: mean, threshold).
+        `lora_scale` (keyword only; None: nothing changes, no launch, no bit): ONE number that multiplies the active LoRA adapter weights of both UNets for this
+        call (`set_adapters` / `load_lora_weights`); the state before is put back afterwards, also when the call raises."""
+        if lora_scale is not None:
+            with self.lora_scaled(lora_scale):
+                return self(inst, mm_data, alpha=alpha, h=h, norm=norm, refinement=refinement, llm_only=llm_only, num_inference_steps=num_inference_steps,
+                            use_cache=use_cache, debug=debug, diffusion_mode=diffusion_mode, subject_strength=subject_strength, cfg=cfg, scale=scale,
+                            output_type=output_type, seed=seed, edit_mask=edit_mask, edit_feather=edit_feather, auto_mask=auto_mask)
         if seed is not None:
             seed = _noise.check_seed(seed)
         check_output_type(self, output_type)

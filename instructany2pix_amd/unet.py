@@ -27,6 +27,7 @@ from .weights import attn_processor_names
 
 class HipUNet2DConditionModel(_ffi.Executor):
     dtype = torch.float16
+    _lora = None                        # lora.LoraManager, created when the first adapter is loaded (class default: a stand-in that skipped the constructor has none)
 
     def __init__(self, config: UNetConfig, device: Union[str, torch.device] = "cuda:0"):
         config.validate()
@@ -61,6 +62,14 @@ class HipUNet2DConditionModel(_ffi.Executor):
         self._weights_gen += 1
         self.load_tensor(key, v)
 
+    def read_tensor(self, key: str, shape) -> torch.Tensor:
+        """The parameter `key` as it was loaded: fp16, the checkpoint's layout and bits (`ia2p_read_tensor`, the inverse of `load_tensor`)."""
+        shape = tuple(int(d) for d in shape)
+        t = torch.empty(shape, dtype=torch.float16, device=self.device)
+        with self._on_device():
+            self.check(self._lib.ia2p_read_tensor(self._ctx, key.encode(), _ffi.ptr(t), (C.c_int64 * len(shape))(*shape), len(shape), _ffi.current_stream()))
+        return t
+
     @property
     def arena_raw(self) -> torch.Tensor:
         """Head of the arena: the parameters as loaded (5.8 GB for SDXL-base + IP-Adapter). The tail behind it holds data derived at
@@ -72,6 +81,46 @@ class HipUNet2DConditionModel(_ffi.Executor):
         tail (LayerNorm folds) locally with the same kernel rank 0 used, so ranks hold bit-identical arenas."""
         _ffi.check(self._lib.ia2p_adopt_arena_on(self._ctx, int(with_ip_adapter), _ffi.current_stream()), self._ctx)   # ordered behind the broadcast
         self._weights_gen += 1
+
+    # ---- LoRA adapters (lora.py; DESIGN.md §18) --------------------------------------------------------------------------
+    @property
+    def lora(self):
+        """The adapter state of this UNet (`lora.LoraManager`), created at first use."""
+        if self._lora is None:
+            from .lora import LoraManager
+            self._lora = LoraManager(self)
+        return self._lora
+
+    def load_lora_adapter(self, path_or_dict, adapter_name: str = "default", **parse_kw):
+        """Read an adapter (`.safetensors` path or state dict, `lora.parse_lora_state_dict`) onto the device under `adapter_name`. It is not active
+        until `set_adapters` names it."""
+        self.lora.load(path_or_dict, adapter_name, **parse_kw)
+
+    def set_adapters(self, names, weights=1.0):
+        """The active adapters and their weights (one number for all, or one per name): every touched weight whose contribution changes is merged again
+        from its pristine copy (`ia2p_lora_merge`) and reloaded; the same state twice launches nothing."""
+        self.lora.set_adapters(names, weights)
+
+    def disable_lora(self):
+        """The weights as loaded, bit for bit; the adapters and the active set are kept for `enable_lora`."""
+        if self._lora is not None:
+            self._lora.disable()
+
+    def enable_lora(self):
+        if self._lora is not None:
+            self._lora.enable()
+
+    def delete_adapters(self, names):
+        self.lora.delete(names)
+
+    def unload_lora(self):
+        """The weights as loaded, and every adapter and pristine copy released."""
+        if self._lora is not None:
+            self._lora.unload()
+
+    def active_adapters(self):
+        """[(adapter name, weight)] merged into the weights now (empty while disabled)."""
+        return self._lora.active_adapters() if self._lora is not None else []
 
     # ---- operator-plugin API (reference ip_adapter.py:120-154) ----------------------------------------------------
     @property
