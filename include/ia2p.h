@@ -211,7 +211,7 @@ ia2p_status ia2p_image_composite_u8(void* stream, const void* edited, const void
  * A value depends on (seed, draw, e) ONLY: not on the batch, the row's place in a launch, the output pointer's alignment, the grid or the sub-range asked for.
  * Draw ids of an edit request (instructany2pix_amd/noise.py): 0 base-image VAE posterior, 1 polar-mixing noise, 2 posterior of the refiner hand-off
  * re-encode, 3 refiner start noise, 4 + k inpaint noise of subject pass k (k < 65532: the ids stay below the next one), 65536 = 1 << 16 the n noises of an
- * automatic edit mask (below; element k * per + e is element e of noise k).
+ * automatic edit mask (below; element k * per + e is element e of noise k), 65537 = (1 << 16) + 1 the step noise of the consistency sampler (lcm_step_v below).
  * seeds, draws (and alphas below): HOST arrays [B]. They travel by value in the kernel arguments, 8 rows per launch; a larger B goes in chunks of 8 rows, one launch
  * each. No call copies anything to the device, allocates or waits. Every refusal is decided on the host before any launch: a null (or misaligned) pointer is
  * IA2P_ERR_INVALID; B < 1, per < 1, a `first` that is negative or no multiple of 4, first + per > 2^34 are IA2P_ERR_SHAPE.
@@ -229,6 +229,30 @@ ia2p_status ia2p_posterior_sample_seeded(void* stream, const void* moments, void
  * The three sums of squares have ONE fixed association that depends on `per` alone, so a row's bits do not depend on B or on its place in the batch.
  * nl = 0 gives the reference's non-finite result; it is not an error. The arithmetic is fp32: it is NOT the bit pattern of the reference's CPU fp16 tensor ops. */
 ia2p_status ia2p_polar_mix_v(void* stream, const void* x, const void* y, const float* alphas, void* out, int B, int64_t per);
+
+/* ---- Consistency sampler: the step of a latent consistency model (Luo et al. 2023; diffusers LCMScheduler.step), with its noise drawn in the kernel -------
+ * The reference only points at it (pipeline.py:102, a commented-out `build_sdxl_ip(lcm_lora=True)`). One step of the sampler is, per element,
+ *   x0 = c_skip x + c_out (x - sqrt(1 - abar_t) eps) / sqrt(abar_t),   x_next = sqrt(abar_next) x0 + sqrt(1 - abar_next) z,   z fresh, none after the last step,
+ * which the host collapses to three numbers per request and step (instructany2pix_amd/scheduler.py `LCMScheduler.step_coeffs`).
+ * lcm_step_v: x, eps_u, eps_c, out, out2 fp16 [B, per] dense; coef DEVICE float [B][4] = {g, c_x, c_e, c_n} of row b; noise DEVICE fp16 [B, per] or NULL;
+ *   seeds, draws, firsts HOST arrays [B], all three or none. Per element i of row b, fp32 arithmetic in ONE order (fused multiply-adds as written, nothing
+ *   contracted or reassociated), one rounding to fp16:
+ *     e = eps_c ? fmaf(g, eps_c - eps_u, eps_u) : eps_u;    o = fmaf(c_e, e, c_x * x);    if (c_n != 0) o = fmaf(c_n, z, o);    out[i] = fp16(o)
+ *   out2, when not NULL, receives the same 16 bits. eps_c NULL: no guidance (g is not read into the result).
+ *   z: a row is SEEDED when the host arrays are given and firsts[b] >= 0; its z is element firsts[b] + i of stream (seeds[b], draws[b]) by THE NOISE RULE,
+ *   rounded to fp16 before use -- so the launch equals, bit for bit, the same launch reading noise written by randn_seeded(out_is_f16 = 1, first = firsts[b]).
+ *   Every other row reads noise[b, i]. A row with c_n == 0 forms no noise term: no Philox block is computed and `noise` is not read for it (it may hold
+ *   anything). A held row {0, 1, 0, 0} returns x's bits when the eps values are finite (a -0 of x comes back as +0 where the zero product is +0).
+ *   Draw id 65537 = (1 << 16) + 1 is the step noise of an edit request: the noise injected after step s of the request's own schedule is elements
+ *   s P .. s P + per - 1 of that draw, P = per rounded up to a multiple of 4.
+ *   Ownership is by element index, 8 elements (two Philox blocks) per thread; 16-byte accesses where a row pointer is 16-byte aligned and the group lies inside
+ *   the row, guarded scalar accesses elsewhere. A row's bits depend on neither B, its place in the launch, pointer alignment nor the grid.
+ *   seeds, draws and firsts travel by value, 8 rows per launch; a larger B goes in chunks of 8 rows. Nothing is copied to the device, allocated or waited for.
+ *   Refusals, all on the host before any launch: a null x, eps_u, coef or out, a misaligned pointer (2 bytes for the tensors, 4 for coef), noise == NULL while
+ *   some row is not seeded, only some of the three host arrays: IA2P_ERR_INVALID. B < 1, per < 1, a non-negative firsts[b] that is no multiple of 4 or with
+ *   firsts[b] + per > 2^34: IA2P_ERR_SHAPE. */
+ia2p_status ia2p_lcm_step_v(void* stream, const void* x, const void* eps_u, const void* eps_c, const float* coef, const void* noise, const uint64_t* seeds,
+                            const uint32_t* draws, const int64_t* firsts, void* out, void* out2, int B, int64_t per);
 
 /* ---- Automatic edit mask: where two noise predictions differ, the instruction wants a change (the DiffEdit construction, Couairon et al. 2022) ---------------
  * New: the reference has no mask at all. The result is a latent mask that goes into the edit-mask path above unchanged.

@@ -109,6 +109,7 @@ SIGNATURES = {
     "ia2p_mask_feather_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
     "ia2p_image_composite_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "ia2p_randn_seeded": (_I, [_P, _P, _I, _I, _I64, _I64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "ia2p_lcm_step_v": (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int64), _P, _P, _I, _I64]),
     "ia2p_posterior_sample_seeded": (_I, [_P, _P, _P, _I, _I, _I64, _F, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "ia2p_polar_mix_v": (_I, [_P, _P, _P, C.POINTER(_F), _P, _I, _I64]),
     "ia2p_eps_contrast_map": (_I, [_P, _P, _P, _P, _I, _I, _I, _I64]),

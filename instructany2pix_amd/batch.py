@@ -29,9 +29,13 @@ An edit inside a mask (`EditRequest.edit_mask`, `RefineRequest.k
 has a mask, `invert_batch` records its trajectory through `out2` of its update launch, `sample_batch` follows the start and every iteration with one selection
 launch at each request's own level (`scheduler.known_levels`, a table like the coefficient tables) and `_refine_group` blends the base latents in at the loop's
 noise level; a group without masks runs the launch sequence it always ran.
+Few-step sampling (`EditRequest.sampler` / `.sample_steps` / `.step_noise`, `edit_batch(samplers=, sample_steps=, sample_adapters=)`): a group holds one
+sampler; under "lcm" `sample_batch` hands its rows to `lcm_sample`, the one loop of the consistency sampler (`lcm_tables`, `ia2p_lcm_step_v`), which the serial
+pipeline calls too. With every such keyword at None nothing here launches or draws anything it did not before.
 """
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -40,7 +44,8 @@ import torch
 from . import dist as D
 from . import noise as _noise
 from .ddim import conditioning, get_add_time_ids
-from .scheduler import DDIMScheduler, check_kept_steps, fused_update_v, kept_steps, known_blend_v, known_levels, level_table, mask_blend_v
+from .scheduler import (DDIMScheduler, LCMScheduler, check_kept_steps, check_step_noise, fused_update_v, kept_steps, known_blend_v, known_levels, lcm_update_v,
+                        level_table, mask_blend_v, resolve_sampler)
 
 
 @dataclass
@@ -62,6 +67,9 @@ class EditRequest:
     seed: Optional[int] = None                 # the request's own Philox stream (noise.py): without `noise`, draw DRAW_POLAR of it, made and mixed on the device
     edit_mask: Optional[object] = None         # edit inside this mask only (what `pipeline.resolve_edit_mask` takes: a pixel mask, or a latent mask [1, 1, h, w])
     auto_mask: Optional[object] = None         # estimate the mask from the request itself (auto_mask.py: True, a dict or an AutoMask); times `edit_mask` where both are given
+    sampler: Optional[str] = None              # "ddim" or "lcm"; None: what `pipe.pipe.scheduler` is (DDIM, or LCM when an `LCMScheduler` is assigned there)
+    sample_steps: Optional[int] = None         # length of the LCM schedule (default 4, 1 .. 50); `num_inference_steps` keeps governing the inversion
+    step_noise: Optional[torch.Tensor] = None  # LCM: the noise injected after every step but the last, fp16 [sample_steps - 1, 4, h, w]; wins over the seed (draw DRAW_LCM)
 
 
 def _coef_table(rows: Sequence[Sequence[tuple]], device) -> torch.Tensor:
@@ -106,6 +114,93 @@ def sample_tables(scheduler_config, steps: Sequence[int], cfg: Sequence[float]):
         hold.append((float(desc[-1]), (0.0, 1.0, 0.0)))
     ts, coef = _joint_tables(records, hold)
     return [row + row for row in ts], coef
+
+
+def lcm_tables(scheduler_config, steps: Sequence[int], cfg: Sequence[float], per: Optional[int] = None, seeded: Optional[Sequence[bool]] = None):
+    """What `LCMScheduler` gives every request alone over its own `steps[r]`-step LCM schedule, laid out for the joint loop: -> (timesteps, coef, firsts),
+    each `[iterations][requests]` (the caller repeats a timestep row for the two halves of a guided evaluation). A live row is (cfg[r], *step_coeffs(s)) =
+    (g, c_x, c_e, c_n) at the request's own timestep; a held row is (0, 1, 0, 0) at its last timestep. `firsts` is what `ia2p_lcm_step_v` takes: for a
+    request with seeded[r] (and `per` elements per request) at its step s the element `noise.lcm_first(s, per)` of draw DRAW_LCM its step noise starts at;
+    -1 for a held row and for a request whose noise comes by pointer. Pure host arithmetic."""
+    records, hold = [], []
+    seeded = [False] * len(steps) if seeded is None or per is None else [bool(s) for s in seeded]
+    for n, g, own in zip(steps, cfg, seeded):
+        sch = LCMScheduler.from_config(scheduler_config)
+        sch.set_timesteps(int(n))
+        desc = [int(t) for t in sch.timesteps]
+        records.append([(float(t), (float(g),) + sch.step_coeffs(s), _noise.lcm_first(s, per) if own else -1) for s, t in enumerate(desc)])
+        hold.append((float(desc[-1]), (0.0, 1.0, 0.0, 0.0), -1))
+    return _joint_tables(records, hold)
+
+
+def lcm_blend_tables(scheduler_config, steps: Sequence[int]):
+    """The re-noising of the base latents outside an edit mask after every LCM step, `[iterations][requests]` in the (c0, c1) form of `ia2p_mask_blend_v`:
+    (sqrt(p), sqrt(1 - p)) at the timestep the step arrives at, (1, 0) after a request's last step and while it is held."""
+    records = []
+    for n in steps:
+        sch = LCMScheduler.from_config(scheduler_config)
+        sch.set_timesteps(int(n))
+        records.append([(sch.renoise_coeffs(s),) for s in range(int(n))])
+    return _joint_tables(records, [((1.0, 0.0),)] * len(records))[0]
+
+
+@torch.no_grad()
+def lcm_sample(unet, scheduler_config, x, ctx, added, steps: Sequence[int], cfg: Sequence[float], guided: bool, step_noise=None, seeds=None, ip_scales=None,
+               base=None, edit_mask=None, unet_kw=None, callback=None):
+    """The loop of the consistency sampler, serial (`ddim.StableDiffusionXLPipeline.__call__` under an `LCMScheduler`) and batched (`sample_batch`): x [n, 4, h, w]
+    on the device -> x0, request r over its own `steps[r]`-step LCM schedule (`lcm_tables`). `guided`: one evaluation at 2 n rows [uncond x n | cond x n] and
+    eps_u + g (eps_c - eps_u) per iteration; else the n conditional rows alone and eps_c = NULL (`ctx`, `added`, `ip_scales` come laid out accordingly).
+    The noise injected after step s of request r: `step_noise[r]` [steps[r] - 1, 4, h, w] read by pointer, else draw DRAW_LCM of `seeds[r]` made inside the
+    update launch -- a request with more than one step has one of the two.
+    `base` + `edit_mask` (an edit inside a mask): each step's result is replaced, where the mask is 0, by sqrt(p) base + sqrt(1 - p) z with the z of the step
+    itself (`ia2p_mask_blend_v`; (1, 0) after the last step: the base latents' bits). The step noise of an iteration is then materialised first
+    (`randn_seeded(first = s P)` for the seeded rows) and the step reads it by pointer."""
+    dev, n = x.device, x.shape[0]
+    per = x.numel() // n
+    steps = [int(s) for s in steps]
+    step_noise = [None] * n if step_noise is None else list(step_noise)
+    seeds = [None] * n if seeds is None else list(seeds)
+    for r in range(n):
+        if step_noise[r] is not None:
+            check_step_noise(step_noise[r], steps[r], x.shape, f" (request {r})")
+        elif seeds[r] is None and steps[r] > 1:
+            raise ValueError(f"request {r} takes {steps[r]} LCM steps and has neither `step_noise` nor a seed to draw it from")
+    own = [r for r in range(n) if step_noise[r] is None and seeds[r] is not None]
+    masked = edit_mask is not None
+    if masked != (base is not None):
+        raise ValueError("`base` and `edit_mask` go together: pass both or neither")
+    ts, coef, firsts = lcm_tables(scheduler_config, steps, cfg, per, [r in own and not masked for r in range(n)])
+    ts_all, coef_all = _coef_table([row + row for row in ts] if guided else ts, dev), _coef_table(coef, dev)
+    noise_all = None
+    if masked or len(own) < n:                  # rows that read their noise by pointer: [iterations, n, 4, h, w], zeros where no noise is injected
+        noise_all = torch.zeros((len(ts),) + tuple(x.shape), dtype=torch.float16, device=dev)
+        for r, z in enumerate(step_noise):
+            if z is not None and steps[r] > 1:
+                noise_all[:steps[r] - 1, r] = z.to(dev)
+    if masked:
+        blend_all = _coef_table(lcm_blend_tables(scheduler_config, steps), dev)
+    cs, draws = [0 if s is None else _noise.check_seed(s) for s in seeds], [_noise.DRAW_LCM] * n
+    model_in = torch.cat([x, x], dim=0).contiguous() if guided else x.clone()
+    eps, nxt = torch.empty_like(model_in), torch.empty_like(model_in)
+    for i in range(len(ts)):
+        unet(model_in, ts_all[i], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps, ip_scales=ip_scales, **(unet_kw or {}))
+        cur, eps_u, eps_c, out2 = model_in[:n], eps[:n], (eps[n:] if guided else None), (nxt[n:] if guided else None)
+        if not masked:
+            if noise_all is not None:
+                z = noise_all[i]
+            else:                               # every row is seeded; a held row (first -1) carries c_n = 0, so the pointer it is given is never read
+                z = cur if min(firsts[i]) < 0 else None
+            lcm_update_v(cur, eps_u, eps_c, coef_all[i], nxt[:n], out2, noise=z, seeds=cs, draws=draws, firsts=firsts[i])
+        else:
+            z = noise_all[i]
+            if own:
+                z[own] = _noise.randn_seeded([cs[r] for r in own], _noise.DRAW_LCM, x.shape[1:], torch.float16, dev, first=_noise.lcm_first(i, per))
+            lcm_update_v(cur, eps_u, eps_c, coef_all[i], nxt[:n], noise=z)
+            mask_blend_v(nxt[:n], base, z, edit_mask, blend_all[i], nxt[:n], out2)
+        model_in, nxt = nxt, model_in
+        if callback is not None:
+            callback(i, ts[i][0], model_in[:n])
+    return model_in[:n].clone()
 
 
 def _shard(N: int, shard: bool):
@@ -186,19 +281,39 @@ def invert_batch(unet, scheduler_config, latents, prompt_embeds, pooled, steps: 
 
 @torch.no_grad()
 def sample_batch(unet, scheduler_config, latents, cond_ctx, uncond_ctx, cond_pooled, uncond_pooled, steps: Sequence[int], cfg: Sequence[float],
-                 scales: Optional[Sequence[float]] = None, known: Optional[torch.Tensor] = None, edit_mask: Optional[torch.Tensor] = None):
+                 scales: Optional[Sequence[float]] = None, known: Optional[torch.Tensor] = None, edit_mask: Optional[torch.Tensor] = None, sampler: Optional[str] = None,
+                 step_noise=None, seeds=None, base: Optional[torch.Tensor] = None):
     """Guided DDIM sampling xT -> x0 of n requests at once: one UNet evaluation at B_eff = 2 n per iteration, rows [uncond x n | cond x n]
     (the reference's cat([latents] * 2), sdxl_pipeline.py:826, per request), request r with its own schedule length, guidance and IP scale
     (`sample_tables`).
     `known` + `edit_mask` (both None: nothing changes): mask-guided decoding. `known` is `invert_batch(return_trajectory=True)`'s store over the same
     `steps`, `edit_mask` the {0, 1} latent masks [n, 1, h, w] (all ones for a request without a mask: the selection returns its bits). Where a mask is 0 the
     start is the request's level N_r and the result of iteration i its level max(N_r - 1 - i, 0) (`scheduler.known_levels`, uploaded once next to the
-    coefficient tables): one `ia2p_known_blend_v` launch per iteration, written to both halves of the model input."""
+    coefficient tables): one `ia2p_known_blend_v` launch per iteration, written to both halves of the model input.
+    `sampler` (None or "ddim": nothing changes) = "lcm": the consistency sampler. `steps` are then the lengths of the requests' LCM schedules and the update is
+    `ia2p_lcm_step_v` (`lcm_sample`: `step_noise`, `seeds`, and `base` + `edit_mask` for an edit inside a mask -- `known` has no use there). When every
+    request has cfg <= 1 the group runs without guidance, on its n conditional rows; a group that mixes cfg <= 1 with cfg > 1 is refused."""
+    if sampler not in (None, "ddim", "lcm"):
+        raise ValueError(f"sampler must be 'ddim', 'lcm' or None, got {sampler!r}")
+    lcm = sampler == "lcm"
+    if not lcm and (step_noise is not None or base is not None):
+        raise ValueError("`step_noise` and `base` belong to sampler='lcm'")
+    guided = not (lcm and all(float(g) <= 1.0 for g in cfg))
+    if lcm and guided and any(float(g) <= 1.0 for g in cfg):
+        raise ValueError("LCM requests with cfg <= 1 (no guidance: conditional rows only) and with cfg > 1 cannot share a call")
     dev = unet.device
     n = latents.shape[0]
     x = latents.to(device=dev, dtype=torch.float16).contiguous()
     h, w = x.shape[-2] * 8, x.shape[-1] * 8
-    ctx, added = conditioning(dev, cond_ctx, cond_pooled, get_add_time_ids(unet, (h, w), (0, 0), (h, w), int(cond_pooled.shape[-1])), uncond_ctx, uncond_pooled)
+    ctx, added = conditioning(dev, cond_ctx, cond_pooled, get_add_time_ids(unet, (h, w), (0, 0), (h, w), int(cond_pooled.shape[-1])),
+                              *((uncond_ctx, uncond_pooled) if guided else ()))
+    if lcm:
+        if known is not None:
+            raise ValueError("the LCM timesteps are not the inversion's levels: pass `base`, not `known`")
+        sc = None if scales is None else torch.tensor(list(scales) * (2 if guided else 1), dtype=torch.float32).to(dev)
+        if base is not None:
+            base = base.to(device=dev, dtype=torch.float16).contiguous()
+        return lcm_sample(unet, scheduler_config, x, ctx, added, steps, cfg, guided, step_noise, seeds, sc, base, edit_mask)
     ts, coef = sample_tables(scheduler_config, steps, cfg)
     ts_all, coef_all = _coef_table(ts, dev), _coef_table(coef, dev)
     sc = None
@@ -227,10 +342,13 @@ def sample_batch(unet, scheduler_config, latents, cond_ctx, uncond_ctx, cond_poo
 
 
 @torch.no_grad()
-def _denoise_group(pipeline, reqs: List[EditRequest], noises, masks=None):
+def _denoise_group(pipeline, reqs: List[EditRequest], noises, masks=None, lcm=None, sample_adapters=None):
     """one group through inversion, polar mixing and guided sampling -> (sampled latents, inverted latents). `noises[i]` None: request i mixes on the device
     with draw DRAW_POLAR of its own stream. `masks[i]`: request i's latent edit mask [1, 1, h, w] or None; with at least one mask in the group the inversion
-    records its trajectory and the sampling is mask-guided, the requests without one carrying all ones. Without any, the launch sequence is the unmasked one."""
+    records its trajectory and the sampling is mask-guided, the requests without one carrying all ones. Without any, the launch sequence is the unmasked one.
+    `lcm` (None: a DDIM group): per request (length of its LCM schedule, its step noise or None for a seeded request) -- the guided sampling runs the
+    consistency sampler (`sample_batch(sampler="lcm")`); an edit mask then needs no trajectory, the base latents themselves are re-noised outside it.
+    `sample_adapters`: (names, weights) active on the UNet around the guided sampling loop only (`LoraManager.using`)."""
     from . import pipeline as P                  # (`polar_intrtpolate` looked up at call time)
     unet, cfgs, ipa = pipeline.pipe.unet, pipeline.pipe.scheduler.config, pipeline.ip_adapter_xl
     dev = unet.device
@@ -243,7 +361,11 @@ def _denoise_group(pipeline, reqs: List[EditRequest], noises, masks=None):
         hw = tuple(reqs[0].base_latents.shape[-2:])
         guided["edit_mask"] = torch.cat([torch.ones((1, 1) + hw, dtype=torch.float16, device=dev) if m is None else m.to(device=dev, dtype=torch.float16)
                                          for m in masks], dim=0).contiguous()
-        x_inv, guided["known"] = invert_batch(unet, cfgs, cat([r.base_latents for r in reqs]), inv_ctx, inv_pool, steps, return_trajectory=True)
+        if lcm is None:
+            x_inv, guided["known"] = invert_batch(unet, cfgs, cat([r.base_latents for r in reqs]), inv_ctx, inv_pool, steps, return_trajectory=True)
+        else:
+            guided["base"] = cat([r.base_latents for r in reqs])
+            x_inv = invert_batch(unet, cfgs, guided["base"], inv_ctx, inv_pool, steps)
     else:
         x_inv = invert_batch(unet, cfgs, cat([r.base_latents for r in reqs]), inv_ctx, inv_pool, steps)
     own = [i for i in range(len(reqs)) if noises[i] is None]
@@ -261,28 +383,74 @@ def _denoise_group(pipeline, reqs: List[EditRequest], noises, masks=None):
     ip, ip_un = ipa.get_image_embeds(clip_image_embeds=torch.stack([r.latent_la.reshape(-1) for r in reqs]), mode="global")
     cond_ctx = torch.cat([cat([r.prompt_embeds for r in reqs]).to(torch.float16), ip], dim=1)              # ip_adapter.py:341-342
     uncond_ctx = torch.cat([cat([r.negative_prompt_embeds for r in reqs]).to(torch.float16), ip_un], dim=1)
-    x = sample_batch(unet, cfgs, mixed, cond_ctx, uncond_ctx, cat([r.pooled_prompt_embeds for r in reqs]), cat([r.negative_pooled_prompt_embeds for r in reqs]),
-                     steps, [float(r.cfg) for r in reqs], [float(r.scale) for r in reqs], **guided)
+    if lcm is not None:
+        steps = [n for n, _ in lcm]
+        guided.update(sampler="lcm", step_noise=[z for _, z in lcm], seeds=[r.seed for r in reqs])
+    with (contextlib.nullcontext() if sample_adapters is None else unet.lora.using(*sample_adapters)):
+        x = sample_batch(unet, cfgs, mixed, cond_ctx, uncond_ctx, cat([r.pooled_prompt_embeds for r in reqs]), cat([r.negative_pooled_prompt_embeds for r in reqs]),
+                         steps, [float(r.cfg) for r in reqs], [float(r.scale) for r in reqs], **guided)
     return x, x_inv
 
 
+def resolve_sample_adapters(unet, sample_adapters):
+    """`sample_adapters=` -> None or (names, weights) for `LoraManager.using`: a name, a list of names (weight 1 each) or (names, weights). An adapter that
+    is not loaded is refused here, before any launch."""
+    if sample_adapters is None:
+        return None
+    names, weights = sample_adapters if isinstance(sample_adapters, tuple) else (sample_adapters, 1.0)
+    names = [names] if isinstance(names, str) else list(names)
+    if not names:
+        raise ValueError("sample_adapters names no adapter")
+    weights = [float(weights)] * len(names) if not isinstance(weights, (list, tuple)) else [float(w) for w in weights]
+    if len(weights) != len(names):
+        raise ValueError(f"sample_adapters: {len(names)} adapter names for {len(weights)} weights")
+    loaded = list(unet.lora.adapters) if getattr(unet, "_lora", None) is not None else []
+    for nm in names:
+        if nm not in loaded:
+            raise ValueError(f"sample_adapters: no adapter '{nm}' is loaded (loaded: {loaded})")
+    return names, weights
+
+
+def lcm_plan(scheduler, requests):
+    """per request ("ddim", None) or ("lcm", length of its LCM schedule) (`scheduler.resolve_sampler`), with the refusals that need no model: `sample_steps`
+    under DDIM, a `step_noise` of the wrong shape or under DDIM, LCM requests with cfg <= 1 next to LCM requests with cfg > 1"""
+    plan = [resolve_sampler(scheduler, r.sampler, r.sample_steps, f" (request {i})") for i, r in enumerate(requests)]
+    for i, (r, (smp, n)) in enumerate(zip(requests, plan)):
+        if r.step_noise is not None:
+            if smp != "lcm":
+                raise ValueError(f"`step_noise` is the noise of the LCM sampler; request {i} samples with DDIM")
+            check_step_noise(r.step_noise, n, r.base_latents.shape, f" (request {i})")
+    g = [float(r.cfg) <= 1.0 for r, (smp, _) in zip(requests, plan) if smp == "lcm"]
+    if any(g) and not all(g):
+        raise ValueError("LCM requests with cfg <= 1 (no guidance: conditional rows only) and with cfg > 1 cannot share a call")
+    return plan
+
+
 @torch.no_grad()
-def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: bool = True):
+def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: bool = True, sample_adapters=None):
     """N independent edit requests through the hot segment, batched and (with an initialised process group) sharded over the ranks.
     Returns (sampled latents [N,4,h,w], inverted latents [N,4,h,w]) in request order on every rank.
     `group` requests share one launch sequence (B_eff = 2 * group under guidance): 4 is the headline shape; with a queue of requests 8 is 16 %
     cheaper per image (2.05 vs 2.44 ms per image-step, profiles/r03j_two_stream_probe.txt) at twice the latency of a group.
     A request with a `seed` (and no `noise`) takes its mixing noise from its own Philox stream (noise.py, draw DRAW_POLAR) and is mixed on the device
     (`ia2p_polar_mix_v`: fp32, not the bits of the CPU fp16 mix): its inverted latents never leave the device, its result does not depend on the requests around
-    it, and no rank needs to be seeded alike for it. Requests without a seed draw and mix as ever, also next to seeded ones in one group."""
+    it, and no rank needs to be seeded alike for it. Requests without a seed draw and mix as ever, also next to seeded ones in one group.
+    A request with `sampler="lcm"` (or None under an assigned `LCMScheduler`) is sampled by the consistency sampler over `sample_steps` steps
+    after the same inversion and mixing; its step noise is `step_noise`, else draw DRAW_LCM of its seed made inside the update launch, else `sample_steps - 1`
+    host draws right after its own polar-mixing draw. A group holds one sampler: a call that mixes samplers runs the DDIM requests' groups, then the LCM
+    requests', each in request order. LCM requests with cfg <= 1 run without guidance (n rows per evaluation); all LCM requests of a call must agree on that.
+    `sample_adapters`: a name, a list or (names, weights) -- LoRA adapters active around the guided sampling loops only."""
     latents = [r.base_latents for r in requests]
     _check_latents(latents, "denoise_batch")
     if pipeline.ip_adapter_xl is None:
         raise NotImplementedError("denoise_batch drives the IP-Adapter path (construct the pipeline with ip_ckpt=)")
-    for r in requests:
+    plan = lcm_plan(getattr(getattr(pipeline, "pipe", None), "scheduler", None), requests)
+    if sample_adapters is not None:
+        sample_adapters = resolve_sample_adapters(pipeline.pipe.unet, sample_adapters)
+    for r, (smp, _) in zip(requests, plan):
         if r.num_inference_steps is None or int(r.num_inference_steps) <= 0:
             raise ValueError(f"`num_inference_steps` has to be a positive integer but is {r.num_inference_steps}")
-        if float(r.cfg) <= 1.0:
+        if smp == "ddim" and float(r.cfg) <= 1.0:
             # the reference (and pipeline.denoise) switch guidance OFF at guidance_scale <= 1 -- one conditional evaluation, eps = eps_c (sdxl_pipeline.py:842-844
             # behind do_classifier_free_guidance) -- while a batched group always evaluates [uncond | cond] and blends: not the same numbers. Say so instead.
             raise ValueError(f"denoise_batch blends eps_u + g (eps_c - eps_u) for every request; cfg={r.cfg} <= 1 means NO guidance in the reference: run that request "
@@ -293,13 +461,39 @@ def denoise_batch(pipeline, requests: List[EditRequest], group: int = 4, shard: 
         requests = apply_auto_masks(pipeline, requests, group)
     # polar-mixing noise comes from the global CPU RNG in REQUEST order (what N sequential reference calls would draw), on every rank alike; a request with a
     # seed and no noise draws nothing here: its noise is made on the device in its group, from its own stream
-    noises = _noise.host_noises([r.noise for r in requests], [x.shape for x in latents], [r.seed for r in requests])
-    if all(r.edit_mask is None for r in requests):
-        return _run_groups(requests, latents[0], pipeline.pipe.unet, group, shard, lambda g0, reqs: _denoise_group(pipeline, reqs, noises[g0:g0 + len(reqs)]), n_out=2)
-    from .pipeline import resolve_edit_mask
-    masks = [None if r.edit_mask is None else resolve_edit_mask(pipeline, r.edit_mask, r.base_latents, pixels=False)[1] for r in requests]      # every refusal before any launch
-    return _run_groups(requests, latents[0], pipeline.pipe.unet, group, shard,
-                       lambda g0, reqs: _denoise_group(pipeline, reqs, noises[g0:g0 + len(reqs)], masks[g0:g0 + len(reqs)]), n_out=2)
+    lcm_idx = [i for i, (smp, _) in enumerate(plan) if smp == "lcm"]
+    if not lcm_idx:
+        noises = _noise.host_noises([r.noise for r in requests], [x.shape for x in latents], [r.seed for r in requests])
+    else:                            # an unseeded LCM request draws its step noise right after its own polar-mixing noise, in step order: what N serial calls draw
+        noises, step_noises = [], []
+        for r, x, (smp, n) in zip(requests, latents, plan):
+            noises += _noise.host_noises([r.noise], [x.shape], [r.seed])
+            z = r.step_noise
+            if smp == "lcm" and z is None and r.seed is None and n > 1:
+                z = torch.cat([torch.randn(tuple(x.shape), dtype=torch.float16) for _ in range(n - 1)], dim=0)
+            step_noises.append(z)
+    masks = None
+    if any(r.edit_mask is not None for r in requests):
+        from .pipeline import resolve_edit_mask
+        masks = [None if r.edit_mask is None else resolve_edit_mask(pipeline, r.edit_mask, r.base_latents, pixels=False)[1] for r in requests]      # every refusal before any launch
+    extra = {} if sample_adapters is None else {"sample_adapters": sample_adapters}
+
+    def run(idx, lcm):
+        """the requests `idx` (one sampler) in groups -> (sampled, inverted) in their order"""
+        sub = lambda xs, g0, k: [xs[i] for i in idx[g0:g0 + k]]
+        kw = lambda g0, k: dict(extra, **({"lcm": [(plan[i][1], step_noises[i]) for i in idx[g0:g0 + k]]} if lcm else {}))
+        if masks is None:
+            return _run_groups([requests[i] for i in idx], latents[0], pipeline.pipe.unet, group, shard,
+                               lambda g0, reqs: _denoise_group(pipeline, reqs, sub(noises, g0, len(reqs)), **kw(g0, len(reqs))), n_out=2)
+        return _run_groups([requests[i] for i in idx], latents[0], pipeline.pipe.unet, group, shard,
+                           lambda g0, reqs: _denoise_group(pipeline, reqs, sub(noises, g0, len(reqs)), sub(masks, g0, len(reqs)), **kw(g0, len(reqs))), n_out=2)
+    if not lcm_idx or len(lcm_idx) == len(requests):
+        return run(list(range(len(requests))), bool(lcm_idx))
+    ddim_idx = [i for i in range(len(requests)) if i not in lcm_idx]
+    parts = {False: run(ddim_idx, False), True: run(lcm_idx, True)}
+    place = {i: (False, j) for j, i in enumerate(ddim_idx)}
+    place.update({i: (True, j) for j, i in enumerate(lcm_idx)})
+    return tuple(torch.cat([parts[place[i][0]][o][place[i][1]:place[i][1] + 1] for i in range(len(requests))], dim=0) for o in range(2))
 
 
 # ---- the stages after the hot segment, batched the same way: refiner pass and subject-consistency inpainting ---------------------------------------------
@@ -546,15 +740,17 @@ def _vae_in_batches(pipeline, fn, t: torch.Tensor, group: int, decode: bool, see
 @torch.no_grad()
 def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
                scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None,
-               lora_scale=None):
+               lora_scale=None, samplers=None, sample_steps=None, sample_adapters=None):
     """`InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
     See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding). `lora_scale`: one number for the whole call (a batch
-    shares its weights: no per-request adapters); None launches nothing."""
+    shares its weights: no per-request adapters); None launches nothing. `samplers`, `sample_steps` (a scalar or a list of N; None: as ever) and
+    `sample_adapters` (one value per call): the consistency sampler for the guided sampling stage (`denoise_batch`)."""
     if lora_scale is not None:
         with pipeline.lora_scaled(lora_scale):
             return edit_batch(pipeline, insts, mm_datas, alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
                               subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds,
-                              edit_masks=edit_masks, edit_feather=edit_feather, auto_masks=auto_masks)
+                              edit_masks=edit_masks, edit_feather=edit_feather, auto_masks=auto_masks, samplers=samplers, sample_steps=sample_steps,
+                              sample_adapters=sample_adapters)
     from . import pipeline as P
     from .auto_mask import auto_mask_t_start, estimate_requests, intersect, resolve_auto_mask
     from .image_processor import requantize
@@ -577,10 +773,20 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     alpha, norm, refinement = per_request(alpha, N, "alpha"), per_request(norm, N, "norm"), per_request(refinement, N, "refinement")
     steps, subject_strength = per_request(num_inference_steps, N, "num_inference_steps"), per_request(subject_strength, N, "subject_strength")
     cfg, scale, h = per_request(cfg, N, "cfg"), per_request(scale, N, "scale"), per_request(h, N, "h", _is_one_h)
+    samplers, sample_steps = per_request(samplers, N, "samplers"), per_request(sample_steps, N, "sample_steps")
+    lcm = [False] * N
+    sch = getattr(getattr(pipeline, "pipe", None), "scheduler", None)
+    if any(v is not None for v in samplers + sample_steps) or isinstance(sch, LCMScheduler):
+        lcm = [resolve_sampler(sch, samplers[i], sample_steps[i], f" (request {i})")[0] == "lcm" for i in range(N)]
+        unguided = [float(cfg[i]) <= 1.0 for i in range(N) if lcm[i]]
+        if any(unguided) and not all(unguided):
+            raise ValueError("LCM requests with cfg <= 1 (no guidance: conditional rows only) and with cfg > 1 cannot share a call")
+    if sample_adapters is not None:
+        resolve_sample_adapters(pipeline.pipe.unet, sample_adapters)
     for i in range(N):
         if steps[i] is None or int(steps[i]) <= 0:
             raise ValueError(f"`num_inference_steps` has to be a positive integer but is {steps[i]} (request {i})")
-        if float(cfg[i]) <= 1.0:
+        if float(cfg[i]) <= 1.0 and not lcm[i]:
             raise ValueError(f"edit_batch blends eps_u + g (eps_c - eps_u) for every request; cfg={cfg[i]} <= 1 (request {i}) means NO guidance in the "
                              f"reference: run that request through __call__ instead")
         if float(refinement[i]) > 0:
@@ -625,7 +831,8 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     # ---- the hot segment ---------------------------------------------------------------------------------------------------------------------------------
     reqs = [EditRequest(base_latents=base[i], latent_la=latent_la[i].reshape(1, -1)[0], **P.embeds(cs[i]), inv_prompt_embeds=cs[i].get("inv_prompt_embeds"),
                         inv_pooled_prompt_embeds=cs[i].get("inv_pooled_prompt_embeds"), alpha=alpha[i], num_inference_steps=int(steps[i]), cfg=float(cfg[i]),
-                        scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i], edit_mask=edit_m[i], auto_mask=auto_masks[i]) for i in live]
+                        scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i], edit_mask=edit_m[i], auto_mask=auto_masks[i], sampler=samplers[i],
+                        sample_steps=sample_steps[i], step_noise=cs[i].get("step_noise")) for i in live]
     pipeline.pipe_inversion.unet = pipeline.pipe.unet
     # automatic masks, before the inversion: the estimate times the user's latent mask is the request's edit mask from here on; its pixel mask is
     # the latent mask's cells, inside the user's pixel mask where there is one
@@ -639,7 +846,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             edit[i] = (torch.minimum(px, edit[i][0]) if i in edit else px, m)
             edit_m[i] = m
             reqs[j].edit_mask, reqs[j].auto_mask = m, None
-    images, latent_inv = denoise_batch(pipeline, reqs, group=group, shard=shard)
+    images, latent_inv = denoise_batch(pipeline, reqs, group=group, shard=shard, **({} if sample_adapters is None else {"sample_adapters": sample_adapters}))
     row = {i: j for j, i in enumerate(live)}
     non_refined = {i: images[row[i]:row[i] + 1] for i in live}
     oo = dict(non_refined)

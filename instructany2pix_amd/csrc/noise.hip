@@ -17,9 +17,7 @@
 // (k * 1024 + t) * 8 in index order with __fmaf_rn, the lanes fold by xor-butterfly, the 16 wave totals are added in wave order -- and then writes its slices
 // of the output. Every workgroup of a row holds the same three numbers bit for bit, so a row does not depend on B, on its place or on the slice count.
 #include "engine_rt.h"
-#include "philox.h"
-
-#include <cmath>
+#include "normal4.h"
 
 namespace {
 
@@ -32,22 +30,6 @@ constexpr long long MAX_ELEMS = 1ll << 34;      // block index j = e >> 2 is one
 
 struct NoiseRows { uint64_t seed[MAX_BY_VALUE]; uint32_t draw[MAX_BY_VALUE]; };
 struct MixRows { float alpha[MAX_BY_VALUE]; };
-
-// the four normals of block j: z[0..3] = elements 4 j .. 4 j + 3
-__device__ __forceinline__ void normal4(uint64_t seed, uint32_t draw, uint32_t j, float z[4]) {
-  uint32_t w[4];
-  philox4x32_10(j, draw, 0u, 1u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const float u1 = (float)((w[2 * p] >> 8) + 1u) * 5.9604644775390625e-8f;      // 2^-24: exact, (0, 1]
-    const float u2 = (float)(w[2 * p + 1] >> 8) * 5.9604644775390625e-8f;         // [0, 1)
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincospif(2.0f * u2, &s, &c);                                                 // the argument is exact
-    z[2 * p] = __fmul_rn(r, c);
-    z[2 * p + 1] = __fmul_rn(r, s);
-  }
-}
 
 template <bool F16>
 __global__ __launch_bounds__(NT) void randn_seeded_kernel(void* out, long per, uint32_t j0, NoiseRows rows) {

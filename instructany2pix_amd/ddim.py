@@ -18,7 +18,8 @@ from typing import Callable, Optional, Tuple
 
 import torch
 
-from .scheduler import DDIMScheduler, fused_update, known_blend_v, level_table
+from . import noise as _noise
+from .scheduler import DDIMScheduler, LCMScheduler, fused_update, known_blend_v, level_table
 
 OUTPUT_TYPES = ("latent", "pt", "np", "pil")            # (image_processor.OUTPUT_TYPES; repeated so that importing this module loads no PIL)
 
@@ -206,7 +207,7 @@ class SDXLDDIMPipeline(_PipelineBase):
 
 
 class StableDiffusionXLPipeline(_PipelineBase):
-    """DDIM sampling xT -> x0 with classifier-free guidance (2x batch UNet evaluation)."""
+    """DDIM sampling xT -> x0 with classifier-free guidance (2x batch UNet evaluation); under an `LCMScheduler` the few-step consistency sampler."""
 
     @torch.no_grad()
     def __call__(self, prompt=None, height=None, width=None, num_inference_steps: int = 50, guidance_scale: float = 5.0,
@@ -214,11 +215,25 @@ class StableDiffusionXLPipeline(_PipelineBase):
                  prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                  output_type="latent", return_dict=True, callback=None, callback_steps=1, cross_attention_kwargs=None,
                  guidance_rescale: float = 0.0, original_size=None, crops_coords_top_left=(0, 0), target_size=None, known_trajectory=None, edit_mask=None,
-                 **unused):
+                 step_noise=None, noise_seed=None, known_latents=None, **unused):
         """`known_trajectory` + `edit_mask` (new; both None: nothing changes): mask-guided decoding. `known_trajectory` is `inverse(return_trajectory=True)`'s
         store over the SAME `num_inference_steps`, fp16 [N + 1, B, 4, h, w]; `edit_mask` a {0, 1} latent mask [B or 1, 1, h, w]. Where the mask is 0 the start
         is level N and the result of sampling step i is replaced by level N - 1 - i (`ia2p_known_blend_v`: a selection, one launch per step), so the last
-        step leaves level 0 there, bit for bit."""
+        step leaves level 0 there, bit for bit.
+        With `self.scheduler` an `LCMScheduler` (as diffusers users switch samplers) the loop is the consistency sampler over `num_inference_steps` LCM steps
+        (`batch.lcm_sample`). The noise injected after step s: `step_noise` (fp16 [steps - 1, 4, h, w], or [steps - 1, B, 4, h, w] for a
+        batch), else draw DRAW_LCM of `noise_seed` (row b: seed + b) made inside the update launch, else one fp16 CPU draw of the latents' shape per step
+        from `generator` or the global RNG. An edit inside a mask takes `known_latents` (the base latents) + `edit_mask` there: the LCM timesteps are not the
+        inversion's levels. Under DDIM these three keywords are refused."""
+        lcm = isinstance(self.scheduler, LCMScheduler)
+        if not lcm and (step_noise is not None or noise_seed is not None or known_latents is not None):
+            raise ValueError("`step_noise`, `noise_seed` and `known_latents` belong to the LCM sampler: assign an LCMScheduler to `.scheduler` first")
+        if lcm and known_trajectory is not None:
+            raise ValueError("the LCM timesteps are not the inversion's levels: pass `known_latents`, not `known_trajectory`")
+        if lcm and (known_latents is None) != (edit_mask is None):
+            raise ValueError("`known_latents` and `edit_mask` go together: pass both or neither")
+        if lcm:
+            known_trajectory = known_latents           # (for the pairing check below)
         if guidance_rescale != 0.0 or eta != 0.0:
             raise NotImplementedError("guidance_rescale / eta are inactive on the reference's path (sdxl_pipeline.py:846, eta=0)")
         if (known_trajectory is None) != (edit_mask is None):
@@ -258,6 +273,11 @@ class StableDiffusionXLPipeline(_PipelineBase):
         prompt_embeds, added = conditioning(dev, prompt_embeds, pooled_prompt_embeds, add_time_ids, *neg)
 
         B = latents.shape[0]
+        if lcm:
+            latents = self._lcm_sample(latents, prompt_embeds, added, num_inference_steps, guidance_scale, do_cfg, step_noise, noise_seed, generator, known_latents,
+                                       edit_mask, cross_attention_kwargs, callback, callback_steps)
+            image = self._output(latents, output_type)
+            return StableDiffusionXLPipelineOutput(images=image) if return_dict else (image,)
         lv = None
         if known_trajectory is not None:
             known = known_trajectory.to(device=dev, dtype=torch.float16).contiguous()
@@ -293,3 +313,33 @@ class StableDiffusionXLPipeline(_PipelineBase):
         latents = model_in[:B]
         image = self._output(latents, output_type)                                              # :859-880
         return StableDiffusionXLPipelineOutput(images=image) if return_dict else (image,)
+
+    def _lcm_sample(self, latents, ctx, added, steps, guidance_scale, do_cfg, step_noise, noise_seed, generator, known_latents, edit_mask, cross_attention_kwargs,
+                    callback, callback_steps):
+        """the serial call's rows as B requests of one schedule through `batch.lcm_sample`"""
+        from .batch import lcm_sample                                                           # (batch.py imports this module)
+        dev, B, steps = self.device, latents.shape[0], int(steps)
+        rows = seeds = None
+        if step_noise is not None:
+            z = step_noise.reshape((steps - 1, -1) + tuple(latents.shape[1:])) if torch.is_tensor(step_noise) and step_noise.numel() == (steps - 1) * latents.numel() else None
+            if z is None or step_noise.dtype != torch.float16:
+                raise ValueError(f"`step_noise` must be an fp16 tensor [steps - 1 = {steps - 1}, {', '.join(map(str, latents.shape))}] (the batch axis may be left out for "
+                                 f"one row), got {tuple(step_noise.shape) if torch.is_tensor(step_noise) else type(step_noise)}")
+            rows = [z[:, b].contiguous() for b in range(B)]
+        elif noise_seed is not None:
+            seeds = _noise.batch_seeds(noise_seed, B)
+        elif steps > 1:
+            g = generator if not isinstance(generator, list) else generator[0]
+            gen_dev = g.device if g is not None else torch.device("cpu")
+            z = torch.stack([torch.randn(tuple(latents.shape), generator=g, device=gen_dev, dtype=torch.float16) for _ in range(steps - 1)])
+            rows = [z[:, b].contiguous() for b in range(B)]
+        if edit_mask is not None:
+            known_latents = known_latents.to(device=dev, dtype=torch.float16).contiguous()
+            edit_mask = edit_mask.to(device=dev, dtype=torch.float16)
+            if tuple(known_latents.shape) != tuple(latents.shape) or tuple(edit_mask.shape) not in ((1, 1) + tuple(latents.shape[-2:]), (B, 1) + tuple(latents.shape[-2:])):
+                raise ValueError(f"`known_latents` must have the latents' shape {tuple(latents.shape)} and `edit_mask` be a latent mask [{B} or 1, 1, {latents.shape[-2]}, "
+                                 f"{latents.shape[-1]}], got {tuple(known_latents.shape)} and {tuple(edit_mask.shape)}")
+            edit_mask = edit_mask.expand(B, -1, -1, -1).contiguous()
+        cb = None if callback is None else (lambda i, t, x: callback(i, int(t), x) if i % callback_steps == 0 else None)
+        return lcm_sample(self.unet, self.scheduler.config, latents, ctx, added, [steps] * B, [float(guidance_scale)] * B, do_cfg, rows, seeds, None, known_latents,
+                          edit_mask, dict(cross_attention_kwargs=cross_attention_kwargs, return_dict=False), cb)

@@ -330,6 +330,19 @@ class LoraManager:
             self.active = before
             self.sync()
 
+    @contextlib.contextmanager
+    def using(self, names: Union[str, Sequence[str]], weights: Union[float, Sequence[float]] = 1.0):
+        """The adapters `names` at `weights` active (and enabled) inside the block, the state before it afterwards (also when the block raises, and when
+        `set_adapters` itself refuses the names: nothing has changed then)."""
+        before, enabled = OrderedDict(self.active), self.enabled
+        try:
+            self.enabled = True
+            self.set_adapters(names, weights)
+            yield
+        finally:
+            self.active, self.enabled = before, enabled
+            self.sync()
+
     # -- state -> arena
     def _wanted(self) -> Dict[str, tuple]:
         want: Dict[str, list] = {}

@@ -9,6 +9,7 @@ domains never share a Philox block (the last counter word tells them apart).
   posterior_sample(moments, seeds, draw, scaling)    the VAE posterior sample `DiagonalGaussianDistribution.sample() * scaling_factor` from such a draw
   polar_mix(x, y, alphas)                            the reference's `polar_intrtpolate` (pipeline.py:295-300) per request, in fp32 on the device
   seeds_from_global(n)                               n fresh seeds from torch's global CPU generator, as the LLM's device sampler draws its own
+  lcm_first(s, per)                                  where the step noise of the consistency sampler starts in draw DRAW_LCM (drawn inside `ia2p_lcm_step_v`)
 
 `polar_mix` is the arithmetic of the seeded path only: fp32 sums and one rounding to fp16 at the end. It is NOT bit-equal to the CPU fp16 tensor arithmetic
 of `pipeline.polar_intrtpolate`, which the unseeded path keeps.
@@ -28,6 +29,12 @@ DRAW_HANDOFF_POSTERIOR = 2     # posterior sample of the refiner hand-off's re-e
 DRAW_REFINER = 3               # refiner start noise
 DRAW_INPAINT = 4               # + k: inpaint noise of subject pass k (k < 65 532: below the next id)
 DRAW_AUTO_MASK = 1 << 16       # the n noises of an automatic edit mask (auto_mask.py): element k * per + e is element e of noise k
+DRAW_LCM = (1 << 16) + 1         # step noise of the consistency sampler: the noise injected after step s is elements s * P .. s * P + per - 1, P = per rounded up to 4
+
+
+def lcm_first(s: int, per: int) -> int:
+    """the first element of draw DRAW_LCM that the noise injected after step s of a request's own schedule starts at (a multiple of 4: a whole Philox block)"""
+    return int(s) * (-(-int(per) // 4) * 4)
 
 
 def inpaint_draw(k: int) -> int:

@@ -34,7 +34,7 @@ from .inpaint import StableDiffusionXLInpaintPipeline, subject_consistency, subj
 from .image_processor import OUTPUT_TYPES, requantize
 from .ip_adapter import IPAdapterXL
 from .prior import MODALITY
-from .scheduler import DDIMScheduler
+from .scheduler import DDIMScheduler, LCMScheduler, check_step_noise, resolve_sampler
 from .unet import HipUNet2DConditionModel
 
 
@@ -349,8 +349,17 @@ class InstructAny2PixPipeline:
     @torch.no_grad()
     def denoise(self, base_latents, latent_la, *, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds,
                 inv_prompt_embeds=None, inv_pooled_prompt_embeds=None, alpha=0.7, num_inference_steps=25, cfg=10, scale=1.0, noise=None, seed=None,
-                edit_mask=None, auto_mask=None):
+                edit_mask=None, auto_mask=None, sampler=None, sample_steps=None, step_noise=None, sample_adapters=None):
         """inversion -> polar mixing -> IP-Adapter guided sampling; returns (sampled latents, inverted latents).
+        `sampler` ("ddim", "lcm"; None: what `self.pipe.scheduler` is -- DDIM, or LCM once an `LCMScheduler` is assigned there; with None nothing changes, no
+        launch and no draw) and `sample_steps` (the length of the LCM schedule, default 4, 1 .. 50; refused under DDIM): the guided sampling stage runs the
+        few-step consistency sampler for the length of the `generate` call -- the scheduler is swapped and put back, also when the call raises.
+        `num_inference_steps` keeps governing the inversion; inversion and mixing are untouched. The noise re-injected after every step but the last:
+        `step_noise` (fp16 [sample_steps - 1, 4, h, w]), else draw DRAW_LCM of `seed` made inside the update launch, else fp16 draws from the global CPU
+        generator right after the polar-mixing draw, in step order. `cfg <= 1` evaluates the conditional rows only. Under an edit mask the base latents,
+        re-noised with the step's own noise, replace every step's result outside the mask; the inversion records no trajectory.
+        `sample_adapters` (a name, a list or (names, weights); None: nothing happens): LoRA adapters active around the guided sampling loop only
+        (`LoraManager.using`), so that the inversion and the mask estimate run on the weights the caller left active.
         `auto_mask` (None: nothing changes, no launch and no draw): True, a dict or an `auto_mask.AutoMask` -- the edit mask is estimated from the request itself
         before the inversion (`estimate_edit_mask`) and, where `edit_mask` is given too, multiplied by its latent mask; the rest is the `edit_mask` path.
         `edit_mask` (None: nothing changes): edit inside the mask only (`resolve_edit_mask`: a pixel mask at vae_scale_factor x the latent grid, or a latent
@@ -360,6 +369,13 @@ class InstructAny2PixPipeline:
         (`noise.randn_seeded`, `noise.polar_mix`): the inverted latents never leave it -- no `.cpu()`, no host `randn`, no CPU mix, no upload. Row b of a
         batch of base latents draws from seed + b. A supplied `noise` wins over the seed. The device mix is fp32 arithmetic rounded once; it is not bit-equal
         to the CPU fp16 mix of the unseeded path."""
+        from .batch import resolve_sample_adapters
+        smp, n_lcm = resolve_sampler(self.pipe.scheduler, sampler, sample_steps)
+        if step_noise is not None:
+            if smp != "lcm":
+                raise ValueError("`step_noise` is the noise of the LCM sampler; this call samples with DDIM")
+            check_step_noise(step_noise, n_lcm, base_latents.shape)
+        sample_adapters = resolve_sample_adapters(self.pipe.unet, sample_adapters)
         self.pipe_inversion.unet = self.pipe.unet                                              # :306
         self.pipe_inversion.scheduler = DDIMScheduler.from_config(self.pipe.scheduler.config)  # :307
         if inv_prompt_embeds is None:        # reference inverts with prompt='' (:330); callers pass its embedding
@@ -374,10 +390,12 @@ class InstructAny2PixPipeline:
                                           num_inference_steps=num_inference_steps, scale=scale, seed=seed, auto_mask=auto_mask)[0]
             masked["edit_mask"] = intersect(est, masked.get("edit_mask"))
         inverted =self.pipe_inversion.inverse(num_inference_steps=num_inference_steps, latents=base_latents, prompt_embeds=inv_prompt_embeds,
-                                               pooled_prompt_embeds=inv_pooled_prompt_embeds, **({"return_trajectory": True} if masked else {}))
+                                               pooled_prompt_embeds=inv_pooled_prompt_embeds, **({"return_trajectory": True} if masked and smp == "ddim" else {}))
         latent_inv = inverted.images
-        if masked:
+        if masked and smp == "ddim":
             masked["known_trajectory"] = inverted.trajectory
+        elif masked:
+            masked["known_latents"] = base_latents
         if noise is None and seed is not None:
             z = _noise.randn_seeded(_noise.batch_seeds(seed, latent_inv.shape[0]), _noise.DRAW_POLAR, latent_inv.shape[1:], torch.float16, latent_inv.device)
             mixed = _noise.polar_mix(latent_inv, z, float(alpha))
@@ -386,11 +404,21 @@ class InstructAny2PixPipeline:
             if noise is None:
                 noise = torch.randn_like(latent_inv_cpu)                                       # :335 global RNG, CPU, fp16
             mixed = polar_intrtpolate(latent_inv_cpu, noise, alpha)                            # :333-337
-        images = self.ip_adapter_xl.generate(pil_image=None, num_samples=1, clip_image_embeds=latent_la, num_inference_steps=num_inference_steps,
-                                             scale=scale, mode="global", guidance_scale=cfg, latents=mixed,
-                                             prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
-                                             pooled_prompt_embeds=pooled_prompt_embeds, negative_pooled_prompt_embeds=negative_pooled_prompt_embeds,
-                                             output_type="latent", **masked)
+        saved = self.pipe.scheduler
+        if smp == "lcm":
+            masked.update({} if step_noise is None else {"step_noise": step_noise}, **({} if seed is None or step_noise is not None else {"noise_seed": seed}))
+            num_inference_steps = n_lcm
+        try:
+            if (smp == "lcm") != isinstance(saved, LCMScheduler):                              # the sampler asked for, for the length of this call
+                self.pipe.scheduler = (LCMScheduler if smp == "lcm" else DDIMScheduler).from_config(saved.config)
+            with (contextlib.nullcontext() if sample_adapters is None else self.pipe.unet.lora.using(*sample_adapters)):
+                images = self.ip_adapter_xl.generate(pil_image=None, num_samples=1, clip_image_embeds=latent_la, num_inference_steps=num_inference_steps,
+                                                     scale=scale, mode="global", guidance_scale=cfg, latents=mixed,
+                                                     prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                                                     pooled_prompt_embeds=pooled_prompt_embeds, negative_pooled_prompt_embeds=negative_pooled_prompt_embeds,
+                                                     output_type="latent", **masked)
+        finally:
+            self.pipe.scheduler = saved
         return images, latent_inv
 
     def estimate_edit_mask(self, base_latents, latent_la, **kw):
@@ -402,13 +430,13 @@ class InstructAny2PixPipeline:
         return estimate_edit_mask(self, base_latents, latent_la, **kw)
 
     # ---- N independent requests as one batch per evaluation, sharded over the ranks (batch.py) ---------------------------------------------------
-    def denoise_batch(self, requests, group: int = 4, shard: bool = True):
+    def denoise_batch(self, requests, group: int = 4, shard: bool = True, sample_adapters=None):
         """`denoise` for a list of `batch.EditRequest`s with their own `num_inference_steps` / `cfg` / `scale` / `alpha`: grouped `group` at a time
         (B_eff = 2 x group in the guided loop), contiguous shards per rank when a process group is up, results all-gathered in request order.
         -> (sampled latents [N,4,h,w], inverted latents [N,4,h,w])."""
         from .batch import denoise_batch
         self.pipe_inversion.unet = self.pipe.unet
-        return denoise_batch(self, requests, group=group, shard=shard)
+        return denoise_batch(self, requests, group=group, shard=shard, **({} if sample_adapters is None else {"sample_adapters": sample_adapters}))
 
     # ---- base image -> latents (reference :289-293, :328-330) -------------------------------------------------------------
     base_image_size = 1024          # the square `loas_base_img` loads a base_img_path to
@@ -634,7 +662,7 @@ class InstructAny2PixPipeline:
 
     def edit_batch(self, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
                    scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None,
-                   lora_scale=None):
+                   lora_scale=None, samplers=None, sample_steps=None, sample_adapters=None):
         """`__call__` for N instructions on N images -> the list of its `(non_refined, oo, msg)` tuples, in request order. Every knob of `__call__` is a
         scalar (for all requests) or a list of N (`h`: one triple or N triples). `group` requests share one launch sequence in every loop.
 
@@ -683,17 +711,26 @@ class InstructAny2PixPipeline:
 
         LoRA (`lora_scale`: ONE number for the call; None: no launch, no bit): the active adapter weights of both UNets are multiplied by it for this call and
         the state before is put back afterwards, also when the call raises. A batch shares its weights: per-request adapters inside one `edit_batch` are not
-        offered (requests that want different adapters go into different calls)."""
+        offered (requests that want different adapters go into different calls).
+
+        Few-step sampling (`samplers`, `sample_steps`: a scalar or a list of N; None: nothing changes, no launch, no draw, no bit). Request i with
+        sampler "lcm" (or None once an `LCMScheduler` is assigned to `pipe.scheduler`) is sampled by the consistency sampler over `sample_steps` steps (default 4)
+        after the same inversion and mixing. A group holds one sampler; a call that mixes them runs the DDIM requests' groups, then the LCM requests'. The step
+        noise: the conditioner's `step_noise`, else draw 65537 of the request's seed inside the update launch, else host draws right after the request's own
+        polar-mixing draw. LCM requests with cfg <= 1 run without guidance (all LCM requests of a call must agree on that). `sample_adapters` (ONE value per
+        call: a name, a list or (names, weights)): LoRA adapters active around the guided sampling loops only."""
         from .batch import edit_batch
         return edit_batch(self, insts, mm_datas, **({} if lora_scale is None else dict(lora_scale=lora_scale)), alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
                           subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds,
                           **({} if edit_masks is None else dict(edit_masks=edit_masks)), **({} if auto_masks is None else dict(auto_masks=auto_masks)),
-                          **({} if edit_masks is None and auto_masks is None else dict(edit_feather=edit_feather)))
+                          **({} if edit_masks is None and auto_masks is None else dict(edit_feather=edit_feather)),
+                          **({} if samplers is None else dict(samplers=samplers)), **({} if sample_steps is None else dict(sample_steps=sample_steps)),
+                          **({} if sample_adapters is None else dict(sample_adapters=sample_adapters)))
 
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
                  use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None,
-                 edit_mask=None, edit_feather=8, *, auto_mask=None, lora_scale=None) -> Any:
+                 edit_mask=None, edit_feather=8, *, auto_mask=None, lora_scale=None, sampler=None, sample_steps=None, sample_adapters=None) -> Any:
         """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
         `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images).
         `seed` (a 64-bit unsigned integer; None: every draw from the global CPU generator, as ever): every normal draw of the request comes from its own
@@ -720,14 +757,24 @@ class InstructAny2PixPipeline:
         polar-mixing noise. An empty mask returns the base image, a full one the unmasked edit. With `debug=True` the message also carries `edit_mask` (the
         latent mask used), `auto_mask_map` (fp32 [1, h, w]) and `auto_mask_stats` (fp32 [2]: mean, threshold).
         `lora_scale` (keyword only; None: nothing changes, no launch, no bit): ONE number that multiplies the active LoRA adapter weights of both UNets for this
-        call (`set_adapters` / `load_lora_weights`); the state before is put back afterwards, also when the call raises."""
+        call (`set_adapters` / `load_lora_weights`); the state before is put back afterwards, also when the call raises.
+        `sampler`, `sample_steps`, `sample_adapters` (keyword only; None: nothing changes, no launch, no draw, no bit): the few-step consistency sampler for the
+        guided sampling stage, and LoRA adapters active around that stage only (`denoise`). The conditioner may supply `step_noise`, which wins
+        over the seed (draw 65537 of it), which wins over the global generator. The refiner and the subject passes are untouched."""
         if lora_scale is not None:
             with self.lora_scaled(lora_scale):
                 return self(inst, mm_data, alpha=alpha, h=h, norm=norm, refinement=refinement, llm_only=llm_only, num_inference_steps=num_inference_steps,
                             use_cache=use_cache, debug=debug, diffusion_mode=diffusion_mode, subject_strength=subject_strength, cfg=cfg, scale=scale,
-                            output_type=output_type, seed=seed, edit_mask=edit_mask, edit_feather=edit_feather, auto_mask=auto_mask)
+                            output_type=output_type, seed=seed, edit_mask=edit_mask, edit_feather=edit_feather, auto_mask=auto_mask, sampler=sampler,
+                            sample_steps=sample_steps, sample_adapters=sample_adapters)
         if seed is not None:
             seed = _noise.check_seed(seed)
+        few, smp = {}, "ddim"
+        if sampler is not None or sample_steps is not None or sample_adapters is not None or isinstance(getattr(getattr(self, "pipe", None), "scheduler", None), LCMScheduler):
+            from .batch import resolve_sample_adapters
+            smp, _ = resolve_sampler(self.pipe.scheduler, sampler, sample_steps)                # every refusal before the conditioner is asked
+            resolve_sample_adapters(self.pipe.unet, sample_adapters)
+            few = {k: v for k, v in dict(sampler=sampler, sample_steps=sample_steps, sample_adapters=sample_adapters).items() if v is not None}
         check_output_type(self, output_type)
         if auto_mask is not None:
             from .auto_mask import auto_mask_t_start, intersect, resolve_auto_mask
@@ -769,7 +816,8 @@ class InstructAny2PixPipeline:
         images, latent_inv = self.denoise(base_latents, latent_la.reshape(1, -1)[0], **embeds(c),
                                           inv_prompt_embeds=c.get("inv_prompt_embeds"), inv_pooled_prompt_embeds=c.get("inv_pooled_prompt_embeds"),
                                           alpha=alpha, num_inference_steps=num_inference_steps, cfg=cfg, scale=scale, seed=seed,
-                                          noise=c.get("polar_noise") if seed is not None else None, **masked)      # (unseeded: this call has always drawn its own)
+                                          noise=c.get("polar_noise") if seed is not None else None, **masked,      # (unseeded: this call has always drawn its own)
+                                          **few, **({"step_noise": c["step_noise"]} if smp == "lcm" and c.get("step_noise") is not None else {}))
         non_refined = images
         oo = images
         decoded = None          # the decode of `images`, when the refiner hand-over made it

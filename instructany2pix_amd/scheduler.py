@@ -9,9 +9,12 @@ Mirrors the surface of diffusers' `DDIMScheduler` that the reference touches:
 Configuration = SDXL-base `scheduler_config.json` fields that DDIM keeps.
 The tensor update itself runs in `ia2p_ddim_step` (one fused kernel: CFG combine + x_{t-1}); coefficient
 tables are computed here in float32/float64 exactly as diffusers does (float32 cumprod).
+Beside it: the Euler scheduler of the refiner, the DDPM scheduler of the embedding prior, and `LCMScheduler`, the few-step consistency sampler whose step
+(`ia2p_lcm_step_v`, wrapped by `lcm_update_v`) also re-injects noise -- from a tensor, or drawn inside the launch from a request's seed.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from types import SimpleNamespace
 from typing import Optional
@@ -190,6 +193,153 @@ def fused_update_v(x, eps_u, eps_c, coef, out, out2=None):
     L = _ffi.lib()
     _ffi.check(L.ia2p_ddim_step_v(_ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(eps_u), _ffi.ptr(eps_c), _ffi.ptr(coef), _ffi.ptr(out), _ffi.ptr(out2), B, per))
     return out
+
+
+def lcm_update_v(x, eps_u, eps_c, coef, out, out2=None, noise=None, seeds=None, draws=None, firsts=None):
+    """The step of the consistency sampler with per-request coefficients (ia2p_lcm_step_v): coef = float32 device tensor [B, 4] = (guidance, c_x, c_e, c_n)
+    of every batch element of x [B, ...]; out = fp16(c_x x + c_e (eps_u + g (eps_c - eps_u)) + c_n z). z of row b: element firsts[b] + i of stream
+    (seeds[b], draws[b]) made inside the kernel when `seeds`, `draws`, `firsts` (host lists of B, all three or none) are given and firsts[b] >= 0; else
+    noise[b] (fp16 device tensor of x's shape). A row with c_n = 0 reads neither."""
+    for t in (x, eps_u, out):
+        assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous(), "latents must be contiguous fp16 device tensors"
+    B = x.shape[0]
+    per = x.numel() // B
+    assert coef.dtype == torch.float32 and coef.is_cuda and coef.is_contiguous() and tuple(coef.shape) == (B, 4)
+    assert eps_u.numel() == x.numel() and out.numel() == x.numel() and (eps_c is None or eps_c.numel() == x.numel())
+    for t in (eps_c, out2, noise):
+        assert t is None or (t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.numel() == x.numel())
+    given = [a is not None for a in (seeds, draws, firsts)]
+    assert all(given) or not any(given), "seeds, draws and firsts come together or not at all"
+    cs = cd = cf = None
+    if all(given):
+        assert len(seeds) == B and len(draws) == B and len(firsts) == B
+        cs = (C.c_uint64 * B)(*[0 if s is None else int(s) for s in seeds])
+        cd = (C.c_uint32 * B)(*[int(d) for d in draws])
+        cf = (C.c_int64 * B)(*[int(f) for f in firsts])
+    _ffi.check(_ffi.lib().ia2p_lcm_step_v(_ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(eps_u), _ffi.ptr(eps_c), _ffi.ptr(coef), _ffi.ptr(noise), cs, cd, cf,
+                                          _ffi.ptr(out), _ffi.ptr(out2), B, per))
+    return out
+
+
+class LCMScheduler:
+    """The multistep consistency sampler of Latent Consistency Models (Luo et al. 2023) as diffusers 0.26.3's `LCMScheduler` runs it on the SDXL-base
+    configuration (what `build_sdxl_ip(lcm_lora=True)`, commented out at reference pipeline.py:102, would have installed): scaled-linear betas, epsilon
+    prediction, no clipping or thresholding, original_inference_steps 50, timestep_scaling 10, sigma_data 0.5. With a = abar_t, p = abar of the NEXT timestep
+    of the schedule and s = timestep_scaling * t:
+
+        c_skip = sd^2 / (s^2 + sd^2);  c_out = s / sqrt(s^2 + sd^2);  x0 = (x - sqrt(1 - a) eps) / sqrt(a);  x_next = sqrt(p) (c_out x0 + c_skip x) + sqrt(1 - p) z
+
+    with fresh z at every step but the last, where x_next = c_out x0 + c_skip x. Every move is  out = c_x x + c_e eps + c_n z  (`step_coeffs`); the tensor
+    update runs in `ia2p_lcm_step_v`. Parity with the diffusers package itself is not pinned by a test: it is restated from its rule."""
+    order = 1
+    init_noise_sigma = 1.0
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", original_inference_steps=50,
+                 prediction_type="epsilon", clip_sample=False, thresholding=False, set_alpha_to_one=True, timestep_scaling=10.0, sigma_data=0.5,
+                 rescale_betas_zero_snr=False, steps_offset=0, timestep_spacing="leading", **unused):
+        if beta_schedule != "scaled_linear" or prediction_type != "epsilon" or clip_sample or thresholding or rescale_betas_zero_snr:
+            raise NotImplementedError("only the SDXL-base LCM configuration is implemented")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                                      original_inference_steps=original_inference_steps, prediction_type=prediction_type, clip_sample=clip_sample,
+                                      thresholding=thresholding, set_alpha_to_one=set_alpha_to_one, timestep_scaling=timestep_scaling, sigma_data=sigma_data,
+                                      steps_offset=steps_offset, timestep_spacing=timestep_spacing)      # (the last three: carried for a DDIM scheduler built from this config)
+        self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.num_inference_steps: Optional[int] = None
+        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        """from an LCM config, or from the DDIM / SDXL one: the fields LCM has no use for (spacing, offset, set_alpha_to_one) are carried along, so that the
+        inversion's `DDIMScheduler.from_config(pipe.scheduler.config)` gets the schedule it always got"""
+        d = dict(vars(config)) if not isinstance(config, dict) else dict(config)
+        d.update(kw)
+        return cls(**d)
+
+    def set_timesteps(self, num_inference_steps: int, device=None, original_inference_steps: Optional[int] = None, strength: float = 1.0):
+        if strength != 1.0:
+            raise NotImplementedError("strength on the LCM schedule is not implemented")
+        orig = int(self.config.original_inference_steps if original_inference_steps is None else original_inference_steps)
+        if orig < 1 or orig > self.config.num_train_timesteps:
+            raise ValueError(f"`original_inference_steps`: {orig} must lie in 1 .. {self.config.num_train_timesteps}")
+        if num_inference_steps is None or int(num_inference_steps) < 1 or int(num_inference_steps) > orig:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} must lie in 1 .. `original_inference_steps`: {orig}")
+        self.num_inference_steps = int(num_inference_steps)
+        k = self.config.num_train_timesteps // orig
+        origin = (np.arange(1, orig + 1) * k - 1)[::-1].copy()
+        idx = np.floor(np.linspace(0, len(origin), num=self.num_inference_steps, endpoint=False)).astype(np.int64)
+        self.timesteps = torch.from_numpy(origin[idx].astype(np.int64))
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def index_for_timestep(self, timestep) -> int:
+        idx = (self.timesteps == int(timestep)).nonzero()
+        if len(idx) == 0:
+            raise ValueError(f"timestep {timestep} is not on the current schedule")
+        return int(idx[0])
+
+    def renoise_coeffs(self, index: int):
+        """(sqrt(p), sqrt(1 - p)) of the timestep step `index` arrives at; (1, 0) after the last step"""
+        if index + 1 >= len(self.timesteps):
+            return 1.0, 0.0
+        p = float(self.alphas_cumprod[int(self.timesteps[index + 1])])
+        return math.sqrt(p), math.sqrt(1.0 - p)
+
+    def step_coeffs(self, index: int):
+        """step `index` of the schedule collapsed to  out = c_x x + c_e eps + c_n z  (float64 arithmetic on the float32 table); c_n = 0 at the last step"""
+        t = int(self.timesteps[index])
+        a = float(self.alphas_cumprod[t])
+        s, sd = float(self.config.timestep_scaling) * t, float(self.config.sigma_data)
+        c_skip = sd * sd / (s * s + sd * sd)
+        c_out = s / math.sqrt(s * s + sd * sd)
+        sp, c_n = self.renoise_coeffs(index)
+        return sp * (c_out / math.sqrt(a) + c_skip), -sp * c_out * math.sqrt(1.0 - a) / math.sqrt(a), c_n
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = False, **kw):
+        """One step on tensors, the noise drawn the way the other samplers of this module draw theirs (a CPU draw from `generator` or the global RNG, fp16,
+        of the output's shape), through the pointer path of the launch."""
+        c_x, c_e, c_n = self.step_coeffs(self.index_for_timestep(timestep))
+        B = sample.shape[0]
+        noise = None
+        if c_n != 0.0:
+            noise = torch.randn(model_output.shape, generator=generator, device=generator.device if generator is not None else "cpu",
+                                dtype=model_output.dtype).to(model_output.device).contiguous()
+        coef = torch.tensor([[1.0, c_x, c_e, c_n]] * B, dtype=torch.float32).to(sample.device)
+        out = torch.empty_like(sample)
+        lcm_update_v(sample, model_output, None, coef, out, noise=noise if noise is not None else sample)      # (c_n = 0: the noise pointer is not read)
+        return (out,) if not return_dict else SimpleNamespace(prev_sample=out)
+
+
+SAMPLERS = ("ddim", "lcm")
+LCM_DEFAULT_STEPS = 4
+
+
+def resolve_sampler(scheduler, sampler, sample_steps, who: str = ""):
+    """`sampler=` / `sample_steps=` of a request -> ("ddim", None) or ("lcm", length of its LCM schedule). None is what `scheduler` (the pipeline's own) is:
+    DDIM, or LCM when the caller has assigned an `LCMScheduler` there. `sample_steps` is refused under DDIM, where `num_inference_steps` governs."""
+    if sampler is None:
+        sampler = "lcm" if isinstance(scheduler, LCMScheduler) else "ddim"
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS} or None, got {sampler!r}{who}")
+    if sampler == "ddim":
+        if sample_steps is not None:
+            raise ValueError(f"`sample_steps` is the length of the LCM schedule; under DDIM `num_inference_steps` governs the sampling too{who}")
+        return sampler, None
+    n = LCM_DEFAULT_STEPS if sample_steps is None else sample_steps
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 50:
+        raise ValueError(f"`sample_steps` must be an integer in 1 .. 50 (the LCM schedule picks from 50 origin steps), got {sample_steps!r}{who}")
+    return sampler, n
+
+
+def check_step_noise(step_noise, sample_steps: int, latent_shape, who: str = ""):
+    """a supplied `step_noise`: fp16 [sample_steps - 1, *latent_shape[1:]] (one request), the noise injected after step s at index s"""
+    want = (int(sample_steps) - 1,) + tuple(latent_shape[1:])
+    if not torch.is_tensor(step_noise) or step_noise.dtype != torch.float16 or tuple(step_noise.shape) != want:
+        got = (tuple(step_noise.shape), step_noise.dtype) if torch.is_tensor(step_noise) else type(step_noise)
+        raise ValueError(f"`step_noise` must be an fp16 tensor {list(want)} = [sample_steps - 1, C, h, w], got {got}{who}")
+    return step_noise
 
 
 class EulerDiscreteScheduler:

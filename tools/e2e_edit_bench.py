@@ -44,7 +44,15 @@ adds one selection launch per sampling step, one blend launch per refiner step a
 their defaults) next to the run without one, interleaved repeat by repeat in the one process: serial, serial auto-masked, edit_batch, edit_batch auto-masked. The estimate --
 add_noise, two UNet evaluations of N_MAPS rows per request, the two mask launches -- is timed as a stage of its own, `mask estimate`.
 
-    python tools/e2e_edit_bench.py --auto-mask 8 --batch 1,8"""
+    python tools/e2e_edit_bench.py --auto-mask 8 --batch 1,8
+
+--lcm N (with --batch) runs the same requests with the guided sampling stage under the consistency sampler over N steps (`__call__(sampler="lcm", sample_steps=N)`,
+`edit_batch(samplers="lcm", sample_steps=N)`; per-request seeds, so the step noise is drawn inside the update launch) next to the DDIM run, interleaved repeat by
+repeat in the one process: serial, serial lcm, edit_batch, edit_batch lcm. --steps keeps governing the inversion. The stage to read is `guided sampling loop`:
+N evaluations against --steps. Its table gains the two update launches ALONE (`ia2p_ddim_step_v`, `ia2p_lcm_step_v` with every row seeded, guided, B = 1 and B = 8
+on 4 x PX/8 x PX/8 latents), measured like the seeded-noise launches of --seeded. Synthetic weights: the figures are times, the images mean nothing.
+
+    python tools/e2e_edit_bench.py --lcm 4 --batch 1,4"""
 import argparse
 import os
 import sys
@@ -79,6 +87,7 @@ _ap.add_argument("--reps", type=int, default=3)
 _ap.add_argument("--seeded", action="store_true", help="with --batch: the same requests with per-request seeds next to the unseeded run, and the three noise launches alone")
 _ap.add_argument("--edit-mask", action="store_true", help="with --batch: the same requests with a centred half-area edit mask next to the unmasked run")
 _ap.add_argument("--auto-mask", type=int, nargs="?", const=8, default=None, metavar="N_MAPS", help="with --batch: the same requests with an automatic edit mask of N_MAPS maps next to the run without")
+_ap.add_argument("--lcm", type=int, default=None, metavar="N", help="with --batch: the same requests sampled by the N-step consistency sampler next to the DDIM run, and the two update launches alone")
 _ap.add_argument("--steps", type=int, default=25)
 _ap.add_argument("--refinement", type=float, default=0.5)
 ARGS = _ap.parse_args()
@@ -88,6 +97,8 @@ if ARGS.edit_mask and not ARGS.batch:
     _ap.error("--edit-mask compares against the unmasked run of --batch: give --batch too")
 if ARGS.auto_mask is not None and not ARGS.batch:
     _ap.error("--auto-mask compares against the run without a mask of --batch: give --batch too")
+if ARGS.lcm is not None and not ARGS.batch:
+    _ap.error("--lcm compares against the DDIM run of --batch: give --batch too")
 BATCHES = [int(n) for n in ARGS.batch.split(",")] if ARGS.batch else []
 DEV = "cuda:0"
 PX = int(os.environ.get("PX", 1024))
@@ -278,6 +289,42 @@ if BATCHES:
     def batched_auto(n):
         return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), auto_masks=AUTO, **knobs)
 
+    def serial_lcm(n):
+        return [pipe(inst, [], seed=SEEDS[i], sampler="lcm", sample_steps=ARGS.lcm, **knobs) for i, inst in enumerate(insts[:n])]
+
+    def batched_lcm(n):
+        return pipe.edit_batch(insts[:n], [[]] * n, group=min(n, 8), seeds=SEEDS[:n], samplers="lcm", sample_steps=ARGS.lcm, **knobs)
+
+    def updates_alone():
+        """the DDIM and the LCM update launch on their own, guided: us per launch, median of 5 trains of 200 launches between two device events"""
+        import statistics as st_
+        from instructany2pix_amd import noise, scheduler
+        h = PX // 8
+        rows = []
+        for B in (1, 8):
+            x, eu, ec = (noise.randn_seeded([k + 1] * B, 9, (4, h, h), torch.float16, DEV) for k in range(3))
+            out, out2 = torch.empty_like(x), torch.empty_like(x)
+            c3 = torch.tensor([[10.0, 1.02, -0.05]] * B).to(DEV)
+            c4 = torch.tensor([[10.0, 2.31, -2.25, 0.85]] * B).to(DEV)
+            seeds, draws, firsts = [SEEDS[0] + b for b in range(B)], [noise.DRAW_LCM] * B, [noise.lcm_first(1, 4 * h * h)] * B
+            work = {"ia2p_ddim_step_v": lambda: scheduler.fused_update_v(x, eu, ec, c3, out, out2),
+                    "ia2p_lcm_step_v": lambda: scheduler.lcm_update_v(x, eu, ec, c4, out, out2, seeds=seeds, draws=draws, firsts=firsts)}
+            for name, fn in work.items():
+                for _ in range(20):
+                    fn()
+                us = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    for _ in range(200):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us.append(e0.elapsed_time(e1) * 1e3 / 200)
+                rows.append(f"{name} B={B} {st_.median(us):.1f} (min {min(us):.1f}, max {max(us):.1f})")
+        print(f"# sampler update launches alone, guided, 4 x {h} x {h} latents, us per launch incl. the Python call: " + "; ".join(rows), flush=True)
+
     def launches_alone():
         """the three seeded-noise launches on their own: us per launch, median of 5 trains of 200 launches between two device events"""
         import statistics as st_
@@ -336,6 +383,10 @@ if BATCHES:
             run(serial_auto, n), run(batched_auto, n)
             runs.update({"serial auto-masked": [], "edit_batch auto-masked": []})
             sides += [("serial auto-masked", serial_auto), ("edit_batch auto-masked", batched_auto)]
+        if ARGS.lcm is not None:
+            run(serial_lcm, n), run(batched_lcm, n)
+            runs.update({"serial lcm": [], "edit_batch lcm": []})
+            sides += [("serial lcm", serial_lcm), ("edit_batch lcm", batched_lcm)]
         for _ in range(ARGS.reps):
             for side, fn in sides:
                 runs[side].append(run(fn, n))
@@ -359,5 +410,10 @@ if BATCHES:
         if AUTO is not None:
             print(f"  per image, auto-masked / without: serial {per_image['serial auto-masked'] / per_image['serial']:.4f}, "
                   f"edit_batch {per_image['edit_batch auto-masked'] / per_image['edit_batch']:.4f}", flush=True)
+        if ARGS.lcm is not None:
+            print(f"  per image, lcm ({ARGS.lcm} steps) / ddim ({ARGS.steps} steps): serial {per_image['serial lcm'] / per_image['serial']:.4f}, "
+                  f"edit_batch {per_image['edit_batch lcm'] / per_image['edit_batch']:.4f}", flush=True)
     if ARGS.seeded:
         launches_alone()
+    if ARGS.lcm is not None:
+        updates_alone()
