@@ -81,9 +81,11 @@ def _v(g, *shape):
 
 
 # ---- the bound -------------------------------------------------------------------------------------------------------------------------------------------------
-def _core(s, Dn, Dm, v, kind, exact=True):
-    """s, Dn, Dm [G, Tq, Tk] (scores, their plain and modelled error without u |x|), v [G, Tk, Dh]; kind full / relpos / small; exact: (*) term by term
-    -> out [G, Tq, Dh], bound, the largest share of the exponential model and of the MFMA model in it"""
+def _core(s, Dn, Dm, v, kind, exact=True, tail=None, parts=False):
+    """s, Dn, Dm [G, Tq, Tk] (scores, their plain and modelled error without u |x|), v [G, Tk, Dh]; kind full / relpos / small / unet; exact: (*) term by term
+    -> out [G, Tq, Dh], bound, the largest share of the exponential model and of the MFMA model in it.
+    kind unet (csrc/attention_core.h; unet_attn_ref.py lists its terms) is relpos' online softmax with the score arithmetic of that kernel; `tail` [G, Tq, 1]: keys
+    with a non-zero fp16 probability that the same P.V accumulator takes in after this segment's; `parts`: -> (out, plain, model, ex, S) without SECOND and the store"""
     Tk, Dh = s.shape[-1], v.shape[-1]
     m = s.max(-1, keepdim=True).values
     x = s - m
@@ -112,7 +114,7 @@ def _core(s, Dn, Dm, v, kind, exact=True):
         plain = lin(Dn + U * x.abs()) + (nl + 6) * U * (wv + oa) + 3 * U * oa
         model = torch.zeros_like(out)
     else:
-        if kind == "relpos":                            # p is rounded against the running maximum of its tile
+        if kind in ("relpos", "unet"):                  # p is rounded against the running maximum of its tile
             pad = nl * 64 - Tk
             sp = torch.nn.functional.pad(s, (0, pad), value=-math.inf) if pad else s
             rm = torch.cummax(sp.reshape(*s.shape[:-1], nl, 64).max(-1).values, -1).values
@@ -121,16 +123,22 @@ def _core(s, Dn, Dm, v, kind, exact=True):
             X = X + 4 * 2.0 ** -23 * rise.flip(-1).cumsum(-1).flip(-1).repeat_interleave(64, -1)[..., :Tk]      # the alphas a key's weight passes through
         else:
             mt = m.expand_as(s)
+        if kind == "unet":                              # fl(m_t c) is rounded per tile and alpha's exponent is not the difference of two of them (unet_attn_ref.py)
+            Dn = Dn + U * (mt.abs() + x.abs()) + 3 * U * (m - mt)
         et = torch.exp(s - mt) * 1.001
         nt = -(-Tk // 16)
         nz = torch.nn.functional.pad((et >= 2.0 ** -25).double(), (0, nt * 16 - Tk)).reshape(*s.shape[:-1], nt, 16).sum(-1)      # keys per MFMA whose fp16 p is not 0
         cnt = nz.flip(-1).cumsum(-1).flip(-1).repeat_interleave(16, -1)[..., :Tk]
+        if tail is not None:
+            cnt = cnt + tail
         model = lin(Dm) + 2 * U * ((w * cnt) @ va)
         h = torch.minimum(et, half_ulp16(et)) * torch.exp(mt - m)
         plain = lin(Dn + U * x.abs()) + (h @ va) / S + (Tk + 5) * U * oa
-        if kind == "relpos":
+        if kind in ("relpos", "unet"):
             plain = plain + nl * U * (wv + oa)
     ex = lin(X)
+    if parts:
+        return out, plain, model, ex, S
     total = with_store16(out, SECOND * (plain + model + ex))
     return out, total, float((SECOND * ex / total).max()), float((SECOND * model / total).max())
 
