@@ -9,7 +9,9 @@
  *   operator plugin attn.processor(attn, hidden_states, encoder_hidden_states)
  *                   instructany2pix/diffusion/ip_adapter/attention_processor.py:205-279 (AttnProcessor2_0),
  *                   :310-412 (IPAttnProcessor2_0); installed by ip_adapter.py:120-142, scale set by :211-214
- *                   -> ia2p_set_ip_adapter, ia2p_attention / ia2p_qproj_attention (+ ia2p_gemm for the projections)
+ *                   -> ia2p_set_ip_adapter, ia2p_attention / ia2p_qproj_attention (+ ia2p_gemm for the projections);
+ *                   with regional image prompts (diffusers' `ip_adapter_masks`, new here: one token group per subject, each under
+ *                   its own mask) -> ia2p_attention_regions + ia2p_region_levels, and ia2p_unet_forward_r on the UNet callable
  *   sampler update  _backward_ddim pnp_pipeline.py:73-85; CFG combine sdxl_pipeline.py:842-844;
  *                   DDIMScheduler.step (diffusers 0.26.3) called at sdxl_pipeline.py:851
  *                   -> ia2p_ddim_step
@@ -124,6 +126,17 @@ ia2p_status ia2p_unet_forward(ia2p_ctx* ctx, void* stream, const void* sample, f
 ia2p_status ia2p_unet_forward_v(ia2p_ctx* ctx, void* stream, const void* sample, const float* timesteps, const float* ip_scales,
                                 const void* context, const void* kv, int L, const void* text_embeds, const void* time_ids, void* out,
                                 int B, int h, int w, void* workspace, size_t workspace_bytes);
+/* ia2p_unet_forward_v with regional image prompts (what diffusers offers as cross_attention_kwargs={"ip_adapter_masks": ...}; the reference repaints one subject per
+ * inpainting loop, gdino/lib.py:85-103). The adapter's image tokens are G groups of four (one group per subject; ia2p_set_ip_adapter(1, 4 G, scale) first, else
+ * IA2P_ERR_STATE); group g acts on the queries of every cross-attention site under region_masks[b, g] -- fp16 [B, G, h, w] on the latent grid, device, any finite
+ * values -- pooled to the site's resolution by the block mean (ia2p_region_levels: one launch per distinct attention resolution, once per forward, into the
+ * workspace). Every cross-attention site runs its q GEMM and ia2p_attention_regions (the fused to_q launch has no regional form). Both routes to the context K/V
+ * work: `context` (projected in the step, Li = 4 G image-token rows) or `kv` (ia2p_project_context under the same ia2p_set_ip_adapter state). The workspace is
+ * sized by ia2p_workspace_bytes_r (the plain pass's plus the pyramid; 0 on a bad shape); ia2p_workspace_bytes is unchanged. No allocation, no synchronisation. */
+size_t ia2p_workspace_bytes_r(ia2p_ctx* ctx, int B, int h, int w, int L, int G);
+ia2p_status ia2p_unet_forward_r(ia2p_ctx* ctx, void* stream, const void* sample, const float* timesteps, const float* ip_scales,
+                                const void* context, const void* kv, int L, const void* text_embeds, const void* time_ids, void* out,
+                                int B, int h, int w, void* workspace, size_t workspace_bytes, const void* region_masks, int G);
 
 /* ---- context K/V hoisted out of the step (optional) ------------------------------------------------------------------
  * The K/V projections of every cross-attention layer (reference attention_processor.py:358-359,379-380) depend only on the context and the
@@ -365,6 +378,23 @@ ia2p_status ia2p_conv_out(void* stream, const void* x_nhwc, const void* w_packed
 ia2p_status ia2p_attention(void* stream, const void* Q, int ldq, void* O, int ldo, int B, int heads, int Nq, int nseg,
                            const void* K0, const void* V0, int ld0, int nkeys0, float w0,
                            const void* K1, const void* V1, int ld1, int nkeys1, float w1);
+/* Regional image prompts -- what diffusers offers as cross_attention_kwargs={"ip_adapter_masks": ...}: every subject's four image tokens ride in ONE context, each
+ * token group has a softmax of its own and acts only where its own spatial mask says so, so S subjects cost one denoising loop instead of S:
+ *   O[b,q,h*64:] = w0 softmax_j(q . k_text_j / 8) v_text_j + sum_{g < G} s[b] m[b,g,q] softmax_{j in group g}(q . k_ip_j / 8) v_ip_j
+ * The arguments of ia2p_attention (nseg must be 2), plus: region_w = m, fp16 [B, G, Nq], device memory, any finite values (usually [0, 1]; a per-group scale is folded
+ * into it by the host); G token groups, group g = rows 4 g .. 4 g + 3 of segment 1, 1 <= G <= 16 and nkeys1 == 4 G; s[b] = w1_b[b] (device, float [B]) or, w1_b NULL,
+ * w1. m == 0 puts a probability of exactly +0 into the P.V product: a group's keys and values cannot move a bit of the output at queries its mask leaves out, and
+ * all-zero groups appended to a call (padding a batch to its largest G) leave every bit as it was. The text softmax never sees an image-token key, a group's softmax
+ * never another group's keys. Refusals, all before any launch: a NULL pointer (w1_b may be NULL), nseg != 2 or w0 == 0 (the merged accumulator divides by it)
+ * IA2P_ERR_INVALID; G outside 1 .. 16, nkeys1 != 4 G or a stride that is no multiple of 8 elements IA2P_ERR_SHAPE. */
+ia2p_status ia2p_attention_regions(void* stream, const void* Q, int ldq, void* O, int ldo, int B, int heads, int Nq, int nseg,
+                                   const void* K0, const void* V0, int ld0, int nkeys0, float w0,
+                                   const void* K1, const void* V1, int ld1, int nkeys1, float w1,
+                                   const void* region_w, int G, const float* w1_b);
+/* The mask pyramid of the launch above: masks fp16 [B, G, h, w] on the latent grid -> out fp16 [B, G, (h / f) * (w / f)], the mean of each f x f block -- summed in
+ * fp32 in row-major order (one fixed order, no atomics), scaled by the exact 1 / f^2 and rounded once. {0, 1} masks come out exact. f is 1, 2, 4 or 8 (anything
+ * else IA2P_ERR_INVALID); h % f or w % f non-zero is IA2P_ERR_SHAPE. */
+ia2p_status ia2p_region_levels(void* stream, const void* masks, void* out, int B, int G, int h, int w, int f);
 /* `to_q` fused with the cross-attention that consumes it (reference attention_processor.py:344 + :371 / :387 / :397; AttnProcessor2_0 :239 + :259):
  *   O = ia2p_attention(Q = epilogue(X . Wq^T), ...)  in ONE launch, Q never written -- bit-identical to ia2p_gemm_ex on a 128 x 64 tile followed
  *   by ia2p_attention. X [B*Nq, K], Wq [heads*64, K] (gamma-folded when ln != NULL, as ia2p_gemm_ex), bias [heads*64] or NULL (ignored with ln).

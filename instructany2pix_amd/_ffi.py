@@ -92,6 +92,8 @@ SIGNATURES = {
     "ia2p_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
     "ia2p_unet_forward": (_I, [_P, _P, _P, _F, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ]),
     "ia2p_unet_forward_v": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ]),
+    "ia2p_workspace_bytes_r": (_SZ, [_P, _I, _I, _I, _I, _I]),
+    "ia2p_unet_forward_r": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ, _P, _I]),
     "ia2p_context_kv_bytes": (_SZ, [_P, _I, _I]),
     "ia2p_project_context": (_I, [_P, _P, _P, _I, _I, _P, _SZ, _P, _SZ]),
     "ia2p_unet_forward_kv": (_I, [_P, _P, _P, _F, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ]),
@@ -131,6 +133,8 @@ SIGNATURES = {
     "ia2p_conv_in": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "ia2p_conv_out": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "ia2p_attention": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _P, _I, _I, _F]),
+    "ia2p_attention_regions": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _P, _I, _I, _F, _P, _I, _P]),
+    "ia2p_region_levels": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
     "ia2p_qkv_self_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "ia2p_qkv_self_attention_ctx": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "ia2p_qproj_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _P, _P, _I, _I, _F]),

@@ -169,8 +169,30 @@ class IPAttnProcessor2_0(_HipAttnBase):
         self.attn_map = None
         self.fuse_to_q = True
 
+    @staticmethod
+    def _region_weights(masks, B, Nq, dev):
+        """`ip_adapter_masks` -> fp16 [B, G, Nq] for a site of Nq queries: [B, G, Nq] as is; [B, G, h, w] / [G, h, w] on a finer grid pooled by the block mean
+        (`ia2p_region_levels`), the grid's aspect kept"""
+        m = torch.as_tensor(masks).to(device=dev, dtype=torch.float16)
+        if m.ndim == 3 and m.shape[-1] == Nq and m.shape[0] == B:
+            return m.contiguous()
+        if m.ndim == 3:
+            m = m[None].expand(B, *m.shape)
+        if m.ndim != 4 or m.shape[0] != B:
+            raise ValueError(f"ip_adapter_masks must be [B, G, h, w], [G, h, w] or [B, G, Nq]; got {tuple(m.shape)}")
+        G, h, w = m.shape[1:]
+        f = next((f for f in (1, 2, 4, 8) if h % f == 0 and w % f == 0 and (h // f) * (w // f) == Nq), None)
+        if f is None:
+            raise ValueError(f"ip_adapter_masks on a {h} x {w} grid do not pool to the {Nq} queries of this site by a factor of 1, 2, 4 or 8")
+        m = m.contiguous()
+        out = torch.empty(B, G, Nq, dtype=torch.float16, device=dev)
+        _ffi.check(_ffi.lib().ia2p_region_levels(_ffi.current_stream(), _p(m), _p(out), B, G, h, w, f))
+        return out
+
     @torch.no_grad()
-    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, *args, **kwargs):
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, *args, ip_adapter_masks=None, **kwargs):
+        """`ip_adapter_masks` (diffusers' regional image prompts): the last 4 G context rows are G groups of four image tokens, group g acts on the queries under
+        mask g (`ia2p_attention_regions`); the processor's own `num_tokens` is not consulted for such a call."""
         self._check(attn, hidden_states, attention_mask, temb)
         residual = hidden_states
         hidden_states, shape4 = self._enter(hidden_states)
@@ -178,6 +200,8 @@ class IPAttnProcessor2_0(_HipAttnBase):
         dev, heads, inner = hidden_states.device, attn.heads, attn.to_q.weight.shape[0]
         if encoder_hidden_states is None:                                    # :346-347
             encoder_hidden_states = hidden_states
+        if ip_adapter_masks is not None:
+            return self._call_regions(attn, hidden_states, encoder_hidden_states, ip_adapter_masks, residual, shape4)
         end = encoder_hidden_states.shape[1] - self.num_tokens               # :350 (a 77-token context loses its last 4 text rows here)
         if end < 1:
             raise ValueError(f"context length {encoder_hidden_states.shape[1]} must exceed the {self.num_tokens} image tokens")
@@ -207,6 +231,36 @@ class IPAttnProcessor2_0(_HipAttnBase):
         wo, bo = self._stack("out", [attn.to_out[0]], dev)                   # :400 (+ dropout(0) :402)
         res = None
         if getattr(attn, "residual_connection", False) and shape4 is None:  # :407-408
+            res = _f16c(residual).reshape(B * Nq, -1)
+        out = self._gemm(self._rows(o, wo.shape[1]), wo, bo, res).reshape(B, Nq, -1)
+        return self._leave(out, attn, shape4, residual if getattr(attn, "residual_connection", False) else None)
+
+
+    def _call_regions(self, attn, hidden_states, encoder_hidden_states, masks, residual, shape4):
+        B, Nq, _ = hidden_states.shape
+        dev, heads, inner = hidden_states.device, attn.heads, attn.to_q.weight.shape[0]
+        if self.store_attn_map:
+            raise NotImplementedError("attn_map is not produced for a regional call")
+        rw = self._region_weights(masks, B, Nq, dev)
+        G = rw.shape[1]
+        ntok = 4 * G
+        end = encoder_hidden_states.shape[1] - ntok
+        if not 1 <= G <= 16 or end < 1:
+            raise ValueError(f"{G} regions need 1 <= G <= 16 and a context longer than {ntok} rows (got {encoder_hidden_states.shape[1]})")
+        text, ip = encoder_hidden_states[:, :end], encoder_hidden_states[:, end:]
+        L = _ffi.lib()
+        wq, bq = self._stack("q", [attn.to_q], dev)
+        wkv, bkv = self._stack("kv", [attn.to_k, attn.to_v], dev)
+        wip, _ = self._stack("kvip", [self.to_k_ip, self.to_v_ip], dev)
+        q = self._gemm(self._rows(hidden_states.reshape(B * Nq, -1), wq.shape[1]), wq, bq)
+        kv = self._gemm(self._rows(text.reshape(B * end, -1), wkv.shape[1]), wkv, bkv)
+        kvip = self._gemm(self._rows(ip.reshape(B * ntok, -1), wip.shape[1]), wip, None)
+        o = torch.empty(B * Nq, inner, dtype=torch.float16, device=dev)
+        _ffi.check(L.ia2p_attention_regions(_ffi.current_stream(), _p(q), inner, _p(o), inner, B, heads, Nq, 2, _p(kv), _p(kv, inner), 2 * inner, end, 1.0,
+                                            _p(kvip), _p(kvip, inner), 2 * inner, ntok, float(self.scale), _p(rw), G, None))
+        wo, bo = self._stack("out", [attn.to_out[0]], dev)
+        res = None
+        if getattr(attn, "residual_connection", False) and shape4 is None:
             res = _f16c(residual).reshape(B * Nq, -1)
         out = self._gemm(self._rows(o, wo.shape[1]), wo, bo, res).reshape(B, Nq, -1)
         return self._leave(out, attn, shape4, residual if getattr(attn, "residual_connection", False) else None)

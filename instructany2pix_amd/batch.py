@@ -70,6 +70,7 @@ class EditRequest:
     sampler: Optional[str] = None              # "ddim" or "lcm"; None: what `pipe.pipe.scheduler` is (DDIM, or LCM when an `LCMScheduler` is assigned there)
     sample_steps: Optional[int] = None         # length of the LCM schedule (default 4, 1 .. 50); `num_inference_steps` keeps governing the inversion
     step_noise: Optional[torch.Tensor] = None  # LCM: the noise injected after every step but the last, fp16 [sample_steps - 1, 4, h, w]; wins over the seed (draw DRAW_LCM)
+    subject_mode: str = "serial"               # the request's subject-consistency stage, serial or joint (`edit_batch(subject_modes=)` sets it; the hot segment does not read it)
 
 
 def _coef_table(rows: Sequence[Sequence[tuple]], device) -> torch.Tensor:
@@ -630,6 +631,28 @@ class InpaintRequest:
     noise: Optional[torch.Tensor] = None       # start and re-noising noise; None: drawn from the global CPU RNG in request order
     seed: Optional[int] = None                 # without `noise`: draw `draw` of the request's own stream, on the device
     draw: int = _noise.DRAW_INPAINT            # DRAW_INPAINT + k for subject pass k
+    # a JOINT pass over several subjects (regional image prompts: one loop, every subject's tokens under its own mask, the blend under their union): the
+    # subjects' masks and embeddings as lists of equal length (1 .. 16); `mask` / `subject_embed` are then not read (pass None)
+    masks: Optional[list] = None
+    subject_embeds: Optional[list] = None
+
+
+def pad_subjects(subjects: Sequence[tuple], h: int, w: int, device) -> tuple:
+    """The padding rule of a joint group. `subjects`: per request (masks, embeddings), 1 .. 16 each -> (regions [n, G, h, w] fp16 in {0, 1}, embeddings
+    [n G, D] fp16, G) with G the group's largest subject count: a request with fewer subjects is padded with ALL-ZERO masks and zero embeddings. A zero region weight
+    puts a probability of exactly +0 into the attention's P.V product (`ia2p_attention_regions`), so the padding changes no bit of that row's result."""
+    from .inpaint import prepare_mask
+    G = max(len(m) for m, _ in subjects)
+    if not 1 <= G <= 16 or any(len(m) != len(e) or len(m) < 1 for m, e in subjects):
+        raise ValueError("a joint subject pass takes 1 .. 16 subjects per request, one embedding per mask")
+    D = int(torch.as_tensor(subjects[0][1][0]).numel())
+    regions = torch.zeros(len(subjects), G, h, w, dtype=torch.float16, device=device)
+    embeds = torch.zeros(len(subjects), G, D, dtype=torch.float16, device=device)
+    for r, (ms, es) in enumerate(subjects):
+        for g, (m, e) in enumerate(zip(ms, es)):
+            regions[r, g] = prepare_mask(m, h, w, device)[0, 0]
+            embeds[r, g] = torch.as_tensor(e).reshape(-1).to(device=device, dtype=torch.float16)
+    return regions, embeds.reshape(len(subjects) * G, D), G
 
 
 @dataclass
@@ -664,11 +687,21 @@ def _inpaint_group(ipa, reqs: List[InpaintRequest], noises, tb: InpaintTables, s
     dev, n = unet.device, len(reqs)
     lat, noise = _rows([r.latents for r in reqs], dev), _rows(noises, dev)
     h, w = lat.shape[-2:]
-    mask = torch.cat([prepare_mask(r.mask, h, w, dev) for r in reqs], dim=0).contiguous()
-    if tuple(mask.shape) != (n, 1, h, w):
-        raise ValueError(f"every request carries ONE mask, got {tuple(mask.shape)} for {n} requests")
-    # the subjects' 'local' image tokens, one call per group, with the crop weights IPAdapterXL.generate passes (scale_g = 1.0, scale_l = 0.5)
-    ip, ip_un = ipa.get_image_embeds(clip_image_embeds_local=torch.stack([r.subject_embed.reshape(-1) for r in reqs]), mode="local", scale_g=1.0, scale_l=0.5)
+    regions = None
+    if any(r.masks is not None for r in reqs):
+        # a joint group: every request's subjects padded to the group's largest count (`pad_subjects`), their tokens [n, 4 G, ctx] from ONE image-projection
+        # call, the blend under the union of each request's masks
+        from .inpaint import union_mask
+        regions, embeds, G = pad_subjects([(list(r.masks), list(r.subject_embeds)) if r.masks is not None else ([r.mask], [r.subject_embed]) for r in reqs], h, w, dev)
+        mask = union_mask(regions).contiguous()
+        ip, ip_un = ipa.get_image_embeds(clip_image_embeds_local=embeds, mode="local", scale_g=1.0, scale_l=0.5)
+        ip, ip_un = ip.reshape(n, 4 * G, -1), ip_un.reshape(n, 4 * G, -1)
+    else:
+        mask = torch.cat([prepare_mask(r.mask, h, w, dev) for r in reqs], dim=0).contiguous()
+        if tuple(mask.shape) != (n, 1, h, w):
+            raise ValueError(f"every request carries ONE mask, got {tuple(mask.shape)} for {n} requests")
+        # the subjects' 'local' image tokens, one call per group, with the crop weights IPAdapterXL.generate passes (scale_g = 1.0, scale_l = 0.5)
+        ip, ip_un = ipa.get_image_embeds(clip_image_embeds_local=torch.stack([r.subject_embed.reshape(-1) for r in reqs]), mode="local", scale_g=1.0, scale_l=0.5)
     size = (h * ipa.pipe.vae_scale_factor, w * ipa.pipe.vae_scale_factor)
     ctx, added = conditioning(dev, torch.cat([_rows([r.prompt_embeds for r in reqs], dev), ip], dim=1), _rows([r.pooled_prompt_embeds for r in reqs], dev),
                               get_add_time_ids(unet, size, (0, 0), size, int(reqs[0].pooled_prompt_embeds.shape[-1])),
@@ -681,8 +714,9 @@ def _inpaint_group(ipa, reqs: List[InpaintRequest], noises, tb: InpaintTables, s
     fused_update_v(lat, noise, None, _coef_table(tb.start, dev), x)
     model_in = torch.cat([x, x], dim=0).contiguous()
     eps, stepped = torch.empty_like(model_in), torch.empty_like(x)
+    kw = {} if regions is None else {"cross_attention_kwargs": {"ip_adapter_masks": torch.cat([regions, regions], dim=0).contiguous()}}      # both CFG rows: the same masks
     for k in range(len(tb.timesteps)):
-        unet(model_in, ts_all[k], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps, ip_scales=sc)
+        unet(model_in, ts_all[k], encoder_hidden_states=ctx, added_cond_kwargs=added, out=eps, ip_scales=sc, **kw)
         fused_update_v(model_in[:n], eps[:n], eps[n:], coef_all[k], stepped)
         mask_blend_v(stepped, lat, noise, mask, blend_all[k], model_in[:n], model_in[n:])
     return model_in[:n].clone()
@@ -695,6 +729,8 @@ def inpaint_batch(ipa, requests: List[InpaintRequest], group: int = 4, shard: bo
     requests, one subject each: one UNet evaluation at B_eff = 2 n per iteration of a group, request r on its own `strength`-shortened tail of the shared
     schedule with its own mask and subject tokens. `ipa` is the adapter over the inpainting pipeline (`InstructAny2PixPipeline.ip_adapter_xl_inpaint`); steps,
     guidance and IP scale are what `subject_consistency` passes. The processors' own scale is left alone: the IP scale goes in per row.
+    A request with `masks` / `subject_embeds` (lists) is a JOINT pass over its subjects; a group that holds one runs the regional route, every request padded
+    to the group's largest subject count (`pad_subjects`: no bit of a row changes by it).
     -> latents [N, 4, h, w] in request order on every rank."""
     latents, unet = [r.latents for r in requests], ipa.pipe.unet
     _check_latents(latents, "inpaint_batch")
@@ -740,8 +776,10 @@ def _vae_in_batches(pipeline, fn, t: torch.Tensor, group: int, decode: bool, see
 @torch.no_grad()
 def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
                scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None,
-               lora_scale=None, samplers=None, sample_steps=None, sample_adapters=None):
-    """`InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
+               lora_scale=None, samplers=None, sample_steps=None, sample_adapters=None, subject_modes="serial"):
+    """`subject_modes` ("serial", "joint" or a list of N): a "joint" request repaints all its subjects in ONE inpaint stage (regional image prompts, one noise:
+    draw DRAW_INPAINT + 0) -- not the serial result, where pass k + 1 starts from the repaint of pass k and draws its own noise. The serial requests of the call keep
+    their bits. `InstructAny2PixPipeline.__call__` for N instructions on N images in one call -> the list of its `(non_refined, oo, msg)` tuples in request order.
     See `InstructAny2PixPipeline.edit_batch` for the contract (knobs, stages, RNG rule, sharding). `lora_scale`: one number for the whole call (a batch
     shares its weights: no per-request adapters); None launches nothing. `samplers`, `sample_steps` (a scalar or a list of N; None: as ever) and
     `sample_adapters` (one value per call): the consistency sampler for the guided sampling stage (`denoise_batch`)."""
@@ -750,7 +788,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             return edit_batch(pipeline, insts, mm_datas, alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
                               subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds,
                               edit_masks=edit_masks, edit_feather=edit_feather, auto_masks=auto_masks, samplers=samplers, sample_steps=sample_steps,
-                              sample_adapters=sample_adapters)
+                              sample_adapters=sample_adapters, subject_modes=subject_modes)
     from . import pipeline as P
     from .auto_mask import auto_mask_t_start, estimate_requests, intersect, resolve_auto_mask
     from .image_processor import requantize
@@ -774,6 +812,10 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     steps, subject_strength = per_request(num_inference_steps, N, "num_inference_steps"), per_request(subject_strength, N, "subject_strength")
     cfg, scale, h = per_request(cfg, N, "cfg"), per_request(scale, N, "scale"), per_request(h, N, "h", _is_one_h)
     samplers, sample_steps = per_request(samplers, N, "samplers"), per_request(sample_steps, N, "sample_steps")
+    subject_modes = per_request(subject_modes, N, "subject_modes")
+    for i, m in enumerate(subject_modes):
+        if m not in ("serial", "joint"):
+            raise ValueError(f"subject_modes: 'serial' or 'joint', got {m!r} (request {i})")
     lcm = [False] * N
     sch = getattr(getattr(pipeline, "pipe", None), "scheduler", None)
     if any(v is not None for v in samplers + sample_steps) or isinstance(sch, LCMScheduler):
@@ -832,7 +874,7 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
     reqs = [EditRequest(base_latents=base[i], latent_la=latent_la[i].reshape(1, -1)[0], **P.embeds(cs[i]), inv_prompt_embeds=cs[i].get("inv_prompt_embeds"),
                         inv_pooled_prompt_embeds=cs[i].get("inv_pooled_prompt_embeds"), alpha=alpha[i], num_inference_steps=int(steps[i]), cfg=float(cfg[i]),
                         scale=float(scale[i]), noise=cs[i].get("polar_noise"), seed=seeds[i], edit_mask=edit_m[i], auto_mask=auto_masks[i], sampler=samplers[i],
-                        sample_steps=sample_steps[i], step_noise=cs[i].get("step_noise")) for i in live]
+                        sample_steps=sample_steps[i], step_noise=cs[i].get("step_noise"), subject_mode=subject_modes[i]) for i in live]
     pipeline.pipe_inversion.unet = pipeline.pipe.unet
     # automatic masks, before the inversion: the estimate times the user's latent mask is the request's edit mask from here on; its pixel mask is
     # the latent mask's cells, inside the user's pixel mask where there is one
@@ -878,7 +920,15 @@ def edit_batch(pipeline, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=
             pairs[i] = pipeline._subject_mask_pairs(cs[i], cs[i]["subject_data"], oo[i])
             if i in edit:                                                                          # a subject pass under an edit mask repaints inside both
                 pairs[i] = [(P.intersect_subject_mask(mk, edit[i][0]), emb) for mk, emb in pairs[i]]
-        for k in range(max(len(p) for p in pairs.values())):
+        joint = [i for i in sub if subject_modes[i] == "joint"]
+        if joint:                    # one inpaint stage for the joint requests: all subjects of a request in one loop, one noise
+            ir = [InpaintRequest(latents=oo[i], mask=None, subject_embed=None, masks=[mk for mk, _ in pairs[i]], subject_embeds=[emb for _, emb in pairs[i]],
+                                 **P.embeds(cs[i], "subject_"), strength=float(subject_strength[i]), noise=cs[i].get("subject_noise"), seed=seeds[i],
+                                 draw=_noise.inpaint_draw(0)) for i in joint]
+            painted = inpaint_batch(pipeline.ip_adapter_xl_inpaint, ir, group=group, shard=shard)
+            oo.update({i: painted[j:j + 1] for j, i in enumerate(joint)})
+        sub = [i for i in sub if subject_modes[i] != "joint"]
+        for k in range(max([len(pairs[i]) for i in sub], default=0)):
             now = [i for i in sub if len(pairs[i]) > k]
             ir = [InpaintRequest(latents=oo[i], mask=pairs[i][k][0], subject_embed=pairs[i][k][1], **P.embeds(cs[i], "subject_"), strength=float(subject_strength[i]),
                                  noise=cs[i].get("subject_noise"), seed=seeds[i], draw=_noise.inpaint_draw(k)) for i in now]

@@ -12,14 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDES = [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ia2p.h", "ia2p_debug.h")]
 OUT = os.path.join(HERE, "libia2p_hip.so")
-SOURCES = ["gemm.hip", "qxattn.hip", "attention.hip", "norm.hip", "misc.hip", "engine_rt.hip", "engine.hip", "ops_abi.hip", "vae_engine.hip", "clip_engine.hip", "vit.hip", "vit_engine.hip", "llm_engine.hip", "image.hip", "sample.hip", "noise.hip", "auto_mask.hip", "lora.hip", "sam.hip", "sam_engine.hip", "lcm.hip"]
+SOURCES = ["gemm.hip", "qxattn.hip", "attention.hip", "attention_regions.hip", "norm.hip", "misc.hip", "engine_rt.hip", "engine.hip", "ops_abi.hip", "vae_engine.hip", "clip_engine.hip", "vit.hip", "vit_engine.hip", "llm_engine.hip", "image.hip", "sample.hip", "noise.hip", "auto_mask.hip", "lora.hip", "sam.hip", "sam_engine.hip", "lcm.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"] + os.environ.get("IA2P_EXTRA_FLAGS", "").split()    # (A/B builds of compile-time knobs)
 # attention: MFMA results feed VALU softmax directly; the VGPR form avoids ~250 v_accvgpr_read/write per key tile
 # kernarg preload: the leading dwords of a kernel's (scalar) arguments arrive in SGPRs instead of through a cold read of the argument block -- FOURTEEN of them
 # (16 user SGPRs less the argument block's address: `.amdhsa_user_sgpr_kernarg_preload_length 14` whatever count is asked for; the kernels' leading arguments are packed to fit)
 PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
-FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + PRELOAD, "qxattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + PRELOAD, "gemm.hip": PRELOAD, "norm.hip": PRELOAD, "vit.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "sam.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + PRELOAD, "attention_regions.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + PRELOAD,"qxattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + PRELOAD, "gemm.hip": PRELOAD, "norm.hip": PRELOAD, "vit.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "sam.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _stamp():

@@ -289,6 +289,10 @@ struct Fwd {
   bool gn_on = false;
   std::unordered_map<int, int> kv_inlaunch;      // context K/V column (TBlock::kv_col) -> 1: left for the block's fused QKV + self-attention launch to project (plan_context_kv); 2: done
   bool tune_like = false;      // the autotune pass (or the dry pass that sizes the workspace for it): GroupNorm launches, plus what tune_site needs to time the fused forms beside them
+  // regional image prompts (ia2p_unet_forward_r): G token groups and the per-query weights [B, G, HW] of every distinct attention resolution (region_levels),
+  // built once per forward at the front of the workspace
+  int G = 0, n_rlev = 0;
+  struct { int HW; T2 w; } rlev[IA2P_MAX_BLOCKS + 1];
 };
 static void gst_put(Fwd& f, T2 t, const GnStats& s) { if (s.ok() && t.off != (size_t)-1) f.gst[t.off] = s; else if (s.buf.off != (size_t)-1) wsfree(f.c, s.buf); }
 static GnStats gst_get(Fwd& f, T2 t) { auto it = f.gst.find(t.off); return it == f.gst.end() ? GnStats{} : it->second; }
@@ -461,6 +465,13 @@ static void op_qkv_sattn(RunCtx* c, const half_t* A, int lda, const half_t* W, c
                2.0 * ((double)M * C + 3.0 * C * C + (double)M * C) + (ck ? 2.0 * (ck_rows * ck->K + (ck->Li > 0 ? 2.0 : 1.0) * ck->N * ck->K + ck_rows * ck->N) : 0.0));
   ps.pf = a.pf ? (double)a.pf_bytes : 0.0;
   CHECK_LAUNCH(c, ia2p_launch_qkv_sattn(a, x, c->stream, ck), "qkv projection + self-attention");
+}
+
+// cross-attention with G image-token groups, each under its own per-query weight (attention_regions.hip)
+static void op_attn_regions(RunCtx* c, const AttnArgs& a, const half_t* region_w, int G) {
+  const double keys = a.seg[0].nkeys + a.seg[1].nkeys;
+  ProfScope ps(c, PK_ATTN, 4.0 * a.B * a.heads * (double)a.Nq * keys * 64, 2.0 * ((double)a.B * a.Nq * a.heads * 64 * 2 + 2.0 * a.B * keys * a.heads * 64 + (double)a.B * G * a.Nq));
+  CHECK_LAUNCH(c, ia2p_launch_attention_regions(a, region_w, G, c->stream), "regional cross-attention");
 }
 
 static void op_attn(RunCtx* c, const AttnArgs& a) {
@@ -640,7 +651,11 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
       a.w1_b = Li ? f.ip_scales : nullptr;
       // a 128 x 64 tile of to_q is 128 queries x one head: projection and attention run as one launch when tiles do not straddle batch elements
       // (and the context fits 3 key tiles: its K / V ride in registers through the projection loop); small problems keep the finer 64 x 64 split
-      const bool fuse = c->xattn_fuse && HW % 128 == 0 && C == t.heads * 64 && (Lt + 63) / 64 + (Li + 63) / 64 <= 3 && (long)(M / 128) * t.heads >= c->xattn_min_tiles;
+      // (a regional site -- ia2p_unet_forward_r -- always takes the q GEMM and the stand-alone regional launch)
+      const half_t* rw = nullptr;
+      for (int i = 0; i < f.n_rlev; ++i) if (f.rlev[i].HW == HW) rw = f.rlev[i].w.p;
+      const bool regional = f.G > 0;
+      const bool fuse = !regional && c->xattn_fuse && HW % 128 == 0 && C == t.heads * 64 && (Lt + 63) / 64 + (Li + 63) / 64 <= 3 && (long)(M / 128) * t.heads >= c->xattn_min_tiles;
       if (fold) {
         const LnIn ln{st, slots, F_(b.cs2), F_(b.lb2), eps};
         if (fuse) op_qxattn(c, tk.p, C, W_(c, b.fq2), &ln, M, C, C, a);
@@ -650,7 +665,8 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
         if (fuse) op_qxattn(c, lnb.p, C, W_(c, b.wq2), nullptr, M, C, C, a);
         else op_gemm(c, lnb.p, C, W_(c, b.wq2), nullptr, nullptr, 0, qkv.p, C, M, C, C);
       }
-      if (!fuse) op_attn(c, a);
+      if (regional) op_attn_regions(c, a, rw, f.G);
+      else if (!fuse) op_attn(c, a);
     }
     { RoleScope role(c, ROLE_ATTN_OUT); op_gemm(c, att.p, C, W_(c, b.wo2), W_(c, b.bo2), tk.p, C, tk.p, C, M, C, C, to_tk); }
     // GEGLU feed-forward
@@ -682,7 +698,8 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
 // 3: the sizing pass of ia2p_autotune
 static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, float timestep, const half_t* context, int L,
                                const half_t* text_embeds, const half_t* time_ids, half_t* out, int B, int h, int w,
-                               const half_t* kv_cached = nullptr, const float* timesteps = nullptr, const float* ip_scales = nullptr) {
+                               const half_t* kv_cached = nullptr, const float* timesteps = nullptr, const float* ip_scales = nullptr,
+                               const half_t* region_masks = nullptr, int G = 0) {
   const ia2p_unet_config& g = c->cfg;
   const int n = g.n_blocks;
   const int T = g.time_embed_dim, Tp = g.time_proj_dim, Ain = g.projection_class_embeddings_input_dim, Ad = g.addition_time_embed_dim;
@@ -693,6 +710,31 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   f.tune_like = c->gn_fuse != 0 && (c->dry && !c->record ? gn_mode == 3 : c->tuning);      // (a sizing pass takes its mode's word; a recording or real pass is what the context is doing)
   f.gn_on = gn_mode != 0 && gn_mode != 3 && !c->tuning;      // (the autotune pass measures the plain kernels: GroupNorm launches there)
 
+  // regional image prompts: the mask pyramid, one launch per distinct attention resolution, FIRST in the workspace (a regional pass needs what the plain pass needs
+  // plus exactly these tensors: ia2p_workspace_bytes_r)
+  f.G = G;
+  if (G > 0) {
+    int H = h, Wd = w;
+    auto level = [&](bool has_att) {
+      if (!has_att) return;
+      for (int i = 0; i < f.n_rlev; ++i) if (f.rlev[i].HW == H * Wd) return;
+      auto& lv = f.rlev[f.n_rlev++];
+      lv.HW = H * Wd;
+      lv.w = wsalloc(c, (size_t)B * G * H * Wd);
+      RoleScope role(c, ROLE_Q_XATTN);
+      ProfScope ps(c, PK_EMBED, 0, 0);
+      CHECK_LAUNCH(c, ia2p_launch_region_levels(region_masks, lv.w.p, B, G, h, w, h / H, c->stream), "region_levels");
+    };
+    for (const Stage& st : c->down) {
+      level(!st.att.empty());
+      if (st.resample) { H = (H - 1) / 2 + 1; Wd = (Wd - 1) / 2 + 1; }
+    }
+    level(!c->mid_t.blocks.empty());
+    for (const Stage& st : c->up) {
+      level(!st.att.empty());
+      if (st.resample) { H *= 2; Wd *= 2; }
+    }
+  }
   // GroupNorm partial sums (fp32) live at the front of the workspace
   T2 gnp = wsalloc(c, (size_t)B * 64 * g.norm_num_groups * 2 * 2);
   f.gn_partial = (float*)gnp.p;
@@ -842,6 +884,7 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   for (auto& kv : f.gst) wsfree(c, kv.second.buf);      // (none left on a complete pass)
   f.gst.clear();
   wsfree(c, no); wsfree(c, f.temb_all); wsfree(c, gnp); wsfree(c, f.kv_text); wsfree(c, f.kv_ip);
+  for (int i = 0; i < f.n_rlev; ++i) wsfree(c, f.rlev[i].w);
   return c->failed ? IA2P_ERR_HIP : IA2P_OK;
 }
 
@@ -1009,9 +1052,22 @@ size_t ia2p_workspace_bytes(ia2p_ctx* c, int B, int h, int w, int L) {
   return need;
 }
 
+// a workspace for ia2p_unet_forward_r with G token groups: the plain pass's, plus the mask pyramid in front of it (a sizing call of its own: ia2p_workspace_bytes and
+// every workspace sized by it stay what they were)
+size_t ia2p_workspace_bytes_r(ia2p_ctx* c, int B, int h, int w, int L, int G) {
+  if (!c || G < 1 || G > 16 || check_fwd_shape(c, B, h, w, L) != IA2P_OK) return 0;
+  size_t need = 0;
+  for (int mode = 0; mode < 3; ++mode) {      // (the autotune pass runs no regions)
+    const size_t n = pass_dry(c, [&] { return run_forward(c, mode, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, nullptr, nullptr, nullptr, nullptr, G); });
+    if (!n) return 0;
+    need = std::max(need, n);
+  }
+  return need;
+}
+
 static ia2p_status unet_forward_impl(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, const void* kv, int L,
                                      const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes,
-                                     const float* timesteps = nullptr, const float* ip_scales = nullptr) {
+                                     const float* timesteps = nullptr, const float* ip_scales = nullptr, const void* region_masks = nullptr, int G = 0) {
   if (!c || !sample || (!context && !kv) || !text_embeds || !time_ids || !out || !ws) return fail(c, IA2P_ERR_INVALID, "unet_forward: null argument");
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "unet_forward before weights were finalized");
   ia2p_status st = check_fwd_shape(c, B, h, w, L);
@@ -1022,11 +1078,11 @@ static ia2p_status unet_forward_impl(ia2p_ctx* c, void* stream, const void* samp
   if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
   if (st != IA2P_OK) return st;
   // the weight launch sequence: a dry pass of the same code path
-  pass_record(c, (c->ip_enabled ? 1 + c->ip_tokens : 0) + (kv ? 1000 : 0),
-              [&] { return run_forward(c, c->gn_fuse, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, kv ? (const half_t*)1 : nullptr); });
+  pass_record(c, (c->ip_enabled ? 1 + c->ip_tokens : 0) + (kv ? 1000 : 0) + (G ? 2000 : 0),
+              [&] { return run_forward(c, c->gn_fuse, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, kv ? (const half_t*)1 : nullptr, nullptr, nullptr, nullptr, G); });
   c->tail_pf = c->arena + c->embed_lo; c->tail_pf_bytes = (c->embed_hi - c->embed_lo) * sizeof(half_t);   // the next step starts with these
   return pass_leave(c, run_forward(c, c->gn_fuse, (const half_t*)sample, timestep, (const half_t*)context, L, (const half_t*)text_embeds, (const half_t*)time_ids, (half_t*)out,
-                                   B, h, w, (const half_t*)kv, timesteps, ip_scales));
+                                   B, h, w, (const half_t*)kv, timesteps, ip_scales, (const half_t*)region_masks, G));
 }
 ia2p_status ia2p_unet_forward(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, int L,
                               const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes) {
@@ -1044,6 +1100,19 @@ ia2p_status ia2p_unet_forward_v(ia2p_ctx* c, void* stream, const void* sample, c
   if (!timesteps || (!context) == (!kv)) return fail(c, IA2P_ERR_INVALID, "unet_forward_v: timesteps and exactly one of context / kv are required");
   if (ip_scales && c && !c->ip_enabled) return fail(c, IA2P_ERR_STATE, "unet_forward_v: per-request IP-Adapter scales without an installed adapter");
   return unet_forward_impl(c, stream, sample, 0.f, context, kv, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes, timesteps, ip_scales);
+}
+
+// ia2p_unet_forward_v with regional image prompts (diffusers' `ip_adapter_masks`): the adapter's image tokens are G groups of four, group g acts on the queries of
+// every cross-attention site under region_masks[b, g] (fp16 [B, G, h, w] on the latent grid, device), pooled to the site's resolution by the block mean
+// (ia2p_region_levels, one launch per distinct attention resolution, once per forward). Every cross-attention site runs its q GEMM and ia2p_attention_regions.
+ia2p_status ia2p_unet_forward_r(ia2p_ctx* c, void* stream, const void* sample, const float* timesteps, const float* ip_scales, const void* context, const void* kv,
+                                int L, const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes,
+                                const void* region_masks, int G) {
+  if (!c) return IA2P_ERR_INVALID;
+  if (!timesteps || (!context) == (!kv) || !region_masks) return fail(c, IA2P_ERR_INVALID, "unet_forward_r: timesteps, region_masks and exactly one of context / kv are required");
+  if (G < 1 || G > 16) return fail(c, IA2P_ERR_SHAPE, "unet_forward_r: G=%d (1 .. 16)", G);
+  if (!c->ip_enabled || c->ip_tokens != 4 * G) return fail(c, IA2P_ERR_STATE, "unet_forward_r: %d token groups need the IP-Adapter enabled with num_tokens = %d (ia2p_set_ip_adapter)", G, 4 * G);
+  return unet_forward_impl(c, stream, sample, 0.f, context, kv, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes, timesteps, ip_scales, region_masks, G);
 }
 
 // ---- context K/V hoisted out of the step: the projections depend on (context, weights) only, constant over a request's steps

@@ -35,6 +35,9 @@ hipError_t ia2p_launch_splitk_reduce(const GemmArgs& a, hipStream_t s);
 bool ia2p_splitk_inkernel(int M, int N, int splitk);
 void ia2p_gemm_candidates(int M, int N, int K, bool conv, bool geglu, size_t max_slab_bytes, double slack, std::vector<GemmPlan>* out);
 hipError_t ia2p_launch_attention(const AttnArgs& a, hipStream_t s);
+// attention_regions.hip: text keys + G groups of four image-token keys, each group with its own softmax and per-query weight region_w [B, G, Nq]; the mask pyramid
+hipError_t ia2p_launch_attention_regions(const AttnArgs& a, const half_t* region_w, int G, hipStream_t s);
+hipError_t ia2p_launch_region_levels(const half_t* masks, half_t* out, int B, int G, int h, int w, int f, hipStream_t s);
 bool ia2p_qproj_xattn_ok(const GemmArgs& a, const AttnArgs& x);
 hipError_t ia2p_launch_qproj_xattn(const GemmArgs& a, const AttnArgs& x, hipStream_t s);   // qxattn.hip: to_q tile -> attention core, one launch
 bool ia2p_qkv_sattn_ok(const GemmArgs& a, const AttnArgs& x);

@@ -310,6 +310,34 @@ ia2p_status ia2p_attention(void* stream, const void* Q, int ldq, void* O, int ld
   hipError_t e = ia2p_launch_attention(a, (hipStream_t)stream);
   RET_HIP(e, "attention");
 }
+// Regional image prompts (diffusers' `ip_adapter_masks`): segment 1 is G groups of four image-token keys, each with its own softmax and its own per-query weight.
+// Every refusal comes before any HIP call.
+ia2p_status ia2p_attention_regions(void* stream, const void* Q, int ldq, void* O, int ldo, int B, int heads, int Nq, int nseg,
+                                   const void* K0, const void* V0, int ld0, int nkeys0, float w0, const void* K1, const void* V1, int ld1, int nkeys1, float w1,
+                                   const void* region_w, int G, const float* w1_b) {
+  if (!Q || !O || !K0 || !V0 || !K1 || !V1 || !region_w) return fail(nullptr, IA2P_ERR_INVALID, "attention_regions: null pointer");
+  if (nseg != 2) return fail(nullptr, IA2P_ERR_INVALID, "attention_regions: nseg=%d (text keys and image-token keys: 2)", nseg);
+  if (w0 == 0.f) return fail(nullptr, IA2P_ERR_INVALID, "attention_regions: w0 == 0 (the merged accumulator divides by it)");
+  if (G < 1 || G > 16 || nkeys1 != 4 * G) return fail(nullptr, IA2P_ERR_SHAPE, "attention_regions: G=%d (1 .. 16), nkeys1=%d must be 4 G", G, nkeys1);
+  if (ldq % 8 || ldo % 8 || ld0 % 8 || ld1 % 8) return fail(nullptr, IA2P_ERR_SHAPE, "attention_regions: strides ldq=%d ldo=%d ld0=%d ld1=%d must be multiples of 8", ldq, ldo, ld0, ld1);
+  if (B < 1 || heads < 1 || Nq < 1 || nkeys0 < 1 || (((uintptr_t)O) & 15) || (((uintptr_t)region_w) & 1))
+    return fail(nullptr, IA2P_ERR_SHAPE, "attention_regions: B=%d heads=%d Nq=%d nkeys0=%d must be >= 1, O 16-byte aligned", B, heads, Nq, nkeys0);
+  if ((int64_t)((Nq + 127) / 128) * heads * B > INT32_MAX) return fail(nullptr, IA2P_ERR_SHAPE, "attention_regions: too many workgroups for one launch");
+  AttnArgs a = attn_desc((const half_t*)Q, ldq, (half_t*)O, ldo, B, heads, Nq, 2, AttnSeg{(const half_t*)K0, (const half_t*)V0, nkeys0, ld0, nkeys0, w0},
+                         AttnSeg{(const half_t*)K1, (const half_t*)V1, nkeys1, ld1, nkeys1, w1});
+  a.w1_b = w1_b;
+  hipError_t e = ia2p_launch_attention_regions(a, (const half_t*)region_w, G, (hipStream_t)stream);
+  RET_HIP(e, "attention_regions");
+}
+// masks [B, G, h, w] on the latent grid -> [B, G, (h / f) (w / f)]: the mean of each f x f block (fp32 sum in row-major order, rounded once)
+ia2p_status ia2p_region_levels(void* stream, const void* masks, void* out, int B, int G, int h, int w, int f) {
+  if (!masks || !out) return fail(nullptr, IA2P_ERR_INVALID, "region_levels: null pointer");
+  if (f != 1 && f != 2 && f != 4 && f != 8) return fail(nullptr, IA2P_ERR_INVALID, "region_levels: f=%d (1, 2, 4 or 8)", f);
+  if (B < 1 || G < 1 || h < 1 || w < 1 || h % f || w % f) return fail(nullptr, IA2P_ERR_SHAPE, "region_levels: B=%d G=%d h=%d w=%d must be >= 1, h and w multiples of f=%d", B, G, h, w, f);
+  if ((int64_t)B * G * h * w > INT32_MAX) return fail(nullptr, IA2P_ERR_SHAPE, "region_levels: %lld elements exceed the 32-bit count of one launch", (long long)B * G * h * w);
+  hipError_t e = ia2p_launch_region_levels((const half_t*)masks, (half_t*)out, B, G, h, w, f, (hipStream_t)stream);
+  RET_HIP(e, "region_levels");
+}
 ia2p_status ia2p_qproj_attention(void* stream, const void* X, const void* Wq, const void* bias, const ia2p_ln_fold* ln, void* O, int ldo, int B, int heads,
                                  int Nq, int K, int nseg, const void* K0, const void* V0, int ld0, int nkeys0, float w0,
                                  const void* K1, const void* V1, int ld1, int nkeys1, float w1) {

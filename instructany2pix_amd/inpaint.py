@@ -43,6 +43,27 @@ def prepare_mask(mask_image, h: int, w: int, device) -> torch.Tensor:
     return m.to(device=device, dtype=torch.float16).contiguous()
 
 
+def prepare_region_masks(region_masks, h: int, w: int, device) -> torch.Tensor:
+    """The subject masks of a joint pass on the latent grid: a list of G masks ([H,W] / [1,H,W], one per subject, the same for every row) or a [G,H,W] /
+    [B,G,H,W] array -> [B or 1, G, h, w] fp16 in {0,1}, each mask through `prepare_mask`."""
+    if isinstance(region_masks, (list, tuple)):
+        if not region_masks:
+            raise ValueError("region_masks is empty")
+        return torch.cat([prepare_mask(torch.as_tensor(m).reshape(1, 1, *torch.as_tensor(m).shape[-2:]), h, w, device) for m in region_masks], 1)
+    m = torch.as_tensor(region_masks)
+    if m.ndim == 3:
+        m = m[None]
+    if m.ndim != 4:
+        raise ValueError(f"region_masks must be a list of masks, [G,H,W] or [B,G,H,W]; got shape {tuple(m.shape)}")
+    B, G = m.shape[:2]
+    return prepare_mask(m.reshape(B * G, 1, *m.shape[2:]), h, w, device).reshape(B, G, h, w)
+
+
+def union_mask(regions: torch.Tensor) -> torch.Tensor:
+    """[B, G, h, w] region weights -> the blend mask [B, 1, h, w] of a joint pass: the element-wise maximum of the subject masks"""
+    return regions.amax(1, keepdim=True)
+
+
 def _is_pil(x) -> bool:
     if isinstance(x, list):
         return len(x) > 0 and all(_is_pil(i) for i in x)
@@ -60,8 +81,12 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                  output_type="pil", return_dict=True, callback=None, callback_steps=1, cross_attention_kwargs=None,
-                 guidance_rescale: float = 0.0, original_size=None, crops_coords_top_left=(0, 0), target_size=None, noise_seed=None, noise_draw=None, **unused):
-        """`latents` = clean image latents (scaled) instead of `image`; `noise` = the start / re-noising noise instead of drawing it
+                 guidance_rescale: float = 0.0, original_size=None, crops_coords_top_left=(0, 0), target_size=None, noise_seed=None, noise_draw=None,
+                 region_masks=None, **unused):
+        """`region_masks` (a list of G subject masks, [G,H,W] or [B,G,H,W]): a JOINT subject pass -- the last 4 G rows of the prompt embeddings are G groups of
+        four image tokens, group g acts where mask g says (`prepare_region_masks`; the UNet's `ip_adapter_masks`), and the blend mask is the element-wise maximum
+        of the subject masks unless `mask_image` is given too (then the blend keeps to `mask_image`). Both classifier-free-guidance rows carry the same masks.
+        `latents` = clean image latents (scaled) instead of `image`; `noise` = the start / re-noising noise instead of drawing it
         from `generator` (conveniences for tests and latent-space callers, as in img2img.py).
         `noise_seed` (an int, or one per batch element; None: `generator` as ever): the noise is drawn on the device from the request's own stream (noise.py:
         draw id `noise_draw`, default DRAW_INPAINT, the first subject pass). A supplied `noise` wins over the seed, the seed over `generator`."""
@@ -69,7 +94,7 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if guidance_rescale != 0.0 or eta != 0.0:
             raise NotImplementedError("guidance_rescale / eta are inactive on the reference's path")
-        if mask_image is None:
+        if mask_image is None and region_masks is None:
             raise ValueError("`mask_image` input cannot be undefined.")
         self._check_embeds(prompt, prompt_embeds, pooled_prompt_embeds)
         self._check_output_type(output_type)
@@ -91,7 +116,13 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
         B, _, h, w = image_latents.shape
         if self.vae is not None and _is_pil(mask_image):                   # PIL mask: mask_processor (resize, grayscale, binarise at 0.5)
             mask_image = self.mask_processor.preprocess(mask_image, height=h * self.vae_scale_factor, width=w * self.vae_scale_factor)
-        mask = prepare_mask(mask_image, h, w, dev)
+        regions = None
+        if region_masks is not None:
+            regions = prepare_region_masks(region_masks, h, w, dev)
+            if regions.shape[0] not in (1, B):
+                raise ValueError(f"region_masks carry {regions.shape[0]} rows for a batch of {B}")
+            regions = regions.expand(B, -1, -1, -1)
+        mask = prepare_mask(mask_image, h, w, dev) if mask_image is not None else union_mask(regions).contiguous()
         if mask.shape[0] != B:
             mask = mask.expand(B, -1, -1, -1).contiguous()
         noise, = _noise.resolve_noises([noise], [image_latents.shape], [noise_seed], [_noise.DRAW_INPAINT if noise_draw is None else noise_draw], dev, generator)
@@ -108,6 +139,8 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
         neg = (expand_rows(negative_prompt_embeds, B), expand_rows(negative_pooled_prompt_embeds, B)) if do_cfg else ()
         prompt_embeds, added = conditioning(dev, expand_rows(prompt_embeds, B), expand_rows(pooled_prompt_embeds, B), add_time_ids, *neg)
 
+        if regions is not None:
+            cross_attention_kwargs = dict(cross_attention_kwargs or {}, ip_adapter_masks=(torch.cat([regions, regions], 0) if do_cfg else regions).contiguous())
         model_in = torch.cat([x, x], dim=0) if do_cfg else x.clone()
         eps = torch.empty_like(model_in)
         stepped = torch.empty_like(x)
@@ -129,10 +162,19 @@ class StableDiffusionXLInpaintPipeline(_PipelineBase):
         return StableDiffusionXLPipelineOutput(images=image_out) if return_dict else (image_out,)
 
 
-def subject_consistency(subject_data, latents, ip_adapter_xl_inpaint, subject_strength: float = 0.7, **generate_kwargs):
+def subject_consistency(subject_data, latents, ip_adapter_xl_inpaint, subject_strength: float = 0.7, joint: bool = False, **generate_kwargs):
     """The per-subject loop of reference gdino/lib.py:85-103 on given masks: `subject_data` = [(mask, subject embedding)], each pass
     re-paints the masked region guided by the subject's 'local' image tokens (50 steps, IP scale 0.8). With `noise_seed=` among the keywords, pass k
-    draws its noise from draw id DRAW_INPAINT + k of that seed (unless `noise=` is supplied, which wins)."""
+    draws its noise from draw id DRAW_INPAINT + k of that seed (unless `noise=` is supplied, which wins).
+    `joint=True`: ONE pass for all subjects -- every subject's tokens in one context, each acting under its own mask, the blend under the union of the masks,
+    one noise (draw id DRAW_INPAINT + 0). This is NOT the serial result: serially, pass k + 1 starts from the repaint of pass k and draws its own noise;
+    jointly, all subjects are repainted from the same start under one noise."""
+    if joint and len(subject_data):
+        if generate_kwargs.get("noise_seed") is not None:
+            generate_kwargs["noise_draw"] = _noise.inpaint_draw(0)
+        embs = torch.stack([emb.reshape(-1) for _, emb in subject_data])
+        return ip_adapter_xl_inpaint.generate(latents=latents, mask_image=[m for m, _ in subject_data], pil_image=None, strength=subject_strength,
+                                              clip_image_embeds_local=embs, mode="local", joint=True, num_inference_steps=50, scale=0.8, **generate_kwargs)
     subject = latents
     for k, (msk, emb) in enumerate(subject_data):
         if generate_kwargs.get("noise_seed") is not None:
@@ -143,13 +185,14 @@ def subject_consistency(subject_data, latents, ip_adapter_xl_inpaint, subject_st
     return subject
 
 
-def subject_consistency_from_boxes(subject_data, latents, ip_adapter_xl_inpaint, segmenter, boxes, phrases, vae, subject_strength: float = 0.7, **generate_kwargs):
+def subject_consistency_from_boxes(subject_data, latents, ip_adapter_xl_inpaint, segmenter, boxes, phrases, vae, subject_strength: float = 0.7, joint: bool = False,
+                                   **generate_kwargs):
     """Reference gdino/lib.py:69-103 on given detector output: `subject_data` = [(phrase, subject embedding)], `boxes` cxcywh in [0, 1] [n, 4] with their
     `phrases`. The current result is decoded through `vae` once and set as the segmenter's image (:73); per subject the phrase loses '.' and "'s" (:86), its
     mask is `get_mask(..., d=40, b=20)` (:87) and the inpaint pass of `subject_consistency` follows. Boxes are scaled by the decoded image's longer side
     (the reference's literal 1024 is the side of the images it generates). -> (latents, masks as PIL images)"""
     pairs, masks = subject_masks_from_boxes(subject_data, latents, segmenter, boxes, phrases, vae)
-    return subject_consistency(pairs, latents, ip_adapter_xl_inpaint, subject_strength, **generate_kwargs), masks
+    return subject_consistency(pairs, latents, ip_adapter_xl_inpaint, subject_strength, joint=joint, **generate_kwargs), masks
 
 
 def subject_masks_from_boxes(subject_data, latents, segmenter, boxes, phrases, vae):

@@ -49,12 +49,11 @@ class ImageProjModel(nn.Module):
         bs = image_embeds.shape[0]
         D, T = self.cross_attention_dim, self.clip_extra_context_tokens
         x = image_embeds.to(dtype=torch.float16).reshape(bs * self.num_crops, -1).contiguous()
-        if bs * self.num_crops > 16:
-            raise ValueError("ImageProjModel: at most 8 requests per call")
         w, b = self.proj.weight.to(torch.float16).contiguous(), self.proj.bias.to(torch.float16).contiguous()
         y = torch.empty(bs * self.num_crops, T * D, dtype=torch.float16, device=x.device)
-        _ffi.check(L.ia2p_linear_small(_ffi.current_stream(), _ffi.ptr(x), _ffi.ptr(w), _ffi.ptr(b), _ffi.ptr(y),
-                                       bs * self.num_crops, T * D, x.shape[1], 0, 0))
+        for r0 in range(0, bs * self.num_crops, 16):      # the skinny linear holds 16 rows per launch (a joint subject pass brings up to 16 subjects x 2 crops)
+            rows = min(16, bs * self.num_crops - r0)
+            _ffi.check(L.ia2p_linear_small(_ffi.current_stream(), _ffi.ptr(x[r0:r0 + rows]), _ffi.ptr(w), _ffi.ptr(b), _ffi.ptr(y[r0:r0 + rows]), rows, T * D, x.shape[1], 0, 0))
         t = y.float().reshape(bs, self.num_crops, T, D)
         g = t[:, 0:1]
         loc = g * (1 - scales[1]) + t[:, 1:] * scales[1]                     # :49
@@ -172,8 +171,11 @@ class IPAdapterXL(IPAdapter):
     def generate(self, pil_image=None, prompt=None, negative_prompt=None, scale=1.0, scale_g=1.0, scale_l=0.5, num_samples=1,
                  seed=None, num_inference_steps=30, pil_image_local=None, clip_image_embeds_local=None, clip_image_embeds=None,
                  mode="global", prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
-                 negative_pooled_prompt_embeds=None, noise_seed=None, noise_draw=None, **kwargs):
-        """`seed` builds the torch generator the pipeline draws from, as in the reference. `noise_seed` / `noise_draw` go through to a pipeline that draws noise
+                 negative_pooled_prompt_embeds=None, noise_seed=None, noise_draw=None, joint=False, **kwargs):
+        """`joint=True` (with mode="local", `clip_image_embeds_local` [S, D] and `mask_image` a list of S masks): ONE inpainting loop for S subjects. The S
+        embeddings go through `get_image_embeds` once and become [1, 4 S, ctx] conditional tokens (the zero-embedding tokens, repeated, for the unconditional
+        row); the masks reach the pipeline as `region_masks` -- token group s acts where mask s says, the blend runs under their union.
+        `seed` builds the torch generator the pipeline draws from, as in the reference. `noise_seed` / `noise_draw` go through to a pipeline that draws noise
         of its own (the inpainting pipeline): the request's Philox stream and the draw id in it (noise.py); they win over the generator.
         `known_trajectory=` / `edit_mask=` (an edit inside a mask, ddim.py) reach the pipeline with the other keywords."""
         if noise_seed is not None:
@@ -181,6 +183,14 @@ class IPAdapterXL(IPAdapter):
         self.set_scale(scale)
         image_prompt_embeds, uncond_image_prompt_embeds = self.get_image_embeds(
             pil_image, clip_image_embeds, pil_image_local, clip_image_embeds_local, mode=mode, scale_g=scale_g, scale_l=scale_l)
+        if joint:
+            masks = kwargs.pop("mask_image", None)
+            S = image_prompt_embeds.shape[0]
+            if mode != "local" or masks is None or not isinstance(masks, (list, tuple)) or len(masks) != S or not 1 <= S <= 16:
+                raise ValueError(f"joint=True takes mode='local', clip_image_embeds_local [S, D] and mask_image as a list of S masks, 1 <= S <= 16 (got {S} embeddings)")
+            image_prompt_embeds = image_prompt_embeds.reshape(1, S * image_prompt_embeds.shape[1], -1)
+            uncond_image_prompt_embeds = uncond_image_prompt_embeds.reshape(1, S * uncond_image_prompt_embeds.shape[1], -1)
+            kwargs["region_masks"] = list(masks)
         bs_embed, seq_len, _ = image_prompt_embeds.shape
         image_prompt_embeds = image_prompt_embeds.repeat(1, num_samples, 1).view(bs_embed * num_samples, seq_len, -1)
         uncond_image_prompt_embeds = uncond_image_prompt_embeds.repeat(1, num_samples, 1).view(bs_embed * num_samples, seq_len, -1)

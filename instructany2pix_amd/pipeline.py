@@ -662,7 +662,7 @@ class InstructAny2PixPipeline:
 
     def edit_batch(self, insts, mm_datas, *, alpha=0.7, h=(0.0, 0.4, 1.0), norm=20.0, refinement=0.5, num_inference_steps=25, subject_strength=0.0, cfg=10,
                    scale=1.0, output_type="latent", debug=False, group: int = 4, shard: bool = True, seeds=None, edit_masks=None, edit_feather=8, auto_masks=None,
-                   lora_scale=None, samplers=None, sample_steps=None, sample_adapters=None):
+                   lora_scale=None, samplers=None, sample_steps=None, sample_adapters=None, subject_modes=None):
         """`__call__` for N instructions on N images -> the list of its `(non_refined, oo, msg)` tuples, in request order. Every knob of `__call__` is a
         scalar (for all requests) or a list of N (`h`: one triple or N triples). `group` requests share one launch sequence in every loop.
 
@@ -718,19 +718,26 @@ class InstructAny2PixPipeline:
         after the same inversion and mixing. A group holds one sampler; a call that mixes them runs the DDIM requests' groups, then the LCM requests'. The step
         noise: the conditioner's `step_noise`, else draw 65537 of the request's seed inside the update launch, else host draws right after the request's own
         polar-mixing draw. LCM requests with cfg <= 1 run without guidance (all LCM requests of a call must agree on that). `sample_adapters` (ONE value per
-        call: a name, a list or (names, weights)): LoRA adapters active around the guided sampling loops only."""
+        call: a name, a list or (names, weights)): LoRA adapters active around the guided sampling loops only.
+
+        Subject passes (`subject_modes`: "serial", "joint" or a list of N; None: serial, as ever). A "joint" request repaints ALL its subjects in one inpaint
+        stage -- every subject's image tokens in one context, each acting under its own mask (regional image prompts, `ia2p_attention_regions`), the blend
+        under the union of the masks, one noise (draw DRAW_INPAINT + 0) -- so S subjects cost one loop instead of S. It is NOT the serial result: serially,
+        pass k + 1 starts from the repaint of pass k and draws its own noise; jointly, all subjects are repainted from the same start under one noise. The
+        joint requests of a call share groups (padded to the group's largest subject count, which changes no bit of a row); the serial ones keep their bits."""
         from .batch import edit_batch
         return edit_batch(self, insts, mm_datas, **({} if lora_scale is None else dict(lora_scale=lora_scale)), alpha=alpha, h=h, norm=norm, refinement=refinement, num_inference_steps=num_inference_steps,
                           subject_strength=subject_strength, cfg=cfg, scale=scale, output_type=output_type, debug=debug, group=group, shard=shard, seeds=seeds,
                           **({} if edit_masks is None else dict(edit_masks=edit_masks)), **({} if auto_masks is None else dict(auto_masks=auto_masks)),
                           **({} if edit_masks is None and auto_masks is None else dict(edit_feather=edit_feather)),
                           **({} if samplers is None else dict(samplers=samplers)), **({} if sample_steps is None else dict(sample_steps=sample_steps)),
-                          **({} if sample_adapters is None else dict(sample_adapters=sample_adapters)))
+                          **({} if sample_adapters is None else dict(sample_adapters=sample_adapters)), **({} if subject_modes is None else dict(subject_modes=subject_modes)))
 
     # ---- reference keyword surface ----------------------------------------------------------------------------------
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
                  use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None,
-                 edit_mask=None, edit_feather=8, *, auto_mask=None, lora_scale=None, sampler=None, sample_steps=None, sample_adapters=None) -> Any:
+                 edit_mask=None, edit_feather=8, *, auto_mask=None, lora_scale=None, sampler=None, sample_steps=None, sample_adapters=None,
+                 subject_mode="serial") -> Any:
         """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
         `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images).
         `seed` (a 64-bit unsigned integer; None: every draw from the global CPU generator, as ever): every normal draw of the request comes from its own
@@ -760,13 +767,19 @@ class InstructAny2PixPipeline:
         call (`set_adapters` / `load_lora_weights`); the state before is put back afterwards, also when the call raises.
         `sampler`, `sample_steps`, `sample_adapters` (keyword only; None: nothing changes, no launch, no draw, no bit): the few-step consistency sampler for the
         guided sampling stage, and LoRA adapters active around that stage only (`denoise`). The conditioner may supply `step_noise`, which wins
-        over the seed (draw 65537 of it), which wins over the global generator. The refiner and the subject passes are untouched."""
+        over the seed (draw 65537 of it), which wins over the global generator. The refiner and the subject passes are untouched.
+        `subject_mode` (keyword only; "serial": as ever, one inpainting loop per subject as the reference runs them): "joint" repaints all subjects in ONE
+        loop -- every subject's image tokens in one context, each under its own mask, the blend under the union of the masks, one noise (draw
+        DRAW_INPAINT + 0 of a seeded request). "joint" is NOT the serial result: in the serial form later passes see earlier repaints and draw their own
+        noise; in the joint form all subjects are repainted from the same start under one noise."""
+        if subject_mode not in ("serial", "joint"):
+            raise ValueError(f"subject_mode: 'serial' or 'joint', got {subject_mode!r}")
         if lora_scale is not None:
             with self.lora_scaled(lora_scale):
                 return self(inst, mm_data, alpha=alpha, h=h, norm=norm, refinement=refinement, llm_only=llm_only, num_inference_steps=num_inference_steps,
                             use_cache=use_cache, debug=debug, diffusion_mode=diffusion_mode, subject_strength=subject_strength, cfg=cfg, scale=scale,
                             output_type=output_type, seed=seed, edit_mask=edit_mask, edit_feather=edit_feather, auto_mask=auto_mask, sampler=sampler,
-                            sample_steps=sample_steps, sample_adapters=sample_adapters)
+                            sample_steps=sample_steps, sample_adapters=sample_adapters, subject_mode=subject_mode)
         if seed is not None:
             seed = _noise.check_seed(seed)
         few, smp = {}, "ddim"
@@ -841,7 +854,7 @@ class InstructAny2PixPipeline:
         subject_data = c.get("subject_data") or []
         if subject_strength > 0 and len(subject_data) > 0:                                     # :363-368
             _need(c, SUBJECT_KEYS, "subject-consistency pass")
-            kw = dict(output_type="latent", **embeds(c, "subject_"), noise=c.get("subject_noise"))
+            kw = dict(output_type="latent", **embeds(c, "subject_"), noise=c.get("subject_noise"), **({"joint": True} if subject_mode == "joint" else {}))
             if seed is not None:
                 kw["noise_seed"] = seed                                                        # pass k draws from DRAW_INPAINT + k (inpaint.subject_consistency)
             by_phrase = [isinstance(k, str) for k, _ in subject_data]

@@ -194,16 +194,83 @@ class HipUNet2DConditionModel(_ffi.Executor):
             self._ws_key = key
         return self._ws
 
+    def workspace_for_regions(self, B: int, h: int, w: int, L: int, G: int) -> torch.Tensor:
+        """the workspace of a regional forward (`ia2p_workspace_bytes_r`: the plain pass's plus the mask pyramid)"""
+        key = (B, h, w, L, self._ip_sig[:3] if self._ip_sig else None, self._lib.ia2p_plan_generation(), "regions", G)
+        if self._ws_key != key:
+            self.workspace(self._lib.ia2p_workspace_bytes_r(self._ctx, B, h, w, L, G))
+            self._ws_key = key
+        return self._ws
+
+    def _call_regions(self, masks, sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict, out, ip_scales):
+        """cross_attention_kwargs={"ip_adapter_masks": masks}: `ia2p_unet_forward_r`. The installed adapter's token count becomes 4 G for this call and is put back
+        afterwards; context K/V cached under the other count are not reused (`_context_kv` keys them by it)."""
+        self._sync_processors()
+        if self._ip_sig is None or self._ip_sig[0] != "on":
+            raise ValueError("ip_adapter_masks needs the IP-Adapter processors installed (set_attn_processor / load_ip_adapter_weights)")
+        B, c_in, h, w = sample.shape
+        m = torch.as_tensor(masks)
+        if m.ndim == 3:
+            m = m.unsqueeze(0).expand(B, *m.shape)
+        if m.ndim != 4 or m.shape[0] != B or tuple(m.shape[2:]) != (h, w) or not 1 <= m.shape[1] <= 16:
+            raise ValueError(f"ip_adapter_masks must be [B, G, h, w] or [G, h, w] on the latent grid {h} x {w} of `sample`, 1 <= G <= 16; got {tuple(m.shape)}")
+        G = int(m.shape[1])
+        m = m.to(device=self.device, dtype=torch.float16).contiguous()
+        f16 = lambda t: t.to(device=self.device, dtype=torch.float16).contiguous()      # noqa: E731
+        ctx_in = encoder_hidden_states
+        sample, ctx = f16(sample), f16(encoder_hidden_states)
+        te, tid = f16(added_cond_kwargs["text_embeds"]), f16(added_cond_kwargs["time_ids"])
+        if c_in != self.config.in_channels or ctx.shape[0] != B or ctx.shape[2] != self.config.cross_attention_dim:
+            raise ValueError(f"sample must have {self.config.in_channels} channels and encoder_hidden_states be [B, L, {self.config.cross_attention_dim}]")
+        L = ctx.shape[1]
+        if L <= 4 * G:
+            raise ValueError(f"encoder_hidden_states holds {L} rows: {G} regions need {4 * G} image-token rows behind the text rows")
+        ts = timestep if torch.is_tensor(timestep) else torch.full((B,), float(timestep))
+        ts = ts.to(device=self.device, dtype=torch.float32).reshape(-1)
+        ts = (ts.expand(B) if ts.numel() == 1 else ts).contiguous()
+        if ts.numel() != B:
+            raise ValueError(f"timestep tensor has {ts.numel()} elements for a batch of {B}")
+        sc = None
+        if ip_scales is not None:
+            sc = torch.as_tensor(ip_scales).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+            if sc.numel() != B:
+                raise ValueError(f"ip_scales has {sc.numel()} elements for a batch of {B}")
+        if out is None:
+            out = torch.empty(B, self.config.out_channels, h, w, dtype=torch.float16, device=self.device)
+        sig = self._ip_sig
+        try:
+            if sig[2] != 4 * G:
+                _ffi.check(self._lib.ia2p_set_ip_adapter(self._ctx, 1, 4 * G, sig[1]), self._ctx)
+                self._ip_sig = sig[:2] + (4 * G,) + sig[3:]
+            ws = self.workspace_for_regions(B, h, w, L, G)
+            kv = self._context_kv(ctx_in, ctx, B, L, ws) if self.cache_context_kv else None
+            _ffi.check(self._lib.ia2p_unet_forward_r(self._ctx, _ffi.current_stream(), _ffi.ptr(sample), _ffi.ptr(ts), _ffi.ptr(sc) if sc is not None else None,
+                                                     None if kv is not None else _ffi.ptr(ctx), _ffi.ptr(kv) if kv is not None else None, L, _ffi.ptr(te), _ffi.ptr(tid),
+                                                     _ffi.ptr(out), B, h, w, _ffi.ptr(ws), ws.numel(), _ffi.ptr(m), G), self._ctx)
+        finally:
+            if self._ip_sig is not sig:
+                self._ip_sig = sig
+                _ffi.check(self._lib.ia2p_set_ip_adapter(self._ctx, 1, sig[2], sig[1]), self._ctx)
+        return (out,) if not return_dict else SimpleNamespace(sample=out)
+
     def __call__(self, sample, timestep, encoder_hidden_states=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                  return_dict: bool = False, out: Optional[torch.Tensor] = None, _tune_reps: Optional[int] = None,
                  ip_scales: Optional[torch.Tensor] = None, **unused):
-        """`timestep`: a number / 0-dim tensor as the reference passes it, or a [B] tensor -- one timestep per batch element, as diffusers' UNet
+        """cross_attention_kwargs={"ip_adapter_masks": t} (t [B, G, h, w] on the latent grid of `sample`, or [G, h, w] for every row): regional image prompts -- the
+        last 4 G rows of the context are G groups of four image tokens, group g acts where t[:, g] says (diffusers' `ip_adapter_masks`; `ia2p_unet_forward_r`).
+        `timestep`: a number / 0-dim tensor as the reference passes it, or a [B] tensor -- one timestep per batch element, as diffusers' UNet
         accepts (`ia2p_unet_forward_v`); `ip_scales` (or cross_attention_kwargs={"ip_scales": ...}): optional [B] tensor, the IP-Adapter scale of
         every batch element (the reference sets one value per call, ip_adapter.py:211-214). Both let independent requests share one evaluation."""
         if encoder_hidden_states is None or added_cond_kwargs is None:
             raise ValueError("encoder_hidden_states and added_cond_kwargs (text_embeds, time_ids) are required (text_time UNet)")
         if "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
             raise ValueError("added_cond_kwargs must carry `text_embeds` and `time_ids`")      # diffusers raises ValueError here too
+        if cross_attention_kwargs and cross_attention_kwargs.get("ip_adapter_masks") is not None:
+            if _tune_reps is not None:
+                raise ValueError("autotune takes no ip_adapter_masks")
+            if ip_scales is None:
+                ip_scales = cross_attention_kwargs.get("ip_scales")
+            return self._call_regions(cross_attention_kwargs["ip_adapter_masks"], sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict, out, ip_scales)
         self._sync_processors()
         B, c_in, h, w = sample.shape
         if c_in != self.config.in_channels:

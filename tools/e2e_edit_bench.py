@@ -52,7 +52,15 @@ repeat in the one process: serial, serial lcm, edit_batch, edit_batch lcm. --ste
 N evaluations against --steps. Its table gains the two update launches ALONE (`ia2p_ddim_step_v`, `ia2p_lcm_step_v` with every row seeded, guided, B = 1 and B = 8
 on 4 x PX/8 x PX/8 latents), measured like the seeded-noise launches of --seeded. Synthetic weights: the figures are times, the images mean nothing.
 
-    python tools/e2e_edit_bench.py --lcm 4 --batch 1,4"""
+    python tools/e2e_edit_bench.py --lcm 4 --batch 1,4
+
+--subjects 1,2,4 [--subject-mode serial,joint] times the SUBJECT-CONSISTENCY STAGE of one full-size request alone (`inpaint.subject_consistency` on PX/8 x PX/8
+latents: 50 steps at strength 0.7 = 35 UNet evaluations of 2 rows per loop, IP scale 0.8, guidance 7.5): for each S, the serial form (S loops) and the joint form
+(one loop under regional image prompts, `ia2p_unet_forward_r`) alternate --reps times after both have run once untimed; a host clock around a device synchronise.
+Only the base UNet and the IP-Adapter are built. Printed per S: ms per stage of both (median, min..max), serial / joint, and ms per UNet step of the regional route
+against the plain one (stage time over the loop's steps; the image-token projection and the start launch are in it).
+
+    python tools/e2e_edit_bench.py --subjects 1,2,4 --subject-mode serial,joint"""
 import argparse
 import os
 import sys
@@ -88,6 +96,8 @@ _ap.add_argument("--seeded", action="store_true", help="with --batch: the same r
 _ap.add_argument("--edit-mask", action="store_true", help="with --batch: the same requests with a centred half-area edit mask next to the unmasked run")
 _ap.add_argument("--auto-mask", type=int, nargs="?", const=8, default=None, metavar="N_MAPS", help="with --batch: the same requests with an automatic edit mask of N_MAPS maps next to the run without")
 _ap.add_argument("--lcm", type=int, default=None, metavar="N", help="with --batch: the same requests sampled by the N-step consistency sampler next to the DDIM run, and the two update launches alone")
+_ap.add_argument("--subjects", default=None, help="comma-separated subject counts: time the subject-consistency stage of one request alone (see the module docstring)")
+_ap.add_argument("--subject-mode", default="serial,joint", help="with --subjects: the forms to time, interleaved")
 _ap.add_argument("--steps", type=int, default=25)
 _ap.add_argument("--refinement", type=float, default=0.5)
 ARGS = _ap.parse_args()
@@ -106,6 +116,51 @@ t_all = time.perf_counter()
 bcfg, rcfg, vcfg = sdxl_base(), sdxl_refiner(), sdxl_vae()
 base = HipUNet2DConditionModel(bcfg, DEV); base.load_state_dict(iter_synthetic(unet_param_specs(bcfg), 7, DEV, torch.float16))
 ref = HipUNet2DConditionModel(rcfg, DEV); ref.load_state_dict(iter_synthetic(unet_param_specs(rcfg), 11, DEV, torch.float16))
+if ARGS.subjects:
+    import statistics
+    from instructany2pix_amd.inpaint import StableDiffusionXLInpaintPipeline, subject_consistency
+    from instructany2pix_amd.ip_adapter import IPAdapterXL
+    specs = ip_adapter_specs(bcfg, 1024)
+    ipa = IPAdapterXL(StableDiffusionXLInpaintPipeline(base), "", ip_ckpt={"image_proj": synthetic_state_dict(specs["image_proj"], seed=7),
+                                                                          "ip_adapter": synthetic_state_dict(specs["ip_adapter"], seed=7)}, device=DEV, clip_embeddings_dim=1024)
+    print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter)", flush=True)
+    gg = torch.Generator().manual_seed(3)
+    rn = lambda *sh: torch.randn(*sh, generator=gg)      # noqa: E731
+    hl = PX // 8
+    emb = dict(prompt_embeds=rn(1, 77, bcfg.cross_attention_dim).half(), pooled_prompt_embeds=rn(1, bcfg.pooled_dim).half(),
+               negative_prompt_embeds=rn(1, 77, bcfg.cross_attention_dim).half(), negative_pooled_prompt_embeds=rn(1, bcfg.pooled_dim).half())
+    lat, noise = rn(1, 4, hl, hl).half().to(DEV), rn(1, 4, hl, hl).half().to(DEV)
+    modes = ARGS.subject_mode.split(",")
+    assert all(m in ("serial", "joint") for m in modes)
+    STEPS = 35      # 50 steps at strength 0.7
+    print(f"# {PX} x {PX}, subject stage alone: 50 steps at strength 0.7 = {STEPS} UNet evaluations of 2 rows per loop; {ARGS.reps} alternating repeats after one untimed run of each", flush=True)
+    for S in (int(n) for n in ARGS.subjects.split(",")):
+        data = []
+        for k in range(S):      # S overlapping pixel-space rectangles, each about a quarter of the image
+            mk = torch.zeros(PX, PX)
+            y0, x0 = (PX // 8) * (k % 4), (PX // 8) * ((k // 2) % 4)
+            mk[y0:y0 + PX // 2, x0:x0 + PX // 2] = 1.0
+            data.append((mk, rn(1024)))
+
+        def stage(mode):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            out = subject_consistency(data, lat, ipa, 0.7, joint=mode == "joint", output_type="latent", noise=noise, **emb)
+            torch.cuda.synchronize()
+            assert out.shape == lat.shape and bool(torch.isfinite(out.float()).all())
+            return (time.perf_counter() - t0) * 1e3
+
+        for m in modes:
+            stage(m)
+        ms = {m: [] for m in modes}
+        for _ in range(ARGS.reps):
+            for m in modes:
+                ms[m].append(stage(m))
+        med = {m: statistics.median(v) for m, v in ms.items()}
+        line = f"S = {S}: " + ", ".join(f"{m} {med[m]:.1f} ms (min {min(v):.1f}, max {max(v):.1f})" for m, v in ms.items())
+        if len(med) == 2:
+            line += f"; serial / joint {med['serial'] / med['joint']:.3f}; ms per UNet step: plain route {med['serial'] / (S * STEPS):.2f}, regional route {med['joint'] / STEPS:.2f}"
+        print(line, flush=True)
+    sys.exit(0)
 vae = HipAutoencoderKL(vcfg, DEV); vae.load_state_dict(iter_synthetic(vae_param_specs(vcfg), 5, DEV, torch.float16))
 c1, c2 = sdxl_text_encoder(), sdxl_text_encoder_2()
 te1 = HipCLIPTextModel(c1, DEV); te1.load_state_dict(iter_synthetic(clip_param_specs(c1), 7, DEV, torch.float16))
