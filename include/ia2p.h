@@ -138,6 +138,75 @@ ia2p_status ia2p_unet_forward_r(ia2p_ctx* ctx, void* stream, const void* sample,
                                 const void* context, const void* kv, int L, const void* text_embeds, const void* time_ids, void* out,
                                 int B, int h, int w, void* workspace, size_t workspace_bytes, const void* region_masks, int G);
 
+/* ---- ControlNet: structure-guided sampling (diffusers 0.26.3 ControlNetModel + StableDiffusionXLControlNetPipeline) ---------------------------------------------------
+ * New: the reference attaches no ControlNet (pipeline.py), it only prepares the attention seam -- IPAdapter.set_ip_adapter installs CNAttnProcessor on `pipe.controlnet`
+ * when the pipe has one (diffusion/ip_adapter/ip_adapter.py:143-148), and CNAttnProcessor2_0 (attention_processor.py:481-568) cuts the image tokens off the context
+ * (`encoder_hidden_states[:, :end_pos]`, :530-531). diffusers is not installed next to this library: parity with it is restated in tests/controlnet_ref.py, not pinned.
+ *
+ * A ControlNet is the UNet's conv_in, embeddings, down path and mid block under a second set of weights (same state-dict keys), plus
+ *   controlnet_cond_embedding.{conv_in, blocks.0..5, conv_out}   eight 3x3 convolutions (pad 1, bias) over the condition image, RGB in [0, 1], [B, 3, 8 h, 8 w]:
+ *       silu(conv_in 3 -> c0); for i < 3: silu(blocks[2 i]: c_i -> c_i, stride 1), silu(blocks[2 i + 1]: c_i -> c_(i+1), stride 2); conv_out c3 -> block_out_channels[0]
+ *   controlnet_down_blocks.k, controlnet_mid_block               1x1 "zero" convolutions, one per skip of the down path (skip order) and one for the mid block's output
+ * Forward: x = conv_in(sample) + cond_embedding; embeddings, down path and mid block exactly the UNet's, on the TEXT rows of the context only (L - num_tokens rows);
+ *   residual_k = fp16(scale_b * fp16(zero_conv_k(skip_k))), the mid residual likewise. The UNet adds residual_k to skip_k after the whole down path has run (the hidden
+ *   state flowing down is the unmodified one) and the mid residual to the mid block's output: skip' = fp16(skip + residual).
+ * Handle lifecycle as every executor's: create -> arena_bytes -> bind_arena -> load_tensor per key -> finalize_weights (checks exactly the key set above) -> queries,
+ * embed once per request, forward per step. The handle is an ia2p_ctx of its own kind: the UNet entry points refuse it and the other way round (IA2P_ERR_STATE). */
+typedef struct {
+  ia2p_unet_config unet;                          /* block_out_channels, layers_per_block, cross_attention_dim as the UNet it guides; transformer_layers_per_block may differ */
+  int conditioning_channels;                      /* 3 */
+  int conditioning_embedding_out_channels[4];     /* (16, 32, 96, 256): multiples of 16 in 16 .. 256 */
+} ia2p_controlnet_config;
+ia2p_status ia2p_controlnet_create(const ia2p_controlnet_config* cfg, ia2p_ctx** out);
+void ia2p_controlnet_destroy(ia2p_ctx* ctx);
+const char* ia2p_controlnet_last_error(ia2p_ctx* ctx);
+size_t ia2p_controlnet_arena_bytes(ia2p_ctx* ctx);
+ia2p_status ia2p_controlnet_bind_arena(ia2p_ctx* ctx, void* dev_arena, size_t bytes);
+ia2p_status ia2p_controlnet_load_tensor(ia2p_ctx* ctx, const char* key, const void* dev_src, const int64_t* shape, int ndim, void* stream);
+ia2p_status ia2p_controlnet_finalize_weights(ia2p_ctx* ctx);
+/* the contexts handed to this ControlNet end in `num_tokens` image-token rows it must not see (0: none; CNAttnProcessor's rule) */
+ia2p_status ia2p_controlnet_set_image_tokens(ia2p_ctx* ctx, int num_tokens);
+/* IA2P_OK when the residuals of `ctx` fit the skips of `unet` (block_out_channels, layers_per_block, in_channels, cross_attention_dim), else IA2P_ERR_SHAPE */
+ia2p_status ia2p_controlnet_check_unet(ia2p_ctx* ctx, ia2p_ctx* unet);
+int ia2p_controlnet_num_residuals(ia2p_ctx* ctx);                   /* skips + 1 (the mid residual is the last) */
+/* the residual buffer of a forward at (B, h, w): its bytes (0 on a bad shape); offsets (elements), channels and grid of residual k, arrays of num_residuals or NULL.
+ * Residual k is channels-last [B * hs[k] * ws[k], channels[k]], dense, back to back. */
+size_t ia2p_controlnet_residual_layout(ia2p_ctx* ctx, int B, int h, int w, int64_t* offsets, int* channels, int* hs, int* ws);
+/* condition embedding: image fp16 NCHW [B, conditioning_channels, 8 h, 8 w] -> out [B * h * w, block_out_channels[0]] channels-last (ia2p_controlnet_embed_bytes).
+ * Depends on the image and the weights only: once per request. Workspace: ia2p_controlnet_embed_workspace_bytes. */
+size_t ia2p_controlnet_embed_bytes(ia2p_ctx* ctx, int B, int h, int w);
+size_t ia2p_controlnet_embed_workspace_bytes(ia2p_ctx* ctx, int B, int h, int w);
+ia2p_status ia2p_controlnet_embed(ia2p_ctx* ctx, void* stream, const void* image, int B, int h, int w, void* out, size_t out_bytes, void* workspace, size_t workspace_bytes);
+size_t ia2p_controlnet_workspace_bytes(ia2p_ctx* ctx, int B, int h, int w, int L);
+size_t ia2p_controlnet_context_kv_bytes(ia2p_ctx* ctx, int B, int L);
+ia2p_status ia2p_controlnet_project_context(ia2p_ctx* ctx, void* stream, const void* context, int L, int B, void* kv, size_t kv_bytes, void* workspace, size_t workspace_bytes);
+/* one evaluation: the arguments of ia2p_unet_forward_v (timesteps device float [B]; exactly one of context [B, L, cross_attention_dim] / kv), cond = the embedded
+ * condition, scales = device float [B] (conditioning_scale of batch element b). Writes num_residuals tensors into `residuals` (ia2p_controlnet_residual_layout). */
+ia2p_status ia2p_controlnet_forward(ia2p_ctx* ctx, void* stream, const void* sample, const float* timesteps, const void* context, const void* kv, int L,
+                                    const void* text_embeds, const void* time_ids, const void* cond, const float* scales, void* residuals, size_t residual_bytes,
+                                    int B, int h, int w, void* workspace, size_t workspace_bytes);
+/* ia2p_unet_forward_v plus the residuals: down_residuals[k] (k < n_down = ia2p_unet_num_skips) is added to skip k where the up path pops it, mid_residual to the mid
+ * block's output -- in place in the workspace, by ia2p_residual_add_gnstats, which also renews the GroupNorm column sums the tensor carries (every ia2p_set_gn_fuse
+ * mode sees the injected tensors). Needs no more workspace than the plain pass (ia2p_workspace_bytes_c == ia2p_workspace_bytes; the plain query and the plain pass's
+ * allocation order are untouched). Refusals, all before any launch: a null pointer or a residual off the 16-byte grid (IA2P_ERR_INVALID), n_down != the UNet's skips
+ * (IA2P_ERR_SHAPE), region_masks != NULL or G != 0 (IA2P_ERR_INVALID: the regional pass is not combined with a ControlNet; pass NULL, 0). */
+size_t ia2p_workspace_bytes_c(ia2p_ctx* ctx, int B, int h, int w, int L);
+int ia2p_unet_num_skips(ia2p_ctx* ctx);
+ia2p_status ia2p_unet_forward_c(ia2p_ctx* ctx, void* stream, const void* sample, const float* timesteps, const float* ip_scales, const void* context, const void* kv,
+                                int L, const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* workspace, size_t workspace_bytes,
+                                const void* const* down_residuals, int n_down, const void* mid_residual, const void* region_masks, int G);
+/* the operators of the path, one by one:
+ *   conv_in_act        ia2p_conv_in with an optional SiLU: y = fp16(silu(fp16(conv + bias))) for silu = 1 (the embedding's 3 -> 16 convolution)
+ *   conv3x3_narrow     3x3, pad 1, stride 1 | 2 over channels-last x [B, H, W, Cin], Cin % 16 == 0 in 16 .. 256 (the widths ia2p_conv3x3 and ia2p_conv_in do not take),
+ *                      Co % 16 == 0; Wp [Co][3][3][Cin] (ia2p_pack_conv_out); y [B, (H - 1) / stride + 1, (W - 1) / stride + 1, Co]; the same two roundings
+ *   gemm_rowscale      C[m, :] = fp16(scales[m / HW] * fp16(A . W^T + bias)), scales device float [M / HW]; K % 64 == 0, N % 4 == 0, no K split
+ *   residual_add_gnstats   y = fp16(x + r) over [M, C] (y may alias x; C % 8 == 0, 16-byte aligned tensors); gn_out != NULL: the GroupNorm column sums of y,
+ *                      [M / rows][C][2] fp64 with rows a multiple of 16 dividing M -- to the bit what ia2p_gn_colstats returns for y */
+ia2p_status ia2p_conv_in_act(void* stream, const void* x_nchw, const void* w_oihw, const void* bias, void* y_nhwc, void* w_scratch, int B, int Cin, int H, int W, int Co, int silu);
+ia2p_status ia2p_conv3x3_narrow(void* stream, const void* x, const void* Wp, const void* bias, void* y, int B, int H, int W, int Cin, int Co, int stride, int silu);
+ia2p_status ia2p_gemm_rowscale(void* stream, const void* A, const void* W, const void* bias, const float* scales, void* C, int M, int N, int K, int HW);
+ia2p_status ia2p_residual_add_gnstats(void* stream, const void* x, const void* r, void* y, int M, int C, int rows, double* gn_out);
+
 /* ---- context K/V hoisted out of the step (optional) ------------------------------------------------------------------
  * The K/V projections of every cross-attention layer (reference attention_processor.py:358-359,379-380) depend only on the context and the
  * weights; over the 25-50 denoise steps of a request the context does not change. ia2p_project_context computes them once into a caller-owned

@@ -29,6 +29,11 @@ class UNetConfigC(C.Structure):
     ]
 
 
+class ControlNetConfigC(C.Structure):
+    """ia2p_controlnet_config (include/ia2p.h): the UNet config plus the condition embedding's widths"""
+    _fields_ = [("unet", UNetConfigC), ("conditioning_channels", C.c_int), ("conditioning_embedding_out_channels", C.c_int * 4)]
+
+
 class LnFoldC(C.Structure):
     _fields_ = [("stats", C.c_void_p), ("slots", C.c_int), ("colsum", C.c_void_p), ("fbias", C.c_void_p), ("eps", C.c_float)]
 
@@ -94,6 +99,31 @@ SIGNATURES = {
     "ia2p_unet_forward_v": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ]),
     "ia2p_workspace_bytes_r": (_SZ, [_P, _I, _I, _I, _I, _I]),
     "ia2p_unet_forward_r": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ, _P, _I]),
+    "ia2p_workspace_bytes_c": (_SZ, [_P, _I, _I, _I, _I]),
+    "ia2p_unet_num_skips": (_I, [_P]),
+    "ia2p_unet_forward_c": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ, C.POINTER(_P), _I, _P, _P, _I]),
+    "ia2p_controlnet_create": (_I, [C.POINTER(ControlNetConfigC), C.POINTER(_P)]),
+    "ia2p_controlnet_destroy": (None, [_P]),
+    "ia2p_controlnet_last_error": (C.c_char_p, [_P]),
+    "ia2p_controlnet_arena_bytes": (_SZ, [_P]),
+    "ia2p_controlnet_bind_arena": (_I, [_P, _P, _SZ]),
+    "ia2p_controlnet_load_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(_I64), _I, _P]),
+    "ia2p_controlnet_finalize_weights": (_I, [_P]),
+    "ia2p_controlnet_set_image_tokens": (_I, [_P, _I]),
+    "ia2p_controlnet_check_unet": (_I, [_P, _P]),
+    "ia2p_controlnet_num_residuals": (_I, [_P]),
+    "ia2p_controlnet_residual_layout": (_SZ, [_P, _I, _I, _I, C.POINTER(_I64), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "ia2p_controlnet_embed_bytes": (_SZ, [_P, _I, _I, _I]),
+    "ia2p_controlnet_embed_workspace_bytes": (_SZ, [_P, _I, _I, _I]),
+    "ia2p_controlnet_embed": (_I, [_P, _P, _P, _I, _I, _I, _P, _SZ, _P, _SZ]),
+    "ia2p_controlnet_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
+    "ia2p_controlnet_context_kv_bytes": (_SZ, [_P, _I, _I]),
+    "ia2p_controlnet_project_context": (_I, [_P, _P, _P, _I, _I, _P, _SZ, _P, _SZ]),
+    "ia2p_controlnet_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P, _SZ]),
+    "ia2p_conv_in_act": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
+    "ia2p_conv3x3_narrow": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
+    "ia2p_gemm_rowscale": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "ia2p_residual_add_gnstats": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ia2p_context_kv_bytes": (_SZ, [_P, _I, _I]),
     "ia2p_project_context": (_I, [_P, _P, _P, _I, _I, _P, _SZ, _P, _SZ]),
     "ia2p_unet_forward_kv": (_I, [_P, _P, _P, _F, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ]),
@@ -303,6 +333,7 @@ def lib() -> C.CDLL:
 
 
 FAMILIES = ("", "vae", "clip", "vit", "sam", "llm")      # the executors behind `ia2p_<family>_*`; "" is the UNet's unprefixed `ia2p_*`
+UNET_KIND_FAMILIES = ("controlnet",)                     # ... and those whose handle is an ia2p_ctx of the UNet's kind under a prefix of its own (same lifecycle names)
 
 
 def _family_fn(l, family: str, name: str):
@@ -316,7 +347,7 @@ def check(status: int, ctx=None, family: str = "", **spelled):
     if status == IA2P_OK:
         return
     family = next((f for f, on in spelled.items() if on), family)
-    if family not in FAMILIES:
+    if family not in FAMILIES + UNET_KIND_FAMILIES:
         raise TypeError(f"check: no executor family '{family}'")
     msg = _family_fn(lib(), family, "last_error")(ctx)
     msg = msg.decode() if msg else ""
@@ -454,6 +485,17 @@ def make_config(cfg) -> UNetConfigC:
     c.projection_class_embeddings_input_dim = cfg.projection_class_embeddings_input_dim
     c.time_embed_dim, c.time_proj_dim = cfg.time_embed_dim, cfg.time_proj_dim
     c.mid_transformer_layers, c.num_time_ids = cfg.mid_block_transformer_layers, cfg.num_time_ids
+    return c
+
+
+def make_controlnet_config(cfg) -> ControlNetConfigC:
+    c = ControlNetConfigC()
+    c.unet = make_config(cfg)
+    c.conditioning_channels = cfg.conditioning_channels
+    if len(cfg.conditioning_embedding_out_channels) != 4:
+        raise ValueError("conditioning_embedding_out_channels must name four widths")
+    for i, v in enumerate(cfg.conditioning_embedding_out_channels):
+        c.conditioning_embedding_out_channels[i] = int(v)
     return c
 
 

@@ -95,6 +95,36 @@ def tiny(depths=(0, 1, 2)) -> UNetConfig:
 
 
 @dataclass
+class ControlNetConfig(UNetConfig):
+    """diffusers' `ControlNetModel` config for SDXL: the UNet's fields (its conv_in, embeddings, down path and mid block are the UNet's under a second set of
+    weights; no up path) plus the condition embedding. `transformer_layers_per_block` may differ from the guided UNet's (the small and mid SDXL ControlNets);
+    `block_out_channels`, `layers_per_block` and `cross_attention_dim` must match it."""
+    conditioning_channels: int = 3
+    conditioning_embedding_out_channels: Tuple[int, ...] = (16, 32, 96, 256)
+
+    def validate(self):
+        super().validate()
+        assert len(self.conditioning_embedding_out_channels) == 4 and all(c % 16 == 0 and 16 <= c <= 256 for c in self.conditioning_embedding_out_channels)
+        assert 1 <= self.conditioning_channels <= 7
+        return self
+
+
+def controlnet_sdxl() -> ControlNetConfig:
+    """the full-size SDXL ControlNet (e.g. `diffusers/controlnet-canny-sdxl-1.0`): the SDXL-base UNet's topology"""
+    return ControlNetConfig().validate()
+
+
+def tiny_controlnet(depths=(0, 1, 2)) -> ControlNetConfig:
+    """the `tiny()` UNet topology with the REAL embedding widths (16, 32, 96, 256), so the tests meet the 96-channel convolutions"""
+    return ControlNetConfig(
+        block_out_channels=(64, 128, 256), transformer_layers_per_block=tuple(depths),
+        attention_head_dim=(1, 2, 4), cross_attention_dim=128, sample_size=32,
+        addition_time_embed_dim=32, projection_class_embeddings_input_dim=6 * 32 + 64,
+        time_embed_dim=256, time_proj_dim=64,
+    ).validate()
+
+
+@dataclass
 class VAEConfig:
     """diffusers `AutoencoderKL` fields of the SDXL VAE (the object behind `pipe.vae`, reference
     instructany2pix/pipeline.py:109,134; ddim/sdxl_pipeline.py:859-871). First row of SURVEY.md §8f."""

@@ -159,7 +159,7 @@ struct GemmArgs {
   // range extension (VAE executor): out = acc * acc_scale + (bias + rowvec) * bias_scale + residual; 0 = 1.0. The VAE keeps its residual
   // stream multiplied by a power of two < 1 so that fp16 storage does not overflow where the reference upcasts to fp32 (vae_engine.hip)
   float acc_scale, bias_scale;
-  int act;               // activation on (acc + bias) before rowvec / residual: 0 none, 1 GELU (erf), 2 quick-GELU x*sigmoid(1.702x) (CLIP MLPs)
+  int act;               // activation on (acc + bias) before rowvec / residual: 0 none, 1 GELU (erf), 2 quick-GELU x*sigmoid(1.702x) (CLIP MLPs); 4: none, and the per-image output scale `rscale` (last field)
   // LayerNorm folded into this contraction (consumer side). A is the un-normalised residual stream [M, K], W was pre-scaled by
   // the norm's gamma when the weights were finalized (fold_ln_kernel), and the epilogue finishes the normalisation:
   //   out[m][n] = rstd_m * (acc[m][n] - mean_m * ln_cs[n]) + ln_bias[n]        ln_cs[n] = sum_k W'[n][k],  ln_bias = b + W.beta
@@ -192,6 +192,11 @@ struct GemmArgs {
     int groups;
     float eps; int silu;
   } gn;                                // gn.st0 == nullptr: plain convolution
+  // act == 4 only: per-image scale of the layer's fp16 output (a ControlNet's zero convolutions: `sample * conditioning_scale` of diffusers' ControlNetModel.forward, one
+  // scale per batch element): out[m] = fp16(rscale[m / rows_per_batch] * fp16(acc + bias)), device float [M / rows_per_batch]. Linear launches without K split, row
+  // vector, residual or GEGLU (the launcher refuses the rest), on the fp32 epilogue route like every `act`. The LAST field, read only under act == 4: every other
+  // field sits where it sat, and a launch without the scale reads nothing more from its argument block than before.
+  const float* rscale;
 };
 
 // buffer-load staging (linear layers, the halo-staged convolution) addresses an operand with a 31-bit byte offset: what a launch of `rows` x `ld` fp16 elements needs

@@ -57,7 +57,19 @@ struct ia2p_ctx : RunCtx {
   Transformer mid_t;
   int n_attn2 = 0;
   size_t arena_raw_elems = 0;   // head of the arena: everything a checkpoint provides; [arena_raw_elems, arena_elems) is derived at finalize
+  int n_skips = 0;              // tensors the down path leaves for the up path: conv_in's output, every block's, every downsampler's
+  // ---- ControlNet (ia2p_controlnet_*; diffusers 0.26.3 ControlNetModel): this context is the UNet's conv_in, embeddings, down path and mid block under a second set of
+  //      weights -- no up path, no conv_norm_out / conv_out -- plus the condition embedding (eight 3x3 convolutions over the condition image) and one 1x1 "zero"
+  //      convolution per skip and for the mid block's output
+  bool cn = false;
+  int ctx_drop = 0;             // trailing rows of every context that are not text: a ControlNet under an IP-Adapter pipe sees the text rows only (reference CNAttnProcessor2_0, attention_processor.py:530-531)
+  int ce_in_ch = 3, ce_ch[4] = {16, 32, 96, 256};
+  size_t ce_in_w = 0, ce_in_b = 0, ce_w[6] = {0}, ce_b[6] = {0}, ce_out_w = 0, ce_out_b = 0, zm_w = 0, zm_b = 0;
+  std::vector<size_t> zc_w, zc_b;
 };
+// the context rows a cross-attention layer sees as text / as image tokens
+static inline int ctx_li(const ia2p_ctx* c) { return c->ip_enabled ? c->ip_tokens : 0; }
+static inline int ctx_lt(const ia2p_ctx* c, int L) { return L - ctx_li(c) - c->ctx_drop; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // plan: enumerate parameters in the diffusers key layout (same walk as instructany2pix_amd/weights.py)
@@ -170,7 +182,7 @@ static ia2p_status plan_pass(ia2p_ctx* c, size_t fold_base, size_t* raw_elems, s
   c->ae2w = P.mat("add_embedding.linear_2.weight", T, T); c->ae2b = P.vec("add_embedding.linear_2.bias", T);
   // all time_emb_proj matrices stacked into one [sum Cout, T] projection
   int tot = 2 * ch[n - 1];
-  for (int i = 0; i < n; ++i) tot += g.layers_per_block * ch[i] + (g.layers_per_block + 1) * ch[n - 1 - i];
+  for (int i = 0; i < n; ++i) tot += g.layers_per_block * ch[i] + (c->cn ? 0 : (g.layers_per_block + 1) * ch[n - 1 - i]);
   c->tw_all = P.take((size_t)tot * T);
   c->tb_all = P.take(tot);
   c->embed_lo = c->te1w; c->embed_hi = P.cur;      // [time/add embedding MLPs | stacked time_emb_proj]: the first weights a pass reads
@@ -179,10 +191,10 @@ static ia2p_status plan_pass(ia2p_ctx* c, size_t fold_base, size_t* raw_elems, s
     int rows = 0;
     for (int i = 0; i < n; ++i) rows += g.layers_per_block * g.transformer_layers_per_block[i] * 2 * ch[i];          // down
     rows += g.mid_transformer_layers * 2 * ch[n - 1];                                                               // mid
-    for (int i = 0; i < n; ++i) rows += (g.layers_per_block + 1) * g.transformer_layers_per_block[n - 1 - i] * 2 * ch[n - 1 - i];   // up
+    for (int i = 0; i < n && !c->cn; ++i) rows += (g.layers_per_block + 1) * g.transformer_layers_per_block[n - 1 - i] * 2 * ch[n - 1 - i];   // up
     c->kv_rows = rows;
     c->kv_text_base = P.take((size_t)rows * ctx);
-    c->kv_ip_base = P.take((size_t)rows * ctx);
+    c->kv_ip_base = c->cn ? c->kv_text_base : P.take((size_t)rows * ctx);      // (a ControlNet carries no IP-Adapter: its image-token slots are never registered nor read)
   }
 
   std::vector<std::pair<std::string, size_t>> ipslots_down, ipslots_up, ipslots_mid;
@@ -212,7 +224,8 @@ static ia2p_status plan_pass(ia2p_ctx* c, size_t fold_base, size_t* raw_elems, s
   c->mid_t = P.transformer("mid_block.attentions.0", cm, g.num_heads[n - 1], g.mid_transformer_layers, ctx, ipslots_mid);
   c->mid_r1 = P.resnet("mid_block.resnets.1", cm, cm, T, c->tw_all, c->tb_all);
   cprev = cm;
-  for (int i = 0; i < n; ++i) {
+  c->n_skips = (int)skip_ch.size();
+  for (int i = 0; i < n && !c->cn; ++i) {
     Stage st;
     const int co = ch[n - 1 - i];
     const std::string bp = "up_blocks." + std::to_string(i);
@@ -230,6 +243,26 @@ static ia2p_status plan_pass(ia2p_ctx* c, size_t fold_base, size_t* raw_elems, s
   }
   if (c->temb_total != tot) return fail(c, IA2P_ERR_STATE, "internal: time_emb_proj stacking mismatch %d != %d", c->temb_total, tot);
   if (P.kv_cursor != c->kv_rows) return fail(c, IA2P_ERR_STATE, "internal: context K/V stacking mismatch %d != %d", P.kv_cursor, c->kv_rows);
+  if (c->cn) {
+    // condition embedding (ControlNetConditioningEmbedding): conv_in, blocks.{0..5} (pairs: same width stride 1, next width stride 2), conv_out -- all 3x3, pad 1
+    const std::string ep = "controlnet_cond_embedding.";
+    c->ce_in_w = P.take((size_t)c->ce_ch[0] * 64); P.reg(ep + "conv_in.weight", c->ce_in_w, (size_t)c->ce_ch[0] * c->ce_in_ch * 9, PK_PAD_CONV_IN, c->ce_ch[0], c->ce_in_ch * 9);
+    c->ce_in_b = P.vec(ep + "conv_in.bias", c->ce_ch[0]);
+    for (int i = 0; i < 3; ++i) {
+      c->ce_w[2 * i] = P.conv3(ep + "blocks." + std::to_string(2 * i) + ".weight", c->ce_ch[i], c->ce_ch[i], PK_CONV_TAP); c->ce_b[2 * i] = P.vec(ep + "blocks." + std::to_string(2 * i) + ".bias", c->ce_ch[i]);
+      c->ce_w[2 * i + 1] = P.conv3(ep + "blocks." + std::to_string(2 * i + 1) + ".weight", c->ce_ch[i + 1], c->ce_ch[i], PK_CONV_TAP); c->ce_b[2 * i + 1] = P.vec(ep + "blocks." + std::to_string(2 * i + 1) + ".bias", c->ce_ch[i + 1]);
+    }
+    c->ce_out_w = P.conv3(ep + "conv_out.weight", ch[0], c->ce_ch[3], PK_CONV_TAP); c->ce_out_b = P.vec(ep + "conv_out.bias", ch[0]);
+    // zero convolutions: 1x1, one per skip in skip order, one for the mid block's output ([C, C, 1, 1] in the checkpoint = the GEMM's [N, K])
+    c->zc_w.clear(); c->zc_b.clear();
+    for (size_t k = 0; k < skip_ch.size(); ++k) {
+      const std::string zp = "controlnet_down_blocks." + std::to_string(k);
+      c->zc_w.push_back(P.mat(zp + ".weight", skip_ch[k], skip_ch[k])); c->zc_b.push_back(P.vec(zp + ".bias", skip_ch[k]));
+    }
+    c->zm_w = P.mat("controlnet_mid_block.weight", cm, cm); c->zm_b = P.vec("controlnet_mid_block.bias", cm);
+    *raw_elems = P.cur; *fold_elems = P.fold_cur;
+    return IA2P_OK;
+  }
   c->ngo = P.vec("conv_norm_out.weight", ch[0]); c->nbo = P.vec("conv_norm_out.bias", ch[0]);
   c->conv_out_w = P.conv3("conv_out.weight", g.out_channels, ch[0], PK_CONV_TAP); c->conv_out_b = P.vec("conv_out.bias", g.out_channels);
 
@@ -509,7 +542,7 @@ static void project_context(ia2p_ctx* c, const half_t* context, int L, int B, ha
   RegionScope rs(c, PR_TRANSFORMER);
   RoleScope role(c, ROLE_CTX_KV);
   const int ctxd = c->cfg.cross_attention_dim;
-  const int Lt = c->ip_enabled ? L - c->ip_tokens : L, Li = c->ip_enabled ? c->ip_tokens : 0;
+  const int Lt = ctx_lt(c, L), Li = ctx_li(c);
   if (ncols < 0) ncols = c->kv_rows - col0;
   GemmOpt o;      // rows of the text / image tokens of every batch element; a column range on the whole projection's plan
   o.rpb = Lt; o.bstride = L; o.roff = 0; o.plan_n = ncols != c->kv_rows ? c->kv_rows : 0;
@@ -537,7 +570,7 @@ static bool sattn_fusable(Fwd& f, const Transformer& t, const TBlock& b, int HW,
 static CtxKvSlice ctx_kv_slice(Fwd& f, const Transformer& t, const TBlock& b) {
   ia2p_ctx* c = f.c;
   const int ctxd = c->cfg.cross_attention_dim;
-  const int Li = c->ip_enabled ? c->ip_tokens : 0, Lt = f.L - Li;
+  const int Li = ctx_li(c), Lt = ctx_lt(c, f.L);
   CtxKvSlice k;
   memset(&k, 0, sizeof k);
   k.ctx = f.ctxp; k.lda = ctxd; k.L = f.L; k.Lt = Lt; k.Li = Li; k.B = f.B;
@@ -554,8 +587,8 @@ static std::vector<std::pair<int, int>> plan_context_kv(Fwd& f, int h, int w) {
   std::vector<std::pair<int, int>> up_front;
   f.kv_inlaunch.clear();
   const int ctxd = c->cfg.cross_attention_dim;
-  const int Li = c->ip_enabled ? c->ip_tokens : 0, Lt = f.L - Li;
-  bool on = c->ctx_kv_inlaunch && ia2p_gemm_plan(f.B * Lt, c->kv_rows, ctxd, false, false).splitk <= 1 && (!Li || ia2p_gemm_plan(f.B * Li, c->kv_rows, ctxd, false, false).splitk <= 1);
+  const int Li = ctx_li(c), Lt = ctx_lt(c, f.L);
+  bool on = c->ctx_kv_inlaunch && !c->ctx_drop && ia2p_gemm_plan(f.B * Lt, c->kv_rows, ctxd, false, false).splitk <= 1 && (!Li || ia2p_gemm_plan(f.B * Li, c->kv_rows, ctxd, false, false).splitk <= 1);
   std::vector<std::pair<int, int>> cols;      // every block's {column, width}
   auto visit = [&](const Transformer& t, int HW) {
     for (const TBlock& b : t.blocks) {
@@ -587,8 +620,8 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
   ia2p_ctx* c = f.c;
   RegionScope rs(c, PR_TRANSFORMER);
   const int HW = H * Wd, M = f.B * HW, C = t.c;
-  const int Lt = c->ip_enabled ? f.L - c->ip_tokens : f.L;
-  const int Li = c->ip_enabled ? c->ip_tokens : 0;
+  const int Lt = ctx_lt(c, f.L);
+  const int Li = ctx_li(c);
   T2 n = wsalloc(c, (size_t)M * C);
   op_gn(c, x.p, n.p, t.ng, t.nb, f.B, HW, C, 1e-6f, 0, f.gn_partial);
   // The three LayerNorms of a block never run as kernels: every GEMM that writes the token stream `tk` also emits per-row
@@ -693,13 +726,44 @@ static T2 run_transformer(Fwd& f, const Transformer& t, T2 x, int H, int Wd, boo
   return out;
 }
 
+// What a controlled pass carries on top of the plain one (diffusers UNet2DConditionModel.forward `down_block_additional_residuals` / `mid_block_additional_residual`, and
+// ControlNetModel.forward). UNet side: one residual per skip (skip order) and one for the mid block's output, channels-last like the tensors they are added to.
+// ControlNet side: the embedded condition [B*h*w, C0], the per-image conditioning scales, and the buffer the n_skips + 1 residuals are written to, back to back.
+struct CtlIo {
+  const half_t* const* down = nullptr; const half_t* mid = nullptr;
+  const half_t* cond = nullptr; const float* scales = nullptr; half_t* res = nullptr;
+};
+// t += r in place ([M, C]); the statistics the tensor carries are taken again over the sum, in the slots its producer chose (a consumer that fuses its GroupNorm reads them
+// from f.gst; without any, the consumer's own pass -- gn_ensure_stats, or a GroupNorm launch -- sees the sum in memory)
+static void add_residual(Fwd& f, T2 t, const half_t* r, long M, int C) {
+  ia2p_ctx* c = f.c;
+  double* st = nullptr;
+  int rows = 0;
+  auto it = f.gst.find(t.off);
+  if (it != f.gst.end()) {
+    if (it->second.ok() && it->second.rows % 16 == 0 && M % it->second.rows == 0) { st = (double*)it->second.buf.p; rows = it->second.rows; }
+    else { wsfree(c, it->second.buf); f.gst.erase(it); }
+  }
+  CHECK_LAUNCH(c, ia2p_launch_residual_add_gnstats(t.p, r, t.p, (int)M, C, rows, st, c->stream), "residual injection");
+}
+// a zero convolution: out[m, :] = fp16(scales[m / HW] * fp16(x[m, :] . W^T + bias)), no K split (the scaled epilogue has no reduce-launch form)
+static void zero_conv(ia2p_ctx* c, const half_t* x, size_t w, size_t b, const float* scales, half_t* out, int M, int C, int HW) {
+  GemmArgs a = gemm_args(c, x, C, W_(c, w), W_(c, b), nullptr, 0, out, C, M, C, C);
+  a.act = 4; a.rscale = scales; a.rows_per_batch = HW;
+  set_prefetch(c, a, W_(c, w), (size_t)C * C * sizeof(half_t));
+  const GemmPlan pl = ia2p_gemm_plan(M, C, C, false, false);
+  RoleScope role(c, ROLE_PROJ_IO);
+  ProfScope ps(c, PK_GEMM0 + pl.variant, 2.0 * M * C * C, gemm_bytes(M, C, C, 0, false));
+  CHECK_LAUNCH(c, ia2p_launch_gemm_variant(a, false, pl.variant, c->stream), "zero convolution");
+}
+
 // kv_cached != nullptr: the context projections were computed before (ia2p_project_context) and are read from there
 // gn_mode: the GroupNorm mode of the pass -- the context's gn_fuse (0 launches, 1 fused, 2 the unfused twin), or, from ia2p_workspace_bytes, every one of them and
 // 3: the sizing pass of ia2p_autotune
 static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, float timestep, const half_t* context, int L,
                                const half_t* text_embeds, const half_t* time_ids, half_t* out, int B, int h, int w,
                                const half_t* kv_cached = nullptr, const float* timesteps = nullptr, const float* ip_scales = nullptr,
-                               const half_t* region_masks = nullptr, int G = 0) {
+                               const half_t* region_masks = nullptr, int G = 0, const CtlIo* io = nullptr) {
   const ia2p_unet_config& g = c->cfg;
   const int n = g.n_blocks;
   const int T = g.time_embed_dim, Tp = g.time_proj_dim, Ain = g.projection_class_embeddings_input_dim, Ad = g.addition_time_embed_dim;
@@ -768,7 +832,8 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   // ---- context K/V for every cross-attention layer in one GEMM each (text rows / image-token rows of ctx);
   //      per layer: reference attention_processor.py:358-359 (to_k/to_v) and :379-380 (to_k_ip/to_v_ip)
   if (c->kv_rows > 0) {
-    const int Lt = c->ip_enabled ? L - c->ip_tokens : L, Li = c->ip_enabled ? c->ip_tokens : 0;
+    const int Lt = ctx_lt(c, L), Li = ctx_li(c);
+    if (Lt < 1) return fail(c, IA2P_ERR_SHAPE, "context length %d leaves no text rows", L);
     if (kv_cached) {
       f.kv_text.p = const_cast<half_t*>(kv_cached);
       if (Li) f.kv_ip.p = const_cast<half_t*>(kv_cached) + (size_t)B * Lt * c->kv_rows;
@@ -800,7 +865,10 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   }
   // Every tensor below feeds a GroupNorm in front of a 3x3 convolution -- the next ResnetBlock2D's norm1, or (the skips) the norm1 of an up-path block much later --
   // and carries its producer's column sums with it (f.gst); conv_in is a direct kernel: the consumer that fuses runs the canonical statistics pass over its output
-  skips.push_back(x); skip_c.push_back(g.block_out_channels[0]);
+  // ControlNet: sample = conv_in(sample) + controlnet_cond (the embedded condition, on the latent grid)
+  if (c->cn) CHECK_LAUNCH(c, ia2p_launch_residual_add_gnstats(x.p, io ? io->cond : nullptr, x.p, B * H * Wd, g.block_out_channels[0], 0, nullptr, c->stream), "condition embedding");
+  std::vector<int> skip_hw;      // (ControlNet: pixels per image of every skip, for its zero convolution)
+  skips.push_back(x); skip_c.push_back(g.block_out_channels[0]); skip_hw.push_back(H * Wd);
   for (int i = 0; i < n; ++i) {
     const Stage& st = c->down[i];
     for (size_t j = 0; j < st.res.size(); ++j) {
@@ -808,7 +876,7 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
       T2 r = run_resnet(f, st.res[j], x, H, Wd, nullptr, 0, !att);      // (with a transformer behind it the block's output only feeds that transformer's own GroupNorm)
       if (att) { T2 t = run_transformer(f, st.att[j], r, H, Wd, true); act_free(f, r); r = t; }
       x = r;
-      skips.push_back(x); skip_c.push_back(st.res[j].cout);
+      skips.push_back(x); skip_c.push_back(st.res[j].cout); skip_hw.push_back(H * Wd);
     }
     if (st.resample) {
       const int Ho = (H - 1) / 2 + 1, Wo = (Wd - 1) / 2 + 1;
@@ -820,16 +888,37 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
       op_conv3(c, x.p, B, H, Wd, st.rc, W_(c, st.rw), W_(c, st.rb), st.rc, d.p, o);
       if (want) gst_put(f, d, gw.out);
       H = Ho; Wd = Wo; x = d;
-      skips.push_back(x); skip_c.push_back(st.rc);
+      skips.push_back(x); skip_c.push_back(st.rc); skip_hw.push_back(H * Wd);
     }
   }
   // ---- mid
   {
     T2 r0 = run_resnet(f, c->mid_r0, x, H, Wd);          // x stays alive: it is the top skip
     T2 t = run_transformer(f, c->mid_t, r0, H, Wd, true); act_free(f, r0);
-    T2 r1 = run_resnet(f, c->mid_r1, t, H, Wd, nullptr, 0, true); act_free(f, t);
+    T2 r1 = run_resnet(f, c->mid_r1, t, H, Wd, nullptr, 0, !c->cn); act_free(f, t);
     x = r1;
   }
+  if (c->cn) {
+    // ---- ControlNet: no up path. Residual k = zero_conv_k(skip_k) * conditioning_scale, the mid residual likewise, back to back in the caller's buffer
+    half_t* res = io ? io->res : nullptr;
+    const float* scales = io ? io->scales : nullptr;
+    size_t off = 0;
+    for (size_t k = 0; k < skips.size(); ++k) {
+      const int Mk = B * skip_hw[k];
+      zero_conv(c, skips[k].p, c->zc_w[k], c->zc_b[k], scales, res ? res + off : nullptr, Mk, skip_c[k], skip_hw[k]);
+      off += (size_t)Mk * skip_c[k];
+    }
+    zero_conv(c, x.p, c->zm_w, c->zm_b, scales, res ? res + off : nullptr, B * H * Wd, g.block_out_channels[n - 1], H * Wd);
+    for (T2 s : skips) act_free(f, s);
+    act_free(f, x);
+    for (auto& kv : f.gst) wsfree(c, kv.second.buf);
+    f.gst.clear();
+    wsfree(c, f.temb_all); wsfree(c, gnp); wsfree(c, f.kv_text); wsfree(c, f.kv_ip);
+    return c->failed ? IA2P_ERR_HIP : IA2P_OK;
+  }
+  // a controlled UNet pass: mid_out += mid_residual; every skip gets its residual where the up path pops it -- after the whole down path and the mid block have read
+  // the unmodified tensors, which is diffusers' order (the residuals are added to the finished tuple of skips)
+  if (io && io->mid) add_residual(f, x, io->mid, (long)B * H * Wd, g.block_out_channels[n - 1]);
   // ---- up path
   for (int i = 0; i < n; ++i) {
     const Stage& st = c->up[i];
@@ -838,6 +927,7 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
       const int cs = skip_c.back(); skip_c.pop_back();
       const int cx = st.res[j].cin - cs;
       const long M = (long)B * H * Wd;
+      if (io && io->down) add_residual(f, sk, io->down[skips.size()], M, cs);
       T2 r;
       const bool att = !st.att.empty();
       const bool last = i == n - 1 && j + 1 == st.res.size();      // (the last block's output feeds conv_norm_out: a GroupNorm launch of its own)
@@ -1021,6 +1111,7 @@ ia2p_status ia2p_set_gn_fuse(ia2p_ctx* c, int mode) {
 }
 ia2p_status ia2p_set_ip_adapter(ia2p_ctx* c, int enabled, int num_tokens, float scale) {
   if (!c) return IA2P_ERR_INVALID;
+  if (c->cn) return fail(c, IA2P_ERR_STATE, "set_ip_adapter on a ControlNet context (ia2p_controlnet_set_image_tokens: it sees the text rows only)");
   if (enabled) {
     if (num_tokens < 1 || num_tokens > 64) return fail(c, IA2P_ERR_INVALID, "num_tokens %d out of range", num_tokens);
     for (auto& kv : c->params)
@@ -1036,11 +1127,12 @@ static ia2p_status check_fwd_shape(ia2p_ctx* c, int B, int h, int w, int L) {
   if (h < div || w < div || h % div || w % div) return fail(c, IA2P_ERR_SHAPE, "latent %dx%d must be divisible by %d", h, w, div);
   if (L < 1) return fail(c, IA2P_ERR_SHAPE, "context length %d", L);
   if (c->ip_enabled && L <= c->ip_tokens) return fail(c, IA2P_ERR_SHAPE, "context length %d must exceed the %d image tokens", L, c->ip_tokens);
+  if (L <= c->ctx_drop) return fail(c, IA2P_ERR_SHAPE, "context length %d must exceed the %d image-token rows the ControlNet leaves out", L, c->ctx_drop);
   return IA2P_OK;
 }
 
 size_t ia2p_workspace_bytes(ia2p_ctx* c, int B, int h, int w, int L) {
-  if (!c || check_fwd_shape(c, B, h, w, L) != IA2P_OK) return 0;
+  if (!c || c->cn || check_fwd_shape(c, B, h, w, L) != IA2P_OK) return 0;
   // four dry passes: the GroupNorms as launches of their own, inside their convolutions (the product path), the fused path's unfused twin, and the autotune pass
   // (GroupNorm launches + the statistics and live tensors its fused candidates need) -- a workspace sized here serves every ia2p_set_gn_fuse mode and ia2p_autotune
   size_t need = 0;
@@ -1067,8 +1159,9 @@ size_t ia2p_workspace_bytes_r(ia2p_ctx* c, int B, int h, int w, int L, int G) {
 
 static ia2p_status unet_forward_impl(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, const void* kv, int L,
                                      const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes,
-                                     const float* timesteps = nullptr, const float* ip_scales = nullptr, const void* region_masks = nullptr, int G = 0) {
+                                     const float* timesteps = nullptr, const float* ip_scales = nullptr, const void* region_masks = nullptr, int G = 0, const CtlIo* io = nullptr) {
   if (!c || !sample || (!context && !kv) || !text_embeds || !time_ids || !out || !ws) return fail(c, IA2P_ERR_INVALID, "unet_forward: null argument");
+  if (c->cn) return fail(c, IA2P_ERR_STATE, "unet_forward on a ControlNet context (ia2p_controlnet_forward)");
   if (!c->finalized) return fail(c, IA2P_ERR_STATE, "unet_forward before weights were finalized");
   ia2p_status st = check_fwd_shape(c, B, h, w, L);
   if (st != IA2P_OK) return st;
@@ -1082,7 +1175,7 @@ static ia2p_status unet_forward_impl(ia2p_ctx* c, void* stream, const void* samp
               [&] { return run_forward(c, c->gn_fuse, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, kv ? (const half_t*)1 : nullptr, nullptr, nullptr, nullptr, G); });
   c->tail_pf = c->arena + c->embed_lo; c->tail_pf_bytes = (c->embed_hi - c->embed_lo) * sizeof(half_t);   // the next step starts with these
   return pass_leave(c, run_forward(c, c->gn_fuse, (const half_t*)sample, timestep, (const half_t*)context, L, (const half_t*)text_embeds, (const half_t*)time_ids, (half_t*)out,
-                                   B, h, w, (const half_t*)kv, timesteps, ip_scales, (const half_t*)region_masks, G));
+                                   B, h, w, (const half_t*)kv, timesteps, ip_scales, (const half_t*)region_masks, G, io));
 }
 ia2p_status ia2p_unet_forward(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, int L,
                               const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes) {
@@ -1113,6 +1206,181 @@ ia2p_status ia2p_unet_forward_r(ia2p_ctx* c, void* stream, const void* sample, c
   if (G < 1 || G > 16) return fail(c, IA2P_ERR_SHAPE, "unet_forward_r: G=%d (1 .. 16)", G);
   if (!c->ip_enabled || c->ip_tokens != 4 * G) return fail(c, IA2P_ERR_STATE, "unet_forward_r: %d token groups need the IP-Adapter enabled with num_tokens = %d (ia2p_set_ip_adapter)", G, 4 * G);
   return unet_forward_impl(c, stream, sample, 0.f, context, kv, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes, timesteps, ip_scales, region_masks, G);
+}
+
+// ia2p_unet_forward_v with a ControlNet's residuals (diffusers UNet2DConditionModel.forward: down_block_additional_residuals, mid_block_additional_residual): residual k
+// ([B * H_k * W_k, C_k], channels-last, device) is added to skip k where the up path pops it, mid_residual to the mid block's output; both in place in the workspace, with
+// the GroupNorm column sums of the sums taken by the same launch (ia2p_residual_add_gnstats), so every ia2p_set_gn_fuse mode sees the injected tensors. No allocation
+// beyond the plain pass's: ia2p_workspace_bytes_c is ia2p_workspace_bytes. Every refusal comes before any launch and leaves the workspace untouched.
+size_t ia2p_workspace_bytes_c(ia2p_ctx* c, int B, int h, int w, int L) { return ia2p_workspace_bytes(c, B, h, w, L); }
+int ia2p_unet_num_skips(ia2p_ctx* c) { return c ? c->n_skips : 0; }
+ia2p_status ia2p_unet_forward_c(ia2p_ctx* c, void* stream, const void* sample, const float* timesteps, const float* ip_scales, const void* context, const void* kv,
+                                int L, const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes,
+                                const void* const* down_residuals, int n_down, const void* mid_residual, const void* region_masks, int G) {
+  if (!c) return IA2P_ERR_INVALID;
+  if (!timesteps || (!context) == (!kv)) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: timesteps and exactly one of context / kv are required");
+  if (!down_residuals || !mid_residual) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: null residuals (the plain pass is ia2p_unet_forward_v)");
+  if (region_masks || G) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: residuals together with region_masks (the regional pass, ia2p_unet_forward_r, is not combined with a ControlNet)");
+  if (n_down != c->n_skips) return fail(c, IA2P_ERR_SHAPE, "unet_forward_c: %d down residuals, this UNet has %d skips", n_down, c->n_skips);
+  for (int i = 0; i < n_down; ++i)
+    if (!down_residuals[i] || (((uintptr_t)down_residuals[i]) & 15)) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: down residual %d is null or not 16-byte aligned", i);
+  if (((uintptr_t)mid_residual) & 15) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: the mid residual is not 16-byte aligned");
+  if (ip_scales && !c->ip_enabled) return fail(c, IA2P_ERR_STATE, "unet_forward_c: per-request IP-Adapter scales without an installed adapter");
+  CtlIo io;
+  io.down = (const half_t* const*)down_residuals; io.mid = (const half_t*)mid_residual;
+  return unet_forward_impl(c, stream, sample, 0.f, context, kv, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes, timesteps, ip_scales, nullptr, 0, &io);
+}
+
+// ---- the ControlNet executor (diffusers 0.26.3 ControlNetModel; the reference prepares its attention seam only: ip_adapter.py:143-148) -----------------------------------
+ia2p_status ia2p_controlnet_create(const ia2p_controlnet_config* cfg, ia2p_ctx** out) {
+  if (!cfg || !out) return fail(nullptr, IA2P_ERR_INVALID, "ia2p_controlnet_create: null argument");
+  return rc_create(&cfg->unet, out, "ia2p_controlnet_create", [&](ia2p_ctx* c) {
+    c->cn = true;
+    c->ce_in_ch = cfg->conditioning_channels;
+    for (int i = 0; i < 4; ++i) c->ce_ch[i] = cfg->conditioning_embedding_out_channels[i];
+    if (c->ce_in_ch < 1 || c->ce_in_ch * 9 > 64) return fail(c, IA2P_ERR_SHAPE, "controlnet: conditioning_channels %d (1 .. 7: the first convolution takes Cin * 9 <= 64)", c->ce_in_ch);
+    for (int i = 0; i < 4; ++i)
+      if (c->ce_ch[i] < 16 || c->ce_ch[i] > 256 || c->ce_ch[i] % 16) return fail(c, IA2P_ERR_SHAPE, "controlnet: conditioning_embedding_out_channels[%d]=%d must be a multiple of 16 in 16 .. 256", i, c->ce_ch[i]);
+    const ia2p_status st = build_plan(c);
+    if (st != IA2P_OK) return st;
+    c->groups = c->cfg.norm_num_groups;
+    ia2p_sk_counters_invalidate();
+    return IA2P_OK;
+  });
+}
+void ia2p_controlnet_destroy(ia2p_ctx* c) { delete c; }
+const char* ia2p_controlnet_last_error(ia2p_ctx* c) { return rc_last_error(c); }
+size_t ia2p_controlnet_arena_bytes(ia2p_ctx* c) { return rc_arena_bytes(c); }
+ia2p_status ia2p_controlnet_bind_arena(ia2p_ctx* c, void* dev, size_t bytes) { return rc_bind_arena(c, dev, bytes); }
+ia2p_status ia2p_controlnet_load_tensor(ia2p_ctx* c, const char* key, const void* src, const int64_t* shape, int ndim, void* stream) { return rc_load_tensor(c, key, src, shape, ndim, stream); }
+ia2p_status ia2p_controlnet_finalize_weights(ia2p_ctx* c) {
+  if (!c || !c->cn) return fail(c, IA2P_ERR_STATE, "controlnet_finalize_weights: not a ControlNet context");
+  const ia2p_status st = rc_finalize(c, "ControlNet");
+  return st == IA2P_OK ? fold_all(c, nullptr, true) : st;
+}
+// the ControlNet's contexts carry `num_tokens` trailing image-token rows it must not see (0: none): it attends to rows [0, L - num_tokens) of every context
+ia2p_status ia2p_controlnet_set_image_tokens(ia2p_ctx* c, int num_tokens) {
+  if (!c || !c->cn) return fail(c, IA2P_ERR_STATE, "controlnet_set_image_tokens: not a ControlNet context");
+  if (num_tokens < 0 || num_tokens > 64) return fail(c, IA2P_ERR_INVALID, "controlnet_set_image_tokens: num_tokens %d out of range", num_tokens);
+  c->ctx_drop = num_tokens;
+  c->wseq_key = -1;
+  return IA2P_OK;
+}
+int ia2p_controlnet_num_residuals(ia2p_ctx* c) { return c && c->cn ? c->n_skips + 1 : 0; }
+// does this ControlNet fit a UNet? (block_out_channels, layers_per_block and cross_attention_dim must match: the residuals are added to that UNet's skips)
+ia2p_status ia2p_controlnet_check_unet(ia2p_ctx* c, ia2p_ctx* unet) {
+  if (!c || !c->cn || !unet || unet->cn) return fail(c, IA2P_ERR_INVALID, "controlnet_check_unet: a ControlNet context and a UNet context are required");
+  const ia2p_unet_config &a = c->cfg, &b = unet->cfg;
+  bool same = a.n_blocks == b.n_blocks && a.layers_per_block == b.layers_per_block && a.cross_attention_dim == b.cross_attention_dim && a.in_channels == b.in_channels;
+  for (int i = 0; same && i < a.n_blocks; ++i) same = a.block_out_channels[i] == b.block_out_channels[i];
+  if (!same) return fail(c, IA2P_ERR_SHAPE, "controlnet: block_out_channels, layers_per_block, in_channels and cross_attention_dim must match the UNet's");
+  return IA2P_OK;
+}
+// the residual buffer of a forward at (B, h, w): total bytes (0 on a bad shape); per residual k < n_skips + 1 (the mid residual last) its element offset, channels and grid
+size_t ia2p_controlnet_residual_layout(ia2p_ctx* c, int B, int h, int w, int64_t* offsets, int* channels, int* hs, int* ws) {
+  if (!c || !c->cn || check_fwd_shape(c, B, h, w, c->ctx_drop + 1) != IA2P_OK) return 0;
+  const ia2p_unet_config& g = c->cfg;
+  size_t off = 0;
+  int k = 0, H = h, Wd = w;
+  auto put = [&](int ch) {
+    if (offsets) offsets[k] = (int64_t)off;
+    if (channels) channels[k] = ch;
+    if (hs) hs[k] = H;
+    if (ws) ws[k] = Wd;
+    off += (size_t)B * H * Wd * ch; ++k;
+  };
+  put(g.block_out_channels[0]);
+  for (int i = 0; i < g.n_blocks; ++i) {
+    for (int j = 0; j < g.layers_per_block; ++j) put(g.block_out_channels[i]);
+    if (i != g.n_blocks - 1) { H = (H - 1) / 2 + 1; Wd = (Wd - 1) / 2 + 1; put(g.block_out_channels[i]); }
+  }
+  put(g.block_out_channels[g.n_blocks - 1]);
+  return off * sizeof(half_t);
+}
+// condition embedding: image [B, conditioning_channels, 8 h, 8 w] NCHW fp16 in [0, 1] -> [B * h * w, block_out_channels[0]] channels-last. Depends on the image and the
+// weights only: once per request, not per step.
+static ia2p_status run_embed(ia2p_ctx* c, const half_t* image, half_t* out, int B, int h, int w) {
+  RoleScope role(c, ROLE_CONV_IO);
+  int H = 8 * h, Wd = 8 * w;
+  T2 cur = wsalloc(c, (size_t)B * H * Wd * c->ce_ch[0]);
+  CHECK_LAUNCH(c, ia2p_launch_conv_in(image, W_(c, c->ce_in_w), W_(c, c->ce_in_b), cur.p, B, c->ce_in_ch, H, Wd, c->ce_ch[0], c->stream, 1.0f, 1), "controlnet_cond_embedding.conv_in");
+  for (int i = 0; i < 3; ++i) {
+    T2 t = wsalloc(c, (size_t)B * H * Wd * c->ce_ch[i]);
+    CHECK_LAUNCH(c, ia2p_launch_conv3x3_narrow(cur.p, W_(c, c->ce_w[2 * i]), W_(c, c->ce_b[2 * i]), t.p, B, H, Wd, c->ce_ch[i], c->ce_ch[i], 1, 1, c->stream), "controlnet_cond_embedding.blocks (stride 1)");
+    wsfree(c, cur);
+    const int Ho = (H - 1) / 2 + 1, Wo = (Wd - 1) / 2 + 1;
+    T2 u = wsalloc(c, (size_t)B * Ho * Wo * c->ce_ch[i + 1]);
+    CHECK_LAUNCH(c, ia2p_launch_conv3x3_narrow(t.p, W_(c, c->ce_w[2 * i + 1]), W_(c, c->ce_b[2 * i + 1]), u.p, B, H, Wd, c->ce_ch[i], c->ce_ch[i + 1], 2, 1, c->stream), "controlnet_cond_embedding.blocks (stride 2)");
+    wsfree(c, t);
+    cur = u; H = Ho; Wd = Wo;
+  }
+  const int C0 = c->cfg.block_out_channels[0];
+  if (c->ce_ch[3] % 64 == 0) op_conv3(c, cur.p, B, H, Wd, c->ce_ch[3], W_(c, c->ce_out_w), W_(c, c->ce_out_b), C0, out);
+  else CHECK_LAUNCH(c, ia2p_launch_conv3x3_narrow(cur.p, W_(c, c->ce_out_w), W_(c, c->ce_out_b), out, B, H, Wd, c->ce_ch[3], C0, 1, 0, c->stream), "controlnet_cond_embedding.conv_out");
+  wsfree(c, cur);
+  return c->failed ? IA2P_ERR_HIP : IA2P_OK;
+}
+static bool embed_shape_ok(ia2p_ctx* c, int B, int h, int w) { return c && c->cn && B >= 1 && B <= 1024 && h >= 1 && w >= 1 && (int64_t)B * 64 * h * w <= (int64_t)1 << 30; }
+size_t ia2p_controlnet_embed_bytes(ia2p_ctx* c, int B, int h, int w) { return embed_shape_ok(c, B, h, w) ? (size_t)B * h * w * c->cfg.block_out_channels[0] * sizeof(half_t) : 0; }
+size_t ia2p_controlnet_embed_workspace_bytes(ia2p_ctx* c, int B, int h, int w) {
+  if (!embed_shape_ok(c, B, h, w)) return 0;
+  return pass_dry(c, [&] { return run_embed(c, nullptr, nullptr, B, h, w); });
+}
+ia2p_status ia2p_controlnet_embed(ia2p_ctx* c, void* stream, const void* image, int B, int h, int w, void* out, size_t out_bytes, void* ws, size_t ws_bytes) {
+  if (!c || !c->cn) return fail(c, IA2P_ERR_STATE, "controlnet_embed: not a ControlNet context");
+  if (!image || !out || !ws) return fail(c, IA2P_ERR_INVALID, "controlnet_embed: null argument");
+  if (!c->finalized) return fail(c, IA2P_ERR_STATE, "controlnet_embed before weights were finalized");
+  if (!embed_shape_ok(c, B, h, w)) return fail(c, IA2P_ERR_SHAPE, "controlnet_embed: B=%d h=%d w=%d", B, h, w);
+  if (out_bytes < ia2p_controlnet_embed_bytes(c, B, h, w)) return fail(c, IA2P_ERR_NOMEM, "controlnet_embed: the output holds %zu bytes, needs %zu", out_bytes, ia2p_controlnet_embed_bytes(c, B, h, w));
+  ia2p_status st = pass_ready(c, [&] { return fold_all(c, (hipStream_t)stream, true); });
+  if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
+  if (st != IA2P_OK) return st;
+  const bool pf = c->prefetch;
+  c->prefetch = false;               // a stand-alone call: no "next launch" to stream weights for
+  st = run_embed(c, (const half_t*)image, (half_t*)out, B, h, w);
+  c->prefetch = pf;
+  c->wseq_key = -1;
+  return pass_leave(c, st);
+}
+size_t ia2p_controlnet_workspace_bytes(ia2p_ctx* c, int B, int h, int w, int L) {
+  if (!c || !c->cn || check_fwd_shape(c, B, h, w, L) != IA2P_OK) return 0;
+  size_t need = 0;
+  for (int mode = 0; mode < 3; ++mode) {
+    const size_t n = pass_dry(c, [&] { return run_forward(c, mode, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w); });
+    if (!n) return 0;
+    need = std::max(need, n);
+  }
+  return need;
+}
+size_t ia2p_controlnet_context_kv_bytes(ia2p_ctx* c, int B, int L) { return c && c->cn && L > c->ctx_drop ? ia2p_context_kv_bytes(c, B, L) : 0; }
+ia2p_status ia2p_controlnet_project_context(ia2p_ctx* c, void* stream, const void* context, int L, int B, void* kv, size_t kv_bytes, void* ws, size_t ws_bytes) {
+  if (!c || !c->cn) return fail(c, IA2P_ERR_STATE, "controlnet_project_context: not a ControlNet context");
+  if (L <= c->ctx_drop) return fail(c, IA2P_ERR_SHAPE, "controlnet_project_context: context length %d must exceed the %d image-token rows", L, c->ctx_drop);
+  return ia2p_project_context(c, stream, context, L, B, kv, kv_bytes, ws, ws_bytes);
+}
+// One ControlNet evaluation: the `_v` argument shape (per-row timesteps, `context` or cached `kv`) plus the embedded condition (ia2p_controlnet_embed) and the per-image
+// conditioning scales (device float [B]). Writes the n_skips + 1 residuals channels-last into `residuals` (ia2p_controlnet_residual_layout).
+ia2p_status ia2p_controlnet_forward(ia2p_ctx* c, void* stream, const void* sample, const float* timesteps, const void* context, const void* kv, int L,
+                                    const void* text_embeds, const void* time_ids, const void* cond, const float* scales, void* residuals, size_t residual_bytes,
+                                    int B, int h, int w, void* ws, size_t ws_bytes) {
+  if (!c || !c->cn) return fail(c, IA2P_ERR_STATE, "controlnet_forward: not a ControlNet context");
+  if (!sample || !timesteps || (!context) == (!kv) || !text_embeds || !time_ids || !cond || !scales || !residuals || !ws)
+    return fail(c, IA2P_ERR_INVALID, "controlnet_forward: null argument (exactly one of context / kv)");
+  if ((((uintptr_t)cond) | ((uintptr_t)residuals)) & 15) return fail(c, IA2P_ERR_INVALID, "controlnet_forward: cond and residuals must be 16-byte aligned");
+  if (!c->finalized) return fail(c, IA2P_ERR_STATE, "controlnet_forward before weights were finalized");
+  ia2p_status st = check_fwd_shape(c, B, h, w, L);
+  if (st != IA2P_OK) return st;
+  const size_t need = ia2p_controlnet_residual_layout(c, B, h, w, nullptr, nullptr, nullptr, nullptr);
+  if (residual_bytes < need) return fail(c, IA2P_ERR_NOMEM, "controlnet_forward: the residual buffer holds %zu bytes, needs %zu", residual_bytes, need);
+  st = pass_ready(c, [&] { return fold_all(c, (hipStream_t)stream, true); });
+  if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
+  if (st != IA2P_OK) return st;
+  pass_record(c, (kv ? 1000 : 0) + c->ctx_drop, [&] { return run_forward(c, c->gn_fuse, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, kv ? (const half_t*)1 : nullptr); });
+  c->tail_pf = c->arena + c->embed_lo; c->tail_pf_bytes = (c->embed_hi - c->embed_lo) * sizeof(half_t);
+  CtlIo io;
+  io.cond = (const half_t*)cond; io.scales = scales; io.res = (half_t*)residuals;
+  return pass_leave(c, run_forward(c, c->gn_fuse, (const half_t*)sample, 0.f, (const half_t*)context, L, (const half_t*)text_embeds, (const half_t*)time_ids, nullptr,
+                                   B, h, w, (const half_t*)kv, timesteps, nullptr, nullptr, 0, &io));
 }
 
 // ---- context K/V hoisted out of the step: the projections depend on (context, weights) only, constant over a request's steps

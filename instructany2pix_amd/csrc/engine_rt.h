@@ -29,6 +29,9 @@ int ia2p_gemm_variant_ran(const GemmArgs& a, bool conv, int v);
 bool ia2p_conv_gn_fusable(const GemmArgs& a, int v, int splitk);
 bool ia2p_plan_any_gn(int M);
 void ia2p_conv_gn_candidates(const GemmArgs& a, size_t max_slab_bytes, std::vector<GemmPlan>* out);
+// controlnet.hip: the narrow 3x3 convolution of the ControlNet condition embedding; y = fp16(x + r) with the GroupNorm column sums of y (out == nullptr: none)
+hipError_t ia2p_launch_conv3x3_narrow(const half_t* x, const half_t* w, const half_t* bias, half_t* y, int B, int H, int W, int Cin, int Co, int stride, int silu, hipStream_t s);
+hipError_t ia2p_launch_residual_add_gnstats(const half_t* x, const half_t* r, half_t* y, int M, int C, int rows, double* out, hipStream_t s);
 hipError_t ia2p_launch_gn_colstats(const half_t* x, int ldx, int M, int C, int rows, double* out, hipStream_t s);
 hipError_t ia2p_launch_gn_apply_stats(const half_t* x0, int ld0, const half_t* x1, int ld1, half_t* y, int ldy, int B, int HW, int C, const GemmArgs::GnIn& g, hipStream_t s);
 hipError_t ia2p_launch_splitk_reduce(const GemmArgs& a, hipStream_t s);
@@ -54,7 +57,7 @@ hipError_t ia2p_launch_embed(float t, const float* ts, const half_t* text_embeds
                              int B, int Tp, int P, int Ad, int nids, hipStream_t s);
 hipError_t ia2p_launch_linear_small(const half_t* X, int ldx, const half_t* W, const half_t* bias, const half_t* addend, int ldadd,
                                     half_t* out, int ldo, int M, int N, int K, int silu_in, int silu_out, hipStream_t s);
-hipError_t ia2p_launch_conv_in(const half_t* x, const half_t* w, const half_t* bias, half_t* y, int B, int Cin, int H, int W, int Co, hipStream_t s, float out_scale = 1.0f);
+hipError_t ia2p_launch_conv_in(const half_t* x, const half_t* w, const half_t* bias, half_t* y, int B, int Cin, int H, int W, int Co, hipStream_t s, float out_scale = 1.0f, int silu = 0);
 hipError_t ia2p_launch_conv_out(const half_t* x, int ldx, const half_t* w, const half_t* bias, half_t* y, int B, int C, int H, int W, int Co, hipStream_t s);
 hipError_t ia2p_launch_concat(const half_t* a, int lda, int Ca, const half_t* b, int ldb, int Cb, half_t* y, long M, hipStream_t s);
 hipError_t ia2p_launch_ddim_step(const half_t* x, const half_t* eps_u, const half_t* eps_c, float g, float c_x, float c_e,

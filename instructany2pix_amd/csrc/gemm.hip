@@ -396,6 +396,8 @@ static hipError_t launch_any(const GemmArgs& a0, int v, hipStream_t s, bool with
   hipError_t e;
   if (v < 0 || v >= IA2P_GEMM_NVARIANT) return hipErrorInvalidValue;
   if (a0.geglu && IA2P_GEMM_TILES[v].bn % 32) return hipErrorInvalidValue;   // a (value, gate) block of 32 packed columns must not straddle tiles
+  // the per-image output scale: plain linear launches only (the K-split reduce kernel, the GEGLU tile and the fused attention tiles have no such epilogue)
+  if (a0.act == 4 && (!a0.rscale || CONV || a0.geglu || a0.splitk > 1 || a0.rowvec || a0.residual || a0.stats_out || a0.gn_out || a0.ln_stats || a0.rows_per_batch < 1)) return hipErrorInvalidValue;
   GemmArgs a = a0;
   a.sk_counters = nullptr;
   if (a.splitk > 1 && ia2p_splitk_inkernel(a.M, a.N, a.splitk))

@@ -36,7 +36,7 @@ __device__ __forceinline__ void tile_epilogue(f4 (&acc)[BM / WGM / 16][BN / WGN 
   // two routes: the register epilogue (no K split, 16-byte accesses everywhere -- every shape of the executors; below) and the chunked fp32 route (K splits: the slabs are
   // fp32; odd strides). Both compute  h = fp16(acc * as + bias * bs | folded LayerNorm, activation)  and  out = fp16(h + rowvec * bs + residual): the rounding of the
   // reference's own fp16 modules (a Linear / Conv2d output is an fp16 tensor before the time-embedding row or the residual is added to it).
-  const bool reg_epi = XA == 0 && EC::REG_EPI && nsplit == 1 && p.vec8 != 0 && (hN & 7) == 0 && !p.act;      // (activations other than GEGLU: the CLIP / prior MLPs, on the fp32 route)
+  const bool reg_epi = XA == 0 && EC::REG_EPI && nsplit == 1 && p.vec8 != 0 && (hN & 7) == 0 && !p.act;      // (activations other than GEGLU -- the CLIP / prior MLPs -- and act 4, the per-image output scale: on the fp32 route)
   char* cbase = smem + (reg_epi ? EC::T16_BYTES : EC::TILE_BYTES);
   float* ln_rows = (float*)cbase;                                       // [0, BM): mean, [BM, 2 BM): rstd
   float* ln_cs = ln_rows + 2 * BM;                                      // BN column sums and BN folded biases of this tile
@@ -544,6 +544,26 @@ __device__ __forceinline__ void tile_epilogue(f4 (&acc)[BM / WGM / 16][BN / WGN 
     }
     __syncthreads();
     IA2P_STAMP(if (((IA2P_STAMP_AT == 1 && ch == 0) || (IA2P_STAMP_AT == 3 && ch == 1))) stamp_put(p, nsplit, 7);)
+    if (p.act == 4) {
+      // ---- per-image output scale (act 4; a ControlNet's zero convolution): out = fp16(rscale[image] * fp16(acc + bias)), the product one fp32 operation. A loop of
+      //      its own, four columns per thread and pass, so that the loops every other launch runs are the code they were.
+      constexpr int GPR4 = BN / 4;
+#pragma unroll 1
+      for (int idx = tid; idx < CR * GPR4; idx += NT) {
+        const int r = idx / GPR4, g = idx - r * GPR4;
+        const int m = rowm(r), n = bn0 + g * 4;
+        if (m >= hM || n >= hN) continue;
+        f4 v = tl(r, g);
+        v[0] *= e_as; v[1] *= e_as; v[2] *= e_as; v[3] *= e_as;
+        if (p.bias) { const h4 b = *(const h4*)(p.bias + n); v[0] = fmaf((float)b[0], e_bs, v[0]); v[1] = fmaf((float)b[1], e_bs, v[1]); v[2] = fmaf((float)b[2], e_bs, v[2]); v[3] = fmaf((float)b[3], e_bs, v[3]); }
+        const float sc = p.rscale[m / p.rows_per_batch];
+        h4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = (half_t)((float)(half_t)v[e] * sc);
+        *(h4*)(p.C + (size_t)m * p.ldc + n) = o;
+      }
+      continue;
+    }
     if (p.geglu) {                    // packed columns: 32-wide blocks [16 values | 16 gates]; out[m][n/2] = a * gelu(g)
       constexpr int GPR = BN / 16;    // groups of 8 OUTPUT columns per row
 #ifndef IA2P_GEGLU_U

@@ -102,6 +102,8 @@ __global__ __launch_bounds__(64) void linear_small_kernel(const half_t* X, int l
 // workgroup as a zero-padded [Co][64] LDS image (first operand: a lane ends up with 4 consecutive output channels of one pixel), the
 // im2col fragment of the 16 pixels is gathered straight from the NCHW input into registers, and the 16 x Co output block goes through LDS
 // so that every pixel row leaves as whole 16-byte pieces. HBM-bound on the output write (B*H*W*Co*2 bytes).
+// SILU (the ControlNet condition embedding's first convolution): out = fp16(silu(fp16(acc + bias))) -- the activation of an fp16 module output, as the reference rounds
+template <bool SILU>
 __global__ __launch_bounds__(256) void conv_in_kernel(const half_t* x, const half_t* w /*[Co][64]: k = ci*9 + tap, zero padded (ia2p_launch_pack_conv_in)*/, const half_t* bias,
                                                       half_t* y, int B, int Cin, int H, int W, int Co, int pix_per_block, float out_scale) {
   extern __shared__ __attribute__((aligned(16))) char cin_smem[];
@@ -154,7 +156,10 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const half_t* x, const hal
       const h4 bv = *(const h4*)(bias + n);
       h4 o;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) o[i] = (half_t)((acc[i] + (float)bv[i]) * out_scale);
+      for (int i = 0; i < 4; ++i) {
+        o[i] = (half_t)((acc[i] + (float)bv[i]) * out_scale);
+        if constexpr (SILU) o[i] = (half_t)silu_f((float)o[i]);
+      }
       *(h4*)(ow + (size_t)pl * Co + n) = o;
     }
   }
@@ -658,7 +663,7 @@ hipError_t ia2p_launch_linear_small(const half_t* X, int ldx, const half_t* W, c
   hipLaunchKernelGGL(linear_small_kernel, dim3((N + 3) / 4), dim3(64), 0, s, X, ldx, W, bias, addend, ldadd, out, ldo, M, N, K, silu_in, silu_out);
   return hipGetLastError();
 }
-hipError_t ia2p_launch_conv_in(const half_t* x, const half_t* w, const half_t* bias, half_t* y, int B, int Cin, int H, int W, int Co, hipStream_t s, float out_scale) {
+hipError_t ia2p_launch_conv_in(const half_t* x, const half_t* w, const half_t* bias, half_t* y, int B, int Cin, int H, int W, int Co, hipStream_t s, float out_scale, int silu) {
   if (Co % 8 || Cin * 9 > 64) return hipErrorInvalidValue;
   const int ppb = 64;
   const size_t sm = (size_t)Co * 64 * sizeof(half_t) + (size_t)64 * Co * sizeof(half_t);      // padded weights + 4 x 16 pixel rows of output
@@ -667,11 +672,13 @@ hipError_t ia2p_launch_conv_in(const half_t* x, const half_t* w, const half_t* b
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (sm > 65536 && (dev < 0 || dev >= 64 || !attr[dev])) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_in_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute((const void*)conv_in_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_in_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     if (dev >= 0 && dev < 64) attr[dev] = true;
   }
-  hipLaunchKernelGGL(conv_in_kernel, dim3((B * H * W + ppb - 1) / ppb), dim3(256), sm, s, x, w, bias, y, B, Cin, H, W, Co, ppb, out_scale);
+  if (silu) hipLaunchKernelGGL(conv_in_kernel<true>, dim3((B * H * W + ppb - 1) / ppb), dim3(256), sm, s, x, w, bias, y, B, Cin, H, W, Co, ppb, out_scale);
+  else hipLaunchKernelGGL(conv_in_kernel<false>, dim3((B * H * W + ppb - 1) / ppb), dim3(256), sm, s, x, w, bias, y, B, Cin, H, W, Co, ppb, out_scale);
   return hipGetLastError();
 }
 hipError_t ia2p_launch_conv_out(const half_t* x, int ldx, const half_t* w, const half_t* bias, half_t* y, int B, int C, int H, int W, int Co, hipStream_t s) {

@@ -290,6 +290,44 @@ ia2p_status ia2p_conv_in(void* stream, const void* x_nchw, const void* w_oihw, c
   if (e == hipSuccess) e = ia2p_launch_conv_in((const half_t*)x_nchw, (const half_t*)w_scratch, (const half_t*)bias, (half_t*)y_nhwc, B, Cin, H, W, Co, (hipStream_t)stream);
   RET_HIP(e, "conv_in");
 }
+// ---- the ControlNet path's operators (controlnet.hip; diffusers ControlNetModel: ControlNetConditioningEmbedding, controlnet_down_blocks / controlnet_mid_block, and the
+//      `sample + residual` of UNet2DConditionModel.forward). Every refusal comes before any launch.
+ia2p_status ia2p_conv_in_act(void* stream, const void* x_nchw, const void* w_oihw, const void* bias, void* y_nhwc, void* w_scratch, int B, int Cin, int H, int W, int Co, int silu) {
+  if (!x_nchw || !w_oihw || !bias || !y_nhwc || !w_scratch) return fail(nullptr, IA2P_ERR_INVALID, "conv_in_act: null argument");
+  if (silu != 0 && silu != 1) return fail(nullptr, IA2P_ERR_INVALID, "conv_in_act: silu=%d (0 or 1)", silu);
+  if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cin * 9 > 64 || Co < 8 || Co % 8) return fail(nullptr, IA2P_ERR_SHAPE, "conv_in_act: Cin*9=%d must be <= 64, Co=%d a multiple of 8", Cin * 9, Co);
+  hipError_t e = ia2p_launch_pack_conv_in((const half_t*)w_oihw, (half_t*)w_scratch, Co, Cin * 9, (hipStream_t)stream);
+  if (e == hipSuccess) e = ia2p_launch_conv_in((const half_t*)x_nchw, (const half_t*)w_scratch, (const half_t*)bias, (half_t*)y_nhwc, B, Cin, H, W, Co, (hipStream_t)stream, 1.0f, silu);
+  RET_HIP(e, "conv_in_act");
+}
+ia2p_status ia2p_conv3x3_narrow(void* stream, const void* x, const void* Wp, const void* bias, void* y, int B, int H, int W, int Cin, int Co, int stride, int silu) {
+  if (!x || !Wp || !bias || !y) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_narrow: null argument");
+  if (silu != 0 && silu != 1) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_narrow: silu=%d (0 or 1)", silu);
+  if (B < 1 || H < 1 || W < 1 || Cin < 16 || Cin > 256 || Cin % 16 || Co < 16 || Co % 16 || (stride != 1 && stride != 2))
+    return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_narrow: Cin=%d (multiple of 16, 16 .. 256) Co=%d (multiple of 16) stride=%d (1 or 2)", Cin, Co, stride);
+  if ((int64_t)B * H * W > INT32_MAX - 64) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_narrow: %lld pixels exceed the 32-bit count of one launch", (long long)B * H * W);
+  hipError_t e = ia2p_launch_conv3x3_narrow((const half_t*)x, (const half_t*)Wp, (const half_t*)bias, (half_t*)y, B, H, W, Cin, Co, stride, silu, (hipStream_t)stream);
+  RET_HIP(e, "conv3x3_narrow");
+}
+// C[m, :] = fp16(scales[m / HW] * fp16(A . W^T + bias)): a zero convolution (1x1) with its image's conditioning scale in the epilogue; no K split
+ia2p_status ia2p_gemm_rowscale(void* stream, const void* A, const void* W, const void* bias, const float* scales, void* C, int M, int N, int K, int HW) {
+  if (!A || !W || !C || !scales) return fail(nullptr, IA2P_ERR_INVALID, "gemm_rowscale: null argument");
+  if (((uintptr_t)scales) & 3) return fail(nullptr, IA2P_ERR_INVALID, "gemm_rowscale: scales must be 4-byte aligned");
+  if (M < 1 || K < 64 || K % 64 || N < 4 || N % 4 || HW < 1 || M % HW) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_rowscale: K=%d must be a multiple of 64, N=%d of 4, HW=%d must divide M=%d", K, N, HW, M);
+  GemmArgs a = gemm_desc(zero_page(), (const half_t*)A, K, (const half_t*)W, K, (const half_t*)bias, nullptr, 0, (half_t*)C, N, M, N, K);
+  a.act = 4; a.rscale = scales; a.rows_per_batch = HW;
+  hipError_t e = ia2p_launch_gemm_variant(a, false, ia2p_gemm_plan(M, N, K, false, false).variant, (hipStream_t)stream);
+  RET_HIP(e, "gemm_rowscale");
+}
+// y = fp16(x + r) over [M, C] (y may alias x); gn_out != NULL: also the GroupNorm column sums of y, [M / rows][C][2] fp64, to the bit what ia2p_gn_colstats(y) returns
+ia2p_status ia2p_residual_add_gnstats(void* stream, const void* x, const void* r, void* y, int M, int C, int rows, double* gn_out) {
+  if (!x || !r || !y) return fail(nullptr, IA2P_ERR_INVALID, "residual_add_gnstats: null argument");
+  if ((((uintptr_t)x) | ((uintptr_t)r) | ((uintptr_t)y)) & 15) return fail(nullptr, IA2P_ERR_INVALID, "residual_add_gnstats: tensors must be 16-byte aligned");
+  if (M < 1 || C < 8 || C % 8 || (int64_t)M * C > INT32_MAX) return fail(nullptr, IA2P_ERR_SHAPE, "residual_add_gnstats: M=%d C=%d (C a multiple of 8, M C below 2^31)", M, C);
+  if (gn_out && (rows < 16 || rows % 16 || M % rows)) return fail(nullptr, IA2P_ERR_SHAPE, "residual_add_gnstats: rows=%d (multiple of 16 dividing M=%d)", rows, M);
+  hipError_t e = ia2p_launch_residual_add_gnstats((const half_t*)x, (const half_t*)r, (half_t*)y, M, C, rows, gn_out, (hipStream_t)stream);
+  RET_HIP(e, "residual_add_gnstats");
+}
 ia2p_status ia2p_conv_out(void* stream, const void* x_nhwc, const void* w_packed, const void* bias, void* y_nchw, int B, int C, int H, int W, int Co) {
   if (!x_nhwc || !w_packed || !bias || !y_nchw) return fail(nullptr, IA2P_ERR_INVALID, "conv_out: null argument");
   if (B < 1 || H < 1 || W < 1 || C < 32 || C % 32 || Co < 1 || Co > 8) return fail(nullptr, IA2P_ERR_SHAPE, "conv_out: C=%d must be a multiple of 32, Co=%d <= 8", C, Co);

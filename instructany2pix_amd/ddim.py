@@ -343,3 +343,82 @@ class StableDiffusionXLPipeline(_PipelineBase):
         cb = None if callback is None else (lambda i, t, x: callback(i, int(t), x) if i % callback_steps == 0 else None)
         return lcm_sample(self.unet, self.scheduler.config, latents, ctx, added, [steps] * B, [float(guidance_scale)] * B, do_cfg, rows, seeds, None, known_latents,
                           edit_mask, dict(cross_attention_kwargs=cross_attention_kwargs, return_dict=False), cb)
+
+
+# ---- ControlNet: structure-guided sampling (diffusers 0.26.3 StableDiffusionXLControlNetPipeline) ---------------------------------------------------
+def control_active(i: int, n: int, start: float, end: float) -> bool:
+    """does step i of n run the ControlNet? diffusers' `control_guidance_start` / `control_guidance_end`: `controlnet_keep[i] = 1 - (i / n < start or (i + 1) / n > end)`"""
+    return not (i / n < start or (i + 1) / n > end)
+
+
+class ControlledUNet:
+    """The (ControlNet, UNet) pair behind the UNet's call signature: evaluation i of a sampling loop of `steps` steps runs the ControlNet on the same inputs and the
+    UNet with its residuals while the step lies in the control window, the plain UNet entry otherwise. The DDIM loop and `batch.lcm_sample` run it unchanged; every
+    other attribute is the UNet's."""
+
+    def __init__(self, unet, controlnet, image, scale, start, end, steps):
+        self.unet, self.controlnet, self.image, self.scale, self.window, self.steps, self.calls = unet, controlnet, image, scale, (float(start), float(end)), int(steps), 0
+
+    def __getattr__(self, name):            # (only what this object does not carry itself: config, device, add_embedding, lora, ...)
+        return getattr(self.__dict__["unet"], name)
+
+    def __call__(self, sample, timestep, encoder_hidden_states=None, cross_attention_kwargs=None, added_cond_kwargs=None, **kw):
+        i, self.calls = self.calls, self.calls + 1
+        if not control_active(i, self.steps, *self.window):
+            return self.unet(sample, timestep, encoder_hidden_states=encoder_hidden_states, cross_attention_kwargs=cross_attention_kwargs,
+                             added_cond_kwargs=added_cond_kwargs, **kw)
+        down, mid = self.controlnet(sample, timestep, encoder_hidden_states=encoder_hidden_states, controlnet_cond=self.image, conditioning_scale=self.scale,
+                                    added_cond_kwargs=added_cond_kwargs, return_dict=False)
+        return self.unet(sample, timestep, encoder_hidden_states=encoder_hidden_states, cross_attention_kwargs=cross_attention_kwargs,
+                         added_cond_kwargs=added_cond_kwargs, down_block_additional_residuals=down, mid_block_additional_residual=mid, **kw)
+
+
+class StableDiffusionXLControlNetPipeline(StableDiffusionXLPipeline):
+    """`StableDiffusionXLPipeline` with a `.controlnet` (a `HipControlNetModel` whose block_out_channels, layers_per_block and cross_attention_dim match the UNet's:
+    refused here otherwise). `image=` is the condition map the caller brings (edges, depth, pose, a sketch; no detector runs here): a float tensor or array in [0, 1],
+    [B or 1, 3, H, W] with H x W the sampled image's size, 8 x the latent grid. With classifier-free guidance it is repeated for both halves. `image=None`,
+    `controlnet_conditioning_scale=0` or a control window that holds no step run today's `StableDiffusionXLPipeline` call: no ControlNet launch, the plain UNet
+    entry, the same bits. Multi-ControlNet, `guess_mode=True` and T2I-Adapters are not built."""
+
+    def __init__(self, unet, controlnet, *a, **kw):
+        super().__init__(unet, *a, **kw)
+        controlnet.check_unet(unet)
+        self.controlnet = controlnet
+
+    @torch.no_grad()
+    def __call__(self, *a, image=None, controlnet_conditioning_scale=1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
+                 guess_mode: bool = False, **kw):
+        if guess_mode:
+            raise ValueError("guess_mode=True is not supported")
+        if isinstance(controlnet_conditioning_scale, (list, tuple)) or isinstance(control_guidance_start, (list, tuple)) or isinstance(control_guidance_end, (list, tuple)):
+            raise ValueError("one ControlNet: controlnet_conditioning_scale, control_guidance_start and control_guidance_end are single numbers")
+        start, end = float(control_guidance_start), float(control_guidance_end)
+        if not (0.0 <= start <= 1.0 and 0.0 <= end <= 1.0) or start > end:
+            raise ValueError(f"control guidance window [{start}, {end}] must lie in [0, 1] with start <= end")
+        steps = int(kw.get("num_inference_steps", a[3] if len(a) > 3 else 50))
+        scale = controlnet_conditioning_scale
+        off = image is None or (not torch.is_tensor(scale) and float(scale) == 0.0) or not any(control_active(i, steps, start, end) for i in range(steps))
+        if off:
+            return super().__call__(*a, **kw)
+        if kw.get("cross_attention_kwargs") and kw["cross_attention_kwargs"].get("ip_adapter_masks") is not None:
+            raise ValueError("ControlNet residuals together with ip_adapter_masks: the regional pass is not combined with a ControlNet")
+        cond = torch.as_tensor(image)
+        if cond.ndim == 3:
+            cond = cond[None]
+        if cond.ndim != 4 or cond.shape[1] != self.controlnet.config.conditioning_channels or not cond.is_floating_point():
+            raise ValueError(f"`image` must be a float condition map [B or 1, {self.controlnet.config.conditioning_channels}, H, W] in [0, 1]; got {tuple(cond.shape)} {cond.dtype}")
+        lat = kw.get("latents")
+        if lat is not None:
+            hw = (lat.shape[-2] * self.vae_scale_factor, lat.shape[-1] * self.vae_scale_factor)
+        else:
+            ss = getattr(self.unet.config, "sample_size", 128) * self.vae_scale_factor
+            hw = (kw.get("height") or (a[1] if len(a) > 1 else None) or ss, kw.get("width") or (a[2] if len(a) > 2 else None) or ss)
+        if tuple(cond.shape[-2:]) != tuple(hw) or self.vae_scale_factor != 8:
+            raise ValueError(f"the condition image is {cond.shape[-2]} x {cond.shape[-1]}; the sampled image is {hw[0]} x {hw[1]} (8 x the latent grid)")
+        cond = cond.to(device=self.device, dtype=torch.float16).contiguous()
+        plain = self.unet
+        self.unet = ControlledUNet(plain, self.controlnet, cond, scale, start, end, steps)
+        try:
+            return super().__call__(*a, **kw)
+        finally:
+            self.unet = plain

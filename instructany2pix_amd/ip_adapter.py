@@ -105,6 +105,9 @@ class IPAdapter:
                                  scale=1.0, num_tokens=self.num_tokens)
             plugins[name] = ip.to(self.device, dtype=torch.float16)
         unet.set_attn_processor(plugins)
+        # a pipe with a ControlNet (reference :143-148 installs CNAttnProcessor(num_tokens) on it): the ControlNet attends to the text rows only
+        if hasattr(self.pipe, "controlnet"):
+            self.pipe.controlnet.set_image_tokens(self.num_tokens)
 
     def enable(self):
         self.set_ip_adapter()
@@ -112,6 +115,8 @@ class IPAdapter:
 
     def disable(self):
         self.pipe.unet.set_attn_processor(AttnProcessor())
+        if hasattr(self.pipe, "controlnet"):
+            self.pipe.controlnet.set_image_tokens(0)
 
     @staticmethod
     def _read_checkpoint(ck):
@@ -177,7 +182,8 @@ class IPAdapterXL(IPAdapter):
         row); the masks reach the pipeline as `region_masks` -- token group s acts where mask s says, the blend runs under their union.
         `seed` builds the torch generator the pipeline draws from, as in the reference. `noise_seed` / `noise_draw` go through to a pipeline that draws noise
         of its own (the inpainting pipeline): the request's Philox stream and the draw id in it (noise.py); they win over the generator.
-        `known_trajectory=` / `edit_mask=` (an edit inside a mask, ddim.py) reach the pipeline with the other keywords."""
+        `known_trajectory=` / `edit_mask=` (an edit inside a mask, ddim.py) reach the pipeline with the other keywords, and so do the control keywords of a
+        `StableDiffusionXLControlNetPipeline` (`image=`, `controlnet_conditioning_scale=`, `control_guidance_start=`, `control_guidance_end=`)."""
         if noise_seed is not None:
             kwargs.update(noise_seed=noise_seed, noise_draw=noise_draw)
         self.set_scale(scale)

@@ -23,12 +23,13 @@ import contextlib
 import os
 from typing import Any, Callable, Optional
 
+import numpy as np
 import PIL.Image
 import torch
 
 from . import noise as _noise
 from .config import UNetConfig, sdxl_base
-from .ddim import SDXLDDIMPipeline, StableDiffusionXLPipeline
+from .ddim import SDXLDDIMPipeline, StableDiffusionXLControlNetPipeline, StableDiffusionXLPipeline
 from .img2img import StableDiffusionXLImg2ImgPipeline
 from .inpaint import StableDiffusionXLInpaintPipeline, subject_consistency, subject_consistency_from_boxes
 from .image_processor import OUTPUT_TYPES, requantize
@@ -239,7 +240,7 @@ class InstructAny2PixPipeline:
                  vae_encode: Optional[Callable] = None, vae_decode: Optional[Callable] = None, clip_embeddings_dim: int = 1024,
                  refiner_unet: Optional[HipUNet2DConditionModel] = None, refiner_text_encoder: Optional[Callable] = None, prior=None,
                  refiner_handoff: str = "image", vae=None, llm=None, llm_tokenizer: Optional[Callable] = None,
-                 modality_encoder: Optional[Callable] = None, imagebind=None, segmenter=None, detector: Optional[Callable] = None):
+                 modality_encoder: Optional[Callable] = None, imagebind=None, segmenter=None, detector: Optional[Callable] = None, controlnet=None):
         # llm: a HipInstructAny2PixLM (reference :117 `self.any2pix_lm`; built with `load_in_4bit=True` it computes from 4-bit weights as the
         # reference's `from_pretrained(..., load_in_4bit=True)` model does, nothing changes here) with its tokenizer (:126 `self.any2pix_tokenizer`, injected: the
         # sentencepiece model is checkpoint data); modality_encoder(entry) -> [1024] embedding of an mm_data entry (reference :155-166:
@@ -275,7 +276,13 @@ class InstructAny2PixPipeline:
         new_sch = DDIMScheduler()
         # one shared UNet object for sampling and inversion (reference :106-116)
         self.vae = vae
-        self.pipe = StableDiffusionXLPipeline(unet, DDIMScheduler(), encode_prompt=text_encoder, vae_decode=vae_decode, vae=vae)
+        # controlnet: a HipControlNetModel (new: the reference attaches none). The guided sampling stage then takes `control_image=`; without one, or with the
+        # control off, the stage is the plain pipeline's call
+        self.controlnet = controlnet
+        if controlnet is not None:
+            self.pipe = StableDiffusionXLControlNetPipeline(unet, controlnet, DDIMScheduler(), encode_prompt=text_encoder, vae_decode=vae_decode, vae=vae)
+        else:
+            self.pipe = StableDiffusionXLPipeline(unet, DDIMScheduler(), encode_prompt=text_encoder, vae_decode=vae_decode, vae=vae)
         self.pipe_inversion = SDXLDDIMPipeline(unet, new_sch, encode_prompt=text_encoder, vae_encode=vae_encode, vae=vae)
         # the refiner pipeline object (:128-131): second UNet config of the same engine, Euler img2img loop (img2img.py)
         self.piperf = StableDiffusionXLImg2ImgPipeline(refiner_unet, encode_prompt=refiner_text_encoder, vae_encode=vae_encode,
@@ -349,8 +356,14 @@ class InstructAny2PixPipeline:
     @torch.no_grad()
     def denoise(self, base_latents, latent_la, *, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds,
                 inv_prompt_embeds=None, inv_pooled_prompt_embeds=None, alpha=0.7, num_inference_steps=25, cfg=10, scale=1.0, noise=None, seed=None,
-                edit_mask=None, auto_mask=None, sampler=None, sample_steps=None, step_noise=None, sample_adapters=None):
+                edit_mask=None, auto_mask=None, sampler=None, sample_steps=None, step_noise=None, sample_adapters=None,
+                control_image=None, control_scale=1.0, control_start=0.0, control_end=1.0):
         """inversion -> polar mixing -> IP-Adapter guided sampling; returns (sampled latents, inverted latents).
+        `control_image` (None: nothing changes, no launch and no bit; needs the pipeline built with controlnet=): the structure that must survive the edit -- a
+        condition map the caller brings (edges, depth, pose, a sketch), a PIL image, a uint8 / float array or a path, resized and cropped like the base image to
+        8 x the latent grid, values in [0, 1]. It guides the guided sampling stage only, at `control_scale` over the fraction [`control_start`, `control_end`] of
+        its steps (diffusers' `controlnet_conditioning_scale`, `control_guidance_start` / `_end`); a scale of 0 or a window that holds no step is the plain call.
+        The inversion, the automatic mask's evaluations, the refiner and the subject passes run without control.
         `sampler` ("ddim", "lcm"; None: what `self.pipe.scheduler` is -- DDIM, or LCM once an `LCMScheduler` is assigned there; with None nothing changes, no
         launch and no draw) and `sample_steps` (the length of the LCM schedule, default 4, 1 .. 50; refused under DDIM): the guided sampling stage runs the
         few-step consistency sampler for the length of the `generate` call -- the scheduler is swapped and put back, also when the call raises.
@@ -380,7 +393,12 @@ class InstructAny2PixPipeline:
         self.pipe_inversion.scheduler = DDIMScheduler.from_config(self.pipe.scheduler.config)  # :307
         if inv_prompt_embeds is None:        # reference inverts with prompt='' (:330); callers pass its embedding
             inv_prompt_embeds, inv_pooled_prompt_embeds = negative_prompt_embeds, negative_pooled_prompt_embeds
-        masked = {}
+        masked, control = {}, {}
+        if control_image is not None:
+            if self.controlnet is None:
+                raise ValueError("control_image needs the pipeline built with controlnet=<HipControlNetModel>")
+            control.update(image=self.control_tensor(control_image, base_latents), controlnet_conditioning_scale=float(control_scale),
+                          control_guidance_start=float(control_start), control_guidance_end=float(control_end))
         if edit_mask is not None:
             masked["edit_mask"] = resolve_edit_mask(self, edit_mask, base_latents, pixels=False)[1]
         if auto_mask is not None:
@@ -416,10 +434,34 @@ class InstructAny2PixPipeline:
                                                      scale=scale, mode="global", guidance_scale=cfg, latents=mixed,
                                                      prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                                                      pooled_prompt_embeds=pooled_prompt_embeds, negative_pooled_prompt_embeds=negative_pooled_prompt_embeds,
-                                                     output_type="latent", **masked)
+                                                     output_type="latent", **masked, **control)
         finally:
             self.pipe.scheduler = saved
         return images, latent_inv
+
+    def control_tensor(self, control_image, base_latents):
+        """a condition map -> fp16 [1, 3, 8 h, 8 w] in [0, 1] on the device: a path or PIL image goes through the base image's resize-and-crop and the 8-bit upload
+        (`ia2p_image_from_u8` without normalisation); a uint8 array [H, W, 3] likewise without the resize; float arrays / tensors ([3, H, W] or [1, 3, H, W], in [0, 1])
+        are taken as they are. The size must be 8 x the latent grid."""
+        from .image_processor import image_from_u8
+        H, W = 8 * base_latents.shape[-2], 8 * base_latents.shape[-1]
+        dev = self.pipe.unet.device
+        if isinstance(control_image, (str, os.PathLike)):
+            control_image = PIL.Image.open(control_image)
+        if isinstance(control_image, PIL.Image.Image):
+            control_image = np.asarray(resize_and_crop(control_image.convert("RGB"), (W, H), crop_type="middle").resize((W, H)))
+        if isinstance(control_image, np.ndarray) and control_image.dtype == np.uint8:
+            if control_image.ndim != 3 or control_image.shape[2] != 3:
+                raise ValueError(f"a uint8 control image is [H, W, 3]; got {control_image.shape}")
+            t = image_from_u8(torch.from_numpy(np.ascontiguousarray(control_image))[None].to(dev), normalize=False)
+        else:
+            t = torch.as_tensor(control_image)
+            if not t.is_floating_point():
+                raise ValueError("control_image: a path, a PIL image, a uint8 array [H, W, 3] or a float map in [0, 1]")
+            t = (t[None] if t.ndim == 3 else t).to(device=dev, dtype=torch.float16)
+        if t.ndim != 4 or tuple(t.shape[1:]) != (3, H, W):
+            raise ValueError(f"the control image must be 3 x {H} x {W} (8 x the latent grid {base_latents.shape[-2]} x {base_latents.shape[-1]}); got {tuple(t.shape)}")
+        return t.contiguous()
 
     def estimate_edit_mask(self, base_latents, latent_la, **kw):
         """The automatic edit mask of one request on explicit conditioning, for a caller who wants to look at it (or change it) before `denoise(edit_mask=)`:
@@ -737,7 +779,7 @@ class InstructAny2PixPipeline:
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
                  use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None,
                  edit_mask=None, edit_feather=8, *, auto_mask=None, lora_scale=None, sampler=None, sample_steps=None, sample_adapters=None,
-                 subject_mode="serial") -> Any:
+                 subject_mode="serial", control_image=None, control_scale=1.0, control_start=0.0, control_end=1.0) -> Any:
         """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
         `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images).
         `seed` (a 64-bit unsigned integer; None: every draw from the global CPU generator, as ever): every normal draw of the request comes from its own
@@ -768,6 +810,8 @@ class InstructAny2PixPipeline:
         `sampler`, `sample_steps`, `sample_adapters` (keyword only; None: nothing changes, no launch, no draw, no bit): the few-step consistency sampler for the
         guided sampling stage, and LoRA adapters active around that stage only (`denoise`). The conditioner may supply `step_noise`, which wins
         over the seed (draw 65537 of it), which wins over the global generator. The refiner and the subject passes are untouched.
+        `control_image`, `control_scale`, `control_start`, `control_end` (keyword only; None: nothing changes, no launch, no bit; needs controlnet=): a ControlNet
+        guides the guided sampling stage by the condition map the caller brings (`denoise`). The other stages run without control.
         `subject_mode` (keyword only; "serial": as ever, one inpainting loop per subject as the reference runs them): "joint" repaints all subjects in ONE
         loop -- every subject's image tokens in one context, each under its own mask, the blend under the union of the masks, one noise (draw
         DRAW_INPAINT + 0 of a seeded request). "joint" is NOT the serial result: in the serial form later passes see earlier repaints and draw their own
@@ -779,7 +823,11 @@ class InstructAny2PixPipeline:
                 return self(inst, mm_data, alpha=alpha, h=h, norm=norm, refinement=refinement, llm_only=llm_only, num_inference_steps=num_inference_steps,
                             use_cache=use_cache, debug=debug, diffusion_mode=diffusion_mode, subject_strength=subject_strength, cfg=cfg, scale=scale,
                             output_type=output_type, seed=seed, edit_mask=edit_mask, edit_feather=edit_feather, auto_mask=auto_mask, sampler=sampler,
-                            sample_steps=sample_steps, sample_adapters=sample_adapters, subject_mode=subject_mode)
+                            sample_steps=sample_steps, sample_adapters=sample_adapters, subject_mode=subject_mode, control_image=control_image,
+                            control_scale=control_scale, control_start=control_start, control_end=control_end)
+        if control_image is not None and self.controlnet is None:
+            raise ValueError("control_image needs the pipeline built with controlnet=<HipControlNetModel>")
+        control = {} if control_image is None else dict(control_image=control_image, control_scale=control_scale, control_start=control_start, control_end=control_end)
         if seed is not None:
             seed = _noise.check_seed(seed)
         few, smp = {}, "ddim"
@@ -830,7 +878,7 @@ class InstructAny2PixPipeline:
                                           inv_prompt_embeds=c.get("inv_prompt_embeds"), inv_pooled_prompt_embeds=c.get("inv_pooled_prompt_embeds"),
                                           alpha=alpha, num_inference_steps=num_inference_steps, cfg=cfg, scale=scale, seed=seed,
                                           noise=c.get("polar_noise") if seed is not None else None, **masked,      # (unseeded: this call has always drawn its own)
-                                          **few, **({"step_noise": c["step_noise"]} if smp == "lcm" and c.get("step_noise") is not None else {}))
+                                          **few, **({"step_noise": c["step_noise"]} if smp == "lcm" and c.get("step_noise") is not None else {}), **control)
         non_refined = images
         oo = images
         decoded = None          # the decode of `images`, when the refiner hand-over made it

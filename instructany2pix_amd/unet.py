@@ -253,10 +253,77 @@ class HipUNet2DConditionModel(_ffi.Executor):
                 _ffi.check(self._lib.ia2p_set_ip_adapter(self._ctx, 1, sig[2], sig[1]), self._ctx)
         return (out,) if not return_dict else SimpleNamespace(sample=out)
 
+    def _channels_last(self, t, B, C_, H, W, what):
+        """a logical-NCHW residual [B, C, H, W] as a channels-last device buffer: by pointer when its strides already are, converted otherwise"""
+        t = torch.as_tensor(t)
+        if tuple(t.shape) != (B, C_, H, W):
+            raise ValueError(f"{what} has shape {tuple(t.shape)}, this UNet's tensor there is {(B, C_, H, W)}")
+        t = t.to(device=self.device, dtype=torch.float16)
+        nhwc = t.permute(0, 2, 3, 1)
+        if not nhwc.is_contiguous() or nhwc.data_ptr() % 16:
+            nhwc = nhwc.contiguous()
+            if nhwc.data_ptr() % 16:
+                nhwc = nhwc.clone()
+        return nhwc
+
+    def skip_shapes(self, h: int, w: int):
+        """[(channels, height, width)] of the tensors the down path leaves for the up path at an h x w latent, in skip order -- the shapes of
+        `down_block_additional_residuals`; the mid block's output is (block_out_channels[-1], height, width of the last entry)"""
+        ch = list(self.config.block_out_channels)
+        out = [(ch[0], h, w)]
+        for i in range(len(ch)):
+            out += [(ch[i], h, w)] * self.config.layers_per_block
+            if i != len(ch) - 1:
+                h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+                out.append((ch[i], h, w))
+        return out
+
+    def _call_controlled(self, down, mid, sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict, out, ip_scales):
+        """`ia2p_unet_forward_c`: the per-row pass plus the residuals, injected in place where the up path pops each skip. Every refusal comes before any launch."""
+        self._sync_processors()
+        B, c_in, h, w = sample.shape
+        if c_in != self.config.in_channels:
+            raise ValueError(f"sample has {c_in} channels, expected {self.config.in_channels}")
+        shapes = self.skip_shapes(h, w)
+        if len(down) != len(shapes):
+            raise ValueError(f"{len(down)} down_block_additional_residuals, this UNet has {len(shapes)} skips")
+        f16 = lambda t: t.to(device=self.device, dtype=torch.float16).contiguous()      # noqa: E731
+        ctx_in = encoder_hidden_states
+        sample, ctx = f16(sample), f16(encoder_hidden_states)
+        te, tid = f16(added_cond_kwargs["text_embeds"]), f16(added_cond_kwargs["time_ids"])
+        if ctx.shape[0] != B or ctx.shape[2] != self.config.cross_attention_dim:
+            raise ValueError(f"encoder_hidden_states must be [B, L, {self.config.cross_attention_dim}]")
+        if te.shape != (B, self.config.pooled_dim) or tid.shape != (B, self.config.num_time_ids):
+            raise ValueError("added_cond_kwargs do not fit this UNet's text_time embedding")
+        keep = [self._channels_last(t, B, c_, hh, ww, f"down_block_additional_residuals[{k}]") for k, (t, (c_, hh, ww)) in enumerate(zip(down, shapes))]
+        keep.append(self._channels_last(mid, B, self.config.block_out_channels[-1], shapes[-1][1], shapes[-1][2], "mid_block_additional_residual"))
+        L = ctx.shape[1]
+        ts = timestep if torch.is_tensor(timestep) else torch.full((B,), float(timestep))
+        ts = ts.to(device=self.device, dtype=torch.float32).reshape(-1)
+        ts = (ts.expand(B) if ts.numel() == 1 else ts).contiguous()
+        if ts.numel() != B:
+            raise ValueError(f"timestep tensor has {ts.numel()} elements for a batch of {B}")
+        sc = None
+        if ip_scales is not None:
+            sc = torch.as_tensor(ip_scales).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+            if sc.numel() != B:
+                raise ValueError(f"ip_scales has {sc.numel()} elements for a batch of {B}")
+        ws = self.workspace_for(B, h, w, L)
+        if out is None:
+            out = torch.empty(B, self.config.out_channels, h, w, dtype=torch.float16, device=self.device)
+        kv = self._context_kv(ctx_in, ctx, B, L, ws) if self.cache_context_kv else None
+        ptrs = (C.c_void_p * len(down))(*[t.data_ptr() for t in keep[:-1]])
+        _ffi.check(self._lib.ia2p_unet_forward_c(self._ctx, _ffi.current_stream(), _ffi.ptr(sample), _ffi.ptr(ts), _ffi.ptr(sc) if sc is not None else None,
+                                                 None if kv is not None else _ffi.ptr(ctx), _ffi.ptr(kv) if kv is not None else None, L, _ffi.ptr(te), _ffi.ptr(tid),
+                                                 _ffi.ptr(out), B, h, w, _ffi.ptr(ws), ws.numel(), ptrs, len(down), C.c_void_p(keep[-1].data_ptr()), None, 0), self._ctx)
+        return (out,) if not return_dict else SimpleNamespace(sample=out)
+
     def __call__(self, sample, timestep, encoder_hidden_states=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                  return_dict: bool = False, out: Optional[torch.Tensor] = None, _tune_reps: Optional[int] = None,
-                 ip_scales: Optional[torch.Tensor] = None, **unused):
-        """cross_attention_kwargs={"ip_adapter_masks": t} (t [B, G, h, w] on the latent grid of `sample`, or [G, h, w] for every row): regional image prompts -- the
+                 ip_scales: Optional[torch.Tensor] = None, down_block_additional_residuals=None, mid_block_additional_residual=None, **unused):
+        """down_block_additional_residuals / mid_block_additional_residual (diffusers' names): a ControlNet's residuals, one logical-NCHW tensor per skip and one for the
+        mid block's output; tensors with channels-last strides (what `HipControlNetModel` returns) are passed by pointer, others are converted. Both None: today's path.
+        cross_attention_kwargs={"ip_adapter_masks": t} (t [B, G, h, w] on the latent grid of `sample`, or [G, h, w] for every row): regional image prompts -- the
         last 4 G rows of the context are G groups of four image tokens, group g acts where t[:, g] says (diffusers' `ip_adapter_masks`; `ia2p_unet_forward_r`).
         `timestep`: a number / 0-dim tensor as the reference passes it, or a [B] tensor -- one timestep per batch element, as diffusers' UNet
         accepts (`ia2p_unet_forward_v`); `ip_scales` (or cross_attention_kwargs={"ip_scales": ...}): optional [B] tensor, the IP-Adapter scale of
@@ -265,6 +332,18 @@ class HipUNet2DConditionModel(_ffi.Executor):
             raise ValueError("encoder_hidden_states and added_cond_kwargs (text_embeds, time_ids) are required (text_time UNet)")
         if "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
             raise ValueError("added_cond_kwargs must carry `text_embeds` and `time_ids`")      # diffusers raises ValueError here too
+        controlled = down_block_additional_residuals is not None or mid_block_additional_residual is not None
+        if controlled:
+            if down_block_additional_residuals is None or mid_block_additional_residual is None:
+                raise ValueError("down_block_additional_residuals and mid_block_additional_residual come together")
+            if cross_attention_kwargs and cross_attention_kwargs.get("ip_adapter_masks") is not None:
+                raise ValueError("ControlNet residuals together with ip_adapter_masks: the regional pass is not combined with a ControlNet")
+            if _tune_reps is not None:
+                raise ValueError("autotune takes no ControlNet residuals")
+            if ip_scales is None and cross_attention_kwargs:
+                ip_scales = cross_attention_kwargs.get("ip_scales")
+            return self._call_controlled(list(down_block_additional_residuals), mid_block_additional_residual, sample, timestep, encoder_hidden_states,
+                                         added_cond_kwargs, return_dict, out, ip_scales)
         if cross_attention_kwargs and cross_attention_kwargs.get("ip_adapter_masks") is not None:
             if _tune_reps is not None:
                 raise ValueError("autotune takes no ip_adapter_masks")

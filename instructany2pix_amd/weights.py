@@ -115,6 +115,36 @@ def unet_param_specs(cfg: UNetConfig) -> List[Spec]:
     return s
 
 
+def controlnet_skip_channels(cfg: UNetConfig) -> List[int]:
+    """channels of the tensors the down path leaves for the up path, in skip order: conv_in's output, every block's, every downsampler's"""
+    ch = list(cfg.block_out_channels)
+    out = [ch[0]]
+    for i in range(len(ch)):
+        out += [ch[i]] * cfg.layers_per_block
+        if i != len(ch) - 1:
+            out.append(ch[i])
+    return out
+
+
+def controlnet_param_specs(cfg) -> List[Spec]:
+    """Every parameter of diffusers' `ControlNetModel` (0.26.3) for `cfg` (config.ControlNetConfig): the UNet's own keys for conv_in, the embeddings, the down path
+    and the mid block; `controlnet_cond_embedding.{conv_in, blocks.0..5, conv_out}`; `controlnet_down_blocks.k` (1x1, one per skip, skip order) and
+    `controlnet_mid_block`. The synthetic zero convolutions are NOT zero (a trained ControlNet's are not either): with zeros every test of the path would be vacuous."""
+    s = [sp for sp in unet_param_specs(cfg) if not sp[0].startswith(("up_blocks.", "conv_norm_out.", "conv_out."))]
+    e = tuple(cfg.conditioning_embedding_out_channels)
+    p = "controlnet_cond_embedding"
+    s += [(f"{p}.conv_in.weight", (e[0], cfg.conditioning_channels, 3, 3), "w"), (f"{p}.conv_in.bias", (e[0],), "b")]
+    for i in range(3):
+        s += [(f"{p}.blocks.{2 * i}.weight", (e[i], e[i], 3, 3), "w"), (f"{p}.blocks.{2 * i}.bias", (e[i],), "b"),
+              (f"{p}.blocks.{2 * i + 1}.weight", (e[i + 1], e[i], 3, 3), "w"), (f"{p}.blocks.{2 * i + 1}.bias", (e[i + 1],), "b")]
+    s += [(f"{p}.conv_out.weight", (cfg.block_out_channels[0], e[3], 3, 3), "w"), (f"{p}.conv_out.bias", (cfg.block_out_channels[0],), "b")]
+    for k, c in enumerate(controlnet_skip_channels(cfg)):
+        s += [(f"controlnet_down_blocks.{k}.weight", (c, c, 1, 1), "w"), (f"controlnet_down_blocks.{k}.bias", (c,), "b")]
+    cm = cfg.block_out_channels[-1]
+    s += [("controlnet_mid_block.weight", (cm, cm, 1, 1), "w"), ("controlnet_mid_block.bias", (cm,), "b")]
+    return s
+
+
 def attn_processor_names(cfg: UNetConfig) -> List[str]:
     """Keys of `unet.attn_processors` in diffusers' module-registration order: down_blocks, up_blocks,
     mid_block. The position in this list is the `<idx>` of the IP-Adapter

@@ -60,7 +60,16 @@ latents: 50 steps at strength 0.7 = 35 UNet evaluations of 2 rows per loop, IP s
 Only the base UNet and the IP-Adapter are built. Printed per S: ms per stage of both (median, min..max), serial / joint, and ms per UNet step of the regional route
 against the plain one (stage time over the loop's steps; the image-token projection and the start launch are in it).
 
-    python tools/e2e_edit_bench.py --subjects 1,2,4 --subject-mode serial,joint"""
+    python tools/e2e_edit_bench.py --subjects 1,2,4 --subject-mode serial,joint
+
+--control times the GUIDED SAMPLING STAGE of one full-size request alone (`IPAdapterXL.generate` over `StableDiffusionXLControlNetPipeline`: --steps steps, guidance 10,
+B_eff = 2) with and without a full-size ControlNet of seeded synthetic weights (scale 1, the whole window): the two sides alternate --reps times after both have run once
+untimed; a host clock around a device synchronise. Only the base UNet, the IP-Adapter and the ControlNet are built. Printed: ms per stage of both (median, min..max), ms
+per step of both and their ratio (a controlled step is one ControlNet evaluation -- the UNet's down path and mid block, ten small GEMMs -- plus the UNet with ten
+injections: dearer than two plain steps would mean something is wrong), and the one-off cost of `embed_condition` (median of --reps, the condition image on the device).
+The uncontrolled side is the plain pipeline's call: it is the number to hold against another build's.
+
+    python tools/e2e_edit_bench.py --control [--steps 25] [--reps 5]"""
 import argparse
 import os
 import sys
@@ -98,6 +107,7 @@ _ap.add_argument("--auto-mask", type=int, nargs="?", const=8, default=None, meta
 _ap.add_argument("--lcm", type=int, default=None, metavar="N", help="with --batch: the same requests sampled by the N-step consistency sampler next to the DDIM run, and the two update launches alone")
 _ap.add_argument("--subjects", default=None, help="comma-separated subject counts: time the subject-consistency stage of one request alone (see the module docstring)")
 _ap.add_argument("--subject-mode", default="serial,joint", help="with --subjects: the forms to time, interleaved")
+_ap.add_argument("--control", action="store_true", help="time the guided sampling stage of one request with and without a ControlNet (see the module docstring)")
 _ap.add_argument("--steps", type=int, default=25)
 _ap.add_argument("--refinement", type=float, default=0.5)
 ARGS = _ap.parse_args()
@@ -115,6 +125,54 @@ PX = int(os.environ.get("PX", 1024))
 t_all = time.perf_counter()
 bcfg, rcfg, vcfg = sdxl_base(), sdxl_refiner(), sdxl_vae()
 base = HipUNet2DConditionModel(bcfg, DEV); base.load_state_dict(iter_synthetic(unet_param_specs(bcfg), 7, DEV, torch.float16))
+if ARGS.control:
+    import statistics
+    from instructany2pix_amd.config import controlnet_sdxl
+    from instructany2pix_amd.controlnet import HipControlNetModel
+    from instructany2pix_amd.ddim import StableDiffusionXLControlNetPipeline
+    from instructany2pix_amd.ip_adapter import IPAdapterXL
+    from instructany2pix_amd.weights import controlnet_param_specs
+    ccfg = controlnet_sdxl()
+    cn = HipControlNetModel(ccfg, DEV); cn.load_state_dict(iter_synthetic(controlnet_param_specs(ccfg), 13, DEV, torch.float16))
+    specs = ip_adapter_specs(bcfg, 1024)
+    ipa = IPAdapterXL(StableDiffusionXLControlNetPipeline(base, cn), "", ip_ckpt={"image_proj": synthetic_state_dict(specs["image_proj"], seed=7),
+                                                                                "ip_adapter": synthetic_state_dict(specs["ip_adapter"], seed=7)}, device=DEV, clip_embeddings_dim=1024)
+    print(f"models ready in {time.perf_counter() - t_all:.1f} s (base UNet + IP-Adapter, ControlNet: arena {cn.arena.numel() / 1e9:.2f} GB)", flush=True)
+    gg = torch.Generator().manual_seed(3)
+    rn = lambda *sh: torch.randn(*sh, generator=gg)      # noqa: E731
+    hl = PX // 8
+    kw = dict(clip_image_embeds=rn(1024), prompt_embeds=rn(1, 77, bcfg.cross_attention_dim).half(), pooled_prompt_embeds=rn(1, bcfg.pooled_dim).half(),
+              negative_prompt_embeds=rn(1, 77, bcfg.cross_attention_dim).half(), negative_pooled_prompt_embeds=rn(1, bcfg.pooled_dim).half(),
+              latents=rn(1, 4, hl, hl).half(), num_inference_steps=ARGS.steps, guidance_scale=10, scale=1.0, output_type="latent")
+    cond = torch.rand(1, 3, PX, PX, generator=gg).half().to(DEV)
+
+    def stage(controlled):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = ipa.generate(**kw, **(dict(image=cond, controlnet_conditioning_scale=1.0) if controlled else {}))
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out.float()).all())
+        return (time.perf_counter() - t0) * 1e3
+
+    def embed():
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        cn.embed_condition(cond)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    print(f"# {PX} x {PX}, guided sampling stage alone: {ARGS.steps} steps, guidance 10, B_eff = 2; {ARGS.reps} alternating repeats after one untimed run of each; cost-model plans", flush=True)
+    for c_ in (False, True):
+        stage(c_)
+    embed()
+    ms = {False: [], True: []}
+    for _ in range(ARGS.reps):
+        for c_ in (False, True):
+            ms[c_].append(stage(c_))
+    em = [embed() for _ in range(ARGS.reps)]
+    med = {c_: statistics.median(v) for c_, v in ms.items()}
+    print("; ".join(f"{'controlled' if c_ else 'plain'} {med[c_]:.1f} ms (min {min(v):.1f}, max {max(v):.1f})" for c_, v in ms.items()), flush=True)
+    print(f"ms per step: plain {med[False] / ARGS.steps:.2f}, controlled {med[True] / ARGS.steps:.2f}, "
+          f"controlled / plain {med[True] / med[False]:.3f}; embed_condition alone {statistics.median(em):.2f} ms (min {min(em):.2f}, max {max(em):.2f})", flush=True)
+    sys.exit(0)
 ref = HipUNet2DConditionModel(rcfg, DEV); ref.load_state_dict(iter_synthetic(unet_param_specs(rcfg), 11, DEV, torch.float16))
 if ARGS.subjects:
     import statistics
