@@ -543,6 +543,44 @@ ia2p_status ia2p_image_to_f32(void* stream, const void* src, float* dst, int B, 
  * = ia2p_image_from_u8(ia2p_image_to_u8(x), normalize = 1) element-wise. dst may equal src. */
 ia2p_status ia2p_image_requantize(void* stream, const void* src, void* dst, int64_t n);
 
+/* ---- condition maps: what a ControlNet is guided by, made from the base image on the device ---------------------------------------------------
+ * New: the reference attaches no ControlNet and makes no condition map. The Canny detector restates OpenCV's cv::Canny (8-bit input, aperture 3) and its 8-bit
+ * RGB2GRAY rule; OpenCV is not installed next to this library: parity with it is restated in tests/canny_ref.py, not pinned.
+ * All images are device pointers, u8, [B, H, W] or [B, H, W, C] (HWC, as the image codec above); 1 <= H, W and B*H*W*3 < 2^31. Integer arithmetic only: every
+ * result is exact, independent of summation order and of scheduling. Arguments are checked before any HIP call: null pointers, aliasing, misalignment, bad knobs
+ * are IA2P_ERR_INVALID, bad sizes IA2P_ERR_SHAPE, a workspace that is too small IA2P_ERR_NOMEM.
+ *
+ * image_grey_u8: rgb [B, H, W, 3] -> grey [B, H, W]:  Y = (4899 R + 9617 G + 1868 B + 8192) >> 14.
+ * image_gauss_u8: src, dst [B, H, W, C], C = 1 or 3; separable blur with a replicated border. taps: a HOST array of r + 1 integers q_0 .. q_r (centre first, the
+ *   kernel is symmetric), 0 <= r <= 32, q_0 + 2 sum_{i >= 1} q_i == 4096 (checked). rows: row = sum_i q_|i| src[x + i] (32-bit, to the workspace); columns:
+ *   dst = (sum_j q_|j| row[y + j] + 2^23) >> 24. r = 0 copies. dst may equal src. workspace: ia2p_image_gauss_workspace_bytes, 4-byte aligned.
+ * canny_u8: grey [B, H, W] -> edges [B, H, W] in {0, 255}.
+ *   gradients  dx, dy: the 3x3 Sobel responses ([-1 0 1; -2 0 2; -1 0 1] and its transpose) of the grey image with a REPLICATED border.
+ *   magnitude  m = |dx| + |dy|, lo = floor(low), hi = floor(high); with l2_gradient: m = dx^2 + dy^2, lo = floor(low)^2, hi = floor(high)^2. m is 0 outside the image.
+ *   non-maximum suppression, only where m > lo; with x = |dx|, y = |dy| << 15, t22 = x * 13573, t67 = t22 + (x << 16):
+ *     y < t22:   keep iff m > m[y, x-1] and m >= m[y, x+1]
+ *     y > t67:   keep iff m > m[y-1, x] and m >= m[y+1, x]
+ *     otherwise, s = -1 if (dx ^ dy) < 0 else 1:  keep iff m > m[y-1, x-s] and m > m[y+1, x+s]
+ *     a kept pixel is STRONG if m > hi, else WEAK; every other pixel is OFF.
+ *   hysteresis a weak pixel is an edge iff it is 8-connected, through weak or strong pixels, to a strong one. 255 on edges, 0 elsewhere.
+ *   low > high swaps the two; negative or non-finite thresholds are IA2P_ERR_INVALID. edges may not alias grey.
+ *   The hysteresis runs in rounds over 64 x 64 tiles of a state map (0 off, 1 weak, 2 edge) until a round promotes nothing; the host reads a 16-byte flag block per
+ *   group of four rounds, so the call SYNCHRONISES the stream and cannot be captured into a graph. *rounds_out (may be NULL): the first round that promoted nothing.
+ *   The loop is bounded by ia2p_canny_max_rounds = 2 B ring(H, W) + 2, ring = the pixels on the outermost ring of their tile (condition maps); on
+ *   reaching the bound the call returns IA2P_ERR_STATE and no map. workspace: ia2p_canny_workspace_bytes (the state map, then the flags), 4-byte aligned.
+ * canny_hysteresis_u8: the second half of canny_u8 on a state map [B, H, W] the caller brings (values other than 1 and 2 count as off); the map is not changed.
+ * condition_from_u8: map [B, H, W, C_in], C_in = 1 or 3 -> fp16 [B, 3, H, W], q / 255 with one rounding: bit for bit what ia2p_image_from_u8 with normalize = 0 gives
+ *   for the same byte; a one-channel map is replicated to three. */
+ia2p_status ia2p_image_grey_u8(void* stream, const void* rgb, void* grey, int B, int H, int W);
+size_t ia2p_image_gauss_workspace_bytes(int B, int H, int W, int C);
+ia2p_status ia2p_image_gauss_u8(void* stream, const void* src, void* dst, void* workspace, int B, int H, int W, int C, const uint16_t* taps, int r);
+size_t ia2p_canny_workspace_bytes(int B, int H, int W);
+int64_t ia2p_canny_max_rounds(int B, int H, int W);
+ia2p_status ia2p_canny_u8(void* stream, const void* grey, void* edges, void* workspace, size_t workspace_bytes, int B, int H, int W, float low, float high,
+                          int l2_gradient, int* rounds_out);
+ia2p_status ia2p_canny_hysteresis_u8(void* stream, const void* state, void* edges, void* workspace, size_t workspace_bytes, int B, int H, int W, int* rounds_out);
+ia2p_status ia2p_condition_from_u8(void* stream, const void* map_u8, void* dst_f16, int B, int H, int W, int C_in);
+
 /* ---- CLIP text encoders (conditioning side): the two encoders behind `encode_prompt` ------------------
  * (reference ddim/sdxl_pipeline.py:202-395: `text_encoder(ids, output_hidden_states=True)`, `.hidden_states[-2]` of both encoders
  * concatenated, pooled `[0]` of the second). transformers `CLIPTextModel` / `CLIPTextModelWithProjection` semantics: token + position

@@ -290,6 +290,14 @@ SIGNATURES = {
     "ia2p_image_to_u8": (_I, [_P, _P, _P, _I, _I, _I, _I]),
     "ia2p_image_to_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
     "ia2p_image_requantize": (_I, [_P, _P, _P, _I64]),
+    "ia2p_image_grey_u8": (_I, [_P, _P, _P, _I, _I, _I]),
+    "ia2p_image_gauss_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ia2p_image_gauss_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_uint16), _I]),
+    "ia2p_canny_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "ia2p_canny_max_rounds": (_I64, [_I, _I, _I]),
+    "ia2p_canny_u8": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, _F, _F, _I, C.POINTER(_I)]),
+    "ia2p_canny_hysteresis_u8": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, C.POINTER(_I)]),
+    "ia2p_condition_from_u8": (_I, [_P, _P, _P, _I, _I, _I, _I]),
     "ia2p_profile_enable": (_I, [_P, _I]),
     "ia2p_profile_classes": (_I, []),
     "ia2p_profile_read_region": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDES = [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ia2p.h", "ia2p_debug.h")]
 OUT = os.path.join(HERE, "libia2p_hip.so")
-SOURCES = ["gemm.hip", "qxattn.hip", "attention.hip", "attention_regions.hip", "norm.hip", "misc.hip", "engine_rt.hip", "engine.hip", "ops_abi.hip", "vae_engine.hip", "clip_engine.hip", "vit.hip", "vit_engine.hip", "llm_engine.hip", "image.hip", "sample.hip", "noise.hip", "auto_mask.hip", "lora.hip", "sam.hip", "sam_engine.hip", "lcm.hip", "controlnet.hip"]
+SOURCES = ["gemm.hip", "qxattn.hip", "attention.hip", "attention_regions.hip", "norm.hip", "misc.hip", "engine_rt.hip", "engine.hip", "ops_abi.hip", "vae_engine.hip", "clip_engine.hip", "vit.hip", "vit_engine.hip", "llm_engine.hip", "image.hip", "sample.hip", "noise.hip", "auto_mask.hip", "lora.hip", "sam.hip", "sam_engine.hip", "lcm.hip", "controlnet.hip", "condition.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"] + os.environ.get("IA2P_EXTRA_FLAGS", "").split()    # (A/B builds of compile-time knobs)
 # attention: MFMA results feed VALU softmax directly; the VGPR form avoids ~250 v_accvgpr_read/write per key tile

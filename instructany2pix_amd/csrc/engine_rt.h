@@ -70,6 +70,15 @@ hipError_t ia2p_launch_known_blend(const half_t* x, const half_t* known, const i
 hipError_t ia2p_launch_mask_to_latent(const uint8_t* mask, half_t* out, int B, int H, int W, int f, hipStream_t s);
 hipError_t ia2p_launch_mask_feather_u8(const uint8_t* mask, uint8_t* out, uint16_t* ws, int B, int H, int W, int r, hipStream_t s);
 hipError_t ia2p_launch_image_composite_u8(const uint8_t* edited, const uint8_t* base, const uint8_t* alpha, uint8_t* out, int B, int H, int W, int C, hipStream_t s);
+// condition.hip: the condition-map kernels behind ia2p_image_grey_u8 / ia2p_image_gauss_u8 / ia2p_canny_u8 / ia2p_condition_from_u8 (arguments checked in ops_abi.hip)
+struct GaussTaps { uint16_t q[33]; };          // q_0 .. q_r, centre first; travels as a kernel argument
+hipError_t ia2p_launch_grey_u8(const uint8_t* rgb, uint8_t* grey, int npix, hipStream_t s);
+hipError_t ia2p_launch_gauss_u8(const uint8_t* src, uint8_t* dst, uint32_t* ws, int B, int H, int W, int C, const GaussTaps& taps, int r, hipStream_t s);
+hipError_t ia2p_launch_canny_classify(const uint8_t* grey, uint8_t* state, int B, int H, int W, int lo, int hi, int l2, hipStream_t s);
+int64_t ia2p_canny_round_bound(int B, int H, int W);
+hipError_t ia2p_run_canny_hysteresis(uint8_t* state, uint32_t* flags, int B, int H, int W, int64_t bound, int64_t* rounds, bool* converged, hipStream_t s);
+hipError_t ia2p_launch_canny_finish(const uint8_t* state, uint8_t* edges, int n, hipStream_t s);
+hipError_t ia2p_launch_condition_from_u8_c1(const uint8_t* map, half_t* dst, int B, int HW, hipStream_t s);
 hipError_t ia2p_launch_cat_rows(const half_t* a, int Ka, const half_t* b, int Kb, const half_t* bias_a, const half_t* bias_b, half_t* dst, half_t* bias_dst, int rows, hipStream_t s);
 hipError_t ia2p_launch_fold_ln(const half_t* W, const half_t* gamma, const half_t* beta, const half_t* bias, half_t* Wf, float* cs, float* lb,
                                int N, int K, hipStream_t s);

@@ -92,6 +92,122 @@ ia2p_status ia2p_image_composite_u8(void* stream, const void* edited, const void
   return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "image_composite_u8");
 }
 
+// ---- condition maps from the base image (condition.hip): grey, Gaussian blur, Canny, and the conversion a ControlNet takes. Every refusal comes before any HIP call. ----
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + nb && pb < pa + na;
+}
+static size_t canny_state_bytes(int B, int H, int W) { return (((size_t)B * H * W) + 15) & ~(size_t)15; }
+
+ia2p_status ia2p_image_grey_u8(void* stream, const void* rgb, void* grey, int B, int H, int W) {
+  if (!rgb || !grey) return fail(nullptr, IA2P_ERR_INVALID, "image_grey_u8: null pointer");
+  ia2p_status st = check_mask_image("image_grey_u8", B, H, W, 3);
+  if (st != IA2P_OK) return st;
+  if (ranges_overlap(rgb, (size_t)B * H * W * 3, grey, (size_t)B * H * W)) return fail(nullptr, IA2P_ERR_INVALID, "image_grey_u8: grey may not overlap rgb");
+  hipError_t e = ia2p_launch_grey_u8((const uint8_t*)rgb, (uint8_t*)grey, B * H * W, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "image_grey_u8");
+}
+
+size_t ia2p_image_gauss_workspace_bytes(int B, int H, int W, int C) {
+  if (B < 1 || H < 1 || W < 1 || C < 1) return 0;
+  return (size_t)B * H * W * C * sizeof(uint32_t);
+}
+
+ia2p_status ia2p_image_gauss_u8(void* stream, const void* src, void* dst, void* workspace, int B, int H, int W, int C, const uint16_t* taps, int r) {
+  if (!src || !dst || !workspace || !taps) return fail(nullptr, IA2P_ERR_INVALID, "image_gauss_u8: null pointer");
+  if (((uintptr_t)workspace & 3) != 0) return fail(nullptr, IA2P_ERR_INVALID, "image_gauss_u8: the workspace holds 32-bit sums and must be 4-byte aligned");
+  if (C != 1 && C != 3) return fail(nullptr, IA2P_ERR_SHAPE, "image_gauss_u8: C=%d (1 or 3 channels)", C);
+  ia2p_status st = check_mask_image("image_gauss_u8", B, H, W, 3);
+  if (st != IA2P_OK) return st;
+  if (r < 0 || r > 32) return fail(nullptr, IA2P_ERR_INVALID, "image_gauss_u8: r=%d (0 .. 32)", r);
+  const size_t n = (size_t)B * H * W * C;
+  if (ranges_overlap(workspace, n * 4, src, n) || ranges_overlap(workspace, n * 4, dst, n)) return fail(nullptr, IA2P_ERR_INVALID, "image_gauss_u8: the workspace overlaps an image");
+  if (dst != src && ranges_overlap(src, n, dst, n)) return fail(nullptr, IA2P_ERR_INVALID, "image_gauss_u8: dst overlaps src (dst == src, in place, is allowed)");
+  GaussTaps t;
+  memset(&t, 0, sizeof t);
+  uint32_t sum = taps[0];
+  t.q[0] = taps[0];
+  for (int i = 1; i <= r; ++i) { t.q[i] = taps[i]; sum += 2u * taps[i]; }
+  if (sum != 4096u) return fail(nullptr, IA2P_ERR_INVALID, "image_gauss_u8: q_0 + 2 sum q_i = %u, must be 4096", sum);
+  hipError_t e = ia2p_launch_gauss_u8((const uint8_t*)src, (uint8_t*)dst, (uint32_t*)workspace, B, H, W, C, t, r, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "image_gauss_u8");
+}
+
+size_t ia2p_canny_workspace_bytes(int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1) return 0;
+  return canny_state_bytes(B, H, W) + 16;      // the state map, then the round flags
+}
+
+int64_t ia2p_canny_max_rounds(int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1) return 0;
+  return ia2p_canny_round_bound(B, H, W);
+}
+
+static ia2p_status check_canny(const char* what, const void* in, const void* edges, const void* workspace, size_t workspace_bytes, int B, int H, int W) {
+  if (!in || !edges || !workspace) return fail(nullptr, IA2P_ERR_INVALID, "%s: null pointer", what);
+  if (((uintptr_t)workspace & 3) != 0) return fail(nullptr, IA2P_ERR_INVALID, "%s: the workspace must be 4-byte aligned", what);
+  ia2p_status st = check_mask_image(what, B, H, W, 3);
+  if (st != IA2P_OK) return st;
+  const size_t n = (size_t)B * H * W;
+  if (ranges_overlap(in, n, edges, n)) return fail(nullptr, IA2P_ERR_INVALID, "%s: edges may not alias the input", what);
+  if (workspace_bytes < ia2p_canny_workspace_bytes(B, H, W)) return fail(nullptr, IA2P_ERR_NOMEM, "%s: workspace too small (%zu bytes, %zu needed)", what, workspace_bytes, ia2p_canny_workspace_bytes(B, H, W));
+  if (ranges_overlap(workspace, workspace_bytes, in, n) || ranges_overlap(workspace, workspace_bytes, edges, n)) return fail(nullptr, IA2P_ERR_INVALID, "%s: the workspace overlaps an image", what);
+  return IA2P_OK;
+}
+
+// the rounds of the hysteresis over the state map at the head of the workspace, then the 0 / 255 output
+static ia2p_status canny_finish_from_state(const char* what, void* stream, void* edges, void* workspace, int B, int H, int W, int* rounds_out) {
+  uint8_t* state = (uint8_t*)workspace;
+  uint32_t* flags = (uint32_t*)(state + canny_state_bytes(B, H, W));
+  const int64_t bound = ia2p_canny_round_bound(B, H, W);
+  int64_t rounds = 0;
+  bool converged = false;
+  hipError_t e = ia2p_run_canny_hysteresis(state, flags, B, H, W, bound, &rounds, &converged, (hipStream_t)stream);
+  if (rounds_out) *rounds_out = (int)std::min<int64_t>(rounds, INT32_MAX);
+  if (e != hipSuccess) return fail_hip(nullptr, e, what);
+  if (!converged) return fail(nullptr, IA2P_ERR_STATE, "%s: the hysteresis still promoted pixels in round %lld, its bound for B=%d H=%d W=%d: no map is returned", what, (long long)bound, B, H, W);
+  e = ia2p_launch_canny_finish(state, (uint8_t*)edges, B * H * W, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, what);
+}
+
+ia2p_status ia2p_canny_u8(void* stream, const void* grey, void* edges, void* workspace, size_t workspace_bytes, int B, int H, int W, float low, float high,
+                          int l2_gradient, int* rounds_out) {
+  if (rounds_out) *rounds_out = 0;
+  ia2p_status st = check_canny("canny_u8", grey, edges, workspace, workspace_bytes, B, H, W);
+  if (st != IA2P_OK) return st;
+  if (!(low >= 0.f) || !(high >= 0.f) || std::isinf(low) || std::isinf(high)) return fail(nullptr, IA2P_ERR_INVALID, "canny_u8: thresholds low=%g high=%g must be finite and >= 0", (double)low, (double)high);
+  if (l2_gradient != 0 && l2_gradient != 1) return fail(nullptr, IA2P_ERR_INVALID, "canny_u8: l2_gradient=%d (0 or 1)", l2_gradient);
+  if (low > high) std::swap(low, high);
+  // no magnitude exceeds 2040 (|dx| + |dy|) or 2 * 1020^2: thresholds are clamped to 4096 before the square, which keeps every comparison as it was
+  int lo = (int)std::floor(std::min(low, 4096.f)), hi = (int)std::floor(std::min(high, 4096.f));
+  if (l2_gradient) { lo *= lo; hi *= hi; }
+  hipError_t e = ia2p_launch_canny_classify((const uint8_t*)grey, (uint8_t*)workspace, B, H, W, lo, hi, l2_gradient, (hipStream_t)stream);
+  if (e != hipSuccess) return fail_hip(nullptr, e, "canny_u8");
+  return canny_finish_from_state("canny_u8", stream, edges, workspace, B, H, W, rounds_out);
+}
+
+// the second half of ia2p_canny_u8 on a state map the caller brings (0 off, 1 weak, 2 strong; any other value counts as off)
+ia2p_status ia2p_canny_hysteresis_u8(void* stream, const void* state, void* edges, void* workspace, size_t workspace_bytes, int B, int H, int W, int* rounds_out) {
+  if (rounds_out) *rounds_out = 0;
+  ia2p_status st = check_canny("canny_hysteresis_u8", state, edges, workspace, workspace_bytes, B, H, W);
+  if (st != IA2P_OK) return st;
+  hipError_t e = hipMemcpyAsync(workspace, state, (size_t)B * H * W, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (e != hipSuccess) return fail_hip(nullptr, e, "canny_hysteresis_u8");
+  return canny_finish_from_state("canny_hysteresis_u8", stream, edges, workspace, B, H, W, rounds_out);
+}
+
+ia2p_status ia2p_condition_from_u8(void* stream, const void* map_u8, void* dst_f16, int B, int H, int W, int C_in) {
+  if (!map_u8 || !dst_f16) return fail(nullptr, IA2P_ERR_INVALID, "condition_from_u8: null pointer");
+  if (((uintptr_t)dst_f16 & 1) != 0) return fail(nullptr, IA2P_ERR_INVALID, "condition_from_u8: dst holds 16-bit values and must be 2-byte aligned");
+  if (C_in != 1 && C_in != 3) return fail(nullptr, IA2P_ERR_SHAPE, "condition_from_u8: C_in=%d (1 or 3 channels)", C_in);
+  ia2p_status st = check_mask_image("condition_from_u8", B, H, W, 3);
+  if (st != IA2P_OK) return st;
+  if (ranges_overlap(map_u8, (size_t)B * H * W * C_in, dst_f16, (size_t)B * H * W * 6)) return fail(nullptr, IA2P_ERR_INVALID, "condition_from_u8: dst overlaps the map");
+  if (C_in == 3) return ia2p_image_from_u8(stream, map_u8, dst_f16, B, H, W, 3, 0);
+  hipError_t e = ia2p_launch_condition_from_u8_c1((const uint8_t*)map_u8, (half_t*)dst_f16, B, H * W, (hipStream_t)stream);
+  return e == hipSuccess ? IA2P_OK : fail_hip(nullptr, e, "condition_from_u8");
+}
+
 ia2p_status ia2p_prior_step(void* stream, const float* sample, const void* out_cond, const void* out_uncond, const float* noise, float g, float sqrt_a,
                             float sqrt_b, float k0, float k1, float sigma, float* out, int64_t n) {
   if (!sample || !out_uncond || !out || n < 0 || !(sqrt_a > 0.f) || !(sqrt_b > 0.f)) return fail(nullptr, IA2P_ERR_INVALID, "prior_step: bad argument");

@@ -140,6 +140,16 @@ def base_image(pipeline, c, who: str = ""):
     return img
 
 
+def check_control_from(pipeline, control_from, control_image):
+    """the refusals of `control_from=` that need no device: together with `control_image`, without a ControlNet, an unknown kind or knob -> the `Condition`"""
+    from .condition import resolve
+    if control_image is not None:
+        raise ValueError("control_from makes the condition map from the base image; control_image brings one: give one of the two")
+    if pipeline.controlnet is None:
+        raise ValueError("control_from needs the pipeline built with controlnet=<HipControlNetModel>")
+    return resolve(control_from)
+
+
 def refiner_handoff_by_image(pipeline) -> bool:
     """whether the base result reaches the refiner the reference's way (decode, 8-bit image, VAE re-encode with a posterior SAMPLE). Where that route was
     asked for but cannot be taken, say so once: the latent route has different numerics and draws nothing from the RNG"""
@@ -357,8 +367,12 @@ class InstructAny2PixPipeline:
     def denoise(self, base_latents, latent_la, *, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds,
                 inv_prompt_embeds=None, inv_pooled_prompt_embeds=None, alpha=0.7, num_inference_steps=25, cfg=10, scale=1.0, noise=None, seed=None,
                 edit_mask=None, auto_mask=None, sampler=None, sample_steps=None, step_noise=None, sample_adapters=None,
-                control_image=None, control_scale=1.0, control_start=0.0, control_end=1.0):
+                control_image=None, control_scale=1.0, control_start=0.0, control_end=1.0, control_from=None, control_base=None):
         """inversion -> polar mixing -> IP-Adapter guided sampling; returns (sampled latents, inverted latents).
+        `control_from` (None: nothing changes, no launch, no allocation and no bit): "canny", "blur", "grey", a dict such as {"kind": "canny", "low": 50, "high": 150,
+        "blur_sigma": 1.4} or a `condition.Condition` -- the condition map is made on the device (condition.py) from `control_base`, the base image's
+        8-bit pixels at 8 x the latent grid (a uint8 tensor / array [H, W, 3], a PIL image or a path), and passed on exactly as a `control_image` would be. This
+        call gets latents: without `control_base` the base image is not available as 8-bit pixels and the call raises. Together with `control_image`: ValueError.
         `control_image` (None: nothing changes, no launch and no bit; needs the pipeline built with controlnet=): the structure that must survive the edit -- a
         condition map the caller brings (edges, depth, pose, a sketch), a PIL image, a uint8 / float array or a path, resized and cropped like the base image to
         8 x the latent grid, values in [0, 1]. It guides the guided sampling stage only, at `control_scale` over the fraction [`control_start`, `control_end`] of
@@ -394,6 +408,8 @@ class InstructAny2PixPipeline:
         if inv_prompt_embeds is None:        # reference inverts with prompt='' (:330); callers pass its embedding
             inv_prompt_embeds, inv_pooled_prompt_embeds = negative_prompt_embeds, negative_pooled_prompt_embeds
         masked, control = {}, {}
+        if control_from is not None:
+            control_image = self.control_map(check_control_from(self, control_from, control_image), control_base, base_latents)
         if control_image is not None:
             if self.controlnet is None:
                 raise ValueError("control_image needs the pipeline built with controlnet=<HipControlNetModel>")
@@ -454,6 +470,9 @@ class InstructAny2PixPipeline:
             if control_image.ndim != 3 or control_image.shape[2] != 3:
                 raise ValueError(f"a uint8 control image is [H, W, 3]; got {control_image.shape}")
             t = image_from_u8(torch.from_numpy(np.ascontiguousarray(control_image))[None].to(dev), normalize=False)
+        elif torch.is_tensor(control_image) and control_image.dtype == torch.uint8:      # a map made on the device (`control_map`): one or three channels
+            from .condition import to_condition
+            t = to_condition(control_image.to(dev))
         else:
             t = torch.as_tensor(control_image)
             if not t.is_floating_point():
@@ -462,6 +481,53 @@ class InstructAny2PixPipeline:
         if t.ndim != 4 or tuple(t.shape[1:]) != (3, H, W):
             raise ValueError(f"the control image must be 3 x {H} x {W} (8 x the latent grid {base_latents.shape[-2]} x {base_latents.shape[-1]}); got {tuple(t.shape)}")
         return t.contiguous()
+
+    def base_pixels(self, base_image):
+        """a base image (a path: through `loas_base_img`; a PIL image; a uint8 array [H, W, 3]) -> uint8 [1, H, W, 3] on the device, as the pipeline holds it: the
+        host half of the inversion pipeline's `preprocess` (its resize to multiples of the VAE's scale factor) -- the bytes the VAE encode is fed. A uint8 tensor
+        ([H, W, 3] or [1, H, W, 3]) is taken as it is."""
+        from .condition import as_u8
+        if torch.is_tensor(base_image):
+            return as_u8(base_image, self.pipe.unet.device)[0]
+        if isinstance(base_image, (str, os.PathLike)):
+            base_image = self.loas_base_img(base_image)
+        if isinstance(base_image, np.ndarray) and base_image.dtype == np.uint8 and base_image.ndim == 3:
+            base_image = PIL.Image.fromarray(base_image)
+        if not isinstance(base_image, PIL.Image.Image):
+            raise ValueError("the base image of a condition map is a path, a PIL image, a uint8 array [H, W, 3] or a uint8 tensor")
+        proc = self.pipe_inversion.image_processor
+        if proc is None:
+            from .image_processor import VaeImageProcessor
+            proc = VaeImageProcessor(vae_scale_factor=8, device=self.pipe.unet.device)
+        return as_u8(proc.pil_to_u8([base_image])[0], self.pipe.unet.device)[0]
+
+    def control_map(self, cond, control_base, base_latents=None):
+        """the condition map `cond` asks for (condition.py) of the base image's 8-bit pixels -> uint8 [1, H, W] or [1, H, W, 3] on the device. `control_base` None:
+        the base image is not available as 8-bit pixels (the caller brought latents), which is refused; a size other than 8 x the latent grid is refused too."""
+        from . import condition
+        if control_base is None:
+            raise ValueError("control_from makes the condition map from the base image's 8-bit pixels, and this request brings base latents only: give the base "
+                             "image (base_image / base_img_path from the conditioner; `control_base=` on denoise), or bring the map as control_image=")
+        px = self.base_pixels(control_base)
+        if px.shape[0] != 1 or px.shape[-1] != 3:
+            raise ValueError(f"control_from: the base image must be one RGB image, got {tuple(px.shape)}")
+        if base_latents is not None and tuple(px.shape[1:3]) != (8 * base_latents.shape[-2], 8 * base_latents.shape[-1]):
+            raise ValueError(f"control_from: the base image is {px.shape[1]} x {px.shape[2]}, not 8 x the latent grid {base_latents.shape[-2]} x {base_latents.shape[-1]}")
+        return condition.make(cond, px)
+
+    def make_control_image(self, kind, base_image=None):
+        """The condition map `control_from=kind` would make, as a PIL image ("L" for canny and grey, "RGB" for blur), for a caller who wants to look at it or edit
+        it and pass it back as `control_image=`. `base_image`: a path (loaded by `loas_base_img`), a PIL image or a uint8 array; None: the base image of the last
+        request a `conditioner=` served (`self.cache`)."""
+        from . import condition
+        cond = condition.resolve(kind)
+        if base_image is None:
+            c = self.cache if isinstance(self.cache, dict) else {}
+            base_image = c.get("base_image") if c.get("base_image") is not None else c.get("base_img_path")
+            if base_image is None:
+                raise ValueError("make_control_image: no base image is held (the last request brought none): pass base_image=")
+        m = self.control_map(cond, base_image)[0].cpu().numpy()
+        return PIL.Image.fromarray(m)
 
     def estimate_edit_mask(self, base_latents, latent_la, **kw):
         """The automatic edit mask of one request on explicit conditioning, for a caller who wants to look at it (or change it) before `denoise(edit_mask=)`:
@@ -779,7 +845,7 @@ class InstructAny2PixPipeline:
     def __call__(self, inst, mm_data, alpha=0.7, h=[0.0, 0.4, 1.0], norm=20.0, refinement=0.5, llm_only=False, num_inference_steps=25,
                  use_cache=False, debug=False, diffusion_mode="default", subject_strength=0.0, cfg=10, scale=1.0, output_type="latent", seed=None,
                  edit_mask=None, edit_feather=8, *, auto_mask=None, lora_scale=None, sampler=None, sample_steps=None, sample_adapters=None,
-                 subject_mode="serial", control_image=None, control_scale=1.0, control_start=0.0, control_end=1.0) -> Any:
+                 subject_mode="serial", control_image=None, control_scale=1.0, control_start=0.0, control_end=1.0, control_from=None) -> Any:
         """-> (non_refined, oo, msg). output_type "latent" (default): latents; "pil" / "np" / "pt" (needs vae=): decoded images as diffusers'
         `postprocess` gives them, each latent decoded once (reference :356-386 returns PIL images).
         `seed` (a 64-bit unsigned integer; None: every draw from the global CPU generator, as ever): every normal draw of the request comes from its own
@@ -812,6 +878,12 @@ class InstructAny2PixPipeline:
         over the seed (draw 65537 of it), which wins over the global generator. The refiner and the subject passes are untouched.
         `control_image`, `control_scale`, `control_start`, `control_end` (keyword only; None: nothing changes, no launch, no bit; needs controlnet=): a ControlNet
         guides the guided sampling stage by the condition map the caller brings (`denoise`). The other stages run without control.
+        `control_from` (keyword only; None: nothing changes, no launch, no allocation, no bit; needs controlnet=): "canny", "blur", "grey", a dict such as
+        {"kind": "canny", "low": 50, "high": 150, "blur_sigma": 1.4} or a `condition.Condition` -- the condition map is made on the device from the base image as
+        the pipeline holds it (the 8-bit image after `loas_base_img`'s resize and crop, at 8 x the latent grid) and passed on exactly as a
+        `control_image` would be, under the same `control_scale` / `control_start` / `control_end`. Together with `control_image`: ValueError. A conditioner that
+        brings `base_latents` leaves no 8-bit pixels to make the map from: ValueError. With `debug=True` the message also carries `control_map` (uint8, on the
+        device). `make_control_image` returns the same map as a PIL image.
         `subject_mode` (keyword only; "serial": as ever, one inpainting loop per subject as the reference runs them): "joint" repaints all subjects in ONE
         loop -- every subject's image tokens in one context, each under its own mask, the blend under the union of the masks, one noise (draw
         DRAW_INPAINT + 0 of a seeded request). "joint" is NOT the serial result: in the serial form later passes see earlier repaints and draw their own
@@ -824,7 +896,9 @@ class InstructAny2PixPipeline:
                             use_cache=use_cache, debug=debug, diffusion_mode=diffusion_mode, subject_strength=subject_strength, cfg=cfg, scale=scale,
                             output_type=output_type, seed=seed, edit_mask=edit_mask, edit_feather=edit_feather, auto_mask=auto_mask, sampler=sampler,
                             sample_steps=sample_steps, sample_adapters=sample_adapters, subject_mode=subject_mode, control_image=control_image,
-                            control_scale=control_scale, control_start=control_start, control_end=control_end)
+                            control_scale=control_scale, control_start=control_start, control_end=control_end, control_from=control_from)
+        if control_from is not None:
+            control_from = check_control_from(self, control_from, control_image)
         if control_image is not None and self.controlnet is None:
             raise ValueError("control_image needs the pipeline built with controlnet=<HipControlNetModel>")
         control = {} if control_image is None else dict(control_image=control_image, control_scale=control_scale, control_start=control_start, control_end=control_end)
@@ -862,7 +936,12 @@ class InstructAny2PixPipeline:
                 return None, None, c["caption"]
         latent_la = fuse_instruction_embedding(c["base_embed"], c["image_embeds"], prior_y0(self, c), h, norm)
         masked, kept, edit_px, edit_m = {}, {}, None, None
-        base_latents = self._base_latents(c, seed) if edit_mask is None and auto_mask is None else self._base_latents(c, seed, kept)
+        base_latents = self._base_latents(c, seed) if edit_mask is None and auto_mask is None and control_from is None else self._base_latents(c, seed, kept)
+        control_map = None
+        if control_from is not None:                                                           # the map of the image the VAE encode was fed, made on the device
+            from .image_processor import image_to_u8
+            control_map = self.control_map(control_from, image_to_u8(kept["image"]) if "image" in kept else None, base_latents)
+            control = dict(control_image=control_map, control_scale=control_scale, control_start=control_start, control_end=control_end)
         if edit_mask is not None:
             edit_px, edit_m = resolve_edit_mask(self, edit_mask, base_latents, edit_mask_file_size(c))
             masked = dict(edit_mask=edit_m)
@@ -916,7 +995,7 @@ class InstructAny2PixPipeline:
             else:                                                                              # masks given by the conditioner
                 oo = subject_consistency(subject_data, oo, self.ip_adapter_xl_inpaint, subject_strength, **kw)
         msg = "SUCCESS!" if not debug else dict(output_caption=c["caption"], latent_inv=latent_inv, latent_la=latent_la, **({} if seed is None else {"seed": seed}),
-                                                **({} if edit_m is None else {"edit_mask_latent": edit_m}),
+                                                **({} if edit_m is None else {"edit_mask_latent": edit_m}), **({} if control_map is None else {"control_map": control_map}),
                                                 **({} if auto is None else {"edit_mask": edit_m, "auto_mask_map": auto[1], "auto_mask_stats": auto[2]}))
         if output_type != "latent" and edit_px is not None:                                    # "pil": composited with the base image in 8 bits
             from .image_processor import image_to_u8, mask_feather
