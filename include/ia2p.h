@@ -110,7 +110,47 @@ ia2p_status ia2p_set_gn_fuse(ia2p_ctx* ctx, int mode);
 /* IP-Adapter plugin state: set_ip_adapter (ip_adapter.py:120-142) / set_scale (:211-214) / disable (:153-154). */
 ia2p_status ia2p_set_ip_adapter(ia2p_ctx* ctx, int enabled, int num_tokens, float scale);
 
-/* ---- the UNet callable ------------------------------------------------------------------------------------------- */
+/* ---- the UNet callable -------------------------------------------------------------------------------------------
+ * One evaluation is one record. Zero the record, set struct_size = sizeof(ia2p_unet_call), fill what the call uses. A size below the record as first published (it
+ * ended with mid_residual) or above this library's own is IA2P_ERR_INVALID; fields a caller's older header did not have read as zero. Tensors are fp16 on the device:
+ * sample, out [B, in/out_channels, h, w] NCHW; context [B, L, cross_attention_dim]; text_embeds [B, pooled]; time_ids [B, num_time_ids]. With the IP-Adapter enabled the
+ * last num_tokens rows of each context are the image tokens.
+ *
+ *   field(s)                          may be set when                                                       otherwise
+ *   context | kv                      exactly one: context, or its projections -- ia2p_project_context      IA2P_ERR_INVALID
+ *   timestep                          timesteps == NULL: one timestep for the batch, by value               (ignored)
+ *   timesteps   device float [B]      always; REQUIRED with ip_scales, regions or residuals                 IA2P_ERR_INVALID
+ *   ip_scales   device float [B]      the IP-Adapter is enabled -- ia2p_set_ip_adapter                      IA2P_ERR_STATE
+ *   region_masks, G                   together; 1 <= G <= 16 (IA2P_ERR_SHAPE); the adapter enabled with      IA2P_ERR_STATE
+ *     fp16 [B, G, h, w]               num_tokens = 4 G; no residuals in the same call                       IA2P_ERR_INVALID
+ *   down_residuals, n_down,           together; n_down == ia2p_unet_num_skips (IA2P_ERR_SHAPE); every        IA2P_ERR_INVALID
+ *     mid_residual                    pointer non-NULL and 16-byte aligned; no regions in the same call     IA2P_ERR_INVALID
+ *   the handle                        a UNet context (a ControlNet's: IA2P_ERR_STATE), weights finalized    IA2P_ERR_STATE
+ *   B, h, w, L                        as ia2p_workspace_bytes accepts them                                  IA2P_ERR_SHAPE
+ *
+ * Every refusal comes before any launch. The workspace query reads B, h, w, L and G only (pointers may be NULL; residuals need no more than the plain pass; a regional
+ * pass needs the plain pass's workspace plus the mask pyramid); 0 on a refusal. The argument-list forms below are thin callers of the record form. */
+typedef struct ia2p_unet_call {
+  uint32_t struct_size;
+  int B, h, w, L;
+  int G;                               /* token groups of region_masks; 0: no regions */
+  int n_down;                          /* entries of down_residuals; 0: no residuals */
+  float timestep;
+  const void* sample;
+  const void* context;
+  const void* kv;
+  const void* text_embeds;
+  const void* time_ids;
+  void* out;
+  const float* timesteps;
+  const float* ip_scales;
+  const void* region_masks;
+  const void* const* down_residuals;   /* residual k: channels-last [B * H_k * W_k, C_k], skip order */
+  const void* mid_residual;
+} ia2p_unet_call;
+size_t ia2p_workspace_bytes_x(ia2p_ctx* ctx, const ia2p_unet_call* call);
+ia2p_status ia2p_unet_forward_x(ia2p_ctx* ctx, void* stream, const ia2p_unet_call* call, void* workspace, size_t workspace_bytes);
+
 size_t ia2p_workspace_bytes(ia2p_ctx* ctx, int B, int h, int w, int L);
 /* sample, out: [B, in/out_channels, h, w] NCHW; context: [B, L, cross_attention_dim]; text_embeds: [B, pooled];
  * time_ids: [B, num_time_ids]. With the IP-Adapter enabled the last num_tokens rows of each context are the image tokens. */

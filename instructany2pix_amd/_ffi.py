@@ -77,6 +77,15 @@ class ConvGnC(C.Structure):
 
 
 _P, _I, _F, _SZ, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
+
+
+class UNetCallC(C.Structure):
+    """ia2p_unet_call (include/ia2p.h): one UNet evaluation as a record; which fields may meet is the table there"""
+    _fields_ = [("struct_size", C.c_uint32), ("B", _I), ("h", _I), ("w", _I), ("L", _I), ("G", _I), ("n_down", _I), ("timestep", _F),
+                ("sample", _P), ("context", _P), ("kv", _P), ("text_embeds", _P), ("time_ids", _P), ("out", _P), ("timesteps", _P), ("ip_scales", _P),
+                ("region_masks", _P), ("down_residuals", C.POINTER(_P)), ("mid_residual", _P)]
+
+
 # every symbol include/ia2p.h and include/ia2p_debug.h declare: name -> (restype, argtypes)
 SIGNATURES = {
     "ia2p_create": (_I, [C.POINTER(UNetConfigC), C.POINTER(_P)]),
@@ -94,6 +103,8 @@ SIGNATURES = {
     "ia2p_bcast_arena": (_I, [_P, _P, _I, _I, _P]),
     "ia2p_rccl_available": (_I, []),
     "ia2p_set_ip_adapter": (_I, [_P, _I, _I, _F]),
+    "ia2p_workspace_bytes_x": (_SZ, [_P, C.POINTER(UNetCallC)]),
+    "ia2p_unet_forward_x": (_I, [_P, _P, C.POINTER(UNetCallC), _P, _SZ]),
     "ia2p_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
     "ia2p_unet_forward": (_I, [_P, _P, _P, _F, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ]),
     "ia2p_unet_forward_v": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _SZ]),
@@ -369,12 +380,17 @@ def check(status: int, ctx=None, family: str = "", **spelled):
     raise IA2PError(text)
 
 
-def ptr(t):
-    """Device pointer of a torch tensor (None -> NULL). Tensors must be contiguous fp16 CUDA tensors."""
+def addr(t):
+    """Device address of a torch tensor as an integer, for a pointer field of a record (None -> NULL). Tensors must be contiguous CUDA tensors."""
     if t is None:
         return None
     assert t.is_cuda and t.is_contiguous(), "ia2p needs contiguous device tensors"
-    return C.c_void_p(t.data_ptr())
+    return t.data_ptr()
+
+
+def ptr(t):
+    """... as a pointer argument"""
+    return None if t is None else C.c_void_p(addr(t))
 
 
 def current_stream():
@@ -403,7 +419,6 @@ class Executor:
 
     _h = None            # class-level defaults: an object whose constructor raised (or never ran: a test stand-in) still destroys cleanly
     _ws = None
-
     def __init__(self, family: str, config_c, device, prepare=None):
         """`config_c`: the family's config struct; `prepare()`: what must happen between create and the sizing of the arena."""
         import torch
@@ -474,6 +489,24 @@ class Executor:
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def _context_kv(self, topology, kv_bytes, project, ctx_in, ctx, B, L, ws):
+        """K/V projections of `ctx` (an executor of the UNet's kind, which keeps `_kv` and `_weights_gen`; `kv_bytes` / `project`: its `*_context_kv_bytes` /
+        `*_project_context`), cached in `_kv` = (context tensor, its _version, topology, weight generation, (B, L), kv buffer) while the same
+        unmodified tensor object `ctx_in` arrives with the same weights and `topology` (how the context's rows split into text and image tokens). The source tensor
+        is kept alive so its address cannot be handed to another tensor."""
+        import torch
+        k = self._kv
+        if k is not None and k[0] is ctx_in and k[1] == ctx_in._version and k[2] == topology and k[3] == self._weights_gen and k[4] == (B, L):
+            return k[5]
+        n = kv_bytes(self._h, B, L)
+        if n == 0:
+            self.check(2)
+        buf = k[5] if (k is not None and k[5].numel() == n) else torch.empty(n, dtype=torch.uint8, device=self.device)
+        self._kv = None
+        self.check(project(self._h, current_stream(), ptr(ctx), L, B, ptr(buf), n, ptr(ws), ws.numel()))
+        self._kv = (ctx_in, ctx_in._version, topology, self._weights_gen, (B, L), buf)
+        return buf
 
 
 def make_config(cfg) -> UNetConfigC:

@@ -22,6 +22,7 @@ import torch
 
 from . import _ffi
 from .config import ControlNetConfig
+from .unet import _inputs, per_row
 
 
 class HipControlNetModel(_ffi.Executor):
@@ -108,19 +109,6 @@ class HipControlNetModel(_ffi.Executor):
             self.check(2)
         return total, [(int(offs[k]), int(ch[k]), int(hs[k]), int(ws[k])) for k in range(n)]
 
-    def _context_kv(self, ctx_in, ctx, B, L, ws):
-        k = self._kv
-        if k is not None and k[0] is ctx_in and k[1] == ctx_in._version and k[2] == self.num_tokens and k[3] == self._weights_gen and k[4] == (B, L):
-            return k[5]
-        n = self._lib.ia2p_controlnet_context_kv_bytes(self._h, B, L)
-        if n == 0:
-            raise ValueError(f"a context of {L} rows leaves no text rows in front of the {self.num_tokens} image tokens")
-        buf = k[5] if (k is not None and k[5].numel() == n) else torch.empty(n, dtype=torch.uint8, device=self.device)
-        self._kv = None
-        self.check(self._lib.ia2p_controlnet_project_context(self._h, _ffi.current_stream(), _ffi.ptr(ctx), L, B, _ffi.ptr(buf), n, _ffi.ptr(ws), ws.numel()))
-        self._kv = (ctx_in, ctx_in._version, self.num_tokens, self._weights_gen, (B, L), buf)
-        return buf
-
     @_ffi.on_device
     def __call__(self, sample, timestep, encoder_hidden_states=None, controlnet_cond=None, conditioning_scale=1.0, added_cond_kwargs=None,
                  guess_mode: bool = False, return_dict: bool = False, **unused):
@@ -128,33 +116,14 @@ class HipControlNetModel(_ffi.Executor):
         call overwrites them). `conditioning_scale`: a number, or a [B] tensor -- one scale per batch element. `timestep`: a number or a [B] tensor."""
         if guess_mode:
             raise ValueError("guess_mode=True is not supported")
-        if encoder_hidden_states is None or added_cond_kwargs is None or controlnet_cond is None:
-            raise ValueError("encoder_hidden_states, controlnet_cond and added_cond_kwargs (text_embeds, time_ids) are required")
-        if "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
-            raise ValueError("added_cond_kwargs must carry `text_embeds` and `time_ids`")
-        B, c_in, h, w = sample.shape
-        if c_in != self.config.in_channels:
-            raise ValueError(f"sample has {c_in} channels, expected {self.config.in_channels}")
-        f16 = lambda t: t.to(device=self.device, dtype=torch.float16).contiguous()      # noqa: E731
+        if controlnet_cond is None:
+            raise ValueError("controlnet_cond is required")
         ctx_in = encoder_hidden_states
-        sample, ctx = f16(sample), f16(encoder_hidden_states)
-        te, tid = f16(added_cond_kwargs["text_embeds"]), f16(added_cond_kwargs["time_ids"])
-        if ctx.shape[0] != B or ctx.shape[2] != self.config.cross_attention_dim:
-            raise ValueError(f"encoder_hidden_states must be [B, L, {self.config.cross_attention_dim}]")
-        if te.shape != (B, self.config.pooled_dim) or tid.shape != (B, self.config.num_time_ids):
-            raise ValueError("added_cond_kwargs do not fit this model's text_time embedding")
-        L = ctx.shape[1]
+        sample, ctx, te, tid, (B, h, w, L) = _inputs(self, sample, encoder_hidden_states, added_cond_kwargs)
         if L <= self.num_tokens:
             raise ValueError(f"a context of {L} rows leaves no text rows in front of the {self.num_tokens} image tokens")
         cond = self._embedded(controlnet_cond, B, h, w)
-        ts = timestep if torch.is_tensor(timestep) else torch.full((B,), float(timestep))
-        ts = ts.to(device=self.device, dtype=torch.float32).reshape(-1)
-        ts = (ts.expand(B) if ts.numel() == 1 else ts).contiguous()
-        sc = conditioning_scale if torch.is_tensor(conditioning_scale) else torch.full((B,), float(conditioning_scale))
-        sc = sc.to(device=self.device, dtype=torch.float32).reshape(-1)
-        sc = (sc.expand(B) if sc.numel() == 1 else sc).contiguous()
-        if ts.numel() != B or sc.numel() != B:
-            raise ValueError(f"timestep / conditioning_scale must hold one value or {B}")
+        ts, sc = per_row(timestep, B, "timestep tensor", self.device), per_row(conditioning_scale, B, "conditioning_scale", self.device)
         key = (B, h, w, L, self.num_tokens, self._lib.ia2p_plan_generation())
         if self._ws_key != key:
             self.workspace(self._lib.ia2p_controlnet_workspace_bytes(self._h, B, h, w, L))
@@ -164,7 +133,9 @@ class HipControlNetModel(_ffi.Executor):
         if self._res is None or self._res.numel() * 2 != total:
             self._res = torch.empty(total // 2, dtype=torch.float16, device=self.device)
         res = self._res
-        kv = self._context_kv(ctx_in, ctx, B, L, ws) if self.cache_context_kv else None
+        kv = None
+        if self.cache_context_kv:
+            kv = self._context_kv(self.num_tokens, self._lib.ia2p_controlnet_context_kv_bytes, self._lib.ia2p_controlnet_project_context, ctx_in, ctx, B, L, ws)
         self.check(self._lib.ia2p_controlnet_forward(self._h, _ffi.current_stream(), _ffi.ptr(sample), _ffi.ptr(ts), None if kv is not None else _ffi.ptr(ctx),
                                                      _ffi.ptr(kv) if kv is not None else None, L, _ffi.ptr(te), _ffi.ptr(tid), _ffi.ptr(cond), _ffi.ptr(sc),
                                                      _ffi.ptr(res), total, B, h, w, _ffi.ptr(ws), ws.numel()))

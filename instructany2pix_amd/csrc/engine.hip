@@ -757,19 +757,38 @@ static void zero_conv(ia2p_ctx* c, const half_t* x, size_t w, size_t b, const fl
   CHECK_LAUNCH(c, ia2p_launch_gemm_variant(a, false, pl.variant, c->stream), "zero convolution");
 }
 
-// kv_cached != nullptr: the context projections were computed before (ia2p_project_context) and are read from there
-// gn_mode: the GroupNorm mode of the pass -- the context's gn_fuse (0 launches, 1 fused, 2 the unfused twin), or, from ia2p_workspace_bytes, every one of them and
+// One evaluation as run_forward sees it, whichever entry point asked for it: the shape, the tensors, and what the pass carries on top of the plain one. A sizing or
+// recording pass runs over a record that holds the shape and the option switches only (shape_only): no pointer is read there.
+struct FwdCall {
+  int B = 0, h = 0, w = 0, L = 0;
+  const half_t *sample = nullptr, *context = nullptr, *kv = nullptr, *text_embeds = nullptr, *time_ids = nullptr;
+  half_t* out = nullptr;
+  float timestep = 0.f;                   // the one timestep of the batch, unless ...
+  const float* timesteps = nullptr;       // ... device [B]: one per batch element
+  const float* ip_scales = nullptr;       // device [B] or null: per-request IP-Adapter scale
+  const half_t* region_masks = nullptr;   // fp16 [B, G, h, w] (regional image prompts), with ...
+  int G = 0;                              // ... G token groups; 0: none
+  bool kv_cached = false;                 // the context projections were computed before (ia2p_project_context) and are read from `kv`
+  CtlIo io;
+  static FwdCall shape(int B, int h, int w, int L, int G = 0, bool kv_cached = false) {
+    FwdCall s;
+    s.B = B; s.h = h; s.w = w; s.L = L; s.G = G; s.kv_cached = kv_cached;
+    return s;
+  }
+  FwdCall shape_only() const { return shape(B, h, w, L, G, kv_cached); }
+};
+
+// gn_mode: the GroupNorm mode of the pass -- the context's gn_fuse (0 launches, 1 fused, 2 the unfused twin), or, from forward_workspace, every one of them and
 // 3: the sizing pass of ia2p_autotune
-static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, float timestep, const half_t* context, int L,
-                               const half_t* text_embeds, const half_t* time_ids, half_t* out, int B, int h, int w,
-                               const half_t* kv_cached = nullptr, const float* timesteps = nullptr, const float* ip_scales = nullptr,
-                               const half_t* region_masks = nullptr, int G = 0, const CtlIo* io = nullptr) {
+static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const FwdCall& call) {
+  const int B = call.B, h = call.h, w = call.w, L = call.L, G = call.G;
+  const CtlIo& io = call.io;
   const ia2p_unet_config& g = c->cfg;
   const int n = g.n_blocks;
   const int T = g.time_embed_dim, Tp = g.time_proj_dim, Ain = g.projection_class_embeddings_input_dim, Ad = g.addition_time_embed_dim;
   const int pooled = Ain - g.num_time_ids * Ad;
-  Fwd f{c, B, h, w, L, context, T2{(size_t)-1, nullptr}, nullptr, T2{(size_t)-1, nullptr}, T2{(size_t)-1, nullptr}};
-  f.ip_scales = ip_scales;
+  Fwd f{c, B, h, w, L, call.context, T2{(size_t)-1, nullptr}, nullptr, T2{(size_t)-1, nullptr}, T2{(size_t)-1, nullptr}};
+  f.ip_scales = call.ip_scales;
   f.gn_mode = gn_mode;
   f.tune_like = c->gn_fuse != 0 && (c->dry && !c->record ? gn_mode == 3 : c->tuning);      // (a sizing pass takes its mode's word; a recording or real pass is what the context is doing)
   f.gn_on = gn_mode != 0 && gn_mode != 3 && !c->tuning;      // (the autotune pass measures the plain kernels: GroupNorm launches there)
@@ -787,7 +806,7 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
       lv.w = wsalloc(c, (size_t)B * G * H * Wd);
       RoleScope role(c, ROLE_Q_XATTN);
       ProfScope ps(c, PK_EMBED, 0, 0);
-      CHECK_LAUNCH(c, ia2p_launch_region_levels(region_masks, lv.w.p, B, G, h, w, h / H, c->stream), "region_levels");
+      CHECK_LAUNCH(c, ia2p_launch_region_levels(call.region_masks, lv.w.p, B, G, h, w, h / H, c->stream), "region_levels");
     };
     for (const Stage& st : c->down) {
       level(!st.att.empty());
@@ -809,7 +828,7 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   {
     RoleScope role(c, ROLE_EMBED);
     ProfScope ps(c, PK_EMBED, 0, 0);
-    CHECK_LAUNCH(c, ia2p_launch_embed(timestep, timesteps, text_embeds, time_ids, tsin.p, addin.p, B, Tp, pooled, Ad, g.num_time_ids, c->stream), "embed");
+    CHECK_LAUNCH(c, ia2p_launch_embed(call.timestep, call.timesteps, call.text_embeds, call.time_ids, tsin.p, addin.p, B, Tp, pooled, Ad, g.num_time_ids, c->stream), "embed");
     // skinny linears hold <= 16 rows per launch: larger batches go in row chunks
     auto lin = [&](const half_t* X, int ldx, size_t w, size_t b, const half_t* add, int ldadd, half_t* o, int ldo, int N, int K, int si, int so, const char* what) {
       for (int r0 = 0; r0 < B; r0 += 16) {
@@ -834,9 +853,9 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   if (c->kv_rows > 0) {
     const int Lt = ctx_lt(c, L), Li = ctx_li(c);
     if (Lt < 1) return fail(c, IA2P_ERR_SHAPE, "context length %d leaves no text rows", L);
-    if (kv_cached) {
-      f.kv_text.p = const_cast<half_t*>(kv_cached);
-      if (Li) f.kv_ip.p = const_cast<half_t*>(kv_cached) + (size_t)B * Lt * c->kv_rows;
+    if (call.kv_cached) {
+      f.kv_text.p = const_cast<half_t*>(call.kv);
+      if (Li && call.kv) f.kv_ip.p = const_cast<half_t*>(call.kv) + (size_t)B * Lt * c->kv_rows;
     } else {
       f.kv_text = wsalloc(c, (size_t)B * Lt * c->kv_rows);
       if (Li) f.kv_ip = wsalloc(c, (size_t)B * Li * c->kv_rows);
@@ -846,8 +865,8 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
       // step keeps the other blocks' column ranges. The autotune pass projects everything here as well -- the whole projection's plan is what every range runs on, and
       // it is measured on the whole projection -- and lets the fused launches rewrite their columns with the same bits.
       const std::vector<std::pair<int, int>> up_front = plan_context_kv(f, h, w);
-      if (c->tuning || f.tune_like) project_context(c, context, L, B, f.kv_text.p, f.kv_ip.p);
-      else for (const auto& r : up_front) project_context(c, context, L, B, f.kv_text.p, f.kv_ip.p, r.first, r.second - r.first);
+      if (c->tuning || f.tune_like) project_context(c, call.context, L, B, f.kv_text.p, f.kv_ip.p);
+      else for (const auto& r : up_front) project_context(c, call.context, L, B, f.kv_text.p, f.kv_ip.p, r.first, r.second - r.first);
     }
   }
 
@@ -861,12 +880,12 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
     RoleScope role(c, ROLE_CONV_IO);
     ProfScope ps(c, PK_CONV_IN, 2.0 * B * H * Wd * 9.0 * g.in_channels * g.block_out_channels[0],
                  2.0 * ((double)B * H * Wd * (g.in_channels + g.block_out_channels[0]) + 64.0 * g.block_out_channels[0]));
-    CHECK_LAUNCH(c, ia2p_launch_conv_in(sample, W_(c, c->conv_in_w), W_(c, c->conv_in_b), x.p, B, g.in_channels, H, Wd, g.block_out_channels[0], c->stream), "conv_in");
+    CHECK_LAUNCH(c, ia2p_launch_conv_in(call.sample, W_(c, c->conv_in_w), W_(c, c->conv_in_b), x.p, B, g.in_channels, H, Wd, g.block_out_channels[0], c->stream), "conv_in");
   }
   // Every tensor below feeds a GroupNorm in front of a 3x3 convolution -- the next ResnetBlock2D's norm1, or (the skips) the norm1 of an up-path block much later --
   // and carries its producer's column sums with it (f.gst); conv_in is a direct kernel: the consumer that fuses runs the canonical statistics pass over its output
   // ControlNet: sample = conv_in(sample) + controlnet_cond (the embedded condition, on the latent grid)
-  if (c->cn) CHECK_LAUNCH(c, ia2p_launch_residual_add_gnstats(x.p, io ? io->cond : nullptr, x.p, B * H * Wd, g.block_out_channels[0], 0, nullptr, c->stream), "condition embedding");
+  if (c->cn) CHECK_LAUNCH(c, ia2p_launch_residual_add_gnstats(x.p, io.cond, x.p, B * H * Wd, g.block_out_channels[0], 0, nullptr, c->stream), "condition embedding");
   std::vector<int> skip_hw;      // (ControlNet: pixels per image of every skip, for its zero convolution)
   skips.push_back(x); skip_c.push_back(g.block_out_channels[0]); skip_hw.push_back(H * Wd);
   for (int i = 0; i < n; ++i) {
@@ -900,8 +919,8 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   }
   if (c->cn) {
     // ---- ControlNet: no up path. Residual k = zero_conv_k(skip_k) * conditioning_scale, the mid residual likewise, back to back in the caller's buffer
-    half_t* res = io ? io->res : nullptr;
-    const float* scales = io ? io->scales : nullptr;
+    half_t* res = io.res;
+    const float* scales = io.scales;
     size_t off = 0;
     for (size_t k = 0; k < skips.size(); ++k) {
       const int Mk = B * skip_hw[k];
@@ -918,7 +937,7 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   }
   // a controlled UNet pass: mid_out += mid_residual; every skip gets its residual where the up path pops it -- after the whole down path and the mid block have read
   // the unmodified tensors, which is diffusers' order (the residuals are added to the finished tuple of skips)
-  if (io && io->mid) add_residual(f, x, io->mid, (long)B * H * Wd, g.block_out_channels[n - 1]);
+  if (io.mid) add_residual(f, x, io.mid, (long)B * H * Wd, g.block_out_channels[n - 1]);
   // ---- up path
   for (int i = 0; i < n; ++i) {
     const Stage& st = c->up[i];
@@ -927,7 +946,7 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
       const int cs = skip_c.back(); skip_c.pop_back();
       const int cx = st.res[j].cin - cs;
       const long M = (long)B * H * Wd;
-      if (io && io->down) add_residual(f, sk, io->down[skips.size()], M, cs);
+      if (io.down) add_residual(f, sk, io.down[skips.size()], M, cs);
       T2 r;
       const bool att = !st.att.empty();
       const bool last = i == n - 1 && j + 1 == st.res.size();      // (the last block's output feeds conv_norm_out: a GroupNorm launch of its own)
@@ -969,7 +988,7 @@ static ia2p_status run_forward(ia2p_ctx* c, int gn_mode, const half_t* sample, f
   {
     RoleScope role(c, ROLE_CONV_IO);
     ProfScope ps(c, PK_CONV_OUT, 2.0 * B * H * Wd * 9.0 * c0 * g.out_channels, 2.0 * ((double)B * H * Wd * (c0 + g.out_channels) + 9.0 * c0 * g.out_channels));
-    CHECK_LAUNCH(c, ia2p_launch_conv_out(no.p, c0, W_(c, c->conv_out_w), W_(c, c->conv_out_b), out, B, c0, H, Wd, g.out_channels, c->stream), "conv_out");
+    CHECK_LAUNCH(c, ia2p_launch_conv_out(no.p, c0, W_(c, c->conv_out_w), W_(c, c->conv_out_b), call.out, B, c0, H, Wd, g.out_channels, c->stream), "conv_out");
   }
   for (auto& kv : f.gst) wsfree(c, kv.second.buf);      // (none left on a complete pass)
   f.gst.clear();
@@ -1131,104 +1150,157 @@ static ia2p_status check_fwd_shape(ia2p_ctx* c, int B, int h, int w, int L) {
   return IA2P_OK;
 }
 
-size_t ia2p_workspace_bytes(ia2p_ctx* c, int B, int h, int w, int L) {
-  if (!c || c->cn || check_fwd_shape(c, B, h, w, L) != IA2P_OK) return 0;
-  // four dry passes: the GroupNorms as launches of their own, inside their convolutions (the product path), the fused path's unfused twin, and the autotune pass
-  // (GroupNorm launches + the statistics and live tensors its fused candidates need) -- a workspace sized here serves every ia2p_set_gn_fuse mode and ia2p_autotune
+// the workspace of a pass: a dry pass per GroupNorm mode 0 .. n_modes - 1, the maximum (0: a mode failed). Modes 0 .. 2: the GroupNorms as launches of their own, inside
+// their convolutions (the product path), the fused path's unfused twin -- a workspace sized here serves every ia2p_set_gn_fuse mode; mode 3: the autotune pass (GroupNorm
+// launches + the statistics and live tensors its fused candidates need), which only the plain UNet pass runs (no regions, no ControlNet)
+static size_t forward_workspace(ia2p_ctx* c, const FwdCall& shape, int n_modes) {
   size_t need = 0;
-  for (int mode = 0; mode < 4; ++mode) {
-    const size_t n = pass_dry(c, [&] { return run_forward(c, mode, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w); });
+  for (int mode = 0; mode < n_modes; ++mode) {
+    const size_t n = pass_dry(c, [&] { return run_forward(c, mode, shape); });
     if (!n) return 0;
     need = std::max(need, n);
   }
   return need;
 }
-
-// a workspace for ia2p_unet_forward_r with G token groups: the plain pass's, plus the mask pyramid in front of it (a sizing call of its own: ia2p_workspace_bytes and
-// every workspace sized by it stay what they were)
-size_t ia2p_workspace_bytes_r(ia2p_ctx* c, int B, int h, int w, int L, int G) {
-  if (!c || G < 1 || G > 16 || check_fwd_shape(c, B, h, w, L) != IA2P_OK) return 0;
-  size_t need = 0;
-  for (int mode = 0; mode < 3; ++mode) {      // (the autotune pass runs no regions)
-    const size_t n = pass_dry(c, [&] { return run_forward(c, mode, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, nullptr, nullptr, nullptr, nullptr, G); });
-    if (!n) return 0;
-    need = std::max(need, n);
-  }
-  return need;
-}
-
-static ia2p_status unet_forward_impl(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, const void* kv, int L,
-                                     const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes,
-                                     const float* timesteps = nullptr, const float* ip_scales = nullptr, const void* region_masks = nullptr, int G = 0, const CtlIo* io = nullptr) {
-  if (!c || !sample || (!context && !kv) || !text_embeds || !time_ids || !out || !ws) return fail(c, IA2P_ERR_INVALID, "unet_forward: null argument");
-  if (c->cn) return fail(c, IA2P_ERR_STATE, "unet_forward on a ControlNet context (ia2p_controlnet_forward)");
-  if (!c->finalized) return fail(c, IA2P_ERR_STATE, "unet_forward before weights were finalized");
-  ia2p_status st = check_fwd_shape(c, B, h, w, L);
-  if (st != IA2P_OK) return st;
+// one evaluation, once its entry point's own checks passed. record_key names the weight launch sequence of the pass: when it is not the recorded one, a dry pass of the
+// same code path over the shape-only record notes it.
+static ia2p_status forward_pass(ia2p_ctx* c, void* stream, void* ws, size_t ws_bytes, int record_key, const FwdCall& call) {
   // a tensor was reloaded after finalize (hot swap, strict=False load): re-derive the folds on this stream and wait (rare; the wait keeps a following forward on
   // ANOTHER stream from reading half-written folds)
-  st = pass_ready(c, [&] { return fold_all(c, (hipStream_t)stream, true); });
+  ia2p_status st = pass_ready(c, [&] { return fold_all(c, (hipStream_t)stream, true); });
   if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
   if (st != IA2P_OK) return st;
-  // the weight launch sequence: a dry pass of the same code path
-  pass_record(c, (c->ip_enabled ? 1 + c->ip_tokens : 0) + (kv ? 1000 : 0) + (G ? 2000 : 0),
-              [&] { return run_forward(c, c->gn_fuse, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, kv ? (const half_t*)1 : nullptr, nullptr, nullptr, nullptr, G); });
+  pass_record(c, record_key, [&] { return run_forward(c, c->gn_fuse, call.shape_only()); });
   c->tail_pf = c->arena + c->embed_lo; c->tail_pf_bytes = (c->embed_hi - c->embed_lo) * sizeof(half_t);   // the next step starts with these
-  return pass_leave(c, run_forward(c, c->gn_fuse, (const half_t*)sample, timestep, (const half_t*)context, L, (const half_t*)text_embeds, (const half_t*)time_ids, (half_t*)out,
-                                   B, h, w, (const half_t*)kv, timesteps, ip_scales, (const half_t*)region_masks, G, io));
+  return pass_leave(c, run_forward(c, c->gn_fuse, call));
 }
+
+// ---- the UNet callable: one record (ia2p_unet_call), one validator, and the legacy argument lists as thin callers of the record form
+// the record as first published ends with mid_residual: a caller compiled against a later header may pass more, never less
+static const size_t UNET_CALL_V1 = offsetof(ia2p_unet_call, mid_residual) + sizeof(const void*);
+// Every rule on which fields of an ia2p_unet_call may meet (the table in include/ia2p.h), in the order the legacy exports applied them: what the options need, the
+// tensors every pass needs, the context's kind and state, the shape. u: the caller's record, fields it did not know zeroed. sizing: a workspace query -- the shape,
+// G and the presence of residuals count, no pointer is required and no adapter state (the query may come before ia2p_set_ip_adapter).
+static ia2p_status check_call(ia2p_ctx* c, const ia2p_unet_call* in, const void* ws, bool sizing, ia2p_unet_call& u) {
+  if (!c || !in) return fail(c, IA2P_ERR_INVALID, "unet_forward: null argument");
+  if (in->struct_size < UNET_CALL_V1 || in->struct_size > sizeof u)
+    return fail(c, IA2P_ERR_INVALID, "unet_forward: struct_size %u (this library reads records of %zu .. %zu bytes)", in->struct_size, UNET_CALL_V1, sizeof u);
+  memset(&u, 0, sizeof u);
+  memcpy(&u, in, in->struct_size);
+  const bool regions = u.region_masks || u.G, residuals = u.down_residuals || u.mid_residual || u.n_down;
+  if (!sizing) {
+    if ((!u.context) == (!u.kv)) return fail(c, IA2P_ERR_INVALID, "unet_forward: exactly one of context / kv is required");
+    if (!u.timesteps && (u.ip_scales || regions || residuals)) return fail(c, IA2P_ERR_INVALID, "unet_forward: ip_scales, region_masks and residuals need per-row timesteps");
+  }
+  if (regions && residuals) return fail(c, IA2P_ERR_INVALID, "unet_forward: residuals together with region_masks (the regional pass is not combined with a ControlNet)");
+  if (regions) {
+    if (!sizing && !u.region_masks) return fail(c, IA2P_ERR_INVALID, "unet_forward: G=%d without region_masks", u.G);
+    if (u.G < 1 || u.G > 16) return fail(c, IA2P_ERR_SHAPE, "unet_forward: G=%d (1 .. 16)", u.G);
+    if (!sizing && (!c->ip_enabled || c->ip_tokens != 4 * u.G))
+      return fail(c, IA2P_ERR_STATE, "unet_forward: %d token groups need the IP-Adapter enabled with num_tokens = %d (ia2p_set_ip_adapter)", u.G, 4 * u.G);
+  }
+  if (residuals && !sizing) {
+    if (!u.down_residuals || !u.mid_residual) return fail(c, IA2P_ERR_INVALID, "unet_forward: down_residuals and mid_residual come together");
+    if (u.n_down != c->n_skips) return fail(c, IA2P_ERR_SHAPE, "unet_forward: %d down residuals, this UNet has %d skips", u.n_down, c->n_skips);
+    for (int i = 0; i < u.n_down; ++i)
+      if (!u.down_residuals[i] || (((uintptr_t)u.down_residuals[i]) & 15)) return fail(c, IA2P_ERR_INVALID, "unet_forward: down residual %d is null or not 16-byte aligned", i);
+    if (((uintptr_t)u.mid_residual) & 15) return fail(c, IA2P_ERR_INVALID, "unet_forward: the mid residual is not 16-byte aligned");
+  }
+  if (!sizing) {
+    if (u.ip_scales && !c->ip_enabled) return fail(c, IA2P_ERR_STATE, "unet_forward: per-request IP-Adapter scales without an installed adapter");
+    if (!u.sample || !u.text_embeds || !u.time_ids || !u.out || !ws) return fail(c, IA2P_ERR_INVALID, "unet_forward: null argument");
+  }
+  if (c->cn) return fail(c, IA2P_ERR_STATE, "unet_forward on a ControlNet context (ia2p_controlnet_forward)");
+  if (!sizing && !c->finalized) return fail(c, IA2P_ERR_STATE, "unet_forward before weights were finalized");
+  return check_fwd_shape(c, u.B, u.h, u.w, u.L);
+}
+static FwdCall fwd_call(const ia2p_unet_call& u) {
+  FwdCall f = FwdCall::shape(u.B, u.h, u.w, u.L);
+  f.sample = (const half_t*)u.sample; f.context = (const half_t*)u.context; f.kv = (const half_t*)u.kv; f.kv_cached = u.kv != nullptr;
+  f.text_embeds = (const half_t*)u.text_embeds; f.time_ids = (const half_t*)u.time_ids; f.out = (half_t*)u.out;
+  f.timestep = u.timestep; f.timesteps = u.timesteps; f.ip_scales = u.ip_scales;
+  f.region_masks = (const half_t*)u.region_masks; f.G = u.G;
+  f.io.down = (const half_t* const*)u.down_residuals; f.io.mid = (const half_t*)u.mid_residual;
+  return f;
+}
+// 0 on a refusal. A regional pass needs what the plain pass needs plus the mask pyramid in front of it (and the autotune pass runs no regions: three modes); residuals
+// are added in place: no allocation beyond the plain pass's.
+size_t ia2p_workspace_bytes_x(ia2p_ctx* c, const ia2p_unet_call* call) {
+  ia2p_unet_call u;
+  if (check_call(c, call, nullptr, true, u) != IA2P_OK) return 0;
+  return forward_workspace(c, fwd_call(u).shape_only(), u.G ? 3 : 4);
+}
+ia2p_status ia2p_unet_forward_x(ia2p_ctx* c, void* stream, const ia2p_unet_call* call, void* ws, size_t ws_bytes) {
+  ia2p_unet_call u;
+  const ia2p_status st = check_call(c, call, ws, false, u);
+  if (st != IA2P_OK) return st;
+  return forward_pass(c, stream, ws, ws_bytes, (c->ip_enabled ? 1 + c->ip_tokens : 0) + (u.kv ? 1000 : 0) + (u.G ? 2000 : 0), fwd_call(u));
+}
+
+// ---- the legacy argument lists: each fills a record and calls the record form; its own checks are what makes it THIS form (the pointers it cannot do without)
+static ia2p_unet_call unet_call(int B, int h, int w, int L, const void* sample = nullptr, const void* context = nullptr, const void* kv = nullptr,
+                                const void* text_embeds = nullptr, const void* time_ids = nullptr, void* out = nullptr) {
+  ia2p_unet_call u;
+  memset(&u, 0, sizeof u);
+  u.struct_size = sizeof u;
+  u.B = B; u.h = h; u.w = w; u.L = L;
+  u.sample = sample; u.context = context; u.kv = kv; u.text_embeds = text_embeds; u.time_ids = time_ids; u.out = out;
+  return u;
+}
+size_t ia2p_workspace_bytes(ia2p_ctx* c, int B, int h, int w, int L) {
+  const ia2p_unet_call u = unet_call(B, h, w, L);
+  return ia2p_workspace_bytes_x(c, &u);
+}
+size_t ia2p_workspace_bytes_r(ia2p_ctx* c, int B, int h, int w, int L, int G) {
+  if (G < 1) return 0;      // (G = 0 is the plain query in a record)
+  ia2p_unet_call u = unet_call(B, h, w, L);
+  u.G = G;
+  return ia2p_workspace_bytes_x(c, &u);
+}
+size_t ia2p_workspace_bytes_c(ia2p_ctx* c, int B, int h, int w, int L) { return ia2p_workspace_bytes(c, B, h, w, L); }
+int ia2p_unet_num_skips(ia2p_ctx* c) { return c ? c->n_skips : 0; }
+
 ia2p_status ia2p_unet_forward(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* context, int L,
                               const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes) {
-  if (!context) return fail(c, IA2P_ERR_INVALID, "unet_forward: null argument");
-  return unet_forward_impl(c, stream, sample, timestep, context, nullptr, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes);
+  ia2p_unet_call u = unet_call(B, h, w, L, sample, context, nullptr, text_embeds, time_ids, out);
+  u.timestep = timestep;
+  return ia2p_unet_forward_x(c, stream, &u, ws, ws_bytes);
 }
-
-// Per-request knobs inside ONE evaluation: `timesteps` (device, float [B]) gives every batch element its own timestep -- diffusers' UNet accepts
-// a [B] timestep tensor; the reference always passes one scalar (pnp_pipeline.py:253-260, sdxl_pipeline.py:832-839) because it serves one
-// request at a time -- and `ip_scales` (device, float [B], or NULL) its own IP-Adapter scale (reference: one `set_scale` value per call,
-// ip_adapter.py:211-214, attention_processor.py:397). Exactly one of `context` / `kv` (ia2p_project_context) is non-NULL. Batch element b gets
-// the same bits as in a uniform batch of the same size evaluated at (timesteps[b], ip_scales[b]) (tests/test_batch_gpu.py).
+ia2p_status ia2p_unet_forward_kv(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* kv, int L, const void* text_embeds,
+                                 const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes) {
+  ia2p_unet_call u = unet_call(B, h, w, L, sample, nullptr, kv, text_embeds, time_ids, out);
+  u.timestep = timestep;
+  return ia2p_unet_forward_x(c, stream, &u, ws, ws_bytes);
+}
+// per-row timesteps and IP-Adapter scales: batch element b gets the bits of a uniform batch evaluated at (timesteps[b], ip_scales[b]) (tests/test_batch_gpu.py)
 ia2p_status ia2p_unet_forward_v(ia2p_ctx* c, void* stream, const void* sample, const float* timesteps, const float* ip_scales, const void* context, const void* kv,
                                 int L, const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes) {
-  if (!timesteps || (!context) == (!kv)) return fail(c, IA2P_ERR_INVALID, "unet_forward_v: timesteps and exactly one of context / kv are required");
-  if (ip_scales && c && !c->ip_enabled) return fail(c, IA2P_ERR_STATE, "unet_forward_v: per-request IP-Adapter scales without an installed adapter");
-  return unet_forward_impl(c, stream, sample, 0.f, context, kv, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes, timesteps, ip_scales);
+  if (!timesteps) return fail(c, IA2P_ERR_INVALID, "unet_forward_v: timesteps and exactly one of context / kv are required");
+  ia2p_unet_call u = unet_call(B, h, w, L, sample, context, kv, text_embeds, time_ids, out);
+  u.timesteps = timesteps; u.ip_scales = ip_scales;
+  return ia2p_unet_forward_x(c, stream, &u, ws, ws_bytes);
 }
-
-// ia2p_unet_forward_v with regional image prompts (diffusers' `ip_adapter_masks`): the adapter's image tokens are G groups of four, group g acts on the queries of
-// every cross-attention site under region_masks[b, g] (fp16 [B, G, h, w] on the latent grid, device), pooled to the site's resolution by the block mean
-// (ia2p_region_levels, one launch per distinct attention resolution, once per forward). Every cross-attention site runs its q GEMM and ia2p_attention_regions.
+// ... with regional image prompts: G token groups of four under region_masks [B, G, h, w] (run_forward builds the pyramid; run_transformer the regional sites)
 ia2p_status ia2p_unet_forward_r(ia2p_ctx* c, void* stream, const void* sample, const float* timesteps, const float* ip_scales, const void* context, const void* kv,
                                 int L, const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes,
                                 const void* region_masks, int G) {
   if (!c) return IA2P_ERR_INVALID;
-  if (!timesteps || (!context) == (!kv) || !region_masks) return fail(c, IA2P_ERR_INVALID, "unet_forward_r: timesteps, region_masks and exactly one of context / kv are required");
-  if (G < 1 || G > 16) return fail(c, IA2P_ERR_SHAPE, "unet_forward_r: G=%d (1 .. 16)", G);
-  if (!c->ip_enabled || c->ip_tokens != 4 * G) return fail(c, IA2P_ERR_STATE, "unet_forward_r: %d token groups need the IP-Adapter enabled with num_tokens = %d (ia2p_set_ip_adapter)", G, 4 * G);
-  return unet_forward_impl(c, stream, sample, 0.f, context, kv, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes, timesteps, ip_scales, region_masks, G);
+  if (!timesteps || !region_masks) return fail(c, IA2P_ERR_INVALID, "unet_forward_r: timesteps, region_masks and exactly one of context / kv are required");
+  ia2p_unet_call u = unet_call(B, h, w, L, sample, context, kv, text_embeds, time_ids, out);
+  u.timesteps = timesteps; u.ip_scales = ip_scales; u.region_masks = region_masks; u.G = G;
+  return ia2p_unet_forward_x(c, stream, &u, ws, ws_bytes);
 }
-
-// ia2p_unet_forward_v with a ControlNet's residuals (diffusers UNet2DConditionModel.forward: down_block_additional_residuals, mid_block_additional_residual): residual k
-// ([B * H_k * W_k, C_k], channels-last, device) is added to skip k where the up path pops it, mid_residual to the mid block's output; both in place in the workspace, with
-// the GroupNorm column sums of the sums taken by the same launch (ia2p_residual_add_gnstats), so every ia2p_set_gn_fuse mode sees the injected tensors. No allocation
-// beyond the plain pass's: ia2p_workspace_bytes_c is ia2p_workspace_bytes. Every refusal comes before any launch and leaves the workspace untouched.
-size_t ia2p_workspace_bytes_c(ia2p_ctx* c, int B, int h, int w, int L) { return ia2p_workspace_bytes(c, B, h, w, L); }
-int ia2p_unet_num_skips(ia2p_ctx* c) { return c ? c->n_skips : 0; }
+// ... with a ControlNet's residuals, added in place where the up path pops each skip (add_residual)
 ia2p_status ia2p_unet_forward_c(ia2p_ctx* c, void* stream, const void* sample, const float* timesteps, const float* ip_scales, const void* context, const void* kv,
                                 int L, const void* text_embeds, const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes,
                                 const void* const* down_residuals, int n_down, const void* mid_residual, const void* region_masks, int G) {
   if (!c) return IA2P_ERR_INVALID;
-  if (!timesteps || (!context) == (!kv)) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: timesteps and exactly one of context / kv are required");
+  if (!timesteps) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: timesteps and exactly one of context / kv are required");
   if (!down_residuals || !mid_residual) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: null residuals (the plain pass is ia2p_unet_forward_v)");
-  if (region_masks || G) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: residuals together with region_masks (the regional pass, ia2p_unet_forward_r, is not combined with a ControlNet)");
-  if (n_down != c->n_skips) return fail(c, IA2P_ERR_SHAPE, "unet_forward_c: %d down residuals, this UNet has %d skips", n_down, c->n_skips);
-  for (int i = 0; i < n_down; ++i)
-    if (!down_residuals[i] || (((uintptr_t)down_residuals[i]) & 15)) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: down residual %d is null or not 16-byte aligned", i);
-  if (((uintptr_t)mid_residual) & 15) return fail(c, IA2P_ERR_INVALID, "unet_forward_c: the mid residual is not 16-byte aligned");
-  if (ip_scales && !c->ip_enabled) return fail(c, IA2P_ERR_STATE, "unet_forward_c: per-request IP-Adapter scales without an installed adapter");
-  CtlIo io;
-  io.down = (const half_t* const*)down_residuals; io.mid = (const half_t*)mid_residual;
-  return unet_forward_impl(c, stream, sample, 0.f, context, kv, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes, timesteps, ip_scales, nullptr, 0, &io);
+  ia2p_unet_call u = unet_call(B, h, w, L, sample, context, kv, text_embeds, time_ids, out);
+  u.timesteps = timesteps; u.ip_scales = ip_scales; u.region_masks = region_masks; u.G = G;
+  u.down_residuals = down_residuals; u.n_down = n_down; u.mid_residual = mid_residual;
+  return ia2p_unet_forward_x(c, stream, &u, ws, ws_bytes);
 }
 
 // ---- the ControlNet executor (diffusers 0.26.3 ControlNetModel; the reference prepares its attention seam only: ip_adapter.py:143-148) -----------------------------------
@@ -1344,13 +1416,7 @@ ia2p_status ia2p_controlnet_embed(ia2p_ctx* c, void* stream, const void* image, 
 }
 size_t ia2p_controlnet_workspace_bytes(ia2p_ctx* c, int B, int h, int w, int L) {
   if (!c || !c->cn || check_fwd_shape(c, B, h, w, L) != IA2P_OK) return 0;
-  size_t need = 0;
-  for (int mode = 0; mode < 3; ++mode) {
-    const size_t n = pass_dry(c, [&] { return run_forward(c, mode, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w); });
-    if (!n) return 0;
-    need = std::max(need, n);
-  }
-  return need;
+  return forward_workspace(c, FwdCall::shape(B, h, w, L), 3);
 }
 size_t ia2p_controlnet_context_kv_bytes(ia2p_ctx* c, int B, int L) { return c && c->cn && L > c->ctx_drop ? ia2p_context_kv_bytes(c, B, L) : 0; }
 ia2p_status ia2p_controlnet_project_context(ia2p_ctx* c, void* stream, const void* context, int L, int B, void* kv, size_t kv_bytes, void* ws, size_t ws_bytes) {
@@ -1372,15 +1438,11 @@ ia2p_status ia2p_controlnet_forward(ia2p_ctx* c, void* stream, const void* sampl
   if (st != IA2P_OK) return st;
   const size_t need = ia2p_controlnet_residual_layout(c, B, h, w, nullptr, nullptr, nullptr, nullptr);
   if (residual_bytes < need) return fail(c, IA2P_ERR_NOMEM, "controlnet_forward: the residual buffer holds %zu bytes, needs %zu", residual_bytes, need);
-  st = pass_ready(c, [&] { return fold_all(c, (hipStream_t)stream, true); });
-  if (st == IA2P_OK) st = pass_enter(c, stream, ws, ws_bytes);
-  if (st != IA2P_OK) return st;
-  pass_record(c, (kv ? 1000 : 0) + c->ctx_drop, [&] { return run_forward(c, c->gn_fuse, nullptr, 0.f, nullptr, L, nullptr, nullptr, nullptr, B, h, w, kv ? (const half_t*)1 : nullptr); });
-  c->tail_pf = c->arena + c->embed_lo; c->tail_pf_bytes = (c->embed_hi - c->embed_lo) * sizeof(half_t);
-  CtlIo io;
-  io.cond = (const half_t*)cond; io.scales = scales; io.res = (half_t*)residuals;
-  return pass_leave(c, run_forward(c, c->gn_fuse, (const half_t*)sample, 0.f, (const half_t*)context, L, (const half_t*)text_embeds, (const half_t*)time_ids, nullptr,
-                                   B, h, w, (const half_t*)kv, timesteps, nullptr, nullptr, 0, &io));
+  FwdCall f = FwdCall::shape(B, h, w, L);
+  f.sample = (const half_t*)sample; f.context = (const half_t*)context; f.kv = (const half_t*)kv; f.kv_cached = kv != nullptr;
+  f.text_embeds = (const half_t*)text_embeds; f.time_ids = (const half_t*)time_ids; f.timesteps = timesteps;
+  f.io.cond = (const half_t*)cond; f.io.scales = scales; f.io.res = (half_t*)residuals;
+  return forward_pass(c, stream, ws, ws_bytes, (kv ? 1000 : 0) + c->ctx_drop, f);
 }
 
 // ---- context K/V hoisted out of the step: the projections depend on (context, weights) only, constant over a request's steps
@@ -1405,12 +1467,6 @@ ia2p_status ia2p_project_context(ia2p_ctx* c, void* stream, const void* context,
   c->wseq_key = -1;                  // the launch sequence of the next forward is rebuilt
   return pass_leave(c, IA2P_OK);
 }
-ia2p_status ia2p_unet_forward_kv(ia2p_ctx* c, void* stream, const void* sample, float timestep, const void* kv, int L, const void* text_embeds,
-                                 const void* time_ids, void* out, int B, int h, int w, void* ws, size_t ws_bytes) {
-  if (!kv) return fail(c, IA2P_ERR_INVALID, "unet_forward_kv: null argument");
-  return unet_forward_impl(c, stream, sample, timestep, nullptr, kv, L, text_embeds, time_ids, out, B, h, w, ws, ws_bytes);
-}
-
 // Measure-and-pick pass: one forward in which every GEMM / conv site whose shape has no measured plan yet times its
 // candidate tile / K-split plans in place (tune_site) and records the fastest in the process-wide plan table.
 // Re-query ia2p_workspace_bytes afterwards: K-split choices change the slab sizes.

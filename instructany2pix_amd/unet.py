@@ -7,7 +7,7 @@ What callers in the reference touch, and where it lives here:
         pnp_pipeline.py:44-47; diffusion/ip_adapter/ip_adapter.py:114,124-132                   -> .config
   unet.add_embedding.linear_1.in_features       pnp_pipeline.py:47                            -> .add_embedding
   unet.attn_processors / unet.set_attn_processor(...)   ip_adapter.py:123,142,154,168          -> same names
-All arithmetic runs in libia2p_hip.so (`ia2p_unet_forward`); this class owns the flat weight arena and the
+All arithmetic runs in libia2p_hip.so (`ia2p_unet_forward_x`); this class owns the flat weight arena and the
 activation workspace as torch tensors (device memory plumbing only) and keeps no CPU fallback.
 """
 from __future__ import annotations
@@ -23,6 +23,42 @@ from . import _ffi
 from .attention_processor import AttnProcessor2_0, IPAttnProcessor2_0
 from .config import UNetConfig
 from .weights import attn_processor_names
+
+
+_CALL_SIZE = C.sizeof(_ffi.UNetCallC)
+
+
+def per_row(value, B: int, name: str, device, broadcast: bool = True) -> torch.Tensor:
+    """`value` -- a number, a one-element tensor (both stand for every row, unless `broadcast` is off) or B values -- as a contiguous float32 [B] device tensor"""
+    t = torch.full((B,), float(value)) if isinstance(value, (int, float)) else torch.as_tensor(value)
+    t = t.to(device=device, dtype=torch.float32).reshape(-1)
+    if broadcast and t.numel() == 1:
+        t = t.expand(B)
+    if t.numel() != B:
+        raise ValueError(f"{name} has {t.numel()} elements for a batch of {B}")
+    return t.contiguous()
+
+
+def _inputs(model, sample, encoder_hidden_states, added_cond_kwargs):
+    """What every forward of the UNet's kind (this UNet, `HipControlNetModel`) takes, checked against `model.config` and as contiguous fp16 tensors on `model.device`:
+    -> sample, context, text_embeds, time_ids, (B, h, w, L)"""
+    cfg = model.config
+    if encoder_hidden_states is None or added_cond_kwargs is None:
+        raise ValueError("encoder_hidden_states and added_cond_kwargs (text_embeds, time_ids) are required (text_time UNet)")
+    if "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
+        raise ValueError("added_cond_kwargs must carry `text_embeds` and `time_ids`")      # diffusers raises ValueError here too
+    B, c_in, h, w = sample.shape
+    if c_in != cfg.in_channels:
+        raise ValueError(f"sample has {c_in} channels, expected {cfg.in_channels}")
+    f16 = lambda t: t.to(device=model.device, dtype=torch.float16).contiguous()      # noqa: E731
+    sample, ctx = f16(sample), f16(encoder_hidden_states)
+    te, tid = f16(added_cond_kwargs["text_embeds"]), f16(added_cond_kwargs["time_ids"])
+    if ctx.shape[0] != B or ctx.shape[2] != cfg.cross_attention_dim:
+        raise ValueError(f"encoder_hidden_states must be [B, L, {cfg.cross_attention_dim}]")
+    if te.shape != (B, cfg.pooled_dim) or tid.shape != (B, cfg.num_time_ids):
+        raise ValueError(f"Model expects an added time embedding vector of length {cfg.projection_class_embeddings_input_dim}, "
+                         f"but a vector of {te.shape[-1] + tid.shape[-1] * cfg.addition_time_embed_dim} was created.")
+    return sample, ctx, te, tid, (B, h, w, ctx.shape[1])
 
 
 class HipUNet2DConditionModel(_ffi.Executor):
@@ -186,72 +222,14 @@ class HipUNet2DConditionModel(_ffi.Executor):
         self.set_attn_processor(procs)
 
     # ---- forward -----------------------------------------------------------------------------------------------------
-    def workspace_for(self, B: int, h: int, w: int, L: int) -> torch.Tensor:
+    def workspace_for(self, B: int, h: int, w: int, L: int, G: int = 0) -> torch.Tensor:
+        """the workspace of a forward (`ia2p_workspace_bytes_x`); G > 0: a regional one, the plain pass's plus the mask pyramid"""
         # (ip on/off, scale, tokens); the kernel plan table decides the K-split slabs, so its generation is part of the key
-        key = (B, h, w, L, self._ip_sig[:3] if self._ip_sig else None, self._lib.ia2p_plan_generation())
+        key = (B, h, w, L, self._ip_sig[:3] if self._ip_sig else None, self._lib.ia2p_plan_generation(), G)
         if self._ws_key != key:
-            self.workspace(self._lib.ia2p_workspace_bytes(self._ctx, B, h, w, L))
+            self.workspace(self._lib.ia2p_workspace_bytes_x(self._ctx, _ffi.UNetCallC(struct_size=_CALL_SIZE, B=B, h=h, w=w, L=L, G=G)))
             self._ws_key = key
         return self._ws
-
-    def workspace_for_regions(self, B: int, h: int, w: int, L: int, G: int) -> torch.Tensor:
-        """the workspace of a regional forward (`ia2p_workspace_bytes_r`: the plain pass's plus the mask pyramid)"""
-        key = (B, h, w, L, self._ip_sig[:3] if self._ip_sig else None, self._lib.ia2p_plan_generation(), "regions", G)
-        if self._ws_key != key:
-            self.workspace(self._lib.ia2p_workspace_bytes_r(self._ctx, B, h, w, L, G))
-            self._ws_key = key
-        return self._ws
-
-    def _call_regions(self, masks, sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict, out, ip_scales):
-        """cross_attention_kwargs={"ip_adapter_masks": masks}: `ia2p_unet_forward_r`. The installed adapter's token count becomes 4 G for this call and is put back
-        afterwards; context K/V cached under the other count are not reused (`_context_kv` keys them by it)."""
-        self._sync_processors()
-        if self._ip_sig is None or self._ip_sig[0] != "on":
-            raise ValueError("ip_adapter_masks needs the IP-Adapter processors installed (set_attn_processor / load_ip_adapter_weights)")
-        B, c_in, h, w = sample.shape
-        m = torch.as_tensor(masks)
-        if m.ndim == 3:
-            m = m.unsqueeze(0).expand(B, *m.shape)
-        if m.ndim != 4 or m.shape[0] != B or tuple(m.shape[2:]) != (h, w) or not 1 <= m.shape[1] <= 16:
-            raise ValueError(f"ip_adapter_masks must be [B, G, h, w] or [G, h, w] on the latent grid {h} x {w} of `sample`, 1 <= G <= 16; got {tuple(m.shape)}")
-        G = int(m.shape[1])
-        m = m.to(device=self.device, dtype=torch.float16).contiguous()
-        f16 = lambda t: t.to(device=self.device, dtype=torch.float16).contiguous()      # noqa: E731
-        ctx_in = encoder_hidden_states
-        sample, ctx = f16(sample), f16(encoder_hidden_states)
-        te, tid = f16(added_cond_kwargs["text_embeds"]), f16(added_cond_kwargs["time_ids"])
-        if c_in != self.config.in_channels or ctx.shape[0] != B or ctx.shape[2] != self.config.cross_attention_dim:
-            raise ValueError(f"sample must have {self.config.in_channels} channels and encoder_hidden_states be [B, L, {self.config.cross_attention_dim}]")
-        L = ctx.shape[1]
-        if L <= 4 * G:
-            raise ValueError(f"encoder_hidden_states holds {L} rows: {G} regions need {4 * G} image-token rows behind the text rows")
-        ts = timestep if torch.is_tensor(timestep) else torch.full((B,), float(timestep))
-        ts = ts.to(device=self.device, dtype=torch.float32).reshape(-1)
-        ts = (ts.expand(B) if ts.numel() == 1 else ts).contiguous()
-        if ts.numel() != B:
-            raise ValueError(f"timestep tensor has {ts.numel()} elements for a batch of {B}")
-        sc = None
-        if ip_scales is not None:
-            sc = torch.as_tensor(ip_scales).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-            if sc.numel() != B:
-                raise ValueError(f"ip_scales has {sc.numel()} elements for a batch of {B}")
-        if out is None:
-            out = torch.empty(B, self.config.out_channels, h, w, dtype=torch.float16, device=self.device)
-        sig = self._ip_sig
-        try:
-            if sig[2] != 4 * G:
-                _ffi.check(self._lib.ia2p_set_ip_adapter(self._ctx, 1, 4 * G, sig[1]), self._ctx)
-                self._ip_sig = sig[:2] + (4 * G,) + sig[3:]
-            ws = self.workspace_for_regions(B, h, w, L, G)
-            kv = self._context_kv(ctx_in, ctx, B, L, ws) if self.cache_context_kv else None
-            _ffi.check(self._lib.ia2p_unet_forward_r(self._ctx, _ffi.current_stream(), _ffi.ptr(sample), _ffi.ptr(ts), _ffi.ptr(sc) if sc is not None else None,
-                                                     None if kv is not None else _ffi.ptr(ctx), _ffi.ptr(kv) if kv is not None else None, L, _ffi.ptr(te), _ffi.ptr(tid),
-                                                     _ffi.ptr(out), B, h, w, _ffi.ptr(ws), ws.numel(), _ffi.ptr(m), G), self._ctx)
-        finally:
-            if self._ip_sig is not sig:
-                self._ip_sig = sig
-                _ffi.check(self._lib.ia2p_set_ip_adapter(self._ctx, 1, sig[2], sig[1]), self._ctx)
-        return (out,) if not return_dict else SimpleNamespace(sample=out)
 
     def _channels_last(self, t, B, C_, H, W, what):
         """a logical-NCHW residual [B, C, H, W] as a channels-last device buffer: by pointer when its strides already are, converted otherwise"""
@@ -278,130 +256,93 @@ class HipUNet2DConditionModel(_ffi.Executor):
                 out.append((ch[i], h, w))
         return out
 
-    def _call_controlled(self, down, mid, sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict, out, ip_scales):
-        """`ia2p_unet_forward_c`: the per-row pass plus the residuals, injected in place where the up path pops each skip. Every refusal comes before any launch."""
-        self._sync_processors()
-        B, c_in, h, w = sample.shape
-        if c_in != self.config.in_channels:
-            raise ValueError(f"sample has {c_in} channels, expected {self.config.in_channels}")
+    def _region_masks(self, masks, B, h, w, L):
+        """`ip_adapter_masks` as a contiguous fp16 device tensor [B, G, h, w]"""
+        if self._ip_sig is None or self._ip_sig[0] != "on":
+            raise ValueError("ip_adapter_masks needs the IP-Adapter processors installed (set_attn_processor / load_ip_adapter_weights)")
+        m = torch.as_tensor(masks)
+        if m.ndim == 3:
+            m = m.unsqueeze(0).expand(B, *m.shape)
+        if m.ndim != 4 or m.shape[0] != B or tuple(m.shape[2:]) != (h, w) or not 1 <= m.shape[1] <= 16:
+            raise ValueError(f"ip_adapter_masks must be [B, G, h, w] or [G, h, w] on the latent grid {h} x {w} of `sample`, 1 <= G <= 16; got {tuple(m.shape)}")
+        if L <= 4 * m.shape[1]:
+            raise ValueError(f"encoder_hidden_states holds {L} rows: {m.shape[1]} regions need {4 * m.shape[1]} image-token rows behind the text rows")
+        return m.to(device=self.device, dtype=torch.float16).contiguous()
+
+    def _residuals(self, down, mid, B, h, w):
+        """a ControlNet's residuals as channels-last device buffers, the mid residual last"""
         shapes = self.skip_shapes(h, w)
         if len(down) != len(shapes):
             raise ValueError(f"{len(down)} down_block_additional_residuals, this UNet has {len(shapes)} skips")
-        f16 = lambda t: t.to(device=self.device, dtype=torch.float16).contiguous()      # noqa: E731
-        ctx_in = encoder_hidden_states
-        sample, ctx = f16(sample), f16(encoder_hidden_states)
-        te, tid = f16(added_cond_kwargs["text_embeds"]), f16(added_cond_kwargs["time_ids"])
-        if ctx.shape[0] != B or ctx.shape[2] != self.config.cross_attention_dim:
-            raise ValueError(f"encoder_hidden_states must be [B, L, {self.config.cross_attention_dim}]")
-        if te.shape != (B, self.config.pooled_dim) or tid.shape != (B, self.config.num_time_ids):
-            raise ValueError("added_cond_kwargs do not fit this UNet's text_time embedding")
         keep = [self._channels_last(t, B, c_, hh, ww, f"down_block_additional_residuals[{k}]") for k, (t, (c_, hh, ww)) in enumerate(zip(down, shapes))]
-        keep.append(self._channels_last(mid, B, self.config.block_out_channels[-1], shapes[-1][1], shapes[-1][2], "mid_block_additional_residual"))
-        L = ctx.shape[1]
-        ts = timestep if torch.is_tensor(timestep) else torch.full((B,), float(timestep))
-        ts = ts.to(device=self.device, dtype=torch.float32).reshape(-1)
-        ts = (ts.expand(B) if ts.numel() == 1 else ts).contiguous()
-        if ts.numel() != B:
-            raise ValueError(f"timestep tensor has {ts.numel()} elements for a batch of {B}")
-        sc = None
-        if ip_scales is not None:
-            sc = torch.as_tensor(ip_scales).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-            if sc.numel() != B:
-                raise ValueError(f"ip_scales has {sc.numel()} elements for a batch of {B}")
-        ws = self.workspace_for(B, h, w, L)
-        if out is None:
-            out = torch.empty(B, self.config.out_channels, h, w, dtype=torch.float16, device=self.device)
-        kv = self._context_kv(ctx_in, ctx, B, L, ws) if self.cache_context_kv else None
-        ptrs = (C.c_void_p * len(down))(*[t.data_ptr() for t in keep[:-1]])
-        _ffi.check(self._lib.ia2p_unet_forward_c(self._ctx, _ffi.current_stream(), _ffi.ptr(sample), _ffi.ptr(ts), _ffi.ptr(sc) if sc is not None else None,
-                                                 None if kv is not None else _ffi.ptr(ctx), _ffi.ptr(kv) if kv is not None else None, L, _ffi.ptr(te), _ffi.ptr(tid),
-                                                 _ffi.ptr(out), B, h, w, _ffi.ptr(ws), ws.numel(), ptrs, len(down), C.c_void_p(keep[-1].data_ptr()), None, 0), self._ctx)
-        return (out,) if not return_dict else SimpleNamespace(sample=out)
+        return keep + [self._channels_last(mid, B, self.config.block_out_channels[-1], shapes[-1][1], shapes[-1][2], "mid_block_additional_residual")]
 
     def __call__(self, sample, timestep, encoder_hidden_states=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                  return_dict: bool = False, out: Optional[torch.Tensor] = None, _tune_reps: Optional[int] = None,
                  ip_scales: Optional[torch.Tensor] = None, down_block_additional_residuals=None, mid_block_additional_residual=None, **unused):
-        """down_block_additional_residuals / mid_block_additional_residual (diffusers' names): a ControlNet's residuals, one logical-NCHW tensor per skip and one for the
-        mid block's output; tensors with channels-last strides (what `HipControlNetModel` returns) are passed by pointer, others are converted. Both None: today's path.
+        """One evaluation: the options are resolved, the inputs marshalled once (`_inputs`), and one record goes to `ia2p_unet_forward_x` (include/ia2p.h states which
+        options may meet). Every refusal comes before any launch.
+        down_block_additional_residuals / mid_block_additional_residual (diffusers' names): a ControlNet's residuals, one logical-NCHW tensor per skip and one for the
+        mid block's output; tensors with channels-last strides (what `HipControlNetModel` returns) are passed by pointer, others are converted. Both None: none.
         cross_attention_kwargs={"ip_adapter_masks": t} (t [B, G, h, w] on the latent grid of `sample`, or [G, h, w] for every row): regional image prompts -- the
-        last 4 G rows of the context are G groups of four image tokens, group g acts where t[:, g] says (diffusers' `ip_adapter_masks`; `ia2p_unet_forward_r`).
-        `timestep`: a number / 0-dim tensor as the reference passes it, or a [B] tensor -- one timestep per batch element, as diffusers' UNet
-        accepts (`ia2p_unet_forward_v`); `ip_scales` (or cross_attention_kwargs={"ip_scales": ...}): optional [B] tensor, the IP-Adapter scale of
-        every batch element (the reference sets one value per call, ip_adapter.py:211-214). Both let independent requests share one evaluation."""
-        if encoder_hidden_states is None or added_cond_kwargs is None:
-            raise ValueError("encoder_hidden_states and added_cond_kwargs (text_embeds, time_ids) are required (text_time UNet)")
-        if "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
-            raise ValueError("added_cond_kwargs must carry `text_embeds` and `time_ids`")      # diffusers raises ValueError here too
-        controlled = down_block_additional_residuals is not None or mid_block_additional_residual is not None
-        if controlled:
-            if down_block_additional_residuals is None or mid_block_additional_residual is None:
-                raise ValueError("down_block_additional_residuals and mid_block_additional_residual come together")
-            if cross_attention_kwargs and cross_attention_kwargs.get("ip_adapter_masks") is not None:
-                raise ValueError("ControlNet residuals together with ip_adapter_masks: the regional pass is not combined with a ControlNet")
-            if _tune_reps is not None:
-                raise ValueError("autotune takes no ControlNet residuals")
-            if ip_scales is None and cross_attention_kwargs:
-                ip_scales = cross_attention_kwargs.get("ip_scales")
-            return self._call_controlled(list(down_block_additional_residuals), mid_block_additional_residual, sample, timestep, encoder_hidden_states,
-                                         added_cond_kwargs, return_dict, out, ip_scales)
-        if cross_attention_kwargs and cross_attention_kwargs.get("ip_adapter_masks") is not None:
-            if _tune_reps is not None:
-                raise ValueError("autotune takes no ip_adapter_masks")
-            if ip_scales is None:
-                ip_scales = cross_attention_kwargs.get("ip_scales")
-            return self._call_regions(cross_attention_kwargs["ip_adapter_masks"], sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict, out, ip_scales)
+        last 4 G rows of the context are G groups of four image tokens, group g acts where t[:, g] says (diffusers' `ip_adapter_masks`). The installed adapter's token
+        count becomes 4 G for this call and is put back afterwards; context K/V cached under the other count are not reused (`_context_kv` keys them by it).
+        `timestep`: a number / 0-dim tensor as the reference passes it (it travels by value), or a [B] tensor -- one timestep per batch element, as diffusers' UNet
+        accepts; `ip_scales` (or cross_attention_kwargs={"ip_scales": ...}): optional [B] tensor, the IP-Adapter scale of every batch element (the reference sets one
+        value per call, ip_adapter.py:211-214). Both let independent requests share one evaluation."""
+        # 1. the options
+        kw = cross_attention_kwargs or {}
+        masks, down, mid = kw.get("ip_adapter_masks"), down_block_additional_residuals, mid_block_additional_residual
+        if ip_scales is None:
+            ip_scales = kw.get("ip_scales")
+        if (down is None) != (mid is None):
+            raise ValueError("down_block_additional_residuals and mid_block_additional_residual come together")
+        if down is not None and masks is not None:
+            raise ValueError("ControlNet residuals together with ip_adapter_masks: the regional pass is not combined with a ControlNet")
+        per_row_call = down is not None or masks is not None or ip_scales is not None or (torch.is_tensor(timestep) and timestep.numel() > 1)
+        if _tune_reps is not None and per_row_call:
+            raise ValueError("autotune takes a scalar timestep and no ip_scales, ip_adapter_masks or ControlNet residuals")
+        # 2. the inputs
         self._sync_processors()
-        B, c_in, h, w = sample.shape
-        if c_in != self.config.in_channels:
-            raise ValueError(f"sample has {c_in} channels, expected {self.config.in_channels}")
-        f16 = lambda t: t.to(device=self.device, dtype=torch.float16).contiguous()
         ctx_in = encoder_hidden_states
-        sample, ctx = f16(sample), f16(encoder_hidden_states)
-        te, tid = f16(added_cond_kwargs["text_embeds"]), f16(added_cond_kwargs["time_ids"])
-        if ctx.shape[0] != B or ctx.shape[2] != self.config.cross_attention_dim:
-            raise ValueError(f"encoder_hidden_states must be [B, L, {self.config.cross_attention_dim}]")
-        if te.shape != (B, self.config.pooled_dim) or tid.shape != (B, self.config.num_time_ids):
-            raise ValueError(f"Model expects an added time embedding vector of length {self.config.projection_class_embeddings_input_dim}, "
-                             f"but a vector of {te.shape[-1] + tid.shape[-1] * self.config.addition_time_embed_dim} was created.")
-        L = ctx.shape[1]
-        ws = self.workspace_for(B, h, w, L)
+        sample, ctx, te, tid, (B, h, w, L) = _inputs(self, sample, encoder_hidden_states, added_cond_kwargs)
+        m = self._region_masks(masks, B, h, w, L) if masks is not None else None
+        G = int(m.shape[1]) if m is not None else 0
+        res = self._residuals(list(down), mid, B, h, w) if down is not None else None
+        # (a scalar timestep with no per-row option travels by value: no [B] tensor, no copy to the device)
+        ts = per_row(timestep, B, "timestep tensor", self.device) if per_row_call else None
+        sc = per_row(ip_scales, B, "ip_scales", self.device, broadcast=False) if ip_scales is not None else None
         if out is None:
             out = torch.empty(B, self.config.out_channels, h, w, dtype=torch.float16, device=self.device)
-        if ip_scales is None and cross_attention_kwargs:
-            ip_scales = cross_attention_kwargs.get("ip_scales")
-        per_sample = (torch.is_tensor(timestep) and timestep.numel() > 1) or ip_scales is not None
-        if per_sample:
-            if _tune_reps is not None:
-                raise ValueError("autotune takes a scalar timestep")
-            ts = timestep if torch.is_tensor(timestep) else torch.full((B,), float(timestep))
-            ts = ts.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-            if ts.numel() == 1:
-                ts = ts.expand(B).contiguous()
-            if ts.numel() != B:
-                raise ValueError(f"timestep tensor has {ts.numel()} elements for a batch of {B}")
-            sc = None
-            if ip_scales is not None:
-                sc = torch.as_tensor(ip_scales).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-                if sc.numel() != B:
-                    raise ValueError(f"ip_scales has {sc.numel()} elements for a batch of {B}")
-            kv = self._context_kv(ctx_in, ctx, B, L, ws) if self.cache_context_kv else None
-            _ffi.check(self._lib.ia2p_unet_forward_v(self._ctx, _ffi.current_stream(), _ffi.ptr(sample), _ffi.ptr(ts), _ffi.ptr(sc) if sc is not None else None,
-                                                     None if kv is not None else _ffi.ptr(ctx), _ffi.ptr(kv) if kv is not None else None, L, _ffi.ptr(te), _ffi.ptr(tid),
-                                                     _ffi.ptr(out), B, h, w, _ffi.ptr(ws), ws.numel()), self._ctx)
-            return (out,) if not return_dict else SimpleNamespace(sample=out)
-        t = float(timestep.item()) if torch.is_tensor(timestep) else float(timestep)
-        args = (self._ctx, _ffi.current_stream(), _ffi.ptr(sample), t, _ffi.ptr(ctx), L, _ffi.ptr(te), _ffi.ptr(tid), _ffi.ptr(out), B, h, w,
-                _ffi.ptr(ws), ws.numel())
-        if _tune_reps is not None:
-            sites = C.c_int(0)
-            _ffi.check(self._lib.ia2p_autotune(*args, int(_tune_reps), C.addressof(sites)), self._ctx)
-            return sites.value
-        if self.cache_context_kv:
-            kv = self._context_kv(ctx_in, ctx, B, L, ws)
-            _ffi.check(self._lib.ia2p_unet_forward_kv(self._ctx, _ffi.current_stream(), _ffi.ptr(sample), t, _ffi.ptr(kv), L, _ffi.ptr(te), _ffi.ptr(tid),
-                                                      _ffi.ptr(out), B, h, w, _ffi.ptr(ws), ws.numel()), self._ctx)
-        else:
-            _ffi.check(self._lib.ia2p_unet_forward(*args), self._ctx)
+        call = _ffi.UNetCallC(struct_size=_CALL_SIZE, B=B, h=h, w=w, L=L, G=G, sample=_ffi.addr(sample), text_embeds=_ffi.addr(te), time_ids=_ffi.addr(tid),
+                              out=_ffi.addr(out), timesteps=_ffi.addr(ts), ip_scales=_ffi.addr(sc), region_masks=_ffi.addr(m))
+        if ts is None:
+            call.timestep = float(timestep.item()) if torch.is_tensor(timestep) else float(timestep)
+        if res is not None:
+            call.n_down, call.mid_residual = len(res) - 1, _ffi.addr(res[-1])
+            call.down_residuals = (C.c_void_p * call.n_down)(*[t.data_ptr() for t in res[:-1]])
+        sig = self._ip_sig
+        try:
+            if G and sig[2] != 4 * G:
+                _ffi.check(self._lib.ia2p_set_ip_adapter(self._ctx, 1, 4 * G, sig[1]), self._ctx)
+                self._ip_sig = sig[:2] + (4 * G,) + sig[3:]
+            # 3. the workspace, 4. the context or its cached projections, 5. + 6. the record and the call
+            ws = self.workspace_for(B, h, w, L, G)
+            if _tune_reps is not None:      # (ia2p_autotune keeps the scalar argument list)
+                sites = C.c_int(0)
+                _ffi.check(self._lib.ia2p_autotune(self._ctx, _ffi.current_stream(), _ffi.ptr(sample), call.timestep, _ffi.ptr(ctx), L, _ffi.ptr(te), _ffi.ptr(tid),
+                                                   _ffi.ptr(out), B, h, w, _ffi.ptr(ws), ws.numel(), int(_tune_reps), C.addressof(sites)), self._ctx)
+                return sites.value
+            if self.cache_context_kv:
+                ip = sig and self._ip_sig[:1] + self._ip_sig[2:3]          # (on/off, tokens): the split of the context rows
+                call.kv = _ffi.addr(self._context_kv(ip, self._lib.ia2p_context_kv_bytes, self._lib.ia2p_project_context, ctx_in, ctx, B, L, ws))
+            else:
+                call.context = _ffi.addr(ctx)
+            _ffi.check(self._lib.ia2p_unet_forward_x(self._ctx, _ffi.current_stream(), call, _ffi.ptr(ws), ws.numel()), self._ctx)
+        finally:
+            if self._ip_sig is not sig:
+                self._ip_sig = sig
+                _ffi.check(self._lib.ia2p_set_ip_adapter(self._ctx, 1, sig[2], sig[1]), self._ctx)
         return (out,) if not return_dict else SimpleNamespace(sample=out)
 
     def set_gn_fuse(self, mode: int):
@@ -413,22 +354,6 @@ class HipUNet2DConditionModel(_ffi.Executor):
         """Forget the cached context K/V projections (a new request begins: the next evaluation projects its context again); the buffer is kept."""
         if self._kv is not None:
             self._kv = (None, -1, None, -1, self._kv[4], self._kv[5])
-
-    def _context_kv(self, ctx_in, ctx, B, L, ws):
-        """K/V projections of `ctx` (ia2p_project_context), cached while the same unmodified tensor object arrives with the same weights
-        and IP-Adapter topology. The source tensor is kept alive so its address cannot be handed to another tensor."""
-        ip = self._ip_sig[:1] + self._ip_sig[2:3] if self._ip_sig else None          # (on/off, tokens): the split of the context rows
-        k = self._kv
-        if k is not None and k[0] is ctx_in and k[1] == ctx_in._version and k[2] == ip and k[3] == self._weights_gen and k[4] == (B, L):
-            return k[5]
-        n = self._lib.ia2p_context_kv_bytes(self._ctx, B, L)
-        if n == 0:
-            _ffi.check(2, self._ctx)
-        buf = k[5] if (k is not None and k[5].numel() == n) else torch.empty(n, dtype=torch.uint8, device=self.device)
-        self._kv = None
-        _ffi.check(self._lib.ia2p_project_context(self._ctx, _ffi.current_stream(), _ffi.ptr(ctx), L, B, _ffi.ptr(buf), n, _ffi.ptr(ws), ws.numel()), self._ctx)
-        self._kv = (ctx_in, ctx_in._version, ip, self._weights_gen, (B, L), buf)
-        return buf
 
     def autotune(self, sample, timestep, encoder_hidden_states, added_cond_kwargs, reps: int = 7) -> int:
         """Measure the candidate (tile, K-split) plans of every GEMM / conv shape of this call in place and keep the fastest

@@ -77,13 +77,18 @@ def test_workspace_scales_with_batch(lib):
 def test_workspace_bytes_are_the_recorded_ones(lib):
     """every executor's workspace query (host dry runs over a first-fit allocator: the ORDER of allocations decides the answer) returns the bytes it returned before the
     pass protocol moved into engine_rt (pass_dry) and run_resnet's two GroupNorm-before-convolution branches became one helper. UNet: the maximum over the four GroupNorm
-    modes, on the cost-model plans and with every eligible 3x3 site on its GroupNorm-fused plan."""
+    modes, on the cost-model plans and with every eligible 3x3 site on its GroupNorm-fused plan. The record query (ia2p_workspace_bytes_x) answers what the
+    argument-list queries answer, and those what they answered before they became its callers."""
     from instructany2pix_amd import _ffi
     from instructany2pix_amd import imagebind as ib
-    from instructany2pix_amd.config import sdxl_base, tiny, tiny_clip, tiny_vae
+    from instructany2pix_amd.config import sdxl_base, tiny, tiny_clip, tiny_controlnet, tiny_vae
     lib.ia2p_plan_clear()
     unet = {"tiny": (tiny(), {(-1, 1, 16, 16, 77): 1889280, (-1, 2, 16, 24, 77): 4474112, (1, 1, 16, 16, 77): 1897472, (1, 2, 16, 24, 77): 4523264}),
             "sdxl": (sdxl_base(), {(-1, 1, 64, 64, 77): 78135808, (-1, 8, 64, 64, 77): 457310464, (1, 1, 64, 64, 77): 78135808, (1, 8, 64, 64, 77): 457310464})}
+    # (added with the call record, from the parent's library: the regional query -- (B, h, w, L, G), adapter off --, the ControlNet's and its condition embedding's)
+    regions = {(-1, 2, 16, 16, 85, 2): 3999744, (-1, 1, 16, 16, 81, 1): 1940992, (1, 2, 16, 16, 85, 2): 4032512, (1, 1, 16, 16, 81, 1): 1957376}
+    cnet = {(-1, 1, 16, 16, 77): 893696, (-1, 2, 16, 24, 77): 2106368, (1, 1, 16, 16, 77): 910080, (1, 2, 16, 24, 77): 2130944}
+    record = lambda B, h, w, L, G=0: _ffi.UNetCallC(struct_size=C.sizeof(_ffi.UNetCallC), B=B, h=h, w=w, L=L, G=G)      # noqa: E731
     try:
         for name, (cfg, want) in unet.items():
             ctx = C.c_void_p()
@@ -91,7 +96,18 @@ def test_workspace_bytes_are_the_recorded_ones(lib):
             for (plan, *shape), n in want.items():
                 lib.ia2p_debug_set_gn_plan(plan)
                 assert lib.ia2p_workspace_bytes(ctx, *shape) == n, (name, plan, shape)
+                assert lib.ia2p_workspace_bytes_x(ctx, record(*shape)) == n and lib.ia2p_workspace_bytes_c(ctx, *shape) == n, (name, plan, shape)
+            for (plan, *shape), n in (regions if name == "tiny" else {}).items():
+                lib.ia2p_debug_set_gn_plan(plan)
+                assert lib.ia2p_workspace_bytes_r(ctx, *shape) == n and lib.ia2p_workspace_bytes_x(ctx, record(*shape)) == n, (plan, shape)
             lib.ia2p_destroy(ctx)
+        h = C.c_void_p()
+        _ffi.check(lib.ia2p_controlnet_create(C.byref(_ffi.make_controlnet_config(tiny_controlnet())), C.byref(h)), None, "controlnet")
+        for (plan, *shape), n in cnet.items():
+            lib.ia2p_debug_set_gn_plan(plan)
+            assert lib.ia2p_controlnet_workspace_bytes(h, *shape) == n, (plan, shape)
+            assert lib.ia2p_controlnet_embed_workspace_bytes(h, 2, 16, 16) == 2097408, plan
+        lib.ia2p_controlnet_destroy(h)
     finally:
         lib.ia2p_debug_set_gn_plan(-1)
     h = C.c_void_p()

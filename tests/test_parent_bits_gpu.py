@@ -22,6 +22,9 @@ PARENT = {
     "unet_halo_gn12": "7bee3b3a39c04856df149a559e32f656ce75fb0ebe74e6fbbf4c3f358a0010f6",
     "unet_kv": "5f5b034f68cfc3f1cf98bf8b6754b23cf5864aa8305c68a9b320f952a674e12d",
     "unet_v": "50a8c4eba196253cdd11c0fb6d925326b49b9fdee23dd0eabbfb5ea6ea39244b",
+    "unet_r": "a447c40ac2e920d8fdcb15870c439bbcf5100c9301375bc17be3846ef2642dcd",
+    "unet_c": "8c691c270425bf697d0e4802a7963247ca7517b13ec198cb631de7c10c4a1eef",
+    "controlnet": "ec5e129c67447fa8e5b66e17c33bb4c59c8250d1587dbd2c84f51a81e40930dd",
     "vae_decode": "bd8dbd6d5816b11c407b3c74e8338e9956c56b33b2686af0163f3c2ef34263e6",
     "vae_encode": "9475492b2bd7c96785f720bce78130c91585102a21939cdd2e1aadc97568b7b4",
     "vit": "4b5e5cd8cc3a31327579324404146a8b34afc6a523e8e47895684ed845d34d6a",
@@ -61,14 +64,15 @@ class UNetCase:
         self.ctx = rnd(self.B, self.L, cfg.cross_attention_dim, seed=2).to(DEV)
         self.cond = dict(text_embeds=rnd(self.B, cfg.pooled_dim, seed=3).to(DEV), time_ids=torch.tensor([[128.0, 128.0, 0, 0, 128.0, 128.0]] * self.B).half().to(DEV))
 
-    def run(self, gn, kv=False, timestep=None, ip_scales=None, tile=-1):
+    def run(self, gn, kv=False, timestep=None, ip_scales=None, tile=-1, ctx=None, **options):
         self.net.set_gn_fuse(gn)
         self.net.cache_context_kv = kv
         self.net.invalidate_context_kv()
         self.lib.ia2p_debug_set_gemm_tile(tile)
         self.net._ws_key = None      # (the forced tile changes the K splits: the workspace is sized again)
         try:
-            out = self.net(self.sample, self.t if timestep is None else timestep, encoder_hidden_states=self.ctx, added_cond_kwargs=self.cond, ip_scales=ip_scales)[0]
+            out = self.net(self.sample, self.t if timestep is None else timestep, encoder_hidden_states=self.ctx if ctx is None else ctx, added_cond_kwargs=self.cond,
+                           ip_scales=ip_scales, **options)[0]
             torch.cuda.synchronize()
         finally:
             self.lib.ia2p_debug_set_gemm_tile(-1)
@@ -108,6 +112,46 @@ def test_unet_project_context_then_forward_kv(unet):
 
 def test_unet_forward_v_two_timesteps_two_ip_scales(unet):
     assert sha(unet.run(1, timestep=torch.tensor([981.0, 441.0]), ip_scales=torch.tensor([1.0, 0.4]))) == PARENT["unet_v"]
+
+
+# ---- the option paths of the UNet callable and the ControlNet, through the public `__call__` only: recorded from the parent of the commit that made one call record
+# (ia2p_unet_call) of the five argument lists. Both routes to the context K/V in one digest.
+TS2 = torch.tensor([981.0, 441.0])
+
+
+def test_unet_regional_image_prompts(unet):
+    """ip_adapter_masks [2, 2, 16, 16]: two token groups, an 85-row context (77 text rows + 2 x 4 image tokens), per-row timesteps"""
+    masks = torch.rand(2, 2, 16, 16, generator=torch.Generator().manual_seed(5)).half().to(DEV)
+    ctx = rnd(unet.B, 85, unet.ctx.shape[2], seed=4).to(DEV)
+    outs = [unet.run(1, kv=kv, timestep=TS2, ctx=ctx, cross_attention_kwargs={"ip_adapter_masks": masks}) for kv in (False, True)]
+    assert sha(*outs) == PARENT["unet_r"]
+
+
+def test_unet_controlnet_residuals(unet):
+    """a residual per skip of the 16 x 16 latent and one for the mid block's output, logical NCHW"""
+    shapes = unet.net.skip_shapes(unet.h, unet.h)
+    res = [0.25 * rnd(unet.B, c, hh, ww, seed=40 + k).to(DEV) for k, (c, hh, ww) in enumerate(shapes + [shapes[-1]])]
+    outs = [unet.run(1, kv=kv, timestep=TS2, down_block_additional_residuals=res[:-1], mid_block_additional_residual=res[-1]) for kv in (False, True)]
+    assert sha(*outs) == PARENT["unet_c"]
+
+
+def test_controlnet_residual_buffer(unet):
+    """the tiny ControlNet on the UNet case's inputs, a seeded condition [2, 3, 128, 128], conditioning scales (0.6, 1.3): the whole residual buffer"""
+    from instructany2pix_amd.config import tiny_controlnet
+    from instructany2pix_amd.controlnet import HipControlNetModel
+    from instructany2pix_amd.weights import controlnet_param_specs, synthetic_state_dict
+    cfg = tiny_controlnet()
+    cn = HipControlNetModel(cfg, DEV)
+    cn.load_state_dict(synthetic_state_dict(controlnet_param_specs(cfg), seed=9))
+    cn.set_gn_fuse(1)
+    cond = torch.rand(unet.B, 3, 128, 128, generator=torch.Generator().manual_seed(6)).half().to(DEV)
+    bufs = []
+    for kv in (False, True):
+        cn.cache_context_kv = kv
+        cn(unet.sample, TS2, encoder_hidden_states=unet.ctx, controlnet_cond=cond, conditioning_scale=torch.tensor([0.6, 1.3]), added_cond_kwargs=unet.cond)
+        torch.cuda.synchronize()
+        bufs.append(cn._res.clone())
+    assert sha(*bufs) == PARENT["controlnet"]
 
 
 # ---- VAE, ViT towers, LLM prefill, CLIP ----------------------------------------------------------------------------------------------------------------------------
