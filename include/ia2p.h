@@ -440,6 +440,38 @@ ia2p_status ia2p_gemm_splitk(void* stream, const void* A, const void* W, const v
  * stride 1|2; up=1 convolves the nearest-x2 upsampled x; rowvec [B,Co] (time embedding) and residual optional. */
 ia2p_status ia2p_conv3x3(void* stream, const void* x, const void* Wp, const void* bias, const void* rowvec, const void* residual,
                          void* y, int B, int Hs, int Ws, int Cin, int Co, int stride, int up);
+/* The GEMM and the 3x3 convolution with every option an executor sets on its own launch descriptor, as records (zero a record, fill what the launch uses):
+ *   C[m, n] = fp16(fp16(act(acc_scale * sum_k A[row(m), k] W[n, k] + bias_scale * bias[n])) + bias_scale * rowvec[m / rows_per_batch, n] + residual[m, n])
+ * with the fp16 rounding in the middle only where a row vector or a residual follows, and with ln != NULL the folded LayerNorm of ia2p_gemm_ex in place of the scales
+ * and the bias. row(m) = m, or with rpb > 0 (m / rpb) * bstride + m % rpb + roff: rows [roff, roff + rpb) of every block of bstride rows (the text rows or the
+ * image-token rows of a [B, L, K] context). lda / ldw >= K and ldc / ldr >= N are row strides in elements: an operand may be a column block of a wider tensor, C a
+ * column block of a wider output (pass C + col0). act: 0 none, 1 GELU (erf), 2 quick-GELU x sigmoid(1.702 x), 3 GELU (tanh, GPT-2's). acc_scale / bias_scale: 0 = 1.
+ * stats_out / stats_slots, splitk / partial: as ia2p_gemm_ex. The library's plan picks the tile (ia2p_debug_set_gemm_tile forces one).
+ * Refusals, all on the host before any launch: a NULL record, A, W or C, an incomplete ln, act outside 0 .. 3, a scale that is not finite, A or W not 16-byte aligned
+ *   or lda / ldw no multiple of 8, C / bias / residual / rowvec not 8-byte aligned or ldc / ldr / rowvec_ld no multiple of 4, ln->colsum / ln->fbias / partial not
+ *   16-byte or ln->stats / stats_out not 8-byte aligned are IA2P_ERR_INVALID; M < 1, N % 4, K % 64, a stride below its width, splitk outside 0 .. min(K / 64, 255),
+ *   rpb or roff outside 0 .. 65535 (they travel in 16 bits each), bstride < 0, a stride or offset without rpb, an operand of 2 GiB or more are IA2P_ERR_SHAPE.
+ * ia2p_conv3x3_form: ia2p_conv3x3 plus pad_lo (zero rows / columns in front of the image: 1, or 0 -- the VAE encoder's stride-2 downsample pads only behind it; one row
+ *   and column behind the image in every mode: Ho = ((Hs << up) + pad_lo - 2) / stride + 1), the two scales and the K split (partial: splitk * B Ho Wo * Co floats).
+ *   Refused on the host like ia2p_gemm_form's: NULL x, Wp or y, scales that are not finite, x / Wp / partial not 16-byte or y / bias / rowvec / residual not 8-byte
+ *   aligned IA2P_ERR_INVALID; Cin % 64, Co % 4, stride, up or pad_lo outside their two values, an image without an output pixel, splitk outside
+ *   0 .. min(9 Cin / 64, 255), an operand of 2 GiB or more (whichever tile the plan picks) IA2P_ERR_SHAPE. */
+struct ia2p_gemm_form {
+  const void* A; int lda; const void* W; int ldw; const void* bias; const void* residual; int ldr; void* C; int ldc; int M, N, K;
+  int rpb, bstride, roff;
+  int act; float acc_scale, bias_scale;
+  const void* rowvec; int rowvec_ld, rows_per_batch;
+  const ia2p_ln_fold* ln; float* stats_out; int* stats_slots;
+  int splitk; float* partial;
+};      /* (a struct tag: the entry point carries the same name) */
+ia2p_status ia2p_gemm_form(void* stream, const struct ia2p_gemm_form* d);
+typedef struct {
+  const void* x; const void* Wp; const void* bias; const void* rowvec; const void* residual; void* y;
+  int B, Hs, Ws, Cin, Co, stride, up, pad_lo;
+  float acc_scale, bias_scale;
+  int splitk; float* partial;
+} ia2p_conv_form;
+ia2p_status ia2p_conv3x3_form(void* stream, const ia2p_conv_form* d);
 /* ---- GroupNorm + SiLU fused into the 3x3 convolution that consumes it (round 5). Reference: diffusers ResnetBlock2D `conv1(nonlinearity(norm1(x)))` /
  * `conv2(dropout(nonlinearity(norm2(h))))` behind instructany2pix/ddim/pnp_pipeline.py:253-260 (in-tree twin: llm/model/vae/modules/blocks.py:122-142).
  * The norm's statistics come from the PRODUCER of its input: per slot of `rows` consecutive rows (one M-tile; HW / rows slots per image) and per channel, fp64

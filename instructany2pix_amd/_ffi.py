@@ -79,6 +79,20 @@ class ConvGnC(C.Structure):
 _P, _I, _F, _SZ, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 
 
+class GemmFormC(C.Structure):
+    """ia2p_gemm_form (include/ia2p.h): a GEMM launch with every option of its descriptor (strides, row map, activation, epilogue scales, folded LayerNorm)"""
+    _fields_ = [("A", _P), ("lda", _I), ("W", _P), ("ldw", _I), ("bias", _P), ("residual", _P), ("ldr", _I), ("C", _P), ("ldc", _I), ("M", _I), ("N", _I), ("K", _I),
+                ("rpb", _I), ("bstride", _I), ("roff", _I), ("act", _I), ("acc_scale", _F), ("bias_scale", _F),
+                ("rowvec", _P), ("rowvec_ld", _I), ("rows_per_batch", _I), ("ln", _P), ("stats_out", _P), ("stats_slots", _P), ("splitk", _I), ("partial", _P)]
+
+
+class ConvFormC(C.Structure):
+    """ia2p_conv_form (include/ia2p.h): ia2p_conv3x3 plus pad_lo, the epilogue scales and the K split"""
+    _fields_ = [("x", _P), ("Wp", _P), ("bias", _P), ("rowvec", _P), ("residual", _P), ("y", _P),
+                ("B", _I), ("Hs", _I), ("Ws", _I), ("Cin", _I), ("Co", _I), ("stride", _I), ("up", _I), ("pad_lo", _I),
+                ("acc_scale", _F), ("bias_scale", _F), ("splitk", _I), ("partial", _P)]
+
+
 class UNetCallC(C.Structure):
     """ia2p_unet_call (include/ia2p.h): one UNet evaluation as a record; which fields may meet is the table there"""
     _fields_ = [("struct_size", C.c_uint32), ("B", _I), ("h", _I), ("w", _I), ("L", _I), ("G", _I), ("n_down", _I), ("timestep", _F),
@@ -164,6 +178,8 @@ SIGNATURES = {
     "ia2p_ffn": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ia2p_fold_layernorm": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I]),
     "ia2p_gemm_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "ia2p_gemm_form": (_I, [_P, C.POINTER(GemmFormC)]),
+    "ia2p_conv3x3_form": (_I, [_P, C.POINTER(ConvFormC)]),
     "ia2p_debug_set_gemm_splitk": (None, [_I]),
     "ia2p_conv3x3": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "ia2p_conv3x3_splitk": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -1,6 +1,7 @@
 // The context-less C ABI (include/ia2p.h, ia2p_debug.h): the sampler updates and one entry point per operator -- argument checks, a launch descriptor from launch_args.h,
 // the launcher. The surface the per-operator GPU tests go through; needs engine_rt.hip (error state, zero page, plan helpers), nothing of any executor.
 #include "engine_rt.h"
+#include "gemm_tile.h"      // ia2p_pack_rowmap: ia2p_gemm_form refuses a row map by the launcher's own rule
 
 extern "C" {
 
@@ -303,6 +304,61 @@ ia2p_status ia2p_conv3x3_splitk(void* stream, const void* x, const void* Wp, con
   if (splitk > 1) { a.splitk = splitk; a.partial = partial; }
   hipError_t e = ia2p_launch_gemm(a, true, (hipStream_t)stream, nullptr);
   RET_HIP(e, "conv3x3_splitk");
+}
+// ---- the GEMM and the 3x3 convolution with every option an executor sets on its own descriptor (CLIP / ViT / SAM / prior: activation on a folded LayerNorm; VAE: epilogue
+//      scales, operand strides, pad_lo = 0; context K/V projection: row map, column offset): gemm_desc / conv3_desc plus the fields a site writes itself, then the
+//      launcher. Every refusal comes before any launch: what the kernels assume (16-byte operand rows, 8-byte epilogue pieces) the launcher does not all check.
+static bool al_(const void* q, uintptr_t a) { return (((uintptr_t)q) & (a - 1)) == 0; }
+ia2p_status ia2p_gemm_form(void* stream, const struct ia2p_gemm_form* d) {
+  if (d && d->stats_slots) *d->stats_slots = 0;
+  if (!d || !d->A || !d->W || !d->C || (d->splitk > 1 && !d->partial)) return fail(nullptr, IA2P_ERR_INVALID, "gemm_form: null argument (partial is needed for splitk > 1)");
+  if (d->M < 1 || d->N < 4 || d->N % 4 || d->K < 64 || d->K % 64) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_form: M=%d (>= 1) N=%d (multiple of 4) K=%d (multiple of 64)", d->M, d->N, d->K);
+  if (d->lda < d->K || d->ldw < d->K || d->ldc < d->N || (d->residual && d->ldr < d->N) || (d->rowvec && (d->rowvec_ld < d->N || d->rows_per_batch < 1)))
+    return fail(nullptr, IA2P_ERR_SHAPE, "gemm_form: lda=%d ldw=%d (>= K=%d) ldc=%d ldr=%d rowvec_ld=%d (>= N=%d) rows_per_batch=%d (>= 1)", d->lda, d->ldw, d->K, d->ldc, d->ldr, d->rowvec_ld, d->N, d->rows_per_batch);
+  if (d->act < 0 || d->act > 3) return fail(nullptr, IA2P_ERR_INVALID, "gemm_form: act=%d (0 none, 1 GELU erf, 2 quick-GELU, 3 GELU tanh; the per-image scale is ia2p_gemm_rowscale)", d->act);
+  if (!std::isfinite(d->acc_scale) || !std::isfinite(d->bias_scale)) return fail(nullptr, IA2P_ERR_INVALID, "gemm_form: acc_scale / bias_scale must be finite (0: 1)");
+  // operand rows are staged in 16-byte pieces; the epilogue's narrowest accesses are 8 bytes (4 columns), the folded-LayerNorm constants and the slabs 16
+  if (d->lda % 8 || d->ldw % 8 || !al_(d->A, 16) || !al_(d->W, 16)) return fail(nullptr, IA2P_ERR_INVALID, "gemm_form: A and W must be 16-byte aligned with lda=%d ldw=%d multiples of 8", d->lda, d->ldw);
+  if (d->ldc % 4 || !al_(d->C, 8) || (d->bias && !al_(d->bias, 8)) || (d->residual && (d->ldr % 4 || !al_(d->residual, 8))) || (d->rowvec && (d->rowvec_ld % 4 || !al_(d->rowvec, 8))))
+    return fail(nullptr, IA2P_ERR_INVALID, "gemm_form: C, bias, residual and rowvec must be 8-byte aligned with ldc=%d ldr=%d rowvec_ld=%d multiples of 4", d->ldc, d->ldr, d->rowvec_ld);
+  if (!ln_fold_ok(d->ln)) return fail(nullptr, IA2P_ERR_INVALID, "gemm_form: incomplete ia2p_ln_fold");
+  if (d->ln && (!al_(d->ln->stats, 8) || !al_(d->ln->colsum, 16) || !al_(d->ln->fbias, 16))) return fail(nullptr, IA2P_ERR_INVALID, "gemm_form: ln->stats must be 8-byte, ln->colsum and ln->fbias 16-byte aligned");
+  if ((d->stats_out && !al_(d->stats_out, 8)) || (d->splitk > 1 && !al_(d->partial, 16))) return fail(nullptr, IA2P_ERR_INVALID, "gemm_form: stats_out must be 8-byte, partial 16-byte aligned");
+  if (d->splitk < 0 || d->splitk > d->K / 64 || d->splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_form: splitk=%d (0 .. min(K / 64, 255))", d->splitk);
+  int rowmap = 0;
+  if (d->bstride < 0 || !ia2p_pack_rowmap(d->rpb, d->roff, &rowmap) || (!d->rpb && (d->bstride || d->roff)))
+    return fail(nullptr, IA2P_ERR_SHAPE, "gemm_form: row map rpb=%d bstride=%d roff=%d (rpb and roff in 0 .. 65535, bstride >= 0; rpb == 0 is the identity and takes neither)", d->rpb, d->bstride, d->roff);
+  const size_t a_rows = d->rpb ? ((size_t)d->M / d->rpb + 1) * (size_t)d->bstride + d->roff + d->rpb : (size_t)d->M;
+  if (!ia2p_fits_buffer(a_rows, d->lda) || !ia2p_fits_buffer(d->N, d->ldw)) return fail(nullptr, IA2P_ERR_SHAPE, "gemm_form: an operand of 2 GiB or more (%zu rows of lda=%d, N=%d rows of ldw=%d)", a_rows, d->lda, d->N, d->ldw);
+  GemmArgs a = gemm_desc(zero_page(), (const half_t*)d->A, d->lda, (const half_t*)d->W, d->ldw, (const half_t*)d->bias, (const half_t*)d->residual, d->residual ? d->ldr : 0, (half_t*)d->C, d->ldc,
+                         d->M, d->N, d->K, 0, d->rpb, d->bstride, d->roff, d->act);
+  a.acc_scale = d->acc_scale == 0.f ? 1.f : d->acc_scale; a.bias_scale = d->bias_scale == 0.f ? 1.f : d->bias_scale;
+  if (d->rowvec) { a.rowvec = (const half_t*)d->rowvec; a.rowvec_ld = d->rowvec_ld; a.rows_per_batch = d->rows_per_batch; }
+  ln_attach(a, d->ln);
+  a.stats_out = d->stats_out;
+  if (d->splitk > 1) { a.splitk = d->splitk; a.partial = d->partial; }
+  int pick = 0, combined = 0;
+  hipError_t e = ia2p_launch_gemm(a, false, (hipStream_t)stream, &pick, &combined);
+  if (e == hipSuccess && d->stats_slots && d->stats_out && pick >= 0 && pick < IA2P_GEMM_NVARIANT) *d->stats_slots = (d->splitk > 1 && !combined) ? 1 : (d->N + IA2P_GEMM_TILES[pick].bn - 1) / IA2P_GEMM_TILES[pick].bn;
+  RET_HIP(e, "gemm_form");
+}
+ia2p_status ia2p_conv3x3_form(void* stream, const ia2p_conv_form* d) {
+  if (!d || !d->x || !d->Wp || !d->y || (d->splitk > 1 && !d->partial)) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_form: null argument (partial is needed for splitk > 1)");
+  if (d->B < 1 || d->Hs < 1 || d->Ws < 1 || d->Cin < 64 || d->Cin % 64 || d->Co < 4 || d->Co % 4 || (d->stride != 1 && d->stride != 2) || (d->up != 0 && d->up != 1) || (d->pad_lo != 0 && d->pad_lo != 1))
+    return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_form: B=%d Hs=%d Ws=%d Cin=%d (mult of 64) Co=%d (mult of 4) stride=%d (1 | 2) up=%d pad_lo=%d (0 | 1)", d->B, d->Hs, d->Ws, d->Cin, d->Co, d->stride, d->up, d->pad_lo);
+  if (((d->Hs << d->up) + d->pad_lo + 1 < 3) || ((d->Ws << d->up) + d->pad_lo + 1 < 3)) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_form: a %d x %d image with pad_lo=%d has no output pixel", d->Hs, d->Ws, d->pad_lo);
+  if (d->splitk < 0 || d->splitk > 9 * d->Cin / 64 || d->splitk > 255) return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_form: splitk=%d (0 .. min(9 Cin / 64, 255))", d->splitk);
+  if (!std::isfinite(d->acc_scale) || !std::isfinite(d->bias_scale)) return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_form: acc_scale / bias_scale must be finite (0: 1)");
+  if (!al_(d->x, 16) || !al_(d->Wp, 16) || !al_(d->y, 8) || (d->bias && !al_(d->bias, 8)) || (d->rowvec && !al_(d->rowvec, 8)) || (d->residual && !al_(d->residual, 8)) || (d->splitk > 1 && !al_(d->partial, 16)))
+    return fail(nullptr, IA2P_ERR_INVALID, "conv3x3_form: x, Wp and partial must be 16-byte, y, bias, rowvec and residual 8-byte aligned");
+  GemmArgs a = conv3_desc(zero_page(), (const half_t*)d->x, d->B, d->Hs, d->Ws, d->Cin, (const half_t*)d->Wp, (const half_t*)d->bias, d->Co, d->stride, d->up, d->pad_lo, (const half_t*)d->rowvec, d->Co,
+                          (const half_t*)d->residual, (half_t*)d->y);
+  if ((int64_t)d->B * a.Ho * a.Wo > INT32_MAX || !ia2p_fits_buffer((size_t)d->B * d->Hs * d->Ws, d->Cin) || !ia2p_fits_buffer(d->Co, a.K) || !ia2p_fits_buffer((size_t)d->B * a.Ho * a.Wo, d->Co))
+    return fail(nullptr, IA2P_ERR_SHAPE, "conv3x3_form: an operand of 2 GiB or more");
+  a.acc_scale = d->acc_scale == 0.f ? 1.f : d->acc_scale; a.bias_scale = d->bias_scale == 0.f ? 1.f : d->bias_scale;
+  if (d->splitk > 1) { a.splitk = d->splitk; a.partial = d->partial; }
+  hipError_t e = ia2p_launch_gemm(a, true, (hipStream_t)stream, nullptr);
+  RET_HIP(e, "conv3x3_form");
 }
 // ---- GroupNorm from producer-side column sums (round 5; csrc/gn_fold.h): the operators of the fused path, one by one -----------------------------------------------
 // canonical statistics of a tensor x [M, C]: out[(slot * C + c) * 2 + {0, 1}] = {sum, sum of squares} (fp64) over the `rows` rows of slot `slot` (what a GEMM / conv epilogue
